@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mbp/s predicted at window=200 stride=50, 5 classes (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mbp M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mbp M] [--dump-outputs DIR]
 
 Workload: one synthetic chromosome of M Mbp per GPU, default 250 (BASELINE configs[2], the size the north-star target is
 quoted on; `--mbp 50` = configs[1]).  A "step" is one pass of the whole hot path over it -- class-index encode -> GRU +
@@ -27,6 +27,11 @@ Prints ONE JSON line (rank 0):
                         chunk table from per-rank host scans, records shared out by byte length, rank-local upload + ingest,
                         RCCL gather of the rows, rank 0 writes the TSV), with the bytes every rank uploaded
 (stages, e2e, accuracy and fast_mode at N = 1 only.)
+
+--dump-outputs DIR (rank 0): the segment records the LAST timed step returned (every rank's, after the gather), one float64
+file per field: DIR/segments_{start,end,label,contig}.npy, in record order.  Above 64 MB in all, a fixed seeded sample of
+the rows (in record order) is written instead, with its row numbers in DIR/segments_row.npy.  The input is the same on every
+run with the same arguments (seeded synthetic chromosome, stored or seeded weights), so two builds compare row for row.
 """
 import argparse
 import json
@@ -61,7 +66,36 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--master-port", type=int, default=29533, help="rendezvous port when bench.py starts the ranks itself")
     ap.add_argument("--no-sharded-file", action="store_true", help="N > 1: skip the sharded command-line leg")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the segment records of the last timed step to DIR/*.npy (float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000                 # all files of --dump-outputs together, .npy headers included
+
+
+def dump_outputs(out_dir: str, rows) -> dict:
+    """The timed path's result as float64 .npy files (int64 positions < 2^53 are exact in float64)."""
+    import numpy as np
+    fields = rows.dtype.names
+    n = rows.shape[0]
+    keep = None
+    if n * len(fields) * 8 + 4096 > DUMP_LIMIT_BYTES:
+        cap = (DUMP_LIMIT_BYTES - 4096) // ((len(fields) + 1) * 8)
+        keep = np.sort(np.random.default_rng(20240).choice(n, cap, replace=False))
+        rows = rows[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name in fields:
+        files[f"segments_{name}"] = rows[name].astype(np.float64)
+    if keep is not None:
+        files["segments_row"] = keep.astype(np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "rows": int(n), "rows_written": int(rows.shape[0]), "files": sorted(f + ".npy" for f in files)}
 
 
 def spawn_ranks(args) -> int:
@@ -293,11 +327,12 @@ def main():
     fence()
     check(L.dgrp_kernel_timer_enable(1), "dgrp_kernel_timer_enable")      # HIP events around the recurrent kernel, on its stream
     t0 = time.perf_counter()
-    nrows = 0
+    last_rows = None
     for _ in range(args.steps):
-        nrows = len(step())
+        last_rows = step()
     fence()
     dt = dt_local = time.perf_counter() - t0
+    nrows = len(last_rows)
     kern_ms, kern_launches, kern_windows = kernel_timer_read()
     check(L.dgrp_kernel_timer_enable(0), "dgrp_kernel_timer_enable")
     if world > 1:
@@ -455,6 +490,8 @@ def main():
             out["distinct_gpus"] = len({(r["host"], r["pci_bus_id"] or r["uuid"] or r["device"]) for r in ranks_block})
         if sharded is not None:
             out["sharded_file"] = sharded
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last_rows)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -30,18 +30,23 @@ def test_mss_raw(orc):
 
 
 def test_mss_segments_vs_compiled_reference_c(orc):
-    """orc_mss_find_all against the reference's mss.c (oracle/_ref) on random folds,
-    including scores/endpoints bit for bit."""
-    if orc.ref_c() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    rng = np.random.default_rng(5)
-    for n in (0, 1, 5, 100, 3000, 50000):
-        for trial in range(6):
-            S = rng.normal(-0.2, 2.0, size=n) if trial % 2 else rng.integers(-5, 4, size=n).astype(float)
-            for (msc, xd) in ((0.0, -1.0), (3.7, 2.5), (229.756, 2297.56), (1.0, 0.5)):
-                a = orc.mss_find_all(S, msc, xd)
-                b = orc.mss_find_all(S, msc, xd, use_ref=True)
-                assert a == b
+    """orc_mss_find_all against the reference's mss.c on random folds, including
+    scores/endpoints bit for bit: the reference's segments are stored as counts and
+    SHA-256 digests (oracle/make_golden_mss_segments.py, which also makes the folds);
+    where oracle/_ref is built, the live reference is held to the same digests."""
+    from oracle.make_golden_mss_segments import fold_digest, folds, segments_digest
+    g = golden("mss_segments.npz")
+    fs = folds()
+    assert len(fs) == g["sha"].shape[0]
+    for k, (n, trial, S) in enumerate(fs):
+        assert np.array_equal(fold_digest(S), g["folds"][k]), f"fold {k} (n={n}) is not the input the fixture was made from"
+        for p, (msc, xd) in enumerate(g["params"].tolist()):
+            impls = [False, True] if orc.ref_c() is not None else [False]
+            for use_ref in impls:
+                segs = orc.mss_find_all(S, msc, xd, use_ref=use_ref)
+                where = f"{'reference' if use_ref else 'oracle'}: fold {k} (n={n}, trial {trial}), params {msc}, {xd}"
+                assert len(segs) == g["nseg"][k, p], where
+                assert np.array_equal(segments_digest(segs), g["sha"][k, p]), where
 
 
 def test_probs_to_rows(orc):
