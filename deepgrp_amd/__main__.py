@@ -7,6 +7,8 @@ Differences, all additive:
   * `--xla` and `--threads` are accepted and ignored (there is no TensorFlow here);
   * under torchrun (WORLD_SIZE > 1) the records of all input files are sharded by contig over
     the GPUs and rank 0 writes the rows in input order;
+  * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
+    (deepgrp_amd/masking.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
 """
 from __future__ import annotations
@@ -48,6 +50,50 @@ def _predict(dnasequence: str, model, options, step_size: int, use_mss: bool) ->
     return labels.cpu().numpy().astype(np.int64), start_pos
 
 
+class _RowsByRecord:
+    """The rows of one input file in record order, `contig` = the record's ordinal in the file (masking.mask_fasta's input)."""
+
+    def __init__(self):
+        self.parts, self.records = [], 0
+
+    def add(self, rows, nrec: int) -> None:
+        """`nrec` records' rows: one record (contig ignored) or a batch (contig = index in the batch)."""
+        rows = np.array(rows, copy=True)
+        if nrec == 1:
+            rows["contig"] = self.records
+        else:
+            rows["contig"] += self.records
+        self.parts.append(rows)
+        self.records += nrec
+
+    def rows(self):
+        from .pipeline import SEGMENT_DTYPE
+        return np.concatenate(self.parts) if self.parts else np.zeros(0, SEGMENT_DTYPE)
+
+
+def _class_list(text: str) -> Tuple[int, ...]:
+    """--mask_classes: comma-separated labels."""
+    try:
+        out = tuple(int(x) for x in text.split(",") if x.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma-separated list of labels: {text!r}") from None
+    if not out:
+        raise argparse.ArgumentTypeError("no label given")
+    return out
+
+
+def _add_mask_options(parser, suppress: bool) -> None:
+    """The masking flags: on `predict` and, for the README form with the flags in front, on the main parser as well (the values
+    are only set where given, so neither parser's default hides the other's)."""
+    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
+    parser.add_argument("--mask_dir", type=str, default=d(None),
+                        help="(addition) also write a masked copy of every input FASTA file as DIR/<basename of the input>")
+    parser.add_argument("--mask", choices=("soft", "hard"), default=d("soft"),
+                        help="(addition) soft: predicted repeats lower case, the rest upper case; hard: predicted repeats 'N'")
+    parser.add_argument("--mask_classes", type=_class_list, default=d(None),
+                        help="(addition) comma-separated labels to mask, e.g. 1,3 (default: every label > 0)")
+
+
 class CommandLineParser:
     """Commandline parser (deepgrp/__main__.py:86-250)."""
 
@@ -71,6 +117,7 @@ class CommandLineParser:
         self.parser.add_argument("--threads", "-t", type=int, default=1, help="Accepted for compatibility (ignored)")
         self.parser.add_argument("--xla", action="store_true", help="Accepted for compatibility (ignored)")
         self.parser.add_argument("-v", "--verbose", action="count", default=0, help="Increase verbosity")
+        _add_mask_options(self.parser, suppress=True)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (not available in deepgrp_amd)")
         train.add_argument("parameter", type=str)
@@ -103,13 +150,14 @@ class CommandLineParser:
         predict.add_argument("--split_contigs", action="store_true",
                              help="multi-GPU only: spread the windows of EVERY record over all GPUs (for a few huge "
                                   "records) instead of sharding whole records")
+        _add_mask_options(predict, suppress=True)
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
         # README form `deepgrp <modelfile> <fastafile>`: insert the sub-command before the first positional
         if not any(a in ("predict", "train", "verify") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
-                           "--threads", "-t"}
+                           "--threads", "-t", "--mask_dir", "--mask", "--mask_classes"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -144,6 +192,7 @@ class CommandLineParser:
     @staticmethod
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
+        masks = CommandLineParser._mask_plan(args)              # refusals come before anything runs
         import torch
         import torch.distributed as dist
         from . import model as dgmodel
@@ -173,6 +222,8 @@ class CommandLineParser:
         model = dgmodel.load_model(args.model, custom_objects={"ReverseComplement": dgmodel.ReverseComplement})
         options.vecsize = model.input_shape[1]
         _LOG.info("Model loading finished successfully!")
+        if masks is not None:
+            CommandLineParser._check_mask_classes(args, model.output_shape[2])
         pipe = ContigPipeline(model, args.step_size, options.batch_size, options.min_mss_len, options.xdrop_len,
                               use_mss=not args.no_use_mss, precise=getattr(args, "precise", False),
                               fast=getattr(args, "fast", False))
@@ -222,6 +273,7 @@ class CommandLineParser:
                 for filename in args.FASTA:
                     _LOG.info("Processing %s", filename)
                     t_file, bases = time.perf_counter(), 0
+                    kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
                     if _LOG.isEnabledFor(logging.DEBUG):
                         # -vv: record by record through the staged form of the same path, a device sync and a clock around every
                         # stage (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
@@ -229,10 +281,19 @@ class CommandLineParser:
                             rows, n = CommandLineParser._predict_staged(pipe, header, rec)
                             bases += n
                             outstream.write(rows_text(filename, header, rows))
+                            if kept is not None:
+                                kept.add(rows, 1)
                     else:
                         for kind, key, rows in runner.results(CommandLineParser._counted(records_of(filename), lambda n: None)):
                             outstream.write(rows_text_batch(filename, key, rows) if kind == "batch" else rows_text(filename, key, rows))
+                            if kept is not None:
+                                kept.add(rows, len(key) if kind == "batch" else 1)
                         bases = CommandLineParser._last_count
+                    if kept is not None:
+                        outstream.flush()
+                        t_mask = time.perf_counter()
+                        CommandLineParser._write_mask(filename, masks[filename], kept.rows(), args)
+                        _LOG.debug("%s: masked copy %s in %.2f ms", filename, masks[filename], (time.perf_counter() - t_mask) * 1e3)
                     dt = time.perf_counter() - t_file
                     _LOG.info("%s: %d bases in %.3f s (%.1f Mbp/s; ingest, upload, forward, MSS, segments and TSV text)", filename, bases, dt,
                               bases / max(dt, 1e-9) / 1e6)
@@ -258,8 +319,24 @@ class CommandLineParser:
                     if rank == 0:
                         for i, (filename, header, _seq) in enumerate(records):
                             outstream.write(rows_text(filename, header, allrows[allrows["contig"] == i]))
+                    if masks is not None:
+                        # rank 0 holds every row: it writes the masked copies; the other ranks learn how that went
+                        from .distributed import raise_together
+                        err = None
+                        if rank == 0:
+                            try:
+                                outstream.flush()
+                                for filename in args.FASTA:
+                                    ids = [i for i, r in enumerate(records) if r[0] == filename]
+                                    i0, i1 = (ids[0], ids[-1] + 1) if ids else (0, 0)
+                                    rows = allrows[(allrows["contig"] >= i0) & (allrows["contig"] < i1)].copy()
+                                    rows["contig"] -= i0
+                                    CommandLineParser._write_mask(filename, masks[filename], rows, args)
+                            except Exception as e:          # noqa: BLE001 -- re-raised on every rank together
+                                err = e
+                        raise_together(err)
                 else:
-                    CommandLineParser._predict_sharded(args, runner, records_of, outstream)
+                    CommandLineParser._predict_sharded(args, runner, records_of, outstream, masks)
                 dist.barrier()
         finally:
             # rows already produced reach the file even when a later record raises (the reference leaves that to
@@ -323,7 +400,7 @@ class CommandLineParser:
         return rows, n
 
     @staticmethod
-    def _predict_sharded(args, runner, records_of, outstream) -> None:
+    def _predict_sharded(args, runner, records_of, outstream, masks=None) -> None:
         """Records sharded over the ranks (the reference's record loop, deepgrp/__main__.py:275-292, carries no state from one
         record to the next).  Ingest is rank-local: the chunk table of every FASTA file comes from host scans of 1/world of its
         bytes per rank, the chunks are shared out longest-first by byte length (runs of short records travel together), and a
@@ -386,6 +463,7 @@ class CommandLineParser:
             if r == rank:
                 gid[lid] = g
         local = np.concatenate(parts) if parts else np.zeros(0, SEGMENT_DTYPE)
+        local_ids = local["contig"].copy()
         local["contig"] = gid[local["contig"]]
         allrows = gather_records(local, torch.device("cuda", torch.cuda.current_device()))
         CommandLineParser.last_sharded = {"uploaded_bytes": fasta.UPLOAD_STATS["bytes"] - uploaded0, "records": len(entries),
@@ -402,8 +480,109 @@ class CommandLineParser:
                 rows = allrows[lo:hi].copy()
                 rows["contig"] -= g0
                 outstream.write(rows_text_batch(files[fi], [every[r][lid][1] for _k, r, lid in order[g0:g]], rows))
+        if masks is not None:
+            if rank == 0:
+                outstream.flush()
+            # each rank masks its own byte ranges of every file with its own rows (contig = ordinal of the record among the records
+            # of that file this rank ingested, in file order: the local ids of one file are consecutive), into one temporary file
+            # per input that rank 0 creates at full size and renames once every rank has written
+            file_of = np.array([key[0] for key, _h in entries], np.int64)
+            for f, fi in enumerate(sharded):
+                sel = file_of[local_ids] == fi
+                mine = local[sel].copy()
+                mine["contig"] = local_ids[sel] - int(np.searchsorted(file_of, fi))
+                spans = [(a, b) for ff, a, b in ranges[rank] if ff == f]
+                CommandLineParser._write_mask_sharded(files[fi], masks[files[fi]], mine, spans, args)
 
     last_sharded: dict = {}
+
+    @staticmethod
+    def _mask_plan(args):
+        """--mask_dir: {input file: masked copy}, or None without the flag.  Everything that can be refused without the model is
+        refused here, before any prediction."""
+        mdir = getattr(args, "mask_dir", None)
+        if mdir is None:
+            if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None:
+                sys.exit("--mask and --mask_classes need --mask_dir")
+            return None
+        plan, seen = {}, {}
+        for f in args.FASTA:
+            if f == "-":
+                sys.exit("--mask_dir: standard input cannot be masked (give a FASTA file)")
+            if f.endswith(".npz"):
+                sys.exit(f"--mask_dir: {f} is a one-hot .npz, not a FASTA file; it cannot be masked")
+            base = os.path.basename(f)
+            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
+                sys.exit(f"--mask_dir: {seen[base]} and {f} have the same file name; their masked copies would collide")
+            seen[base] = f
+            out = os.path.join(mdir, base)
+            if os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
+                sys.exit(f"--mask_dir: the masked copy {out} would overwrite the input {f}")
+            plan[f] = out
+        if len(plan) != len(args.FASTA):
+            sys.exit("--mask_dir: an input file is given twice")
+        os.makedirs(mdir, exist_ok=True)
+        return plan
+
+    @staticmethod
+    def _check_mask_classes(args, classes: int) -> None:
+        bad = [c for c in (getattr(args, "mask_classes", None) or ()) if not 0 < c < classes]
+        if bad:
+            sys.exit(f"--mask_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
+
+    @staticmethod
+    def _write_mask(filename: str, final: str, rows, args) -> None:
+        """The masked copy of one file: written to a temporary file next to `final`, renamed on success, removed on failure."""
+        import tempfile
+
+        from .masking import mask_fasta
+        fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
+        os.close(fd)
+        try:
+            mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None))
+            os.replace(tmp, final)
+        except BaseException:
+            os.remove(tmp)
+            raise
+
+    @staticmethod
+    def _write_mask_sharded(filename: str, final: str, rows, spans, args) -> None:
+        """_write_mask over the ranks: rank 0 creates the temporary file at the input's size, every rank writes its byte ranges,
+        rank 0 renames it (or removes it when any rank failed)."""
+        import tempfile
+
+        import torch.distributed as dist
+
+        from .distributed import raise_together
+        from .masking import mask_fasta
+        rank = dist.get_rank()
+        name = [None]
+        err = None
+        if rank == 0:
+            try:
+                fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
+                os.ftruncate(fd, os.path.getsize(filename))
+                os.close(fd)
+                name = [tmp]
+            except Exception as e:              # noqa: BLE001 -- re-raised on every rank together
+                err = e
+        raise_together(err)
+        dist.broadcast_object_list(name, src=0)          # (after rank 0 made the file: the barrier in front of the writes)
+        tmp = name[0]
+        try:
+            if spans:
+                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft",
+                           classes=getattr(args, "mask_classes", None), ranges=spans)
+        except Exception as e:                  # noqa: BLE001
+            err = e
+        try:
+            raise_together(err)                 # every rank has written (or failed): the barrier behind the writes
+        except BaseException:
+            if rank == 0:
+                os.remove(tmp)
+            raise
+        if rank == 0:
+            os.replace(tmp, final)
 
     @staticmethod
     def verify(args: argparse.Namespace, options) -> None:

@@ -296,16 +296,12 @@ def ingest_ranges(path: Union[str, os.PathLike], ranges=None, group_bytes: int =
             yield from _ingest_range(L, dev, path, mm, a, b, group_bytes, group_records)
 
 
-def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int):
-    """ingest_ranges for one range [r0, r1) of the mapped file; offsets below are relative to r0 unless they say `abs`."""
+def _chunk_table(L, dev, path, mm, r0: int, r1: int):
+    """The chunk table of the range [r0, r1) of the mapped file, offsets relative to r0: (d_file = the range in HBM or None above
+    RESIDENT_BYTES, chunk starts + [size], end of each chunk's header line, start of each body, whether the chunk opens with '>')."""
     import numpy as np
-    import torch
-
-    from ._lib import check
-    from .pipeline import stream_ptr
 
     size = r1 - r0
-    loop = LineLoop()
     d_file = None
     if size <= RESIDENT_BYTES:
         # the whole range goes up once (pinned slabs, the read of slab k+1 overlaps the DMA of slab k) and the chunk
@@ -332,8 +328,31 @@ def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
     head_end_np = np.minimum(first_lf, starts_np[1:])                 # no line feed inside the chunk: header runs to its end
     body0_np = np.where(first_lf < starts_np[1:], first_lf + 1, starts_np[1:])
     del first_lf
-    starts = starts_np.tolist()
-    head_ends, body0_all, gt_all = head_end_np.tolist(), body0_np.tolist(), gt_np.tolist()
+    return d_file, starts_np.tolist(), head_end_np.tolist(), body0_np.tolist(), gt_np.tolist()
+
+
+class ChunkGroup:
+    """One ingest group of chunks [c0, c1) of a range (offsets relative to the range start): `cand[i]` = the chunk's header line
+    qualifies for the device path, `info[i]` = dgrp_fasta_encode_batch's four values of its body (info[i][0] == 1: plain), `d_idx`
+    the class indices (group offsets), `d_raw` the group's file bytes in HBM when the caller asked to keep them (else None)."""
+
+    __slots__ = ("c0", "c1", "starts", "head_ends", "body0s", "cand", "info", "d_idx", "d_raw")
+
+    def plain(self, i: int) -> bool:
+        """Chunk c0 + i goes the device path: a header line that qualifies and a plain body."""
+        return bool(self.cand[i] and self.info[i][0] == 1)
+
+
+def _chunk_groups(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int, keep_raw: bool = False):
+    """The chunks of [r0, r1) in groups (up to `group_bytes` of file or `group_records` chunks): per group one upload (or a view of
+    the resident range) and one dgrp_fasta_encode_batch over the bodies whose header line qualifies.  Yields ChunkGroup."""
+    import numpy as np
+    import torch
+
+    from ._lib import check
+    from .pipeline import stream_ptr
+
+    d_file, starts, head_ends, body0_all, gt_all = _chunk_table(L, dev, path, mm, r0, r1)
     nchunks = len(starts) - 1
     c0 = 0
     while c0 < nchunks:
@@ -350,8 +369,8 @@ def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
             cand.append(gt_all[c] and head.isascii() and b"\r" not in head[:-1])
         g0, g1 = starts[c0], starts[c1]
         infos = np.zeros((c1 - c0, 4), np.int64)
-        d_idx = None
-        if any(cand):
+        d_idx = d_raw = None
+        if any(cand) or keep_raw:
             # resident range: a view; else the group's bytes go up now (numpy view of the mmap: no host copy)
             if d_file is not None:
                 d_raw = d_file[g0:g1]
@@ -359,6 +378,7 @@ def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
                 UPLOAD_STATS["bytes"] += g1 - g0
                 UPLOAD_STATS["uploads"] += 1
                 d_raw = torch.from_numpy(np.frombuffer(mm, dtype=np.uint8, count=g1 - g0, offset=r0 + g0)).to(dev)
+        if any(cand):
             d_idx = torch.empty(g1 - g0, dtype=torch.uint8, device=dev)
             off = np.array([body0s[i] - g0 for i in range(c1 - c0)], np.int64)
             ln = np.array([(starts[c0 + i + 1] - body0s[i]) if cand[i] else 0 for i in range(c1 - c0)], np.int64)
@@ -366,22 +386,36 @@ def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
             work = torch.empty(wb, dtype=torch.uint8, device=dev)
             check(L.dgrp_fasta_encode_batch(d_raw.data_ptr(), c1 - c0, off.ctypes.data, ln.ctypes.data, d_idx.data_ptr(),
                                             infos.ctypes.data, work.data_ptr(), wb, stream_ptr()), "dgrp_fasta_encode_batch")
-            del d_raw, work
-        info_rows = infos.tolist()                   # plain ints: numpy scalar indexing per record is slow
-        for i, c in enumerate(range(c0, c1)):
+            del work
+        if not keep_raw:
+            d_raw = None
+        grp = ChunkGroup()
+        grp.c0, grp.c1, grp.starts, grp.head_ends, grp.body0s, grp.cand = c0, c1, starts, head_ends, body0s, cand
+        grp.info, grp.d_idx, grp.d_raw = infos.tolist(), d_idx, d_raw          # plain ints: numpy scalar indexing per record is slow
+        del d_idx, d_raw
+        yield grp
+        del grp
+        c0 = c1
+
+
+def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int):
+    """ingest_ranges for one range [r0, r1) of the mapped file; offsets below are relative to r0 unless they say `abs`."""
+    loop = LineLoop()
+    for grp in _chunk_groups(L, dev, path, mm, r0, r1, group_bytes, group_records):
+        starts, head_ends, g0 = grp.starts, grp.head_ends, grp.starts[grp.c0]
+        for i, c in enumerate(range(grp.c0, grp.c1)):
             a, b = r0 + starts[c], r0 + starts[c + 1]                  # abs
-            if cand[i] and info_rows[i][0] == 1:
+            if grp.plain(i):
                 for header, seq in loop.flush():
                     yield loop.last_key, header, seq
                 header = mm[a:r0 + head_ends[c]].decode("ascii").strip()[1:]
                 if header:
-                    st, kept = info_rows[i][2], info_rows[i][3]
-                    lo = body0s[i] - g0 + st
-                    yield (a, 0), header, DeviceRecord(st, None, kept, d_idx, lo)
+                    st, kept = grp.info[i][2], grp.info[i][3]
+                    lo = grp.body0s[i] - g0 + st
+                    yield (a, 0), header, DeviceRecord(st, None, kept, grp.d_idx, lo)
                 continue
             for header, seq in loop.feed(_text_lines(mm[a:b]), tag=a):
                 yield loop.last_key, header, seq
-        del d_idx
-        c0 = c1
+        del grp
     for header, seq in loop.flush():
         yield loop.last_key, header, seq

@@ -1,0 +1,223 @@
+"""Masked FASTA output (`predict --mask_dir`): a copy of the input file whose sequence bytes state the prediction -- soft (inside a
+masked TSV row lower case, every other letter upper case, as RepeatMasker -xsmall) or hard (inside a row 'N').  The copy has the
+input's length; headers, line ends, text before the first header and records without a header are copied byte for byte.
+
+A record's sequence position p is the p-th character of the sequence the reference's line loop builds (deepgrp/__main__.py:20-43),
+the coordinate of the TSV rows.  Plain records (fasta.py's device path: LF / CRLF line ends only) are rewritten on the GPU
+(dgrp_fasta_mask_batch, in place on the uploaded bytes); the others through `sequence_byte_offsets`, the byte-level mirror of
+fasta.LineLoop."""
+from __future__ import annotations
+
+import logging
+import mmap
+import os
+import re
+from typing import Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+_LOG = logging.getLogger(__name__)
+
+MODES = {"soft": 0, "hard": 1}
+_STRIP = b" \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"            # what str.strip() removes from an ASCII line
+_LINE = re.compile(rb"[^\r\n]*(?:\r\n|\r|\n)?")          # one line of text mode's universal newlines, terminator included
+_IS_LETTER = np.zeros(256, bool)
+_IS_LETTER[65:91] = _IS_LETTER[97:123] = True
+
+
+def class_bits(classes: Optional[Iterable[int]]) -> int:
+    """The class mask of dgrp_fasta_mask_batch: bit c set for every label c to mask; None = every label > 0."""
+    if classes is None:
+        return ((1 << 64) - 1) & ~1
+    bits = 0
+    for c in classes:
+        c = int(c)
+        if not 0 < c < 64:
+            raise ValueError(f"class {c} cannot be masked (labels 1..63)")
+        bits |= 1 << c
+    return bits
+
+
+def _text_encoding() -> str:
+    """The encoding `open(path, "r")` reads with (fasta._text_lines)."""
+    from .fasta import _text_lines
+    return _text_lines(b"").encoding
+
+
+def sequence_byte_offsets(chunk: bytes) -> List[Tuple[str, Optional[np.ndarray]]]:
+    """The records fasta.LineLoop yields from this piece of a file (a chunk: it starts at the file start or with a '>' line), in
+    order, as (header, offsets): `offsets` are the positions in `chunk` of the record's sequence characters in the reference's order,
+    so that bytes(chunk[offsets]).upper() is the sequence the loop builds -- or None when a sequence line of the record is not ASCII
+    (its characters are not bytes).  Lines as text mode splits them (LF, CRLF, lone CR), each stripped as str.strip() strips; a blank
+    line raises IndexError as the loop does."""
+    enc = None
+    out: List[Tuple[str, Optional[np.ndarray]]] = []
+    header, parts, ascii_ok = "", [], True
+
+    def close():
+        if header:
+            out.append((header, (np.concatenate(parts) if parts else np.zeros(0, np.int64)) if ascii_ok else None))
+
+    pos, n = 0, len(chunk)
+    while pos < n:
+        m = _LINE.match(chunk, pos)
+        line_end = m.end()
+        content = chunk[pos:line_end].rstrip(b"\r\n")
+        start = pos
+        pos = line_end
+        if content.isascii():
+            body = content.strip(_STRIP)
+            if not body:
+                raise IndexError("string index out of range")          # the reference loop's blank line
+            lead = len(content) - len(content.lstrip(_STRIP))
+            if body[0] == 62:
+                close()
+                header, parts, ascii_ok = body[1:].decode("ascii"), [], True
+            else:
+                parts.append(np.arange(start + lead, start + lead + len(body), dtype=np.int64))
+        else:
+            enc = enc or _text_encoding()
+            text = content.decode(enc, "surrogateescape").strip()
+            if not text:
+                raise IndexError("string index out of range")
+            if text[0] == ">":
+                close()
+                header, parts, ascii_ok = text[1:], [], True
+            else:
+                ascii_ok = False
+    close()
+    return out
+
+
+def _paint(n: int, rows: np.ndarray, bits: int, what: str) -> np.ndarray:
+    """Per sequence position of a record of n characters: inside a row whose label is in the mask."""
+    edge = np.zeros(n + 1, np.int32)
+    if rows.size:
+        st, en = rows["start"].astype(np.int64), rows["end"].astype(np.int64)
+        if (st < 0).any() or (en <= st).any() or (en > n).any():
+            raise ValueError(f"{what}: a row lies outside its sequence of {n} characters")
+        lab = rows["label"].astype(np.int64)
+        ok = (lab >= 0) & (lab < 64)
+        sel = ok & ((np.uint64(bits) >> np.where(ok, lab, 0).astype(np.uint64)) & np.uint64(1)).astype(bool)
+        np.add.at(edge, st[sel], 1)
+        np.add.at(edge, en[sel], -1)
+    return np.cumsum(edge[:n]) > 0
+
+
+def _apply_host(buf: np.ndarray, pos: np.ndarray, inside: np.ndarray, mode: int) -> None:
+    """Mask the bytes buf[pos] (inside[i] for buf[pos[i]]) as dgrp_fasta_mask_batch does."""
+    b = buf[pos]
+    if mode == 1:
+        b = np.where(inside, np.uint8(78), b)
+    else:
+        letter = _IS_LETTER[b]
+        b = np.where(letter, np.where(inside, b | 0x20, b & 0xDF), b).astype(np.uint8)
+    buf[pos] = b
+
+
+def _pwrite_all(fd: int, data, offset: int) -> None:
+    view = memoryview(data).cast("B")
+    done = 0
+    while done < len(view):
+        done += os.pwrite(fd, view[done:], offset + done)
+
+
+def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional[Iterable[int]] = None,
+               ranges: Optional[Sequence[Tuple[int, int]]] = None, group_bytes: int = 256 << 20, group_records: int = 4096) -> int:
+    """Write the masked copy of `fasta_path`.  `rows` (pipeline.SEGMENT_DTYPE): the TSV rows, `contig` = the record's ordinal among
+    the records the reference loop yields from the processed bytes, in file order.  `classes`: the labels to mask (None: every label
+    > 0).  `ranges=None`: the whole file goes to `out_path` (created or truncated to the input's size); else only those byte ranges
+    (whole chunks, as fasta.ingest_ranges takes them) are processed and written into the existing `out_path`, which must already
+    have the input's size -- ranks of a sharded run each write their own share.  Works in groups as the ingest does: one upload,
+    dgrp_fasta_encode_batch (which tells the plain records), dgrp_fasta_mask_batch in place, one read-back, one write.  Returns the
+    number of records seen."""
+    import torch
+
+    from ._lib import check, lib
+    from .fasta import _chunk_groups
+    from .pipeline import SEGMENT_DTYPE, require_gpu, stream_ptr
+
+    if mode not in MODES:
+        raise ValueError(f"mask mode must be one of {sorted(MODES)}, not {mode!r}")
+    mcode, bits = MODES[mode], class_bits(classes)
+    rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+    rows = rows[np.lexsort((rows["start"], rows["contig"]))] if rows.size else rows
+    contig = rows["contig"]
+    size = os.path.getsize(fasta_path)
+    if ranges is None:
+        with open(out_path, "wb") as fh:
+            fh.truncate(size)
+        ranges = [(0, size)] if size else []
+    elif os.path.getsize(out_path) != size:
+        raise ValueError(f"{out_path}: {os.path.getsize(out_path)} bytes, the input has {size}")
+    if size == 0:
+        return 0
+    L = lib()
+    dev = require_gpu()
+
+    def rows_of(k):
+        lo, hi = np.searchsorted(contig, [k, k + 1])
+        return lo, hi
+
+    ordinal = 0
+    fd = os.open(out_path, os.O_WRONLY)
+    try:
+        with open(fasta_path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_COPY) as mm:
+            for r0, r1 in ranges:
+                if not (0 <= r0 < r1 <= size) or (r0 and not (mm[r0] == 62 and mm[r0 - 1] == 10)):
+                    raise ValueError(f"{fasta_path}: [{r0}, {r1}) is not a range of whole chunks")
+                for grp in _chunk_groups(L, dev, fasta_path, mm, r0, r1, group_bytes, group_records, keep_raw=True):
+                    g0, g1 = grp.starts[grp.c0], grp.starts[grp.c1]
+                    dev_recs, host_chunks = [], []              # (i, ordinal); (chunk start, chunk end, [(header, offsets, ordinal)])
+                    for i, c in enumerate(range(grp.c0, grp.c1)):
+                        a, b = grp.starts[c], grp.starts[c + 1]
+                        if grp.plain(i):
+                            if mm[r0 + a:r0 + grp.head_ends[c]].decode("ascii").strip()[1:]:
+                                dev_recs.append((i, ordinal))
+                                ordinal += 1
+                            continue
+                        recs = []
+                        for header, offs in sequence_byte_offsets(mm[r0 + a:r0 + b]):
+                            recs.append((header, offs, ordinal))
+                            ordinal += 1
+                        if recs:
+                            host_chunks.append((a, recs))
+                    d_raw = grp.d_raw
+                    if dev_recs:
+                        # d_raw may be a view of the resident range at any offset: the kernel takes the 16-byte aligned address below
+                        # it (inside the same allocation) and offsets that include the difference
+                        ptr = d_raw.data_ptr()
+                        shift = ptr & 15
+                        h_off = np.array([grp.body0s[i] - g0 + shift for i, _k in dev_recs], np.int64)
+                        h_len = np.array([grp.starts[grp.c0 + i + 1] - grp.body0s[i] for i, _k in dev_recs], np.int64)
+                        spans = [rows_of(k) for _i, k in dev_recs]
+                        h_row_off = np.zeros(len(dev_recs) + 1, np.int64)
+                        np.cumsum([hi - lo for lo, hi in spans], out=h_row_off[1:])
+                        sel = np.concatenate([rows[lo:hi] for lo, hi in spans]) if h_row_off[-1] else np.zeros(0, SEGMENT_DTYPE)
+                        d_rows = torch.from_numpy(sel.view(np.uint8)).to(dev) if sel.size else None
+                        wb = L.dgrp_fasta_mask_workspace_bytes(len(dev_recs), int(h_len.sum()), int(h_row_off[-1]))
+                        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+                        check(L.dgrp_fasta_mask_batch(ptr - shift, len(dev_recs), h_off.ctypes.data, h_len.ctypes.data,
+                                                      d_rows.data_ptr() if d_rows is not None else None, h_row_off.ctypes.data,
+                                                      mcode, bits, ptr - shift, work.data_ptr(), wb, stream_ptr()),
+                              f"dgrp_fasta_mask_batch ({fasta_path})")
+                        host = d_raw.cpu().numpy()
+                        del work, d_rows
+                    else:
+                        host = np.frombuffer(mm, dtype=np.uint8, count=g1 - g0, offset=r0 + g0).copy()
+                    del d_raw, grp
+                    for a, recs in host_chunks:
+                        for header, offs, k in recs:
+                            lo, hi = rows_of(k)
+                            if offs is None:
+                                _LOG.warning("%s: record %r has sequence lines that are not ASCII; copied unmasked", fasta_path, header)
+                                continue
+                            inside = _paint(offs.size, rows[lo:hi], bits, f"{fasta_path}: record {header!r}")
+                            _apply_host(host, offs + (a - g0), inside, mcode)
+                    _pwrite_all(fd, host, r0 + g0)
+                    del host
+    finally:
+        os.close(fd)
+    if contig.size and int(contig[-1]) >= ordinal:
+        raise ValueError(f"{fasta_path}: rows name record {int(contig[-1])}, but only {ordinal} records were read")
+    return ordinal

@@ -95,6 +95,20 @@ int64_t dgrp_fasta_chunks_workspace_bytes(int64_t cap);
 int dgrp_fasta_chunks(const uint8_t *d_raw, int64_t nbytes, int64_t cap, int64_t *h_start, int64_t *h_first_lf,
                       int64_t *n_chunks, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- Masked FASTA (predict --mask_dir; an addition, no counterpart in the reference): the sequence bytes of nrec plain record
+ * bodies of ONE device buffer rewritten after the TSV rows of their records.  Record r = bytes [h_off[r], h_off[r] + h_len[r]) of
+ * d_raw, a body that dgrp_fasta_encode_batch calls plain (LF or CRLF line ends only); its sequence position p is the p-th byte that
+ * is neither CR nor LF, the coordinate of the TSV rows.  Its rows are d_rows[h_row_off[r] .. h_row_off[r+1]) (device), ascending
+ * and disjoint, 0 <= start < end <= its sequence length (else DGRP_EINVAL before anything is written).  A position is inside when a
+ * row with (class_mask >> label) & 1 covers it.  mode 0 (soft): ASCII letters inside -> lower case, other letters -> upper case;
+ * mode 1 (hard): inside -> 'N', other bytes unchanged.  Line ends are copied.  The bytes land at the same offsets of d_out (may be
+ * d_raw); nothing else of d_out is written.  d_raw and d_out 16-byte aligned.  Stream-ordered after the row check (which
+ * synchronises once). */
+int64_t dgrp_fasta_mask_workspace_bytes(int64_t nrec, int64_t total_bytes, int64_t nrows);
+int dgrp_fasta_mask_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                          const dgrp_segment *d_rows, const int64_t *h_row_off, int mode, uint64_t class_mask,
+                          uint8_t *d_out, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3: deepgrp.prediction.fetch_validation_batch (deepgrp/prediction.py:14-37)
  * Number of windows len(range(0, n - T, s)). */
 int64_t dgrp_window_count(int64_t n, int64_t T, int64_t s);
