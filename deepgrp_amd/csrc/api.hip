@@ -686,7 +686,7 @@ static int forward_common(const dgrp_model *m, const uint8_t *d_idx, int64_t n, 
         place = dgrp_make_placement(total, batch);
     }
     if (m->ref_only) return forward_ref(m, d_idx, n, s, place, w0, nw, merge, d_out, d_work, work_bytes, stream);
-    if (!m->attention) return dgrp_gru_launch(m, d_idx, n, s, place, w0, nw, merge ? 0 : 1, d_out, nullptr, stream);
+    if (!m->attention) return dgrp_gru_launch(m, dgrp_gru_plan_for(m, merge ? 0 : 1, s), d_idx, n, place, w0, nw, d_out, nullptr, stream);
     if (work_bytes < dgrp_forward_workspace_bytes(m, nw) || !d_work) {
         dgrp_set_error("dgrp_forward: attention model needs %lld bytes of workspace for %lld windows",
                        (long long)dgrp_forward_workspace_bytes(m, nw), (long long)nw);
@@ -694,9 +694,10 @@ static int forward_common(const dgrp_model *m, const uint8_t *d_idx, int64_t n, 
     }
     void *avg = d_work;
     float *pl = (float *)((char *)d_work + dgrp_align_up(nw * m->T * (int64_t)m->UP * 4, 256));
-    int rc = dgrp_gru_launch(m, d_idx, n, s, place, w0, nw, 2, pl, avg, stream);
+    const dgrp_gru_plan pre = dgrp_gru_plan_for(m, 2, s);
+    int rc = dgrp_gru_launch(m, pre, d_idx, n, place, w0, nw, pl, avg, stream);
     if (rc) return rc;
-    return dgrp_attention_launch(m, s, place, w0, nw, merge, n, avg, pl, d_out, stream);
+    return dgrp_attention_launch_recs(m, pre, place, w0, nw, merge, n, avg, pl, d_out, nullptr, 0, stream);
 }
 
 DGRP_EXPORT int dgrp_forward_windows(const dgrp_model *m, const uint8_t *d_idx, int64_t n, int64_t s, int64_t w0,
@@ -1033,15 +1034,17 @@ DGRP_EXPORT int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, in
     DGRP_HIP(hipMemsetAsync(out, 0, (size_t)rows * m->C * 4, stream));
     int rc;
     if (!m->attention) {
-        rc = dgrp_gru_launch_batch(m, d_idx, s, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec], 0, out, nullptr, stream);
+        rc = dgrp_gru_launch_batch(m, dgrp_gru_plan_for(m, 0, s), d_idx, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec],
+                                   out, nullptr, stream);
         if (rc) return rc;
     } else {
         // GRU pre-pass for all windows (avg[t] and the avg half of the logits, windows numbered through the batch),
         // then the attention kernel with the same record table for placement
-        rc = dgrp_gru_launch_batch(m, d_idx, s, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec], 2,
-                                   (float *)(w + l.pl), w + l.avg, stream);
+        const dgrp_gru_plan pre = dgrp_gru_plan_for(m, 2, s);
+        rc = dgrp_gru_launch_batch(m, pre, d_idx, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec], (float *)(w + l.pl),
+                                   w + l.avg, stream);
         if (rc) return rc;
-        rc = dgrp_attention_launch_recs(m, s, dgrp_placement{ 0, 0 }, 0, windows, 1, rows, w + l.avg, (const float *)(w + l.pl), out,
+        rc = dgrp_attention_launch_recs(m, pre, dgrp_placement{ 0, 0 }, 0, windows, 1, rows, w + l.avg, (const float *)(w + l.pl), out,
                                         w + l.recs, nrec, stream);
         if (rc) return rc;
     }

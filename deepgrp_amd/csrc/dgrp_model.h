@@ -49,12 +49,20 @@ struct dgrp_timer_scope {
     ~dgrp_timer_scope();
 };
 
-// rows of LDS the fused kernel may use to pre-merge a workgroup's windows
-int dgrp_gru_launch(const dgrp_model *m, const uint8_t *d_idx, int64_t n, int64_t s, dgrp_placement place,
-                    int64_t w0, int64_t nw, int mode, float *d_out, void *d_avg, hipStream_t stream);
-int dgrp_attention_launch(const dgrp_model *m, int64_t s, dgrp_placement place, int64_t w0, int64_t nw,
-                          int merge, int64_t n, const void *d_avg, const float *d_pl, float *d_out,
-                          hipStream_t stream);
+// Which recurrent kernel runs a launch of mode 0 (merged), 1 (window probabilities) or 2 (attention pre-pass) with step s, and
+// what its LDS carve sets (gru_kernel.hip).  The attention kernel reads the avg[t] rows its pre-pass's plan wrote.
+enum class dgrp_kernel { none, wave, split2, stream64, stream, split, lstm, fused };   // none: the window does not fit the LDS
+struct dgrp_gru_plan {
+    dgrp_kernel kernel;
+    int mode;
+    int64_t s;
+    size_t lds;                         // dynamic LDS bytes: of a workgroup, of a wave (wave) or of one of the two row tiles (split2)
+    int ospan, lo_tile_off, xtab_off;   // gru_params fields of the carve
+    int avg_up;                         // row length (elements) of the avg[t] spill: 16 NU16 behind gru_wave_kernel, else UP
+};
+dgrp_gru_plan dgrp_gru_plan_for(const dgrp_model *m, int mode, int64_t s);
+int dgrp_gru_launch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, int64_t n, dgrp_placement place,
+                    int64_t w0, int64_t nw, float *d_out, void *d_avg, hipStream_t stream);
 // rnn_stream.hip: the streamed split-operand kernel (cell 0 = GRU with 5..8 waves, 1 = LSTM with 1..4 waves)
 struct gru_params;
 int dgrp_stream_launch(const gru_params &p, int cell, int NW, int64_t groups, size_t lds, hipStream_t stream);
@@ -62,14 +70,13 @@ int dgrp_stream_launch(const gru_params &p, int cell, int NW, int64_t groups, si
 int dgrp_wave_carve(int NU, gru_params &p, int mode, int64_t s, int64_t budget);
 int dgrp_wave_table_bytes(int NU);
 int dgrp_wave_launch(const gru_params &p, int NU, int64_t groups, int wave_bytes, bool onercp, hipStream_t stream);
-int dgrp_spill_row(const dgrp_model *m);   // row length of the avg[t] spill (gru_kernel.hip)
 // rnn_stream.hip: GRU with 129-256 units on waves of 64 units with resident hi fragments (NW = 32-unit slices of the model)
 size_t dgrp_stream64_carve(int NW, gru_params &p, int mode, int64_t s, int64_t budget);
 int dgrp_stream64_launch(const gru_params &p, int NW, int64_t groups, size_t lds, hipStream_t stream);
 // batched records (mode 0): see gru_kernel.hip
-int dgrp_gru_launch_batch(const dgrp_model *m, const uint8_t *d_idx, int64_t s, const void *d_recs, const int64_t *d_wg_first,
-                          int64_t nrec, int64_t total_groups, int mode, float *d_out, void *d_avg, hipStream_t stream);
-int dgrp_attention_launch_recs(const dgrp_model *m, int64_t s, dgrp_placement place, int64_t w0, int64_t nw,
+int dgrp_gru_launch_batch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, const void *d_recs,
+                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, hipStream_t stream);
+int dgrp_attention_launch_recs(const dgrp_model *m, const dgrp_gru_plan &pre, dgrp_placement place, int64_t w0, int64_t nw,
                                int merge, int64_t n, const void *d_avg, const float *d_pl, float *d_out,
                                const void *d_recs, int64_t nrec, hipStream_t stream);
 // layout of one record-table entry (64 bytes): idx_off, n, out_row, nwin, place.nfullB, place.shift, win_first, 0

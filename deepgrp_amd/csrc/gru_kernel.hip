@@ -50,17 +50,12 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
 {
     gru_params p = pin;
     const int64_t bid = wg_record<MODE>(pin, p);
-    constexpr bool PIPE = DGRP_PIPE;
     constexpr int UP = 32 * NW, KS = UP / 16, HS = UP + 8;   // HS: padded row pitch (halves) -> conflict-free b128 reads
     // u > 128: the three gate slices no longer fit 256 VGPRs; the z gate's fragments (needed last in a
     // step) are then re-read from L2 every step (16 KB per wave-step, a few % of L2 bandwidth)
     constexpr bool ZSTREAM = NW > 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-#ifdef DGRP_STAMP
-    const uint64_t stamp_entry = __builtin_amdgcn_s_memtime();
-    const uint64_t stamp_rentry = __builtin_amdgcn_s_memrealtime();
-#endif
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -176,18 +171,12 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
         for (int reg = 0; reg < 4; ++reg) dw[reg * NW * 64] = d[reg];
     };
 
-#ifdef DGRP_STAMP
-    uint32_t stamp_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    uint64_t stamp_prev = __builtin_amdgcn_s_memtime();
-    const uint64_t stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // Step t, in program order (the matrix pipe runs behind the wave's instruction stream, so whatever is
     // issued after a group of MFMAs executes in their shadow):
     //   loads of h_{t-1} | r chain + Dense(t-1) MFMAs | softmax/merge of step t-2 | g chain + sigmoid(r) |
     //   z chain + r*g, candidate input projection, tanh | store Dense(t-1) partials | sigmoid(z), blend,
     //   publish h_t | barrier
     for (int t = 0; t < T; ++t) {
-        STAMP(0);
         // ---- A operand of the input k-step: one-hot(base) | 1 ------------------------------
         uint32_t b = myseq[dir ? T - 1 - t : t];
         if (dir) b = b < 4 ? 3 - b : 4;                      // complement table [3,2,1,0,4], model.py:233-237
@@ -208,10 +197,7 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
         auto hfrag = [&](int k) -> half8 { return ZSTREAM ? *reinterpret_cast<const half8 *>(arow + 16 * k) : af[ZSTREAM ? 0 : k]; };
         // the streamed z fragments: ZPF of them in flight, the first ones requested before the g chain (same box, u=256:
         // 8 deep 157 ms, 4 deep 116, 2 deep 105, 1 deep 104 per 5 Mbp -- spilled registers cost more than exposed latency)
-#ifndef DGRP_ZPF
-#define DGRP_ZPF (NW >= 7 ? 2 : 4)
-#endif
-        constexpr int ZPF = DGRP_ZPF;                        // 224+ units spill: every register counts more than latency
+        constexpr int ZPF = NW >= 7 ? 2 : 4;                 // 224+ units spill: every register counts more than latency
         uint4 zq[ZSTREAM ? ZPF : 1];
         if (ZSTREAM) {
 #pragma unroll
@@ -276,27 +262,24 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
         }
         f32x4 dpl = zero4;
         if (t > 0) dpl = dense_issue(hcur, t - 1);
-        if (PIPE) __builtin_amdgcn_sched_barrier(0);
-        STAMP(1);
+        __builtin_amdgcn_sched_barrier(0);
         if (t > 1) {
             if (STAGED) finish_commit(t - 2);
             else finish_step(t - 2);
         }
-        if (PIPE) __builtin_amdgcn_sched_barrier(0);
-        STAMP(2);
+        __builtin_amdgcn_sched_barrier(0);
         f32x16 ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bg[KS], xa, zero16, 0, 0, 0);
         f32x2 rr[8];
 #pragma unroll
         for (int k = 0; k < KS; ++k) {
             ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bg[k], hfrag(k), ag, 0, 0, 0);
-            if (PIPE) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 2 * (k * 8 / KS); i < 2 * ((k + 1) * 8 / KS); i += 2) {
                 rr[i / 2] = rcp1p_exp2_pair(ar[i], ar[i + 1]);
             }
-            if (PIPE) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        STAMP(3);
         f32x16 az = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bz[KS], xa, zero16, 0, 0, 0);
         // z chain: its first half hides r * g, then the candidate's input projection is issued and the
         // second half hides the tanh
@@ -307,7 +290,7 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
             const half8 bz = ZSTREAM ? __builtin_bit_cast(half8, zq[ZSTREAM ? k % ZPF : 0]) : Bz[ZSTREAM ? KS : k];
             if (ZSTREAM && k + ZPF < KS) zq[ZSTREAM ? k % ZPF : 0] = mypack[(size_t)(k + ZPF) * 64];
             az = __builtin_amdgcn_mfma_f32_32x32x16_f16(bz, hfrag(k), az, 0, 0, 0);
-            if (PIPE) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             if (k < KH) {
 #pragma unroll
                 for (int i = 2 * (k * 8 / KH); i < 2 * ((k + 1) * 8 / KH); i += 2) {      // r * (h.U_h + b_rec_h)
@@ -322,10 +305,9 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
                     else hh[i / 2] = 1.0f - 2.0f * rcp1p_exp2_pair(ag[i], ag[i + 1]);
                 }
             }
-            if (PIPE) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         if (t > 0) dense_store(t - 1, dpl);
-        STAMP(4);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (ONERCP) {
@@ -351,21 +333,9 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
             const half4 hv = { (_Float16)h0.x, (_Float16)h0.y, (_Float16)h1.x, (_Float16)h1.y };
             *reinterpret_cast<half4 *>(wrow + 8 * q) = hv;
         }
-        STAMP(5);
         __syncthreads();
-        STAMP(6);
         _Float16 *tmp = hcur; hcur = hnxt; hnxt = tmp;
     }
-#ifdef DGRP_STAMP
-    if (p.stamps && lane == 0) {
-        uint64_t *o = p.stamps + ((size_t)blockIdx.x * NW + wave) * 16;
-        for (int k = 0; k < 8; ++k) o[k] = stamp_acc[k];
-        o[8] = __builtin_amdgcn_s_memtime() - stamp_t0;
-        o[9] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-        o[10] = stamp_t0 - stamp_entry;
-        o[11] = __builtin_amdgcn_s_getreg(6148 | (11 << 11)) ;   // HW_ID low 12 bits
-    }
-#endif
     // drain: Dense of the last step, the two outstanding softmax/merge steps
     {
         const f32x4 dpl = dense_issue(hcur, T - 1);
@@ -376,15 +346,6 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_fused_kernel(const gru_params 
     }
 
     if (MODE == 0 && p.ospan > 0) flush_image<NW>(p, ctx);
-#ifdef DGRP_STAMP
-    if (p.stamps && lane == 0) {
-        uint64_t *o = p.stamps + ((size_t)blockIdx.x * NW + wave) * 16;
-        o[11] = __builtin_amdgcn_s_memtime() - stamp_entry;
-        o[12] = stamp_rentry;
-        o[13] = __builtin_amdgcn_s_memrealtime();
-        o[14] = __builtin_amdgcn_s_getreg((15 << 11) | 4);     // HW_ID[15:0]
-    }
-#endif
 }
 
 // ---- split-operand variant (dgrp_model_set_precision(m, 1)) -------------------------------------------------------
@@ -400,13 +361,7 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_split_kernel(const gru_params 
 {
     gru_params p = pin;
     const int64_t bid = wg_record<MODE>(pin, p);
-#ifndef DGRP_SPLIT_PF
-#define DGRP_SPLIT_PF 6
-#endif
-#ifndef DGRP_SPLIT_PIN
-#define DGRP_SPLIT_PIN 1
-#endif
-    constexpr int UP = 32 * NW, KS = UP / 16, HS = UP + 8, NLO = 3 * KS, PF = DGRP_SPLIT_PF < NLO ? DGRP_SPLIT_PF : NLO;
+    constexpr int UP = 32 * NW, KS = UP / 16, HS = UP + 8, NLO = 3 * KS, PF = 6 < NLO ? 6 : NLO;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -499,7 +454,7 @@ __global__ void __launch_bounds__(64 * NW, 2) gru_split_kernel(const gru_params 
             // Keep the refills HERE for the attention pre-pass: left alone the scheduler sinks each load to two MFMAs in front of its
             // use (the ring then hides nothing: 2 500 of a wave-step's 6 700 cycles waiting on vmcnt).  defaults.toml shape +4.7 %;
             // without the avg[t] stores in the step (MODE 0 / 1) the sunk form is 1 % faster at 64 units and stays.
-            if (DGRP_SPLIT_PIN && (MODE == 2 || DGRP_SPLIT_PIN == 2)) __builtin_amdgcn_sched_barrier(0);
+            if (MODE == 2) __builtin_amdgcn_sched_barrier(0);
             ar = __builtin_amdgcn_mfma_f32_32x32x16_f16(Br[k], hf, ar, 0, 0, 0);
             ag = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bg[k], hf, ag, 0, 0, 0);
             az = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bz[k], hf, az, 0, 0, 0);
@@ -886,17 +841,8 @@ __device__ __forceinline__ float att_elem(const att_chunk (&row)[N], int k)
     else return __builtin_bit_cast(f32x4, row[k / 4])[k % 4];
 }
 
-#ifndef DGRP_ATT_OCC
-#define DGRP_ATT_OCC 1
-#endif
-#ifndef DGRP_ATT_PIPE_MINUP
-#define DGRP_ATT_PIPE_MINUP 48
-#endif
-#ifndef DGRP_ATT_DEPTH2_MINUP
-#define DGRP_ATT_DEPTH2_MINUP 48
-#endif
 template <int UP, int CM, typename AT>
-__global__ void __launch_bounds__(256, (UP <= 64 && sizeof(AT) == 4) ? DGRP_ATT_OCC : 2) attention_wave_kernel(const att_params p)
+__global__ void __launch_bounds__(256, (UP <= 64 && sizeof(AT) == 4) ? 1 : 2) attention_wave_kernel(const att_params p)
 {
     constexpr int CT = UP <= 64 ? 64 : 128;                  // context registers per lane (butterfly width)
     constexpr int EPC = 16 / sizeof(AT);                     // elements per 16-byte chunk
@@ -923,10 +869,10 @@ __global__ void __launch_bounds__(256, (UP <= 64 && sizeof(AT) == 4) ? DGRP_ATT_
     constexpr int CPR = UP / EPC, TP = UP + EPC;             // 16-byte chunks per row, LDS row pitch
     AT *mytile = &tile[wave][0][0];
     // Tiles in flight per wave, in registers: with the 512-register budget of a lone wave a second tile ahead is free.
-    constexpr int DEPTH = (sizeof(AT) == 4 && UP <= 64 && UP >= DGRP_ATT_DEPTH2_MINUP && DGRP_ATT_OCC == 1) ? 2 : 1;
+    constexpr int DEPTH = (sizeof(AT) == 4 && UP <= 64 && UP >= 48) ? 2 : 1;
     constexpr bool AHEAD = UP * sizeof(AT) <= 128 || UP <= 64;   // beyond 64 units the registers for a tile in flight are gone
     constexpr int QN = (UP + 63) / 64;                       // units per lane of a window's q row (k = lane, lane + 64)
-    constexpr bool PIPE = sizeof(AT) == 4 && UP <= 64 && UP >= DGRP_ATT_PIPE_MINUP && DGRP_ATT_OCC == 1;   // a lone wave per SIMD: registers to spare for the next window's first loads
+    constexpr bool PIPE = sizeof(AT) == 4 && UP <= 64 && UP >= 48;   // a lone wave per SIMD: registers to spare for the next window's first loads
     constexpr int PCH = (CM <= 8 && PIPE) ? 8 : 0;           // 64-step chunks of stored logit halves kept in registers (T <= 512)
     att_chunk nxt[DEPTH][CPR];
     auto fetch = [&](att_chunk (&dst)[CPR], const AT *avg, int t0) {
@@ -1241,14 +1187,6 @@ static int launch_split(const gru_params &p, int64_t groups, size_t lds, hipStre
     return p.zfold != 0.0f ? launch_split_rcp<NW, true>(p, groups, lds, stream) : launch_split_rcp<NW, false>(p, groups, lds, stream);
 }
 
-// split-operand kernel selected (dgrp_model_set_precision) and applicable to this launch
-// (the LSTM cell beyond 128 units has the streamed split-operand kernel only: it runs at either precision level)
-static bool use_split(const dgrp_model *m, int)
-{
-    if (m->cell == 1 && m->NW > 4 && m->d_stream) return true;
-    return m->precision == 1 && ((m->cell == 0 && m->NW <= 4 && m->d_pack_lo) || m->d_stream);
-}
-
 template <int NW>
 static int launch_lstm(const gru_params &p, int64_t groups, size_t lds, hipStream_t stream)
 {
@@ -1291,7 +1229,6 @@ static size_t gru_tile_carve(const dgrp_model *m, gru_params &p, int mode, int64
 // with 39 KiB; its fp16-operand kernel is 1 % better off with the larger image).  Five waves and more: one workgroup per CU.
 static int64_t tile_budget(const dgrp_model *m, bool split)
 {
-    if (const char *e = getenv("DGRP_TILE_BUDGET_KB")) return (int64_t)atoi(e) * 1024;
     if (m->NW == 1) return 19 * 1024;
     if (m->NW == 2 && split) return 39 * 1024;
     return (m->NW > 4 ? 144 : 72) * 1024;
@@ -1299,210 +1236,152 @@ static int64_t tile_budget(const dgrp_model *m, bool split)
 // gru_split2_kernel (gru_split2.hip): two tile carves with row pitch UP + 16, then the input-projection table
 #define DGRP_SPLIT2_PAD 16
 #define DGRP_SPLIT2_XTAB_BYTES (5 * (4 * 128 * 4 + 32))
-static bool split2_applies(const dgrp_model *m) { return m->NW == 4 && m->d_pack16 && !getenv("DGRP_SPLIT_ONE_TILE"); }
-// gru_wave_kernel (gru_wave.hip): GRU up to 64 units; four waves' carves and the table must fit the CU's LDS -- a property of the model's
-// window and step, never of the record
-// (17-32 units as an attention pre-pass: the one-wave workgroups of gru_split_kernel<1> -- no partner wave to meet either -- measured 5-7 %
-// faster than two unit groups here, r03 `tools/bench_shapes.py`; every other count of unit groups and every merged / window-output launch
-// is faster on this kernel)
-static bool wave_applies(const dgrp_model *m, int mode)
-{
-    return m->cell == 0 && m->NU16 > 0 && m->d_packw && !(m->NU16 == 2 && mode == 2) && !getenv("DGRP_SPLIT_ONE_TILE");
-}
-static int wave_try(const dgrp_model *m, gru_params &p, int mode, int64_t s);
-// Row length (elements) of the avg[t] spill between the attention pre-pass and the second kernel: the pre-pass kernel's unit padding --
-// 16 NU for gru_wave_kernel (a 36-unit model spills 48 floats per step, not 64), the model's UP (multiple of 32) otherwise.  A property
-// of the model and its precision level only: the pre-pass never needs an image, so whether four waves' carves fit depends on T alone.
-int dgrp_spill_row(const dgrp_model *m)
-{
-    if (m->precision == 1 && wave_applies(m, 2)) {
-        gru_params q;
-        q.T = m->T; q.C = m->C; q.Tp = (int)dgrp_align_up(m->T, 16);
-        if (wave_try(m, q, 2, 1)) return 16 * m->NU16;
-    }
-    return m->UP;
-}
-static int wave_try(const dgrp_model *m, gru_params &p, int mode, int64_t s)
-{
-    const int64_t budget = (160 * 1024 - dgrp_wave_table_bytes(m->NU16)) / 4 / 16 * 16;
-    const int wb = dgrp_wave_carve(m->NU16, p, mode, s, budget);
-    return wb <= budget ? wb : 0;
-}
 
-int dgrp_gru_launch(const dgrp_model *m, const uint8_t *d_idx, int64_t n, int64_t s, dgrp_placement place,
-                    int64_t w0, int64_t nw, int mode, float *d_out, void *d_avg, hipStream_t stream)
+// The recurrent kernel of a launch, in order of preference, and its LDS carve.  A property of the model, the mode and the step,
+// never of the record: a record never changes kernels with the way it is batched.
+dgrp_gru_plan dgrp_gru_plan_for(const dgrp_model *m, int mode, int64_t s)
 {
-    if (nw <= 0) return DGRP_OK;
-    dgrp_timer_scope timed(stream, nw);                             // bench.py: HIP events around the launch (no-op unless enabled)
-    gru_params p;
-    p.idx = d_idx; p.n = n; p.s = s; p.w0 = w0; p.nw = nw; p.place = place;
-    p.pack = m->d_pack; p.ffb = m->d_ffb; p.out = d_out; p.avg = d_avg; p.avg_f32 = m->precision == 1 ? 1 : 0;
-    p.T = m->T; p.C = m->C; p.nfrag = m->nfrag; p.mode = mode;
-    p.Tp = (int)dgrp_align_up(m->T, 16);
-    p.stamps = nullptr;
-    p.recs = nullptr; p.wg_first = nullptr; p.nrec = 0; p.avgw = 0;
-#ifdef DGRP_STAMP
-    static uint64_t *d_stamps = nullptr;
-    const int64_t ngroups = (nw + DGRP_WG_WINDOWS - 1) / DGRP_WG_WINDOWS;
-    const size_t stamp_bytes = (size_t)ngroups * m->NW * 16 * 8;
-    if (getenv("DGRP_STAMP_DUMP")) {
-        if (d_stamps) (void)hipFree(d_stamps);
-        DGRP_HIP(hipMalloc((void **)&d_stamps, stamp_bytes));
-        DGRP_HIP(hipMemset(d_stamps, 0, stamp_bytes));
-        p.stamps = d_stamps;
+    gru_params p{};
+    p.T = m->T; p.C = m->C; p.Tp = (int)dgrp_align_up(m->T, 16);
+    dgrp_gru_plan plan{};
+    plan.mode = mode; plan.s = s; plan.avg_up = m->UP;
+    auto pick = [&](dgrp_kernel k, size_t lds) {
+        plan.kernel = k; plan.lds = lds;
+        plan.ospan = p.ospan; plan.lo_tile_off = p.lo_tile_off; plan.xtab_off = p.xtab_off;
+        return plan;
+    };
+    // split-operand kernel selected (dgrp_model_set_precision) and present
+    // (the LSTM cell beyond 128 units has the streamed split-operand kernel only: it runs at either precision level)
+    const bool split = (m->cell == 1 && m->NW > 4 && m->d_stream) ||
+                       (m->precision == 1 && ((m->cell == 0 && m->NW <= 4 && m->d_pack_lo) || m->d_stream));
+    const bool one_tile = getenv("DGRP_SPLIT_ONE_TILE") != nullptr;    // neither gru_wave_kernel nor gru_split2_kernel
+    // gru_wave_kernel (gru_wave.hip): GRU up to 64 units; four waves' carves and the table must fit the CU's LDS
+    // (17-32 units as an attention pre-pass: the one-wave workgroups of gru_split_kernel<1> -- no partner wave to meet either -- measured 5-7 %
+    // faster than two unit groups here, r03 `tools/bench_shapes.py`; every other count of unit groups and every merged / window-output launch
+    // is faster on this kernel).  Its avg[t] rows are 16 NU long (a 36-unit model spills 48 floats per step, not 64).
+    if (split && !one_tile && m->cell == 0 && m->NU16 > 0 && m->d_packw && !(m->NU16 == 2 && mode == 2)) {
+        const int64_t budget = (160 * 1024 - dgrp_wave_table_bytes(m->NU16)) / 4 / 16 * 16;
+        const int wave_bytes = dgrp_wave_carve(m->NU16, p, mode, s, budget);
+        if (wave_bytes <= budget) {
+            plan.avg_up = 16 * m->NU16;
+            return pick(dgrp_kernel::wave, wave_bytes);
+        }
     }
-#endif
-    const bool split = use_split(m, mode);
-    p.pack_lo = m->d_pack_lo; p.zfold = m->onercp ? 1.0f : 0.0f;
-    p.pack16 = m->d_pack16; p.xtab = m->d_xtab; p.xtab_off = 0; p.stream = m->d_stream;
-    p.packw = m->d_packw; p.xtabw = m->d_xtabw; p.avg_up = dgrp_spill_row(m);
-    const int64_t groups = (nw + DGRP_WG_WINDOWS - 1) / DGRP_WG_WINDOWS;
-    DGRP_REQUIRE(groups < (1ll << 31), "too many windows in one launch (%lld)", (long long)nw);
-    if (split && wave_applies(m, mode)) {
-        if (const int wb = wave_try(m, p, mode, s)) return dgrp_wave_launch(p, m->NU16, groups, wb, m->onercp != 0, stream);
-    }
-    if (split && split2_applies(m)) {
-        // 128-unit class: two row tiles per workgroup, everything resident, whenever two carves and the table fit the CU's LDS
-        // (a property of the model's window size, not of the record: a record never changes kernels with the way it is batched)
+    // 128-unit class: two row tiles per workgroup, everything resident, whenever two carves and the table fit the CU's LDS
+    if (split && !one_tile && m->NW == 4 && m->d_pack16) {
         const int half_bytes = (int)dgrp_align_up((int64_t)gru_tile_carve(m, p, mode, s, true, DGRP_SPLIT2_PAD, 74 * 1024), 256);
         if (2 * half_bytes + DGRP_SPLIT2_XTAB_BYTES <= 160 * 1024) {
             p.xtab_off = 2 * half_bytes;
-            return dgrp_split2_launch(p, groups, half_bytes, m->onercp != 0, stream);
+            return pick(dgrp_kernel::split2, half_bytes);
         }
     }
     // rows spanned by 16 consecutive windows, capped so that the workgroups the registers allow fit a CU's 160 KiB (tile_budget)
     const size_t lds = gru_tile_carve(m, p, mode, s, split, 8, tile_budget(m, split));
-    DGRP_REQUIRE(lds <= 160 * 1024, "window size %d: the workgroup's staged sequences (%d bytes of LDS) do not fit 160 KiB", m->T,
-                 gru_lds_seq(p.Tp));
-    if (split && m->d_stream && m->cell == 0 && m->d_xtab && !getenv("DGRP_STREAM_PLAIN")) {
+    if (lds > 160 * 1024) return pick(dgrp_kernel::none, lds);
+    if (split && m->d_stream && m->cell == 0 && m->d_xtab) {
         // GRU, 129-256 units: waves of 64 units, resident hi fragments (rnn_stream.hip); one workgroup per CU
         const size_t lds64 = dgrp_stream64_carve(m->NW, p, mode, s, 158 * 1024);
-        if (lds64 <= 160 * 1024) return dgrp_stream64_launch(p, m->NW, groups, lds64, stream);
+        if (lds64 <= 160 * 1024) return pick(dgrp_kernel::stream64, lds64);
         (void)gru_tile_carve(m, p, mode, s, split, 8, tile_budget(m, split));          // (window too long for that carve: the all-streamed kernel)
     }
-    if (split && m->d_stream) return dgrp_stream_launch(p, m->cell, m->NW, groups, lds, stream);
-    if (split) {
+    if (split && m->d_stream) return pick(dgrp_kernel::stream, lds);
+    if (split) return pick(dgrp_kernel::split, lds);
+    return pick(m->cell == 1 ? dgrp_kernel::lstm : dgrp_kernel::fused, lds);
+}
+
+// `p` carries what the launch covers (windows and placement, or the record table) and the output buffers: the rest comes from the
+// model and the plan
+static int gru_dispatch(const dgrp_model *m, const dgrp_gru_plan &plan, gru_params p, int64_t groups, hipStream_t stream)
+{
+    p.pack = m->d_pack; p.ffb = m->d_ffb; p.avg_f32 = m->precision == 1 ? 1 : 0;
+    p.T = m->T; p.C = m->C; p.nfrag = m->nfrag; p.mode = plan.mode; p.s = plan.s;
+    p.Tp = (int)dgrp_align_up(m->T, 16);
+    p.ospan = plan.ospan; p.lo_tile_off = plan.lo_tile_off; p.xtab_off = plan.xtab_off; p.avg_up = plan.avg_up;
+    p.pack_lo = m->d_pack_lo; p.zfold = m->onercp ? 1.0f : 0.0f;
+    p.pack16 = m->d_pack16; p.xtab = m->d_xtab; p.stream = m->d_stream;
+    p.packw = m->d_packw; p.xtabw = m->d_xtabw;
+    const bool onercp = m->onercp != 0;
+    switch (plan.kernel) {
+    case dgrp_kernel::none: break;
+    case dgrp_kernel::wave: return dgrp_wave_launch(p, m->NU16, groups, (int)plan.lds, onercp, stream);
+    case dgrp_kernel::split2: return dgrp_split2_launch(p, groups, (int)plan.lds, onercp, stream);
+    case dgrp_kernel::stream64: return dgrp_stream64_launch(p, m->NW, groups, plan.lds, stream);
+    case dgrp_kernel::stream: return dgrp_stream_launch(p, m->cell, m->NW, groups, plan.lds, stream);
+    case dgrp_kernel::split:
         switch (m->NW) {
-        case 1: return launch_split<1>(p, groups, lds, stream);
-        case 2: return launch_split<2>(p, groups, lds, stream);
-        case 3: return launch_split<3>(p, groups, lds, stream);
-        default: return launch_split<4>(p, groups, lds, stream);
+        case 1: return launch_split<1>(p, groups, plan.lds, stream);
+        case 2: return launch_split<2>(p, groups, plan.lds, stream);
+        case 3: return launch_split<3>(p, groups, plan.lds, stream);
+        default: return launch_split<4>(p, groups, plan.lds, stream);
         }
-    }
-    if (m->cell == 1) {
+    case dgrp_kernel::lstm:
         switch (m->NW) {
-        case 1: return launch_lstm<1>(p, groups, lds, stream);
-        case 2: return launch_lstm<2>(p, groups, lds, stream);
-        case 3: return launch_lstm<3>(p, groups, lds, stream);
-        case 4: return launch_lstm<4>(p, groups, lds, stream);
+        case 1: return launch_lstm<1>(p, groups, plan.lds, stream);
+        case 2: return launch_lstm<2>(p, groups, plan.lds, stream);
+        case 3: return launch_lstm<3>(p, groups, plan.lds, stream);
+        case 4: return launch_lstm<4>(p, groups, plan.lds, stream);
         default:
             dgrp_set_error("LSTM units=%d not supported (max 128)", m->u);
             return DGRP_EINVAL;
         }
+    case dgrp_kernel::fused:
+        switch (m->NW) {
+        case 1: return launch_gru<1>(p, groups, plan.lds, onercp, stream);
+        case 2: return launch_gru<2>(p, groups, plan.lds, onercp, stream);
+        case 3: return launch_gru<3>(p, groups, plan.lds, onercp, stream);
+        case 4: return launch_gru<4>(p, groups, plan.lds, onercp, stream);
+        case 5: return launch_gru<5>(p, groups, plan.lds, onercp, stream);
+        case 6: return launch_gru<6>(p, groups, plan.lds, onercp, stream);
+        case 7: return launch_gru<7>(p, groups, plan.lds, onercp, stream);
+        case 8: return launch_gru<8>(p, groups, plan.lds, onercp, stream);
+        default:
+            dgrp_set_error("units=%d not supported by the GRU kernel (max 256)", m->u);
+            return DGRP_EINVAL;
+        }
     }
-#ifdef DGRP_STAMP
-    if (p.stamps && m->NW == 4) {
-        int rc = launch_gru<4>(p, groups, lds, m->onercp != 0, stream);
-        (void)hipStreamSynchronize(stream);
-        std::vector<uint64_t> hst(stamp_bytes / 8);
-        (void)hipMemcpy(hst.data(), p.stamps, stamp_bytes, hipMemcpyDeviceToHost);
-        FILE *f = fopen(getenv("DGRP_STAMP_DUMP"), "wb");
-        if (f) { fwrite(hst.data(), 1, stamp_bytes, f); fclose(f); }
-        return rc;
-    }
-#endif
-    switch (m->NW) {
-    case 1: return launch_gru<1>(p, groups, lds, m->onercp != 0, stream);
-    case 2: return launch_gru<2>(p, groups, lds, m->onercp != 0, stream);
-    case 3: return launch_gru<3>(p, groups, lds, m->onercp != 0, stream);
-    case 4: return launch_gru<4>(p, groups, lds, m->onercp != 0, stream);
-    case 5: return launch_gru<5>(p, groups, lds, m->onercp != 0, stream);
-    case 6: return launch_gru<6>(p, groups, lds, m->onercp != 0, stream);
-    case 7: return launch_gru<7>(p, groups, lds, m->onercp != 0, stream);
-    case 8: return launch_gru<8>(p, groups, lds, m->onercp != 0, stream);
-    default:
-        dgrp_set_error("units=%d not supported by the GRU kernel (max 256)", m->u);
-        return DGRP_EINVAL;
-    }
+    dgrp_set_error("window size %d: the workgroup's staged sequences (%d bytes of LDS) do not fit 160 KiB", m->T, gru_lds_seq(p.Tp));
+    return DGRP_EINVAL;
 }
 
-// GRU forward + merge for a batch of records in ONE launch (mode 0, no attention): the record table and the
-// cumulative workgroup counts are device arrays prepared by the caller (api.hip: dgrp_predict_batch)
-int dgrp_gru_launch_batch(const dgrp_model *m, const uint8_t *d_idx, int64_t s, const void *d_recs, const int64_t *d_wg_first,
-                          int64_t nrec, int64_t total_groups, int mode, float *d_out, void *d_avg, hipStream_t stream)
+int dgrp_gru_launch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, int64_t n, dgrp_placement place,
+                    int64_t w0, int64_t nw, float *d_out, void *d_avg, hipStream_t stream)
+{
+    if (nw <= 0) return DGRP_OK;
+    dgrp_timer_scope timed(stream, nw);                             // bench.py: HIP events around the launch (no-op unless enabled)
+    gru_params p{};
+    p.idx = d_idx; p.n = n; p.w0 = w0; p.nw = nw; p.place = place; p.out = d_out; p.avg = d_avg;
+    const int64_t groups = (nw + DGRP_WG_WINDOWS - 1) / DGRP_WG_WINDOWS;
+    DGRP_REQUIRE(groups < (1ll << 31), "too many windows in one launch (%lld)", (long long)nw);
+    return gru_dispatch(m, plan, p, groups, stream);
+}
+
+// A batch of records in ONE launch (mode 0, or the GRU attention pre-pass): the record table and the cumulative workgroup counts
+// are device arrays prepared by the caller (api.hip: dgrp_predict_batch)
+int dgrp_gru_launch_batch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, const void *d_recs,
+                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, hipStream_t stream)
 {
     if (nrec <= 0 || total_groups <= 0) return DGRP_OK;
     dgrp_timer_scope timed(stream, total_groups * DGRP_WG_WINDOWS);
-    DGRP_REQUIRE(m->NW <= 8 && (mode == 0 || (mode == 2 && m->cell == 0)), "dgrp_gru_launch_batch: mode 0, or the GRU attention pre-pass");
-    gru_params p;
-    p.idx = d_idx; p.n = 0; p.s = s; p.w0 = 0; p.nw = 0; p.place = dgrp_placement{ 0, 0 };
-    p.pack = m->d_pack; p.ffb = m->d_ffb; p.out = d_out; p.avg = d_avg; p.avg_f32 = m->precision == 1 ? 1 : 0;
-    p.T = m->T; p.C = m->C; p.nfrag = m->nfrag; p.mode = mode;
-    p.Tp = (int)dgrp_align_up(m->T, 16);
-    p.stamps = nullptr;
-    p.recs = (const gru_rec *)d_recs; p.wg_first = d_wg_first; p.nrec = nrec; p.avgw = 0;
-    const bool split = use_split(m, mode);
-    p.pack_lo = m->d_pack_lo; p.zfold = m->onercp ? 1.0f : 0.0f;
-    p.pack16 = m->d_pack16; p.xtab = m->d_xtab; p.xtab_off = 0; p.stream = m->d_stream;
-    p.packw = m->d_packw; p.xtabw = m->d_xtabw; p.avg_up = dgrp_spill_row(m);
+    DGRP_REQUIRE(m->NW <= 8 && (plan.mode == 0 || (plan.mode == 2 && m->cell == 0)), "dgrp_gru_launch_batch: mode 0, or the GRU attention pre-pass");
+    gru_params p{};
+    p.idx = d_idx; p.out = d_out; p.avg = d_avg;
+    p.recs = (const gru_rec *)d_recs; p.wg_first = d_wg_first; p.nrec = nrec;
     DGRP_REQUIRE(total_groups < (1ll << 31), "too many windows in one launch");
-    if (split && wave_applies(m, mode)) {
-        if (const int wb = wave_try(m, p, mode, s)) return dgrp_wave_launch(p, m->NU16, total_groups, wb, m->onercp != 0, stream);
-    }
-    if (split && split2_applies(m)) {
-        const int half_bytes = (int)dgrp_align_up((int64_t)gru_tile_carve(m, p, mode, s, true, DGRP_SPLIT2_PAD, 74 * 1024), 256);
-        if (2 * half_bytes + DGRP_SPLIT2_XTAB_BYTES <= 160 * 1024) {
-            p.xtab_off = 2 * half_bytes;
-            return dgrp_split2_launch(p, total_groups, half_bytes, m->onercp != 0, stream);
-        }
-    }
-    const size_t lds = gru_tile_carve(m, p, mode, s, split, 8, tile_budget(m, split));
-    DGRP_REQUIRE(lds <= 160 * 1024, "window size %d: the workgroup's staged sequences (%d bytes of LDS) do not fit 160 KiB", m->T,
-                 gru_lds_seq(p.Tp));
-    if (split && m->d_stream && m->cell == 0 && m->d_xtab && !getenv("DGRP_STREAM_PLAIN")) {
-        const size_t lds64 = dgrp_stream64_carve(m->NW, p, mode, s, 158 * 1024);
-        if (lds64 <= 160 * 1024) return dgrp_stream64_launch(p, m->NW, total_groups, lds64, stream);
-        (void)gru_tile_carve(m, p, mode, s, split, 8, tile_budget(m, split));
-    }
-    if (split && m->d_stream) return dgrp_stream_launch(p, m->cell, m->NW, total_groups, lds, stream);
-    if (split) {
-        switch (m->NW) {
-        case 1: return launch_split<1>(p, total_groups, lds, stream);
-        case 2: return launch_split<2>(p, total_groups, lds, stream);
-        case 3: return launch_split<3>(p, total_groups, lds, stream);
-        default: return launch_split<4>(p, total_groups, lds, stream);
-        }
-    }
-    if (m->cell == 1) {
-        switch (m->NW) {
-        case 1: return launch_lstm<1>(p, total_groups, lds, stream);
-        case 2: return launch_lstm<2>(p, total_groups, lds, stream);
-        case 3: return launch_lstm<3>(p, total_groups, lds, stream);
-        default: return launch_lstm<4>(p, total_groups, lds, stream);
-        }
-    }
-    switch (m->NW) {
-    case 1: return launch_gru<1>(p, total_groups, lds, m->onercp != 0, stream);
-    case 2: return launch_gru<2>(p, total_groups, lds, m->onercp != 0, stream);
-    case 3: return launch_gru<3>(p, total_groups, lds, m->onercp != 0, stream);
-    case 4: return launch_gru<4>(p, total_groups, lds, m->onercp != 0, stream);
-    case 5: return launch_gru<5>(p, total_groups, lds, m->onercp != 0, stream);
-    case 6: return launch_gru<6>(p, total_groups, lds, m->onercp != 0, stream);
-    case 7: return launch_gru<7>(p, total_groups, lds, m->onercp != 0, stream);
-    default: return launch_gru<8>(p, total_groups, lds, m->onercp != 0, stream);
-    }
+    return gru_dispatch(m, plan, p, total_groups, stream);
 }
 
+// pre: the plan of the attention pre-pass that wrote d_avg and d_pl (its step, and the row length of its avg[t] spill)
 // d_recs / nrec: record table of a batch (windows numbered through the batch, n = rows of the whole batch) or NULL / 0
-int dgrp_attention_launch_recs(const dgrp_model *m, int64_t s, dgrp_placement place, int64_t w0, int64_t nw,
+int dgrp_attention_launch_recs(const dgrp_model *m, const dgrp_gru_plan &pre, dgrp_placement place, int64_t w0, int64_t nw,
                                int merge, int64_t n, const void *d_avg, const float *d_pl, float *d_out,
                                const void *d_recs, int64_t nrec, hipStream_t stream)
 {
     if (nw <= 0) return DGRP_OK;
+    const int64_t s = pre.s;
     att_params p;
     p.avg = d_avg; p.pl = d_pl; p.scale = m->d_scale; p.wtop = m->d_wtop; p.out = d_out;
     p.n = n; p.s = s; p.w0 = w0; p.nw = nw; p.place = place;
-    p.T = m->T; p.C = m->C; p.UP = dgrp_spill_row(m); p.merge = merge;
+    p.T = m->T; p.C = m->C; p.UP = pre.avg_up; p.merge = merge;
     p.recs = (const gru_rec *)d_recs; p.nrec = nrec;
     const int UPs = p.UP;                                     // row length of the spill: the pre-pass kernel's unit padding
     // element type of the avg[t] spill: fp32 behind a split-operand pre-pass (the level the model is set to), else fp16
@@ -1516,7 +1395,7 @@ int dgrp_attention_launch_recs(const dgrp_model *m, int64_t s, dgrp_placement pl
         // one wave per window; beyond 64 units its per-lane context (UP registers) no longer fits beside the row
         const int stat = 4 * UPs * 2 * 4 + 4 * 64 * (UPs + 16 / esz) * esz;  // qs + tiles (static LDS of the kernel)
         if (merge) {
-            const int64_t budget = (stat <= 40 * 1024 && !f32) || DGRP_ATT_OCC == 2 ? 78 * 1024 : 156 * 1024;   // two workgroups per CU where tiles and registers leave room
+            const int64_t budget = stat <= 40 * 1024 && !f32 ? 78 * 1024 : 156 * 1024;   // two workgroups per CU where tiles and registers leave room
             const int64_t cap = (budget - stat) / (m->C * 4);
             p.ospan = (int)(want < cap ? want : cap);
             if (p.ospan < m->T) p.ospan = 0;
@@ -1569,11 +1448,3 @@ int dgrp_attention_launch_recs(const dgrp_model *m, int64_t s, dgrp_placement pl
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
 }
-
-int dgrp_attention_launch(const dgrp_model *m, int64_t s, dgrp_placement place, int64_t w0, int64_t nw,
-                          int merge, int64_t n, const void *d_avg, const float *d_pl, float *d_out,
-                          hipStream_t stream)
-{
-    return dgrp_attention_launch_recs(m, s, place, w0, nw, merge, n, d_avg, d_pl, d_out, nullptr, 0, stream);
-}
-

@@ -2,7 +2,6 @@
 // set-up, softmax/merge of one logit register, image flush.
 #pragma once
 #include "dgrp_model.h"
-#include <vector>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -30,7 +29,6 @@ struct gru_params {
     int T, C, nfrag, mode;
     int Tp;               // T rounded up to 16 (row pitch of the staged sequences)
     int ospan;            // rows of the LDS output image (mode 0), 0 = none
-    uint64_t *stamps;
     // batched records (mode 0): workgroup b belongs to record r with wg_first[r] <= b < wg_first[r+1]; idx / out / n /
     // placement then come from recs[r] and windows count from 0 inside the record
     const struct gru_rec *recs;
@@ -49,7 +47,7 @@ struct gru_params {
     // rnn_split_stream_kernel only (rnn_stream.hip): hi and lo recurrent fragments in consumption order, [NW][KS][2 G][64]
     const uint4 *stream;
     // gru_wave_kernel only (gru_wave.hip, GRU up to 64 units): all-unit 16x16x32 A fragments + Dense B fragments, the input-projection
-    // table [5][4][16 NU], and the row length (floats) of the avg[t] spill (the model's UP)
+    // table [5][4][16 NU], and the row length (floats) of the avg[t] spill (dgrp_gru_plan::avg_up)
     const uint4 *packw;
     const float *xtabw;
     int avg_up;
@@ -248,15 +246,6 @@ __device__ __forceinline__ void flush_image(const gru_params &p, const wg_ctx &c
         if (v != 0u && i < lim) global_atomic_max(gout + i, v);
     }
 }
-
-#ifdef DGRP_STAMP
-#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const uint64_t now_ = __builtin_amdgcn_s_memtime(); stamp_acc[i] += (uint32_t)(now_ - stamp_prev); stamp_prev = now_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-#ifndef DGRP_PIPE
-#define DGRP_PIPE 1
-#endif
 
 // attention pre-pass of the split-operand kernels: avg[t] of this wave's 32 units for window (lane & 15), summed from the
 // hi and lo halves of both strands (the second kernel's operand)

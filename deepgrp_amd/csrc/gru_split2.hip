@@ -40,17 +40,6 @@
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// experiment switch (never set in the product build): 1 drops the U_lo.h_hi pass, 2 the U_hi.h_lo pass -- what a two-pass
-// split would cost in accuracy (tools/twopass_probe.py)
-#ifndef DGRP_SPLIT_DROP
-#define DGRP_SPLIT_DROP 0
-#endif
-// order of the 36 MFMAs of a k-step: 0 = pass, gate, unit half, row half (two in a row share the A fragment); 1 = pass, row half, gate, unit
-// half (six share B); 2 = gate, unit half, pass, row half (four in a row share U_hi, then two U_lo; an accumulator's passes two MFMAs apart)
-#ifndef DGRP_MK_ORDER
-#define DGRP_MK_ORDER 0
-#endif
-
 namespace {
 
 constexpr int NW = 4, UP = 128, KS = 4, HPAD = 16, HS = UP + HPAD;   // k-steps of 32; row pitch 144 halves: conflict-free ds_read_b128
@@ -158,11 +147,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         if (g == 0) Z.ar[sub] = v; else if (g == 1) Z.ag[sub] = v; else Z.az[sub] = v;
     };
 
-#ifdef DGRP_STAMP
-    // diagnostic build: cycles per phase section (ST(2) phase start .. ST(0) in front of the barrier .. ST(1) behind it)
-    uint32_t stamp_acc[3] = { 0, 0, 0 };
-    uint64_t stamp_prev = 0;
-#endif
     // ---- one phase: tile X's step tx on the matrix pipe, tile Y's epilogue of step ty in the gaps --------------------
     struct frag_ring { half8 h[2][2], l[2][2]; };                 // [k-step parity][row half]
     struct dense_ops { half8 a0, a1, l0, l1; };
@@ -180,19 +164,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         const int tf = tx - 2;                                    // step whose logits X finishes in this phase (stored one phase ago, a barrier since)
         if constexpr (DO_X) { F.h[0][0] = X.f0h[0]; F.h[0][1] = X.f0h[1]; F.l[0][0] = X.f0l[0]; F.l[0][1] = X.f0l[1]; }
 #define GAP __builtin_amdgcn_sched_barrier(0);
-#ifdef DGRP_STAMP
-#define ST(i) if constexpr (DO_X && DO_Y) { __builtin_amdgcn_sched_barrier(0); const uint64_t now_ = __builtin_amdgcn_s_memtime(); \
-        stamp_acc[i] += (uint32_t)(now_ - stamp_prev); stamp_prev = now_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define ST(i)
-#endif
-        // MFMA n (0..35) of k-step ks: pass n / 12 (hi.h_hi, hi.h_lo, lo.h_hi), then gate, unit half, row half
+        // MFMA n (0..35) of k-step ks: pass n / 12 (hi.h_hi, hi.h_lo, lo.h_hi), then gate, unit half, row half (two in a row share
+        // the A fragment)
 #define M_K(ks, n)                                                                                               \
-    if constexpr (DO_X && !(DGRP_MK_ORDER != 2 && DGRP_SPLIT_DROP == 1 && (n) >= 24) && !(DGRP_MK_ORDER != 2 && DGRP_SPLIT_DROP == 2 && (n) >= 12 && (n) < 24)) { \
-        constexpr int ps_ = DGRP_MK_ORDER == 2 ? ((n) % 6) / 2 : (n) / 12,                                                          \
-                      g_ = DGRP_MK_ORDER == 0 ? ((n) % 12) / 4 : DGRP_MK_ORDER == 2 ? (n) / 12 : ((n) % 6) / 2,                    \
-                      uh_ = DGRP_MK_ORDER == 0 ? ((n) % 4) / 2 : DGRP_MK_ORDER == 2 ? ((n) / 6) % 2 : (n) % 2,                     \
-                      rh_ = DGRP_MK_ORDER == 1 ? ((n) % 12) / 6 : (n) % 2, sub_ = 2 * uh_ + rh_;                                   \
+    if constexpr (DO_X) {                                                                                        \
+        constexpr int ps_ = (n) / 12, g_ = ((n) % 12) / 4, uh_ = ((n) % 4) / 2, rh_ = (n) % 2, sub_ = 2 * uh_ + rh_; \
         const half8 &b_ = ps_ == 1 ? F.l[(ks) & 1][rh_] : F.h[(ks) & 1][rh_];                                    \
         const u32x4 &w_ = ps_ == 2 ? W.lo[g_][ks][uh_] : W.hi[g_][ks][uh_];                                      \
         if constexpr (g_ == 0) MFMA_R(X.ar[sub_], w_, b_);                                                       \
@@ -291,7 +267,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 #include "gru_split2_phase.inc"
 #undef GAP
-#undef ST
 #undef M_K
 #undef M_D
 #undef PF
@@ -322,10 +297,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     first_step(S0);
     first_step(S1);
     phase(yes, no, no, S0, S1, 0, 0);
-#ifdef DGRP_STAMP
-    stamp_prev = __builtin_amdgcn_s_memtime();
-    const uint64_t stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // Register copies the allocator places on a control-flow edge (loop entry, back edge, exit) are VALU reads it does not know to
     // keep away from the asm MFMAs in front of them: the last MFMAs of a phase have to be complete before the edge.
 #define EDGE_PAD do { asm volatile("s_nop 15\n\ts_nop 7"); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -335,14 +306,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         phase(yes, yes, yes, S0, S1, t + 1, t);      // tile 0's step t + 1  ||  tile 1 finishes step t
         EDGE_PAD;
     }
-#ifdef DGRP_STAMP
-    if (pin.stamps && lane == 0) {
-        uint64_t *o = pin.stamps + ((size_t)blockIdx.x * NW + wave) * 8;
-        o[0] = stamp_acc[0]; o[1] = stamp_acc[1]; o[2] = stamp_acc[2];
-        o[3] = __builtin_amdgcn_s_memtime() - stamp_t0;
-        o[4] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-    }
-#endif
     phase(yes, yes, yes, S1, S0, T - 1, T - 1);
     phase(no, yes, yes, S0, S1, T, T - 1);      // (tile 0's logits of step T - 2 are finished here; tile 1's in its drain)
 
@@ -373,21 +336,6 @@ int launch_split2(const gru_params &p, int64_t groups, int half_bytes, hipStream
     static hipError_t cfg_err = hipSuccess;
     std::call_once(configured, [] { cfg_err = hipFuncSetAttribute((const void *)gru_split2_kernel<MODE, ONERCP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     DGRP_HIP(cfg_err);
-#ifdef DGRP_STAMP
-    if (const char *dump = getenv("DGRP_STAMP_DUMP")) {
-        gru_params q = p;
-        const size_t bytes = (size_t)((groups + 1) / 2) * NW * 8 * 8;
-        DGRP_HIP(hipMalloc((void **)&q.stamps, bytes));
-        DGRP_HIP(hipMemset(q.stamps, 0, bytes));
-        hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)((groups + 1) / 2)), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH, stream, q, half_bytes);
-        DGRP_HIP(hipStreamSynchronize(stream));
-        std::vector<uint64_t> hst(bytes / 8);
-        DGRP_HIP(hipMemcpy(hst.data(), q.stamps, bytes, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(dump, "wb")) { fwrite(hst.data(), 1, bytes, f); fclose(f); }
-        (void)hipFree(q.stamps);
-        return DGRP_OK;
-    }
-#endif
     hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)((groups + 1) / 2)), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH, stream, p, half_bytes);
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;

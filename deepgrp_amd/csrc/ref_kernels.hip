@@ -18,10 +18,7 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // CELL 1: Keras LSTM, gate columns i|f|c|o, bias [4u]
 // A workgroup carries RP (window, strand) pairs through all T steps; thread j owns unit j of every pair, so each
 // element of U it loads is used RP times (the kernel is bound by L1/L2 reads of U otherwise).
-#ifndef DGRP_REF_RP
-#define DGRP_REF_RP 8
-#endif
-constexpr int RP = DGRP_REF_RP;
+constexpr int RP = 8;
 
 // NSL = unit slots per thread: thread j owns units j, j + 256, ... (one slot up to 256 units -- the yardstick of the fused kernels --,
 // more for the models beyond the fused kernels' sizes, which run on these kernels: api.hip, "fp32 path")

@@ -191,12 +191,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define SLOAD2A(a, pa, b, pb)                                                                                           \
     asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %3, off\n\ts_waitcnt vmcnt(0)"            \
                  : "=&a"(a), "=&a"(b) : "v"(pa), "v"(pb) : "memory")
-#ifndef DGRP_S64_RING
-#define DGRP_S64_RING 2
-#endif
-#ifndef DGRP_S64_DIAG
-#define DGRP_S64_DIAG 0
-#endif
 
 template <int NW, int MODE>               // NW = 32-unit slices of the model (5..8); waves = (NW + 1) / 2
 __global__ void __launch_bounds__(64 * ((NW + 1) / 2)) __attribute__((amdgpu_waves_per_eu(1, 1))) gru_stream64_kernel(const gru_params pin)
@@ -330,7 +324,7 @@ __global__ void __launch_bounds__(64 * ((NW + 1) / 2)) __attribute__((amdgpu_wav
 
     // The ring: blocks b = uh KS + k in the order the MFMAs take them (all k-steps of half 0, then of half 1), cyclic across time steps;
     // per block the four streamed fragments: 0 hi z, 1 lo z, 2 lo r, 3 lo h (stream slots 0, 3, 4, 5).
-    constexpr int D = DGRP_S64_RING, NB = 2 * KS;
+    constexpr int D = 2, NB = 2 * KS;
     static_assert(NB % D == 0, "the ring's slot of a block must not depend on the time step");
     uint4 q[D][4];
 #pragma unroll
@@ -359,11 +353,7 @@ __global__ void __launch_bounds__(64 * ((NW + 1) / 2)) __attribute__((amdgpu_wav
     acc_start(0);
 
     // one block of the MFMA stream: the nine MFMAs of (half UH, k-step k) with the ring's reloads; HOOK(i) = what goes behind MFMA i
-#if DGRP_S64_DIAG == 2
-#define S64_LD(slot, f) do { } while (0)
-#else
 #define S64_LD(slot, f) qk[slot] = frag(nsb, nf0 + (f))
-#endif
 #define S64_BLOCK(UH, HOOK)                                                                                              \
     {                                                                                                                   \
         const int b_ = (UH) * KS + k, nb_ = (b_ + D) % NB;                                                              \

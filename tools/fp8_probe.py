@@ -3,8 +3,9 @@
 
 The recurrence of the benchmark model is evaluated in torch on the GPU with the operand roundings of each candidate contraction and
 float64 accumulation -- an EMULATION of the arithmetic, not a kernel: it isolates what the operand formats cost.  Validated by its
-first rows, which re-create the measured table of tools/twopass_probe.py (three fp16 passes: median 3.6e-7, max 1.9e-5; a pass
-dropped: median 5e-5 .. 8e-5, max 8e-3 .. 1e-2 -- DESIGN.md 1).  Same windows as that probe and as bench.py's `accuracy` block: 4096
+first rows, which re-create the table of an earlier experiment that built the kernel with one of its passes dropped (three fp16
+passes: median 3.6e-7, max 1.9e-5; a pass dropped: median 5e-5 .. 8e-5, max 8e-3 .. 1e-2 -- the numbers are in DESIGN.md 1).  Same
+windows as that experiment and as bench.py's `accuracy` block: 4096
 windows spread over the 50 Mbp synthetic chromosome, the benchmark's fitted model, yardstick = the same recurrence in float64.
 
     python tools/fp8_probe.py [Mbp] [windows]
