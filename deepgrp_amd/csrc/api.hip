@@ -607,6 +607,29 @@ DGRP_EXPORT int dgrp_model_flags(const dgrp_model *m)
     return (m->onercp ? 1 : 0) | (m->precision == 1 ? 2 : 0) | (m->ref_only ? 4 : 0);
 }
 
+static_assert((int)dgrp_kernel::none == DGRP_KERNEL_NONE && (int)dgrp_kernel::wave == DGRP_KERNEL_WAVE &&
+              (int)dgrp_kernel::split2 == DGRP_KERNEL_SPLIT2 && (int)dgrp_kernel::stream64 == DGRP_KERNEL_STREAM64 &&
+              (int)dgrp_kernel::stream == DGRP_KERNEL_STREAM && (int)dgrp_kernel::split == DGRP_KERNEL_SPLIT &&
+              (int)dgrp_kernel::lstm == DGRP_KERNEL_LSTM && (int)dgrp_kernel::fused == DGRP_KERNEL_FUSED,
+              "DGRP_KERNEL_* (deepgrp_hip.h) follow dgrp_kernel (dgrp_model.h)");
+
+// what dgrp_forward_* would launch: the plan the launch itself takes (dgrp_gru_plan_for), copied out
+DGRP_EXPORT int dgrp_model_plan(const dgrp_model *m, int mode, int64_t step, int *kernel, int64_t *lds_bytes, int *ospan, int *avg_up)
+{
+    DGRP_REQUIRE(m, "dgrp_model_plan: NULL model");
+    DGRP_REQUIRE(kernel && lds_bytes && ospan && avg_up, "dgrp_model_plan: NULL output pointer");
+    DGRP_REQUIRE(mode >= 0 && mode <= 2, "dgrp_model_plan: mode %d (0 merged, 1 window probabilities, 2 attention pre-pass)", mode);
+    DGRP_REQUIRE(step >= 1, "dgrp_model_plan: step %lld < 1", (long long)step);
+    DGRP_REQUIRE(mode != 2 || m->attention, "dgrp_model_plan: mode 2 on a model without attention");
+    if (m->ref_only) {
+        *kernel = DGRP_KERNEL_FP32; *lds_bytes = 0; *ospan = 0; *avg_up = 0;
+        return DGRP_OK;
+    }
+    const dgrp_gru_plan plan = dgrp_gru_plan_for(m, mode, step);
+    *kernel = (int)plan.kernel; *lds_bytes = (int64_t)plan.lds; *ospan = plan.ospan; *avg_up = plan.avg_up;
+    return DGRP_OK;
+}
+
 DGRP_EXPORT int dgrp_model_set_precision(dgrp_model *m, int level)
 {
     DGRP_REQUIRE(m, "dgrp_model_set_precision: NULL model");

@@ -12,7 +12,7 @@ PyTorch is used only to own device memory and the stream.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -39,6 +39,18 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _np_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# DGRP_KERNEL_* (include/deepgrp_hip.h) by value
+KERNEL_NAMES = ("none", "wave", "split2", "stream64", "stream", "split", "lstm", "fused", "fp32")
+
+
+class KernelPlan(NamedTuple):
+    """DeviceModel.plan: kernel name (KERNEL_NAMES), dynamic LDS bytes, rows of the merged-output LDS image (0: none), avg[t] row length."""
+    kernel: str
+    lds: int
+    ospan: int
+    avg_up: int
 
 
 class DeviceModel:
@@ -145,6 +157,14 @@ class DeviceModel:
         v = C.c_void_p()
         check(lib().dgrp_model_view(self.handle, int(level), C.byref(v)), "dgrp_model_view")
         return v
+
+    def plan(self, mode: int, step: int, handle=None) -> "KernelPlan":
+        """dgrp_model_plan: the recurrent kernel a launch of `mode` (0 merged, 1 window probabilities, 2 attention pre-pass) with
+        step `step` would run on this handle (or on `handle`, a view) at its current precision level, and its LDS carve."""
+        k, lds, ospan, avg_up = C.c_int(), C.c_int64(), C.c_int(), C.c_int()
+        check(lib().dgrp_model_plan(handle if handle is not None else self.handle, int(mode), int(step), C.byref(k), C.byref(lds),
+                                    C.byref(ospan), C.byref(avg_up)), "dgrp_model_plan")
+        return KernelPlan(KERNEL_NAMES[k.value], lds.value, ospan.value, avg_up.value)
 
     def close(self):
         if getattr(self, "handle", None):

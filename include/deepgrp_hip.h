@@ -161,6 +161,24 @@ int dgrp_model_set_precision(dgrp_model *m, int level);
  * different levels can run records on a pool of host threads without touching each other's setting. */
 int dgrp_model_view(const dgrp_model *m, int level, dgrp_model **out);
 
+/* (addition) The recurrent kernel a launch of `mode` (0 merged, 1 window probabilities, 2 attention pre-pass) with step `step`
+ * would run on this handle at its current precision level, and its carve (diagnostic; host only, no device work).  *kernel is a
+ * DGRP_KERNEL_* value; *lds_bytes the dynamic LDS of the launch (of a workgroup, of a wave for gru_wave_kernel, of one of the two
+ * row tiles for gru_split2_kernel); *ospan the rows of the merged-output LDS image (mode 0; 0 = no image, every window merges
+ * into HBM); *avg_up the row length of the avg[t] spill (mode 2).  A model on the fp32 path gives DGRP_KERNEL_FP32 and zeros.
+ * DGRP_SPLIT_ONE_TILE in the environment is read as by a launch.  DGRP_EINVAL for a NULL argument, a mode outside 0..2,
+ * step < 1, or mode 2 on a model without attention. */
+#define DGRP_KERNEL_NONE 0       /* the window does not fit the LDS: the launch is refused */
+#define DGRP_KERNEL_WAVE 1       /* gru_wave_kernel (GRU up to 64 units, split operands) */
+#define DGRP_KERNEL_SPLIT2 2     /* gru_split2_kernel (GRU 97-128 units, split operands) */
+#define DGRP_KERNEL_STREAM64 3   /* gru_stream64_kernel (GRU 129-256 units, split operands) */
+#define DGRP_KERNEL_STREAM 4     /* rnn_split_stream_kernel (GRU 129-256 units, LSTM) */
+#define DGRP_KERNEL_SPLIT 5      /* gru_split_kernel (GRU up to 128 units, split operands) */
+#define DGRP_KERNEL_LSTM 6       /* lstm_fused_kernel (LSTM up to 128 units, fp16 operands) */
+#define DGRP_KERNEL_FUSED 7      /* gru_fused_kernel (GRU up to 256 units, fp16 operands) */
+#define DGRP_KERNEL_FP32 8       /* the plain-fp32 kernels of ref_kernels.hip (dgrp_model_flags bit 2) */
+int dgrp_model_plan(const dgrp_model *m, int mode, int64_t step, int *kernel, int64_t *lds_bytes, int *ospan, int *avg_up);
+
 /* ---- A4: model.predict_on_batch (deepgrp/prediction.py:106)
  * Bytes of scratch HBM dgrp_forward_* needs for `nw` windows in one call. */
 int64_t dgrp_forward_workspace_bytes(const dgrp_model *m, int64_t nw);

@@ -17,6 +17,14 @@ def info4():
     return (C.c_int64 * 4)()
 
 
+def plan_out(null=None):
+    """The four output pointers of dgrp_model_plan (kernel, lds_bytes, ospan, avg_up), the one at index `null` NULL."""
+    out = [C.pointer(C.c_int()), C.pointer(C.c_int64()), C.pointer(C.c_int()), C.pointer(C.c_int())]
+    if null is not None:
+        out[null] = None
+    return out
+
+
 CASES = [
     ("dgrp_strip_n", lambda: (None, 5, i64x1, i64x1), "dgrp_strip_n"),
     ("dgrp_strip_n", lambda: (P, -1, i64x1, i64x1), "dgrp_strip_n"),
@@ -83,6 +91,16 @@ CASES = [
     ("dgrp_filter_segments", lambda: (P, P, -1, 50, None), "negative length"),
     ("dgrp_filter_segments", lambda: (None, P, 10, 50, None), "NULL pointer"),
     ("dgrp_filter_segments", lambda: (P, P, 1 << 39, 50, None), "too long"),
+    # (mode 2 on a model without attention needs a model: tests/test_gpu_classes.py)
+    ("dgrp_model_plan", lambda: (None, 0, 50, *plan_out()), "NULL model"),
+    ("dgrp_model_plan", lambda: (P, 0, 50, *plan_out(0)), "NULL output"),
+    ("dgrp_model_plan", lambda: (P, 0, 50, *plan_out(1)), "NULL output"),
+    ("dgrp_model_plan", lambda: (P, 0, 50, *plan_out(2)), "NULL output"),
+    ("dgrp_model_plan", lambda: (P, 0, 50, *plan_out(3)), "NULL output"),
+    ("dgrp_model_plan", lambda: (P, -1, 50, *plan_out()), "mode -1"),
+    ("dgrp_model_plan", lambda: (P, 3, 50, *plan_out()), "mode 3"),
+    ("dgrp_model_plan", lambda: (P, 1, 0, *plan_out()), "step 0"),
+    ("dgrp_model_plan", lambda: (P, 2, -5, *plan_out()), "step -5"),
 ]
 
 

@@ -244,22 +244,25 @@ def test_predict_on_batch_keras_style(dev, orc):
     dm.close()
 
 
-@pytest.mark.parametrize("N,T,s,B,u,attention", [(1050, 200, 50, 4, 128, False), (1001, 200, 50, 5, 64, False),
-                                                  (5000, 200, 50, 7, 128, False), (5000, 200, 50, 256, 128, False),
-                                                  (777, 30, 4, 10, 32, True), (200, 200, 50, 4, 32, False),
-                                                  (201, 200, 50, 4, 32, False), (3000, 100, 300, 3, 32, False),
-                                                  (3000, 500, 25, 256, 256, True),
-                                                  # the row kernel's four-window workgroups across the partial-last-batch boundary
-                                                  # (nwin % 4 != 0, nfull * B % 4 != 0: an idle fourth wave, the image's flush guard)
-                                                  (1500, 100, 10, 7, 128, True), (1507, 100, 10, 5, 160, True), (1203, 90, 10, 9, 72, True),
-                                                  # gru_stream64_kernel's own merge (image, rows outside it, short last batch), 5..8 slices
-                                                  (2100, 120, 20, 6, 192, False), (1800, 90, 15, 4, 224, False), (1333, 80, 10, 3, 136, False),
-                                                  (2600, 500, 25, 7, 256, False),
-                                                  # gru_wave_kernel: 16-window groups of two 8-window tiles, every image / no-image path
-                                                  (2000, 200, 50, 7, 36, False), (2013, 200, 50, 5, 44, True), (1000, 60, 3, 11, 60, True),
-                                                  (9000, 342, 50, 256, 60, True), (9000, 342, 50, 13, 48, False), (1700, 1500, 50, 3, 20, False),
-                                                  # the fp32 path's merge: runs of equally spaced rows, the short last batch elsewhere
-                                                  (1050, 200, 50, 4, 300, False), (2003, 100, 10, 7, 288, True)])
+MERGE_CASES = [(1050, 200, 50, 4, 128, False), (1001, 200, 50, 5, 64, False),
+                (5000, 200, 50, 7, 128, False), (5000, 200, 50, 256, 128, False),
+                (777, 30, 4, 10, 32, True), (200, 200, 50, 4, 32, False),
+                (201, 200, 50, 4, 32, False), (3000, 100, 300, 3, 32, False),
+                (3000, 500, 25, 256, 256, True),
+                # the row kernel's four-window workgroups across the partial-last-batch boundary
+                # (nwin % 4 != 0, nfull * B % 4 != 0: an idle fourth wave, the image's flush guard)
+                (1500, 100, 10, 7, 128, True), (1507, 100, 10, 5, 160, True), (1203, 90, 10, 9, 72, True),
+                # gru_stream64_kernel's own merge (image, rows outside it, short last batch), 5..8 slices
+                (2100, 120, 20, 6, 192, False), (1800, 90, 15, 4, 224, False), (1333, 80, 10, 3, 136, False),
+                (2600, 500, 25, 7, 256, False),
+                # gru_wave_kernel: 16-window groups of two 8-window tiles, every image / no-image path
+                (2000, 200, 50, 7, 36, False), (2013, 200, 50, 5, 44, True), (1000, 60, 3, 11, 60, True),
+                (9000, 342, 50, 256, 60, True), (9000, 342, 50, 13, 48, False), (1700, 1500, 50, 3, 20, False),
+                # the fp32 path's merge: runs of equally spaced rows, the short last batch elsewhere
+                (1050, 200, 50, 4, 300, False), (2003, 100, 10, 7, 288, True)]
+
+
+@pytest.mark.parametrize("N,T,s,B,u,attention", MERGE_CASES)
 def test_forward_merge_placement_exact(dev, orc, L, N, T, s, B, u, attention):
     """The fused max-merge must equal get_max applied batch by batch to the SAME probabilities
     (bit for bit), incl. the partial-last-batch offset, and be within 1e-3 of the
