@@ -39,7 +39,7 @@ __device__ __forceinline__ float np_expf(float x)
 {
     if (x != x) return x;
     if (x >= 88.72283905206835f) return INFINITY;
-    if (x <= -103.97208f) return 0.0f;
+    if (x <= -103.97208404541015625f) return 0.0f;       // numpy's xmin, 0xc2cff1b5 (-103.97208f is one ulp above)
     const float q = rintf(x * 1.44269504088896340736f);
     float r = fmaf(q, -6.93145752e-1f, x);
     r = fmaf(q, -1.42860677e-6f, r);
@@ -112,10 +112,26 @@ __global__ void __launch_bounds__(256) softmax_labels_kernel(const float *__rest
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthreads) {
         // (the exponentials twice -- a deterministic routine -- instead of an array of them: any number of classes in registers)
-        float sum = 0.0f;
-        for (int c = 0; c < C; ++c) {
-            const float ec = np_expf(a[i * C + c] - gmax);
-            sum = c == 0 ? ec : sum + ec;                     // numpy folds a short row left to right
+        // e_x.sum(axis=1) in numpy's order (pairwise_sum of a row of at most 128): fewer than 8 columns fold left to right;
+        // from 8 on, 8 accumulators take columns k, k+8, k+16, ... of the whole blocks of 8, are combined as
+        // ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), and the C % 8 remaining columns are added to that in order
+        const float *row = a + i * C;
+        float sum;
+        if (C < 8) {
+            sum = np_expf(row[0] - gmax);
+            for (int c = 1; c < C; ++c) sum = sum + np_expf(row[c] - gmax);
+        } else {
+            float r[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) r[k] = np_expf(row[k] - gmax);
+            const int whole = C - C % 8;
+            int c = 8;
+            for (; c < whole; c += 8) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) r[k] = r[k] + np_expf(row[c + k] - gmax);
+            }
+            sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+            for (; c < C; ++c) sum = sum + np_expf(row[c] - gmax);
         }
         int best = 0;
         float bv = __fdiv_rn(np_expf(a[i * C] - gmax), sum);

@@ -121,8 +121,8 @@ def softmax(array: np.ndarray) -> np.ndarray:
     """Softmax with the global maximum subtracted (prediction.py:62-65)."""
     array = np.asarray(array)
     dev = require_gpu()
-    if array.dtype != np.float32 or array.ndim != 2 or array.shape[1] > 16:
-        # other dtypes / wider rows: same expression in the input precision on the device
+    if array.dtype != np.float32 or array.ndim != 2 or array.shape[1] > 64:
+        # other dtypes / rows wider than DGRP_MAXC: same expression in the input precision on the device (not bit-exact)
         x = torch.from_numpy(np.ascontiguousarray(array)).to(dev)
         e_x = torch.exp(x - x.max())
         return (e_x / e_x.sum(dim=1, keepdim=True)).cpu().numpy()

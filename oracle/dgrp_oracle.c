@@ -151,7 +151,8 @@ ORC_API void orc_merge_all(float *out, int64_t N, const float *probs, int64_t nw
  * (numpy/core/src/umath/loops_exponent_log.dispatch.c.src; numpy is a
  * dependency of the reference, pyproject.toml, not part of its tree).  They were
  * checked bit-for-bit against np.log / np.exp of the installed numpy on 6e6
- * random float32 values each (tests/test_oracle_numpy_math.py repeats that).
+ * random float32 values each (test_numpy_math in tests/test_oracle_golden.py repeats that;
+ * tests/test_oracle_post_numerics.py checks whole arrays through orc_scores / orc_softmax_argmax).
  */
 static const float LP1 = 9.999999999999998702752e-01f, LP2 = 2.112677543073053063722e+00f,
                    LP3 = 1.480000633576506585156e+00f, LP4 = 3.808837741388407920751e-01f,
@@ -184,7 +185,7 @@ ORC_API float orc_np_expf(float x)
 {
     if (isnan(x)) return x;
     if (x >= 88.72283905206835f) return INFINITY;
-    if (x <= -103.97208f) return 0.0f;
+    if (x <= -103.97208404541015625f) return 0.0f;       /* numpy's xmin, 0xc2cff1b5 (-103.97208f is one ulp above) */
     float q = rintf(x * 1.44269504088896340736f);
     float r = fmaf(q, -6.93145752e-1f, x);
     r = fmaf(q, -1.42860677e-6f, r);
@@ -229,9 +230,23 @@ ORC_API void orc_softmax_argmax(const float *a, int64_t N, int64_t C, float *out
         if (a[i] > gmax) gmax = a[i];
     float *row = (float *)malloc(sizeof(float) * (size_t)(C > 0 ? C : 1));
     for (int64_t i = 0; i < N; ++i) {
-        /* numpy sums a length-C row pairwise; for C < 8 that is a plain left fold */
-        float sum = 0.0f;
-        for (int64_t c = 0; c < C; ++c) { row[c] = orc_np_expf(a[i * C + c] - gmax); sum += row[c]; }
+        /* numpy sums a length-C row with pairwise_sum, which for C <= 128 (DGRP_MAXC is 64) is: a left fold for C < 8;
+         * otherwise 8 accumulators r[k] = a[k] + a[k+8] + ... over the whole blocks of 8, combined as
+         * ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the C % 8 remaining columns added in order */
+        for (int64_t c = 0; c < C; ++c) row[c] = orc_np_expf(a[i * C + c] - gmax);
+        float sum;
+        if (C < 8) {
+            sum = row[0];
+            for (int64_t c = 1; c < C; ++c) sum += row[c];
+        } else {
+            float r[8];
+            for (int k = 0; k < 8; ++k) r[k] = row[k];
+            int64_t c = 8;
+            for (; c < C - C % 8; c += 8)
+                for (int k = 0; k < 8; ++k) r[k] += row[c + k];
+            sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+            for (; c < C; ++c) sum += row[c];
+        }
         int64_t best = 0;
         float bv = row[0] / sum;
         if (out) out[i * C] = bv;
