@@ -9,6 +9,7 @@ Differences, all additive:
     the GPUs and rank 0 writes the rows in input order;
   * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
     (deepgrp_amd/masking.py);
+  * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
 """
 from __future__ import annotations
@@ -48,6 +49,42 @@ def _predict(dnasequence: str, model, options, step_size: int, use_mss: bool) ->
         _LOG.debug("Applying MSS.")
     labels = pipe.labels(merged)
     return labels.cpu().numpy().astype(np.int64), start_pos
+
+
+def _records_of(filename):
+    """(header, record) pairs of one input as `predict` reads it: a FASTA file (device ingest), '-' or another stream (the
+    reference's line loop), or a one-hot `<name>.gz.npz`."""
+    import torch
+    from .fasta import DeviceRecord, read_multi_fasta_device
+    if filename.endswith(".npz") and os.path.isfile(filename):
+        # (addition, SURVEY 8f N4) the one-hot `<fasta>.gz.npz` that `preprocess_sequence` writes for training
+        # (deepgrp/_scripts/preprocess_sequence.py:71-78), as an alternative input: ONE record, named after the file
+        # (the format keeps no header); same stripping of leading/trailing N as one_hot_encode_dna_sequence
+        from .preprocessing import load_onehot_npz
+        fwd = load_onehot_npz(filename)
+        if fwd.size and not (np.isin(fwd, (0, 1)).all() and (fwd.sum(axis=0) == 1).all()):
+            raise ValueError(f"{filename}: `fwd` is not one-hot")
+        idx = fwd.argmax(axis=0).astype(np.uint8)
+        header = os.path.basename(filename)[:-len(".npz")]
+        keep = np.flatnonzero(idx != 4)
+        if idx.size == 0:
+            return
+        if keep.size == 0:
+            yield header, DeviceRecord(int(idx.size), None, -int(idx.size))        # all N: the reference raises (sequence.pyx:32)
+            return
+        st, en = int(keep[0]), int(keep[-1]) + 1
+        d_idx = torch.from_numpy(np.ascontiguousarray(idx[st:en])).to(torch.device("cuda", torch.cuda.current_device()))
+        yield header, DeviceRecord(st, d_idx, en - st)
+        return
+    if filename == "-" or not os.path.isfile(filename):
+        filestream = sys.stdin if filename == "-" else open(filename, "r")
+        try:
+            yield from _read_multi_fasta(filestream)
+        finally:
+            if filename != "-":
+                filestream.close()
+    else:
+        yield from read_multi_fasta_device(filename)
 
 
 class _RowsByRecord:
@@ -151,11 +188,34 @@ class CommandLineParser:
                              help="multi-GPU only: spread the windows of EVERY record over all GPUs (for a few huge "
                                   "records) instead of sharding whole records")
         _add_mask_options(predict, suppress=True)
+        evaluate = subparsers.add_parser(
+            name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+            description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
+                        "confusion matrix, TPR, PPV, F1 and MCC over the bases from the first to the last non-N base of every "
+                        "record, and element counts.  Truth of a base: the smallest kept repeat number of the annotation rows that "
+                        "cover it (0: none).  Unlike the reference's HPO objective (deepgrp/optimization.py:52-69) the last non-N "
+                        "base is evaluated too (its drop_start_end_n drops it) and no extra filter_segments pass runs: the TSV "
+                        "users get is what is measured.")
+        evaluate.add_argument("model", type=str, help="Keras model in HDF5 format")
+        evaluate.add_argument("annotation", type=str, help="table as parse_rm writes it: contig, 0-based begin, exclusive end, "
+                                                           "repeat number, further columns ignored")
+        evaluate.add_argument("FASTA", nargs="+", type=str, help="inputs as for predict: FASTA files, '-', `<name>.gz.npz`; a "
+                                                                 "record is matched to the annotation by the first word of its "
+                                                                 "header (.npz: the file name up to the first '.')")
+        evaluate.add_argument("--no_use_mss", "-m", action="store_true", help="Disable maximum scoring segment algorithm")
+        evaluate.add_argument("--fast", action="store_true", help="fp16-operand fused kernels, as for predict")
+        evaluate.add_argument("--repeats", type=_class_list, default=None,
+                              help="comma-separated repeat numbers to keep from the annotation (default: 1..C-1 of the model)")
+        evaluate.add_argument("--min_overlap", type=float, default=0.5,
+                              help="an element is found (a predicted row supported) when at least this fraction of its bases "
+                                   "carries its class on the other side, in (0, 1]")
+        evaluate.add_argument("--output", type=str, default="-", help="TSV report ('-' = standard output)")
+        evaluate.add_argument("--json", type=str, default=None, help="also write every figure as JSON here")
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
         # README form `deepgrp <modelfile> <fastafile>`: insert the sub-command before the first positional
-        if not any(a in ("predict", "train", "verify") for a in argv):
+        if not any(a in ("predict", "train", "verify", "evaluate") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes"}
             i = 0
@@ -224,46 +284,13 @@ class CommandLineParser:
         _LOG.info("Model loading finished successfully!")
         if masks is not None:
             CommandLineParser._check_mask_classes(args, model.output_shape[2])
-        pipe = ContigPipeline(model, args.step_size, options.batch_size, options.min_mss_len, options.xdrop_len,
-                              use_mss=not args.no_use_mss, precise=getattr(args, "precise", False),
-                              fast=getattr(args, "fast", False))
-        _LOG.info("Forward kernel: %s", "plain fp32 kernels (more units than the fused kernels take)" if getattr(model, "fp32_only", False)
-                  else "fused, split operands (fp32-grade)" if pipe.split else "fused, fp16 operands")
+        pipe = CommandLineParser._pipeline(args, options, model)
         outstream = None
         if rank == 0:
             # (headers are carried as bytes through surrogateescape: a Latin-1 header must reach the file as the bytes it was)
             outstream = sys.stdout if args.output == "-" else open(args.output, "w", errors="surrogateescape")
 
-        def records_of(filename):
-            if filename.endswith(".npz") and os.path.isfile(filename):
-                # (addition) the one-hot `<fasta>.gz.npz` that `preprocess_sequence` writes for training
-                # (deepgrp/_scripts/preprocess_sequence.py:71-78), as an alternative input: ONE record, named after the file
-                # (the format keeps no header); same stripping of leading/trailing N as one_hot_encode_dna_sequence
-                from .preprocessing import load_onehot_npz
-                fwd = load_onehot_npz(filename)
-                if fwd.size and not (np.isin(fwd, (0, 1)).all() and (fwd.sum(axis=0) == 1).all()):
-                    raise ValueError(f"{filename}: `fwd` is not one-hot")
-                idx = fwd.argmax(axis=0).astype(np.uint8)
-                header = os.path.basename(filename)[:-len(".npz")]
-                keep = np.flatnonzero(idx != 4)
-                if idx.size == 0:
-                    return
-                if keep.size == 0:
-                    yield header, DeviceRecord(int(idx.size), None, -int(idx.size))        # all N: the reference raises (sequence.pyx:32)
-                    return
-                st, en = int(keep[0]), int(keep[-1]) + 1
-                d_idx = torch.from_numpy(np.ascontiguousarray(idx[st:en])).to(torch.device("cuda", torch.cuda.current_device()))
-                yield header, DeviceRecord(st, d_idx, en - st)
-                return
-            if filename == "-" or not os.path.isfile(filename):
-                filestream = sys.stdin if filename == "-" else open(filename, "r")
-                try:
-                    yield from _read_multi_fasta(filestream)
-                finally:
-                    if filename != "-":
-                        filestream.close()
-            else:
-                yield from read_multi_fasta_device(filename)
+        records_of = _records_of
 
         runner = RecordRunner(pipe)
 
@@ -343,6 +370,17 @@ class CommandLineParser:
             # interpreter shutdown)
             if rank == 0 and args.output != "-":
                 outstream.close()
+
+    @staticmethod
+    def _pipeline(args, options, model):
+        """The record pipeline of `predict`'s flags (-s -l -x -b -m --fast --precise)."""
+        from .pipeline import ContigPipeline
+        pipe = ContigPipeline(model, args.step_size, options.batch_size, options.min_mss_len, options.xdrop_len,
+                              use_mss=not args.no_use_mss, precise=getattr(args, "precise", False),
+                              fast=getattr(args, "fast", False))
+        _LOG.info("Forward kernel: %s", "plain fp32 kernels (more units than the fused kernels take)" if getattr(model, "fp32_only", False)
+                  else "fused, split operands (fp32-grade)" if pipe.split else "fused, fp16 operands")
+        return pipe
 
     _last_count = 0
 
@@ -583,6 +621,53 @@ class CommandLineParser:
             raise
         if rank == 0:
             os.replace(tmp, final)
+
+    @staticmethod
+    def evaluate(args: argparse.Namespace, options) -> None:
+        """Score `predict`'s rows against an annotation (deepgrp_amd/evaluation.py): TSV report, optionally JSON."""
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
+        if getattr(args, "mask_dir", None) is not None:
+            sys.exit("--mask_dir belongs to predict, not evaluate")
+        if not 0.0 < args.min_overlap <= 1.0:
+            sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
+        import json
+
+        from . import model as dgmodel
+        from .evaluation import AnnotationError, NoMatchError, evaluate, tsv_report, read_annotation
+        # host work first: the model's class count, the repeat numbers and the annotation are checked before the GPU is touched
+        weights = dgmodel.read_keras_hdf5(args.model)
+        classes = int(weights["ff_kernel"].shape[-1])
+        repeats = sorted(set(args.repeats)) if args.repeats is not None else list(range(1, classes))
+        bad = [r for r in repeats if not 0 < r < classes]
+        if bad:
+            sys.exit(f"--repeats: {bad[0]} is not a repeat class of this model (1..{classes - 1})")
+        try:
+            annotation = read_annotation(args.annotation, repeats)
+        except AnnotationError as e:
+            sys.exit(str(e))
+        model = dgmodel.device_model(weights)
+        options.vecsize = model.input_shape[1]
+        pipe = CommandLineParser._pipeline(args, options, model)
+        info = dict(model=args.model, annotation=args.annotation, inputs=list(args.FASTA), repeats=repeats,
+                    options=dict(step_size=args.step_size, min_mss_length=args.min_mss_length, xdrop_length=args.xdrop_length,
+                                 batch_size=args.batch_size, use_mss=not args.no_use_mss, fast=bool(args.fast),
+                                 min_overlap=args.min_overlap))
+        try:
+            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info)
+        except NoMatchError as e:
+            sys.exit(str(e))
+        text = tsv_report(rep)
+        if args.output == "-":
+            sys.stdout.write(text)
+            sys.stdout.flush()
+        else:
+            with open(args.output, "w") as fh:
+                fh.write(text)
+        if args.json is not None:
+            with open(args.json, "w") as fh:
+                json.dump(rep, fh, indent=1, allow_nan=False)
+                fh.write("\n")
 
     @staticmethod
     def verify(args: argparse.Namespace, options) -> None:

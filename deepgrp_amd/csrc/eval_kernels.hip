@@ -97,3 +97,289 @@ DGRP_EXPORT int dgrp_filter_segments(const int8_t *d_labels, int8_t *d_out, int6
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// evaluate: label rows painted onto a flat per-base buffer, and per-row hit counts against such a buffer.  Records lie back to back
+// in one int8 buffer (record r: [off[r], off[r] + len[r]), its first base has the original coordinate origin[r]); rows are
+// dgrp_segment in original coordinates, clipped to their record.  Work is shared out by LENGTH, not by row: an exclusive scan of
+// the clipped lengths gives every row its place on one line of positions, and workgroup b takes positions
+// [b * EVAL_SLICE, (b + 1) * EVAL_SLICE) of that line (rows run from 10 bp to megabases).
+// ------------------------------------------------------------------------------------------------------------------------------
+#include "scan.h"
+#include <vector>
+
+namespace {
+
+#define EVAL_SLICE 8192           // positions per workgroup: 256 lanes x 32, lane-interleaved (a wave's stores are 64 adjacent bytes)
+#define EVAL_LDS_ROWS 2048        // hits: the slice's per-row counters in LDS; a slice crossing more rows adds to d_hits directly
+#define EVAL_HEAD 2048            // workspace head: flag + first bad row at 0, clipped length per label (128 x u64) at 1024
+
+__device__ __forceinline__ int64_t eval_record_of(const int64_t *__restrict__ row_off, int64_t nrec, int64_t i)
+{
+    int64_t lo = 0, hi = nrec;                    // largest r < nrec with row_off[r] <= i
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (row_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// row j's span on the record: [cs, cs + cl) of its bases (cl = 0 when the row misses the record)
+__device__ __forceinline__ void eval_clip(const dgrp_segment &q, int64_t origin, int64_t len, int64_t &cs, int64_t &cl)
+{
+    int64_t a = q.start - origin, e = q.end - origin;
+    a = a < 0 ? 0 : (a > len ? len : a);
+    e = e < 0 ? 0 : (e > len ? len : e);
+    cs = a;
+    cl = e > a ? e - a : 0;
+}
+
+// largest j in [lo, hi) with ex[j] <= p, given ex[lo] <= p < ex[hi]
+__device__ __forceinline__ int64_t eval_row_of(const uint64_t *__restrict__ ex, int64_t lo, int64_t hi, uint64_t p)
+{
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ex[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// one lane per row: 0 <= start <= end and 1 <= label <= 127, else g[0] |= 1 and g[1] = smallest bad row; tot[label] += clipped length
+// (summed per workgroup in LDS first: a handful of labels would otherwise serialise one global atomic per row)
+__global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__restrict__ rows, const int64_t *__restrict__ row_off,
+                                                         int64_t nrec, const int64_t *__restrict__ len,
+                                                         const int64_t *__restrict__ origin, unsigned long long *__restrict__ g,
+                                                         unsigned long long *__restrict__ tot)
+{
+    __shared__ unsigned long long s_tot[128];
+    if (threadIdx.x < 128) s_tot[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int64_t i = row_off[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < row_off[nrec]) {
+        const dgrp_segment q = rows[i];
+        if (q.start < 0 || q.end < q.start || q.label < 1 || q.label > 127) {
+            atomicOr(&g[0], 1ull);
+            atomicMin(&g[1], (unsigned long long)i);
+        } else {
+            const int64_t r = eval_record_of(row_off, nrec, i);
+            int64_t cs, cl;
+            eval_clip(q, origin[r], len[r], cs, cl);
+            if (cl) atomicAdd(&s_tot[q.label], (unsigned long long)cl);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 128 && s_tot[threadIdx.x]) atomicAdd(&tot[threadIdx.x], s_tot[threadIdx.x]);
+}
+
+// one lane per row j (= row row_off[0] + j): cl[j] = its clipped length if its label is `label` (0: any), else 0; dst[j] = the
+// buffer position of its first clipped base
+__global__ void __launch_bounds__(256) eval_span_kernel(const dgrp_segment *__restrict__ rows, const int64_t *__restrict__ row_off,
+                                                        int64_t nrec, const int64_t *__restrict__ off, const int64_t *__restrict__ len,
+                                                        const int64_t *__restrict__ origin, int label, uint64_t *__restrict__ cl,
+                                                        int64_t *__restrict__ dst)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = row_off[0] + j;
+    if (i >= row_off[nrec]) return;
+    const dgrp_segment q = rows[i];
+    const int64_t r = eval_record_of(row_off, nrec, i);
+    int64_t cs, n;
+    eval_clip(q, origin[r], len[r], cs, n);
+    cl[j] = (label == 0 || q.label == label) ? (uint64_t)n : 0;
+    dst[j] = off[r] + cs;
+}
+
+// ex[0..n] = exclusive scan of the rows' lengths in this pass (ex[n] = total): every position of the slice gets `label`
+__global__ void __launch_bounds__(256) eval_paint_kernel(int8_t *__restrict__ labels, const uint64_t *__restrict__ ex,
+                                                         const int64_t *__restrict__ dst, int64_t n, int label)
+{
+    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
+    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;
+    const uint64_t p0 = s0 + threadIdx.x;
+    if (p0 >= s1) return;
+    int64_t j = eval_row_of(ex, 0, n, p0);
+    uint64_t jst = ex[j], jend = ex[j + 1];
+    for (uint64_t p = p0; p < s1; p += 256) {
+        while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
+        labels[dst[j] + (int64_t)(p - jst)] = (int8_t)label;
+    }
+}
+
+// hits[j] += bases of row j's clipped span whose label equals row j's: per-lane counts per row, gathered in LDS per row of the
+// slice, then one 64-bit atomic per (workgroup, row) with hits
+__global__ void __launch_bounds__(256) eval_hits_kernel(const int8_t *__restrict__ labels, const uint64_t *__restrict__ ex,
+                                                        const int64_t *__restrict__ dst, const dgrp_segment *__restrict__ rows,
+                                                        int64_t n, unsigned long long *__restrict__ hits)
+{
+    __shared__ unsigned cnt[EVAL_LDS_ROWS];
+    __shared__ int64_t s_r0, s_r1;
+    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
+    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;    // (s0 < total: the grid covers the line exactly)
+    if (threadIdx.x == 0) {
+        s_r0 = eval_row_of(ex, 0, n, s0);
+        s_r1 = eval_row_of(ex, s_r0, n, s1 - 1);
+    }
+    for (int k = threadIdx.x; k < EVAL_LDS_ROWS; k += 256) cnt[k] = 0u;
+    __syncthreads();
+    const int64_t r0 = s_r0, r1 = s_r1;
+    const bool staged = r1 - r0 < EVAL_LDS_ROWS;
+    const uint64_t p0 = s0 + threadIdx.x;
+    if (p0 < s1) {
+        int64_t j = eval_row_of(ex, r0, r1 + 1, p0);
+        uint64_t jst = ex[j], jend = ex[j + 1];
+        int lab = rows[j].label;
+        unsigned c = 0;
+        for (uint64_t p = p0; p < s1; p += 256) {
+            if (jend <= p) {
+                if (c) {
+                    if (staged) atomicAdd(&cnt[j - r0], c);
+                    else atomicAdd(&hits[j], (unsigned long long)c);
+                }
+                c = 0;
+                while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
+                lab = rows[j].label;
+            }
+            c += labels[dst[j] + (int64_t)(p - jst)] == lab ? 1u : 0u;
+        }
+        if (c) {
+            if (staged) atomicAdd(&cnt[j - r0], c);
+            else atomicAdd(&hits[j], (unsigned long long)c);
+        }
+    }
+    __syncthreads();
+    if (staged) {
+        for (int64_t k = threadIdx.x; k <= r1 - r0; k += 256) {
+            const unsigned v = cnt[k];
+            if (v) atomicAdd(&hits[r0 + k], (unsigned long long)v);
+        }
+    }
+}
+
+struct eval_plan {
+    std::vector<int64_t> tab;          // off[nrec], len[nrec], origin[nrec], row_off[nrec + 1]
+    int64_t nrows = 0;
+    int64_t *d_off = nullptr, *d_len, *d_origin, *d_row_off, *d_dst;
+    uint64_t *d_cl = nullptr, *d_tiles = nullptr;
+    unsigned long long tot[128];       // clipped length per label
+};
+
+// argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written
+static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                        const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes,
+                        hipStream_t stream, eval_plan &pl)
+{
+    DGRP_REQUIRE(nrec >= 0 && h_row_off && (nrec == 0 || (h_off && h_len && h_origin)), "%s: bad arguments", what);
+    DGRP_REQUIRE(h_row_off[0] >= 0, "%s: negative row offset", what);
+    pl.tab.assign((size_t)(4 * nrec + 1), 0);
+    int64_t *off = pl.tab.data(), *len = off + nrec, *origin = len + nrec, *row_off = origin + nrec;
+    for (int64_t r = 0; r < nrec; ++r) {
+        DGRP_REQUIRE(h_off[r] >= 0 && h_len[r] >= 0 && h_origin[r] >= 0, "%s: negative offset, length or origin (record %lld)", what,
+                     (long long)r);
+        DGRP_REQUIRE(h_row_off[r + 1] >= h_row_off[r], "%s: row offsets must ascend (record %lld)", what, (long long)r);
+        off[r] = h_off[r];
+        len[r] = h_len[r];
+        origin[r] = h_origin[r];
+    }
+    for (int64_t r = 0; r <= nrec; ++r) row_off[r] = h_row_off[r];
+    pl.nrows = row_off[nrec] - row_off[0];
+    for (int k = 0; k < 128; ++k) pl.tot[k] = 0ull;
+    if (pl.nrows == 0 || nrec == 0) return DGRP_OK;
+    DGRP_REQUIRE(d_rows && d_work, "%s: NULL pointer", what);
+    if (work_bytes < dgrp_eval_workspace_bytes(nrec, pl.nrows)) {
+        dgrp_set_error("%s: workspace too small", what);
+        return DGRP_ENOMEM;
+    }
+    unsigned long long *g = (unsigned long long *)d_work, *d_tot = (unsigned long long *)((char *)d_work + 1024);
+    char *p = (char *)d_work + EVAL_HEAD;
+    pl.d_off = (int64_t *)p;
+    pl.d_len = pl.d_off + nrec;
+    pl.d_origin = pl.d_len + nrec;
+    pl.d_row_off = pl.d_origin + nrec;
+    p += dgrp_align_up((4 * nrec + 1) * 8, 256);
+    pl.d_cl = (uint64_t *)p;
+    p += dgrp_align_up((pl.nrows + 1) * 8, 256);
+    pl.d_dst = (int64_t *)p;
+    p += dgrp_align_up(pl.nrows * 8, 256);
+    pl.d_tiles = (uint64_t *)p;
+    const unsigned long long init[2] = { 0ull, ~0ull };
+    DGRP_HIP(hipMemcpyAsync(g, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    DGRP_HIP(hipMemsetAsync(d_tot, 0, 128 * 8, stream));
+    DGRP_HIP(hipMemcpyAsync(pl.d_off, pl.tab.data(), pl.tab.size() * 8, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(eval_check_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
+                       pl.d_len, pl.d_origin, g, d_tot);
+    DGRP_LAUNCH_CHECK();
+    unsigned long long hg[2];
+    DGRP_HIP(hipMemcpyAsync(hg, g, sizeof(hg), hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipMemcpyAsync(pl.tot, d_tot, sizeof(pl.tot), hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    if (hg[0]) {
+        const int64_t i = (int64_t)hg[1];
+        dgrp_segment q;
+        DGRP_HIP(hipMemcpy(&q, d_rows + i, sizeof(q), hipMemcpyDeviceToHost));
+        DGRP_REQUIRE(false, "%s: row %lld [%lld, %lld) label %d: rows need 0 <= start <= end and 1 <= label <= 127", what, (long long)i,
+                     (long long)q.start, (long long)q.end, (int)q.label);
+    }
+    return DGRP_OK;
+}
+
+// the pass's clipped lengths and first positions, scanned: d_cl[0..nrows] = exclusive scan, d_cl[nrows] = the pass's total
+static int eval_spans(const eval_plan &pl, const dgrp_segment *d_rows, int64_t nrec, int label, hipStream_t stream)
+{
+    hipLaunchKernelGGL(eval_span_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
+                       pl.d_off, pl.d_len, pl.d_origin, label, pl.d_cl, pl.d_dst);
+    DGRP_LAUNCH_CHECK();
+    return device_exclusive_scan(pl.d_cl, pl.d_cl, pl.nrows, pl.d_tiles, pl.d_cl + pl.nrows, stream);
+}
+
+}   // namespace
+
+DGRP_EXPORT int64_t dgrp_eval_workspace_bytes(int64_t nrec, int64_t nrows)
+{
+    if (nrec < 0 || nrows < 0) return 0;
+    return EVAL_HEAD + dgrp_align_up((4 * nrec + 1) * 8, 256) + dgrp_align_up((nrows + 1) * 8, 256) + dgrp_align_up(nrows * 8, 256) +
+           dgrp_align_up(((nrows + SCAN_TILE - 1) / SCAN_TILE + 1) * 8, 256);
+}
+
+DGRP_EXPORT int dgrp_paint_rows_batch(int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                                      const int64_t *h_origin, const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work,
+                                      int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    eval_plan pl;
+    const int rc = eval_prepare("dgrp_paint_rows_batch", nrec, h_off, h_len, h_origin, d_rows, h_row_off, d_work, work_bytes, stream, pl);
+    if (rc != DGRP_OK || pl.nrows == 0 || nrec == 0) return rc;
+    DGRP_REQUIRE(d_labels, "dgrp_paint_rows_batch: NULL pointer");
+    const dgrp_segment *rows = d_rows;
+    // one pass per label, highest first: the smallest label covering a base is written last (plain stores, no atomics)
+    for (int lab = 127; lab >= 1; --lab) {
+        if (pl.tot[lab] == 0) continue;
+        const int e = eval_spans(pl, rows, nrec, lab, stream);
+        if (e != DGRP_OK) return e;
+        const uint64_t groups = (pl.tot[lab] + EVAL_SLICE - 1) / EVAL_SLICE;
+        hipLaunchKernelGGL(eval_paint_kernel, dim3((unsigned)groups), dim3(256), 0, stream, d_labels, pl.d_cl, pl.d_dst, pl.nrows, lab);
+        DGRP_LAUNCH_CHECK();
+    }
+    return DGRP_OK;
+}
+
+DGRP_EXPORT int dgrp_row_hits_batch(const int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                                    const int64_t *h_origin, const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_hits,
+                                    void *d_work, int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    eval_plan pl;
+    const int rc = eval_prepare("dgrp_row_hits_batch", nrec, h_off, h_len, h_origin, d_rows, h_row_off, d_work, work_bytes, stream, pl);
+    if (rc != DGRP_OK || pl.nrows == 0 || nrec == 0) return rc;
+    DGRP_REQUIRE(d_hits, "dgrp_row_hits_batch: NULL pointer");
+    const int64_t r0 = h_row_off[0];
+    DGRP_HIP(hipMemsetAsync(d_hits + r0, 0, pl.nrows * 8, stream));
+    uint64_t total = 0;
+    for (int k = 1; k < 128; ++k) total += pl.tot[k];
+    if (total == 0) return DGRP_OK;
+    DGRP_REQUIRE(d_labels, "dgrp_row_hits_batch: NULL pointer");
+    const int e = eval_spans(pl, d_rows, nrec, 0, stream);
+    if (e != DGRP_OK) return e;
+    hipLaunchKernelGGL(eval_hits_kernel, dim3((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE)), dim3(256), 0, stream, d_labels,
+                       pl.d_cl, pl.d_dst, d_rows + r0, pl.nrows, reinterpret_cast<unsigned long long *>(d_hits + r0));
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}

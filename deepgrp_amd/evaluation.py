@@ -1,0 +1,313 @@
+"""`evaluate`: how well a model finds the repeats of an annotation -- per-class precision, recall, F1 and MCC on the bases `predict`
+labels, the measure of the DeepGRP paper and of the reference's model selection (deepgrp/optimization.py:52-69 scores the MSS labels
+of a held-out chromosome with calculate_metrics against the truth of preprocess_y), plus element-level counts.
+
+Per record, the evaluated bases are those `predict` labels: from the first to the last non-N base (DeviceRecord's startpos and
+kept length).  The prediction of a base is the label of the TSV row `predict` writes over it (0 where none does); its truth is
+the smallest kept repeat number among the annotation rows that cover it (0 where none does), which is
+preprocess_y(...).argmax(axis=0).  Two deliberate differences from the reference's objective: its drop_start_end_n also drops the
+last non-N base, and it runs filter_segments over the labels once more; here the TSV users get is measured as it is.
+
+Both label tracks are painted on the GPU from their rows (dgrp_paint_rows_batch) into flat buffers of the work item's records,
+scored by dgrp_confusion_matrix, and every row is counted against the other track (dgrp_row_hits_batch)."""
+from __future__ import annotations
+
+import logging
+import math
+import os
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .pipeline import SEGMENT_DTYPE
+
+_LOG = logging.getLogger(__name__)
+
+TSV_COLUMNS = ("class", "true_bases", "predicted_bases", "TP", "FP", "FN", "TPR", "PPV", "F1", "elements", "found", "segments",
+               "supported")
+
+
+class AnnotationError(ValueError):
+    """A row of the annotation table that cannot be read."""
+
+
+class NoMatchError(ValueError):
+    """Not one annotation row names a record of the inputs (the usual cause: `chr1` against `1`)."""
+
+
+def _bad(path, lineno: int, line: str, why: str):
+    return AnnotationError(f"{path}:{lineno}: {why}: {line.rstrip()!r}")
+
+
+def read_annotation(path, repeats: Optional[Iterable[int]] = None) -> Dict[str, np.ndarray]:
+    """The rows of a `parse_rm` table (whitespace separated: contig, 0-based begin, exclusive end, repeat number, further columns
+    ignored; blank lines and lines starting with '#' skipped) as {contig: SEGMENT_DTYPE rows} with label = repeat number, in file
+    order.  Rows whose number is not in `repeats` are dropped (None keeps every row).  A negative begin or end, an end below its
+    begin or a column 2-4 that is not an integer raises AnnotationError naming the file and the line."""
+    with open(path, "r", errors="surrogateescape") as fh:
+        lines = fh.read().splitlines()
+    recs: List[List[str]] = []
+    linenos: List[int] = []
+    for k, line in enumerate(lines):
+        f = line.split(None, 4)
+        if not f or f[0][0] == "#":
+            continue
+        if len(f) < 4:
+            raise _bad(path, k + 1, line, "expected contig, begin, end and repeat number")
+        recs.append(f)
+        linenos.append(k + 1)
+    n = len(recs)
+    names = [f[0] for f in recs]
+    tokens = [t for f in recs for t in f[1:4]]
+    try:
+        vals = np.fromiter(map(int, tokens), np.int64, count=3 * n).reshape(n, 3).T
+    except (ValueError, OverflowError):
+        for k, t in enumerate(tokens):                           # the first line at fault
+            try:
+                np.int64(int(t))
+            except (ValueError, OverflowError):
+                ln = linenos[k // 3]
+                raise _bad(path, ln, lines[ln - 1], f"{('begin', 'end', 'repeat number')[k % 3]} {t!r} is not an integer") from None
+        raise
+    begin, end, number = vals
+    bad = np.flatnonzero((begin < 0) | (end < begin))
+    if bad.size:
+        k = int(bad[0])
+        raise _bad(path, linenos[k], lines[linenos[k] - 1], "negative begin" if begin[k] < 0 else "end below begin")
+    keep = np.ones(n, bool) if repeats is None else np.isin(number, np.array(sorted(set(int(r) for r in repeats)), np.int64))
+    out: Dict[str, np.ndarray] = {}
+    idx = np.flatnonzero(keep)
+    if idx.size == 0:
+        return out
+    uniq, inv = np.unique(np.array(names)[idx], return_inverse=True)
+    order = np.argsort(inv, kind="stable")
+    for u, part in zip(uniq, np.split(order, np.cumsum(np.bincount(inv, minlength=len(uniq)))[:-1])):
+        sel = idx[part]
+        rows = np.zeros(sel.size, SEGMENT_DTYPE)
+        rows["start"], rows["end"], rows["label"] = begin[sel], end[sel], number[sel]
+        out[str(u)] = rows
+    return out
+
+
+def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
+    """Bases of each row inside the evaluated span [origin, origin + length)."""
+    a = np.clip(rows["start"].astype(np.int64), origin, origin + length)
+    e = np.clip(rows["end"].astype(np.int64), origin, origin + length)
+    return np.maximum(e - a, 0)
+
+
+class Accumulator:
+    """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
+
+    def __init__(self, classes: int, min_overlap: float):
+        if not 0.0 < min_overlap <= 1.0:
+            raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
+        self.C, self.theta = int(classes), float(min_overlap)
+        self.cnf = np.zeros((self.C, self.C), np.int64)
+        self.elements = np.zeros(self.C, np.int64)
+        self.found = np.zeros(self.C, np.int64)
+        self.segments = np.zeros(self.C, np.int64)
+        self.supported = np.zeros(self.C, np.int64)
+        self.bases = self.records = self.records_annotated = self.rows_used = self.outside = 0
+
+    def _count(self, labels: np.ndarray, clen: np.ndarray, hits: np.ndarray, total: np.ndarray, good: np.ndarray) -> None:
+        ok = clen > 0
+        np.add.at(total, labels[ok], 1)
+        hit = ok & (hits.astype(np.float64) >= self.theta * clen.astype(np.float64))
+        np.add.at(good, labels[hit], 1)
+
+    def add(self, origins: Sequence[int], lengths: Sequence[int], pred_rows: Sequence[np.ndarray],
+            true_rows: Sequence[np.ndarray]) -> None:
+        """One work item: records r = 0.. with startpos origins[r], kept length lengths[r], the TSV rows `predict` wrote for it
+        (original coordinates) and its kept annotation rows."""
+        import torch
+
+        from ._lib import check, lib
+        from .pipeline import require_gpu, stream_ptr
+        L = lib()
+        nrec = len(lengths)
+        if nrec == 0:
+            return
+        ln = np.ascontiguousarray(lengths, np.int64)
+        org = np.ascontiguousarray(origins, np.int64)
+        off = np.zeros(nrec + 1, np.int64)
+        np.cumsum(ln, out=off[1:])
+        n = int(off[-1])
+        self.records += nrec
+        self.bases += n
+        self.records_annotated += sum(1 for t in true_rows if len(t))
+        tr = [np.ascontiguousarray(t, SEGMENT_DTYPE) for t in true_rows]
+        pr = [np.ascontiguousarray(p, SEGMENT_DTYPE) for p in pred_rows]
+        t_clen = [clipped_lengths(t, int(org[r]), int(ln[r])) for r, t in enumerate(tr)]
+        self.rows_used += sum(len(t) for t in tr)
+        self.outside += int(sum(int((c == 0).sum()) for c in t_clen))
+        if n == 0:
+            return
+        dev = require_gpu()
+        d_true = torch.zeros(n, dtype=torch.int8, device=dev)
+        d_pred = torch.zeros(n, dtype=torch.int8, device=dev)
+
+        def upload(rows: List[np.ndarray]):
+            ro = np.zeros(nrec + 1, np.int64)
+            np.cumsum([len(x) for x in rows], out=ro[1:])
+            flat = np.concatenate(rows) if ro[-1] else np.zeros(0, SEGMENT_DTYPE)
+            d = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
+            return ro, flat, d
+
+        t_off, t_flat, d_trows = upload(tr)
+        p_off, p_flat, d_prows = upload(pr)
+        wb = L.dgrp_eval_workspace_bytes(nrec, max(int(t_off[-1]), int(p_off[-1])))
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        s = stream_ptr()
+        ptr = lambda t: None if t is None else t.data_ptr()
+
+        def paint(d_labels, ro, d_rows):
+            check(L.dgrp_paint_rows_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_rows),
+                                          ro.ctypes.data, work.data_ptr(), wb, s), "dgrp_paint_rows_batch")
+
+        def hits(d_labels, ro, d_rows):
+            d_hits = torch.zeros(max(int(ro[-1]), 1), dtype=torch.int64, device=dev)
+            check(L.dgrp_row_hits_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_rows),
+                                        ro.ctypes.data, d_hits.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_hits_batch")
+            return d_hits
+
+        paint(d_true, t_off, d_trows)
+        paint(d_pred, p_off, d_prows)
+        d_ht = hits(d_pred, t_off, d_trows)            # annotation rows against the predicted labels
+        d_hp = hits(d_true, p_off, d_prows)            # predicted rows against the truth
+        d_cnf = torch.empty((self.C, self.C), dtype=torch.int64, device=dev)
+        d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+        check(L.dgrp_confusion_matrix(d_true.data_ptr(), d_pred.data_ptr(), n, self.C, d_cnf.data_ptr(), d_bad.data_ptr(), s),
+              "dgrp_confusion_matrix")
+        cnf, bad = d_cnf.cpu().numpy(), int(d_bad.item())
+        ht, hp = d_ht.cpu().numpy()[:int(t_off[-1])], d_hp.cpu().numpy()[:int(p_off[-1])]
+        if bad:
+            raise ValueError(f"a label outside 0..{self.C - 1} reached the confusion matrix")
+        self.cnf += cnf
+        if t_flat.size:
+            self._count(t_flat["label"].astype(np.int64), np.concatenate(t_clen), ht, self.elements, self.found)
+        if p_flat.size:
+            p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(pr)])
+            self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
+
+
+def metrics_of(cnf: np.ndarray, bases: int) -> Dict[str, object]:
+    """prediction._calculate_metrics of the matrix (numpy's NaN where a formula divides by zero), TotalACC = trace / bases."""
+    from .prediction import _calculate_metrics
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = _calculate_metrics(np.asarray(cnf, np.int64))
+        m["TotalACC"] = float(np.trace(cnf)) / bases if bases else float("nan")
+    return m
+
+
+def _num(x) -> Optional[float]:
+    x = float(x)
+    return None if math.isnan(x) else x
+
+
+def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
+    """The JSON content: `info` (paths, options) plus counts, the confusion matrix, every metric (NaN as None) and the element
+    counts."""
+    m = metrics_of(acc.cnf, acc.bases)
+    metrics = {}
+    for k, v in m.items():
+        metrics[k] = [_num(x) for x in np.asarray(v).ravel()] if np.ndim(v) else _num(v)
+    out = dict(info)
+    out.update(classes=acc.C, bases=int(acc.bases), records=int(acc.records), records_annotated=int(acc.records_annotated),
+               rows_used=int(acc.rows_used), outside=int(acc.outside), confusion_matrix=acc.cnf.astype(int).tolist(),
+               metrics=metrics, min_overlap=acc.theta, elements=acc.elements.tolist(), found=acc.found.tolist(),
+               segments=acc.segments.tolist(), supported=acc.supported.tolist())
+    return out
+
+
+def tsv_report(rep: Dict[str, object]) -> str:
+    """The report table: a header line, one line per class, then #TotalACC and #MCC; floats as repr(float) ('nan' for NaN)."""
+    f = lambda x: repr(float("nan") if x is None else float(x))
+    cnf = np.asarray(rep["confusion_matrix"], np.int64)
+    m = rep["metrics"]
+    lines = ["#" + "\t".join(TSV_COLUMNS)]
+    for c in range(int(rep["classes"])):
+        tp = int(cnf[c, c])
+        lines.append("\t".join([str(c), str(int(cnf[c].sum())), str(int(cnf[:, c].sum())), str(tp), str(int(cnf[:, c].sum()) - tp),
+                                str(int(cnf[c].sum()) - tp), f(m["TPR"][c]), f(m["PPV"][c]), f(m["F1"][c]),
+                                str(rep["elements"][c]), str(rep["found"][c]), str(rep["segments"][c]), str(rep["supported"][c])]))
+    lines.append(f"#TotalACC\t{f(m['TotalACC'])}")
+    lines.append(f"#MCC\t{f(m['MCC'])}")
+    return "\n".join(lines) + "\n"
+
+
+def strip_n(raw: bytes) -> Tuple[int, int]:
+    """(startpos, kept length) of a record's sequence bytes, as upload_sequence strips them (kept < 0: all N)."""
+    import ctypes as C
+
+    from ._lib import check, lib
+    st, kept = C.c_int64(0), C.c_int64(0)
+    host = np.frombuffer(raw, dtype=np.uint8)
+    check(lib().dgrp_strip_n(host.ctypes.data if len(raw) else None, len(raw), C.byref(st), C.byref(kept)), "dgrp_strip_n")
+    return int(st.value), int(kept.value)
+
+
+def record_name(filename: str, header: str) -> str:
+    """The annotation contig a record is matched to: a `.npz` input's basename up to the first '.' (the reference's `train` rule,
+    deepgrp/__main__.py:315-316), else the first whitespace-delimited word of the FASTA header."""
+    if filename.endswith(".npz") and os.path.isfile(filename):
+        return os.path.basename(filename).split(".")[0]
+    words = header.split()
+    return words[0] if words else ""
+
+
+def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
+             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None) -> Dict[str, object]:
+    """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
+    `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
+    content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
+    record read has none)."""
+    from .runner import RecordRunner
+
+    classes = int(model.output_shape[2])
+    acc = Accumulator(classes, min_overlap)
+    runner = RecordRunner(pipe)
+    empty = np.zeros(0, SEGMENT_DTYPE)
+    seen_names: List[str] = []
+    state = {"matched": False, "warned": False}
+
+    def keyed():
+        for filename, records in inputs:
+            for header, rec in records:
+                if isinstance(rec, str):
+                    # text records stay text: the runner's worker uploads them on its own stream, as `predict` does; their
+                    # startpos and kept length come from the same host scan (dgrp_strip_n; kept < 0: the worker raises)
+                    rec = rec.encode("utf-8")
+                    startpos, length = strip_n(rec)
+                else:
+                    startpos, length = int(rec.startpos), int(rec.length)
+                name = record_name(filename, header)
+                if len(seen_names) < 5 and name not in seen_names:
+                    seen_names.append(name)
+                if name in annotation:
+                    state["matched"] = True
+                elif not state["matched"] and not state["warned"]:
+                    # the usual cause of an empty evaluation (`chr1` against `1`) shows before the first forward pass ends
+                    state["warned"] = True
+                    _LOG.warning("record %r of %s has no annotation rows; annotation contigs: %s", name, filename,
+                                 ", ".join(repr(x) for x in sorted(annotation)[:5]) or "none with kept rows")
+                # the key carries what the evaluation needs past the runner: name, startpos, kept length
+                yield (name, startpos, length), rec
+
+    for kind, key, rows in runner.results(keyed()):
+        keys = key if kind == "batch" else [key]
+        rows = np.asarray(rows)
+        if kind == "batch":
+            contig = rows["contig"] if rows.size else np.zeros(0, np.int32)
+            cut = np.searchsorted(contig, np.arange(len(keys) + 1))
+            pred = [rows[cut[r]:cut[r + 1]] for r in range(len(keys))]
+        else:
+            pred = [rows]
+        acc.add([k[1] for k in keys], [k[2] for k in keys], pred, [annotation.get(k[0], empty) for k in keys])
+    if acc.rows_used == 0:
+        raise NoMatchError("no annotation row names a record of the inputs (records: {}; annotation: {})".format(
+            ", ".join(repr(x) for x in seen_names) or "none",
+            ", ".join(repr(x) for x in sorted(annotation)[:5]) or "no kept rows"))
+    info = dict(info or {})
+    info.setdefault("repeats", [int(r) for r in repeats])
+    return report(acc, info)

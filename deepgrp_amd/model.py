@@ -232,8 +232,12 @@ def load_model(path: str, custom_objects: Optional[dict] = None):
     """Drop-in for ``tf.keras.models.load_model(path, custom_objects=...)`` on the prediction path:
     returns a device-resident model exposing ``input_shape``, ``output_shape`` and
     ``predict_on_batch``."""
+    return device_model(read_keras_hdf5(path))
+
+
+def device_model(w: Dict[str, Any]):
+    """The device-resident model of read_keras_hdf5's weights (load_model's second half: the first GPU work)."""
     from .pipeline import DeviceModel
-    w = read_keras_hdf5(path)
     model = DeviceModel(w["kernel"], w["recurrent_kernel"], w["bias"], w["ff_kernel"], w["ff_bias"], w["scale"],
                         vecsize=w["vecsize"], rnn=w["rnn"])
     model.config = w["config"]

@@ -3,7 +3,7 @@ weights or genomes offline, so benchmarks, the smoke test and parity tests use
 seeded random chromosomes and Keras-initialiser weights."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -59,6 +59,21 @@ def synthetic_chromosome(n_bases: int, contig: int = 0, n_frac: float = 0.01, fl
 def synthetic_truth(n_bases: int, contig: int = 0, n_frac: float = 0.01, flank: int = 10_000):
     """(class index uint8 [n], truth label uint8 [n]) of the same chromosome."""
     return _planted(n_bases, contig, n_frac, flank, True)
+
+
+def synthetic_annotation(n_bases: int, contig: int = 0, name: Optional[str] = None, n_frac: float = 0.01,
+                         flank: int = 10_000) -> List[str]:
+    """The planted truth runs of synthetic_chromosome(n_bases, contig, n_frac, flank) as lines of the table parse_rm writes
+    (contig name, 0-based begin, exclusive end, repeat class, repeat name, family; newline-terminated), in position order.
+    `name` defaults to "chr<contig + 1>"."""
+    _, lab = _planted(n_bases, contig, n_frac, flank, True)
+    name = f"chr{contig + 1}" if name is None else name
+    edge = np.flatnonzero(np.diff(lab.astype(np.int16), prepend=0, append=0))      # run boundaries (planted runs never touch)
+    lines = []
+    for b, e in zip(edge[:-1], edge[1:]):
+        if lab[b]:
+            lines.append(f"{name}\t{b}\t{e}\t{int(lab[b])}\tsynthetic_tr\tSimple_repeat\n")
+    return lines
 
 
 def trained_weights(path: Optional[str] = None) -> Dict[str, Optional[np.ndarray]]:

@@ -316,6 +316,24 @@ int dgrp_confusion_matrix(const int8_t *d_true, const int8_t *d_pred, int64_t n,
  * min_len become 0.  d_out may be d_labels (the reference works in place). */
 int dgrp_filter_segments(const int8_t *d_labels, int8_t *d_out, int64_t n, int64_t min_len, void *stream);
 
+/* ---- evaluate (an addition; the reference scores label arrays on the host, deepgrp/preprocessing.py:9-48 and
+ * deepgrp/prediction.py:225-241).  A flat int8 buffer holds the evaluated bases of nrec records back to back: record r is
+ * d_labels[h_off[r] .. h_off[r] + h_len[r]) and its first base has the original coordinate h_origin[r] (its startpos).  Its rows
+ * are d_rows[h_row_off[r] .. h_row_off[r+1]) (device), in ORIGINAL record coordinates, in any order, overlapping or not, and are
+ * clipped to the record.  Every row must satisfy 0 <= start <= end and 1 <= label <= 127: a bad row gives DGRP_EINVAL before
+ * anything is written (the check synchronises the stream once).  Work is balanced by clipped length, not by row.
+ * dgrp_paint_rows_batch: every base some row covers is set to the SMALLEST label among the rows that cover it; no other byte is
+ * written; deterministic (one pass per label present, highest first, plain stores).
+ * dgrp_row_hits_batch: d_hits[i] (int64, for i in [h_row_off[0], h_row_off[nrec])) = bases of row i's clipped span whose label
+ * in d_labels equals row i's label (exact integer sums).
+ * Both take a workspace of dgrp_eval_workspace_bytes(nrec, rows) bytes. */
+int64_t dgrp_eval_workspace_bytes(int64_t nrec, int64_t nrows);
+int dgrp_paint_rows_batch(int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                          const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes, void *stream);
+int dgrp_row_hits_batch(const int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                        const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_hits, void *d_work, int64_t work_bytes,
+                        void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
