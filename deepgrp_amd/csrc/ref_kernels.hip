@@ -2,7 +2,8 @@
 // fp32 state, libm-grade expf/tanhf, no MFMA, no fp16 anywhere -- for a handful of windows.  It exists so that a user
 // can measure, on THEIR weights and THEIR sequence, how far the fp16-operand fused kernel (gru_kernel.hip) is from
 // full precision (`python -m deepgrp_amd verify`), and so that the tests have a third, independent statement of the
-// forward pass that runs at sizes the CPU checker of the test suite does not.  Not a fallback: nothing on the prediction path calls it.
+// forward pass that runs at sizes the CPU checker of the test suite does not.  Not a fallback for a model the fused kernels take; a
+// model beyond their sizes (257-2048 units or 17-64 classes) runs every forward call on these kernels (api.hip, "fp32 path").
 //
 //   ref_rnn_kernel   one workgroup per 8 (window, strand) pairs: thread j owns unit j of each, h_{t-1} in LDS, U read
 //                    coalesced from L2 (k-major rows), outputs h_t for every step  -> seq [nw][2][T][u], last [nw][2][u]
@@ -19,6 +20,11 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // A workgroup carries RP (window, strand) pairs through all T steps; thread j owns unit j of every pair, so each
 // element of U it loads is used RP times (the kernel is bound by L1/L2 reads of U otherwise).
 constexpr int RP = 8;
+// h_{t-1} of a workgroup: 256 threads x NSL unit slots x RP pairs of floats, the launcher's dynamic LDS; every instantiation opts into
+// REF_RNN_LDS_MAX, which the largest carve (NSL 8: 2048 units) must fit
+constexpr size_t REF_RNN_LDS_MAX = 64 * 1024;
+constexpr size_t ref_rnn_lds(int nsl) { return (size_t)256 * nsl * RP * sizeof(float); }
+static_assert(ref_rnn_lds(8) <= REF_RNN_LDS_MAX, "ref_rnn_kernel<CELL, 8>: h_{t-1} of 2048 units x RP pairs exceeds the LDS it opts into");
 
 // NSL = unit slots per thread: thread j owns units j, j + 256, ... (one slot up to 256 units -- the yardstick of the fused kernels --,
 // more for the models beyond the fused kernels' sizes, which run on these kernels: api.hip, "fp32 path")
@@ -245,10 +251,10 @@ DGRP_EXPORT int dgrp_forward_windows_reference(const dgrp_model *m, const uint8_
     const int nsl = (m->u + 255) / 256;
     DGRP_REQUIRE(nsl <= 8, "dgrp_forward_windows_reference: units=%d (up to 2048)", m->u);
     const dim3 grid((unsigned)((npairs + RP - 1) / RP)), block((unsigned)(nsl > 1 ? 256 : (m->u + 63) / 64 * 64));
-    const size_t lds = (size_t)256 * (nsl <= 1 ? 1 : nsl <= 2 ? 2 : nsl <= 4 ? 4 : 8) * RP * sizeof(float);
+    const size_t lds = ref_rnn_lds(nsl <= 1 ? 1 : nsl <= 2 ? 2 : nsl <= 4 ? 4 : 8);
 #define REF_GO(CELLv, NSLv) do {                                                                                              \
         static std::once_flag once_; static hipError_t err_ = hipSuccess;                                                     \
-        std::call_once(once_, [] { err_ = hipFuncSetAttribute((const void *)ref_rnn_kernel<CELLv, NSLv>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); }); \
+        std::call_once(once_, [] { err_ = hipFuncSetAttribute((const void *)ref_rnn_kernel<CELLv, NSLv>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)REF_RNN_LDS_MAX); }); \
         DGRP_HIP(err_);                                                                                                        \
         hipLaunchKernelGGL((ref_rnn_kernel<CELLv, NSLv>), grid, block, lds, stream, d_idx, s, w0, npairs, m->T, m->u, kernel, rec, bias, seq, last); } while (0)
     if (m->cell == 0) { if (nsl <= 1) REF_GO(0, 1); else if (nsl <= 2) REF_GO(0, 2); else if (nsl <= 4) REF_GO(0, 4); else REF_GO(0, 8); }
