@@ -10,6 +10,7 @@ Differences, all additive:
   * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
     (deepgrp_amd/masking.py);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
+  * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
 """
 from __future__ import annotations
@@ -253,6 +254,12 @@ class CommandLineParser:
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
         masks = CommandLineParser._mask_plan(args)              # refusals come before anything runs
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            from .gz import compressed_inputs
+            packed = compressed_inputs(args.FASTA)
+            if packed:
+                sys.exit(f"{packed[0]} is gzip-compressed: compressed input cannot be sharded over ranks (WORLD_SIZE > 1); "
+                         "decompress it or run in one process")
         import torch
         import torch.distributed as dist
         from . import model as dgmodel
@@ -543,12 +550,16 @@ class CommandLineParser:
             if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None:
                 sys.exit("--mask and --mask_classes need --mask_dir")
             return None
+        from .gz import compressed_inputs
         plan, seen = {}, {}
         for f in args.FASTA:
             if f == "-":
                 sys.exit("--mask_dir: standard input cannot be masked (give a FASTA file)")
             if f.endswith(".npz"):
                 sys.exit(f"--mask_dir: {f} is a one-hot .npz, not a FASTA file; it cannot be masked")
+            if compressed_inputs([f]):
+                sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
+                         "uncompressed FASTA")
             base = os.path.basename(f)
             if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
                 sys.exit(f"--mask_dir: {seen[base]} and {f} have the same file name; their masked copies would collide")

@@ -73,6 +73,9 @@ _SIGNATURES = {
     "dgrp_eval_workspace_bytes": (i64, [i64, i64]),
     "dgrp_paint_rows_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_row_hits_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_inflate_raw_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cint)]),
+    "dgrp_inflate_workspace_bytes": (i64, [i64]),
+    "dgrp_inflate_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(cint), vp, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

@@ -1,0 +1,307 @@
+// DEFLATE (RFC 1951) decode core, written once for the host and the device.
+//
+// The decoder is serial (one symbol after the other, canonical Huffman decode one bit at a time against the per-length code
+// counts, as RFC 1951 3.2.2 constructs the codes).  Where the output goes is a template parameter: the host writes bytes one by
+// one; the device runs the same code on every lane of a wave (all lanes hold the same state) and spreads match and stored-block
+// copies over the lanes (inflate_kernels.hip).
+//
+// Every read is checked against the input slice [0, in_len) and every write and back-reference against the output slice
+// [0, out_cap): a bad stream ends with a DGRP_INFLATE_E* reason (include/deepgrp_hip.h), never with an access outside either slice.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/deepgrp_hip.h"
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define DGRP_HD __host__ __device__
+#else
+#define DGRP_HD
+#endif
+
+#define DGRP_HUFF_MAXBITS 15
+
+// one canonical code: count[len] = codes of that length, symbol[] = symbols ordered by (length, value)
+struct dgrp_huff {
+    int16_t count[DGRP_HUFF_MAXBITS + 1];
+    int16_t symbol[288];
+};
+
+// per-stream tables (LDS on the device: 2 KB)
+struct dgrp_inflate_tables {
+    dgrp_huff lencode, distcode;
+    int16_t lengths[288 + 32];
+    int16_t offs[DGRP_HUFF_MAXBITS + 1];
+    int fixed;                                   // the tables hold the fixed codes (rebuilt only when a dynamic block intervened)
+};
+
+struct dgrp_bits {
+    const uint8_t *in;
+    uint32_t len, pos;                           // input slice and the next byte to load into buf
+    uint64_t buf;                                // bits not yet consumed, LSB first
+    int cnt;
+};
+
+DGRP_HD static inline void dgrp_bits_refill(dgrp_bits &s)
+{
+    if (s.cnt <= 32 && s.pos + 4 <= s.len) {
+        const uint8_t *p = s.in + s.pos;
+        const uint64_t w = (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
+        s.buf |= w << s.cnt;
+        s.cnt += 32;
+        s.pos += 4;
+    }
+    while (s.cnt <= 56 && s.pos < s.len) {
+        s.buf |= (uint64_t)s.in[s.pos++] << s.cnt;
+        s.cnt += 8;
+    }
+}
+
+// n <= 16 bits; false when the input ends first
+DGRP_HD static inline bool dgrp_bits_get(dgrp_bits &s, int n, uint32_t &v)
+{
+    if (s.cnt < n) {
+        dgrp_bits_refill(s);
+        if (s.cnt < n) return false;
+    }
+    v = (uint32_t)(s.buf & ((1ull << n) - 1));
+    s.buf >>= n;
+    s.cnt -= n;
+    return true;
+}
+
+// Canonical code of lengths length[0..n): 0 = complete, > 0 = incomplete (codes left over), < 0 = over-subscribed.
+DGRP_HD static int dgrp_huff_build(dgrp_huff *h, int16_t *offs, const int16_t *length, int n)
+{
+    for (int len = 0; len <= DGRP_HUFF_MAXBITS; ++len) h->count[len] = 0;
+    for (int sym = 0; sym < n; ++sym) h->count[length[sym]]++;
+    if (h->count[0] == n) return 0;              // no codes: decoding with it fails (ESYMBOL)
+    int left = 1;
+    for (int len = 1; len <= DGRP_HUFF_MAXBITS; ++len) {
+        left <<= 1;
+        left -= h->count[len];
+        if (left < 0) return left;
+    }
+    offs[1] = 0;
+    for (int len = 1; len < DGRP_HUFF_MAXBITS; ++len) offs[len + 1] = (int16_t)(offs[len] + h->count[len]);
+    for (int sym = 0; sym < n; ++sym)
+        if (length[sym] != 0) h->symbol[offs[length[sym]]++] = (int16_t)sym;
+    return left;
+}
+
+// next symbol, or -reason
+DGRP_HD static inline int dgrp_huff_decode(dgrp_bits &s, const dgrp_huff *h)
+{
+    if (s.cnt < DGRP_HUFF_MAXBITS) dgrp_bits_refill(s);
+    uint64_t buf = s.buf;
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= DGRP_HUFF_MAXBITS; ++len) {
+        if (len > s.cnt) return -DGRP_INFLATE_EINPUT;
+        code |= (int)(buf & 1);
+        buf >>= 1;
+        const int count = h->count[len];
+        if (code - count < first) {
+            s.buf >>= len;
+            s.cnt -= len;
+            return h->symbol[index + (code - first)];
+        }
+        index += count;
+        first += count;
+        first <<= 1;
+        code <<= 1;
+    }
+    return -DGRP_INFLATE_ESYMBOL;                // a bit pattern no code of an incomplete set has
+}
+
+// RFC 1951 3.2.5 in closed form: base length / extra bits of length symbol i = sym - 257 (0..28), distance symbol d (0..29)
+DGRP_HD static inline void dgrp_len_code(int i, int &base, int &extra)
+{
+    if (i < 8) { base = 3 + i; extra = 0; }
+    else if (i == 28) { base = 258; extra = 0; }
+    else { extra = (i - 4) >> 2; base = ((4 + (i & 3)) << extra) + 3; }
+}
+DGRP_HD static inline void dgrp_dist_code(int d, int &base, int &extra)
+{
+    if (d < 4) { base = d + 1; extra = 0; }
+    else { extra = (d - 2) >> 1; base = ((2 + (d & 1)) << extra) + 1; }
+}
+// order of the code length code lengths (RFC 1951 3.2.7): 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
+DGRP_HD static inline int dgrp_clen_order(int i)
+{
+    if (i < 3) return 16 + i;
+    if (i == 3) return 0;
+    const int k = (i - 4) >> 1;
+    return (i & 1) ? 7 - k : 8 + k;
+}
+
+// A code set of a dynamic block may be incomplete only when it is a single code of one bit (RFC 1951 allows one distance code;
+// zlib accepts the same for literal/length).
+DGRP_HD static inline bool dgrp_code_ok(int err, const dgrp_huff *h, int n)
+{
+    return err == 0 || (err > 0 && n - h->count[0] == 1 && h->count[1] == 1);
+}
+
+DGRP_HD static int dgrp_read_dynamic(dgrp_bits &s, dgrp_inflate_tables *t)
+{
+    uint32_t nlen, ndist, ncode, v;
+    if (!dgrp_bits_get(s, 5, nlen) || !dgrp_bits_get(s, 5, ndist) || !dgrp_bits_get(s, 4, ncode)) return DGRP_INFLATE_EINPUT;
+    nlen += 257;
+    ndist += 1;
+    ncode += 4;
+    if (nlen > 286 || ndist > 30) return DGRP_INFLATE_ECODES;
+    for (int i = 0; i < 19; ++i) {
+        v = 0;
+        if (i < (int)ncode && !dgrp_bits_get(s, 3, v)) return DGRP_INFLATE_EINPUT;
+        t->lengths[dgrp_clen_order(i)] = (int16_t)v;
+    }
+    if (dgrp_huff_build(&t->lencode, t->offs, t->lengths, 19) != 0) return DGRP_INFLATE_ECODES;   // must be complete
+    const int total = (int)(nlen + ndist);
+    int index = 0;
+    while (index < total) {
+        const int sym = dgrp_huff_decode(s, &t->lencode);
+        if (sym < 0) return -sym;
+        if (sym < 16) { t->lengths[index++] = (int16_t)sym; continue; }
+        int16_t len = 0;
+        uint32_t rep;
+        if (sym == 16) {
+            if (index == 0) return DGRP_INFLATE_ECODES;        // repeat with no previous length
+            len = t->lengths[index - 1];
+            if (!dgrp_bits_get(s, 2, rep)) return DGRP_INFLATE_EINPUT;
+            rep += 3;
+        } else if (sym == 17) {
+            if (!dgrp_bits_get(s, 3, rep)) return DGRP_INFLATE_EINPUT;
+            rep += 3;
+        } else {
+            if (!dgrp_bits_get(s, 7, rep)) return DGRP_INFLATE_EINPUT;
+            rep += 11;
+        }
+        if (index + (int)rep > total) return DGRP_INFLATE_ECODES;
+        while (rep--) t->lengths[index++] = len;
+    }
+    if (t->lengths[256] == 0) return DGRP_INFLATE_ECODES;          // no end-of-block code
+    int err = dgrp_huff_build(&t->lencode, t->offs, t->lengths, (int)nlen);
+    if (!dgrp_code_ok(err, &t->lencode, (int)nlen)) return DGRP_INFLATE_ECODES;
+    err = dgrp_huff_build(&t->distcode, t->offs, t->lengths + nlen, (int)ndist);
+    if (!dgrp_code_ok(err, &t->distcode, (int)ndist)) return DGRP_INFLATE_ECODES;
+    t->fixed = 0;
+    return DGRP_INFLATE_OK;
+}
+
+DGRP_HD static void dgrp_build_fixed(dgrp_inflate_tables *t)
+{
+    for (int i = 0; i < 288; ++i) t->lengths[i] = (int16_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+    dgrp_huff_build(&t->lencode, t->offs, t->lengths, 288);
+    for (int i = 0; i < 30; ++i) t->lengths[i] = 5;
+    dgrp_huff_build(&t->distcode, t->offs, t->lengths, 30);
+    t->fixed = 1;
+}
+
+// One raw DEFLATE stream in[0, in_len) -> output [0, out_cap) through `sink`:
+//   sink.literal(pos, byte)           out[pos] = byte
+//   sink.match(pos, dist, len)        out[pos + j] = out[pos - dist + j] for j = 0 .. len-1 in order (dist <= pos checked)
+//   sink.stored(pos, src, len)        out[pos + j] = src[j]            (src inside the input slice, checked)
+// On return *out_len = bytes produced, *in_used = whole input bytes consumed up to the end of the last block.
+template <class Sink>
+DGRP_HD static int dgrp_inflate_core(const uint8_t *in, uint32_t in_len, uint32_t out_cap, dgrp_inflate_tables *t, Sink &sink,
+                                     uint32_t *out_len, uint32_t *in_used)
+{
+    dgrp_bits s;
+    s.in = in;
+    s.len = in_len;
+    s.pos = 0;
+    s.buf = 0;
+    s.cnt = 0;
+    t->fixed = 0;
+    uint32_t pos = 0, last = 0, type, v;
+    int rc = DGRP_INFLATE_OK;
+    do {
+        if (!dgrp_bits_get(s, 1, last) || !dgrp_bits_get(s, 2, type)) { rc = DGRP_INFLATE_EINPUT; break; }
+        if (type == 0) {
+            // stored: skip to a byte boundary, LEN and NLEN, LEN bytes as they are
+            s.buf >>= (s.cnt & 7);
+            s.cnt &= ~7;
+            const uint32_t at = s.pos - (uint32_t)(s.cnt >> 3);      // first byte not consumed
+            s.buf = 0;
+            s.cnt = 0;
+            if (at + 4 > in_len) { s.pos = in_len; rc = DGRP_INFLATE_EINPUT; break; }
+            const uint32_t len = (uint32_t)in[at] | ((uint32_t)in[at + 1] << 8);
+            const uint32_t nlen = (uint32_t)in[at + 2] | ((uint32_t)in[at + 3] << 8);
+            if (len != (~nlen & 0xffffu)) { s.pos = at + 4; rc = DGRP_INFLATE_ESTORED; break; }
+            if (len > in_len - (at + 4)) { s.pos = in_len; rc = DGRP_INFLATE_EINPUT; break; }
+            if (len > out_cap - pos) { s.pos = at + 4; rc = DGRP_INFLATE_EOUTPUT; break; }
+            sink.stored(pos, in + at + 4, len);
+            pos += len;
+            s.pos = at + 4 + len;
+            continue;
+        }
+        if (type == 3) { rc = DGRP_INFLATE_EBLOCK; break; }
+        if (type == 1) {
+            if (!t->fixed) dgrp_build_fixed(t);
+        } else if ((rc = dgrp_read_dynamic(s, t)) != DGRP_INFLATE_OK) {
+            break;
+        }
+        for (;;) {
+            int sym = dgrp_huff_decode(s, &t->lencode);
+            if (sym < 0) { rc = -sym; break; }
+            if (sym < 256) {
+                if (pos >= out_cap) { rc = DGRP_INFLATE_EOUTPUT; break; }
+                sink.literal(pos, (uint32_t)sym);
+                ++pos;
+                continue;
+            }
+            if (sym == 256) break;
+            sym -= 257;
+            if (sym >= 29) { rc = DGRP_INFLATE_ESYMBOL; break; }
+            int base, extra;
+            dgrp_len_code(sym, base, extra);
+            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
+            const uint32_t len = (uint32_t)base + v;
+            const int dsym = dgrp_huff_decode(s, &t->distcode);
+            if (dsym < 0) { rc = -dsym; break; }
+            if (dsym >= 30) { rc = DGRP_INFLATE_ESYMBOL; break; }
+            dgrp_dist_code(dsym, base, extra);
+            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
+            const uint32_t dist = (uint32_t)base + v;
+            if (dist > pos) { rc = DGRP_INFLATE_EDIST; break; }
+            if (len > out_cap - pos) { rc = DGRP_INFLATE_EOUTPUT; break; }
+            sink.match(pos, dist, len);
+            pos += len;
+        }
+    } while (rc == DGRP_INFLATE_OK && !last);
+    *out_len = pos;
+    *in_used = s.pos - (uint32_t)(s.cnt >> 3);
+    return rc;
+}
+
+// ---- CRC-32 (ISO-HDLC, the gzip trailer's): reflected polynomial 0xedb88320.  Byte-table update, and the combination of the CRCs
+// of two adjacent pieces (crc(A B) from crc(A), crc(B), |B|) by multiplication with x^(8|B|) modulo the polynomial.
+DGRP_HD static inline uint32_t dgrp_crc_table_entry(uint32_t n)
+{
+    uint32_t c = n;
+    for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0xedb88320u : c >> 1;
+    return c;
+}
+// a * b modulo the polynomial (bit 31 = x^0)
+DGRP_HD static inline uint32_t dgrp_crc_multmodp(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (int k = 0; k < 32; ++k) {
+        if (a & (0x80000000u >> k)) p ^= b;
+        b = (b & 1) ? (b >> 1) ^ 0xedb88320u : b >> 1;
+    }
+    return p;
+}
+// x^(8 n) modulo the polynomial
+DGRP_HD static inline uint32_t dgrp_crc_x8n(uint64_t n)
+{
+    uint32_t p = 0x80000000u, q = 0x00800000u;   // x^0, x^8
+    while (n) {
+        if (n & 1) p = dgrp_crc_multmodp(q, p);
+        q = dgrp_crc_multmodp(q, q);
+        n >>= 1;
+    }
+    return p;
+}
+DGRP_HD static inline uint32_t dgrp_crc_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
+{
+    return dgrp_crc_multmodp(dgrp_crc_x8n(len_b), crc_a) ^ crc_b;
+}

@@ -276,9 +276,15 @@ def ingest_ranges(path: Union[str, os.PathLike], ranges=None, group_bytes: int =
     piece) sorts the records of a file in file order whichever process produced them."""
     import numpy as np
 
+    from . import gz
     from ._lib import lib
     from .pipeline import require_gpu
 
+    if gz.is_gzip(path):
+        if ranges is not None:
+            raise ValueError(f"{path}: a compressed file is read whole; it cannot be ingested by byte ranges")
+        yield from _ingest_gzip(path, group_bytes, group_records)
+        return
     dev = require_gpu()
     L = lib()
     size = os.path.getsize(path)
@@ -296,17 +302,31 @@ def ingest_ranges(path: Union[str, os.PathLike], ranges=None, group_bytes: int =
             yield from _ingest_range(L, dev, path, mm, a, b, group_bytes, group_records)
 
 
-def _chunk_table(L, dev, path, mm, r0: int, r1: int):
+def _ingest_gzip(path, group_bytes: int, group_records: int):
+    """ingest_ranges for a gzip file (deepgrp_amd/gz.py): its inflated bytes, in HBM, take the place of the uploaded file; the host
+    reads header lines (and the bodies the reference loop takes) from the zlib output or, for BGZF, from the device."""
+    from . import gz
+    from ._lib import lib
+    from .pipeline import require_gpu
+
+    text, d_text, size = gz.open_inflated(path, RESIDENT_BYTES, require_gpu, _upload_file)
+    if size == 0:
+        return
+    yield from _ingest_range(lib(), d_text.device, path, text, 0, size, group_bytes, group_records, d_file=d_text)
+
+
+def _chunk_table(L, dev, path, mm, r0: int, r1: int, d_file=None):
     """The chunk table of the range [r0, r1) of the mapped file, offsets relative to r0: (d_file = the range in HBM or None above
-    RESIDENT_BYTES, chunk starts + [size], end of each chunk's header line, start of each body, whether the chunk opens with '>')."""
+    RESIDENT_BYTES, chunk starts + [size], end of each chunk's header line, start of each body, whether the chunk opens with '>').
+    A `d_file` given by the caller is the range already in HBM (inflated compressed input)."""
     import numpy as np
 
     size = r1 - r0
-    d_file = None
-    if size <= RESIDENT_BYTES:
+    if d_file is not None or size <= RESIDENT_BYTES:
         # the whole range goes up once (pinned slabs, the read of slab k+1 overlaps the DMA of slab k) and the chunk
         # table comes from a device pass over it (dgrp_fasta_chunks): the host touches the header lines only
-        d_file = _upload_file(path, size, dev, r0)
+        if d_file is None:
+            d_file = _upload_file(path, size, dev, r0)
         st, first_lf = _device_chunks(L, d_file, size)
         starts_np = np.concatenate([st, [size]]).astype(np.int64)
         gt_np = np.ones(st.size, bool)
@@ -343,7 +363,7 @@ class ChunkGroup:
         return bool(self.cand[i] and self.info[i][0] == 1)
 
 
-def _chunk_groups(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int, keep_raw: bool = False):
+def _chunk_groups(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int, keep_raw: bool = False, d_file=None):
     """The chunks of [r0, r1) in groups (up to `group_bytes` of file or `group_records` chunks): per group one upload (or a view of
     the resident range) and one dgrp_fasta_encode_batch over the bodies whose header line qualifies.  Yields ChunkGroup."""
     import numpy as np
@@ -352,7 +372,9 @@ def _chunk_groups(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
     from ._lib import check
     from .pipeline import stream_ptr
 
-    d_file, starts, head_ends, body0_all, gt_all = _chunk_table(L, dev, path, mm, r0, r1)
+    d_file, starts, head_ends, body0_all, gt_all = _chunk_table(L, dev, path, mm, r0, r1, d_file)
+    if hasattr(mm, "prime"):
+        mm.prime(starts, head_ends)                                    # device-resident text: every header line in one copy
     nchunks = len(starts) - 1
     c0 = 0
     while c0 < nchunks:
@@ -398,10 +420,10 @@ def _chunk_groups(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_re
         c0 = c1
 
 
-def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int):
+def _ingest_range(L, dev, path, mm, r0: int, r1: int, group_bytes: int, group_records: int, d_file=None):
     """ingest_ranges for one range [r0, r1) of the mapped file; offsets below are relative to r0 unless they say `abs`."""
     loop = LineLoop()
-    for grp in _chunk_groups(L, dev, path, mm, r0, r1, group_bytes, group_records):
+    for grp in _chunk_groups(L, dev, path, mm, r0, r1, group_bytes, group_records, d_file=d_file):
         starts, head_ends, g0 = grp.starts, grp.head_ends, grp.starts[grp.c0]
         for i, c in enumerate(range(grp.c0, grp.c1)):
             a, b = r0 + starts[c], r0 + starts[c + 1]                  # abs

@@ -1,0 +1,250 @@
+"""Compressed FASTA input (an addition; the reference reads plain text only).
+
+A gzip file is recognised by its magic bytes, not by its name.  A BGZF file (every member carries the `BC` extra subfield with its
+compressed size BSIZE, and inflates to at most 64 KiB) is split into its members by a walk over the member headers on the host;
+the compressed file is uploaded as it is and the members are inflated side by side on the device (dgrp_inflate_batch), straight
+into the buffer the FASTA ingest consumes.  Any other gzip file (one member as gzip/pigz write it, members without `BC`) is
+inflated on the host with zlib and uploaded.  Corrupt input raises GzipError naming the file and the compressed byte offset of
+the first bad member."""
+from __future__ import annotations
+
+import logging
+import os
+import struct
+import zlib
+from typing import Optional
+
+import numpy as np
+
+MAGIC = b"\x1f\x8b"
+BGZF_MAX_ISIZE = 1 << 16
+_LOG = logging.getLogger(__name__)
+
+# DGRP_INFLATE_* (include/deepgrp_hip.h)
+REASONS = {1: "input ends inside the DEFLATE stream", 2: "invalid block type", 3: "stored block LEN/NLEN mismatch",
+           4: "invalid code lengths", 5: "invalid symbol", 6: "distance too far back", 7: "more output than ISIZE",
+           8: "CRC-32 mismatch", 9: "output shorter than ISIZE", 10: "DEFLATE stream ends before the member's trailer"}
+
+
+class GzipError(ValueError):
+    """Corrupt or truncated gzip input: `path` and the compressed byte `offset` of the first bad member."""
+
+    def __init__(self, path, offset: int, what: str):
+        super().__init__(f"{path}: corrupt gzip input, member at compressed byte offset {offset}: {what}")
+        self.path, self.offset = path, int(offset)
+
+
+def is_gzip(path) -> bool:
+    """The file starts with the gzip magic bytes 1f 8b (False for anything that cannot be opened)."""
+    try:
+        with open(path, "rb") as fh:
+            return fh.read(2) == MAGIC
+    except OSError:
+        return False
+
+
+def compressed_inputs(files):
+    """The command-line inputs that are gzip files (stdin and the one-hot .npz are never)."""
+    return [f for f in files if f != "-" and not f.endswith(".npz") and os.path.isfile(f) and is_gzip(f)]
+
+
+class Members:
+    """Result of the member walk.  kind = "bgzf" or "gzip"; for BGZF, per member: `start` (offset of its header), `data_off` and
+    `data_len` (its DEFLATE data), `isize` (its trailer's ISIZE); `size` = compressed file size."""
+
+    __slots__ = ("kind", "start", "data_off", "data_len", "isize", "size")
+
+    def __init__(self, kind, size, start=(), data_off=(), data_len=(), isize=()):
+        self.kind, self.size = kind, int(size)
+        self.start, self.data_off, self.data_len, self.isize = (np.asarray(a, np.int64) for a in (start, data_off, data_len, isize))
+
+
+def walk_members(buf, path="<buffer>") -> Members:
+    """Classify the gzip bytes `buf` (bytes or a mapping of the file) by a walk over its member headers: "bgzf" when every member
+    has FLG = FEXTRA, a `BC` subfield whose BSIZE frames it inside the file, and an ISIZE of at most 64 KiB; "gzip" as soon as a
+    member does not (that file goes to zlib, which finds member ends by inflating).  A BGZF member whose header or BSIZE runs past
+    the end of the file, or bytes after a BGZF member that are not a gzip member, raise GzipError."""
+    n = len(buf)
+    pos = 0
+    start, doff, dlen, isize = [], [], [], []
+    while pos < n:
+        if n - pos < 12:
+            if pos == 0 or buf[pos:pos + 2] == MAGIC[:n - pos]:
+                raise GzipError(path, pos, "truncated member header")
+            raise GzipError(path, pos, "not a gzip member")
+        id12, cm, flg = buf[pos:pos + 2], buf[pos + 2], buf[pos + 3]
+        if id12 != MAGIC:
+            raise GzipError(path, pos, "not a gzip member")
+        if cm != 8:
+            raise GzipError(path, pos, f"compression method {cm} is not DEFLATE")
+        if flg != 4:
+            return Members("gzip", n)
+        xlen = struct.unpack_from("<H", buf, pos + 10)[0]
+        hlen = 12 + xlen
+        if pos + hlen > n:
+            raise GzipError(path, pos, "truncated member header")
+        bsize, x = None, pos + 12
+        while x + 4 <= pos + hlen:
+            si1, si2, slen = buf[x], buf[x + 1], struct.unpack_from("<H", buf, x + 2)[0]
+            if si1 == 66 and si2 == 67 and slen == 2 and x + 6 <= pos + hlen:
+                bsize = struct.unpack_from("<H", buf, x + 4)[0]
+            x += 4 + slen
+        if bsize is None:
+            return Members("gzip", n)
+        end = pos + bsize + 1
+        if bsize + 1 < hlen + 8:
+            raise GzipError(path, pos, f"BSIZE {bsize} leaves no room for the header and trailer")
+        if end > n:
+            raise GzipError(path, pos, f"truncated member (BSIZE {bsize} runs past the end of the file at {n})")
+        isz = struct.unpack_from("<I", buf, end - 4)[0]
+        if isz > BGZF_MAX_ISIZE:
+            return Members("gzip", n)
+        start.append(pos)
+        doff.append(pos + hlen)
+        dlen.append(bsize + 1 - hlen - 8)
+        isize.append(isz)
+        pos = end
+    return Members("bgzf", n, start, doff, dlen, isize)
+
+
+def too_large(path, nbytes: int, limit: int) -> ValueError:
+    return ValueError(f"{path}: inflates to more than {limit} bytes (DGRP_FASTA_RESIDENT_BYTES); compressed input is read whole "
+                      "into device memory, so decompress this file and give the FASTA instead")
+
+
+def inflate_host(buf, path, limit: int) -> bytearray:
+    """Every member of the gzip bytes `buf` inflated with zlib (CRC-32 and ISIZE checked), concatenated.  Raises GzipError for a
+    bad or truncated member and ValueError once the output exceeds `limit` bytes."""
+    out = bytearray()
+    n = len(buf)
+    step = 1 << 20
+    pos = 0
+    while pos < n:
+        d = zlib.decompressobj(31)
+        o = pos
+        while not d.eof:
+            if o >= n:
+                raise GzipError(path, pos, "truncated member")
+            data = buf[o:o + step]                                   # (a copy: no view of the mapping outlives this call)
+            o += len(data)
+            while data:
+                try:
+                    piece = d.decompress(data, limit - len(out) + 1)
+                except zlib.error as e:
+                    raise GzipError(path, pos, str(e)) from None
+                out += piece
+                if len(out) > limit:
+                    raise too_large(path, len(out), limit)
+                data = d.unconsumed_tail
+                if d.eof:
+                    break
+        pos = o - len(d.unused_data)
+    return out
+
+
+def inflate_device(path, members: Members, dev, upload):
+    """The BGZF file's members inflated on the device into one buffer (uint8 tensor of sum(ISIZE) bytes).  `upload(path, size,
+    dev)` puts the compressed file into HBM (the ingest's pinned-slab uploader)."""
+    import ctypes as C
+
+    import torch
+
+    from ._lib import check, lib
+    from .pipeline import stream_ptr
+    L = lib()
+    nmem = int(members.start.size)
+    out_off = np.zeros(nmem + 1, np.int64)
+    np.cumsum(members.isize, out=out_off[1:])
+    total = int(out_off[-1])
+    d_in = upload(path, members.size, dev)
+    d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+    wb = int(L.dgrp_inflate_workspace_bytes(nmem))
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    bad, reason = C.c_int64(-1), C.c_int(0)
+    rc = L.dgrp_inflate_batch(d_in.data_ptr(), members.size, nmem, members.data_off.ctypes.data, members.data_len.ctypes.data,
+                              out_off.ctypes.data, d_out.data_ptr(), total, C.byref(bad), C.byref(reason), work.data_ptr(), wb,
+                              stream_ptr())
+    if rc == -5:                                                     # DGRP_EDATA
+        raise GzipError(path, int(members.start[bad.value]), REASONS.get(reason.value, f"reason {reason.value}"))
+    check(rc, "dgrp_inflate_batch")
+    return d_out
+
+
+class DeviceText:
+    """The inflated bytes of a BGZF file, resident on the device, as the ingest reads them on the host: `t[i]` and `t[a:b]` like
+    the mapping of a plain file.  `prime` fetches every chunk's header line in one gather and one copy; any other slice (the body
+    of a chunk that takes the reference loop) is copied when asked for."""
+
+    def __init__(self, d_text):
+        self.d = d_text
+        self.spans, self.blob = {}, b""
+
+    def prime(self, starts, head_ends) -> None:
+        import torch
+        st = np.asarray(starts[:len(head_ends)], np.int64)
+        ln = np.asarray(head_ends, np.int64) - st
+        offs = np.cumsum(ln) - ln
+        total = int(ln.sum())
+        if total:
+            dev = self.d.device
+            d_ln = torch.from_numpy(ln).to(dev)
+            shift = torch.repeat_interleave(torch.from_numpy(st - offs).to(dev), d_ln, output_size=total)
+            self.blob = self.d[torch.arange(total, device=dev) + shift].cpu().numpy().tobytes()
+        self.spans = dict(zip(st.tolist(), zip(offs.tolist(), (st + ln).tolist())))
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            a, b = k.start, k.stop
+            hit = self.spans.get(a)
+            if hit is not None and hit[1] == b:
+                return self.blob[hit[0]:hit[0] + b - a]
+            return self.d[a:b].cpu().numpy().tobytes()
+        return int(self.d[k])
+
+
+def open_inflated(path, limit: int, dev_fn, upload):
+    """(host view, device bytes, size) of the gzip file `path`: the member walk, then the device (BGZF) or zlib (other gzip).
+    Everything that can be refused -- corrupt headers, an inflated size above `limit` -- is refused before `dev_fn()` is called."""
+    import mmap
+    with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as cm:
+        members = walk_members(cm, path)
+        text: Optional[bytearray] = None
+        if members.kind == "bgzf":
+            total = int(members.isize.sum())
+            if total > limit:
+                raise too_large(path, total, limit)
+        else:
+            _LOG.info("%s: gzip but not BGZF, inflated on the host with zlib; `bgzip` would let the GPU inflate it", path)
+            text = inflate_host(cm, path, limit)
+            total = len(text)
+    if total == 0:
+        return None, None, 0
+    dev = dev_fn()
+    if text is None:
+        d_text = inflate_device(path, members, dev, upload)
+        return DeviceText(d_text), d_text, total
+    import torch
+    return text, torch.frombuffer(text, dtype=torch.uint8).to(dev), total
+
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # the empty member bgzip ends a file with
+BGZF_BLOCK = 0xff00                                                                     # input bytes per member, as bgzip takes them
+
+
+def bgzf_member(data: bytes, level: int = 6, strategy: int = zlib.Z_DEFAULT_STRATEGY) -> bytes:
+    """One BGZF member of `data` (at most 64 KiB) as bgzip lays it out: FLG = FEXTRA, the `BC` subfield with BSIZE, raw DEFLATE,
+    CRC-32 and ISIZE."""
+    co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    body = co.compress(data) + co.flush()
+    bsize = 18 + len(body) + 8 - 1
+    if len(data) > BGZF_MAX_ISIZE or bsize > 0xffff:
+        raise ValueError("a BGZF member holds at most 64 KiB and compresses to at most 64 KiB")
+    head = MAGIC + bytes([8, 4, 0, 0, 0, 0, 0, 255]) + struct.pack("<HBBHH", 6, 66, 67, 2, bsize)
+    return head + body + struct.pack("<II", zlib.crc32(data), len(data))
+
+
+def bgzf_compress(data: bytes, level: int = 6, strategy: int = zlib.Z_DEFAULT_STRATEGY, block: int = BGZF_BLOCK,
+                  eof: bool = True) -> bytes:
+    """`data` as a BGZF file written the way bgzip writes it: members of `block` input bytes, then the EOF member."""
+    out = [bgzf_member(data[o:o + block], level, strategy) for o in range(0, len(data), block)]
+    return b"".join(out) + (BGZF_EOF if eof else b"")

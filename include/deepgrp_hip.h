@@ -36,6 +36,7 @@ extern "C" {
 #define DGRP_EHIP (-2)     /* a HIP runtime call or kernel launch failed              */
 #define DGRP_ENOMEM (-3)   /* caller-provided workspace / output capacity too small   */
 #define DGRP_ENODEV (-4)   /* no gfx950 device visible                                */
+/* DGRP_EDATA (-5): corrupt compressed input, see dgrp_inflate_batch */
 
 #define DGRP_ABI_VERSION 1
 
@@ -335,6 +336,41 @@ int dgrp_paint_rows_batch(int8_t *d_labels, int64_t nrec, const int64_t *h_off, 
 int dgrp_row_hits_batch(const int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
                         const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_hits, void *d_work, int64_t work_bytes,
                         void *stream);
+
+/* ---- compressed input (an addition; the reference reads plain text only): DEFLATE (RFC 1951) streams inflated by the
+ * same decode core on the device and on the host (deepgrp_amd/csrc/inflate.h).  A stream that cannot be decoded gives
+ * DGRP_EDATA and one of these reasons; no read or write leaves the stream's input and output slices. */
+#define DGRP_EDATA (-5)                /* corrupt compressed data (reason below)                  */
+#define DGRP_INFLATE_OK 0
+#define DGRP_INFLATE_EINPUT 1          /* the input ends inside the stream                         */
+#define DGRP_INFLATE_EBLOCK 2          /* block type 3                                              */
+#define DGRP_INFLATE_ESTORED 3         /* stored block whose LEN and NLEN do not match              */
+#define DGRP_INFLATE_ECODES 4          /* over-subscribed, incomplete or malformed code length set  */
+#define DGRP_INFLATE_ESYMBOL 5         /* a symbol that no valid stream contains                    */
+#define DGRP_INFLATE_EDIST 6           /* a distance before the start of the output                 */
+#define DGRP_INFLATE_EOUTPUT 7         /* more output than the slice (ISIZE) allows                 */
+#define DGRP_INFLATE_ECRC 8            /* gzip member: CRC-32 differs from its trailer              */
+#define DGRP_INFLATE_EISIZE 9          /* gzip member: fewer bytes than its trailer's ISIZE         */
+#define DGRP_INFLATE_ETRAIL 10         /* gzip member: the stream ends before the member's trailer  */
+
+/* One raw DEFLATE stream h_in[0, in_len) inflated on the HOST (no device needed): the output goes to h_out[0, out_cap);
+ * *h_out_len = bytes produced and *h_in_used = input bytes up to the end of the final block (also on failure: how far it got);
+ * *h_reason = DGRP_INFLATE_* (0 on success).  Returns 0, DGRP_EDATA for a bad stream, DGRP_EINVAL for bad arguments
+ * (sizes above 2^31 - 1 included).  Synchronous. */
+int dgrp_inflate_raw_host(const uint8_t *h_in, int64_t in_len, uint8_t *h_out, int64_t out_cap, int64_t *h_out_len,
+                          int64_t *h_in_used, int *h_reason);
+
+/* nmem gzip members of ONE device buffer inflated in one launch (BGZF: up to 64 KiB each).  Member m's DEFLATE data is
+ * d_in[h_in_off[m], h_in_off[m] + h_in_len[m]) and its 8-byte trailer (CRC-32, ISIZE, little endian) follows directly; all of it
+ * lies inside d_in[0, in_bytes).  Its output is d_out[h_out_off[m], h_out_off[m+1]) (h_out_off: nmem + 1 ascending values, the
+ * prefix sum of the ISIZEs, h_out_off[nmem] <= out_bytes, each slice < 2^31).  Every member must end its final block exactly at
+ * its trailer and match the trailer's CRC-32 and ISIZE (checked on the device).  On DGRP_EDATA *h_bad = the lowest failing member
+ * and *h_reason its DGRP_INFLATE_* reason (bytes of failing members are undefined); on success *h_bad = -1, *h_reason = 0.
+ * Workspace dgrp_inflate_workspace_bytes(nmem).  Synchronous (one read-back of the per-member status). */
+int64_t dgrp_inflate_workspace_bytes(int64_t nmem);
+int dgrp_inflate_batch(const uint8_t *d_in, int64_t in_bytes, int64_t nmem, const int64_t *h_in_off, const int64_t *h_in_len,
+                       const int64_t *h_out_off, uint8_t *d_out, int64_t out_bytes, int64_t *h_bad, int *h_reason, void *d_work,
+                       int64_t work_bytes, void *stream);
 
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this

@@ -1,0 +1,358 @@
+"""Compressed input without a GPU: the host entry of the DEFLATE decode core (dgrp_inflate_raw_host, the same code the device
+runs) against zlib, a corrupt corpus that must come back as reasons, the argument checks of both entries, the gzip member walk,
+and the refusals of compressed input that happen before any device work."""
+import ctypes as C
+import gzip
+import zlib
+
+import numpy as np
+import pytest
+
+from deepgrp_amd import gz
+from deepgrp_amd._lib import lib
+
+EINVAL, ENOMEM, EDATA = -1, -3, -5
+EINPUT, EBLOCK, ESTORED, ECODES, ESYMBOL, EDIST, EOUTPUT = 1, 2, 3, 4, 5, 6, 7
+STRATEGIES = {"default": zlib.Z_DEFAULT_STRATEGY, "fixed": zlib.Z_FIXED, "rle": zlib.Z_RLE, "huffman_only": zlib.Z_HUFFMAN_ONLY,
+              "filtered": zlib.Z_FILTERED}
+
+
+def inflate(comp: bytes, cap: int):
+    """-> (return code, output, input bytes used, reason)"""
+    out = (C.c_uint8 * max(cap, 1))()
+    ol, iu, r = C.c_int64(-1), C.c_int64(-1), C.c_int(-1)
+    rc = lib().dgrp_inflate_raw_host(comp, len(comp), out, cap, C.byref(ol), C.byref(iu), C.byref(r))
+    assert 0 <= ol.value <= cap and 0 <= iu.value <= len(comp)
+    return rc, bytes(out[:ol.value]), iu.value, r.value
+
+
+def deflate(data: bytes, level: int, strategy: int) -> bytes:
+    co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    return co.compress(data) + co.flush()
+
+
+# ---------------------------------------------------------------- a hand-written fixed-Huffman encoder (streams zlib never emits)
+class Bits:
+    def __init__(self):
+        self.acc, self.n = 0, 0
+
+    def put(self, v: int, k: int):                 # k bits of v, LSB first (header fields, extra bits)
+        self.acc |= (v & ((1 << k) - 1)) << self.n
+        self.n += k
+
+    def code(self, c: int, k: int):                 # a Huffman code: MSB first
+        self.put(int(format(c, f"0{k}b")[::-1], 2), k)
+
+    def bytes(self) -> bytes:
+        return self.acc.to_bytes((self.n + 7) // 8, "little")
+
+
+def fixed_lit(b: Bits, sym: int):
+    if sym < 144:
+        b.code(0x30 + sym, 8)
+    elif sym < 256:
+        b.code(0x190 + sym - 144, 9)
+    elif sym < 280:
+        b.code(sym - 256, 7)
+    else:
+        b.code(0xC0 + sym - 280, 8)
+
+
+def fixed_match(b: Bits, length: int, dist: int):
+    lbase = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+    lext = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
+    dbase = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
+             8193, 12289, 16385, 24577]
+    dext = [0, 0, 0, 0] + [k // 2 for k in range(2, 28)]
+    i = max(k for k in range(29) if lbase[k] <= length and (k == 28) == (length == 258))
+    fixed_lit(b, 257 + i)
+    b.put(length - lbase[i], lext[i])
+    d = max(k for k in range(30) if dbase[k] <= dist)
+    b.code(d, 5)
+    b.put(dist - dbase[d], dext[d])
+
+
+def fixed_stream(items, final=True) -> bytes:
+    """items: ints (literals / raw symbols) or (length, distance) pairs; one fixed block ended by symbol 256."""
+    b = Bits()
+    b.put(1 if final else 0, 1)
+    b.put(1, 2)
+    for it in items:
+        if isinstance(it, tuple):
+            fixed_match(b, *it)
+        else:
+            fixed_lit(b, it)
+    fixed_lit(b, 256)
+    return b.bytes()
+
+
+# ---------------------------------------------------------------- inputs
+def _inputs():
+    rng = np.random.default_rng(11)
+    acgt = rng.choice(list(b"ACGT"), size=50_000).astype(np.uint8).tobytes()
+    fasta = b">chr1 test\n" + b"\n".join(acgt[i:i + 60] for i in range(0, len(acgt), 60)) + b"\n"
+    nrun = b"N" * 30_000 + acgt[:500] + b"N" * 20_000 + b"n" * 3
+    rand = rng.integers(0, 256, size=40_000, dtype=np.uint8).tobytes()
+    x = rng.integers(0, 256, size=300, dtype=np.uint8).tobytes()
+    far = x + rng.integers(0, 256, size=32_768 - 300, dtype=np.uint8).tobytes() + x + x[:100] * 3
+    return {"fasta": fasta, "nrun": nrun, "random": rand, "far": far, "empty": b"", "max": (acgt + acgt)[:65536]}
+
+
+INPUTS = _inputs()
+
+
+@pytest.mark.parametrize("strategy", sorted(STRATEGIES))
+@pytest.mark.parametrize("level", [0, 1, 6, 9])
+@pytest.mark.parametrize("name", sorted(INPUTS))
+def test_host_entry_equals_zlib(name, level, strategy):
+    data = INPUTS[name]
+    comp = deflate(data, level, STRATEGIES[strategy])
+    want = zlib.decompress(comp, -15)
+    assert want == data
+    rc, out, used, reason = inflate(comp, len(data))
+    assert (rc, reason) == (0, 0)
+    assert out == want and used == len(comp)
+
+
+def test_hand_encoded_longest_match_at_the_farthest_distance():
+    rng = np.random.default_rng(2)
+    lits = rng.integers(0, 256, size=32_768).tolist()
+    items = lits + [(258, 32_768), (258, 32_768), (3, 1), (258, 1)]
+    comp = fixed_stream(items)
+    want = zlib.decompress(comp, -15)
+    assert len(want) == 32_768 + 2 * 258 + 3 + 258
+    rc, out, used, reason = inflate(comp, len(want))
+    assert (rc, reason) == (0, 0) and out == want and used == len(comp)
+    assert inflate(comp, len(want) - 1)[3] == EOUTPUT          # one byte short
+
+
+def test_output_of_exactly_64k_and_over_the_cap():
+    data = INPUTS["max"]
+    for level in (0, 6):
+        comp = deflate(data, level, zlib.Z_DEFAULT_STRATEGY)
+        assert inflate(comp, 65536)[:2] == (0, data)
+        rc, out, _used, reason = inflate(comp, 65535)
+        assert (rc, reason) == (EDATA, EOUTPUT) and out == data[:len(out)]
+
+
+def _dynamic_header(clen, hlit=0, hdist=0):
+    """A dynamic block header: BFINAL=1, BTYPE=2, the code length code lengths `clen` in transmission order."""
+    b = Bits()
+    b.put(1, 1)
+    b.put(2, 2)
+    b.put(hlit, 5)
+    b.put(hdist, 5)
+    b.put(len(clen) - 4, 4)
+    for v in clen:
+        b.put(v, 3)
+    return b
+
+
+def _corrupt_corpus():
+    """(name, stream, output cap, expected reason or None = any failure)."""
+    data = INPUTS["fasta"][:20_000]
+    good = deflate(data, 6, zlib.Z_DEFAULT_STRATEGY)
+    cases = []
+    for k in (0, 1, 2, 5, len(good) // 2, len(good) - 1):
+        cases.append((f"truncated_{k}", good[:k], len(data), EINPUT))
+    cases.append(("block_type_3", bytes([0x07, 0, 0, 0]), 100, EBLOCK))
+    cases.append(("stored_len_nlen", bytes([0x01, 5, 0, 0, 0]) + b"hello", 100, ESTORED))
+    cases.append(("stored_truncated", bytes([0x01, 5, 0, 0xFA, 0xFF]) + b"hel", 100, EINPUT))
+    cases.append(("stored_over_cap", bytes([0x01, 5, 0, 0xFA, 0xFF]) + b"hello", 4, EOUTPUT))
+    cases.append(("distance_too_far", fixed_stream([65, (3, 2)]), 100, EDIST))
+    cases.append(("distance_before_any_output", fixed_stream([(3, 1)]), 100, EDIST))
+    cases.append(("literal_286", fixed_stream([65, 286]), 100, ESYMBOL))
+    b = Bits()
+    b.put(1, 1), b.put(1, 2), fixed_lit(b, 65), fixed_lit(b, 257), b.code(30, 5)
+    cases.append(("distance_code_30", b.bytes() + b"\0" * 4, 100, ESYMBOL))
+    cases.append(("clen_oversubscribed", _dynamic_header([1] * 19).bytes() + b"\0" * 8, 100, ECODES))
+    cases.append(("clen_incomplete", _dynamic_header([2, 0, 0, 0]).bytes() + b"\0" * 8, 100, ECODES))
+    b = _dynamic_header([1, 0, 1, 0])                    # codes for 16 and 18 only: the first symbol is a repeat of nothing
+    b.put(0, 1)
+    cases.append(("repeat_without_previous", b.bytes() + b"\0" * 8, 100, ECODES))
+    b = _dynamic_header([0] * 3 + [1] + [0] * 14 + [1], hlit=31)     # 0 and 1 only; hlit = 288 lengths > 286
+    cases.append(("too_many_lengths", b.bytes() + b"\0" * 8, 100, ECODES))
+    b = _dynamic_header([0] * 3 + [1] + [0] * 14 + [1])              # every literal/length code length 0: no end-of-block code
+    for _ in range(258):
+        b.put(0, 1)
+    cases.append(("no_end_of_block", b.bytes() + b"\0" * 8, 100, ECODES))
+    cases.append(("output_over_cap", good, len(data) - 1, EOUTPUT))
+    cases.append(("empty_input", b"", 100, EINPUT))
+    rng = np.random.default_rng(9)
+    for k in range(40):
+        bad = bytearray(good)
+        bad[int(rng.integers(0, len(bad)))] ^= 1 << int(rng.integers(0, 8))
+        cases.append((f"flipped_{k}", bytes(bad), 1 << 20, None))
+    for k in range(20):
+        cases.append((f"random_{k}", rng.integers(0, 256, size=int(rng.integers(1, 400)), dtype=np.uint8).tobytes(), 1 << 16, None))
+    return cases
+
+
+CORRUPT = _corrupt_corpus()
+
+
+@pytest.mark.parametrize("name,stream,cap,reason", CORRUPT, ids=[c[0] for c in CORRUPT])
+def test_corrupt_corpus(name, stream, cap, reason):
+    rc, out, used, got = inflate(stream, cap)
+    if reason is not None:
+        assert (rc, got) == (EDATA, reason)
+        return
+    # no expectation of our own: agree with zlib on whether the stream is valid, and on its output where it is
+    d = zlib.decompressobj(-15)
+    try:
+        want = d.decompress(stream)
+        ok = d.eof and len(want) <= cap
+    except zlib.error:
+        ok = False
+    if ok:
+        assert (rc, got, out, used) == (0, 0, want, len(stream) - len(d.unused_data))
+    else:
+        assert rc == EDATA and got > 0
+
+
+# ---------------------------------------------------------------- argument checks (DGRP_EINVAL without a GPU)
+P = 0x10000
+I64 = lambda: C.pointer(C.c_int64())
+INT = lambda: C.pointer(C.c_int())
+
+ARG_CASES = [
+    ("dgrp_inflate_raw_host", lambda: (P, 10, P, 10, None, I64(), INT()), EINVAL),
+    ("dgrp_inflate_raw_host", lambda: (P, 10, P, 10, I64(), I64(), None), EINVAL),
+    ("dgrp_inflate_raw_host", lambda: (P, -1, P, 10, I64(), I64(), INT()), EINVAL),
+    ("dgrp_inflate_raw_host", lambda: (P, 10, P, 1 << 31, I64(), I64(), INT()), EINVAL),
+    ("dgrp_inflate_raw_host", lambda: (None, 10, P, 10, I64(), I64(), INT()), EINVAL),
+    ("dgrp_inflate_raw_host", lambda: (P, 10, None, 10, I64(), I64(), INT()), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, -1, None, None, None, P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, None, None, None, P, 100, None, INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, None, None, None, P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, *_tab([0], [93], [0, 10]), P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, *_tab([-1], [10], [0, 10]), P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, *_tab([0], [10], [0, 101]), P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 2, *_tab([0, 20], [10, 10], [0, 10, 5]), P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (None, 100, 1, *_tab([0], [10], [0, 10]), P, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, *_tab([0], [10], [0, 10]), None, 100, I64(), INT(), P, 1 << 20, None), EINVAL),
+    ("dgrp_inflate_batch", lambda: (P, 100, 1, *_tab([0], [10], [0, 10]), P, 100, I64(), INT(), P, 8, None), ENOMEM),
+]
+_KEEP = []
+
+
+def _tab(in_off, in_len, out_off):
+    arrs = [np.asarray(a, np.int64) for a in (in_off, in_len, out_off)]
+    _KEEP.append(arrs)
+    return [a.ctypes.data for a in arrs]
+
+
+@pytest.mark.parametrize("k", range(len(ARG_CASES)))
+def test_argument_checks(k):
+    name, args, code = ARG_CASES[k]
+    assert getattr(lib(), name)(*args()) == code
+    assert name.encode() in lib().dgrp_last_error()
+
+
+def test_batch_with_no_members_is_a_no_op():
+    bad, reason = C.c_int64(7), C.c_int(7)
+    assert lib().dgrp_inflate_batch(None, 0, 0, None, None, None, None, 0, C.byref(bad), C.byref(reason), None, 0, None) == 0
+    assert (bad.value, reason.value) == (-1, 0)
+
+
+# ---------------------------------------------------------------- the member walk
+def test_walk_bgzf_with_eof_block():
+    data = INPUTS["fasta"] * 3
+    comp = gz.bgzf_compress(data)
+    m = gz.walk_members(comp)
+    assert m.kind == "bgzf" and m.size == len(comp)
+    assert m.start.size == (len(data) + gz.BGZF_BLOCK - 1) // gz.BGZF_BLOCK + 1 and m.isize[-1] == 0
+    assert int(m.isize.sum()) == len(data) and m.start[0] == 0
+    for k in range(m.start.size):                        # every member's DEFLATE data inflates to its ISIZE
+        raw = comp[m.data_off[k]:m.data_off[k] + m.data_len[k]]
+        assert len(zlib.decompress(raw, -15)) == m.isize[k]
+    only_eof = gz.walk_members(gz.BGZF_EOF)
+    assert only_eof.kind == "bgzf" and only_eof.isize.tolist() == [0]
+
+
+def test_walk_other_gzip():
+    data = INPUTS["fasta"]
+    assert gz.walk_members(gzip.compress(data)).kind == "gzip"                                 # one member, FNAME-less gzip
+    assert gz.walk_members(gz.bgzf_compress(data, eof=False) + gzip.compress(data)).kind == "gzip"   # mixed members
+    big = gz.bgzf_member(b"A" * 100)
+    big = big[:-4] + (70_000).to_bytes(4, "little")                                         # ISIZE above 64 KiB: not BGZF
+    assert gz.walk_members(big).kind == "gzip"
+
+
+def test_walk_truncated_and_trailing_garbage():
+    comp = gz.bgzf_compress(INPUTS["fasta"] * 3, eof=False)
+    m = gz.walk_members(comp)
+    last = int(m.start[-1])
+    with pytest.raises(gz.GzipError) as e:
+        gz.walk_members(comp[:-10], "t.fa.gz")
+    assert e.value.offset == last and "t.fa.gz" in str(e.value) and f"offset {last}" in str(e.value)
+    with pytest.raises(gz.GzipError) as e:
+        gz.walk_members(comp[:last + 7], "t.fa.gz")
+    assert e.value.offset == last
+    with pytest.raises(gz.GzipError) as e:
+        gz.walk_members(comp + b"trailing garbage here", "t.fa.gz")
+    assert e.value.offset == len(comp)
+
+
+def test_zlib_path_names_the_bad_member():
+    a, b = INPUTS["fasta"], INPUTS["nrun"]
+    ga, gb = gzip.compress(a), gzip.compress(b)
+    assert gz.inflate_host(ga + gb, "x.gz", 1 << 30) == a + b
+    bad = bytearray(ga + gb)
+    bad[len(ga) + len(gb) - 6] ^= 1                                  # second member's CRC-32
+    with pytest.raises(gz.GzipError) as e:
+        gz.inflate_host(bytes(bad), "x.gz", 1 << 30)
+    assert e.value.offset == len(ga)
+    with pytest.raises(gz.GzipError) as e:
+        gz.inflate_host(ga + gb[:len(gb) // 2], "x.gz", 1 << 30)
+    assert e.value.offset == len(ga) and "truncated" in str(e.value)
+    with pytest.raises(ValueError, match="inflates to more than"):
+        gz.inflate_host(ga + gb, "x.gz", len(a) + 10)
+
+
+# ---------------------------------------------------------------- refusals before any device work
+@pytest.fixture
+def no_gpu(monkeypatch):
+    """Any attempt to reach the device fails the test."""
+    from deepgrp_amd import pipeline
+
+    def touched(*_a, **_k):
+        raise AssertionError("the GPU was touched")
+    monkeypatch.setattr(pipeline, "require_gpu", touched)
+
+
+@pytest.mark.parametrize("form", ["bgzf", "gzip"])
+def test_refuses_inflated_size_above_resident_bytes(tmp_path, monkeypatch, no_gpu, form):
+    from deepgrp_amd import fasta
+    data = INPUTS["fasta"]
+    p = tmp_path / "x.fa.gz"
+    p.write_bytes(gz.bgzf_compress(data) if form == "bgzf" else gzip.compress(data))
+    monkeypatch.setattr(fasta, "RESIDENT_BYTES", len(data) - 1)
+    with pytest.raises(ValueError, match="inflates to more than"):
+        list(fasta.read_multi_fasta_device(str(p)))
+
+
+def test_corrupt_plain_gzip_is_refused_before_the_device(tmp_path, no_gpu):
+    from deepgrp_amd import fasta
+    comp = bytearray(gzip.compress(INPUTS["fasta"]))
+    comp[-7] ^= 2
+    p = tmp_path / "x.fa.gz"
+    p.write_bytes(bytes(comp))
+    with pytest.raises(gz.GzipError, match="offset 0"):
+        list(fasta.read_multi_fasta_device(str(p)))
+
+
+def test_cli_refuses_sharded_and_masked_compressed_input(tmp_path, monkeypatch, no_gpu):
+    from deepgrp_amd.__main__ import main
+    p = tmp_path / "in.fa"                                              # the name does not matter: the magic bytes do
+    p.write_bytes(gz.bgzf_compress(INPUTS["fasta"]))
+    model = str(tmp_path / "no_model.h5")
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    with pytest.raises(SystemExit) as e:
+        main(["predict", model, str(p)])
+    assert "cannot be sharded" in str(e.value.code) and str(p) in str(e.value.code)
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    with pytest.raises(SystemExit) as e:
+        main(["predict", model, str(p), "--mask_dir", str(tmp_path / "m")])
+    assert "--mask_dir" in str(e.value.code) and "gzip" in str(e.value.code)
+    assert not (tmp_path / "m").exists()
