@@ -9,6 +9,8 @@ Differences, all additive:
     the GPUs and rank 0 writes the rows in input order;
   * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
     (deepgrp_amd/masking.py);
+  * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B]` also writes the per-base class
+    probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
@@ -132,6 +134,22 @@ def _add_mask_options(parser, suppress: bool) -> None:
                         help="(addition) comma-separated labels to mask, e.g. 1,3 (default: every label > 0)")
 
 
+def _add_track_options(parser) -> None:
+    """The probability-track flags, like the masking flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--track_dir", type=str, default=s,
+                        help="(addition) also write the merged per-base probabilities of every selected class as bedGraph files "
+                             "DIR/<basename of the input>.class<c>.bedGraph ('stdin' for '-'); with --fast they are those of the "
+                             "fp16-operand kernels")
+    parser.add_argument("--track_classes", type=_class_list, default=s,
+                        help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
+    parser.add_argument("--track_digits", type=int, default=s,
+                        help="(addition) decimals of the track values, 1..4 (default: 2)")
+    parser.add_argument("--track_bin", type=int, default=s,
+                        help="(addition) bin width of the tracks in bases, >= 1; a bin's value is the maximum over its bases "
+                             "(default: 1)")
+
+
 class CommandLineParser:
     """Commandline parser (deepgrp/__main__.py:86-250)."""
 
@@ -156,6 +174,7 @@ class CommandLineParser:
         self.parser.add_argument("--xla", action="store_true", help="Accepted for compatibility (ignored)")
         self.parser.add_argument("-v", "--verbose", action="count", default=0, help="Increase verbosity")
         _add_mask_options(self.parser, suppress=True)
+        _add_track_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (not available in deepgrp_amd)")
         train.add_argument("parameter", type=str)
@@ -189,6 +208,7 @@ class CommandLineParser:
                              help="multi-GPU only: spread the windows of EVERY record over all GPUs (for a few huge "
                                   "records) instead of sharding whole records")
         _add_mask_options(predict, suppress=True)
+        _add_track_options(predict)
         evaluate = subparsers.add_parser(
             name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
             description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
@@ -218,7 +238,8 @@ class CommandLineParser:
         # README form `deepgrp <modelfile> <fastafile>`: insert the sub-command before the first positional
         if not any(a in ("predict", "train", "verify", "evaluate") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
-                           "--threads", "-t", "--mask_dir", "--mask", "--mask_classes"}
+                           "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
+                           "--track_digits", "--track_bin"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -254,6 +275,12 @@ class CommandLineParser:
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
         masks = CommandLineParser._mask_plan(args)              # refusals come before anything runs
+        from . import tracks as tk
+        track_plan = tk.plan(args)
+        track_spec = None
+        if track_plan is not None:
+            from .model import read_keras_hdf5
+            track_spec = tk.resolve(track_plan, int(read_keras_hdf5(args.model)["ff_kernel"].shape[-1]))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             from .gz import compressed_inputs
             packed = compressed_inputs(args.FASTA)
@@ -299,7 +326,7 @@ class CommandLineParser:
 
         records_of = _records_of
 
-        runner = RecordRunner(pipe)
+        runner = RecordRunner(pipe, tracks=track_spec)
 
         try:
             if world == 1:
@@ -308,7 +335,12 @@ class CommandLineParser:
                     _LOG.info("Processing %s", filename)
                     t_file, bases = time.perf_counter(), 0
                     kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
-                    if _LOG.isEnabledFor(logging.DEBUG):
+                    if track_spec is not None:
+                        # --track_dir: record by record (merged -> tracks -> labels -> segments); the input's track files are renamed
+                        # into place when all of its records are done, and removed when one raises
+                        bases = CommandLineParser._predict_tracked(pipe, runner, filename, records_of(filename), outstream, kept,
+                                                                   tk.TrackFiles(track_plan, track_spec, filename), track_spec)
+                    elif _LOG.isEnabledFor(logging.DEBUG):
                         # -vv: record by record through the staged form of the same path, a device sync and a clock around every
                         # stage (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
                         for header, rec in records_of(filename):
@@ -401,9 +433,42 @@ class CommandLineParser:
             yield header, rec
 
     @staticmethod
-    def _predict_staged(pipe, header, rec):
+    def _predict_tracked(pipe, runner, filename, records, outstream, kept, files, spec) -> int:
+        """predict's loop over one input with --track_dir: TSV rows as without it, the track text of every record to `files`
+        (tracks.TrackFiles).  -> bases read"""
+        from .evaluation import record_name
+        from .runner import rows_text
+        from .tracks import record_texts
+        try:
+            if _LOG.isEnabledFor(logging.DEBUG):
+                bases = 0
+                for header, rec in records:
+                    name = record_name(filename, header)
+                    sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec))
+                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, sink)
+                    bases += n
+                    outstream.write(rows_text(filename, header, rows))
+                    if kept is not None:
+                        kept.add(rows, 1)
+            else:
+                keyed = (((header, record_name(filename, header)), rec) for header, rec in records)
+                for (header, _name), rows, texts in runner.track_results(CommandLineParser._counted(keyed, lambda n: None)):
+                    outstream.write(rows_text(filename, header, rows))
+                    files.write(texts)
+                    if kept is not None:
+                        kept.add(rows, 1)
+                bases = CommandLineParser._last_count
+        except BaseException:
+            files.abort()
+            raise
+        files.commit()
+        return bases
+
+    @staticmethod
+    def _predict_staged(pipe, header, rec, track_sink=None):
         """One record through encode -> forward + merge -> scores / MSS / vote (or softmax) -> segments, each stage between device
-        syncs, with the reference's debug lines (deepgrp/__main__.py:69-79) carrying the stage's milliseconds.  -> (rows, bases)"""
+        syncs, with the reference's debug lines (deepgrp/__main__.py:69-79) carrying the stage's milliseconds.  -> (rows, bases)
+        track_sink(merged, startpos), if given, runs between the forward pass and the labels (--track_dir)."""
         import time
 
         import torch
@@ -431,6 +496,10 @@ class CommandLineParser:
         merged = pipe.merged(d_idx)
         ms_fwd = lap(t)
         _LOG.debug("Finish prediction.")
+        if track_sink is not None:
+            t = time.perf_counter()
+            track_sink(merged, startpos)
+            _LOG.debug("%s: probability tracks %.2f ms", header, lap(t))
         t = time.perf_counter()
         if pipe.use_mss:
             _LOG.debug("Applying MSS.")
@@ -640,6 +709,8 @@ class CommandLineParser:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
         if getattr(args, "mask_dir", None) is not None:
             sys.exit("--mask_dir belongs to predict, not evaluate")
+        if getattr(args, "track_dir", None) is not None:
+            sys.exit("--track_dir belongs to predict, not evaluate")
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
         import json

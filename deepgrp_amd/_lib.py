@@ -36,6 +36,8 @@ _SIGNATURES = {
     "dgrp_fasta_mask_batch": (cint, [vp, i64, vp, vp, vp, vp, cint, C.c_uint64, vp, vp, i64, vp]),
     "dgrp_format_rows_bound": (i64, [i64, i64]),
     "dgrp_format_rows": (cint, [vp, vp, i64, cint, vp, i64, vp, i64, C.POINTER(i64)]),
+    "dgrp_track_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_track_text": (cint, [vp, i64, cint, cint, cint, i64, i64, C.c_char_p, i64, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_window_count": (i64, [i64, i64, i64]),
     "dgrp_windows_onehot": (cint, [vp, i64, i64, i64, i64, i64, cint, vp, vp]),
     "dgrp_model_create": (cint, [C.POINTER(vp), cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]),

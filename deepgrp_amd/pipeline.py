@@ -431,6 +431,34 @@ class ContigPipeline:
         host = rec[: total * SEGMENT_DTYPE.itemsize].cpu().numpy()
         return host.view(SEGMENT_DTYPE).copy()
 
+    # predict --track_dir
+    def track_text(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> bytes:
+        """bedGraph lines of class `cls` of one record's merged probabilities (dgrp_track_text): `name` (str, surrogateescape, or
+        bytes) in the first column, row i at coordinate startpos + i, bins of `bin` bases, values with `digits` decimals."""
+        L = lib()
+        if merged.dtype != torch.float32 or merged.ndim != 2 or not merged.is_contiguous():
+            raise ValueError("track_text takes the contiguous float32 [n, C] array of merged()")
+        n, c = merged.shape
+        raw = name if isinstance(name, bytes) else name.encode("utf-8", "surrogateescape")
+        if n == 0:
+            return b""
+        dev = merged.device
+        wb = L.dgrp_track_workspace_bytes(n, bin)
+        if wb <= 0:
+            raise ValueError(f"track_text: bad record length {n} or bin {bin}")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        nb = n // bin + 2
+        cap = min(nb * (len(raw) + 50), (1 << 20) + nb * (len(raw) + 12))      # (a line per bin at most; the guess fits most runs)
+        total = C.c_int64(0)
+        while True:
+            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            check(L.dgrp_track_text(_ptr(merged), n, c, int(cls), int(digits), int(bin), int(startpos), raw, len(raw), _ptr(text),
+                                    cap, C.byref(total), _ptr(work), wb, stream_ptr()), "dgrp_track_text")
+            if total.value <= cap:
+                break
+            cap = int(total.value)                          # more text than guessed: run again with room for all of it
+        return text[:total.value].cpu().numpy().tobytes()
+
     def run_idx(self, d_idx: torch.Tensor, startpos: int, contig: int = 0) -> np.ndarray:
         """Segment records of one record whose class indices are on the device: one dgrp_predict_record call
         (the staged merged -> labels -> segments path is kept for callers that time or inspect the stages)."""

@@ -8,13 +8,19 @@ import collections
 import os
 import threading
 from concurrent.futures import ThreadPoolExecutor
-from typing import Iterable, Iterator, List, Tuple
+from typing import Iterable, Iterator, List, NamedTuple, Tuple
 
 import numpy as np
 import torch
 
 from .fasta import DeviceRecord
 from .pipeline import ContigPipeline
+
+class _Tracked(NamedTuple):
+    """A work item of track_results: one record and the name of its track lines."""
+    name: str
+    rec: object
+
 
 _BATCH = object()             # key slot of a work item that is a batch of records (never equal to a user's key, e.g. a header "batch")
 SMALL_RECORD = 1 << 18        # bases: up to here a record may join a batch
@@ -73,8 +79,9 @@ class RecordRunner:
     """Runs (key, record) pairs -- record = DeviceRecord or sequence text -- and yields results in input order:
     ("one", key, rows) for a record on its own, ("batch", [keys], rows) for a batch (rows["contig"] indexes the keys)."""
 
-    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29):
+    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None):
         self.pipe = pipe
+        self.tracks = tracks          # tracks.TrackSpec: records run one by one through the staged path (track_results)
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
@@ -87,6 +94,22 @@ class RecordRunner:
                 raise ValueError("negative dimensions are not allowed")     # all-N record, sequence.pyx:32
             return self.pipe.run_idx(rec.d_idx, rec.startpos, contig)
         return self.pipe.run(rec, contig)
+
+    def run_tracked(self, rec, name: str):
+        """(rows, track texts) of one record: merged -> the text of every class of self.tracks -> labels -> segments."""
+        from .pipeline import SEGMENT_DTYPE, upload_sequence
+        from .tracks import record_texts
+        if isinstance(rec, DeviceRecord):
+            if rec.length < 0:
+                raise ValueError("negative dimensions are not allowed")     # all-N record, sequence.pyx:32
+            startpos, d_idx = rec.startpos, rec.d_idx
+        else:
+            startpos, d_idx = upload_sequence(rec.encode("utf-8") if isinstance(rec, str) else bytes(rec))
+        if d_idx.numel() == 0:
+            return np.zeros(0, SEGMENT_DTYPE), [b""] * len(self.tracks.classes)
+        merged = self.pipe.merged(d_idx)
+        texts = record_texts(self.pipe, merged, startpos, name, self.tracks)
+        return self.pipe.segments(self.pipe.labels(merged), startpos), texts
 
     # ---- batching
     def _batch_cost(self, n: int) -> int:
@@ -102,7 +125,7 @@ class RecordRunner:
         else stays (key, record)."""
         group: List[Tuple[object, DeviceRecord]] = []
         cost = 0
-        batchable = self.pipe.batchable()
+        batchable = self.pipe.batchable() and self.tracks is None
         for key, rec in records:
             small = batchable and isinstance(rec, DeviceRecord) and rec.base is not None and 1 <= rec.length <= SMALL_RECORD
             if small:
@@ -121,6 +144,8 @@ class RecordRunner:
             yield _BATCH, group
 
     def run_item(self, item):
+        if isinstance(item, _Tracked):
+            return self.run_tracked(item.rec, item.name)
         if isinstance(item, list):                        # a batch: rows of all its records, contig = position in the batch
             rows = self.pipe.run_batch(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
                                        [r.startpos for _k, r in item], list(range(len(item))))
@@ -130,6 +155,8 @@ class RecordRunner:
     # ---- ordered execution
     @staticmethod
     def _size(item) -> int:
+        if isinstance(item, _Tracked):
+            item = item.rec
         if isinstance(item, list):
             return sum(r.length for _k, r in item)
         return item.d_idx.numel() if isinstance(item, DeviceRecord) else len(item)
@@ -176,3 +203,10 @@ class RecordRunner:
                 yield "batch", keys, rows
             else:
                 yield "one", key, result
+
+    def track_results(self, records: Iterable[Tuple[object, object]]):
+        """With self.tracks: (key, rows, texts) per record in input order; every key is (header, name), name the first column of
+        the record's track lines (evaluation.record_name), and texts[k] is the track text of class self.tracks.classes[k]."""
+        items = ((key, _Tracked(key[1], rec)) for key, rec in records)
+        for key, (rows, texts) in self.in_order(items):
+            yield key, rows, texts

@@ -283,6 +283,20 @@ int64_t dgrp_format_rows_bound(int64_t nrows, int64_t longest_prefix);
 int dgrp_format_rows(const char *prefixes, const int64_t *prefix_off, int64_t nprefix, int by_contig,
                      const dgrp_segment *rows, int64_t nrows, char *out, int64_t cap, int64_t *written);
 
+/* ---- probability tracks (an addition, predict --track_dir; the reference writes no probabilities): class `cls` of ONE record's
+ * merged probabilities d_probs [n, C] float32 (device) as 4-column bedGraph text "name\tstart\tend\tvalue\n" in d_text (device).
+ * Row i of d_probs is record coordinate offset + i (offset = startpos).  Bin k is [k * bin, (k + 1) * bin) of those coordinates,
+ * clipped to [offset, offset + n); its value is the maximum of the class column over the bin's rows (starting from 0: a NaN never
+ * wins), quantised to q = floor(v * 10^digits + 0.5) in float32 (two roundings) and clamped to [0, 10^digits].  Consecutive bins of
+ * equal q are one line; lines of q = 0 are left out.  The value is printed from the integer: q / 10^digits with exactly `digits`
+ * decimals ("0.05", "1.00").  name = name_len raw bytes (host), written as they are.  *h_bytes (host) = the text's length, also
+ * when it exceeds cap: then nothing is written and the caller retries with a larger buffer.  digits 1..4, bin >= 1, n, offset
+ * and bin up to 2^40.  Workspace dgrp_track_workspace_bytes(n, bin) (4 bytes per bin).  Synchronises the stream. */
+int64_t dgrp_track_workspace_bytes(int64_t n, int64_t bin);
+int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls, int digits, int64_t bin, int64_t offset,
+                    const char *name, int64_t name_len, char *d_text, int64_t cap, int64_t *h_bytes,
+                    void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3-A11 in one call: everything deepgrp/__main__.py:46-83 and :288-292 do for ONE record whose class indices
  * (after N stripping, startpos = offset) are in HBM: windows, forward, max-merge with the reference's placement for
  * `batch`, then scores + MSS labels (use_mss != 0; deepgrp/prediction.py:40-59) or softmax + argmax
