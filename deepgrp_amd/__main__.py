@@ -132,6 +132,9 @@ def _add_mask_options(parser, suppress: bool) -> None:
                         help="(addition) soft: predicted repeats lower case, the rest upper case; hard: predicted repeats 'N'")
     parser.add_argument("--mask_classes", type=_class_list, default=d(None),
                         help="(addition) comma-separated labels to mask, e.g. 1,3 (default: every label > 0)")
+    parser.add_argument("--mask_gzip", action="store_true", default=d(False),
+                        help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
+                             "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
 
 
 def _add_track_options(parser) -> None:
@@ -615,10 +618,14 @@ class CommandLineParser:
         """--mask_dir: {input file: masked copy}, or None without the flag.  Everything that can be refused without the model is
         refused here, before any prediction."""
         mdir = getattr(args, "mask_dir", None)
+        packed_out = bool(getattr(args, "mask_gzip", False))
         if mdir is None:
-            if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None:
-                sys.exit("--mask and --mask_classes need --mask_dir")
+            if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None or packed_out:
+                sys.exit("--mask, --mask_classes and --mask_gzip need --mask_dir")
             return None
+        if packed_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
+            sys.exit("--mask_gzip: a compressed masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
+                     "they share a file out by byte ranges, and a compressed file has none; run in one process")
         from .gz import compressed_inputs
         plan, seen = {}, {}
         for f in args.FASTA:
@@ -626,12 +633,14 @@ class CommandLineParser:
                 sys.exit("--mask_dir: standard input cannot be masked (give a FASTA file)")
             if f.endswith(".npz"):
                 sys.exit(f"--mask_dir: {f} is a one-hot .npz, not a FASTA file; it cannot be masked")
-            if compressed_inputs([f]):
+            if not packed_out and compressed_inputs([f]):
                 sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
-                         "uncompressed FASTA")
+                         "uncompressed FASTA or pass --mask_gzip")
             base = os.path.basename(f)
+            if packed_out and not base.endswith(".gz"):
+                base += ".gz"
             if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
-                sys.exit(f"--mask_dir: {seen[base]} and {f} have the same file name; their masked copies would collide")
+                sys.exit(f"--mask_dir: the masked copies of {seen[base]} and {f} have the same file name {base}; they would collide")
             seen[base] = f
             out = os.path.join(mdir, base)
             if os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
@@ -657,7 +666,8 @@ class CommandLineParser:
         fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
         os.close(fd)
         try:
-            mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None))
+            mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
+                       compress=bool(getattr(args, "mask_gzip", False)))
             os.replace(tmp, final)
         except BaseException:
             os.remove(tmp)
@@ -707,7 +717,7 @@ class CommandLineParser:
         """Score `predict`'s rows against an annotation (deepgrp_amd/evaluation.py): TSV report, optionally JSON."""
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
-        if getattr(args, "mask_dir", None) is not None:
+        if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
             sys.exit("--mask_dir belongs to predict, not evaluate")
         if getattr(args, "track_dir", None) is not None:
             sys.exit("--track_dir belongs to predict, not evaluate")

@@ -78,6 +78,10 @@ _SIGNATURES = {
     "dgrp_inflate_raw_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cint)]),
     "dgrp_inflate_workspace_bytes": (i64, [i64]),
     "dgrp_inflate_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(cint), vp, i64, vp]),
+    "dgrp_bgzf_bound": (i64, [i64, cint]),
+    "dgrp_bgzf_workspace_bytes": (i64, [i64]),
+    "dgrp_bgzf_compress": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, vp, i64, vp]),
+    "dgrp_bgzf_compress_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

@@ -5,7 +5,10 @@ compressed size BSIZE, and inflates to at most 64 KiB) is split into its members
 the compressed file is uploaded as it is and the members are inflated side by side on the device (dgrp_inflate_batch), straight
 into the buffer the FASTA ingest consumes.  Any other gzip file (one member as gzip/pigz write it, members without `BC`) is
 inflated on the host with zlib and uploaded.  Corrupt input raises GzipError naming the file and the compressed byte offset of
-the first bad member."""
+the first bad member.
+
+The other direction (`predict --mask_dir --mask_gzip`): bgzf_compress_device deflates device bytes into BGZF members on the device
+(dgrp_bgzf_compress: literals under a per-member Huffman code, no matches); bgzf_compress_host is the same encoder on the host."""
 from __future__ import annotations
 
 import logging
@@ -248,3 +251,41 @@ def bgzf_compress(data: bytes, level: int = 6, strategy: int = zlib.Z_DEFAULT_ST
     """`data` as a BGZF file written the way bgzip writes it: members of `block` input bytes, then the EOF member."""
     out = [bgzf_member(data[o:o + block], level, strategy) for o in range(0, len(data), block)]
     return b"".join(out) + (BGZF_EOF if eof else b"")
+
+
+def bgzf_compress_host(data, eof: bool = True) -> bytes:
+    """`data` as a BGZF file by the library's own encoder on the host (dgrp_bgzf_compress_host: members of BGZF_BLOCK input bytes,
+    literals under a per-member Huffman code or a stored block, no matches): the bytes bgzf_compress_device gives."""
+    import ctypes as C
+
+    from ._lib import check, lib
+    L = lib()
+    data = bytes(data)
+    cap = int(L.dgrp_bgzf_bound(len(data), int(eof)))
+    out = (C.c_uint8 * max(cap, 1))()
+    got = C.c_int64(0)
+    check(L.dgrp_bgzf_compress_host(data, len(data), out, cap, C.byref(got), int(eof)), "dgrp_bgzf_compress_host")
+    return bytes(memoryview(out)[:got.value])
+
+
+def bgzf_compress_device(d_text, eof: bool = True):
+    """The bytes of the uint8 device tensor `d_text` (contiguous, any alignment) as a BGZF file, deflated on the device
+    (dgrp_bgzf_compress); -> uint8 device tensor.  One read-back: the size."""
+    import ctypes as C
+
+    import torch
+
+    from ._lib import check, lib
+    from .pipeline import stream_ptr
+    L = lib()
+    if d_text.dtype != torch.uint8 or not d_text.is_contiguous():
+        raise ValueError("bgzf_compress_device takes a contiguous uint8 tensor")
+    n = int(d_text.numel())
+    cap = int(L.dgrp_bgzf_bound(n, int(eof)))
+    d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_text.device)
+    wb = int(L.dgrp_bgzf_workspace_bytes(n))
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=d_text.device)
+    got = C.c_int64(0)
+    check(L.dgrp_bgzf_compress(d_text.data_ptr() if n else None, n, d_out.data_ptr(), cap, C.byref(got), int(eof), work.data_ptr(), wb,
+                               stream_ptr()), "dgrp_bgzf_compress")
+    return d_out[:got.value]

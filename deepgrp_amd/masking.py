@@ -123,18 +123,25 @@ def _pwrite_all(fd: int, data, offset: int) -> None:
 
 
 def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional[Iterable[int]] = None,
-               ranges: Optional[Sequence[Tuple[int, int]]] = None, group_bytes: int = 256 << 20, group_records: int = 4096) -> int:
+               ranges: Optional[Sequence[Tuple[int, int]]] = None, group_bytes: int = 256 << 20, group_records: int = 4096,
+               compress: bool = False) -> int:
     """Write the masked copy of `fasta_path`.  `rows` (pipeline.SEGMENT_DTYPE): the TSV rows, `contig` = the record's ordinal among
     the records the reference loop yields from the processed bytes, in file order.  `classes`: the labels to mask (None: every label
     > 0).  `ranges=None`: the whole file goes to `out_path` (created or truncated to the input's size); else only those byte ranges
     (whole chunks, as fasta.ingest_ranges takes them) are processed and written into the existing `out_path`, which must already
     have the input's size -- ranks of a sharded run each write their own share.  Works in groups as the ingest does: one upload,
-    dgrp_fasta_encode_batch (which tells the plain records), dgrp_fasta_mask_batch in place, one read-back, one write.  Returns the
-    number of records seen."""
+    dgrp_fasta_encode_batch (which tells the plain records), dgrp_fasta_mask_batch in place, one read-back, one write.
+    A gzip-compressed `fasta_path` (no `ranges`) is masked as its inflated text (gz.open_inflated: BGZF members inflated on the
+    device, other gzip through zlib), resident on the device.  `compress=True` (no `ranges`): `out_path` becomes a BGZF file of the
+    masked text -- every group is deflated on the device where it was masked (gz.bgzf_compress_device) and its members are
+    appended, the EOF member behind the last; a group boundary is just a short member.  Returns the number of records seen."""
     import torch
 
+    import contextlib
+
+    from . import gz
     from ._lib import check, lib
-    from .fasta import _chunk_groups
+    from .fasta import RESIDENT_BYTES, _chunk_groups, _upload_file
     from .pipeline import SEGMENT_DTYPE, require_gpu, stream_ptr
 
     if mode not in MODES:
@@ -143,10 +150,20 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
     rows = rows[np.lexsort((rows["start"], rows["contig"]))] if rows.size else rows
     contig = rows["contig"]
-    size = os.path.getsize(fasta_path)
+    packed = gz.is_gzip(fasta_path)
+    if ranges is not None and (packed or compress):
+        raise ValueError(f"{fasta_path}: a compressed input or output has no byte ranges to share out; it is masked whole")
+    text = d_text = None
+    if packed:
+        text, d_text, size = gz.open_inflated(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
+    else:
+        size = os.path.getsize(fasta_path)
     if ranges is None:
         with open(out_path, "wb") as fh:
-            fh.truncate(size)
+            if compress and size == 0:
+                fh.write(gz.BGZF_EOF)
+            elif not compress:
+                fh.truncate(size)
         ranges = [(0, size)] if size else []
     elif os.path.getsize(out_path) != size:
         raise ValueError(f"{out_path}: {os.path.getsize(out_path)} bytes, the input has {size}")
@@ -154,6 +171,7 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
         return 0
     L = lib()
     dev = require_gpu()
+    written = 0                                                 # compress: bytes of out_path so far
 
     def rows_of(k):
         lo, hi = np.searchsorted(contig, [k, k + 1])
@@ -162,11 +180,16 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     ordinal = 0
     fd = os.open(out_path, os.O_WRONLY)
     try:
-        with open(fasta_path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_COPY) as mm:
+        with contextlib.ExitStack() as stack:
+            if packed:
+                mm = text
+            else:
+                fh = stack.enter_context(open(fasta_path, "rb"))
+                mm = stack.enter_context(mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_COPY))
             for r0, r1 in ranges:
                 if not (0 <= r0 < r1 <= size) or (r0 and not (mm[r0] == 62 and mm[r0 - 1] == 10)):
                     raise ValueError(f"{fasta_path}: [{r0}, {r1}) is not a range of whole chunks")
-                for grp in _chunk_groups(L, dev, fasta_path, mm, r0, r1, group_bytes, group_records, keep_raw=True):
+                for grp in _chunk_groups(L, dev, fasta_path, mm, r0, r1, group_bytes, group_records, keep_raw=True, d_file=d_text):
                     g0, g1 = grp.starts[grp.c0], grp.starts[grp.c1]
                     dev_recs, host_chunks = [], []              # (i, ordinal); (chunk start, chunk end, [(header, offsets, ordinal)])
                     for i, c in enumerate(range(grp.c0, grp.c1)):
@@ -201,11 +224,17 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                                                       d_rows.data_ptr() if d_rows is not None else None, h_row_off.ctypes.data,
                                                       mcode, bits, ptr - shift, work.data_ptr(), wb, stream_ptr()),
                               f"dgrp_fasta_mask_batch ({fasta_path})")
-                        host = d_raw.cpu().numpy()
                         del work, d_rows
+                    host = None
+                    if compress and not host_chunks:
+                        pass                                    # the group stays on the device
+                    elif dev_recs or packed:
+                        host = d_raw.cpu().numpy()
                     else:
                         host = np.frombuffer(mm, dtype=np.uint8, count=g1 - g0, offset=r0 + g0).copy()
-                    del d_raw, grp
+                    if not compress:
+                        d_raw = None
+                    del grp
                     for a, recs in host_chunks:
                         for header, offs, k in recs:
                             lo, hi = rows_of(k)
@@ -214,8 +243,18 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                                 continue
                             inside = _paint(offs.size, rows[lo:hi], bits, f"{fasta_path}: record {header!r}")
                             _apply_host(host, offs + (a - g0), inside, mcode)
-                    _pwrite_all(fd, host, r0 + g0)
-                    del host
+                    if compress:
+                        # (a group with host-masked records went down, was patched and goes up again: rare)
+                        d_comp = gz.bgzf_compress_device(d_raw if host is None else torch.from_numpy(host).to(dev), eof=False)
+                        comp = d_comp.cpu().numpy()
+                        _pwrite_all(fd, comp, written)
+                        written += comp.size
+                        del d_comp, comp
+                    else:
+                        _pwrite_all(fd, host, r0 + g0)
+                    del host, d_raw
+        if compress:
+            _pwrite_all(fd, gz.BGZF_EOF, written)
     finally:
         os.close(fd)
     if contig.size and int(contig[-1]) >= ordinal:

@@ -386,6 +386,22 @@ int dgrp_inflate_batch(const uint8_t *d_in, int64_t in_bytes, int64_t nmem, cons
                        const int64_t *h_out_off, uint8_t *d_out, int64_t out_bytes, int64_t *h_bad, int *h_reason, void *d_work,
                        int64_t work_bytes, void *stream);
 
+/* ---- compressed output (an addition): n bytes as a BGZF file, the way bgzip lays it out -- members of 0xff00 input bytes (the last
+ * one shorter; n = 0: none), each an 18-byte header with BC / BSIZE, ONE DEFLATE block, CRC-32 and ISIZE; with `eof` the empty
+ * EOF member (28 bytes) behind them.  The block holds literals under a per-member dynamic Huffman code (no matches), or is a
+ * stored block when that is not larger, so a member never exceeds its input by more than 31 bytes.  The encode core
+ * (deepgrp_amd/csrc/deflate.h) is the same on the device and on the host: both entries give the same bytes.
+ * dgrp_bgzf_bound(n, eof): an output capacity that always suffices.  *h_out_bytes = bytes of the file (on DGRP_ENOMEM: the
+ * capacity it needs).  DGRP_EINVAL for negative sizes and NULL pointers with something to read or write; DGRP_ENOMEM when the
+ * workspace (dgrp_bgzf_workspace_bytes(n), 16-byte aligned) or the output is too small: the device entry then writes nothing to
+ * d_out, the host entry nothing from the first member that does not fit.  d_in may have any alignment.
+ * dgrp_bgzf_compress is synchronous (one read-back of the total). */
+int64_t dgrp_bgzf_bound(int64_t n, int eof);
+int64_t dgrp_bgzf_workspace_bytes(int64_t n);
+int dgrp_bgzf_compress(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof, void *d_work,
+                       int64_t work_bytes, void *stream);
+int dgrp_bgzf_compress_host(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
