@@ -9,8 +9,9 @@ Differences, all additive:
     the GPUs and rank 0 writes the rows in input order;
   * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
     (deepgrp_amd/masking.py);
-  * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B]` also writes the per-base class
-    probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py);
+  * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B] [--track_gzip]` also writes the per-base class
+    probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py), with --track_gzip as BGZF deflated on the GPU
+    (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
@@ -135,6 +136,9 @@ def _add_mask_options(parser, suppress: bool) -> None:
     parser.add_argument("--mask_gzip", action="store_true", default=d(False),
                         help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
                              "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
+    parser.add_argument("--gzip_level", type=int, default=d(None),
+                        help="(addition) level of the GPU deflate of --mask_gzip and --track_gzip: 0 literals only, 1 with matches "
+                             "(default: 0 for masked copies, 1 for tracks)")
 
 
 def _add_track_options(parser) -> None:
@@ -144,6 +148,9 @@ def _add_track_options(parser) -> None:
                         help="(addition) also write the merged per-base probabilities of every selected class as bedGraph files "
                              "DIR/<basename of the input>.class<c>.bedGraph ('stdin' for '-'); with --fast they are those of the "
                              "fp16-operand kernels")
+    parser.add_argument("--track_gzip", action="store_true", default=s,
+                        help="(addition) with --track_dir: write every track as BGZF (bgzip's format, deflated on the GPU where the "
+                             "text is made) to DIR/<basename>.class<c>.bedGraph.gz")
     parser.add_argument("--track_classes", type=_class_list, default=s,
                         help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
     parser.add_argument("--track_digits", type=int, default=s,
@@ -242,7 +249,7 @@ class CommandLineParser:
         if not any(a in ("predict", "train", "verify", "evaluate") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
-                           "--track_digits", "--track_bin"}
+                           "--track_digits", "--track_bin", "--gzip_level"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -277,8 +284,9 @@ class CommandLineParser:
     @staticmethod
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
-        masks = CommandLineParser._mask_plan(args)              # refusals come before anything runs
         from . import tracks as tk
+        tk.check_gzip_flags(args)                               # refusals come before anything runs
+        masks = CommandLineParser._mask_plan(args)
         track_plan = tk.plan(args)
         track_spec = None
         if track_plan is not None:
@@ -667,7 +675,7 @@ class CommandLineParser:
         os.close(fd)
         try:
             mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
-                       compress=bool(getattr(args, "mask_gzip", False)))
+                       compress=bool(getattr(args, "mask_gzip", False)), level=getattr(args, "gzip_level", None) or 0)
             os.replace(tmp, final)
         except BaseException:
             os.remove(tmp)
@@ -719,8 +727,10 @@ class CommandLineParser:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
         if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
             sys.exit("--mask_dir belongs to predict, not evaluate")
-        if getattr(args, "track_dir", None) is not None:
+        if getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False):
             sys.exit("--track_dir belongs to predict, not evaluate")
+        if getattr(args, "gzip_level", None) is not None:
+            sys.exit("--gzip_level belongs to predict, not evaluate")
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
         import json

@@ -82,6 +82,9 @@ _SIGNATURES = {
     "dgrp_bgzf_workspace_bytes": (i64, [i64]),
     "dgrp_bgzf_compress": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, vp, i64, vp]),
     "dgrp_bgzf_compress_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint]),
+    "dgrp_bgzf_workspace_bytes_level": (i64, [i64, cint]),
+    "dgrp_bgzf_compress_level": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, cint, vp, i64, vp]),
+    "dgrp_bgzf_compress_host_level": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, cint]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

@@ -9,6 +9,17 @@
 //      packs its codes into a 64-bit accumulator and writes whole 32-bit words into an LDS image of the member -- words it shares
 //      with a neighbouring run, the header or the end-of-block code through ds_or_b32 on the zeroed image, its own words as stores;
 //   4. the image (header, block, CRC-32, ISIZE) leaves LDS as 16-byte stores into the member's fixed-stride slot.
+// Level 1 (deflate_lz_member_kernel, deflate.h's second level) puts four stages in front of the body, with the text in LDS:
+//   a. candidates and lengths, in tiles of 256 positions (one per thread): a tile reads the bucket table in LDS (its state is every
+//      earlier tile), looks for the nearest equal key among the tile's own earlier positions, and the last position of each key in
+//      the tile stores itself into the table -- one writer per bucket and tile, so no atomics and no order; then the common prefix
+//      at the nearer candidate, four bytes a step; one word per position goes to the member's part of the workspace;
+//   b. the parse, tile by tile: reachability inside a tile by pointer doubling over the tile's jumps (at most 8 rounds, fewer when
+//      a round adds nothing), the position that jumps out of the tile carries the entry into the next one; the positions reached
+//      count their symbols into the two histograms;
+//   c. both plans side by side (level 0's on one wave, level 1's on another), and the smaller block is the member;
+//   d. the body as in 3., a run's bits now being those of its tokens (up to 20 bits of literal/length, up to 28 of distance).
+// The image shares its LDS with the bucket table, which is dead by then.
 // Then the member sizes are scanned and a second kernel places the members back to back (16-byte stores where the destination
 // allows), with the EOF member behind them on request.  Only the total is read back.
 #include "dgrp_common.h"
@@ -24,14 +35,32 @@ namespace {
 #define DEFLATE_RUN 16
 #define DEFLATE_ROUND (DEFLATE_THREADS * DEFLATE_RUN)      // input bytes between two runs of one thread
 
-struct deflate_lds {
-    uint32_t image[DGRP_BGZF_SLOT / 4];                    // the member as it leaves
+struct deflate_shared {
     dgrp_deflate_plan plan;
     uint32_t hist[DEFLATE_THREADS / 64][DGRP_DEFLATE_NSYM];
     uint32_t crctab[256];
     uint64_t scan[4];
     uint32_t crc[DEFLATE_THREADS / 64];
 };
+struct deflate_lds {
+    uint32_t image[DGRP_BGZF_SLOT / 4];                    // the member as it leaves
+    deflate_shared s;
+};
+#define DEFLATE_LZ_TILE DEFLATE_THREADS
+struct deflate_lz_lds {
+    union {
+        uint32_t image[DGRP_BGZF_SLOT / 4];
+        uint16_t table[1 << DGRP_LZ_HASH_BITS];            // bucket -> its last position so far, 0xffff: none
+    };
+    deflate_shared s;
+    dgrp_lz_plan lz;
+    alignas(16) uint32_t text[(DGRP_BGZF_BLOCK + 16) / 4]; // the member's bytes, zeros behind them
+    alignas(16) uint32_t tkey[DEFLATE_LZ_TILE];            // the tile's keys (read four at a time)
+    uint16_t jump[DEFLATE_LZ_TILE];
+    uint8_t flag[DEFLATE_LZ_TILE];                         // a: a later position of the tile has this key; b: reached
+    uint32_t entry;
+};
+static_assert(sizeof(deflate_lz_lds) <= 160 * 1024, "deflate_lz_lds exceeds the CU's LDS");
 
 // the (at most 16) bytes of a run: one 16-byte load when it is whole (any address: the input may start anywhere)
 struct deflate_run {
@@ -65,25 +94,10 @@ __device__ __forceinline__ uint32_t deflate_x128n(uint32_t j)
     return p;
 }
 
-// one workgroup per member m: in[m * 0xff00 ...) -> slots[m * DGRP_BGZF_SLOT ...), sizes[m]
-__global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const uint8_t *__restrict__ in, int64_t n,
-                                                                         uint8_t *__restrict__ slots, uint64_t *__restrict__ sizes)
+// ---- 1. histogram and CRC-32 of src[0, len) (hist and crctab are set, the workgroup in step): S.plan.freq and S.crc
+__device__ __forceinline__ void deflate_hist_crc(const uint8_t *__restrict__ src, uint32_t len, uint32_t nrun, deflate_shared &S)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char deflate_smem[];
-    deflate_lds &L = *reinterpret_cast<deflate_lds *>(deflate_smem);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t m = blockIdx.x;
-    const uint8_t *src = in + m * DGRP_BGZF_BLOCK;
-    const int64_t left = n - m * DGRP_BGZF_BLOCK;
-    const uint32_t len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
-    const uint32_t nrun = (len + DEFLATE_RUN - 1) / DEFLATE_RUN;
-
-    for (uint32_t i = tid; i < DGRP_BGZF_SLOT / 4; i += DEFLATE_THREADS) L.image[i] = 0;
-    for (uint32_t i = tid; i < (DEFLATE_THREADS / 64) * DGRP_DEFLATE_NSYM; i += DEFLATE_THREADS) (&L.hist[0][0])[i] = 0;
-    L.crctab[tid] = dgrp_crc_table_entry(tid);
-    __syncthreads();
-
-    // ---- 1. histogram and CRC-32
     constexpr uint32_t x_round = dgrp_crc_x8n(DEFLATE_ROUND);
     uint32_t crc = 0, end = 0;                               // raw CRC (register starts at 0) of this thread's runs up to byte `end`
     for (uint32_t r = tid; r < nrun; r += DEFLATE_THREADS) {
@@ -94,8 +108,8 @@ __global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const u
         for (int j = 0; j < DEFLATE_RUN; ++j) {
             if ((uint32_t)j < k) {
                 const uint32_t b = v.byte(j);
-                atomicAdd(&L.hist[wave][b], 1u);
-                c = L.crctab[(c ^ b) & 0xffu] ^ (c >> 8);
+                atomicAdd(&S.hist[wave][b], 1u);
+                c = S.crctab[(c ^ b) & 0xffu] ^ (c >> 8);
             }
         }
         if (r != tid) crc = dgrp_crc_multmodp(k == DEFLATE_RUN ? x_round : dgrp_crc_x8n(at + k - end), crc);
@@ -109,32 +123,27 @@ __global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const u
         crc = dgrp_crc_multmodp(dgrp_crc_x8n(tail), crc);
     }
     for (int o = 32; o > 0; o >>= 1) crc ^= __shfl_xor(crc, o);
-    if (lane == 0) L.crc[wave] = crc;
+    if (lane == 0) S.crc[wave] = crc;
     __syncthreads();
     for (uint32_t s = tid; s < DGRP_DEFLATE_NSYM; s += DEFLATE_THREADS) {
         uint32_t f = 0;
-        for (int w = 0; w < DEFLATE_THREADS / 64; ++w) f += L.hist[w][s];
-        L.plan.freq[s] = s == 256 ? 1u : f;
+        for (int w = 0; w < DEFLATE_THREADS / 64; ++w) f += S.hist[w][s];
+        S.plan.freq[s] = s == 256 ? 1u : f;
     }
     __syncthreads();
+}
 
-    // ---- 2. the plan
-    for (uint32_t s = tid; s < DGRP_DEFLATE_NSYM; s += DEFLATE_THREADS) dgrp_deflate_place(&L.plan, (int)s);
-    __syncthreads();
-    if (tid == 0) dgrp_deflate_plan_member(&L.plan, len);
-    __syncthreads();
-    const uint32_t hdr_end = L.plan.hdr_end, deflate_bytes = L.plan.deflate_bytes;
-    const bool stored = L.plan.stored != 0;
-    if (tid < 4) L.image[tid] = dgrp_bgzf_head_word((int)tid);
-    if (tid < (hdr_end + 31) / 32) L.image[4 + tid] = L.plan.hdr[tid];
-    __syncthreads();
-
-    // ---- 3. the body
-    if (stored) {
-        uint8_t *body = reinterpret_cast<uint8_t *>(L.image) + 16 + hdr_end / 8;
+// ---- 3. level 0's body into the zeroed image that holds the header (S.plan is made)
+__device__ __forceinline__ void deflate_body_literals(const uint8_t *__restrict__ src, uint32_t len, uint32_t nrun, uint32_t *image,
+                                                      deflate_shared &S)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t hdr_end = S.plan.hdr_end;
+    if (S.plan.stored != 0) {
+        uint8_t *body = reinterpret_cast<uint8_t *>(image) + 16 + hdr_end / 8;
         for (uint32_t i = tid; i < len; i += DEFLATE_THREADS) body[i] = src[i];
     } else {
-        uint32_t *img = L.image + 4;
+        uint32_t *img = image + 4;
         uint64_t carry = hdr_end;
         for (uint32_t base = 0; base < nrun; base += DEFLATE_THREADS) {
             const uint32_t r = base + tid, at = r * DEFLATE_RUN;
@@ -145,16 +154,16 @@ __global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const u
             uint32_t bits = 0;
 #pragma unroll
             for (int j = 0; j < DEFLATE_RUN; ++j)
-                if ((uint32_t)j < k) bits += L.plan.table[v.byte(j)] >> 16;
+                if ((uint32_t)j < k) bits += S.plan.table[v.byte(j)] >> 16;
             uint64_t total;
-            const uint64_t pos = block_exclusive_scan(bits, &total, L.scan) + carry;
+            const uint64_t pos = block_exclusive_scan(bits, &total, S.scan) + carry;
             carry += total;
             uint32_t w = (uint32_t)(pos >> 5), nb = (uint32_t)pos & 31u;
             uint64_t acc = 0;
             bool shared = true;                               // the run's first word may hold a neighbour's bits as well
 #pragma unroll
             for (int j = 0; j < DEFLATE_RUN; ++j) {
-                const uint32_t e = (uint32_t)j < k ? L.plan.table[v.byte(j)] : 0u;     // (nothing behind the run: no bits)
+                const uint32_t e = (uint32_t)j < k ? S.plan.table[v.byte(j)] : 0u;     // (nothing behind the run: no bits)
                 acc |= (uint64_t)(e & 0xffffu) << nb;
                 nb += e >> 16;
                 if (nb >= 32) {
@@ -169,28 +178,275 @@ __global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const u
             if (nb && k) atomicOr(&img[w], (uint32_t)acc);
         }
         if (tid == 0) {
-            const uint32_t e = L.plan.table[256], s = (uint32_t)carry & 31u, w = (uint32_t)(carry >> 5);
+            const uint32_t e = S.plan.table[256], s = (uint32_t)carry & 31u, w = (uint32_t)(carry >> 5);
             const uint64_t acc = (uint64_t)(e & 0xffffu) << s;
             atomicOr(&img[w], (uint32_t)acc);
             if (s + (e >> 16) > 32) atomicOr(&img[w + 1], (uint32_t)(acc >> 32));
         }
     }
     __syncthreads();
+}
 
-    // ---- 4. trailer, and out
+// ---- 4. trailer, and out
+__device__ __forceinline__ void deflate_finish(uint32_t len, uint32_t deflate_bytes, uint32_t *image, deflate_shared &S, uint8_t *__restrict__ slot,
+                                               uint64_t *__restrict__ size)
+{
+    const uint32_t tid = threadIdx.x;
     const uint32_t total = 18 + deflate_bytes + 8;
     if (tid < 8) {
-        uint32_t c = L.crc[0];
-        for (int w = 1; w < DEFLATE_THREADS / 64; ++w) c ^= L.crc[w];
+        uint32_t c = S.crc[0];
+        for (int w = 1; w < DEFLATE_THREADS / 64; ++w) c ^= S.crc[w];
         c ^= dgrp_crc_multmodp(dgrp_crc_x8n(len), 0xffffffffu) ^ 0xffffffffu;     // the register's start value carried over len bytes
         const uint32_t word = tid < 4 ? c : len;
-        reinterpret_cast<uint8_t *>(L.image)[18 + deflate_bytes + tid] = (uint8_t)(word >> (8 * (tid & 3)));
+        reinterpret_cast<uint8_t *>(image)[18 + deflate_bytes + tid] = (uint8_t)(word >> (8 * (tid & 3)));
     }
     __syncthreads();
-    uint4 *dst = reinterpret_cast<uint4 *>(slots + m * DGRP_BGZF_SLOT);
-    const uint4 *img16 = reinterpret_cast<const uint4 *>(L.image);
+    uint4 *dst = reinterpret_cast<uint4 *>(slot);
+    const uint4 *img16 = reinterpret_cast<const uint4 *>(image);
     for (uint32_t q = tid; q < (total + 15) / 16; q += DEFLATE_THREADS) dst[q] = img16[q];
-    if (tid == 0) sizes[m] = total;
+    if (tid == 0) *size = total;
+}
+
+// one workgroup per member m: in[m * 0xff00 ...) -> slots[m * DGRP_BGZF_SLOT ...), sizes[m]
+__global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const uint8_t *__restrict__ in, int64_t n,
+                                                                         uint8_t *__restrict__ slots, uint64_t *__restrict__ sizes)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char deflate_smem[];
+    deflate_lds &L = *reinterpret_cast<deflate_lds *>(deflate_smem);
+    const uint32_t tid = threadIdx.x;
+    const int64_t m = blockIdx.x;
+    const uint8_t *src = in + m * DGRP_BGZF_BLOCK;
+    const int64_t left = n - m * DGRP_BGZF_BLOCK;
+    const uint32_t len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
+    const uint32_t nrun = (len + DEFLATE_RUN - 1) / DEFLATE_RUN;
+
+    for (uint32_t i = tid; i < DGRP_BGZF_SLOT / 4; i += DEFLATE_THREADS) L.image[i] = 0;
+    for (uint32_t i = tid; i < (DEFLATE_THREADS / 64) * DGRP_DEFLATE_NSYM; i += DEFLATE_THREADS) (&L.s.hist[0][0])[i] = 0;
+    L.s.crctab[tid] = dgrp_crc_table_entry(tid);
+    __syncthreads();
+    deflate_hist_crc(src, len, nrun, L.s);
+
+    // ---- 2. the plan
+    for (uint32_t s = tid; s < DGRP_DEFLATE_NSYM; s += DEFLATE_THREADS) dgrp_deflate_place(&L.s.plan, (int)s);
+    __syncthreads();
+    if (tid == 0) dgrp_deflate_plan_member(&L.s.plan, len);
+    __syncthreads();
+    const uint32_t hdr_end = L.s.plan.hdr_end, deflate_bytes = L.s.plan.deflate_bytes;
+    if (tid < 4) L.image[tid] = dgrp_bgzf_head_word((int)tid);
+    if (tid < (hdr_end + 31) / 32) L.image[4 + tid] = L.s.plan.hdr[tid];
+    __syncthreads();
+    deflate_body_literals(src, len, nrun, L.image, L.s);
+    deflate_finish(len, deflate_bytes, L.image, L.s, slots + m * DGRP_BGZF_SLOT, sizes + m);
+}
+
+// four bytes of the text at any position (text: little-endian words)
+__device__ __forceinline__ uint32_t deflate_lz_ld4(const uint32_t *text, uint32_t p)
+{
+    const uint32_t i = p >> 2;
+    const uint64_t w = (uint64_t)text[i] | ((uint64_t)text[i + 1] << 32);
+    return (uint32_t)(w >> (8 * (p & 3)));
+}
+
+// level 1: as deflate_member_kernel, with lz[m * 0xff00 ...) for the member's word per position
+__global__ void __launch_bounds__(DEFLATE_THREADS) deflate_lz_member_kernel(const uint8_t *__restrict__ in, int64_t n, uint8_t *__restrict__ slots,
+                                                                            uint64_t *__restrict__ sizes, uint32_t *lz)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char deflate_smem[];
+    deflate_lz_lds &L = *reinterpret_cast<deflate_lz_lds *>(deflate_smem);
+    const uint32_t tid = threadIdx.x;
+    const int64_t m = blockIdx.x;
+    const uint8_t *src = in + m * DGRP_BGZF_BLOCK;
+    const int64_t left = n - m * DGRP_BGZF_BLOCK;
+    const uint32_t len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
+    const uint32_t nrun = (len + DEFLATE_RUN - 1) / DEFLATE_RUN, ntile = (len + DEFLATE_LZ_TILE - 1) / DEFLATE_LZ_TILE;
+    uint32_t *ws = lz + m * DGRP_BGZF_BLOCK;
+
+    for (uint32_t i = tid; i < (1u << DGRP_LZ_HASH_BITS) / 2; i += DEFLATE_THREADS) reinterpret_cast<uint32_t *>(L.table)[i] = 0xffffffffu;
+    for (uint32_t i = tid; i < (DEFLATE_THREADS / 64) * DGRP_DEFLATE_NSYM; i += DEFLATE_THREADS) (&L.s.hist[0][0])[i] = 0;
+    for (uint32_t i = tid; i < DGRP_LZ_NSYM; i += DEFLATE_THREADS) L.lz.freq[i] = i == 256;
+    L.s.crctab[tid] = dgrp_crc_table_entry(tid);
+    for (uint32_t r = tid; r < (DGRP_BGZF_BLOCK + 16) / DEFLATE_RUN; r += DEFLATE_THREADS) {
+        const uint32_t at = r * DEFLATE_RUN, k = at < len ? min(len - at, (uint32_t)DEFLATE_RUN) : 0;
+        deflate_run v;
+        v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
+        if (k) v = deflate_load_run(src + at, k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) L.text[at / 4 + j] = v.w[j];
+    }
+    __syncthreads();
+    deflate_hist_crc(src, len, nrun, L.s);
+
+    // ---- a. candidates and lengths
+    for (uint32_t t = 0; t < ntile; ++t) {
+        const uint32_t p = t * DEFLATE_LZ_TILE + tid;
+        const bool keyed = p + 4 <= len;
+        uint32_t key = 0xffff0000u | tid, cand = 0xffffu;     // (a position without a key equals nobody)
+        if (keyed) {
+            key = dgrp_lz_key(deflate_lz_ld4(L.text, p));
+            cand = L.table[key];
+        }
+        L.tkey[tid] = key;
+        L.flag[tid] = 0;
+        __syncthreads();
+        if (keyed) {
+            // the nearest earlier position of the tile with this key, four keys a step
+            const uint4 *k4 = reinterpret_cast<const uint4 *>(L.tkey);
+            for (int c = (int)(tid >> 2); c >= 0; --c) {
+                const uint4 q = k4[c];
+                const int j0 = 4 * c;
+                int hit = -1;
+                if (q.x == key && j0 < (int)tid) hit = j0;
+                if (q.y == key && j0 + 1 < (int)tid) hit = j0 + 1;
+                if (q.z == key && j0 + 2 < (int)tid) hit = j0 + 2;
+                if (q.w == key && j0 + 3 < (int)tid) hit = j0 + 3;
+                if (hit >= 0) {
+                    cand = t * DEFLATE_LZ_TILE + (uint32_t)hit;
+                    L.flag[hit] = 1;
+                    break;
+                }
+            }
+        }
+        __syncthreads();
+        if (keyed && !L.flag[tid]) L.table[key] = (uint16_t)p;
+        uint32_t e = 0;
+        if (cand != 0xffffu && p - cand <= DGRP_LZ_WINDOW) {
+            const uint32_t cap = min(len - p, (uint32_t)DGRP_LZ_MAX);
+            uint32_t l = 0;
+            while (l < cap) {
+                const uint32_t x = deflate_lz_ld4(L.text, p + l) ^ deflate_lz_ld4(L.text, cand + l);
+                if (x) {
+                    l += (uint32_t)__builtin_ctz(x) >> 3;
+                    break;
+                }
+                l += 4;
+            }
+            e = min(l, cap) | ((p - cand - 1) << 9);
+        }
+        if (p < len) ws[p] = e;
+        __syncthreads();
+    }
+
+    // ---- b. the parse and the histograms of its tokens
+    uint32_t entry = 0;
+    for (uint32_t t = 0; t < ntile; ++t) {
+        if (entry >= DEFLATE_LZ_TILE) {                        // a match jumped over the whole tile
+            entry -= DEFLATE_LZ_TILE;
+            continue;
+        }
+        const uint32_t p = t * DEFLATE_LZ_TILE + tid;
+        const bool valid = p < len;
+        const uint32_t e = valid ? ws[p] : 0u;
+        const uint32_t out = valid ? tid + dgrp_lz_step(e) : 2u * DEFLATE_LZ_TILE;     // next(p) relative to the tile
+        uint32_t jump = out;                                    // next^(2^k)(p), or some position behind the tile
+        L.flag[tid] = tid == entry;
+        for (;;) {
+            L.jump[tid] = (uint16_t)jump;
+            const bool reached = L.flag[tid] != 0;
+            __syncthreads();
+            int added = 0;
+            if (reached && jump < DEFLATE_LZ_TILE) {
+                added = L.flag[jump] == 0;
+                L.flag[jump] = 1;
+            }
+            if (jump < DEFLATE_LZ_TILE) jump = L.jump[jump];
+            if (!__syncthreads_or(added)) break;              // the first 2^k positions of the path are in: none added, all in
+        }
+        if (L.flag[tid] != 0 && valid) {
+            ws[p] = e | DGRP_LZ_TOKEN;
+            if (dgrp_lz_len(e) < DGRP_LZ_MIN) {
+                atomicAdd(&L.lz.freq[(L.text[p >> 2] >> (8 * (p & 3))) & 0xffu], 1u);
+            } else {
+                atomicAdd(&L.lz.freq[dgrp_lz_len_sym(dgrp_lz_len(e)) & 0xffffu], 1u);
+                atomicAdd(&L.lz.freq[DGRP_LZ_NLIT + (dgrp_lz_dist_sym(dgrp_lz_dist(e)) & 0xffu)], 1u);
+            }
+            if (out >= DEFLATE_LZ_TILE) L.entry = out - DEFLATE_LZ_TILE;
+        }
+        __syncthreads();
+        entry = L.entry;
+    }
+
+    // ---- c. both plans, the smaller block
+    for (uint32_t s = tid; s < DGRP_DEFLATE_NSYM; s += DEFLATE_THREADS) dgrp_deflate_place(&L.s.plan, (int)s);
+    for (uint32_t s = tid; s < DGRP_LZ_NSYM; s += DEFLATE_THREADS) dgrp_lz_place(&L.lz, (int)s);
+    for (uint32_t i = tid; i < DGRP_BGZF_SLOT / 4; i += DEFLATE_THREADS) L.image[i] = 0;      // (the bucket table is done)
+    __syncthreads();
+    if (tid == 0) dgrp_deflate_plan_member(&L.s.plan, len);
+    if (tid == 64) dgrp_lz_plan_member(&L.lz);
+    __syncthreads();
+    const bool matches = dgrp_lz_wins(&L.lz, &L.s.plan);
+    const uint32_t hdr_end = matches ? L.lz.hdr_end : L.s.plan.hdr_end;
+    const uint32_t deflate_bytes = matches ? L.lz.deflate_bytes : L.s.plan.deflate_bytes;
+    if (tid < 4) L.image[tid] = dgrp_bgzf_head_word((int)tid);
+    if (tid < (hdr_end + 31) / 32) L.image[4 + tid] = matches ? L.lz.hdr[tid] : L.s.plan.hdr[tid];
+    __syncthreads();
+
+    // ---- d. the body
+    if (!matches) {
+        deflate_body_literals(src, len, nrun, L.image, L.s);
+    } else {
+        uint32_t *img = L.image + 4;
+        uint64_t carry = hdr_end;
+        for (uint32_t base = 0; base < nrun; base += DEFLATE_THREADS) {
+            const uint32_t r = base + tid, at = r * DEFLATE_RUN;
+            const uint32_t k = r < nrun ? min(len - at, (uint32_t)DEFLATE_RUN) : 0;
+            uint32_t ent[DEFLATE_RUN];
+            deflate_run v;
+            v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
+#pragma unroll
+            for (int j = 0; j < DEFLATE_RUN; ++j) ent[j] = 0;
+            if (k) {
+                const uint4 *e4 = reinterpret_cast<const uint4 *>(ws + at);       // (whole: 0xff00 is a multiple of the run)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint4 q = e4[j];
+                    ent[4 * j] = q.x, ent[4 * j + 1] = q.y, ent[4 * j + 2] = q.z, ent[4 * j + 3] = q.w;
+                    v.w[j] = L.text[at / 4 + j];
+                }
+            }
+            uint32_t bits = 0;
+#pragma unroll
+            for (int j = 0; j < DEFLATE_RUN; ++j) {
+                if ((uint32_t)j < k && (ent[j] & DGRP_LZ_TOKEN)) {
+                    uint32_t lo, nlo, hi, nhi;
+                    dgrp_lz_token_bits(L.lz.table, ent[j], v.byte(j), lo, nlo, hi, nhi);
+                    bits += nlo + nhi;
+                }
+            }
+            uint64_t total;
+            const uint64_t pos = block_exclusive_scan(bits, &total, L.s.scan) + carry;
+            carry += total;
+            uint32_t w = (uint32_t)(pos >> 5), nb = (uint32_t)pos & 31u;
+            uint64_t acc = 0;
+            bool shared = true;                               // the run's first word may hold a neighbour's bits as well
+#pragma unroll
+            for (int j = 0; j < DEFLATE_RUN; ++j) {
+                uint32_t lo = 0, nlo = 0, hi = 0, nhi = 0;
+                if ((uint32_t)j < k && (ent[j] & DGRP_LZ_TOKEN)) dgrp_lz_token_bits(L.lz.table, ent[j], v.byte(j), lo, nlo, hi, nhi);
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {        // at most 20 bits, then at most 28: either fits behind nb < 32
+                    acc |= (uint64_t)(half ? hi : lo) << nb;
+                    nb += half ? nhi : nlo;
+                    if (nb >= 32) {
+                        if (shared) atomicOr(&img[w], (uint32_t)acc);
+                        else img[w] = (uint32_t)acc;
+                        shared = false;
+                        ++w;
+                        acc >>= 32;
+                        nb -= 32;
+                    }
+                }
+            }
+            if (nb && k) atomicOr(&img[w], (uint32_t)acc);
+        }
+        if (tid == 0) {
+            const uint32_t e = L.lz.table[256], s = (uint32_t)carry & 31u, w = (uint32_t)(carry >> 5);
+            const uint64_t acc = (uint64_t)(e & 0xffffu) << s;
+            atomicOr(&img[w], (uint32_t)acc);
+            if (s + (e >> 16) > 32) atomicOr(&img[w + 1], (uint32_t)(acc >> 32));
+        }
+        __syncthreads();
+    }
+    deflate_finish(len, deflate_bytes, L.image, L.s, slots + m * DGRP_BGZF_SLOT, sizes + m);
 }
 
 __device__ __forceinline__ uint8_t bgzf_eof_byte(uint32_t i)
@@ -239,48 +495,78 @@ DGRP_EXPORT int64_t dgrp_bgzf_bound(int64_t n, int eof)
     return n + 31 * bgzf_members(n) + (eof ? DGRP_BGZF_EOF_BYTES : 0);
 }
 
-DGRP_EXPORT int64_t dgrp_bgzf_workspace_bytes(int64_t n)
+static int64_t bgzf_workspace(int64_t n, int level)
 {
-    if (n < 0) return 0;
     const int64_t nmem = bgzf_members(n);
-    return dgrp_align_up(nmem * DGRP_BGZF_SLOT, 256) + dgrp_align_up((nmem + 1) * 8, 256);
+    const int64_t base = dgrp_align_up(nmem * DGRP_BGZF_SLOT, 256) + dgrp_align_up((nmem + 1) * 8, 256);
+    return level == 0 ? base : base + nmem * DGRP_BGZF_BLOCK * (int64_t)sizeof(uint32_t);
 }
 
-DGRP_EXPORT int dgrp_bgzf_compress(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
-                                   void *d_work, int64_t work_bytes, void *stream_)
+DGRP_EXPORT int64_t dgrp_bgzf_workspace_bytes(int64_t n) { return n < 0 ? 0 : bgzf_workspace(n, 0); }
+
+DGRP_EXPORT int64_t dgrp_bgzf_workspace_bytes_level(int64_t n, int level)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    DGRP_REQUIRE(n >= 0 && out_cap >= 0 && work_bytes >= 0 && h_out_bytes, "dgrp_bgzf_compress: bad arguments");
+    return n < 0 || level < 0 || level > 1 ? 0 : bgzf_workspace(n, level);
+}
+
+static int bgzf_compress_device(const char *who, const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
+                                int level, void *d_work, int64_t work_bytes, hipStream_t stream)
+{
+    if (!(n >= 0 && out_cap >= 0 && work_bytes >= 0 && h_out_bytes)) {
+        dgrp_set_error("%s: bad arguments", who);
+        return DGRP_EINVAL;
+    }
     *h_out_bytes = 0;
     const int64_t nmem = bgzf_members(n);
-    DGRP_REQUIRE(nmem <= INT32_MAX - 1, "dgrp_bgzf_compress: too many members");
-    DGRP_REQUIRE(n == 0 || (d_in && d_work), "dgrp_bgzf_compress: NULL pointer");
-    DGRP_REQUIRE(d_out || (n == 0 && !eof) || out_cap == 0, "dgrp_bgzf_compress: NULL pointer");
+    if (level < 0 || level > 1) {
+        dgrp_set_error("%s: level %d (0: literals, 1: matches)", who, level);
+        return DGRP_EINVAL;
+    }
+    if (nmem > INT32_MAX - 1) {
+        dgrp_set_error("%s: too many members", who);
+        return DGRP_EINVAL;
+    }
+    if (!(n == 0 || (d_in && d_work)) || !(d_out || (n == 0 && !eof) || out_cap == 0)) {
+        dgrp_set_error("%s: NULL pointer", who);
+        return DGRP_EINVAL;
+    }
     if (n == 0) {
         if (!eof) return DGRP_OK;
         *h_out_bytes = DGRP_BGZF_EOF_BYTES;
         if (out_cap < DGRP_BGZF_EOF_BYTES) {
-            dgrp_set_error("dgrp_bgzf_compress: output of %lld bytes, the EOF member takes %d", (long long)out_cap, DGRP_BGZF_EOF_BYTES);
+            dgrp_set_error("%s: output of %lld bytes, the EOF member takes %d", who, (long long)out_cap, DGRP_BGZF_EOF_BYTES);
             return DGRP_ENOMEM;
         }
         DGRP_HIP(hipMemcpyAsync(d_out, BGZF_EOF_MEMBER, DGRP_BGZF_EOF_BYTES, hipMemcpyHostToDevice, stream));
         DGRP_HIP(hipStreamSynchronize(stream));
         return DGRP_OK;
     }
-    if (work_bytes < dgrp_bgzf_workspace_bytes(n)) {
-        dgrp_set_error("dgrp_bgzf_compress: workspace too small");
+    if (work_bytes < bgzf_workspace(n, level)) {
+        dgrp_set_error("%s: workspace too small", who);
         return DGRP_ENOMEM;
     }
-    DGRP_REQUIRE(((uintptr_t)d_work & 15) == 0, "dgrp_bgzf_compress: d_work must be 16-byte aligned");
+    if (((uintptr_t)d_work & 15) != 0) {
+        dgrp_set_error("%s: d_work must be 16-byte aligned", who);
+        return DGRP_EINVAL;
+    }
     static std::once_flag configured;
     static hipError_t cfg_err = hipSuccess;
     std::call_once(configured, [] {
         cfg_err = hipFuncSetAttribute((const void *)deflate_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(deflate_lds));
+        if (cfg_err == hipSuccess)
+            cfg_err = hipFuncSetAttribute((const void *)deflate_lz_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sizeof(deflate_lz_lds));
     });
     DGRP_HIP(cfg_err);
     uint8_t *slots = (uint8_t *)d_work;
     uint64_t *sizes = (uint64_t *)(slots + dgrp_align_up(nmem * DGRP_BGZF_SLOT, 256));
-    hipLaunchKernelGGL(deflate_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lds), stream, d_in, n, slots, sizes);
+    if (level == 0) {
+        hipLaunchKernelGGL(deflate_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lds), stream, d_in, n, slots, sizes);
+    } else {
+        uint32_t *lz = (uint32_t *)((uint8_t *)sizes + dgrp_align_up((nmem + 1) * 8, 256));
+        hipLaunchKernelGGL(deflate_lz_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lz_lds), stream, d_in, n, slots,
+                           sizes, lz);
+    }
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, sizes, nmem, sizes + nmem);
     DGRP_LAUNCH_CHECK();
@@ -291,25 +577,38 @@ DGRP_EXPORT int dgrp_bgzf_compress(const uint8_t *d_in, int64_t n, uint8_t *d_ou
     DGRP_HIP(hipStreamSynchronize(stream));
     *h_out_bytes = (int64_t)all + (eof ? DGRP_BGZF_EOF_BYTES : 0);
     if (*h_out_bytes > out_cap) {
-        dgrp_set_error("dgrp_bgzf_compress: output of %lld bytes, %lld needed (nothing written)", (long long)out_cap, (long long)*h_out_bytes);
+        dgrp_set_error("%s: output of %lld bytes, %lld needed (nothing written)", who, (long long)out_cap, (long long)*h_out_bytes);
         return DGRP_ENOMEM;
     }
     return DGRP_OK;
 }
 
-DGRP_EXPORT int dgrp_bgzf_compress_host(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof)
+static int bgzf_compress_host(const char *who, const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
+                              int level)
 {
-    DGRP_REQUIRE(n >= 0 && out_cap >= 0 && h_out_bytes, "dgrp_bgzf_compress_host: bad arguments");
+    if (!(n >= 0 && out_cap >= 0 && h_out_bytes)) {
+        dgrp_set_error("%s: bad arguments", who);
+        return DGRP_EINVAL;
+    }
     *h_out_bytes = 0;
-    DGRP_REQUIRE(h_in || n == 0, "dgrp_bgzf_compress_host: NULL pointer");
-    DGRP_REQUIRE(h_out || (n == 0 && !eof) || out_cap == 0, "dgrp_bgzf_compress_host: NULL pointer");
-    std::vector<uint32_t> slot(DGRP_BGZF_SLOT / 4);
+    if (level < 0 || level > 1) {
+        dgrp_set_error("%s: level %d (0: literals, 1: matches)", who, level);
+        return DGRP_EINVAL;
+    }
+    if (!(h_in || n == 0) || !(h_out || (n == 0 && !eof) || out_cap == 0)) {
+        dgrp_set_error("%s: NULL pointer", who);
+        return DGRP_EINVAL;
+    }
+    std::vector<uint32_t> slot(DGRP_BGZF_SLOT / 4), lz(level ? DGRP_BGZF_BLOCK : 0);
+    std::vector<uint16_t> head(level ? 1 << DGRP_LZ_HASH_BITS : 0);
     dgrp_deflate_plan plan;
+    dgrp_lz_plan lzplan;
     int64_t pos = 0;
     bool fits = true;                                        // once a member does not fit nothing more is written, only counted
     for (int64_t o = 0; o < n; o += DGRP_BGZF_BLOCK) {
         const uint32_t k = (uint32_t)(n - o < DGRP_BGZF_BLOCK ? n - o : DGRP_BGZF_BLOCK);
-        const uint32_t size = dgrp_bgzf_member_serial(h_in + o, k, slot.data(), &plan);
+        const uint32_t size = level ? dgrp_bgzf_member_serial_lz(h_in + o, k, slot.data(), &plan, &lzplan, lz.data(), head.data())
+                                    : dgrp_bgzf_member_serial(h_in + o, k, slot.data(), &plan);
         fits = fits && pos + size <= out_cap;
         if (fits) memcpy(h_out + pos, slot.data(), size);
         pos += size;
@@ -321,8 +620,32 @@ DGRP_EXPORT int dgrp_bgzf_compress_host(const uint8_t *h_in, int64_t n, uint8_t 
     }
     *h_out_bytes = pos;
     if (!fits) {
-        dgrp_set_error("dgrp_bgzf_compress_host: output of %lld bytes, %lld needed", (long long)out_cap, (long long)pos);
+        dgrp_set_error("%s: output of %lld bytes, %lld needed", who, (long long)out_cap, (long long)pos);
         return DGRP_ENOMEM;
     }
     return DGRP_OK;
+}
+
+DGRP_EXPORT int dgrp_bgzf_compress(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
+                                   void *d_work, int64_t work_bytes, void *stream)
+{
+    return bgzf_compress_device("dgrp_bgzf_compress", d_in, n, d_out, out_cap, h_out_bytes, eof, 0, d_work, work_bytes, (hipStream_t)stream);
+}
+
+DGRP_EXPORT int dgrp_bgzf_compress_level(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
+                                         int level, void *d_work, int64_t work_bytes, void *stream)
+{
+    return bgzf_compress_device("dgrp_bgzf_compress_level", d_in, n, d_out, out_cap, h_out_bytes, eof, level, d_work, work_bytes,
+                                (hipStream_t)stream);
+}
+
+DGRP_EXPORT int dgrp_bgzf_compress_host(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof)
+{
+    return bgzf_compress_host("dgrp_bgzf_compress_host", h_in, n, h_out, out_cap, h_out_bytes, eof, 0);
+}
+
+DGRP_EXPORT int dgrp_bgzf_compress_host_level(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes,
+                                              int eof, int level)
+{
+    return bgzf_compress_host("dgrp_bgzf_compress_host_level", h_in, n, h_out, out_cap, h_out_bytes, eof, level);
 }

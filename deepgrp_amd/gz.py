@@ -8,7 +8,8 @@ inflated on the host with zlib and uploaded.  Corrupt input raises GzipError nam
 the first bad member.
 
 The other direction (`predict --mask_dir --mask_gzip`): bgzf_compress_device deflates device bytes into BGZF members on the device
-(dgrp_bgzf_compress: literals under a per-member Huffman code, no matches); bgzf_compress_host is the same encoder on the host."""
+(dgrp_bgzf_compress_level: level 0 writes literals under a per-member Huffman code, level 1 adds matches inside the member);
+bgzf_compress_host is the same encoder on the host.  `predict --track_dir --track_gzip` writes its tracks through it as well."""
 from __future__ import annotations
 
 import logging
@@ -253,9 +254,13 @@ def bgzf_compress(data: bytes, level: int = 6, strategy: int = zlib.Z_DEFAULT_ST
     return b"".join(out) + (BGZF_EOF if eof else b"")
 
 
-def bgzf_compress_host(data, eof: bool = True) -> bytes:
-    """`data` as a BGZF file by the library's own encoder on the host (dgrp_bgzf_compress_host: members of BGZF_BLOCK input bytes,
-    literals under a per-member Huffman code or a stored block, no matches): the bytes bgzf_compress_device gives."""
+LEVELS = (0, 1)                                                                         # dgrp_bgzf_compress_level's
+
+
+def bgzf_compress_host(data, eof: bool = True, level: int = 0) -> bytes:
+    """`data` as a BGZF file by the library's own encoder on the host (dgrp_bgzf_compress_host_level: members of BGZF_BLOCK input
+    bytes; level 0: literals under a per-member Huffman code or a stored block; level 1: with matches inside the member, never a
+    larger member than level 0's): the bytes bgzf_compress_device gives."""
     import ctypes as C
 
     from ._lib import check, lib
@@ -264,13 +269,13 @@ def bgzf_compress_host(data, eof: bool = True) -> bytes:
     cap = int(L.dgrp_bgzf_bound(len(data), int(eof)))
     out = (C.c_uint8 * max(cap, 1))()
     got = C.c_int64(0)
-    check(L.dgrp_bgzf_compress_host(data, len(data), out, cap, C.byref(got), int(eof)), "dgrp_bgzf_compress_host")
+    check(L.dgrp_bgzf_compress_host_level(data, len(data), out, cap, C.byref(got), int(eof), int(level)), "dgrp_bgzf_compress_host_level")
     return bytes(memoryview(out)[:got.value])
 
 
-def bgzf_compress_device(d_text, eof: bool = True):
+def bgzf_compress_device(d_text, eof: bool = True, level: int = 0):
     """The bytes of the uint8 device tensor `d_text` (contiguous, any alignment) as a BGZF file, deflated on the device
-    (dgrp_bgzf_compress); -> uint8 device tensor.  One read-back: the size."""
+    (dgrp_bgzf_compress_level); -> uint8 device tensor.  One read-back: the size."""
     import ctypes as C
 
     import torch
@@ -280,12 +285,14 @@ def bgzf_compress_device(d_text, eof: bool = True):
     L = lib()
     if d_text.dtype != torch.uint8 or not d_text.is_contiguous():
         raise ValueError("bgzf_compress_device takes a contiguous uint8 tensor")
+    if level not in LEVELS:
+        raise ValueError(f"bgzf_compress_device: level {level} is not one of {LEVELS}")
     n = int(d_text.numel())
     cap = int(L.dgrp_bgzf_bound(n, int(eof)))
     d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=d_text.device)
-    wb = int(L.dgrp_bgzf_workspace_bytes(n))
+    wb = int(L.dgrp_bgzf_workspace_bytes_level(n, int(level)))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=d_text.device)
     got = C.c_int64(0)
-    check(L.dgrp_bgzf_compress(d_text.data_ptr() if n else None, n, d_out.data_ptr(), cap, C.byref(got), int(eof), work.data_ptr(), wb,
-                               stream_ptr()), "dgrp_bgzf_compress")
+    check(L.dgrp_bgzf_compress_level(d_text.data_ptr() if n else None, n, d_out.data_ptr(), cap, C.byref(got), int(eof), int(level),
+                                     work.data_ptr(), wb, stream_ptr()), "dgrp_bgzf_compress_level")
     return d_out[:got.value]

@@ -124,7 +124,7 @@ def _pwrite_all(fd: int, data, offset: int) -> None:
 
 def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional[Iterable[int]] = None,
                ranges: Optional[Sequence[Tuple[int, int]]] = None, group_bytes: int = 256 << 20, group_records: int = 4096,
-               compress: bool = False) -> int:
+               compress: bool = False, level: int = 0) -> int:
     """Write the masked copy of `fasta_path`.  `rows` (pipeline.SEGMENT_DTYPE): the TSV rows, `contig` = the record's ordinal among
     the records the reference loop yields from the processed bytes, in file order.  `classes`: the labels to mask (None: every label
     > 0).  `ranges=None`: the whole file goes to `out_path` (created or truncated to the input's size); else only those byte ranges
@@ -133,8 +133,9 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     dgrp_fasta_encode_batch (which tells the plain records), dgrp_fasta_mask_batch in place, one read-back, one write.
     A gzip-compressed `fasta_path` (no `ranges`) is masked as its inflated text (gz.open_inflated: BGZF members inflated on the
     device, other gzip through zlib), resident on the device.  `compress=True` (no `ranges`): `out_path` becomes a BGZF file of the
-    masked text -- every group is deflated on the device where it was masked (gz.bgzf_compress_device) and its members are
-    appended, the EOF member behind the last; a group boundary is just a short member.  Returns the number of records seen."""
+    masked text -- every group is deflated on the device where it was masked (gz.bgzf_compress_device at `level`: 0 literals only,
+    1 with matches) and its members are appended, the EOF member behind the last; a group boundary is just a short member.  Returns
+    the number of records seen."""
     import torch
 
     import contextlib
@@ -146,6 +147,8 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
 
     if mode not in MODES:
         raise ValueError(f"mask mode must be one of {sorted(MODES)}, not {mode!r}")
+    if level not in gz.LEVELS:
+        raise ValueError(f"compression level must be one of {gz.LEVELS}, not {level!r}")
     mcode, bits = MODES[mode], class_bits(classes)
     rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
     rows = rows[np.lexsort((rows["start"], rows["contig"]))] if rows.size else rows
@@ -245,7 +248,8 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                             _apply_host(host, offs + (a - g0), inside, mcode)
                     if compress:
                         # (a group with host-masked records went down, was patched and goes up again: rare)
-                        d_comp = gz.bgzf_compress_device(d_raw if host is None else torch.from_numpy(host).to(dev), eof=False)
+                        d_comp = gz.bgzf_compress_device(d_raw if host is None else torch.from_numpy(host).to(dev), eof=False,
+                                                         level=level)
                         comp = d_comp.cpu().numpy()
                         _pwrite_all(fd, comp, written)
                         written += comp.size

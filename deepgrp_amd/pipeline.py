@@ -435,14 +435,18 @@ class ContigPipeline:
     def track_text(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> bytes:
         """bedGraph lines of class `cls` of one record's merged probabilities (dgrp_track_text): `name` (str, surrogateescape, or
         bytes) in the first column, row i at coordinate startpos + i, bins of `bin` bases, values with `digits` decimals."""
+        return self.track_text_device(merged, startpos, name, cls, digits, bin).cpu().numpy().tobytes()
+
+    def track_text_device(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> torch.Tensor:
+        """track_text's bytes as a uint8 device tensor, where dgrp_track_text wrote them: nothing but the size is read back."""
         L = lib()
         if merged.dtype != torch.float32 or merged.ndim != 2 or not merged.is_contiguous():
             raise ValueError("track_text takes the contiguous float32 [n, C] array of merged()")
         n, c = merged.shape
         raw = name if isinstance(name, bytes) else name.encode("utf-8", "surrogateescape")
-        if n == 0:
-            return b""
         dev = merged.device
+        if n == 0:
+            return torch.empty(0, dtype=torch.uint8, device=dev)
         wb = L.dgrp_track_workspace_bytes(n, bin)
         if wb <= 0:
             raise ValueError(f"track_text: bad record length {n} or bin {bin}")
@@ -457,7 +461,7 @@ class ContigPipeline:
             if total.value <= cap:
                 break
             cap = int(total.value)                          # more text than guessed: run again with room for all of it
-        return text[:total.value].cpu().numpy().tobytes()
+        return text[:total.value]
 
     def run_idx(self, d_idx: torch.Tensor, startpos: int, contig: int = 0) -> np.ndarray:
         """Segment records of one record whose class indices are on the device: one dgrp_predict_record call

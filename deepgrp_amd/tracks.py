@@ -4,7 +4,11 @@ probabilities the model computes for each base (ContigPipeline.merged), as text 
 A line is `name<TAB>start<TAB>end<TAB>value<LF>`: the record's name (evaluation.record_name, raw header bytes), a 0-based half-open
 span in the TSV's coordinates, and the maximum probability of the class over the span's bins at `digits` decimals.  Bin k is
 [k * bin, (k + 1) * bin) of the record's coordinates, clipped to the predicted span [startpos, startpos + n); consecutive bins of
-equal value are one line, and spans of value 0 are left out.  `reference_text` restates the format in numpy."""
+equal value are one line, and spans of value 0 are left out.  `reference_text` restates the format in numpy.
+
+With `--track_gzip` the files are `<basename>.class<c>.bedGraph.gz`, BGZF as bgzip writes it: a record's text is deflated on the device
+where it was written (gz.bgzf_compress_device, --gzip_level, 1 unless given) and only the members are read back and appended; a record
+boundary is a short member, and the EOF member is written once, when the file is committed."""
 from __future__ import annotations
 
 import os
@@ -20,6 +24,7 @@ class TrackSpec(NamedTuple):
     classes: Tuple[int, ...]
     digits: int = 2
     bin: int = 1
+    gzip_level: Optional[int] = None                # None: plain text; else BGZF members at this level
 
 
 class TrackPlan(NamedTuple):
@@ -28,19 +33,45 @@ class TrackPlan(NamedTuple):
     digits: int
     bin: int
     bases: dict                                     # input file -> basename of its track files
+    gzip_level: Optional[int] = None                # --track_gzip: the level (None: plain bedGraph)
 
 
 def input_basename(filename: str) -> str:
     return "stdin" if filename == "-" else os.path.basename(filename)
 
 
-def track_path(directory: str, base: str, cls: int) -> str:
-    return os.path.join(directory, f"{base}.class{cls}.bedGraph")
+def track_path(directory: str, base: str, cls: int, gzip: bool = False) -> str:
+    return os.path.join(directory, f"{base}.class{cls}.bedGraph" + (".gz" if gzip else ""))
+
+
+GZIP_PIECE = 4096 * 0xff00                          # bytes deflated per call (the level-1 workspace is five times the piece)
+
+
+def gzip_level(args, default: int) -> Optional[int]:
+    """--gzip_level checked (sys.exit outside {0, 1}), or `default` without the flag."""
+    from .gz import LEVELS
+    level = getattr(args, "gzip_level", None)
+    if level is None:
+        return default
+    if level not in LEVELS:
+        sys.exit(f"--gzip_level must be 0 (literals only) or 1 (with matches), not {level}")
+    return level
+
+
+def check_gzip_flags(args) -> None:
+    """The refusals of --track_gzip and --gzip_level that need nothing but the flags (sys.exit)."""
+    if getattr(args, "track_gzip", False) and getattr(args, "track_dir", None) is None:
+        sys.exit("--track_gzip needs --track_dir")
+    if getattr(args, "gzip_level", None) is not None:
+        if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False)):
+            sys.exit("--gzip_level needs --mask_gzip or --track_gzip")
+        gzip_level(args, 0)
 
 
 def plan(args) -> Optional[TrackPlan]:
     """--track_dir and its options, or None without the flag.  Everything that can be refused without the model is refused here
     (sys.exit), before any device work."""
+    check_gzip_flags(args)
     tdir = getattr(args, "track_dir", None)
     classes, digits, width = (getattr(args, k, None) for k in ("track_classes", "track_digits", "track_bin"))
     if tdir is None:
@@ -62,7 +93,8 @@ def plan(args) -> Optional[TrackPlan]:
             sys.exit(f"--track_dir: {seen[base]} and {f} have the same file name; their tracks would collide")
         seen[base] = f
         bases[f] = base
-    return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases)
+    level = gzip_level(args, 1) if getattr(args, "track_gzip", False) else None
+    return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases, level)
 
 
 def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
@@ -71,20 +103,33 @@ def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
     bad = [c for c in classes if not 0 <= c < nclasses]
     if bad:
         sys.exit(f"--track_classes: label {bad[0]} is not a class of this model (labels 0..{nclasses - 1})")
-    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin)
+    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level)
 
 
 def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec) -> List[bytes]:
-    """The track text of every class of `spec` for one record (merged: ContigPipeline.merged of it)."""
-    return [pipe.track_text(merged, startpos, name, c, spec.digits, spec.bin) for c in spec.classes]
+    """The track text of every class of `spec` for one record (merged: ContigPipeline.merged of it); with spec.gzip_level its BGZF
+    members instead (no EOF member), deflated on the device piece by piece."""
+    if spec.gzip_level is None:
+        return [pipe.track_text(merged, startpos, name, c, spec.digits, spec.bin) for c in spec.classes]
+    from . import gz
+    out = []
+    for c in spec.classes:
+        d_text = pipe.track_text_device(merged, startpos, name, c, spec.digits, spec.bin)
+        pieces = [gz.bgzf_compress_device(d_text[o:o + GZIP_PIECE], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
+                  for o in range(0, int(d_text.numel()), GZIP_PIECE)]
+        out.append(b"".join(pieces))
+        del d_text
+    return out
 
 
 class TrackFiles:
-    """The track files of one input, written to temporary files in the directory and renamed by `commit` (`abort` removes them)."""
+    """The track files of one input, written to temporary files in the directory and renamed by `commit` (`abort` removes them).
+    With spec.gzip_level `write` takes BGZF members and `commit` puts the EOF member behind them."""
 
     def __init__(self, p: TrackPlan, spec: TrackSpec, filename: str):
         os.makedirs(p.directory, exist_ok=True)
-        self.final = [track_path(p.directory, p.bases[filename], c) for c in spec.classes]
+        self.gzip = spec.gzip_level is not None
+        self.final = [track_path(p.directory, p.bases[filename], c, self.gzip) for c in spec.classes]
         self.tmp, self.fh = [], []
         try:
             for path in self.final:
@@ -102,6 +147,9 @@ class TrackFiles:
 
     def commit(self) -> None:
         for fh in self.fh:
+            if self.gzip:
+                from .gz import BGZF_EOF
+                fh.write(BGZF_EOF)
             fh.close()
         for tmp, path in zip(self.tmp, self.final):
             os.replace(tmp, path)

@@ -402,6 +402,21 @@ int dgrp_bgzf_compress(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t o
                        int64_t work_bytes, void *stream);
 int dgrp_bgzf_compress_host(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof);
 
+/* The same file at a chosen level; everything above holds (arguments, capacities, DGRP_ENOMEM, dgrp_bgzf_bound), with the workspace
+ * dgrp_bgzf_workspace_bytes_level(n, level).
+ *   level 0: the encoder above, byte for byte what dgrp_bgzf_compress / dgrp_bgzf_compress_host write.
+ *   level 1: matches.  Per position of a member the candidate is the nearest earlier position IN THE SAME MEMBER whose 4 bytes hash
+ *            to the same 15-bit bucket; it is a match when at least 4 bytes agree (up to 258, distance up to 32768, overlap allowed);
+ *            the parse is greedy from the member's first byte.  One block under a dynamic literal/length code and a dynamic distance
+ *            code.  Per member the smaller of this block and level 0's is written, so no member is larger than at level 0.
+ * Both levels are stated once for host and device (deflate.h): the two entries give the same bytes.  Any other level: DGRP_EINVAL
+ * (dgrp_bgzf_workspace_bytes_level: 0). */
+int64_t dgrp_bgzf_workspace_bytes_level(int64_t n, int level);
+int dgrp_bgzf_compress_level(const uint8_t *d_in, int64_t n, uint8_t *d_out, int64_t out_cap, int64_t *h_out_bytes, int eof, int level,
+                             void *d_work, int64_t work_bytes, void *stream);
+int dgrp_bgzf_compress_host_level(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
+                                  int level);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
