@@ -1600,6 +1600,9 @@ DGRP_EXPORT int dgrp_mss_segments_host(const void *d_work, int64_t work_bytes, i
     }
     mss_layout l = mss_carve((void *)d_work, lo);
     uint64_t cnt = 0;
+    // dgrp_mss_labels writes the list behind its last synchronisation, on the caller's stream; this function has no stream argument and
+    // the blocking copies below run on the null stream, which a non-blocking stream does not wait for: wait for the device
+    DGRP_HIP(hipDeviceSynchronize());
     DGRP_HIP(hipMemcpy(&cnt, l.grand + 3, 8, hipMemcpyDeviceToHost));
     *n_seg = (int64_t)cnt;
     const int64_t take = (int64_t)cnt < cap ? (int64_t)cnt : cap;

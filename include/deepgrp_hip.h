@@ -245,14 +245,17 @@ int dgrp_softmax_labels(const float *d_probs, int64_t n, int C, float *d_softmax
  * msseg_t *mss_find_all(int n, const double *S, double min_sc, double xdrop, int *n_seg)
  * (deepgrp/_mss/mss.h:16-17).  scores float64 [n], labels int8 [n] in; labels int8 [n] out (the
  * argmax of the reference's one-hot rows).  n < 2^31 like the reference.  If d_nseg != NULL it
- * receives the number of maximal segments kept (device int64).  Synchronises the stream (the
- * fixed-point loop over independently scanned stretches reads a flag back). */
+ * receives the number of maximal segments kept (device int64).  Synchronises the stream INSIDE the
+ * call (the fixed-point loop over independently scanned stretches reads a flag back); the vote that
+ * writes d_labels_out and d_nseg is enqueued behind that: stream-ordered, not complete on return. */
 int64_t dgrp_mss_workspace_bytes(int64_t n);
 int dgrp_mss_labels(const double *d_scores, const int8_t *d_cls, int64_t n, int nof_labels,
                     int min_mss_len, int xdrop_len, int8_t *d_labels_out, int64_t *d_nseg,
                     void *d_work, int64_t work_bytes, void *stream);
 /* The segments themselves (st, en as int32 pairs, in order) for the last dgrp_mss_labels call on
- * this workspace: copies up to cap pairs to the host, returns the count via *n_seg (synchronous). */
+ * this workspace: copies up to cap pairs to the host, returns the count via *n_seg (synchronous:
+ * it has no stream argument and waits for all work on the device first, so it may follow a
+ * dgrp_mss_labels call on any stream, non-blocking ones included). */
 int dgrp_mss_segments_host(const void *d_work, int64_t work_bytes, int32_t *h_st_en, int64_t cap,
                            int64_t *n_seg);
 
