@@ -347,8 +347,9 @@ class CommandLineParser:
                     t_file, bases = time.perf_counter(), 0
                     kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
                     if track_spec is not None:
-                        # --track_dir: record by record (merged -> tracks -> labels -> segments); the input's track files are renamed
-                        # into place when all of its records are done, and removed when one raises
+                        # --track_dir: short records as batches (rows and track texts of a batch in two calls), the others one by one
+                        # (merged -> tracks -> labels -> segments); the input's track files are renamed into place when all of its
+                        # records are done, and removed when one raises
                         bases = CommandLineParser._predict_tracked(pipe, runner, filename, records_of(filename), outstream, kept,
                                                                    tk.TrackFiles(track_plan, track_spec, filename), track_spec)
                     elif _LOG.isEnabledFor(logging.DEBUG):
@@ -448,7 +449,7 @@ class CommandLineParser:
         """predict's loop over one input with --track_dir: TSV rows as without it, the track text of every record to `files`
         (tracks.TrackFiles).  -> bases read"""
         from .evaluation import record_name
-        from .runner import rows_text
+        from .runner import rows_text, rows_text_batch
         from .tracks import record_texts
         try:
             if _LOG.isEnabledFor(logging.DEBUG):
@@ -463,11 +464,14 @@ class CommandLineParser:
                         kept.add(rows, 1)
             else:
                 keyed = (((header, record_name(filename, header)), rec) for header, rec in records)
-                for (header, _name), rows, texts in runner.track_results(CommandLineParser._counted(keyed, lambda n: None)):
-                    outstream.write(rows_text(filename, header, rows))
+                for kind, key, rows, texts in runner.tracked_results(CommandLineParser._counted(keyed, lambda n: None)):
+                    if kind == "batch":
+                        outstream.write(rows_text_batch(filename, [header for header, _name in key], rows))
+                    else:
+                        outstream.write(rows_text(filename, key[0], rows))
                     files.write(texts)
                     if kept is not None:
-                        kept.add(rows, 1)
+                        kept.add(rows, len(key) if kind == "batch" else 1)
                 bases = CommandLineParser._last_count
         except BaseException:
             files.abort()

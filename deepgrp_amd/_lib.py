@@ -38,6 +38,8 @@ _SIGNATURES = {
     "dgrp_format_rows": (cint, [vp, vp, i64, cint, vp, i64, vp, i64, C.POINTER(i64)]),
     "dgrp_track_workspace_bytes": (i64, [i64, i64]),
     "dgrp_track_text": (cint, [vp, i64, cint, cint, cint, i64, i64, C.c_char_p, i64, vp, i64, C.POINTER(i64), vp, i64, vp]),
+    "dgrp_track_batch_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64]),
+    "dgrp_track_text_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp]),
     "dgrp_window_count": (i64, [i64, i64, i64]),
     "dgrp_windows_onehot": (cint, [vp, i64, i64, i64, i64, i64, cint, vp, vp]),
     "dgrp_model_create": (cint, [C.POINTER(vp), cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]),
@@ -70,6 +72,8 @@ _SIGNATURES = {
     "dgrp_predict_record": (cint, [vp, vp, i64, i64, i64, cint, cint, cint, i64, i32, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_batch_workspace_bytes": (i64, [vp, i64, vp, i64]),
     "dgrp_predict_batch": (cint, [vp, vp, i64, vp, vp, vp, vp, i64, i64, cint, cint, vp, i64, C.POINTER(i64), vp, i64, vp]),
+    "dgrp_batch_rows": (i64, [i64, vp]),
+    "dgrp_predict_batch_probs": (cint, [vp, vp, i64, vp, vp, vp, vp, i64, i64, cint, cint, vp, i64, C.POINTER(i64), vp, i64, vp, vp]),
     "dgrp_confusion_matrix": (cint, [vp, vp, i64, cint, vp, vp, vp]),
     "dgrp_filter_segments": (cint, [vp, vp, i64, i64, vp]),
     "dgrp_eval_workspace_bytes": (i64, [i64, i64]),

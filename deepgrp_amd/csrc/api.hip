@@ -1011,26 +1011,31 @@ DGRP_EXPORT int64_t dgrp_batch_workspace_bytes(const dgrp_model *m, int64_t nrec
     return batch_carve(m, nrec, batch_rows(nrec, h_n), batch_windows(m, nrec, h_n, s)).bytes;
 }
 
-DGRP_EXPORT int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, const int64_t *h_idx_off,
-                                   const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s,
-                                   int64_t batch, int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap,
-                                   int64_t *h_count, void *d_work, int64_t work_bytes, void *stream_)
+DGRP_EXPORT int64_t dgrp_batch_rows(int64_t nrec, const int64_t *h_n)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    DGRP_REQUIRE(m && nrec >= 0 && s >= 1 && batch >= 1 && cap >= 0 && h_count, "dgrp_predict_batch: bad arguments");
+    return nrec > 0 && h_n ? batch_rows(nrec, h_n) : 0;
+}
+
+// dgrp_predict_batch and dgrp_predict_batch_probs (`who`): the merged probabilities go to d_probs, or to the workspace slot without one
+static int predict_batch_common(const char *who, const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, const int64_t *h_idx_off,
+                                const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s,
+                                int64_t batch, int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap,
+                                int64_t *h_count, void *d_work, int64_t work_bytes, hipStream_t stream, float *d_probs)
+{
+    DGRP_REQUIRE(m && nrec >= 0 && s >= 1 && batch >= 1 && cap >= 0 && h_count, "%s: bad arguments", who);
     *h_count = 0;
     if (nrec == 0) return DGRP_OK;
-    DGRP_REQUIRE(!m->ref_only && (m->cell == 0 || (m->cell == 1 && m->NW <= 8)), "dgrp_predict_batch: unsupported model (fp32 path: record by record)");
-    DGRP_REQUIRE(d_idx && h_idx_off && h_n && h_startpos && h_contig && d_work && (cap == 0 || d_records), "dgrp_predict_batch: NULL pointer");
+    DGRP_REQUIRE(!m->ref_only && (m->cell == 0 || (m->cell == 1 && m->NW <= 8)), "%s: unsupported model (fp32 path: record by record)", who);
+    DGRP_REQUIRE(d_idx && h_idx_off && h_n && h_startpos && h_contig && d_work && (cap == 0 || d_records), "%s: NULL pointer", who);
     for (int64_t r = 0; r < nrec; ++r)
-        DGRP_REQUIRE(h_n[r] >= 1 && h_idx_off[r] >= 0, "dgrp_predict_batch: record %lld: empty records do not belong in a batch", (long long)r);
+        DGRP_REQUIRE(h_n[r] >= 1 && h_idx_off[r] >= 0, "%s: record %lld: empty records do not belong in a batch", who, (long long)r);
     const int64_t rows = batch_rows(nrec, h_n);
-    DGRP_REQUIRE(rows < (1ll << 31), "dgrp_predict_batch: %lld rows in one batch (limit 2^31)", (long long)rows);
+    DGRP_REQUIRE(rows < (1ll << 31), "%s: %lld rows in one batch (limit 2^31)", who, (long long)rows);
     const int64_t windows = batch_windows(m, nrec, h_n, s);
-    DGRP_REQUIRE(windows < (1ll << 31), "dgrp_predict_batch: too many windows in one batch");
+    DGRP_REQUIRE(windows < (1ll << 31), "%s: too many windows in one batch", who);
     const batch_layout l = batch_carve(m, nrec, rows, windows);
     if (work_bytes < l.bytes) {
-        dgrp_set_error("dgrp_predict_batch: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
+        dgrp_set_error("%s: workspace %lld < %lld bytes", who, (long long)work_bytes, (long long)l.bytes);
         return DGRP_ENOMEM;
     }
     char *w = (char *)d_work;
@@ -1053,7 +1058,7 @@ DGRP_EXPORT int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, in
     DGRP_HIP(hipMemcpyAsync(w + l.spos, h_startpos, (size_t)nrec * 8, hipMemcpyHostToDevice, stream));
     DGRP_HIP(hipMemcpyAsync(w + l.contig, h_contig, (size_t)nrec * 4, hipMemcpyHostToDevice, stream));
     // ---- A3-A6 for all records: one launch
-    float *out = (float *)(w + l.out);
+    float *out = d_probs ? d_probs : (float *)(w + l.out);
     DGRP_HIP(hipMemsetAsync(out, 0, (size_t)rows * m->C * 4, stream));
     int rc;
     if (!m->attention) {
@@ -1090,5 +1095,24 @@ DGRP_EXPORT int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, in
     DGRP_HIP(hipMemcpyAsync(h_count, d_count, 8, hipMemcpyDeviceToHost, stream));
     DGRP_HIP(hipStreamSynchronize(stream));
     return DGRP_OK;
+}
+
+DGRP_EXPORT int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, const int64_t *h_idx_off,
+                                   const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s,
+                                   int64_t batch, int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap,
+                                   int64_t *h_count, void *d_work, int64_t work_bytes, void *stream)
+{
+    return predict_batch_common("dgrp_predict_batch", m, d_idx, nrec, h_idx_off, h_n, h_startpos, h_contig, s, batch, min_mss_len, xdrop_len,
+                                d_records, cap, h_count, d_work, work_bytes, (hipStream_t)stream, nullptr);
+}
+
+DGRP_EXPORT int dgrp_predict_batch_probs(const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, const int64_t *h_idx_off,
+                                         const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s,
+                                         int64_t batch, int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap,
+                                         int64_t *h_count, void *d_work, int64_t work_bytes, void *stream, float *d_probs)
+{
+    DGRP_REQUIRE(d_probs || nrec <= 0, "dgrp_predict_batch_probs: NULL d_probs");
+    return predict_batch_common("dgrp_predict_batch_probs", m, d_idx, nrec, h_idx_off, h_n, h_startpos, h_contig, s, batch, min_mss_len,
+                                xdrop_len, d_records, cap, h_count, d_work, work_bytes, (hipStream_t)stream, d_probs);
 }
 

@@ -4,6 +4,8 @@
 // See include/deepgrp_hip.h.
 #include "dgrp_common.h"
 #include "scan.h"
+#include <string.h>
+#include <vector>
 
 namespace {
 
@@ -222,6 +224,394 @@ DGRP_EXPORT int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls,
     if (total == 0 || (int64_t)total > cap) return DGRP_OK;                 // (too small: the caller retries with room for all of it)
     if (name_len > 0) DGRP_HIP(hipMemcpyAsync(d_text, name, (size_t)name_len, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(track_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, g, name_len, digits, qmax, tiles, d_text);
+    DGRP_LAUNCH_CHECK();
+    DGRP_HIP(hipStreamSynchronize(stream));
+    return DGRP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The same text for a BATCH of records and every selected class in one chain (dgrp_track_text_batch): a file of thousands of short
+// records costs a handful of launches and two synchronisations instead of that per record and class.  The flat bin space is
+// [class k][record r][bin j]; every class starts at a tile boundary (NBpad = bins of all records rounded up to TRACK_TILE), so no
+// tile straddles a class and the scanned tile offsets at each class's first tile are the class boundaries of the text.
+namespace {
+
+#define TRACK_STAGE 32768                // bytes of one round's text that are assembled in LDS (longer rounds write directly)
+
+struct tb_rec { int64_t row0, n, offset, kb0, nb, name_off, name_len, pad; };     // one record: 64 bytes of the uploaded table
+struct tb_geom {
+    int64_t nrec, NB, NBpad, bin;        // records, bins of all records, the same rounded up to TRACK_TILE, bin width
+    int C, ncls, digits;
+};
+
+// record of flat bin f < pref[nrec]: the largest r with pref[r] <= f (every record has at least one bin)
+__device__ __forceinline__ int64_t tb_record_of(const int64_t *__restrict__ pref, int64_t nrec, int64_t f)
+{
+    int64_t lo = 0, hi = nrec;                    // pref[lo] <= f < pref[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (pref[mid] <= f) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the same for f >= f0 when r0 is the record of f0 (found once per tile): mostly r0 itself, else one of the next f - f0 records
+__device__ __forceinline__ int64_t tb_record_from(const int64_t *__restrict__ pref, int64_t nrec, int64_t r0, int64_t f0, int64_t f)
+{
+    if (pref[r0 + 1] > f) return r0;
+    int64_t lo = r0 + 1, hi = r0 + (f - f0) + 1;
+    if (hi > nrec) hi = nrec;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (pref[mid] <= f) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ track_geom tb_geom_of(const tb_rec &R, int64_t bin)
+{
+    track_geom g;
+    g.offset = R.offset; g.n = R.n; g.bin = bin; g.kb0 = R.kb0; g.nb = R.nb;
+    return g;
+}
+
+#define TB_CLS 8                         // classes reduced side by side from one read of a row (more classes: one more pass per 8)
+
+// one lane per (record, bin), bins up to TRACK_WAVE_BIN wide: every row is read once for up to TB_CLS selected classes
+__global__ void __launch_bounds__(256) tb_bin_lane_kernel(const float *__restrict__ probs, const tb_rec *__restrict__ recs,
+                                                          const int64_t *__restrict__ pref, const int *__restrict__ cls, tb_geom G,
+                                                          float scale, uint32_t qmax, uint32_t *__restrict__ q)
+{
+    __shared__ int64_t s_r0;
+    const int64_t f0 = (int64_t)blockIdx.x * 256, f = f0 + threadIdx.x;
+    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    __syncthreads();
+    if (f >= G.NB) return;
+    const int64_t r = tb_record_from(pref, G.nrec, s_r0, f0, f);
+    const tb_rec R = recs[r];
+    int64_t lo, hi;
+    track_bin_span(tb_geom_of(R, G.bin), f - pref[r], lo, hi);
+    const float *p = probs + (R.row0 + (lo - R.offset)) * G.C;
+    const int rows = (int)(hi - lo);
+    for (int k0 = 0; k0 < G.ncls; k0 += TB_CLS) {
+        float m[TB_CLS];
+        int c[TB_CLS];
+#pragma unroll
+        for (int k = 0; k < TB_CLS; ++k) {
+            m[k] = 0.0f;
+            c[k] = k0 + k < G.ncls ? cls[k0 + k] : 0;
+        }
+        for (int i = 0; i < rows; ++i) {
+            const float *row = p + (int64_t)i * G.C;
+#pragma unroll
+            for (int k = 0; k < TB_CLS; ++k)
+                if (k0 + k < G.ncls) m[k] = fmaxf(m[k], row[c[k]]);
+        }
+#pragma unroll
+        for (int k = 0; k < TB_CLS; ++k)
+            if (k0 + k < G.ncls) q[(int64_t)(k0 + k) * G.NBpad + f] = track_quantise(m[k], scale, qmax);
+    }
+}
+
+// one wave per (record, bin): wider bins
+__global__ void __launch_bounds__(256) tb_bin_wave_kernel(const float *__restrict__ probs, const tb_rec *__restrict__ recs,
+                                                          const int64_t *__restrict__ pref, const int *__restrict__ cls, tb_geom G,
+                                                          float scale, uint32_t qmax, uint32_t *__restrict__ q)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t f = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); f < G.NB; f += waves) {
+        const int64_t r = tb_record_of(pref, G.nrec, f);
+        const tb_rec R = recs[r];
+        int64_t lo, hi;
+        track_bin_span(tb_geom_of(R, G.bin), f - pref[r], lo, hi);
+        const float *p = probs + (R.row0 + (lo - R.offset)) * G.C;
+        const int64_t rows = hi - lo;
+        for (int k0 = 0; k0 < G.ncls; k0 += TB_CLS) {
+            float m[TB_CLS];
+            int c[TB_CLS];
+#pragma unroll
+            for (int k = 0; k < TB_CLS; ++k) {
+                m[k] = 0.0f;
+                c[k] = k0 + k < G.ncls ? cls[k0 + k] : 0;
+            }
+            for (int64_t i = lane; i < rows; i += 64) {
+                const float *row = p + i * G.C;
+#pragma unroll
+                for (int k = 0; k < TB_CLS; ++k)
+                    if (k0 + k < G.ncls) m[k] = fmaxf(m[k], row[c[k]]);
+            }
+#pragma unroll
+            for (int k = 0; k < TB_CLS; ++k) {
+                if (k0 + k >= G.ncls) continue;                      // (uniform)
+                float v = m[k];
+                for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+                if (lane == 0) q[(int64_t)(k0 + k) * G.NBpad + f] = track_quantise(v, scale, qmax);
+            }
+        }
+    }
+}
+
+// track_part_of for flat bin f of one class (qk = that class's NBpad values): a run never leaves its record, bin 0 of a record is
+// always `first` and its last bin always `last`.  Bins in [NB, NBpad) read as q = 0.
+struct tb_part { track_part p; int64_t name_off, name_len; };
+
+__device__ __forceinline__ tb_part tb_part_of(const uint32_t *__restrict__ qk, const tb_rec *__restrict__ recs,
+                                              const int64_t *__restrict__ pref, const tb_geom &G, int64_t r0, int64_t f0, int64_t f)
+{
+    tb_part t;
+    t.p.v = f < G.NB ? qk[f] : 0u;
+    t.p.first = t.p.last = false;
+    t.p.head = t.p.tail = 0;
+    t.p.lo = t.p.hi = 0;
+    t.name_off = t.name_len = 0;
+    if (t.p.v == 0) return t;
+    const int64_t r = tb_record_from(pref, G.nrec, r0, f0, f);
+    const int64_t j = f - pref[r], nb = recs[r].nb;
+    t.p.first = j == 0 || qk[f - 1] != t.p.v;
+    t.p.last = j == nb - 1 || qk[f + 1] != t.p.v;
+    if (!t.p.first && !t.p.last) return t;
+    const tb_rec R = recs[r];
+    track_bin_span(tb_geom_of(R, G.bin), j, t.p.lo, t.p.hi);
+    t.name_off = R.name_off;
+    t.name_len = R.name_len;
+    if (t.p.first) t.p.head = R.name_len + track_decimal_width((uint64_t)t.p.lo) + 2;
+    if (t.p.last) t.p.tail = track_decimal_width((uint64_t)t.p.hi) + G.digits + 4;
+    return t;
+}
+
+// bytes of text per tile; tile t belongs to class t / (NBpad / TRACK_TILE)
+__global__ void __launch_bounds__(256) tb_count_kernel(const uint32_t *__restrict__ q, const tb_rec *__restrict__ recs,
+                                                       const int64_t *__restrict__ pref, tb_geom G, uint64_t *__restrict__ tilebytes)
+{
+    __shared__ uint64_t lds[4];
+    __shared__ int64_t s_r0;
+    const int64_t tpc = G.NBpad / TRACK_TILE;
+    const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
+    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    __syncthreads();
+    const int64_t r0 = s_r0;
+    const uint32_t *qk = q + k * G.NBpad;
+    uint64_t s = 0;
+    for (int r = 0; r < TRACK_TILE / 256; ++r) {
+        const tb_part t = tb_part_of(qk, recs, pref, G, r0, f0, f0 + r * 256 + threadIdx.x);
+        s += (uint64_t)(t.p.head + t.p.tail);
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) tilebytes[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+// the class boundaries of the text, side by side for one copy to the host: the scanned offset of each class's first tile, the total
+__global__ void __launch_bounds__(128) tb_bounds_kernel(const uint64_t *__restrict__ tileoff, int64_t tpc, int ncls,
+                                                       const uint64_t *__restrict__ grand, uint64_t *__restrict__ bounds)
+{
+    const int k = threadIdx.x;
+    if (k < ncls) bounds[k] = tileoff[(int64_t)k * tpc];
+    if (k == ncls) bounds[k] = *grand;
+}
+
+// the parts of one bin at o (LDS image or d_text); the name comes from the uploaded blob
+__device__ __forceinline__ void tb_emit(char *o, const tb_part &t, const char *__restrict__ names, int digits, uint32_t qmax)
+{
+    if (t.p.first) {
+        const char *nm = names + t.name_off;
+        for (int64_t c = 0; c < t.name_len; ++c) o[c] = nm[c];
+        o += t.name_len;
+        *o++ = '\t';
+        const int w = track_decimal_width((uint64_t)t.p.lo);
+        track_put_decimal(o, (uint64_t)t.p.lo, w);
+        o += w;
+        *o++ = '\t';
+    }
+    if (t.p.last) {
+        const int w = track_decimal_width((uint64_t)t.p.hi);
+        track_put_decimal(o, (uint64_t)t.p.hi, w);
+        o += w;
+        *o++ = '\t';
+        *o++ = (char)('0' + t.p.v / qmax);
+        *o++ = '.';
+        track_put_decimal(o, t.p.v % qmax, digits);
+        o += digits;
+        *o = '\n';
+    }
+}
+
+// The text, in 8 rounds of 256 consecutive bins per tile.  A round of up to TRACK_STAGE bytes is assembled in LDS, laid out congruent
+// to its global address modulo 16, and flushed with aligned 16-byte stores: only words that lie wholly inside the round's byte range
+// go out wide, the bytes at its two edges as byte stores, so no word is shared between rounds or tiles and no byte is written
+// twice.  A longer round (long names) writes directly; the choice is uniform, the round's total comes from the block scan.
+__global__ void __launch_bounds__(256) tb_write_kernel(const uint32_t *__restrict__ q, const tb_rec *__restrict__ recs,
+                                                       const int64_t *__restrict__ pref, const char *__restrict__ names, tb_geom G,
+                                                       uint32_t qmax, const uint64_t *__restrict__ tileoff, char *text)
+{
+    __shared__ uint64_t lds[4];
+    __shared__ int64_t s_r0;
+    __shared__ __attribute__((aligned(16))) char stage[TRACK_STAGE + 16];
+    const int64_t tpc = G.NBpad / TRACK_TILE;
+    const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
+    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    __syncthreads();
+    const int64_t r0 = s_r0;
+    const uint32_t *qk = q + k * G.NBpad;
+    int64_t at = (int64_t)tileoff[blockIdx.x];
+    for (int r = 0; r < TRACK_TILE / 256; ++r) {
+        const tb_part t = tb_part_of(qk, recs, pref, G, r0, f0, f0 + r * 256 + threadIdx.x);
+        uint64_t round_bytes;
+        const int64_t ex = (int64_t)block_exclusive_scan((uint64_t)(t.p.head + t.p.tail), &round_bytes, lds);
+        if (round_bytes == 0) continue;                                    // (uniform)
+        if (round_bytes > TRACK_STAGE) {
+            tb_emit(text + at + ex, t, names, G.digits, qmax);
+        } else {
+            const int64_t mis = (int64_t)((uintptr_t)(text + at) & 15);
+            tb_emit(stage + mis + ex, t, names, G.digits, qmax);
+            __syncthreads();
+            char *dst = text + at - mis;                                   // the 16-byte aligned address of stage[0]
+            const int64_t b0 = mis, b1 = mis + (int64_t)round_bytes;       // the round's bytes in the image
+            const int64_t w0 = (b0 + 15) & ~(int64_t)15, w1 = b1 & ~(int64_t)15;
+            const int64_t h1 = w0 < b1 ? w0 : b1;
+            for (int64_t i = b0 + threadIdx.x; i < h1; i += 256) dst[i] = stage[i];
+            for (int64_t i = w0 + 16 * (int64_t)threadIdx.x; i < w1; i += 16 * 256)
+                *reinterpret_cast<uint4 *>(dst + i) = *reinterpret_cast<const uint4 *>(stage + i);
+            for (int64_t i = (w1 > h1 ? w1 : h1) + threadIdx.x; i < b1; i += 256) dst[i] = stage[i];
+            __syncthreads();
+        }
+        at += (int64_t)round_bytes;
+    }
+}
+
+struct tb_layout { int64_t NB, NBpad, tables, tables_bytes, recs, pref, cls, names, q, tiles, bytes; };
+
+// 0: arguments the entry refuses
+static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes,
+                     tb_layout *l)
+{
+    if (nrec < 0 || bin < 1 || bin > TRACK_MAX_EXTENT || ncls < 1 || ncls > DGRP_MAXC || names_bytes < 0) return false;
+    if (nrec > 0 && (!h_n || !h_startpos)) return false;
+    int64_t NB = 0;
+    for (int64_t r = 0; r < nrec; ++r) {
+        if (h_n[r] < 1 || h_n[r] > TRACK_MAX_EXTENT || h_startpos[r] < 0 || h_startpos[r] > TRACK_MAX_EXTENT) return false;
+        NB += (h_startpos[r] + h_n[r] - 1) / bin - h_startpos[r] / bin + 1;
+        if (NB > 4 * TRACK_MAX_EXTENT) return false;
+    }
+    l->NB = NB;
+    l->NBpad = dgrp_align_up(NB, TRACK_TILE);
+    if (l->NBpad / TRACK_TILE * ncls >= (1ll << 31) || (NB + 255) / 256 >= (1ll << 31)) return false;
+    // the uploaded tables: records | bin prefix | classes | names
+    l->recs = 0;
+    l->pref = l->recs + nrec * (int64_t)sizeof(tb_rec);
+    l->cls = l->pref + (nrec + 1) * 8;
+    l->names = l->cls + dgrp_align_up((int64_t)ncls * 4, 8);
+    l->tables_bytes = l->names + names_bytes;
+    int64_t p = 256 + dgrp_align_up((int64_t)(ncls + 1) * 8, 256);        // total, class boundaries
+    l->tables = p;
+    p += dgrp_align_up(l->tables_bytes, 256);
+    l->q = p;
+    p += dgrp_align_up(l->NBpad * ncls * 4, 256);
+    l->tiles = p;
+    p += dgrp_align_up(l->NBpad / TRACK_TILE * ncls * 8, 256);
+    l->bytes = p;
+    return true;
+}
+
+}   // namespace
+
+DGRP_EXPORT int64_t dgrp_track_batch_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                                     int64_t names_bytes)
+{
+    tb_layout l;
+    return tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                      const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls,
+                                      int ncls, int digits, int64_t bin, char *d_text, int64_t cap, int64_t *h_class_off,
+                                      void *d_work, int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC, "dgrp_track_text_batch: bad C %d", C);
+    DGRP_REQUIRE(ncls >= 1 && ncls <= C, "dgrp_track_text_batch: ncls must lie in 1..C (%d, C = %d)", ncls, C);
+    DGRP_REQUIRE(h_class_off && h_cls, "dgrp_track_text_batch: NULL h_class_off or h_cls");
+    for (int k = 0; k <= ncls; ++k) h_class_off[k] = 0;
+    DGRP_REQUIRE(nrec >= 0, "dgrp_track_text_batch: bad nrec %lld", (long long)nrec);
+    for (int k = 0; k < ncls; ++k)
+        DGRP_REQUIRE(h_cls[k] >= 0 && h_cls[k] < C, "dgrp_track_text_batch: class %d is not in 0..%d", h_cls[k], C - 1);
+    DGRP_REQUIRE(digits >= 1 && digits <= 4, "dgrp_track_text_batch: digits must lie in 1..4, got %d", digits);
+    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "dgrp_track_text_batch: bad bin %lld", (long long)bin);
+    DGRP_REQUIRE(cap >= 0, "dgrp_track_text_batch: bad cap %lld", (long long)cap);
+    if (nrec == 0) return DGRP_OK;
+    DGRP_REQUIRE(h_row0 && h_n && h_startpos && h_name_off, "dgrp_track_text_batch: NULL host table");
+    DGRP_REQUIRE(h_name_off[0] >= 0, "dgrp_track_text_batch: record 0: bad name offset %lld", (long long)h_name_off[0]);
+    for (int64_t r = 0; r < nrec; ++r) {
+        DGRP_REQUIRE(h_n[r] >= 1 && h_n[r] <= TRACK_MAX_EXTENT, "dgrp_track_text_batch: record %lld: bad n %lld", (long long)r,
+                     (long long)h_n[r]);
+        DGRP_REQUIRE(h_startpos[r] >= 0 && h_startpos[r] <= TRACK_MAX_EXTENT, "dgrp_track_text_batch: record %lld: bad offset %lld",
+                     (long long)r, (long long)h_startpos[r]);
+        DGRP_REQUIRE(h_row0[r] >= 0, "dgrp_track_text_batch: record %lld: bad first row %lld", (long long)r, (long long)h_row0[r]);
+        DGRP_REQUIRE(h_name_off[r + 1] >= h_name_off[r], "dgrp_track_text_batch: record %lld: descending name offsets (%lld, %lld)",
+                     (long long)r, (long long)h_name_off[r], (long long)h_name_off[r + 1]);
+    }
+    const int64_t names_bytes = h_name_off[nrec];
+    DGRP_REQUIRE((names || names_bytes == 0) && (d_text || cap == 0) && d_probs && d_work, "dgrp_track_text_batch: NULL pointer");
+    tb_layout l;
+    DGRP_REQUIRE(tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l), "dgrp_track_text_batch: too many bins in one call");
+    if (work_bytes < l.bytes) {
+        dgrp_set_error("dgrp_track_text_batch: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
+        return DGRP_ENOMEM;
+    }
+    // ---- tables: one upload
+    std::vector<char> tab((size_t)l.tables_bytes);
+    tb_rec *recs = (tb_rec *)(tab.data() + l.recs);
+    int64_t *pref = (int64_t *)(tab.data() + l.pref);
+    pref[0] = 0;
+    for (int64_t r = 0; r < nrec; ++r) {
+        tb_rec &R = recs[r];
+        R.row0 = h_row0[r]; R.n = h_n[r]; R.offset = h_startpos[r];
+        R.kb0 = R.offset / bin;
+        R.nb = (R.offset + R.n - 1) / bin - R.kb0 + 1;
+        R.name_off = h_name_off[r]; R.name_len = h_name_off[r + 1] - h_name_off[r]; R.pad = 0;
+        pref[r + 1] = pref[r] + R.nb;
+    }
+    memcpy(tab.data() + l.cls, h_cls, (size_t)ncls * 4);
+    if (names_bytes > 0) memcpy(tab.data() + l.names, names, (size_t)names_bytes);
+    char *w = (char *)d_work;
+    DGRP_HIP(hipMemcpyAsync(w + l.tables, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
+    uint64_t *grand = (uint64_t *)w, *bounds = (uint64_t *)(w + 256);
+    const tb_rec *d_recs = (const tb_rec *)(w + l.tables + l.recs);
+    const int64_t *d_pref = (const int64_t *)(w + l.tables + l.pref);
+    const int *d_cls = (const int *)(w + l.tables + l.cls);
+    const char *d_names = w + l.tables + l.names;
+    uint32_t *q = (uint32_t *)(w + l.q);
+    uint64_t *tiles = (uint64_t *)(w + l.tiles);
+    tb_geom G;
+    G.nrec = nrec; G.NB = l.NB; G.NBpad = l.NBpad; G.bin = bin; G.C = C; G.ncls = ncls; G.digits = digits;
+    uint32_t qmax = 1;
+    for (int k = 0; k < digits; ++k) qmax *= 10;
+    const float scale = (float)qmax;
+    const int64_t tpc = l.NBpad / TRACK_TILE, ntiles = tpc * ncls;
+
+    if (bin <= TRACK_WAVE_BIN) {
+        hipLaunchKernelGGL(tb_bin_lane_kernel, dim3((unsigned)((l.NB + 255) / 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
+                           scale, qmax, q);
+    } else {
+        hipLaunchKernelGGL(tb_bin_wave_kernel, dim3(grid_for(l.NB * 64, 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
+                           scale, qmax, q);
+    }
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, G, tiles);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, tiles, ntiles, grand);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tb_bounds_kernel, dim3(1), dim3(128), 0, stream, tiles, tpc, ncls, grand, bounds);
+    DGRP_LAUNCH_CHECK();
+    std::vector<uint64_t> off((size_t)ncls + 1, 0);
+    DGRP_HIP(hipMemcpyAsync(off.data(), bounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    for (int k = 0; k <= ncls; ++k) h_class_off[k] = (int64_t)off[(size_t)k];
+    const int64_t total = (int64_t)off[(size_t)ncls];
+    if (total == 0 || total > cap) return DGRP_OK;                          // (too small: the caller retries with room for all of it)
+    hipLaunchKernelGGL(tb_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, d_names, G, qmax, tiles, d_text);
     DGRP_LAUNCH_CHECK();
     DGRP_HIP(hipStreamSynchronize(stream));
     return DGRP_OK;

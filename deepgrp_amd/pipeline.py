@@ -492,9 +492,10 @@ class ContigPipeline:
         """dgrp_predict_batch covers every model on the MSS path (the -m softmax is normalised per record)."""
         return self.use_mss and self.event_log is None and not self.fp32 and not getattr(self.model, "fp32_only", False)
 
-    def run_batch(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs) -> np.ndarray:
+    def run_batch(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, d_probs: Optional[torch.Tensor] = None) -> np.ndarray:
         """Segment records of MANY short records whose class indices lie in one device buffer (record r: `lengths[r]`
-        >= 1 indices at `d_base[offsets[r]:]`): one dgrp_predict_batch call.  Rows come back in record order."""
+        >= 1 indices at `d_base[offsets[r]:]`): one dgrp_predict_batch call.  Rows come back in record order.  With `d_probs`
+        (float32 [dgrp_batch_rows, C]) the call is dgrp_predict_batch_probs and the merged probabilities are left there."""
         L = lib()
         nrec = len(lengths)
         if nrec == 0:
@@ -512,14 +513,83 @@ class ContigPipeline:
         count = C.c_int64(0)
         while True:
             rec = torch.empty(cap * SEGMENT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            check(L.dgrp_predict_batch(self.handle, _ptr(d_base), nrec, off.ctypes.data, ln.ctypes.data, sp.ctypes.data,
-                                       cg.ctypes.data, self.step, self.batch, self.min_mss_len, self.xdrop_len, _ptr(rec), cap,
-                                       C.byref(count), _ptr(work), wb, stream_ptr()), "dgrp_predict_batch")
+            args = (self.handle, _ptr(d_base), nrec, off.ctypes.data, ln.ctypes.data, sp.ctypes.data, cg.ctypes.data, self.step,
+                    self.batch, self.min_mss_len, self.xdrop_len, _ptr(rec), cap, C.byref(count), _ptr(work), wb, stream_ptr())
+            if d_probs is None:
+                check(L.dgrp_predict_batch(*args), "dgrp_predict_batch")
+            else:
+                check(L.dgrp_predict_batch_probs(*args, _ptr(d_probs)), "dgrp_predict_batch_probs")
             if count.value <= cap:
                 break
             cap = int(count.value)
         host = rec[: count.value * SEGMENT_DTYPE.itemsize].cpu().numpy()
         return host.view(SEGMENT_DTYPE).copy()
+
+    def track_text_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, names, classes, digits: int = 2,
+                                bin: int = 1) -> Tuple[torch.Tensor, np.ndarray]:
+        """The track text of many records and classes in one dgrp_track_text_batch call: record r is rows [row0[r], row0[r] +
+        lengths[r]) of `d_probs` (float32 [*, C]), `names[r]` (str, surrogateescape, or bytes) its first column.  -> (uint8 device
+        tensor, offsets [len(classes) + 1]): the text is class-major, class classes[k] of all records in order at [off[k], off[k + 1])."""
+        L = lib()
+        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
+            raise ValueError("track_text_batch_device takes a contiguous float32 [rows, C] array")
+        c = int(d_probs.shape[1])
+        nrec, ncls = len(lengths), len(classes)
+        dev = d_probs.device
+        r0 = np.ascontiguousarray(row0, np.int64)
+        ln = np.ascontiguousarray(lengths, np.int64)
+        sp = np.ascontiguousarray(startposes, np.int64)
+        cl = np.ascontiguousarray(classes, np.int32)
+        raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+        noff = np.zeros(nrec + 1, np.int64)
+        np.cumsum([len(x) for x in raw], out=noff[1:])
+        blob = b"".join(raw)
+        wb = L.dgrp_track_batch_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
+        if wb <= 0:
+            raise ValueError(f"track_text_batch_device: bad record lengths, start positions, bin {bin} or class count {ncls}")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        nb = ln // int(bin) + 2                                               # (a line per bin at most; the guess fits most runs)
+        nlen = np.diff(noff)
+        cap = ncls * int(min(int((nb * (nlen + 50)).sum()), (1 << 20) + int((nb * (nlen + 12)).sum())))
+        off = np.zeros(ncls + 1, np.int64)
+        while True:
+            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            check(L.dgrp_track_text_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob, noff.ctypes.data,
+                                          cl.ctypes.data, ncls, int(digits), int(bin), _ptr(text), cap, off.ctypes.data, _ptr(work), wb,
+                                          stream_ptr()), "dgrp_track_text_batch")
+            if int(off[ncls]) <= cap:
+                break
+            cap = int(off[ncls])                            # more text than guessed: run again with room for all of it
+        return text[:int(off[ncls])], off
+
+    def run_batch_tracked(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, names, spec):
+        """run_batch with probability tracks: one dgrp_predict_batch_probs call, then one dgrp_track_text_batch call on its merged
+        probabilities.  -> (rows, texts), texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
+        give one after the other); with spec.gzip_level the BGZF members of that slice instead (no EOF member), deflated on the
+        device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member."""
+        L = lib()
+        nrec = len(lengths)
+        if nrec == 0:
+            return np.zeros(0, SEGMENT_DTYPE), [b""] * len(spec.classes)
+        ln = np.ascontiguousarray(lengths, np.int64)
+        total = int(L.dgrp_batch_rows(nrec, ln.ctypes.data))
+        d_probs = torch.empty((total, self.model.classes), dtype=torch.float32, device=d_base.device)
+        rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
+        row0 = np.zeros(nrec, np.int64)
+        np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
+        d_text, off = self.track_text_batch_device(d_probs, row0, ln, startposes, names, spec.classes, spec.digits, spec.bin)
+        del d_probs
+        if spec.gzip_level is None:
+            host = d_text.cpu().numpy()
+            return rows, [host[off[k]:off[k + 1]].tobytes() for k in range(len(spec.classes))]
+        from . import gz
+        from .tracks import GZIP_PIECE
+        texts = []
+        for k in range(len(spec.classes)):
+            pieces = [gz.bgzf_compress_device(d_text[o:min(o + GZIP_PIECE, int(off[k + 1]))], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
+                      for o in range(int(off[k]), int(off[k + 1]), GZIP_PIECE)]
+            texts.append(b"".join(pieces))
+        return rows, texts
 
     def run(self, sequence, contig: int = 0) -> np.ndarray:
         raw = sequence.encode("utf-8") if isinstance(sequence, str) else bytes(sequence)

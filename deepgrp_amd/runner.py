@@ -1,7 +1,8 @@
 """How the command line pushes records through the device pipeline: independent records (deepgrp/__main__.py:280-292)
 run on a small pool of host threads, one HIP stream each, with ordered results; consecutive short records of one
-ingest buffer go to the GPU as one batch (dgrp_predict_batch).  `RecordRunner.results` yields what the
-reference's loop would have produced record after record, and raises where that loop would raise."""
+ingest buffer go to the GPU as one batch (dgrp_predict_batch; with probability tracks dgrp_predict_batch_probs and
+dgrp_track_text_batch).  `RecordRunner.results` yields what the reference's loop would have produced record after
+record, and raises where that loop would raise."""
 from __future__ import annotations
 
 import collections
@@ -20,6 +21,10 @@ class _Tracked(NamedTuple):
     """A work item of track_results: one record and the name of its track lines."""
     name: str
     rec: object
+
+
+class _TrackedBatch(list):
+    """A batch work item of tracked_results: [((header, name), record), ...]."""
 
 
 _BATCH = object()             # key slot of a work item that is a batch of records (never equal to a user's key, e.g. a header "batch")
@@ -81,7 +86,7 @@ class RecordRunner:
 
     def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None):
         self.pipe = pipe
-        self.tracks = tracks          # tracks.TrackSpec: records run one by one through the staged path (track_results)
+        self.tracks = tracks          # tracks.TrackSpec: every record's track text comes with its rows (tracked_results)
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
@@ -113,9 +118,12 @@ class RecordRunner:
 
     # ---- batching
     def _batch_cost(self, n: int) -> int:
-        """Workspace bytes a record of n bases adds to a batch (attention: the avg[t] spill of its windows dominates)."""
+        """Workspace bytes a record of n bases adds to a batch (attention: the avg[t] spill of its windows dominates).  With
+        tracks: the merged copy, 4 bytes per bin and class, and the text guess (a line of 12 bytes and a short name per bin)."""
         cost = 80 * n
         m = self.pipe.model
+        if self.tracks is not None:
+            cost += 4 * m.classes * (n + 64) + len(self.tracks.classes) * (n // self.tracks.bin + 2) * (4 + 12 + 32)
         if m.attention:
             cost += len(range(0, n - self._T, self.pipe.step)) * self._T * (self._UP * 4 + m.classes * 4)
         return cost
@@ -125,7 +133,7 @@ class RecordRunner:
         else stays (key, record)."""
         group: List[Tuple[object, DeviceRecord]] = []
         cost = 0
-        batchable = self.pipe.batchable() and self.tracks is None
+        batchable = self.pipe.batchable()
         for key, rec in records:
             small = batchable and isinstance(rec, DeviceRecord) and rec.base is not None and 1 <= rec.length <= SMALL_RECORD
             if small:
@@ -146,6 +154,11 @@ class RecordRunner:
     def run_item(self, item):
         if isinstance(item, _Tracked):
             return self.run_tracked(item.rec, item.name)
+        if isinstance(item, _TrackedBatch):               # the same with the track texts of the whole batch, class by class
+            rows, texts = self.pipe.run_batch_tracked(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
+                                                      [r.startpos for _k, r in item], list(range(len(item))),
+                                                      [k[1] for k, _r in item], self.tracks)
+            return [k for k, _r in item], rows, texts
         if isinstance(item, list):                        # a batch: rows of all its records, contig = position in the batch
             rows = self.pipe.run_batch(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
                                        [r.startpos for _k, r in item], list(range(len(item))))
@@ -210,3 +223,21 @@ class RecordRunner:
         items = ((key, _Tracked(key[1], rec)) for key, rec in records)
         for key, (rows, texts) in self.in_order(items):
             yield key, rows, texts
+
+    def tracked_results(self, records: Iterable[Tuple[object, object]]):
+        """With self.tracks, keys as in track_results: ("one", key, rows, texts) for a record on its own, ("batch", [keys], rows,
+        texts) for a batch of short records -- rows["contig"] indexes the keys, texts[k] is the text of class
+        self.tracks.classes[k] of all its records in order.  Records batch exactly when they do without tracks."""
+        def items():
+            for key, item in self.work_items(records):
+                if key is _BATCH:
+                    yield _BATCH, _TrackedBatch(item)
+                else:
+                    yield key, _Tracked(key[1], item)
+        for key, result in self.in_order(items()):
+            if key is _BATCH:
+                keys, rows, texts = result
+                yield "batch", keys, rows, texts
+            else:
+                rows, texts = result
+                yield "one", key, rows, texts

@@ -6,9 +6,13 @@ span in the TSV's coordinates, and the maximum probability of the class over the
 [k * bin, (k + 1) * bin) of the record's coordinates, clipped to the predicted span [startpos, startpos + n); consecutive bins of
 equal value are one line, and spans of value 0 are left out.  `reference_text` restates the format in numpy.
 
-With `--track_gzip` the files are `<basename>.class<c>.bedGraph.gz`, BGZF as bgzip writes it: a record's text is deflated on the device
-where it was written (gz.bgzf_compress_device, --gzip_level, 1 unless given) and only the members are read back and appended; a record
-boundary is a short member, and the EOF member is written once, when the file is committed."""
+Short records run as batches (ContigPipeline.run_batch_tracked: dgrp_predict_batch_probs, then dgrp_track_text_batch for all records
+and classes of the batch); the text of a batch is the records' texts one after the other.
+
+With `--track_gzip` the files are `<basename>.class<c>.bedGraph.gz`, BGZF as bgzip writes it: the text of a record (of a batch: of one
+class of all its records) is deflated on the device where it was written (gz.bgzf_compress_device, --gzip_level, 1 unless given) and
+only the members are read back and appended; a record or batch boundary is a short member, and the EOF member is written once, when
+the file is committed."""
 from __future__ import annotations
 
 import os

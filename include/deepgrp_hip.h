@@ -300,6 +300,23 @@ int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls, int digits,
                     const char *name, int64_t name_len, char *d_text, int64_t cap, int64_t *h_bytes,
                     void *d_work, int64_t work_bytes, void *stream);
 
+/* The same text for a BATCH of records and several classes in one chain (files of thousands of short records).  Record r is rows
+ * [h_row0[r], h_row0[r] + h_n[r]) of d_probs [*, C] (any layout: the rows of dgrp_predict_batch_probs, or one record at row 0), its
+ * coordinates start at h_startpos[r], and its first column is names[h_name_off[r] : h_name_off[r + 1]] (raw host bytes).  The
+ * output is class-major: d_text[h_class_off[k] : h_class_off[k + 1]] is the text of class h_cls[k] of record 0, then record 1, ...
+ * -- exactly the bytes the one-record entry gives record by record, concatenated (a run never crosses a record boundary).
+ * h_class_off (host, ncls + 1 entries) is always filled in full, also when h_class_off[ncls] > cap: then nothing is written and the
+ * caller retries with a larger buffer.  Format, quantisation, bin alignment and limits as above; ncls in 1..C, classes in 0..C-1,
+ * h_n[r] >= 1, ascending h_name_off.  nrec = 0: zero offsets, no device work.  Workspace
+ * dgrp_track_batch_workspace_bytes (0 on arguments the entry refuses; names_bytes = h_name_off[nrec]).  Synchronises the stream (at
+ * most twice per call, however many records and classes); the host tables may be dropped on return. */
+int64_t dgrp_track_batch_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                         int64_t names_bytes);
+int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                          const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls, int ncls,
+                          int digits, int64_t bin, char *d_text, int64_t cap, int64_t *h_class_off, void *d_work,
+                          int64_t work_bytes, void *stream);
+
 /* ---- A3-A11 in one call: everything deepgrp/__main__.py:46-83 and :288-292 do for ONE record whose class indices
  * (after N stripping, startpos = offset) are in HBM: windows, forward, max-merge with the reference's placement for
  * `batch`, then scores + MSS labels (use_mss != 0; deepgrp/prediction.py:40-59) or softmax + argmax
@@ -325,6 +342,15 @@ int dgrp_predict_batch(const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, 
                        const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s, int64_t batch,
                        int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap, int64_t *h_count,
                        void *d_work, int64_t work_bytes, void *stream);
+
+/* dgrp_batch_rows: the rows of a batch's merged array, the sum of h_n[r] rounded up to 64 each; record r starts at the prefix sum of
+ * the same terms.  dgrp_predict_batch_probs: dgrp_predict_batch, with the merged probabilities [dgrp_batch_rows, C] float32 written
+ * to the caller's d_probs (device) instead of the workspace; padding rows are zero, the segment rows are the same bit for bit. */
+int64_t dgrp_batch_rows(int64_t nrec, const int64_t *h_n);
+int dgrp_predict_batch_probs(const dgrp_model *m, const uint8_t *d_idx, int64_t nrec, const int64_t *h_idx_off,
+                             const int64_t *h_n, const int64_t *h_startpos, const int32_t *h_contig, int64_t s, int64_t batch,
+                             int min_mss_len, int xdrop_len, dgrp_segment *d_records, int64_t cap, int64_t *h_count,
+                             void *d_work, int64_t work_bytes, void *stream, float *d_probs);
 
 /* ---- N2: evaluation helpers of deepgrp.prediction on label arrays that are already in HBM.
  * deepgrp.prediction.confusion_matrix (deepgrp/prediction.py:204-222): d_cnf int64 [ncls, ncls] (zeroed here),

@@ -1,4 +1,5 @@
-"""Command line on a draft-assembly-like FASTA: many short records (file -> TSV file, warm)."""
+"""Command line on a draft-assembly-like FASTA: many short records (file -> TSV file, warm), without tracks, with --track_dir and
+with --track_dir --track_gzip (file -> TSV file and four track files); two runs per leg, the second one warm."""
 import os, sys, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepgrp_amd import synthetic, model as dgmodel
@@ -19,8 +20,14 @@ with open(fa, "wb") as fh:
         fh.write(b">ctg%d\n" % (k + 1))
         fh.write(b"\n".join(seq[i:i + 60] for i in range(0, len(seq), 60)) + b"\n")
 mbp = ncontig * kbp / 1e3
-for it in range(2):
-    t0 = time.perf_counter()
-    main(["predict", mpath, fa, "--output", os.path.join(d, "out.tsv")])
-    dt = time.perf_counter() - t0
-    print(f"run {it}: {ncontig} records x {kbp:g} kbp = {mbp:g} Mbp -> TSV in {dt:.3f} s = {mbp/dt:.1f} Mbp/s, {sum(1 for _ in open(os.path.join(d,'out.tsv')))} rows", flush=True)
+legs = [("no tracks", []), ("tracks", ["--track_dir", os.path.join(d, "T")]), ("tracks gzip", ["--track_dir", os.path.join(d, "Tz"), "--track_gzip"])]
+if len(sys.argv) > 3:
+    legs = [leg for leg in legs if leg[0] in sys.argv[3].split(",")]
+for label, extra in legs:
+    for it in range(2):
+        t0 = time.perf_counter()
+        main(["predict", mpath, fa, "--output", os.path.join(d, "out.tsv")] + extra)
+        dt = time.perf_counter() - t0
+        size = sum(os.path.getsize(os.path.join(extra[1], f)) for f in os.listdir(extra[1])) if extra else 0
+        print(f"{label}, run {it}: {ncontig} records x {kbp:g} kbp = {mbp:g} Mbp -> TSV in {dt:.3f} s = {mbp/dt:.1f} Mbp/s, "
+              f"{sum(1 for _ in open(os.path.join(d,'out.tsv')))} rows, {size} track bytes", flush=True)
