@@ -187,7 +187,10 @@ def test_gru_blend_variants_agree(dev, orc, u, T, attention, monkeypatch):
 
 def test_gru_large_weights_take_the_safe_blend(dev, orc):
     """Weights whose pre-activations could reach 2^60 and beyond: the overflow bound fails, the two-reciprocal
-    kernel runs, and the probabilities stay finite and on the float64 statement (saturated gates)."""
+    kernel runs, and the probabilities stay finite and normalised.  Nothing more is checked here: at gain 12 the
+    cell is chaotic (float32 and float64 evaluations of the plain statement disagree by O(1) at these sizes), so
+    no kernel can be compared with float64 on these weights.  test_gpu_blend.py compares the two-reciprocal
+    kernels with float64 on weights that cross the bound and stay well conditioned."""
     rng = np.random.default_rng(5)
     u, T, s, nw = 128, 60, 13, 29
     w, dm = _model(orc, u, T, False, 12.0)
