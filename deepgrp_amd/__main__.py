@@ -302,8 +302,8 @@ class CommandLineParser:
         import torch.distributed as dist
         from . import model as dgmodel
         from .distributed import gather_records, shard_contigs
-        from .fasta import DeviceRecord, read_multi_fasta_device
-        from .pipeline import SEGMENT_DTYPE, ContigPipeline, upload_sequence
+        from .fasta import read_multi_fasta_device
+        from .pipeline import SEGMENT_DTYPE, ContigPipeline, record_indices
         from .runner import RecordRunner, rows_text, rows_text_batch
 
         world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -386,12 +386,7 @@ class CommandLineParser:
                             records.append((filename, header, rec))
                     parts = []
                     for i, (_f, _h, rec) in enumerate(records):
-                        if isinstance(rec, DeviceRecord):
-                            if rec.length < 0:
-                                raise ValueError("negative dimensions are not allowed")
-                            startpos, d_idx = rec.startpos, rec.d_idx
-                        else:
-                            startpos, d_idx = upload_sequence(rec.encode("utf-8"))
+                        startpos, d_idx = record_indices(rec)
                         parts.append(run_split(pipe, d_idx, startpos, i))
                     allrows = np.concatenate(parts) if parts else np.zeros(0, SEGMENT_DTYPE)
                     if rank == 0:
@@ -488,20 +483,14 @@ class CommandLineParser:
 
         import torch
 
-        from .fasta import DeviceRecord
-        from .pipeline import SEGMENT_DTYPE, upload_sequence
+        from .pipeline import SEGMENT_DTYPE, record_indices
 
         def lap(t):
             torch.cuda.synchronize()
             return (time.perf_counter() - t) * 1e3
         t = time.perf_counter()
         _LOG.debug("One hot encoding sequence.")
-        if isinstance(rec, DeviceRecord):
-            if rec.length < 0:
-                raise ValueError("negative dimensions are not allowed")
-            startpos, d_idx = rec.startpos, rec.d_idx
-        else:
-            startpos, d_idx = upload_sequence(rec.encode("utf-8"))
+        startpos, d_idx = record_indices(rec)
         n = int(d_idx.numel())
         ms_enc = lap(t)
         if n == 0:

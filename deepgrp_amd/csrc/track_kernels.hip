@@ -1,6 +1,11 @@
-// Probability tracks (predict --track_dir): one class column of a record's merged probabilities [n, C] as 4-column bedGraph text,
-// built in HBM.  Three passes: bin max + quantisation (reads the strided column), bytes of text per tile of bins, and the text itself;
-// between them one scan of the tile sums.  Every index and byte offset is 64-bit.
+// Probability tracks (predict --track_dir): class columns of merged probabilities [rows, C] as 4-column bedGraph text, built in HBM.
+// Three passes: bin max + quantisation (reads the strided columns), bytes of text per tile of bins, and the text itself; between
+// them one scan of the tile sums.  Every index and byte offset is 64-bit.
+// One chain writes any number of records and classes (dgrp_track_text_batch): a file of thousands of short records costs a handful
+// of launches and two synchronisations instead of that per record and class.  One class of one record (dgrp_track_text) is the same
+// chain with one record and one class.  The flat bin space is [class k][record r][bin j]; every class starts at a tile boundary
+// (NBpad = bins of all records rounded up to TRACK_TILE), so no tile straddles a class and the scanned tile offsets at each
+// class's first tile are the class boundaries of the text.
 // See include/deepgrp_hip.h.
 #include "dgrp_common.h"
 #include "scan.h"
@@ -32,80 +37,11 @@ __device__ __forceinline__ uint32_t track_quantise(float v, float scale, uint32_
     return q <= 0.0f ? 0u : q >= (float)qmax ? qmax : (uint32_t)q;
 }
 
-// one lane per bin (bins up to TRACK_WAVE_BIN wide).  The max starts from 0: a NaN never wins (fmaxf), values below 0 read as 0.
-__global__ void __launch_bounds__(256) track_bin_lane_kernel(const float *__restrict__ probs, int C, int cls, track_geom g,
-                                                             float scale, uint32_t qmax, uint32_t *__restrict__ q)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < g.nb; j += stride) {
-        int64_t lo, hi;
-        track_bin_span(g, j, lo, hi);
-        float m = 0.0f;
-        for (int64_t i = lo - g.offset; i < hi - g.offset; ++i) m = fmaxf(m, probs[i * C + cls]);
-        q[j] = track_quantise(m, scale, qmax);
-    }
-}
-
-// one wave per bin (wider bins)
-__global__ void __launch_bounds__(256) track_bin_wave_kernel(const float *__restrict__ probs, int C, int cls, track_geom g,
-                                                             float scale, uint32_t qmax, uint32_t *__restrict__ q)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t j = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); j < g.nb; j += waves) {
-        int64_t lo, hi;
-        track_bin_span(g, j, lo, hi);
-        float m = 0.0f;
-        for (int64_t i = lo - g.offset + lane; i < hi - g.offset; i += 64) m = fmaxf(m, probs[i * C + cls]);
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if (lane == 0) q[j] = track_quantise(m, scale, qmax);
-    }
-}
-
 __device__ __forceinline__ int track_decimal_width(uint64_t v)
 {
     int w = 1;
     for (uint64_t p = 10; w < 19 && v >= p; p *= 10) ++w;
     return w;
-}
-
-// A line "name\tstart\tend\tv.vv\n" is written in two parts: the bin where its run starts writes "name\tstart\t", the bin where it
-// ends writes "end\tv.vv\n" (one bin may do both).  The exclusive prefix sum of the parts' bytes over the bins is then where each
-// part goes: no per-run arrays.  Bins outside [0, nb) read as q = 0.
-struct track_part { uint32_t v; bool first, last; int64_t lo, hi; int64_t head, tail; };
-
-__device__ __forceinline__ track_part track_part_of(const uint32_t *__restrict__ q, const track_geom &g, int64_t j, int64_t name_len,
-                                                    int digits)
-{
-    track_part p;
-    p.v = j < g.nb ? q[j] : 0u;
-    p.first = p.last = false;
-    p.head = p.tail = 0;
-    if (p.v == 0) return p;
-    p.first = j == 0 || q[j - 1] != p.v;
-    p.last = j == g.nb - 1 || q[j + 1] != p.v;
-    track_bin_span(g, j, p.lo, p.hi);
-    if (p.first) p.head = name_len + track_decimal_width((uint64_t)p.lo) + 2;
-    if (p.last) p.tail = track_decimal_width((uint64_t)p.hi) + digits + 4;
-    return p;
-}
-
-#define TRACK_TILE 2048                  // bins per workgroup: 8 rounds of 256 consecutive bins
-
-// bytes of text per tile
-__global__ void __launch_bounds__(256) track_count_kernel(const uint32_t *__restrict__ q, track_geom g, int64_t name_len, int digits,
-                                                          uint64_t *__restrict__ tilebytes)
-{
-    __shared__ uint64_t lds[4];
-    uint64_t s = 0;
-    for (int r = 0; r < TRACK_TILE / 256; ++r) {
-        const track_part p = track_part_of(q, g, (int64_t)blockIdx.x * TRACK_TILE + r * 256 + threadIdx.x, name_len, digits);
-        s += (uint64_t)(p.head + p.tail);
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tilebytes[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
 }
 
 __device__ __forceinline__ void track_put_decimal(char *o, uint64_t v, int w)
@@ -121,121 +57,7 @@ __device__ __forceinline__ void track_put_decimal(char *o, uint64_t v, int w)
     }
 }
 
-// The text, in 8 rounds of 256 consecutive bins per tile: neighbouring lanes write neighbouring parts.  The name was copied to
-// text[0, name_len) in front of this launch (the head of the first line): the other heads copy it from there, and no lane writes
-// text[0, name_len), so no byte is both read and written.
-__global__ void __launch_bounds__(256) track_write_kernel(const uint32_t *__restrict__ q, track_geom g, int64_t name_len, int digits,
-                                                          uint32_t qmax, const uint64_t *__restrict__ tileoff, char *text)
-{
-    __shared__ uint64_t lds[4];
-    int64_t at = (int64_t)tileoff[blockIdx.x];
-    for (int r = 0; r < TRACK_TILE / 256; ++r) {
-        const int64_t j = (int64_t)blockIdx.x * TRACK_TILE + r * 256 + threadIdx.x;
-        const track_part p = track_part_of(q, g, j, name_len, digits);
-        uint64_t round_bytes;
-        char *o = text + at + (int64_t)block_exclusive_scan((uint64_t)(p.head + p.tail), &round_bytes, lds);
-        at += (int64_t)round_bytes;
-        if (p.first) {
-            if (o - text >= name_len)
-                for (int64_t c = 0; c < name_len; ++c) o[c] = text[c];
-            o += name_len;
-            *o++ = '\t';
-            const int w = track_decimal_width((uint64_t)p.lo);
-            track_put_decimal(o, (uint64_t)p.lo, w);
-            o += w;
-            *o++ = '\t';
-        }
-        if (p.last) {
-            const int w = track_decimal_width((uint64_t)p.hi);
-            track_put_decimal(o, (uint64_t)p.hi, w);
-            o += w;
-            *o++ = '\t';
-            *o++ = (char)('0' + p.v / qmax);
-            *o++ = '.';
-            track_put_decimal(o, p.v % qmax, digits);
-            o += digits;
-            *o = '\n';
-        }
-    }
-}
-
-static inline int64_t track_bins_bound(int64_t n, int64_t bin) { return n / bin + 2; }
-
-}   // namespace
-
-#define TRACK_MAX_EXTENT (1ll << 40)     // n, offset and bin: far beyond any genome; no product overflows, tiles fit a grid
-
-DGRP_EXPORT int64_t dgrp_track_workspace_bytes(int64_t n, int64_t bin)
-{
-    if (n < 0 || n > TRACK_MAX_EXTENT || bin < 1 || bin > TRACK_MAX_EXTENT) return 0;
-    const int64_t nb = track_bins_bound(n, bin);
-    return 256 + dgrp_align_up(nb * 4, 256) + dgrp_align_up((nb + TRACK_TILE - 1) / TRACK_TILE * 8, 256);
-}
-
-DGRP_EXPORT int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls, int digits, int64_t bin, int64_t offset,
-                                const char *name, int64_t name_len, char *d_text, int64_t cap, int64_t *h_bytes,
-                                void *d_work, int64_t work_bytes, void *stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    DGRP_REQUIRE(h_bytes, "dgrp_track_text: NULL h_bytes");
-    DGRP_REQUIRE(n >= 0 && n <= TRACK_MAX_EXTENT, "dgrp_track_text: bad n %lld", (long long)n);
-    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC && cls >= 0 && cls < C, "dgrp_track_text: bad C/cls (%d, %d)", C, cls);
-    DGRP_REQUIRE(digits >= 1 && digits <= 4, "dgrp_track_text: digits must lie in 1..4, got %d", digits);
-    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "dgrp_track_text: bad bin %lld", (long long)bin);
-    DGRP_REQUIRE(offset >= 0 && offset <= TRACK_MAX_EXTENT, "dgrp_track_text: bad offset %lld", (long long)offset);
-    DGRP_REQUIRE(name_len >= 0 && cap >= 0, "dgrp_track_text: bad name_len/cap");
-    DGRP_REQUIRE((name || name_len == 0) && (d_text || cap == 0) && (n == 0 || (d_probs && d_work)),
-                 "dgrp_track_text: NULL pointer");
-    *h_bytes = 0;
-    if (n == 0) return DGRP_OK;
-    if (work_bytes < dgrp_track_workspace_bytes(n, bin)) {
-        dgrp_set_error("dgrp_track_text: workspace %lld < %lld bytes", (long long)work_bytes,
-                       (long long)dgrp_track_workspace_bytes(n, bin));
-        return DGRP_ENOMEM;
-    }
-    track_geom g;
-    g.offset = offset;
-    g.n = n;
-    g.bin = bin;
-    g.kb0 = offset / bin;
-    g.nb = (offset + n - 1) / bin - g.kb0 + 1;
-    const int64_t ntiles = (g.nb + TRACK_TILE - 1) / TRACK_TILE;
-    uint64_t *grand = (uint64_t *)d_work;                                    // total bytes
-    uint32_t *q = (uint32_t *)((char *)d_work + 256);
-    uint64_t *tiles = (uint64_t *)((char *)q + dgrp_align_up(track_bins_bound(n, bin) * 4, 256));   // bytes per tile -> offsets
-    uint32_t qmax = 1;
-    for (int k = 0; k < digits; ++k) qmax *= 10;
-    const float scale = (float)qmax;
-
-    if (bin <= TRACK_WAVE_BIN) {
-        hipLaunchKernelGGL(track_bin_lane_kernel, dim3(grid_for(g.nb, 256)), dim3(256), 0, stream, d_probs, C, cls, g, scale, qmax, q);
-    } else {
-        hipLaunchKernelGGL(track_bin_wave_kernel, dim3(grid_for(g.nb * 64, 256)), dim3(256), 0, stream, d_probs, C, cls, g, scale, qmax, q);
-    }
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(track_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, g, name_len, digits, tiles);
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, tiles, ntiles, grand);
-    DGRP_LAUNCH_CHECK();
-    uint64_t total = 0;
-    DGRP_HIP(hipMemcpyAsync(&total, grand, 8, hipMemcpyDeviceToHost, stream));
-    DGRP_HIP(hipStreamSynchronize(stream));
-    *h_bytes = (int64_t)total;
-    if (total == 0 || (int64_t)total > cap) return DGRP_OK;                 // (too small: the caller retries with room for all of it)
-    if (name_len > 0) DGRP_HIP(hipMemcpyAsync(d_text, name, (size_t)name_len, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(track_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, g, name_len, digits, qmax, tiles, d_text);
-    DGRP_LAUNCH_CHECK();
-    DGRP_HIP(hipStreamSynchronize(stream));
-    return DGRP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// The same text for a BATCH of records and every selected class in one chain (dgrp_track_text_batch): a file of thousands of short
-// records costs a handful of launches and two synchronisations instead of that per record and class.  The flat bin space is
-// [class k][record r][bin j]; every class starts at a tile boundary (NBpad = bins of all records rounded up to TRACK_TILE), so no
-// tile straddles a class and the scanned tile offsets at each class's first tile are the class boundaries of the text.
-namespace {
-
+#define TRACK_TILE 2048                  // bins per workgroup: 8 rounds of 256 consecutive bins
 #define TRACK_STAGE 32768                // bytes of one round's text that are assembled in LDS (longer rounds write directly)
 
 struct tb_rec { int64_t row0, n, offset, kb0, nb, name_off, name_len, pad; };     // one record: 64 bytes of the uploaded table
@@ -352,7 +174,12 @@ __global__ void __launch_bounds__(256) tb_bin_wave_kernel(const float *__restric
     }
 }
 
-// track_part_of for flat bin f of one class (qk = that class's NBpad values): a run never leaves its record, bin 0 of a record is
+// A line "name\tstart\tend\tv.vv\n" is written in two parts: the bin where its run starts writes "name\tstart\t", the bin where it
+// ends writes "end\tv.vv\n" (one bin may do both).  The exclusive prefix sum of the parts' bytes over the bins is then where each
+// part goes: no per-run arrays.
+struct track_part { uint32_t v; bool first, last; int64_t lo, hi; int64_t head, tail; };
+
+// the parts of flat bin f of one class (qk = that class's NBpad values): a run never leaves its record, bin 0 of a record is
 // always `first` and its last bin always `last`.  Bins in [NB, NBpad) read as q = 0.
 struct tb_part { track_part p; int64_t name_off, name_len; };
 
@@ -481,20 +308,14 @@ __global__ void __launch_bounds__(256) tb_write_kernel(const uint32_t *__restric
     }
 }
 
+// byte offsets of the workspace's parts (recs .. names within the uploaded tables); NB = the bins per class it has room for
 struct tb_layout { int64_t NB, NBpad, tables, tables_bytes, recs, pref, cls, names, q, tiles, bytes; };
 
-// 0: arguments the entry refuses
-static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes,
-                     tb_layout *l)
+#define TRACK_MAX_EXTENT (1ll << 40)     // n, offset and bin: far beyond any genome; no product overflows
+
+// the workspace with room for NB bins per class; false: more bins than the grids take (2^39)
+static bool tb_carve_bins(int64_t nrec, int64_t NB, int ncls, int64_t names_bytes, tb_layout *l)
 {
-    if (nrec < 0 || bin < 1 || bin > TRACK_MAX_EXTENT || ncls < 1 || ncls > DGRP_MAXC || names_bytes < 0) return false;
-    if (nrec > 0 && (!h_n || !h_startpos)) return false;
-    int64_t NB = 0;
-    for (int64_t r = 0; r < nrec; ++r) {
-        if (h_n[r] < 1 || h_n[r] > TRACK_MAX_EXTENT || h_startpos[r] < 0 || h_startpos[r] > TRACK_MAX_EXTENT) return false;
-        NB += (h_startpos[r] + h_n[r] - 1) / bin - h_startpos[r] / bin + 1;
-        if (NB > 4 * TRACK_MAX_EXTENT) return false;
-    }
     l->NB = NB;
     l->NBpad = dgrp_align_up(NB, TRACK_TILE);
     if (l->NBpad / TRACK_TILE * ncls >= (1ll << 31) || (NB + 255) / 256 >= (1ll << 31)) return false;
@@ -515,7 +336,130 @@ static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos
     return true;
 }
 
+// the same for the bins of the given records; false: arguments the entry refuses
+static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes,
+                     tb_layout *l)
+{
+    if (nrec < 0 || bin < 1 || bin > TRACK_MAX_EXTENT || ncls < 1 || ncls > DGRP_MAXC || names_bytes < 0) return false;
+    if (nrec > 0 && (!h_n || !h_startpos)) return false;
+    int64_t NB = 0;
+    for (int64_t r = 0; r < nrec; ++r) {
+        if (h_n[r] < 1 || h_n[r] > TRACK_MAX_EXTENT || h_startpos[r] < 0 || h_startpos[r] > TRACK_MAX_EXTENT) return false;
+        NB += (h_startpos[r] + h_n[r] - 1) / bin - h_startpos[r] / bin + 1;
+        if (NB > 4 * TRACK_MAX_EXTENT) return false;
+    }
+    return tb_carve_bins(nrec, NB, ncls, names_bytes, l);
+}
+
+// The chain of both entries on checked arguments and a workspace carved as `l` (room for at least the records' bins and names): one
+// upload of the tables, bin pass, count, scan, the class boundaries to h_class_off (first synchronisation), and, if the text fits
+// cap, the write pass (second synchronisation).
+static int tb_run(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                  const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin, char *d_text,
+                  int64_t cap, int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream)
+{
+    const int64_t names_bytes = h_name_off[nrec];
+    std::vector<char> tab((size_t)(l.names + names_bytes));
+    tb_rec *recs = (tb_rec *)(tab.data() + l.recs);
+    int64_t *pref = (int64_t *)(tab.data() + l.pref);
+    pref[0] = 0;
+    for (int64_t r = 0; r < nrec; ++r) {
+        tb_rec &R = recs[r];
+        R.row0 = h_row0[r]; R.n = h_n[r]; R.offset = h_startpos[r];
+        R.kb0 = R.offset / bin;
+        R.nb = (R.offset + R.n - 1) / bin - R.kb0 + 1;
+        R.name_off = h_name_off[r]; R.name_len = h_name_off[r + 1] - h_name_off[r]; R.pad = 0;
+        pref[r + 1] = pref[r] + R.nb;
+    }
+    memcpy(tab.data() + l.cls, h_cls, (size_t)ncls * 4);
+    if (names_bytes > 0) memcpy(tab.data() + l.names, names, (size_t)names_bytes);
+    char *w = (char *)d_work;
+    DGRP_HIP(hipMemcpyAsync(w + l.tables, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
+    uint64_t *grand = (uint64_t *)w, *bounds = (uint64_t *)(w + 256);
+    const tb_rec *d_recs = (const tb_rec *)(w + l.tables + l.recs);
+    const int64_t *d_pref = (const int64_t *)(w + l.tables + l.pref);
+    const int *d_cls = (const int *)(w + l.tables + l.cls);
+    const char *d_names = w + l.tables + l.names;
+    uint32_t *q = (uint32_t *)(w + l.q);
+    uint64_t *tiles = (uint64_t *)(w + l.tiles);
+    tb_geom G;
+    G.nrec = nrec; G.NB = pref[nrec]; G.NBpad = l.NBpad; G.bin = bin; G.C = C; G.ncls = ncls; G.digits = digits;
+    uint32_t qmax = 1;
+    for (int k = 0; k < digits; ++k) qmax *= 10;
+    const float scale = (float)qmax;
+    const int64_t tpc = l.NBpad / TRACK_TILE, ntiles = tpc * ncls;
+
+    if (bin <= TRACK_WAVE_BIN) {
+        hipLaunchKernelGGL(tb_bin_lane_kernel, dim3((unsigned)((G.NB + 255) / 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
+                           scale, qmax, q);
+    } else {
+        hipLaunchKernelGGL(tb_bin_wave_kernel, dim3(grid_for(G.NB * 64, 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
+                           scale, qmax, q);
+    }
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, G, tiles);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, tiles, ntiles, grand);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tb_bounds_kernel, dim3(1), dim3(128), 0, stream, tiles, tpc, ncls, grand, bounds);
+    DGRP_LAUNCH_CHECK();
+    std::vector<uint64_t> off((size_t)ncls + 1, 0);
+    DGRP_HIP(hipMemcpyAsync(off.data(), bounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    for (int k = 0; k <= ncls; ++k) h_class_off[k] = (int64_t)off[(size_t)k];
+    const int64_t total = (int64_t)off[(size_t)ncls];
+    if (total == 0 || total > cap) return DGRP_OK;                          // (too small: the caller retries with room for all of it)
+    hipLaunchKernelGGL(tb_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, d_names, G, qmax, tiles, d_text);
+    DGRP_LAUNCH_CHECK();
+    DGRP_HIP(hipStreamSynchronize(stream));
+    return DGRP_OK;
+}
+
+// one record, whatever its offset, has at most n / bin + 2 bins
+static bool track_carve_one(int64_t n, int64_t bin, tb_layout *l)
+{
+    if (n < 0 || n > TRACK_MAX_EXTENT || bin < 1 || bin > TRACK_MAX_EXTENT) return false;
+    return tb_carve_bins(1, n / bin + 2, 1, DGRP_TRACK_NAME_ROOM, l);
+}
+
 }   // namespace
+
+DGRP_EXPORT int64_t dgrp_track_workspace_bytes(int64_t n, int64_t bin)
+{
+    tb_layout l;
+    return track_carve_one(n, bin, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls, int digits, int64_t bin, int64_t offset,
+                                const char *name, int64_t name_len, char *d_text, int64_t cap, int64_t *h_bytes,
+                                void *d_work, int64_t work_bytes, void *stream_)
+{
+    DGRP_REQUIRE(h_bytes, "dgrp_track_text: NULL h_bytes");
+    DGRP_REQUIRE(n >= 0 && n <= TRACK_MAX_EXTENT, "dgrp_track_text: bad n %lld", (long long)n);
+    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC && cls >= 0 && cls < C, "dgrp_track_text: bad C/cls (%d, %d)", C, cls);
+    DGRP_REQUIRE(digits >= 1 && digits <= 4, "dgrp_track_text: digits must lie in 1..4, got %d", digits);
+    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "dgrp_track_text: bad bin %lld", (long long)bin);
+    DGRP_REQUIRE(offset >= 0 && offset <= TRACK_MAX_EXTENT, "dgrp_track_text: bad offset %lld", (long long)offset);
+    DGRP_REQUIRE(name_len >= 0 && cap >= 0, "dgrp_track_text: bad name_len/cap");
+    DGRP_REQUIRE(name_len <= DGRP_TRACK_NAME_ROOM, "dgrp_track_text: a name of %lld bytes is longer than the limit of %d",
+                 (long long)name_len, DGRP_TRACK_NAME_ROOM);
+    DGRP_REQUIRE((name || name_len == 0) && (d_text || cap == 0) && (n == 0 || (d_probs && d_work)),
+                 "dgrp_track_text: NULL pointer");
+    *h_bytes = 0;
+    if (n == 0) return DGRP_OK;
+    tb_layout l;
+    DGRP_REQUIRE(track_carve_one(n, bin, &l), "dgrp_track_text: too many bins in one call");
+    if (work_bytes < l.bytes) {
+        dgrp_set_error("dgrp_track_text: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
+        return DGRP_ENOMEM;
+    }
+    const int64_t row0 = 0, name_off[2] = {0, name_len};
+    int64_t class_off[2] = {0, 0};
+    const int rc = tb_run(d_probs, C, 1, &row0, &n, &offset, name, name_off, &cls, 1, digits, bin, d_text, cap, class_off, d_work, l,
+                          (hipStream_t)stream_);
+    *h_bytes = class_off[1];
+    return rc;
+}
 
 DGRP_EXPORT int64_t dgrp_track_batch_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
                                                      int64_t names_bytes)
@@ -529,7 +473,6 @@ DGRP_EXPORT int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec,
                                       int ncls, int digits, int64_t bin, char *d_text, int64_t cap, int64_t *h_class_off,
                                       void *d_work, int64_t work_bytes, void *stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC, "dgrp_track_text_batch: bad C %d", C);
     DGRP_REQUIRE(ncls >= 1 && ncls <= C, "dgrp_track_text_batch: ncls must lie in 1..C (%d, C = %d)", ncls, C);
     DGRP_REQUIRE(h_class_off && h_cls, "dgrp_track_text_batch: NULL h_class_off or h_cls");
@@ -560,59 +503,6 @@ DGRP_EXPORT int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec,
         dgrp_set_error("dgrp_track_text_batch: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
         return DGRP_ENOMEM;
     }
-    // ---- tables: one upload
-    std::vector<char> tab((size_t)l.tables_bytes);
-    tb_rec *recs = (tb_rec *)(tab.data() + l.recs);
-    int64_t *pref = (int64_t *)(tab.data() + l.pref);
-    pref[0] = 0;
-    for (int64_t r = 0; r < nrec; ++r) {
-        tb_rec &R = recs[r];
-        R.row0 = h_row0[r]; R.n = h_n[r]; R.offset = h_startpos[r];
-        R.kb0 = R.offset / bin;
-        R.nb = (R.offset + R.n - 1) / bin - R.kb0 + 1;
-        R.name_off = h_name_off[r]; R.name_len = h_name_off[r + 1] - h_name_off[r]; R.pad = 0;
-        pref[r + 1] = pref[r] + R.nb;
-    }
-    memcpy(tab.data() + l.cls, h_cls, (size_t)ncls * 4);
-    if (names_bytes > 0) memcpy(tab.data() + l.names, names, (size_t)names_bytes);
-    char *w = (char *)d_work;
-    DGRP_HIP(hipMemcpyAsync(w + l.tables, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
-    uint64_t *grand = (uint64_t *)w, *bounds = (uint64_t *)(w + 256);
-    const tb_rec *d_recs = (const tb_rec *)(w + l.tables + l.recs);
-    const int64_t *d_pref = (const int64_t *)(w + l.tables + l.pref);
-    const int *d_cls = (const int *)(w + l.tables + l.cls);
-    const char *d_names = w + l.tables + l.names;
-    uint32_t *q = (uint32_t *)(w + l.q);
-    uint64_t *tiles = (uint64_t *)(w + l.tiles);
-    tb_geom G;
-    G.nrec = nrec; G.NB = l.NB; G.NBpad = l.NBpad; G.bin = bin; G.C = C; G.ncls = ncls; G.digits = digits;
-    uint32_t qmax = 1;
-    for (int k = 0; k < digits; ++k) qmax *= 10;
-    const float scale = (float)qmax;
-    const int64_t tpc = l.NBpad / TRACK_TILE, ntiles = tpc * ncls;
-
-    if (bin <= TRACK_WAVE_BIN) {
-        hipLaunchKernelGGL(tb_bin_lane_kernel, dim3((unsigned)((l.NB + 255) / 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
-                           scale, qmax, q);
-    } else {
-        hipLaunchKernelGGL(tb_bin_wave_kernel, dim3(grid_for(l.NB * 64, 256)), dim3(256), 0, stream, d_probs, d_recs, d_pref, d_cls, G,
-                           scale, qmax, q);
-    }
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, G, tiles);
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, tiles, ntiles, grand);
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tb_bounds_kernel, dim3(1), dim3(128), 0, stream, tiles, tpc, ncls, grand, bounds);
-    DGRP_LAUNCH_CHECK();
-    std::vector<uint64_t> off((size_t)ncls + 1, 0);
-    DGRP_HIP(hipMemcpyAsync(off.data(), bounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
-    DGRP_HIP(hipStreamSynchronize(stream));
-    for (int k = 0; k <= ncls; ++k) h_class_off[k] = (int64_t)off[(size_t)k];
-    const int64_t total = (int64_t)off[(size_t)ncls];
-    if (total == 0 || total > cap) return DGRP_OK;                          // (too small: the caller retries with room for all of it)
-    hipLaunchKernelGGL(tb_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, d_names, G, qmax, tiles, d_text);
-    DGRP_LAUNCH_CHECK();
-    DGRP_HIP(hipStreamSynchronize(stream));
-    return DGRP_OK;
+    return tb_run(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, d_text, cap, h_class_off, d_work,
+                  l, (hipStream_t)stream_);
 }

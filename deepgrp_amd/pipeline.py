@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .fasta import DeviceRecord
 
 SEGMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")])
 
@@ -261,6 +262,13 @@ class DeviceModel:
         return self.forward_windows(idx, self.vecsize, 0, b).cpu().numpy()
 
 
+def kept_length(n: int) -> int:
+    """The all-N rule: such a record's kept length is negative, and the reference's np.zeros raises on it (sequence.pyx:32)."""
+    if n < 0:
+        raise ValueError("negative dimensions are not allowed")
+    return n
+
+
 def upload_sequence(raw: bytes) -> Tuple[int, torch.Tensor]:
     """A2 on the device: (startpos, class-index uint8 [N]).  Mirrors
     one_hot_encode_dna_sequence's stripping of leading/trailing 'N' (sequence.pyx:27-30),
@@ -269,14 +277,21 @@ def upload_sequence(raw: bytes) -> Tuple[int, torch.Tensor]:
     st, kept = C.c_int64(0), C.c_int64(0)
     host = np.frombuffer(raw, dtype=np.uint8)
     check(lib().dgrp_strip_n(_np_ptr(host) if len(raw) else None, len(raw), C.byref(st), C.byref(kept)), "dgrp_strip_n")
-    if kept.value < 0:
-        raise ValueError("negative dimensions are not allowed")
-    n = kept.value
+    n = kept_length(kept.value)
     d_idx = torch.empty(n, dtype=torch.uint8, device=dev)
     if n:
         d_seq = torch.from_numpy(host[st.value:st.value + n].copy()).to(dev, non_blocking=False)
         check(lib().dgrp_encode(_ptr(d_seq), n, _ptr(d_idx), stream_ptr()), "dgrp_encode")
     return st.value, d_idx
+
+
+def record_indices(rec) -> Tuple[int, torch.Tensor]:
+    """(startpos, class-index uint8 [N]) of a record in either form: a fasta.DeviceRecord, parsed and encoded on the GPU, or the
+    sequence as text (str or bytes), uploaded here.  An all-N record raises in both."""
+    if isinstance(rec, DeviceRecord):
+        kept_length(rec.length)
+        return rec.startpos, rec.d_idx
+    return upload_sequence(rec.encode("utf-8") if isinstance(rec, str) else bytes(rec))
 
 
 class ContigPipeline:
@@ -433,35 +448,16 @@ class ContigPipeline:
 
     # predict --track_dir
     def track_text(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> bytes:
-        """bedGraph lines of class `cls` of one record's merged probabilities (dgrp_track_text): `name` (str, surrogateescape, or
+        """bedGraph lines of class `cls` of one record's merged probabilities (ContigPipeline.merged): `name` (str, surrogateescape, or
         bytes) in the first column, row i at coordinate startpos + i, bins of `bin` bases, values with `digits` decimals."""
         return self.track_text_device(merged, startpos, name, cls, digits, bin).cpu().numpy().tobytes()
 
     def track_text_device(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> torch.Tensor:
-        """track_text's bytes as a uint8 device tensor, where dgrp_track_text wrote them: nothing but the size is read back."""
-        L = lib()
-        if merged.dtype != torch.float32 or merged.ndim != 2 or not merged.is_contiguous():
-            raise ValueError("track_text takes the contiguous float32 [n, C] array of merged()")
-        n, c = merged.shape
-        raw = name if isinstance(name, bytes) else name.encode("utf-8", "surrogateescape")
-        dev = merged.device
-        if n == 0:
-            return torch.empty(0, dtype=torch.uint8, device=dev)
-        wb = L.dgrp_track_workspace_bytes(n, bin)
-        if wb <= 0:
-            raise ValueError(f"track_text: bad record length {n} or bin {bin}")
-        work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        nb = n // bin + 2
-        cap = min(nb * (len(raw) + 50), (1 << 20) + nb * (len(raw) + 12))      # (a line per bin at most; the guess fits most runs)
-        total = C.c_int64(0)
-        while True:
-            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            check(L.dgrp_track_text(_ptr(merged), n, c, int(cls), int(digits), int(bin), int(startpos), raw, len(raw), _ptr(text),
-                                    cap, C.byref(total), _ptr(work), wb, stream_ptr()), "dgrp_track_text")
-            if total.value <= cap:
-                break
-            cap = int(total.value)                          # more text than guessed: run again with room for all of it
-        return text[:total.value]
+        """track_text's bytes as a uint8 device tensor, where the kernels wrote them (nothing but the size is read back): a
+        one-record, one-class call of track_text_batch_device."""
+        if merged.ndim == 2 and merged.shape[0] == 0:
+            return torch.empty(0, dtype=torch.uint8, device=merged.device)
+        return self.track_text_batch_device(merged, [0], [len(merged)], [startpos], [name], [cls], digits, bin)[0]
 
     def run_idx(self, d_idx: torch.Tensor, startpos: int, contig: int = 0) -> np.ndarray:
         """Segment records of one record whose class indices are on the device: one dgrp_predict_record call
@@ -592,6 +588,5 @@ class ContigPipeline:
         return rows, texts
 
     def run(self, sequence, contig: int = 0) -> np.ndarray:
-        raw = sequence.encode("utf-8") if isinstance(sequence, str) else bytes(sequence)
-        startpos, d_idx = upload_sequence(raw)
+        startpos, d_idx = record_indices(sequence)
         return self.run_idx(d_idx, startpos, contig)

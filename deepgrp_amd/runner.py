@@ -15,10 +15,10 @@ import numpy as np
 import torch
 
 from .fasta import DeviceRecord
-from .pipeline import ContigPipeline
+from .pipeline import ContigPipeline, record_indices
 
 class _Tracked(NamedTuple):
-    """A work item of track_results: one record and the name of its track lines."""
+    """A work item of tracked_results: one record and the name of its track lines."""
     name: str
     rec: object
 
@@ -95,21 +95,15 @@ class RecordRunner:
     # ---- one record
     def run_record(self, rec, contig: int = 0) -> np.ndarray:
         if isinstance(rec, DeviceRecord):                 # parsed and encoded on the GPU
-            if rec.length < 0:
-                raise ValueError("negative dimensions are not allowed")     # all-N record, sequence.pyx:32
-            return self.pipe.run_idx(rec.d_idx, rec.startpos, contig)
+            startpos, d_idx = record_indices(rec)
+            return self.pipe.run_idx(d_idx, startpos, contig)
         return self.pipe.run(rec, contig)
 
     def run_tracked(self, rec, name: str):
         """(rows, track texts) of one record: merged -> the text of every class of self.tracks -> labels -> segments."""
-        from .pipeline import SEGMENT_DTYPE, upload_sequence
+        from .pipeline import SEGMENT_DTYPE
         from .tracks import record_texts
-        if isinstance(rec, DeviceRecord):
-            if rec.length < 0:
-                raise ValueError("negative dimensions are not allowed")     # all-N record, sequence.pyx:32
-            startpos, d_idx = rec.startpos, rec.d_idx
-        else:
-            startpos, d_idx = upload_sequence(rec.encode("utf-8") if isinstance(rec, str) else bytes(rec))
+        startpos, d_idx = record_indices(rec)
         if d_idx.numel() == 0:
             return np.zeros(0, SEGMENT_DTYPE), [b""] * len(self.tracks.classes)
         merged = self.pipe.merged(d_idx)
@@ -217,17 +211,11 @@ class RecordRunner:
             else:
                 yield "one", key, result
 
-    def track_results(self, records: Iterable[Tuple[object, object]]):
-        """With self.tracks: (key, rows, texts) per record in input order; every key is (header, name), name the first column of
-        the record's track lines (evaluation.record_name), and texts[k] is the track text of class self.tracks.classes[k]."""
-        items = ((key, _Tracked(key[1], rec)) for key, rec in records)
-        for key, (rows, texts) in self.in_order(items):
-            yield key, rows, texts
-
     def tracked_results(self, records: Iterable[Tuple[object, object]]):
-        """With self.tracks, keys as in track_results: ("one", key, rows, texts) for a record on its own, ("batch", [keys], rows,
-        texts) for a batch of short records -- rows["contig"] indexes the keys, texts[k] is the text of class
-        self.tracks.classes[k] of all its records in order.  Records batch exactly when they do without tracks."""
+        """With self.tracks; every key is (header, name), name the first column of the record's track lines
+        (evaluation.record_name): ("one", key, rows, texts) for a record on its own, ("batch", [keys], rows, texts) for a batch of
+        short records -- rows["contig"] indexes the keys, texts[k] is the text of class self.tracks.classes[k] of all its records in
+        order.  Records batch exactly when they do without tracks."""
         def items():
             for key, item in self.work_items(records):
                 if key is _BATCH:

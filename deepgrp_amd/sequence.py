@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .pipeline import ContigPipeline, require_gpu, stream_ptr
+from .pipeline import ContigPipeline, kept_length, require_gpu, stream_ptr
 
 
 def one_hot_encode_dna_sequence(sequence: str) -> Tuple[int, np.ndarray]:
@@ -23,9 +23,7 @@ def one_hot_encode_dna_sequence(sequence: str) -> Tuple[int, np.ndarray]:
     st, kept = C.c_int64(0), C.c_int64(0)
     host = np.frombuffer(raw, dtype=np.uint8)
     check(lib().dgrp_strip_n(host.ctypes.data_as(C.c_void_p) if len(raw) else None, len(raw), C.byref(st), C.byref(kept)))
-    if kept.value < 0:
-        raise ValueError("negative dimensions are not allowed")
-    n = kept.value
+    n = kept_length(kept.value)
     if n == 0:
         return st.value, np.zeros((5, 0), np.int8)
     d_seq = torch.from_numpy(host[st.value:st.value + n].copy()).to(dev)

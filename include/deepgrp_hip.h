@@ -292,9 +292,14 @@ int dgrp_format_rows(const char *prefixes, const int64_t *prefix_off, int64_t np
  * clipped to [offset, offset + n); its value is the maximum of the class column over the bin's rows (starting from 0: a NaN never
  * wins), quantised to q = floor(v * 10^digits + 0.5) in float32 (two roundings) and clamped to [0, 10^digits].  Consecutive bins of
  * equal q are one line; lines of q = 0 are left out.  The value is printed from the integer: q / 10^digits with exactly `digits`
- * decimals ("0.05", "1.00").  name = name_len raw bytes (host), written as they are.  *h_bytes (host) = the text's length, also
- * when it exceeds cap: then nothing is written and the caller retries with a larger buffer.  digits 1..4, bin >= 1, n, offset
- * and bin up to 2^40.  Workspace dgrp_track_workspace_bytes(n, bin) (4 bytes per bin).  Synchronises the stream. */
+ * decimals ("0.05", "1.00").  name = name_len raw bytes (host), written as they are; up to DGRP_TRACK_NAME_ROOM of them, a longer
+ * name is refused (DGRP_EINVAL).  *h_bytes (host) = the text's length, also when it exceeds cap: then nothing is written and the
+ * caller retries with a larger buffer.  digits 1..4, bin >= 1, n, offset and bin up to 2^40, and at most 2^39 bins in one call (the
+ * grids of the chain; "too many bins in one call" beyond that, and the workspace query gives 0).  This is the batched entry below
+ * with one record and one class: the same kernels, the same launch sequence.  Workspace dgrp_track_workspace_bytes(n, bin): the
+ * batched layout for one record of at most n / bin + 2 bins, whatever its offset, and a name of DGRP_TRACK_NAME_ROOM bytes -- 4
+ * bytes per bin rounded up to tiles of 2048 bins, 8 bytes per tile, and the tables.  Synchronises the stream (at most twice). */
+#define DGRP_TRACK_NAME_ROOM 65536     /* bytes: two orders of magnitude above any first word of a FASTA header */
 int64_t dgrp_track_workspace_bytes(int64_t n, int64_t bin);
 int dgrp_track_text(const float *d_probs, int64_t n, int C, int cls, int digits, int64_t bin, int64_t offset,
                     const char *name, int64_t name_len, char *d_text, int64_t cap, int64_t *h_bytes,

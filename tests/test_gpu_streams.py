@@ -519,6 +519,40 @@ def test_sync_track_text(H, L, fill):
     assert late["text"][:total].tobytes() == want and (late["text"][total:] == 0x5A).all()
 
 
+@fills
+def test_sync_track_text_batch(H, L, fill):
+    from deepgrp_amd.tracks import reference_text
+    c, digits, bin_ = 5, 2, 7
+    n = np.array([1, 65, 4097], np.int64)
+    row0 = np.r_[0, np.cumsum((n[:-1] + 63) // 64 * 64)].astype(np.int64)
+    rows = int(row0[-1] + n[-1])
+    spos = np.array([0, 10 ** 11 + 3, 123], np.int64)
+    names = [b"a", b"chr\xce\xb1 1", b"scaffold_3"]
+    noff = np.r_[0, np.cumsum([len(x) for x in names])].astype(np.int64)
+    blob = b"".join(names)
+    cls = np.array([0, 3], np.int32)
+    real, poison = _probs(13, rows, c), _probs(130, rows, c)
+    real[row0[2] + 1000:row0[2] + 1500, 0] = 0.0
+    real[row0[2] + 2000:row0[2] + 2600, 3] = 0.5
+    want = [b"".join(reference_text(real[row0[r]:row0[r] + n[r], k], int(spos[r]), names[r], digits, bin_) for r in range(len(n))) for k in cls]
+    total = sum(len(w) for w in want)
+    cap = total + 64
+    wb = L.dgrp_track_batch_workspace_bytes(len(n), n.ctypes.data, spos.ctypes.data, bin_, len(cls), len(blob))
+
+    def call(b, wk, st, t):
+        off = np.full(len(cls) + 1, -1, np.int64)
+        nm = C.create_string_buffer(blob, len(blob))
+        rc = L.dgrp_track_text_batch(b["p"].data_ptr(), c, len(n), i64ptr(t["row0"]), i64ptr(t["n"]), i64ptr(t["spos"]), nm, i64ptr(t["noff"]),
+                                     t["cls"].ctypes.data, len(cls), digits, bin_, b["text"].data_ptr(), cap, off.ctypes.data, wk.data_ptr(), wb, st)
+        C.memset(nm, ord("#"), len(blob))                                     # the names are a host table too
+        return rc, off.tolist()
+    late, off, _, off_idle = H.run(call, {"p": (real, poison)}, {"text": np.full(cap, 0x5A, np.uint8)}, work_bytes=wb, fill=fill, sync=True,
+                                   tables={"row0": row0, "n": n.copy(), "spos": spos, "noff": noff, "cls": cls})
+    assert off == off_idle == np.r_[0, np.cumsum([len(w) for w in want])].tolist()
+    assert late["text"][:total].tobytes() == b"".join(want) and (late["text"][total:] == 0x5A).all()
+    assert total > 3000
+
+
 # ---------------------------------------------------------------------------------------------------------- synchronising: predict
 def _rows3(a):
     return np.stack([a["start"], a["end"], a["label"]], 1).reshape(-1, 3)

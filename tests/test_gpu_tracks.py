@@ -93,6 +93,64 @@ def test_track_kernel_against_the_statement():
     assert checked > 150 and lines > 100_000
 
 
+def _exact_text(L, probs, startpos, name, cls, digits, bin):
+    """dgrp_track_text in a workspace of exactly dgrp_track_workspace_bytes(n, bin) bytes and a text buffer of exactly the length
+    a first call (cap 0) reports."""
+    from deepgrp_amd._lib import check
+    from deepgrp_amd.pipeline import stream_ptr
+    n, c = probs.shape
+    wb = L.dgrp_track_workspace_bytes(n, bin)
+    assert wb > 0
+    work = torch.empty(wb, dtype=torch.uint8, device=probs.device)
+    total = C.c_int64(-1)
+    text = torch.empty(1, dtype=torch.uint8, device=probs.device)
+    for _ in range(2):
+        check(L.dgrp_track_text(probs.data_ptr(), n, c, cls, digits, bin, startpos, name, len(name), text.data_ptr(), max(total.value, 0),
+                                C.byref(total), work.data_ptr(), wb, stream_ptr()), "dgrp_track_text")
+        if total.value > 0 and text.numel() != total.value:
+            text = torch.empty(total.value, dtype=torch.uint8, device=probs.device)
+    return text[:total.value].cpu().numpy().tobytes()
+
+
+def test_track_kernel_long_names():
+    """Names of 300 bytes and of exactly the name room through the one-record entry: the ten lines of the first are assembled in
+    the write kernel's staging area, those of the second (655 KB) pass its size and take the direct (unstaged) branch."""
+    from deepgrp_amd._lib import lib
+    from deepgrp_amd.tracks import reference_text
+    L = lib()
+    rng = np.random.default_rng(11)
+    n, Cn, bin = 65, 2, 7
+    arr = rng.random((n, Cn)).astype(np.float32)
+    d = torch.from_numpy(arr).cuda()
+    for name in (b"n" * 300, bytes(rng.integers(33, 127, 65536, dtype=np.uint8))):
+        for cls in range(Cn):
+            want = reference_text(arr[:, cls], 3, name, 2, bin)
+            assert want.count(b"\n") == 10                          # noise: every bin its own line
+            assert _exact_text(L, d, 3, name, cls, 2, bin) == want, (len(name), cls)
+
+
+def test_track_kernel_offsets_in_the_exact_workspace():
+    """Every offset, in a workspace of exactly the query's size: the shapes where the offset-free bin bound, the tile rounding and
+    the lane / wave switch could disagree with the call."""
+    from deepgrp_amd._lib import lib
+    from deepgrp_amd.tracks import reference_text
+    L = lib()
+    rng = np.random.default_rng(12)
+    checked = lines = 0
+    for n in (1, 63, 64, 65, 2049):
+        arr = rng.random((n, 2)).astype(np.float32)
+        arr[:, 1] = _column(rng, "runs", n, 2)
+        d = torch.from_numpy(arr).cuda()
+        for bin in (1, 7, 200):
+            for startpos in (0, bin * 3 + bin // 2, 10 ** 11 + 3):
+                for cls in (0, 1):
+                    want = reference_text(arr[:, cls], startpos, b"chr1", 2, bin)
+                    assert _exact_text(L, d, startpos, b"chr1", cls, 2, bin) == want, (n, bin, startpos, cls)
+                    checked += 1
+                    lines += want.count(b"\n")
+    assert checked == 90 and lines > 3000
+
+
 def test_track_kernel_tens_of_mbp():
     """One record of 40 Mbp (runs, a stretch of noise, boundary values) at base resolution and at bin 50, name with non-ASCII."""
     from deepgrp_amd.tracks import reference_text

@@ -185,5 +185,7 @@ def test_runner_batches_short_records_with_a_track_spec():
     assert got[0][3] == [b"r0:1;r1:1;", b"r0:3;r1:3;"] and got[0][2] == 2
     assert got[2][3] == [b"one:r3"] * 2
     assert pipe.calls[:3] == [["r0", "r1"], ["r2"], ["r4"]]
-    # track_results keeps its per-record contract
-    assert [(k[1], texts) for k, _rows, texts in with_tracks.track_results(recs[:3])] == [(h, [b"one:" + h.encode()] * 2) for h in ("r0", "r1", "r2")]
+    # records that do not batch (text, long, text) come out record by record, with their keys and their own texts
+    lone = [recs[3], recs[5], (key("r9"), "TTGA")]
+    assert [(kind, k, texts) for kind, k, _rows, texts in with_tracks.tracked_results(lone)] == \
+        [("one", key(h), [b"one:" + h.encode()] * 2) for h in ("r3", "r5", "r9")]

@@ -117,13 +117,33 @@ def test_track_text_without_device_work():
     L = _lib()
     assert L.dgrp_track_workspace_bytes(-1, 1) == 0 and L.dgrp_track_workspace_bytes(10, 0) == 0
     assert L.dgrp_track_workspace_bytes(1 << 50, 1) == 0
-    assert L.dgrp_track_workspace_bytes(1000, 1) >= 4 * 1000 > L.dgrp_track_workspace_bytes(1000, 50) > 0
+    ws = L.dgrp_track_workspace_bytes
+    # 4 bytes per bin at least; never less for a longer record, never more for a wider bin
+    ns, bins = (1, 63, 1000, 2047, 2048, 2049, 100_000, 10_000_000), (1, 2, 7, 50, 64, 65, 1000)
+    assert all(ws(n, 1) >= 4 * n for n in ns)
+    assert all(ws(a, b) <= ws(a2, b) for b in bins for a, a2 in zip(ns, ns[1:]))
+    assert all(ws(n, b) >= ws(n, b2) for n in ns for b, b2 in zip(bins, bins[1:]))
+    assert ws(1000, 50) > 0
+    assert ws(1 << 39, 1) == 0 and ws(1 << 40, 4) > 0                  # the 2^39 bins of one call
     h = C.c_int64(-7)
     # an empty record writes nothing (NULL buffers are fine); a workspace below the bound is refused before any launch
     assert L.dgrp_track_text(None, 0, 5, 1, 2, 1, 3, b"x", 1, None, 0, C.byref(h), None, 0, None) == 0 and h.value == 0
     assert _track_call(wb=L.dgrp_track_workspace_bytes(100, 1) - 1) == ENOMEM
     assert "workspace" in L.dgrp_last_error().decode()
     assert "dgrp_track_text" in __import__("deepgrp_amd._lib", fromlist=["exported_symbols"]).exported_symbols()
+
+
+def test_track_text_name_room():
+    """A name of exactly DGRP_TRACK_NAME_ROOM bytes passes the argument checks (the workspace check is what refuses this call);
+    one byte more is a bad argument, and the message names the limit."""
+    L = _lib()
+    room = 65536
+    short = L.dgrp_track_workspace_bytes(100, 1) - 1
+    assert _track_call(name=b"x" * room, wb=short) == ENOMEM
+    assert "workspace" in L.dgrp_last_error().decode()
+    assert _track_call(name=b"x" * (room + 1), wb=short) == EINVAL
+    msg = L.dgrp_last_error().decode()
+    assert "name" in msg and str(room) in msg, msg
 
 
 # ---------------------------------------------------------------- the format, stated in numpy

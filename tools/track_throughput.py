@@ -74,7 +74,7 @@ merged, t_fwd = timed(lambda: pipe.merged(d_idx), 3)
 texts, t_trk = timed(lambda: [pipe.track_text(merged, st, name, c) for c in (1, 2, 3, 4)], 3)
 out(what="in-process", mbp=mbp, forward_merge_ms=t_fwd, tracks_4_classes_ms=t_trk,
     track_share_of_forward=round(min(t_trk) / min(t_fwd), 4),
-    note="tracks: 4 calls of dgrp_track_text incl. the device->host copy of the text and the bytes object")
+    note="tracks: 4 one-class calls of the track chain incl. the device->host copy of the text and the bytes object")
 text_bytes = sum(len(t) for t in texts)
 del merged, texts
 
