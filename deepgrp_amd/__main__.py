@@ -11,7 +11,8 @@ Differences, all additive:
     (deepgrp_amd/masking.py);
   * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B] [--track_gzip]` also writes the per-base class
     probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py), with --track_gzip as BGZF deflated on the GPU
-    (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well);
+    (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well) and with --track_index a tabix index beside
+    every BGZF track (deepgrp_amd/tabix.py);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
@@ -151,6 +152,10 @@ def _add_track_options(parser) -> None:
     parser.add_argument("--track_gzip", action="store_true", default=s,
                         help="(addition) with --track_dir: write every track as BGZF (bgzip's format, deflated on the GPU where the "
                              "text is made) to DIR/<basename>.class<c>.bedGraph.gz")
+    parser.add_argument("--track_index", action="store_true", default=s,
+                        help="(addition) with --track_gzip: write the tabix index <track>.gz.tbi of every track, built on the GPU "
+                             "beside the text (records must end at or below 2^29 and names must not reappear after another name; "
+                             "otherwise a warning and no index)")
     parser.add_argument("--track_classes", type=_class_list, default=s,
                         help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
     parser.add_argument("--track_digits", type=int, default=s,
@@ -720,7 +725,7 @@ class CommandLineParser:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
         if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
             sys.exit("--mask_dir belongs to predict, not evaluate")
-        if getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False):
+        if getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False):
             sys.exit("--track_dir belongs to predict, not evaluate")
         if getattr(args, "gzip_level", None) is not None:
             sys.exit("--gzip_level belongs to predict, not evaluate")

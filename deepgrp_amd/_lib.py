@@ -40,7 +40,9 @@ _SIGNATURES = {
     "dgrp_track_text": (cint, [vp, i64, cint, cint, cint, i64, i64, C.c_char_p, i64, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_track_batch_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64]),
     "dgrp_track_text_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp]),
-    "dgrp_window_count": (i64, [i64, i64, i64]),
+    "dgrp_track_index_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64]),
+    "dgrp_track_index_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp, i64, vp]),
+    "dgrp_window_count":(i64, [i64, i64, i64]),
     "dgrp_windows_onehot": (cint, [vp, i64, i64, i64, i64, i64, cint, vp, vp]),
     "dgrp_model_create": (cint, [C.POINTER(vp), cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]),
     "dgrp_model_create_lstm": (cint, [C.POINTER(vp), cint, cint, cint, vp, vp, vp, vp, vp]),

@@ -351,12 +351,25 @@ static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos
     return tb_carve_bins(nrec, NB, ncls, names_bytes, l);
 }
 
-// The chain of both entries on checked arguments and a workspace carved as `l` (room for at least the records' bins and names): one
-// upload of the tables, bin pass, count, scan, the class boundaries to h_class_off (first synchronisation), and, if the text fits
-// cap, the write pass (second synchronisation).
-static int tb_run(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
-                  const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin, char *d_text,
-                  int64_t cap, int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream)
+// what the front half of the chain leaves on the device for the pass that follows it
+struct tb_dev {
+    uint64_t *grand, *bounds;            // the text's total, its class boundaries [ncls + 1]
+    const tb_rec *recs;
+    const int64_t *pref;
+    const int *cls;
+    const char *names;
+    uint32_t *q;
+    uint64_t *tiles;                     // scanned: the text offset of every tile
+    tb_geom G;
+    uint32_t qmax;
+    int64_t tpc, ntiles;                 // tiles per class, tiles
+};
+
+// The front half of every chain on checked arguments and a workspace carved as `l` (room for at least the records' bins and names):
+// one upload of the tables, bin pass, count, scan, the class boundaries to h_class_off (one synchronisation).
+static int tb_front(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                    const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin,
+                    int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream, tb_dev *D)
 {
     const int64_t names_bytes = h_name_off[nrec];
     std::vector<char> tab((size_t)(l.names + names_bytes));
@@ -379,7 +392,6 @@ static int tb_run(const float *d_probs, int C, int64_t nrec, const int64_t *h_ro
     const tb_rec *d_recs = (const tb_rec *)(w + l.tables + l.recs);
     const int64_t *d_pref = (const int64_t *)(w + l.tables + l.pref);
     const int *d_cls = (const int *)(w + l.tables + l.cls);
-    const char *d_names = w + l.tables + l.names;
     uint32_t *q = (uint32_t *)(w + l.q);
     uint64_t *tiles = (uint64_t *)(w + l.tiles);
     tb_geom G;
@@ -407,9 +419,25 @@ static int tb_run(const float *d_probs, int C, int64_t nrec, const int64_t *h_ro
     DGRP_HIP(hipMemcpyAsync(off.data(), bounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
     DGRP_HIP(hipStreamSynchronize(stream));
     for (int k = 0; k <= ncls; ++k) h_class_off[k] = (int64_t)off[(size_t)k];
-    const int64_t total = (int64_t)off[(size_t)ncls];
+    D->grand = grand; D->bounds = bounds; D->recs = d_recs; D->pref = d_pref; D->cls = d_cls; D->names = w + l.tables + l.names;
+    D->q = q; D->tiles = tiles; D->G = G; D->qmax = qmax; D->tpc = tpc; D->ntiles = ntiles;
+    return DGRP_OK;
+}
+
+// The text chain of both text entries: the front half (first synchronisation) and, if the text fits cap, the write pass (second
+// synchronisation).
+static int tb_run(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                  const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin, char *d_text,
+                  int64_t cap, int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream)
+{
+    tb_dev D;
+    const int rc = tb_front(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, h_class_off, d_work, l,
+                            stream, &D);
+    if (rc != DGRP_OK) return rc;
+    const int64_t total = h_class_off[ncls];
     if (total == 0 || total > cap) return DGRP_OK;                          // (too small: the caller retries with room for all of it)
-    hipLaunchKernelGGL(tb_write_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, d_names, G, qmax, tiles, d_text);
+    hipLaunchKernelGGL(tb_write_kernel, dim3((unsigned)D.ntiles), dim3(256), 0, stream, D.q, D.recs, D.pref, D.names, D.G, D.qmax, D.tiles,
+                       d_text);
     DGRP_LAUNCH_CHECK();
     DGRP_HIP(hipStreamSynchronize(stream));
     return DGRP_OK;
@@ -420,6 +448,239 @@ static bool track_carve_one(int64_t n, int64_t bin, tb_layout *l)
 {
     if (n < 0 || n > TRACK_MAX_EXTENT || bin < 1 || bin > TRACK_MAX_EXTENT) return false;
     return tb_carve_bins(1, n / bin + 2, 1, DGRP_TRACK_NAME_ROOM, l);
+}
+
+// ---- tabix index of the text (dgrp_track_index_batch): the chunks of hts_idx_push and the 16 kb linear index, in offsets of the text
+// the text entry would write.  A line exists only as its `first` and its `last` bin, possibly tiles apart, so what a line needs of
+// itself and of the line in front of it comes from one forward scan: the two latest `first` positions and the two latest `last`
+// positions at or in front of every bin (firsts and lasts alternate, so at a `last` bin these are the line's own first bin, the
+// previous line's first bin, the bin itself and the previous line's last bin).  Coordinates follow from bin positions by
+// arithmetic, and a line's first byte is its end minus its length, which its coordinates give.  No lane walks a run or a gap.
+#define IX_SHIFT 14
+#define IX_MAX_END (1ll << 29)           // TBI: min_shift 14, depth 5
+
+__device__ __forceinline__ uint32_t ix_reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
+    return 0;
+}
+
+struct ix_top2 { int64_t a, b; };        // the largest and the second largest position of a set (-1: none)
+struct ix_state { ix_top2 F, L; };       // of the `first` bins and of the `last` bins
+
+// the two largest of l and r, every position of r being above every position of l
+__device__ __forceinline__ ix_top2 ix_join(ix_top2 l, ix_top2 r)
+{
+    if (r.a < 0) return l;
+    ix_top2 o;
+    o.a = r.a;
+    o.b = r.b >= 0 ? r.b : l.a;
+    return o;
+}
+
+__device__ __forceinline__ ix_state ix_join(const ix_state &l, const ix_state &r)
+{
+    ix_state o;
+    o.F = ix_join(l.F, r.F);
+    o.L = ix_join(l.L, r.L);
+    return o;
+}
+
+__device__ __forceinline__ ix_state ix_none()
+{
+    ix_state o;
+    o.F.a = o.F.b = o.L.a = o.L.b = -1;
+    return o;
+}
+
+// 256 threads: the inclusive scan of v under ix_join, on top of `carry` (what lies in front of the workgroup's elements), which
+// becomes the state behind them (uniform)
+__device__ __forceinline__ ix_state ix_block_scan(ix_state v, ix_state &carry, ix_state *lds)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    ix_state x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        ix_state y;
+        y.F.a = (int64_t)__shfl_up((long long)x.F.a, o);
+        y.F.b = (int64_t)__shfl_up((long long)x.F.b, o);
+        y.L.a = (int64_t)__shfl_up((long long)x.L.a, o);
+        y.L.b = (int64_t)__shfl_up((long long)x.L.b, o);
+        if (lane >= o) x = ix_join(y, x);
+    }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    ix_state base = carry, tot = carry;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) base = ix_join(base, lds[w]);
+        tot = ix_join(tot, lds[w]);
+    }
+    __syncthreads();
+    carry = tot;
+    return ix_join(base, x);
+}
+
+// One pass over the tiles of the text chain, in three modes.  0: the state of every tile on its own (tilestate).  Between 0 and the
+// others ix_carry_kernel turns these into the state at every tile's end.  1: the chunks that start in every tile (tilechunks).
+// 2, with tilechunks scanned: the chunks and the windows.  A chunk starts at a line whose bin differs from the previous line's, or
+// that has no previous line in its record; it ends where the next chunk of its class begins (the text holds nothing but lines), the
+// last one of a class at the class's end (ix_ends_kernel).  Line i owns the windows w with previous line's end <= w << 14 < its
+// own end; the windows of a round's lines are numbered by a scan and dealt out to the lanes one by one, so a line that owns
+// thousands costs its lane what any other does.
+template <int MODE>
+__global__ void __launch_bounds__(256) ix_tile_kernel(const uint32_t *__restrict__ q, const tb_rec *__restrict__ recs,
+                                                      const int64_t *__restrict__ pref, const int64_t *__restrict__ wpref, tb_geom G,
+                                                      int64_t W, const uint64_t *__restrict__ tileoff, const uint64_t *__restrict__ bounds,
+                                                      ix_state *__restrict__ tilestate, uint64_t *__restrict__ tilechunks,
+                                                      const uint64_t *__restrict__ cbounds, dgrp_track_chunk *__restrict__ chunks,
+                                                      int64_t *__restrict__ linear)
+{
+    __shared__ uint64_t lds[4];
+    __shared__ ix_state slds[4];
+    __shared__ int64_t s_r0;
+    __shared__ int64_t w_off[MODE == 2 ? 256 : 1], w_base[MODE == 2 ? 256 : 1], w_val[MODE == 2 ? 256 : 1];
+    const int64_t tpc = G.NBpad / TRACK_TILE;
+    const int64_t k = blockIdx.x / tpc, ti = (int64_t)blockIdx.x % tpc, f0 = ti * TRACK_TILE;
+    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    __syncthreads();
+    const int64_t r0 = s_r0;
+    const uint32_t *qk = q + k * G.NBpad;
+    ix_state carry = ix_none();
+    if (MODE != 0 && ti > 0) carry = tilestate[blockIdx.x - 1];
+    int64_t at = 0;                                                        // offset in the class's slice of the text
+    uint64_t nchunk = 0, cfirst = 0, count = 0;
+    if (MODE == 2) {
+        at = (int64_t)(tileoff[blockIdx.x] - bounds[k]);
+        nchunk = tilechunks[blockIdx.x];
+        cfirst = cbounds[k];
+    }
+    for (int r = 0; r < TRACK_TILE / 256; ++r) {
+        const int64_t f = f0 + r * 256 + threadIdx.x;
+        const tb_part t = tb_part_of(qk, recs, pref, G, r0, f0, f);
+        ix_state v = ix_none();
+        if (t.p.first) v.F.a = f;
+        if (t.p.last) v.L.a = f;
+        const ix_state s = ix_block_scan(v, carry, slds);
+        if (MODE == 0) continue;
+        uint64_t round_bytes = 0;
+        int64_t ex = 0;
+        if (MODE == 2) ex = (int64_t)block_exclusive_scan((uint64_t)(t.p.head + t.p.tail), &round_bytes, lds);
+        bool cs = false;
+        uint32_t bn = 0;
+        int64_t rr = 0, beg = 0, wbase = 0, wc = 0;
+        if (t.p.last) {
+            rr = tb_record_from(pref, G.nrec, r0, f0, f);
+            const tb_rec R = recs[rr];
+            const track_geom g = tb_geom_of(R, G.bin);
+            const int64_t p0 = pref[rr], end = t.p.hi;
+            int64_t start, pstart, pend = 0, x;
+            track_bin_span(g, s.F.a - p0, start, x);                       // the line's first bin
+            bn = ix_reg2bin(start, end);
+            const bool prev = s.L.b >= p0;                                 // the previous `last` bin lies in this record
+            cs = true;
+            if (prev) {
+                track_bin_span(g, s.F.b - p0, pstart, x);
+                track_bin_span(g, s.L.b - p0, x, pend);
+                cs = ix_reg2bin(pstart, pend) != bn;
+            }
+            if (MODE == 2) {
+                const int64_t len = R.name_len + track_decimal_width((uint64_t)start) + track_decimal_width((uint64_t)end) + G.digits + 6;
+                beg = at + ex + t.p.head + t.p.tail - len;
+                const int64_t wl = prev ? (pend + (1 << IX_SHIFT) - 1) >> IX_SHIFT : 0;
+                wc = ((end - 1) >> IX_SHIFT) - wl + 1;
+                wbase = k * W + wpref[rr] + wl;
+            }
+        }
+        if (MODE == 1) {
+            count += cs ? 1 : 0;
+            continue;
+        }
+        uint64_t ctot, wtot;
+        const uint64_t cex = block_exclusive_scan(cs ? 1 : 0, &ctot, lds);
+        if (cs) {
+            const uint64_t c = nchunk + cex;
+            chunks[c].beg = beg;
+            chunks[c].rec = (int32_t)rr;
+            chunks[c].bin = bn;
+            if (c > cfirst) chunks[c - 1].end = beg;
+        }
+        nchunk += ctot;
+        const uint64_t wex = block_exclusive_scan((uint64_t)wc, &wtot, lds);
+        if (wtot > 0) {                                                    // (uniform)
+            w_off[threadIdx.x] = (int64_t)wex;
+            w_base[threadIdx.x] = wbase;
+            w_val[threadIdx.x] = beg;
+            __syncthreads();
+            for (int64_t i = threadIdx.x; i < (int64_t)wtot; i += 256) {
+                int lo = 0, hi = 256;                                      // w_off[lo] <= i < w_off[hi]: the last line at or below i owns it
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (w_off[mid] <= i) lo = mid; else hi = mid;
+                }
+                linear[w_base[lo] + (i - w_off[lo])] = w_val[lo];
+            }
+            __syncthreads();
+        }
+        at += (int64_t)round_bytes;
+    }
+    if (MODE == 0 && threadIdx.x == 0) tilestate[blockIdx.x] = carry;
+    if (MODE == 1) {
+        for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o);
+        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = count;
+        __syncthreads();
+        if (threadIdx.x == 0) tilechunks[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+    }
+}
+
+// the tiles' own states to the states at their ends, class by class: one workgroup per class
+__global__ void __launch_bounds__(256) ix_carry_kernel(ix_state *__restrict__ tilestate, int64_t tpc)
+{
+    __shared__ ix_state slds[4];
+    ix_state *ts = tilestate + (int64_t)blockIdx.x * tpc;
+    ix_state carry = ix_none();
+    for (int64_t base = 0; base < tpc; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        const ix_state s = ix_block_scan(i < tpc ? ts[i] : ix_none(), carry, slds);
+        if (i < tpc) ts[i] = s;
+    }
+}
+
+// the last chunk of every class ends where the class's text ends
+__global__ void __launch_bounds__(128) ix_ends_kernel(const uint64_t *__restrict__ cbounds, const uint64_t *__restrict__ bounds, int ncls,
+                                                     dgrp_track_chunk *__restrict__ chunks)
+{
+    const int k = threadIdx.x;
+    if (k < ncls && cbounds[k + 1] > cbounds[k]) chunks[cbounds[k + 1] - 1].end = (int64_t)(bounds[k + 1] - bounds[k]);
+}
+
+// the index entry's workspace: the text chain's, then its own parts
+struct ix_layout { tb_layout t; int64_t wpref, state, tilechunks, cgrand, cbounds, bytes; };
+
+static bool ix_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes,
+                     ix_layout *l)
+{
+    if (!tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l->t) || nrec >= (1ll << 31)) return false;
+    for (int64_t r = 0; r < nrec; ++r)
+        if (h_startpos[r] + h_n[r] > IX_MAX_END) return false;
+    const int64_t ntiles = l->t.NBpad / TRACK_TILE * ncls;
+    int64_t p = l->t.bytes;
+    l->wpref = p;
+    p += dgrp_align_up((nrec + 1) * 8, 256);
+    l->state = p;
+    p += dgrp_align_up(ntiles * (int64_t)sizeof(ix_state), 256);
+    l->tilechunks = p;
+    p += dgrp_align_up(ntiles * 8, 256);
+    l->cgrand = p;
+    p += 256;
+    l->cbounds = p;
+    p += dgrp_align_up((int64_t)(ncls + 1) * 8, 256);
+    l->bytes = p;
+    return true;
 }
 
 }   // namespace
@@ -505,4 +766,95 @@ DGRP_EXPORT int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec,
     }
     return tb_run(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, d_text, cap, h_class_off, d_work,
                   l, (hipStream_t)stream_);
+}
+
+DGRP_EXPORT int64_t dgrp_track_index_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                                     int64_t names_bytes)
+{
+    ix_layout l;
+    return ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                       const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls,
+                                       int ncls, int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap,
+                                       int64_t *h_chunk_off, int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes,
+                                       void *stream_)
+{
+    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC, "dgrp_track_index_batch: bad C %d", C);
+    DGRP_REQUIRE(ncls >= 1 && ncls <= C, "dgrp_track_index_batch: ncls must lie in 1..C (%d, C = %d)", ncls, C);
+    DGRP_REQUIRE(h_chunk_off && h_cls, "dgrp_track_index_batch: NULL h_chunk_off or h_cls");
+    for (int k = 0; k <= ncls; ++k) h_chunk_off[k] = 0;
+    DGRP_REQUIRE(nrec >= 0 && nrec < (1ll << 31), "dgrp_track_index_batch: bad nrec %lld", (long long)nrec);
+    for (int k = 0; k < ncls; ++k)
+        DGRP_REQUIRE(h_cls[k] >= 0 && h_cls[k] < C, "dgrp_track_index_batch: class %d is not in 0..%d", h_cls[k], C - 1);
+    DGRP_REQUIRE(digits >= 1 && digits <= 4, "dgrp_track_index_batch: digits must lie in 1..4, got %d", digits);
+    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: bad bin %lld", (long long)bin);
+    DGRP_REQUIRE(chunk_cap >= 0 && linear_cap >= 0, "dgrp_track_index_batch: bad chunk_cap/linear_cap (%lld, %lld)", (long long)chunk_cap,
+                 (long long)linear_cap);
+    if (nrec == 0) return DGRP_OK;
+    DGRP_REQUIRE(h_row0 && h_n && h_startpos && h_name_off, "dgrp_track_index_batch: NULL host table");
+    DGRP_REQUIRE(h_name_off[0] >= 0, "dgrp_track_index_batch: record 0: bad name offset %lld", (long long)h_name_off[0]);
+    std::vector<int64_t> wpref((size_t)nrec + 1, 0);                       // windows in front of every record
+    for (int64_t r = 0; r < nrec; ++r) {
+        DGRP_REQUIRE(h_n[r] >= 1 && h_n[r] <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: record %lld: bad n %lld", (long long)r,
+                     (long long)h_n[r]);
+        DGRP_REQUIRE(h_startpos[r] >= 0 && h_startpos[r] <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: record %lld: bad offset %lld",
+                     (long long)r, (long long)h_startpos[r]);
+        DGRP_REQUIRE(h_startpos[r] + h_n[r] <= IX_MAX_END,
+                     "dgrp_track_index_batch: record %lld ends at %lld, above 2^29 = 536870912, the largest coordinate of a tabix index",
+                     (long long)r, (long long)(h_startpos[r] + h_n[r]));
+        DGRP_REQUIRE(h_row0[r] >= 0, "dgrp_track_index_batch: record %lld: bad first row %lld", (long long)r, (long long)h_row0[r]);
+        DGRP_REQUIRE(h_name_off[r + 1] >= h_name_off[r], "dgrp_track_index_batch: record %lld: descending name offsets (%lld, %lld)",
+                     (long long)r, (long long)h_name_off[r], (long long)h_name_off[r + 1]);
+        wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_startpos[r] + h_n[r] - 1) >> IX_SHIFT) + 1;
+    }
+    const int64_t names_bytes = h_name_off[nrec], W = wpref[(size_t)nrec];
+    DGRP_REQUIRE(linear_cap >= W * ncls, "dgrp_track_index_batch: linear_cap %lld < %lld windows of %d classes", (long long)linear_cap,
+                 (long long)(W * ncls), ncls);
+    DGRP_REQUIRE((names || names_bytes == 0) && (d_chunks || chunk_cap == 0) && d_linear && d_probs && d_work,
+                 "dgrp_track_index_batch: NULL pointer");
+    ix_layout l;
+    DGRP_REQUIRE(ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l), "dgrp_track_index_batch: too many bins in one call");
+    if (work_bytes < l.bytes) {
+        dgrp_set_error("dgrp_track_index_batch: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
+        return DGRP_ENOMEM;
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    char *w = (char *)d_work;
+    int64_t *d_wpref = (int64_t *)(w + l.wpref);
+    ix_state *state = (ix_state *)(w + l.state);
+    uint64_t *tilechunks = (uint64_t *)(w + l.tilechunks), *cgrand = (uint64_t *)(w + l.cgrand), *cbounds = (uint64_t *)(w + l.cbounds);
+    DGRP_HIP(hipMemcpyAsync(d_wpref, wpref.data(), wpref.size() * 8, hipMemcpyHostToDevice, stream));
+    tb_dev D;
+    std::vector<int64_t> text_off((size_t)ncls + 1, 0);
+    const int rc = tb_front(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, text_off.data(), d_work,
+                            l.t, stream, &D);
+    if (rc != DGRP_OK) return rc;
+    const dim3 grid((unsigned)D.ntiles), block(256);
+    hipLaunchKernelGGL(ix_tile_kernel<0>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
+                       cbounds, d_chunks, d_linear);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ix_carry_kernel, dim3((unsigned)ncls), block, 0, stream, state, D.tpc);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ix_tile_kernel<1>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
+                       cbounds, d_chunks, d_linear);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), block, 0, stream, tilechunks, D.ntiles, cgrand);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tb_bounds_kernel, dim3(1), dim3(128), 0, stream, tilechunks, D.tpc, ncls, cgrand, cbounds);
+    DGRP_LAUNCH_CHECK();
+    std::vector<uint64_t> off((size_t)ncls + 1, 0);
+    DGRP_HIP(hipMemcpyAsync(off.data(), cbounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    for (int k = 0; k <= ncls; ++k) h_chunk_off[k] = (int64_t)off[(size_t)k];
+    if (h_chunk_off[ncls] > chunk_cap) return DGRP_OK;                      // (too small: the caller retries with room for all of them)
+    DGRP_HIP(hipMemsetAsync(d_linear, 0xff, (size_t)(W * ncls) * 8, stream));          // -1: no line ends behind this window
+    hipLaunchKernelGGL(ix_tile_kernel<2>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
+                       cbounds, d_chunks, d_linear);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ix_ends_kernel, dim3(1), dim3(128), 0, stream, cbounds, D.bounds, ncls, d_chunks);
+    DGRP_LAUNCH_CHECK();
+    DGRP_HIP(hipStreamSynchronize(stream));
+    return DGRP_OK;
 }

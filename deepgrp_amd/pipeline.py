@@ -558,11 +558,59 @@ class ContigPipeline:
             cap = int(off[ncls])                            # more text than guessed: run again with room for all of it
         return text[:int(off[ncls])], off
 
+    def track_index_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, names, classes, digits: int = 2,
+                                 bin: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The tabix index of the text track_text_batch_device gives for the same arguments, in text offsets (one
+        dgrp_track_index_batch call, read back once): -> (chunks, chunk_off [len(classes) + 1], linear [len(classes), W], wpref
+        [records + 1]).  chunks (tabix.CHUNK_DTYPE) is class-major, class classes[k] at [chunk_off[k], chunk_off[k + 1]), offsets
+        inside that class's slice of the text; record r of class k has its windows at linear[k, wpref[r]:wpref[r + 1]], -1 where
+        none of its lines ends behind the window.  A record that ends above 2^29 raises tabix.IndexRefused."""
+        from .tabix import CHUNK_DTYPE, MAX_END, MIN_SHIFT, IndexRefused
+        L = lib()
+        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
+            raise ValueError("track_index_batch_device takes a contiguous float32 [rows, C] array")
+        c = int(d_probs.shape[1])
+        nrec, ncls = len(lengths), len(classes)
+        dev = d_probs.device
+        r0 = np.ascontiguousarray(row0, np.int64)
+        ln = np.ascontiguousarray(lengths, np.int64)
+        sp = np.ascontiguousarray(startposes, np.int64)
+        cl = np.ascontiguousarray(classes, np.int32)
+        over = np.flatnonzero(sp + ln > MAX_END)
+        if over.size:
+            raise IndexRefused(f"record {int(over[0])} ends at {int((sp + ln)[over[0]])}, above 2^29, the largest coordinate of a tabix index")
+        raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+        noff = np.zeros(nrec + 1, np.int64)
+        np.cumsum([len(x) for x in raw], out=noff[1:])
+        blob = b"".join(raw)
+        wpref = np.zeros(nrec + 1, np.int64)
+        np.cumsum(((sp + ln - 1) >> MIN_SHIFT) + 1, out=wpref[1:])
+        nwin = int(wpref[-1])
+        wb = L.dgrp_track_index_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
+        if wb <= 0:
+            raise ValueError(f"track_index_batch_device: bad record lengths, start positions, bin {bin} or class count {ncls}")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        linear = torch.empty(max(ncls * nwin, 1), dtype=torch.int64, device=dev)
+        cap = ncls * (2 * nwin + 4 * nrec + 16)             # (a leaf chunk per window, one per line across a window edge, a few per
+                                                            # record: 1.2 per window on a 250 Mbp record; the guess fits most runs)
+        off = np.zeros(ncls + 1, np.int64)
+        while True:
+            chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_track_index_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob, noff.ctypes.data,
+                                           cl.ctypes.data, ncls, int(digits), int(bin), _ptr(chunks), cap, off.ctypes.data, _ptr(linear),
+                                           ncls * nwin, _ptr(work), wb, stream_ptr()), "dgrp_track_index_batch")
+            if int(off[ncls]) <= cap:
+                break
+            cap = int(off[ncls])                            # more chunks than guessed: run again with room for all of them
+        host = chunks[:int(off[ncls]) * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
+        return host, off, linear[:ncls * nwin].cpu().numpy().reshape(ncls, nwin), wpref
+
     def run_batch_tracked(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, names, spec):
         """run_batch with probability tracks: one dgrp_predict_batch_probs call, then one dgrp_track_text_batch call on its merged
         probabilities.  -> (rows, texts), texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
         give one after the other); with spec.gzip_level the BGZF members of that slice instead (no EOF member), deflated on the
-        device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member."""
+        device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member; with spec.index the batch's
+        tracks.WriteIndex comes with them (texts.index)."""
         L = lib()
         nrec = len(lengths)
         if nrec == 0:
@@ -574,13 +622,18 @@ class ContigPipeline:
         row0 = np.zeros(nrec, np.int64)
         np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
         d_text, off = self.track_text_batch_device(d_probs, row0, ln, startposes, names, spec.classes, spec.digits, spec.bin)
+        index = None
+        if spec.gzip_level is not None and spec.index:
+            from .tracks import write_index
+            index = write_index(self, d_probs, row0, ln, startposes, names, spec)
         del d_probs
         if spec.gzip_level is None:
             host = d_text.cpu().numpy()
             return rows, [host[off[k]:off[k + 1]].tobytes() for k in range(len(spec.classes))]
         from . import gz
-        from .tracks import GZIP_PIECE
-        texts = []
+        from .tracks import GZIP_PIECE, TrackTexts
+        texts = TrackTexts()
+        texts.index = index
         for k in range(len(spec.classes)):
             pieces = [gz.bgzf_compress_device(d_text[o:min(o + GZIP_PIECE, int(off[k + 1]))], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
                       for o in range(int(off[k]), int(off[k + 1]), GZIP_PIECE)]

@@ -1,0 +1,266 @@
+"""The tabix index (`.tbi`) of a BGZF bedGraph track (`predict --track_dir --track_gzip --track_index`), stated in numpy/Python.
+
+`reference_index` computes the index's payload from a finished `.gz` file alone and is the statement every other path is held to;
+`IndexBuilder` puts the same payload together from what the track writer knows (chunks and linear index in text offsets from
+dgrp_track_index_batch, the compressed size of every member written); `read_index` and `query` are a small reader that works as
+tabix does.  The `.tbi` file is the payload as BGZF (`index_file`).
+
+The format.  Bins are the standard scheme with min_shift 14 and depth 5 (`reg2bin`), so coordinates end at or below 2^29.  The
+virtual offset of text byte u is (file offset of the BGZF member that holds u) << 16 | (offset of u inside that member); for u = the
+text's length it is (offset of the EOF member) << 16, so the end of a line is always the virtual offset of the byte behind it.
+Reference sequences are the distinct names in order of first appearance.  A chunk (the rule of htslib's hts_idx_push) is a maximal
+run of consecutive lines with the same name and the same bin, from its first line's begin to its last line's end; there is no
+further merging and no pseudo-bin 37450.  The linear index of a sequence has n_intv = ((end of its last line - 1) >> 14) + 1 entries,
+ioff[w] = the begin of its first line whose end is greater than w << 14.  Bytes: `TBI\\1`, n_ref, format 0x10000 (generic, zero-based
+half-open: htslib's `bed` preset), col_seq 1, col_beg 2, col_end 3, meta `#`, skip 0, l_nm, the names with a NUL each; per sequence
+n_bin, the bins in ascending number (bin, n_chunk, (beg, end)... in file order), n_intv, ioff...; n_no_coor = 0 as uint64."""
+from __future__ import annotations
+
+import struct
+import zlib
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+
+MIN_SHIFT = 14
+MAX_END = 1 << 29
+FORMAT_BED = 0x10000
+_LEVELS = ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1))
+BLOCK = 0xff00                                      # text bytes per member of a write (gz.BGZF_BLOCK)
+
+CHUNK_DTYPE = np.dtype([("beg", "<i8"), ("end", "<i8"), ("rec", "<i4"), ("bin", "<u4")])     # struct dgrp_track_chunk
+
+
+class IndexRefused(ValueError):
+    """The file has no tabix index: coordinates above 2^29, a name that reappears after another name, an empty name."""
+
+
+def reg2bin(beg: int, end: int) -> int:
+    """The bin of [beg, end) (end exclusive, 0 <= beg < end <= 2^29)."""
+    if not 0 <= beg < end <= MAX_END:
+        raise IndexRefused(f"[{beg}, {end}) is not a span inside [0, 2^29]")
+    end -= 1
+    for shift, first in _LEVELS:
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def reg2bins(beg: int, end: int) -> List[int]:
+    """Every bin that can hold a line overlapping [beg, end)."""
+    end = min(end, MAX_END) - 1
+    out = [0]
+    for shift, first in reversed(_LEVELS):
+        out.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
+    return out
+
+
+def payload(names: Sequence[bytes], bins: Sequence[Dict[int, List[Tuple[int, int]]]], linear: Sequence[Sequence[int]]) -> bytes:
+    """The index's bytes from its parts: per sequence its name, bin -> [(beg, end), ...] in file order, and ioff."""
+    blob = b"".join(nm + b"\0" for nm in names)
+    out = [b"TBI\1", struct.pack("<8i", len(names), FORMAT_BED, 1, 2, 3, ord("#"), 0, len(blob)), blob]
+    for b, lin in zip(bins, linear):
+        out.append(struct.pack("<i", len(b)))
+        for k in sorted(b):
+            out.append(struct.pack("<Ii", k, len(b[k])))
+            out.append(np.asarray(b[k], "<u8").tobytes())
+        out.append(struct.pack("<i", len(lin)))
+        out.append(np.asarray(lin, "<u8").tobytes())
+    out.append(struct.pack("<Q", 0))
+    return b"".join(out)
+
+
+def index_file(pl: bytes) -> bytes:
+    """The `.tbi` file of a payload: BGZF from the host, EOF member included."""
+    from .gz import bgzf_compress
+    return bgzf_compress(pl)
+
+
+def _member_size(gz_bytes, off: int) -> int:
+    if gz_bytes[off:off + 4] != b"\x1f\x8b\x08\x04" or gz_bytes[off + 12:off + 16] != b"BC\x02\x00":
+        raise ValueError(f"no BGZF member at byte {off}")
+    return struct.unpack_from("<H", gz_bytes, off + 16)[0] + 1
+
+
+def _inflate_member(gz_bytes, off: int) -> Tuple[bytes, int]:
+    size = _member_size(gz_bytes, off)
+    return zlib.decompress(bytes(gz_bytes[off:off + size]), 31), size
+
+
+def reference_index(gz_bytes: bytes) -> bytes:
+    """The payload of the index of the BGZF bedGraph file `gz_bytes`, from the file alone: a walk over its members, zlib, the lines."""
+    starts, tstarts, parts = [], [], []
+    off = total = 0
+    while off < len(gz_bytes):
+        text, size = _inflate_member(gz_bytes, off)
+        starts.append(off)
+        tstarts.append(total)
+        parts.append(text)
+        total += len(text)
+        off += size
+    text = b"".join(parts)
+    tstarts = np.asarray(tstarts, np.int64)
+
+    def voff(u: int) -> int:
+        m = int(np.searchsorted(tstarts, u, "right")) - 1               # the last member that starts at or in front of u
+        return starts[m] << 16 | (u - int(tstarts[m]))
+
+    names: List[bytes] = []
+    bins: List[Dict[int, List[Tuple[int, int]]]] = []
+    linear: List[List[int]] = []
+    last_end: List[int] = []
+    run = None                                                          # the open chunk: [sequence, bin, begin, end] in text offsets
+    u = 0
+    lines = text.split(b"\n")
+    if not lines[-1]:
+        lines.pop()
+    for line in lines:
+        v = u + len(line) + 1
+        f = line.split(b"\t")
+        name, beg, end = f[0], int(f[1]), int(f[2])
+        if not name:
+            raise IndexRefused("a line with an empty name")
+        if not names or names[-1] != name:
+            if name in names:
+                raise IndexRefused(f"the name {name!r} reappears after another name")
+            names.append(name)
+            bins.append({})
+            linear.append([])
+            last_end.append(0)
+        s = len(names) - 1
+        b = reg2bin(beg, end)
+        if run is not None and run[0] == s and run[1] == b:
+            run[3] = v
+        else:
+            if run is not None:
+                bins[run[0]].setdefault(run[1], []).append((voff(run[2]), voff(run[3])))
+            run = [s, b, u, v]
+        lin = linear[s]
+        if (end - 1) >> MIN_SHIFT >= len(lin):                          # the first line whose end is greater than w << 14
+            lin.extend([voff(u)] * (((end - 1) >> MIN_SHIFT) + 1 - len(lin)))
+        last_end[s] = end
+        u = v
+    if run is not None:
+        bins[run[0]].setdefault(run[1], []).append((voff(run[2]), voff(run[3])))
+    linear = [lin[:((e - 1) >> MIN_SHIFT) + 1] for lin, e in zip(linear, last_end)]
+    return payload(names, bins, linear)
+
+
+def read_index(pl: bytes) -> dict:
+    """The payload's parts: {"names": [...], "bins": [{bin: [(beg, end), ...]}, ...], "linear": [uint64 array, ...]}."""
+    if pl[:4] != b"TBI\1":
+        raise ValueError("not a tabix index")
+    n_ref, fmt, col_seq, col_beg, col_end, meta, skip, l_nm = struct.unpack_from("<8i", pl, 4)
+    if (fmt, col_seq, col_beg, col_end) != (FORMAT_BED, 1, 2, 3):
+        raise ValueError("not an index of the bed preset")
+    p = 36
+    names = pl[p:p + l_nm].split(b"\0")[:-1]
+    p += l_nm
+    bins, linear = [], []
+    for _ in range(n_ref):
+        n_bin, = struct.unpack_from("<i", pl, p)
+        p += 4
+        b = {}
+        for _k in range(n_bin):
+            k, n_chunk = struct.unpack_from("<Ii", pl, p)
+            p += 8
+            c = np.frombuffer(pl, "<u8", 2 * n_chunk, p).reshape(-1, 2)
+            p += 16 * n_chunk
+            b[k] = [(int(x), int(y)) for x, y in c]
+        n_intv, = struct.unpack_from("<i", pl, p)
+        p += 4
+        linear.append(np.frombuffer(pl, "<u8", n_intv, p))
+        p += 8 * n_intv
+        bins.append(b)
+    if len(names) != n_ref or p + 8 > len(pl):
+        raise ValueError("truncated tabix index")
+    return {"names": names, "bins": bins, "linear": linear}
+
+
+def query(index: dict, gz_bytes: bytes, name: bytes, beg: int, end: int) -> List[bytes]:
+    """The lines of sequence `name` that overlap [beg, end), in file order, as tabix finds them: the bins of the region, their
+    chunks that end above ioff[beg >> 14], only the members those chunks touch, and an overlap filter on the lines."""
+    if name not in index["names"] or beg >= end:
+        return []
+    s = index["names"].index(name)
+    lin = index["linear"][s]
+    w = beg >> MIN_SHIFT
+    min_off = int(lin[w]) if w < len(lin) else (int(lin[-1]) if len(lin) else 0)
+    chunks = sorted(c for b in reg2bins(beg, end) for c in index["bins"][s].get(b, ()) if c[1] > min_off)
+    out = []
+    for cb, ce in chunks:
+        off, parts = cb >> 16, []
+        while off < ce >> 16 or (off == ce >> 16 and ce & 0xffff):
+            text, size = _inflate_member(gz_bytes, off)
+            parts.append(text if off < ce >> 16 else text[:ce & 0xffff])
+            off += size
+        for line in b"".join(parts)[cb & 0xffff:].split(b"\n")[:-1]:
+            f = line.split(b"\t")
+            if f[0] == name and int(f[1]) < end and int(f[2]) > beg:
+                out.append(line)
+    return out
+
+
+def member_sizes(members: bytes) -> Tuple[np.ndarray, int]:
+    """(the compressed size of every BGZF member of `members`, the text bytes they hold), from their BSIZE and ISIZE fields."""
+    out, off, text_len = [], 0, 0
+    while off < len(members):
+        out.append(_member_size(members, off))
+        off += out[-1]
+        text_len += struct.unpack_from("<I", members, off - 4)[0]
+    return np.asarray(out, np.int64), text_len
+
+
+class IndexBuilder:
+    """The index of one track file from its writes.  A write is the BGZF members of one text (one record, or one class of a batch)
+    appended at a file offset; every write starts a member and its members hold BLOCK text bytes each but the last, so text offset u
+    of a write lies in member u // BLOCK of it."""
+
+    def __init__(self):
+        self.names: List[bytes] = []
+        self.bins: List[Dict[int, List[List[int]]]] = []
+        self.linear: List[np.ndarray] = []
+        self.n_intv: List[int] = []
+        self.last_bin = -1                                              # the bin of the last chunk of the last sequence
+
+    def add(self, file_off: int, sizes: np.ndarray, text_len: int, rec_names: Sequence[bytes], chunks: np.ndarray, linear: np.ndarray,
+            wpref: np.ndarray) -> None:
+        """One write of `text_len` text bytes in members of `sizes` compressed bytes at `file_off`: its chunks (CHUNK_DTYPE, text
+        offsets, `rec` an index into rec_names) and its linear index (record r at linear[wpref[r]:wpref[r + 1]], -1: no line)."""
+        mstart = np.zeros(len(sizes) + 1, np.int64)
+        np.cumsum(sizes, out=mstart[1:])
+        if len(sizes) != (text_len + BLOCK - 1) // BLOCK:
+            raise ValueError(f"{len(sizes)} members for {text_len} bytes of text")
+
+        def voff(u):
+            u = np.asarray(u, np.int64)
+            m = u // BLOCK
+            v = (file_off + mstart[np.minimum(m, len(sizes))]) << 16 | (u - m * BLOCK)
+            return np.where(u >= text_len, (file_off + int(mstart[-1])) << 16, v)
+
+        cb, ce = voff(chunks["beg"]).tolist(), voff(chunks["end"]).tolist()
+        for rec, b, vb, ve in zip(chunks["rec"].tolist(), chunks["bin"].tolist(), cb, ce):
+            name = rec_names[rec]
+            if not self.names or self.names[-1] != name:
+                if name in self.names or not name:
+                    raise IndexRefused(f"the name {name!r} reappears after another name" if name else "an empty name")
+                self.names.append(name)
+                self.bins.append({})
+                self.linear.append(np.zeros(0, np.int64))
+                self.n_intv.append(0)
+                self.last_bin = -1
+            if b == self.last_bin:                                      # consecutive records of one name: the run goes on
+                self.bins[-1][b][-1][1] = ve
+            else:
+                self.bins[-1].setdefault(b, []).append([vb, ve])
+                self.last_bin = b
+        for r in np.unique(chunks["rec"]).tolist():                     # the records with a line, in order
+            lin = linear[wpref[r]:wpref[r + 1]]
+            lin = voff(lin[:int(np.flatnonzero(lin >= 0)[-1]) + 1])
+            s = self.names.index(rec_names[r])
+            have = self.linear[s]                                       # an earlier record's line comes first in the file
+            self.linear[s] = np.concatenate([have, lin[len(have):]])
+            self.n_intv[s] = len(lin)                                   # ... but the sequence ends with its last line
+
+    def payload(self) -> bytes:
+        return payload(self.names, self.bins, [lin[:n] for lin, n in zip(self.linear, self.n_intv)])

@@ -12,15 +12,22 @@ and classes of the batch); the text of a batch is the records' texts one after t
 With `--track_gzip` the files are `<basename>.class<c>.bedGraph.gz`, BGZF as bgzip writes it: the text of a record (of a batch: of one
 class of all its records) is deflated on the device where it was written (gz.bgzf_compress_device, --gzip_level, 1 unless given) and
 only the members are read back and appended; a record or batch boundary is a short member, and the EOF member is written once, when
-the file is committed."""
+the file is committed.
+
+With `--track_index` every `.gz` gets its tabix index `<track>.gz.tbi` (tabix.py states the format): chunks and linear index come
+from the device in text offsets (dgrp_track_index_batch, for the arguments of the text), `TrackFiles` turns them into virtual
+offsets with the compressed size of every member it appends, and `commit` writes the index."""
 from __future__ import annotations
 
+import logging
 import os
 import sys
 import tempfile
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
+
+_LOG = logging.getLogger(__name__)
 
 
 class TrackSpec(NamedTuple):
@@ -29,6 +36,7 @@ class TrackSpec(NamedTuple):
     digits: int = 2
     bin: int = 1
     gzip_level: Optional[int] = None                # None: plain text; else BGZF members at this level
+    index: bool = False                             # --track_index: a tabix index beside every BGZF track
 
 
 class TrackPlan(NamedTuple):
@@ -38,6 +46,7 @@ class TrackPlan(NamedTuple):
     bin: int
     bases: dict                                     # input file -> basename of its track files
     gzip_level: Optional[int] = None                # --track_gzip: the level (None: plain bedGraph)
+    index: bool = False                             # --track_index
 
 
 def input_basename(filename: str) -> str:
@@ -63,9 +72,11 @@ def gzip_level(args, default: int) -> Optional[int]:
 
 
 def check_gzip_flags(args) -> None:
-    """The refusals of --track_gzip and --gzip_level that need nothing but the flags (sys.exit)."""
+    """The refusals of --track_gzip, --track_index and --gzip_level that need nothing but the flags (sys.exit)."""
     if getattr(args, "track_gzip", False) and getattr(args, "track_dir", None) is None:
         sys.exit("--track_gzip needs --track_dir")
+    if getattr(args, "track_index", False) and not getattr(args, "track_gzip", False):
+        sys.exit("--track_index needs --track_gzip (a tabix index belongs to a BGZF file)")
     if getattr(args, "gzip_level", None) is not None:
         if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False)):
             sys.exit("--gzip_level needs --mask_gzip or --track_gzip")
@@ -98,7 +109,8 @@ def plan(args) -> Optional[TrackPlan]:
         seen[base] = f
         bases[f] = base
     level = gzip_level(args, 1) if getattr(args, "track_gzip", False) else None
-    return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases, level)
+    return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases, level,
+                     bool(getattr(args, "track_index", False)))
 
 
 def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
@@ -107,34 +119,73 @@ def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
     bad = [c for c in classes if not 0 <= c < nclasses]
     if bad:
         sys.exit(f"--track_classes: label {bad[0]} is not a class of this model (labels 0..{nclasses - 1})")
-    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level)
+    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index)
+
+
+class WriteIndex(NamedTuple):
+    """What one write (a record, or a batch) adds to the indexes of its input: the records' names and, in offsets of every class's
+    text, ContigPipeline.track_index_batch_device's arrays -- or why this input cannot have an index."""
+    names: List[bytes]
+    refused: Optional[str] = None
+    chunks: Optional[np.ndarray] = None
+    chunk_off: Optional[np.ndarray] = None
+    linear: Optional[np.ndarray] = None
+    wpref: Optional[np.ndarray] = None
+
+
+class TrackTexts(list):
+    """The texts (or BGZF members) of one write, class by class; with --track_index `index` is its WriteIndex."""
+    index: Optional[WriteIndex] = None
+
+
+def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec) -> WriteIndex:
+    """The WriteIndex of the records whose text track_text_batch_device gives for the same arguments."""
+    from .tabix import MAX_END
+    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+    for nm, sp, n in zip(raw, startposes, lengths):
+        if int(sp) + int(n) > MAX_END:
+            return WriteIndex(raw, f"record {nm.decode('utf-8', 'replace')!r} ends at {int(sp) + int(n)}, above 2^29 = {MAX_END}, the "
+                                   "largest coordinate of a tabix index")
+    return WriteIndex(raw, None, *pipe.track_index_batch_device(d_probs, row0, lengths, startposes, raw, spec.classes, spec.digits, spec.bin))
 
 
 def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec) -> List[bytes]:
     """The track text of every class of `spec` for one record (merged: ContigPipeline.merged of it); with spec.gzip_level its BGZF
-    members instead (no EOF member), deflated on the device piece by piece."""
+    members instead (no EOF member), deflated on the device piece by piece; with spec.index a TrackTexts with the record's index."""
     if spec.gzip_level is None:
         return [pipe.track_text(merged, startpos, name, c, spec.digits, spec.bin) for c in spec.classes]
     from . import gz
-    out = []
+    out = TrackTexts()
     for c in spec.classes:
         d_text = pipe.track_text_device(merged, startpos, name, c, spec.digits, spec.bin)
         pieces = [gz.bgzf_compress_device(d_text[o:o + GZIP_PIECE], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
                   for o in range(0, int(d_text.numel()), GZIP_PIECE)]
         out.append(b"".join(pieces))
         del d_text
+    if spec.index and len(merged):
+        out.index = write_index(pipe, merged, [0], [len(merged)], [startpos], [name], spec)
     return out
 
 
 class TrackFiles:
     """The track files of one input, written to temporary files in the directory and renamed by `commit` (`abort` removes them).
-    With spec.gzip_level `write` takes BGZF members and `commit` puts the EOF member behind them."""
+    With spec.gzip_level `write` takes BGZF members and `commit` puts the EOF member behind them.  With spec.index it keeps, per
+    class, the file offset of every write and a tabix.IndexBuilder, and `commit` writes `<track>.gz.tbi` the same way.  An input
+    whose records cannot be indexed (WriteIndex.refused, a name that reappears after another name, an empty name) gets one warning
+    and no index; its tracks are what they are without the flag."""
 
     def __init__(self, p: TrackPlan, spec: TrackSpec, filename: str):
         os.makedirs(p.directory, exist_ok=True)
         self.gzip = spec.gzip_level is not None
         self.final = [track_path(p.directory, p.bases[filename], c, self.gzip) for c in spec.classes]
         self.tmp, self.fh = [], []
+        self.filename, self.builders = filename, None
+        if self.gzip and spec.index:
+            from .tabix import IndexBuilder
+            self.builders = [IndexBuilder() for _ in spec.classes]
+            self.offs = [0] * len(spec.classes)
+            self.seen, self.last = set(), None
+        self.index_wanted = self.builders is not None
         try:
             for path in self.final:
                 fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=p.directory)
@@ -144,10 +195,45 @@ class TrackFiles:
             self.abort()
             raise
 
+    def _no_index(self, why: str) -> None:
+        if self.builders is not None:
+            _LOG.warning("%s: no tabix index is written (--track_index): %s", self.filename, why)
+            self.builders = None
+
+    def _index(self, texts: Sequence[bytes]) -> None:
+        """The write's part of every class's index; the members of class k go to file offset self.offs[k]."""
+        from .tabix import IndexRefused, member_sizes
+        ix = getattr(texts, "index", None)
+        if ix is None:
+            if any(texts):
+                self._no_index("a write came without its index")
+            return
+        for nm in ix.names:
+            if not nm:
+                return self._no_index("a record with an empty name")
+            if nm != self.last:
+                if nm in self.seen:
+                    return self._no_index(f"the record name {nm.decode('utf-8', 'replace')!r} reappears after another name")
+                self.seen.add(nm)
+                self.last = nm
+        if ix.refused is not None:
+            return self._no_index(ix.refused)
+        for k, t in enumerate(texts):
+            if t:
+                sizes, text_len = member_sizes(t)
+                try:
+                    self.builders[k].add(self.offs[k], sizes, text_len, ix.names, ix.chunks[ix.chunk_off[k]:ix.chunk_off[k + 1]],
+                                         ix.linear[k], ix.wpref)
+                except IndexRefused as e:
+                    return self._no_index(str(e))
+                self.offs[k] += len(t)
+
     def write(self, texts: Sequence[bytes]) -> None:
         for fh, t in zip(self.fh, texts):
             if t:
                 fh.write(t)
+        if self.builders is not None:
+            self._index(texts)
 
     def commit(self) -> None:
         for fh in self.fh:
@@ -155,9 +241,27 @@ class TrackFiles:
                 from .gz import BGZF_EOF
                 fh.write(BGZF_EOF)
             fh.close()
+        if self.index_wanted:
+            self._commit_index()
         for tmp, path in zip(self.tmp, self.final):
             os.replace(tmp, path)
         self.tmp = []
+
+    def _commit_index(self) -> None:
+        """`<track>.gz.tbi` of every class through a temporary file; without an index, one left by an earlier run goes."""
+        from .tabix import index_file
+        tbi = [path + ".tbi" for path in self.final]
+        if self.builders is None:
+            for path in tbi:
+                if os.path.exists(path):
+                    os.remove(path)
+            return
+        for b, path in zip(self.builders, tbi):
+            fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(path))
+            self.tmp.append(tmp)
+            self.final.append(path)
+            with os.fdopen(fd, "wb") as fh:
+                fh.write(index_file(b.payload()))
 
     def abort(self) -> None:
         for fh in self.fh:

@@ -322,6 +322,30 @@ int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec, const int64
                           int digits, int64_t bin, char *d_text, int64_t cap, int64_t *h_class_off, void *d_work,
                           int64_t work_bytes, void *stream);
 
+/* The tabix index of that text (predict --track_index), in offsets of the text: for the same arguments as dgrp_track_text_batch, the
+ * chunks and the 16 kb linear index of every class's slice, from the same bin, count and scan passes and kernels of its own that
+ * follow them; the text itself is not written.  A chunk (the rule of htslib's hts_idx_push) is a maximal run of consecutive lines
+ * of ONE record with the same bin reg2bin(start, end) of the standard scheme (min_shift 14, depth 5); it never spans two records,
+ * even when they share a name.  beg and end are byte offsets inside the class's slice of the text (slice k is d_text[h_class_off[k]
+ * : h_class_off[k + 1]] of the text entry): the first byte of its first line and the byte behind its last line.  Chunks are
+ * class-major, in the order of the text: those of class h_cls[k] are d_chunks[h_chunk_off[k] : h_chunk_off[k + 1]].  h_chunk_off
+ * (host, ncls + 1 entries) is always filled in full, also when h_chunk_off[ncls] > chunk_cap: then nothing is written, d_linear
+ * included, and the caller retries with more room.  d_linear is laid out [class k][record r][window w], w = 0 ..
+ * (h_startpos[r] + h_n[r] - 1) >> 14 inclusive, so record r of class k starts at k * W + (windows of the records in front of r), W
+ * the windows of all records; linear_cap (in elements) must be at least ncls * W.  A value is the slice offset of the first byte of
+ * the record's first line whose end is greater than w << 14, or -1 where the record has no such line.  A record that ends above
+ * 2^29 (h_startpos[r] + h_n[r] > 536870912, the largest coordinate of a tabix index) is refused with DGRP_EINVAL before any launch;
+ * the other limits and refusals are the text entry's.  Workspace dgrp_track_index_workspace_bytes (0 on arguments the entry
+ * refuses): the text entry's, then one int64 per record, 40 bytes per tile of 2048 bins and class, and the chunk boundaries.
+ * Synchronises the stream (at most three times). */
+typedef struct { int64_t beg, end; int32_t rec; uint32_t bin; } dgrp_track_chunk;
+int64_t dgrp_track_index_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                         int64_t names_bytes);
+int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                           const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls, int ncls,
+                           int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_chunk_off,
+                           int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3-A11 in one call: everything deepgrp/__main__.py:46-83 and :288-292 do for ONE record whose class indices
  * (after N stripping, startpos = offset) are in HBM: windows, forward, max-merge with the reference's placement for
  * `batch`, then scores + MSS labels (use_mss != 0; deepgrp/prediction.py:40-59) or softmax + argmax
