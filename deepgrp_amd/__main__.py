@@ -12,7 +12,8 @@ Differences, all additive:
   * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B] [--track_gzip]` also writes the per-base class
     probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py), with --track_gzip as BGZF deflated on the GPU
     (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well) and with --track_index a tabix index beside
-    every BGZF track (deepgrp_amd/tabix.py);
+    every BGZF track (deepgrp_amd/tabix.py); with --track_bigwig the tracks are bigWig files instead (`.bw`, deepgrp_amd/bigwig.py:
+    binary sections and zoom levels written and deflated on the GPU);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
@@ -138,8 +139,8 @@ def _add_mask_options(parser, suppress: bool) -> None:
                         help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
                              "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
     parser.add_argument("--gzip_level", type=int, default=d(None),
-                        help="(addition) level of the GPU deflate of --mask_gzip and --track_gzip: 0 literals only, 1 with matches "
-                             "(default: 0 for masked copies, 1 for tracks)")
+                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip and --track_bigwig: 0 literals only, 1 with "
+                             "matches (default: 0 for masked copies, 1 for tracks)")
 
 
 def _add_track_options(parser) -> None:
@@ -156,6 +157,12 @@ def _add_track_options(parser) -> None:
                         help="(addition) with --track_gzip: write the tabix index <track>.gz.tbi of every track, built on the GPU "
                              "beside the text (records must end at or below 2^29 and names must not reappear after another name; "
                              "otherwise a warning and no index)")
+    parser.add_argument("--track_bigwig", action="store_true", default=s,
+                        help="(addition) with --track_dir: write every track as bigWig, DIR/<basename>.class<c>.bw, instead of bedGraph: "
+                             "the same items in binary sections with zoom levels, built and deflated on the GPU (--gzip_level, 1 unless "
+                             "given).  A chromosome's size is the end of its predicted span (trailing N are not counted).  Record "
+                             "names must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and "
+                             "no bigWig for that input.  Not with --track_gzip or --track_index")
     parser.add_argument("--track_classes", type=_class_list, default=s,
                         help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
     parser.add_argument("--track_digits", type=int, default=s,
@@ -454,10 +461,14 @@ class CommandLineParser:
         try:
             if _LOG.isEnabledFor(logging.DEBUG):
                 bases = 0
-                for header, rec in records:
+                for chrom, (header, rec) in enumerate(records):
                     name = record_name(filename, header)
-                    sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec))
+                    sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec, chrom))
                     rows, n = CommandLineParser._predict_staged(pipe, header, rec, sink)
+                    if n == 0 and spec.bigwig:                      # no base to predict: still a chromosome of the bigWig
+                        from .pipeline import record_indices
+                        from .tracks import empty_texts
+                        files.write(empty_texts(spec, name, record_indices(rec)[0]))
                     bases += n
                     outstream.write(rows_text(filename, header, rows))
                     if kept is not None:
@@ -725,7 +736,8 @@ class CommandLineParser:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
         if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
             sys.exit("--mask_dir belongs to predict, not evaluate")
-        if getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False):
+        if (getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False)
+                or getattr(args, "track_bigwig", False)):
             sys.exit("--track_dir belongs to predict, not evaluate")
         if getattr(args, "gzip_level", None) is not None:
             sys.exit("--gzip_level belongs to predict, not evaluate")

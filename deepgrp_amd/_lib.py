@@ -42,6 +42,14 @@ _SIGNATURES = {
     "dgrp_track_text_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp]),
     "dgrp_track_index_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64]),
     "dgrp_track_index_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp, i64, vp]),
+    "dgrp_track_sections_workspace_bytes": (i64, [i64, vp, vp, i64, cint]),
+    "dgrp_track_sections_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, i64, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_track_zoom_workspace_bytes": (i64, [i64, vp, vp, i64, cint]),
+    "dgrp_track_zoom_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, i64, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "dgrp_zlib_bound": (i64, [i64, i64]),
+    "dgrp_zlib_workspace_bytes": (i64, [i64, cint]),
+    "dgrp_zlib_compress_batch": (cint, [vp, i64, vp, i64, i64, cint, vp, i64, vp, C.POINTER(i64), vp, i64, vp]),
+    "dgrp_zlib_compress_host": (cint, [vp, i64, vp, i64, i64, cint, vp, i64, vp, C.POINTER(i64)]),
     "dgrp_window_count":(i64, [i64, i64, i64]),
     "dgrp_windows_onehot": (cint, [vp, i64, i64, i64, i64, i64, cint, vp, vp]),
     "dgrp_model_create": (cint, [C.POINTER(vp), cint, cint, cint, cint, vp, vp, vp, vp, vp, vp]),

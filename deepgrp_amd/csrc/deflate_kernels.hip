@@ -24,6 +24,7 @@
 // allows), with the EOF member behind them on request.  Only the total is read back.
 #include "dgrp_common.h"
 #include "deflate.h"
+#include "deflate_blocks.h"
 #include "scan.h"
 #include <string.h>
 #include <mutex>
@@ -207,17 +208,37 @@ __device__ __forceinline__ void deflate_finish(uint32_t len, uint32_t deflate_by
     if (tid == 0) *size = total;
 }
 
-// one workgroup per member m: in[m * 0xff00 ...) -> slots[m * DGRP_BGZF_SLOT ...), sizes[m]
+// where member m's bytes lie: in[m * 0xff00 ...) of n bytes, or, with a block table (rows of `stride` bytes that begin with int64
+// offset and int64 length <= 0xff00), in[offset ...); a row that does not lie in in[0, n) reads as empty
+__device__ __forceinline__ const uint8_t *deflate_member_src(const uint8_t *__restrict__ in, int64_t n, const char *__restrict__ rows,
+                                                             int64_t stride, int64_t m, uint32_t &len)
+{
+    if (rows) {
+        const int64_t *row = reinterpret_cast<const int64_t *>(rows + m * stride);
+        const bool ok = row[0] >= 0 && row[1] >= 0 && row[1] <= DGRP_BGZF_BLOCK && row[0] <= n - row[1];
+        len = ok ? (uint32_t)row[1] : 0u;
+        return in + (ok ? row[0] : 0);
+    }
+    const int64_t left = n - m * DGRP_BGZF_BLOCK;
+    len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
+    return in + m * DGRP_BGZF_BLOCK;
+}
+
+// one workgroup per member m: its bytes (deflate_member_src) -> slots[m * DGRP_BGZF_SLOT ...), sizes[m]
 __global__ void __launch_bounds__(DEFLATE_THREADS) deflate_member_kernel(const uint8_t *__restrict__ in, int64_t n,
+                                                                         const char *__restrict__ rows, int64_t stride,
                                                                          uint8_t *__restrict__ slots, uint64_t *__restrict__ sizes)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char deflate_smem[];
     deflate_lds &L = *reinterpret_cast<deflate_lds *>(deflate_smem);
     const uint32_t tid = threadIdx.x;
     const int64_t m = blockIdx.x;
-    const uint8_t *src = in + m * DGRP_BGZF_BLOCK;
-    const int64_t left = n - m * DGRP_BGZF_BLOCK;
-    const uint32_t len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
+    uint32_t len;
+    const uint8_t *src = deflate_member_src(in, n, rows, stride, m, len);
+    if (len == 0) {                                           // (uniform; a table's empty block: no member, the caller frames it)
+        if (tid == 0) sizes[m] = 0;
+        return;
+    }
     const uint32_t nrun = (len + DEFLATE_RUN - 1) / DEFLATE_RUN;
 
     for (uint32_t i = tid; i < DGRP_BGZF_SLOT / 4; i += DEFLATE_THREADS) L.image[i] = 0;
@@ -248,16 +269,21 @@ __device__ __forceinline__ uint32_t deflate_lz_ld4(const uint32_t *text, uint32_
 }
 
 // level 1: as deflate_member_kernel, with lz[m * 0xff00 ...) for the member's word per position
-__global__ void __launch_bounds__(DEFLATE_THREADS) deflate_lz_member_kernel(const uint8_t *__restrict__ in, int64_t n, uint8_t *__restrict__ slots,
-                                                                            uint64_t *__restrict__ sizes, uint32_t *lz)
+__global__ void __launch_bounds__(DEFLATE_THREADS) deflate_lz_member_kernel(const uint8_t *__restrict__ in, int64_t n,
+                                                                            const char *__restrict__ rows, int64_t stride,
+                                                                            uint8_t *__restrict__ slots, uint64_t *__restrict__ sizes,
+                                                                            uint32_t *lz)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char deflate_smem[];
     deflate_lz_lds &L = *reinterpret_cast<deflate_lz_lds *>(deflate_smem);
     const uint32_t tid = threadIdx.x;
     const int64_t m = blockIdx.x;
-    const uint8_t *src = in + m * DGRP_BGZF_BLOCK;
-    const int64_t left = n - m * DGRP_BGZF_BLOCK;
-    const uint32_t len = left < DGRP_BGZF_BLOCK ? (uint32_t)left : DGRP_BGZF_BLOCK;
+    uint32_t len;
+    const uint8_t *src = deflate_member_src(in, n, rows, stride, m, len);
+    if (len == 0) {                                           // (uniform; a table's empty block: no member, the caller frames it)
+        if (tid == 0) sizes[m] = 0;
+        return;
+    }
     const uint32_t nrun = (len + DEFLATE_RUN - 1) / DEFLATE_RUN, ntile = (len + DEFLATE_LZ_TILE - 1) / DEFLATE_LZ_TILE;
     uint32_t *ws = lz + m * DGRP_BGZF_BLOCK;
 
@@ -489,6 +515,32 @@ static const uint8_t BGZF_EOF_MEMBER[DGRP_BGZF_EOF_BYTES] = {0x1f, 0x8b, 8, 4, 0
 
 }   // namespace
 
+// The member kernel of `level` for nmem members (contiguous blocks of d_in[0, n), or the blocks of a table: deflate_member_src), on the
+// stream: slots (nmem * DGRP_BGZF_SLOT bytes, 16-byte aligned), sizes[nmem], lz (level 1: nmem * 0xff00 words).  Also for
+// bigwig_kernels.hip, which reframes the members as zlib streams (deflate_blocks.h).
+int dgrp_deflate_members(const uint8_t *d_in, int64_t n, const char *d_rows, int64_t stride, int64_t nmem, int level, uint8_t *slots,
+                         uint64_t *sizes, uint32_t *lz, hipStream_t stream)
+{
+    static std::once_flag configured;
+    static hipError_t cfg_err = hipSuccess;
+    std::call_once(configured, [] {
+        cfg_err = hipFuncSetAttribute((const void *)deflate_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(deflate_lds));
+        if (cfg_err == hipSuccess)
+            cfg_err = hipFuncSetAttribute((const void *)deflate_lz_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sizeof(deflate_lz_lds));
+    });
+    DGRP_HIP(cfg_err);
+    if (level == 0) {
+        hipLaunchKernelGGL(deflate_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lds), stream, d_in, n, d_rows,
+                           stride, slots, sizes);
+    } else {
+        hipLaunchKernelGGL(deflate_lz_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lz_lds), stream, d_in, n,
+                           d_rows, stride, slots, sizes, lz);
+    }
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
 DGRP_EXPORT int64_t dgrp_bgzf_bound(int64_t n, int eof)
 {
     if (n < 0) return 0;
@@ -549,25 +601,11 @@ static int bgzf_compress_device(const char *who, const uint8_t *d_in, int64_t n,
         dgrp_set_error("%s: d_work must be 16-byte aligned", who);
         return DGRP_EINVAL;
     }
-    static std::once_flag configured;
-    static hipError_t cfg_err = hipSuccess;
-    std::call_once(configured, [] {
-        cfg_err = hipFuncSetAttribute((const void *)deflate_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(deflate_lds));
-        if (cfg_err == hipSuccess)
-            cfg_err = hipFuncSetAttribute((const void *)deflate_lz_member_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)sizeof(deflate_lz_lds));
-    });
-    DGRP_HIP(cfg_err);
     uint8_t *slots = (uint8_t *)d_work;
     uint64_t *sizes = (uint64_t *)(slots + dgrp_align_up(nmem * DGRP_BGZF_SLOT, 256));
-    if (level == 0) {
-        hipLaunchKernelGGL(deflate_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lds), stream, d_in, n, slots, sizes);
-    } else {
-        uint32_t *lz = (uint32_t *)((uint8_t *)sizes + dgrp_align_up((nmem + 1) * 8, 256));
-        hipLaunchKernelGGL(deflate_lz_member_kernel, dim3((unsigned)nmem), dim3(DEFLATE_THREADS), sizeof(deflate_lz_lds), stream, d_in, n, slots,
-                           sizes, lz);
-    }
-    DGRP_LAUNCH_CHECK();
+    uint32_t *lz = level == 0 ? nullptr : (uint32_t *)((uint8_t *)sizes + dgrp_align_up((nmem + 1) * 8, 256));
+    const int rc = dgrp_deflate_members(d_in, n, nullptr, 0, nmem, level, slots, sizes, lz, stream);
+    if (rc != DGRP_OK) return rc;
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, sizes, nmem, sizes + nmem);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(bgzf_place_kernel, dim3((unsigned)(nmem + (eof ? 1 : 0))), dim3(256), 0, stream, slots, sizes, nmem, eof, d_out, out_cap);

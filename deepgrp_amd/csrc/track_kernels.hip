@@ -9,25 +9,13 @@
 // See include/deepgrp_hip.h.
 #include "dgrp_common.h"
 #include "scan.h"
+#include "track_chain.h"
 #include <string.h>
 #include <vector>
 
 namespace {
 
 #define TRACK_WAVE_BIN 64         // bins wider than this are reduced by a whole wave, narrower ones by one lane
-
-struct track_geom {
-    int64_t offset, n, bin;       // span [offset, offset + n) in record coordinates, bin width
-    int64_t kb0, nb;              // first bin (offset / bin), bins touching the span
-};
-
-// the coordinates [lo, hi) of bin j, clipped to the span
-__device__ __forceinline__ void track_bin_span(const track_geom &g, int64_t j, int64_t &lo, int64_t &hi)
-{
-    const int64_t a = (g.kb0 + j) * g.bin, b = a + g.bin;
-    lo = a > g.offset ? a : g.offset;
-    hi = b < g.offset + g.n ? b : g.offset + g.n;
-}
 
 // floor(v * 10^D + 0.5) as two float32 roundings (this file is compiled with -ffp-contract=off), clamped to [0, 10^D]
 __device__ __forceinline__ uint32_t track_quantise(float v, float scale, uint32_t qmax)
@@ -57,45 +45,7 @@ __device__ __forceinline__ void track_put_decimal(char *o, uint64_t v, int w)
     }
 }
 
-#define TRACK_TILE 2048                  // bins per workgroup: 8 rounds of 256 consecutive bins
 #define TRACK_STAGE 32768                // bytes of one round's text that are assembled in LDS (longer rounds write directly)
-
-struct tb_rec { int64_t row0, n, offset, kb0, nb, name_off, name_len, pad; };     // one record: 64 bytes of the uploaded table
-struct tb_geom {
-    int64_t nrec, NB, NBpad, bin;        // records, bins of all records, the same rounded up to TRACK_TILE, bin width
-    int C, ncls, digits;
-};
-
-// record of flat bin f < pref[nrec]: the largest r with pref[r] <= f (every record has at least one bin)
-__device__ __forceinline__ int64_t tb_record_of(const int64_t *__restrict__ pref, int64_t nrec, int64_t f)
-{
-    int64_t lo = 0, hi = nrec;                    // pref[lo] <= f < pref[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (pref[mid] <= f) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the same for f >= f0 when r0 is the record of f0 (found once per tile): mostly r0 itself, else one of the next f - f0 records
-__device__ __forceinline__ int64_t tb_record_from(const int64_t *__restrict__ pref, int64_t nrec, int64_t r0, int64_t f0, int64_t f)
-{
-    if (pref[r0 + 1] > f) return r0;
-    int64_t lo = r0 + 1, hi = r0 + (f - f0) + 1;
-    if (hi > nrec) hi = nrec;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (pref[mid] <= f) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ track_geom tb_geom_of(const tb_rec &R, int64_t bin)
-{
-    track_geom g;
-    g.offset = R.offset; g.n = R.n; g.bin = bin; g.kb0 = R.kb0; g.nb = R.nb;
-    return g;
-}
 
 #define TB_CLS 8                         // classes reduced side by side from one read of a row (more classes: one more pass per 8)
 
@@ -308,11 +258,6 @@ __global__ void __launch_bounds__(256) tb_write_kernel(const uint32_t *__restric
     }
 }
 
-// byte offsets of the workspace's parts (recs .. names within the uploaded tables); NB = the bins per class it has room for
-struct tb_layout { int64_t NB, NBpad, tables, tables_bytes, recs, pref, cls, names, q, tiles, bytes; };
-
-#define TRACK_MAX_EXTENT (1ll << 40)     // n, offset and bin: far beyond any genome; no product overflows
-
 // the workspace with room for NB bins per class; false: more bins than the grids take (2^39)
 static bool tb_carve_bins(int64_t nrec, int64_t NB, int ncls, int64_t names_bytes, tb_layout *l)
 {
@@ -351,28 +296,14 @@ static bool tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos
     return tb_carve_bins(nrec, NB, ncls, names_bytes, l);
 }
 
-// what the front half of the chain leaves on the device for the pass that follows it
-struct tb_dev {
-    uint64_t *grand, *bounds;            // the text's total, its class boundaries [ncls + 1]
-    const tb_rec *recs;
-    const int64_t *pref;
-    const int *cls;
-    const char *names;
-    uint32_t *q;
-    uint64_t *tiles;                     // scanned: the text offset of every tile
-    tb_geom G;
-    uint32_t qmax;
-    int64_t tpc, ntiles;                 // tiles per class, tiles
-};
-
-// The front half of every chain on checked arguments and a workspace carved as `l` (room for at least the records' bins and names):
-// one upload of the tables, bin pass, count, scan, the class boundaries to h_class_off (one synchronisation).
-static int tb_front(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
-                    const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin,
-                    int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream, tb_dev *D)
+// The shared start of every chain on checked arguments and a workspace carved as `l`: one upload of the tables (`tab`, which the
+// caller keeps until its next synchronisation) and the bin pass.  No synchronisation.
+static int tb_bins(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                   const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin, void *d_work,
+                   const tb_layout &l, hipStream_t stream, std::vector<char> &tab, tb_dev *D)
 {
     const int64_t names_bytes = h_name_off[nrec];
-    std::vector<char> tab((size_t)(l.names + names_bytes));
+    tab.assign((size_t)(l.names + names_bytes), 0);
     tb_rec *recs = (tb_rec *)(tab.data() + l.recs);
     int64_t *pref = (int64_t *)(tab.data() + l.pref);
     pref[0] = 0;
@@ -409,6 +340,26 @@ static int tb_front(const float *d_probs, int C, int64_t nrec, const int64_t *h_
                            scale, qmax, q);
     }
     DGRP_LAUNCH_CHECK();
+    D->grand = grand; D->bounds = bounds; D->recs = d_recs; D->pref = d_pref; D->cls = d_cls; D->names = w + l.tables + l.names;
+    D->q = q; D->tiles = tiles; D->G = G; D->qmax = qmax; D->tpc = tpc; D->ntiles = ntiles;
+    return DGRP_OK;
+}
+
+// The front half of every text chain on checked arguments and a workspace carved as `l` (room for at least the records' bins and
+// names): one upload of the tables, bin pass, count, scan, the class boundaries to h_class_off (one synchronisation).
+static int tb_front(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                    const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin,
+                    int64_t *h_class_off, void *d_work, const tb_layout &l, hipStream_t stream, tb_dev *D)
+{
+    std::vector<char> tab;                                                 // (alive until the synchronisation below)
+    const int rc = tb_bins(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, d_work, l, stream, tab, D);
+    if (rc != DGRP_OK) return rc;
+    const tb_rec *d_recs = D->recs;
+    const int64_t *d_pref = D->pref;
+    uint32_t *q = D->q;
+    uint64_t *tiles = D->tiles, *grand = D->grand, *bounds = D->bounds;
+    const tb_geom G = D->G;
+    const int64_t tpc = D->tpc, ntiles = D->ntiles;
     hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, stream, q, d_recs, d_pref, G, tiles);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, tiles, ntiles, grand);
@@ -419,8 +370,6 @@ static int tb_front(const float *d_probs, int C, int64_t nrec, const int64_t *h_
     DGRP_HIP(hipMemcpyAsync(off.data(), bounds, off.size() * 8, hipMemcpyDeviceToHost, stream));
     DGRP_HIP(hipStreamSynchronize(stream));
     for (int k = 0; k <= ncls; ++k) h_class_off[k] = (int64_t)off[(size_t)k];
-    D->grand = grand; D->bounds = bounds; D->recs = d_recs; D->pref = d_pref; D->cls = d_cls; D->names = w + l.tables + l.names;
-    D->q = q; D->tiles = tiles; D->G = G; D->qmax = qmax; D->tpc = tpc; D->ntiles = ntiles;
     return DGRP_OK;
 }
 
@@ -684,6 +633,18 @@ static bool ix_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos
 }
 
 }   // namespace
+
+bool dgrp_tb_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes, tb_layout *l)
+{
+    return tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, l);
+}
+
+int dgrp_tb_bins(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n, const int64_t *h_startpos,
+                 const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits, int64_t bin, void *d_work,
+                 const tb_layout &l, hipStream_t stream, std::vector<char> &tab, tb_dev *D)
+{
+    return tb_bins(d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin, d_work, l, stream, tab, D);
+}
 
 DGRP_EXPORT int64_t dgrp_track_workspace_bytes(int64_t n, int64_t bin)
 {

@@ -605,12 +605,100 @@ class ContigPipeline:
         host = chunks[:int(off[ncls]) * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, off, linear[:ncls * nwin].cpu().numpy().reshape(ncls, nwin), wpref
 
-    def run_batch_tracked(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, names, spec):
+    @staticmethod
+    def _track_tables(d_probs: torch.Tensor, row0, lengths, startposes, classes, who: str):
+        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
+            raise ValueError(f"{who} takes a contiguous float32 [rows, C] array")
+        return (np.ascontiguousarray(row0, np.int64), np.ascontiguousarray(lengths, np.int64), np.ascontiguousarray(startposes, np.int64),
+                np.ascontiguousarray(classes, np.int32))
+
+    def track_sections_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, classes, digits: int = 2, bin: int = 1,
+                                    chrom0: int = 0):
+        """The bigWig sections of many records and classes in one dgrp_track_sections_batch call (arguments as
+        track_text_batch_device, no names): -> (uint8 device tensor of the uncompressed sections, class-major; byte offsets
+        [len(classes) + 1]; uint8 device tensor of the section table, rows of bigwig.SECTION_DTYPE; section offsets [len(classes) + 1]).
+        `rec` counts the records of this call, chromId is chrom0 + rec."""
+        from .bigwig import SECTION_DTYPE
+        L = lib()
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, row0, lengths, startposes, classes, "track_sections_batch_device")
+        c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
+        wb = L.dgrp_track_sections_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls)
+        if wb <= 0:
+            raise ValueError(f"track_sections_batch_device: bad record lengths, start positions (ends above 2^32 - 1?), bin {bin} or class count {ncls}")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        nb = int((ln // int(bin) + 2).sum())
+        cap = ncls * min(12 * nb + 24 * (nb // 1024 + nrec), (1 << 20) + 3 * nb)        # (the guess fits most runs)
+        tcap = ncls * (cap // (ncls * 12 * 1024) + nrec + 1)
+        off, soff = np.zeros(ncls + 1, np.int64), np.zeros(ncls + 1, np.int64)
+        while True:
+            out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+            table = torch.empty(max(tcap, 1) * SECTION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_track_sections_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, cl.ctypes.data, ncls,
+                                              int(digits), int(bin), int(chrom0), _ptr(out), cap, off.ctypes.data, _ptr(table), tcap, soff.ctypes.data,
+                                              _ptr(work), wb, stream_ptr()), "dgrp_track_sections_batch")
+            if int(off[ncls]) <= cap and int(soff[ncls]) <= tcap:
+                break
+            cap, tcap = max(cap, int(off[ncls])), max(tcap, int(soff[ncls]))       # more than guessed: run again with room for all
+        return out[:int(off[ncls])], off, table[:int(soff[ncls]) * SECTION_DTYPE.itemsize], soff
+
+    def track_zoom_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, classes, digits: int = 2, bin: int = 1,
+                                chrom0: int = 0):
+        """The zoom records of the same arguments in one dgrp_track_zoom_batch call: -> (uint8 device tensor of the 32-byte records;
+        record offsets [len(classes) * bigwig.ZOOM_LEVELS + 1], segment k * ZOOM_LEVELS + level; uint8 device tensor of the block
+        table, rows of bigwig.ZOOM_BLOCK_DTYPE; block offsets, as the record offsets; totals, bigwig.TOTALS_DTYPE [len(classes)])."""
+        from .bigwig import TOTALS_DTYPE, ZOOM_BLOCK_DTYPE, ZOOM_LEVELS
+        L = lib()
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, row0, lengths, startposes, classes, "track_zoom_batch_device")
+        c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
+        wb = L.dgrp_track_zoom_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls)
+        if wb <= 0:
+            raise ValueError(f"track_zoom_batch_device: bad record lengths, start positions (ends above 2^32 - 1?), bin {bin} or class count {ncls}")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        nseg = ncls * ZOOM_LEVELS
+        nwin = int((ln // (16 * int(bin)) + 2).sum())
+        cap = 32 * ncls * (nwin // 4 + ZOOM_LEVELS * nrec + 64)                     # (the guess fits sparse tracks)
+        tcap = cap // (32 * 1024) + nseg
+        roff, boff = np.zeros(nseg + 1, np.int64), np.zeros(nseg + 1, np.int64)
+        totals = np.zeros(ncls, TOTALS_DTYPE)
+        while True:
+            out = torch.empty(max(cap, 32), dtype=torch.uint8, device=dev)
+            table = torch.empty(max(tcap, 1) * ZOOM_BLOCK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_track_zoom_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, cl.ctypes.data, ncls,
+                                          int(digits), int(bin), int(chrom0), _ptr(out), cap, roff.ctypes.data, _ptr(table), tcap, boff.ctypes.data,
+                                          totals.ctypes.data, _ptr(work), wb, stream_ptr()), "dgrp_track_zoom_batch")
+            if 32 * int(roff[nseg]) <= cap and int(boff[nseg]) <= tcap:
+                break
+            cap, tcap = max(cap, 32 * int(roff[nseg])), max(tcap, int(boff[nseg]))
+        return out[:32 * int(roff[nseg])], roff, table[:int(boff[nseg]) * ZOOM_BLOCK_DTYPE.itemsize], boff, totals
+
+    @staticmethod
+    def zlib_compress_device(d_in: torch.Tensor, d_rows: torch.Tensor, stride: int, level: int = 1):
+        """The blocks of the uint8 device tensor `d_in` that the rows of `d_rows` name (uint8 device tensor, `stride` bytes a row,
+        each beginning with int64 offset and int64 length: a section or zoom block table as it comes) as zlib streams back to back
+        (dgrp_zlib_compress_batch): -> (uint8 device tensor, int64 device tensor of the streams' sizes).  One read-back: the total."""
+        L = lib()
+        nblk = int(d_rows.numel()) // stride
+        dev = d_in.device
+        if nblk == 0:
+            return torch.empty(0, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+        n = int(d_in.numel())
+        cap = int(L.dgrp_zlib_bound(nblk, n))
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(nblk, dtype=torch.int64, device=dev)
+        wb = int(L.dgrp_zlib_workspace_bytes(nblk, int(level)))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        got = C.c_int64(0)
+        check(L.dgrp_zlib_compress_batch(_ptr(d_in), n, _ptr(d_rows), stride, nblk, int(level), _ptr(out), cap, _ptr(sizes), C.byref(got),
+                                         _ptr(work), wb, stream_ptr()), "dgrp_zlib_compress_batch")
+        return out[:got.value], sizes
+
+    def run_batch_tracked(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, names, spec, chrom0: int = 0):
         """run_batch with probability tracks: one dgrp_predict_batch_probs call, then one dgrp_track_text_batch call on its merged
         probabilities.  -> (rows, texts), texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
         give one after the other); with spec.gzip_level the BGZF members of that slice instead (no EOF member), deflated on the
         device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member; with spec.index the batch's
-        tracks.WriteIndex comes with them (texts.index)."""
+        tracks.WriteIndex comes with them (texts.index); with spec.bigwig tracks.bigwig_write's result instead (chrom0: the
+        ordinal of the batch's first record in its input)."""
         L = lib()
         nrec = len(lengths)
         if nrec == 0:
@@ -621,6 +709,9 @@ class ContigPipeline:
         rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
         row0 = np.zeros(nrec, np.int64)
         np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
+        if spec.bigwig:                                      # --track_bigwig: sections and zoom blocks instead of text
+            from .tracks import bigwig_write
+            return rows, bigwig_write(self, d_probs, row0, ln, startposes, names, spec, chrom0)
         d_text, off = self.track_text_batch_device(d_probs, row0, ln, startposes, names, spec.classes, spec.digits, spec.bin)
         index = None
         if spec.gzip_level is not None and spec.index:

@@ -21,10 +21,12 @@ class _Tracked(NamedTuple):
     """A work item of tracked_results: one record and the name of its track lines."""
     name: str
     rec: object
+    chrom: int = 0            # the record's ordinal in its input (the chromId of --track_bigwig)
 
 
 class _TrackedBatch(list):
-    """A batch work item of tracked_results: [((header, name), record), ...]."""
+    """A batch work item of tracked_results: [((header, name), record), ...]; chrom0: the ordinal of its first record in the input."""
+    chrom0 = 0
 
 
 _BATCH = object()             # key slot of a work item that is a batch of records (never equal to a user's key, e.g. a header "batch")
@@ -99,15 +101,15 @@ class RecordRunner:
             return self.pipe.run_idx(d_idx, startpos, contig)
         return self.pipe.run(rec, contig)
 
-    def run_tracked(self, rec, name: str):
+    def run_tracked(self, rec, name: str, chrom: int = 0):
         """(rows, track texts) of one record: merged -> the text of every class of self.tracks -> labels -> segments."""
         from .pipeline import SEGMENT_DTYPE
-        from .tracks import record_texts
+        from .tracks import empty_texts, record_texts
         startpos, d_idx = record_indices(rec)
         if d_idx.numel() == 0:
-            return np.zeros(0, SEGMENT_DTYPE), [b""] * len(self.tracks.classes)
+            return np.zeros(0, SEGMENT_DTYPE), empty_texts(self.tracks, name, startpos)
         merged = self.pipe.merged(d_idx)
-        texts = record_texts(self.pipe, merged, startpos, name, self.tracks)
+        texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom)
         return self.pipe.segments(self.pipe.labels(merged), startpos), texts
 
     # ---- batching
@@ -147,11 +149,13 @@ class RecordRunner:
 
     def run_item(self, item):
         if isinstance(item, _Tracked):
+            if self.tracks.bigwig:                        # (the record's ordinal in its input is the chromId of its sections)
+                return self.run_tracked(item.rec, item.name, item.chrom)
             return self.run_tracked(item.rec, item.name)
         if isinstance(item, _TrackedBatch):               # the same with the track texts of the whole batch, class by class
             rows, texts = self.pipe.run_batch_tracked(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
                                                       [r.startpos for _k, r in item], list(range(len(item))),
-                                                      [k[1] for k, _r in item], self.tracks)
+                                                      [k[1] for k, _r in item], self.tracks, *((item.chrom0,) if self.tracks.bigwig else ()))
             return [k for k, _r in item], rows, texts
         if isinstance(item, list):                        # a batch: rows of all its records, contig = position in the batch
             rows = self.pipe.run_batch(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
@@ -217,11 +221,16 @@ class RecordRunner:
         short records -- rows["contig"] indexes the keys, texts[k] is the text of class self.tracks.classes[k] of all its records in
         order.  Records batch exactly when they do without tracks."""
         def items():
+            chrom = 0                                     # records of this input so far
             for key, item in self.work_items(records):
                 if key is _BATCH:
-                    yield _BATCH, _TrackedBatch(item)
+                    batch = _TrackedBatch(item)
+                    batch.chrom0 = chrom
+                    chrom += len(item)
+                    yield _BATCH, batch
                 else:
-                    yield key, _Tracked(key[1], item)
+                    yield key, _Tracked(key[1], item, chrom)
+                    chrom += 1
         for key, result in self.in_order(items()):
             if key is _BATCH:
                 keys, rows, texts = result

@@ -16,7 +16,11 @@ the file is committed.
 
 With `--track_index` every `.gz` gets its tabix index `<track>.gz.tbi` (tabix.py states the format): chunks and linear index come
 from the device in text offsets (dgrp_track_index_batch, for the arguments of the text), `TrackFiles` turns them into virtual
-offsets with the compressed size of every member it appends, and `commit` writes the index."""
+offsets with the compressed size of every member it appends, and `commit` writes the index.
+
+With `--track_bigwig` the files are `<basename>.class<c>.bw` instead, bigWig as bigwig.py states it: the same items in binary
+sections with ten zoom levels at most, sections and zoom records written and deflated on the device (`bigwig_write`), the container
+put around them by a bigwig.BigWigBuilder per class."""
 from __future__ import annotations
 
 import logging
@@ -37,6 +41,7 @@ class TrackSpec(NamedTuple):
     bin: int = 1
     gzip_level: Optional[int] = None                # None: plain text; else BGZF members at this level
     index: bool = False                             # --track_index: a tabix index beside every BGZF track
+    bigwig: bool = False                            # --track_bigwig: bigWig files (zlib streams at gzip_level) instead of bedGraph
 
 
 class TrackPlan(NamedTuple):
@@ -47,13 +52,16 @@ class TrackPlan(NamedTuple):
     bases: dict                                     # input file -> basename of its track files
     gzip_level: Optional[int] = None                # --track_gzip: the level (None: plain bedGraph)
     index: bool = False                             # --track_index
+    bigwig: bool = False                            # --track_bigwig (gzip_level is then the level of its zlib streams)
 
 
 def input_basename(filename: str) -> str:
     return "stdin" if filename == "-" else os.path.basename(filename)
 
 
-def track_path(directory: str, base: str, cls: int, gzip: bool = False) -> str:
+def track_path(directory: str, base: str, cls: int, gzip: bool = False, bigwig: bool = False) -> str:
+    if bigwig:
+        return os.path.join(directory, f"{base}.class{cls}.bw")
     return os.path.join(directory, f"{base}.class{cls}.bedGraph" + (".gz" if gzip else ""))
 
 
@@ -72,13 +80,18 @@ def gzip_level(args, default: int) -> Optional[int]:
 
 
 def check_gzip_flags(args) -> None:
-    """The refusals of --track_gzip, --track_index and --gzip_level that need nothing but the flags (sys.exit)."""
+    """The refusals of --track_gzip, --track_index, --track_bigwig and --gzip_level that need nothing but the flags (sys.exit)."""
     if getattr(args, "track_gzip", False) and getattr(args, "track_dir", None) is None:
         sys.exit("--track_gzip needs --track_dir")
+    if getattr(args, "track_bigwig", False):
+        if getattr(args, "track_dir", None) is None:
+            sys.exit("--track_bigwig needs --track_dir")
+        if getattr(args, "track_gzip", False) or getattr(args, "track_index", False):
+            sys.exit("--track_bigwig writes bigWig files instead of bedGraph: it does not go with --track_gzip or --track_index")
     if getattr(args, "track_index", False) and not getattr(args, "track_gzip", False):
         sys.exit("--track_index needs --track_gzip (a tabix index belongs to a BGZF file)")
     if getattr(args, "gzip_level", None) is not None:
-        if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False)):
+        if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False) or getattr(args, "track_bigwig", False)):
             sys.exit("--gzip_level needs --mask_gzip or --track_gzip")
         gzip_level(args, 0)
 
@@ -108,9 +121,10 @@ def plan(args) -> Optional[TrackPlan]:
             sys.exit(f"--track_dir: {seen[base]} and {f} have the same file name; their tracks would collide")
         seen[base] = f
         bases[f] = base
-    level = gzip_level(args, 1) if getattr(args, "track_gzip", False) else None
+    bigwig = bool(getattr(args, "track_bigwig", False))
+    level = gzip_level(args, 1) if getattr(args, "track_gzip", False) or bigwig else None
     return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases, level,
-                     bool(getattr(args, "track_index", False)))
+                     bool(getattr(args, "track_index", False)), bigwig)
 
 
 def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
@@ -119,7 +133,7 @@ def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
     bad = [c for c in classes if not 0 <= c < nclasses]
     if bad:
         sys.exit(f"--track_classes: label {bad[0]} is not a class of this model (labels 0..{nclasses - 1})")
-    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index)
+    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index, p.bigwig)
 
 
 class WriteIndex(NamedTuple):
@@ -133,9 +147,78 @@ class WriteIndex(NamedTuple):
     wpref: Optional[np.ndarray] = None
 
 
+class BigWigWrite(NamedTuple):
+    """What one write (a record, or a batch) adds to the bigWig files of its input: the records' names and chromSizes (startpos + n)
+    and, class by class, a bigwig.ClassWrite -- or why this input cannot have bigWig files."""
+    names: List[bytes]
+    sizes: List[int]
+    refused: Optional[str] = None
+    classes: Optional[list] = None                  # None: records without a predicted base (names and sizes only)
+    chrom0: Optional[int] = None                    # the chromId of the first record, as the device wrote it (None: unchecked)
+
+
 class TrackTexts(list):
-    """The texts (or BGZF members) of one write, class by class; with --track_index `index` is its WriteIndex."""
+    """The texts (or BGZF members) of one write, class by class; with --track_index `index` is its WriteIndex.  With
+    --track_bigwig the entries are the compressed sections and `bigwig` is the write's BigWigWrite."""
     index: Optional[WriteIndex] = None
+    bigwig: Optional[BigWigWrite] = None
+
+
+ZLIB_PIECE = 4096                                   # blocks deflated per call (GZIP_PIECE's reason: the level-1 workspace)
+
+
+def _zlib_pieces(pipe, d_in, d_table, stride: int, level: int):
+    """The blocks of a table as zlib streams, ZLIB_PIECE blocks a call: -> (bytes, int64 sizes)."""
+    blobs, sizes = [], []
+    for a in range(0, int(d_table.numel()), ZLIB_PIECE * stride):
+        d_out, d_sizes = pipe.zlib_compress_device(d_in, d_table[a:a + ZLIB_PIECE * stride], stride, level)
+        blobs.append(d_out.cpu().numpy().tobytes())
+        sizes.append(d_sizes.cpu().numpy())
+    return b"".join(blobs), (np.concatenate(sizes) if sizes else np.zeros(0, np.int64))
+
+
+def empty_texts(spec: TrackSpec, name, startpos: int):
+    """The write of a record without a predicted base: no text; with spec.bigwig its name and size for the chromosome tree."""
+    if not spec.bigwig:
+        return [b""] * len(spec.classes)
+    out = TrackTexts(b"" for _ in spec.classes)
+    out.bigwig = BigWigWrite([name if isinstance(name, bytes) else name.encode("utf-8", "surrogateescape")], [int(startpos)], None, None)
+    return out
+
+
+def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec, chrom0: int = 0) -> TrackTexts:
+    """The bigWig part of the records whose text track_text_batch_device gives for the same arguments: sections and zoom blocks
+    from the device (dgrp_track_sections_batch, dgrp_track_zoom_batch), deflated there (dgrp_zlib_compress_batch).  chrom0 is
+    the ordinal of the first record in its input: chromIds count from there."""
+    from . import bigwig as bw
+    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+    sizes = [int(sp) + int(n) for sp, n in zip(startposes, lengths)]
+    out = TrackTexts(b"" for _ in spec.classes)
+    for nm, end in zip(raw, sizes):
+        if end > bw.MAX_END:
+            out.bigwig = BigWigWrite(raw, sizes, f"record {nm.decode('utf-8', 'replace')!r} ends at {end}, above 2^32 - 1 = {bw.MAX_END}, "
+                                                 "the largest coordinate of a bigWig")
+            return out
+    args = (d_probs, row0, lengths, startposes, spec.classes, spec.digits, spec.bin, chrom0)
+    level = 1 if spec.gzip_level is None else spec.gzip_level
+    d_sec, _off, d_stab, soff = pipe.track_sections_batch_device(*args)
+    sec_blob, sec_sizes = _zlib_pieces(pipe, d_sec, d_stab, bw.SECTION_DTYPE.itemsize, level)
+    stab = d_stab.cpu().numpy().view(bw.SECTION_DTYPE)
+    del d_sec, d_stab
+    d_zoom, _roff, d_ztab, boff, totals = pipe.track_zoom_batch_device(*args)
+    zoom_blob, zoom_sizes = _zlib_pieces(pipe, d_zoom, d_ztab, bw.ZOOM_BLOCK_DTYPE.itemsize, level)
+    ztab = d_ztab.cpu().numpy().view(bw.ZOOM_BLOCK_DTYPE)
+    del d_zoom, d_ztab
+    sat, zat = np.r_[0, np.cumsum(sec_sizes)], np.r_[0, np.cumsum(zoom_sizes)]
+    writes = []
+    for k in range(len(spec.classes)):
+        a, b = int(soff[k]), int(soff[k + 1])
+        za, zb = int(boff[k * bw.ZOOM_LEVELS]), int(boff[(k + 1) * bw.ZOOM_LEVELS])
+        writes.append(bw.ClassWrite(sec_blob[int(sat[a]):int(sat[b])], sec_sizes[a:b], stab[a:b], zoom_blob[int(zat[za]):int(zat[zb])],
+                                    zoom_sizes[za:zb], ztab[za:zb], tuple(int(x) for x in totals[k])))
+        out[k] = writes[-1].sections
+    out.bigwig = BigWigWrite(raw, sizes, None, writes, chrom0)
+    return out
 
 
 def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec) -> WriteIndex:
@@ -149,9 +232,12 @@ def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec
     return WriteIndex(raw, None, *pipe.track_index_batch_device(d_probs, row0, lengths, startposes, raw, spec.classes, spec.digits, spec.bin))
 
 
-def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec) -> List[bytes]:
+def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec, chrom: int = 0) -> List[bytes]:
     """The track text of every class of `spec` for one record (merged: ContigPipeline.merged of it); with spec.gzip_level its BGZF
-    members instead (no EOF member), deflated on the device piece by piece; with spec.index a TrackTexts with the record's index."""
+    members instead (no EOF member), deflated on the device piece by piece; with spec.index a TrackTexts with the record's index; with
+    spec.bigwig the record's bigwig_write (chrom: its ordinal in the input)."""
+    if spec.bigwig:
+        return bigwig_write(pipe, merged, [0], [len(merged)], [startpos], [name], spec, chrom)
     if spec.gzip_level is None:
         return [pipe.track_text(merged, startpos, name, c, spec.digits, spec.bin) for c in spec.classes]
     from . import gz
@@ -172,12 +258,17 @@ class TrackFiles:
     With spec.gzip_level `write` takes BGZF members and `commit` puts the EOF member behind them.  With spec.index it keeps, per
     class, the file offset of every write and a tabix.IndexBuilder, and `commit` writes `<track>.gz.tbi` the same way.  An input
     whose records cannot be indexed (WriteIndex.refused, a name that reappears after another name, an empty name) gets one warning
-    and no index; its tracks are what they are without the flag."""
+    and no index; its tracks are what they are without the flag.  With spec.bigwig the files are `.bw`, every class has a
+    bigwig.BigWigBuilder on its temporary file, `write` takes TrackTexts with a BigWigWrite, and an input a bigWig cannot hold (an
+    empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and no `.bw` files: `commit` then
+    removes the temporary files and any `.bw` an earlier run left."""
 
     def __init__(self, p: TrackPlan, spec: TrackSpec, filename: str):
         os.makedirs(p.directory, exist_ok=True)
-        self.gzip = spec.gzip_level is not None
-        self.final = [track_path(p.directory, p.bases[filename], c, self.gzip) for c in spec.classes]
+        self.bigwig = bool(spec.bigwig)
+        self.gzip = spec.gzip_level is not None and not self.bigwig
+        self.final = [track_path(p.directory, p.bases[filename], c, self.gzip, self.bigwig) for c in spec.classes]
+        self.bw, self.bw_refused, self.bw_names = None, None, set()
         self.tmp, self.fh = [], []
         self.filename, self.builders = filename, None
         if self.gzip and spec.index:
@@ -190,7 +281,10 @@ class TrackFiles:
             for path in self.final:
                 fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=p.directory)
                 self.tmp.append(tmp)
-                self.fh.append(os.fdopen(fd, "wb"))
+                self.fh.append(os.fdopen(fd, "w+b" if self.bigwig else "wb"))
+            if self.bigwig:
+                from .bigwig import BigWigBuilder
+                self.bw = [BigWigBuilder(fh, spec.digits, spec.bin, p.directory) for fh in self.fh]
         except BaseException:
             self.abort()
             raise
@@ -228,14 +322,56 @@ class TrackFiles:
                     return self._no_index(str(e))
                 self.offs[k] += len(t)
 
+    def _bigwig(self, texts: Sequence[bytes]) -> None:
+        """The write's part of every class's bigWig, or the input's refusal (one warning)."""
+        w = getattr(texts, "bigwig", None)
+        if self.bw_refused is not None or (w is None and not any(texts)):
+            return
+        why = "a write came without its sections" if w is None else w.refused
+        if why is None:
+            for nm in w.names:
+                if not nm:
+                    why = "a record with an empty name"
+                elif nm in self.bw_names:
+                    why = f"two records have the name {nm.decode('utf-8', 'replace')!r}"
+                if why is not None:
+                    break
+                self.bw_names.add(nm)
+        if why is not None:
+            self.bw_refused = why
+            _LOG.warning("%s: no bigWig files are written (--track_bigwig): %s", self.filename, why)
+            return
+        if w.chrom0 is not None and w.chrom0 != len(self.bw[0].names):
+            raise ValueError(f"{self.filename}: a bigWig write of chromId {w.chrom0} arrived as record {len(self.bw[0].names)} of the input")
+        for k, b in enumerate(self.bw):
+            b.add(w.names, w.sizes, None if w.classes is None else w.classes[k])
+
     def write(self, texts: Sequence[bytes]) -> None:
+        if self.bigwig:
+            return self._bigwig(texts)
         for fh, t in zip(self.fh, texts):
             if t:
                 fh.write(t)
         if self.builders is not None:
             self._index(texts)
 
+    def _commit_bigwig(self) -> None:
+        if self.bw_refused is not None:
+            self.abort()
+            for path in self.final:
+                if os.path.exists(path):
+                    os.remove(path)
+            return
+        for b, fh in zip(self.bw, self.fh):
+            b.finish()
+            fh.close()
+        for tmp, path in zip(self.tmp, self.final):
+            os.replace(tmp, path)
+        self.tmp = []
+
     def commit(self) -> None:
+        if self.bigwig:
+            return self._commit_bigwig()
         for fh in self.fh:
             if self.gzip:
                 from .gz import BGZF_EOF
@@ -264,6 +400,8 @@ class TrackFiles:
                 fh.write(index_file(b.payload()))
 
     def abort(self) -> None:
+        for b in self.bw or ():
+            b.close()
         for fh in self.fh:
             fh.close()
         for tmp in self.tmp:

@@ -346,6 +346,72 @@ int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int6
                            int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_chunk_off,
                            int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- bigWig tracks (predict --track_bigwig; deepgrp_amd/bigwig.py states the file format).  The ITEMS of a class are the lines of
+ * the text above without the name: (start, end, q) of every maximal run of bins of equal q != 0 inside one record.  An item's value is
+ * (float)((double)q / 10^digits), the float32 a reader gets from the text's decimal.
+ *
+ * dgrp_track_sections_batch: for the arguments of dgrp_track_text_batch (no names), the items as uncompressed bigWig sections.  A
+ * section is up to 1024 consecutive items of ONE record: 24 bytes of header (chromId u32 = chrom0 + the record's index r in this call,
+ * chromStart u32 = its first item's start, chromEnd u32 = its last item's end, itemStep u32 = 0, itemSpan u32 = 0, type u8 = 1,
+ * reserved u8 = 0, itemCount u16), then itemCount items of (start u32, end u32, value f32), little-endian.  The output is class-major,
+ * sections back to back in the order record, start: d_out[h_class_off[k] : h_class_off[k + 1]] holds those of class h_cls[k], and
+ * d_table[h_section_off[k] : h_section_off[k + 1]] one row for each of them (off: byte offset in d_out, bytes, rec, start, end).
+ * h_class_off and h_section_off (host, ncls + 1 entries each) are always filled in full, also when h_class_off[ncls] > cap or
+ * h_section_off[ncls] > table_cap: then nothing is written, to either, and the caller retries with room for all of it.  d_out is
+ * 4-byte, d_table 8-byte aligned.  chrom0 >= 0 (the records of the file in front of this call).  Limits and refusals are the text
+ * entry's, nrec < 2^31, and a record that ends above 2^32 - 1
+ * (h_startpos[r] + h_n[r] > 4294967295, the largest coordinate of a bigWig) is refused with DGRP_EINVAL before any launch.
+ * Workspace dgrp_track_sections_workspace_bytes (0 on arguments the entry refuses): the text entry's without names, then 24 bytes
+ * per record and class.  Synchronises the stream (at most twice). */
+typedef struct { int64_t off, bytes; int32_t rec; uint32_t start, end, pad; } dgrp_track_section;
+int64_t dgrp_track_sections_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls);
+int dgrp_track_sections_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                              const int64_t *h_startpos, const int *h_cls, int ncls, int digits, int64_t bin, int64_t chrom0, char *d_out,
+                              int64_t cap, int64_t *h_class_off, dgrp_track_section *d_table, int64_t table_cap, int64_t *h_section_off,
+                              void *d_work, int64_t work_bytes, void *stream);
+
+/* dgrp_track_zoom_batch: for the same arguments, the zoom summaries of DGRP_TRACK_ZOOM_LEVELS levels.  Window w of level l of a record
+ * is [w * R, (w + 1) * R) of the record's coordinates, R = 16 * bin * 4^l.  A window with a covered base (a base of a bin with q != 0,
+ * edge bins counting only their bases inside [startpos, startpos + n)) gives one 32-byte record: chromId u32 = chrom0 + r, chromStart u32 = its
+ * first covered base, chromEnd u32 = one past its last, validCount u32 = its covered bases, then as f32 minVal and maxVal = (float)
+ * ((double)q / 10^digits) of the smallest and largest q != 0, sumData = (float)((double)(sum of q * bases) / 10^digits) and sumSquares
+ * = (float)((double)(sum of q * q * bases) / 10^(2 * digits)), the sums exact in uint64.  Level 0 is computed from the bins, level
+ * l + 1 from level l, four windows at a time.  The records of segment s = k * DGRP_TRACK_ZOOM_LEVELS + l (class h_cls[k], level l) are
+ * d_out[32 * h_record_off[s] : 32 * h_record_off[s + 1]], in the order record, window; every 1024 of a segment (the last ones: the
+ * rest) are one BLOCK with one row of d_table[h_block_off[s] : h_block_off[s + 1]]: off (bytes in d_out), bytes, cls = k, level = l,
+ * the first and last record's chromId, the first one's chromStart and the last one's chromEnd.  h_record_off and h_block_off (host,
+ * ncls * DGRP_TRACK_ZOOM_LEVELS + 1 entries each) and h_totals (host, ncls entries: covered bases, smallest and largest q != 0, sum of
+ * q * bases, sum of q * q * bases; all 0 with nothing covered) are always filled in full; when the records exceed cap (bytes) or the
+ * blocks table_cap nothing is written and the caller retries.  d_out is 16-byte, d_table 8-byte aligned; bin <= 2^32.  Otherwise as
+ * dgrp_track_sections_batch.  Workspace dgrp_track_zoom_workspace_bytes: the front's, 80 bytes per record, and 40 bytes per window
+ * of all levels and classes (3.4 bytes per bin and class on long records).  Synchronises the stream (at most twice). */
+#define DGRP_TRACK_ZOOM_LEVELS 10
+typedef struct { int64_t off, bytes; int32_t cls, level, rec0, rec1; uint32_t start, end; } dgrp_track_zoom_block;
+typedef struct { uint64_t covered, qmin, qmax, sum, sumsq; } dgrp_track_totals;
+int64_t dgrp_track_zoom_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls);
+int dgrp_track_zoom_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                          const int64_t *h_startpos, const int *h_cls, int ncls, int digits, int64_t bin, int64_t chrom0, char *d_out,
+                          int64_t cap, int64_t *h_record_off, dgrp_track_zoom_block *d_table, int64_t table_cap, int64_t *h_block_off,
+                          dgrp_track_totals *h_totals, void *d_work, int64_t work_bytes, void *stream);
+
+/* dgrp_zlib_compress_batch: nblk blocks of d_in[0, in_bytes), each as one zlib stream (RFC 1950): 78 01, ONE DEFLATE block from the
+ * encoder of the BGZF entries below at `level` (0: literals, 1: matches; a stored block where that is smaller, so a stream is never
+ * more than 11 bytes longer than its block), and the Adler-32 of the block, big-endian.  Block m is given by row m of a table on the
+ * device: d_rows + m * stride holds int64 offset and int64 length (at most 65280 bytes; the rest of a row is the caller's: the
+ * tables of the two entries above fit).  The streams are written back to back to d_out, d_sizes[m] (device) = the size of stream m,
+ * *h_out_bytes = their total, also when it exceeds out_cap: then nothing is written and DGRP_ENOMEM is returned.  A row that does
+ * not lie in the input or is too long: DGRP_EINVAL, nothing written.  An empty block gives the 11-byte stream of an empty stored
+ * block.  dgrp_zlib_bound(nblk, in_bytes) always suffices; workspace dgrp_zlib_workspace_bytes(nblk, level), 16-byte aligned (a
+ * 65312-byte slot per block, at level 1 four bytes per input byte of a full block more).  The Adler-32 is computed in parallel on
+ * the device.  Synchronises the stream once.  dgrp_zlib_compress_host: the same bytes from host tables, serially. */
+int64_t dgrp_zlib_bound(int64_t nblk, int64_t in_bytes);
+int64_t dgrp_zlib_workspace_bytes(int64_t nblk, int level);
+int dgrp_zlib_compress_batch(const uint8_t *d_in, int64_t in_bytes, const void *d_rows, int64_t stride, int64_t nblk, int level,
+                             uint8_t *d_out, int64_t out_cap, int64_t *d_sizes, int64_t *h_out_bytes, void *d_work, int64_t work_bytes,
+                             void *stream);
+int dgrp_zlib_compress_host(const uint8_t *h_in, int64_t in_bytes, const void *h_rows, int64_t stride, int64_t nblk, int level,
+                            uint8_t *h_out, int64_t out_cap, int64_t *h_sizes, int64_t *h_out_bytes);
+
 /* ---- A3-A11 in one call: everything deepgrp/__main__.py:46-83 and :288-292 do for ONE record whose class indices
  * (after N stripping, startpos = offset) are in HBM: windows, forward, max-merge with the reference's placement for
  * `batch`, then scores + MSS labels (use_mss != 0; deepgrp/prediction.py:40-59) or softmax + argmax
