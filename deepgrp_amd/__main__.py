@@ -14,6 +14,8 @@ Differences, all additive:
     (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well) and with --track_index a tabix index beside
     every BGZF track (deepgrp_amd/tabix.py); with --track_bigwig the tracks are bigWig files instead (`.bw`, deepgrp_amd/bigwig.py:
     binary sections and zoom levels written and deflated on the GPU);
+  * `predict --bed_dir DIR [--bed_min_score S]` also writes the predicted repeats of every input as a scored BED file: per row the
+    mean and the smallest probability of its class and the share of its bases that carry it, summed on the GPU (deepgrp_amd/bed.py);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
@@ -172,6 +174,18 @@ def _add_track_options(parser) -> None:
                              "(default: 1)")
 
 
+def _add_bed_options(parser) -> None:
+    """The scored-BED flags, like the track flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--bed_dir", type=str, default=s,
+                        help="(addition) also write the predicted repeats of every input as BED, DIR/<basename of the input>.bed ('stdin' "
+                             "for '-'): name, start, end, class<label>, score 0..1000, '.', then the mean and the smallest merged "
+                             "probability of the row's class over its bases and the share of its bases at which that class is the "
+                             "largest, four decimals each; summed on the GPU; one process only")
+    parser.add_argument("--bed_min_score", type=int, default=s,
+                        help="(addition) with --bed_dir: leave out BED lines whose score is below this, 0..1000 (the TSV is not filtered)")
+
+
 class CommandLineParser:
     """Commandline parser (deepgrp/__main__.py:86-250)."""
 
@@ -197,6 +211,7 @@ class CommandLineParser:
         self.parser.add_argument("-v", "--verbose", action="count", default=0, help="Increase verbosity")
         _add_mask_options(self.parser, suppress=True)
         _add_track_options(self.parser)
+        _add_bed_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (not available in deepgrp_amd)")
         train.add_argument("parameter", type=str)
@@ -231,6 +246,7 @@ class CommandLineParser:
                                   "records) instead of sharding whole records")
         _add_mask_options(predict, suppress=True)
         _add_track_options(predict)
+        _add_bed_options(predict)
         evaluate = subparsers.add_parser(
             name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
             description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
@@ -261,7 +277,7 @@ class CommandLineParser:
         if not any(a in ("predict", "train", "verify", "evaluate") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
-                           "--track_digits", "--track_bin", "--gzip_level"}
+                           "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -296,8 +312,10 @@ class CommandLineParser:
     @staticmethod
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
+        from . import bed
         from . import tracks as tk
         tk.check_gzip_flags(args)                               # refusals come before anything runs
+        bed_plan = bed.plan(args)
         masks = CommandLineParser._mask_plan(args)
         track_plan = tk.plan(args)
         track_spec = None
@@ -358,7 +376,12 @@ class CommandLineParser:
                     _LOG.info("Processing %s", filename)
                     t_file, bases = time.perf_counter(), 0
                     kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
-                    if track_spec is not None:
+                    if bed_plan is not None:
+                        # --bed_dir: as --track_dir below, and the rows' scores from the same merged array (tracks or not)
+                        bases = CommandLineParser._predict_scored(pipe, runner, filename, records_of(filename), outstream, kept,
+                                                                  tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None,
+                                                                  track_spec, bed_plan)
+                    elif track_spec is not None:
                         # --track_dir: short records as batches (rows and track texts of a batch in two calls), the others one by one
                         # (merged -> tracks -> labels -> segments); the input's track files are renamed into place when all of its
                         # records are done, and removed when one raises
@@ -491,10 +514,67 @@ class CommandLineParser:
         return bases
 
     @staticmethod
-    def _predict_staged(pipe, header, rec, track_sink=None):
+    def _predict_scored(pipe, runner, filename, records, outstream, kept, files, spec, bed_plan) -> int:
+        """predict's loop over one input with --bed_dir: TSV rows as without it, every row's BED line to the input's bed.BedFiles and,
+        with --track_dir as well (`files`, `spec`; else None), the track texts from the same merged array.  -> bases read"""
+        from .bed import BedFiles
+        from .evaluation import record_name
+        from .runner import rows_text, rows_text_batch
+        from .tracks import record_texts
+        try:
+            beds = BedFiles(bed_plan, filename)
+        except BaseException:
+            if files is not None:
+                files.abort()
+            raise
+        try:
+            if _LOG.isEnabledFor(logging.DEBUG):
+                bases = 0
+                for chrom, (header, rec) in enumerate(records):
+                    name = record_name(filename, header)
+                    sink = None
+                    if files is not None:
+                        sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec, chrom))
+                    scored = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
+                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, sink, scored)
+                    if n == 0 and files is not None and spec.bigwig:    # no base to predict: still a chromosome of the bigWig
+                        from .pipeline import record_indices
+                        from .tracks import empty_texts
+                        files.write(empty_texts(spec, name, record_indices(rec)[0]))
+                    bases += n
+                    outstream.write(rows_text(filename, header, rows))
+                    if kept is not None:
+                        kept.add(rows, 1)
+            else:
+                keyed = (((header, record_name(filename, header)), rec) for header, rec in records)
+                for kind, key, rows, scores, texts in runner.scored_results(CommandLineParser._counted(keyed, lambda n: None)):
+                    if kind == "batch":
+                        outstream.write(rows_text_batch(filename, [header for header, _name in key], rows))
+                        beds.write([name for _header, name in key], True, rows, scores)
+                    else:
+                        outstream.write(rows_text(filename, key[0], rows))
+                        beds.write([key[1]], False, rows, scores)
+                    if files is not None:
+                        files.write(texts)
+                    if kept is not None:
+                        kept.add(rows, len(key) if kind == "batch" else 1)
+                bases = CommandLineParser._last_count
+        except BaseException:
+            beds.abort()
+            if files is not None:
+                files.abort()
+            raise
+        if files is not None:
+            files.commit()
+        beds.commit()
+        return bases
+
+    @staticmethod
+    def _predict_staged(pipe, header, rec, track_sink=None, score_sink=None):
         """One record through encode -> forward + merge -> scores / MSS / vote (or softmax) -> segments, each stage between device
         syncs, with the reference's debug lines (deepgrp/__main__.py:69-79) carrying the stage's milliseconds.  -> (rows, bases)
-        track_sink(merged, startpos), if given, runs between the forward pass and the labels (--track_dir)."""
+        track_sink(merged, startpos), if given, runs between the forward pass and the labels (--track_dir); score_sink(merged,
+        startpos, rows) behind the segments (--bed_dir)."""
         import time
 
         import torch
@@ -528,6 +608,10 @@ class CommandLineParser:
         t = time.perf_counter()
         rows = pipe.segments(labels, startpos)
         ms_seg = lap(t)
+        if score_sink is not None:
+            t = time.perf_counter()
+            score_sink(merged, startpos, rows)
+            _LOG.debug("%s: row scores %.2f ms", header, lap(t))
         _LOG.debug("%s: %d bases; encode %.2f ms, forward + merge %.2f ms (%.1f Mbp/s), %s %.2f ms, segments + read-back %.2f ms, %d rows",
                    header, n, ms_enc, ms_fwd, n / max(ms_fwd, 1e-6) / 1e3, "scores + MSS + vote" if pipe.use_mss else "softmax", ms_post,
                    ms_seg, len(rows))
@@ -741,6 +825,8 @@ class CommandLineParser:
             sys.exit("--track_dir belongs to predict, not evaluate")
         if getattr(args, "gzip_level", None) is not None:
             sys.exit("--gzip_level belongs to predict, not evaluate")
+        from .bed import refuse_on_evaluate
+        refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
         import json

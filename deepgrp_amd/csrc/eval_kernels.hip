@@ -144,12 +144,12 @@ __device__ __forceinline__ int64_t eval_row_of(const uint64_t *__restrict__ ex, 
     return lo;
 }
 
-// one lane per row: 0 <= start <= end and 1 <= label <= 127, else g[0] |= 1 and g[1] = smallest bad row; tot[label] += clipped length
+// one lane per row: 0 <= start <= end and 1 <= label <= max_label (at most 127), else g[0] |= 1 and g[1] = smallest bad row; tot[label] += clipped length
 // (summed per workgroup in LDS first: a handful of labels would otherwise serialise one global atomic per row)
 __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__restrict__ rows, const int64_t *__restrict__ row_off,
                                                          int64_t nrec, const int64_t *__restrict__ len,
-                                                         const int64_t *__restrict__ origin, unsigned long long *__restrict__ g,
-                                                         unsigned long long *__restrict__ tot)
+                                                         const int64_t *__restrict__ origin, int max_label,
+                                                         unsigned long long *__restrict__ g, unsigned long long *__restrict__ tot)
 {
     __shared__ unsigned long long s_tot[128];
     if (threadIdx.x < 128) s_tot[threadIdx.x] = 0ull;
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__r
     const int64_t i = row_off[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < row_off[nrec]) {
         const dgrp_segment q = rows[i];
-        if (q.start < 0 || q.end < q.start || q.label < 1 || q.label > 127) {
+        if (q.start < 0 || q.end < q.start || q.label < 1 || q.label > max_label) {
             atomicOr(&g[0], 1ull);
             atomicMin(&g[1], (unsigned long long)i);
         } else {
@@ -265,7 +265,7 @@ struct eval_plan {
 // argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written
 static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
                         const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes,
-                        hipStream_t stream, eval_plan &pl)
+                        hipStream_t stream, eval_plan &pl, int max_label = 127)
 {
     DGRP_REQUIRE(nrec >= 0 && h_row_off && (nrec == 0 || (h_off && h_len && h_origin)), "%s: bad arguments", what);
     DGRP_REQUIRE(h_row_off[0] >= 0, "%s: negative row offset", what);
@@ -305,7 +305,7 @@ static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, co
     DGRP_HIP(hipMemsetAsync(d_tot, 0, 128 * 8, stream));
     DGRP_HIP(hipMemcpyAsync(pl.d_off, pl.tab.data(), pl.tab.size() * 8, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(eval_check_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
-                       pl.d_len, pl.d_origin, g, d_tot);
+                       pl.d_len, pl.d_origin, max_label, g, d_tot);
     DGRP_LAUNCH_CHECK();
     unsigned long long hg[2];
     DGRP_HIP(hipMemcpyAsync(hg, g, sizeof(hg), hipMemcpyDeviceToHost, stream));
@@ -315,8 +315,8 @@ static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, co
         const int64_t i = (int64_t)hg[1];
         dgrp_segment q;
         DGRP_HIP(hipMemcpy(&q, d_rows + i, sizeof(q), hipMemcpyDeviceToHost));
-        DGRP_REQUIRE(false, "%s: row %lld [%lld, %lld) label %d: rows need 0 <= start <= end and 1 <= label <= 127", what, (long long)i,
-                     (long long)q.start, (long long)q.end, (int)q.label);
+        DGRP_REQUIRE(false, "%s: row %lld [%lld, %lld) label %d: rows need 0 <= start <= end and 1 <= label <= %d", what, (long long)i,
+                     (long long)q.start, (long long)q.end, (int)q.label, max_label);
     }
     return DGRP_OK;
 }
@@ -380,6 +380,166 @@ DGRP_EXPORT int dgrp_row_hits_batch(const int8_t *d_labels, int64_t nrec, const 
     if (e != DGRP_OK) return e;
     hipLaunchKernelGGL(eval_hits_kernel, dim3((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE)), dim3(256), 0, stream, d_labels,
                        pl.d_cl, pl.d_dst, d_rows + r0, pl.nrows, reinterpret_cast<unsigned long long *>(d_hits + r0));
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// predict --bed_dir: per-row statistics of the row's label column of the merged probabilities [*, C] over its clipped span, as exact
+// integers (include/deepgrp_hip.h states them).  The same line of positions as the hits above: workgroup b takes positions
+// [b * EVAL_SLICE, (b + 1) * EVAL_SLICE) of the scanned clipped lengths, lane-interleaved, so the 64 lanes of a wave read 64
+// consecutive rows of the array -- 64 * C * 4 contiguous bytes -- and every lane reads its row whole.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// q(p): p * 2^24 rounded half up, clamped to [0, 2^24].  The product is exact in double; so is x + 0.5 except below 2^-30, where
+// it stays under 1 and the floor is 0 either way.
+__device__ __forceinline__ uint32_t score_q(float p)
+{
+    if (!(p > 0.0f)) return 0u;
+    const double x = (double)p * 16777216.0;
+    if (x >= 16777216.0) return 16777216u;
+    return (uint32_t)floor(x + 0.5);
+}
+
+// one lane per row j, after the scan: bases = its clipped length, qmin = the identity of the minimum when it has bases, the rest 0
+__global__ void __launch_bounds__(256) score_init_kernel(const uint64_t *__restrict__ ex, int64_t n, dgrp_row_score *__restrict__ sc)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t cl = ex[j + 1] - ex[j];
+    dgrp_row_score v;
+    v.sum = 0;
+    v.bases = (int64_t)cl;
+    v.agree = 0;
+    v.qmin = cl ? 0xffffffffu : 0u;
+    v.pad = 0;
+    sc[j] = v;
+}
+
+struct score_acc {
+    unsigned long long sum;
+    unsigned agree, qmin;
+};
+
+// CT: the class count at compile time (0: the runtime value) -- the row's loads are then issued together
+template <int CT>
+__global__ void __launch_bounds__(256) score_rows_kernel(const float *__restrict__ probs, int Crt, const uint64_t *__restrict__ ex,
+                                                         const int64_t *__restrict__ dst, const dgrp_segment *__restrict__ rows,
+                                                         int64_t n, dgrp_row_score *__restrict__ sc)
+{
+    __shared__ unsigned long long s_sum[EVAL_LDS_ROWS];
+    __shared__ unsigned s_agree[EVAL_LDS_ROWS], s_min[EVAL_LDS_ROWS];
+    __shared__ int64_t s_r0, s_r1;
+    const int C = CT ? CT : Crt;
+    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
+    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;    // (s0 < total: the grid covers the line exactly)
+    if (threadIdx.x == 0) {
+        s_r0 = eval_row_of(ex, 0, n, s0);
+        s_r1 = eval_row_of(ex, s_r0, n, s1 - 1);
+    }
+    for (int k = threadIdx.x; k < EVAL_LDS_ROWS; k += 256) {
+        s_sum[k] = 0ull;
+        s_agree[k] = 0u;
+        s_min[k] = 0xffffffffu;
+    }
+    __syncthreads();
+    const int64_t r0 = s_r0, r1 = s_r1;
+    const bool staged = r1 - r0 < EVAL_LDS_ROWS;
+    auto flush = [&](int64_t j, const score_acc &a) {
+        if (staged) {
+            atomicAdd(&s_sum[j - r0], a.sum);
+            if (a.agree) atomicAdd(&s_agree[j - r0], a.agree);
+            atomicMin(&s_min[j - r0], a.qmin);
+        } else {
+            atomicAdd(reinterpret_cast<unsigned long long *>(&sc[j].sum), a.sum);
+            if (a.agree) atomicAdd(reinterpret_cast<unsigned long long *>(&sc[j].agree), (unsigned long long)a.agree);
+            atomicMin(&sc[j].qmin, a.qmin);
+        }
+    };
+    const uint64_t p0 = s0 + threadIdx.x;
+    if (p0 < s1) {
+        int64_t j = eval_row_of(ex, r0, r1 + 1, p0);
+        uint64_t jst = ex[j], jend = ex[j + 1];
+        int lab = rows[j].label;
+        score_acc a = { 0ull, 0u, 0xffffffffu };
+        bool any = false;
+        for (uint64_t p = p0; p < s1; p += 256) {
+            if (jend <= p) {
+                if (any) flush(j, a);
+                a = { 0ull, 0u, 0xffffffffu };
+                any = false;
+                while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
+                lab = rows[j].label;
+            }
+            const float *__restrict__ row = probs + (dst[j] + (int64_t)(p - jst)) * C;
+            float vbest = row[0], vlab = vbest;
+            int best = 0;
+#pragma unroll
+            for (int c = 1; c < C; ++c) {
+                const float v = row[c];
+                if (c == lab) vlab = v;
+                if (v > vbest) { vbest = v; best = c; }
+            }
+            const uint32_t q = score_q(vlab);
+            a.sum += q;
+            a.agree += best == lab ? 1u : 0u;
+            a.qmin = q < a.qmin ? q : a.qmin;
+            any = true;
+        }
+        if (any) flush(j, a);
+    }
+    __syncthreads();
+    if (staged) {
+        for (int64_t k = threadIdx.x; k <= r1 - r0; k += 256) {
+            const unsigned m = s_min[k];
+            if (m == 0xffffffffu) continue;                                   // no position of this row in the slice (q <= 2^24)
+            atomicAdd(reinterpret_cast<unsigned long long *>(&sc[r0 + k].sum), s_sum[k]);
+            if (s_agree[k]) atomicAdd(reinterpret_cast<unsigned long long *>(&sc[r0 + k].agree), (unsigned long long)s_agree[k]);
+            atomicMin(&sc[r0 + k].qmin, m);
+        }
+    }
+}
+
+}   // namespace
+
+DGRP_EXPORT int64_t dgrp_row_scores_workspace_bytes(int64_t nrec, int64_t nrows)
+{
+    return dgrp_eval_workspace_bytes(nrec, nrows);
+}
+
+DGRP_EXPORT int dgrp_row_scores_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                      const int64_t *h_startpos, const dgrp_segment *d_rows, const int64_t *h_row_off,
+                                      dgrp_row_score *d_scores, void *d_work, int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    static_assert(sizeof(dgrp_row_score) == 32, "dgrp_row_score is 32 bytes");
+    DGRP_REQUIRE(C >= 2 && C <= DGRP_MAXC, "dgrp_row_scores_batch: 2 <= classes <= 64");
+    DGRP_REQUIRE(nrec >= 0 && (nrec == 0 || h_n), "dgrp_row_scores_batch: bad arguments");
+    for (int64_t r = 0; r < nrec; ++r)
+        DGRP_REQUIRE(h_n[r] >= 1, "dgrp_row_scores_batch: record %lld has no row of probabilities", (long long)r);
+    eval_plan pl;
+    const int rc = eval_prepare("dgrp_row_scores_batch", nrec, h_row0, h_n, h_startpos, d_rows, h_row_off, d_work, work_bytes, stream, pl,
+                                C - 1);
+    if (rc != DGRP_OK || pl.nrows == 0 || nrec == 0) return rc;
+    DGRP_REQUIRE(d_scores, "dgrp_row_scores_batch: NULL pointer");
+    const int64_t r0 = h_row_off[0];
+    uint64_t total = 0;
+    for (int k = 1; k < C; ++k) total += pl.tot[k];
+    if (total == 0) {
+        DGRP_HIP(hipMemsetAsync(d_scores + r0, 0, pl.nrows * sizeof(dgrp_row_score), stream));
+        return DGRP_OK;
+    }
+    DGRP_REQUIRE(d_probs, "dgrp_row_scores_batch: NULL pointer");
+    const int e = eval_spans(pl, d_rows, nrec, 0, stream);
+    if (e != DGRP_OK) return e;
+    hipLaunchKernelGGL(score_init_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, pl.d_cl, pl.nrows, d_scores + r0);
+    DGRP_LAUNCH_CHECK();
+    const dim3 grid((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE));
+    if (C == 5)
+        hipLaunchKernelGGL(score_rows_kernel<5>, grid, dim3(256), 0, stream, d_probs, C, pl.d_cl, pl.d_dst, d_rows + r0, pl.nrows, d_scores + r0);
+    else
+        hipLaunchKernelGGL(score_rows_kernel<0>, grid, dim3(256), 0, stream, d_probs, C, pl.d_cl, pl.d_dst, d_rows + r0, pl.nrows, d_scores + r0);
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
 }

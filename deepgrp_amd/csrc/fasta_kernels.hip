@@ -439,3 +439,73 @@ DGRP_EXPORT int dgrp_format_rows(const char *prefixes, const int64_t *prefix_off
     return DGRP_OK;
 }
 
+// The scored rows of predict --bed_dir as BED text: "name\tstart\tend\tclass<label>\tscore\t.\tmean\tmin\tagree\n" per row, every
+// figure an integer rounded half up, R(num, den, k) = floor((2 k num + den) / (2 den)), in 128 bits (2 k sum passes 64).
+typedef unsigned __int128 u128;
+
+static inline uint64_t bed_round(u128 num, u128 den, uint64_t k)
+{
+    return (uint64_t)((2 * (u128)k * num + den) / (2 * den));
+}
+
+static inline char *put_fixed4(char *o, uint64_t v)          // v / 10^4 as "d.dddd"
+{
+    o = put_int(o, (long long)(v / 10000));
+    *o++ = '.';
+    const unsigned f = (unsigned)(v % 10000);
+    *o++ = (char)('0' + f / 1000);
+    *o++ = (char)('0' + f / 100 % 10);
+    *o++ = (char)('0' + f / 10 % 10);
+    *o++ = (char)('0' + f % 10);
+    return o;
+}
+
+DGRP_EXPORT int64_t dgrp_format_bed_bound(int64_t nrows, int64_t longest_name)
+{
+    if (nrows < 0 || longest_name < 0) return 0;
+    // name, two coordinates, "class" + label, score, ".", three figures of at most 20 + 5 characters, nine separators
+    return nrows * (longest_name + 21 + 21 + 5 + 12 + 21 + 1 + 3 * 26 + 9) + 1;
+}
+
+DGRP_EXPORT int dgrp_format_bed_rows(const char *names, const int64_t *name_off, int64_t nnames, int by_contig,
+                                     const dgrp_segment *rows, const dgrp_row_score *scores, int64_t nrows, int min_score,
+                                     char *out, int64_t cap, int64_t *written)
+{
+    DGRP_REQUIRE(nrows >= 0 && nnames >= 1 && names && name_off && written && (nrows == 0 || (rows && scores && out)),
+                 "dgrp_format_bed_rows: bad arguments");
+    int64_t longest = 0;
+    for (int64_t i = 0; i < nnames; ++i) {
+        DGRP_REQUIRE(name_off[i + 1] >= name_off[i], "dgrp_format_bed_rows: name offsets must ascend");
+        if (name_off[i + 1] - name_off[i] > longest) longest = name_off[i + 1] - name_off[i];
+    }
+    if (cap < dgrp_format_bed_bound(nrows, longest)) {
+        dgrp_set_error("dgrp_format_bed_rows: output buffer too small (dgrp_format_bed_bound)");
+        return DGRP_ENOMEM;
+    }
+    char *o = out;
+    for (int64_t r = 0; r < nrows; ++r) {
+        const int64_t c = by_contig ? rows[r].contig : 0;
+        DGRP_REQUIRE(c >= 0 && c < nnames, "dgrp_format_bed_rows: row %lld names record %lld of %lld", (long long)r, (long long)c, (long long)nnames);
+        const dgrp_row_score &sc = scores[r];
+        DGRP_REQUIRE(sc.bases > 0, "dgrp_format_bed_rows: row %lld has no scored base", (long long)r);
+        const u128 den = (u128)(uint64_t)sc.bases << 24;
+        const uint64_t score = bed_round(sc.sum, den, 1000);
+        if (score < (uint64_t)(min_score < 0 ? 0 : min_score)) continue;
+        const int64_t len = name_off[c + 1] - name_off[c];
+        memcpy(o, names + name_off[c], (size_t)len);
+        o += len;
+        *o++ = '\t';
+        o = put_int(o, rows[r].start); *o++ = '\t';
+        o = put_int(o, rows[r].end); *o++ = '\t';
+        memcpy(o, "class", 5);
+        o = put_int(o + 5, rows[r].label); *o++ = '\t';
+        o = put_int(o, (long long)score); *o++ = '\t';
+        *o++ = '.'; *o++ = '\t';
+        o = put_fixed4(o, bed_round(sc.sum, den, 10000)); *o++ = '\t';
+        o = put_fixed4(o, bed_round(sc.qmin, (u128)1 << 24, 10000)); *o++ = '\t';
+        o = put_fixed4(o, bed_round((u128)(uint64_t)sc.agree, (u128)(uint64_t)sc.bases, 10000)); *o++ = '\n';
+    }
+    *written = o - out;
+    return DGRP_OK;
+}
+

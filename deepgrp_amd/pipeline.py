@@ -21,6 +21,8 @@ from ._lib import check, lib
 from .fasta import DeviceRecord
 
 SEGMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")])
+# struct dgrp_row_score (predict --bed_dir): exact integer statistics of a row's label column over its clipped span
+ROW_SCORE_DTYPE = np.dtype([("sum", "<u8"), ("bases", "<i8"), ("agree", "<i8"), ("qmin", "<u4"), ("pad", "<u4")])
 
 
 def require_gpu() -> torch.device:
@@ -709,9 +711,13 @@ class ContigPipeline:
         rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
         row0 = np.zeros(nrec, np.int64)
         np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
+        return rows, self.batch_track_texts(d_probs, row0, ln, startposes, names, spec, chrom0)
+
+    def batch_track_texts(self, d_probs: torch.Tensor, row0, ln, startposes, names, spec, chrom0: int = 0):
+        """The `texts` of run_batch_tracked from a batch's merged probabilities (record r at rows [row0[r], row0[r] + ln[r]))."""
         if spec.bigwig:                                      # --track_bigwig: sections and zoom blocks instead of text
             from .tracks import bigwig_write
-            return rows, bigwig_write(self, d_probs, row0, ln, startposes, names, spec, chrom0)
+            return bigwig_write(self, d_probs, row0, ln, startposes, names, spec, chrom0)
         d_text, off = self.track_text_batch_device(d_probs, row0, ln, startposes, names, spec.classes, spec.digits, spec.bin)
         index = None
         if spec.gzip_level is not None and spec.index:
@@ -720,7 +726,7 @@ class ContigPipeline:
         del d_probs
         if spec.gzip_level is None:
             host = d_text.cpu().numpy()
-            return rows, [host[off[k]:off[k + 1]].tobytes() for k in range(len(spec.classes))]
+            return [host[off[k]:off[k + 1]].tobytes() for k in range(len(spec.classes))]
         from . import gz
         from .tracks import GZIP_PIECE, TrackTexts
         texts = TrackTexts()
@@ -729,7 +735,66 @@ class ContigPipeline:
             pieces = [gz.bgzf_compress_device(d_text[o:min(o + GZIP_PIECE, int(off[k + 1]))], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
                       for o in range(int(off[k]), int(off[k + 1]), GZIP_PIECE)]
             texts.append(b"".join(pieces))
-        return rows, texts
+        return texts
+
+    # predict --bed_dir
+    def row_scores_batch(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off) -> np.ndarray:
+        """The scores (ROW_SCORE_DTYPE, one per row) of the segment rows of many records in one dgrp_row_scores_batch call: record r
+        is rows [row0[r], row0[r] + lengths[r]) of `d_probs` (float32 [*, C]), its first row has coordinate startposes[r], and its
+        segment rows are rows[row_off[r]:row_off[r + 1]] (SEGMENT_DTYPE, original coordinates, clipped to the record)."""
+        L = lib()
+        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
+            raise ValueError("row_scores_batch takes a contiguous float32 [rows, C] array")
+        rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+        r0 = np.ascontiguousarray(row0, np.int64)
+        ln = np.ascontiguousarray(lengths, np.int64)
+        sp = np.ascontiguousarray(startposes, np.int64)
+        ro = np.ascontiguousarray(row_off, np.int64)
+        nrec = len(ln)
+        if len(ro) != nrec + 1 or len(r0) != nrec or len(sp) != nrec or (nrec and int(ro[-1]) > len(rows)):
+            raise ValueError("row_scores_batch: tables of different lengths, or row offsets beyond the rows")
+        if nrec and int((r0 + ln).max()) > d_probs.shape[0]:
+            raise ValueError("row_scores_batch: a record lies beyond the probability array")
+        out = np.zeros(len(rows), ROW_SCORE_DTYPE)
+        if nrec == 0 or len(rows) == 0:
+            return out
+        dev = d_probs.device
+        d_rows = torch.from_numpy(rows.view(np.uint8)).to(dev)
+        d_scores = torch.zeros(len(rows) * ROW_SCORE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        wb = int(L.dgrp_row_scores_workspace_bytes(nrec, int(ro[-1] - ro[0])))
+        work = torch.empty(max(wb, 256), dtype=torch.uint8, device=dev)
+        check(L.dgrp_row_scores_batch(_ptr(d_probs), int(d_probs.shape[1]), nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data,
+                                      _ptr(d_rows), ro.ctypes.data, _ptr(d_scores), _ptr(work), work.numel(), stream_ptr()),
+              "dgrp_row_scores_batch")
+        return d_scores.cpu().numpy().view(ROW_SCORE_DTYPE).copy()
+
+    def row_scores(self, merged: torch.Tensor, startpos: int, rows: np.ndarray) -> np.ndarray:
+        """The scores of one record's segment rows against its merged probabilities (ContigPipeline.merged): row i of `merged` has
+        coordinate startpos + i."""
+        if len(rows) == 0 or len(merged) == 0:
+            return np.zeros(len(rows), ROW_SCORE_DTYPE)
+        return self.row_scores_batch(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)])
+
+    def run_batch_scored(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs):
+        """run_batch with the rows' scores: one dgrp_predict_batch_probs call, then one dgrp_row_scores_batch call on its merged
+        probabilities.  -> (rows, scores, d_probs, row0): the probabilities [dgrp_batch_rows, C] stay on the device for a caller that
+        also writes tracks from them; record r starts at row row0[r].  `contigs` must ascend with the records (rows come back in
+        record order: the row offsets are the running count of rows["contig"])."""
+        L = lib()
+        nrec = len(lengths)
+        ln = np.ascontiguousarray(lengths, np.int64)
+        row0 = np.zeros(nrec, np.int64)
+        if nrec == 0:
+            return np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE), None, row0
+        total = int(L.dgrp_batch_rows(nrec, ln.ctypes.data))
+        d_probs = torch.empty((total, self.model.classes), dtype=torch.float32, device=d_base.device)
+        rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
+        np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
+        cg = np.ascontiguousarray(contigs, np.int64)
+        if nrec > 1 and not (np.diff(cg) > 0).all():
+            raise ValueError("run_batch_scored: contigs must ascend with the records")
+        row_off = np.searchsorted(rows["contig"], np.r_[cg, cg[-1] + 1], side="left").astype(np.int64)
+        return rows, self.row_scores_batch(d_probs, row0, ln, startposes, rows, row_off), d_probs, row0
 
     def run(self, sequence, contig: int = 0) -> np.ndarray:
         startpos, d_idx = record_indices(sequence)

@@ -29,6 +29,18 @@ class _TrackedBatch(list):
     chrom0 = 0
 
 
+class _Scored(NamedTuple):
+    """A work item of scored_results: one record, the name of its BED (and track) lines, its ordinal in the input."""
+    name: str
+    rec: object
+    chrom: int = 0
+
+
+class _ScoredBatch(list):
+    """A batch work item of scored_results, as _TrackedBatch."""
+    chrom0 = 0
+
+
 _BATCH = object()             # key slot of a work item that is a batch of records (never equal to a user's key, e.g. a header "batch")
 SMALL_RECORD = 1 << 18        # bases: up to here a record may join a batch
 BATCH_RECORDS = 4096
@@ -88,7 +100,7 @@ class RecordRunner:
 
     def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None):
         self.pipe = pipe
-        self.tracks = tracks          # tracks.TrackSpec: every record's track text comes with its rows (tracked_results)
+        self.tracks = tracks          # tracks.TrackSpec: every record's track text comes with its rows (tracked_results, scored_results)
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
@@ -111,6 +123,20 @@ class RecordRunner:
         merged = self.pipe.merged(d_idx)
         texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom)
         return self.pipe.segments(self.pipe.labels(merged), startpos), texts
+
+    def run_scored(self, rec, name: str, chrom: int = 0):
+        """(rows, scores, track texts or None) of one record: merged -> [the texts of self.tracks] -> labels -> segments -> the rows'
+        scores (ContigPipeline.row_scores) from the same merged array."""
+        from .pipeline import ROW_SCORE_DTYPE, SEGMENT_DTYPE
+        from .tracks import empty_texts, record_texts
+        startpos, d_idx = record_indices(rec)
+        if d_idx.numel() == 0:
+            texts = empty_texts(self.tracks, name, startpos) if self.tracks is not None else None
+            return np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE), texts
+        merged = self.pipe.merged(d_idx)
+        texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
+        rows = self.pipe.segments(self.pipe.labels(merged), startpos)
+        return rows, self.pipe.row_scores(merged, startpos, rows), texts
 
     # ---- batching
     def _batch_cost(self, n: int) -> int:
@@ -157,6 +183,17 @@ class RecordRunner:
                                                       [r.startpos for _k, r in item], list(range(len(item))),
                                                       [k[1] for k, _r in item], self.tracks, *((item.chrom0,) if self.tracks.bigwig else ()))
             return [k for k, _r in item], rows, texts
+        if isinstance(item, _Scored):
+            return self.run_scored(item.rec, item.name, item.chrom)
+        if isinstance(item, _ScoredBatch):                # rows, their scores and (with tracks) the texts from one merged array
+            lengths, startposes = [r.length for _k, r in item], [r.startpos for _k, r in item]
+            rows, scores, d_probs, row0 = self.pipe.run_batch_scored(item[0][1].base, [r.offset for _k, r in item], lengths, startposes,
+                                                                     list(range(len(item))))
+            texts = None
+            if self.tracks is not None:
+                texts = self.pipe.batch_track_texts(d_probs, row0, np.ascontiguousarray(lengths, np.int64), startposes,
+                                                    [k[1] for k, _r in item], self.tracks, item.chrom0 if self.tracks.bigwig else 0)
+            return [k for k, _r in item], rows, scores, texts
         if isinstance(item, list):                        # a batch: rows of all its records, contig = position in the batch
             rows = self.pipe.run_batch(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
                                        [r.startpos for _k, r in item], list(range(len(item))))
@@ -166,7 +203,7 @@ class RecordRunner:
     # ---- ordered execution
     @staticmethod
     def _size(item) -> int:
-        if isinstance(item, _Tracked):
+        if isinstance(item, (_Tracked, _Scored)):
             item = item.rec
         if isinstance(item, list):
             return sum(r.length for _k, r in item)
@@ -238,3 +275,26 @@ class RecordRunner:
             else:
                 rows, texts = result
                 yield "one", key, rows, texts
+
+    def scored_results(self, records: Iterable[Tuple[object, object]]):
+        """tracked_results with the rows' scores (predict --bed_dir), self.tracks or not: ("one", key, rows, scores, texts) and
+        ("batch", [keys], rows, scores, texts); scores (pipeline.ROW_SCORE_DTYPE) go row by row with `rows`, texts is None without
+        self.tracks.  Records batch exactly when they do without scores."""
+        def items():
+            chrom = 0
+            for key, item in self.work_items(records):
+                if key is _BATCH:
+                    batch = _ScoredBatch(item)
+                    batch.chrom0 = chrom
+                    chrom += len(item)
+                    yield _BATCH, batch
+                else:
+                    yield key, _Scored(key[1], item, chrom)
+                    chrom += 1
+        for key, result in self.in_order(items()):
+            if key is _BATCH:
+                keys, rows, scores, texts = result
+                yield "batch", keys, rows, scores, texts
+            else:
+                rows, scores, texts = result
+                yield "one", key, rows, scores, texts

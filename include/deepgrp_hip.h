@@ -475,6 +475,42 @@ int dgrp_row_hits_batch(const int8_t *d_labels, int64_t nrec, const int64_t *h_o
                         const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_hits, void *d_work, int64_t work_bytes,
                         void *stream);
 
+/* ---- scored rows (an addition, predict --bed_dir; the reference reports no confidence per element): for every row, exact integer
+ * statistics of its label's column of the merged probabilities over its clipped span.
+ * Records as for dgrp_track_text_batch: record r is rows [h_row0[r], h_row0[r] + h_n[r]) of d_probs [*, C] float32 (device; the rows
+ * of dgrp_predict_batch_probs, or one record at row 0), its row i has the coordinate h_startpos[r] + i.  Rows as for
+ * dgrp_row_hits_batch: record r's rows are d_rows[h_row_off[r] .. h_row_off[r+1]) (device), in ORIGINAL coordinates, in any order,
+ * overlapping or not, each clipped to its record.  d_scores[i] is written for i in [h_row_off[0], h_row_off[nrec]), nothing else is.
+ * The fixed-point value q(p) of a float32 p: 0 when !(p > 0) (NaN, zero, negatives); else with x = (double)p * 2^24, 2^24 when
+ * x >= 2^24, else (uint32_t)floor(x + 0.5) (exact in double).  With L the row's label, over the `bases` rows i of its clipped span:
+ * sum = sum of q(P[i, L]), qmin = the smallest q(P[i, L]), agree = the number of i whose first-maximum column is L (best = 0; for c
+ * in 1 .. C-1: if P[i, c] > P[i, best] then best = c -- raw floats, a NaN never wins).  bases == 0 gives all zeros; pad is 0.
+ * Every statistic is an integer sum, minimum or count: the result does not depend on the grid, on timing or on summation order.
+ * Work is shared out by clipped length, not by row: a workgroup takes 8192 positions of the scanned lengths, gathers its rows'
+ * partial results in LDS and adds them to d_scores with at most two 64-bit atomic adds (sum, agree) and one 32-bit atomic minimum
+ * per (workgroup, row).
+ * DGRP_EINVAL before anything is written unless 2 <= C <= 64, h_n[r] >= 1, h_row0[r] >= 0, h_startpos[r] >= 0, h_row_off ascending
+ * from a value >= 0, and every row has 0 <= start <= end and 1 <= label < C (that check runs on the device and synchronises the
+ * stream once).  DGRP_ENOMEM for a workspace below dgrp_row_scores_workspace_bytes(nrec, rows).  nrec == 0 or no rows: no device
+ * work.  After the row check the entry is stream-ordered: the scores are complete behind it on `stream`, not on return. */
+typedef struct { uint64_t sum; int64_t bases; int64_t agree; uint32_t qmin; uint32_t pad; } dgrp_row_score;   /* 32 bytes */
+int64_t dgrp_row_scores_workspace_bytes(int64_t nrec, int64_t nrows);
+int dgrp_row_scores_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                          const int64_t *h_startpos, const dgrp_segment *d_rows, const int64_t *h_row_off,
+                          dgrp_row_score *d_scores, void *d_work, int64_t work_bytes, void *stream);
+
+/* The scored rows as BED text (host code, host buffers): per row "name\tstart\tend\tclass<label>\tscore\t.\tmean\tmin\tagree\n".
+ * name i = bytes [name_off[i], name_off[i+1]) of `names`; a row takes name rows[r].contig if by_contig != 0, else name 0 (the rule
+ * of dgrp_format_rows).  With R(num, den, k) = floor((2 k num + den) / (2 den)), integer round-half-up evaluated in 128 bits:
+ * score = R(sum, bases * 2^24, 1000), an integer 0..1000 (BED column 5); mean = R(sum, bases * 2^24, 10000), min = R(qmin, 2^24,
+ * 10000) and agree = R(agree, bases, 10000), each printed "d.dddd".  Rows with score < min_score are left out.  A row with
+ * bases <= 0 gives DGRP_EINVAL.  out capacity >= dgrp_format_bed_bound(nrows, longest name), else DGRP_ENOMEM; *written = bytes
+ * produced. */
+int64_t dgrp_format_bed_bound(int64_t nrows, int64_t longest_name);
+int dgrp_format_bed_rows(const char *names, const int64_t *name_off, int64_t nnames, int by_contig,
+                         const dgrp_segment *rows, const dgrp_row_score *scores, int64_t nrows, int min_score,
+                         char *out, int64_t cap, int64_t *written);
+
 /* ---- compressed input (an addition; the reference reads plain text only): DEFLATE (RFC 1951) streams inflated by the
  * same decode core on the device and on the host (deepgrp_amd/csrc/inflate.h).  A stream that cannot be decoded gives
  * DGRP_EDATA and one of these reasons; no read or write leaves the stream's input and output slices. */
