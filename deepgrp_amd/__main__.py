@@ -18,6 +18,8 @@ Differences, all additive:
     mean and the smallest probability of its class and the share of its bases that carry it, summed on the GPU (deepgrp_amd/bed.py);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
+  * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
+    command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
   * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
 """
 from __future__ import annotations
@@ -328,6 +330,11 @@ class CommandLineParser:
             if packed:
                 sys.exit(f"{packed[0]} is gzip-compressed: compressed input cannot be sharded over ranks (WORLD_SIZE > 1); "
                          "decompress it or run in one process")
+            from .twobit import twobit_inputs
+            packed = twobit_inputs(args.FASTA)
+            if packed and not getattr(args, "split_contigs", False):
+                sys.exit(f"{packed[0]} is a 2bit file: the ranks share a file out by byte ranges of FASTA text, and a 2bit file has "
+                         "none (WORLD_SIZE > 1); convert it to FASTA, pass --split_contigs or run in one process")
         import torch
         import torch.distributed as dist
         from . import model as dgmodel
@@ -728,6 +735,7 @@ class CommandLineParser:
             sys.exit("--mask_gzip: a compressed masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
                      "they share a file out by byte ranges, and a compressed file has none; run in one process")
         from .gz import compressed_inputs
+        from .twobit import is_twobit
         plan, seen = {}, {}
         for f in args.FASTA:
             if f == "-":
@@ -738,6 +746,8 @@ class CommandLineParser:
                 sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
                          "uncompressed FASTA or pass --mask_gzip")
             base = os.path.basename(f)
+            if is_twobit(f):
+                base += ".fa"                                     # the masked copy of a 2bit file is its FASTA text
             if packed_out and not base.endswith(".gz"):
                 base += ".gz"
             if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):

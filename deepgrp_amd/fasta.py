@@ -264,7 +264,9 @@ def read_multi_fasta_device(path: Union[str, os.PathLike], group_bytes: int = 25
 
     Records are taken in groups (up to `group_bytes` of file or `group_records` records): one upload, the encode
     kernels of all of them queued back to back, one read-back -- a file of thousands of short records pays one
-    wait per group, not one per record."""
+    wait per group, not one per record.
+
+    A gzip file (gz.py) and a UCSC .2bit file (twobit.py) are recognised by their first bytes and yield what their text yields."""
     for _key, header, rec in ingest_ranges(path, None, group_bytes, group_records):
         yield header, rec
 
@@ -276,7 +278,7 @@ def ingest_ranges(path: Union[str, os.PathLike], ranges=None, group_bytes: int =
     piece) sorts the records of a file in file order whichever process produced them."""
     import numpy as np
 
-    from . import gz
+    from . import gz, twobit
     from ._lib import lib
     from .pipeline import require_gpu
 
@@ -284,6 +286,11 @@ def ingest_ranges(path: Union[str, os.PathLike], ranges=None, group_bytes: int =
         if ranges is not None:
             raise ValueError(f"{path}: a compressed file is read whole; it cannot be ingested by byte ranges")
         yield from _ingest_gzip(path, group_bytes, group_records)
+        return
+    if twobit.is_twobit(path):
+        if ranges is not None:
+            raise ValueError(f"{path}: a 2bit file is read whole; it cannot be ingested by byte ranges of FASTA text")
+        yield from _ingest_twobit(path, group_bytes, group_records)
         return
     dev = require_gpu()
     L = lib()
@@ -313,6 +320,50 @@ def _ingest_gzip(path, group_bytes: int, group_records: int):
     if size == 0:
         return
     yield from _ingest_range(lib(), d_text.device, path, text, 0, size, group_bytes, group_records, d_file=d_text)
+
+
+def _ingest_twobit(path, group_bytes: int, group_records: int):
+    """ingest_ranges for a UCSC .2bit file (deepgrp_amd/twobit.py): the records the FASTA ingest yields from the text of the file.
+    The host parses and validates the index and the block tables, the file goes up as it is, and the packed bases of a group of
+    records (up to `group_bytes` bases or `group_records` records) become class indices in one dgrp_twobit_encode_batch; leading
+    and trailing N come from the N blocks, so nothing is read back.  `key` = (file offset of the record, 0)."""
+    from . import twobit
+    from ._lib import lib
+    from .pipeline import require_gpu
+
+    tb = twobit.open_twobit(path)
+    if tb.size > RESIDENT_BYTES:
+        raise twobit.too_large(path, RESIDENT_BYTES)
+    if tb.nrec == 0:
+        return
+    dev = require_gpu()
+    lib()
+    dtb = twobit.DeviceTwoBit(tb, dev, _upload_file)
+    if not tb.plain_names():
+        # a header line the FASTA ingest would not take on its device path (not ASCII, or a line break inside the name): the text
+        # of the file, built on the device, goes through that ingest itself
+        from .gz import DeviceText
+        if tb.text_size > RESIDENT_BYTES:
+            raise twobit.too_large(path, RESIDENT_BYTES)
+        d_text = dtb.text()
+        del dtb
+        yield from _ingest_range(lib(), dev, path, DeviceText(d_text), 0, tb.text_size, group_bytes, group_records, d_file=d_text)
+        return
+    dna, startpos, kept, rec_off = tb.dna_size.tolist(), tb.startpos.tolist(), tb.kept.tolist(), tb.rec_off.tolist()
+    r0 = 0
+    while r0 < tb.nrec:
+        r1, bases = r0 + 1, dna[r0]
+        while r1 < tb.nrec and r1 - r0 < group_records and bases + dna[r1] <= group_bytes:
+            bases += dna[r1]
+            r1 += 1
+        d_idx, out_off = dtb.encode(r0, r1)
+        out_off = out_off.tolist()
+        for r in range(r0, r1):
+            header = tb.header(r)
+            if header:                                                # a record without header is dropped, as in the text
+                yield (rec_off[r], 0), header, DeviceRecord(startpos[r], None, kept[r], d_idx, out_off[r - r0] + startpos[r])
+        del d_idx
+        r0 = r1
 
 
 def _chunk_table(L, dev, path, mm, r0: int, r1: int, d_file=None):

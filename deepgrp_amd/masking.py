@@ -134,13 +134,14 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     A gzip-compressed `fasta_path` (no `ranges`) is masked as its inflated text (gz.open_inflated: BGZF members inflated on the
     device, other gzip through zlib), resident on the device.  `compress=True` (no `ranges`): `out_path` becomes a BGZF file of the
     masked text -- every group is deflated on the device where it was masked (gz.bgzf_compress_device at `level`: 0 literals only,
-    1 with matches) and its members are appended, the EOF member behind the last; a group boundary is just a short member.  Returns
-    the number of records seen."""
+    1 with matches) and its members are appended, the EOF member behind the last; a group boundary is just a short member.  A UCSC
+    .2bit `fasta_path` (no `ranges`) is masked as the text of the file (twobit.open_text: built on the device by
+    dgrp_twobit_text_batch), which takes the place inflated gzip text takes.  Returns the number of records seen."""
     import torch
 
     import contextlib
 
-    from . import gz
+    from . import gz, twobit
     from ._lib import check, lib
     from .fasta import RESIDENT_BYTES, _chunk_groups, _upload_file
     from .pipeline import SEGMENT_DTYPE, require_gpu, stream_ptr
@@ -159,6 +160,12 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     text = d_text = None
     if packed:
         text, d_text, size = gz.open_inflated(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
+    elif twobit.is_twobit(fasta_path):
+        if ranges is not None:
+            raise ValueError(f"{fasta_path}: a 2bit input has no byte ranges of FASTA text to share out; it is masked whole")
+        # the masked copy is the text of the file (twobit.py), built on the device: from here on as inflated gzip text
+        packed = True
+        text, d_text, size = twobit.open_text(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
     else:
         size = os.path.getsize(fasta_path)
     if ranges is None:

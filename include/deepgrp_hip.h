@@ -110,6 +110,39 @@ int dgrp_fasta_mask_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_o
                           const dgrp_segment *d_rows, const int64_t *h_row_off, int mode, uint64_t class_mask,
                           uint8_t *d_out, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- UCSC .2bit input (an addition; the reference reads FASTA text only).  d_file [file_bytes] = the .2bit file as it is, any
+ * alignment.  Record r has h_dna_size[r] bases (at most 2^32 - 1), packed four per byte from file offset h_packed_off[r]: T=0 C=1
+ * A=2 G=3, the first base of a byte in its two most significant bits, the unused bits of the last byte arbitrary.  Its N blocks are
+ * the intervals h_n_iv_off[r] .. h_n_iv_off[r + 1] of d_n_iv (device, n_iv intervals as int64 pairs [start, end)): ascending,
+ * disjoint, inside the record (the host parser merges the file's blocks; an interval that is not only costs or loses N, no access
+ * leaves a buffer).  Every host table is read before the call returns and checked against file_bytes, n_iv and the output
+ * capacity (DGRP_EINVAL before anything is queued); the work is stream-ordered, nothing synchronises or reads back.
+ * Workspace of either entry: dgrp_twobit_workspace_bytes of nrec (else DGRP_ENOMEM).  nrec == 0: nothing is queued.
+ *
+ * dgrp_twobit_encode_batch: one class index per base (A=0 C=1 G=2 T=3, inside an N block 4 whatever the two bits say -- what
+ * dgrp_encode gives for the letters) to d_idx[h_out_off[r] .. + h_dna_size[r]), the WHOLE record before N stripping, as
+ * dgrp_fasta_encode; nothing else of d_idx [idx_cap] is written.  Any alignment of packed bytes and output is correct; a lane
+ * owns one 16-byte aligned word of d_idx and stores it whole where it lies inside the record.  With o = (d_idx + h_out_off[r]) mod
+ * 16, word g of record r starts with base 16 g - o, i.e. with packed byte 4 g - o / 4 when o is a multiple of 4; the lane reads its
+ * four packed bytes in one 4-byte load when that byte's address is a multiple of 4, which holds for every word of the record when
+ * o = 4 * (address of the record's packed bytes mod 4) -- the caller chooses h_out_off so (twobit.placed_offsets) -- and in five
+ * byte loads otherwise.
+ *
+ * dgrp_twobit_text_batch: the FASTA text of the records -- '>', the h_name_len[r] (<= 255) name bytes at file offset
+ * h_name_off[r], LF, then the bases 50 per line, every line LF-terminated (no base: the header line only); letters ACGT, N inside
+ * an N block, lower case inside a soft-mask interval (d_m_iv, h_m_iv_off, m_iv: as the N intervals) -- to d_text[h_text_off[r] ..
+ * + 2 + h_name_len[r] + h_dna_size[r] + ceil(h_dna_size[r] / 50)); nothing else of d_text [text_cap] is written. */
+int64_t dgrp_twobit_workspace_bytes(int64_t nrec);
+int dgrp_twobit_encode_batch(const uint8_t *d_file, int64_t file_bytes, int64_t nrec, const int64_t *h_packed_off,
+                             const int64_t *h_dna_size, const int64_t *d_n_iv, const int64_t *h_n_iv_off, int64_t n_iv,
+                             const int64_t *h_out_off, uint8_t *d_idx, int64_t idx_cap, void *d_work, int64_t work_bytes,
+                             void *stream);
+int dgrp_twobit_text_batch(const uint8_t *d_file, int64_t file_bytes, int64_t nrec, const int64_t *h_name_off,
+                           const int64_t *h_name_len, const int64_t *h_packed_off, const int64_t *h_dna_size,
+                           const int64_t *d_n_iv, const int64_t *h_n_iv_off, int64_t n_iv, const int64_t *d_m_iv,
+                           const int64_t *h_m_iv_off, int64_t m_iv, const int64_t *h_text_off, uint8_t *d_text,
+                           int64_t text_cap, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3: deepgrp.prediction.fetch_validation_batch (deepgrp/prediction.py:14-37)
  * Number of windows len(range(0, n - T, s)). */
 int64_t dgrp_window_count(int64_t n, int64_t T, int64_t s);
