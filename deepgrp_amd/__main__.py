@@ -20,7 +20,9 @@ Differences, all additive:
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
-  * `train` exits with an error: training is TensorFlow's job in the reference and out of scope.
+  * `train <parameter.toml> <trainfile.npz> <validfile.npz> <bedfile>` trains a GRU model on the GPU (deepgrp_amd/training.py:
+    forward, backward through time and the optimizer are HIP kernels) and writes a Keras HDF5 file `predict` loads; `--seed N`
+    (an addition) seeds the initial weights, the sampler and the dropout masks.  No TensorBoard output.
 """
 from __future__ import annotations
 
@@ -215,13 +217,16 @@ class CommandLineParser:
         _add_track_options(self.parser)
         _add_bed_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
-                                      description="Train a deepgrp model (not available in deepgrp_amd)")
+                                      description="Train a deepgrp model (GRU) on the GPU")
         train.add_argument("parameter", type=str)
         train.add_argument("trainfile", type=str)
         train.add_argument("validfile", type=str)
         train.add_argument("bedfile", type=str)
         train.add_argument("--logdir", type=str, default=".")
         train.add_argument("--modelfile", type=str, default="model.hdf5")
+        train.add_argument("--seed", type=int, default=None,
+                           help="(addition) seed of the initial weights, the sampler and the dropout masks: the same seed "
+                                "writes the same model file, byte for byte")
         predict = subparsers.add_parser(name="predict", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                         description="predict using a deepgrp model")
         predict.add_argument("model", type=str, help="Keras model in HDF5 format")
@@ -917,8 +922,43 @@ class CommandLineParser:
 
     @staticmethod
     def train(args: argparse.Namespace, options) -> None:
-        sys.exit("deepgrp_amd implements the prediction path only; train with the reference (TensorFlow) and "
-                 "pass the saved .hdf5 to `predict`")
+        """Train deepgrp (deepgrp/__main__.py:299-351): options from the TOML file, truth from the BED table for the contigs the
+        two file names start with, a freshly initialised model trained on the GPU, saved as Keras HDF5."""
+        from . import model as dgmodel
+        from . import preprocessing as dgpreprocess
+        from . import training as dgtrain
+        for path in (args.parameter, args.trainfile, args.validfile, args.bedfile):
+            if not os.path.isfile(path):
+                sys.exit(f"train: {path}: no such file")
+        with open(args.parameter, "r") as file:
+            parameter = dgmodel.Options.from_toml(file)
+        # the reference goes on with parameter.fromdict(options.todict()), which puts every default back over the file's values
+        # (units, vecsize, batch_size, ...): the parameter file would be ignored.  Here the file holds.
+        try:
+            dgtrain.check_options(parameter)                     # refusals come before anything is read or run
+        except dgtrain.TrainingRefused as exc:
+            sys.exit(f"train: {exc}")
+        logdir = args.logdir
+        train_chr = os.path.basename(args.trainfile).split(".")[0]
+        val_chr = os.path.basename(args.validfile).split(".")[0]
+        if not os.path.isdir(logdir):
+            os.mkdir(logdir)
+        _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
+        train_fwd = dgpreprocess.load_onehot_npz(args.trainfile)
+        val_fwd = dgpreprocess.load_onehot_npz(args.validfile)
+        y_train = dgpreprocess.preprocess_y(args.bedfile, train_chr, train_fwd.shape[1], parameter.repeats_to_search)
+        y_val = dgpreprocess.preprocess_y(args.bedfile, val_chr, val_fwd.shape[1], parameter.repeats_to_search)
+        train_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(train_fwd, y_train))
+        val_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(val_fwd, y_val))
+        _LOG.info("Creating model for training")
+        dgmodel.reset_layer_names()
+        config = {"class_name": "Functional", "config": dgmodel.model_config(parameter)}
+        weights = dgmodel.initial_weights(parameter, args.seed)
+        _LOG.info("Training Model")
+        best = dgtrain.training((train_data, val_data), parameter, weights, logdir, seed=args.seed)
+        _LOG.info("Saving model as %s", args.modelfile)
+        dgmodel.save_keras_hdf5(args.modelfile, best["kernel"], best["recurrent_kernel"], best["bias"], best["ff_kernel"],
+                                best["ff_bias"], best["scale"], vecsize=int(parameter.vecsize), config=config)
 
 
 def main(argv=None):

@@ -106,6 +106,10 @@ _SIGNATURES = {
     "dgrp_bgzf_workspace_bytes_level": (i64, [i64, cint]),
     "dgrp_bgzf_compress_level": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, cint, vp, i64, vp]),
     "dgrp_bgzf_compress_host_level": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, cint]),
+    "dgrp_train_param_count": (i64, [cint, cint, cint]),
+    "dgrp_train_workspace_bytes": (i64, [cint, cint, cint, cint, i64]),
+    "dgrp_train_step": (cint, [cint, cint, cint, cint, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "dgrp_optimizer_step": (cint, [cint, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

@@ -5,7 +5,7 @@
 (deepgrp/__main__.py:264-269): it reads the Keras HDF5 file with the built-in reader
 (deepgrp_amd.hdf5), checks that the layer graph is the one ``create_model``
 (deepgrp/model.py:293-336) builds, and uploads the tensors to the GPU.
-``create_model`` / training are out of scope (TensorFlow's job in the reference).
+``initial_weights`` / ``create_model`` give a freshly initialised model; deepgrp_amd.training trains it on the GPU.
 """
 from __future__ import annotations
 
@@ -379,7 +379,7 @@ def initial_weights(options: "Options", seed: Optional[int] = None) -> Dict[str,
 def create_model(options: "Options", seed: Optional[int] = None):
     """Mirror of ``deepgrp.model.create_model`` (deepgrp/model.py:293-336) on the prediction side: a freshly
     initialised, device-resident model of that architecture (``predict_on_batch``, ``get_config``, ``save``).
-    Training it is the reference's business (out of scope)."""
+    deepgrp_amd.training trains the tensors of ``initial_weights`` (the `train` command)."""
     from .pipeline import DeviceModel
     w = initial_weights(options, seed)
     model = DeviceModel(w["kernel"], w["recurrent_kernel"], w["bias"], w["ff_kernel"], w["ff_bias"], w["scale"],

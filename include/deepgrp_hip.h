@@ -610,6 +610,43 @@ int dgrp_bgzf_compress_level(const uint8_t *d_in, int64_t n, uint8_t *d_out, int
 int dgrp_bgzf_compress_host_level(const uint8_t *h_in, int64_t n, uint8_t *h_out, int64_t out_cap, int64_t *h_out_bytes, int eof,
                                   int level);
 
+/* ---- training (deepgrp/training.py and model.compile / model.fit of deepgrp/model.py:293-336; TensorFlow's job in the reference).
+ * GRU models only, 1 <= u <= 256, 2 <= C <= 16, 1 <= T <= 4096, 1 <= B <= 2^18.  The parameters are ONE flat float32 device buffer
+ * in Keras layout, tensors back to back: kernel [5, 3u], recurrent_kernel [u, 3u], bias [2, 3u], scale [u] (attention only),
+ * FF/kernel [(attention ? 2u : u), C], FF/bias [C]; the count is what the param_count entry returns (0 on sizes the step refuses).
+ * The gradients have the same layout.
+ *
+ * dgrp_train_step: window i of the batch is d_idx[d_starts[i] .. + T) (class indices as dgrp_encode writes them, any value above 4
+ * read as 4 = N); its truth is d_truth[c * n + d_starts[i] + t], the int8 [C, n] multi-hot array of preprocess_y.  d_starts is a
+ * DEVICE array; a start outside [0, n - T] is clamped into it (no access leaves the arrays), starts may repeat.  d_masks [B, 2, 5]
+ * float32 are the GRU cell's input dropout masks per (window, direction: 0 the window, 1 its reverse complement, input channel),
+ * constant over the steps, 0 or 1 / (1 - rate); NULL = no dropout.  *d_loss (device float) = Keras' CategoricalCrossentropy: the
+ * probabilities divided by their sum, clipped to [1e-7, 1 - 1e-7], -sum_c y_c log p_c averaged over the B T positions.  d_grads
+ * receives d loss / d parameters (every element written, nothing accumulated); with d_grads NULL only the loss is computed, by the
+ * same kernels: the same bits.  A clipped probability has no gradient, as in Keras.  Every sum across threads runs in a fixed
+ * order: the same call gives the same bytes.  Stream-ordered: nothing synchronises or reads back.  Workspace
+ * dgrp_train_workspace_bytes (0 on sizes the step refuses), 16-byte aligned, DGRP_ENOMEM when smaller.
+ * Batch size in practice: the last kernel adds the partial gradients in index order, one thread per parameter over
+ * 2 ceil(B / 16) ceil(T / 32) partials (and B for the head's tensors and the loss), so its time grows with B: microseconds at
+ * the reference's batch of 256, a serial tail of milliseconds beyond some 10^4 windows.  Sizes up to 2^18 are correct, not fast. */
+int64_t dgrp_train_param_count(int u, int C, int attention);
+int64_t dgrp_train_workspace_bytes(int T, int u, int C, int attention, int64_t B);
+int dgrp_train_step(int T, int u, int C, int attention, const float *d_params, const uint8_t *d_idx, const int8_t *d_truth,
+                    int64_t n, const int64_t *d_starts, int64_t B, const float *d_masks, float *d_loss, float *d_grads,
+                    void *d_work, int64_t work_bytes, void *stream);
+
+/* One optimizer step on `count` float32 parameters, in place, in float32, one rounding per operation as written:
+ * DGRP_OPT_RMSPROP  s1 = rho s1 + ((1 - rho) g) g;  s2 = momentum s2 + (lr g) / sqrt(s1 + epsilon);  w = w - s2
+ * DGRP_OPT_ADAM     s1 = b1 s1 + (1 - b1) g;  s2 = b2 s2 + ((1 - b2) g) g;  w = w - (lr_t s1) / (sqrt(s2) + epsilon), with b1 = momentum,
+ *                   b2 = rho (the mapping of deepgrp/model.py's _get_optimizer) and lr_t = lr sqrt(1 - b2^step) / (1 - b1^step) computed in
+ *                   double on the host; step counts from 1.
+ * The scalars are rounded to float32 once ((1 - rho) from the double difference).  d_state1 / d_state2: zero before the first step.
+ * Stream-ordered. */
+#define DGRP_OPT_RMSPROP 0
+#define DGRP_OPT_ADAM 1
+int dgrp_optimizer_step(int kind, float *d_params, const float *d_grads, float *d_state1, float *d_state2, int64_t count,
+                        double learning_rate, double rho, double momentum, double epsilon, int64_t step, void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits

@@ -3,7 +3,8 @@
 chromosomes' planted tandem repeats, on CPU with torch, and store the tensors in Keras layout
 (deepgrp_amd/data/synthetic_gru128.npz).  Benchmark tooling only: it gives bench.py a model whose
 output looks like a genome annotation (long confident background, confident repeat runs) instead
-of the stationary noise random weights produce.  Training is NOT part of the product."""
+of the stationary noise random weights produce.  It predates the package's own trainer (`python -m deepgrp_amd train`,
+deepgrp_amd/training.py) and is kept as the record of how the shipped benchmark model was made."""
 import os
 import sys
 import time
