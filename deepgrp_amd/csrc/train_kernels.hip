@@ -19,6 +19,8 @@ namespace {
 
 constexpr int TR_MAXC = 16;
 constexpr int TR_TCHUNK = 32;        // steps per partial of the kernel / bias column sums
+constexpr int TR_HCHUNK = 32;        // the head's sums over the steps of a window: blocks of 32 terms, then the blocks (error ~ sqrt(32) +
+                                     // sqrt(T / 32) roundings, not sqrt(T): 1300 terms in one chain cost 1e-6 of FF/kernel's gradient)
 
 struct train_params {
     int T, u, Up, C, att, F;         // F = rows of FF/kernel (2u with attention)
@@ -233,7 +235,12 @@ __global__ void train_head_kernel(train_params p)
         __syncthreads();
         if (tid < u) {
             float c = 0.0f;
-            for (int t = 0; t < T; ++t) c += a[t] * avg[(int64_t)t * u + tid];
+            for (int t0 = 0; t0 < T; t0 += TR_HCHUNK) {
+                const int t1 = min(T, t0 + TR_HCHUNK);
+                float blk = 0.0f;
+                for (int t = t0; t < t1; ++t) blk += a[t] * avg[(int64_t)t * u + tid];
+                c += blk;
+            }
             ctx[tid] = c;
         }
         __syncthreads();
@@ -299,11 +306,13 @@ __global__ void train_head_kernel(train_params p)
     if (!p.grads) return;
     __syncthreads();
 
-    if (tid < 16) {
+    // column sums of d loss / d logits: one wave per class, a lane adds every 64th step, then the butterfly
+    for (int c = wave; c < 16; c += nwave) {
         float s = 0.0f;
-        if (tid < C)
-            for (int t = 0; t < T; ++t) s += dl[(int64_t)t * C + tid];
-        sdl[tid] = s;
+        if (c < C)
+            for (int t = lane; t < T; t += 64) s += dl[(int64_t)t * C + c];
+        s = tr_wave_sum(s);
+        if (lane == 0) sdl[c] = s;
     }
     __syncthreads();
     if (att) {
@@ -330,13 +339,15 @@ __global__ void train_head_kernel(train_params p)
     const int G = NT / u, PS = C + 2;
     if (tid < G * u) {
         const int g = tid / u, j = tid % u;
-        float wrow[TR_MAXC], accw[TR_MAXC];
+        float wrow[TR_MAXC], accw[TR_MAXC], blkw[TR_MAXC];
         for (int c = 0; c < TR_MAXC; ++c) {
             wrow[c] = c < C ? Wff[(off + j) * C + c] : 0.0f;
             accw[c] = 0.0f;
+            blkw[c] = 0.0f;
         }
-        float dsc = 0.0f, dq = 0.0f;
+        float dsc = 0.0f, dq = 0.0f, bsc = 0.0f, bq = 0.0f;
         const float sj = att ? scale[j] : 0.0f, qj = att ? q[j] : 0.0f, dcj = att ? dctx[j] : 0.0f;
+        int k = 0;
         for (int t = g; t < T; t += G) {
             const float av = avg[(int64_t)t * u + j];
             float dv = 0.0f;
@@ -344,16 +355,26 @@ __global__ void train_head_kernel(train_params p)
                 if (c < C) {
                     const float d = dl[(int64_t)t * C + c];
                     dv += d * wrow[c];
-                    accw[c] += av * d;
+                    blkw[c] += av * d;
                 }
             if (att) {
                 const float th = tanhf(qj + av), de = da[t];
-                dsc += de * th;
+                bsc += de * th;
                 const float dp = de * sj * (1.0f - th * th);
-                dq += dp;
+                bq += dp;
                 dv += a[t] * dcj + dp;
             }
             davg[(int64_t)t * u + j] = dv;
+            if (++k == TR_HCHUNK || t + G >= T) {                 // a block of the thread's steps is complete: add it to the total
+                for (int c = 0; c < TR_MAXC; ++c) {
+                    accw[c] += blkw[c];
+                    blkw[c] = 0.0f;
+                }
+                dsc += bsc;
+                dq += bq;
+                bsc = bq = 0.0f;
+                k = 0;
+            }
         }
         for (int c = 0; c < TR_MAXC; ++c)
             if (c < C) part[tid * PS + c] = accw[c];

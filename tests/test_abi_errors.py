@@ -25,6 +25,23 @@ def plan_out(null=None):
     return out
 
 
+def train_args(T=50, u=20, C=5, attention=1, params=P, idx=P, truth=P, n=1000, starts=P, B=4, masks=None, loss=P, grads=None, work=P,
+               work_bytes=1 << 40, stream=None):
+    """The arguments of dgrp_train_step: a call that would be accepted (P is 16-byte aligned), but for the ones given."""
+    return (T, u, C, attention, params, idx, truth, n, starts, B, masks, loss, grads, work, work_bytes, stream)
+
+
+def train_layout(T, u, C, attention, B):
+    """(parameter count, workspace bytes) as csrc/train_kernels.hip lays them out: the Keras tensors back to back; the
+    workspace's ten float buffers, each rounded up to 256 bytes."""
+    Up, F, nt, ntc = (u + 15) // 16 * 16, (2 if attention else 1) * u, (B + 15) // 16, (T + 31) // 32
+    total = 15 * u + 3 * u * u + 6 * u + (u if attention else 0) + F * C + C
+    nh = total - (15 * u + 3 * u * u + 6 * u)
+    floats = [Up * 3 * Up, Up * 3 * Up, 2 * nt * T * 5 * 16 * Up, B * T * u, B * T * u, B * T * C, B * nh, B, 2 * nt * Up * 3 * Up,
+              2 * nt * ntc * 7 * 3 * Up]
+    return total, sum((4 * f + 255) // 256 * 256 for f in floats)
+
+
 CASES = [
     ("dgrp_strip_n", lambda: (None, 5, i64x1, i64x1), "dgrp_strip_n"),
     ("dgrp_strip_n", lambda: (P, -1, i64x1, i64x1), "dgrp_strip_n"),
@@ -101,6 +118,33 @@ CASES = [
     ("dgrp_model_plan", lambda: (P, 3, 50, *plan_out()), "mode 3"),
     ("dgrp_model_plan", lambda: (P, 1, 0, *plan_out()), "step 0"),
     ("dgrp_model_plan", lambda: (P, 2, -5, *plan_out()), "step -5"),
+    # dgrp_train_step(T, u, C, attention, params, idx, truth, n, starts, B, masks, loss, grads, work, work_bytes, stream): masks and grads
+    # may be NULL, every other pointer in turn
+    ("dgrp_train_step", lambda: train_args(params=None), "NULL parameter, index, truth, start or loss"),
+    ("dgrp_train_step", lambda: train_args(idx=None), "NULL parameter, index, truth, start or loss"),
+    ("dgrp_train_step", lambda: train_args(truth=None), "NULL parameter, index, truth, start or loss"),
+    ("dgrp_train_step", lambda: train_args(starts=None), "NULL parameter, index, truth, start or loss"),
+    ("dgrp_train_step", lambda: train_args(loss=None), "NULL parameter, index, truth, start or loss"),
+    ("dgrp_train_step", lambda: train_args(work=None), "workspace NULL or not 16-byte aligned"),
+    ("dgrp_train_step", lambda: train_args(work=P + 8), "workspace NULL or not 16-byte aligned"),
+    ("dgrp_train_step", lambda: train_args(n=49), "record of 49 bases is shorter than the window (50)"),
+    ("dgrp_train_step", lambda: train_args(T=0), "vecsize 0 outside 1..4096"),
+    ("dgrp_train_step", lambda: train_args(T=4097, n=5000), "vecsize 4097 outside 1..4096"),
+    ("dgrp_train_step", lambda: train_args(u=0), "0 units outside 1..256"),
+    ("dgrp_train_step", lambda: train_args(u=257), "257 units outside 1..256"),
+    ("dgrp_train_step", lambda: train_args(C=1), "1 classes outside 2..16"),
+    ("dgrp_train_step", lambda: train_args(C=17), "17 classes outside 2..16"),
+    ("dgrp_train_step", lambda: train_args(B=0), "batch size 0 outside 1..2^18"),
+    ("dgrp_train_step", lambda: train_args(B=(1 << 18) + 1), "batch size 262145 outside 1..2^18"),
+    # dgrp_optimizer_step(kind, params, grads, state1, state2, count, lr, rho, momentum, epsilon, step, stream)
+    ("dgrp_optimizer_step", lambda: (2, P, P, P, P, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "optimizer kind 2"),
+    ("dgrp_optimizer_step", lambda: (-1, P, P, P, P, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "optimizer kind -1"),
+    ("dgrp_optimizer_step", lambda: (0, P, P, P, P, 0, 1e-3, 0.9, 0.9, 1e-7, 1, None), "optimizer: 0 parameters"),
+    ("dgrp_optimizer_step", lambda: (1, P, P, P, P, 4, 1e-3, 0.9, 0.9, 1e-7, 0, None), "step 0 (the first step is 1)"),
+    ("dgrp_optimizer_step", lambda: (0, None, P, P, P, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "NULL parameter, gradient or state"),
+    ("dgrp_optimizer_step", lambda: (0, P, None, P, P, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "NULL parameter, gradient or state"),
+    ("dgrp_optimizer_step", lambda: (1, P, P, None, P, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "NULL parameter, gradient or state"),
+    ("dgrp_optimizer_step", lambda: (1, P, P, P, None, 4, 1e-3, 0.9, 0.9, 1e-7, 1, None), "NULL parameter, gradient or state"),
 ]
 
 
@@ -120,15 +164,47 @@ SMALL_WORKSPACE = [
     ("dgrp_mss_labels", lambda: (P, P, 1000, 5, 50, 50, P, None, P, 8, None)),
     ("dgrp_mss_labels_batch", lambda: (P, P, 128, 2, (C.c_int64 * 3)(0, 64, 128), 5, 50, 50, P, P, 8, None)),
     ("dgrp_segments", lambda: (P, 1000, 0, 0, P, 10, P, P, 8, None)),
+    ("dgrp_train_step", lambda: train_args(work_bytes=8)),
+    ("dgrp_train_step", lambda: train_args(work_bytes=train_layout(50, 20, 5, 1, 4)[1] - 1)),
 ]
 
 
-@pytest.mark.parametrize("name,make", SMALL_WORKSPACE, ids=[c[0] for c in SMALL_WORKSPACE])
+@pytest.mark.parametrize("name,make", SMALL_WORKSPACE, ids=[f"{c[0]}-{i}" if c[0] == "dgrp_train_step" else c[0] for i, c in enumerate(SMALL_WORKSPACE)])
 def test_short_workspace_is_refused_before_any_device_work(name, make):
     """The sizes come from the matching *_workspace_bytes call; a shorter buffer is DGRP_ENOMEM, never a partial run."""
     L = lib()
     assert getattr(L, name)(*make()) == ENOMEM
     assert "workspace" in L.dgrp_last_error().decode()
+
+
+@pytest.mark.parametrize("shape", [(50, 20, 5, 1, 4), (1, 1, 2, 0, 1), (342, 60, 5, 1, 256), (4096, 256, 16, 1, 17)], ids=str)
+def test_train_workspace_one_byte_short_names_both_sizes(shape):
+    L = lib()
+    need = L.dgrp_train_workspace_bytes(*shape)
+    assert need == train_layout(*shape)[1]
+    T, u, C, att, B = shape
+    assert L.dgrp_train_step(*train_args(T=T, u=u, C=C, attention=att, B=B, n=T, work_bytes=need - 1)) == ENOMEM
+    msg = L.dgrp_last_error().decode()
+    assert f"workspace of {need - 1} bytes, {need} needed" in msg, msg
+
+
+def test_train_size_queries_follow_the_layout_and_are_0_outside_the_envelope():
+    """Units 1..256, classes 2..16, windows 1..4096, batch 1..2^18: the formula of train_layout inside, 0 one step outside."""
+    L = lib()
+    for u in (0, 1, 2, 15, 16, 17, 60, 128, 255, 256, 257, -1):
+        for C in (1, 2, 3, 5, 16, 17, 0):
+            for att in (0, 1):
+                inside = 1 <= u <= 256 and 2 <= C <= 16
+                assert L.dgrp_train_param_count(u, C, att) == (train_layout(1, u, C, att, 1)[0] if inside else 0), (u, C, att)
+    assert L.dgrp_train_param_count(20, 5, 7) == L.dgrp_train_param_count(20, 5, 1)          # attention is a flag: non-zero is yes
+    for T in (0, 1, 31, 32, 33, 342, 4096, 4097, -1):
+        for u in (0, 1, 16, 17, 256, 257):
+            for C in (1, 2, 16, 17):
+                for B in (0, 1, 15, 16, 17, 256, 1 << 18, (1 << 18) + 1, -1):
+                    inside = 1 <= T <= 4096 and 1 <= u <= 256 and 2 <= C <= 16 and 1 <= B <= 1 << 18
+                    for att in (0, 1):
+                        want = train_layout(T, u, C, att, B)[1] if inside else 0
+                        assert L.dgrp_train_workspace_bytes(T, u, C, att, B) == want, (T, u, C, att, B)
 
 
 def test_size_queries_are_total_functions():
@@ -141,6 +217,12 @@ def test_size_queries_are_total_functions():
                     ("dgrp_mss_workspace_bytes", (0,)), ("dgrp_mss_batch_workspace_bytes", (0, 0)),
                     ("dgrp_segments_workspace_bytes", (0,))):
         assert getattr(L, f)(*args) >= 0, f
+    for f, args in (("dgrp_train_param_count", (0, 0, 0)), ("dgrp_train_workspace_bytes", (0, 0, 0, 0, 0)),
+                    ("dgrp_train_workspace_bytes", (50, 20, 5, 1, 2 ** 62)), ("dgrp_train_workspace_bytes", (50, 20, 5, 1, -2 ** 62)),
+                    ("dgrp_train_workspace_bytes", (-2 ** 31, 2 ** 31 - 1, -2 ** 31, 1, 4))):
+        assert getattr(L, f)(*args) == 0, (f, args)                         # "0 on sizes the step refuses"
+    sizes = [L.dgrp_train_workspace_bytes(342, 60, 5, 1, b) for b in (1, 16, 17, 256, 1 << 18)]
+    assert sizes == sorted(sizes) and sizes[0] > 0, sizes
     # monotone in n: a caller may size for the largest record once
     for f in ("dgrp_fasta_workspace_bytes", "dgrp_mss_workspace_bytes", "dgrp_segments_workspace_bytes"):
         sizes = [getattr(L, f)(n) for n in (1, 1000, 10 ** 6, 10 ** 8, 2 ** 31 - 1)]

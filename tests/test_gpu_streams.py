@@ -311,6 +311,75 @@ def test_async_forward_windows_reference(H, L, orc, m, fill):
         dm.close()
 
 
+# ---------------------------------------------------------------------------------------------------------- async: training
+@fills
+def test_async_train_step(H, L, fill):
+    """dgrp_train_step behind the late producer.  The poison is another valid batch of the same shapes (other weights, a record of N,
+    an all-background truth, starts of 0, masks of 1).  A workspace of 0xFF is NaN in every float: a workspace float that is read
+    before this call wrote it shows in the gradients.  The harness proves late == idle; the checker proves both are right."""
+    import train_oracle as tro
+    from deepgrp_amd import synthetic
+    from deepgrp_amd.training import flatten_weights, unflatten_weights
+    units, T, batch, classes = 20, 7, 17, 5
+    case = tro.make_case(units, T, batch, classes, True, seed=units + T + batch)
+    n = case["idx"].size
+    params = flatten_weights(case["weights"])
+    other = flatten_weights(synthetic.synthetic_weights(units, classes, True, seed=99))
+    background = np.zeros_like(case["truth"])
+    background[0] = 1
+    inputs = {"params": (params, other), "idx": (case["idx"], np.full(n, 4, np.uint8)), "truth": (case["truth"], background),
+              "starts": (case["starts"], np.zeros(batch, np.int64)), "masks": (case["masks"], np.ones((batch, 2, 5), np.float32))}
+    wb = L.dgrp_train_workspace_bytes(T, units, classes, 1, batch)
+    assert wb > 0 and L.dgrp_train_param_count(units, classes, 1) == params.size
+
+    def call(b, wk, st, t):
+        return L.dgrp_train_step(T, units, classes, 1, b["params"].data_ptr(), b["idx"].data_ptr(), b["truth"].data_ptr(), n,
+                                 b["starts"].data_ptr(), batch, b["masks"].data_ptr(), b["loss"].data_ptr(), b["grads"].data_ptr(),
+                                 wk.data_ptr(), wb, st), None
+    late, *_ = H.run(call, inputs, {"loss": np.full(1, 7.0, np.float32), "grads": np.full(params.size, 7.0, np.float32)},
+                     work_bytes=wb, fill=fill)
+    args = (case["weights"], case["idx"], case["truth"], case["starts"], T, case["masks"])
+    l64, g64, _ = tro.loss_and_grads(*args, torch.float64)
+    l32, g32, _ = tro.loss_and_grads(*args, torch.float32)
+    e, e32 = abs(float(late["loss"][0]) - l64) / abs(l64), abs(l32 - l64) / abs(l64)
+    print(f"loss: hip {e:.3e} float32 {e32:.3e}")
+    assert e <= tro.bound(e32)
+    grads = unflatten_weights(late["grads"], units, classes, True)
+    for name, want in g64.items():
+        e, e32 = tro.rel_err(grads[name], want), tro.rel_err(g32[name], want)
+        print(f"{name}: hip {e:.3e} float32 {e32:.3e}")
+        assert e <= tro.bound(e32), f"{name}: {e:.3e} > {tro.bound(e32):.3e}"
+
+
+@pytest.mark.parametrize("kind", ("RMSprop", "Adam"))
+@fills
+def test_async_optimizer_step(H, L, fill, kind):
+    """dgrp_optimizer_step has no workspace: parameters and both states are in/out buffers, and the poison of all three is the fill
+    (0xFF: NaN; 0x00: the state of a first step; 0xA5: small negative numbers), late-overwritten by the real values."""
+    import train_oracle as tro
+    from deepgrp_amd.training import OPTIMIZERS
+    count, step, lr, eps = 1000, 3, 1e-3, 1e-7
+    rho, momentum = (0.9, 0.9) if kind == "RMSprop" else (0.999, 0.9)
+    rng = np.random.default_rng(19)
+    w = rng.normal(size=count).astype(np.float32)
+    g = rng.normal(scale=0.1, size=count).astype(np.float32)
+    s1 = rng.normal(scale=0.03, size=count).astype(np.float32) if kind == "Adam" else (0.01 * rng.random(count) + 1e-4).astype(np.float32)
+    s2 = (0.01 * rng.random(count) + 1e-4).astype(np.float32) if kind == "Adam" else rng.normal(scale=0.003, size=count).astype(np.float32)
+    junk = np.full(count * 4, fill, np.uint8).view(np.float32)
+    late, *_ = H.run(lambda b, wk, st, t: (L.dgrp_optimizer_step(OPTIMIZERS[kind.lower()], b["w"].data_ptr(), b["g"].data_ptr(), b["s1"].data_ptr(),
+                                                                 b["s2"].data_ptr(), count, lr, rho, momentum, eps, step, st), None),
+                     {"w": (w, junk), "g": (g, np.full(count, 0.5, np.float32)), "s1": (s1, junk), "s2": (s2, junk)},
+                     {"w": None, "s1": None, "s2": None}, fill=fill)
+    ref = {}
+    for f in (np.float64, np.float32):
+        a = (w.astype(f), g, s1.astype(f), s2.astype(f))
+        ref[f] = tro.rmsprop_step(*a, lr, rho, momentum, eps, f) if kind == "RMSprop" else tro.adam_step(*a, lr, momentum, rho, eps, step, f)
+    for name, want, f32 in zip(("w", "s1", "s2"), ref[np.float64], ref[np.float32]):
+        e, e32 = tro.rel_err(late[name], want), tro.rel_err(f32, want)
+        print(f"{kind} {name}: hip {e:.3e} float32 {e32:.3e}")
+        assert e <= tro.bound(e32), f"{name}: {e:.3e} > {tro.bound(e32):.3e}"
+
+
 # ---------------------------------------------------------------------------------------------------------- synchronising: FASTA
 def _wrap(seq: bytes, width=60, nl=b"\n"):
     return nl.join(seq[i:i + width] for i in range(0, len(seq), width)) + nl
