@@ -346,7 +346,7 @@ class CommandLineParser:
         from .distributed import gather_records, shard_contigs
         from .fasta import read_multi_fasta_device
         from .pipeline import SEGMENT_DTYPE, ContigPipeline, record_indices
-        from .runner import RecordRunner, rows_text, rows_text_batch
+        from .runner import RecordRunner, rows_text
 
         world = int(os.environ.get("WORLD_SIZE", "1"))
         rank = int(os.environ.get("RANK", "0"))
@@ -379,41 +379,25 @@ class CommandLineParser:
 
         records_of = _records_of
 
-        runner = RecordRunner(pipe, tracks=track_spec)
+        runner = RecordRunner(pipe, tracks=track_spec, scores=bed_plan is not None)
 
         try:
             if world == 1:
                 import time
                 for filename in args.FASTA:
                     _LOG.info("Processing %s", filename)
-                    t_file, bases = time.perf_counter(), 0
+                    t_file = time.perf_counter()
                     kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
-                    if bed_plan is not None:
-                        # --bed_dir: as --track_dir below, and the rows' scores from the same merged array (tracks or not)
-                        bases = CommandLineParser._predict_scored(pipe, runner, filename, records_of(filename), outstream, kept,
-                                                                  tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None,
-                                                                  track_spec, bed_plan)
-                    elif track_spec is not None:
-                        # --track_dir: short records as batches (rows and track texts of a batch in two calls), the others one by one
-                        # (merged -> tracks -> labels -> segments); the input's track files are renamed into place when all of its
-                        # records are done, and removed when one raises
-                        bases = CommandLineParser._predict_tracked(pipe, runner, filename, records_of(filename), outstream, kept,
-                                                                   tk.TrackFiles(track_plan, track_spec, filename), track_spec)
-                    elif _LOG.isEnabledFor(logging.DEBUG):
-                        # -vv: record by record through the staged form of the same path, a device sync and a clock around every
-                        # stage (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
-                        for header, rec in records_of(filename):
-                            rows, n = CommandLineParser._predict_staged(pipe, header, rec)
-                            bases += n
-                            outstream.write(rows_text(filename, header, rows))
-                            if kept is not None:
-                                kept.add(rows, 1)
-                    else:
-                        for kind, key, rows in runner.results(CommandLineParser._counted(records_of(filename), lambda n: None)):
-                            outstream.write(rows_text_batch(filename, key, rows) if kind == "batch" else rows_text(filename, key, rows))
-                            if kept is not None:
-                                kept.add(rows, len(key) if kind == "batch" else 1)
-                        bases = CommandLineParser._last_count
+                    # --track_dir, --bed_dir: the input's files are renamed into place when all of its records are done, and removed
+                    # when one raises
+                    files = tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None
+                    try:
+                        beds = bed.BedFiles(bed_plan, filename) if bed_plan is not None else None
+                    except BaseException:
+                        if files is not None:
+                            files.abort()
+                        raise
+                    bases = CommandLineParser._predict_file(pipe, runner, filename, records_of(filename), outstream, kept, files, beds)
                     if kept is not None:
                         outstream.flush()
                         t_mask = time.perf_counter()
@@ -475,110 +459,62 @@ class CommandLineParser:
                   else "fused, split operands (fp32-grade)" if pipe.split else "fused, fp16 operands")
         return pipe
 
-    _last_count = 0
-
     @staticmethod
-    def _counted(records, _cb):
-        """Pass (header, record) pairs through, adding up the bases they hold (for the per-file rate of -v)."""
+    def _predict_file(pipe, runner, filename, records, outstream, kept, files=None, beds=None) -> int:
+        """predict's loop over one input: the TSV rows of every record to `outstream` and to `kept` (_RowsByRecord, --mask_dir);
+        with --track_dir the track texts to `files` (tracks.TrackFiles), with --bed_dir every row's BED line to `beds`
+        (bed.BedFiles), both from the merged array the rows come from (`runner` was made with the same two choices).  -> bases read"""
+        from .evaluation import record_name
         from .fasta import DeviceRecord
-        CommandLineParser._last_count = 0
-        for header, rec in records:
-            CommandLineParser._last_count += max(rec.length, 0) + max(rec.startpos, 0) if isinstance(rec, DeviceRecord) else len(rec)
-            yield header, rec
-
-    @staticmethod
-    def _predict_tracked(pipe, runner, filename, records, outstream, kept, files, spec) -> int:
-        """predict's loop over one input with --track_dir: TSV rows as without it, the track text of every record to `files`
-        (tracks.TrackFiles).  -> bases read"""
-        from .evaluation import record_name
+        from .pipeline import record_indices
         from .runner import rows_text, rows_text_batch
-        from .tracks import record_texts
+        from .tracks import empty_texts, record_texts
+        named = files is not None or beds is not None           # the runner's keys are then (header, name of the track and BED lines)
+        bases = 0
         try:
             if _LOG.isEnabledFor(logging.DEBUG):
-                bases = 0
+                # -vv: record by record through the staged form of the same path, a device sync and a clock around every stage
+                # (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
                 for chrom, (header, rec) in enumerate(records):
-                    name = record_name(filename, header)
-                    sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec, chrom))
-                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, sink)
-                    if n == 0 and spec.bigwig:                      # no base to predict: still a chromosome of the bigWig
-                        from .pipeline import record_indices
-                        from .tracks import empty_texts
-                        files.write(empty_texts(spec, name, record_indices(rec)[0]))
-                    bases += n
-                    outstream.write(rows_text(filename, header, rows))
-                    if kept is not None:
-                        kept.add(rows, 1)
-            else:
-                keyed = (((header, record_name(filename, header)), rec) for header, rec in records)
-                for kind, key, rows, texts in runner.tracked_results(CommandLineParser._counted(keyed, lambda n: None)):
-                    if kind == "batch":
-                        outstream.write(rows_text_batch(filename, [header for header, _name in key], rows))
-                    else:
-                        outstream.write(rows_text(filename, key[0], rows))
-                    files.write(texts)
-                    if kept is not None:
-                        kept.add(rows, len(key) if kind == "batch" else 1)
-                bases = CommandLineParser._last_count
-        except BaseException:
-            files.abort()
-            raise
-        files.commit()
-        return bases
-
-    @staticmethod
-    def _predict_scored(pipe, runner, filename, records, outstream, kept, files, spec, bed_plan) -> int:
-        """predict's loop over one input with --bed_dir: TSV rows as without it, every row's BED line to the input's bed.BedFiles and,
-        with --track_dir as well (`files`, `spec`; else None), the track texts from the same merged array.  -> bases read"""
-        from .bed import BedFiles
-        from .evaluation import record_name
-        from .runner import rows_text, rows_text_batch
-        from .tracks import record_texts
-        try:
-            beds = BedFiles(bed_plan, filename)
-        except BaseException:
-            if files is not None:
-                files.abort()
-            raise
-        try:
-            if _LOG.isEnabledFor(logging.DEBUG):
-                bases = 0
-                for chrom, (header, rec) in enumerate(records):
-                    name = record_name(filename, header)
-                    sink = None
+                    name = record_name(filename, header) if named else None
+                    track_sink = score_sink = None
                     if files is not None:
-                        sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, spec, chrom))
-                    scored = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
-                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, sink, scored)
-                    if n == 0 and files is not None and spec.bigwig:    # no base to predict: still a chromosome of the bigWig
-                        from .pipeline import record_indices
-                        from .tracks import empty_texts
-                        files.write(empty_texts(spec, name, record_indices(rec)[0]))
+                        track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
+                    if beds is not None:
+                        score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
+                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
+                    if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
+                        files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
                     bases += n
                     outstream.write(rows_text(filename, header, rows))
                     if kept is not None:
                         kept.add(rows, 1)
             else:
-                keyed = (((header, record_name(filename, header)), rec) for header, rec in records)
-                for kind, key, rows, scores, texts in runner.scored_results(CommandLineParser._counted(keyed, lambda n: None)):
-                    if kind == "batch":
-                        outstream.write(rows_text_batch(filename, [header for header, _name in key], rows))
-                        beds.write([name for _header, name in key], True, rows, scores)
-                    else:
-                        outstream.write(rows_text(filename, key[0], rows))
-                        beds.write([key[1]], False, rows, scores)
+                def keyed():
+                    nonlocal bases
+                    for header, rec in records:
+                        bases += max(rec.length, 0) + max(rec.startpos, 0) if isinstance(rec, DeviceRecord) else len(rec)
+                        yield ((header, record_name(filename, header)) if named else header), rec
+                for kind, key, rows, scores, texts in runner.outputs(keyed()):
+                    keys = key if kind == "batch" else [key]
+                    headers = [header for header, _name in keys] if named else keys
+                    outstream.write(rows_text_batch(filename, headers, rows) if kind == "batch" else rows_text(filename, headers[0], rows))
+                    if beds is not None:
+                        beds.write([name for _header, name in keys], kind == "batch", rows, scores)
                     if files is not None:
                         files.write(texts)
                     if kept is not None:
-                        kept.add(rows, len(key) if kind == "batch" else 1)
-                bases = CommandLineParser._last_count
+                        kept.add(rows, len(keys))
         except BaseException:
-            beds.abort()
+            if beds is not None:
+                beds.abort()
             if files is not None:
                 files.abort()
             raise
         if files is not None:
             files.commit()
-        beds.commit()
+        if beds is not None:
+            beds.commit()
         return bases
 
     @staticmethod

@@ -145,5 +145,15 @@ def check(rc: int, what: str = "") -> None:
         raise DgrpError(f"{what or 'libdeepgrp_hip'} failed (code {rc}): {msg}")
 
 
+def name_blob(names):
+    """Names as the entries take them: str (UTF-8, surrogateescape) or bytes -> (the names as bytes, their bytes back to back,
+    int64 offsets [len(names) + 1] into those)."""
+    import numpy as np
+    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+    off = np.zeros(len(raw) + 1, np.int64)
+    np.cumsum([len(x) for x in raw], out=off[1:])
+    return raw, b"".join(raw), off
+
+
 def exported_symbols():
     return sorted(_SIGNATURES)

@@ -16,7 +16,7 @@ import ctypes as C
 import os
 import sys
 import tempfile
-from typing import List, NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -96,26 +96,20 @@ class BedFiles:
         self.tmp = None
 
 
-def _raw(names: Sequence) -> List[bytes]:
-    return [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
-
-
 def format_rows(names: Sequence, by_contig: bool, rows, scores, min_score: int = 0) -> bytes:
     """dgrp_format_bed_rows (host code of the library): the BED lines of `rows` (SEGMENT_DTYPE) with `scores` (ROW_SCORE_DTYPE)."""
-    from ._lib import check, lib
+    from ._lib import check, lib, name_blob
     from .pipeline import ROW_SCORE_DTYPE, SEGMENT_DTYPE
     L = lib()
     rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
     scores = np.ascontiguousarray(scores, dtype=ROW_SCORE_DTYPE)
     if len(rows) != len(scores):
         raise ValueError(f"{len(rows)} rows but {len(scores)} scores")
-    raw = _raw(names)
-    off = np.zeros(len(raw) + 1, np.int64)
-    np.cumsum([len(x) for x in raw], out=off[1:])
+    raw, blob, off = name_blob(names)
     cap = int(L.dgrp_format_bed_bound(len(rows), max(len(x) for x in raw)))
     out = np.empty(cap, np.uint8)
     written = C.c_int64()
-    check(L.dgrp_format_bed_rows(b"".join(raw), off.ctypes.data, len(raw), int(by_contig), rows.ctypes.data, scores.ctypes.data, len(rows),
+    check(L.dgrp_format_bed_rows(blob, off.ctypes.data, len(raw), int(by_contig), rows.ctypes.data, scores.ctypes.data, len(rows),
                                  int(min_score), out.ctypes.data, cap, C.byref(written)), "dgrp_format_bed_rows")
     return out[:written.value].tobytes()
 
@@ -170,7 +164,7 @@ def _half_up(num: int, den: int, k: int) -> int:
 
 def reference_lines(names: Sequence, by_contig: bool, rows, scores, min_score: int = 0) -> bytes:
     """The BED lines in Python integers: the format's statement."""
-    raw = _raw(names)
+    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
     out = []
     for row, sc in zip(rows, scores):
         total, bases, agree, qmin = int(sc["sum"]), int(sc["bases"]), int(sc["agree"]), int(sc["qmin"])

@@ -17,7 +17,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, lib, name_blob
 from .fasta import DeviceRecord
 
 SEGMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")])
@@ -296,6 +296,18 @@ def record_indices(rec) -> Tuple[int, torch.Tensor]:
     return upload_sequence(rec.encode("utf-8") if isinstance(rec, str) else bytes(rec))
 
 
+def _segment_rows(dev, cap: int, launch) -> np.ndarray:
+    """The segment rows of a launch that learns their number only by running: launch(d_rec, cap) writes up to `cap` rows and
+    returns how many there are; where the guess was short (rare) it runs again with room for all of them."""
+    while True:
+        rec = torch.empty(cap * SEGMENT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        total = launch(rec, cap)
+        if total <= cap:
+            break
+        cap = total
+    return rec[: total * SEGMENT_DTYPE.itemsize].cpu().numpy().view(SEGMENT_DTYPE).copy()
+
+
 class ContigPipeline:
     """Runs records through the device pipeline with the reference's CLI parameters."""
 
@@ -433,20 +445,15 @@ class ContigPipeline:
         dev = labels.device
         if n == 0:
             return np.zeros(0, SEGMENT_DTYPE)
-        cap = cap if cap is not None else max(1024, n // 64)
         wb = L.dgrp_segments_workspace_bytes(n)
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
         count = torch.zeros(1, dtype=torch.int64, device=dev)
-        while True:
-            rec = torch.empty(cap * SEGMENT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+
+        def launch(rec, cap):
             check(L.dgrp_segments(_ptr(labels), n, offset, contig, _ptr(rec), cap, _ptr(count), _ptr(work), wb,
                                   stream_ptr()), "dgrp_segments")
-            total = int(count.item())
-            if total <= cap:
-                break
-            cap = total                                     # rare: more segments than guessed, run again
-        host = rec[: total * SEGMENT_DTYPE.itemsize].cpu().numpy()
-        return host.view(SEGMENT_DTYPE).copy()
+            return int(count.item())
+        return _segment_rows(dev, cap if cap is not None else max(1024, n // 64), launch)
 
     # predict --track_dir
     def track_text(self, merged: torch.Tensor, startpos: int, name, cls: int, digits: int = 2, bin: int = 1) -> bytes:
@@ -473,18 +480,14 @@ class ContigPipeline:
         dev = d_idx.device
         wb = L.dgrp_record_workspace_bytes(self.handle, n, self.step, int(self.use_mss))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        cap = max(1024, n // 64)
         count = C.c_int64(0)
-        while True:
-            rec = torch.empty(cap * SEGMENT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+
+        def launch(rec, cap):
             check(L.dgrp_predict_record(self.handle, _ptr(d_idx), n, self.step, self.batch, self.min_mss_len,
                                         self.xdrop_len, int(self.use_mss), int(startpos), int(contig), _ptr(rec), cap,
                                         C.byref(count), _ptr(work), wb, stream_ptr()), "dgrp_predict_record")
-            if count.value <= cap:
-                break
-            cap = int(count.value)                          # rare: more segments than guessed, run again
-        host = rec[: count.value * SEGMENT_DTYPE.itemsize].cpu().numpy()
-        return host.view(SEGMENT_DTYPE).copy()
+            return int(count.value)
+        return _segment_rows(dev, max(1024, n // 64), launch)
 
     def batchable(self) -> bool:
         """dgrp_predict_batch covers every model on the MSS path (the -m softmax is normalised per record)."""
@@ -507,21 +510,17 @@ class ContigPipeline:
         if wb <= 0:
             raise ValueError("run_batch: every record of a batch needs at least one base")
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        cap = max(1024, int(ln.sum()) // 64 + 2 * nrec)
         count = C.c_int64(0)
-        while True:
-            rec = torch.empty(cap * SEGMENT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+
+        def launch(rec, cap):
             args = (self.handle, _ptr(d_base), nrec, off.ctypes.data, ln.ctypes.data, sp.ctypes.data, cg.ctypes.data, self.step,
                     self.batch, self.min_mss_len, self.xdrop_len, _ptr(rec), cap, C.byref(count), _ptr(work), wb, stream_ptr())
             if d_probs is None:
                 check(L.dgrp_predict_batch(*args), "dgrp_predict_batch")
             else:
                 check(L.dgrp_predict_batch_probs(*args, _ptr(d_probs)), "dgrp_predict_batch_probs")
-            if count.value <= cap:
-                break
-            cap = int(count.value)
-        host = rec[: count.value * SEGMENT_DTYPE.itemsize].cpu().numpy()
-        return host.view(SEGMENT_DTYPE).copy()
+            return int(count.value)
+        return _segment_rows(dev, max(1024, int(ln.sum()) // 64 + 2 * nrec), launch)
 
     def track_text_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, names, classes, digits: int = 2,
                                 bin: int = 1) -> Tuple[torch.Tensor, np.ndarray]:
@@ -529,19 +528,9 @@ class ContigPipeline:
         lengths[r]) of `d_probs` (float32 [*, C]), `names[r]` (str, surrogateescape, or bytes) its first column.  -> (uint8 device
         tensor, offsets [len(classes) + 1]): the text is class-major, class classes[k] of all records in order at [off[k], off[k + 1])."""
         L = lib()
-        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
-            raise ValueError("track_text_batch_device takes a contiguous float32 [rows, C] array")
-        c = int(d_probs.shape[1])
-        nrec, ncls = len(lengths), len(classes)
-        dev = d_probs.device
-        r0 = np.ascontiguousarray(row0, np.int64)
-        ln = np.ascontiguousarray(lengths, np.int64)
-        sp = np.ascontiguousarray(startposes, np.int64)
-        cl = np.ascontiguousarray(classes, np.int32)
-        raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
-        noff = np.zeros(nrec + 1, np.int64)
-        np.cumsum([len(x) for x in raw], out=noff[1:])
-        blob = b"".join(raw)
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_text_batch_device", row0, lengths, startposes, classes)
+        c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
+        blob, noff = name_blob(names)[1:]
         wb = L.dgrp_track_batch_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
         if wb <= 0:
             raise ValueError(f"track_text_batch_device: bad record lengths, start positions, bin {bin} or class count {ncls}")
@@ -569,22 +558,12 @@ class ContigPipeline:
         none of its lines ends behind the window.  A record that ends above 2^29 raises tabix.IndexRefused."""
         from .tabix import CHUNK_DTYPE, MAX_END, MIN_SHIFT, IndexRefused
         L = lib()
-        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
-            raise ValueError("track_index_batch_device takes a contiguous float32 [rows, C] array")
-        c = int(d_probs.shape[1])
-        nrec, ncls = len(lengths), len(classes)
-        dev = d_probs.device
-        r0 = np.ascontiguousarray(row0, np.int64)
-        ln = np.ascontiguousarray(lengths, np.int64)
-        sp = np.ascontiguousarray(startposes, np.int64)
-        cl = np.ascontiguousarray(classes, np.int32)
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_index_batch_device", row0, lengths, startposes, classes)
+        c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
         over = np.flatnonzero(sp + ln > MAX_END)
         if over.size:
             raise IndexRefused(f"record {int(over[0])} ends at {int((sp + ln)[over[0]])}, above 2^29, the largest coordinate of a tabix index")
-        raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
-        noff = np.zeros(nrec + 1, np.int64)
-        np.cumsum([len(x) for x in raw], out=noff[1:])
-        blob = b"".join(raw)
+        blob, noff = name_blob(names)[1:]
         wpref = np.zeros(nrec + 1, np.int64)
         np.cumsum(((sp + ln - 1) >> MIN_SHIFT) + 1, out=wpref[1:])
         nwin = int(wpref[-1])
@@ -608,7 +587,8 @@ class ContigPipeline:
         return host, off, linear[:ncls * nwin].cpu().numpy().reshape(ncls, nwin), wpref
 
     @staticmethod
-    def _track_tables(d_probs: torch.Tensor, row0, lengths, startposes, classes, who: str):
+    def _track_tables(d_probs: torch.Tensor, who: str, row0, lengths, startposes, classes=()):
+        """The check every method that takes `d_probs` makes, and its record tables as the library reads them."""
         if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
             raise ValueError(f"{who} takes a contiguous float32 [rows, C] array")
         return (np.ascontiguousarray(row0, np.int64), np.ascontiguousarray(lengths, np.int64), np.ascontiguousarray(startposes, np.int64),
@@ -622,7 +602,7 @@ class ContigPipeline:
         `rec` counts the records of this call, chromId is chrom0 + rec."""
         from .bigwig import SECTION_DTYPE
         L = lib()
-        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, row0, lengths, startposes, classes, "track_sections_batch_device")
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_sections_batch_device", row0, lengths, startposes, classes)
         c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
         wb = L.dgrp_track_sections_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls)
         if wb <= 0:
@@ -650,7 +630,7 @@ class ContigPipeline:
         table, rows of bigwig.ZOOM_BLOCK_DTYPE; block offsets, as the record offsets; totals, bigwig.TOTALS_DTYPE [len(classes)])."""
         from .bigwig import TOTALS_DTYPE, ZOOM_BLOCK_DTYPE, ZOOM_LEVELS
         L = lib()
-        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, row0, lengths, startposes, classes, "track_zoom_batch_device")
+        r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_zoom_batch_device", row0, lengths, startposes, classes)
         c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
         wb = L.dgrp_track_zoom_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls)
         if wb <= 0:
@@ -694,27 +674,13 @@ class ContigPipeline:
                                          _ptr(work), wb, stream_ptr()), "dgrp_zlib_compress_batch")
         return out[:got.value], sizes
 
-    def run_batch_tracked(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs, names, spec, chrom0: int = 0):
-        """run_batch with probability tracks: one dgrp_predict_batch_probs call, then one dgrp_track_text_batch call on its merged
-        probabilities.  -> (rows, texts), texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
+    def batch_track_texts(self, d_probs: torch.Tensor, row0, ln, startposes, names, spec, chrom0: int = 0):
+        """The track texts of a batch from its merged probabilities (run_batch_probs: record r at rows [row0[r], row0[r] + ln[r])),
+        one dgrp_track_text_batch call: texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
         give one after the other); with spec.gzip_level the BGZF members of that slice instead (no EOF member), deflated on the
         device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member; with spec.index the batch's
         tracks.WriteIndex comes with them (texts.index); with spec.bigwig tracks.bigwig_write's result instead (chrom0: the
         ordinal of the batch's first record in its input)."""
-        L = lib()
-        nrec = len(lengths)
-        if nrec == 0:
-            return np.zeros(0, SEGMENT_DTYPE), [b""] * len(spec.classes)
-        ln = np.ascontiguousarray(lengths, np.int64)
-        total = int(L.dgrp_batch_rows(nrec, ln.ctypes.data))
-        d_probs = torch.empty((total, self.model.classes), dtype=torch.float32, device=d_base.device)
-        rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
-        row0 = np.zeros(nrec, np.int64)
-        np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
-        return rows, self.batch_track_texts(d_probs, row0, ln, startposes, names, spec, chrom0)
-
-    def batch_track_texts(self, d_probs: torch.Tensor, row0, ln, startposes, names, spec, chrom0: int = 0):
-        """The `texts` of run_batch_tracked from a batch's merged probabilities (record r at rows [row0[r], row0[r] + ln[r]))."""
         if spec.bigwig:                                      # --track_bigwig: sections and zoom blocks instead of text
             from .tracks import bigwig_write
             return bigwig_write(self, d_probs, row0, ln, startposes, names, spec, chrom0)
@@ -743,12 +709,8 @@ class ContigPipeline:
         is rows [row0[r], row0[r] + lengths[r]) of `d_probs` (float32 [*, C]), its first row has coordinate startposes[r], and its
         segment rows are rows[row_off[r]:row_off[r + 1]] (SEGMENT_DTYPE, original coordinates, clipped to the record)."""
         L = lib()
-        if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous():
-            raise ValueError("row_scores_batch takes a contiguous float32 [rows, C] array")
+        r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "row_scores_batch", row0, lengths, startposes)
         rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
-        r0 = np.ascontiguousarray(row0, np.int64)
-        ln = np.ascontiguousarray(lengths, np.int64)
-        sp = np.ascontiguousarray(startposes, np.int64)
         ro = np.ascontiguousarray(row_off, np.int64)
         nrec = len(ln)
         if len(ro) != nrec + 1 or len(r0) != nrec or len(sp) != nrec or (nrec and int(ro[-1]) > len(rows)):
@@ -768,6 +730,15 @@ class ContigPipeline:
               "dgrp_row_scores_batch")
         return d_scores.cpu().numpy().view(ROW_SCORE_DTYPE).copy()
 
+    @staticmethod
+    def batch_row_offsets(rows: np.ndarray, contigs) -> np.ndarray:
+        """row_scores_batch's row_off for the rows of a run_batch call: they come back in record order, so record r's rows are the
+        running count of rows["contig"] -- for which `contigs` must ascend with the records."""
+        cg = np.ascontiguousarray(contigs, np.int64)
+        if not (np.diff(cg) > 0).all():
+            raise ValueError("batch_row_offsets: contigs must ascend with the records")
+        return np.searchsorted(rows["contig"], np.r_[cg, cg[-1] + 1], side="left").astype(np.int64)
+
     def row_scores(self, merged: torch.Tensor, startpos: int, rows: np.ndarray) -> np.ndarray:
         """The scores of one record's segment rows against its merged probabilities (ContigPipeline.merged): row i of `merged` has
         coordinate startpos + i."""
@@ -775,26 +746,19 @@ class ContigPipeline:
             return np.zeros(len(rows), ROW_SCORE_DTYPE)
         return self.row_scores_batch(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)])
 
-    def run_batch_scored(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs):
-        """run_batch with the rows' scores: one dgrp_predict_batch_probs call, then one dgrp_row_scores_batch call on its merged
-        probabilities.  -> (rows, scores, d_probs, row0): the probabilities [dgrp_batch_rows, C] stay on the device for a caller that
-        also writes tracks from them; record r starts at row row0[r].  `contigs` must ascend with the records (rows come back in
-        record order: the row offsets are the running count of rows["contig"])."""
-        L = lib()
-        nrec = len(lengths)
+    def run_batch_probs(self, d_base: torch.Tensor, offsets, lengths, startposes, contigs):
+        """run_batch that keeps the merged probabilities: one dgrp_predict_batch_probs call.  -> (rows, d_probs, row0): the
+        probabilities [dgrp_batch_rows, C] stay on the device for batch_track_texts and row_scores_batch (its row_off:
+        batch_row_offsets); record r starts at row row0[r]."""
         ln = np.ascontiguousarray(lengths, np.int64)
+        nrec = len(ln)
         row0 = np.zeros(nrec, np.int64)
         if nrec == 0:
-            return np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE), None, row0
-        total = int(L.dgrp_batch_rows(nrec, ln.ctypes.data))
-        d_probs = torch.empty((total, self.model.classes), dtype=torch.float32, device=d_base.device)
-        rows = self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs)
+            return np.zeros(0, SEGMENT_DTYPE), None, row0
         np.cumsum((ln[:-1] + 63) // 64 * 64, out=row0[1:])
-        cg = np.ascontiguousarray(contigs, np.int64)
-        if nrec > 1 and not (np.diff(cg) > 0).all():
-            raise ValueError("run_batch_scored: contigs must ascend with the records")
-        row_off = np.searchsorted(rows["contig"], np.r_[cg, cg[-1] + 1], side="left").astype(np.int64)
-        return rows, self.row_scores_batch(d_probs, row0, ln, startposes, rows, row_off), d_probs, row0
+        total = int(lib().dgrp_batch_rows(nrec, ln.ctypes.data))
+        d_probs = torch.empty((total, self.model.classes), dtype=torch.float32, device=d_base.device)
+        return self.run_batch(d_base, offsets, lengths, startposes, contigs, d_probs=d_probs), d_probs, row0
 
     def run(self, sequence, contig: int = 0) -> np.ndarray:
         startpos, d_idx = record_indices(sequence)

@@ -1,8 +1,9 @@
 """How the command line pushes records through the device pipeline: independent records (deepgrp/__main__.py:280-292)
 run on a small pool of host threads, one HIP stream each, with ordered results; consecutive short records of one
-ingest buffer go to the GPU as one batch (dgrp_predict_batch; with probability tracks dgrp_predict_batch_probs and
-dgrp_track_text_batch).  `RecordRunner.results` yields what the reference's loop would have produced record after
-record, and raises where that loop would raise."""
+ingest buffer go to the GPU as one batch.  `RecordRunner.outputs` yields what the reference's loop would have produced
+record after record -- the rows and, where asked for, the track texts (predict --track_dir) and the rows' scores (--bed_dir)
+from the same forward pass -- and raises where that loop would raise; `results` is its rows alone.  Every mode takes the
+same path: `work_items` groups, `run_item` runs a record or a batch, `in_order` keeps the order."""
 from __future__ import annotations
 
 import collections
@@ -17,28 +18,21 @@ import torch
 from .fasta import DeviceRecord
 from .pipeline import ContigPipeline, record_indices
 
-class _Tracked(NamedTuple):
-    """A work item of tracked_results: one record and the name of its track lines."""
-    name: str
+
+class _One(NamedTuple):
+    """A work item: one record, the name of its track and BED lines (None where neither is made), its ordinal in its input (the
+    chromId of --track_bigwig)."""
+    name: object
     rec: object
-    chrom: int = 0            # the record's ordinal in its input (the chromId of --track_bigwig)
+    chrom: int
 
 
-class _TrackedBatch(list):
-    """A batch work item of tracked_results: [((header, name), record), ...]; chrom0: the ordinal of its first record in the input."""
-    chrom0 = 0
+class _Batch(list):
+    """A batch work item: [(key, record), ...]; chrom0: the ordinal of its first record in its input."""
 
-
-class _Scored(NamedTuple):
-    """A work item of scored_results: one record, the name of its BED (and track) lines, its ordinal in the input."""
-    name: str
-    rec: object
-    chrom: int = 0
-
-
-class _ScoredBatch(list):
-    """A batch work item of scored_results, as _TrackedBatch."""
-    chrom0 = 0
+    def __init__(self, pairs, chrom0: int):
+        super().__init__(pairs)
+        self.chrom0 = chrom0
 
 
 _BATCH = object()             # key slot of a work item that is a batch of records (never equal to a user's key, e.g. a header "batch")
@@ -65,13 +59,11 @@ def _format(prefixes: List[bytes], by_contig: bool, rows) -> str:
     """dgrp_format_rows (host code of the library): one pass over the row records, no per-row Python objects."""
     import ctypes as C
 
-    from ._lib import check, lib
+    from ._lib import check, lib, name_blob
     from .pipeline import SEGMENT_DTYPE
     L = lib()
     rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
-    blob = b"".join(prefixes)
-    off = np.zeros(len(prefixes) + 1, np.int64)
-    np.cumsum([len(p) for p in prefixes], out=off[1:])
+    blob, off = name_blob(prefixes)[1:]
     cap = L.dgrp_format_rows_bound(len(rows), max(len(p) for p in prefixes))
     out = np.empty(cap, np.uint8)
     written = C.c_int64()
@@ -95,48 +87,59 @@ def rows_text_batch(filename: str, headers, rows) -> str:
 
 
 class RecordRunner:
-    """Runs (key, record) pairs -- record = DeviceRecord or sequence text -- and yields results in input order:
-    ("one", key, rows) for a record on its own, ("batch", [keys], rows) for a batch (rows["contig"] indexes the keys)."""
+    """Runs (key, record) pairs -- record = DeviceRecord or sequence text -- and yields results in input order (`outputs`,
+    `results`).  tracks (a tracks.TrackSpec): every record's track texts come with its rows; scores: the rows' scores
+    (pipeline.ROW_SCORE_DTYPE, predict --bed_dir) do.  With either, every key is (header, name), name the first column of the
+    record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged array; with neither,
+    keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch)."""
 
-    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None):
+    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None, scores: bool = False):
         self.pipe = pipe
-        self.tracks = tracks          # tracks.TrackSpec: every record's track text comes with its rows (tracked_results, scored_results)
+        self.tracks, self.scores = tracks, bool(scores)
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
         self._T, self._UP = m.vecsize, (m.units + 31) // 32 * 32
 
-    # ---- one record
-    def run_record(self, rec, contig: int = 0) -> np.ndarray:
-        if isinstance(rec, DeviceRecord):                 # parsed and encoded on the GPU
-            startpos, d_idx = record_indices(rec)
-            return self.pipe.run_idx(d_idx, startpos, contig)
-        return self.pipe.run(rec, contig)
-
-    def run_tracked(self, rec, name: str, chrom: int = 0):
-        """(rows, track texts) of one record: merged -> the text of every class of self.tracks -> labels -> segments."""
-        from .pipeline import SEGMENT_DTYPE
-        from .tracks import empty_texts, record_texts
-        startpos, d_idx = record_indices(rec)
-        if d_idx.numel() == 0:
-            return np.zeros(0, SEGMENT_DTYPE), empty_texts(self.tracks, name, startpos)
-        merged = self.pipe.merged(d_idx)
-        texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom)
-        return self.pipe.segments(self.pipe.labels(merged), startpos), texts
-
-    def run_scored(self, rec, name: str, chrom: int = 0):
-        """(rows, scores, track texts or None) of one record: merged -> [the texts of self.tracks] -> labels -> segments -> the rows'
-        scores (ContigPipeline.row_scores) from the same merged array."""
+    # ---- one work item -> (rows, scores or None, texts or None)
+    def run_record(self, rec, name=None, chrom: int = 0):
+        """One record: the fused call, or merged -> [the texts of self.tracks] -> labels -> segments -> [the rows' scores], because
+        the fused call keeps its merged array inside its workspace."""
+        if self.tracks is None and not self.scores:
+            if isinstance(rec, DeviceRecord):             # parsed and encoded on the GPU
+                startpos, d_idx = record_indices(rec)
+                return self.pipe.run_idx(d_idx, startpos), None, None
+            return self.pipe.run(rec), None, None
         from .pipeline import ROW_SCORE_DTYPE, SEGMENT_DTYPE
         from .tracks import empty_texts, record_texts
         startpos, d_idx = record_indices(rec)
-        if d_idx.numel() == 0:
-            texts = empty_texts(self.tracks, name, startpos) if self.tracks is not None else None
-            return np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE), texts
+        if d_idx.numel() == 0:                            # no base: no rows; with --track_bigwig still a chromosome (empty_texts)
+            return (np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE) if self.scores else None,
+                    empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
         merged = self.pipe.merged(d_idx)
         texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
         rows = self.pipe.segments(self.pipe.labels(merged), startpos)
-        return rows, self.pipe.row_scores(merged, startpos, rows), texts
+        return rows, self.pipe.row_scores(merged, startpos, rows) if self.scores else None, texts
+
+    def run_batch(self, batch: _Batch):
+        """A batch: rows of all its records, contig = position in the batch; scores go row by row with them, texts[k] is the text of
+        class self.tracks.classes[k] of all its records in order."""
+        recs = [r for _k, r in batch]
+        args = (recs[0].base, [r.offset for r in recs], [r.length for r in recs], [r.startpos for r in recs], list(range(len(recs))))
+        if self.tracks is None and not self.scores:
+            return self.pipe.run_batch(*args), None, None
+        rows, d_probs, row0 = self.pipe.run_batch_probs(*args)
+        ln = np.ascontiguousarray(args[2], np.int64)
+        scores = texts = None
+        if self.scores:
+            scores = self.pipe.row_scores_batch(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]))
+        if self.tracks is not None:
+            texts = self.pipe.batch_track_texts(d_probs, row0, ln, args[3], [k[1] for k, _r in batch], self.tracks,
+                                                batch.chrom0 if self.tracks.bigwig else 0)
+        return rows, scores, texts
+
+    def run_item(self, item):
+        return self.run_batch(item) if isinstance(item, _Batch) else self.run_record(item.rec, item.name, item.chrom)
 
     # ---- batching
     def _batch_cost(self, n: int) -> int:
@@ -173,41 +176,12 @@ class RecordRunner:
         if group:
             yield _BATCH, group
 
-    def run_item(self, item):
-        if isinstance(item, _Tracked):
-            if self.tracks.bigwig:                        # (the record's ordinal in its input is the chromId of its sections)
-                return self.run_tracked(item.rec, item.name, item.chrom)
-            return self.run_tracked(item.rec, item.name)
-        if isinstance(item, _TrackedBatch):               # the same with the track texts of the whole batch, class by class
-            rows, texts = self.pipe.run_batch_tracked(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
-                                                      [r.startpos for _k, r in item], list(range(len(item))),
-                                                      [k[1] for k, _r in item], self.tracks, *((item.chrom0,) if self.tracks.bigwig else ()))
-            return [k for k, _r in item], rows, texts
-        if isinstance(item, _Scored):
-            return self.run_scored(item.rec, item.name, item.chrom)
-        if isinstance(item, _ScoredBatch):                # rows, their scores and (with tracks) the texts from one merged array
-            lengths, startposes = [r.length for _k, r in item], [r.startpos for _k, r in item]
-            rows, scores, d_probs, row0 = self.pipe.run_batch_scored(item[0][1].base, [r.offset for _k, r in item], lengths, startposes,
-                                                                     list(range(len(item))))
-            texts = None
-            if self.tracks is not None:
-                texts = self.pipe.batch_track_texts(d_probs, row0, np.ascontiguousarray(lengths, np.int64), startposes,
-                                                    [k[1] for k, _r in item], self.tracks, item.chrom0 if self.tracks.bigwig else 0)
-            return [k for k, _r in item], rows, scores, texts
-        if isinstance(item, list):                        # a batch: rows of all its records, contig = position in the batch
-            rows = self.pipe.run_batch(item[0][1].base, [r.offset for _k, r in item], [r.length for _k, r in item],
-                                       [r.startpos for _k, r in item], list(range(len(item))))
-            return [k for k, _r in item], rows
-        return self.run_record(item)
-
     # ---- ordered execution
     @staticmethod
     def _size(item) -> int:
-        if isinstance(item, (_Tracked, _Scored)):
-            item = item.rec
-        if isinstance(item, list):
+        if isinstance(item, _Batch):
             return sum(r.length for _k, r in item)
-        return item.d_idx.numel() if isinstance(item, DeviceRecord) else len(item)
+        return item.rec.d_idx.numel() if isinstance(item.rec, DeviceRecord) else len(item.rec)
 
     def in_order(self, items: Iterable[Tuple[object, object]]) -> Iterator[Tuple[object, object]]:
         """`run_item` for every (key, item) on the pool; yields (key, result) in input order.  While one record is in
@@ -244,57 +218,23 @@ class RecordRunner:
                 k0, f0, _w0 = pending.popleft()
                 yield k0, f0.result()
 
-    def results(self, records: Iterable[Tuple[object, object]]):
-        for key, result in self.in_order(self.work_items(records)):
-            if key is _BATCH:
-                keys, rows = result
-                yield "batch", keys, rows
-            else:
-                yield "one", key, result
-
-    def tracked_results(self, records: Iterable[Tuple[object, object]]):
-        """With self.tracks; every key is (header, name), name the first column of the record's track lines
-        (evaluation.record_name): ("one", key, rows, texts) for a record on its own, ("batch", [keys], rows, texts) for a batch of
-        short records -- rows["contig"] indexes the keys, texts[k] is the text of class self.tracks.classes[k] of all its records in
-        order.  Records batch exactly when they do without tracks."""
+    def outputs(self, records: Iterable[Tuple[object, object]]):
+        """("one", key, rows, scores, texts) for a record on its own, ("batch", [keys], rows, scores, texts) for a batch of short
+        records (rows["contig"] indexes the keys); scores and texts are None where the runner was not asked for them.  Records
+        batch the same way whatever is asked for."""
         def items():
             chrom = 0                                     # records of this input so far
             for key, item in self.work_items(records):
                 if key is _BATCH:
-                    batch = _TrackedBatch(item)
-                    batch.chrom0 = chrom
+                    yield ("batch", [k for k, _r in item]), _Batch(item, chrom)
                     chrom += len(item)
-                    yield _BATCH, batch
                 else:
-                    yield key, _Tracked(key[1], item, chrom)
+                    yield ("one", key), _One(key[1] if self.tracks is not None or self.scores else None, item, chrom)
                     chrom += 1
-        for key, result in self.in_order(items()):
-            if key is _BATCH:
-                keys, rows, texts = result
-                yield "batch", keys, rows, texts
-            else:
-                rows, texts = result
-                yield "one", key, rows, texts
+        for head, result in self.in_order(items()):
+            yield head + result
 
-    def scored_results(self, records: Iterable[Tuple[object, object]]):
-        """tracked_results with the rows' scores (predict --bed_dir), self.tracks or not: ("one", key, rows, scores, texts) and
-        ("batch", [keys], rows, scores, texts); scores (pipeline.ROW_SCORE_DTYPE) go row by row with `rows`, texts is None without
-        self.tracks.  Records batch exactly when they do without scores."""
-        def items():
-            chrom = 0
-            for key, item in self.work_items(records):
-                if key is _BATCH:
-                    batch = _ScoredBatch(item)
-                    batch.chrom0 = chrom
-                    chrom += len(item)
-                    yield _BATCH, batch
-                else:
-                    yield key, _Scored(key[1], item, chrom)
-                    chrom += 1
-        for key, result in self.in_order(items()):
-            if key is _BATCH:
-                keys, rows, scores, texts = result
-                yield "batch", keys, rows, scores, texts
-            else:
-                rows, scores, texts = result
-                yield "one", key, rows, scores, texts
+    def results(self, records: Iterable[Tuple[object, object]]):
+        """`outputs` without scores and texts: ("one", key, rows) and ("batch", [keys], rows)."""
+        for kind, key, rows, _scores, _texts in self.outputs(records):
+            yield kind, key, rows

@@ -6,8 +6,8 @@ span in the TSV's coordinates, and the maximum probability of the class over the
 [k * bin, (k + 1) * bin) of the record's coordinates, clipped to the predicted span [startpos, startpos + n); consecutive bins of
 equal value are one line, and spans of value 0 are left out.  `reference_text` restates the format in numpy.
 
-Short records run as batches (ContigPipeline.run_batch_tracked: dgrp_predict_batch_probs, then dgrp_track_text_batch for all records
-and classes of the batch); the text of a batch is the records' texts one after the other.
+Short records run as batches (ContigPipeline.run_batch_probs: dgrp_predict_batch_probs, then batch_track_texts: dgrp_track_text_batch
+for all records and classes of the batch); the text of a batch is the records' texts one after the other.
 
 With `--track_gzip` the files are `<basename>.class<c>.bedGraph.gz`, BGZF as bgzip writes it: the text of a record (of a batch: of one
 class of all its records) is deflated on the device where it was written (gz.bgzf_compress_device, --gzip_level, 1 unless given) and
@@ -30,6 +30,8 @@ import tempfile
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
+
+from ._lib import name_blob
 
 _LOG = logging.getLogger(__name__)
 
@@ -179,10 +181,8 @@ def _zlib_pieces(pipe, d_in, d_table, stride: int, level: int):
 
 def empty_texts(spec: TrackSpec, name, startpos: int):
     """The write of a record without a predicted base: no text; with spec.bigwig its name and size for the chromosome tree."""
-    if not spec.bigwig:
-        return [b""] * len(spec.classes)
     out = TrackTexts(b"" for _ in spec.classes)
-    out.bigwig = BigWigWrite([name if isinstance(name, bytes) else name.encode("utf-8", "surrogateescape")], [int(startpos)], None, None)
+    out.bigwig = BigWigWrite(name_blob([name])[0], [int(startpos)], None, None) if spec.bigwig else None
     return out
 
 
@@ -191,7 +191,7 @@ def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpe
     from the device (dgrp_track_sections_batch, dgrp_track_zoom_batch), deflated there (dgrp_zlib_compress_batch).  chrom0 is
     the ordinal of the first record in its input: chromIds count from there."""
     from . import bigwig as bw
-    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+    raw = name_blob(names)[0]
     sizes = [int(sp) + int(n) for sp, n in zip(startposes, lengths)]
     out = TrackTexts(b"" for _ in spec.classes)
     for nm, end in zip(raw, sizes):
@@ -224,7 +224,7 @@ def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpe
 def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec) -> WriteIndex:
     """The WriteIndex of the records whose text track_text_batch_device gives for the same arguments."""
     from .tabix import MAX_END
-    raw = [nm if isinstance(nm, bytes) else nm.encode("utf-8", "surrogateescape") for nm in names]
+    raw = name_blob(names)[0]
     for nm, sp, n in zip(raw, startposes, lengths):
         if int(sp) + int(n) > MAX_END:
             return WriteIndex(raw, f"record {nm.decode('utf-8', 'replace')!r} ends at {int(sp) + int(n)}, above 2^29 = {MAX_END}, the "

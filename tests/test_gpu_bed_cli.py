@@ -35,7 +35,7 @@ def _fasta_bytes(recs):
 
 def _compose(model_file, recs, use_mss=True, fast=False, min_score=0, name=None):
     """-> (BED bytes, column 5 of every line before the filter, lines of the record without a window)
-    (a record without a base has no merged array, no rows and no lines: the command line's own rule, runner.run_scored)"""
+    (a record without a base has no merged array, no rows and no lines: the command line's own rule, RecordRunner.run_record)"""
     from deepgrp_amd import bed, model as dgmodel
     from deepgrp_amd.pipeline import ContigPipeline, upload_sequence
     model = dgmodel.load_model(model_file)
@@ -93,12 +93,12 @@ def test_bed_is_the_composition_on_every_path(tmp_path, monkeypatch, quiet, mode
     assert plain.read_bytes().count(b"\n") == want.count(b"\n")                       # a BED line per TSV row
 
     batched = []
-    real = ContigPipeline.run_batch_scored
+    real = ContigPipeline.run_batch_probs
 
     def counting(self, d_base, offsets, lengths, *a, **k):
         batched.append(len(lengths))
         return real(self, d_base, offsets, lengths, *a, **k)
-    monkeypatch.setattr(ContigPipeline, "run_batch_scored", counting)
+    monkeypatch.setattr(ContigPipeline, "run_batch_probs", counting)
 
     def run(tag, extra=(), top=()):
         d, tsv = tmp_path / f"bed_{tag}", tmp_path / f"{tag}.tsv"
@@ -146,7 +146,8 @@ def test_bed_is_the_composition_on_every_path(tmp_path, monkeypatch, quiet, mode
 
 
 def test_other_outputs_are_unchanged(tmp_path, monkeypatch):
-    """--mask_dir and every kind of --track_dir output beside --bed_dir: the same bytes as without it, and the same BED."""
+    """--mask_dir and every kind of --track_dir output beside --bed_dir: the same bytes as without it, and the same BED; under -vv
+    (the staged path, both sinks on every record) the same bytes again."""
     from deepgrp_amd import runner
     model_file, T = os.path.join(GOLDEN, MODELS[0][0]), MODELS[0][1]
     recs = _records(T, twins=False)                                                   # (a bigWig takes no two records of one name)
@@ -154,22 +155,38 @@ def test_other_outputs_are_unchanged(tmp_path, monkeypatch):
     fa.write_bytes(_fasta_bytes(recs))
     want = _compose(model_file, recs)[0]
     combos = {"text": [], "gz": ["--track_gzip", "--track_index"], "bw": ["--track_bigwig"]}
+    by_grouping = {}
     for small in (None, 0):
         with monkeypatch.context() as mp:
             if small is not None:
                 mp.setattr(runner, "SMALL_RECORD", small)
             for tag, extra in combos.items():
+                legs = [("0", False, []), ("1", True, [])]
+                # -vv never batches: once per combination.  Text is the same bytes however the records are grouped into writes; a
+                # bigWig's zoom blocks span the records of a write, so its bytes are those of the run that writes record by record
+                if (tag, small) in (("text", None), ("bw", 0)):
+                    legs.append(("vv", True, ["-vv"]))
                 outs = []
-                for with_bed in (False, True):
-                    d = tmp_path / f"{tag}_{small}_{int(with_bed)}"
+                for leg, with_bed, top in legs:
+                    d = tmp_path / f"{tag}_{small}_{leg}"
                     argv = FLAGS + ["predict", model_file, str(fa), "--output", str(d / "o.tsv"), "--mask_dir", str(d / "mask"),
                                     "--track_dir", str(d / "tracks"), "--track_bin", "3"] + extra
                     os.makedirs(d)
-                    _main(argv + (["--bed_dir", str(d / "bed")] if with_bed else []))
+                    try:
+                        _main(top + argv + (["--bed_dir", str(d / "bed")] if with_bed else []))
+                    finally:
+                        logging.getLogger("deepgrp_amd.__main__").setLevel(logging.WARNING)   # -vv sets the level for the process
                     outs.append((open(d / "o.tsv", "rb").read(), _files(d / "mask"), _files(d / "tracks")))
-                assert outs[0] == outs[1], (tag, small)
+                    if with_bed:
+                        assert _files(d / "bed") == {"in.fa.bed": want}, (tag, small, leg)
+                assert all(out == outs[0] for out in outs[1:]), (tag, small)
                 assert len(outs[1][2]) >= 4 and outs[1][1]
-                assert _files(d / "bed") == {"in.fa.bed": want}, (tag, small)
+                by_grouping[tag, small] = outs[0]
+    # batched or record by record: the same TSV and masked copy, the same track files, and for text tracks the same bytes in them
+    for tag in combos:
+        a, b = by_grouping[tag, None], by_grouping[tag, 0]
+        assert a[:2] == b[:2] and sorted(a[2]) == sorted(b[2]), tag
+    assert by_grouping["text", None] == by_grouping["text", 0]
 
 
 def test_all_n_record_leaves_no_bed(tmp_path):

@@ -280,16 +280,16 @@ def test_cli_tracks_run_short_records_as_batches(tmp_path, monkeypatch):
     fa = tmp_path / "asm.fa"
     _write_fasta(fa, recs)
     batches, singles = [], []
-    run_batch_tracked, track_text_device = ContigPipeline.run_batch_tracked, ContigPipeline.track_text_device
+    run_batch_probs, track_text_device = ContigPipeline.run_batch_probs, ContigPipeline.track_text_device
 
     def counted_batch(self, d_base, offsets, lengths, *a, **k):
         batches.append(len(lengths))
-        return run_batch_tracked(self, d_base, offsets, lengths, *a, **k)
+        return run_batch_probs(self, d_base, offsets, lengths, *a, **k)
 
     def counted_single(self, merged, startpos, name, *a, **k):
         singles.append(name)
         return track_text_device(self, merged, startpos, name, *a, **k)
-    monkeypatch.setattr(ContigPipeline, "run_batch_tracked", counted_batch)
+    monkeypatch.setattr(ContigPipeline, "run_batch_probs", counted_batch)
     monkeypatch.setattr(ContigPipeline, "track_text_device", counted_single)
     main(["predict", model_file, str(fa), "--output", str(tmp_path / "p.tsv"), "--mask_dir", str(tmp_path / "mp")])
     assert not batches and not singles

@@ -1,5 +1,5 @@
 """The batched track entries without a GPU: the four symbols of the ABI, every refusal of dgrp_track_text_batch with its message,
-the empty batch, the workspace function, and RecordRunner.work_items / tracked_results with a TrackSpec and a stand-in pipe."""
+the empty batch, the workspace function, and RecordRunner.work_items / outputs / results with a TrackSpec, with scores and a stand-in pipe."""
 import ctypes as C
 
 import numpy as np
@@ -124,47 +124,91 @@ def test_workspace_is_zero_on_bad_input_and_grows(L):
     assert wb(n=(1_000_000,), spos=(0,), ncls=3) >= 3 * 4 * 1_000_000
 
 
-def test_runner_batches_short_records_with_a_track_spec():
-    """work_items with a TrackSpec groups exactly as without one; tracked_results hands batches out as batches, the rest one by one,
-    in input order, and an all-N record raises in place."""
+SEG = [("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")]
+
+
+class FakeModel:
+    vecsize, units, classes, attention = 20, 32, 5, False
+
+
+class FakePipe:
+    """Stands in for a ContigPipeline: `seen` lists the methods the runner called, `calls` the (names, chrom0) of every batch's
+    texts -- both in the order the pool's threads got there, so they are compared as sets or sorted."""
+    model, step = FakeModel(), 4
+
+    def __init__(self):
+        self.seen, self.calls = [], []
+
+    def batchable(self):
+        return True
+
+    def run_batch(self, base, offsets, lengths, startposes, contigs, who="run_batch"):
+        self.seen.append(who)
+        out = np.zeros(len(lengths), dtype=SEG)
+        out["start"], out["end"], out["label"], out["contig"] = offsets, lengths, 1, contigs
+        return out
+
+    def run_idx(self, d_idx, startpos, contig=0):
+        self.seen.append("run_idx")
+        return np.array([(startpos, startpos + 1, 2, contig)], dtype=SEG)
+
+    def run(self, seq, contig=0):
+        self.seen.append("run")
+        return np.array([(0, len(seq), 2, contig)], dtype=SEG)
+
+    def run_batch_probs(self, base, offsets, lengths, startposes, contigs):
+        rows = self.run_batch(base, offsets, lengths, startposes, contigs, "run_batch_probs")
+        return rows, "probs", np.arange(len(lengths)) * 64
+
+    def merged(self, d_idx):
+        self.seen.append("merged")
+        raise AssertionError("the stand-in has no forward pass")
+
+    def batch_track_texts(self, d_probs, row0, ln, startposes, names, spec, chrom0=0):
+        assert d_probs == "probs" and len(row0) == len(ln) == len(startposes) == len(names)
+        self.calls.append((tuple(names), chrom0))
+        return [b"".join(b"%s:%d;" % (nm.encode(), c) for nm in names) for c in spec.classes]
+
+    def batch_row_offsets(self, rows, contigs):
+        from deepgrp_amd.pipeline import ContigPipeline
+        return ContigPipeline.batch_row_offsets(rows, contigs)                          # host arithmetic: the real one
+
+    def row_scores_batch(self, d_probs, row0, lengths, startposes, rows, row_off):
+        assert d_probs == "probs" and row_off.tolist() == list(range(len(lengths) + 1))     # the stand-in: a row per record
+        return [("score", int(n)) for n in lengths]
+
+
+class Buf:
+    def __getitem__(self, _s):
+        return self
+
+    def numel(self):
+        return 0
+
+
+def _nine_records():
     from deepgrp_amd import runner as rn
     from deepgrp_amd.fasta import DeviceRecord
-    from deepgrp_amd.tracks import TrackSpec
-    SEG = [("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")]
-
-    class FakeModel:
-        vecsize, units, classes, attention = 20, 32, 5, False
-
-    class FakePipe:
-        model, step = FakeModel(), 4
-        calls = []
-        def batchable(self):
-            return True
-        def run_batch(self, base, offsets, lengths, startposes, contigs):
-            out = np.zeros(len(lengths), dtype=SEG)
-            out["start"], out["end"], out["label"], out["contig"] = offsets, lengths, 1, contigs
-            return out
-        def run_batch_tracked(self, base, offsets, lengths, startposes, contigs, names, spec):
-            self.calls.append(list(names))
-            return self.run_batch(base, offsets, lengths, startposes, contigs), [b"".join(b"%s:%d;" % (nm.encode(), c) for nm in names)
-                                                                               for c in spec.classes]
-
-    class Buf:
-        def __getitem__(self, _s):
-            return self
-        def numel(self):
-            return 0
-
     a, b = Buf(), Buf()
-    spec = TrackSpec((1, 3), 2, 1)
     key = lambda h: (h + " description", h)
-    recs = [(key("r0"), DeviceRecord(0, None, 100, a, 0)), (key("r1"), DeviceRecord(2, None, 50, a, 200)),
+    return [(key("r0"), DeviceRecord(0, None, 100, a, 0)), (key("r1"), DeviceRecord(2, None, 50, a, 200)),
             (key("r2"), DeviceRecord(0, None, 70, b, 0)),                                  # other buffer: new batch
             (key("r3"), "ACGT"),                                                           # text record: single
             (key("r4"), DeviceRecord(0, None, 30, b, 100)),
             (key("r5"), DeviceRecord(0, None, rn.SMALL_RECORD + 1, b, 200)),               # long: single
             (key("r6"), DeviceRecord(4, None, -4, b, 300)),                                # all-N: single (and raises when run)
             (key("r7"), DeviceRecord(1, None, 10, b, 400)), (key("r8"), DeviceRecord(1, None, 10, b, 500))]
+
+
+def test_runner_batches_short_records_with_a_track_spec():
+    """work_items with a TrackSpec groups exactly as without one; outputs hands batches out as batches, the rest one by one,
+    in input order, and an all-N record raises in place."""
+    from deepgrp_amd import runner as rn
+    from deepgrp_amd.fasta import DeviceRecord
+    from deepgrp_amd.tracks import TrackSpec
+    spec = TrackSpec((1, 3), 2, 1)
+    key = lambda h: (h + " description", h)
+    recs = _nine_records()
     pipe = FakePipe()
     with_tracks, without = rn.RecordRunner(pipe, workers=2, tracks=spec), rn.RecordRunner(pipe, workers=2)
     shape = lambda r: [("batch", [kk[1] for kk, _ in v]) if k is rn._BATCH else (k[1], None) for k, v in r.work_items(recs)]
@@ -172,20 +216,77 @@ def test_runner_batches_short_records_with_a_track_spec():
     assert shape(with_tracks) == want == shape(without)
     assert with_tracks._batch_cost(1000) > without._batch_cost(1000)
     # batches come out as batches with the texts of the whole batch; the all-N record stops the run where it stands
-    def one(rec, name):
+    def one(rec, name, chrom):
         if isinstance(rec, DeviceRecord) and rec.length < 0:
             raise ValueError("negative dimensions are not allowed")
-        return np.zeros(0, SEG), [b"one:" + name.encode()] * 2
-    with_tracks.run_tracked = one
+        return np.zeros(0, SEG), None, [b"one:" + name.encode()] * 2
+    with_tracks.run_record = one
     got = []
     with pytest.raises(ValueError, match="negative dimensions"):
-        for kind, k, rows, texts in with_tracks.tracked_results(recs):
+        for kind, k, rows, scores, texts in with_tracks.outputs(recs):
+            assert scores is None
             got.append((kind, [kk[1] for kk in k] if kind == "batch" else k[1], len(rows), texts))
     assert [(g[0], g[1]) for g in got] == [("batch", ["r0", "r1"]), ("batch", ["r2"]), ("one", "r3"), ("batch", ["r4"]), ("one", "r5")]
     assert got[0][3] == [b"r0:1;r1:1;", b"r0:3;r1:3;"] and got[0][2] == 2
     assert got[2][3] == [b"one:r3"] * 2
-    assert pipe.calls[:3] == [["r0", "r1"], ["r2"], ["r4"]]
+    assert sorted(names for names, _chrom0 in pipe.calls)[:3] == [("r0", "r1"), ("r2",), ("r4",)]
     # records that do not batch (text, long, text) come out record by record, with their keys and their own texts
     lone = [recs[3], recs[5], (key("r9"), "TTGA")]
-    assert [(kind, k, texts) for kind, k, _rows, texts in with_tracks.tracked_results(lone)] == \
+    assert [(kind, k, texts) for kind, k, _rows, _scores, texts in with_tracks.outputs(lone)] == \
         [("one", key(h), [b"one:" + h.encode()] * 2) for h in ("r3", "r5", "r9")]
+
+
+def test_one_path_for_rows_tracks_and_scores():
+    """The four runners (tracks or not, scores or not) group the same records into the same work items; outputs yields None for
+    what was not asked for and a batch's scores and texts together; the plain runner's results are 3-tuples from the fused calls
+    alone; the record ordinals count the input's records without a gap or a repeat."""
+    from deepgrp_amd import runner as rn
+    from deepgrp_amd.fasta import DeviceRecord
+    from deepgrp_amd.tracks import TrackSpec
+    recs = _nine_records()
+    spec = TrackSpec((1, 3), 2, 1, None, False, True)                                       # bigWig: the ordinals reach the pipe
+    runners = {(t, sc): rn.RecordRunner(FakePipe(), workers=2, tracks=spec if t else None, scores=sc)
+               for t in (False, True) for sc in (False, True)}
+    shape = lambda r: [("batch", [kk[1] for kk, _ in v]) if k is rn._BATCH else (k[1], None) for k, v in r.work_items(recs)]
+    shapes = [shape(r) for r in runners.values()]
+    assert all(sh == shapes[0] for sh in shapes) and len(shapes[0]) == 7 and sum(len(v or [0]) for _k, v in shapes[0]) == 9
+
+    singles = []                                                                            # (name, chrom) of every lone record
+
+    def one(r):
+        def run(rec, name, chrom):
+            singles.append((name, chrom))
+            if isinstance(rec, DeviceRecord) and rec.length < 0:
+                raise ValueError("negative dimensions are not allowed")
+            return np.zeros(0, SEG), [] if r.scores else None, [b"one"] if r.tracks is not None else None
+        return run
+    for (t, sc), r in runners.items():
+        if t or sc:
+            r.run_record = one(r)
+        del singles[:]
+        got = []
+        with pytest.raises(ValueError, match="negative dimensions"):
+            for out in (r.outputs(recs) if t or sc else r.outputs([(k[0], rec) for k, rec in recs])):
+                got.append(out)
+        assert [len(out) for out in got] == [5] * 5 and [out[0] for out in got] == ["batch", "batch", "one", "batch", "one"], (t, sc)
+        for kind, _key, rows, scores, texts in got:
+            assert (scores is not None) == sc and (texts is not None) == t, (t, sc, kind)
+        # a batch's scores and texts come together, from one run_batch_probs call
+        if t and sc:
+            assert got[0][3] == [("score", 100), ("score", 50)] and got[0][4] == [b"r0:1;r1:1;", b"r0:3;r1:3;"]
+            assert set(r.pipe.seen) == {"run_batch_probs"}
+        if t:
+            # ordinals: the chrom0 of the batches and the chrom of the singles count the records, the all-N record included (the
+            # batch behind it, records 7 and 8, may have run on the pool before the all-N record raised)
+            before = {(("r0", "r1"), 0), (("r2",), 2), (("r4",), 4)}
+            assert before <= set(r.pipe.calls) <= before | {(("r7", "r8"), 7)} and len(r.pipe.calls) == len(set(r.pipe.calls)), r.pipe.calls
+            assert sorted(singles) == [("r3", 3), ("r5", 5), ("r6", 6)], (sc, singles)
+    # the plain runner: 3-tuples with arbitrary keys, and only the fused calls
+    plain = rn.RecordRunner(FakePipe(), workers=2)
+    ok = [(k[0], rec) for k, rec in recs if not (isinstance(rec, DeviceRecord) and rec.length < 0)]
+    res = list(plain.results(ok))
+    assert [len(x) for x in res] == [3] * 6
+    assert [(x[0], x[1]) for x in res][:3] == [("batch", ["r0 description", "r1 description"]), ("batch", ["r2 description"]),
+                                               ("one", "r3 description")]
+    assert set(plain.pipe.seen) == {"run_batch", "run_idx", "run"} and len(plain.pipe.seen) == 6
+    assert [x[3:] for x in plain.outputs(ok)] == [(None, None)] * 6
