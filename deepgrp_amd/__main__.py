@@ -22,7 +22,9 @@ Differences, all additive:
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
   * `train <parameter.toml> <trainfile.npz> <validfile.npz> <bedfile>` trains a GRU model on the GPU (deepgrp_amd/training.py:
     forward, backward through time and the optimizer are HIP kernels) and writes a Keras HDF5 file `predict` loads; `--seed N`
-    (an addition) seeds the initial weights, the sampler and the dropout masks.  No TensorBoard output.
+    (an addition) seeds the initial weights, the sampler and the dropout masks.  No TensorBoard output;
+  * `optimize <space.toml> <parameter.toml> <trainfile.npz> <validfile.npz> <bedfile>` runs the hyper-parameter search of
+    deepgrp/optimization.py as seeded random search (deepgrp_amd/optimization.py), `--cohort` trials trained side by side.
 """
 from __future__ import annotations
 
@@ -36,6 +38,8 @@ import numpy as np
 
 logging.basicConfig()
 _LOG = logging.getLogger(__name__)
+
+DEFAULT_COHORT = 8                   # optimize --cohort: the job count with the lowest measured time per job
 
 
 def _read_multi_fasta(filestream: TextIO) -> Iterator[Tuple[str, str]]:
@@ -227,6 +231,23 @@ class CommandLineParser:
         train.add_argument("--seed", type=int, default=None,
                            help="(addition) seed of the initial weights, the sampler and the dropout masks: the same seed "
                                 "writes the same model file, byte for byte")
+        optimize = subparsers.add_parser(name="optimize", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                                         description="(addition) hyper-parameter search (deepgrp/optimization.py): seeded random "
+                                                     "search over the [space] table of a TOML file, trials trained side by side on "
+                                                     "the GPU, results in <project_root_dir>/results.json")
+        optimize.add_argument("space", type=str, help='TOML file with a [space] table: gru_units = ["qnormal", 34, 5, 2]; kinds: '
+                                                      "uniform, quniform, normal, qnormal, loguniform, lognormal, choice")
+        optimize.add_argument("parameter", type=str)
+        optimize.add_argument("trainfile", type=str)
+        optimize.add_argument("validfile", type=str)
+        optimize.add_argument("bedfile", type=str)
+        optimize.add_argument("--max_evals", type=int, default=20, help="trials to add to results.json")
+        optimize.add_argument("--cohort", type=int, default=DEFAULT_COHORT,
+                              help="trials trained side by side, 1..64 (more than 8 run in slices of 8 per step)")
+        optimize.add_argument("--seed", type=int, default=None, help="seed of the search: trial t of a seed is the same trial "
+                                                                     "whatever --cohort is and wherever a run was resumed")
+        optimize.add_argument("--project_root_dir", type=str, default=None,
+                              help="where results.json and tf_logs/ go (default: project_root_dir of the parameter file)")
         predict = subparsers.add_parser(name="predict", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                         description="predict using a deepgrp model")
         predict.add_argument("model", type=str, help="Keras model in HDF5 format")
@@ -281,7 +302,7 @@ class CommandLineParser:
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
         # README form `deepgrp <modelfile> <fastafile>`: insert the sub-command before the first positional
-        if not any(a in ("predict", "train", "verify", "evaluate") for a in argv):
+        if not any(a in ("predict", "train", "verify", "evaluate", "optimize") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
                            "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score"}
@@ -895,6 +916,71 @@ class CommandLineParser:
         _LOG.info("Saving model as %s", args.modelfile)
         dgmodel.save_keras_hdf5(args.modelfile, best["kernel"], best["recurrent_kernel"], best["bias"], best["ff_kernel"],
                                 best["ff_bias"], best["scale"], vecsize=int(parameter.vecsize), config=config)
+
+    @staticmethod
+    def optimize(args: argparse.Namespace, options) -> None:
+        """Hyper-parameter search (deepgrp/optimization.py, driven by the reference's notebook): data as `train` loads it, the
+        space from the [space] table, `--max_evals` trials in cohorts of `--cohort`, one line per finished trial."""
+        import functools
+        import json
+        import tomli
+        from . import model as dgmodel
+        from . import optimization as dgopt
+        from . import preprocessing as dgpreprocess
+        for path in (args.space, args.parameter, args.trainfile, args.validfile, args.bedfile):
+            if not os.path.isfile(path):
+                sys.exit(f"optimize: {path}: no such file")
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+        if world > 1:
+            sys.exit(f"optimize: WORLD_SIZE = {world}: the search runs in one process on one GPU")
+        if not 1 <= args.cohort <= 64:
+            sys.exit(f"optimize: --cohort {args.cohort}: 1..64 trials can be trained side by side")
+        if args.max_evals < 1:
+            sys.exit(f"optimize: --max_evals {args.max_evals}: at least one trial")
+        with open(args.space, "rb") as file:
+            try:
+                space = tomli.load(file).get("space")
+            except tomli.TOMLDecodeError as exc:
+                sys.exit(f"optimize: {args.space}: {exc}")
+        if not isinstance(space, dict) or not space:
+            sys.exit(f"optimize: {args.space}: no [space] table")
+        try:
+            dgopt.check_space(space)
+        except ValueError as exc:
+            sys.exit(f"optimize: {args.space}: {exc}")
+        with open(args.parameter, "r") as file:
+            parameter = dgmodel.Options.from_toml(file)
+        if args.project_root_dir is not None:
+            parameter.project_root_dir = args.project_root_dir
+        train_chr = os.path.basename(args.trainfile).split(".")[0]
+        val_chr = os.path.basename(args.validfile).split(".")[0]
+        _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
+        train_fwd = dgpreprocess.load_onehot_npz(args.trainfile)
+        val_fwd = dgpreprocess.load_onehot_npz(args.validfile)
+        y_train = dgpreprocess.preprocess_y(args.bedfile, train_chr, train_fwd.shape[1], parameter.repeats_to_search)
+        y_val = dgpreprocess.preprocess_y(args.bedfile, val_chr, val_fwd.shape[1], parameter.repeats_to_search)
+        train_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(train_fwd, y_train))
+        val_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(val_fwd, y_val))
+        run = functools.partial(dgopt.build_and_optimize if args.cohort == 1 else dgopt.build_and_optimize_cohort,
+                                train_data, val_data, args.step_size, parameter)
+
+        def objective(draws):
+            got = run(draws)
+            for draw, res in zip([draws] if args.cohort == 1 else draws, [got] if args.cohort == 1 else got):
+                values = " ".join(f"{k}={v:.6g}" if isinstance(v, float) else f"{k}={v}" for k, v in draw.items())
+                print(f"trial {draw.tid}\t{res['status']}\tloss {res['loss']:.6g}\t{values}"
+                      + (f"\t{res['error']}" if res["error"] else ""), flush=True)
+            return got
+
+        count = dgopt.run_a_trial(space, objective, parameter.project_root_dir, args.max_evals, seed=args.seed, cohort=args.cohort)
+        with open(os.path.join(parameter.project_root_dir, "results.json"), "r") as file:
+            done = [t for t in json.load(file) if t["status"] == dgopt.STATUS_OK]
+        if not done:
+            print(f"no trial of {count} gave a finite MCC")
+            return
+        best = min(done, key=lambda t: t["loss"])
+        values = " ".join(f"{k}={v:.6g}" if isinstance(v, float) else f"{k}={v}" for k, v in best["params"].items())
+        print(f"best of {count}: trial {best['tid']}\tloss {best['loss']:.6g}\t{values}\t{best['logdir']}")
 
 
 def main(argv=None):

@@ -19,6 +19,15 @@ class Segment(C.Structure):
     _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("label", C.c_int32), ("contig", C.c_int32)]
 
 
+class TrainJob(C.Structure):
+    """struct dgrp_train_job: the argument list of dgrp_train_step"""
+    _fields_ = [("T", cint), ("u", cint), ("C", cint), ("attention", cint), ("d_params", vp), ("d_idx", vp), ("d_truth", vp),
+                ("n", i64), ("d_starts", vp), ("B", i64), ("d_masks", vp), ("d_loss", vp), ("d_grads", vp), ("d_work", vp),
+                ("work_bytes", i64)]
+
+
+TRAIN_MAX_JOBS = 8                  # DGRP_TRAIN_MAX_JOBS
+
 _SIGNATURES = {
     "dgrp_abi_version": (cint, []),
     "dgrp_last_error": (C.c_char_p, []),
@@ -109,6 +118,7 @@ _SIGNATURES = {
     "dgrp_train_param_count": (i64, [cint, cint, cint]),
     "dgrp_train_workspace_bytes": (i64, [cint, cint, cint, cint, i64]),
     "dgrp_train_step": (cint, [cint, cint, cint, cint, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "dgrp_train_step_multi": (cint, [C.POINTER(TrainJob), cint, vp]),
     "dgrp_optimizer_step": (cint, [cint, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),

@@ -11,6 +11,7 @@
 //   gradient  dU[Up, 3Up]  = sum over rows of h_prev^T . dG      over all B.T rows of a direction, split into fixed chunks
 #include "dgrp_common.h"
 
+#include <algorithm>
 #include <mutex>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -29,6 +30,7 @@ struct train_params {
     int ntc;                         // ceil(T / TR_TCHUNK)
     int nh;                          // floats of one window's head partial
     int total;                       // parameters
+    int nthr;                        // block width of the forward and backward kernels (256 up to 64 padded units, else 512)
     int oK, oU, oB, oS, oFk, oFb;    // offsets into the flat parameter buffer
     const float *w;                  // flat parameters
     const uint8_t *idx;
@@ -37,6 +39,13 @@ struct train_params {
     const float *masks;              // [B, 2, 5] or null
     float *Upad, *UTpad, *S, *AVG, *DAVG, *DL, *PH, *LOSSP, *PU, *PW;
     float *loss, *grads;
+};
+
+// The jobs of one launch chain, passed by value in the kernel arguments (8 x 224 bytes): blockIdx.z is the job.  Every kernel
+// takes its own job's parameters and runs the one-job body; grid, block width and dynamic LDS are the largest of the jobs, and
+// a workgroup or thread outside its own job's extent returns before the first barrier.
+struct train_table {
+    train_params job[DGRP_TRAIN_MAX_JOBS];
 };
 
 __device__ __forceinline__ int64_t tr_start(const train_params &p, int64_t b)
@@ -62,8 +71,9 @@ __device__ __forceinline__ int64_t tr_slot(const train_params &p, int dir, int t
     return ((((int64_t)dir * p.nt + tile) * p.T + t) * 5 + q) * 16 * p.Up;
 }
 
-__global__ void train_pack_kernel(train_params p)
+__global__ void train_pack_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     const int Up = p.Up, u = p.u;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= Up * 3 * Up) return;
@@ -76,12 +86,14 @@ __global__ void train_pack_kernel(train_params p)
 // ---------------------------------------------------------------------------------------------------------------- forward
 // grid (nt, 2), one workgroup per tile of 16 windows and direction.  LDS: h [16][Up + 4], hm [16][3Up], kernel [5][3u], bias [2][3u],
 // masks [16][5], starts [16], channels [16].
-__global__ void train_forward_kernel(train_params p)
+__global__ void train_forward_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     extern __shared__ __align__(16) unsigned char tr_lds[];
     const int Up = p.Up, u = p.u, T = p.T, HS = Up + 4, G3 = 3 * Up;
-    const int tile = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, NT = blockDim.x;
+    const int tile = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, NT = p.nthr;
     const int lane = tid & 63, wave = tid >> 6, nwave = NT >> 6;
+    if (tile >= p.nt || tid >= NT) return;
     int64_t *st = (int64_t *)tr_lds;
     float *h = (float *)(st + 16);
     float *hm = h + 16 * HS;
@@ -178,12 +190,14 @@ __device__ float tr_block_max(float v, float *red)
 
 // one workgroup of 256 threads per window.  LDS: Wff [F][C], bff [16], q / ctx / dctx [u] each, cl [16], sdl [16], a [T], da [T],
 // red [256], part [256][C + 2].
-__global__ void train_head_kernel(train_params p)
+__global__ void train_head_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     extern __shared__ __align__(16) unsigned char tr_lds[];
     const int u = p.u, Up = p.Up, T = p.T, C = p.C, F = p.F, att = p.att, off = att ? u : 0;
     const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = NT >> 6;
     const int64_t b = blockIdx.x;
+    if (b >= p.B) return;
     const int tile = (int)(b >> 4), row = (int)(b & 15);
     float *Wff = (float *)tr_lds;
     float *bff = Wff + F * C;
@@ -401,12 +415,14 @@ __global__ void train_head_kernel(train_params p)
 // --------------------------------------------------------------------------------------------------------------- backward
 // grid (nt, 2).  LDS: dh [16][Up + 4], dg [16][3Up + 4].  The gate gradients overwrite the saved gates: z <- d a_z, r <- d a_r,
 // hh <- d a_h . r (recurrent side), hmh <- d a_h (input side).
-__global__ void train_backward_kernel(train_params p)
+__global__ void train_backward_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     extern __shared__ __align__(16) unsigned char tr_lds[];
     const int Up = p.Up, u = p.u, T = p.T, HS = Up + 4, G3 = 3 * Up, GS = G3 + 4;
-    const int tile = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, NT = blockDim.x;
+    const int tile = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, NT = p.nthr;
     const int lane = tid & 63, wave = tid >> 6, nwave = NT >> 6;
+    if (!p.grads || tile >= p.nt || tid >= NT) return;
     float *dh = (float *)tr_lds;
     float *dg = dh + 16 * HS;
     for (int e = tid; e < 16 * HS; e += NT) dh[e] = 0.0f;
@@ -454,11 +470,12 @@ __global__ void train_backward_kernel(train_params p)
 }
 
 // dU partials: grid (ceil(tiles / 4), 2 nt), 4 waves, one 16 x 16 output tile per wave, K = the 16 (T - 1) rows of a chunk
-__global__ void train_wgrad_kernel(train_params p)
+__global__ void train_wgrad_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     const int Up = p.Up, T = p.T, G3 = 3 * Up, ntn = G3 / 16, ntile = (Up / 16) * ntn;
     const int lane = threadIdx.x & 63, id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (id >= ntile) return;
+    if (!p.grads || id >= ntile || (int)blockIdx.y >= 2 * p.nt) return;
     const int chunk = blockIdx.y, mi = id / ntn, ni = id % ntn, g = (ni * 16) / Up, nc = (ni * 16) % Up;
     const int64_t step = (int64_t)16 * Up, base = (int64_t)chunk * T * 5 * step;
     f32x4 acc[4];
@@ -475,9 +492,11 @@ __global__ void train_wgrad_kernel(train_params p)
 }
 
 // kernel and bias partials: grid (2 nt, ntc), 3Up threads: thread n owns column n of the chunk's gate gradients
-__global__ void train_colsum_kernel(train_params p)
+__global__ void train_colsum_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     const int Up = p.Up, T = p.T, G3 = 3 * Up, n = threadIdx.x;
+    if (!p.grads || n >= G3 || (int)blockIdx.x >= 2 * p.nt || (int)blockIdx.y >= p.ntc) return;
     const int chunk = blockIdx.x, tc = blockIdx.y, dir = chunk / p.nt, tile = chunk % p.nt;
     const int g = n / Up, j = n % Up;
     const int64_t step = (int64_t)16 * Up, base = (int64_t)chunk * T * 5 * step;
@@ -504,10 +523,11 @@ __global__ void train_colsum_kernel(train_params p)
 }
 
 // every gradient element: the sum of its partials in index order
-__global__ void train_reduce_kernel(train_params p)
+__global__ void train_reduce_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.total) return;
+    if (!p.grads || e >= p.total) return;
     const int u = p.u, Up = p.Up, G3 = 3 * Up, nchunk = 2 * p.nt;
     float s = 0.0f;
     if (e < p.oU || (e >= p.oB && e < p.oS)) {
@@ -527,8 +547,9 @@ __global__ void train_reduce_kernel(train_params p)
     p.grads[e] = s;
 }
 
-__global__ void train_loss_kernel(train_params p)
+__global__ void train_loss_kernel(train_table tab)
 {
+    const train_params &p = tab.job[blockIdx.z];
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float s = 0.0f;
     for (int64_t b = 0; b < p.B; ++b) s += p.LOSSP[b];
@@ -549,6 +570,7 @@ int train_layout(train_params &p, int T, int u, int C, int attention, int64_t B)
     p.oK = 0; p.oU = 15 * u; p.oB = p.oU + 3 * u * u; p.oS = p.oB + 6 * u;
     p.oFk = p.oS + (p.att ? u : 0); p.oFb = p.oFk + p.F * C; p.total = p.oFb + C;
     p.nh = p.total - p.oS;
+    p.nthr = p.Up <= 64 ? 256 : 512;
     return DGRP_OK;
 }
 
@@ -591,27 +613,48 @@ DGRP_EXPORT int64_t dgrp_train_workspace_bytes(int T, int u, int C, int attentio
     return train_carve(p, nullptr);
 }
 
-DGRP_EXPORT int dgrp_train_step(int T, int u, int C, int attention, const float *d_params, const uint8_t *d_idx,
-                                const int8_t *d_truth, int64_t n, const int64_t *d_starts, int64_t B, const float *d_masks,
-                                float *d_loss, float *d_grads, void *d_work, int64_t work_bytes, void *stream)
+namespace {
+
+// checks one job and fills its parameters; launches nothing
+int train_prepare(train_params &p, const dgrp_train_job &j)
 {
-    train_params p;
-    const int rc = train_layout(p, T, u, C, attention, B);
+    const int rc = train_layout(p, j.T, j.u, j.C, j.attention, j.B);
     if (rc != DGRP_OK) return rc;
-    DGRP_REQUIRE(d_params && d_idx && d_truth && d_starts && d_loss, "training: NULL parameter, index, truth, start or loss pointer");
-    DGRP_REQUIRE(n >= T, "training: record of %lld bases is shorter than the window (%d)", (long long)n, T);
-    DGRP_REQUIRE(d_work && ((uintptr_t)d_work & 15) == 0, "training: workspace NULL or not 16-byte aligned");
-    if (work_bytes < train_carve(p, d_work)) {
-        dgrp_set_error("training: workspace of %lld bytes, %lld needed", (long long)work_bytes, (long long)train_carve(p, nullptr));
+    DGRP_REQUIRE(j.d_params && j.d_idx && j.d_truth && j.d_starts && j.d_loss, "training: NULL parameter, index, truth, start or loss pointer");
+    DGRP_REQUIRE(j.n >= j.T, "training: record of %lld bases is shorter than the window (%d)", (long long)j.n, j.T);
+    DGRP_REQUIRE(j.d_work && ((uintptr_t)j.d_work & 15) == 0, "training: workspace NULL or not 16-byte aligned");
+    if (j.work_bytes < train_carve(p, j.d_work)) {
+        dgrp_set_error("training: workspace of %lld bytes, %lld needed", (long long)j.work_bytes, (long long)train_carve(p, nullptr));
         return DGRP_ENOMEM;
     }
-    p.n = n; p.w = d_params; p.idx = d_idx; p.truth = d_truth; p.starts = d_starts; p.masks = d_masks;
-    p.loss = d_loss; p.grads = d_grads;
-    hipStream_t s = (hipStream_t)stream;
-    const int Up = p.Up, HS = Up + 4, G3 = 3 * Up;
-    const size_t lds_fwd = 16 * 8 + (size_t)4 * (16 * HS + 16 * G3 + 21 * u + 80 + 16);
-    const size_t lds_bwd = (size_t)4 * (16 * HS + 16 * (G3 + 4));
-    const size_t lds_head = (size_t)4 * (p.F * C + 16 + 3 * u + 32 + 2 * T + 256 + 256 * (C + 2));
+    p.n = j.n; p.w = j.d_params; p.idx = j.d_idx; p.truth = j.d_truth; p.starts = j.d_starts; p.masks = j.d_masks;
+    p.loss = j.d_loss; p.grads = j.d_grads;
+    return DGRP_OK;
+}
+
+// the launch chain over the K jobs of `tab`: every extent is the largest any job needs
+int train_launch(const train_table &tab, int K, hipStream_t s)
+{
+    unsigned pack = 0, nt = 0, B = 0, wg = 0, ntc = 0, g3 = 0, red = 0, nthr = 0;
+    size_t lds_fwd = 0, lds_bwd = 0, lds_head = 0;
+    bool grads = false;
+    for (int k = 0; k < K; ++k) {
+        const train_params &p = tab.job[k];
+        const unsigned Up = p.Up, HS = Up + 4, G3 = 3 * Up;
+        pack = std::max(pack, (Up * G3 + 255) / 256);
+        nt = std::max(nt, (unsigned)p.nt);
+        B = std::max(B, (unsigned)p.B);
+        nthr = std::max(nthr, (unsigned)p.nthr);
+        lds_fwd = std::max(lds_fwd, 16 * 8 + (size_t)4 * (16 * HS + 16 * G3 + 21 * p.u + 80 + 16));
+        lds_head = std::max(lds_head, (size_t)4 * (p.F * p.C + 16 + 3 * p.u + 32 + 2 * p.T + 256 + 256 * (p.C + 2)));
+        if (!p.grads) continue;
+        grads = true;
+        lds_bwd = std::max(lds_bwd, (size_t)4 * (16 * HS + 16 * (G3 + 4)));
+        wg = std::max(wg, ((Up / 16) * (G3 / 16) + 3) / 4);
+        ntc = std::max(ntc, (unsigned)p.ntc);
+        g3 = std::max(g3, G3);
+        red = std::max(red, ((unsigned)p.total + 255) / 256);
+    }
     static std::once_flag configured;
     static hipError_t cfg_err = hipSuccess;
     std::call_once(configured, [] {
@@ -621,23 +664,58 @@ DGRP_EXPORT int dgrp_train_step(int T, int u, int C, int attention, const float 
         set((const void *)train_head_kernel);
     });
     DGRP_HIP(cfg_err);
-    const int nthr = Up <= 64 ? 256 : 512;
-    hipLaunchKernelGGL(train_pack_kernel, dim3((Up * G3 + 255) / 256), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(train_pack_kernel, dim3(pack, 1, K), dim3(256), 0, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_forward_kernel, dim3(p.nt, 2), dim3(nthr), lds_fwd, s, p);
+    hipLaunchKernelGGL(train_forward_kernel, dim3(nt, 2, K), dim3(nthr), lds_fwd, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_head_kernel, dim3((unsigned)B), dim3(256), lds_head, s, p);
+    hipLaunchKernelGGL(train_head_kernel, dim3(B, 1, K), dim3(256), lds_head, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(train_loss_kernel, dim3(1, 1, K), dim3(64), 0, s, tab);
     DGRP_LAUNCH_CHECK();
-    if (!d_grads) return DGRP_OK;
-    hipLaunchKernelGGL(train_backward_kernel, dim3(p.nt, 2), dim3(nthr), lds_bwd, s, p);
+    if (!grads) return DGRP_OK;
+    hipLaunchKernelGGL(train_backward_kernel, dim3(nt, 2, K), dim3(nthr), lds_bwd, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_wgrad_kernel, dim3(((Up / 16) * (G3 / 16) + 3) / 4, 2 * p.nt), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(train_wgrad_kernel, dim3(wg, 2 * nt, K), dim3(256), 0, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_colsum_kernel, dim3(2 * p.nt, p.ntc), dim3(G3), 0, s, p);
+    hipLaunchKernelGGL(train_colsum_kernel, dim3(2 * nt, ntc, K), dim3(g3), 0, s, tab);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(train_reduce_kernel, dim3((p.total + 255) / 256), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(train_reduce_kernel, dim3(red, 1, K), dim3(256), 0, s, tab);
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
+}
+
+}   // namespace
+
+DGRP_EXPORT int dgrp_train_step(int T, int u, int C, int attention, const float *d_params, const uint8_t *d_idx,
+                                const int8_t *d_truth, int64_t n, const int64_t *d_starts, int64_t B, const float *d_masks,
+                                float *d_loss, float *d_grads, void *d_work, int64_t work_bytes, void *stream)
+{
+    const dgrp_train_job job = {T, u, C, attention, d_params, d_idx, d_truth, n, d_starts, B, d_masks, d_loss, d_grads, d_work, work_bytes};
+    train_table tab = {};
+    const int rc = train_prepare(tab.job[0], job);
+    if (rc != DGRP_OK) return rc;
+    return train_launch(tab, 1, (hipStream_t)stream);
+}
+
+DGRP_EXPORT int dgrp_train_step_multi(const dgrp_train_job *h_jobs, int K, void *stream)
+{
+    DGRP_REQUIRE(K >= 1 && K <= DGRP_TRAIN_MAX_JOBS, "training: %d jobs outside 1..%d", K, DGRP_TRAIN_MAX_JOBS);
+    DGRP_REQUIRE(h_jobs, "training: NULL job list");
+    train_table tab = {};
+    int64_t used[DGRP_TRAIN_MAX_JOBS];
+    for (int k = 0; k < K; ++k) {
+        const int rc = train_prepare(tab.job[k], h_jobs[k]);
+        if (rc != DGRP_OK) {
+            char msg[512];
+            snprintf(msg, sizeof msg, "%s", dgrp_last_error());
+            dgrp_set_error("job %d: %s", k, msg);
+            return rc;
+        }
+        used[k] = train_carve(tab.job[k], h_jobs[k].d_work);
+        for (int i = 0; i < k; ++i) {
+            const char *a = (const char *)h_jobs[i].d_work, *b = (const char *)h_jobs[k].d_work;
+            DGRP_REQUIRE(a + used[i] <= b || b + used[k] <= a, "job %d: training: workspace overlaps the workspace of job %d", k, i);
+        }
+    }
+    return train_launch(tab, K, (hipStream_t)stream);
 }

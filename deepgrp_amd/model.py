@@ -17,6 +17,16 @@ import numpy as np
 from . import hdf5
 
 
+def create_logdir(options, trial: Optional[int] = None) -> str:
+    """Standardised name of a run's directory (deepgrp/model.py:12-25): ``<project_root_dir>/tf_logs/run-<UTC time>``; with
+    `trial` (addition) ``-<trial:04d>`` is appended, so that the trials of one second get directories of their own."""
+    import os
+    from datetime import datetime, timezone
+    now = datetime.now(timezone.utc).strftime("%Y%m%d%H%M%S")
+    name = f"run-{now}" if trial is None else f"run-{now}-{int(trial):04d}"
+    return os.path.join(options.project_root_dir, "tf_logs", name)
+
+
 class Options:
     """Hyper-parameters of a DeepGRP model; see deepgrp/model.py:28-136 for the meaning of each
     attribute.  ``gru_units`` / ``gru_dropout`` are accepted as aliases of ``units`` / ``dropout``."""

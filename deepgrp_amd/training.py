@@ -187,9 +187,10 @@ class DeviceTrainer:
             self._work_batch = batch
         return self._work
 
-    def run(self, record: DeviceRecord, starts, masks=None, loss_out=None, with_grads: bool = True):
-        """One dgrp_train_step on the current stream: the loss (a device scalar, `loss_out` if given) and, with `with_grads`,
-        the gradients in ``self.grads``.  `starts`: int64 array or device tensor; `masks`: [B, 2, 5] float32 or None."""
+    def job(self, record: DeviceRecord, starts, masks=None, loss_out=None, with_grads: bool = True):
+        """The arguments of one training step as a ``_lib.TrainJob`` (struct dgrp_train_job), with the loss tensor and the tensors
+        the job points to, which the caller keeps until the step is enqueued.  `starts`: int64 array or device tensor; `masks`:
+        [B, 2, 5] float32 or None."""
         torch = self._torch
         if record.classes != self.classes:
             raise ValueError(f"truth of {record.classes} classes for a model of {self.classes}")
@@ -208,11 +209,19 @@ class DeviceTrainer:
         batch = int(d_starts.numel())
         work = self._workspace(batch)
         loss = torch.empty(1, dtype=torch.float32, device="cuda") if loss_out is None else loss_out
-        rc = self._lib.lib().dgrp_train_step(
+        job = self._lib.TrainJob(
             self.vecsize, self.units, self.classes, int(self.attention), self.params.data_ptr(), record.d_idx.data_ptr(),
             record.d_truth.data_ptr(), record.n, d_starts.data_ptr(), batch, d_masks.data_ptr() if d_masks is not None else None,
-            loss.data_ptr(), self.grads.data_ptr() if with_grads else None, work.data_ptr(), work.numel(),
-            torch.cuda.current_stream().cuda_stream)
+            loss.data_ptr(), self.grads.data_ptr() if with_grads else None, work.data_ptr(), work.numel())
+        return job, loss, (d_starts, d_masks, work)
+
+    def run(self, record: DeviceRecord, starts, masks=None, loss_out=None, with_grads: bool = True):
+        """One dgrp_train_step on the current stream: the loss (a device scalar, `loss_out` if given) and, with `with_grads`,
+        the gradients in ``self.grads``.  Arguments as job()."""
+        j, loss, _keep = self.job(record, starts, masks, loss_out, with_grads)
+        rc = self._lib.lib().dgrp_train_step(
+            j.T, j.u, j.C, j.attention, j.d_params, j.d_idx, j.d_truth, j.n, j.d_starts, j.B, j.d_masks, j.d_loss, j.d_grads,
+            j.d_work, j.work_bytes, self._torch.cuda.current_stream().cuda_stream)
         self._lib.check(rc, "dgrp_train_step")
         return loss
 
@@ -229,53 +238,135 @@ class DeviceTrainer:
         return unflatten_weights(self.params.cpu().numpy(), self.units, self.classes, self.attention)
 
 
+def run_jobs(jobs) -> None:
+    """One dgrp_train_step_multi per slice of DGRP_TRAIN_MAX_JOBS of `jobs` (the (job, loss, kept tensors) of DeviceTrainer.job),
+    on the current stream."""
+    import torch
+    from . import _lib
+    stream = torch.cuda.current_stream().cuda_stream
+    for first in range(0, len(jobs), _lib.TRAIN_MAX_JOBS):
+        part = [j[0] for j in jobs[first:first + _lib.TRAIN_MAX_JOBS]]
+        table = (_lib.TrainJob * len(part))(*part)
+        _lib.check(_lib.lib().dgrp_train_step_multi(table, len(part), stream), "dgrp_train_step_multi")
+
+
 # ------------------------------------------------------------------------------------------------ loop
+class _Run:
+    """One model of training_multi: its generator, samplers, trainer, history file and early-stopping state."""
+
+    def __init__(self, data, options: Options, weights: Dict[str, Any], logdir, seed, classes: int):
+        import torch
+        self.options, self.logdir = options, logdir
+        os.makedirs(logdir, exist_ok=True)
+        self.rng = np.random.default_rng(seed)
+        self.batches = fetch_batch(options, data[0], self.rng)()
+        self.val_batches = fetch_batch(options, data[1], self.rng)()
+        self.trainer = DeviceTrainer(weights, options.vecsize, options.batch_size)
+        self.config = keras_config(options.vecsize, options.units, classes, bool(options.attention), float(options.dropout))
+        self.losses = torch.empty(max(1, int(options.n_batches)) + 1, dtype=torch.float32, device="cuda")
+        self.best, self.best_weights, self.wait = float("inf"), self.trainer.weights(), 0
+        self.history: List[Tuple[int, float, float]] = []
+        self.hist = open(os.path.join(logdir, "history.tsv"), "w")
+        self.hist.write("epoch\tloss\tval_loss\n")
+
+    def step_job(self, record: DeviceRecord, i: int):
+        o = self.options
+        return self.trainer.job(record, next(self.batches), dropout_masks(self.rng, o.batch_size, float(o.dropout)),
+                                loss_out=self.losses[i:i + 1])
+
+    def apply(self) -> None:
+        o = self.options
+        self.trainer.apply(o.optimizer, o.learning_rate, o.rho, o.momentum, o.epsilon)
+
+    def validation_job(self, record: DeviceRecord):
+        return self.trainer.job(record, next(self.val_batches), None, loss_out=self.losses[-1:], with_grads=False)
+
+    def end_epoch(self, epoch: int, log: Callable[[str], None]) -> bool:
+        """Writes the epoch's line and, on an improvement, the model file; False when the run is over."""
+        o = self.options
+        host = self.losses.cpu().numpy().astype(np.float64)
+        loss, val_loss = float(host[:int(o.n_batches)].mean()), float(host[-1])
+        self.history.append((epoch, loss, val_loss))
+        line = f"{epoch}\t{loss:.9g}\t{val_loss:.9g}"
+        self.hist.write(line + "\n")
+        self.hist.flush()
+        log(f"epoch {line}")
+        if val_loss < self.best:
+            self.best, self.wait, self.best_weights = val_loss, 0, self.trainer.weights()
+            w = self.best_weights
+            save_keras_hdf5(os.path.join(self.logdir, f"{epoch:02d}.hdf5"), w["kernel"], w["recurrent_kernel"], w["bias"],
+                            w["ff_kernel"], w["ff_bias"], w["scale"], vecsize=int(o.vecsize), config=self.config)
+            return True
+        self.wait += 1
+        return self.wait < int(o.early_stopping_th)
+
+    def close(self) -> Dict[str, Any]:
+        self.hist.close()
+        self.trainer = None                                               # the device buffers go back to the allocator
+        self.best_weights["history"] = self.history
+        return self.best_weights
+
+
+def training_multi(data: Tuple[preprocessing.Data, preprocessing.Data], options_list, weights_list, logdirs, seeds,
+                   log: Optional[Callable[[str], None]] = None) -> List[Dict[str, Any]]:
+    """Trains ``len(options_list)`` models side by side on the same data: per step ONE dgrp_train_step_multi over the models still
+    running (slices of DGRP_TRAIN_MAX_JOBS), then their optimizer steps; per epoch one loss-only multi step over their validation
+    batches.  A model has its own units, vecsize, attention, batch_size, optimizer and hyper-parameters, its own generator
+    ``default_rng(seeds[k])``, sampler, dropout masks, early stopping, ``history.tsv`` and model files in ``logdirs[k]``; only
+    `n_batches` and `n_epochs` must agree.  A model that stops early leaves the step and the others go on.  The two records are
+    uploaded once.  Element k of the result, and the files in logdirs[k], are byte for byte those of
+    ``training(data, options_list[k], weights_list[k], logdirs[k], seed=seeds[k])``: a job's bytes do not depend on its cohort."""
+    count = len(options_list)
+    if not (len(weights_list) == len(logdirs) == len(seeds) == count) or count < 1:
+        raise ValueError("training_multi: options, weights, logdirs and seeds must be lists of one length, at least 1")
+    for options in options_list:
+        check_options(options)
+    for name in ("n_batches", "n_epochs"):
+        values = [int(getattr(o, name)) for o in options_list]
+        if len(set(values)) > 1:
+            raise TrainingRefused(f"{name} = {values}: models trained side by side take the same {name}")
+    for options in options_list:
+        classes = len(options.repeats_to_search) + 1
+        for d in data:
+            if d.truelbl.shape[0] != classes:
+                raise ValueError(f"truth of {d.truelbl.shape[0]} rows, {classes} expected from repeats_to_search")
+    say = log or _LOG.info
+    records = [DeviceRecord.from_data(d) for d in data]
+    runs: List[Optional[_Run]] = [None] * count
+    results: List[Optional[Dict[str, Any]]] = [None] * count
+    try:
+        for k in range(count):
+            runs[k] = _Run(data, options_list[k], weights_list[k], logdirs[k], seeds[k], records[0].classes)
+        active = list(range(count))
+        n_batches, n_epochs = int(options_list[0].n_batches), int(options_list[0].n_epochs)
+        for epoch in range(1, n_epochs + 1):
+            for i in range(n_batches):
+                run_jobs([runs[k].step_job(records[0], i) for k in active])
+                for k in active:
+                    runs[k].apply()
+            run_jobs([runs[k].validation_job(records[1]) for k in active])
+            still = []
+            for k in active:
+                if runs[k].end_epoch(epoch, say if count == 1 else (lambda msg, k=k: say(f"model {k}: {msg}"))):
+                    still.append(k)
+                else:
+                    results[k], runs[k] = runs[k].close(), None
+            active = still
+            if not active:
+                break
+    finally:
+        for k in range(count):
+            if runs[k] is not None:
+                results[k], runs[k] = runs[k].close(), None
+    return results
+
+
 def training(data: Tuple[preprocessing.Data, preprocessing.Data], options: Options, model_weights: Dict[str, Any], logdir,
              seed: Optional[int] = None, log: Optional[Callable[[str], None]] = None) -> Dict[str, Any]:
     """Runs training (deepgrp/training.py:15-73): `n_epochs` epochs of `n_batches` steps on data[0]; after each epoch the loss of
     one batch of data[1] without dropout.  An epoch whose validation loss improves writes ``<logdir>/<epoch:02d>.hdf5``
     (ModelCheckpoint, save_best_only); `early_stopping_th` epochs without improvement end the run; the best weights are
     returned (restore_best_weights).  ``<logdir>/history.tsv`` gets one line per epoch: epoch, loss (mean of the epoch's steps),
-    val_loss.  Returns the best weights as Keras tensors, with ``history`` (list of (epoch, loss, val_loss))."""
-    import torch
-    check_options(options)
-    os.makedirs(logdir, exist_ok=True)
-    classes = len(options.repeats_to_search) + 1
-    for d in data:
-        if d.truelbl.shape[0] != classes:
-            raise ValueError(f"truth of {d.truelbl.shape[0]} rows, {classes} expected from repeats_to_search")
-    rng = np.random.default_rng(seed)
-    batches = fetch_batch(options, data[0], rng)()
-    val_batches = fetch_batch(options, data[1], rng)()
-    records = [DeviceRecord.from_data(d) for d in data]
-    trainer = DeviceTrainer(model_weights, options.vecsize, options.batch_size)
-    config = keras_config(options.vecsize, options.units, classes, bool(options.attention), float(options.dropout))
-    losses = torch.empty(max(1, int(options.n_batches)) + 1, dtype=torch.float32, device="cuda")
-    best, best_weights, wait = float("inf"), trainer.weights(), 0
-    history: List[Tuple[int, float, float]] = []
-    with open(os.path.join(logdir, "history.tsv"), "w") as hist:
-        hist.write("epoch\tloss\tval_loss\n")
-        for epoch in range(1, int(options.n_epochs) + 1):
-            for i in range(int(options.n_batches)):
-                trainer.run(records[0], next(batches), dropout_masks(rng, options.batch_size, float(options.dropout)),
-                            loss_out=losses[i:i + 1])
-                trainer.apply(options.optimizer, options.learning_rate, options.rho, options.momentum, options.epsilon)
-            trainer.run(records[1], next(val_batches), None, loss_out=losses[-1:], with_grads=False)
-            host = losses.cpu().numpy().astype(np.float64)
-            loss, val_loss = float(host[:int(options.n_batches)].mean()), float(host[-1])
-            history.append((epoch, loss, val_loss))
-            line = f"{epoch}\t{loss:.9g}\t{val_loss:.9g}"
-            hist.write(line + "\n")
-            hist.flush()
-            (log or _LOG.info)(f"epoch {line}")
-            if val_loss < best:
-                best, wait, best_weights = val_loss, 0, trainer.weights()
-                save_keras_hdf5(os.path.join(logdir, f"{epoch:02d}.hdf5"), best_weights["kernel"], best_weights["recurrent_kernel"],
-                                best_weights["bias"], best_weights["ff_kernel"], best_weights["ff_bias"], best_weights["scale"],
-                                vecsize=int(options.vecsize), config=config)
-            else:
-                wait += 1
-                if wait >= int(options.early_stopping_th):
-                    break
-    best_weights["history"] = history
-    return best_weights
+    val_loss.  Returns the best weights as Keras tensors, with ``history`` (list of (epoch, loss, val_loss)).  The one-model call
+    of training_multi's loop."""
+    return training_multi(data, [options], [model_weights], [logdir], [seed], log)[0]

@@ -635,6 +635,32 @@ int dgrp_train_step(int T, int u, int C, int attention, const float *d_params, c
                     int64_t n, const int64_t *d_starts, int64_t B, const float *d_masks, float *d_loss, float *d_grads,
                     void *d_work, int64_t work_bytes, void *stream);
 
+/* dgrp_train_step_multi: up to DGRP_TRAIN_MAX_JOBS independent training steps in ONE chain of launches (a hyper-parameter search
+ * trains many small models; one step of one model fills an eighth of the device at the reference's batch of 256).  A job is
+ * exactly the argument list of dgrp_train_step, and job k receives the bytes that dgrp_train_step gives for the same arguments
+ * whatever else is in the list: *d_loss, d_grads, or the loss alone where its d_grads is NULL.  Jobs may differ in every field,
+ * mix loss-only and gradient jobs, and share d_idx / d_truth / d_starts / d_masks; their d_loss, d_grads and workspaces must not
+ * overlap (checked for the workspace ranges that the jobs use).  Each job brings its own workspace of dgrp_train_workspace_bytes.
+ * Every job is checked as dgrp_train_step checks its arguments BEFORE anything is launched; a refusal names the job
+ * ("job 2: training: 257 units outside 1..256") and launches nothing.  h_jobs is a HOST array, read during the call only: the
+ * jobs travel in the kernel arguments.  Stream-ordered: nothing synchronises, copies or allocates.  dgrp_train_step is the
+ * call with one job. */
+#define DGRP_TRAIN_MAX_JOBS 8
+typedef struct dgrp_train_job {
+    int T, u, C, attention;
+    const float *d_params;
+    const uint8_t *d_idx;
+    const int8_t *d_truth;
+    int64_t n;
+    const int64_t *d_starts;
+    int64_t B;
+    const float *d_masks;
+    float *d_loss, *d_grads;
+    void *d_work;
+    int64_t work_bytes;
+} dgrp_train_job;
+int dgrp_train_step_multi(const dgrp_train_job *h_jobs, int K, void *stream);
+
 /* One optimizer step on `count` float32 parameters, in place, in float32, one rounding per operation as written:
  * DGRP_OPT_RMSPROP  s1 = rho s1 + ((1 - rho) g) g;  s2 = momentum s2 + (lr g) / sqrt(s1 + epsilon);  w = w - s2
  * DGRP_OPT_ADAM     s1 = b1 s1 + (1 - b1) g;  s2 = b2 s2 + ((1 - b2) g) g;  w = w - (lr_t s1) / (sqrt(s2) + epsilon), with b1 = momentum,
