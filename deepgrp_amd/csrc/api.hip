@@ -762,11 +762,12 @@ static int64_t record_window_chunk(const dgrp_model *m)
 {
     if (m->ref_only) return ref_sub_windows(m);
     // no spill bounds a launch: 8 M windows at a time (a 250 Mbp chromosome in ONE launch: 5 launches of 2^20 windows each ended in a
-    // round of workgroups that filled a fraction of the chip: +0.8 % on the benchmark record)
+    // last round that filled a fraction of the chip: +0.8 % on the benchmark record)
     if (!m->attention) return 1ll << 23;
-    // whole rounds of workgroups where possible: 32 768 windows = 256 CUs x 8 workgroups x 16 windows is a whole number of rounds
-    // for every recurrent kernel (8, 4, 2 or 1 workgroups of 16 windows, or one of 32, per CU); below that 4096 = 256 CUs x 16
-    // (a launch of 4112 windows costs a large model two rounds for the work of one)
+    // whole rounds where possible: 32 768 windows = 256 CUs x 8 workgroups x 16 windows is a whole number of rounds for every
+    // recurrent kernel (8, 4, 2 or 1 workgroups of 16 windows per CU; gru_split2_kernel: one workgroup per CU for the whole launch, which
+    // walks tile pairs of 32 windows -- a round is one pair on every CU, and its last round is as partly filled as a round of
+    // workgroups was); below that 4096 = 256 CUs x 16 (a launch of 4112 windows costs a large model two rounds for the work of one)
     const int64_t per = (int64_t)m->T * ((int64_t)m->UP * 4 + (int64_t)m->C * 4);
     int64_t c = spill_cap_bytes() / per;
     c = c >= 32768 ? c / 32768 * 32768 : c >= 4096 ? c / 4096 * 4096 : c / 16 * 16;

@@ -215,10 +215,12 @@ __device__ __forceinline__ void emit_value(const gru_params &p, const wg_ctx &c,
 
 // Softmax + merge of step t's partial logits for accumulator register `reg`: the 16x16 logit tile (window =
 // 4*(lane>>4) + reg, class = lane & 15) is split by register over the waves, one value per lane.
+// (`lane`: gru_split2_kernel hands in a copy the compiler cannot see through, so that nothing of this is worked out ahead of its time loop)
 template <int NW, int MODE>
-__device__ __forceinline__ void finish_register(const gru_params &p, const wg_ctx &c, int t, int reg, float fbias, int off, int64_t row0)
+__device__ __forceinline__ void finish_register(const gru_params &p, const wg_ctx &c, int t, int reg, float fbias, int off, int64_t row0,
+                                                int lane = threadIdx.x & 63)
 {
-    const int lane = threadIdx.x & 63, cls = lane & 15;
+    const int cls = lane & 15;
     const float *dp = c.dpart + ((size_t)(t & 1) * 4 + reg) * NW * 64 + lane;
     float sum = dp[0];
 #pragma unroll
@@ -235,13 +237,14 @@ __device__ __forceinline__ void finish_register(const gru_params &p, const wg_ct
 }
 
 // flush the pre-merged image: contiguous rows -> 256-byte atomic wave-instructions
+// (`tid`: as `lane` of finish_register)
 template <int NW>
-__device__ __forceinline__ void flush_image(const gru_params &p, const wg_ctx &c)
+__device__ __forceinline__ void flush_image(const gru_params &p, const wg_ctx &c, int tid = threadIdx.x)
 {
     __syncthreads();
     unsigned *gout = reinterpret_cast<unsigned *>(p.out) + c.lo * p.C;
     const int64_t lim = (p.n - c.lo) * p.C;
-    for (int i = threadIdx.x; i < p.ospan * p.C; i += 64 * NW) {
+    for (int i = tid; i < p.ospan * p.C; i += 64 * NW) {
         const unsigned v = c.obuf[i];
         if (v != 0u && i < lim) global_atomic_max(gout + i, v);
     }

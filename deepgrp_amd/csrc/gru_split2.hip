@@ -33,8 +33,14 @@
 //     phase free of anything that touches the previous phase's accumulators or Dense result);
 //   - no MFMA operand is written by VALU code: fragments, table rows and Dense operands come straight from LDS reads, which
 //     are the compiler's own loads (it waits for them in front of the asm statement);
-//   - the weight loads carry their own s_waitcnt inside the statement that issues them.
+//   - the weight loads are asm statements and so is the ONE s_waitcnt behind all 50 of them (volatile asm keeps its program order:
+//     every MFMA stays behind it); the compiler's own counter waits only ever see more loads in flight than it knows of, never fewer.
+//
+// Launch shape: min(tile pairs, CUs) workgroups (a CU holds one: 146 KB of LDS, 512-register waves), each walking the pairs
+// blockIdx.x, blockIdx.x + gridDim.x, ... -- weights and table are loaded once per workgroup, not once per pair; every pair costs the
+// same, so the stride is static and workgroups never wait on one another.
 #include "gru_shared.h"
+#include <cstddef>
 #include <mutex>
 #include <type_traits>
 
@@ -50,9 +56,11 @@ struct split2_weights {                   // 50 fragments = 200 AGPRs per lane, 
     u32x4 Bd_hi, Bd_lo;                   // Dense
 };
 
+// two fragments requested, not waited for: LOAD_WAIT behind the last LOAD2 (50 loads in flight: the counter holds 63)
 #define LOAD2(a, pa, b, pb)                                                                                             \
-    asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %3, off\n\ts_waitcnt vmcnt(0)"            \
+    asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %3, off"                                   \
                  : "=&a"(a), "=&a"(b) : "v"(pa), "v"(pb) : "memory")
+#define LOAD_WAIT asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // recurrent MFMA: A = weights (AGPR), B = hidden fragment; Dense MFMA: A = hidden rows, B = weights (AGPR)
 #define MFMA_R(acc, Wf, b) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(Wf), "v"(b))
@@ -74,9 +82,108 @@ struct tile_state {
     bool pr_on;
 };
 
-template <int MODE, bool ONERCP>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gru_split2_kernel(const gru_params pin, int half_bytes)
+// a workgroup-uniform 64-bit value the compiler worked out on the vector unit, moved to scalar registers: what a tile keeps across the
+// time loop (first window, first image row) must not take vector registers there
+__device__ __forceinline__ int64_t split2_uniform(int64_t v)
 {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(uint64_t)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// Set-up of ONE tile of a pair: what wg_setup (gru_shared.h) does for the one-tile kernels, for this kernel's carve, with wide
+// accesses and WITHOUT the closing barrier -- the kernel runs it for both tiles of a pair and meets once.  Stages the class indices,
+// zeroes h_{-1} (hi and lo tile) and the output image, writes the windows' placement.
+// Sequences: the 16 windows of a tile cover ONE contiguous span of 15 s + T class indices.  Where that span (and up to 15 bytes of
+// alignment shift) fits the [16][Tp] bytes of the carve, it is staged as it lies in HBM -- 16-byte loads between its unaligned ends,
+// nothing outside [first byte of the first valid window, last byte of the last valid window] is read -- and window wi starts at byte
+// seq_row0 + wi * s; otherwise (steps longer than a window) window by window at pitch Tp as in wg_setup.  Windows behind the last valid one
+// then see whatever the bytes hold: every read is clamped to a table row and every output of theirs is masked.
+// (LDS banks: the time loop's two byte reads per step go to wi * s + t.  At pitch Tp = 208 the 16 windows fall into 16 banks; in a span
+// they do unless s is a multiple of 32 bytes -- s = 64 puts them into 4 banks, a 4-way conflict on 2 of a tile-step's ~50 LDS operations.
+// Reasoned, not measured; the usual steps (50, 25, T / 4 of windows that are no multiple of 128) are conflict-free.)
+template <int MODE>
+__device__ __forceinline__ wg_ctx split2_tile_setup(const gru_params &p, unsigned char *base, int64_t bid, int tid, unsigned &seq_row0, unsigned &seq_pitch)
+{
+    wg_ctx c;
+    c.hbuf = reinterpret_cast<_Float16 *>(base);
+    c.dpart = reinterpret_cast<float *>(base + gru_lds_hbuf(UP, HPAD));
+    c.seqs = base + gru_lds_hbuf(UP, HPAD) + gru_lds_dpart(NW);
+    c.row0s = reinterpret_cast<int64_t *>(c.seqs + gru_lds_seq(p.Tp));
+    c.rowoff = reinterpret_cast<int *>(c.row0s + DGRP_WG_WINDOWS);
+    c.obuf = reinterpret_cast<unsigned *>(c.rowoff + DGRP_WG_WINDOWS);
+    const int T = p.T, C = p.C;
+    c.wg_w = split2_uniform(p.w0 + bid * DGRP_WG_WINDOWS);
+    c.nvalid = __builtin_amdgcn_readfirstlane((int)min((int64_t)DGRP_WG_WINDOWS, p.w0 + p.nw - c.wg_w));
+    if ((DGRP_WG_WINDOWS - 1) * p.s + T + 15 <= (int64_t)DGRP_WG_WINDOWS * p.Tp) {
+        const uint8_t *src = p.idx + c.wg_w * p.s;                                   // (not dereferenced without a valid window)
+        const int have = c.nvalid > 0 ? (c.nvalid - 1) * (int)p.s + T : 0;           // bytes of the valid windows
+        const int sh = (int)(reinterpret_cast<uintptr_t>(src) & 15);
+        const int head = min(have, (16 - sh) & 15);                                  // bytes in front of the first aligned 16
+        const int nbody = (have - head) >> 4, tail0 = head + 16 * nbody;
+#pragma nounroll
+        for (int i = tid; i < nbody; i += 64 * NW)
+            *reinterpret_cast<uint4 *>(c.seqs + sh + head + 16 * i) = *reinterpret_cast<const uint4 *>(src + head + 16 * i);
+#pragma nounroll
+        for (int i = tid; i < head + have - tail0; i += 64 * NW) {
+            const int j = i < head ? i : tail0 + (i - head);
+            c.seqs[sh + j] = src[j];
+        }
+        seq_row0 = (unsigned)sh;
+        seq_pitch = (unsigned)p.s;
+    } else {
+#pragma nounroll
+        for (int i = tid; i < DGRP_WG_WINDOWS * T; i += 64 * NW) {
+            const int wi = i / T, t = i - wi * T;
+            c.seqs[wi * p.Tp + t] = wi < c.nvalid ? p.idx[(c.wg_w + wi) * p.s + t] : (uint8_t)4;
+        }
+        seq_row0 = 0;
+        seq_pitch = (unsigned)p.Tp;
+    }
+    unsigned z0 = 0u;
+    asm volatile("" : "+v"(z0));                                                     // (a constant would be kept in four registers across the time loop)
+    const uint4 zero = { z0, z0, z0, z0 };
+#pragma nounroll
+    for (int i = tid; i < 32 * HS * 2 / 16; i += 64 * NW) {                           // h_{-1} = 0: first tile of each ping-pong
+        reinterpret_cast<uint4 *>(base)[i] = zero;
+        reinterpret_cast<uint4 *>(base + p.lo_tile_off)[i] = zero;
+    }
+    c.lo = 0;
+    if (MODE == 0) {
+        // smallest placement row of the two ends; windows that fall outside [lo, lo + ospan) go to HBM directly (wg_setup)
+        const int64_t a = dgrp_place_row(p.place, c.wg_w, p.s), b = dgrp_place_row(p.place, c.wg_w + c.nvalid - 1, p.s);
+        c.lo = split2_uniform(a < b ? a : b);
+        const int words = p.ospan * C;                                               // (the image starts on a 16-byte boundary of the carve)
+#pragma nounroll
+        for (int i = tid; i < words / 4; i += 64 * NW) reinterpret_cast<uint4 *>(c.obuf)[i] = zero;
+        if (tid < (words & 3)) c.obuf[(words & ~3) + tid] = 0u;
+    }
+    if (tid < DGRP_WG_WINDOWS) {
+        int64_t r0 = -1;
+        int off = -1;
+        if (tid < c.nvalid) {
+            r0 = MODE == 0 ? dgrp_place_row(p.place, c.wg_w + tid, p.s) : (c.wg_w + tid - p.w0 + p.avgw) * (int64_t)T;
+            if (MODE == 0 && r0 >= c.lo && r0 - c.lo + T <= p.ospan) off = (int)(r0 - c.lo);
+        }
+        c.row0s[tid] = r0;
+        c.rowoff[tid] = off;
+    }
+    return c;
+}
+
+// The kernel's ONE argument: it is the kernel-argument segment from byte 0 on, and the pair loop re-reads its members from there
+// (offsetof below) instead of keeping them in registers across the time loop.
+struct split2_args {
+    gru_params p;
+    int half_bytes;                       // bytes of one tile's LDS carve
+    int npairs;                           // tile pairs of the launch
+};
+
+template <int MODE, bool ONERCP>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gru_split2_kernel(const split2_args args)
+{
+    static_assert(offsetof(split2_args, p) == 0 && sizeof(gru_params) % 4 == 0 && offsetof(split2_args, half_bytes) % 4 == 0 &&
+                  offsetof(split2_args, npairs) % 4 == 0, "the pair loop reads the argument as 32-bit words");
+    const gru_params &pin = args.p;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -95,6 +202,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             }
         const uint4 *mypack = pin.pack + (size_t)wave * pin.nfrag * 64 + lane;    // Dense fragments of the 32x32 pack (api.hip): same shape
         LOAD2(W.Bd_hi, mypack + (size_t)(3 * (2 * KS + 1) + 1) * 64, W.Bd_lo, mypack + (size_t)(3 * (2 * KS + 1) + 2) * 64);
+        LOAD_WAIT;
     }
     // the input-projection table: [5 bases][4 kinds][128 units] fp32 -> LDS rows of XT_PITCH bytes
     for (int i = tid; i < 5 * 512; i += 256)
@@ -103,33 +211,33 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int wi = lane & 15, q4 = lane >> 4;                     // window of this lane; its k-group / unit group
     const int cls = lane & 15;
     const float fbias = cls < C ? pin.ffb[cls] : 0.0f;
-    const int pwi = 4 * (lane >> 4) + wave;                       // window of the wave's logit register
     const unsigned frag_lane = (unsigned)(wi * HS + 8 * q4) * 2;                            // fragment: row wi (+16: its reverse complement), k 8 q4 ..
     const unsigned dense_lane = (unsigned)(wi * HS + 32 * wave + 8 * q4) * 2;
     const unsigned pub_lane = (unsigned)(wi * HS + 32 * wave + 4 * q4) * 2;                 // publish: 4 units 32 w + 16 uh + 4 q4 ..
     const unsigned tab_lane = (unsigned)pin.xtab_off + (unsigned)(32 * wave + 4 * q4) * 4;  // table: the same 4 units, + 64 B per unit half
 
     tile_state S0, S1;                      // two named objects, never indexed: they must stay in registers
-    auto setup = [&](tile_state &Z, int x) {
-        unsigned char *base = smem + (size_t)x * half_bytes;
-        _Float16 *lbuf = reinterpret_cast<_Float16 *>(base + pin.lo_tile_off);
-        for (int i = tid; i < 32 * HS; i += 256) lbuf[i] = (_Float16)0.0f;
-        Z.p = pin;
-        const int64_t bid = wg_record_at<MODE>(pin, Z.p, 2 * (int64_t)blockIdx.x + x);
-        Z.ctx = wg_setup<NW, MODE, HPAD>(Z.p, base, bid);                              // ends with a barrier
-        Z.hcur = (unsigned)x * half_bytes;                        // hbuf is the first item of the carve
+    auto setup = [&](tile_state &Z, const gru_params &pk, int tid_k, int half_k, int pair, int x) {
+        unsigned char *base = smem + (size_t)x * half_k;
+        Z.p = pk;
+        const int64_t bid = wg_record_at<MODE>(pk, Z.p, 2 * (int64_t)pair + x);
+        unsigned seq_row0, seq_pitch;
+        Z.ctx = split2_tile_setup<MODE>(Z.p, base, bid, tid_k, seq_row0, seq_pitch);  // no barrier: the caller meets once for both tiles
+        Z.hcur = (unsigned)x * half_k;                            // hbuf is the first item of the carve
         Z.hnxt = Z.hcur + 32 * HS * 2;
-        Z.lcur = (unsigned)x * half_bytes + pin.lo_tile_off;
+        Z.lcur = (unsigned)x * half_k + pk.lo_tile_off;
         Z.lnxt = Z.lcur + 32 * HS * 2;
-        Z.myseq = (unsigned)(Z.ctx.seqs - smem) + wi * pin.Tp;
+        Z.myseq = (unsigned)(Z.ctx.seqs - smem) + seq_row0 + (tid_k & 15) * seq_pitch;
 #pragma unroll
         for (int i = 0; i < 16; ++i) Z.h[i] = ONERCP ? -1.0f : 0.0f;
-        Z.p_off = Z.ctx.rowoff[pwi];
-        Z.p_row0 = Z.ctx.row0s[pwi];
-        Z.pr_on = cls < C && pwi < Z.ctx.nvalid;
     };
-    setup(S0, 0);
-    setup(S1, 1);
+    // what setup leaves in LDS for the lane (read behind the barrier)
+    auto placement = [&](tile_state &Z, int tid_k) {
+        const int pwi_k = 4 * ((tid_k & 63) >> 4) + wave;
+        Z.p_off = Z.ctx.rowoff[pwi_k];
+        Z.p_row0 = Z.ctx.row0s[pwi_k];
+        Z.pr_on = cls < C && pwi_k < Z.ctx.nvalid;
+    };
 
     auto lds16 = [&](unsigned off) -> half8 { return *reinterpret_cast<const half8 *>(smem + off); };
     auto ldsf4 = [&](unsigned off) -> f32x4 { return *reinterpret_cast<const f32x4 *>(smem + off); };
@@ -294,6 +402,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         Z.f0h[0] = lds16(Z.hcur + frag_lane); Z.f0h[1] = lds16(Z.hcur + frag_lane + 16 * HS * 2);
         Z.f0l[0] = lds16(Z.lcur + frag_lane); Z.f0l[1] = lds16(Z.lcur + frag_lane + 16 * HS * 2);
     };
+    for (int pair = blockIdx.x;;) {
+    // A pair's set-up is a few hundred instructions in front of 2 T phases that leave no register free.  What it needs is taken afresh for
+    // every pair -- the launch parameters from the kernel-argument segment (= `args`, the kernel's only argument), the thread index
+    // through an opaque copy -- so that nothing of it is hoisted out of this loop and carried, spilled, across the time loop.
+    const __attribute__((address_space(4))) unsigned *kargs = (const __attribute__((address_space(4))) unsigned *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kargs));
+    struct { unsigned w[sizeof(gru_params) / 4]; } kraw;
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(gru_params) / 4; ++i) kraw.w[i] = kargs[offsetof(split2_args, p) / 4 + i];   // (scalar loads; members nothing reads are not loaded)
+    const gru_params pk = __builtin_bit_cast(gru_params, kraw);
+    const int half_k = (int)kargs[offsetof(split2_args, half_bytes) / 4];
+    int tid_k = 64 * wave + lane;                // (= tid, from what the time loop keeps anyway)
+    asm volatile("" : "+v"(tid_k));
+    setup(S0, pk, tid_k, half_k, pair, 0);
+    setup(S1, pk, tid_k, half_k, pair, 1);
+    __syncthreads();
+    placement(S0, tid_k);
+    placement(S1, tid_k);
     first_step(S0);
     first_step(S1);
     phase(yes, no, no, S0, S1, 0, 0);
@@ -310,23 +436,50 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     phase(no, yes, yes, S0, S1, T, T - 1);      // (tile 0's logits of step T - 2 are finished here; tile 1's in its drain)
 
     // drain: Dense and softmax/merge of the last step, image flush
-    auto drain = [&](tile_state &Z, bool prev_open) {
+    auto drain = [&](tile_state &Z, bool prev_open, int tid_d) {
+        const int lane_d = tid_d & 63;
         const half8 a0 = lds16(Z.hcur + dense_lane), a1 = lds16(Z.hcur + dense_lane + 16 * HS * 2);
         const half8 l0 = lds16(Z.lcur + dense_lane), l1 = lds16(Z.lcur + dense_lane + 16 * HS * 2);
-        if (MODE == 2 && (lane & 15) < Z.ctx.nvalid) split_avg_store(Z.p, Z.ctx.wg_w, T - 1, UP, wave, a0, a1, l0, l1);
+        if (MODE == 2 && (lane_d & 15) < Z.ctx.nvalid) split_avg_store_lane(Z.p, Z.ctx.wg_w, T - 1, UP, wave, lane_d, a0, a1, l0, l1);
         f32x4 d;
         MFMA_DZ(d, a0, W.Bd_hi); MFMA_D(d, a1, W.Bd_hi); MFMA_D(d, a0, W.Bd_lo); MFMA_D(d, a1, W.Bd_lo); MFMA_D(d, l0, W.Bd_hi); MFMA_D(d, l1, W.Bd_hi);
         asm volatile("s_nop 15\n\ts_nop 7" : "+v"(d));           // MFMA result -> VALU/LDS read, no compiler padding behind asm
-        float *dw = Z.ctx.dpart + ((size_t)((T - 1) & 1) * 4 * NW + wave) * 64 + lane;
+        float *dw = Z.ctx.dpart + ((size_t)((T - 1) & 1) * 4 * NW + wave) * 64 + lane_d;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) dw[reg * NW * 64] = d[reg];
         __syncthreads();
-        if (prev_open && T > 1) finish_register<NW, MODE>(Z.p, Z.ctx, T - 2, wave, fbias, Z.p_off, Z.p_row0);
-        finish_register<NW, MODE>(Z.p, Z.ctx, T - 1, wave, fbias, Z.p_off, Z.p_row0);
-        if (MODE == 0 && pin.ospan > 0) flush_image<NW>(Z.p, Z.ctx);
+        if (prev_open && T > 1) finish_register<NW, MODE>(Z.p, Z.ctx, T - 2, wave, fbias, Z.p_off, Z.p_row0, lane_d);
+        finish_register<NW, MODE>(Z.p, Z.ctx, T - 1, wave, fbias, Z.p_off, Z.p_row0, lane_d);
+        if (MODE == 0 && Z.p.ospan > 0) flush_image<NW>(Z.p, Z.ctx, tid_d);
     };
-    drain(S0, false);
-    drain(S1, true);                            // tile 1 stored its partials of step T - 2 in the last phase: no phase of its own follows
+    int tid_d = 64 * wave + lane;
+    asm volatile("" : "+v"(tid_d));             // (nothing of the drain is worked out ahead of the time loop and kept across it)
+    drain(S0, false, tid_d);
+    drain(S1, true, tid_d);                            // tile 1 stored its partials of step T - 2 in the last phase: no phase of its own follows
+    __syncthreads();                            // the next pair's set-up rewrites what this pair's drain and flush still read
+    EDGE_PAD;                                   // (the pair loop's back edge and exit: the drain's Dense chain has its own pad; kept as the rule)
+    pair += (int)gridDim.x;
+    if (pair >= (int)kargs[offsetof(split2_args, npairs) / 4]) break;
+    }
+}
+
+// compute units of the current device, looked up once per DEVICE (records run on a pool of host threads, ranks on devices of their own)
+static int split2_cu_count(int *cus)
+{
+    static std::mutex mu;
+    static int known[64];                    // 0 = not asked yet
+    int dev = 0;
+    DGRP_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (dev < 0 || dev >= 64 || known[dev] == 0) {
+        int n = 0;
+        DGRP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        if (n < 1) n = 1;
+        if (dev < 0 || dev >= 64) { *cus = n; return DGRP_OK; }
+        known[dev] = n;
+    }
+    *cus = known[dev];
+    return DGRP_OK;
 }
 
 template <int MODE, bool ONERCP>
@@ -336,7 +489,14 @@ int launch_split2(const gru_params &p, int64_t groups, int half_bytes, hipStream
     static hipError_t cfg_err = hipSuccess;
     std::call_once(configured, [] { cfg_err = hipFuncSetAttribute((const void *)gru_split2_kernel<MODE, ONERCP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     DGRP_HIP(cfg_err);
-    hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)((groups + 1) / 2)), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH, stream, p, half_bytes);
+    // a CU holds ONE workgroup (LDS, registers): as many workgroups as CUs, each walking its share of the tile pairs (any grid gives the
+    // same bits; one larger than the CUs at hand is merely less balanced)
+    const int64_t npairs = (groups + 1) / 2;
+    int cus = 0;
+    if (const int rc = split2_cu_count(&cus)) return rc;
+    const int64_t grid = npairs < cus ? npairs : cus;
+    DGRP_REQUIRE(npairs >= 1 && npairs <= 0x7fff0000, "gru_split2_kernel: tile pairs out of range");      // (the walk counts pairs in an int)
+    hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)grid), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH, stream, split2_args{ p, half_bytes, (int)npairs });
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
 }
