@@ -16,6 +16,8 @@ Differences, all additive:
     binary sections and zoom levels written and deflated on the GPU);
   * `predict --bed_dir DIR [--bed_min_score S]` also writes the predicted repeats of every input as a scored BED file: per row the
     mean and the smallest probability of its class and the share of its bases that carry it, summed on the GPU (deepgrp_amd/bed.py);
+    with --bed_gzip the file is BGZF (`.bed.gz`), its lines written and deflated on the GPU, and with --bed_index a tabix index
+    (`.bed.gz.tbi`) is built there beside it;
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
@@ -149,8 +151,8 @@ def _add_mask_options(parser, suppress: bool) -> None:
                         help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
                              "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
     parser.add_argument("--gzip_level", type=int, default=d(None),
-                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip and --track_bigwig: 0 literals only, 1 with "
-                             "matches (default: 0 for masked copies, 1 for tracks)")
+                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig and --bed_gzip: 0 literals "
+                             "only, 1 with matches (default: 0 for masked copies, 1 for tracks and the BED)")
 
 
 def _add_track_options(parser) -> None:
@@ -192,6 +194,13 @@ def _add_bed_options(parser) -> None:
                              "largest, four decimals each; summed on the GPU; one process only")
     parser.add_argument("--bed_min_score", type=int, default=s,
                         help="(addition) with --bed_dir: leave out BED lines whose score is below this, 0..1000 (the TSV is not filtered)")
+    parser.add_argument("--bed_gzip", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the BED as BGZF (bgzip's format) to DIR/<basename>.bed.gz; the lines are "
+                             "written and deflated on the GPU (--gzip_level, 1 unless given)")
+    parser.add_argument("--bed_index", action="store_true", default=s,
+                        help="(addition) with --bed_gzip: write the tabix index <basename>.bed.gz.tbi, built on the GPU beside the text "
+                             "(records must end at or below 2^29 and names must not reappear after another name; otherwise a warning "
+                             "and no index)")
 
 
 class CommandLineParser:
@@ -400,7 +409,7 @@ class CommandLineParser:
 
         records_of = _records_of
 
-        runner = RecordRunner(pipe, tracks=track_spec, scores=bed_plan is not None)
+        runner = RecordRunner(pipe, tracks=track_spec, scores=bed_plan is not None, bed=bed_plan)
 
         try:
             if world == 1:
@@ -501,7 +510,10 @@ class CommandLineParser:
                     track_sink = score_sink = None
                     if files is not None:
                         track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
-                    if beds is not None:
+                    if beds is not None and runner.bed is not None:     # --bed_gzip: scores, text and members on the device
+                        score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
+                            merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed))
+                    elif beds is not None:
                         score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
                     rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
                     if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)

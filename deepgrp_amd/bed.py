@@ -9,16 +9,28 @@ row's bases (ContigPipeline.merged, the array the labels are computed from): `me
 
 Everything is exact integer arithmetic.  A probability p becomes q(p) = round-half-up(p * 2^24) clamped to [0, 2^24] (0 for a NaN);
 the device sums, minimises and counts per row (dgrp_row_scores_batch, ROW_SCORE_DTYPE), the host formatter (dgrp_format_bed_rows)
-rounds the quotients half up.  `reference_scores` and `reference_lines` restate both in numpy and Python integers."""
+rounds the quotients half up.  `reference_scores` and `reference_lines` restate both in numpy and Python integers.
+
+With `--bed_gzip` the file is `DIR/<basename>.bed.gz`, BGZF as bgzip writes it.  Rows and scores then stay on the device: the lines
+are written there (dgrp_bed_text_batch, the host formatter's bytes), deflated there (gz.bgzf_compress_device, --gzip_level, 1
+unless given) in pieces of tracks.GZIP_PIECE, and only the members are read back; the text of one record, or of one batch, is one
+write, so a record or batch boundary is a short member, and the EOF member is written at `commit`.  With `--bed_index` the file
+gets its tabix index `<basename>.bed.gz.tbi`: chunks and linear index come from the device in text offsets (dgrp_bed_index_batch;
+`reference_index_parts` restates them), `BedFiles` turns them into virtual offsets with the compressed size of every member it
+appends (tabix.IndexBuilder).  The index is tabix.reference_index of the finished `.bed.gz`: that function reads name, start and
+end of every line of a BGZF file and nothing else, so it states the index of a BED as it states a track's."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 import sys
 import tempfile
-from typing import NamedTuple, Optional, Sequence
+import logging
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
+
+_LOG = logging.getLogger(__name__)
 
 ONE = 1 << 24                                       # q(1.0): the fixed-point unit
 
@@ -27,23 +39,43 @@ class BedPlan(NamedTuple):
     directory: str
     min_score: int
     paths: dict                                     # input file -> its BED file
+    gzip_level: Optional[int] = None                # --bed_gzip: the level (None: plain text from the host formatter)
+    index: bool = False                             # --bed_index
 
 
-def bed_path(directory: str, filename: str) -> str:
+class BedWrite(NamedTuple):
+    """What one write (a record, or a batch) adds to a BGZF BED: its members (no EOF member), the records' names and, with
+    --bed_index, ContigPipeline.bed_index_batch's arrays in offsets of the write's text -- or why this input cannot have an index."""
+    members: bytes
+    names: List[bytes]
+    refused: Optional[str] = None
+    chunks: Optional[np.ndarray] = None
+    linear: Optional[np.ndarray] = None
+    wpref: Optional[np.ndarray] = None
+    last_end: Optional[np.ndarray] = None
+
+
+def bed_path(directory: str, filename: str, gzip: bool = False) -> str:
     from .tracks import input_basename
-    return os.path.join(directory, input_basename(filename) + ".bed")
+    return os.path.join(directory, input_basename(filename) + ".bed" + (".gz" if gzip else ""))
 
 
 def refuse_on_evaluate(args) -> None:
-    if getattr(args, "bed_dir", None) is not None or getattr(args, "bed_min_score", None) is not None:
+    if (getattr(args, "bed_dir", None) is not None or getattr(args, "bed_min_score", None) is not None
+            or getattr(args, "bed_gzip", False) or getattr(args, "bed_index", False)):
         sys.exit("--bed_dir belongs to predict, not evaluate")
 
 
 def plan(args) -> Optional[BedPlan]:
-    """--bed_dir and --bed_min_score, or None without the flag.  Every refusal is made here (sys.exit), before the model is read or
+    """--bed_dir and its options, or None without the flag.  Every refusal is made here (sys.exit), before the model is read or
     the GPU is touched."""
     bdir = getattr(args, "bed_dir", None)
     low = getattr(args, "bed_min_score", None)
+    gzip, index = bool(getattr(args, "bed_gzip", False)), bool(getattr(args, "bed_index", False))
+    if gzip and bdir is None:
+        sys.exit("--bed_gzip needs --bed_dir")
+    if index and not gzip:
+        sys.exit("--bed_index needs --bed_gzip")
     if bdir is None:
         if low is not None:
             sys.exit("--bed_min_score needs --bed_dir")
@@ -56,7 +88,7 @@ def plan(args) -> Optional[BedPlan]:
                  "rank that holds the merged probabilities)")
     paths, seen = {}, {}
     for f in args.FASTA:
-        out = bed_path(bdir, f)
+        out = bed_path(bdir, f, gzip)
         base = os.path.basename(out)
         if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
             sys.exit(f"--bed_dir: the BED files of {seen[base]} and {f} have the same file name {base}; they would collide")
@@ -66,34 +98,119 @@ def plan(args) -> Optional[BedPlan]:
         paths[f] = out
     if len(paths) != len(args.FASTA):
         sys.exit("--bed_dir: an input file is given twice")
-    return BedPlan(bdir, int(low), paths)
+    level = None
+    if gzip:
+        from .tracks import gzip_level
+        level = gzip_level(args, 1)
+    return BedPlan(bdir, int(low), paths, level, index)
 
 
 class BedFiles:
-    """The BED file of one input: written to a temporary file next to it, renamed by `commit`, removed by `abort`."""
+    """The BED file of one input: written to a temporary file next to it, renamed by `commit`, removed by `abort`.  With
+    p.gzip_level `write` takes a BedWrite (BGZF members) and `commit` puts the EOF member behind them.  With p.index it keeps the
+    file offset of every write and a tabix.IndexBuilder, and `commit` writes `<file>.tbi` the same way.  An input that cannot be
+    indexed (a record that ends above 2^29, an empty name, a name that reappears after another name) gets one warning and no
+    index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed."""
 
     def __init__(self, p: BedPlan, filename: str):
         os.makedirs(p.directory, exist_ok=True)
         self.final = p.paths[filename]
         self.min_score = p.min_score
+        self.filename = filename
+        self.gzip = p.gzip_level is not None
+        self.builder = None
+        if self.gzip and p.index:
+            from .tabix import IndexBuilder
+            self.builder = IndexBuilder()
+            self.seen, self.last = set(), None
+        self.index_wanted = self.builder is not None
+        self.off = 0                                    # bytes of members written
+        self.tbi_tmp = None
         fd, self.tmp = tempfile.mkstemp(prefix="." + os.path.basename(self.final) + ".", suffix=".tmp", dir=p.directory)
         self.fh = os.fdopen(fd, "wb")
 
     def write(self, names: Sequence, by_contig: bool, rows, scores) -> None:
-        """The lines of one record (by_contig false: names[0]) or of a batch (rows["contig"] indexes the names)."""
+        """The lines of one record (by_contig false: names[0]) or of a batch (rows["contig"] indexes the names); `scores` is the
+        rows' ROW_SCORE_DTYPE array, or with p.gzip_level the BedWrite the device made of rows and scores."""
+        if isinstance(scores, BedWrite):
+            return self._write_members(scores)
+        if self.gzip:
+            raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")
         if len(rows):
             self.fh.write(format_rows(names, by_contig, rows, scores, self.min_score))
 
+    def _write_members(self, w: BedWrite) -> None:
+        if not self.gzip:
+            raise ValueError(f"{self.filename}: BGZF members for a plain BED")
+        if w.members:
+            self.fh.write(w.members)
+        if self.builder is not None:
+            self._index(w)
+        self.off += len(w.members)
+
+    def _no_index(self, why: str) -> None:
+        if self.builder is not None:
+            _LOG.warning("%s: no tabix index is written (--bed_index): %s", self.filename, why)
+            self.builder = None
+
+    def _index(self, w: BedWrite) -> None:
+        """The write's part of the index; its members go to file offset self.off."""
+        from .tabix import IndexRefused, member_sizes
+        for nm in w.names:
+            if not nm:
+                return self._no_index("a record with an empty name")
+            if nm != self.last:
+                if nm in self.seen:
+                    return self._no_index(f"the record name {nm.decode('utf-8', 'replace')!r} reappears after another name")
+                self.seen.add(nm)
+                self.last = nm
+        if w.refused is not None:
+            return self._no_index(w.refused)
+        if not w.members:
+            return
+        if w.chunks is None:
+            return self._no_index("a write came without its index")
+        sizes, text_len = member_sizes(w.members)
+        try:
+            self.builder.add(self.off, sizes, text_len, w.names, w.chunks, w.linear, w.wpref, w.last_end)
+        except IndexRefused as e:
+            self._no_index(str(e))
+
+    def _commit_index(self) -> None:
+        """`<file>.tbi` through a temporary file; without an index, one left by an earlier run goes."""
+        from .tabix import index_file
+        tbi = self.final + ".tbi"
+        if self.builder is None:
+            if os.path.exists(tbi):
+                os.remove(tbi)
+            return
+        fd, self.tbi_tmp = tempfile.mkstemp(prefix="." + os.path.basename(tbi) + ".", suffix=".tmp", dir=os.path.dirname(tbi))
+        with os.fdopen(fd, "wb") as fh:
+            fh.write(index_file(self.builder.payload()))
+
     def commit(self) -> None:
-        self.fh.close()
+        try:
+            if self.gzip:
+                from .gz import BGZF_EOF
+                self.fh.write(BGZF_EOF)
+            self.fh.close()
+            if self.index_wanted:
+                self._commit_index()
+        except BaseException:
+            self.abort()
+            raise
         os.replace(self.tmp, self.final)
         self.tmp = None
+        if self.tbi_tmp is not None:
+            os.replace(self.tbi_tmp, self.final + ".tbi")
+            self.tbi_tmp = None
 
     def abort(self) -> None:
         self.fh.close()
-        if self.tmp is not None and os.path.exists(self.tmp):
-            os.remove(self.tmp)
-        self.tmp = None
+        for tmp in (self.tmp, self.tbi_tmp):
+            if tmp is not None and os.path.exists(tmp):
+                os.remove(tmp)
+        self.tmp = self.tbi_tmp = None
 
 
 def format_rows(names: Sequence, by_contig: bool, rows, scores, min_score: int = 0) -> bytes:
@@ -178,3 +295,40 @@ def reference_lines(names: Sequence, by_contig: bool, rows, scores, min_score: i
         out.append(name + b"\t%d\t%d\tclass%d\t%d\t." % (int(row["start"]), int(row["end"]), int(row["label"]), score)
                    + b"".join(b"\t%d.%04d" % divmod(f, 10000) for f in figs) + b"\n")
     return b"".join(out)
+
+
+def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_score: int, rec_end: Sequence[int]):
+    """What dgrp_bed_index_batch states about the text `reference_lines` gives for the same arguments, in Python integers:
+    -> (chunks tabix.CHUNK_DTYPE, linear int64 [windows of all records], wpref int64 [records + 1], last_end int64 [records]).
+    A chunk is a maximal run of consecutive emitted lines of one record with one bin; linear[wpref[r] + w] is the text offset of
+    the first emitted line of record r, in file order, whose end is greater than w << 14 (the running maximum of the ends), or
+    -1; last_end[r] the end of the record's last emitted line, 0 without one."""
+    from .tabix import CHUNK_DTYPE, MIN_SHIFT, reg2bin
+    nrec = len(rec_end)
+    wpref = np.zeros(nrec + 1, np.int64)
+    np.cumsum([((int(e) - 1) >> MIN_SHIFT) + 1 for e in rec_end], out=wpref[1:])
+    linear = np.full(int(wpref[-1]), -1, np.int64)
+    filled = [0] * nrec
+    last_end = np.zeros(nrec, np.int64)
+    chunks, u = [], 0
+    for k in range(len(rows)):
+        line = reference_lines(names, by_contig, rows[k:k + 1], scores[k:k + 1], min_score)
+        if not line:
+            continue
+        r = int(rows[k]["contig"]) if by_contig else 0
+        start, end = int(rows[k]["start"]), int(rows[k]["end"])
+        b = reg2bin(start, end)
+        if chunks and chunks[-1][2] == r and chunks[-1][3] == b:
+            chunks[-1][1] = u + len(line)
+        else:
+            chunks.append([u, u + len(line), r, b])
+        top = ((end - 1) >> MIN_SHIFT) + 1
+        if top > filled[r]:
+            linear[wpref[r] + filled[r]:wpref[r] + top] = u
+            filled[r] = top
+        last_end[r] = end
+        u += len(line)
+    out = np.zeros(len(chunks), CHUNK_DTYPE)
+    for i, c in enumerate(chunks):
+        out[i] = tuple(c)
+    return out, linear, wpref, last_end

@@ -1,0 +1,563 @@
+// predict --bed_gzip, --bed_index: the scored BED lines written on the device (dgrp_bed_text_batch: the bytes of the host formatter
+// dgrp_format_bed_rows) and the tabix pieces of that text (dgrp_bed_index_batch: chunks and linear index in text offsets, the
+// rules of deepgrp_amd/tabix.py).  Everything is integer arithmetic and plain stores: no floating point, no atomics.
+//
+// The chain.  check (one thread per row, raises a flag word per kind of refusal) -> rows (the line's length, 0 when filtered; for
+// the index also whether it is emitted) -> exclusive scan (scan.h) -> one read-back of the totals and the flags (the only
+// synchronisation) -> write.  The index compacts the emitted lines first (a second scan), marks the line that opens a chunk (a
+// third), and finds a window's line by a binary search over the running maximum of (record, end) keys: records ascend with the
+// lines, so the maximum of record << 32 | end over a prefix is the last record's running maximum of ends.
+#include "dgrp_common.h"
+#include "scan.h"
+#include <string.h>
+#include <vector>
+
+namespace {
+
+#define BED_ONE (1ull << 24)               // q(1.0)
+#define BED_MAX_BASES (1ll << 40)          // the envelope of the 64-bit rounding below
+#define BED_MAX_END (1ll << 29)            // the largest coordinate of a tabix index
+#define BED_MAX_ROWS ((1ll << 31) - 256)   // one thread per row, 256 a workgroup
+
+enum { F_BASES, F_NAME, F_RANGE, F_SPAN, F_END, F_RECORDS, F_STARTS, F_COUNT };
+static const char *const FLAG_TEXT[F_COUNT] = {
+    "a row has no scored base (bases <= 0)",
+    "a row names a record outside the names (by_contig: contig not in 0..nnames-1)",
+    "a row's figures lie outside the envelope (bases < 2^40, sum <= bases * 2^24, 0 <= agree <= bases)",
+    "a row has start < 0 or start >= end",
+    "a row lies outside the records or ends behind its record's end",
+    "the records do not ascend with the rows",
+    "the starts descend inside a record (tabix needs sorted rows)",
+};
+
+struct bed_in {
+    const dgrp_segment *rows;
+    const dgrp_row_score *scores;
+    int64_t nrows;
+    const int64_t *name_off;       // device copies of the host tables
+    const char *names;
+    int64_t nnames;
+    int by_contig;
+    uint64_t min_score;
+};
+
+// The four figures, R(num, den, k) = floor((2 k num + den) / (2 den)) of the header without a 128-bit division: with
+// sum = a * bases + r (0 <= r < bases), R(sum, bases * 2^24, k) = (2 k a + 2^24 + floor(2 k r / bases)) >> 25, every term below
+// 2^64 for k <= 10000, bases < 2^40 and a <= 2^24.
+struct bed_figs { uint64_t score, mean, qmin, agree; };
+
+__device__ __forceinline__ bool bed_scored(const dgrp_row_score &sc)
+{
+    return sc.bases > 0 && sc.bases < BED_MAX_BASES && sc.sum <= ((uint64_t)sc.bases << 24) && sc.agree >= 0 && sc.agree <= sc.bases;
+}
+
+__device__ __forceinline__ bed_figs bed_figures(const dgrp_row_score &sc)
+{
+    const uint64_t bases = (uint64_t)sc.bases, a = sc.sum / bases, r = sc.sum - a * bases;
+    bed_figs f;
+    f.score = (2000 * a + BED_ONE + 2000 * r / bases) >> 25;
+    f.mean = (20000 * a + BED_ONE + 20000 * r / bases) >> 25;
+    f.qmin = (20000ull * sc.qmin + BED_ONE) >> 25;
+    f.agree = (20000 * (uint64_t)sc.agree + bases) / (2 * bases);
+    return f;
+}
+
+__device__ __forceinline__ int dec_chars(uint64_t u)
+{
+    int d = 1;
+    while (u >= 10) { u /= 10; ++d; }
+    return d;
+}
+
+__device__ __forceinline__ int int_chars(long long v)
+{
+    return v < 0 ? 1 + dec_chars(0ull - (unsigned long long)v) : dec_chars((unsigned long long)v);
+}
+
+__device__ __forceinline__ char *put_dec(char *o, uint64_t u)
+{
+    const int d = dec_chars(u);
+    for (int k = d - 1; k >= 0; --k) { o[k] = (char)('0' + u % 10); u /= 10; }
+    return o + d;
+}
+
+__device__ __forceinline__ char *put_int(char *o, long long v)
+{
+    if (v < 0) { *o++ = '-'; return put_dec(o, 0ull - (unsigned long long)v); }
+    return put_dec(o, (unsigned long long)v);
+}
+
+__device__ __forceinline__ char *put_fixed4(char *o, uint64_t v)          // v / 10^4 as "d.dddd"
+{
+    o = put_dec(o, v / 10000);
+    const unsigned f = (unsigned)(v % 10000);
+    *o++ = '.';
+    *o++ = (char)('0' + f / 1000);
+    *o++ = (char)('0' + f / 100 % 10);
+    *o++ = (char)('0' + f / 10 % 10);
+    *o++ = (char)('0' + f % 10);
+    return o;
+}
+
+// the name index of a row, or -1 where it has none
+__device__ __forceinline__ int64_t bed_name(const bed_in &A, const dgrp_segment &row)
+{
+    const int64_t c = A.by_contig ? row.contig : 0;
+    return c >= 0 && c < A.nnames ? c : -1;
+}
+
+// One thread per row: every refusal raises its flag word (plain stores of the same value).  rec_end == nullptr: the text entry's
+// two checks only.
+__global__ void __launch_bounds__(256) bed_check_kernel(bed_in A, const int64_t *__restrict__ rec_end, int64_t nrec,
+                                                        uint32_t *__restrict__ flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nrows) return;
+    const dgrp_segment row = A.rows[i];
+    const dgrp_row_score sc = A.scores[i];
+    if (sc.bases <= 0) flags[F_BASES] = 1;
+    else if (!bed_scored(sc)) flags[F_RANGE] = 1;
+    if (bed_name(A, row) < 0) flags[F_NAME] = 1;
+    if (!rec_end) return;
+    const int64_t r = A.by_contig ? row.contig : 0;
+    if (row.start < 0 || row.start >= row.end) flags[F_SPAN] = 1;
+    if (r < 0 || r >= nrec || row.end > rec_end[r]) flags[F_END] = 1;
+    if (i > 0) {
+        const dgrp_segment prev = A.rows[i - 1];
+        const int64_t rp = A.by_contig ? prev.contig : 0;
+        if (r < rp) flags[F_RECORDS] = 1;
+        if (r == rp && row.start < prev.start) flags[F_STARTS] = 1;
+    }
+}
+
+// One thread per row: the line's length, 0 for a filtered row (and for a row the check refuses: nothing it names is read);
+// emit (the index): 1 where the line is written.
+__global__ void __launch_bounds__(256) bed_rows_kernel(bed_in A, uint64_t *__restrict__ len, uint64_t *__restrict__ emit)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nrows) return;
+    const dgrp_segment row = A.rows[i];
+    const dgrp_row_score sc = A.scores[i];
+    const int64_t c = bed_name(A, row);
+    uint64_t n = 0;
+    if (c >= 0 && bed_scored(sc)) {
+        const bed_figs f = bed_figures(sc);
+        if (f.score >= A.min_score) {
+            // name, start, end, "class" label, score, ".", three "d.dddd" figures, eight tabs and the line feed
+            n = (uint64_t)(A.name_off[c + 1] - A.name_off[c]) + int_chars(row.start) + int_chars(row.end) + 5 + int_chars(row.label) +
+                dec_chars(f.score) + 1 + dec_chars(f.mean / 10000) + dec_chars(f.qmin / 10000) + dec_chars(f.agree / 10000) + 15 + 9;
+        }
+    }
+    len[i] = n;
+    if (emit) emit[i] = n != 0;
+}
+
+// One thread per emitted row: its line at its offset.
+__global__ void __launch_bounds__(256) bed_write_kernel(bed_in A, const uint64_t *__restrict__ len, const uint64_t *__restrict__ off,
+                                                        char *__restrict__ text)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nrows || len[i] == 0) return;
+    const dgrp_segment row = A.rows[i];
+    const bed_figs f = bed_figures(A.scores[i]);
+    const int64_t c = bed_name(A, row);
+    char *o = text + off[i];
+    const char *nm = A.names + A.name_off[c];
+    const int64_t nlen = A.name_off[c + 1] - A.name_off[c];
+    for (int64_t k = 0; k < nlen; ++k) o[k] = nm[k];
+    o += nlen;
+    *o++ = '\t';
+    o = put_int(o, row.start); *o++ = '\t';
+    o = put_int(o, row.end); *o++ = '\t';
+    *o++ = 'c'; *o++ = 'l'; *o++ = 'a'; *o++ = 's'; *o++ = 's';
+    o = put_int(o, row.label); *o++ = '\t';
+    o = put_dec(o, f.score); *o++ = '\t';
+    *o++ = '.'; *o++ = '\t';
+    o = put_fixed4(o, f.mean); *o++ = '\t';
+    o = put_fixed4(o, f.qmin); *o++ = '\t';
+    o = put_fixed4(o, f.agree); *o++ = '\n';
+}
+
+// ---- the index -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t bed_reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
+    return 0;
+}
+
+struct bed_lines {                 // the emitted lines, compacted: m = *count of them
+    const uint64_t *count;
+    int64_t *beg, *end;            // text offsets: the line's first byte, the byte behind it
+    uint64_t *key;                 // record << 32 | the row's end
+    uint32_t *bin;
+};
+
+// One thread per row: an emitted row becomes line eidx[i].
+__global__ void __launch_bounds__(256) bed_compact_kernel(bed_in A, const uint64_t *__restrict__ len, const uint64_t *__restrict__ off,
+                                                          const uint64_t *__restrict__ eidx, bed_lines Ln)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.nrows || len[i] == 0) return;
+    const dgrp_segment row = A.rows[i];
+    const uint64_t j = eidx[i];
+    Ln.beg[j] = (int64_t)off[i];
+    Ln.end[j] = (int64_t)(off[i] + len[i]);
+    Ln.key[j] = (uint64_t)(uint32_t)(A.by_contig ? row.contig : 0) << 32 | (uint64_t)(row.end & 0xffffffffll);
+    Ln.bin[j] = bed_reg2bin(row.start, row.end);
+}
+
+// One thread per slot: 1 where line j opens a chunk (the first line, another record, another bin), 0 elsewhere and behind the lines.
+__global__ void __launch_bounds__(256) bed_opens_kernel(bed_lines Ln, int64_t nrows, uint64_t *__restrict__ opens)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nrows) return;
+    uint64_t f = 0;
+    if ((uint64_t)j < *Ln.count) f = j == 0 || Ln.key[j] >> 32 != Ln.key[j - 1] >> 32 || Ln.bin[j] != Ln.bin[j - 1];
+    opens[j] = f;
+}
+
+// One thread per line: the line that opens chunk c writes its begin, record and bin, the line that closes it its end.
+__global__ void __launch_bounds__(256) bed_chunks_kernel(bed_lines Ln, int64_t nrows, const uint64_t *__restrict__ opens,
+                                                         const uint64_t *__restrict__ cidx, dgrp_track_chunk *__restrict__ chunks)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t m = (int64_t)*Ln.count;
+    if (j >= nrows || j >= m) return;
+    const uint64_t c = cidx[j] + opens[j] - 1;
+    if (opens[j]) {
+        chunks[c].beg = Ln.beg[j];
+        chunks[c].rec = (int32_t)(Ln.key[j] >> 32);
+        chunks[c].bin = Ln.bin[j];
+    }
+    if (j == m - 1 || opens[j + 1]) chunks[c].end = Ln.end[j];
+}
+
+// Inclusive maximum scan of the lines' keys in tiles of SCAN_TILE: tile maxima, their exclusive scan in one workgroup, apply.
+__device__ __forceinline__ uint64_t block_exclusive_max(uint64_t v, uint64_t *lds)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t y = __shfl_up(x, o);
+        if (lane >= o && y > x) x = y;
+    }
+    if (lane == 63) lds[wave] = x;
+    uint64_t ex = __shfl_up(x, 1);
+    if (lane == 0) ex = 0;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) if (lds[w] > ex) ex = lds[w];
+    __syncthreads();
+    return ex;
+}
+
+__global__ void __launch_bounds__(256) bed_tilemax_kernel(bed_lines Ln, uint64_t *__restrict__ tilemax)
+{
+    __shared__ uint64_t lds[4];
+    const int64_t m = (int64_t)*Ln.count, base = (int64_t)blockIdx.x * SCAN_TILE;
+    uint64_t s = 0;
+    for (int k = 0; k < 8; ++k) {
+        const int64_t j = base + k * 256 + threadIdx.x;
+        if (j < m && Ln.key[j] > s) s = Ln.key[j];
+    }
+    for (int o = 32; o > 0; o >>= 1) { const uint64_t y = __shfl_xor(s, o); if (y > s) s = y; }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) if (lds[w] > s) s = lds[w];
+        tilemax[blockIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(256) bed_tilemax_scan_kernel(uint64_t *__restrict__ tilemax, int64_t ntiles)
+{
+    __shared__ uint64_t lds[4];
+    uint64_t carry = 0;
+    for (int64_t base = 0; base < ntiles; base += 256) {
+        const int64_t t = base + threadIdx.x;
+        const uint64_t v = t < ntiles ? tilemax[t] : 0;
+        uint64_t ex = block_exclusive_max(v, lds);
+        if (carry > ex) ex = carry;
+        if (t < ntiles) tilemax[t] = ex;
+        const uint64_t incl = v > ex ? v : ex;            // thread 255 holds the maximum up to the end of this round
+        if (threadIdx.x == 255) lds[0] = incl;
+        __syncthreads();
+        carry = lds[0];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) bed_runmax_kernel(bed_lines Ln, const uint64_t *__restrict__ tilemax, uint64_t *__restrict__ runmax)
+{
+    __shared__ uint64_t lds[4];
+    const int64_t m = (int64_t)*Ln.count, base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * 8;
+    uint64_t v[8], s = 0;
+    for (int k = 0; k < 8; ++k) {
+        v[k] = base + k < m ? Ln.key[base + k] : 0;
+        if (v[k] > s) s = v[k];
+    }
+    uint64_t run = block_exclusive_max(s, lds);
+    if (tilemax[blockIdx.x] > run) run = tilemax[blockIdx.x];
+    for (int k = 0; k < 8; ++k) {
+        if (v[k] > run) run = v[k];
+        if (base + k < m) runmax[base + k] = run;
+    }
+}
+
+__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t *a, int64_t n, uint64_t x)      // the first index with a[i] >= x
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One thread per window of the linear index: the record by a search over the window prefix, the line by a search over the running
+// maximum.  The thread of a record's window 0 also states the end of the record's last line (0: the record has none).
+__global__ void __launch_bounds__(256) bed_linear_kernel(bed_lines Ln, const uint64_t *__restrict__ runmax, const int64_t *__restrict__ wpref,
+                                                         int64_t nrec, int64_t *__restrict__ linear, int64_t *__restrict__ rec_last)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= wpref[nrec]) return;
+    int64_t lo = 0, hi = nrec;                                 // the last record r with wpref[r] <= g
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (wpref[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint64_t r = (uint64_t)lo, w = (uint64_t)(g - wpref[lo]);
+    const int64_t m = (int64_t)*Ln.count;
+    const int64_t j = lower_bound_u64(runmax, m, r << 32 | ((w << 14) + 1));
+    linear[g] = j < m && runmax[j] >> 32 == r ? Ln.beg[j] : -1;
+    if (w == 0 && rec_last) {
+        const int64_t e = lower_bound_u64(runmax, m, (r + 1) << 32);
+        rec_last[r] = e > 0 && Ln.key[e - 1] >> 32 == r ? (int64_t)(Ln.key[e - 1] & 0xffffffffull) : 0;
+    }
+}
+
+// ---- the workspace -------------------------------------------------------------------------------------------------------------
+struct bed_layout {
+    int64_t name_off, rec_end, wpref, names, tables_bytes;     // inside the uploaded tables
+    int64_t tables, len, off, tiles;                           // both entries
+    int64_t emit, eidx, lbeg, lend, key, lbin, runmax, opens, cidx, tilemax;      // the index
+    int64_t bytes;
+};
+
+static bool bed_carve(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t nrec, bool index, bed_layout *l)
+{
+    if (nrows < 0 || nrows > BED_MAX_ROWS || nnames < 1 || nnames > (1ll << 31) - 1 || names_bytes < 0 || names_bytes > (1ll << 40)) return false;
+    if (index && (nrec < 1 || nrec > (1ll << 31) - 1)) return false;
+    l->name_off = 0;
+    l->rec_end = l->name_off + (nnames + 1) * 8;
+    l->wpref = l->rec_end + (index ? nrec * 8 : 0);
+    l->names = l->wpref + (index ? (nrec + 1) * 8 : 0);
+    l->tables_bytes = l->names + names_bytes;
+    const int64_t ntiles = (nrows + SCAN_TILE - 1) / SCAN_TILE, col = dgrp_align_up(nrows * 8, 256);
+    int64_t p = 256;                                           // totals and flags
+    l->tables = p; p += dgrp_align_up(l->tables_bytes, 256);
+    l->len = p; p += col;
+    l->off = p; p += col;
+    l->tiles = p; p += dgrp_align_up(ntiles * 8, 256);
+    l->emit = l->eidx = l->lbeg = l->lend = l->key = l->lbin = l->runmax = l->opens = l->cidx = l->tilemax = 0;
+    if (index) {
+        l->emit = p; p += col;
+        l->eidx = p; p += col;
+        l->lbeg = p; p += col;
+        l->lend = p; p += col;
+        l->key = p; p += col;
+        l->lbin = p; p += dgrp_align_up(nrows * 4, 256);
+        l->runmax = p; p += col;
+        l->opens = p; p += col;
+        l->cidx = p; p += col;
+        l->tilemax = p; p += dgrp_align_up(ntiles * 8, 256);
+    }
+    l->bytes = p;
+    return true;
+}
+
+// header of the workspace: three totals, then the flag words
+struct bed_head { uint64_t bytes, lines, chunks, pad; uint32_t flags[8]; };
+
+static int bed_check_names(const char *who, const char *names, const int64_t *name_off, int64_t nnames)
+{
+    DGRP_REQUIRE(nnames >= 1 && names && name_off, "%s: bad arguments (names)", who);
+    DGRP_REQUIRE(name_off[0] >= 0, "%s: name offsets must start at or above 0", who);
+    for (int64_t i = 0; i < nnames; ++i) DGRP_REQUIRE(name_off[i + 1] >= name_off[i], "%s: name offsets must ascend", who);
+    return DGRP_OK;
+}
+
+static int bed_refusal(const char *who, const bed_head &h)
+{
+    for (int k = 0; k < F_COUNT; ++k) {
+        if (h.flags[k]) {
+            dgrp_set_error("%s: %s", who, FLAG_TEXT[k]);
+            return DGRP_EINVAL;
+        }
+    }
+    return DGRP_OK;
+}
+
+// The shared front on checked arguments: tables up (`tab` lives until the caller's synchronisation), flags cleared, check, lengths,
+// offsets.  No synchronisation.
+static int bed_front(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                     const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end,
+                     const int64_t *h_wpref, char *w, const bed_layout &l, hipStream_t stream, std::vector<char> &tab, bed_in *A)
+{
+    tab.assign((size_t)l.tables_bytes, 0);
+    memcpy(tab.data() + l.name_off, name_off, (size_t)(nnames + 1) * 8);
+    if (h_rec_end) {
+        memcpy(tab.data() + l.rec_end, h_rec_end, (size_t)nrec * 8);
+        memcpy(tab.data() + l.wpref, h_wpref, (size_t)(nrec + 1) * 8);
+    }
+    if (name_off[nnames] > 0) memcpy(tab.data() + l.names, names, (size_t)name_off[nnames]);
+    DGRP_HIP(hipMemcpyAsync(w + l.tables, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
+    DGRP_HIP(hipMemsetAsync(w, 0, 256, stream));
+    bed_head *head = (bed_head *)w;
+    A->rows = d_rows; A->scores = d_scores; A->nrows = nrows;
+    A->name_off = (const int64_t *)(w + l.tables + l.name_off);
+    A->names = w + l.tables + l.names;
+    A->nnames = nnames; A->by_contig = by_contig != 0;
+    A->min_score = (uint64_t)(min_score < 0 ? 0 : min_score);
+    const dim3 grid((unsigned)((nrows + 255) / 256)), block(256);
+    hipLaunchKernelGGL(bed_check_kernel, grid, block, 0, stream, *A, h_rec_end ? (const int64_t *)(w + l.tables + l.rec_end) : nullptr, nrec,
+                       head->flags);
+    DGRP_LAUNCH_CHECK();
+    uint64_t *len = (uint64_t *)(w + l.len);
+    hipLaunchKernelGGL(bed_rows_kernel, grid, block, 0, stream, *A, len, h_rec_end ? (uint64_t *)(w + l.emit) : nullptr);
+    DGRP_LAUNCH_CHECK();
+    return device_exclusive_scan(len, (uint64_t *)(w + l.off), nrows, (uint64_t *)(w + l.tiles), &head->bytes, stream);
+}
+
+}   // namespace
+
+DGRP_EXPORT int64_t dgrp_bed_text_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes)
+{
+    bed_layout l;
+    return bed_carve(nrows, nnames, names_bytes, 0, false, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_bed_text_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                                    const dgrp_row_score *d_scores, int64_t nrows, int min_score, char *d_text, int64_t cap,
+                                    int64_t *h_bytes, void *d_work, int64_t work_bytes, void *stream_)
+{
+    static const char who[] = "dgrp_bed_text_batch";
+    hipStream_t stream = (hipStream_t)stream_;
+    DGRP_REQUIRE(h_bytes && nrows >= 0 && cap >= 0, "%s: bad arguments", who);
+    const int rc = bed_check_names(who, names, name_off, nnames);
+    if (rc != DGRP_OK) return rc;
+    *h_bytes = 0;
+    if (nrows == 0) return DGRP_OK;
+    DGRP_REQUIRE(d_rows && d_scores && (d_text || cap == 0), "%s: bad arguments (NULL rows, scores or text)", who);
+    bed_layout l;
+    DGRP_REQUIRE(bed_carve(nrows, nnames, name_off[nnames], 0, false, &l), "%s: too many rows or names (%lld, %lld)", who, (long long)nrows,
+                 (long long)nnames);
+    if (!d_work || work_bytes < l.bytes) {
+        dgrp_set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)work_bytes, (long long)l.bytes);
+        return DGRP_ENOMEM;
+    }
+    char *w = (char *)d_work;
+    std::vector<char> tab;                                      // (alive until the synchronisation below)
+    bed_in A;
+    int rc2 = bed_front(names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, 0, nullptr, nullptr, w, l, stream, tab, &A);
+    if (rc2 != DGRP_OK) return rc2;
+    bed_head head;
+    DGRP_HIP(hipMemcpyAsync(&head, w, sizeof head, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    rc2 = bed_refusal(who, head);
+    if (rc2 != DGRP_OK) return rc2;
+    *h_bytes = (int64_t)head.bytes;
+    if (head.bytes == 0 || (int64_t)head.bytes > cap) return DGRP_OK;          // (too small: the caller retries with room for all of it)
+    hipLaunchKernelGGL(bed_write_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, stream, A, (const uint64_t *)(w + l.len),
+                       (const uint64_t *)(w + l.off), d_text);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+DGRP_EXPORT int64_t dgrp_bed_index_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t nrec)
+{
+    bed_layout l;
+    return bed_carve(nrows, nnames, names_bytes, nrec, true, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_bed_index_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                                     const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end,
+                                     dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear,
+                                     int64_t linear_cap, int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream_)
+{
+    static const char who[] = "dgrp_bed_index_batch";
+    hipStream_t stream = (hipStream_t)stream_;
+    DGRP_REQUIRE(h_nchunks && nrows >= 0 && chunk_cap >= 0 && linear_cap >= 0, "%s: bad arguments", who);
+    const int rc = bed_check_names(who, names, name_off, nnames);
+    if (rc != DGRP_OK) return rc;
+    DGRP_REQUIRE(nrec >= 1 && nrec <= (1ll << 31) - 1 && h_rec_end, "%s: bad nrec %lld or no record ends", who, (long long)nrec);
+    DGRP_REQUIRE(by_contig || nrec == 1, "%s: without by_contig every row belongs to record 0, so nrec must be 1, not %lld", who, (long long)nrec);
+    std::vector<int64_t> wpref((size_t)nrec + 1, 0);
+    for (int64_t r = 0; r < nrec; ++r) {
+        DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= BED_MAX_END,
+                     "%s: record %lld ends at %lld, outside 1..2^29 (the largest coordinate of a tabix index)", who, (long long)r,
+                     (long long)h_rec_end[r]);
+        wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_rec_end[r] - 1) >> 14) + 1;
+    }
+    const int64_t W = wpref[(size_t)nrec];
+    DGRP_REQUIRE(W <= (1ll << 38), "%s: %lld windows in one call", who, (long long)W);
+    *h_nchunks = 0;
+    if (nrows == 0) return DGRP_OK;
+    DGRP_REQUIRE(d_rows && d_scores && d_linear && (d_chunks || chunk_cap == 0), "%s: bad arguments (NULL rows, scores, chunks or linear index)", who);
+    DGRP_REQUIRE(linear_cap >= W, "%s: linear_cap %lld below the %lld windows of the records", who, (long long)linear_cap, (long long)W);
+    bed_layout l;
+    DGRP_REQUIRE(bed_carve(nrows, nnames, name_off[nnames], nrec, true, &l), "%s: too many rows, names or records", who);
+    if (!d_work || work_bytes < l.bytes) {
+        dgrp_set_error("%s: workspace too small (%lld < %lld bytes)", who, (long long)work_bytes, (long long)l.bytes);
+        return DGRP_ENOMEM;
+    }
+    char *w = (char *)d_work;
+    std::vector<char> tab;                                      // (alive until the synchronisation below)
+    bed_in A;
+    int rc2 = bed_front(names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec, h_rec_end, wpref.data(), w, l, stream,
+                        tab, &A);
+    if (rc2 != DGRP_OK) return rc2;
+    bed_head *d_head = (bed_head *)w;
+    const uint64_t *len = (const uint64_t *)(w + l.len), *off = (const uint64_t *)(w + l.off);
+    uint64_t *tiles = (uint64_t *)(w + l.tiles), *eidx = (uint64_t *)(w + l.eidx), *opens = (uint64_t *)(w + l.opens);
+    uint64_t *cidx = (uint64_t *)(w + l.cidx), *tilemax = (uint64_t *)(w + l.tilemax), *runmax = (uint64_t *)(w + l.runmax);
+    bed_lines Ln;
+    Ln.count = &d_head->lines;
+    Ln.beg = (int64_t *)(w + l.lbeg); Ln.end = (int64_t *)(w + l.lend); Ln.key = (uint64_t *)(w + l.key); Ln.bin = (uint32_t *)(w + l.lbin);
+    const dim3 grid((unsigned)((nrows + 255) / 256)), block(256);
+    const int64_t ntiles = (nrows + SCAN_TILE - 1) / SCAN_TILE;
+    rc2 = device_exclusive_scan((const uint64_t *)(w + l.emit), eidx, nrows, tiles, &d_head->lines, stream);
+    if (rc2 != DGRP_OK) return rc2;
+    hipLaunchKernelGGL(bed_compact_kernel, grid, block, 0, stream, A, len, off, (const uint64_t *)eidx, Ln);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bed_opens_kernel, grid, block, 0, stream, Ln, nrows, opens);
+    DGRP_LAUNCH_CHECK();
+    rc2 = device_exclusive_scan(opens, cidx, nrows, tiles, &d_head->chunks, stream);
+    if (rc2 != DGRP_OK) return rc2;
+    bed_head head;
+    DGRP_HIP(hipMemcpyAsync(&head, w, sizeof head, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    rc2 = bed_refusal(who, head);
+    if (rc2 != DGRP_OK) return rc2;
+    *h_nchunks = (int64_t)head.chunks;
+    if ((int64_t)head.chunks > chunk_cap) return DGRP_OK;       // (too small: the caller retries with room for all of them)
+    hipLaunchKernelGGL(bed_tilemax_kernel, dim3((unsigned)ntiles), block, 0, stream, Ln, tilemax);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bed_tilemax_scan_kernel, dim3(1), block, 0, stream, tilemax, ntiles);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bed_runmax_kernel, dim3((unsigned)ntiles), block, 0, stream, Ln, (const uint64_t *)tilemax, runmax);
+    DGRP_LAUNCH_CHECK();
+    if (head.chunks > 0) {
+        hipLaunchKernelGGL(bed_chunks_kernel, grid, block, 0, stream, Ln, nrows, (const uint64_t *)opens, (const uint64_t *)cidx, d_chunks);
+        DGRP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(bed_linear_kernel, dim3((unsigned)((W + 255) / 256)), block, 0, stream, Ln, (const uint64_t *)runmax,
+                       (const int64_t *)(w + l.tables + l.wpref), nrec, d_linear, d_rec_last);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}

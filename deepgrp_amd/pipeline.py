@@ -720,7 +720,14 @@ class ContigPipeline:
         out = np.zeros(len(rows), ROW_SCORE_DTYPE)
         if nrec == 0 or len(rows) == 0:
             return out
-        dev = d_probs.device
+        return self._row_scores_device(d_probs, r0, ln, sp, rows, ro)[1].cpu().numpy().view(ROW_SCORE_DTYPE).copy()
+
+    @staticmethod
+    def _row_scores_device(d_probs: torch.Tensor, r0, ln, sp, rows: np.ndarray, ro):
+        """row_scores_batch on its checked tables (at least one record and one row): -> (the rows, the scores) as uint8 device
+        tensors, complete behind the call on the current stream."""
+        L = lib()
+        nrec, dev = len(ln), d_probs.device
         d_rows = torch.from_numpy(rows.view(np.uint8)).to(dev)
         d_scores = torch.zeros(len(rows) * ROW_SCORE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         wb = int(L.dgrp_row_scores_workspace_bytes(nrec, int(ro[-1] - ro[0])))
@@ -728,7 +735,106 @@ class ContigPipeline:
         check(L.dgrp_row_scores_batch(_ptr(d_probs), int(d_probs.shape[1]), nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data,
                                       _ptr(d_rows), ro.ctypes.data, _ptr(d_scores), _ptr(work), work.numel(), stream_ptr()),
               "dgrp_row_scores_batch")
-        return d_scores.cpu().numpy().view(ROW_SCORE_DTYPE).copy()
+        return d_rows, d_scores
+
+    # predict --bed_gzip, --bed_index: rows and scores stay on the device
+    @staticmethod
+    def bed_text_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int = 0) -> torch.Tensor:
+        """The BED lines of `d_rows` (uint8 device tensor of SEGMENT_DTYPE rows) with `d_scores` (the same of ROW_SCORE_DTYPE) as a
+        uint8 device tensor: one dgrp_bed_text_batch call, the bytes bed.format_rows gives for the same arrays on the host.  The
+        text is complete behind the call on the current stream."""
+        L = lib()
+        nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
+        if int(d_scores.numel()) != nrows * ROW_SCORE_DTYPE.itemsize:
+            raise ValueError(f"bed_text_batch: {nrows} rows but {int(d_scores.numel())} bytes of scores")
+        raw, blob, off = name_blob(names)
+        wb = int(L.dgrp_bed_text_workspace_bytes(nrows, len(raw), len(blob)))
+        if wb <= 0:
+            raise ValueError(f"bed_text_batch: bad row count {nrows} or names")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        longest = max(len(x) for x in raw)
+        cap = min(int(L.dgrp_format_bed_bound(nrows, longest)), nrows * (longest + 72))       # (the guess fits most runs)
+        got = C.c_int64(0)
+        while True:
+            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            check(L.dgrp_bed_text_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows, int(min_score),
+                                        _ptr(text), cap, C.byref(got), _ptr(work), wb, stream_ptr()), "dgrp_bed_text_batch")
+            if got.value <= cap:
+                break
+            cap = int(got.value)                            # longer lines than guessed: run again with room for all of them
+        return text[:got.value]
+
+    @staticmethod
+    def bed_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end):
+        """The tabix pieces of the text bed_text_batch gives for the same arguments, in text offsets (one dgrp_bed_index_batch call,
+        read back once): -> (chunks tabix.CHUNK_DTYPE, linear int64 [windows], wpref int64 [records + 1], last_end int64 [records]);
+        record r (a row's contig with by_contig, else 0) ends at rec_end[r] and has its windows at linear[wpref[r]:wpref[r + 1]].
+        What bed.reference_index_parts states.  A record that ends above 2^29 raises tabix.IndexRefused."""
+        from .tabix import CHUNK_DTYPE, MAX_END, MIN_SHIFT, IndexRefused
+        L = lib()
+        nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
+        ends = np.ascontiguousarray(rec_end, np.int64)
+        nrec = len(ends)
+        over = np.flatnonzero(ends > MAX_END)
+        if over.size:
+            raise IndexRefused(f"record {int(over[0])} ends at {int(ends[over[0]])}, above 2^29, the largest coordinate of a tabix index")
+        raw, blob, off = name_blob(names)
+        wpref = np.zeros(nrec + 1, np.int64)
+        np.cumsum(((ends - 1) >> MIN_SHIFT) + 1, out=wpref[1:])
+        nwin = int(wpref[-1])
+        wb = int(L.dgrp_bed_index_workspace_bytes(nrows, len(raw), len(blob), nrec))
+        if wb <= 0:
+            raise ValueError(f"bed_index_batch: bad row count {nrows}, record count {nrec} or names")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        linear = torch.full((max(nwin, 1),), -1, dtype=torch.int64, device=dev)
+        last = torch.zeros(max(nrec, 1), dtype=torch.int64, device=dev)
+        cap = min(nrows, 2 * nwin + 4 * nrec + 16)          # (a chunk per line at most; on long records about one per window)
+        got = C.c_int64(0)
+        while True:
+            chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_bed_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows,
+                                         int(min_score), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got), _ptr(linear), nwin,
+                                         _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_bed_index_batch")
+            if got.value <= cap:
+                break
+            cap = int(got.value)                            # more chunks than guessed: run again with room for all of them
+        host = chunks[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
+        return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
+
+    def bed_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan):
+        """One write of a BGZF BED (bed.BedWrite) for the arguments of row_scores_batch, `names` as bed.format_rows takes them and
+        `plan` the bed.BedPlan: scores, text and, with plan.index, the index's pieces are made on the device from the uploaded rows;
+        the text is deflated there in tracks.GZIP_PIECE pieces (members span records, a write ends in a short member) and only the
+        members come back.  row_off must cover all rows (row_off[0] = 0, row_off[-1] = len(rows))."""
+        from . import gz
+        from .bed import BedWrite
+        from .tabix import MAX_END
+        from .tracks import GZIP_PIECE
+        raw = name_blob(names)[0]
+        r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "bed_write", row0, lengths, startposes)
+        ends = sp + ln
+        refused = None
+        if plan.index:
+            for nm, end in zip(raw, ends.tolist()):
+                if end > MAX_END:
+                    refused = (f"record {nm.decode('utf-8', 'replace')!r} ends at {end}, above 2^29 = {MAX_END}, the largest coordinate "
+                               "of a tabix index")
+                    break
+        rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+        ro = np.ascontiguousarray(row_off, np.int64)
+        if len(rows) == 0:
+            return BedWrite(b"", raw, refused)
+        if len(ro) != len(ln) + 1 or int(ro[0]) != 0 or int(ro[-1]) != len(rows):
+            raise ValueError("bed_write: the row offsets must cover all rows")
+        d_rows, d_scores = self._row_scores_device(d_probs, r0, ln, sp, rows, ro)
+        d_text = self.bed_text_batch(raw, by_contig, d_rows, d_scores, plan.min_score)
+        parts = (None,) * 4
+        if plan.index and refused is None and int(d_text.numel()):
+            parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends)
+        del d_probs, d_rows, d_scores
+        pieces = [gz.bgzf_compress_device(d_text[o:o + GZIP_PIECE], eof=False, level=plan.gzip_level).cpu().numpy().tobytes()
+                  for o in range(0, int(d_text.numel()), GZIP_PIECE)]
+        return BedWrite(b"".join(pieces), raw, refused, *parts)
 
     @staticmethod
     def batch_row_offsets(rows: np.ndarray, contigs) -> np.ndarray:

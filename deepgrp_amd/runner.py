@@ -89,13 +89,15 @@ def rows_text_batch(filename: str, headers, rows) -> str:
 class RecordRunner:
     """Runs (key, record) pairs -- record = DeviceRecord or sequence text -- and yields results in input order (`outputs`,
     `results`).  tracks (a tracks.TrackSpec): every record's track texts come with its rows; scores: the rows' scores
-    (pipeline.ROW_SCORE_DTYPE, predict --bed_dir) do.  With either, every key is (header, name), name the first column of the
-    record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged array; with neither,
-    keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch)."""
+    (pipeline.ROW_SCORE_DTYPE, predict --bed_dir) do -- with bed (a bed.BedPlan with a gzip_level, --bed_gzip) the write's
+    bed.BedWrite instead, made on the device where rows and scores then stay.  With either, every key is (header, name), name
+    the first column of the record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged
+    array; with neither, keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch)."""
 
-    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None, scores: bool = False):
+    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None, scores: bool = False, bed=None):
         self.pipe = pipe
         self.tracks, self.scores = tracks, bool(scores)
+        self.bed = bed if bed is not None and bed.gzip_level is not None else None     # --bed_gzip: a bed.BedWrite in the scores' place
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
@@ -114,12 +116,21 @@ class RecordRunner:
         from .tracks import empty_texts, record_texts
         startpos, d_idx = record_indices(rec)
         if d_idx.numel() == 0:                            # no base: no rows; with --track_bigwig still a chromosome (empty_texts)
-            return (np.zeros(0, SEGMENT_DTYPE), np.zeros(0, ROW_SCORE_DTYPE) if self.scores else None,
-                    empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
+            scores = np.zeros(0, ROW_SCORE_DTYPE) if self.scores else None
+            if self.scores and self.bed is not None:
+                from .bed import BedWrite
+                from ._lib import name_blob
+                scores = BedWrite(b"", name_blob([name])[0])
+            return (np.zeros(0, SEGMENT_DTYPE), scores, empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
         merged = self.pipe.merged(d_idx)
         texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
         rows = self.pipe.segments(self.pipe.labels(merged), startpos)
-        return rows, self.pipe.row_scores(merged, startpos, rows) if self.scores else None, texts
+        scores = None
+        if self.scores and self.bed is not None:
+            scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed)
+        elif self.scores:
+            scores = self.pipe.row_scores(merged, startpos, rows)
+        return rows, scores, texts
 
     def run_batch(self, batch: _Batch):
         """A batch: rows of all its records, contig = position in the batch; scores go row by row with them, texts[k] is the text of
@@ -131,7 +142,10 @@ class RecordRunner:
         rows, d_probs, row0 = self.pipe.run_batch_probs(*args)
         ln = np.ascontiguousarray(args[2], np.int64)
         scores = texts = None
-        if self.scores:
+        if self.scores and self.bed is not None:
+            scores = self.pipe.bed_write(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]),
+                                         [k[1] for k, _r in batch], True, self.bed)
+        elif self.scores:
             scores = self.pipe.row_scores_batch(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]))
         if self.tracks is not None:
             texts = self.pipe.batch_track_texts(d_probs, row0, ln, args[3], [k[1] for k, _r in batch], self.tracks,

@@ -1,4 +1,7 @@
 """The tabix index (`.tbi`) of a BGZF bedGraph track (`predict --track_dir --track_gzip --track_index`), stated in numpy/Python.
+The index of a scored BED (`predict --bed_dir --bed_gzip --bed_index`) is the same statement: `reference_index` reads nothing but
+name, start and end of every line, so the `.tbi` of a `.bed.gz` is `reference_index` of that file; its lines vary in width, may
+be nested and may span many 16 kb windows, which is what the running maximum in the linear index's rule is for.
 
 `reference_index` computes the index's payload from a finished `.gz` file alone and is the statement every other path is held to;
 `IndexBuilder` puts the same payload together from what the track writer knows (chunks and linear index in text offsets from
@@ -224,9 +227,11 @@ class IndexBuilder:
         self.last_bin = -1                                              # the bin of the last chunk of the last sequence
 
     def add(self, file_off: int, sizes: np.ndarray, text_len: int, rec_names: Sequence[bytes], chunks: np.ndarray, linear: np.ndarray,
-            wpref: np.ndarray) -> None:
+            wpref: np.ndarray, last_end=None) -> None:
         """One write of `text_len` text bytes in members of `sizes` compressed bytes at `file_off`: its chunks (CHUNK_DTYPE, text
-        offsets, `rec` an index into rec_names) and its linear index (record r at linear[wpref[r]:wpref[r + 1]], -1: no line)."""
+        offsets, `rec` an index into rec_names) and its linear index (record r at linear[wpref[r]:wpref[r + 1]], -1: no line).
+        last_end[r], where given, is the end of record r's last line: a BED's ends need not ascend, and the sequence's linear index
+        ends with its last line, not with its longest (a track's ends ascend: both are one)."""
         mstart = np.zeros(len(sizes) + 1, np.int64)
         np.cumsum(sizes, out=mstart[1:])
         if len(sizes) != (text_len + BLOCK - 1) // BLOCK:
@@ -260,7 +265,8 @@ class IndexBuilder:
             s = self.names.index(rec_names[r])
             have = self.linear[s]                                       # an earlier record's line comes first in the file
             self.linear[s] = np.concatenate([have, lin[len(have):]])
-            self.n_intv[s] = len(lin)                                   # ... but the sequence ends with its last line
+            # ... but the sequence ends with its last line
+            self.n_intv[s] = len(lin) if last_end is None else ((int(last_end[r]) - 1) >> MIN_SHIFT) + 1
 
     def payload(self) -> bytes:
         return payload(self.names, self.bins, [lin[:n] for lin, n in zip(self.linear, self.n_intv)])

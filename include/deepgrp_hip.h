@@ -544,6 +544,48 @@ int dgrp_format_bed_rows(const char *names, const int64_t *name_off, int64_t nna
                          const dgrp_segment *rows, const dgrp_row_score *scores, int64_t nrows, int min_score,
                          char *out, int64_t cap, int64_t *written);
 
+/* dgrp_bed_text_batch (predict --bed_gzip): the same text written on the device, for rows and scores that are there already
+ * (d_rows, d_scores: device; the scores of dgrp_row_scores_batch on the same stream).  names, name_off, nnames and by_contig as
+ * above: host tables, staged on the stream, which may be dropped on return.  d_text (device) receives exactly the bytes
+ * dgrp_format_bed_rows gives for the same arguments, rows with score < min_score left out.  *h_bytes (host) = the text's length,
+ * always; when it exceeds cap nothing is written and the caller retries (dgrp_format_bed_bound(nrows, longest name) never needs
+ * that).  One check kernel runs before any byte is written: a row with bases <= 0, or with by_contig a contig outside
+ * 0..nnames-1, gives DGRP_EINVAL and leaves d_text untouched.  R is evaluated in 64 bits: with sum = a * bases + r,
+ * R(sum, bases * 2^24, k) = (2 k a + 2^24 + floor(2 k r / bases)) >> 25; that holds for what dgrp_row_scores_batch writes, and a
+ * row outside it (bases >= 2^40, sum > bases * 2^24, agree outside 0..bases) is refused with DGRP_EINVAL as well.  nrows == 0: no
+ * device work, *h_bytes = 0.  nrows < 2^31 - 256.  Workspace dgrp_bed_text_workspace_bytes(nrows, nnames, names_bytes =
+ * name_off[nnames]) (0 on arguments the entry refuses): 16 bytes per row, the names and 8 bytes per name; DGRP_ENOMEM when smaller.
+ * Synchronises the stream ONCE, for the read-back of the length and the check's flags; the write kernel is enqueued behind it: the
+ * text is complete behind the call on `stream`, not on return. */
+int64_t dgrp_bed_text_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes);
+int dgrp_bed_text_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                        const dgrp_row_score *d_scores, int64_t nrows, int min_score, char *d_text, int64_t cap, int64_t *h_bytes,
+                        void *d_work, int64_t work_bytes, void *stream);
+
+/* dgrp_bed_index_batch (predict --bed_index): the tabix pieces of the text dgrp_bed_text_batch writes for the same arguments, in
+ * offsets of that text; the text itself is not written.  The record of a row is its contig with by_contig, else 0 (then nrec must
+ * be 1); h_rec_end[r] (host, nrec entries) is the end coordinate of record r.
+ * Chunks (dgrp_track_chunk, the rule of dgrp_track_index_batch): a maximal run of consecutive EMITTED lines of one record with the
+ * same bin reg2bin(start, end), from the first byte of its first line to the byte behind its last line.  A filtered row neither
+ * starts nor breaks a run; a chunk never spans two records.  *h_nchunks (host) is always their number; when it exceeds chunk_cap
+ * nothing is written, d_linear and d_rec_last included, and the caller retries.
+ * d_linear is laid out [record r][window w], w = 0 .. (h_rec_end[r] - 1) >> 14: the text offset of the first emitted line of the
+ * record, in file order, whose end is greater than w << 14, or -1 -- the running maximum of the ends decides, so a line that ends
+ * below an earlier line of its record claims no window.  linear_cap (elements) must cover the windows of all records.  One thread
+ * per window searches the running maximum; a line's windows are never walked.  d_rec_last (device, nrec entries, may be NULL):
+ * the end of the record's last emitted line, 0 without one (a tabix index ends a sequence's linear index with its last line).
+ * DGRP_EINVAL before anything is written: h_rec_end[r] outside 1..2^29; a row with start < 0, start >= end or end > h_rec_end of
+ * its record (or a record outside 0..nrec-1); records that do not ascend with the rows; starts that descend inside a record (every
+ * row counts, filtered or not); and the text entry's refusals.  nrows == 0: *h_nchunks = 0, no device work, nothing written.
+ * Workspace dgrp_bed_index_workspace_bytes(nrows, nnames, names_bytes, nrec): the text entry's, 76 bytes per row more and 16 per
+ * record.  Synchronises the stream ONCE (the read-back of the chunk count and the flags); chunks, linear index and d_rec_last are
+ * complete behind the call on `stream`. */
+int64_t dgrp_bed_index_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t nrec);
+int dgrp_bed_index_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                         const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end,
+                         dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
+                         int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- compressed input (an addition; the reference reads plain text only): DEFLATE (RFC 1951) streams inflated by the
  * same decode core on the device and on the host (deepgrp_amd/csrc/inflate.h).  A stream that cannot be decoded gives
  * DGRP_EDATA and one of these reasons; no read or write leaves the stream's input and output slices. */
