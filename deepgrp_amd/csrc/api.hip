@@ -656,8 +656,16 @@ DGRP_EXPORT int64_t dgrp_forward_workspace_bytes(const dgrp_model *m, int64_t nw
         const int64_t sub = std::min<int64_t>(ref_sub_windows(m), std::max<int64_t>(nw, 1));
         return dgrp_align_up(dgrp_forward_reference_workspace_bytes(m, sub), 256) + dgrp_align_up(sub * m->T * (int64_t)m->C * 4, 256);
     }
-    if (!m->attention) return 256;
-    return dgrp_align_up(nw * m->T * (int64_t)m->UP * 4, 256) + dgrp_align_up(nw * m->T * (int64_t)m->C * 4, 256);
+    if (!m->attention) return 256;                                   // (the recurrent launch's queue word: forward_queue)
+    return dgrp_align_up(nw * m->T * (int64_t)m->UP * 4, 256) + dgrp_align_up(nw * m->T * (int64_t)m->C * 4, 256) + 256;
+}
+
+// the word of the call's workspace that the recurrent launch takes for its queue of tile pairs (gru_split2_kernel): the first one
+// without attention -- NULL where the caller gave none: the launch then walks a static stride --, the last 256 bytes behind the spill
+static unsigned *forward_queue(const dgrp_model *m, int64_t nw, void *d_work, int64_t work_bytes)
+{
+    if (!d_work || work_bytes < dgrp_forward_workspace_bytes(m, nw)) return nullptr;
+    return (unsigned *)((char *)d_work + (m->attention ? dgrp_forward_workspace_bytes(m, nw) - 256 : 0));
 }
 
 // the forward entry points of a ref_only model: plain-fp32 kernels a few thousand windows at a time; merged output = the reference's own
@@ -709,7 +717,9 @@ static int forward_common(const dgrp_model *m, const uint8_t *d_idx, int64_t n, 
         place = dgrp_make_placement(total, batch);
     }
     if (m->ref_only) return forward_ref(m, d_idx, n, s, place, w0, nw, merge, d_out, d_work, work_bytes, stream);
-    if (!m->attention) return dgrp_gru_launch(m, dgrp_gru_plan_for(m, merge ? 0 : 1, s), d_idx, n, place, w0, nw, d_out, nullptr, stream);
+    if (!m->attention)
+        return dgrp_gru_launch(m, dgrp_gru_plan_for(m, merge ? 0 : 1, s), d_idx, n, place, w0, nw, d_out, nullptr,
+                               forward_queue(m, nw, d_work, work_bytes), stream);
     if (work_bytes < dgrp_forward_workspace_bytes(m, nw) || !d_work) {
         dgrp_set_error("dgrp_forward: attention model needs %lld bytes of workspace for %lld windows",
                        (long long)dgrp_forward_workspace_bytes(m, nw), (long long)nw);
@@ -718,7 +728,7 @@ static int forward_common(const dgrp_model *m, const uint8_t *d_idx, int64_t n, 
     void *avg = d_work;
     float *pl = (float *)((char *)d_work + dgrp_align_up(nw * m->T * (int64_t)m->UP * 4, 256));
     const dgrp_gru_plan pre = dgrp_gru_plan_for(m, 2, s);
-    int rc = dgrp_gru_launch(m, pre, d_idx, n, place, w0, nw, pl, avg, stream);
+    int rc = dgrp_gru_launch(m, pre, d_idx, n, place, w0, nw, pl, avg, forward_queue(m, nw, d_work, work_bytes), stream);
     if (rc) return rc;
     return dgrp_attention_launch_recs(m, pre, place, w0, nw, merge, n, avg, pl, d_out, nullptr, 0, stream);
 }
@@ -961,7 +971,7 @@ int dgrp_batch_segments(const int8_t *d_labels, const uint8_t *d_marks, int64_t 
                         int64_t *d_count, void *d_work, int64_t work_bytes, hipStream_t stream);
 
 struct batch_layout {
-    int64_t out, scores, cls, labels, marks, count, recs, wgf, start, len, spos, contig, post, post_bytes, avg, pl, bytes;
+    int64_t out, scores, cls, labels, marks, count, recs, wgf, start, len, spos, contig, post, post_bytes, avg, pl, queue, bytes;
 };
 
 static batch_layout batch_carve(const dgrp_model *m, int64_t nrec, int64_t total_rows, int64_t total_windows)
@@ -986,6 +996,7 @@ static batch_layout batch_carve(const dgrp_model *m, int64_t nrec, int64_t total
     // attention: avg[t] of every window (fp16) and the avg half of the logits
     l.avg = take(m->attention ? total_windows * m->T * (int64_t)m->UP * 4 : 0);
     l.pl = take(m->attention ? total_windows * m->T * (int64_t)m->C * 4 : 0);
+    l.queue = take(4);                                               // the recurrent launch's queue of tile pairs (gru_split2_kernel)
     l.bytes = p;
     return l;
 }
@@ -1064,14 +1075,14 @@ static int predict_batch_common(const char *who, const dgrp_model *m, const uint
     int rc;
     if (!m->attention) {
         rc = dgrp_gru_launch_batch(m, dgrp_gru_plan_for(m, 0, s), d_idx, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec],
-                                   out, nullptr, stream);
+                                   out, nullptr, (unsigned *)(w + l.queue), stream);
         if (rc) return rc;
     } else {
         // GRU pre-pass for all windows (avg[t] and the avg half of the logits, windows numbered through the batch),
         // then the attention kernel with the same record table for placement
         const dgrp_gru_plan pre = dgrp_gru_plan_for(m, 2, s);
         rc = dgrp_gru_launch_batch(m, pre, d_idx, w + l.recs, (const int64_t *)(w + l.wgf), nrec, wgf[(size_t)nrec], (float *)(w + l.pl),
-                                   w + l.avg, stream);
+                                   w + l.avg, (unsigned *)(w + l.queue), stream);
         if (rc) return rc;
         rc = dgrp_attention_launch_recs(m, pre, dgrp_placement{ 0, 0 }, 0, windows, 1, rows, w + l.avg, (const float *)(w + l.pl), out,
                                         w + l.recs, nrec, stream);

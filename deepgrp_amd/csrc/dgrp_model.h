@@ -61,8 +61,9 @@ struct dgrp_gru_plan {
     int avg_up;                         // row length (elements) of the avg[t] spill: 16 NU16 behind gru_wave_kernel, else UP
 };
 dgrp_gru_plan dgrp_gru_plan_for(const dgrp_model *m, int mode, int64_t s);
+// d_queue: one word of the CALL's workspace for gru_split2_kernel's queue of tile pairs (zeroed by the launch on its stream), or NULL
 int dgrp_gru_launch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, int64_t n, dgrp_placement place,
-                    int64_t w0, int64_t nw, float *d_out, void *d_avg, hipStream_t stream);
+                    int64_t w0, int64_t nw, float *d_out, void *d_avg, unsigned *d_queue, hipStream_t stream);
 // rnn_stream.hip: the streamed split-operand kernel (cell 0 = GRU with 5..8 waves, 1 = LSTM with 1..4 waves)
 struct gru_params;
 int dgrp_stream_launch(const gru_params &p, int cell, int NW, int64_t groups, size_t lds, hipStream_t stream);
@@ -75,7 +76,8 @@ size_t dgrp_stream64_carve(int NW, gru_params &p, int mode, int64_t s, int64_t b
 int dgrp_stream64_launch(const gru_params &p, int NW, int64_t groups, size_t lds, hipStream_t stream);
 // batched records (mode 0): see gru_kernel.hip
 int dgrp_gru_launch_batch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, const void *d_recs,
-                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, hipStream_t stream);
+                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, unsigned *d_queue,
+                          hipStream_t stream);
 int dgrp_attention_launch_recs(const dgrp_model *m, const dgrp_gru_plan &pre, dgrp_placement place, int64_t w0, int64_t nw,
                                int merge, int64_t n, const void *d_avg, const float *d_pl, float *d_out,
                                const void *d_recs, int64_t nrec, hipStream_t stream);

@@ -1233,9 +1233,9 @@ static int64_t tile_budget(const dgrp_model *m, bool split)
     if (m->NW == 2 && split) return 39 * 1024;
     return (m->NW > 4 ? 144 : 72) * 1024;
 }
-// gru_split2_kernel (gru_split2.hip): two tile carves with row pitch UP + 16, then the input-projection table
+// gru_split2_kernel (gru_split2.hip): two tile carves with row pitch UP + 16, then the input-projection table and the queue word
 #define DGRP_SPLIT2_PAD 16
-#define DGRP_SPLIT2_XTAB_BYTES (5 * (4 * 128 * 4 + 32))
+#define DGRP_SPLIT2_XTAB_BYTES (5 * (4 * 128 * 4 + 32) + 16)  /* + the word the queue's answer reaches the workgroup through */
 
 // The recurrent kernel of a launch, in order of preference, and its LDS carve.  A property of the model, the mode and the step,
 // never of the record: a record never changes kernels with the way it is batched.
@@ -1344,12 +1344,12 @@ static int gru_dispatch(const dgrp_model *m, const dgrp_gru_plan &plan, gru_para
 }
 
 int dgrp_gru_launch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, int64_t n, dgrp_placement place,
-                    int64_t w0, int64_t nw, float *d_out, void *d_avg, hipStream_t stream)
+                    int64_t w0, int64_t nw, float *d_out, void *d_avg, unsigned *d_queue, hipStream_t stream)
 {
     if (nw <= 0) return DGRP_OK;
     dgrp_timer_scope timed(stream, nw);                             // bench.py: HIP events around the launch (no-op unless enabled)
     gru_params p{};
-    p.idx = d_idx; p.n = n; p.w0 = w0; p.nw = nw; p.place = place; p.out = d_out; p.avg = d_avg;
+    p.idx = d_idx; p.n = n; p.w0 = w0; p.nw = nw; p.place = place; p.out = d_out; p.avg = d_avg; p.queue = d_queue;
     const int64_t groups = (nw + DGRP_WG_WINDOWS - 1) / DGRP_WG_WINDOWS;
     DGRP_REQUIRE(groups < (1ll << 31), "too many windows in one launch (%lld)", (long long)nw);
     return gru_dispatch(m, plan, p, groups, stream);
@@ -1358,13 +1358,14 @@ int dgrp_gru_launch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_
 // A batch of records in ONE launch (mode 0, or the GRU attention pre-pass): the record table and the cumulative workgroup counts
 // are device arrays prepared by the caller (api.hip: dgrp_predict_batch)
 int dgrp_gru_launch_batch(const dgrp_model *m, const dgrp_gru_plan &plan, const uint8_t *d_idx, const void *d_recs,
-                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, hipStream_t stream)
+                          const int64_t *d_wg_first, int64_t nrec, int64_t total_groups, float *d_out, void *d_avg, unsigned *d_queue,
+                          hipStream_t stream)
 {
     if (nrec <= 0 || total_groups <= 0) return DGRP_OK;
     dgrp_timer_scope timed(stream, total_groups * DGRP_WG_WINDOWS);
     DGRP_REQUIRE(m->NW <= 8 && (plan.mode == 0 || (plan.mode == 2 && m->cell == 0)), "dgrp_gru_launch_batch: mode 0, or the GRU attention pre-pass");
     gru_params p{};
-    p.idx = d_idx; p.out = d_out; p.avg = d_avg;
+    p.idx = d_idx; p.out = d_out; p.avg = d_avg; p.queue = d_queue;
     p.recs = (const gru_rec *)d_recs; p.wg_first = d_wg_first; p.nrec = nrec;
     DGRP_REQUIRE(total_groups < (1ll << 31), "too many windows in one launch");
     return gru_dispatch(m, plan, p, total_groups, stream);

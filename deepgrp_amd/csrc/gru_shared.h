@@ -44,6 +44,9 @@ struct gru_params {
     const uint4 *pack16;
     const float *xtab;
     int xtab_off;
+    // gru_split2_kernel only: the launch's queue of tile pairs -- one word of the CALL's workspace, zeroed on the launch's stream in front
+    // of it (launches run side by side on streams and host threads: never a word they share) -- or NULL: every workgroup walks a static stride
+    unsigned *queue;
     // rnn_split_stream_kernel only (rnn_stream.hip): hi and lo recurrent fragments in consumption order, [NW][KS][2 G][64]
     const uint4 *stream;
     // gru_wave_kernel only (gru_wave.hip, GRU up to 64 units): all-unit 16x16x32 A fragments + Dense B fragments, the input-projection

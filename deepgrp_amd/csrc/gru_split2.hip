@@ -36,9 +36,14 @@
 //   - the weight loads are asm statements and so is the ONE s_waitcnt behind all 50 of them (volatile asm keeps its program order:
 //     every MFMA stays behind it); the compiler's own counter waits only ever see more loads in flight than it knows of, never fewer.
 //
-// Launch shape: min(tile pairs, CUs) workgroups (a CU holds one: 146 KB of LDS, 512-register waves), each walking the pairs
-// blockIdx.x, blockIdx.x + gridDim.x, ... -- weights and table are loaded once per workgroup, not once per pair; every pair costs the
-// same, so the stride is static and workgroups never wait on one another.
+// Launch shape: min(tile pairs, CUs) workgroups (a CU holds one: 146 KB of LDS, 512-register waves); weights and table are loaded once
+// per workgroup, not once per pair.  Workgroup b starts with pair b; every later pair comes from the launch's queue (gru_params::queue:
+// one word of the call's workspace, zero at the launch: pair = gridDim.x + its old value).  One lane asks for it in front of the drain,
+// the answer goes through an LDS word behind the barrier that closes the pair: the round trip lies under the drain, and nothing of it
+// lives across the time loop.  A pair costs every workgroup the same instructions but not the same time (a workgroup's XCD is fixed by
+// its index and the XCDs need not hold one clock at the power cap), so a static share is balanced only on paper.  Without a queue
+// (a caller that gave the entry point no workspace) workgroup b walks b, b + gridDim.x, ...; which workgroup runs a pair, and after
+// which others, does not show in a bit of the result (max-merge, disjoint window rows).
 #include "gru_shared.h"
 #include <cstddef>
 #include <mutex>
@@ -50,6 +55,43 @@ namespace {
 
 constexpr int NW = 4, UP = 128, KS = 4, HPAD = 16, HS = UP + HPAD;   // k-steps of 32; row pitch 144 halves: conflict-free ds_read_b128
 constexpr int XT_PITCH = 4 * 128 * 4 + 32;                            // table row of one base: 4 kinds x 128 units fp32 + 32 B (bank spread)
+constexpr int QUEUE_LDS = 16;                                         // behind the table: the word the next pair's index reaches the workgroup through
+
+// Diagnostic build only (tools/build_split2_stamps.sh, -DDGRP_SPLIT2_STAMPS; never the product): per workgroup, words of 8 bytes in a
+// buffer nothing else reads -- [0] s_memrealtime at entry, [1] at exit, [2] pairs run, then per pair s_memtime at set-up start,
+// time-loop start, drain start and pair end.  One stamp per boundary, none inside the time loop; no output value depends on one.
+#ifdef DGRP_SPLIT2_STAMPS
+struct split2_stamp_buf { unsigned long long *at; int pairs_cap; int static_walk; };
+split2_stamp_buf g_stamps = { nullptr, 0, 0 };
+// (what a stamp needs is read where it is written -- buffer and capacity from the kernel-argument segment, the count of pairs run from
+// an LDS word of the one lane that stamps -- so that the time loop carries nothing for it)
+#define STAMP_DO(pair_k, slot, clock)                                                                                   \
+    do {                                                                                                                \
+        const unsigned long long t_ = (clock);                                                                          \
+        const __attribute__((address_space(4))) unsigned *ks_ = (const __attribute__((address_space(4))) unsigned *)__builtin_amdgcn_kernarg_segment_ptr(); \
+        asm volatile("" : "+s"(ks_));                                                                                   \
+        unsigned long long *const sb_ = (unsigned long long *)(((uint64_t)ks_[offsetof(split2_args, stamps) / 4 + 1] << 32) | ks_[offsetof(split2_args, stamps) / 4]); \
+        const unsigned cap_ = ks_[offsetof(split2_args, stamp_pairs) / 4];                                              \
+        unsigned *const nrun_ = reinterpret_cast<unsigned *>(smem + ks_[offsetof(gru_params, xtab_off) / 4] + 5 * XT_PITCH + 4); \
+        if (sb_ && wave == 0 && lane == 0) {                                                                            \
+            unsigned long long *const row_ = sb_ + (size_t)blockIdx.x * (3 + 4 * (size_t)cap_);                         \
+            if ((pair_k) < 0) {                                                                                         \
+                if ((slot) == 0) *nrun_ = 0;                                                                            \
+                row_[slot] = t_;                                                                                        \
+                if ((slot) == 1) row_[2] = *nrun_;                                                                      \
+            } else {                                                                                                    \
+                const unsigned n_ = *nrun_;                                                                             \
+                if (n_ < cap_) row_[3 + 4 * (size_t)n_ + (pair_k)] = t_;                                                \
+                if ((pair_k) == 3) *nrun_ = n_ + 1;                                                                     \
+            }                                                                                                           \
+        }                                                                                                               \
+    } while (0)
+#define STAMP(slot, clock) STAMP_DO(-1, slot, clock)
+#define STAMP_PAIR(k) STAMP_DO(k, 0, __builtin_amdgcn_s_memtime())
+#else
+#define STAMP(slot, clock) do { } while (0)
+#define STAMP_PAIR(k) do { } while (0)
+#endif
 
 struct split2_weights {                   // 50 fragments = 200 AGPRs per lane, resident for the whole kernel
     u32x4 hi[3][KS][2], lo[3][KS][2];     // [gate r, g, z][k-step][unit half]: U_hi, U_lo
@@ -176,19 +218,24 @@ struct split2_args {
     gru_params p;
     int half_bytes;                       // bytes of one tile's LDS carve
     int npairs;                           // tile pairs of the launch
+#ifdef DGRP_SPLIT2_STAMPS
+    unsigned long long *stamps;
+    int stamp_pairs;
+#endif
 };
 
 template <int MODE, bool ONERCP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gru_split2_kernel(const split2_args args)
 {
     static_assert(offsetof(split2_args, p) == 0 && sizeof(gru_params) % 4 == 0 && offsetof(split2_args, half_bytes) % 4 == 0 &&
-                  offsetof(split2_args, npairs) % 4 == 0, "the pair loop reads the argument as 32-bit words");
+                  offsetof(split2_args, npairs) % 4 == 0 && offsetof(gru_params, queue) % 8 == 0, "the pair loop reads the argument as 32-bit words");
     const gru_params &pin = args.p;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = pin.T, C = pin.C;
+    STAMP(0, __builtin_amdgcn_s_memrealtime());
 
     split2_weights W;
     {
@@ -415,6 +462,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     const int half_k = (int)kargs[offsetof(split2_args, half_bytes) / 4];
     int tid_k = 64 * wave + lane;                // (= tid, from what the time loop keeps anyway)
     asm volatile("" : "+v"(tid_k));
+    STAMP_PAIR(0);
     setup(S0, pk, tid_k, half_k, pair, 0);
     setup(S1, pk, tid_k, half_k, pair, 1);
     __syncthreads();
@@ -422,6 +470,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     placement(S1, tid_k);
     first_step(S0);
     first_step(S1);
+    STAMP_PAIR(1);
     phase(yes, no, no, S0, S1, 0, 0);
     // Register copies the allocator places on a control-flow edge (loop entry, back edge, exit) are VALU reads it does not know to
     // keep away from the asm MFMAs in front of them: the last MFMAs of a phase have to be complete before the edge.
@@ -454,13 +503,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     };
     int tid_d = 64 * wave + lane;
     asm volatile("" : "+v"(tid_d));             // (nothing of the drain is worked out ahead of the time loop and kept across it)
+    STAMP_PAIR(2);
+    // the next pair: ONE lane asks the queue in front of the drain (the counter's round trip lies under it: the drain has registers to
+    // spare, the time loop has none) and hands the answer to the workgroup through an LDS word in front of the closing barrier
+    const __attribute__((address_space(4))) unsigned *kargs_d = kargs;
+    asm volatile("" : "+s"(kargs_d));           // (read here, not ahead of the time loop)
+    typedef __attribute__((address_space(1))) unsigned global_u32;
+    global_u32 *const queue = (global_u32 *)(((uint64_t)kargs_d[offsetof(gru_params, queue) / 4 + 1] << 32) | kargs_d[offsetof(gru_params, queue) / 4]);
+    unsigned *const qword = reinterpret_cast<unsigned *>(smem + kargs_d[offsetof(gru_params, xtab_off) / 4] + 5 * XT_PITCH);
+    const bool ask = queue && tid_d == 0;
+    unsigned nxt;
+    asm volatile("" : "=v"(nxt));               // (no value: only the asking lane's is read, and nothing waits for the answer here)
+    // (an increment that never wraps, not an add: the compiler would fold an add over the wave's lanes and wait for the answer at once)
+    if (ask) nxt = __builtin_amdgcn_atomic_inc32(queue, 0xffffffffu, __ATOMIC_RELAXED, "agent");
     drain(S0, false, tid_d);
     drain(S1, true, tid_d);                            // tile 1 stored its partials of step T - 2 in the last phase: no phase of its own follows
+    if (ask) *qword = nxt + gridDim.x;
     __syncthreads();                            // the next pair's set-up rewrites what this pair's drain and flush still read
     EDGE_PAD;                                   // (the pair loop's back edge and exit: the drain's Dense chain has its own pad; kept as the rule)
-    pair += (int)gridDim.x;
-    if (pair >= (int)kargs[offsetof(split2_args, npairs) / 4]) break;
+    STAMP_PAIR(3);
+    if (queue) pair = __builtin_amdgcn_readfirstlane((int)*qword);          // (written once per pair, read behind the barrier: no set-up touches it)
+    else pair += (int)gridDim.x;
+    if (pair >= (int)kargs_d[offsetof(split2_args, npairs) / 4]) break;
     }
+    STAMP(1, __builtin_amdgcn_s_memrealtime());
 }
 
 // compute units of the current device, looked up once per DEVICE (records run on a pool of host threads, ranks on devices of their own)
@@ -496,12 +562,31 @@ int launch_split2(const gru_params &p, int64_t groups, int half_bytes, hipStream
     if (const int rc = split2_cu_count(&cus)) return rc;
     const int64_t grid = npairs < cus ? npairs : cus;
     DGRP_REQUIRE(npairs >= 1 && npairs <= 0x7fff0000, "gru_split2_kernel: tile pairs out of range");      // (the walk counts pairs in an int)
-    hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)grid), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH, stream, split2_args{ p, half_bytes, (int)npairs });
+    // the queue: only a launch with more pairs than workgroups hands any out (short records pay no second launch); zeroed on THIS stream
+    split2_args a{ p, half_bytes, (int)npairs };
+    if (npairs <= grid) a.p.queue = nullptr;
+#ifdef DGRP_SPLIT2_STAMPS
+    if (g_stamps.static_walk) a.p.queue = nullptr;
+    a.stamps = g_stamps.at;
+    a.stamp_pairs = g_stamps.pairs_cap;
+#endif
+    if (a.p.queue) DGRP_HIP(hipMemsetAsync(a.p.queue, 0, sizeof(unsigned), stream));
+    hipLaunchKernelGGL((gru_split2_kernel<MODE, ONERCP>), dim3((unsigned)grid), dim3(256), (size_t)2 * half_bytes + 5 * XT_PITCH + QUEUE_LDS, stream, a);
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
 }
 
 }  // namespace
+
+#ifdef DGRP_SPLIT2_STAMPS
+// diagnostic build: where the next launches write their stamps (3 + 4 pairs_cap words of 8 bytes per workgroup, zeroed by the caller;
+// NULL: nowhere), and whether they walk the static stride although the call has a queue
+extern "C" __attribute__((visibility("default"))) int dgrp_split2_stamps(void *d_buf, int pairs_cap, int static_walk)
+{
+    g_stamps = { (unsigned long long *)d_buf, pairs_cap, static_walk };
+    return DGRP_OK;
+}
+#endif
 
 int dgrp_split2_launch(const gru_params &p, int64_t groups, int half_bytes, bool onercp, hipStream_t stream)
 {

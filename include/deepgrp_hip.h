@@ -216,7 +216,11 @@ int dgrp_model_view(const dgrp_model *m, int level, dgrp_model **out);
 int dgrp_model_plan(const dgrp_model *m, int mode, int64_t step, int *kernel, int64_t *lds_bytes, int *ospan, int *avg_up);
 
 /* ---- A4: model.predict_on_batch (deepgrp/prediction.py:106)
- * Bytes of scratch HBM dgrp_forward_* needs for `nw` windows in one call. */
+ * Bytes of scratch HBM dgrp_forward_* needs for `nw` windows in one call: the avg[t] spill and the avg half of the logits of an attention
+ * model plus 256 bytes, 256 bytes without attention.  One word of it is the launch's queue of tile pairs (gru_split2_kernel, 97-128
+ * units: zeroed by the call on its stream), so a workspace belongs to ONE call at a time: calls that run side by side -- other streams,
+ * other host threads -- each bring their own.  Without attention the workspace may be NULL / 0 as before: the launch then gives every
+ * workgroup a fixed share of the windows instead (same result bit for bit, a few percent slower on records of more than 8 192 windows). */
 int64_t dgrp_forward_workspace_bytes(const dgrp_model *m, int64_t nw);
 /* Windows per call the library itself uses inside dgrp_predict_record, and the size callers of dgrp_forward_merge should cut a
  * record into (the reference's predict loop, deepgrp/prediction.py:104-110, goes batch by batch; here a "batch" is a launch):
