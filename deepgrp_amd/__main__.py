@@ -420,14 +420,17 @@ class CommandLineParser:
                     kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
                     # --track_dir, --bed_dir: the input's files are renamed into place when all of its records are done, and removed
                     # when one raises
-                    files = tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None
+                    outs = []
                     try:
-                        beds = bed.BedFiles(bed_plan, filename) if bed_plan is not None else None
+                        outs.append(tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None)
+                        outs.append(bed.BedFiles(bed_plan, filename) if bed_plan is not None else None)
+                        bases = CommandLineParser._predict_file(pipe, runner, filename, records_of(filename), outstream, kept, *outs)
+                        for out in filter(None, outs):
+                            out.commit()
                     except BaseException:
-                        if files is not None:
-                            files.abort()
+                        for out in filter(None, outs):
+                            out.abort()
                         raise
-                    bases = CommandLineParser._predict_file(pipe, runner, filename, records_of(filename), outstream, kept, files, beds)
                     if kept is not None:
                         outstream.flush()
                         t_mask = time.perf_counter()
@@ -493,7 +496,8 @@ class CommandLineParser:
     def _predict_file(pipe, runner, filename, records, outstream, kept, files=None, beds=None) -> int:
         """predict's loop over one input: the TSV rows of every record to `outstream` and to `kept` (_RowsByRecord, --mask_dir);
         with --track_dir the track texts to `files` (tracks.TrackFiles), with --bed_dir every row's BED line to `beds`
-        (bed.BedFiles), both from the merged array the rows come from (`runner` was made with the same two choices).  -> bases read"""
+        (bed.BedFiles, the caller commits or aborts both), both from the merged array the rows come from (`runner` was made with
+        the same two choices).  -> bases read"""
         from .evaluation import record_name
         from .fasta import DeviceRecord
         from .pipeline import record_indices
@@ -501,53 +505,42 @@ class CommandLineParser:
         from .tracks import empty_texts, record_texts
         named = files is not None or beds is not None           # the runner's keys are then (header, name of the track and BED lines)
         bases = 0
-        try:
-            if _LOG.isEnabledFor(logging.DEBUG):
-                # -vv: record by record through the staged form of the same path, a device sync and a clock around every stage
-                # (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
-                for chrom, (header, rec) in enumerate(records):
-                    name = record_name(filename, header) if named else None
-                    track_sink = score_sink = None
-                    if files is not None:
-                        track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
-                    if beds is not None and runner.bed is not None:     # --bed_gzip: scores, text and members on the device
-                        score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
-                            merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed))
-                    elif beds is not None:
-                        score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
-                    rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
-                    if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
-                        files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
-                    bases += n
-                    outstream.write(rows_text(filename, header, rows))
-                    if kept is not None:
-                        kept.add(rows, 1)
-            else:
-                def keyed():
-                    nonlocal bases
-                    for header, rec in records:
-                        bases += max(rec.length, 0) + max(rec.startpos, 0) if isinstance(rec, DeviceRecord) else len(rec)
-                        yield ((header, record_name(filename, header)) if named else header), rec
-                for kind, key, rows, scores, texts in runner.outputs(keyed()):
-                    keys = key if kind == "batch" else [key]
-                    headers = [header for header, _name in keys] if named else keys
-                    outstream.write(rows_text_batch(filename, headers, rows) if kind == "batch" else rows_text(filename, headers[0], rows))
-                    if beds is not None:
-                        beds.write([name for _header, name in keys], kind == "batch", rows, scores)
-                    if files is not None:
-                        files.write(texts)
-                    if kept is not None:
-                        kept.add(rows, len(keys))
-        except BaseException:
-            if beds is not None:
-                beds.abort()
-            if files is not None:
-                files.abort()
-            raise
-        if files is not None:
-            files.commit()
-        if beds is not None:
-            beds.commit()
+        if _LOG.isEnabledFor(logging.DEBUG):
+            # -vv: record by record through the staged form of the same path, a device sync and a clock around every stage
+            # (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
+            for chrom, (header, rec) in enumerate(records):
+                name = record_name(filename, header) if named else None
+                track_sink = score_sink = None
+                if files is not None:
+                    track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
+                if beds is not None and runner.bed is not None:     # --bed_gzip: scores, text and members on the device
+                    score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
+                        merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed))
+                elif beds is not None:
+                    score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
+                rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
+                if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
+                    files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
+                bases += n
+                outstream.write(rows_text(filename, header, rows))
+                if kept is not None:
+                    kept.add(rows, 1)
+        else:
+            def keyed():
+                nonlocal bases
+                for header, rec in records:
+                    bases += max(rec.length, 0) + max(rec.startpos, 0) if isinstance(rec, DeviceRecord) else len(rec)
+                    yield ((header, record_name(filename, header)) if named else header), rec
+            for kind, key, rows, scores, texts in runner.outputs(keyed()):
+                keys = key if kind == "batch" else [key]
+                headers = [header for header, _name in keys] if named else keys
+                outstream.write(rows_text_batch(filename, headers, rows) if kind == "batch" else rows_text(filename, headers[0], rows))
+                if beds is not None:
+                    beds.write([name for _header, name in keys], kind == "batch", rows, scores)
+                if files is not None:
+                    files.write(texts)
+                if kept is not None:
+                    kept.add(rows, len(keys))
         return bases
 
     @staticmethod

@@ -13,7 +13,7 @@ rounds the quotients half up.  `reference_scores` and `reference_lines` restate 
 
 With `--bed_gzip` the file is `DIR/<basename>.bed.gz`, BGZF as bgzip writes it.  Rows and scores then stay on the device: the lines
 are written there (dgrp_bed_text_batch, the host formatter's bytes), deflated there (gz.bgzf_compress_device, --gzip_level, 1
-unless given) in pieces of tracks.GZIP_PIECE, and only the members are read back; the text of one record, or of one batch, is one
+unless given) in pieces of gz.GZIP_PIECE, and only the members are read back; the text of one record, or of one batch, is one
 write, so a record or batch boundary is a short member, and the EOF member is written at `commit`.  With `--bed_index` the file
 gets its tabix index `<basename>.bed.gz.tbi`: chunks and linear index come from the device in text offsets (dgrp_bed_index_batch;
 `reference_index_parts` restates them), `BedFiles` turns them into virtual offsets with the compressed size of every member it
@@ -24,11 +24,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
-import tempfile
 import logging
 from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
+
+from .outfiles import BgzfSink, StagedFile, StagedOutputs
 
 _LOG = logging.getLogger(__name__)
 
@@ -105,112 +106,36 @@ def plan(args) -> Optional[BedPlan]:
     return BedPlan(bdir, int(low), paths, level, index)
 
 
-class BedFiles:
-    """The BED file of one input: written to a temporary file next to it, renamed by `commit`, removed by `abort`.  With
-    p.gzip_level `write` takes a BedWrite (BGZF members) and `commit` puts the EOF member behind them.  With p.index it keeps the
-    file offset of every write and a tabix.IndexBuilder, and `commit` writes `<file>.tbi` the same way.  An input that cannot be
-    indexed (a record that ends above 2^29, an empty name, a name that reappears after another name) gets one warning and no
-    index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed."""
+class BedFiles(StagedOutputs):
+    """The BED file of one input: a temporary file next to it, renamed by `commit`, removed by `abort` (outfiles.py).  With
+    p.gzip_level `write` takes a BedWrite (BGZF members, to an outfiles.BgzfSink, which with p.index builds `<file>.tbi`).  An
+    input that cannot be indexed (a record that ends above 2^29, an empty name, a name that comes back: name_order) gets one
+    warning and no index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed."""
 
     def __init__(self, p: BedPlan, filename: str):
         os.makedirs(p.directory, exist_ok=True)
-        self.final = p.paths[filename]
-        self.min_score = p.min_score
-        self.filename = filename
-        self.gzip = p.gzip_level is not None
-        self.builder = None
-        if self.gzip and p.index:
-            from .tabix import IndexBuilder
-            self.builder = IndexBuilder()
-            self.seen, self.last = set(), None
-        self.index_wanted = self.builder is not None
-        self.off = 0                                    # bytes of members written
-        self.tbi_tmp = None
-        fd, self.tmp = tempfile.mkstemp(prefix="." + os.path.basename(self.final) + ".", suffix=".tmp", dir=p.directory)
-        self.fh = os.fdopen(fd, "wb")
+        self.final, self.min_score, self.gzip = p.paths[filename], p.min_score, p.gzip_level is not None
+        super().__init__(_LOG, filename, "--bed_index", self.gzip and p.index,
+                         [BgzfSink(self.final, p.index) if self.gzip else StagedFile(self.final)])
 
     def write(self, names: Sequence, by_contig: bool, rows, scores) -> None:
         """The lines of one record (by_contig false: names[0]) or of a batch (rows["contig"] indexes the names); `scores` is the
         rows' ROW_SCORE_DTYPE array, or with p.gzip_level the BedWrite the device made of rows and scores."""
-        if isinstance(scores, BedWrite):
-            return self._write_members(scores)
-        if self.gzip:
-            raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")
-        if len(rows):
-            self.fh.write(format_rows(names, by_contig, rows, scores, self.min_score))
-
-    def _write_members(self, w: BedWrite) -> None:
+        if not isinstance(scores, BedWrite):
+            if self.gzip:
+                raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")
+            if len(rows):
+                self.append(0, format_rows(names, by_contig, rows, scores, self.min_score))
+            return
+        w = scores
         if not self.gzip:
             raise ValueError(f"{self.filename}: BGZF members for a plain BED")
-        if w.members:
-            self.fh.write(w.members)
-        if self.builder is not None:
-            self._index(w)
-        self.off += len(w.members)
-
-    def _no_index(self, why: str) -> None:
-        if self.builder is not None:
-            _LOG.warning("%s: no tabix index is written (--bed_index): %s", self.filename, why)
-            self.builder = None
-
-    def _index(self, w: BedWrite) -> None:
-        """The write's part of the index; its members go to file offset self.off."""
-        from .tabix import IndexRefused, member_sizes
-        for nm in w.names:
-            if not nm:
-                return self._no_index("a record with an empty name")
-            if nm != self.last:
-                if nm in self.seen:
-                    return self._no_index(f"the record name {nm.decode('utf-8', 'replace')!r} reappears after another name")
-                self.seen.add(nm)
-                self.last = nm
-        if w.refused is not None:
-            return self._no_index(w.refused)
-        if not w.members:
-            return
-        if w.chunks is None:
-            return self._no_index("a write came without its index")
-        sizes, text_len = member_sizes(w.members)
-        try:
-            self.builder.add(self.off, sizes, text_len, w.names, w.chunks, w.linear, w.wpref, w.last_end)
-        except IndexRefused as e:
-            self._no_index(str(e))
-
-    def _commit_index(self) -> None:
-        """`<file>.tbi` through a temporary file; without an index, one left by an earlier run goes."""
-        from .tabix import index_file
-        tbi = self.final + ".tbi"
-        if self.builder is None:
-            if os.path.exists(tbi):
-                os.remove(tbi)
-            return
-        fd, self.tbi_tmp = tempfile.mkstemp(prefix="." + os.path.basename(tbi) + ".", suffix=".tmp", dir=os.path.dirname(tbi))
-        with os.fdopen(fd, "wb") as fh:
-            fh.write(index_file(self.builder.payload()))
-
-    def commit(self) -> None:
-        try:
-            if self.gzip:
-                from .gz import BGZF_EOF
-                self.fh.write(BGZF_EOF)
-            self.fh.close()
-            if self.index_wanted:
-                self._commit_index()
-        except BaseException:
-            self.abort()
-            raise
-        os.replace(self.tmp, self.final)
-        self.tmp = None
-        if self.tbi_tmp is not None:
-            os.replace(self.tbi_tmp, self.final + ".tbi")
-            self.tbi_tmp = None
-
-    def abort(self) -> None:
-        self.fh.close()
-        for tmp in (self.tmp, self.tbi_tmp):
-            if tmp is not None and os.path.exists(tmp):
-                os.remove(tmp)
-        self.tmp = self.tbi_tmp = None
+        if self.indexed:                                # (the names count in the order even where the write has no members)
+            why = self.name_order(w.names) or w.refused
+            if why is None and w.members and w.chunks is None:
+                why = "a write came without its index"
+            self.no_index(why)
+        self.append(0, w.members, w.names, w.chunks, w.linear, w.wpref, w.last_end)
 
 
 def format_rows(names: Sequence, by_contig: bool, rows, scores, min_score: int = 0) -> bytes:
@@ -303,10 +228,9 @@ def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_sc
     A chunk is a maximal run of consecutive emitted lines of one record with one bin; linear[wpref[r] + w] is the text offset of
     the first emitted line of record r, in file order, whose end is greater than w << 14 (the running maximum of the ends), or
     -1; last_end[r] the end of the record's last emitted line, 0 without one."""
-    from .tabix import CHUNK_DTYPE, MIN_SHIFT, reg2bin
+    from .tabix import CHUNK_DTYPE, MIN_SHIFT, reg2bin, window_prefix
     nrec = len(rec_end)
-    wpref = np.zeros(nrec + 1, np.int64)
-    np.cumsum([((int(e) - 1) >> MIN_SHIFT) + 1 for e in rec_end], out=wpref[1:])
+    wpref = window_prefix(rec_end)
     linear = np.full(int(wpref[-1]), -1, np.int64)
     filled = [0] * nrec
     last_end = np.zeros(nrec, np.int64)

@@ -9,6 +9,7 @@
 // lines, so the maximum of record << 32 | end over a prefix is the last record's running maximum of ends.
 #include "dgrp_common.h"
 #include "scan.h"
+#include "tabix_bins.h"
 #include <string.h>
 #include <vector>
 
@@ -16,7 +17,6 @@ namespace {
 
 #define BED_ONE (1ull << 24)               // q(1.0)
 #define BED_MAX_BASES (1ll << 40)          // the envelope of the 64-bit rounding below
-#define BED_MAX_END (1ll << 29)            // the largest coordinate of a tabix index
 #define BED_MAX_ROWS ((1ll << 31) - 256)   // one thread per row, 256 a workgroup
 
 enum { F_BASES, F_NAME, F_RANGE, F_SPAN, F_END, F_RECORDS, F_STARTS, F_COUNT };
@@ -179,17 +179,6 @@ __global__ void __launch_bounds__(256) bed_write_kernel(bed_in A, const uint64_t
 }
 
 // ---- the index -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bed_reg2bin(int64_t beg, int64_t end)
-{
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
-    return 0;
-}
-
 struct bed_lines {                 // the emitted lines, compacted: m = *count of them
     const uint64_t *count;
     int64_t *beg, *end;            // text offsets: the line's first byte, the byte behind it
@@ -208,7 +197,7 @@ __global__ void __launch_bounds__(256) bed_compact_kernel(bed_in A, const uint64
     Ln.beg[j] = (int64_t)off[i];
     Ln.end[j] = (int64_t)(off[i] + len[i]);
     Ln.key[j] = (uint64_t)(uint32_t)(A.by_contig ? row.contig : 0) << 32 | (uint64_t)(row.end & 0xffffffffll);
-    Ln.bin[j] = bed_reg2bin(row.start, row.end);
+    Ln.bin[j] = tabix_reg2bin(row.start, row.end);
 }
 
 // One thread per slot: 1 where line j opens a chunk (the first line, another record, another bin), 0 elsewhere and behind the lines.
@@ -499,7 +488,7 @@ DGRP_EXPORT int dgrp_bed_index_batch(const char *names, const int64_t *name_off,
     DGRP_REQUIRE(by_contig || nrec == 1, "%s: without by_contig every row belongs to record 0, so nrec must be 1, not %lld", who, (long long)nrec);
     std::vector<int64_t> wpref((size_t)nrec + 1, 0);
     for (int64_t r = 0; r < nrec; ++r) {
-        DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= BED_MAX_END,
+        DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= TABIX_MAX_END,
                      "%s: record %lld ends at %lld, outside 1..2^29 (the largest coordinate of a tabix index)", who, (long long)r,
                      (long long)h_rec_end[r]);
         wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_rec_end[r] - 1) >> 14) + 1;

@@ -9,6 +9,7 @@
 // See include/deepgrp_hip.h.
 #include "dgrp_common.h"
 #include "scan.h"
+#include "tabix_bins.h"
 #include "track_chain.h"
 #include <string.h>
 #include <vector>
@@ -405,20 +406,6 @@ static bool track_carve_one(int64_t n, int64_t bin, tb_layout *l)
 // positions at or in front of every bin (firsts and lasts alternate, so at a `last` bin these are the line's own first bin, the
 // previous line's first bin, the bin itself and the previous line's last bin).  Coordinates follow from bin positions by
 // arithmetic, and a line's first byte is its end minus its length, which its coordinates give.  No lane walks a run or a gap.
-#define IX_SHIFT 14
-#define IX_MAX_END (1ll << 29)           // TBI: min_shift 14, depth 5
-
-__device__ __forceinline__ uint32_t ix_reg2bin(int64_t beg, int64_t end)
-{
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
-    return 0;
-}
-
 struct ix_top2 { int64_t a, b; };        // the largest and the second largest position of a set (-1: none)
 struct ix_state { ix_top2 F, L; };       // of the `first` bins and of the `last` bins
 
@@ -529,19 +516,19 @@ __global__ void __launch_bounds__(256) ix_tile_kernel(const uint32_t *__restrict
             const int64_t p0 = pref[rr], end = t.p.hi;
             int64_t start, pstart, pend = 0, x;
             track_bin_span(g, s.F.a - p0, start, x);                       // the line's first bin
-            bn = ix_reg2bin(start, end);
+            bn = tabix_reg2bin(start, end);
             const bool prev = s.L.b >= p0;                                 // the previous `last` bin lies in this record
             cs = true;
             if (prev) {
                 track_bin_span(g, s.F.b - p0, pstart, x);
                 track_bin_span(g, s.L.b - p0, x, pend);
-                cs = ix_reg2bin(pstart, pend) != bn;
+                cs = tabix_reg2bin(pstart, pend) != bn;
             }
             if (MODE == 2) {
                 const int64_t len = R.name_len + track_decimal_width((uint64_t)start) + track_decimal_width((uint64_t)end) + G.digits + 6;
                 beg = at + ex + t.p.head + t.p.tail - len;
-                const int64_t wl = prev ? (pend + (1 << IX_SHIFT) - 1) >> IX_SHIFT : 0;
-                wc = ((end - 1) >> IX_SHIFT) - wl + 1;
+                const int64_t wl = prev ? (pend + (1 << TABIX_MIN_SHIFT) - 1) >> TABIX_MIN_SHIFT : 0;
+                wc = ((end - 1) >> TABIX_MIN_SHIFT) - wl + 1;
                 wbase = k * W + wpref[rr] + wl;
             }
         }
@@ -615,7 +602,7 @@ static bool ix_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos
 {
     if (!tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l->t) || nrec >= (1ll << 31)) return false;
     for (int64_t r = 0; r < nrec; ++r)
-        if (h_startpos[r] + h_n[r] > IX_MAX_END) return false;
+        if (h_startpos[r] + h_n[r] > TABIX_MAX_END) return false;
     const int64_t ntiles = l->t.NBpad / TRACK_TILE * ncls;
     int64_t p = l->t.bytes;
     l->wpref = p;
@@ -762,13 +749,13 @@ DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec
                      (long long)h_n[r]);
         DGRP_REQUIRE(h_startpos[r] >= 0 && h_startpos[r] <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: record %lld: bad offset %lld",
                      (long long)r, (long long)h_startpos[r]);
-        DGRP_REQUIRE(h_startpos[r] + h_n[r] <= IX_MAX_END,
+        DGRP_REQUIRE(h_startpos[r] + h_n[r] <= TABIX_MAX_END,
                      "dgrp_track_index_batch: record %lld ends at %lld, above 2^29 = 536870912, the largest coordinate of a tabix index",
                      (long long)r, (long long)(h_startpos[r] + h_n[r]));
         DGRP_REQUIRE(h_row0[r] >= 0, "dgrp_track_index_batch: record %lld: bad first row %lld", (long long)r, (long long)h_row0[r]);
         DGRP_REQUIRE(h_name_off[r + 1] >= h_name_off[r], "dgrp_track_index_batch: record %lld: descending name offsets (%lld, %lld)",
                      (long long)r, (long long)h_name_off[r], (long long)h_name_off[r + 1]);
-        wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_startpos[r] + h_n[r] - 1) >> IX_SHIFT) + 1;
+        wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_startpos[r] + h_n[r] - 1) >> TABIX_MIN_SHIFT) + 1;
     }
     const int64_t names_bytes = h_name_off[nrec], W = wpref[(size_t)nrec];
     DGRP_REQUIRE(linear_cap >= W * ncls, "dgrp_track_index_batch: linear_cap %lld < %lld windows of %d classes", (long long)linear_cap,

@@ -296,3 +296,13 @@ def bgzf_compress_device(d_text, eof: bool = True, level: int = 0):
     check(L.dgrp_bgzf_compress_level(d_text.data_ptr() if n else None, n, d_out.data_ptr(), cap, C.byref(got), int(eof), int(level),
                                      work.data_ptr(), wb, stream_ptr()), "dgrp_bgzf_compress_level")
     return d_out[:got.value]
+
+
+GZIP_PIECE = 4096 * 0xff00                          # bytes deflated per call (the level-1 workspace is five times the piece)
+
+
+def bgzf_members_device(d_text, level: int, piece: int = GZIP_PIECE) -> bytes:
+    """The BGZF members of the uint8 device tensor `d_text` (no EOF member; b"" for no text), deflated on the device `piece` bytes
+    a call (bgzf_compress_device) and read back: members of BGZF_BLOCK text bytes, a short one at the end of every piece."""
+    return b"".join(bgzf_compress_device(d_text[o:o + piece], eof=False, level=level).cpu().numpy().tobytes()
+                    for o in range(0, int(d_text.numel()), piece))

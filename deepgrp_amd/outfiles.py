@@ -1,0 +1,141 @@
+"""Staged output files, the layer under `predict --track_dir` and `--bed_dir` (tracks.TrackFiles, bed.BedFiles): a file is written
+under a temporary name next to its final one and renamed when its input is done (`StagedFile`); a BGZF file takes the members of
+every write and, where a tabix index was asked for, builds `<file>.tbi` beside it (`BgzfSink`); `StagedOutputs` is what the files
+of one input share: the rule on record names, one warning when the input cannot be indexed, and a commit that leaves no temporary
+file behind when it fails."""
+from __future__ import annotations
+
+import os
+import tempfile
+from typing import Iterable, Optional, Sequence
+
+from . import tabix
+from .gz import BGZF_EOF
+
+
+class StagedFile:
+    """`final`, written as `.<basename>.<random>.tmp` in its directory (`fh`).  `finish` completes the temporary file, `commit`
+    renames the finished file into place, `abort` removes it; `commit` and `abort` are safe behind each other."""
+
+    def __init__(self, final: str, mode: str = "wb"):
+        self.final = final
+        fd, self.tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
+        self.fh = os.fdopen(fd, mode)
+
+    def append(self, data: bytes, *_index) -> None:
+        self.fh.write(data)
+
+    def finish(self) -> None:
+        self.fh.close()
+
+    def commit(self) -> None:
+        if self.tmp is not None:
+            os.replace(self.tmp, self.final)
+        self.tmp = None
+
+    def abort(self) -> None:
+        self.fh.close()
+        if self.tmp is not None and os.path.exists(self.tmp):
+            os.remove(self.tmp)
+        self.tmp = None
+
+
+class BgzfSink:
+    """One BGZF file from the members of its writes.  With `index`, `builder` (a tabix.IndexBuilder, until someone sets it to None)
+    takes every write at the file offset it goes to.  `finish` puts the EOF member behind the members and stages the `.tbi`;
+    `commit` renames the file, then its `.tbi` -- or, the index dropped, removes a `.tbi` an earlier run left.  Without `index` a
+    `.tbi` beside the file is not this run's to touch."""
+
+    def __init__(self, final: str, index: bool = False):
+        self.index_wanted, self.builder = index, tabix.IndexBuilder() if index else None
+        self.off = 0                                    # bytes of members written
+        self.tbi: Optional[StagedFile] = None
+        self.data = StagedFile(final)
+
+    def append(self, members: bytes, names: Sequence[bytes], chunks, linear, wpref, last_end=None) -> None:
+        """The members of one write and, while the index lives, its part of it (tabix.IndexBuilder.add; an IndexRefused leaves them written)."""
+        self.data.fh.write(members)
+        off, self.off = self.off, self.off + len(members)
+        if self.builder is not None and members:
+            sizes, text_len = tabix.member_sizes(members)
+            self.builder.add(off, sizes, text_len, names, chunks, linear, wpref, last_end)
+
+    def finish(self) -> None:
+        self.data.fh.write(BGZF_EOF)
+        self.data.finish()
+        if self.builder is not None:
+            self.tbi = StagedFile(self.data.final + ".tbi")
+            self.tbi.fh.write(tabix.index_file(self.builder.payload()))
+            self.tbi.finish()
+
+    def commit(self) -> None:
+        self.data.commit()
+        if self.tbi is not None:
+            self.tbi.commit()
+        elif self.index_wanted and os.path.exists(self.data.final + ".tbi"):
+            os.remove(self.data.final + ".tbi")
+
+    def abort(self) -> None:
+        self.data.abort()
+        if self.tbi is not None:
+            self.tbi.abort()
+
+
+class StagedOutputs:
+    """The files of one input (`parts`: one StagedFile or BgzfSink per file) behind one `commit` and one `abort`.  `indexed` says
+    whether a tabix index is still being built; `no_index` drops it for every part, with one warning to `log` that names the input
+    and the flag."""
+
+    def __init__(self, log, filename: str, flag: str, indexed: bool, parts: Iterable):
+        self.log, self.filename, self.flag, self.indexed = log, filename, flag, indexed
+        self.seen, self.last = set(), None
+        self.parts = []
+        try:
+            for p in parts:                             # (made one by one: the ones made go when a later one cannot be)
+                self.parts.append(p)
+        except BaseException:
+            self.abort()
+            raise
+
+    def name_order(self, names: Sequence[bytes]) -> Optional[str]:
+        """The rule a tabix index has for the record names of an input, over all its writes: none empty, and none that comes back
+        behind another name (the same name twice in a row is one sequence).  Registers `names`: why there is no index, or None."""
+        for nm in names:
+            if not nm:
+                return "a record with an empty name"
+            if nm != self.last:
+                if nm in self.seen:
+                    return f"the record name {nm.decode('utf-8', 'replace')!r} reappears after another name"
+                self.seen.add(nm)
+                self.last = nm
+        return None
+
+    def no_index(self, why: Optional[str]) -> None:
+        if why is not None and self.indexed:
+            self.log.warning("%s: no tabix index is written (%s): %s", self.filename, self.flag, why)
+            for p in self.parts:
+                p.builder = None
+            self.indexed = False
+
+    def append(self, k: int, data: bytes, names: Sequence[bytes] = (), chunks=None, linear=None, wpref=None, last_end=None) -> None:
+        """One write's bytes for file k, with its part of the index while there is one (an IndexRefused ends it)."""
+        try:
+            self.parts[k].append(data, names, chunks, linear, wpref, last_end)
+        except tabix.IndexRefused as e:
+            self.no_index(str(e))
+
+    def commit(self) -> None:
+        """Every part finished, then every part renamed into place.  When a `finish` raises, all parts are aborted first: no
+        temporary file remains, no file of this run appears, and what an earlier run left is untouched."""
+        try:
+            for p in self.parts:
+                p.finish()
+        except BaseException:
+            self.abort()
+            raise
+        for p in self.parts:
+            p.commit()
+
+    def abort(self) -> None:
+        for p in self.parts:
+            p.abort()

@@ -308,6 +308,16 @@ def _segment_rows(dev, cap: int, launch) -> np.ndarray:
     return rec[: total * SEGMENT_DTYPE.itemsize].cpu().numpy().view(SEGMENT_DTYPE).copy()
 
 
+def _with_room(launch, *caps):
+    """What launch(*caps) allocates for an entry that learns how much it writes only by running: launch allocates for the capacities,
+    calls the entry and returns (the allocation, what the entry needs of every capacity).  Where a guess was short (rare) it runs
+    once more, with room for all the entry reported.  -> the last allocation"""
+    out, need = launch(*caps)
+    if any(n > c for n, c in zip(need, caps)):
+        out, need = launch(*(max(c, n) for c, n in zip(caps, need)))
+    return out
+
+
 class ContigPipeline:
     """Runs records through the device pipeline with the reference's CLI parameters."""
 
@@ -539,15 +549,14 @@ class ContigPipeline:
         nlen = np.diff(noff)
         cap = ncls * int(min(int((nb * (nlen + 50)).sum()), (1 << 20) + int((nb * (nlen + 12)).sum())))
         off = np.zeros(ncls + 1, np.int64)
-        while True:
+
+        def launch(cap):
             text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
             check(L.dgrp_track_text_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob, noff.ctypes.data,
                                           cl.ctypes.data, ncls, int(digits), int(bin), _ptr(text), cap, off.ctypes.data, _ptr(work), wb,
                                           stream_ptr()), "dgrp_track_text_batch")
-            if int(off[ncls]) <= cap:
-                break
-            cap = int(off[ncls])                            # more text than guessed: run again with room for all of it
-        return text[:int(off[ncls])], off
+            return text, (int(off[ncls]),)
+        return _with_room(launch, cap)[:int(off[ncls])], off
 
     def track_index_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, names, classes, digits: int = 2,
                                  bin: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
@@ -556,16 +565,12 @@ class ContigPipeline:
         [records + 1]).  chunks (tabix.CHUNK_DTYPE) is class-major, class classes[k] at [chunk_off[k], chunk_off[k + 1]), offsets
         inside that class's slice of the text; record r of class k has its windows at linear[k, wpref[r]:wpref[r + 1]], -1 where
         none of its lines ends behind the window.  A record that ends above 2^29 raises tabix.IndexRefused."""
-        from .tabix import CHUNK_DTYPE, MAX_END, MIN_SHIFT, IndexRefused
+        from .tabix import CHUNK_DTYPE, window_prefix
         L = lib()
         r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_index_batch_device", row0, lengths, startposes, classes)
         c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
-        over = np.flatnonzero(sp + ln > MAX_END)
-        if over.size:
-            raise IndexRefused(f"record {int(over[0])} ends at {int((sp + ln)[over[0]])}, above 2^29, the largest coordinate of a tabix index")
+        wpref = window_prefix(sp + ln)
         blob, noff = name_blob(names)[1:]
-        wpref = np.zeros(nrec + 1, np.int64)
-        np.cumsum(((sp + ln - 1) >> MIN_SHIFT) + 1, out=wpref[1:])
         nwin = int(wpref[-1])
         wb = L.dgrp_track_index_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
         if wb <= 0:
@@ -575,15 +580,14 @@ class ContigPipeline:
         cap = ncls * (2 * nwin + 4 * nrec + 16)             # (a leaf chunk per window, one per line across a window edge, a few per
                                                             # record: 1.2 per window on a 250 Mbp record; the guess fits most runs)
         off = np.zeros(ncls + 1, np.int64)
-        while True:
+
+        def launch(cap):
             chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             check(L.dgrp_track_index_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob, noff.ctypes.data,
                                            cl.ctypes.data, ncls, int(digits), int(bin), _ptr(chunks), cap, off.ctypes.data, _ptr(linear),
                                            ncls * nwin, _ptr(work), wb, stream_ptr()), "dgrp_track_index_batch")
-            if int(off[ncls]) <= cap:
-                break
-            cap = int(off[ncls])                            # more chunks than guessed: run again with room for all of them
-        host = chunks[:int(off[ncls]) * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
+            return chunks, (int(off[ncls]),)
+        host = _with_room(launch, cap)[:int(off[ncls]) * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, off, linear[:ncls * nwin].cpu().numpy().reshape(ncls, nwin), wpref
 
     @staticmethod
@@ -612,15 +616,15 @@ class ContigPipeline:
         cap = ncls * min(12 * nb + 24 * (nb // 1024 + nrec), (1 << 20) + 3 * nb)        # (the guess fits most runs)
         tcap = ncls * (cap // (ncls * 12 * 1024) + nrec + 1)
         off, soff = np.zeros(ncls + 1, np.int64), np.zeros(ncls + 1, np.int64)
-        while True:
+
+        def launch(cap, tcap):
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
             table = torch.empty(max(tcap, 1) * SECTION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             check(L.dgrp_track_sections_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, cl.ctypes.data, ncls,
                                               int(digits), int(bin), int(chrom0), _ptr(out), cap, off.ctypes.data, _ptr(table), tcap, soff.ctypes.data,
                                               _ptr(work), wb, stream_ptr()), "dgrp_track_sections_batch")
-            if int(off[ncls]) <= cap and int(soff[ncls]) <= tcap:
-                break
-            cap, tcap = max(cap, int(off[ncls])), max(tcap, int(soff[ncls]))       # more than guessed: run again with room for all
+            return (out, table), (int(off[ncls]), int(soff[ncls]))
+        out, table = _with_room(launch, cap, tcap)
         return out[:int(off[ncls])], off, table[:int(soff[ncls]) * SECTION_DTYPE.itemsize], soff
 
     def track_zoom_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, classes, digits: int = 2, bin: int = 1,
@@ -642,15 +646,15 @@ class ContigPipeline:
         tcap = cap // (32 * 1024) + nseg
         roff, boff = np.zeros(nseg + 1, np.int64), np.zeros(nseg + 1, np.int64)
         totals = np.zeros(ncls, TOTALS_DTYPE)
-        while True:
+
+        def launch(cap, tcap):
             out = torch.empty(max(cap, 32), dtype=torch.uint8, device=dev)
             table = torch.empty(max(tcap, 1) * ZOOM_BLOCK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             check(L.dgrp_track_zoom_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, cl.ctypes.data, ncls,
                                           int(digits), int(bin), int(chrom0), _ptr(out), cap, roff.ctypes.data, _ptr(table), tcap, boff.ctypes.data,
                                           totals.ctypes.data, _ptr(work), wb, stream_ptr()), "dgrp_track_zoom_batch")
-            if 32 * int(roff[nseg]) <= cap and int(boff[nseg]) <= tcap:
-                break
-            cap, tcap = max(cap, 32 * int(roff[nseg])), max(tcap, int(boff[nseg]))
+            return (out, table), (32 * int(roff[nseg]), int(boff[nseg]))
+        out, table = _with_room(launch, cap, tcap)
         return out[:32 * int(roff[nseg])], roff, table[:int(boff[nseg]) * ZOOM_BLOCK_DTYPE.itemsize], boff, totals
 
     @staticmethod
@@ -678,7 +682,7 @@ class ContigPipeline:
         """The track texts of a batch from its merged probabilities (run_batch_probs: record r at rows [row0[r], row0[r] + ln[r])),
         one dgrp_track_text_batch call: texts[k] = the bytes of class spec.classes[k] for the whole batch (what the records' texts
         give one after the other); with spec.gzip_level the BGZF members of that slice instead (no EOF member), deflated on the
-        device in tracks.GZIP_PIECE pieces: members span records and a batch ends in a short member; with spec.index the batch's
+        device in gz.GZIP_PIECE pieces: members span records and a batch ends in a short member; with spec.index the batch's
         tracks.WriteIndex comes with them (texts.index); with spec.bigwig tracks.bigwig_write's result instead (chrom0: the
         ordinal of the batch's first record in its input)."""
         if spec.bigwig:                                      # --track_bigwig: sections and zoom blocks instead of text
@@ -693,14 +697,10 @@ class ContigPipeline:
         if spec.gzip_level is None:
             host = d_text.cpu().numpy()
             return [host[off[k]:off[k + 1]].tobytes() for k in range(len(spec.classes))]
-        from . import gz
-        from .tracks import GZIP_PIECE, TrackTexts
-        texts = TrackTexts()
+        from .gz import bgzf_members_device
+        from .tracks import TrackTexts
+        texts = TrackTexts(bgzf_members_device(d_text[int(off[k]):int(off[k + 1])], spec.gzip_level) for k in range(len(spec.classes)))
         texts.index = index
-        for k in range(len(spec.classes)):
-            pieces = [gz.bgzf_compress_device(d_text[o:min(o + GZIP_PIECE, int(off[k + 1]))], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
-                      for o in range(int(off[k]), int(off[k + 1]), GZIP_PIECE)]
-            texts.append(b"".join(pieces))
         return texts
 
     # predict --bed_dir
@@ -755,14 +755,13 @@ class ContigPipeline:
         longest = max(len(x) for x in raw)
         cap = min(int(L.dgrp_format_bed_bound(nrows, longest)), nrows * (longest + 72))       # (the guess fits most runs)
         got = C.c_int64(0)
-        while True:
+
+        def launch(cap):
             text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
             check(L.dgrp_bed_text_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows, int(min_score),
                                         _ptr(text), cap, C.byref(got), _ptr(work), wb, stream_ptr()), "dgrp_bed_text_batch")
-            if got.value <= cap:
-                break
-            cap = int(got.value)                            # longer lines than guessed: run again with room for all of them
-        return text[:got.value]
+            return text, (int(got.value),)
+        return _with_room(launch, cap)[:got.value]
 
     @staticmethod
     def bed_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end):
@@ -770,17 +769,13 @@ class ContigPipeline:
         read back once): -> (chunks tabix.CHUNK_DTYPE, linear int64 [windows], wpref int64 [records + 1], last_end int64 [records]);
         record r (a row's contig with by_contig, else 0) ends at rec_end[r] and has its windows at linear[wpref[r]:wpref[r + 1]].
         What bed.reference_index_parts states.  A record that ends above 2^29 raises tabix.IndexRefused."""
-        from .tabix import CHUNK_DTYPE, MAX_END, MIN_SHIFT, IndexRefused
+        from .tabix import CHUNK_DTYPE, window_prefix
         L = lib()
         nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
         ends = np.ascontiguousarray(rec_end, np.int64)
         nrec = len(ends)
-        over = np.flatnonzero(ends > MAX_END)
-        if over.size:
-            raise IndexRefused(f"record {int(over[0])} ends at {int(ends[over[0]])}, above 2^29, the largest coordinate of a tabix index")
+        wpref = window_prefix(ends)
         raw, blob, off = name_blob(names)
-        wpref = np.zeros(nrec + 1, np.int64)
-        np.cumsum(((ends - 1) >> MIN_SHIFT) + 1, out=wpref[1:])
         nwin = int(wpref[-1])
         wb = int(L.dgrp_bed_index_workspace_bytes(nrows, len(raw), len(blob), nrec))
         if wb <= 0:
@@ -790,36 +785,28 @@ class ContigPipeline:
         last = torch.zeros(max(nrec, 1), dtype=torch.int64, device=dev)
         cap = min(nrows, 2 * nwin + 4 * nrec + 16)          # (a chunk per line at most; on long records about one per window)
         got = C.c_int64(0)
-        while True:
+
+        def launch(cap):
             chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
             check(L.dgrp_bed_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows,
                                          int(min_score), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got), _ptr(linear), nwin,
                                          _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_bed_index_batch")
-            if got.value <= cap:
-                break
-            cap = int(got.value)                            # more chunks than guessed: run again with room for all of them
-        host = chunks[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
+            return chunks, (int(got.value),)
+        host = _with_room(launch, cap)[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
 
     def bed_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan):
         """One write of a BGZF BED (bed.BedWrite) for the arguments of row_scores_batch, `names` as bed.format_rows takes them and
         `plan` the bed.BedPlan: scores, text and, with plan.index, the index's pieces are made on the device from the uploaded rows;
-        the text is deflated there in tracks.GZIP_PIECE pieces (members span records, a write ends in a short member) and only the
+        the text is deflated there in gz.GZIP_PIECE pieces (members span records, a write ends in a short member) and only the
         members come back.  row_off must cover all rows (row_off[0] = 0, row_off[-1] = len(rows))."""
-        from . import gz
         from .bed import BedWrite
-        from .tabix import MAX_END
-        from .tracks import GZIP_PIECE
+        from .gz import bgzf_members_device
+        from .tabix import end_refusal
         raw = name_blob(names)[0]
         r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "bed_write", row0, lengths, startposes)
         ends = sp + ln
-        refused = None
-        if plan.index:
-            for nm, end in zip(raw, ends.tolist()):
-                if end > MAX_END:
-                    refused = (f"record {nm.decode('utf-8', 'replace')!r} ends at {end}, above 2^29 = {MAX_END}, the largest coordinate "
-                               "of a tabix index")
-                    break
+        refused = end_refusal(ends, raw) if plan.index else None
         rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
         ro = np.ascontiguousarray(row_off, np.int64)
         if len(rows) == 0:
@@ -832,9 +819,7 @@ class ContigPipeline:
         if plan.index and refused is None and int(d_text.numel()):
             parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends)
         del d_probs, d_rows, d_scores
-        pieces = [gz.bgzf_compress_device(d_text[o:o + GZIP_PIECE], eof=False, level=plan.gzip_level).cpu().numpy().tobytes()
-                  for o in range(0, int(d_text.numel()), GZIP_PIECE)]
-        return BedWrite(b"".join(pieces), raw, refused, *parts)
+        return BedWrite(bgzf_members_device(d_text, plan.gzip_level), raw, refused, *parts)
 
     @staticmethod
     def batch_row_offsets(rows: np.ndarray, contigs) -> np.ndarray:

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import struct
 import zlib
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -47,6 +47,24 @@ def reg2bin(beg: int, end: int) -> int:
         if beg >> shift == end >> shift:
             return first + (beg >> shift)
     return 0
+
+
+def end_refusal(ends, names: Optional[Sequence[bytes]] = None) -> Optional[str]:
+    """Why records that end at `ends` cannot have an index (the first that ends above 2^29, by its name or, without names, by its
+    ordinal), or None."""
+    for i, end in enumerate(np.asarray(ends, np.int64).tolist()):
+        if end > MAX_END:
+            who, limit = (i, "2^29") if names is None else (repr(names[i].decode("utf-8", "replace")), f"2^29 = {MAX_END}")
+            return f"record {who} ends at {end}, above {limit}, the largest coordinate of a tabix index"
+    return None
+
+
+def window_prefix(ends) -> np.ndarray:
+    """wpref [records + 1] of records that end at `ends`: record r has the ((end - 1) >> MIN_SHIFT) + 1 windows of 16 kb up to its
+    end, at [wpref[r], wpref[r + 1]) of a linear index.  A record that ends above 2^29 raises IndexRefused (end_refusal's text)."""
+    if end_refusal(ends) is not None:
+        raise IndexRefused(end_refusal(ends))
+    return np.r_[np.int64(0), np.cumsum(((np.asarray(ends, np.int64) - 1) >> MIN_SHIFT) + 1, dtype=np.int64)]
 
 
 def reg2bins(beg: int, end: int) -> List[int]:

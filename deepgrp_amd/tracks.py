@@ -26,12 +26,12 @@ from __future__ import annotations
 import logging
 import os
 import sys
-import tempfile
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ._lib import name_blob
+from .outfiles import BgzfSink, StagedFile, StagedOutputs
 
 _LOG = logging.getLogger(__name__)
 
@@ -65,9 +65,6 @@ def track_path(directory: str, base: str, cls: int, gzip: bool = False, bigwig: 
     if bigwig:
         return os.path.join(directory, f"{base}.class{cls}.bw")
     return os.path.join(directory, f"{base}.class{cls}.bedGraph" + (".gz" if gzip else ""))
-
-
-GZIP_PIECE = 4096 * 0xff00                          # bytes deflated per call (the level-1 workspace is five times the piece)
 
 
 def gzip_level(args, default: int) -> Optional[int]:
@@ -167,7 +164,7 @@ class TrackTexts(list):
     bigwig: Optional[BigWigWrite] = None
 
 
-ZLIB_PIECE = 4096                                   # blocks deflated per call (GZIP_PIECE's reason: the level-1 workspace)
+ZLIB_PIECE = 4096                                   # blocks deflated per call (gz.GZIP_PIECE's reason: the level-1 workspace)
 
 
 def _zlib_pieces(pipe, d_in, d_table, stride: int, level: int):
@@ -224,12 +221,11 @@ def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpe
 
 def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec) -> WriteIndex:
     """The WriteIndex of the records whose text track_text_batch_device gives for the same arguments."""
-    from .tabix import MAX_END
+    from .tabix import end_refusal
     raw = name_blob(names)[0]
-    for nm, sp, n in zip(raw, startposes, lengths):
-        if int(sp) + int(n) > MAX_END:
-            return WriteIndex(raw, f"record {nm.decode('utf-8', 'replace')!r} ends at {int(sp) + int(n)}, above 2^29 = {MAX_END}, the "
-                                   "largest coordinate of a tabix index")
+    refused = end_refusal([int(sp) + int(n) for sp, n in zip(startposes, lengths)], raw)
+    if refused is not None:
+        return WriteIndex(raw, refused)
     return WriteIndex(raw, None, *pipe.track_index_batch_device(d_probs, row0, lengths, startposes, raw, spec.classes, spec.digits, spec.bin))
 
 
@@ -241,87 +237,53 @@ def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec, chrom: int 
         return bigwig_write(pipe, merged, [0], [len(merged)], [startpos], [name], spec, chrom)
     if spec.gzip_level is None:
         return [pipe.track_text(merged, startpos, name, c, spec.digits, spec.bin) for c in spec.classes]
-    from . import gz
-    out = TrackTexts()
-    for c in spec.classes:
-        d_text = pipe.track_text_device(merged, startpos, name, c, spec.digits, spec.bin)
-        pieces = [gz.bgzf_compress_device(d_text[o:o + GZIP_PIECE], eof=False, level=spec.gzip_level).cpu().numpy().tobytes()
-                  for o in range(0, int(d_text.numel()), GZIP_PIECE)]
-        out.append(b"".join(pieces))
-        del d_text
+    from .gz import bgzf_members_device
+    out = TrackTexts(bgzf_members_device(pipe.track_text_device(merged, startpos, name, c, spec.digits, spec.bin), spec.gzip_level)
+                     for c in spec.classes)
     if spec.index and len(merged):
         out.index = write_index(pipe, merged, [0], [len(merged)], [startpos], [name], spec)
     return out
 
 
-class TrackFiles:
-    """The track files of one input, written to temporary files in the directory and renamed by `commit` (`abort` removes them).
-    With spec.gzip_level `write` takes BGZF members and `commit` puts the EOF member behind them.  With spec.index it keeps, per
-    class, the file offset of every write and a tabix.IndexBuilder, and `commit` writes `<track>.gz.tbi` the same way.  An input
-    whose records cannot be indexed (WriteIndex.refused, a name that reappears after another name, an empty name) gets one warning
-    and no index; its tracks are what they are without the flag.  With spec.bigwig the files are `.bw`, every class has a
-    bigwig.BigWigBuilder on its temporary file, `write` takes TrackTexts with a BigWigWrite, and an input a bigWig cannot hold (an
-    empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and no `.bw` files: `commit` then
-    removes the temporary files and any `.bw` an earlier run left."""
+class _BigWigFile(StagedFile):
+    """One `.bw` file: a bigwig.BigWigBuilder (`bw`) on the staged file."""
+
+    def __init__(self, final: str, digits: int, bin: int):
+        from .bigwig import BigWigBuilder
+        super().__init__(final, "w+b")
+        try:
+            self.bw = BigWigBuilder(self.fh, digits, bin, os.path.dirname(final))
+        except BaseException:
+            super().abort()
+            raise
+
+    def finish(self) -> None:
+        self.bw.finish()
+        self.fh.close()
+
+    def abort(self) -> None:
+        self.bw.close()
+        super().abort()
+
+
+class TrackFiles(StagedOutputs):
+    """The track files of one input: temporary files in the directory, renamed by `commit`, removed by `abort` (outfiles.py).  With
+    spec.gzip_level `write` takes BGZF members, to an outfiles.BgzfSink per class, which with spec.index builds `<track>.gz.tbi`.
+    An input whose records cannot be indexed (WriteIndex.refused, an empty name, a name that comes back: one name_order for all
+    classes) gets one warning and no index; its tracks are what they are without the flag.  With spec.bigwig the files are `.bw`,
+    every class has a bigwig.BigWigBuilder on its temporary file, `write` takes TrackTexts with a BigWigWrite, and an input a
+    bigWig cannot hold (an empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and no `.bw`
+    files: `commit` then removes the temporary files and any `.bw` an earlier run left."""
 
     def __init__(self, p: TrackPlan, spec: TrackSpec, filename: str):
         os.makedirs(p.directory, exist_ok=True)
         self.bigwig = bool(spec.bigwig)
         self.gzip = spec.gzip_level is not None and not self.bigwig
         self.final = [track_path(p.directory, p.bases[filename], c, self.gzip, self.bigwig) for c in spec.classes]
-        self.bw, self.bw_refused, self.bw_names = None, None, set()
-        self.tmp, self.fh = [], []
-        self.filename, self.builders = filename, None
-        if self.gzip and spec.index:
-            from .tabix import IndexBuilder
-            self.builders = [IndexBuilder() for _ in spec.classes]
-            self.offs = [0] * len(spec.classes)
-            self.seen, self.last = set(), None
-        self.index_wanted = self.builders is not None
-        try:
-            for path in self.final:
-                fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=p.directory)
-                self.tmp.append(tmp)
-                self.fh.append(os.fdopen(fd, "w+b" if self.bigwig else "wb"))
-            if self.bigwig:
-                from .bigwig import BigWigBuilder
-                self.bw = [BigWigBuilder(fh, spec.digits, spec.bin, p.directory) for fh in self.fh]
-        except BaseException:
-            self.abort()
-            raise
-
-    def _no_index(self, why: str) -> None:
-        if self.builders is not None:
-            _LOG.warning("%s: no tabix index is written (--track_index): %s", self.filename, why)
-            self.builders = None
-
-    def _index(self, texts: Sequence[bytes]) -> None:
-        """The write's part of every class's index; the members of class k go to file offset self.offs[k]."""
-        from .tabix import IndexRefused, member_sizes
-        ix = getattr(texts, "index", None)
-        if ix is None:
-            if any(texts):
-                self._no_index("a write came without its index")
-            return
-        for nm in ix.names:
-            if not nm:
-                return self._no_index("a record with an empty name")
-            if nm != self.last:
-                if nm in self.seen:
-                    return self._no_index(f"the record name {nm.decode('utf-8', 'replace')!r} reappears after another name")
-                self.seen.add(nm)
-                self.last = nm
-        if ix.refused is not None:
-            return self._no_index(ix.refused)
-        for k, t in enumerate(texts):
-            if t:
-                sizes, text_len = member_sizes(t)
-                try:
-                    self.builders[k].add(self.offs[k], sizes, text_len, ix.names, ix.chunks[ix.chunk_off[k]:ix.chunk_off[k + 1]],
-                                         ix.linear[k], ix.wpref)
-                except IndexRefused as e:
-                    return self._no_index(str(e))
-                self.offs[k] += len(t)
+        self.bw_refused, self.bw_names = None, set()
+        super().__init__(_LOG, filename, "--track_index", self.gzip and spec.index,
+                         (_BigWigFile(path, spec.digits, spec.bin) if self.bigwig else BgzfSink(path, spec.index) if self.gzip
+                          else StagedFile(path) for path in self.final))
 
     def _bigwig(self, texts: Sequence[bytes]) -> None:
         """The write's part of every class's bigWig, or the input's refusal (one warning)."""
@@ -342,73 +304,35 @@ class TrackFiles:
             self.bw_refused = why
             _LOG.warning("%s: no bigWig files are written (--track_bigwig): %s", self.filename, why)
             return
-        if w.chrom0 is not None and w.chrom0 != len(self.bw[0].names):
-            raise ValueError(f"{self.filename}: a bigWig write of chromId {w.chrom0} arrived as record {len(self.bw[0].names)} of the input")
-        for k, b in enumerate(self.bw):
-            b.add(w.names, w.sizes, None if w.classes is None else w.classes[k])
-
-    def write(self, texts: Sequence[bytes]) -> None:
-        if self.bigwig:
-            return self._bigwig(texts)
-        for fh, t in zip(self.fh, texts):
-            if t:
-                fh.write(t)
-        if self.builders is not None:
-            self._index(texts)
-
-    def _commit_bigwig(self) -> None:
-        if self.bw_refused is not None:
-            self.abort()
-            for path in self.final:
-                if os.path.exists(path):
-                    os.remove(path)
-            return
-        for b, fh in zip(self.bw, self.fh):
-            b.finish()
-            fh.close()
-        for tmp, path in zip(self.tmp, self.final):
-            os.replace(tmp, path)
-        self.tmp = []
+        have = len(self.parts[0].bw.names)
+        if w.chrom0 is not None and w.chrom0 != have:
+            raise ValueError(f"{self.filename}: a bigWig write of chromId {w.chrom0} arrived as record {have} of the input")
+        for k, p in enumerate(self.parts):
+            p.bw.add(w.names, w.sizes, None if w.classes is None else w.classes[k])
 
     def commit(self) -> None:
+        if self.bw_refused is None:
+            return super().commit()
+        self.abort()
+        for path in self.final:
+            if os.path.exists(path):
+                os.remove(path)
+
+    def write(self, texts: Sequence[bytes]) -> None:
+        """The write's text (or members) of every class; with an index, the names of its WriteIndex count in the order, and a
+        write with text but no index ends the index."""
         if self.bigwig:
-            return self._commit_bigwig()
-        for fh in self.fh:
-            if self.gzip:
-                from .gz import BGZF_EOF
-                fh.write(BGZF_EOF)
-            fh.close()
-        if self.index_wanted:
-            self._commit_index()
-        for tmp, path in zip(self.tmp, self.final):
-            os.replace(tmp, path)
-        self.tmp = []
-
-    def _commit_index(self) -> None:
-        """`<track>.gz.tbi` of every class through a temporary file; without an index, one left by an earlier run goes."""
-        from .tabix import index_file
-        tbi = [path + ".tbi" for path in self.final]
-        if self.builders is None:
-            for path in tbi:
-                if os.path.exists(path):
-                    os.remove(path)
-            return
-        for b, path in zip(self.builders, tbi):
-            fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(path))
-            self.tmp.append(tmp)
-            self.final.append(path)
-            with os.fdopen(fd, "wb") as fh:
-                fh.write(index_file(b.payload()))
-
-    def abort(self) -> None:
-        for b in self.bw or ():
-            b.close()
-        for fh in self.fh:
-            fh.close()
-        for tmp in self.tmp:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        self.tmp = []
+            return self._bigwig(texts)
+        ix = getattr(texts, "index", None)
+        if self.indexed and ix is None:
+            self.no_index("a write came without its index" if any(texts) else None)
+        elif self.indexed:
+            self.no_index(self.name_order(ix.names) or ix.refused)
+        for k, t in enumerate(texts):
+            if t and self.indexed:
+                self.append(k, t, ix.names, ix.chunks[ix.chunk_off[k]:ix.chunk_off[k + 1]], ix.linear[k], ix.wpref)
+            else:
+                self.append(k, t)
 
 
 def quantise(v: np.ndarray, digits: int) -> np.ndarray:

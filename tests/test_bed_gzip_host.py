@@ -260,3 +260,28 @@ def test_abort_and_plain_gzip(tmp_path):
     files.commit()
     assert os.listdir(q.directory) == ["in.fa.bed.gz"]
     assert open(q.paths["in.fa"], "rb").read() == w.members + gz.BGZF_EOF and _inflate(w.members) == text
+
+
+def test_a_commit_that_fails_leaves_the_earlier_run(tmp_path, monkeypatch):
+    """The `.tbi` cannot be written: commit raises, no temporary file remains, no file of this run appears and the earlier run's
+    files are what they were; abort has nothing left to do."""
+    p = _plan(tmp_path)
+    os.makedirs(p.directory)
+    before = {"in.fa.bed.gz": b"the earlier run's BED", "in.fa.bed.gz.tbi": b"the earlier run's index"}
+    for name, data in before.items():
+        open(os.path.join(p.directory, name), "wb").write(data)
+    listing = lambda: {name: open(os.path.join(p.directory, name), "rb").read() for name in sorted(os.listdir(p.directory))}
+    files = bed.BedFiles(p, "in.fa")
+    rows, sc = _rows([(5, 90), (100, 200), (300, 400)], [0, 1, 1]), _scores(3)
+    for w, _t in (_fake_write([b"a", b"b"], True, rows, sc, 0, [1000, 1000]), _fake_write([b"c"], False, rows[:2], sc[:2], 0, [1000])):
+        files.write(w.names, len(w.names) > 1, None, w)
+    assert len(os.listdir(p.directory)) == 3                                          # the temporary file
+
+    def full_disk(_payload):
+        raise OSError(28, "No space left on device")
+    monkeypatch.setattr(tabix, "index_file", full_disk)
+    with pytest.raises(OSError, match="No space left"):
+        files.commit()
+    assert listing() == before
+    files.abort()
+    assert listing() == before

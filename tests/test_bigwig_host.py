@@ -362,3 +362,32 @@ def test_track_files_abort_removes_everything(tmp_path):
     files.write(_fake(tracks, bw, [b"a"], [500]))
     files.abort()
     assert os.listdir(tmp_path) == []
+
+
+def test_track_files_commit_that_fails_leaves_the_earlier_run(tmp_path, monkeypatch):
+    """The second class's bigWig cannot be finished: commit raises, no temporary file and no spool remains, no file of this run
+    appears and the earlier run's files are what they were; abort has nothing left to do."""
+    from deepgrp_amd import bigwig as bw
+    from deepgrp_amd import tracks
+    plan = tracks.TrackPlan(str(tmp_path), (1, 2), 2, 1, {"in.fa": "in.fa"}, 1, False, True)
+    before = {f"in.fa.class{c}.bw": b"left by an earlier run: %d" % c for c in (1, 2)}
+    for name, data in before.items():
+        (tmp_path / name).write_bytes(data)
+    listing = lambda: {name: (tmp_path / name).read_bytes() for name in sorted(os.listdir(tmp_path))}
+    files = tracks.TrackFiles(plan, tracks.resolve(plan, 5), "in.fa")
+    files.write(_fake(tracks, bw, [b"a", b"b"], [500, 40]))
+    files.write(_fake(tracks, bw, [b"c"], [700], chrom=2))
+    assert len(os.listdir(tmp_path)) == 4                                  # the two temporary files (the spools have no name)
+    real, calls = bw.BigWigBuilder.finish, []
+
+    def full_disk(self):
+        calls.append(self)
+        if len(calls) == 2:
+            raise OSError(28, "No space left on device")
+        return real(self)
+    monkeypatch.setattr(bw.BigWigBuilder, "finish", full_disk)
+    with pytest.raises(OSError, match="No space left"):
+        files.commit()
+    assert len(calls) == 2 and listing() == before
+    files.abort()
+    assert listing() == before

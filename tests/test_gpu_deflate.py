@@ -129,6 +129,29 @@ def test_empty_input_on_the_device():
     assert _device(b"", False) == b""
 
 
+@pytest.mark.parametrize("level", [0, 1])
+def test_members_of_a_text_deflated_in_pieces(level):
+    """gz.bgzf_members_device: the members of every piece one after the other, no EOF member; an empty text, one byte, exactly
+    one piece, and pieces with a rest that is no multiple of a member."""
+    from deepgrp_amd import gz
+    dev = torch.device("cuda", torch.cuda.current_device())
+    piece = 2 * BLOCK
+    rng = np.random.default_rng(31 + level)
+    alphabet = np.frombuffer(b"chr1\t0.25\n", np.uint8)
+    for n in (0, 1, piece, 5 * BLOCK + 17):
+        text = alphabet[rng.integers(0, len(alphabet), n)]
+        d_text = torch.from_numpy(text).to(dev)
+        got = gz.bgzf_members_device(d_text, level, piece)
+        want = b"".join(gz.bgzf_compress_device(d_text[o:o + piece], eof=False, level=level).cpu().numpy().tobytes()
+                        for o in range(0, n, piece))
+        assert isinstance(got, bytes) and got == want, n
+        assert gzip.decompress(got) == text.tobytes(), n
+        assert (got == b"") == (n == 0)
+        assert len(gz.walk_members(got).isize) == sum(-(-min(piece, n - o) // BLOCK) for o in range(0, n, piece)), n
+    assert gz.GZIP_PIECE % BLOCK == 0                                                   # the default piece: whole members
+    assert gz.bgzf_members_device(d_text, level) == gz.bgzf_compress_device(d_text, eof=False, level=level).cpu().numpy().tobytes()
+
+
 # ---------------------------------------------------------------- mask_fasta(compress=True)
 def _body(rng, n, width, crlf, final_nl=True):
     seq = rng.choice(list(b"ACGTNacgtnRY*"), size=n).astype(np.uint8).tobytes()

@@ -187,6 +187,91 @@ def test_index_builder_joins_records_of_one_name_and_refuses_a_returning_name():
         _build([[(b"", reference_text(noisy(100, 26), 0, b""))]])
 
 
+# ------------------------------------------------------------------------------------------ TrackFiles on fake writes
+def _track_write(names, class_texts):
+    """One write as the device path hands it to TrackFiles: class_texts[k][r] is the text of record r of class k; the members are
+    the host encoder's, chunks and linear index device_like's, two windows behind every record's last line."""
+    from deepgrp_amd import gz, tabix, tracks
+    parts = [device_like(ts) for ts in class_texts]
+    wpref = np.cumsum([0] + [max(len(lin[r]) for _c, lin, _t in parts) + 2 for r in range(len(names))])
+    linear = np.full((len(parts), wpref[-1]), -1, np.int64)
+    chunks, coff = [], [0]
+    for k, (ch, lin, _text) in enumerate(parts):
+        for r, l in enumerate(lin):
+            linear[k, wpref[r]:wpref[r] + len(l)] = l
+        chunks += [tuple(c) for c in ch]
+        coff.append(len(chunks))
+    texts = tracks.TrackTexts(gz.bgzf_compress_host(text, eof=False, level=1) if text else b"" for _c, _l, text in parts)
+    texts.index = tracks.WriteIndex(list(names), None, np.array(chunks, tabix.CHUNK_DTYPE), np.array(coff, np.int64), linear, wpref)
+    return texts
+
+
+def _track_files(tmp_path, classes, index=True):
+    from deepgrp_amd import tracks
+    plan = tracks.TrackPlan(str(tmp_path), classes, 2, 1, {"in.fa": "in.fa"}, 1, index)
+    return tracks.TrackFiles(plan, tracks.resolve(plan, 5), "in.fa")
+
+
+def _listing(path):
+    return {name: (path / name).read_bytes() for name in sorted(os.listdir(path))}
+
+
+def _class_texts(names, nclasses, seed):
+    from deepgrp_amd.tracks import reference_text
+    return [[reference_text(noisy(3000 + 500 * k, seed + 10 * k + r), 100 * r, nm) for r, nm in enumerate(names)] for k in range(nclasses)]
+
+
+def test_track_files_commit_that_fails_leaves_the_earlier_run(tmp_path, monkeypatch):
+    """The `.tbi` of the second class cannot be written: commit raises, no temporary file remains (not the first class's staged
+    `.tbi` either), no file of this run appears, and the earlier run's files are what they were; abort has nothing left to do."""
+    from deepgrp_amd import tabix
+    finals = [f"in.fa.class{c}.bedGraph.gz" + ext for c in (1, 2) for ext in ("", ".tbi")]
+    for name in finals:
+        (tmp_path / name).write_bytes(b"left by an earlier run: " + name.encode())
+    before = _listing(tmp_path)
+    files = _track_files(tmp_path, (1, 2))
+    files.write(_track_write([b"a", b"b"], _class_texts([b"a", b"b"], 2, 1)))
+    files.write(_track_write([b"c"], _class_texts([b"c"], 2, 2)))
+    assert len(os.listdir(tmp_path)) == len(finals) + 2                                 # the two temporary files
+    real, calls = tabix.index_file, []
+
+    def full_disk(payload):
+        calls.append(len(payload))
+        if len(calls) == 2:
+            raise OSError(28, "No space left on device")
+        return real(payload)
+    monkeypatch.setattr(tabix, "index_file", full_disk)
+    with pytest.raises(OSError, match="No space left"):
+        files.commit()
+    assert len(calls) == 2 and sorted(before) == sorted(finals) and _listing(tmp_path) == before
+    files.abort()
+    assert _listing(tmp_path) == before
+
+
+def test_track_files_one_warning_drops_the_index_of_every_class(tmp_path, caplog):
+    """Three classes, and a name that comes back in a later write: one warning for the input, no `.tbi`, the stale `.tbi` of every
+    class removed, and the `.gz` files those of a run without --track_index."""
+    import logging
+    classes = (1, 2, 3)
+    writes = [_track_write(nms, _class_texts(nms, 3, seed)) for seed, nms in enumerate([[b"a", b"b"], [b"b", b"c"], [b"a"], [b"d"]])]
+    with_index, without = tmp_path / "with", tmp_path / "without"
+    with_index.mkdir()
+    gz_names = [f"in.fa.class{c}.bedGraph.gz" for c in classes]
+    for name in gz_names:
+        (with_index / (name + ".tbi")).write_bytes(b"left by an earlier run")
+    with caplog.at_level(logging.WARNING):
+        for directory, index in ((with_index, True), (without, False)):
+            files = _track_files(directory, classes, index)
+            for w in writes:
+                files.write(w)
+            files.commit()
+    warned = [r.getMessage() for r in caplog.records]
+    assert len(warned) == 1 and "in.fa: no tabix index is written (--track_index)" in warned[0] and "'a' reappears after another name" in warned[0]
+    assert sorted(os.listdir(with_index)) == gz_names
+    assert _listing(with_index) == _listing(without)
+    assert all(len(data) > 28 for data in _listing(without).values())                   # (more than the EOF member)
+
+
 # ------------------------------------------------------------------------------------------ the ABI
 @pytest.fixture(scope="module")
 def L():
