@@ -22,7 +22,8 @@
 //     workgroup barrier, table rows and first fragments of Y's next step -- and the softmax + max-merge of X's own logits of
 //     two steps ago (stored while X was the epilogue tile, a barrier since: nothing in this phase feeds them), cut
 //     into single operations and dropped into the gaps BETWEEN X's MFMAs (a wave issues in order; an MFMA holds the issue
-//     port for 8 of its 16 cycles).  The barrier itself sits inside X's MFMA stream, four MFMAs from its end.
+//     port for 8 of its 16 cycles).  The barrier itself sits inside X's MFMA stream, four MFMAs from its end, and the last publish
+//     stores two MFMAs in front of it: the barrier's s_waitcnt lgkmcnt(0) finds their LDS round trip already under way.
 //   * The order of that interleave is generated (tools/gen_split2_schedule.py -> gru_split2_phase.inc) and pinned with
 //     sched_barrier between gaps; the MFMAs are asm volatile, which the compiler keeps in program order.
 //

@@ -21,11 +21,13 @@ Cost model (cycles of the SIMD's issue port, MI355X_MICROARCH.md "vector-instruc
 VALU 4, LDS instruction 4.  A 16x16x32 MFMA occupies the pipe for 16 cycles and the port for 8; the epilogue's ~1500 port
 cycles do not fit the 150 x 8 free ones, so the stream is paced by the port and the aim is an even spread: BUDGET cycles of
 work per gap, taken in order from the queue in front of the barrier and the one behind it (layout 2: only RD0 and FN's last,
-branching link are behind it).  Nothing that reads the previous
+branching link are behind it).  The queue in front of the barrier ends --bar-tail gaps ahead of it: the barrier's s_waitcnt
+lgkmcnt(0) waits for the publish stores, and with stores in the barrier's own gap their whole LDS round trip is exposed; the tail
+gaps carry the last links of FN's chain (registers only), so the round trip lies under MFMAs.  Nothing that reads the previous
 phase's accumulators or Dense result goes into the first FREE_HEAD gaps (MFMA result -> VALU read needs wait states the
 compiler does not pad behind inline asm).
 
-    python tools/gen_split2_schedule.py [--skew 3] [--bar 104] [--budget 12] [--report]
+    python tools/gen_split2_schedule.py [--skew 4] [--bar 140] [--bar-tail 2] [--budget 12] [--report]
 """
 import argparse
 import os
@@ -58,7 +60,7 @@ def gate_pipeline(skew, early_ci=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--skew", type=int, default=3)
+    ap.add_argument("--skew", type=int, default=4)
     ap.add_argument("--late-ci", action="store_true", help="layout 2 with CI behind the barrier (bisecting)")
     ap.add_argument("--late-fn", action="store_true", help="layout 2 with FN behind the barrier (bisecting)")
     ap.add_argument("--early-emit", action="store_true",
@@ -71,6 +73,12 @@ def main():
                     help="1: softmax/merge (FN) and the accumulators' restart (CI) behind the barrier; 2: FN spread over the whole "
                          "phase (it finishes the MFMA tile's logits of two steps ago: nothing in this phase feeds it) and CI as soon "
                          "as a sub-tile's chains have read their accumulators, so that only RD0 waits for the barrier")
+    ap.add_argument("--bar-tail", type=int, default=2,
+                    help="cover for the publish stores in front of the barrier: the gate and publish queue ends this many gaps in front of "
+                         "the barrier's, those gaps carry one link each of the end of FN's chain (register-only links that feed no publish and "
+                         "start no LDS operation: the barrier's s_waitcnt lgkmcnt(0) would expose an LDS read there just as it exposes the "
+                         "stores), and the barrier's own gap carries nothing but BAR.  0: the queue runs up to the barrier and what is left "
+                         "of it is paid out in the barrier's gap")
     ap.add_argument("--budget", type=float, default=0, help="port cycles per gap in front of the barrier (0 = the queue's average)")
     ap.add_argument("--post-budget", type=float, default=0)
     ap.add_argument("--free-head", type=int, default=4)
@@ -110,6 +118,13 @@ def main():
     if early_fn and not a.early_emit:
         post += fn[-1:]
         fn = fn[:-1]
+    tail = []
+    if a.bar_tail:
+        assert early_fn and 0 < a.bar_tail <= 6, "--bar-tail: 1..6 links of FN(6)..FN(11), which layout 2 keeps in front of the barrier"
+        k = len(fn) - a.bar_tail
+        assert all(name != "FN(12)" for name, _ in fn[k:])       # (the branching link stays where --early-emit's note puts it)
+        tail = fn[k:]
+        fn = fn[:k]
     if early_fn:
         # FN(0) (an LDS read) goes into the head gaps, which take nothing that touches the previous phase's accumulators; the
         # other links at even distances through the queue
@@ -127,7 +142,9 @@ def main():
         pinned.setdefault(si, []).append((f"PF({ks + 1})", 16))
 
     # even spread: each queue is paid out at its own average rate (its cost / its gaps, --budget / --post-budget if given)
-    npre = bar_slot + 1 - a.free_head
+    pre_last = bar_slot - len(tail) - (1 if tail else 0)           # the last gap that takes from the queue in front of the barrier
+    tail_at = {bar_slot - len(tail) + i: item for i, item in enumerate(tail)}
+    npre = pre_last + 1 - a.free_head
     npost = len(slots) - bar_slot - 1
     rate_pre = a.budget or sum(c for _, c in pre) / npre
     rate_post = a.post_budget or min(12.0, max(8.0, sum(c for _, c in post) / max(1, npost - 8)))
@@ -141,9 +158,11 @@ def main():
         queue, rate = (pre, rate_pre) if si <= bar_slot else (post, rate_post)
         if si == bar_slot + 1:
             credit = 0.0
-        if si >= a.free_head:
+        if si in tail_at:
+            items.append(tail_at[si][0]); used += tail_at[si][1]
+        if si >= a.free_head and not pre_last < si <= bar_slot:
             credit += rate
-            while queue and (queue[0][1] <= credit + 2 or (si == bar_slot and queue is pre)):
+            while queue and (queue[0][1] <= credit + 2 or (si == pre_last and queue is pre)):
                 if queue[0][0].startswith("CI") and si <= a.xp1:   # the table offsets of the next step are not there yet
                     break
                 name, c = queue.pop(0)
