@@ -17,7 +17,8 @@ Differences, all additive:
   * `predict --bed_dir DIR [--bed_min_score S]` also writes the predicted repeats of every input as a scored BED file: per row the
     mean and the smallest probability of its class and the share of its bases that carry it, summed on the GPU (deepgrp_amd/bed.py);
     with --bed_gzip the file is BGZF (`.bed.gz`), its lines written and deflated on the GPU, and with --bed_index a tabix index
-    (`.bed.gz.tbi`) is built there beside it;
+    (`.bed.gz.tbi`) is built there beside it; with --bed_bigbed the file is a bigBed instead (`.bb`, deepgrp_amd/bigbed.py: binary
+    items with 32-bit coordinates, an R-tree and coverage zoom levels, written and deflated on the GPU);
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
@@ -151,7 +152,8 @@ def _add_mask_options(parser, suppress: bool) -> None:
                         help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
                              "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
     parser.add_argument("--gzip_level", type=int, default=d(None),
-                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig and --bed_gzip: 0 literals "
+                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig, --bed_gzip and --bed_bigbed: 0 "
+                             "literals "
                              "only, 1 with matches (default: 0 for masked copies, 1 for tracks and the BED)")
 
 
@@ -201,6 +203,12 @@ def _add_bed_options(parser) -> None:
                         help="(addition) with --bed_gzip: write the tabix index <basename>.bed.gz.tbi, built on the GPU beside the text "
                              "(records must end at or below 2^29 and names must not reappear after another name; otherwise a warning "
                              "and no index)")
+    parser.add_argument("--bed_bigbed", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the scored repeats as bigBed, DIR/<basename>.bb, instead of BED text: one "
+                             "item per BED line (bed6+3, the extra columns typed by an autoSql declaration) with coverage zoom levels, "
+                             "built and deflated on the GPU (--gzip_level, 1 unless given); coordinates up to 2^32 - 1.  Record names "
+                             "must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and no "
+                             "bigBed for that input.  Not with --bed_gzip or --bed_index")
 
 
 class CommandLineParser:
@@ -513,14 +521,17 @@ class CommandLineParser:
                 track_sink = score_sink = None
                 if files is not None:
                     track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
-                if beds is not None and runner.bed is not None:     # --bed_gzip: scores, text and members on the device
+                if beds is not None and runner.bed is not None:     # --bed_gzip, --bed_bigbed: scores and the write on the device
                     score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
-                        merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed))
+                        merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed, chrom))
                 elif beds is not None:
                     score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
                 rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
                 if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
                     files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
+                if n == 0 and beds is not None and runner.bed is not None and runner.bed.bigbed:    # (a chromosome of the bigBed)
+                    from .bed import empty_write
+                    beds.write([name], False, rows, empty_write(runner.bed, name, record_indices(rec)[0], chrom))
                 bases += n
                 outstream.write(rows_text(filename, header, rows))
                 if kept is not None:

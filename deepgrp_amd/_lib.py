@@ -109,6 +109,11 @@ _SIGNATURES = {
     "dgrp_bed_text_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_bed_index_workspace_bytes": (i64, [i64, i64, i64, i64]),
     "dgrp_bed_index_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, i64, vp, vp, i64, C.POINTER(i64), vp, i64, vp, vp, i64, vp]),
+    "dgrp_bed_blocks_workspace_bytes": (i64, [i64, i64, vp]),
+    "dgrp_bed_blocks_batch": (cint, [cint, vp, vp, i64, cint, i64, vp, i64, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64),
+                                     vp, i64, vp]),
+    "dgrp_bed_zoom_workspace_bytes": (i64, [i64, i64, vp]),
+    "dgrp_bed_zoom_batch": (cint, [cint, vp, vp, i64, cint, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]),
     "dgrp_inflate_raw_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cint)]),
     "dgrp_inflate_workspace_bytes": (i64, [i64]),
     "dgrp_inflate_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(cint), vp, i64, vp]),

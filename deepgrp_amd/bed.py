@@ -18,7 +18,13 @@ write, so a record or batch boundary is a short member, and the EOF member is wr
 gets its tabix index `<basename>.bed.gz.tbi`: chunks and linear index come from the device in text offsets (dgrp_bed_index_batch;
 `reference_index_parts` restates them), `BedFiles` turns them into virtual offsets with the compressed size of every member it
 appends (tabix.IndexBuilder).  The index is tabix.reference_index of the finished `.bed.gz`: that function reads name, start and
-end of every line of a BGZF file and nothing else, so it states the index of a BED as it states a track's."""
+end of every line of a BGZF file and nothing else, so it states the index of a BED as it states a track's.
+
+With `--bed_bigbed` the file is `DIR/<basename>.bb` instead, bigBed as bigbed.py states it: one item per BED line, the extra columns
+typed by an autoSql declaration, 32-bit coordinates (a tabix index ends at 2^29), an R-tree over the item blocks and coverage zoom
+levels.  Item blocks and zoom records are written and deflated on the device (ContigPipeline.bigbed_write); `BedFiles` puts the
+container around them with a bigbed.BigBedBuilder.  An input a bigBed cannot hold (an empty record name, two records of one name,
+a record that ends above 2^32 - 1) gets one warning and no `.bb`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,6 +48,7 @@ class BedPlan(NamedTuple):
     paths: dict                                     # input file -> its BED file
     gzip_level: Optional[int] = None                # --bed_gzip: the level (None: plain text from the host formatter)
     index: bool = False                             # --bed_index
+    bigbed: bool = False                            # --bed_bigbed (gzip_level is then the level of its zlib streams)
 
 
 class BedWrite(NamedTuple):
@@ -56,12 +63,27 @@ class BedWrite(NamedTuple):
     last_end: Optional[np.ndarray] = None
 
 
-def bed_path(directory: str, filename: str, gzip: bool = False) -> str:
+def bed_path(directory: str, filename: str, gzip: bool = False, bigbed: bool = False) -> str:
     from .tracks import input_basename
+    if bigbed:
+        return os.path.join(directory, input_basename(filename) + ".bb")
     return os.path.join(directory, input_basename(filename) + ".bed" + (".gz" if gzip else ""))
 
 
+def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
+    """The device write of a record without a predicted base: no members; with p.bigbed its name and size for the chromosome tree
+    (chrom: its ordinal in the input)."""
+    from ._lib import name_blob
+    raw = name_blob([name])[0]
+    if p.bigbed:
+        from .bigbed import BigBedWrite, end_refusal
+        return BigBedWrite(raw, [int(startpos)], end_refusal(raw, [int(startpos)]), chrom0=chrom)
+    return BedWrite(b"", raw)
+
+
 def refuse_on_evaluate(args) -> None:
+    if getattr(args, "bed_bigbed", False):
+        sys.exit("--bed_bigbed belongs to predict, not evaluate")
     if (getattr(args, "bed_dir", None) is not None or getattr(args, "bed_min_score", None) is not None
             or getattr(args, "bed_gzip", False) or getattr(args, "bed_index", False)):
         sys.exit("--bed_dir belongs to predict, not evaluate")
@@ -73,6 +95,11 @@ def plan(args) -> Optional[BedPlan]:
     bdir = getattr(args, "bed_dir", None)
     low = getattr(args, "bed_min_score", None)
     gzip, index = bool(getattr(args, "bed_gzip", False)), bool(getattr(args, "bed_index", False))
+    bigbed = bool(getattr(args, "bed_bigbed", False))
+    if bigbed and bdir is None:
+        sys.exit("--bed_bigbed needs --bed_dir")
+    if bigbed and (gzip or index):
+        sys.exit("--bed_bigbed writes a bigBed file instead of BED text: it does not go with --bed_gzip or --bed_index")
     if gzip and bdir is None:
         sys.exit("--bed_gzip needs --bed_dir")
     if index and not gzip:
@@ -89,7 +116,7 @@ def plan(args) -> Optional[BedPlan]:
                  "rank that holds the merged probabilities)")
     paths, seen = {}, {}
     for f in args.FASTA:
-        out = bed_path(bdir, f, gzip)
+        out = bed_path(bdir, f, gzip, bigbed)
         base = os.path.basename(out)
         if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
             sys.exit(f"--bed_dir: the BED files of {seen[base]} and {f} have the same file name {base}; they would collide")
@@ -100,27 +127,82 @@ def plan(args) -> Optional[BedPlan]:
     if len(paths) != len(args.FASTA):
         sys.exit("--bed_dir: an input file is given twice")
     level = None
-    if gzip:
+    if gzip or bigbed:
         from .tracks import gzip_level
         level = gzip_level(args, 1)
-    return BedPlan(bdir, int(low), paths, level, index)
+    return BedPlan(bdir, int(low), paths, level, index, bigbed)
+
+
+class _BigBedFile(StagedFile):
+    """One `.bb` file: a bigbed.BigBedBuilder (`bb`) on the staged file."""
+
+    def __init__(self, final: str):
+        from .bigbed import BigBedBuilder
+        super().__init__(final, "w+b")
+        try:
+            self.bb = BigBedBuilder(self.fh, os.path.dirname(final))
+        except BaseException:
+            super().abort()
+            raise
+
+    def finish(self) -> None:
+        self.bb.finish()
+        self.fh.close()
+
+    def abort(self) -> None:
+        self.bb.close()
+        super().abort()
 
 
 class BedFiles(StagedOutputs):
     """The BED file of one input: a temporary file next to it, renamed by `commit`, removed by `abort` (outfiles.py).  With
     p.gzip_level `write` takes a BedWrite (BGZF members, to an outfiles.BgzfSink, which with p.index builds `<file>.tbi`).  An
     input that cannot be indexed (a record that ends above 2^29, an empty name, a name that comes back: name_order) gets one
-    warning and no index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed."""
+    warning and no index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed.  With
+    p.bigbed the file is a `.bb` with a bigbed.BigBedBuilder on its temporary file and `write` takes a bigbed.BigBedWrite; an
+    input a bigBed cannot hold (an empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and
+    no `.bb`: `commit` then removes the temporary file and any `.bb` an earlier run left."""
 
     def __init__(self, p: BedPlan, filename: str):
         os.makedirs(p.directory, exist_ok=True)
-        self.final, self.min_score, self.gzip = p.paths[filename], p.min_score, p.gzip_level is not None
+        self.final, self.min_score, self.bigbed = p.paths[filename], p.min_score, bool(p.bigbed)
+        self.gzip = p.gzip_level is not None and not self.bigbed
+        self.bb_refused = None
         super().__init__(_LOG, filename, "--bed_index", self.gzip and p.index,
-                         [BgzfSink(self.final, p.index) if self.gzip else StagedFile(self.final)])
+                         [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index) if self.gzip else StagedFile(self.final)])
+
+    def _bigbed(self, w) -> None:
+        """The write's part of the bigBed, or the input's refusal (one warning)."""
+        from .bigbed import BigBedWrite
+        if not isinstance(w, BigBedWrite):
+            raise ValueError(f"{self.filename}: a bigBed is written from BigBedWrite, not from scores on the host")
+        if self.bb_refused is not None:
+            return
+        why = w.refused
+        if why is None:
+            why = self.distinct_names(w.names)
+        if why is not None:
+            self.bb_refused = why
+            _LOG.warning("%s: no bigBed file is written (--bed_bigbed): %s", self.filename, why)
+            return
+        builder = self.parts[0].bb
+        if w.chrom0 is not None and w.chrom0 != len(builder.names):
+            raise ValueError(f"{self.filename}: a bigBed write of chromId {w.chrom0} arrived as record {len(builder.names)} of the input")
+        builder.add(w.names, w.sizes, w)
+
+    def commit(self) -> None:
+        if self.bb_refused is None:
+            return super().commit()
+        self.abort()
+        if os.path.exists(self.final):
+            os.remove(self.final)
 
     def write(self, names: Sequence, by_contig: bool, rows, scores) -> None:
         """The lines of one record (by_contig false: names[0]) or of a batch (rows["contig"] indexes the names); `scores` is the
-        rows' ROW_SCORE_DTYPE array, or with p.gzip_level the BedWrite the device made of rows and scores."""
+        rows' ROW_SCORE_DTYPE array, or with p.gzip_level the BedWrite the device made of rows and scores, or with p.bigbed its
+        bigbed.BigBedWrite."""
+        if self.bigbed:
+            return self._bigbed(scores)
         if not isinstance(scores, BedWrite):
             if self.gzip:
                 raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")

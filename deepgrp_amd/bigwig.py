@@ -155,16 +155,17 @@ def chrom_tree(names: Sequence[bytes], ids: Sequence[int], sizes: Sequence[int],
     return b"".join(out)
 
 
-def cir_tree(leaves: np.ndarray, at: int, end_offset: int) -> bytes:
-    """The cirTree over `leaves` (LEAF_DTYPE, in (chrom, start) order) as it lies at file offset `at`."""
+def cir_tree(leaves: np.ndarray, at: int, end_offset: int, items_per_slot: int = 1) -> bytes:
+    """The cirTree over `leaves` (LEAF_DTYPE, in (chrom, start) order) as it lies at file offset `at`; items_per_slot is the
+    header's field (1 in a bigWig; bigbed.py: the items of a full block)."""
     n = len(leaves)
     bs = 256
     if n == 0:
-        return struct.pack("<IIQIIIIQII", CIR_MAGIC, bs, 0, 0, 0, 0, 0, end_offset, 1, 0) + struct.pack("<BBH", 1, 0, 0)
+        return struct.pack("<IIQIIIIQII", CIR_MAGIC, bs, 0, 0, 0, 0, 0, end_offset, items_per_slot, 0) + struct.pack("<BBH", 1, 0, 0)
     ends = (leaves["ec"].astype(np.uint64) << np.uint64(32)) | leaves["eb"].astype(np.uint64)
     top = int(ends.max())
     head = struct.pack("<IIQIIIIQII", CIR_MAGIC, bs, n, int(leaves["sc"][0]), int(leaves["sb"][0]), top >> 32, top & 0xffffffff,
-                       end_offset, 1, 0)
+                       end_offset, items_per_slot, 0)
     levels = [(leaves, ends)]
     while len(levels[-1][0]) > bs:
         below, bends = levels[-1]
@@ -231,7 +232,13 @@ class ClassWrite(NamedTuple):
 
 class BigWigBuilder:
     """One `.bw` file on the open binary file `fh` (empty, seekable): `add` appends a write's sections and spools its zoom blocks to a
-    temporary file beside it, `finish` writes indexes, zoom levels, chromosome tree and trailer and rewrites the header."""
+    temporary file beside it, `finish` writes indexes, zoom levels, chromosome tree and trailer and rewrites the header.  The class
+    attributes are what bigbed.BigBedBuilder states differently: the magic, fieldCount and definedFieldCount, the autoSql text behind
+    the zoom headers (none: autoSqlOffset 0) and the itemsPerSlot of the data index."""
+    magic = MAGIC
+    fields = (0, 0)
+    autosql = b""
+    items_per_slot = 1
 
     def __init__(self, fh, digits: int, bin: int, spool_dir: Optional[str] = None):
         self.fh, self.digits, self.bin = fh, digits, bin
@@ -247,8 +254,10 @@ class BigWigBuilder:
         self.buf_size = 0
         self.covered = self.sum = self.sumsq = self.qmax = 0
         self.qmin: Optional[int] = None
-        fh.write(bytes(DATA_OFFSET + 8))
-        self.at = DATA_OFFSET + 8
+        self.summary_at = 64 + 24 * ZOOM_LEVELS + len(self.autosql)
+        self.data_at = self.summary_at + 40
+        fh.write(bytes(self.data_at + 8))
+        self.at = self.data_at + 8
 
     def add(self, names: Sequence[bytes], sizes: Sequence[int], w: Optional[ClassWrite]) -> None:
         first = len(self.names)
@@ -266,7 +275,7 @@ class BigWigBuilder:
             self.leaves.append(leaf)
             self.fh.write(w.sections)
             self.at += len(w.sections)
-            self.nsections += len(t)
+            self.nsections += self.counted(t)
             self.buf_size = max(self.buf_size, int(t["bytes"].max()))
         z = w.zoom_table
         if len(z):
@@ -292,6 +301,11 @@ class BigWigBuilder:
             self.qmin = qmin if self.qmin is None else min(self.qmin, qmin)
             self.qmax = max(self.qmax, qmax)
 
+    @staticmethod
+    def counted(table: np.ndarray) -> int:
+        """What a write's table adds to the count at fullDataOffset: its sections."""
+        return len(table)
+
     def levels(self) -> int:
         """The zoom levels the file gets."""
         longest = max(self.sizes, default=0)
@@ -304,7 +318,7 @@ class BigWigBuilder:
         fh = self.fh
         leaves = np.concatenate(self.leaves) if self.leaves else np.zeros(0, LEAF_DTYPE)
         index_at = self.at
-        fh.write(cir_tree(leaves, index_at, index_at))
+        fh.write(cir_tree(leaves, index_at, index_at, self.items_per_slot))
         nlev = self.levels()
         zoom_heads = []
         for k in range(nlev):
@@ -323,14 +337,14 @@ class BigWigBuilder:
         self.spool.close()
         tree_at = fh.tell()
         fh.write(chrom_tree(self.names, range(len(self.names)), self.sizes, tree_at))
-        fh.write(struct.pack("<I", MAGIC))
+        fh.write(struct.pack("<I", self.magic))
         scale = 10 ** self.digits
         summary = struct.pack("<Qdddd", self.covered, (self.qmin or 0) / scale, self.qmax / scale, self.sum / scale, self.sumsq / scale ** 2)
         fh.seek(0)
-        fh.write(struct.pack("<IHHQQQHHQQIQ", MAGIC, 4, nlev, tree_at, DATA_OFFSET, index_at, 0, 0, 0, 64 + 24 * ZOOM_LEVELS,
-                             max([self.buf_size] + self.zoom_buf[:nlev]), 0))
+        fh.write(struct.pack("<IHHQQQHHQQIQ", self.magic, 4, nlev, tree_at, self.data_at, index_at, *self.fields,
+                             64 + 24 * ZOOM_LEVELS if self.autosql else 0, self.summary_at, max([self.buf_size] + self.zoom_buf[:nlev]), 0))
         fh.write(b"".join(zoom_heads) + bytes(24 * (ZOOM_LEVELS - nlev)))
-        fh.write(summary)
+        fh.write(self.autosql + summary)
         fh.write(struct.pack("<Q", self.nsections))
         fh.seek(0, os.SEEK_END)
 

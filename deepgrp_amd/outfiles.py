@@ -110,6 +110,17 @@ class StagedOutputs:
                 self.last = nm
         return None
 
+    def distinct_names(self, names: Sequence[bytes]) -> Optional[str]:
+        """The rule a bigWig or bigBed has for the record names of an input, over all its writes: none empty, no two alike.
+        Registers `names` (in `seen`, as name_order does: a file has one rule or the other): why there is no file, or None."""
+        for nm in names:
+            if not nm:
+                return "a record with an empty name"
+            if nm in self.seen:
+                return f"two records have the name {nm.decode('utf-8', 'replace')!r}"
+            self.seen.add(nm)
+        return None
+
     def no_index(self, why: Optional[str]) -> None:
         if why is not None and self.indexed:
             self.log.warning("%s: no tabix index is written (%s): %s", self.filename, self.flag, why)

@@ -795,11 +795,15 @@ class ContigPipeline:
         host = _with_room(launch, cap)[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
 
-    def bed_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan):
+    def bed_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan,
+                  chrom0: int = 0):
         """One write of a BGZF BED (bed.BedWrite) for the arguments of row_scores_batch, `names` as bed.format_rows takes them and
         `plan` the bed.BedPlan: scores, text and, with plan.index, the index's pieces are made on the device from the uploaded rows;
         the text is deflated there in gz.GZIP_PIECE pieces (members span records, a write ends in a short member) and only the
-        members come back.  row_off must cover all rows (row_off[0] = 0, row_off[-1] = len(rows))."""
+        members come back.  row_off must cover all rows (row_off[0] = 0, row_off[-1] = len(rows)).  With plan.bigbed the write is
+        `bigbed_write`'s (chrom0: the ordinal of the first record in its input)."""
+        if plan.bigbed:                                     # --bed_bigbed: item blocks and zoom blocks instead of text
+            return self.bigbed_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan, chrom0)
         from .bed import BedWrite
         from .gz import bgzf_members_device
         from .tabix import end_refusal
@@ -820,6 +824,99 @@ class ContigPipeline:
             parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends)
         del d_probs, d_rows, d_scores
         return BedWrite(bgzf_members_device(d_text, plan.gzip_level), raw, refused, *parts)
+
+    # predict --bed_bigbed: the rows as bigBed item blocks and coverage zoom records
+    @staticmethod
+    def _bed_rows(who: str, d_rows: torch.Tensor, d_scores: torch.Tensor, rec_end):
+        nrows = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize
+        if int(d_scores.numel()) != nrows * ROW_SCORE_DTYPE.itemsize:
+            raise ValueError(f"{who}: {nrows} rows but {int(d_scores.numel())} bytes of scores")
+        return nrows, np.ascontiguousarray(rec_end, np.int64)
+
+    @staticmethod
+    def bed_blocks_batch(by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, chrom0: int = 0):
+        """The emitted rows of `d_rows` / `d_scores` (as bed_text_batch takes them) as uncompressed bigBed item blocks, one
+        dgrp_bed_blocks_batch call: -> (uint8 device tensor of the blocks back to back, uint8 device tensor of the block table, rows
+        of bigbed.BLOCK_DTYPE, the number of items).  Record r (a row's contig with by_contig, else 0) ends at rec_end[r] and has
+        chromId chrom0 + r.  What bigbed.reference_blocks states; complete behind the call on the current stream."""
+        from .bigbed import BLOCK_DTYPE, BLOCK_ITEMS
+        L = lib()
+        nrows, ends = ContigPipeline._bed_rows("bed_blocks_batch", d_rows, d_scores, rec_end)
+        nrec, dev = len(ends), d_rows.device
+        wb = int(L.dgrp_bed_blocks_workspace_bytes(nrows, nrec, ends.ctypes.data))
+        if wb <= 0:
+            raise ValueError(f"bed_blocks_batch: bad row count {nrows}, record count {nrec} or record ends (above 2^32 - 1?)")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        got, nblk, items = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+        def launch(cap, tcap):
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            table = torch.empty(max(tcap, 1) * BLOCK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_bed_blocks_batch(int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows, int(min_score), nrec, ends.ctypes.data,
+                                          int(chrom0), _ptr(out), cap, C.byref(got), _ptr(table), tcap, C.byref(nblk), C.byref(items),
+                                          _ptr(work), wb, stream_ptr()), "dgrp_bed_blocks_batch")
+            return (out, table), (int(got.value), int(nblk.value))
+        out, table = _with_room(launch, 48 * nrows, nrows // BLOCK_ITEMS + nrec)     # (an item of predict is 42..46 bytes: the guess fits)
+        return out[:got.value], table[:nblk.value * BLOCK_DTYPE.itemsize], int(items.value)
+
+    @staticmethod
+    def bed_zoom_batch(by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, chrom0: int = 0):
+        """The coverage zoom records of the same arguments, one dgrp_bed_zoom_batch call: -> (uint8 device tensor of the 32-byte
+        records; record offsets [bigwig.ZOOM_LEVELS + 1]; uint8 device tensor of the block table, rows of bigwig.ZOOM_BLOCK_DTYPE;
+        block offsets; totals, bigwig.TOTALS_DTYPE [1]).  What bigbed.reference_zoom and reference_totals state."""
+        from .bigwig import TOTALS_DTYPE, ZOOM_BLOCK_DTYPE, ZOOM_LEVELS
+        L = lib()
+        nrows, ends = ContigPipeline._bed_rows("bed_zoom_batch", d_rows, d_scores, rec_end)
+        nrec, dev = len(ends), d_rows.device
+        wb = int(L.dgrp_bed_zoom_workspace_bytes(nrows, nrec, ends.ctypes.data))
+        if wb <= 0:
+            raise ValueError(f"bed_zoom_batch: bad row count {nrows}, record count {nrec} or record ends (above 2^32 - 1?)")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        roff, boff = np.zeros(ZOOM_LEVELS + 1, np.int64), np.zeros(ZOOM_LEVELS + 1, np.int64)
+        totals = np.zeros(1, TOTALS_DTYPE)
+        nwin = int(((ends - 1) // 1024 + 1).sum())
+        cap = 32 * (min(2 * nrows, 2 * nwin) + ZOOM_LEVELS * nrec + 64)               # (a short row covers one window a level)
+
+        def launch(cap, tcap):
+            out = torch.empty(max(cap, 32), dtype=torch.uint8, device=dev)
+            table = torch.empty(max(tcap, 1) * ZOOM_BLOCK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_bed_zoom_batch(int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows, int(min_score), nrec, ends.ctypes.data,
+                                        int(chrom0), _ptr(out), cap, roff.ctypes.data, _ptr(table), tcap, boff.ctypes.data,
+                                        totals.ctypes.data, _ptr(work), wb, stream_ptr()), "dgrp_bed_zoom_batch")
+            return (out, table), (32 * int(roff[ZOOM_LEVELS]), int(boff[ZOOM_LEVELS]))
+        out, table = _with_room(launch, cap, cap // (32 * 1024) + ZOOM_LEVELS)
+        return out[:32 * int(roff[ZOOM_LEVELS])], roff, table[:int(boff[ZOOM_LEVELS]) * ZOOM_BLOCK_DTYPE.itemsize], boff, totals
+
+    def bigbed_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan,
+                     chrom0: int = 0):
+        """One write of a bigBed (bigbed.BigBedWrite) for the arguments of bed_write: scores -> item blocks -> zoom records on the
+        device from the uploaded rows, both deflated there (zlib_compress_device, plan.gzip_level); only compressed bytes, tables
+        and totals come back.  chrom0 is the ordinal of the first record in its input: chromIds count from there."""
+        from . import bigbed as bb
+        from .bigwig import ZOOM_BLOCK_DTYPE
+        from .tracks import _zlib_pieces
+        raw = name_blob(names)[0]
+        r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "bigbed_write", row0, lengths, startposes)
+        ends = sp + ln
+        sizes = [int(e) for e in ends]
+        refused = bb.end_refusal(raw, sizes)
+        rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+        ro = np.ascontiguousarray(row_off, np.int64)
+        if refused is not None or len(rows) == 0:
+            return bb.BigBedWrite(raw, sizes, refused, chrom0=chrom0)
+        if len(ro) != len(ln) + 1 or int(ro[0]) != 0 or int(ro[-1]) != len(rows):
+            raise ValueError("bigbed_write: the row offsets must cover all rows")
+        level = 1 if plan.gzip_level is None else plan.gzip_level
+        d_rows, d_scores = self._row_scores_device(d_probs, r0, ln, sp, rows, ro)
+        del d_probs
+        d_out, d_tab, _items = self.bed_blocks_batch(by_contig, d_rows, d_scores, plan.min_score, ends, chrom0)
+        blob, bsizes = _zlib_pieces(self, d_out, d_tab, bb.BLOCK_DTYPE.itemsize, level)
+        table = d_tab.cpu().numpy().view(bb.BLOCK_DTYPE)
+        del d_out, d_tab
+        d_zoom, _roff, d_ztab, _boff, totals = self.bed_zoom_batch(by_contig, d_rows, d_scores, plan.min_score, ends, chrom0)
+        zblob, zsizes = _zlib_pieces(self, d_zoom, d_ztab, ZOOM_BLOCK_DTYPE.itemsize, level)
+        ztable = d_ztab.cpu().numpy().view(ZOOM_BLOCK_DTYPE)
+        return bb.BigBedWrite(raw, sizes, None, blob, bsizes, table, zblob, zsizes, ztable, tuple(int(x) for x in totals[0]), chrom0)
 
     @staticmethod
     def batch_row_offsets(rows: np.ndarray, contigs) -> np.ndarray:

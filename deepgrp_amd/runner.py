@@ -21,7 +21,7 @@ from .pipeline import ContigPipeline, record_indices
 
 class _One(NamedTuple):
     """A work item: one record, the name of its track and BED lines (None where neither is made), its ordinal in its input (the
-    chromId of --track_bigwig)."""
+    chromId of --track_bigwig and --bed_bigbed)."""
     name: object
     rec: object
     chrom: int
@@ -90,7 +90,8 @@ class RecordRunner:
     """Runs (key, record) pairs -- record = DeviceRecord or sequence text -- and yields results in input order (`outputs`,
     `results`).  tracks (a tracks.TrackSpec): every record's track texts come with its rows; scores: the rows' scores
     (pipeline.ROW_SCORE_DTYPE, predict --bed_dir) do -- with bed (a bed.BedPlan with a gzip_level, --bed_gzip) the write's
-    bed.BedWrite instead, made on the device where rows and scores then stay.  With either, every key is (header, name), name
+    bed.BedWrite instead, made on the device where rows and scores then stay, and with a bigBed plan (--bed_bigbed) its
+    bigbed.BigBedWrite, chromIds counted by the record's ordinal in its input.  With either, every key is (header, name), name
     the first column of the record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged
     array; with neither, keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch)."""
 
@@ -118,16 +119,15 @@ class RecordRunner:
         if d_idx.numel() == 0:                            # no base: no rows; with --track_bigwig still a chromosome (empty_texts)
             scores = np.zeros(0, ROW_SCORE_DTYPE) if self.scores else None
             if self.scores and self.bed is not None:
-                from .bed import BedWrite
-                from ._lib import name_blob
-                scores = BedWrite(b"", name_blob([name])[0])
+                from .bed import empty_write
+                scores = empty_write(self.bed, name, startpos, chrom)
             return (np.zeros(0, SEGMENT_DTYPE), scores, empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
         merged = self.pipe.merged(d_idx)
         texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
         rows = self.pipe.segments(self.pipe.labels(merged), startpos)
         scores = None
         if self.scores and self.bed is not None:
-            scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed)
+            scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed, chrom)
         elif self.scores:
             scores = self.pipe.row_scores(merged, startpos, rows)
         return rows, scores, texts
@@ -144,7 +144,7 @@ class RecordRunner:
         scores = texts = None
         if self.scores and self.bed is not None:
             scores = self.pipe.bed_write(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]),
-                                         [k[1] for k, _r in batch], True, self.bed)
+                                         [k[1] for k, _r in batch], True, self.bed, batch.chrom0)
         elif self.scores:
             scores = self.pipe.row_scores_batch(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]))
         if self.tracks is not None:

@@ -91,7 +91,7 @@ def check_gzip_flags(args) -> None:
         sys.exit("--track_index needs --track_gzip (a tabix index belongs to a BGZF file)")
     if getattr(args, "gzip_level", None) is not None:
         if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False) or getattr(args, "track_bigwig", False)
-                or getattr(args, "bed_gzip", False)):
+                or getattr(args, "bed_gzip", False) or getattr(args, "bed_bigbed", False)):
             sys.exit("--gzip_level needs --mask_gzip or --track_gzip or --bed_gzip")
         gzip_level(args, 0)
 
@@ -280,7 +280,7 @@ class TrackFiles(StagedOutputs):
         self.bigwig = bool(spec.bigwig)
         self.gzip = spec.gzip_level is not None and not self.bigwig
         self.final = [track_path(p.directory, p.bases[filename], c, self.gzip, self.bigwig) for c in spec.classes]
-        self.bw_refused, self.bw_names = None, set()
+        self.bw_refused = None
         super().__init__(_LOG, filename, "--track_index", self.gzip and spec.index,
                          (_BigWigFile(path, spec.digits, spec.bin) if self.bigwig else BgzfSink(path, spec.index) if self.gzip
                           else StagedFile(path) for path in self.final))
@@ -292,14 +292,7 @@ class TrackFiles(StagedOutputs):
             return
         why = "a write came without its sections" if w is None else w.refused
         if why is None:
-            for nm in w.names:
-                if not nm:
-                    why = "a record with an empty name"
-                elif nm in self.bw_names:
-                    why = f"two records have the name {nm.decode('utf-8', 'replace')!r}"
-                if why is not None:
-                    break
-                self.bw_names.add(nm)
+            why = self.distinct_names(w.names)
         if why is not None:
             self.bw_refused = why
             _LOG.warning("%s: no bigWig files are written (--track_bigwig): %s", self.filename, why)

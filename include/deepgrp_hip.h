@@ -590,6 +590,53 @@ int dgrp_bed_index_batch(const char *names, const int64_t *name_off, int64_t nna
                          dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
                          int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- bigBed (predict --bed_bigbed; deepgrp_amd/bigbed.py states the file format).  Both entries take the rows and scores of
+ * dgrp_bed_text_batch, no names: the record of a row is its contig with by_contig, else 0 (then nrec must be 1); h_rec_end[r] (host,
+ * nrec entries, staged on the stream, may be dropped on return) is the end coordinate of record r; a row is EMITTED when its score
+ * is at least min_score.  One check kernel runs before any byte is written; DGRP_EINVAL, with every output untouched, for: the
+ * text entry's refusals (bases <= 0, with by_contig a contig outside 0..nrec-1, figures outside what dgrp_row_scores_batch writes);
+ * a row with start < 0, start >= end or end > h_rec_end of its record; records that do not ascend with the rows; a row whose start
+ * lies below the largest end of the rows in front of it in its record -- overlapping rows and descending starts alike, every row
+ * counting, filtered or not; rows that touch are fine.  (predict's rows are the runs of a label array and never overlap; the
+ * refusal makes the coverage depth 1 by contract.)  Refused on the host before any device work: h_rec_end[r] outside 1..2^32 - 1,
+ * nrec outside 1..2^31 - 1, chrom0 < 0 or chrom0 + nrec > 2^32 - 1, nrows >= 2^31 - 256.  nrows == 0: no device work, all counts 0.
+ *
+ * dgrp_bed_blocks_batch: the emitted rows as bigBed items, back to back in row order: chromId u32 = chrom0 + record, chromStart
+ * u32, chromEnd u32, then columns 4-9 of the BED line exactly as dgrp_format_bed_rows prints them, tab-separated, without the line
+ * feed, and one zero byte ("class3\t812\t.\t0.8123\t0.4000\t0.9500\0").  An item is at most 60 bytes (12, "class" and an int32 of
+ * at most 11 characters, a score of at most 4, ".", three figures of at most 6, 6 and -- for a qmin up to 2^32 - 1 -- 8, five tabs
+ * and the zero), so a BLOCK, up to 512 consecutive emitted rows of ONE record, is at most 30720 bytes, far below the 65280 of a
+ * dgrp_zlib_compress_batch row.  d_table gets one row per block, in order: off (bytes in d_out), bytes, rec (the record in this
+ * call), start (the first item's), end (the last item's), items; offset and length first, 32 bytes: the row table of
+ * dgrp_zlib_compress_batch as it comes.  *h_bytes, *h_nblocks and *h_items (host: bytes, blocks and emitted rows) are always
+ * filled; when the bytes exceed cap or the blocks table_cap nothing is written and the caller retries.  d_table is 8-byte aligned.
+ * Workspace dgrp_bed_blocks_workspace_bytes (0 on arguments the entry refuses): 28 bytes per row, 24 per record.
+ * Synchronises the stream ONCE (the read-back of the counts and the flags); items and table are complete behind the call on
+ * `stream`, not on return.
+ *
+ * dgrp_bed_zoom_batch: the coverage of the emitted rows as zoom summaries, the outputs of dgrp_track_zoom_batch with one class
+ * (cls 0): window w of level l of a record is [w * R, (w + 1) * R), R = 1024 * 4^l; a window with a covered base gives one 32-byte
+ * record: chromId u32 = chrom0 + r, chromStart u32 = its first covered base, chromEnd u32 = one past its last, validCount u32 = its
+ * covered bases, minVal = maxVal = 1.0f, sumData = sumSquares = (float)validCount.  h_record_off and h_block_off (host,
+ * DGRP_TRACK_ZOOM_LEVELS + 1 entries each) and *h_totals (covered, 1, 1, covered, covered; all 0 with nothing covered) are always
+ * filled; blocks of 1024 records, table rows, capacity protocol and alignment as dgrp_track_zoom_batch.  Level 0 has one thread per
+ * window, which finds the rows that touch it by two binary searches; no thread walks a row's windows or a record's rows.  Every
+ * figure is an integer count until the one conversion of validCount to float: the result does not depend on the grid, on timing
+ * or on any order of summation.  Workspace dgrp_bed_zoom_workspace_bytes (0 on arguments the entry refuses): 48 bytes per row, 88
+ * per record, and 12.04 bytes per window of all levels (about 16 per level-0 window of 1024 bases on long records).  Synchronises the
+ * stream ONCE; records and table are complete behind the call on `stream`. */
+typedef struct { int64_t off, bytes; int32_t rec; uint32_t start, end, items; } dgrp_bed_block;   /* 32 bytes */
+int64_t dgrp_bed_blocks_workspace_bytes(int64_t nrows, int64_t nrec, const int64_t *h_rec_end);
+int dgrp_bed_blocks_batch(int by_contig, const dgrp_segment *d_rows, const dgrp_row_score *d_scores, int64_t nrows, int min_score,
+                          int64_t nrec, const int64_t *h_rec_end, int64_t chrom0, char *d_out, int64_t cap, int64_t *h_bytes,
+                          dgrp_bed_block *d_table, int64_t table_cap, int64_t *h_nblocks, int64_t *h_items, void *d_work,
+                          int64_t work_bytes, void *stream);
+int64_t dgrp_bed_zoom_workspace_bytes(int64_t nrows, int64_t nrec, const int64_t *h_rec_end);
+int dgrp_bed_zoom_batch(int by_contig, const dgrp_segment *d_rows, const dgrp_row_score *d_scores, int64_t nrows, int min_score,
+                        int64_t nrec, const int64_t *h_rec_end, int64_t chrom0, char *d_out, int64_t cap, int64_t *h_record_off,
+                        dgrp_track_zoom_block *d_table, int64_t table_cap, int64_t *h_block_off, dgrp_track_totals *h_totals,
+                        void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- compressed input (an addition; the reference reads plain text only): DEFLATE (RFC 1951) streams inflated by the
  * same decode core on the device and on the host (deepgrp_amd/csrc/inflate.h).  A stream that cannot be decoded gives
  * DGRP_EDATA and one of these reasons; no read or write leaves the stream's input and output slices. */
