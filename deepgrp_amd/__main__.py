@@ -8,7 +8,8 @@ Differences, all additive:
   * under torchrun (WORLD_SIZE > 1) the records of all input files are sharded by contig over
     the GPUs and rank 0 writes the rows in input order;
   * `predict --mask_dir DIR [--mask soft|hard] [--mask_classes 1,3]` also writes a masked copy of every input FASTA file
-    (deepgrp_amd/masking.py);
+    (deepgrp_amd/masking.py); with --mask_twobit the copy is a UCSC .2bit file instead (soft mask = mask blocks, hard mask = N
+    blocks; tables and packed bases built on the GPU, deepgrp_amd/twobit.py);
   * `predict --track_dir DIR [--track_classes 1,3] [--track_digits D] [--track_bin B] [--track_gzip]` also writes the per-base class
     probabilities as one bedGraph file per input and class (deepgrp_amd/tracks.py), with --track_gzip as BGZF deflated on the GPU
     (`--gzip_level {0,1}`: literals only or with matches, for --mask_gzip as well) and with --track_index a tabix index beside
@@ -151,6 +152,10 @@ def _add_mask_options(parser, suppress: bool) -> None:
     parser.add_argument("--mask_gzip", action="store_true", default=d(False),
                         help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
                              "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
+    parser.add_argument("--mask_twobit", action="store_true", default=d(False),
+                        help="(addition) with --mask_dir: write every masked copy as a UCSC .2bit file (soft mask = mask blocks, hard "
+                             "mask = N blocks; packed on the GPU) to DIR/<basename>.2bit instead of FASTA text, and accept "
+                             "gzip-compressed inputs; one process only")
     parser.add_argument("--gzip_level", type=int, default=d(None),
                         help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig, --bed_gzip and --bed_bigbed: 0 "
                              "literals "
@@ -705,13 +710,21 @@ class CommandLineParser:
         refused here, before any prediction."""
         mdir = getattr(args, "mask_dir", None)
         packed_out = bool(getattr(args, "mask_gzip", False))
+        twobit_out = bool(getattr(args, "mask_twobit", False))
         if mdir is None:
+            if twobit_out:
+                sys.exit("--mask_twobit needs --mask_dir")
             if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None or packed_out:
                 sys.exit("--mask, --mask_classes and --mask_gzip need --mask_dir")
             return None
+        if twobit_out and packed_out:
+            sys.exit("--mask_twobit and --mask_gzip exclude each other: a 2bit file is a binary format of its own and is not compressed")
         if packed_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
             sys.exit("--mask_gzip: a compressed masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
                      "they share a file out by byte ranges, and a compressed file has none; run in one process")
+        if twobit_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
+            sys.exit("--mask_twobit: a 2bit masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
+                     "they share a file out by byte ranges, and a 2bit file has none of the input's; run in one process")
         from .gz import compressed_inputs
         from .twobit import is_twobit
         plan, seen = {}, {}
@@ -720,11 +733,17 @@ class CommandLineParser:
                 sys.exit("--mask_dir: standard input cannot be masked (give a FASTA file)")
             if f.endswith(".npz"):
                 sys.exit(f"--mask_dir: {f} is a one-hot .npz, not a FASTA file; it cannot be masked")
-            if not packed_out and compressed_inputs([f]):
+            if not packed_out and not twobit_out and compressed_inputs([f]):
                 sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
                          "uncompressed FASTA or pass --mask_gzip")
             base = os.path.basename(f)
-            if is_twobit(f):
+            if twobit_out:
+                # chr.fa -> chr.fa.2bit, hg38.fa.gz -> hg38.fa.2bit, hg38.2bit -> hg38.2bit
+                if base.endswith(".gz") and compressed_inputs([f]):
+                    base = base[:-3]
+                if not base.endswith(".2bit"):
+                    base += ".2bit"
+            elif is_twobit(f):
                 base += ".fa"                                     # the masked copy of a 2bit file is its FASTA text
             if packed_out and not base.endswith(".gz"):
                 base += ".gz"
@@ -748,16 +767,25 @@ class CommandLineParser:
 
     @staticmethod
     def _write_mask(filename: str, final: str, rows, args) -> None:
-        """The masked copy of one file: written to a temporary file next to `final`, renamed on success, removed on failure."""
+        """The masked copy of one file: written to a temporary file next to `final`, renamed on success, removed on failure.
+        --mask_twobit: an input that has no 2bit file (twobit.Refused) gets one warning and no file; the command goes on."""
         import tempfile
 
         from .masking import mask_fasta
+        from .twobit import Refused
         fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
         os.close(fd)
         try:
-            mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
-                       compress=bool(getattr(args, "mask_gzip", False)), level=getattr(args, "gzip_level", None) or 0)
+            if getattr(args, "mask_twobit", False):
+                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
+                           twobit=True)
+            else:
+                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
+                           compress=bool(getattr(args, "mask_gzip", False)), level=getattr(args, "gzip_level", None) or 0)
             os.replace(tmp, final)
+        except Refused as e:
+            os.remove(tmp)
+            _LOG.warning("--mask_twobit: %s; no %s is written", e, final)
         except BaseException:
             os.remove(tmp)
             raise
@@ -806,6 +834,8 @@ class CommandLineParser:
         """Score `predict`'s rows against an annotation (deepgrp_amd/evaluation.py): TSV report, optionally JSON."""
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
+        if getattr(args, "mask_twobit", False):
+            sys.exit("--mask_twobit belongs to predict, not evaluate")
         if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
             sys.exit("--mask_dir belongs to predict, not evaluate")
         if (getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False)

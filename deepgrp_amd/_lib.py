@@ -46,6 +46,8 @@ _SIGNATURES = {
     "dgrp_twobit_workspace_bytes": (i64, [i64]),
     "dgrp_twobit_encode_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
     "dgrp_twobit_text_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
+    "dgrp_twobit_pack_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_twobit_pack_batch": (cint, [vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
     "dgrp_format_rows_bound": (i64, [i64, i64]),
     "dgrp_format_rows": (cint, [vp, vp, i64, cint, vp, i64, vp, i64, C.POINTER(i64)]),
     "dgrp_track_workspace_bytes": (i64, [i64, i64]),

@@ -2,50 +2,13 @@
 // (inside a masked row lower case, elsewhere upper case) or hard (inside 'N').  A byte stream: one read for the per-tile counts, one
 // read and one write for the rewrite, 16 bytes per lane.  See include/deepgrp_hip.h.
 #include "dgrp_common.h"
+#include "body_tiles.h"
 #include "scan.h"
 #include <vector>
 
 namespace {
 
-#define MASK_TILE 4096            // bytes per workgroup: 256 lanes x 16
 #define MASK_LDS_ROWS 256         // rows of one tile staged in LDS; a tile crossing more reads them from global memory
-
-__device__ __forceinline__ bool mask_lineend(uint32_t b) { return b == '\n' || b == '\r'; }
-
-// record of tile t: the largest r < nrec with tile0[r] <= t (records without tiles share their tile0 with the next record)
-__device__ __forceinline__ int64_t mask_record_of(const int64_t *__restrict__ tile0, int64_t nrec, int64_t t)
-{
-    int64_t lo = 0, hi = nrec;                    // tile0[lo] <= t < tile0[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tile0[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct mask_span {
-    int64_t word;                 // 16-byte aligned address (offset in the buffer) of this lane's bytes
-    int lo, hi;                   // the lane's bytes inside the record: word + [lo, hi)
-};
-
-__device__ __forceinline__ mask_span mask_lane_span(int64_t off, int64_t len, int64_t k)
-{
-    mask_span s;
-    s.word = (off & ~(int64_t)15) + k * MASK_TILE + (int64_t)threadIdx.x * 16;
-    const int64_t a = s.word > off ? s.word : off, e = s.word + 16 < off + len ? s.word + 16 : off + len;
-    s.lo = (int)(a - s.word);
-    s.hi = e > a ? (int)(e - s.word) : s.lo;
-    return s;
-}
-
-__device__ __forceinline__ void mask_load(const uint8_t *__restrict__ raw, const mask_span &s, uint8_t *b)
-{
-    if (s.lo == 0 && s.hi == 16) {
-        *(uint4 *)b = *(const uint4 *)(raw + s.word);
-    } else {
-        for (int j = 0; j < 16; ++j) b[j] = (j >= s.lo && j < s.hi) ? raw[s.word + j] : (uint8_t)'\n';
-    }
-}
 
 __global__ void __launch_bounds__(256) mask_count_kernel(const uint8_t *__restrict__ raw, const int64_t *__restrict__ tile0,
                                                          const int64_t *__restrict__ off, const int64_t *__restrict__ len,
@@ -54,14 +17,14 @@ __global__ void __launch_bounds__(256) mask_count_kernel(const uint8_t *__restri
     __shared__ uint64_t lds[4];
     __shared__ int64_t s_rec;
     const int64_t t = blockIdx.x;
-    if (threadIdx.x == 0) s_rec = mask_record_of(tile0, nrec, t);
+    if (threadIdx.x == 0) s_rec = body_record_of(tile0, nrec, t);
     __syncthreads();
     const int64_t r = s_rec;
-    const mask_span s = mask_lane_span(off[r], len[r], t - tile0[r]);
+    const body_span s = body_lane_span(off[r], len[r], t - tile0[r]);
     alignas(16) uint8_t b[16];
-    mask_load(raw, s, b);
+    body_load(raw, s, b);
     uint64_t c = 0;
-    for (int j = 0; j < 16; ++j) c += mask_lineend(b[j]) ? 0 : 1;
+    for (int j = 0; j < 16; ++j) c += body_lineend(b[j]) ? 0 : 1;
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -104,7 +67,7 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const uint8_t *raw, uin
     __shared__ uint8_t r_in[MASK_LDS_ROWS];
     const int64_t t = blockIdx.x;
     if (threadIdx.x == 0) {
-        const int64_t r = mask_record_of(tile0, nrec, t);
+        const int64_t r = body_record_of(tile0, nrec, t);
         const int64_t p0 = (int64_t)(ex[t] - ex[tile0[r]]), p1 = p0 + (int64_t)(ex[t + 1] - ex[t]);
         // rows of this tile: the first that ends after p0 up to the first that starts at or after p1
         int64_t a = row_off[r], b = row_off[r + 1];
@@ -130,11 +93,11 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const uint8_t *raw, uin
             r_in[j] = (q.label >= 0 && q.label < 64 && ((class_mask >> q.label) & 1)) ? 1 : 0;
         }
     }
-    const mask_span s = mask_lane_span(off[r], len[r], t - tile0[r]);
+    const body_span s = body_lane_span(off[r], len[r], t - tile0[r]);
     alignas(16) uint8_t b[16];
-    mask_load(raw, s, b);
+    body_load(raw, s, b);
     uint64_t c = 0;
-    for (int j = 0; j < 16; ++j) c += mask_lineend(b[j]) ? 0 : 1;
+    for (int j = 0; j < 16; ++j) c += body_lineend(b[j]) ? 0 : 1;
     int64_t p = s_p0 + (int64_t)block_exclusive_scan(c, nullptr, lds);      // (its barriers also publish the staged rows)
     // local row index: the first row of the tile's list that ends after p
     auto row_end = [&](int64_t j) { return staged ? r_en[j] : rows[rlo + j].end; };
@@ -147,7 +110,7 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const uint8_t *raw, uin
     const int64_t n = rhi - rlo;
     for (int k = 0; k < 16; ++k) {
         const uint32_t x = b[k];
-        if (mask_lineend(x)) continue;               // (also the padding outside the record)
+        if (body_lineend(x)) continue;               // (also the padding outside the record)
         while (j < n && row_end(j) <= p) ++j;
         bool inside = false;
         if (j < n) {
@@ -171,17 +134,12 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const uint8_t *raw, uin
     }
 }
 
-static inline int64_t mask_tiles_of(int64_t off, int64_t len)
-{
-    return len > 0 ? (off + len - (off & ~(int64_t)15) + MASK_TILE - 1) / MASK_TILE : 0;
-}
-
 }   // namespace
 
 DGRP_EXPORT int64_t dgrp_fasta_mask_workspace_bytes(int64_t nrec, int64_t total_bytes, int64_t nrows)
 {
     if (nrec < 0 || total_bytes < 0 || nrows < 0) return 0;
-    const int64_t tiles = total_bytes / MASK_TILE + 2 * nrec + 1;          // >= the sum of mask_tiles_of over the records
+    const int64_t tiles = body_tile_bound(nrec, total_bytes);
     return 256 + dgrp_align_up((tiles + 1) * 8, 256) + dgrp_align_up((4 * nrec + 2) * 8, 256);
 }
 
@@ -204,7 +162,7 @@ DGRP_EXPORT int dgrp_fasta_mask_batch(const uint8_t *d_raw, int64_t nrec, const 
         total += h_len[r];
         off[r] = h_off[r];
         len[r] = h_len[r];
-        tile0[r + 1] = tile0[r] + mask_tiles_of(h_off[r], h_len[r]);
+        tile0[r + 1] = tile0[r] + body_tiles_of(h_off[r], h_len[r]);
     }
     for (int64_t r = 0; r <= nrec; ++r) row_off[r] = h_row_off[r];
     const int64_t ntiles = tile0[nrec], nrows = row_off[nrec] - row_off[0];

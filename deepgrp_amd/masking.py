@@ -124,7 +124,7 @@ def _pwrite_all(fd: int, data, offset: int) -> None:
 
 def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional[Iterable[int]] = None,
                ranges: Optional[Sequence[Tuple[int, int]]] = None, group_bytes: int = 256 << 20, group_records: int = 4096,
-               compress: bool = False, level: int = 0) -> int:
+               compress: bool = False, level: int = 0, twobit: bool = False) -> int:
     """Write the masked copy of `fasta_path`.  `rows` (pipeline.SEGMENT_DTYPE): the TSV rows, `contig` = the record's ordinal among
     the records the reference loop yields from the processed bytes, in file order.  `classes`: the labels to mask (None: every label
     > 0).  `ranges=None`: the whole file goes to `out_path` (created or truncated to the input's size); else only those byte ranges
@@ -136,12 +136,17 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     masked text -- every group is deflated on the device where it was masked (gz.bgzf_compress_device at `level`: 0 literals only,
     1 with matches) and its members are appended, the EOF member behind the last; a group boundary is just a short member.  A UCSC
     .2bit `fasta_path` (no `ranges`) is masked as the text of the file (twobit.open_text: built on the device by
-    dgrp_twobit_text_batch), which takes the place inflated gzip text takes.  Returns the number of records seen."""
+    dgrp_twobit_text_batch), which takes the place inflated gzip text takes.  `twobit=True` (no `ranges`, no `compress`):
+    `out_path` becomes the 2bit file of the masked text (twobit.py states it) -- every group stays on the device where it was masked,
+    its plain records are packed there (dgrp_twobit_pack_batch) and only their blobs are read back and spooled; records of the host
+    path are packed by twobit.pack_record from the host-masked bytes; header and index are written when the input is done.
+    twobit.Refused where the input has no 2bit file.  Returns the number of records seen."""
     import torch
 
     import contextlib
 
-    from . import gz, twobit
+    from . import gz
+    from . import twobit as tbit
     from ._lib import check, lib
     from .fasta import RESIDENT_BYTES, _chunk_groups, _upload_file
     from .pipeline import SEGMENT_DTYPE, require_gpu, stream_ptr
@@ -157,18 +162,24 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     packed = gz.is_gzip(fasta_path)
     if ranges is not None and (packed or compress):
         raise ValueError(f"{fasta_path}: a compressed input or output has no byte ranges to share out; it is masked whole")
+    if twobit and (ranges is not None or compress):
+        raise ValueError(f"{fasta_path}: a 2bit masked copy is written whole by one process and is not compressed")
     text = d_text = None
     if packed:
         text, d_text, size = gz.open_inflated(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
-    elif twobit.is_twobit(fasta_path):
+    elif tbit.is_twobit(fasta_path):
         if ranges is not None:
             raise ValueError(f"{fasta_path}: a 2bit input has no byte ranges of FASTA text to share out; it is masked whole")
         # the masked copy is the text of the file (twobit.py), built on the device: from here on as inflated gzip text
         packed = True
-        text, d_text, size = twobit.open_text(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
+        text, d_text, size = tbit.open_text(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
     else:
         size = os.path.getsize(fasta_path)
-    if ranges is None:
+    if twobit:
+        if size == 0:
+            tbit.write_file([], [], out_path, what=str(fasta_path))
+        ranges = [(0, size)] if size else []
+    elif ranges is None:
         with open(out_path, "wb") as fh:
             if compress and size == 0:
                 fh.write(gz.BGZF_EOF)
@@ -188,9 +199,13 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
         return lo, hi
 
     ordinal = 0
-    fd = os.open(out_path, os.O_WRONLY)
+    fd = None if twobit else os.open(out_path, os.O_WRONLY)
+    names, sizes = [], []                                       # twobit: the records so far, their blobs in `spool`
     try:
         with contextlib.ExitStack() as stack:
+            if twobit:
+                import tempfile
+                spool = stack.enter_context(tempfile.TemporaryFile(dir=os.path.dirname(os.path.abspath(out_path))))
             if packed:
                 mm = text
             else:
@@ -202,11 +217,15 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                 for grp in _chunk_groups(L, dev, fasta_path, mm, r0, r1, group_bytes, group_records, keep_raw=True, d_file=d_text):
                     g0, g1 = grp.starts[grp.c0], grp.starts[grp.c1]
                     dev_recs, host_chunks = [], []              # (i, ordinal); (chunk start, chunk end, [(header, offsets, ordinal)])
+                    dev_names = []                              # twobit: the names of dev_recs
                     for i, c in enumerate(range(grp.c0, grp.c1)):
                         a, b = grp.starts[c], grp.starts[c + 1]
                         if grp.plain(i):
-                            if mm[r0 + a:r0 + grp.head_ends[c]].decode("ascii").strip()[1:]:
+                            header = mm[r0 + a:r0 + grp.head_ends[c]].decode("ascii").strip()[1:]
+                            if header:
                                 dev_recs.append((i, ordinal))
+                                if twobit:
+                                    dev_names.append(tbit.record_name(header))
                                 ordinal += 1
                             continue
                         recs = []
@@ -235,6 +254,38 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                                                       mcode, bits, ptr - shift, work.data_ptr(), wb, stream_ptr()),
                               f"dgrp_fasta_mask_batch ({fasta_path})")
                         del work, d_rows
+                    if twobit:
+                        blobs = {}                              # ordinal -> (name, blob)
+                        if dev_recs:
+                            if int(h_len.sum()) > 0xFFFFFFFF:
+                                raise tbit.Refused(f"{fasta_path}: record {dev_recs[0][1]} ({dev_names[0]!r}) has more than 2^32 - 1 "
+                                                   "bases; a 2bit record cannot hold it")
+                            d_blobs, _counts, blob_off = tbit.pack_device(ptr - shift, h_off, h_len, dev,
+                                                                          f"dgrp_twobit_pack_batch ({fasta_path})")
+                            h_blobs = d_blobs[:int(blob_off[-1])].cpu().numpy()
+                            for j, (_i, k) in enumerate(dev_recs):
+                                blobs[k] = (dev_names[j], h_blobs[blob_off[j]:blob_off[j + 1]])
+                            del d_blobs
+                        if host_chunks:                         # these records only go through the host
+                            host = (d_raw.cpu().numpy() if packed else
+                                    np.frombuffer(mm, dtype=np.uint8, count=g1 - g0, offset=r0 + g0).copy())
+                            for a, recs in host_chunks:
+                                for header, offs, k in recs:
+                                    if offs is None:
+                                        raise tbit.Refused(f"{fasta_path}: record {header!r} has sequence lines that are not ASCII; "
+                                                           "it has no 2bit form")
+                                    lo, hi = rows_of(k)
+                                    inside = _paint(offs.size, rows[lo:hi], bits, f"{fasta_path}: record {header!r}")
+                                    _apply_host(host, offs + (a - g0), inside, mcode)
+                                    blobs[k] = (tbit.record_name(header, _text_encoding()), tbit.pack_record(host[offs + (a - g0)]))
+                            del host
+                        del grp, d_raw
+                        for k in sorted(blobs):
+                            name, blob = blobs[k]
+                            names.append(name)
+                            sizes.append(len(blob))
+                            spool.write(memoryview(blob))
+                        continue
                     host = None
                     if compress and not host_chunks:
                         pass                                    # the group stays on the device
@@ -264,10 +315,20 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
                     else:
                         _pwrite_all(fd, host, r0 + g0)
                     del host, d_raw
+            if twobit and size:
+                def pieces():
+                    spool.seek(0)
+                    while True:
+                        piece = spool.read(64 << 20)
+                        if not piece:
+                            return
+                        yield piece
+                tbit.write_file(names, pieces(), out_path, sizes=sizes, what=str(fasta_path))
         if compress:
             _pwrite_all(fd, gz.BGZF_EOF, written)
     finally:
-        os.close(fd)
+        if fd is not None:
+            os.close(fd)
     if contig.size and int(contig[-1]) >= ordinal:
         raise ValueError(f"{fasta_path}: rows name record {int(contig[-1])}, but only {ordinal} records were read")
     return ordinal

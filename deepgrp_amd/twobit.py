@@ -19,7 +19,20 @@ command gives for a 2bit file what it gives for that text (apart from the file-n
 the FASTA ingest yields from the text, and `predict --mask_dir` masks the text itself, built on the device.
 
 open_twobit parses and validates on the host (numpy over a mapping of the file, no Python loop over blocks) and merges the blocks
-into disjoint ascending intervals; the packed bases are unpacked on the GPU (dgrp_twobit_encode_batch, dgrp_twobit_text_batch)."""
+into disjoint ascending intervals; the packed bases are unpacked on the GPU (dgrp_twobit_encode_batch, dgrp_twobit_text_batch).
+
+OUTPUT (`predict --mask_dir DIR --mask_twobit`): the 2bit file of a masked text M, little-endian, version 0, both `reserved` words
+0, the index directly behind the header, the records behind it in file order without padding.  Its records are the records the
+reference's line loop yields from M (no header or an empty one: no record), named by the first whitespace-delimited word of the
+header.  A C G T in either case pack to T=0 C=1 A=2 G=3 (the unused bits of the last byte 0); any other sequence character is N (an
+N block, two bits 0); a character 'a'..'z' -- `n` and lower-case IUPAC letters included -- lies in a mask block.  Both tables hold
+the maximal runs: ascending, disjoint, never adjacent, never empty.  That fixes every byte of the file.  Plain records are packed
+on the device from the bytes dgrp_fasta_mask_batch has just rewritten (dgrp_twobit_pack_batch), the others by `pack_record` from
+the host-masked bytes; `write_file` states the header and the index.  Round trip: the text dgrp_twobit_text_batch gives for the
+output file is M with three changes -- record names are cut to their first word, sequences are re-wrapped at 50 bases per line,
+and every non-ACGT letter becomes `N` or `n`.  No UCSC tool has read these files: they are checked by the tests' own reader and
+writer.  `Refused`: duplicate names, a name above 255 bytes, a record above 2^32 - 1 bases, a file that reaches 2^32 bytes, a
+record whose sequence lines are not ASCII -- no file is written for that input."""
 from __future__ import annotations
 
 import mmap
@@ -269,3 +282,112 @@ def open_text(path, limit: int, dev_fn, upload):
         return None, None, 0
     d_text = DeviceTwoBit(tb, dev_fn(), upload).text()
     return DeviceText(d_text), d_text, tb.text_size
+
+
+# ---- output: the 2bit file of a masked text
+
+class Refused(ValueError):
+    """The input has no 2bit file (the message names the file and the record); nothing is written for it."""
+
+
+_ENOMEM = -3                                               # DGRP_ENOMEM (include/deepgrp_hip.h)
+_CODE = np.full(256, 4, np.uint8)                          # T=0 C=1 A=2 G=3 in either case, 4 = N
+for _i, _c in enumerate(b"TCAG"):
+    _CODE[_c] = _CODE[_c | 0x20] = _i
+
+
+def _runs(inside: np.ndarray):
+    """(starts, sizes) of the maximal runs of True."""
+    edge = np.diff(np.concatenate(([0], inside.view(np.int8), [0])))
+    start = np.flatnonzero(edge == 1)
+    return start, np.flatnonzero(edge == -1) - start
+
+
+def pack_record(seq) -> bytes:
+    """The record blob (dnaSize, the N block table, the mask block table, reserved, packedDna) of the sequence characters `seq`
+    (bytes or uint8 array, no line ends), by the rules of the module docstring -- what dgrp_twobit_pack_batch writes for a plain
+    record."""
+    b = np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else np.ascontiguousarray(seq, np.uint8)
+    if b.size > 0xFFFFFFFF:
+        raise Refused(f"{b.size} bases, a 2bit record holds at most 2^32 - 1")
+    code = _CODE[b]
+    isn = code == 4
+    ns, nz = _runs(isn)
+    ms, mz = _runs((b >= 97) & (b <= 122))
+    two = np.where(isn, 0, code).astype(np.uint8)
+    two = np.concatenate((two, np.zeros((-b.size) % 4, np.uint8))).reshape(-1, 4)
+    packed = (two[:, 0] << 6) | (two[:, 1] << 4) | (two[:, 2] << 2) | two[:, 3]
+    u = lambda a: np.asarray(a, "<u4").tobytes()
+    return b"".join((u([b.size, ns.size]), u(ns), u(nz), u([ms.size]), u(ms), u(mz), u([0]), packed.astype(np.uint8).tobytes()))
+
+
+def record_name(header: str, encoding: str = "ascii") -> bytes:
+    """faToTwoBit's rule: the first whitespace-delimited word of the (stripped) header."""
+    words = header.split()
+    return words[0].encode(encoding, "surrogateescape") if words else b""
+
+
+def write_file(names, blobs, out, sizes=None, what=None) -> int:
+    """Write the 2bit file of the records `names` (bytes) to the path `out`: header (signature, version 0, count, reserved 0),
+    index (nameSize, name, offset of the record), then the record blobs back to back.  `blobs`: one bytes-like per record; with
+    `sizes` (bytes per record) any iterable of pieces whose concatenation is the blobs in order (a spool).  Refused, before
+    anything is written, with `what` (default `out`) and the record in the message: two records of one name, a name above 255
+    bytes, a file that reaches 2^32 bytes.  Returns the file's size."""
+    what = str(out) if what is None else what
+    names = [bytes(n) for n in names]
+    if sizes is None:
+        blobs = [memoryview(b).cast("B") for b in blobs]
+        sizes = [len(b) for b in blobs]
+    if len(sizes) != len(names):
+        raise ValueError(f"{what}: {len(names)} names, {len(sizes)} records")
+    seen = {}
+    for r, nm in enumerate(names):
+        if len(nm) > 255:
+            raise Refused(f"{what}: record {r} ({nm[:40]!r}...): its name has {len(nm)} bytes, a 2bit index entry holds at most 255")
+        if nm in seen:
+            raise Refused(f"{what}: records {seen[nm]} and {r} are both named {nm!r} (the first word of their headers); a 2bit file "
+                          "names every record once")
+        seen[nm] = r
+    pos = 16 + sum(5 + len(nm) for nm in names)
+    index = []
+    for r, (nm, z) in enumerate(zip(names, sizes)):
+        if pos + z >= 1 << 32:
+            raise Refused(f"{what}: record {r} ({nm!r}): the file reaches 2^32 bytes, beyond the 32-bit offsets of 2bit version 0")
+        index.append(bytes([len(nm)]) + nm + struct.pack("<I", pos))
+        pos += z
+    total = 0
+    with open(out, "wb") as fh:
+        fh.write(struct.pack("<IIII", SIGNATURE, 0, len(names), 0))
+        fh.write(b"".join(index))
+        for piece in blobs:
+            total += fh.write(piece)
+    if total != sum(sizes):
+        raise ValueError(f"{what}: {total} bytes of records, the index states {sum(sizes)}")
+    return pos
+
+
+def pack_device(raw_ptr: int, h_off: np.ndarray, h_len: np.ndarray, dev, what: str):
+    """dgrp_twobit_pack_batch over the plain record bodies [h_off[r], + h_len[r]) of the 16-byte aligned device buffer at
+    `raw_ptr` -> (uint8 device buffer, counts int64 [nrec, 3] = dnaSize, nBlockCount, maskBlockCount, blob offsets int64
+    [nrec + 1]): record r's blob is buffer[blob_off[r]:blob_off[r + 1]].  The buffer is sized for few blocks; where the counts ask
+    for more the call is repeated once at the size it names."""
+    import torch
+
+    from ._lib import check, lib
+    from .pipeline import stream_ptr
+    L = lib()
+    nrec, total = len(h_off), int(h_len.sum())
+    counts, blob_off = np.zeros((nrec, 3), np.int64), np.zeros(nrec + 1, np.int64)
+    wb = int(L.dgrp_twobit_pack_workspace_bytes(nrec, total))
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+    cap = 17 * nrec + total // 4 + total // 16 + 4096
+    for attempt in (0, 1):
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        rc = L.dgrp_twobit_pack_batch(raw_ptr, nrec, h_off.ctypes.data, h_len.ctypes.data, d_out.data_ptr(), 0, cap, counts.ctypes.data,
+                                      blob_off.ctypes.data, work.data_ptr(), wb, stream_ptr())
+        if rc == _ENOMEM and attempt == 0 and int(blob_off[-1]) > cap:    # many blocks; the sizes are known now
+            cap = int(blob_off[-1])
+            continue
+        check(rc, what)
+        break
+    return d_out, counts, blob_off

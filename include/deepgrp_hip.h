@@ -143,6 +143,28 @@ int dgrp_twobit_text_batch(const uint8_t *d_file, int64_t file_bytes, int64_t nr
                            const int64_t *h_m_iv_off, int64_t m_iv, const int64_t *h_text_off, uint8_t *d_text,
                            int64_t text_cap, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- UCSC .2bit output (predict --mask_twobit; an addition): the records of a 2bit file from nrec plain record bodies of ONE
+ * device buffer, addressed as dgrp_fasta_mask_batch addresses them -- record r = bytes [h_off[r], h_off[r] + h_len[r]) of d_raw
+ * (16-byte aligned), line ends LF or CRLF, sequence position p = the p-th byte that is neither CR nor LF, the last line with or
+ * without its line end.  It runs on the bytes that dgrp_fasta_mask_batch has just rewritten.  Per sequence byte: A C G T in either
+ * case pack to T=0 C=1 A=2 G=3, the first base of a byte in its two most significant bits, the unused bits of the last byte 0; any
+ * other byte is N (two bits 0); a byte 'a'..'z' is soft-masked.  The N blocks and the mask blocks of a record are the maximal runs
+ * of such bytes: ascending, disjoint, never adjacent, never empty.
+ * Stage 1 counts per tile of text and scans (scan.h, three launches); per record dnaSize, nBlockCount and maskBlockCount come back
+ * to h_counts[3 r ..] -- the entry's only synchronisation.  Stage 2: the blobs
+ *     dnaSize, nBlockCount, nBlockStarts[], nBlockSizes[], maskBlockCount, maskBlockStarts[], maskBlockSizes[], reserved (0),
+ *     packedDna (ceil(dnaSize / 4) bytes)
+ * (uint32, little-endian) are laid out back to back from d_out + out_off, each at whatever byte alignment falls out, record r at
+ * h_blob_off[r], the end of the last at h_blob_off[nrec]; the kernels write every blob whole and nothing else of d_out [out_cap].
+ * Checked before anything is queued: the host tables (DGRP_EINVAL; at most 2^32 - 1 bytes of text per call), the workspace
+ * (dgrp_twobit_pack_workspace_bytes, else DGRP_ENOMEM) and room for the 16 bytes every blob has (DGRP_ENOMEM).  Blobs that do not
+ * fit out_cap once their sizes are known: DGRP_ENOMEM with h_counts and h_blob_off filled and nothing written -- call again with
+ * h_blob_off[nrec] bytes.  nrec == 0: nothing is queued.  The writes are stream-ordered. */
+int64_t dgrp_twobit_pack_workspace_bytes(int64_t nrec, int64_t total_bytes);
+int dgrp_twobit_pack_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_off, const int64_t *h_len, uint8_t *d_out,
+                           int64_t out_off, int64_t out_cap, int64_t *h_counts, int64_t *h_blob_off, void *d_work,
+                           int64_t work_bytes, void *stream);
+
 /* ---- A3: deepgrp.prediction.fetch_validation_batch (deepgrp/prediction.py:14-37)
  * Number of windows len(range(0, n - T, s)). */
 int64_t dgrp_window_count(int64_t n, int64_t T, int64_t s);
