@@ -26,7 +26,9 @@ Differences, all additive:
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
   * `train <parameter.toml> <trainfile.npz> <validfile.npz> <bedfile>` trains a GRU model on the GPU (deepgrp_amd/training.py:
     forward, backward through time and the optimizer are HIP kernels) and writes a Keras HDF5 file `predict` loads; `--seed N`
-    (an addition) seeds the initial weights, the sampler and the dropout masks.  No TensorBoard output;
+    (an addition) seeds the initial weights, the sampler and the dropout masks.  No TensorBoard output.  Both files may instead be
+    sequence files as `predict` takes them (FASTA, gzip, BGZF, .2bit; `--train_contigs a,b` / `--valid_contigs c` pick records by the
+    first word of their header): truth and sampler sets are then built on the GPU, and one record trains to the bytes of its .npz;
   * `optimize <space.toml> <parameter.toml> <trainfile.npz> <validfile.npz> <bedfile>` runs the hyper-parameter search of
     deepgrp/optimization.py as seeded random search (deepgrp_amd/optimization.py), `--cohort` trials trained side by side.
 """
@@ -253,6 +255,10 @@ class CommandLineParser:
         train.add_argument("--seed", type=int, default=None,
                            help="(addition) seed of the initial weights, the sampler and the dropout masks: the same seed "
                                 "writes the same model file, byte for byte")
+        train.add_argument("--train_contigs", type=str, default=None,
+                           help="(addition) with a sequence file (FASTA, gzip, BGZF, .2bit) as trainfile: the records to train on, by "
+                                "the first word of their header, comma separated (default: every record, in file order)")
+        train.add_argument("--valid_contigs", type=str, default=None, help="(addition) the same for validfile")
         optimize = subparsers.add_parser(name="optimize", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                          description="(addition) hyper-parameter search (deepgrp/optimization.py): seeded random "
                                                      "search over the [space] table of a TOML file, trials trained side by side on "
@@ -942,17 +948,49 @@ class CommandLineParser:
         except dgtrain.TrainingRefused as exc:
             sys.exit(f"train: {exc}")
         logdir = args.logdir
-        train_chr = os.path.basename(args.trainfile).split(".")[0]
-        val_chr = os.path.basename(args.validfile).split(".")[0]
-        if not os.path.isdir(logdir):
-            os.mkdir(logdir)
-        _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
-        train_fwd = dgpreprocess.load_onehot_npz(args.trainfile)
-        val_fwd = dgpreprocess.load_onehot_npz(args.validfile)
-        y_train = dgpreprocess.preprocess_y(args.bedfile, train_chr, train_fwd.shape[1], parameter.repeats_to_search)
-        y_val = dgpreprocess.preprocess_y(args.bedfile, val_chr, val_fwd.shape[1], parameter.repeats_to_search)
-        train_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(train_fwd, y_train))
-        val_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(val_fwd, y_val))
+        sides = (("trainfile", args.trainfile, "--train_contigs", args.train_contigs),
+                 ("validfile", args.validfile, "--valid_contigs", args.valid_contigs))
+        npz = [dgtrain.is_npz(path) for _role, path, _flag, _contigs in sides]
+        if npz[0] != npz[1]:
+            kinds = ["a .npz of preprocess_sequence" if z else "a sequence file" for z in npz]
+            sys.exit(f"train: {sides[0][0]} {sides[0][1]} is {kinds[0]} and {sides[1][0]} {sides[1][1]} is {kinds[1]}: "
+                     "give both sides in one form")
+        if npz[0]:
+            for _role, path, flag, contigs in sides:
+                if contigs is not None:
+                    sys.exit(f"train: {flag} selects records of a sequence file; {path} is a .npz of preprocess_sequence, one "
+                             "record named by the file")
+            train_chr = os.path.basename(args.trainfile).split(".")[0]
+            val_chr = os.path.basename(args.validfile).split(".")[0]
+            if not os.path.isdir(logdir):
+                os.mkdir(logdir)
+            _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
+            train_fwd = dgpreprocess.load_onehot_npz(args.trainfile)
+            val_fwd = dgpreprocess.load_onehot_npz(args.validfile)
+            y_train = dgpreprocess.preprocess_y(args.bedfile, train_chr, train_fwd.shape[1], parameter.repeats_to_search)
+            y_val = dgpreprocess.preprocess_y(args.bedfile, val_chr, val_fwd.shape[1], parameter.repeats_to_search)
+            train_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(train_fwd, y_train))
+            val_data = dgpreprocess.Data(*dgpreprocess.drop_start_end_n(val_fwd, y_val))
+        else:
+            # sequence files: the record names are read and checked on the host, then ingest, truth and sampler sets are the GPU's
+            picked = []
+            for _role, path, flag, contigs in sides:
+                contigs = None if contigs is None else [c for c in contigs.split(",") if c]
+                try:
+                    dgtrain.select_contigs(dgtrain.sequence_names(path), contigs, f"train: {flag}: {path}" if contigs is not None
+                                           else f"train: {path}")
+                except ValueError as exc:
+                    sys.exit(str(exc))
+                picked.append(contigs)
+            if not os.path.isdir(logdir):
+                os.mkdir(logdir)
+            _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
+            try:
+                train_data, val_data = (dgtrain.DeviceData.from_sequence_file(path, args.bedfile, parameter.repeats_to_search,
+                                                                             contigs, vecsize=int(parameter.vecsize))
+                                        for (_role, path, _flag, _c), contigs in zip(sides, picked))
+            except ValueError as exc:
+                sys.exit(f"train: {exc}")
         _LOG.info("Creating model for training")
         dgmodel.reset_layer_names()
         config = {"class_name": "Functional", "config": dgmodel.model_config(parameter)}

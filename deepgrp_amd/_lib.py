@@ -131,6 +131,11 @@ _SIGNATURES = {
     "dgrp_train_step": (cint, [cint, cint, cint, cint, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp]),
     "dgrp_train_step_multi": (cint, [C.POINTER(TrainJob), cint, vp]),
     "dgrp_optimizer_step": (cint, [cint, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp]),
+    "dgrp_truth_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_truth_multihot_batch": (cint, [vp, cint, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_class_starts_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_class_window_starts": (cint, [vp, i64, i64, vp, vp, cint, vp, i64, C.POINTER(i64), vp, i64, vp]),
+    "dgrp_train_resolve_starts": (cint, [vp, i64, vp, vp, cint, vp, vp, i64, vp, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

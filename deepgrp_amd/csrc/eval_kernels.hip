@@ -105,44 +105,14 @@ DGRP_EXPORT int dgrp_filter_segments(const int8_t *d_labels, int8_t *d_out, int6
 // the clipped lengths gives every row its place on one line of positions, and workgroup b takes positions
 // [b * EVAL_SLICE, (b + 1) * EVAL_SLICE) of that line (rows run from 10 bp to megabases).
 // ------------------------------------------------------------------------------------------------------------------------------
+#include "eval_paint.h"
 #include "scan.h"
 #include <vector>
 
 namespace {
 
-#define EVAL_SLICE 8192           // positions per workgroup: 256 lanes x 32, lane-interleaved (a wave's stores are 64 adjacent bytes)
 #define EVAL_LDS_ROWS 2048        // hits: the slice's per-row counters in LDS; a slice crossing more rows adds to d_hits directly
 #define EVAL_HEAD 2048            // workspace head: flag + first bad row at 0, clipped length per label (128 x u64) at 1024
-
-__device__ __forceinline__ int64_t eval_record_of(const int64_t *__restrict__ row_off, int64_t nrec, int64_t i)
-{
-    int64_t lo = 0, hi = nrec;                    // largest r < nrec with row_off[r] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (row_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// row j's span on the record: [cs, cs + cl) of its bases (cl = 0 when the row misses the record)
-__device__ __forceinline__ void eval_clip(const dgrp_segment &q, int64_t origin, int64_t len, int64_t &cs, int64_t &cl)
-{
-    int64_t a = q.start - origin, e = q.end - origin;
-    a = a < 0 ? 0 : (a > len ? len : a);
-    e = e < 0 ? 0 : (e > len ? len : e);
-    cs = a;
-    cl = e > a ? e - a : 0;
-}
-
-// largest j in [lo, hi) with ex[j] <= p, given ex[lo] <= p < ex[hi]
-__device__ __forceinline__ int64_t eval_row_of(const uint64_t *__restrict__ ex, int64_t lo, int64_t hi, uint64_t p)
-{
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ex[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // one lane per row: 0 <= start <= end and 1 <= label <= max_label (at most 127), else g[0] |= 1 and g[1] = smallest bad row; tot[label] += clipped length
 // (summed per workgroup in LDS first: a handful of labels would otherwise serialise one global atomic per row)
@@ -186,22 +156,6 @@ __global__ void __launch_bounds__(256) eval_span_kernel(const dgrp_segment *__re
     eval_clip(q, origin[r], len[r], cs, n);
     cl[j] = (label == 0 || q.label == label) ? (uint64_t)n : 0;
     dst[j] = off[r] + cs;
-}
-
-// ex[0..n] = exclusive scan of the rows' lengths in this pass (ex[n] = total): every position of the slice gets `label`
-__global__ void __launch_bounds__(256) eval_paint_kernel(int8_t *__restrict__ labels, const uint64_t *__restrict__ ex,
-                                                         const int64_t *__restrict__ dst, int64_t n, int label)
-{
-    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
-    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;
-    const uint64_t p0 = s0 + threadIdx.x;
-    if (p0 >= s1) return;
-    int64_t j = eval_row_of(ex, 0, n, p0);
-    uint64_t jst = ex[j], jend = ex[j + 1];
-    for (uint64_t p = p0; p < s1; p += 256) {
-        while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
-        labels[dst[j] + (int64_t)(p - jst)] = (int8_t)label;
-    }
 }
 
 // hits[j] += bases of row j's clipped span whose label equals row j's: per-lane counts per row, gathered in LDS per row of the

@@ -7,6 +7,11 @@ returns START POSITIONS into the record instead of copied windows: the record's 
 Differences from the reference, all stated in DESIGN.md: no TensorBoard output and no TensorFlow checkpoint bundles (the best epoch
 is written as ``<logdir>/<epoch:02d>.hdf5``, a Keras HDF5 file), the GRU cell's dropout mask is constant over the steps of a window,
 and ``seed`` makes a run reproducible byte for byte.
+
+A side of the data comes in one of two forms.  ``preprocessing.Data`` is the reference's: host arrays from a one-hot .npz, sampled by
+``fetch_batch`` on the host.  ``DeviceData`` is a sequence file (FASTA, gzip, BGZF, .2bit) as the device ingest left it: the kept
+records back to back in HBM, the multi-hot truth painted there from the annotation rows, the sampler's class index sets built there
+(``DeviceSampler``); the host draws ranks from the generator in ``fetch_batch``'s order and the device turns them into starts.
 """
 from __future__ import annotations
 
@@ -250,6 +255,305 @@ def run_jobs(jobs) -> None:
         _lib.check(_lib.lib().dgrp_train_step_multi(table, len(part), stream), "dgrp_train_step_multi")
 
 
+# ------------------------------------------------------------------------------------------------ sequence files
+SEGMENT_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("label", "<i4"), ("contig", "<i4")])     # struct dgrp_segment
+
+
+def is_npz(path) -> bool:
+    """The file starts with a zip signature: what ``np.savez`` / ``preprocess_sequence`` write (False if it cannot be opened)."""
+    try:
+        with open(path, "rb") as fh:
+            return fh.read(4) in (b"PK\x03\x04", b"PK\x05\x06")
+    except OSError:
+        return False
+
+
+def first_word(header: str) -> str:
+    """The name a record is matched by: the first whitespace-delimited word of its header (evaluation.record_name's rule)."""
+    words = header.split()
+    return words[0] if words else ""
+
+
+def _header_lines(buf, line_start: bool):
+    """(complete header lines of `buf` without their '>', offset of a header line still open at the end or -1): a header line opens
+    with '>' at a line start, which `buf` begins with when `line_start`."""
+    out = []
+    if line_start and buf[:1] == b">":
+        i = 0
+    else:
+        j = buf.find(b"\n>")
+        i = j + 1 if j >= 0 else -1
+    while i >= 0:
+        nl = buf.find(b"\n", i)
+        if nl < 0:
+            return out, i
+        out.append(buf[i + 1:nl])
+        j = buf.find(b"\n>", nl)
+        i = j + 1 if j >= 0 else -1
+    return out, -1
+
+
+def sequence_names(path) -> List[str]:
+    """First words of the record headers of a sequence file in file order, read on the HOST (no device, no library): FASTA text by a
+    scan for '>' at line starts, gzip / BGZF through zlib, .2bit from its index.  Records without a header are left out, as the
+    ingest leaves them out.  `train` checks --train_contigs / --valid_contigs against this before any device work."""
+    import mmap
+    import zlib
+
+    from . import gz, twobit
+    heads: List[bytes] = []
+    if twobit.is_twobit(path):
+        heads = [b" ".join(nm.split(b"\n")[0].split()) for nm in twobit.open_twobit(path).names]
+    elif gz.is_gzip(path):
+        carry, line_start = b"", True
+        with open(path, "rb") as fh:
+            d = zlib.decompressobj(31)
+            while True:
+                data = fh.read(1 << 22)
+                if not data:
+                    break
+                while data:
+                    if d.eof:                                            # the next member
+                        d = zlib.decompressobj(31)
+                    try:
+                        buf = carry + d.decompress(data)
+                    except zlib.error as exc:
+                        raise gz.GzipError(path, fh.tell() - len(data), str(exc)) from None
+                    data = d.unused_data
+                    if not buf:
+                        continue
+                    got, still = _header_lines(buf, line_start)
+                    heads += got
+                    carry = buf[still:] if still >= 0 else b""
+                    line_start = True if still >= 0 else buf.endswith(b"\n")
+        if carry:
+            heads.append(carry[1:])
+    elif os.path.getsize(path):
+        with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            heads, still = _header_lines(mm, True)
+            if still >= 0:
+                heads.append(mm[still + 1:])
+    names = [first_word(h.decode("utf-8", "surrogateescape").strip()) for h in heads if h.strip()]
+    return names
+
+
+def select_contigs(names: List[str], contigs: Optional[List[str]], what: str) -> List[str]:
+    """The names of `names` (file order) that `contigs` selects (None: all of them).  ValueError naming a listed contig the file does
+    not hold, and a first word that two selected records share."""
+    if contigs is not None:
+        have = set(names)
+        for c in contigs:
+            if c not in have:
+                raise ValueError(f"{what}: no record named {c!r} (records: {', '.join(repr(n) for n in names[:5]) or 'none'}"
+                                 f"{', ...' if len(names) > 5 else ''})")
+        wanted = set(contigs)
+        names = [n for n in names if n in wanted]
+    seen = set()
+    for n in names:
+        if n in seen:
+            raise ValueError(f"{what}: two records are named {n!r}: the annotation rows of {n!r} cannot be told apart")
+        seen.add(n)
+    return names
+
+
+def read_truth_rows(bedfile, names: List[str], repeats_to_search) -> Dict[str, np.ndarray]:
+    """The rows preprocess_y keeps for each contig of `names`, as SEGMENT_DTYPE arrays in file order: first column the contig, repeat
+    number (fourth column) in `repeats_to_search`.  A kept number that has no truth row -- the reference's IndexError -- is a
+    ValueError naming the line, as is a negative coordinate; a row that ends at or before its begin paints nothing and is dropped."""
+    classes = len(repeats_to_search) + 1
+    wanted = set(int(r) for r in repeats_to_search)
+    per: Dict[str, List[Tuple[int, int, int]]] = {n: [] for n in names}
+    with open(bedfile, "r") as fh:
+        for lineno, line in enumerate(fh, 1):
+            cols = line.split()
+            if not cols or cols[0] not in per:
+                continue
+            number = int(cols[3])
+            if number not in wanted:
+                continue
+            begin, end = int(cols[1]), int(cols[2])
+            if not 1 <= number < classes:
+                raise ValueError(f"{bedfile}:{lineno}: repeat number {number} has no row in a truth of {classes} classes "
+                                 f"(repeats_to_search = {list(repeats_to_search)}): {line.rstrip()!r}")
+            if begin < 0 or end < 0:
+                raise ValueError(f"{bedfile}:{lineno}: negative coordinate: {line.rstrip()!r}")
+            if end > begin:
+                per[cols[0]].append((begin, end, number))
+    out = {}
+    for n, rows in per.items():
+        arr = np.zeros(len(rows), SEGMENT_DTYPE)
+        if rows:
+            arr["start"], arr["end"], arr["label"] = np.asarray(rows, np.int64).T
+        out[n] = arr
+    return out
+
+
+class DeviceData:
+    """One side of the training data, resident: the class indices uint8 [n] of its records back to back, their multi-hot truth int8
+    [classes, n], and the record table (`names`, `base` = position of each record in the buffer, `lengths`, `startpos` = original
+    coordinate of each record's first base).  A record's bases are those from its first to its last non-N base without the last one
+    (drop_start_end_n's span).  DeviceTrainer.job takes it where it takes a DeviceRecord."""
+
+    def __init__(self, d_idx, d_truth, names, base, lengths, startpos):
+        self.d_idx, self.d_truth = d_idx, d_truth
+        self.n, self.classes = int(d_idx.numel()), int(d_truth.shape[0])
+        self.names = list(names)
+        self.base, self.lengths, self.startpos = (np.ascontiguousarray(a, np.int64) for a in (base, lengths, startpos))
+
+    @classmethod
+    def from_data(cls, data: preprocessing.Data) -> "DeviceData":
+        """The host arrays of a .npz side, uploaded: one record."""
+        rec = DeviceRecord.from_data(data)
+        return cls(rec.d_idx, rec.d_truth, [None], [0], [rec.n], [0])
+
+    @classmethod
+    def from_sequence_file(cls, path, bedfile, repeats_to_search, contigs: Optional[List[str]] = None,
+                           vecsize: Optional[int] = None) -> "DeviceData":
+        """The records of a FASTA / gzip / BGZF / .2bit file that `contigs` names by the first word of their header (None: every
+        record), in file order, and their truth from the parse_rm table `bedfile`, painted on the device.  With `vecsize`, a record
+        that holds no window of that length is left out with a warning.  ValueError: a listed contig the file does not hold, two
+        selected records with one name, a kept annotation row whose repeat number has no truth row, no record left."""
+        import torch
+
+        from . import _lib
+        from .fasta import read_multi_fasta_device
+        from .pipeline import record_indices, stream_ptr
+        wanted = None if contigs is None else set(contigs)
+        found, names, parts, lengths, startpos = [], [], [], [], []
+        for header, rec in read_multi_fasta_device(path):
+            name = first_word(header)
+            found.append(name)
+            if wanted is not None and name not in wanted:
+                continue
+            try:
+                st, d_idx = record_indices(rec)
+            except ValueError:                                           # a record of N only
+                st, d_idx = 0, None
+            n = max(int(d_idx.numel()) - 1, 0) if d_idx is not None else 0
+            if n - (int(vecsize) if vecsize is not None else 0) < 1:
+                _LOG.warning("%s: record %r keeps %d bases: no window%s fits, it is left out", path, name, n,
+                             f" of {vecsize}" if vecsize is not None else "")
+                continue
+            names.append(name)
+            parts.append(d_idx[:n])
+            lengths.append(n)
+            startpos.append(int(st))
+        select_contigs(found, contigs, str(path))                        # names the absent and the duplicated
+        if not parts:
+            raise ValueError(f"{path}: no window of {vecsize if vecsize is not None else 1} fits into a selected record")
+        rows = read_truth_rows(bedfile, names, repeats_to_search)
+        classes = len(repeats_to_search) + 1
+        d_idx = torch.cat(parts)
+        del parts
+        ln = np.asarray(lengths, np.int64)
+        base = np.zeros(len(ln) + 1, np.int64)
+        np.cumsum(ln, out=base[1:])
+        n_total = int(base[-1])
+        org = np.asarray(startpos, np.int64)
+        row_off = np.zeros(len(ln) + 1, np.int64)
+        np.cumsum([len(rows[nm]) for nm in names], out=row_off[1:])
+        flat = np.concatenate([rows[nm] for nm in names])
+        dev = d_idx.device
+        d_rows = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
+        d_truth = torch.empty((classes, n_total), dtype=torch.int8, device=dev)
+        L = _lib.lib()
+        wb = L.dgrp_truth_workspace_bytes(len(ln), int(row_off[-1]))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.dgrp_truth_multihot_batch(d_truth.data_ptr(), classes, n_total, len(ln), base.ctypes.data, ln.ctypes.data,
+                                               org.ctypes.data, d_rows.data_ptr() if d_rows is not None else None,
+                                               row_off.ctypes.data, work.data_ptr(), wb, stream_ptr()), "dgrp_truth_multihot_batch")
+        return cls(d_idx, d_truth, names, base[:-1], ln, org)
+
+
+def draw_picks(rng: np.random.Generator, sizes: List[int], windows: int, batch_size: int, one_class_size: int) -> np.ndarray:
+    """One batch of fetch_batch as (set, rank) pairs, int64 [batch_size, 2], drawn from `rng` exactly as fetch_batch draws: for every
+    set (of `sizes[i]` starts, each larger than `one_class_size`) ``integers(0, size, one_class_size)`` -- what
+    ``choice(indices, one_class_size)`` draws --, then ``integers(0, windows, rest)`` with set -1 for the uniform part, then one
+    ``shuffle`` of the batch's order (a shuffle depends on the length alone)."""
+    picks = np.empty((batch_size, 2), np.int64)
+    q, filled = one_class_size, one_class_size * len(sizes)
+    for i, size in enumerate(sizes):
+        picks[q * i:q * (i + 1), 0] = i
+        picks[q * i:q * (i + 1), 1] = rng.integers(0, size, q)
+    picks[filled:, 0] = -1
+    picks[filled:, 1] = rng.integers(0, windows, size=batch_size - filled)
+    order = np.arange(batch_size)
+    rng.shuffle(order)
+    return picks[order]
+
+
+class DeviceSampler:
+    """fetch_batch on a DeviceData: the same draws from `rng` in the same order -- per class whose index set is larger than
+    ``one_class_size`` that many RANKS into the set, then the uniform rest as ranks into the windows of all records, then one
+    shuffle -- and the device resolves (set, rank) to start positions (dgrp_train_resolve_starts).  The sets are built on the device
+    for this sampler's `vecsize` (dgrp_class_window_starts) and stay there; only their sizes come back.  For one record the starts
+    are fetch_batch's, batch for batch."""
+
+    def __init__(self, options: Options, data: DeviceData, rng: Optional[np.random.Generator] = None):
+        import torch
+
+        from . import _lib
+        from .pipeline import stream_ptr
+        self._torch, self._lib, self._stream = torch, _lib, stream_ptr
+        self.rng = np.random.default_rng() if rng is None else rng
+        self.data = data
+        T, classes = int(options.vecsize), data.classes
+        self.batch_size = int(options.batch_size)
+        self.one_class_size = int(options.batch_size * options.repeat_probability / (classes - 1))
+        windows = np.maximum(data.lengths - T, 0)
+        wprefix = np.zeros(len(windows) + 1, np.int64)
+        np.cumsum(windows, out=wprefix[1:])
+        self.windows = int(wprefix[-1])
+        if self.windows < 1:
+            raise ValueError(f"the record{'s have' if len(windows) > 1 else ' has'} {', '.join(str(int(x)) for x in data.lengths)} "
+                             f"bases: no window of {T} fits")
+        L, dev = _lib.lib(), data.d_idx.device
+        nrec = len(data.lengths)
+        wb = L.dgrp_class_starts_workspace_bytes(nrec, data.n)
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        count = C.c_int64(0)
+
+        def starts_of(c: int, d_out, cap: int) -> int:
+            _lib.check(L.dgrp_class_window_starts(data.d_truth[c].data_ptr(), data.n, nrec, data.base.ctypes.data,
+                                                  data.lengths.ctypes.data, T, d_out.data_ptr() if d_out is not None else None, cap,
+                                                  C.byref(count), work.data_ptr(), wb, stream_ptr()), "dgrp_class_window_starts")
+            return int(count.value)
+
+        self.sets, self.sizes = [], []
+        for c in range(1, classes):
+            size = starts_of(c, None, 0)
+            if size > self.one_class_size:                               # (fetch_batch leaves a class with fewer indices out)
+                d_set = torch.empty(size, dtype=torch.int64, device=dev)
+                starts_of(c, d_set, size)
+                self.sets.append(d_set)
+                self.sizes.append(size)
+        table = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int64)).to(dev)
+        self._set_ptr = table([t.data_ptr() for t in self.sets] or [0])
+        self._set_size = table(self.sizes or [0])
+        self._base, self._wprefix = table(data.base), table(wprefix)
+
+    def batches(self) -> Iterator[Any]:
+        """Device tensors int64 [batch_size] of start positions into the side's buffer, one per batch, without end."""
+        torch, L = self._torch, self._lib.lib()
+        B = self.batch_size
+        while True:
+            picks = draw_picks(self.rng, self.sizes, self.windows, B, self.one_class_size)
+            d_picks = torch.from_numpy(picks).to(self._base.device)
+            d_starts = torch.empty(B, dtype=torch.int64, device=self._base.device)
+            self._lib.check(L.dgrp_train_resolve_starts(d_picks.data_ptr(), B, self._set_ptr.data_ptr(), self._set_size.data_ptr(),
+                                                        len(self.sets), self._base.data_ptr(), self._wprefix.data_ptr(),
+                                                        len(self.data.lengths), d_starts.data_ptr(), self._stream()),
+                            "dgrp_train_resolve_starts")
+            yield d_starts
+
+
+def _batches(options: Options, data, rng: np.random.Generator):
+    """The batch iterator of one side: fetch_batch on the host for a preprocessing.Data, the rank sampler for a DeviceData."""
+    if isinstance(data, DeviceData):
+        return DeviceSampler(options, data, rng).batches()
+    return fetch_batch(options, data, rng)()
+
+
 # ------------------------------------------------------------------------------------------------ loop
 class _Run:
     """One model of training_multi: its generator, samplers, trainer, history file and early-stopping state."""
@@ -259,8 +563,8 @@ class _Run:
         self.options, self.logdir = options, logdir
         os.makedirs(logdir, exist_ok=True)
         self.rng = np.random.default_rng(seed)
-        self.batches = fetch_batch(options, data[0], self.rng)()
-        self.val_batches = fetch_batch(options, data[1], self.rng)()
+        self.batches = _batches(options, data[0], self.rng)
+        self.val_batches = _batches(options, data[1], self.rng)
         self.trainer = DeviceTrainer(weights, options.vecsize, options.batch_size)
         self.config = keras_config(options.vecsize, options.units, classes, bool(options.attention), float(options.dropout))
         self.losses = torch.empty(max(1, int(options.n_batches)) + 1, dtype=torch.float32, device="cuda")
@@ -307,14 +611,15 @@ class _Run:
         return self.best_weights
 
 
-def training_multi(data: Tuple[preprocessing.Data, preprocessing.Data], options_list, weights_list, logdirs, seeds,
+def training_multi(data: Tuple[Any, Any], options_list, weights_list, logdirs, seeds,
                    log: Optional[Callable[[str], None]] = None) -> List[Dict[str, Any]]:
     """Trains ``len(options_list)`` models side by side on the same data: per step ONE dgrp_train_step_multi over the models still
     running (slices of DGRP_TRAIN_MAX_JOBS), then their optimizer steps; per epoch one loss-only multi step over their validation
     batches.  A model has its own units, vecsize, attention, batch_size, optimizer and hyper-parameters, its own generator
     ``default_rng(seeds[k])``, sampler, dropout masks, early stopping, ``history.tsv`` and model files in ``logdirs[k]``; only
-    `n_batches` and `n_epochs` must agree.  A model that stops early leaves the step and the others go on.  The two records are
-    uploaded once.  Element k of the result, and the files in logdirs[k], are byte for byte those of
+    `n_batches` and `n_epochs` must agree.  A model that stops early leaves the step and the others go on.  Each side of `data` is a
+    preprocessing.Data (uploaded once, sampled by fetch_batch on the host) or a DeviceData (resident; every model builds the index
+    sets of its own vecsize on the device).  Element k of the result, and the files in logdirs[k], are byte for byte those of
     ``training(data, options_list[k], weights_list[k], logdirs[k], seed=seeds[k])``: a job's bytes do not depend on its cohort."""
     count = len(options_list)
     if not (len(weights_list) == len(logdirs) == len(seeds) == count) or count < 1:
@@ -328,10 +633,11 @@ def training_multi(data: Tuple[preprocessing.Data, preprocessing.Data], options_
     for options in options_list:
         classes = len(options.repeats_to_search) + 1
         for d in data:
-            if d.truelbl.shape[0] != classes:
-                raise ValueError(f"truth of {d.truelbl.shape[0]} rows, {classes} expected from repeats_to_search")
+            rows = d.classes if isinstance(d, DeviceData) else d.truelbl.shape[0]
+            if rows != classes:
+                raise ValueError(f"truth of {rows} rows, {classes} expected from repeats_to_search")
     say = log or _LOG.info
-    records = [DeviceRecord.from_data(d) for d in data]
+    records = [d if isinstance(d, DeviceData) else DeviceRecord.from_data(d) for d in data]
     runs: List[Optional[_Run]] = [None] * count
     results: List[Optional[Dict[str, Any]]] = [None] * count
     try:
@@ -361,7 +667,7 @@ def training_multi(data: Tuple[preprocessing.Data, preprocessing.Data], options_
     return results
 
 
-def training(data: Tuple[preprocessing.Data, preprocessing.Data], options: Options, model_weights: Dict[str, Any], logdir,
+def training(data: Tuple[Any, Any], options: Options, model_weights: Dict[str, Any], logdir,
              seed: Optional[int] = None, log: Optional[Callable[[str], None]] = None) -> Dict[str, Any]:
     """Runs training (deepgrp/training.py:15-73): `n_epochs` epochs of `n_batches` steps on data[0]; after each epoch the loss of
     one batch of data[1] without dropout.  An epoch whose validation loss improves writes ``<logdir>/<epoch:02d>.hdf5``

@@ -788,6 +788,49 @@ int dgrp_train_step_multi(const dgrp_train_job *h_jobs, int K, void *stream);
 int dgrp_optimizer_step(int kind, float *d_params, const float *d_grads, float *d_state1, float *d_state2, int64_t count,
                         double learning_rate, double rho, double momentum, double epsilon, int64_t step, void *stream);
 
+/* ---- training data from a sequence file (an addition; the reference prepares these on the host from a one-hot .npz:
+ * deepgrp/preprocessing.py:9-70 and deepgrp/training.py:76-132).  A SIDE is the kept records of a file back to back in one buffer of
+ * n_total bases: record r is [h_off[r], h_off[r] + h_len[r]), h_len[r] = its bases from the first to the last non-N WITHOUT the last
+ * one (drop_start_end_n), and its first base has the original coordinate h_origin[r].  All three entries work on the caller's stream
+ * and allocate nothing.
+ *
+ * The truth entry writes EVERY byte of d_truth, int8 [C, n_total] (16-byte aligned), the multi-hot truth of preprocess_y: record r's
+ * rows are d_rows[h_row_off[r] .. h_row_off[r+1]) (device; ORIGINAL coordinates, any order, overlapping or not, clipped to the
+ * record); d_truth[label, b .. e) = 1 for every row, so two classes on one base give two ones, and d_truth[0, j] = 1 where no row
+ * covers j (also outside every record).  Every row must satisfy 0 <= start <= end and 1 <= label <= C - 1: a bad row gives
+ * DGRP_EINVAL naming it BEFORE any byte of d_truth is written (the check runs on the device and synchronises the stream once; without
+ * rows nothing synchronises).  Then: rows 1 .. C-1 cleared, one length-balanced paint pass over all rows (the painter of the evaluate
+ * entries: 8192 positions per workgroup, every store a 1 on the row's own class row), one pass that writes row 0 from the others.
+ * Plain stores, no atomics on d_truth: the same call gives the same bytes.  2 <= C <= 64.  Workspace (256-byte aligned) of the
+ * bytes the companion below returns, DGRP_ENOMEM when smaller. */
+int64_t dgrp_truth_workspace_bytes(int64_t nrec, int64_t nrows);
+int dgrp_truth_multihot_batch(int8_t *d_truth, int C, int64_t n_total, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                              const int64_t *h_origin, const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work,
+                              int64_t work_bytes, void *stream);
+
+/* The class-set entry: the window starts of ONE class row d_row [n_total] (a row of d_truth) for windows of T bases, 1 <= T <= 4096.
+ * Start s of record r is a member when 1 <= s <= h_len[r] - 1 - T and d_row holds a non-zero byte in [s + 1, s + T] of the record
+ * -- exactly _calc_indices(row of the record, T); the bytes tested are the record's own.  The members are written ascending as int64
+ * BUFFER positions h_off[r] + s, records in order, to d_starts[0 .. *h_count).  The entry SYNCHRONISES the stream once, to return
+ * the count in *h_count.  d_starts NULL: count only.  A count above `cap`: DGRP_ENOMEM, *h_count = the capacity needed, d_starts
+ * untouched.  A workgroup takes 8192 starts: it stages their 8191 + T bytes in LDS, counts them into a prefix, and a start is a
+ * member when the prefix moves over its window; one pass counts per workgroup, the counts are scanned, a second pass writes.
+ * Workspace (256-byte aligned) of the bytes the companion below returns. */
+int64_t dgrp_class_starts_workspace_bytes(int64_t nrec, int64_t n_total);
+int dgrp_class_window_starts(const int8_t *d_row, int64_t n_total, int64_t nrec, const int64_t *h_off, const int64_t *h_len, int T,
+                             int64_t *d_starts, int64_t cap, int64_t *h_count, void *d_work, int64_t work_bytes, void *stream);
+
+/* The resolve entry: d_starts[i] (int64, device) for the B picks d_picks [B, 2] int64 (device): (set, rank).  Set k in [0, nsets)
+ * is the ascending array d_set_ptr[k] of d_set_size[k] starts (device tables of device pointers and sizes; what the class-set entry
+ * wrote); the start is its element `rank`.  Any other set, or an empty one, is the uniform part: with W_r = max(h_len[r] - T, 0),
+ * d_wprefix [nrec + 1] the exclusive prefix sums of W_r and d_base[r] = h_off[r], rank k of [0, W) is d_base[r] + k - d_wprefix[r]
+ * for the record with d_wprefix[r] <= k < d_wprefix[r + 1] (binary search).  A rank outside its range is clamped into it; with
+ * W = 0 the start is 0: no access leaves the arrays.  Stream-ordered: nothing synchronises, copies or allocates.  1 <= B <= 2^18,
+ * 0 <= nsets <= 64, nrec >= 1. */
+int dgrp_train_resolve_starts(const int64_t *d_picks, int64_t B, const int64_t *const *d_set_ptr, const int64_t *d_set_size,
+                              int nsets, const int64_t *d_base, const int64_t *d_wprefix, int64_t nrec, int64_t *d_starts,
+                              void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
