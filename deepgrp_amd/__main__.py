@@ -326,6 +326,13 @@ class CommandLineParser:
                                    "carries its class on the other side, in (0, 1]")
         evaluate.add_argument("--output", type=str, default="-", help="TSV report ('-' = standard output)")
         evaluate.add_argument("--json", type=str, default=None, help="also write every figure as JSON here")
+        evaluate.add_argument("--curves", type=str, default=None, metavar="PREFIX",
+                              help="also write threshold curves: PREFIX.bases.tsv (per class and probability threshold k/bins: TP, FP, "
+                                   "FN, TN, TPR, FPR, PPV, F1 of calling a base that class when its probability reaches the threshold) "
+                                   "and PREFIX.rows.tsv (per class and --bed_min_score 0..1000: the predicted rows kept, those the "
+                                   "annotation supports, their ratio); --json gains the key `curves` (AUROC, average precision, best F1)")
+        evaluate.add_argument("--curve_bins", type=int, default=None,
+                              help="probability bins of --curves, 2..4096 (default with --curves: 1000)")
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
@@ -853,6 +860,8 @@ class CommandLineParser:
         refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
+        from . import curves as dgcurves
+        curve_plan = dgcurves.plan(args)
         import json
 
         from . import model as dgmodel
@@ -875,10 +884,13 @@ class CommandLineParser:
                     options=dict(step_size=args.step_size, min_mss_length=args.min_mss_length, xdrop_length=args.xdrop_length,
                                  batch_size=args.batch_size, use_mss=not args.no_use_mss, fast=bool(args.fast),
                                  min_overlap=args.min_overlap))
+        curves = dgcurves.Curves(classes, curve_plan.bins) if curve_plan is not None else None
         try:
-            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info)
+            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves)
         except NoMatchError as e:
             sys.exit(str(e))
+        if curves is not None:
+            curves.write(curve_plan, _LOG)
         text = tsv_report(rep)
         if args.output == "-":
             sys.stdout.write(text)

@@ -1,0 +1,215 @@
+"""`evaluate --curves`: what a threshold does to precision and recall, from integer counts alone.
+
+Base curves.  Per class c the device counts the merged probability P[b, c] of every evaluated base into `bins` bins, split by whether
+the base's truth is c (dgrp_prob_hist_batch; `reference_hist` is its numpy statement): bin k = min(bins - 1, int(float32(p) *
+float32(bins))).  Threshold k / bins means "call the base class c if its bin is >= k"; TP, FP, FN, TN of every threshold are suffix
+sums of the two histograms, every rate a ratio of those integers (float64 only there, NaN where a denominator is 0).
+
+Row curves answer "what does `predict --bed_min_score m` keep": per class and m = 0..1000 the predicted rows whose BED score is at
+least m (`segments`), those of them the annotation supports by `evaluate`'s --min_overlap rule (`supported`), and their ratio.
+
+Everything here is numpy over int64; the same counts give the same file bytes."""
+from __future__ import annotations
+
+import math
+import os
+import sys
+from typing import Dict, List, NamedTuple, Optional
+
+import numpy as np
+
+MIN_BINS, MAX_BINS, DEFAULT_BINS = 2, 4096, 1000
+SCORES = 1001                                       # BED scores 0..1000
+BASES_HEADER = ("class", "threshold", "TP", "FP", "FN", "TN", "TPR", "FPR", "PPV", "F1")
+ROWS_HEADER = ("class", "min_score", "segments", "supported", "precision")
+
+
+class CurvePlan(NamedTuple):
+    prefix: str
+    bins: int
+    bases_path: str
+    rows_path: str
+
+
+def plan(args) -> Optional[CurvePlan]:
+    """--curves and --curve_bins, or None without the flag.  Every refusal is made here (sys.exit), before the model is read or the
+    GPU is touched."""
+    prefix = getattr(args, "curves", None)
+    bins = getattr(args, "curve_bins", None)
+    if prefix is None:
+        if bins is not None:
+            sys.exit("--curve_bins needs --curves")
+        return None
+    bins = DEFAULT_BINS if bins is None else bins
+    if not MIN_BINS <= bins <= MAX_BINS:
+        sys.exit(f"--curve_bins must lie in {MIN_BINS}..{MAX_BINS}, not {bins}")
+    if prefix == "" or prefix.endswith(os.sep):
+        sys.exit(f"--curves takes a file name prefix, not the directory {prefix!r}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("--curves runs in one process (WORLD_SIZE > 1 is not supported: the histograms are summed on the rank that holds "
+                 "the merged probabilities)")
+    where = os.path.dirname(prefix) or "."
+    if not os.path.isdir(where):
+        sys.exit(f"--curves: the directory {where} does not exist")
+    paths = (prefix + ".bases.tsv", prefix + ".rows.tsv")
+    for f in getattr(args, "FASTA", []):
+        for out in paths:
+            if f != "-" and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
+                sys.exit(f"--curves: the file {out} would overwrite the input {f}")
+    return CurvePlan(prefix, int(bins), *paths)
+
+
+def bin_index(p: np.ndarray, bins: int) -> np.ndarray:
+    """The bin of float32 probabilities in [0, 1]: one float32 product, truncated, the last bin closed at 1."""
+    k = (np.asarray(p, np.float32) * np.float32(bins)).astype(np.int64)
+    return np.minimum(k, bins - 1)
+
+
+def reference_hist(probs: np.ndarray, truth: np.ndarray, bins: int):
+    """dgrp_prob_hist_batch's statement in numpy for the bases of any number of records laid back to back: `probs` float32 [n, C],
+    `truth` int8 [n] -> (hist int64 [C, 2, bins], flag).  hist[c, 1] counts the bases whose truth is c, hist[c, 0] the others.  A
+    NaN or a probability outside [0, 1] raises the flag and is not counted; a truth outside 0..C-1 raises it and none of the base's
+    elements is."""
+    probs = np.asarray(probs, np.float32)
+    n, C = probs.shape
+    truth = np.asarray(truth).astype(np.int64).reshape(n)
+    hist = np.zeros((C, 2, bins), np.int64)
+    with np.errstate(invalid="ignore"):
+        good_t = (truth >= 0) & (truth < C)
+        good_p = (probs >= 0) & (probs <= 1)                     # (NaN compares false; -0.0 compares equal to 0)
+        good = good_p & good_t[:, None]
+        k = bin_index(np.where(good, probs, np.float32(0)), bins)
+    for c in range(C):
+        for side in (0, 1):
+            sel = good[:, c] & ((truth == c) == bool(side))
+            hist[c, side] = np.bincount(k[sel, c], minlength=bins)
+    return hist, int(not good.all())
+
+
+def _ratio(num: np.ndarray, den: np.ndarray) -> np.ndarray:
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    out = np.full(np.broadcast(num, den).shape, np.nan)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+def base_curves(hist: np.ndarray) -> Dict[str, np.ndarray]:
+    """TP, FP, FN, TN (int64 [C, bins]) and TPR, FPR, PPV, F1 (float64, NaN where a denominator is 0) of every class and threshold
+    index k: the base is called c when its bin is >= k."""
+    hist = np.asarray(hist, np.int64)
+    tp = hist[:, 1, ::-1].cumsum(axis=1)[:, ::-1]
+    fp = hist[:, 0, ::-1].cumsum(axis=1)[:, ::-1]
+    fn, tn = tp[:, :1] - tp, fp[:, :1] - fp
+    return dict(TP=tp, FP=fp, FN=fn, TN=tn, TPR=_ratio(tp, tp + fn), FPR=_ratio(fp, fp + tn), PPV=_ratio(tp, tp + fp),
+                F1=_ratio(2 * tp, 2 * tp + fp + fn))
+
+
+def summaries(hist: np.ndarray) -> Dict[str, List[float]]:
+    """Per class: auroc (trapezoids over the (FPR, TPR) points from (0, 0) at k = bins down to k = 0), average_precision (sum over
+    k of (TPR[k] - TPR[k+1]) * PPV[k], TPR[bins] = 0, thresholds that call nothing skipped), best_f1 and best_threshold (the lowest
+    k / bins that reaches it).  auroc is NaN where a class has no positive or no negative base, average_precision where it has no
+    positive one, best_f1 and best_threshold where F1 is NaN at every threshold (no base at all)."""
+    hist = np.asarray(hist, np.int64)
+    C, _two, bins = hist.shape
+    cv = base_curves(hist)
+    out = dict(auroc=[], average_precision=[], best_f1=[], best_threshold=[])
+    for c in range(C):
+        tp = [int(x) for x in cv["TP"][c]] + [0]
+        fp = [int(x) for x in cv["FP"][c]] + [0]
+        pos, neg = tp[0], fp[0]
+        # twice the area in units of 1 / (pos * neg): an exact integer
+        area2 = sum((fp[k] - fp[k + 1]) * (tp[k] + tp[k + 1]) for k in range(bins))
+        out["auroc"].append(area2 / (2 * pos * neg) if pos and neg else float("nan"))
+        if pos:
+            terms = [(tp[k] - tp[k + 1]) * tp[k] / (tp[k] + fp[k]) for k in range(bins) if tp[k] + fp[k]]
+            out["average_precision"].append(math.fsum(terms) / pos)
+        else:
+            out["average_precision"].append(float("nan"))
+        f1 = cv["F1"][c]
+        if np.isnan(f1).all():
+            out["best_f1"].append(float("nan"))
+            out["best_threshold"].append(float("nan"))
+        else:
+            k = int(np.nanargmax(f1))                            # (the first maximum: the lowest k on a tie)
+            out["best_f1"].append(float(f1[k]))
+            out["best_threshold"].append(k / bins)
+    return out
+
+
+def row_scores_of(scores: np.ndarray) -> np.ndarray:
+    """The integer 0..1000 `bed.py` prints for each scored row (pipeline.ROW_SCORE_DTYPE, bases > 0)."""
+    from .bed import _half_up
+    return np.fromiter((_half_up(int(s), int(b) << 24, 1000) for s, b in zip(scores["sum"], scores["bases"])), np.int64, count=len(scores))
+
+
+def row_counts(labels: np.ndarray, score: np.ndarray, kept: np.ndarray, supported: np.ndarray, classes: int):
+    """Rows by class and score: -> (kept rows, supported rows), int64 [classes, 1001] each, NOT yet cumulated.  `kept`: the row has a
+    base inside its record; `supported`: it is kept and passes the --min_overlap rule."""
+    seg = np.zeros((classes, SCORES), np.int64)
+    sup = np.zeros((classes, SCORES), np.int64)
+    np.add.at(seg, (labels[kept], score[kept]), 1)
+    np.add.at(sup, (labels[supported], score[supported]), 1)
+    return seg, sup
+
+
+def row_curves(seg: np.ndarray, sup: np.ndarray):
+    """segments_at[c, m] and supported_at[c, m]: the rows of `row_counts` with score >= m."""
+    at = lambda x: np.asarray(x, np.int64)[:, ::-1].cumsum(axis=1)[:, ::-1]
+    return at(seg), at(sup)
+
+
+_f = lambda x: repr(float(x))                                    # floats as `evaluate` prints them ('nan' for NaN)
+
+
+def bases_tsv(hist: np.ndarray) -> str:
+    hist = np.asarray(hist, np.int64)
+    C, _two, bins = hist.shape
+    cv = base_curves(hist)
+    lines = ["#" + "\t".join(BASES_HEADER)]
+    for c in range(C):
+        for k in range(bins):
+            lines.append("\t".join([str(c), repr(k / bins)] + [str(int(cv[x][c, k])) for x in ("TP", "FP", "FN", "TN")]
+                                   + [_f(cv[x][c, k]) for x in ("TPR", "FPR", "PPV", "F1")]))
+    return "\n".join(lines) + "\n"
+
+
+def rows_tsv(seg: np.ndarray, sup: np.ndarray) -> str:
+    seg_at, sup_at = row_curves(seg, sup)
+    prec = _ratio(sup_at, seg_at)
+    lines = ["#" + "\t".join(ROWS_HEADER)]
+    for c in range(1, seg_at.shape[0]):
+        for m in range(SCORES):
+            lines.append("\t".join([str(c), str(m), str(int(seg_at[c, m])), str(int(sup_at[c, m])), _f(prec[c, m])]))
+    return "\n".join(lines) + "\n"
+
+
+class Curves:
+    """The counts of one `evaluate --curves` run, summed over its work items."""
+
+    def __init__(self, classes: int, bins: int = DEFAULT_BINS):
+        if not MIN_BINS <= int(bins) <= MAX_BINS:
+            raise ValueError(f"bins must lie in {MIN_BINS}..{MAX_BINS}, not {bins}")
+        self.C, self.bins = int(classes), int(bins)
+        self.hist = np.zeros((self.C, 2, self.bins), np.int64)
+        self.seg = np.zeros((self.C, SCORES), np.int64)
+        self.sup = np.zeros((self.C, SCORES), np.int64)
+
+    def summary(self) -> Dict[str, object]:
+        """The `curves` key of the JSON report (NaN as None)."""
+        num = lambda x: None if math.isnan(x) else x
+        out: Dict[str, object] = dict(bins=self.bins)
+        out.update({k: [num(x) for x in v] for k, v in summaries(self.hist).items()})
+        return out
+
+    def write(self, p: CurvePlan, log) -> None:
+        """Both files, staged: a failure leaves neither, nor a temporary file."""
+        from .outfiles import StagedFile, StagedOutputs
+        texts = (bases_tsv(self.hist), rows_tsv(self.seg, self.sup))
+        out = StagedOutputs(log, p.prefix, "--curves", False, (StagedFile(f, "w") for f in (p.bases_path, p.rows_path)))
+        try:
+            for part, text in zip(out.parts, texts):
+                part.fh.write(text)
+        except BaseException:
+            out.abort()
+            raise
+        out.commit()

@@ -9,7 +9,11 @@ preprocess_y(...).argmax(axis=0).  Two deliberate differences from the reference
 last non-N base, and it runs filter_segments over the labels once more; here the TSV users get is measured as it is.
 
 Both label tracks are painted on the GPU from their rows (dgrp_paint_rows_batch) into flat buffers of the work item's records,
-scored by dgrp_confusion_matrix, and every row is counted against the other track (dgrp_row_hits_batch)."""
+scored by dgrp_confusion_matrix, and every row is counted against the other track (dgrp_row_hits_batch).
+
+With curves (`evaluate --curves`, deepgrp_amd/curves.py) the runner keeps the merged probabilities of every work item long enough
+for `Accumulator.probe`: it paints the item's truth on the worker's stream and counts every probability into per-class
+histograms split by truth (dgrp_prob_hist_batch); the rows' BED scores come with the rows (dgrp_row_scores_batch)."""
 from __future__ import annotations
 
 import logging
@@ -99,10 +103,11 @@ def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
 class Accumulator:
     """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
 
-    def __init__(self, classes: int, min_overlap: float):
+    def __init__(self, classes: int, min_overlap: float, curves=None):
         if not 0.0 < min_overlap <= 1.0:
             raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
         self.C, self.theta = int(classes), float(min_overlap)
+        self.curves = curves                           # a curves.Curves: probability histograms and rows by score are summed into it
         self.cnf = np.zeros((self.C, self.C), np.int64)
         self.elements = np.zeros(self.C, np.int64)
         self.found = np.zeros(self.C, np.int64)
@@ -110,16 +115,86 @@ class Accumulator:
         self.supported = np.zeros(self.C, np.int64)
         self.bases = self.records = self.records_annotated = self.rows_used = self.outside = 0
 
-    def _count(self, labels: np.ndarray, clen: np.ndarray, hits: np.ndarray, total: np.ndarray, good: np.ndarray) -> None:
+    def _count(self, labels: np.ndarray, clen: np.ndarray, hits: np.ndarray, total: np.ndarray, good: np.ndarray):
+        """total[label] += 1 per row with a base inside its record, good[label] += 1 per such row with hits >= theta * its clipped
+        length; -> the two masks."""
         ok = clen > 0
         np.add.at(total, labels[ok], 1)
         hit = ok & (hits.astype(np.float64) >= self.theta * clen.astype(np.float64))
         np.add.at(good, labels[hit], 1)
+        return ok, hit
+
+    @staticmethod
+    def _tables(origins: Sequence[int], lengths: Sequence[int]):
+        """Records back to back in one flat buffer: -> (lengths, origins, offsets [nrec + 1]) as the library reads them."""
+        ln = np.ascontiguousarray(lengths, np.int64)
+        org = np.ascontiguousarray(origins, np.int64)
+        off = np.zeros(len(ln) + 1, np.int64)
+        np.cumsum(ln, out=off[1:])
+        return ln, org, off
+
+    @staticmethod
+    def _upload(rows: Sequence[np.ndarray], dev):
+        """The rows of the records as one device array: -> (row offsets [nrec + 1], the rows on the host, on the device or None)."""
+        import torch
+        ro = np.zeros(len(rows) + 1, np.int64)
+        np.cumsum([len(x) for x in rows], out=ro[1:])
+        flat = np.concatenate(rows) if ro[-1] else np.zeros(0, SEGMENT_DTYPE)
+        d = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
+        return ro, flat, d
+
+    @staticmethod
+    def _paint(ln: np.ndarray, org: np.ndarray, off: np.ndarray, ro: np.ndarray, d_rows, work, dev):
+        """A zeroed label track of the records with the rows painted on it, on the current stream (dgrp_paint_rows_batch)."""
+        import torch
+
+        from ._lib import check, lib
+        from .pipeline import stream_ptr
+        d_labels = torch.zeros(int(off[-1]), dtype=torch.int8, device=dev)
+        check(lib().dgrp_paint_rows_batch(d_labels.data_ptr(), len(ln), off.ctypes.data, ln.ctypes.data, org.ctypes.data,
+                                          None if d_rows is None else d_rows.data_ptr(), ro.ctypes.data, work.data_ptr(), work.numel(),
+                                          stream_ptr()), "dgrp_paint_rows_batch")
+        return d_labels
+
+    def probe(self, annotation: Dict[str, np.ndarray]):
+        """RecordRunner's probe for the curves: called on the worker's stream with the merged probabilities of a work item (record r:
+        rows [row0[r], row0[r] + lengths[r]) of d_probs; keys[r][1] its annotation contig), it paints the item's truth, counts the
+        histograms (dgrp_prob_hist_batch) and returns them with the flag as host arrays; `add` sums them."""
+        bins, empty = self.curves.bins, np.zeros(0, SEGMENT_DTYPE)
+
+        def run(d_probs, row0, lengths, startposes, keys):
+            import torch
+
+            from ._lib import check, lib
+            from .pipeline import require_gpu, stream_ptr
+            L = lib()
+            ln, org, off = self._tables(startposes, lengths)
+            nrec = len(ln)
+            hist = np.zeros((self.C, 2, bins), np.int64)
+            if nrec == 0 or int(off[-1]) == 0 or d_probs is None:
+                return hist, 0
+            if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous() or d_probs.shape[1] != self.C:
+                raise ValueError(f"the curves take a contiguous float32 [rows, {self.C}] array")
+            dev = require_gpu()
+            tr = [np.ascontiguousarray(annotation.get(k[1], empty), SEGMENT_DTYPE) for k in keys]
+            t_off, _flat, d_trows = self._upload(tr, dev)
+            work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(nrec, int(t_off[-1]))), int(L.dgrp_prob_hist_workspace_bytes(nrec, self.C, bins))),
+                               dtype=torch.uint8, device=dev)
+            d_true = self._paint(ln, org, off, t_off, d_trows, work, dev)
+            r0 = np.ascontiguousarray(row0, np.int64)
+            d_hist = torch.empty((self.C, 2, bins), dtype=torch.int64, device=dev)
+            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+            check(L.dgrp_prob_hist_batch(d_probs.data_ptr(), self.C, nrec, r0.ctypes.data, ln.ctypes.data, d_true.data_ptr(), off.ctypes.data,
+                                         bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), stream_ptr()),
+                  "dgrp_prob_hist_batch")
+            return d_hist.cpu().numpy(), int(d_bad.item())
+        return run
 
     def add(self, origins: Sequence[int], lengths: Sequence[int], pred_rows: Sequence[np.ndarray],
-            true_rows: Sequence[np.ndarray]) -> None:
+            true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = ()) -> None:
         """One work item: records r = 0.. with startpos origins[r], kept length lengths[r], the TSV rows `predict` wrote for it
-        (original coordinates) and its kept annotation rows."""
+        (original coordinates) and its kept annotation rows.  With curves also the scores of the predicted rows, record after record
+        (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names for its error."""
         import torch
 
         from ._lib import check, lib
@@ -128,11 +203,14 @@ class Accumulator:
         nrec = len(lengths)
         if nrec == 0:
             return
-        ln = np.ascontiguousarray(lengths, np.int64)
-        org = np.ascontiguousarray(origins, np.int64)
-        off = np.zeros(nrec + 1, np.int64)
-        np.cumsum(ln, out=off[1:])
+        ln, org, off = self._tables(origins, lengths)
         n = int(off[-1])
+        if self.curves is not None and probed is not None:
+            hist, flag = probed
+            if flag:
+                raise ValueError("a probability outside [0, 1] or a label outside 0..{} reached the probability histogram (record{} {})".format(
+                    self.C - 1, "s" if len(names) > 1 else "", ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else "")))
+            self.curves.hist += hist
         self.records += nrec
         self.bases += n
         self.records_annotated += sum(1 for t in true_rows if len(t))
@@ -144,26 +222,12 @@ class Accumulator:
         if n == 0:
             return
         dev = require_gpu()
-        d_true = torch.zeros(n, dtype=torch.int8, device=dev)
-        d_pred = torch.zeros(n, dtype=torch.int8, device=dev)
-
-        def upload(rows: List[np.ndarray]):
-            ro = np.zeros(nrec + 1, np.int64)
-            np.cumsum([len(x) for x in rows], out=ro[1:])
-            flat = np.concatenate(rows) if ro[-1] else np.zeros(0, SEGMENT_DTYPE)
-            d = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
-            return ro, flat, d
-
-        t_off, t_flat, d_trows = upload(tr)
-        p_off, p_flat, d_prows = upload(pr)
+        t_off, t_flat, d_trows = self._upload(tr, dev)
+        p_off, p_flat, d_prows = self._upload(pr, dev)
         wb = L.dgrp_eval_workspace_bytes(nrec, max(int(t_off[-1]), int(p_off[-1])))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
         s = stream_ptr()
         ptr = lambda t: None if t is None else t.data_ptr()
-
-        def paint(d_labels, ro, d_rows):
-            check(L.dgrp_paint_rows_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_rows),
-                                          ro.ctypes.data, work.data_ptr(), wb, s), "dgrp_paint_rows_batch")
 
         def hits(d_labels, ro, d_rows):
             d_hits = torch.zeros(max(int(ro[-1]), 1), dtype=torch.int64, device=dev)
@@ -171,8 +235,8 @@ class Accumulator:
                                         ro.ctypes.data, d_hits.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_hits_batch")
             return d_hits
 
-        paint(d_true, t_off, d_trows)
-        paint(d_pred, p_off, d_prows)
+        d_true = self._paint(ln, org, off, t_off, d_trows, work, dev)
+        d_pred = self._paint(ln, org, off, p_off, d_prows, work, dev)
         d_ht = hits(d_pred, t_off, d_trows)            # annotation rows against the predicted labels
         d_hp = hits(d_true, p_off, d_prows)            # predicted rows against the truth
         d_cnf = torch.empty((self.C, self.C), dtype=torch.int64, device=dev)
@@ -188,7 +252,16 @@ class Accumulator:
             self._count(t_flat["label"].astype(np.int64), np.concatenate(t_clen), ht, self.elements, self.found)
         if p_flat.size:
             p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(pr)])
-            self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
+            kept, good = self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
+            if self.curves is not None:
+                from .curves import row_counts, row_scores_of
+                if scores is None or len(scores) != len(p_flat):
+                    raise ValueError(f"{len(p_flat)} predicted rows but {0 if scores is None else len(scores)} scores")
+                sc = np.zeros(len(p_flat), np.int64)
+                sc[kept] = row_scores_of(scores[kept])
+                seg, sup = row_counts(p_flat["label"].astype(np.int64), sc, kept, good, self.C)
+                self.curves.seg += seg
+                self.curves.sup += sup
 
 
 def metrics_of(cnf: np.ndarray, bases: int) -> Dict[str, object]:
@@ -207,7 +280,7 @@ def _num(x) -> Optional[float]:
 
 def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
     """The JSON content: `info` (paths, options) plus counts, the confusion matrix, every metric (NaN as None) and the element
-    counts."""
+    counts; with curves also their summaries under `curves`."""
     m = metrics_of(acc.cnf, acc.bases)
     metrics = {}
     for k, v in m.items():
@@ -217,6 +290,8 @@ def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
                rows_used=int(acc.rows_used), outside=int(acc.outside), confusion_matrix=acc.cnf.astype(int).tolist(),
                metrics=metrics, min_overlap=acc.theta, elements=acc.elements.tolist(), found=acc.found.tolist(),
                segments=acc.segments.tolist(), supported=acc.supported.tolist())
+    if acc.curves is not None:
+        out["curves"] = acc.curves.summary()
     return out
 
 
@@ -257,16 +332,20 @@ def record_name(filename: str, header: str) -> str:
 
 
 def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
-             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None) -> Dict[str, object]:
+             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None) -> Dict[str, object]:
     """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
     `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
     content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
-    record read has none)."""
+    record read has none).  curves (a curves.Curves of the model's classes): the runner takes the merged path with scores and
+    `Accumulator.probe`, the counts of the curves are summed into it and the JSON content gains the key `curves`; without it a
+    record is the fused call, as before."""
     from .runner import RecordRunner
 
     classes = int(model.output_shape[2])
-    acc = Accumulator(classes, min_overlap)
-    runner = RecordRunner(pipe)
+    if curves is not None and curves.C != classes:
+        raise ValueError(f"curves of {curves.C} classes for a model of {classes}")
+    acc = Accumulator(classes, min_overlap, curves)
+    runner = RecordRunner(pipe) if curves is None else RecordRunner(pipe, scores=True, probe=acc.probe(annotation))
     empty = np.zeros(0, SEGMENT_DTYPE)
     seen_names: List[str] = []
     state = {"matched": False, "warned": False}
@@ -291,10 +370,13 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
                     state["warned"] = True
                     _LOG.warning("record %r of %s has no annotation rows; annotation contigs: %s", name, filename,
                                  ", ".join(repr(x) for x in sorted(annotation)[:5]) or "none with kept rows")
-                # the key carries what the evaluation needs past the runner: name, startpos, kept length
-                yield (name, startpos, length), rec
+                # the key carries what the evaluation needs past the runner: header, name (where a runner with scores reads a
+                # record's name), startpos, kept length
+                yield (header, name, startpos, length), rec
 
-    for kind, key, rows in runner.results(keyed()):
+    for out in runner.outputs(keyed()):
+        kind, key, rows, scores = out[:4]
+        probed = out[5] if curves is not None else None
         keys = key if kind == "batch" else [key]
         rows = np.asarray(rows)
         if kind == "batch":
@@ -303,7 +385,8 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
             pred = [rows[cut[r]:cut[r + 1]] for r in range(len(keys))]
         else:
             pred = [rows]
-        acc.add([k[1] for k in keys], [k[2] for k in keys], pred, [annotation.get(k[0], empty) for k in keys])
+        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, [annotation.get(k[1], empty) for k in keys], scores, probed,
+                [k[1] for k in keys])
     if acc.rows_used == 0:
         raise NoMatchError("no annotation row names a record of the inputs (records: {}; annotation: {})".format(
             ", ".join(repr(x) for x in seen_names) or "none",

@@ -25,6 +25,7 @@ class _One(NamedTuple):
     name: object
     rec: object
     chrom: int
+    key: object = None            # the record's key, for a runner with a probe
 
 
 class _Batch(list):
@@ -93,22 +94,29 @@ class RecordRunner:
     bed.BedWrite instead, made on the device where rows and scores then stay, and with a bigBed plan (--bed_bigbed) its
     bigbed.BigBedWrite, chromIds counted by the record's ordinal in its input.  With either, every key is (header, name), name
     the first column of the record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged
-    array; with neither, keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch)."""
+    array; with neither, keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch).
+    probe (a callable): called on the worker's stream while the merged array of a work item is alive, probe(d_probs, row0, lengths,
+    startposes, keys) -- record r is rows [row0[r], row0[r] + lengths[r]) of d_probs (None for a record without a base) -- and what it
+    returns travels with the item's result as one more field; it forces the merged path, as tracks and scores do."""
 
-    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None, scores: bool = False, bed=None):
+    def __init__(self, pipe: ContigPipeline, workers: int = 0, max_bases: int = 1 << 29, tracks=None, scores: bool = False, bed=None,
+                 probe=None):
         self.pipe = pipe
-        self.tracks, self.scores = tracks, bool(scores)
+        self.tracks, self.scores, self.probe = tracks, bool(scores), probe
         self.bed = bed if bed is not None and bed.gzip_level is not None else None     # --bed_gzip: a bed.BedWrite in the scores' place
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model
         self._T, self._UP = m.vecsize, (m.units + 31) // 32 * 32
 
-    # ---- one work item -> (rows, scores or None, texts or None)
-    def run_record(self, rec, name=None, chrom: int = 0):
-        """One record: the fused call, or merged -> [the texts of self.tracks] -> labels -> segments -> [the rows' scores], because
-        the fused call keeps its merged array inside its workspace."""
-        if self.tracks is None and not self.scores:
+    # ---- one work item -> (rows, scores or None, texts or None), with a probe also what it returned
+    def _fused(self) -> bool:
+        return self.tracks is None and not self.scores and self.probe is None
+
+    def run_record(self, rec, name=None, chrom: int = 0, key=None):
+        """One record: the fused call, or merged -> [the texts of self.tracks] -> [the probe] -> labels -> segments -> [the rows'
+        scores], because the fused call keeps its merged array inside its workspace."""
+        if self._fused():
             if isinstance(rec, DeviceRecord):             # parsed and encoded on the GPU
                 startpos, d_idx = record_indices(rec)
                 return self.pipe.run_idx(d_idx, startpos), None, None
@@ -121,26 +129,29 @@ class RecordRunner:
             if self.scores and self.bed is not None:
                 from .bed import empty_write
                 scores = empty_write(self.bed, name, startpos, chrom)
-            return (np.zeros(0, SEGMENT_DTYPE), scores, empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
+            out = (np.zeros(0, SEGMENT_DTYPE), scores, empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
+            return out if self.probe is None else out + (self.probe(None, [0], [0], [startpos], [key]),)
         merged = self.pipe.merged(d_idx)
         texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
+        probed = self.probe(merged, [0], [len(merged)], [startpos], [key]) if self.probe is not None else None
         rows = self.pipe.segments(self.pipe.labels(merged), startpos)
         scores = None
         if self.scores and self.bed is not None:
             scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed, chrom)
         elif self.scores:
             scores = self.pipe.row_scores(merged, startpos, rows)
-        return rows, scores, texts
+        return (rows, scores, texts) if self.probe is None else (rows, scores, texts, probed)
 
     def run_batch(self, batch: _Batch):
         """A batch: rows of all its records, contig = position in the batch; scores go row by row with them, texts[k] is the text of
         class self.tracks.classes[k] of all its records in order."""
         recs = [r for _k, r in batch]
         args = (recs[0].base, [r.offset for r in recs], [r.length for r in recs], [r.startpos for r in recs], list(range(len(recs))))
-        if self.tracks is None and not self.scores:
+        if self._fused():
             return self.pipe.run_batch(*args), None, None
         rows, d_probs, row0 = self.pipe.run_batch_probs(*args)
         ln = np.ascontiguousarray(args[2], np.int64)
+        probed = self.probe(d_probs, row0, ln, args[3], [k for k, _r in batch]) if self.probe is not None else None
         scores = texts = None
         if self.scores and self.bed is not None:
             scores = self.pipe.bed_write(d_probs, row0, ln, args[3], rows, self.pipe.batch_row_offsets(rows, args[4]),
@@ -150,10 +161,14 @@ class RecordRunner:
         if self.tracks is not None:
             texts = self.pipe.batch_track_texts(d_probs, row0, ln, args[3], [k[1] for k, _r in batch], self.tracks,
                                                 batch.chrom0 if self.tracks.bigwig else 0)
-        return rows, scores, texts
+        return (rows, scores, texts) if self.probe is None else (rows, scores, texts, probed)
 
     def run_item(self, item):
-        return self.run_batch(item) if isinstance(item, _Batch) else self.run_record(item.rec, item.name, item.chrom)
+        if isinstance(item, _Batch):
+            return self.run_batch(item)
+        if self.probe is None:
+            return self.run_record(item.rec, item.name, item.chrom)
+        return self.run_record(item.rec, item.name, item.chrom, item.key)
 
     # ---- batching
     def _batch_cost(self, n: int) -> int:
@@ -234,8 +249,8 @@ class RecordRunner:
 
     def outputs(self, records: Iterable[Tuple[object, object]]):
         """("one", key, rows, scores, texts) for a record on its own, ("batch", [keys], rows, scores, texts) for a batch of short
-        records (rows["contig"] indexes the keys); scores and texts are None where the runner was not asked for them.  Records
-        batch the same way whatever is asked for."""
+        records (rows["contig"] indexes the keys); scores and texts are None where the runner was not asked for them; with a probe a
+        sixth field holds what it returned for the item.  Records batch the same way whatever is asked for."""
         def items():
             chrom = 0                                     # records of this input so far
             for key, item in self.work_items(records):
@@ -243,12 +258,12 @@ class RecordRunner:
                     yield ("batch", [k for k, _r in item]), _Batch(item, chrom)
                     chrom += len(item)
                 else:
-                    yield ("one", key), _One(key[1] if self.tracks is not None or self.scores else None, item, chrom)
+                    yield ("one", key), _One(key[1] if self.tracks is not None or self.scores else None, item, chrom, key)
                     chrom += 1
         for head, result in self.in_order(items()):
             yield head + result
 
     def results(self, records: Iterable[Tuple[object, object]]):
         """`outputs` without scores and texts: ("one", key, rows) and ("batch", [keys], rows)."""
-        for kind, key, rows, _scores, _texts in self.outputs(records):
-            yield kind, key, rows
+        for out in self.outputs(records):
+            yield out[:3]

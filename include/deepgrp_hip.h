@@ -558,6 +558,29 @@ int dgrp_row_scores_batch(const float *d_probs, int C, int64_t nrec, const int64
                           const int64_t *h_startpos, const dgrp_segment *d_rows, const int64_t *h_row_off,
                           dgrp_row_score *d_scores, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- probability histograms (an addition, evaluate --curves): per class, the histogram of the merged probability over the
+ * evaluated bases, split by whether the base's truth is that class.  Every threshold curve is a function of these integers.
+ * Records as for dgrp_row_scores_batch: record r is rows [h_row0[r], h_row0[r] + h_n[r]) of d_probs [*, C] float32 (device); its
+ * truth is bytes [h_off[r], h_off[r] + h_n[r]) of d_truth (device int8, as dgrp_paint_rows_batch lays its records).
+ * For every base b of every record and every class c, with p = P[b, c] and t the base's truth byte:
+ *   k = min(bins - 1, (int)(p * (float)bins))   -- ONE float32 product rounded to nearest, truncated; no reciprocal, no double --
+ *   d_hist[c][t == c][k] += 1                    (d_hist: device int64 [C][2][bins], 8-byte aligned; -0.0 counts as 0)
+ * A probability that is NaN or outside [0, 1] sets *d_bad (device int) to 1 and that element is not counted; a truth byte outside
+ * 0..C-1 sets it too and none of the base's C elements is counted.  The call still returns DGRP_OK (dgrp_confusion_matrix's
+ * convention).  d_hist and *d_bad are zeroed here on every call; sums are integers (32-bit counters in LDS, sized so that none can
+ * wrap, flushed with 64-bit atomic adds): two calls give the same bytes.  Stream-ordered throughout: nothing synchronises.
+ * The kernel reads the flat array once, 4 C + 1 bytes per base, while the classes' counters fit the LDS of one workgroup:
+ * C * (8 * bins + 512) + 4096 <= 163840 (C <= 18 at 1000 bins, C <= 4 at 4096); beyond that the classes are cut into the largest
+ * groups that fit, and every group reads the array.
+ * DGRP_EINVAL before any device work unless 1 <= C <= 64, 2 <= bins <= 4096, nrec >= 0, every h_row0[r], h_n[r], h_off[r] in
+ * [0, 2^40), d_hist and d_bad non-NULL, d_hist 8-byte aligned and -- where some record has a base -- d_probs, d_truth and d_work
+ * non-NULL and work_bytes >= dgrp_prob_hist_workspace_bytes(nrec, C, bins) (0 for arguments outside the envelope).  nrec == 0 or
+ * no base: d_hist and *d_bad are zeroed, nothing else runs. */
+int64_t dgrp_prob_hist_workspace_bytes(int64_t nrec, int C, int bins);
+int dgrp_prob_hist_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                         const int8_t *d_truth, const int64_t *h_off, int bins, int64_t *d_hist, int *d_bad,
+                         void *d_work, int64_t work_bytes, void *stream);
+
 /* The scored rows as BED text (host code, host buffers): per row "name\tstart\tend\tclass<label>\tscore\t.\tmean\tmin\tagree\n".
  * name i = bytes [name_off[i], name_off[i+1]) of `names`; a row takes name rows[r].contig if by_contig != 0, else name 0 (the rule
  * of dgrp_format_rows).  With R(num, den, k) = floor((2 k num + den) / (2 den)), integer round-half-up evaluated in 128 bits:
