@@ -10,7 +10,7 @@
 //   * dgrp_track_zoom_batch: the bin pass, then level 0 (one lane per window of 16 bins, integer summaries), nine reductions four to
 //     one, a count of the windows with a covered base, one scan, and the 32-byte records with their block table.  Every (class,
 //     level) segment of the window space starts at a multiple of 256 windows, so the scanned tile counts at the segment starts are
-//     the segment boundaries.
+//     the segment boundaries.  Everything behind level 0 but the totals is the ladder of bbi_zoom.h, which bigbed_kernels.hip shares.
 //   * dgrp_zlib_compress_batch: the member kernels of deflate_kernels.hip on a table of blocks, then one workgroup per block frames
 //     the DEFLATE block as a zlib stream: the Adler-32 of the block from per-lane sums (a = sum of bytes, b = sum of (len - i) *
 //     byte, 64-bit, reduced modulo 65521 per lane and again after the tree), no serial walk.
@@ -21,6 +21,7 @@
 #include "deflate_blocks.h"
 #include "scan.h"
 #include "track_chain.h"
+#include "bbi_zoom.h"
 #include <string.h>
 #include <vector>
 
@@ -28,7 +29,6 @@ namespace {
 
 #define BW_SECTION_ITEMS 1024
 #define BW_MAX_END 0xffffffffll          // the largest coordinate of a bigWig
-#define BW_LEVELS DGRP_TRACK_ZOOM_LEVELS
 
 // (float)((double)v / (double)scale): the float32 a reader gets from the decimal text
 __device__ __forceinline__ float bw_value(uint64_t v, double scale) { return (float)((double)v / scale); }
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) bw_count_kernel(const uint32_t *__restric
     const int64_t tpc = G.NBpad / TRACK_TILE;
     const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
     if (threadIdx.x == 0) {
-        s_r0 = f0 < G.NB ? tb_record_of(pref, G.nrec, f0) : 0;
+        s_r0 = f0 < G.NB ? dgrp_record_of(pref, G.nrec, f0) : 0;
         s_own = 0;
     }
     __syncthreads();
@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) bw_write_kernel(const uint32_t *__restric
     __shared__ int64_t s_r0;
     const int64_t tpc = G.NBpad / TRACK_TILE;
     const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
-    if (threadIdx.x == 0) s_r0 = f0 < G.NB ? tb_record_of(pref, G.nrec, f0) : 0;
+    if (threadIdx.x == 0) s_r0 = f0 < G.NB ? dgrp_record_of(pref, G.nrec, f0) : 0;
     __syncthreads();
     const int64_t r0 = s_r0;
     const uint32_t *qk = q + k * G.NBpad;
@@ -195,22 +195,9 @@ __global__ void __launch_bounds__(256) bw_write_kernel(const uint32_t *__restric
 
 // ---------------------------------------------------------------------------------------------------------------------- zoom
 struct bwz_win { uint64_t s1, s2; uint32_t start, end, valid, qmin, qmax, pad; };     // a window's integer summary; valid 0: none
-struct bwz_levels {
-    int64_t R[BW_LEVELS];                // window width in bases
-    int64_t W[BW_LEVELS];                // windows of all records
-    int64_t seg[BW_LEVELS + 1];          // where the level's windows start in a class's window space (multiples of 256); [10]: its size
-};
-
-__device__ __forceinline__ bwz_win bwz_none()
-{
-    bwz_win w;
-    w.s1 = w.s2 = 0;
-    w.start = w.end = w.valid = w.qmin = w.qmax = w.pad = 0;
-    return w;
-}
 
 // a and b, every base of b above every base of a
-__device__ __forceinline__ bwz_win bwz_join(const bwz_win &a, const bwz_win &b)
+__device__ __forceinline__ bwz_win bbi_join(const bwz_win &a, const bwz_win &b)
 {
     if (a.valid == 0) return b;
     if (b.valid == 0) return a;
@@ -226,16 +213,34 @@ __device__ __forceinline__ bwz_win bwz_join(const bwz_win &a, const bwz_win &b)
     return w;
 }
 
+struct bwz_start {                       // a record's first base: its windows are numbered in the record's coordinates
+    const tb_rec *recs;
+    __device__ __forceinline__ int64_t operator()(int64_t r) const { return recs[r].offset; }
+};
+
+struct bwz_tail {                        // min, max, sum and sum of squares of a window's values: one double division each
+    double scale;
+    __device__ __forceinline__ uint4 operator()(const bwz_win &w) const
+    {
+        uint4 b;
+        b.x = __float_as_uint(bw_value(w.qmin, scale));
+        b.y = __float_as_uint(bw_value(w.qmax, scale));
+        b.z = __float_as_uint(bw_value(w.s1, scale));
+        b.w = __float_as_uint(bw_value(w.s2, scale * scale));
+        return b;
+    }
+};
+
 // level 0: one lane per window of 16 bins, from q
 __global__ void __launch_bounds__(256) bwz_level0_kernel(const uint32_t *__restrict__ q, const tb_rec *__restrict__ recs,
                                                          const int64_t *__restrict__ pref, const int64_t *__restrict__ wpref, tb_geom G,
-                                                         bwz_levels Z, bwz_win *__restrict__ win)
+                                                         bbi_levels Z, bwz_win *__restrict__ win)
 {
     const int64_t Wpad = Z.seg[1] - Z.seg[0], bpc = Wpad / 256;
     const int64_t k = blockIdx.x / bpc, i = ((int64_t)blockIdx.x % bpc) * 256 + threadIdx.x;
-    bwz_win w = bwz_none();
+    bwz_win w = bwz_win();
     if (i < Z.W[0]) {
-        const int64_t r = tb_record_of(wpref, G.nrec, i);
+        const int64_t r = dgrp_record_of(wpref, G.nrec, i);
         const tb_rec R = recs[r];
         const track_geom g = tb_geom_of(R, G.bin);
         const int64_t wi = R.offset / Z.R[0] + (i - wpref[r]);           // the window's number in the record's coordinates
@@ -261,63 +266,16 @@ __global__ void __launch_bounds__(256) bwz_level0_kernel(const uint32_t *__restr
             w.s2 += (uint64_t)v * v * bases;
         }
     }
-    win[k * Z.seg[BW_LEVELS] + Z.seg[0] + i] = w;
-}
-
-// level l >= 1 from level l - 1, four windows at a time
-__global__ void __launch_bounds__(256) bwz_reduce_kernel(const tb_rec *__restrict__ recs, const int64_t *__restrict__ wpref_all, int64_t nrec,
-                                                         bwz_levels Z, int l, bwz_win *__restrict__ win)
-{
-    const int64_t Wpad = Z.seg[l + 1] - Z.seg[l], bpc = Wpad / 256;
-    const int64_t k = blockIdx.x / bpc, i = ((int64_t)blockIdx.x % bpc) * 256 + threadIdx.x;
-    const int64_t *wp = wpref_all + (int64_t)l * (nrec + 1), *wc = wp - (nrec + 1);
-    bwz_win w = bwz_none();
-    if (i < Z.W[l]) {
-        const int64_t r = tb_record_of(wp, nrec, i);
-        const int64_t off = recs[r].offset;
-        const int64_t wi = off / Z.R[l] + (i - wp[r]);
-        const int64_t c0 = off / Z.R[l - 1], nc = wc[r + 1] - wc[r];     // the record's first window and windows one level down
-        const bwz_win *child = win + k * Z.seg[BW_LEVELS] + Z.seg[l - 1] + wc[r];
-        for (int64_t c = 4 * wi; c < 4 * wi + 4; ++c)
-            if (c >= c0 && c < c0 + nc) w = bwz_join(w, child[c - c0]);
-    }
-    win[k * Z.seg[BW_LEVELS] + Z.seg[l] + i] = w;
-}
-
-// windows with a covered base per tile of 256 windows (the window space of all classes)
-__global__ void __launch_bounds__(256) bwz_count_kernel(const bwz_win *__restrict__ win, uint64_t *__restrict__ tilecount)
-{
-    __shared__ uint64_t lds[4];
-    uint64_t s = win[(int64_t)blockIdx.x * 256 + threadIdx.x].valid != 0;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tilecount[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
-}
-
-// per (class, level) segment s = k * 10 + l: the records and the blocks in front of it, segb [2][nseg + 1] (also copied to the host)
-__global__ void __launch_bounds__(64) bwz_bounds_kernel(const uint64_t *__restrict__ tileoff, const uint64_t *__restrict__ grand, bwz_levels Z,
-                                                       int ncls, uint64_t *__restrict__ segb)
-{
-    if (threadIdx.x != 0) return;
-    const int nseg = ncls * BW_LEVELS;
-    const int64_t tpc = Z.seg[BW_LEVELS] / 256;
-    uint64_t blocks = 0;
-    for (int s = 0; s <= nseg; ++s) {
-        const uint64_t at = s < nseg ? tileoff[(int64_t)(s / BW_LEVELS) * tpc + Z.seg[s % BW_LEVELS] / 256] : *grand;
-        segb[s] = at;
-        if (s > 0) blocks += (at - segb[s - 1] + BW_SECTION_ITEMS - 1) / BW_SECTION_ITEMS;
-        segb[nseg + 1 + s] = blocks;
-    }
+    win[k * Z.seg[BBI_LEVELS] + Z.seg[0] + i] = w;
 }
 
 // the totals of every class from its top level (one workgroup per class)
-__global__ void __launch_bounds__(256) bwz_totals_kernel(const bwz_win *__restrict__ win, bwz_levels Z, dgrp_track_totals *__restrict__ totals)
+__global__ void __launch_bounds__(256) bwz_totals_kernel(const bwz_win *__restrict__ win, bbi_levels Z, dgrp_track_totals *__restrict__ totals)
 {
     __shared__ dgrp_track_totals part[4];
-    const bwz_win *top = win + (int64_t)blockIdx.x * Z.seg[BW_LEVELS] + Z.seg[BW_LEVELS - 1];
+    const bwz_win *top = win + (int64_t)blockIdx.x * Z.seg[BBI_LEVELS] + Z.seg[BBI_LEVELS - 1];
     uint64_t covered = 0, qmin = ~0ull, qmax = 0, s1 = 0, s2 = 0;
-    for (int64_t i = threadIdx.x; i < Z.W[BW_LEVELS - 1]; i += 256) {
+    for (int64_t i = threadIdx.x; i < Z.W[BBI_LEVELS - 1]; i += 256) {
         const bwz_win w = top[i];
         if (w.valid == 0) continue;
         covered += w.valid;
@@ -350,48 +308,6 @@ __global__ void __launch_bounds__(256) bwz_totals_kernel(const bwz_win *__restri
         }
         if (t.covered == 0) t.qmin = 0;
         totals[blockIdx.x] = t;
-    }
-}
-
-// the zoom records (32 bytes, two 16-byte stores) back to back in segment order, and the block table
-__global__ void __launch_bounds__(256) bwz_write_kernel(const bwz_win *__restrict__ win, const int64_t *__restrict__ wpref_all, int64_t nrec,
-                                                        bwz_levels Z, double scale, const uint64_t *__restrict__ tileoff,
-                                                        const uint64_t *__restrict__ segb, int ncls, uint32_t chrom0,
-                                                        uint4 *__restrict__ out, dgrp_track_zoom_block *__restrict__ table)
-{
-    __shared__ uint64_t lds[4];
-    const int64_t tpc = Z.seg[BW_LEVELS] / 256;
-    const int64_t k = blockIdx.x / tpc, tc = (int64_t)blockIdx.x % tpc;
-    int l = 0;
-    while (l + 1 < BW_LEVELS && Z.seg[l + 1] <= tc * 256) ++l;
-    const int64_t i = tc * 256 - Z.seg[l] + threadIdx.x;                  // the window in its level
-    const bwz_win w = win[(int64_t)blockIdx.x * 256 + threadIdx.x];
-    const uint64_t ex = block_exclusive_scan(w.valid != 0, nullptr, lds);
-    if (w.valid == 0) return;
-    const int nseg = ncls * BW_LEVELS, s = (int)k * BW_LEVELS + l;
-    const uint64_t at = tileoff[blockIdx.x] + ex, j = at - segb[s], n = segb[s + 1] - segb[s];
-    const int64_t r = tb_record_of(wpref_all + (int64_t)l * (nrec + 1), nrec, i);
-    uint4 a, b;
-    a.x = chrom0 + (uint32_t)r; a.y = w.start; a.z = w.end; a.w = w.valid;
-    b.x = __float_as_uint(bw_value(w.qmin, scale));
-    b.y = __float_as_uint(bw_value(w.qmax, scale));
-    b.z = __float_as_uint(bw_value(w.s1, scale));
-    b.w = __float_as_uint(bw_value(w.s2, scale * scale));
-    out[2 * at] = a;
-    out[2 * at + 1] = b;
-    dgrp_track_zoom_block *row = table + segb[nseg + 1 + s] + j / BW_SECTION_ITEMS;
-    if (j % BW_SECTION_ITEMS == 0) {
-        const uint64_t left = n - j, count = left < BW_SECTION_ITEMS ? left : BW_SECTION_ITEMS;
-        row->off = (int64_t)(32 * at);
-        row->bytes = (int64_t)(32 * count);
-        row->cls = (int32_t)k;
-        row->level = l;
-        row->rec0 = (int32_t)r;
-        row->start = w.start;
-    }
-    if (j % BW_SECTION_ITEMS == BW_SECTION_ITEMS - 1 || j == n - 1) {
-        row->rec1 = (int32_t)r;
-        row->end = w.end;
     }
 }
 
@@ -451,31 +367,24 @@ static bool bws_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpo
     return true;
 }
 
-struct bwz_layout { tb_layout t; bwz_levels Z; int64_t wpref, win, tiles, grand, segb, totals, bytes; };
+struct bwz_layout { tb_layout t; bbi_levels Z; int64_t wpref, win, tiles, grand, segb, totals, bytes; };
 
 static bool bwz_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, bwz_layout *l)
 {
     if (!bw_in_range(nrec, h_n, h_startpos) || bin > (1ll << 32) || !dgrp_tb_carve(nrec, h_n, h_startpos, bin, ncls, 0, &l->t)) return false;
-    bwz_levels &Z = l->Z;
-    Z.seg[0] = 0;
-    for (int k = 0; k < BW_LEVELS; ++k) {
-        Z.R[k] = 16 * bin << (2 * k);
-        Z.W[k] = 0;
-        for (int64_t r = 0; r < nrec; ++r) Z.W[k] += (h_startpos[r] + h_n[r] - 1) / Z.R[k] - h_startpos[r] / Z.R[k] + 1;
-        Z.seg[k + 1] = Z.seg[k] + dgrp_align_up(Z.W[k] > 0 ? Z.W[k] : 1, 256);
-    }
-    if (Z.seg[BW_LEVELS] / 256 * ncls >= (1ll << 31)) return false;
+    const bbi_levels &Z = l->Z;
+    if (!bbi_levels_of(16 * bin, ncls, nrec, h_startpos, h_n, &l->Z)) return false;
     int64_t p = l->t.bytes;
     l->wpref = p;
-    p += dgrp_align_up((nrec + 1) * BW_LEVELS * 8, 256);
+    p += dgrp_align_up((nrec + 1) * BBI_LEVELS * 8, 256);
     l->win = p;
-    p += dgrp_align_up(Z.seg[BW_LEVELS] * ncls * (int64_t)sizeof(bwz_win), 256);
+    p += dgrp_align_up(Z.seg[BBI_LEVELS] * ncls * (int64_t)sizeof(bwz_win), 256);
     l->tiles = p;
-    p += dgrp_align_up(Z.seg[BW_LEVELS] / 256 * ncls * 8, 256);
+    p += dgrp_align_up(Z.seg[BBI_LEVELS] / 256 * ncls * 8, 256);
     l->grand = p;
     p += 256;
     l->segb = p;
-    p += dgrp_align_up(2 * ((int64_t)ncls * BW_LEVELS + 1) * 8, 256);
+    p += dgrp_align_up(2 * ((int64_t)ncls * BBI_LEVELS + 1) * 8, 256);
     l->totals = p;
     p += dgrp_align_up((int64_t)ncls * (int64_t)sizeof(dgrp_track_totals), 256);
     l->bytes = p;
@@ -638,7 +547,7 @@ DGRP_EXPORT int dgrp_track_zoom_batch(const float *d_probs, int C, int64_t nrec,
     const char *who = "dgrp_track_zoom_batch";
     DGRP_REQUIRE(h_record_off && h_block_off && h_totals, "%s: NULL h_record_off, h_block_off or h_totals", who);
     if (ncls >= 1 && ncls <= DGRP_MAXC) {
-        for (int s = 0; s <= ncls * BW_LEVELS; ++s) h_record_off[s] = h_block_off[s] = 0;
+        for (int s = 0; s <= ncls * BBI_LEVELS; ++s) h_record_off[s] = h_block_off[s] = 0;
         memset(h_totals, 0, (size_t)ncls * sizeof(dgrp_track_totals));
     }
     const int rc0 = bw_check(who, d_probs, C, nrec, h_row0, h_n, h_startpos, h_cls, ncls, digits, bin, chrom0);
@@ -656,17 +565,13 @@ DGRP_EXPORT int dgrp_track_zoom_batch(const float *d_probs, int C, int64_t nrec,
     }
     hipStream_t stream = (hipStream_t)stream_;
     char *w = (char *)d_work;
-    const bwz_levels &Z = l.Z;
+    const bbi_levels &Z = l.Z;
     int64_t *d_wpref = (int64_t *)(w + l.wpref);
     bwz_win *win = (bwz_win *)(w + l.win);
     uint64_t *tiles = (uint64_t *)(w + l.tiles), *grand = (uint64_t *)(w + l.grand), *segb = (uint64_t *)(w + l.segb);
     dgrp_track_totals *d_totals = (dgrp_track_totals *)(w + l.totals);
-    const int nseg = ncls * BW_LEVELS;
-    std::vector<int64_t> wpref((size_t)(nrec + 1) * BW_LEVELS, 0);        // windows in front of every record, level by level
-    for (int k = 0; k < BW_LEVELS; ++k) {
-        int64_t *wp = wpref.data() + (size_t)k * (size_t)(nrec + 1);
-        for (int64_t r = 0; r < nrec; ++r) wp[r + 1] = wp[r] + (h_startpos[r] + h_n[r] - 1) / Z.R[k] - h_startpos[r] / Z.R[k] + 1;
-    }
+    const int nseg = ncls * BBI_LEVELS;
+    const std::vector<int64_t> wpref = bbi_wpref(Z, nrec, h_startpos, h_n);
     DGRP_HIP(hipMemcpyAsync(d_wpref, wpref.data(), wpref.size() * 8, hipMemcpyHostToDevice, stream));
     std::vector<int64_t> name_off((size_t)nrec + 1, 0);
     std::vector<char> tab;                                                 // (alive until the first synchronisation)
@@ -678,17 +583,17 @@ DGRP_EXPORT int dgrp_track_zoom_batch(const float *d_probs, int C, int64_t nrec,
     hipLaunchKernelGGL(bwz_level0_kernel, dim3((unsigned)((Z.seg[1] - Z.seg[0]) / 256 * ncls)), block, 0, stream, D.q, D.recs, D.pref, d_wpref,
                        D.G, Z, win);
     DGRP_LAUNCH_CHECK();
-    for (int k = 1; k < BW_LEVELS; ++k) {
-        hipLaunchKernelGGL(bwz_reduce_kernel, dim3((unsigned)((Z.seg[k + 1] - Z.seg[k]) / 256 * ncls)), block, 0, stream, D.recs, d_wpref, nrec,
-                           Z, k, win);
+    for (int k = 1; k < BBI_LEVELS; ++k) {
+        hipLaunchKernelGGL((bbi_reduce_kernel<bwz_win, bwz_start>), dim3((unsigned)((Z.seg[k + 1] - Z.seg[k]) / 256 * ncls)), block, 0, stream,
+                           bwz_start{D.recs}, d_wpref, nrec, Z, k, win);
         DGRP_LAUNCH_CHECK();
     }
-    const int64_t ntiles = Z.seg[BW_LEVELS] / 256 * ncls;
-    hipLaunchKernelGGL(bwz_count_kernel, dim3((unsigned)ntiles), block, 0, stream, win, tiles);
+    const int64_t ntiles = Z.seg[BBI_LEVELS] / 256 * ncls;
+    hipLaunchKernelGGL(bbi_count_kernel<bwz_win>, dim3((unsigned)ntiles), block, 0, stream, win, tiles);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), block, 0, stream, tiles, ntiles, grand);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bwz_bounds_kernel, dim3(1), dim3(64), 0, stream, tiles, grand, Z, ncls, segb);
+    hipLaunchKernelGGL((bbi_bounds_kernel<bwz_win, false>), dim3(1), dim3(64), 0, stream, win, tiles, grand, Z, ncls, segb, nullptr);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(bwz_totals_kernel, dim3((unsigned)ncls), block, 0, stream, win, Z, d_totals);
     DGRP_LAUNCH_CHECK();
@@ -703,8 +608,8 @@ DGRP_EXPORT int dgrp_track_zoom_batch(const float *d_probs, int C, int64_t nrec,
     if (h_record_off[nseg] == 0 || 32 * h_record_off[nseg] > cap || h_block_off[nseg] > table_cap) return DGRP_OK;   // (the caller retries)
     double scale = 1.0;
     for (int k = 0; k < digits; ++k) scale *= 10.0;
-    hipLaunchKernelGGL(bwz_write_kernel, dim3((unsigned)ntiles), block, 0, stream, win, d_wpref, nrec, Z, scale, tiles, segb, ncls,
-                       (uint32_t)chrom0, (uint4 *)d_out, d_table);
+    hipLaunchKernelGGL((bbi_write_kernel<bwz_win, bwz_tail>), dim3((unsigned)ntiles), block, 0, stream, win, d_wpref, nrec, Z, bwz_tail{scale}, tiles,
+                       segb, ncls, (uint32_t)chrom0, (uint4 *)d_out, d_table);
     DGRP_LAUNCH_CHECK();
     DGRP_HIP(hipStreamSynchronize(stream));
     return DGRP_OK;

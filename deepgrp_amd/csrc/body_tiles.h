@@ -10,16 +10,7 @@ namespace {
 
 __device__ __forceinline__ bool body_lineend(uint32_t b) { return b == '\n' || b == '\r'; }
 
-// record of tile t: the largest r < nrec with tile0[r] <= t (records without tiles share their tile0 with the next record)
-__device__ __forceinline__ int64_t body_record_of(const int64_t *__restrict__ tile0, int64_t nrec, int64_t t)
-{
-    int64_t lo = 0, hi = nrec;                    // tile0[lo] <= t < tile0[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (tile0[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (the record of tile t is dgrp_record_of(tile0, nrec, t): records without tiles share their tile0 with the next record)
 
 struct body_span {
     int64_t word;                 // 16-byte aligned address (offset in the buffer) of this lane's bytes

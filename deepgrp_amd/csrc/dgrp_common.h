@@ -61,3 +61,15 @@ __host__ __device__ static inline int64_t dgrp_place_row(dgrp_placement p, int64
 {
     return (w < p.nfullB ? w : w + p.shift) * s;
 }
+
+// The record of flat item x (a bin, a window, a tile, a workgroup, a row) under an ascending prefix pref[0 .. nrec] with
+// pref[0] <= x < pref[nrec]: the largest r < nrec with pref[r] <= x.  Records without items share their prefix with the next one.
+static __device__ __forceinline__ int64_t dgrp_record_of(const int64_t *__restrict__ pref, int64_t nrec, int64_t x)
+{
+    int64_t lo = 0, hi = nrec;                    // pref[lo] <= x < pref[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (pref[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}

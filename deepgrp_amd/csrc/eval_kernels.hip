@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__r
             atomicOr(&g[0], 1ull);
             atomicMin(&g[1], (unsigned long long)i);
         } else {
-            const int64_t r = eval_record_of(row_off, nrec, i);
+            const int64_t r = dgrp_record_of(row_off, nrec, i);
             int64_t cs, cl;
             eval_clip(q, origin[r], len[r], cs, cl);
             if (cl) atomicAdd(&s_tot[q.label], (unsigned long long)cl);
@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) eval_span_kernel(const dgrp_segment *__re
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, i = row_off[0] + j;
     if (i >= row_off[nrec]) return;
     const dgrp_segment q = rows[i];
-    const int64_t r = eval_record_of(row_off, nrec, i);
+    const int64_t r = dgrp_record_of(row_off, nrec, i);
     int64_t cs, n;
     eval_clip(q, origin[r], len[r], cs, n);
     cl[j] = (label == 0 || q.label == label) ? (uint64_t)n : 0;

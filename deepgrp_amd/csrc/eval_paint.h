@@ -8,16 +8,6 @@ namespace {
 
 #define EVAL_SLICE 8192           // positions per workgroup: 256 lanes x 32, lane-interleaved (a wave's stores are 64 adjacent bytes)
 
-__device__ __forceinline__ int64_t eval_record_of(const int64_t *__restrict__ row_off, int64_t nrec, int64_t i)
-{
-    int64_t lo = 0, hi = nrec;                    // largest r < nrec with row_off[r] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (row_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // row j's span on the record: [cs, cs + cl) of its bases (cl = 0 when the row misses the record)
 __device__ __forceinline__ void eval_clip(const dgrp_segment &q, int64_t origin, int64_t len, int64_t &cs, int64_t &cl)
 {

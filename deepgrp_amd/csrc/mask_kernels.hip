@@ -17,7 +17,7 @@ __global__ void __launch_bounds__(256) mask_count_kernel(const uint8_t *__restri
     __shared__ uint64_t lds[4];
     __shared__ int64_t s_rec;
     const int64_t t = blockIdx.x;
-    if (threadIdx.x == 0) s_rec = body_record_of(tile0, nrec, t);
+    if (threadIdx.x == 0) s_rec = dgrp_record_of(tile0, nrec, t);
     __syncthreads();
     const int64_t r = s_rec;
     const body_span s = body_lane_span(off[r], len[r], t - tile0[r]);
@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) mask_apply_kernel(const uint8_t *raw, uin
     __shared__ uint8_t r_in[MASK_LDS_ROWS];
     const int64_t t = blockIdx.x;
     if (threadIdx.x == 0) {
-        const int64_t r = body_record_of(tile0, nrec, t);
+        const int64_t r = dgrp_record_of(tile0, nrec, t);
         const int64_t p0 = (int64_t)(ex[t] - ex[tile0[r]]), p1 = p0 + (int64_t)(ex[t + 1] - ex[t]);
         // rows of this tile: the first that ends after p0 up to the first that starts at or after p1
         int64_t a = row_off[r], b = row_off[r + 1];

@@ -1,6 +1,8 @@
 // What the chains over the probability tracks share (track_kernels.hip: text and tabix index; bigwig_kernels.hip: bigWig sections and
 // zoom summaries): the record table, the flat bin space [class k][record r][bin j] with every class at a tile boundary, the
 // workspace layout of its front, and the bin pass that fills q -- defined in track_kernels.hip, one copy in the library.
+// Not here: the record of a flat bin (dgrp_record_of, dgrp_common.h: the search every prefix table of the library uses) and the
+// zoom ladder above bigWig's level 0 (bbi_zoom.h, shared with bigBed).
 #pragma once
 #include "dgrp_common.h"
 #include <vector>
@@ -26,18 +28,8 @@ struct tb_geom {
     int C, ncls, digits;
 };
 
-// record of flat bin f < pref[nrec]: the largest r with pref[r] <= f (every record has at least one bin)
-static __device__ __forceinline__ int64_t tb_record_of(const int64_t *__restrict__ pref, int64_t nrec, int64_t f)
-{
-    int64_t lo = 0, hi = nrec;                    // pref[lo] <= f < pref[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (pref[mid] <= f) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the same for f >= f0 when r0 is the record of f0 (found once per tile): mostly r0 itself, else one of the next f - f0 records
+// The record of flat bin f < pref[nrec] is dgrp_record_of(pref, nrec, f) (every record has at least one bin).  The same for
+// f >= f0 when r0 is the record of f0 (found once per tile): mostly r0 itself, else one of the next f - f0 records
 static __device__ __forceinline__ int64_t tb_record_from(const int64_t *__restrict__ pref, int64_t nrec, int64_t r0, int64_t f0, int64_t f)
 {
     if (pref[r0 + 1] > f) return r0;

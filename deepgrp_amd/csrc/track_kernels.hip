@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) tb_bin_lane_kernel(const float *__restric
 {
     __shared__ int64_t s_r0;
     const int64_t f0 = (int64_t)blockIdx.x * 256, f = f0 + threadIdx.x;
-    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    if (threadIdx.x == 0) s_r0 = dgrp_record_of(pref, G.nrec, f0);
     __syncthreads();
     if (f >= G.NB) return;
     const int64_t r = tb_record_from(pref, G.nrec, s_r0, f0, f);
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) tb_bin_wave_kernel(const float *__restric
     const int lane = threadIdx.x & 63;
     const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t f = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); f < G.NB; f += waves) {
-        const int64_t r = tb_record_of(pref, G.nrec, f);
+        const int64_t r = dgrp_record_of(pref, G.nrec, f);
         const tb_rec R = recs[r];
         int64_t lo, hi;
         track_bin_span(tb_geom_of(R, G.bin), f - pref[r], lo, hi);
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(256) tb_count_kernel(const uint32_t *__restric
     __shared__ int64_t s_r0;
     const int64_t tpc = G.NBpad / TRACK_TILE;
     const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
-    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    if (threadIdx.x == 0) s_r0 = dgrp_record_of(pref, G.nrec, f0);
     __syncthreads();
     const int64_t r0 = s_r0;
     const uint32_t *qk = q + k * G.NBpad;
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(256) tb_write_kernel(const uint32_t *__restric
     __shared__ __attribute__((aligned(16))) char stage[TRACK_STAGE + 16];
     const int64_t tpc = G.NBpad / TRACK_TILE;
     const int64_t k = blockIdx.x / tpc, f0 = ((int64_t)blockIdx.x % tpc) * TRACK_TILE;
-    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    if (threadIdx.x == 0) s_r0 = dgrp_record_of(pref, G.nrec, f0);
     __syncthreads();
     const int64_t r0 = s_r0;
     const uint32_t *qk = q + k * G.NBpad;
@@ -482,7 +482,7 @@ __global__ void __launch_bounds__(256) ix_tile_kernel(const uint32_t *__restrict
     __shared__ int64_t w_off[MODE == 2 ? 256 : 1], w_base[MODE == 2 ? 256 : 1], w_val[MODE == 2 ? 256 : 1];
     const int64_t tpc = G.NBpad / TRACK_TILE;
     const int64_t k = blockIdx.x / tpc, ti = (int64_t)blockIdx.x % tpc, f0 = ti * TRACK_TILE;
-    if (threadIdx.x == 0) s_r0 = tb_record_of(pref, G.nrec, f0);
+    if (threadIdx.x == 0) s_r0 = dgrp_record_of(pref, G.nrec, f0);
     __syncthreads();
     const int64_t r0 = s_r0;
     const uint32_t *qk = q + k * G.NBpad;

@@ -14,16 +14,7 @@ namespace {
 #define TB_LINE 50                              // bases per line of the text
 #define TB_NONE 0x7fffffffffffffffll
 
-// record of workgroup w: the largest r < nrec with wg0[r] <= w (records without workgroups share wg0 with the next record)
-__device__ __forceinline__ int64_t tb_record_of(const int64_t *__restrict__ wg0, int64_t nrec, int64_t w)
-{
-    int64_t lo = 0, hi = nrec;                  // wg0[lo] <= w < wg0[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (wg0[mid] <= w) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+// (the record of workgroup w is dgrp_record_of(wg0, nrec, w): records without workgroups share wg0 with the next record)
 
 // first interval k in [lo, hi) whose end lies above `pos` (hi if none): the first that can cover a base >= pos
 __device__ __forceinline__ int64_t tb_first_ending_after(const int64_t *__restrict__ iv, int64_t lo, int64_t hi, int64_t pos)
@@ -101,7 +92,7 @@ __global__ void __launch_bounds__(256) twobit_encode_kernel(const uint8_t *__res
     const int64_t *poff = tab, *dna = tab + nrec, *ooff = tab + 2 * nrec, *ivoff = tab + 3 * nrec, *wg0 = tab + 4 * nrec + 1;
     const int64_t w = blockIdx.x;
     if (threadIdx.x == 0) {
-        const int64_t r = tb_record_of(wg0, nrec, w);
+        const int64_t r = dgrp_record_of(wg0, nrec, w);
         const int64_t n = dna[r];
         const int64_t o = (int64_t)((uintptr_t)(idx + ooff[r]) & 15);          // the record starts `o` bytes into its first word
         int64_t b0 = (w - wg0[r]) * TB_SPAN - o, b1 = b0 + TB_SPAN;               // bases of this workgroup
@@ -187,7 +178,7 @@ __global__ void __launch_bounds__(256) twobit_text_kernel(const uint8_t *__restr
     __shared__ int64_t s_rec, s_nlo, s_nhi, s_mlo, s_mhi;
     const int64_t w = blockIdx.x;
     if (threadIdx.x == 0) {
-        const int64_t r = tb_record_of(wg0, nrec, w);
+        const int64_t r = dgrp_record_of(wg0, nrec, w);
         const tb_text_rec R = recs[r];
         const int64_t o = (int64_t)((uintptr_t)(text + R.toff) & 15);
         const int64_t hdr = R.name_len + 2;

@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) tbp_count_kernel(const uint8_t *__restric
     __shared__ uint64_t lds[2][4];
     __shared__ int64_t s_rec;
     const int64_t t = blockIdx.x;
-    if (threadIdx.x == 0) s_rec = body_record_of(tile0, nrec, t);
+    if (threadIdx.x == 0) s_rec = dgrp_record_of(tile0, nrec, t);
     __syncthreads();
     const int64_t r = s_rec;
     const body_span s = body_lane_span(off[r], len[r], t - tile0[r]);
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) tbp_write_kernel(const uint8_t *__restric
     __shared__ int64_t s_rec;
     __shared__ alignas(16) uint8_t cd[TBP_CODES];
     const int64_t t = blockIdx.x;
-    if (threadIdx.x == 0) s_rec = body_record_of(tile0, nrec, t);
+    if (threadIdx.x == 0) s_rec = dgrp_record_of(tile0, nrec, t);
     __syncthreads();
     const int64_t r = s_rec;
     const int64_t p0 = (int64_t)(ex[t] - rc[2 * r]), p1 = p0 + (int64_t)(ex[t + 1] - ex[t]);      // sequence positions of this tile

@@ -113,6 +113,30 @@ def test_zoom_records_are_the_reference_bytes(pipe_dev, reference, name):
         assert totals == (0, 0, 0, 0, 0) and zdata == b""
 
 
+def test_bigbed_and_bigwig_zoom_are_one_ladder(pipe_dev):
+    """csrc/bbi_zoom.h is instantiated for both formats.  Coverage rows on 64-base boundaries and the one-class indicator track of
+    the same rows (probability 1.0 on the rows' bases, bins of 64, so windows of 1024 bases in both) give the same records, offsets
+    and block tables; only the totals are in other units (q = 100 a base against 1)."""
+    from deepgrp_amd.pipeline import ContigPipeline
+    ends = np.array([900, 70_016, 5_000, 64], np.int64)
+    spans = [(0, 64), (128, 896), (0, 1024), (1024, 1088), (4096, 66_560), (69_952, 70_016), (0, 64)]
+    contigs = [0, 0, 1, 1, 1, 1, 3]                                        # (record 2 has no row)
+    rows, scores = rows_scores(spans, contigs, means=HIGH)
+    bed = ContigPipeline.bed_zoom_batch(True, _dev(rows, pipe_dev), _dev(scores, pipe_dev), 0, ends, 7)
+    row0 = np.r_[0, np.cumsum((ends[:-1] + 63) // 64 * 64)].astype(np.int64)
+    p = np.zeros((int(row0[-1] + ends[-1]), 1), np.float32)
+    for (a, b), r in zip(spans, contigs):
+        p[row0[r] + a:row0[r] + b, 0] = 1.0
+    track = ContigPipeline.track_zoom_batch_device(None, torch.from_numpy(p).to(pipe_dev), row0, ends, np.zeros(4, np.int64), (0,), 2, 64, 7)
+    raw = lambda t: t.cpu().numpy().tobytes()
+    assert bed[1].tolist() == track[1].tolist() == [0, 66, 86, 93, 97, 100, 103, 106, 109, 112, 115]
+    assert raw(bed[0]) == raw(track[0]) and len(raw(bed[0])) == 3680
+    assert bed[3].tolist() == track[3].tolist() and raw(bed[2]) == raw(track[2]) and len(raw(bed[2])) == 40 * int(bed[3][-1]) > 0
+    c = sum(b - a for a, b in spans)
+    assert tuple(int(x) for x in bed[4][0]) == (c, 1, 1, c, c)
+    assert tuple(int(x) for x in track[4][0]) == (c, 100, 100, 100 * c, 10_000 * c)
+
+
 # ---------------------------------------------------------------------------------------------------- refusals and capacities
 def _raw(L, entry, by_contig, d_rows, d_scores, nrows, low, ends, chrom0, out, cap, table, tcap, work, wb, stream=None):
     """-> (rc, the host counts: blocks (bytes, blocks, items); zoom (record offsets, block offsets, totals))"""
