@@ -333,6 +333,11 @@ class CommandLineParser:
                                    "annotation supports, their ratio); --json gains the key `curves` (AUROC, average precision, best F1)")
         evaluate.add_argument("--curve_bins", type=int, default=None,
                               help="probability bins of --curves, 2..4096 (default with --curves: 1000)")
+        evaluate.add_argument("--curve_elements", action="store_true",
+                              help="with --curves: also PREFIX.elements.tsv (per class and --bed_min_score 0..1000: the annotated "
+                                   "elements still found by the --min_overlap rule once the rows below that score are gone, recall, "
+                                   "the precision of PREFIX.rows.tsv and F1); the JSON's `curves` gains `elements` (recall at 0, the "
+                                   "best element-level F1 and the lowest score that reaches it)")
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
@@ -884,7 +889,7 @@ class CommandLineParser:
                     options=dict(step_size=args.step_size, min_mss_length=args.min_mss_length, xdrop_length=args.xdrop_length,
                                  batch_size=args.batch_size, use_mss=not args.no_use_mss, fast=bool(args.fast),
                                  min_overlap=args.min_overlap))
-        curves = dgcurves.Curves(classes, curve_plan.bins) if curve_plan is not None else None
+        curves = dgcurves.Curves(classes, curve_plan.bins, curve_plan.elements_path is not None) if curve_plan is not None else None
         try:
             rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves)
         except NoMatchError as e:

@@ -107,6 +107,9 @@ _SIGNATURES = {
     "dgrp_row_scores_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_prob_hist_workspace_bytes": (i64, [i64, cint, cint]),
     "dgrp_prob_hist_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, vp, vp, vp, i64, vp]),
+    "dgrp_row_detect_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_paint_row_keys_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_row_detect_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_format_bed_bound": (i64, [i64, i64]),
     "dgrp_format_bed_rows": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, vp, i64, C.POINTER(i64)]),
     "dgrp_bed_text_workspace_bytes": (i64, [i64, i64, i64]),

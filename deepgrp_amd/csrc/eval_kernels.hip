@@ -106,6 +106,7 @@ DGRP_EXPORT int dgrp_filter_segments(const int8_t *d_labels, int8_t *d_out, int6
 // [b * EVAL_SLICE, (b + 1) * EVAL_SLICE) of that line (rows run from 10 bp to megabases).
 // ------------------------------------------------------------------------------------------------------------------------------
 #include "eval_paint.h"
+#include "bed_rows.h"
 #include "scan.h"
 #include <vector>
 
@@ -115,10 +116,14 @@ namespace {
 #define EVAL_HEAD 2048            // workspace head: flag + first bad row at 0, clipped length per label (128 x u64) at 1024
 
 // one lane per row: 0 <= start <= end and 1 <= label <= max_label (at most 127), else g[0] |= 1 and g[1] = smallest bad row; tot[label] += clipped length
-// (summed per workgroup in LDS first: a handful of labels would otherwise serialise one global atomic per row)
+// (summed per workgroup in LDS first: a handful of labels would otherwise serialise one global atomic per row).  With `scores` (the
+// rows are predict's scored rows, dgrp_paint_row_keys_batch) two more rules: a row with a base inside its record is bed_scored(), else
+// g[0] |= 2 and g[2] = the smallest such row; a row does not start below the end of the row in front of it in its record, else
+// g[0] |= 4 and g[3] likewise
 __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__restrict__ rows, const int64_t *__restrict__ row_off,
                                                          int64_t nrec, const int64_t *__restrict__ len,
                                                          const int64_t *__restrict__ origin, int max_label,
+                                                         const dgrp_row_score *__restrict__ scores,
                                                          unsigned long long *__restrict__ g, unsigned long long *__restrict__ tot)
 {
     __shared__ unsigned long long s_tot[128];
@@ -135,6 +140,16 @@ __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__r
             int64_t cs, cl;
             eval_clip(q, origin[r], len[r], cs, cl);
             if (cl) atomicAdd(&s_tot[q.label], (unsigned long long)cl);
+            if (scores) {
+                if (cl && !bed_scored(scores[i])) {
+                    atomicOr(&g[0], 2ull);
+                    atomicMin(&g[2], (unsigned long long)i);
+                }
+                if (i > row_off[r] && q.start < rows[i - 1].end) {
+                    atomicOr(&g[0], 4ull);
+                    atomicMin(&g[3], (unsigned long long)i);
+                }
+            }
         }
     }
     __syncthreads();
@@ -213,13 +228,16 @@ struct eval_plan {
     int64_t nrows = 0;
     int64_t *d_off = nullptr, *d_len, *d_origin, *d_row_off, *d_dst;
     uint64_t *d_cl = nullptr, *d_tiles = nullptr;
+    char *d_extra = nullptr;           // `extra_bytes` behind the tables, for the caller
     unsigned long long tot[128];       // clipped length per label
 };
 
-// argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written
+// argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written.
+// d_scores: the rows are scored rows, checked as eval_check_kernel says; extra_bytes: more workspace, 256-byte aligned, at pl.d_extra
 static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
                         const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes,
-                        hipStream_t stream, eval_plan &pl, int max_label = 127)
+                        hipStream_t stream, eval_plan &pl, int max_label = 127, const dgrp_row_score *d_scores = nullptr,
+                        int64_t extra_bytes = 0)
 {
     DGRP_REQUIRE(nrec >= 0 && h_row_off && (nrec == 0 || (h_off && h_len && h_origin)), "%s: bad arguments", what);
     DGRP_REQUIRE(h_row_off[0] >= 0, "%s: negative row offset", what);
@@ -238,7 +256,7 @@ static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, co
     for (int k = 0; k < 128; ++k) pl.tot[k] = 0ull;
     if (pl.nrows == 0 || nrec == 0) return DGRP_OK;
     DGRP_REQUIRE(d_rows && d_work, "%s: NULL pointer", what);
-    if (work_bytes < dgrp_eval_workspace_bytes(nrec, pl.nrows)) {
+    if (work_bytes < dgrp_eval_workspace_bytes(nrec, pl.nrows) + extra_bytes) {
         dgrp_set_error("%s: workspace too small", what);
         return DGRP_ENOMEM;
     }
@@ -254,21 +272,29 @@ static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, co
     pl.d_dst = (int64_t *)p;
     p += dgrp_align_up(pl.nrows * 8, 256);
     pl.d_tiles = (uint64_t *)p;
-    const unsigned long long init[2] = { 0ull, ~0ull };
+    pl.d_extra = (char *)d_work + dgrp_eval_workspace_bytes(nrec, pl.nrows);
+    const unsigned long long init[4] = { 0ull, ~0ull, ~0ull, ~0ull };
     DGRP_HIP(hipMemcpyAsync(g, init, sizeof(init), hipMemcpyHostToDevice, stream));
     DGRP_HIP(hipMemsetAsync(d_tot, 0, 128 * 8, stream));
     DGRP_HIP(hipMemcpyAsync(pl.d_off, pl.tab.data(), pl.tab.size() * 8, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(eval_check_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
-                       pl.d_len, pl.d_origin, max_label, g, d_tot);
+                       pl.d_len, pl.d_origin, max_label, d_scores, g, d_tot);
     DGRP_LAUNCH_CHECK();
-    unsigned long long hg[2];
+    unsigned long long hg[4];
     DGRP_HIP(hipMemcpyAsync(hg, g, sizeof(hg), hipMemcpyDeviceToHost, stream));
     DGRP_HIP(hipMemcpyAsync(pl.tot, d_tot, sizeof(pl.tot), hipMemcpyDeviceToHost, stream));
     DGRP_HIP(hipStreamSynchronize(stream));
     if (hg[0]) {
-        const int64_t i = (int64_t)hg[1];
+        const int kind = (hg[0] & 1) ? 1 : (hg[0] & 2) ? 2 : 3;
+        const int64_t i = (int64_t)hg[kind];
         dgrp_segment q;
         DGRP_HIP(hipMemcpy(&q, d_rows + i, sizeof(q), hipMemcpyDeviceToHost));
+        DGRP_REQUIRE(kind != 2, "%s: row %lld [%lld, %lld) label %d has a base inside its record but no score (scored rows have 0 < "
+                     "bases < 2^40, sum <= bases * 2^24, 0 <= agree <= bases)", what, (long long)i, (long long)q.start, (long long)q.end,
+                     (int)q.label);
+        DGRP_REQUIRE(kind != 3, "%s: row %lld [%lld, %lld) label %d starts below the end of the row in front of it in its record "
+                     "(the rows of a record ascend and do not overlap)", what, (long long)i, (long long)q.start, (long long)q.end,
+                     (int)q.label);
         DGRP_REQUIRE(false, "%s: row %lld [%lld, %lld) label %d: rows need 0 <= start <= end and 1 <= label <= %d", what, (long long)i,
                      (long long)q.start, (long long)q.end, (int)q.label, max_label);
     }
@@ -495,5 +521,216 @@ DGRP_EXPORT int dgrp_row_scores_batch(const float *d_probs, int C, int64_t nrec,
     else
         hipLaunchKernelGGL(score_rows_kernel<0>, grid, dim3(256), 0, stream, d_probs, C, pl.d_cl, pl.d_dst, d_rows + r0, pl.nrows, d_scores + r0);
     DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// evaluate --curves --curve_elements: the detection score of every annotation row -- the largest --bed_min_score at which the
+// --min_overlap rule still finds it (include/deepgrp_hip.h states it).  The predicted rows are painted once as 16-bit keys
+// (label << 10 | BED score) on the same line of positions as the label paint; the annotation rows then bisect on the score: a pass
+// is the walk of eval_hits_kernel with the test "key in [label << 10 | mid, (label + 1) << 10)", a one-lane-per-row kernel between
+// the passes moves lo or hi.  The search runs over [-1, 1001) -- -1 ("not found even at 0") holds by definition -- so ten passes
+// settle all 1002 outcomes.  Integer adds only: the same bytes on every run.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+#define DETECT_PASSES 10          // 1002 -> 501 -> 251 -> 126 -> 63 -> 32 -> 16 -> 8 -> 4 -> 2 -> 1
+
+// one lane per row j, after the scan: the key of its bases (0 for a row without a base inside its record: nothing paints it)
+__global__ void __launch_bounds__(256) row_key_kernel(const dgrp_segment *__restrict__ rows, const dgrp_row_score *__restrict__ scores,
+                                                      const uint64_t *__restrict__ ex, int64_t n, uint16_t *__restrict__ key)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    key[j] = ex[j + 1] > ex[j] ? (uint16_t)((unsigned)rows[j].label << 10 | (unsigned)bed_figures(scores[j]).score) : (uint16_t)0;
+}
+
+// eval_paint_kernel with a value per row
+__global__ void __launch_bounds__(256) paint_keys_kernel(uint16_t *__restrict__ keys, const uint64_t *__restrict__ ex,
+                                                         const int64_t *__restrict__ dst, int64_t n, const uint16_t *__restrict__ key)
+{
+    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
+    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;
+    const uint64_t p0 = s0 + threadIdx.x;
+    if (p0 >= s1) return;
+    int64_t j = eval_row_of(ex, 0, n, p0);
+    uint64_t jst = ex[j], jend = ex[j + 1];
+    uint16_t v = key[j];
+    for (uint64_t p = p0; p < s1; p += 256) {
+        if (jend <= p) {
+            while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
+            v = key[j];
+        }
+        keys[dst[j] + (int64_t)(p - jst)] = v;
+    }
+}
+
+struct detect_state {
+    int2 *lohi;                    // the row's detection score lies in [lo, hi)
+    unsigned long long *cnt;       // the pass's hits of the row
+    uint32_t *thr;                 // label << 10 | the pass's midpoint
+};
+
+__device__ __forceinline__ uint32_t detect_thr(int label, int2 s)
+{
+    const int mid = s.y - s.x > 1 ? (s.x + s.y) >> 1 : (s.x > 0 ? s.x : 0);       // (a settled row's count is not read)
+    return (uint32_t)label << 10 | (uint32_t)mid;
+}
+
+// one lane per row j, after the scan: [-1, 1001) where the row has a base inside its record and needs one, else settled at -1
+__global__ void __launch_bounds__(256) detect_init_kernel(const dgrp_segment *__restrict__ rows, const uint64_t *__restrict__ ex,
+                                                          const int64_t *__restrict__ need, int64_t n, detect_state st)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int2 s = make_int2(-1, ex[j + 1] > ex[j] && need[j] > 0 ? 1001 : 0);
+    st.lohi[j] = s;
+    st.cnt[j] = 0ull;
+    st.thr[j] = detect_thr(rows[j].label, s);
+}
+
+// cnt[j] += bases of row j's clipped span with a key in [thr[j], (label + 1) << 10): eval_hits_kernel's walk and flush
+__global__ void __launch_bounds__(256) detect_walk_kernel(const uint16_t *__restrict__ keys, const uint64_t *__restrict__ ex,
+                                                          const int64_t *__restrict__ dst, const uint32_t *__restrict__ thr, int64_t n,
+                                                          unsigned long long *__restrict__ hits)
+{
+    __shared__ unsigned cnt[EVAL_LDS_ROWS];
+    __shared__ int64_t s_r0, s_r1;
+    const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
+    const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;    // (s0 < total: the grid covers the line exactly)
+    if (threadIdx.x == 0) {
+        s_r0 = eval_row_of(ex, 0, n, s0);
+        s_r1 = eval_row_of(ex, s_r0, n, s1 - 1);
+    }
+    for (int k = threadIdx.x; k < EVAL_LDS_ROWS; k += 256) cnt[k] = 0u;
+    __syncthreads();
+    const int64_t r0 = s_r0, r1 = s_r1;
+    const bool staged = r1 - r0 < EVAL_LDS_ROWS;
+    const uint64_t p0 = s0 + threadIdx.x;
+    if (p0 < s1) {
+        int64_t j = eval_row_of(ex, r0, r1 + 1, p0);
+        uint64_t jst = ex[j], jend = ex[j + 1];
+        uint32_t klo = thr[j], width = (((klo >> 10) + 1u) << 10) - klo;
+        unsigned c = 0;
+        for (uint64_t p = p0; p < s1; p += 256) {
+            if (jend <= p) {
+                if (c) {
+                    if (staged) atomicAdd(&cnt[j - r0], c);
+                    else atomicAdd(&hits[j], (unsigned long long)c);
+                }
+                c = 0;
+                while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
+                klo = thr[j];
+                width = (((klo >> 10) + 1u) << 10) - klo;
+            }
+            c += (uint32_t)keys[dst[j] + (int64_t)(p - jst)] - klo < width ? 1u : 0u;      // (a key below klo wraps to a large value)
+        }
+        if (c) {
+            if (staged) atomicAdd(&cnt[j - r0], c);
+            else atomicAdd(&hits[j], (unsigned long long)c);
+        }
+    }
+    __syncthreads();
+    if (staged) {
+        for (int64_t k = threadIdx.x; k <= r1 - r0; k += 256) {
+            const unsigned v = cnt[k];
+            if (v) atomicAdd(&hits[r0 + k], (unsigned long long)v);
+        }
+    }
+}
+
+// one lane per row j between the passes: the midpoint becomes lo where the row still has its hits, else hi; the counter is zeroed
+// and the next midpoint set; behind the last pass lo is the detection score
+__global__ void __launch_bounds__(256) detect_step_kernel(const dgrp_segment *__restrict__ rows, const int64_t *__restrict__ need,
+                                                          int64_t n, detect_state st, int32_t *__restrict__ detect)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    int2 s = st.lohi[j];
+    if (s.y - s.x > 1) {
+        const int mid = (s.x + s.y) >> 1;
+        if ((long long)st.cnt[j] >= (long long)need[j]) s.x = mid; else s.y = mid;
+        st.lohi[j] = s;
+    }
+    st.cnt[j] = 0ull;
+    st.thr[j] = detect_thr(rows[j].label, s);
+    if (detect) detect[j] = s.x;
+}
+
+}   // namespace
+
+DGRP_EXPORT int64_t dgrp_row_detect_workspace_bytes(int64_t nrec, int64_t nrows)
+{
+    if (nrec < 0 || nrows < 0) return 0;
+    return dgrp_eval_workspace_bytes(nrec, nrows) + 2 * dgrp_align_up(nrows * 8, 256) + dgrp_align_up(nrows * 4, 256);
+}
+
+DGRP_EXPORT int dgrp_paint_row_keys_batch(uint16_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                                          const int64_t *h_origin, const dgrp_segment *d_pred, const int64_t *h_pred_off,
+                                          const dgrp_row_score *d_scores, void *d_work, int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *what = "dgrp_paint_row_keys_batch";
+    DGRP_REQUIRE(nrec >= 0 && h_pred_off, "%s: bad arguments", what);
+    const int64_t nrows = h_pred_off[nrec] - h_pred_off[0];
+    DGRP_REQUIRE(nrows <= 0 || nrec == 0 || d_scores, "%s: NULL pointer", what);
+    eval_plan pl;
+    const int rc = eval_prepare(what, nrec, h_off, h_len, h_origin, d_pred, h_pred_off, d_work, work_bytes, stream, pl, 63, d_scores,
+                                dgrp_row_detect_workspace_bytes(nrec, nrows > 0 ? nrows : 0) - dgrp_eval_workspace_bytes(nrec, nrows > 0 ? nrows : 0));
+    if (rc != DGRP_OK || pl.nrows == 0 || nrec == 0) return rc;
+    uint64_t total = 0;
+    for (int k = 1; k < 64; ++k) total += pl.tot[k];
+    if (total == 0) return DGRP_OK;
+    DGRP_REQUIRE(d_keys && ((uintptr_t)d_keys & 1) == 0, "%s: the key track must be a 2-byte aligned device pointer", what);
+    const int64_t r0 = h_pred_off[0];
+    const int e = eval_spans(pl, d_pred, nrec, 0, stream);
+    if (e != DGRP_OK) return e;
+    uint16_t *d_key = (uint16_t *)pl.d_extra;
+    hipLaunchKernelGGL(row_key_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_pred + r0, d_scores + r0, pl.d_cl,
+                       pl.nrows, d_key);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(paint_keys_kernel, dim3((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE)), dim3(256), 0, stream, d_keys, pl.d_cl,
+                       pl.d_dst, pl.nrows, d_key);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+DGRP_EXPORT int dgrp_row_detect_batch(const uint16_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                                      const int64_t *h_origin, const dgrp_segment *d_true, const int64_t *h_true_off,
+                                      const int64_t *d_need, int32_t *d_detect, void *d_work, int64_t work_bytes, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *what = "dgrp_row_detect_batch";
+    DGRP_REQUIRE(nrec >= 0 && h_true_off, "%s: bad arguments", what);
+    const int64_t nrows = h_true_off[nrec] - h_true_off[0];
+    eval_plan pl;
+    const int rc = eval_prepare(what, nrec, h_off, h_len, h_origin, d_true, h_true_off, d_work, work_bytes, stream, pl, 63, nullptr,
+                                dgrp_row_detect_workspace_bytes(nrec, nrows > 0 ? nrows : 0) - dgrp_eval_workspace_bytes(nrec, nrows > 0 ? nrows : 0));
+    if (rc != DGRP_OK || pl.nrows == 0 || nrec == 0) return rc;
+    DGRP_REQUIRE(d_detect && d_need, "%s: NULL pointer", what);
+    const int64_t r0 = h_true_off[0];
+    uint64_t total = 0;
+    for (int k = 1; k < 64; ++k) total += pl.tot[k];
+    if (total == 0) {                                                         // no row has a base inside its record: all -1
+        DGRP_HIP(hipMemsetAsync(d_detect + r0, 0xff, pl.nrows * sizeof(int32_t), stream));
+        return DGRP_OK;
+    }
+    DGRP_REQUIRE(d_keys && ((uintptr_t)d_keys & 1) == 0, "%s: the key track must be a 2-byte aligned device pointer", what);
+    const int e = eval_spans(pl, d_true, nrec, 0, stream);
+    if (e != DGRP_OK) return e;
+    detect_state st;
+    st.cnt = (unsigned long long *)pl.d_extra;
+    st.lohi = (int2 *)(pl.d_extra + dgrp_align_up(pl.nrows * 8, 256));
+    st.thr = (uint32_t *)(pl.d_extra + 2 * dgrp_align_up(pl.nrows * 8, 256));
+    const dim3 per_row((unsigned)((pl.nrows + 255) / 256)), per_slice((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE));
+    hipLaunchKernelGGL(detect_init_kernel, per_row, dim3(256), 0, stream, d_true + r0, pl.d_cl, d_need + r0, pl.nrows, st);
+    DGRP_LAUNCH_CHECK();
+    for (int pass = 0; pass < DETECT_PASSES; ++pass) {
+        hipLaunchKernelGGL(detect_walk_kernel, per_slice, dim3(256), 0, stream, d_keys, pl.d_cl, pl.d_dst, st.thr, pl.nrows, st.cnt);
+        DGRP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(detect_step_kernel, per_row, dim3(256), 0, stream, d_true + r0, d_need + r0, pl.nrows, st,
+                           pass == DETECT_PASSES - 1 ? d_detect + r0 : (int32_t *)nullptr);
+        DGRP_LAUNCH_CHECK();
+    }
     return DGRP_OK;
 }

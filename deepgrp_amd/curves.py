@@ -8,6 +8,12 @@ sums of the two histograms, every rate a ratio of those integers (float64 only t
 Row curves answer "what does `predict --bed_min_score m` keep": per class and m = 0..1000 the predicted rows whose BED score is at
 least m (`segments`), those of them the annotation supports by `evaluate`'s --min_overlap rule (`supported`), and their ratio.
 
+Element curves (`--curve_elements`) are the other half: how many annotated elements are still found once the rows below m are gone.
+Predict's rows of one record never overlap, so the bases of an element that rows of its class with score >= m cover cannot rise
+with m: an element has one detection score d, the largest m at which the --min_overlap rule still finds it (-1: not even at 0), and
+`found` at every m is a suffix sum of the histogram of d (dgrp_paint_row_keys_batch and dgrp_row_detect_batch; `reference_detect`
+is their numpy statement).
+
 Everything here is numpy over int64; the same counts give the same file bytes."""
 from __future__ import annotations
 
@@ -22,6 +28,7 @@ MIN_BINS, MAX_BINS, DEFAULT_BINS = 2, 4096, 1000
 SCORES = 1001                                       # BED scores 0..1000
 BASES_HEADER = ("class", "threshold", "TP", "FP", "FN", "TN", "TPR", "FPR", "PPV", "F1")
 ROWS_HEADER = ("class", "min_score", "segments", "supported", "precision")
+ELEMENTS_HEADER = ("class", "min_score", "elements", "found", "recall", "segments", "supported", "precision", "F1")
 
 
 class CurvePlan(NamedTuple):
@@ -29,14 +36,18 @@ class CurvePlan(NamedTuple):
     bins: int
     bases_path: str
     rows_path: str
+    elements_path: Optional[str] = None                 # PREFIX.elements.tsv with --curve_elements
 
 
 def plan(args) -> Optional[CurvePlan]:
-    """--curves and --curve_bins, or None without the flag.  Every refusal is made here (sys.exit), before the model is read or the
+    """--curves, --curve_bins and --curve_elements, or None without --curves.  Every refusal is made here (sys.exit), before the model is read or the
     GPU is touched."""
     prefix = getattr(args, "curves", None)
     bins = getattr(args, "curve_bins", None)
+    elements = bool(getattr(args, "curve_elements", False))
     if prefix is None:
+        if elements:
+            sys.exit("--curve_elements needs --curves")
         if bins is not None:
             sys.exit("--curve_bins needs --curves")
         return None
@@ -51,7 +62,7 @@ def plan(args) -> Optional[CurvePlan]:
     where = os.path.dirname(prefix) or "."
     if not os.path.isdir(where):
         sys.exit(f"--curves: the directory {where} does not exist")
-    paths = (prefix + ".bases.tsv", prefix + ".rows.tsv")
+    paths = (prefix + ".bases.tsv", prefix + ".rows.tsv") + ((prefix + ".elements.tsv",) if elements else ())
     for f in getattr(args, "FASTA", []):
         for out in paths:
             if f != "-" and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
@@ -158,6 +169,81 @@ def row_curves(seg: np.ndarray, sup: np.ndarray):
     return at(seg), at(sup)
 
 
+def need_of(theta: float, clen: np.ndarray) -> np.ndarray:
+    """The bases an element of clipped length clen needs: ceil(theta * float64(clen)), 0 where clen is 0.  For integer hits,
+    hits >= need is `Accumulator._count`'s float64(hits) >= theta * float64(clen): an integer is at least x exactly when it is at
+    least ceil(x), and both sides are exact in float64."""
+    clen = np.asarray(clen, np.int64)
+    return np.where(clen > 0, np.ceil(float(theta) * clen.astype(np.float64)), 0.0).astype(np.int64)
+
+
+def reference_detect(origins, lengths, pred_rows, pred_scores, true_rows, need):
+    """dgrp_paint_row_keys_batch and dgrp_row_detect_batch in numpy for a list of records (record r: `lengths[r]` bases from the
+    coordinate `origins[r]`): pred_rows[r] its predicted rows (SEGMENT_DTYPE fields, ascending, not overlapping), pred_scores[r]
+    their BED scores 0..1000, true_rows[r] its annotation rows, need[r] the bases each needs.
+    -> ([key track uint16 per record], detection scores int32 of all annotation rows, record after record).
+    key = label << 10 | score on every base of a predicted row's clipped span, 0 elsewhere.  The detection score of annotation
+    row j with label L and clipped span S is the largest m in 0..1000 with #{b in S: L << 10 | m <= key[b] < (L + 1) << 10} >=
+    need[j], -1 where there is none, where need[j] <= 0 or where S is empty -- taken by trying every m."""
+    keys, out = [], []
+    for r in range(len(lengths)):
+        n, o = int(lengths[r]), int(origins[r])
+        key = np.zeros(n, np.uint16)
+        for row, sc in zip(pred_rows[r], pred_scores[r]):
+            a, e = min(max(int(row["start"]) - o, 0), n), min(max(int(row["end"]) - o, 0), n)
+            if e > a:
+                key[a:e] = int(row["label"]) << 10 | int(sc)
+        keys.append(key)
+        t = true_rows[r]
+        nd = np.asarray(need[r], np.int64).reshape(len(t))
+        a = np.clip(np.asarray(t["start"], np.int64) - o, 0, n)
+        e = np.maximum(np.clip(np.asarray(t["end"], np.int64) - o, 0, n), a)
+        d = np.full(len(t), -1, np.int32)
+        labels = np.asarray(t["label"], np.int64)
+        live = (e > a) & (nd > 0)
+        for lab in np.unique(labels[live]):
+            sel = np.flatnonzero(live & (labels == lab))
+            k = key.astype(np.int64)
+            for m in range(SCORES):
+                cs = np.concatenate([[0], np.cumsum((k >= (lab << 10 | m)) & (k < (lab + 1) << 10))])
+                ok = cs[e[sel]] - cs[a[sel]] >= nd[sel]
+                d[sel[ok]] = m
+        out.append(d)
+    return keys, (np.concatenate(out) if out else np.zeros(0, np.int32))
+
+
+def element_curves(det: np.ndarray, seg: np.ndarray, sup: np.ndarray) -> Dict[str, np.ndarray]:
+    """Per class and m = 0..1000 from det (int64 [C, 1002]: the elements with a base inside their record by label and detection
+    score + 1) and `row_counts`: elements [C], found (detection score >= m), segments, supported (int64 [C, 1001]) and recall =
+    found / elements, precision = supported / segments, F1 = 2 P R / (P + R) (float64, NaN where a denominator is 0)."""
+    det = np.asarray(det, np.int64)
+    elements = det.sum(axis=1)
+    found = det[:, :0:-1].cumsum(axis=1)[:, ::-1]
+    seg_at, sup_at = row_curves(seg, sup)
+    recall, prec = _ratio(found, elements[:, None]), _ratio(sup_at, seg_at)
+    with np.errstate(invalid="ignore"):
+        f1 = _ratio(2 * prec * recall, prec + recall)
+    f1[np.isnan(prec) | np.isnan(recall)] = np.nan
+    return dict(elements=elements, found=found, recall=recall, segments=seg_at, supported=sup_at, precision=prec, F1=f1)
+
+
+def element_summary(det: np.ndarray, seg: np.ndarray, sup: np.ndarray) -> Dict[str, List[float]]:
+    """Per class: recall_at_0, best_f1 and best_min_score (the lowest m that reaches it; NaN where F1 is NaN at every m)."""
+    cv = element_curves(det, seg, sup)
+    out = dict(recall_at_0=[], best_f1=[], best_min_score=[])
+    for c in range(cv["F1"].shape[0]):
+        f1 = cv["F1"][c]
+        out["recall_at_0"].append(float(cv["recall"][c, 0]))
+        if np.isnan(f1).all():
+            out["best_f1"].append(float("nan"))
+            out["best_min_score"].append(float("nan"))
+        else:
+            m = int(np.nanargmax(f1))                            # (the first maximum: the lowest m on a tie)
+            out["best_f1"].append(float(f1[m]))
+            out["best_min_score"].append(m)
+    return out
+
+
 _f = lambda x: repr(float(x))                                    # floats as `evaluate` prints them ('nan' for NaN)
 
 
@@ -183,29 +269,56 @@ def rows_tsv(seg: np.ndarray, sup: np.ndarray) -> str:
     return "\n".join(lines) + "\n"
 
 
-class Curves:
-    """The counts of one `evaluate --curves` run, summed over its work items."""
+def elements_tsv(det: np.ndarray, seg: np.ndarray, sup: np.ndarray) -> str:
+    cv = element_curves(det, seg, sup)
+    lines = ["#" + "\t".join(ELEMENTS_HEADER)]
+    for c in range(1, cv["found"].shape[0]):
+        for m in range(SCORES):
+            lines.append("\t".join([str(c), str(m), str(int(cv["elements"][c])), str(int(cv["found"][c, m])), _f(cv["recall"][c, m]),
+                                    str(int(cv["segments"][c, m])), str(int(cv["supported"][c, m])), _f(cv["precision"][c, m]),
+                                    _f(cv["F1"][c, m])]))
+    return "\n".join(lines) + "\n"
 
-    def __init__(self, classes: int, bins: int = DEFAULT_BINS):
+
+class Curves:
+    """The counts of one `evaluate --curves` run, summed over its work items; with `elements` (--curve_elements) also `det`, the
+    elements by label and detection score + 1."""
+
+    def __init__(self, classes: int, bins: int = DEFAULT_BINS, elements: bool = False):
         if not MIN_BINS <= int(bins) <= MAX_BINS:
             raise ValueError(f"bins must lie in {MIN_BINS}..{MAX_BINS}, not {bins}")
         self.C, self.bins = int(classes), int(bins)
         self.hist = np.zeros((self.C, 2, self.bins), np.int64)
         self.seg = np.zeros((self.C, SCORES), np.int64)
         self.sup = np.zeros((self.C, SCORES), np.int64)
+        self.elements = bool(elements)
+        self.det = np.zeros((self.C, SCORES + 1), np.int64)
+
+    def element_curves(self) -> Dict[str, np.ndarray]:
+        return element_curves(self.det, self.seg, self.sup)
+
+    def elements_tsv(self) -> str:
+        return elements_tsv(self.det, self.seg, self.sup)
 
     def summary(self) -> Dict[str, object]:
         """The `curves` key of the JSON report (NaN as None)."""
         num = lambda x: None if math.isnan(x) else x
         out: Dict[str, object] = dict(bins=self.bins)
         out.update({k: [num(x) for x in v] for k, v in summaries(self.hist).items()})
+        if self.elements:
+            out["elements"] = {k: [num(x) for x in v] for k, v in element_summary(self.det, self.seg, self.sup).items()}
         return out
 
     def write(self, p: CurvePlan, log) -> None:
-        """Both files, staged: a failure leaves neither, nor a temporary file."""
+        """The two files, with elements the three, staged: a failure leaves none of them, nor a temporary file."""
         from .outfiles import StagedFile, StagedOutputs
-        texts = (bases_tsv(self.hist), rows_tsv(self.seg, self.sup))
-        out = StagedOutputs(log, p.prefix, "--curves", False, (StagedFile(f, "w") for f in (p.bases_path, p.rows_path)))
+        texts, paths = [bases_tsv(self.hist), rows_tsv(self.seg, self.sup)], [p.bases_path, p.rows_path]
+        if self.elements:
+            if p.elements_path is None:
+                raise ValueError("element curves were counted but the plan names no PREFIX.elements.tsv")
+            texts.append(self.elements_tsv())
+            paths.append(p.elements_path)
+        out = StagedOutputs(log, p.prefix, "--curves", False, (StagedFile(f, "w") for f in paths))
         try:
             for part, text in zip(out.parts, texts):
                 part.fh.write(text)

@@ -13,7 +13,9 @@ scored by dgrp_confusion_matrix, and every row is counted against the other trac
 
 With curves (`evaluate --curves`, deepgrp_amd/curves.py) the runner keeps the merged probabilities of every work item long enough
 for `Accumulator.probe`: it paints the item's truth on the worker's stream and counts every probability into per-class
-histograms split by truth (dgrp_prob_hist_batch); the rows' BED scores come with the rows (dgrp_row_scores_batch)."""
+histograms split by truth (dgrp_prob_hist_batch); the rows' BED scores come with the rows (dgrp_row_scores_batch).  With element
+curves (`--curve_elements`) `Accumulator.add` also paints the predicted rows as (label, score) keys and takes every annotation row's
+detection score against them (dgrp_paint_row_keys_batch, dgrp_row_detect_batch)."""
 from __future__ import annotations
 
 import logging
@@ -262,6 +264,38 @@ class Accumulator:
                 seg, sup = row_counts(p_flat["label"].astype(np.int64), sc, kept, good, self.C)
                 self.curves.seg += seg
                 self.curves.sup += sup
+        if self.curves is not None and self.curves.elements and t_flat.size:
+            self._detect(ln, org, off, t_off, t_flat, d_trows, np.concatenate(t_clen), p_off, d_prows, scores, names)
+
+    def _detect(self, ln, org, off, t_off, t_flat, d_trows, t_clen, p_off, d_prows, scores, names) -> None:
+        """The element curves' share of a work item: the predicted rows painted as keys (label << 10 | BED score) on a zeroed
+        uint16 track (dgrp_paint_row_keys_batch), the detection score of every annotation row against it (dgrp_row_detect_batch),
+        counted into curves.det by label and score + 1 for the rows with a base inside their record."""
+        import torch
+
+        from ._lib import check, lib
+        from .curves import need_of
+        from .pipeline import ROW_SCORE_DTYPE, require_gpu, stream_ptr
+        L, dev, s, nrec = lib(), require_gpu(), stream_ptr(), len(ln)
+        wb = int(L.dgrp_row_detect_workspace_bytes(nrec, max(int(t_off[-1]), int(p_off[-1]))))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        d_keys = torch.zeros(int(off[-1]), dtype=torch.int16, device=dev)          # (16-bit keys; the sign of the type is not read)
+        if d_prows is not None:
+            sc = np.ascontiguousarray(scores, ROW_SCORE_DTYPE)
+            d_sc = torch.from_numpy(sc.view(np.uint8)).to(dev)
+            rc = L.dgrp_paint_row_keys_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_prows.data_ptr(),
+                                             p_off.ctypes.data, d_sc.data_ptr(), work.data_ptr(), wb, s)
+            if rc != 0:
+                raise ValueError("the predicted rows of record{} {} cannot be painted by score: {}".format(
+                    "s" if len(names) > 1 else "", ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else ""),
+                    L.dgrp_last_error().decode("utf-8", "replace")))
+        d_need = torch.from_numpy(need_of(self.theta, t_clen)).to(dev)
+        d_det = torch.empty(len(t_flat), dtype=torch.int32, device=dev)
+        check(L.dgrp_row_detect_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_trows.data_ptr(),
+                                      t_off.ctypes.data, d_need.data_ptr(), d_det.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_detect_batch")
+        det = d_det.cpu().numpy().astype(np.int64)
+        ok = t_clen > 0
+        np.add.at(self.curves.det, (t_flat["label"].astype(np.int64)[ok], det[ok] + 1), 1)
 
 
 def metrics_of(cnf: np.ndarray, bases: int) -> Dict[str, object]:

@@ -581,6 +581,33 @@ int dgrp_prob_hist_batch(const float *d_probs, int C, int64_t nrec, const int64_
                          const int8_t *d_truth, const int64_t *h_off, int bins, int64_t *d_hist, int *d_bad,
                          void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- detection scores (an addition, evaluate --curves --curve_elements): for every annotation row the largest
+ * `predict --bed_min_score` m at which the predicted rows that survive m still cover enough of it.  Records are laid out as for
+ * dgrp_paint_rows_batch, the track being uint16 (2-byte aligned): record r is d_keys[h_off[r] .. h_off[r] + h_len[r]), its first
+ * base has the coordinate h_origin[r]; rows in ORIGINAL coordinates, clipped to their record; labels 1..63.  Both entries take a
+ * workspace of dgrp_row_detect_workspace_bytes(nrec, rows) bytes (DGRP_ENOMEM below it) and run one check kernel before anything is
+ * written, which synchronises the stream once; behind it they are stream-ordered.  nrec == 0 or no rows: no device work.
+ * dgrp_paint_row_keys_batch: every base in the clipped span of predicted row i (d_pred[h_pred_off[r] .. h_pred_off[r+1]) for record
+ * r, d_scores[i] its score) is set to key = label << 10 | score, score = R(sum, bases * 2^24, 1000), the integer 0..1000 of BED
+ * column 5 (below).  No other element of d_keys is written: the caller zeroes the track.  DGRP_EINVAL, nothing written, for a row
+ * with start < 0, end < start or a label outside 1..63; for a row with a base inside its record whose score is outside what
+ * dgrp_row_scores_batch writes (0 < bases < 2^40, sum <= bases * 2^24, 0 <= agree <= bases) -- rows without such a base are ignored
+ * whatever their score --; and for a row that starts below the end of the row in front of it in its record (predict's rows ascend
+ * and do not overlap, so one pass of plain stores paints them).
+ * dgrp_row_detect_batch: for annotation row j (d_true[h_true_off[r] .. h_true_off[r+1]); any order, overlapping, nested, sticking
+ * out of the record) with label L and clipped span S, hits_m(j) = #{b in S : (L << 10 | m) <= key[b] < ((L + 1) << 10)}.
+ * d_detect[j] (int32) = the largest m in 0..1000 with hits_m(j) >= d_need[j] (device int64, the caller's ceil(min_overlap * |S|));
+ * -1 when hits_0(j) < d_need[j], when d_need[j] <= 0 or when S is empty.  Written for j in [h_true_off[0], h_true_off[nrec]),
+ * nowhere else; d_need is read there only.  hits_m cannot rise with m, so the entry bisects: ten passes over the clipped spans,
+ * balanced by length as dgrp_row_hits_batch is, 2 bytes read per base and pass; integer sums, the same bytes on every run. */
+int64_t dgrp_row_detect_workspace_bytes(int64_t nrec, int64_t nrows);
+int dgrp_paint_row_keys_batch(uint16_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                              const dgrp_segment *d_pred, const int64_t *h_pred_off, const dgrp_row_score *d_scores, void *d_work,
+                              int64_t work_bytes, void *stream);
+int dgrp_row_detect_batch(const uint16_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                          const dgrp_segment *d_true, const int64_t *h_true_off, const int64_t *d_need, int32_t *d_detect,
+                          void *d_work, int64_t work_bytes, void *stream);
+
 /* The scored rows as BED text (host code, host buffers): per row "name\tstart\tend\tclass<label>\tscore\t.\tmean\tmin\tagree\n".
  * name i = bytes [name_off[i], name_off[i+1]) of `names`; a row takes name rows[r].contig if by_contig != 0, else name 0 (the rule
  * of dgrp_format_rows).  With R(num, den, k) = floor((2 k num + den) / (2 den)), integer round-half-up evaluated in 128 bits:
