@@ -20,6 +20,9 @@ Differences, all additive:
     with --bed_gzip the file is BGZF (`.bed.gz`), its lines written and deflated on the GPU, and with --bed_index a tabix index
     (`.bed.gz.tbi`) is built there beside it; with --bed_bigbed the file is a bigBed instead (`.bb`, deepgrp_amd/bigbed.py: binary
     items with 32-bit coordinates, an R-tree and coverage zoom levels, written and deflated on the GPU);
+  * `predict --seq_dir DIR [--seq_classes 1,3] [--seq_flank N] [--seq_width W]` also writes the sequences of the predicted repeats
+    of every input as FASTA, DIR/<basename>.repeats.fa: one record `>NAME:A-B class<label>` per TSV row, gathered on the GPU
+    (deepgrp_amd/repeatseq.py); with --seq_gzip as BGZF (`.repeats.fa.gz`), with --seq_fai a `.fai` index beside it;
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
@@ -218,6 +221,29 @@ def _add_bed_options(parser) -> None:
                              "bigBed for that input.  Not with --bed_gzip or --bed_index")
 
 
+def _add_seq_options(parser) -> None:
+    """The repeat-sequence flags, like the track flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--seq_dir", type=str, default=s,
+                        help="(addition) also write the sequences of the predicted repeats of every input as FASTA, DIR/<basename of "
+                             "the input>.repeats.fa: per TSV row one record '>NAME:A-B class<label>' (0-based, half-open, as bedtools "
+                             "getfasta names it) with the bases of the row exactly as the input has them, gathered on the GPU; one "
+                             "process only")
+    parser.add_argument("--seq_classes", type=_class_list, default=s,
+                        help="(addition) with --seq_dir: comma-separated labels to write, e.g. 1,3 (default: every label > 0)")
+    parser.add_argument("--seq_flank", type=int, default=s,
+                        help="(addition) with --seq_dir: also take up to N bases on either side of every row, clamped to the record; "
+                             "the header then ends in ' core=<start>-<end>' (default: 0)")
+    parser.add_argument("--seq_width", type=int, default=s,
+                        help="(addition) with --seq_dir: bases per line, 1..2^30 (default: 60)")
+    parser.add_argument("--seq_gzip", action="store_true", default=s,
+                        help="(addition) with --seq_dir: write the FASTA as BGZF (bgzip's format) to DIR/<basename>.repeats.fa.gz, "
+                             "deflated on the GPU (--gzip_level, 1 unless given)")
+    parser.add_argument("--seq_fai", action="store_true", default=s,
+                        help="(addition) with --seq_dir: also write the samtools faidx index DIR/<basename>.repeats.fa.fai; not with "
+                             "--seq_gzip")
+
+
 class CommandLineParser:
     """Commandline parser (deepgrp/__main__.py:86-250)."""
 
@@ -244,6 +270,7 @@ class CommandLineParser:
         _add_mask_options(self.parser, suppress=True)
         _add_track_options(self.parser)
         _add_bed_options(self.parser)
+        _add_seq_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (GRU) on the GPU")
         train.add_argument("parameter", type=str)
@@ -303,6 +330,7 @@ class CommandLineParser:
         _add_mask_options(predict, suppress=True)
         _add_track_options(predict)
         _add_bed_options(predict)
+        _add_seq_options(predict)
         evaluate = subparsers.add_parser(
             name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
             description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
@@ -345,7 +373,8 @@ class CommandLineParser:
         if not any(a in ("predict", "train", "verify", "evaluate", "optimize") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
-                           "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score"}
+                           "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score",
+                           "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -385,11 +414,15 @@ class CommandLineParser:
         tk.check_gzip_flags(args)                               # refusals come before anything runs
         bed_plan = bed.plan(args)
         masks = CommandLineParser._mask_plan(args)
+        seqs = CommandLineParser._seq_plan(args)
         track_plan = tk.plan(args)
         track_spec = None
         if track_plan is not None:
             from .model import read_keras_hdf5
             track_spec = tk.resolve(track_plan, int(read_keras_hdf5(args.model)["ff_kernel"].shape[-1]))
+        if seqs is not None and seqs["classes"] is not None:
+            from .model import read_keras_hdf5
+            CommandLineParser._check_seq_classes(seqs, int(read_keras_hdf5(args.model)["ff_kernel"].shape[-1]))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             from .gz import compressed_inputs
             packed = compressed_inputs(args.FASTA)
@@ -448,7 +481,8 @@ class CommandLineParser:
                 for filename in args.FASTA:
                     _LOG.info("Processing %s", filename)
                     t_file = time.perf_counter()
-                    kept = _RowsByRecord() if masks is not None else None      # --mask_dir: the file's rows, contig = record ordinal
+                    # --mask_dir, --seq_dir: the file's rows, contig = record ordinal
+                    kept = _RowsByRecord() if masks is not None or seqs is not None else None
                     # --track_dir, --bed_dir: the input's files are renamed into place when all of its records are done, and removed
                     # when one raises
                     outs = []
@@ -462,11 +496,14 @@ class CommandLineParser:
                         for out in filter(None, outs):
                             out.abort()
                         raise
-                    if kept is not None:
+                    if masks is not None:
                         outstream.flush()
                         t_mask = time.perf_counter()
                         CommandLineParser._write_mask(filename, masks[filename], kept.rows(), args)
                         _LOG.debug("%s: masked copy %s in %.2f ms", filename, masks[filename], (time.perf_counter() - t_mask) * 1e3)
+                    if seqs is not None:
+                        outstream.flush()
+                        CommandLineParser._write_seq(filename, seqs, kept.rows())
                     dt = time.perf_counter() - t_file
                     _LOG.info("%s: %d bases in %.3f s (%.1f Mbp/s; ingest, upload, forward, MSS, segments and TSV text)", filename, bases, dt,
                               bases / max(dt, 1e-9) / 1e6)
@@ -778,6 +815,71 @@ class CommandLineParser:
         return plan
 
     @staticmethod
+    def _seq_plan(args):
+        """--seq_dir and its options: dict(files={input file: FASTA of its repeats}, classes, flank, width, gzip, fai, level), or None
+        without the flag.  Everything that can be refused without the model is refused here, before any prediction."""
+        sdir = getattr(args, "seq_dir", None)
+        packed_out, fai = bool(getattr(args, "seq_gzip", False)), bool(getattr(args, "seq_fai", False))
+        classes, flank, width = getattr(args, "seq_classes", None), getattr(args, "seq_flank", None), getattr(args, "seq_width", None)
+        if sdir is None:
+            if packed_out or fai or classes is not None or flank is not None or width is not None:
+                sys.exit("--seq_classes, --seq_flank, --seq_width, --seq_gzip and --seq_fai need --seq_dir")
+            return None
+        if fai and packed_out:
+            sys.exit("--seq_fai and --seq_gzip exclude each other: a .fai states offsets of the uncompressed file, a BGZF FASTA would "
+                     "also need a .gzi index, which is not written")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
+            sys.exit("--seq_dir: the repeat sequences of an input are written by one process, in TSV order; they cannot be written by "
+                     "several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
+        flank, width = (0 if flank is None else flank), (60 if width is None else width)
+        if not 1 <= width <= 1 << 30:
+            sys.exit(f"--seq_width must lie in 1..2^30, not {width}")
+        if flank < 0:
+            sys.exit(f"--seq_flank must not be negative, got {flank}")
+        from .tracks import gzip_level, input_basename
+        level = gzip_level(args, 1)
+        files, seen = {}, {}
+        for f in args.FASTA:
+            if f == "-":
+                sys.exit("--seq_dir: standard input cannot be read a second time for the sequences (give a FASTA file)")
+            if f.endswith(".npz"):
+                sys.exit(f"--seq_dir: {f} is a one-hot .npz, not a FASTA file; it holds no sequence bytes to write")
+            base = input_basename(f) + ".repeats.fa" + (".gz" if packed_out else "")
+            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
+                sys.exit(f"--seq_dir: the repeat sequences of {seen[base]} and {f} have the same file name {base}; they would collide")
+            seen[base] = f
+            out = os.path.join(sdir, base)
+            for cand in [out] + ([out + ".fai"] if fai else []):
+                for g in args.FASTA:
+                    if g != "-" and os.path.exists(g) and os.path.realpath(cand) == os.path.realpath(g):
+                        sys.exit(f"--seq_dir: the output {cand} would overwrite the input {g}")
+            files[f] = out
+        if len(files) != len(args.FASTA):
+            sys.exit("--seq_dir: an input file is given twice")
+        os.makedirs(sdir, exist_ok=True)
+        return dict(files=files, classes=classes, flank=flank, width=width, gzip=packed_out, fai=fai, level=level)
+
+    @staticmethod
+    def _check_seq_classes(seqs, classes: int) -> None:
+        bad = [c for c in (seqs["classes"] or ()) if not 0 < c < classes]
+        if bad:
+            sys.exit(f"--seq_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
+
+    @staticmethod
+    def _write_seq(filename: str, seqs, rows) -> None:
+        """The FASTA of one input's repeats (repeatseq.write_repeat_fasta stages its files: renamed on success, removed on failure)."""
+        import time
+
+        from .repeatseq import kept_rows, write_repeat_fasta
+        from .masking import class_bits
+        t0 = time.perf_counter()
+        final = seqs["files"][filename]
+        nbytes = write_repeat_fasta(filename, final, rows, classes=seqs["classes"], flank=seqs["flank"], width=seqs["width"],
+                                    compress=seqs["gzip"], level=seqs["level"], fai_path=final + ".fai" if seqs["fai"] else None)
+        _LOG.info("%s: %d bytes of FASTA, %d of %d rows, to %s in %.2f ms", filename, nbytes,
+                  int(kept_rows(rows, class_bits(seqs["classes"])).sum()), len(rows), final, (time.perf_counter() - t0) * 1e3)
+
+    @staticmethod
     def _check_mask_classes(args, classes: int) -> None:
         bad = [c for c in (getattr(args, "mask_classes", None) or ()) if not 0 < c < classes]
         if bad:
@@ -861,6 +963,8 @@ class CommandLineParser:
             sys.exit("--track_dir belongs to predict, not evaluate")
         if getattr(args, "gzip_level", None) is not None:
             sys.exit("--gzip_level belongs to predict, not evaluate")
+        if any(getattr(args, k, None) not in (None, False) for k in ("seq_dir", "seq_classes", "seq_flank", "seq_width", "seq_gzip", "seq_fai")):
+            sys.exit("--seq_dir belongs to predict, not evaluate")
         from .bed import refuse_on_evaluate
         refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:

@@ -43,6 +43,9 @@ _SIGNATURES = {
     "dgrp_fasta_chunks": (cint, [vp, i64, i64, vp, vp, C.POINTER(i64), vp, i64, vp]),
     "dgrp_fasta_mask_workspace_bytes": (i64, [i64, i64, i64]),
     "dgrp_fasta_mask_batch": (cint, [vp, i64, vp, vp, vp, vp, cint, C.c_uint64, vp, vp, i64, vp]),
+    "dgrp_fasta_extract_workspace_bytes": (i64, [i64, i64, i64]),
+    "dgrp_fasta_extract_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, i64, cint, C.c_uint64, vp, i64, C.POINTER(i64), vp, C.POINTER(i64),
+                                        vp, i64, vp]),
     "dgrp_twobit_workspace_bytes": (i64, [i64]),
     "dgrp_twobit_encode_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
     "dgrp_twobit_text_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp]),

@@ -91,7 +91,7 @@ def check_gzip_flags(args) -> None:
         sys.exit("--track_index needs --track_gzip (a tabix index belongs to a BGZF file)")
     if getattr(args, "gzip_level", None) is not None:
         if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False) or getattr(args, "track_bigwig", False)
-                or getattr(args, "bed_gzip", False) or getattr(args, "bed_bigbed", False)):
+                or getattr(args, "bed_gzip", False) or getattr(args, "bed_bigbed", False) or getattr(args, "seq_gzip", False)):
             sys.exit("--gzip_level needs --mask_gzip or --track_gzip or --bed_gzip")
         gzip_level(args, 0)
 

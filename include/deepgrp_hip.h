@@ -165,6 +165,42 @@ int dgrp_twobit_pack_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_
                            int64_t out_off, int64_t out_cap, int64_t *h_counts, int64_t *h_blob_off, void *d_work,
                            int64_t work_bytes, void *stream);
 
+/* ---- FASTA of the predicted repeats (predict --seq_dir; an addition): the sequence bytes under the TSV rows of nrec plain record
+ * bodies of ONE device buffer, gathered into one compact text.  Records and rows are as for dgrp_fasta_mask_batch: record r = bytes
+ * [h_off[r], h_off[r] + h_len[r]) of d_raw (16-byte aligned; the ranges ascend and do not overlap), a body with LF or CRLF line
+ * ends, sequence position p = the p-th byte that is neither CR nor LF; its rows are d_rows[h_row_off[r] .. h_row_off[r + 1])
+ * (device; any ascending sub-range of the record's rows), ascending and disjoint, 0 <= start < end <= its sequence length.  Its
+ * name is the bytes d_names[h_name_off[r] .. h_name_off[r + 1]) (device, the names back to back, h_name_off [nrec + 1]; at most
+ * 2^20 bytes a name).  A row is kept when (class_mask >> label) & 1.  For a kept row (start, end, label) of a record of len sequence
+ * positions, with A = start - min(flank, start) and B = end + min(flank, len - end), the text is
+ *     >NAME:A-B class<label>LF                      (flank == 0)
+ *     >NAME:A-B class<label> core=<start>-<end>LF   (flank > 0)
+ * followed by the bytes of the sequence positions [A, B) exactly as they are in d_raw, `width` (1 .. 2^30) per line, every line
+ * LF-terminated; numbers are plain decimal.  Every row is read independently: flanks may overlap other rows.  The texts of the kept
+ * rows are written back to back from d_text[0] in row order; *h_text_bytes is their exact size and *h_kept the number of kept rows;
+ * with d_entries (may be NULL; room for one entry per row) entry k states where kept row k's header starts (text_off), where its
+ * first base stands (base_off) and how many bases it has.  No byte of d_text at or beyond *h_text_bytes is ever written.
+ * Checked first, before any device pointer is touched: the host tables and scalars (DGRP_EINVAL), then the workspace
+ * (dgrp_fasta_extract_workspace_bytes of nrec, the sum of h_len and the number of rows; else DGRP_ENOMEM).  nrec == 0 or no rows at
+ * all: nothing to do, both sizes 0.  A bad row: DGRP_EINVAL naming the row, nothing of d_text or d_entries written.  A text larger
+ * than text_cap: DGRP_ENOMEM with *h_text_bytes (the size to call again with) and *h_kept set, nothing written.
+ * Stages: sequence bytes per 4096-byte body tile and in front of every 16-byte word of a tile, scanned; one lane per row checks it
+ * and states its text bytes, scanned; the sizes and the row check are read back -- the entry's one synchronisation of `stream`;
+ * then one workgroup per 4096 bytes of text, 16 per lane: a lane finds its row by binary search over the scanned sizes, formats the
+ * header bytes that fall to it, finds its first source byte by binary search over the record's tile prefix and the tile's word
+ * counts and copies on from there, a line feed behind every `width`-th base.  The write is stream-ordered behind the read-back. */
+typedef struct dgrp_extract_entry {
+    int64_t text_off;   /* offset in d_text of the '>' of the row's header line */
+    int64_t base_off;   /* offset in d_text of the row's first base             */
+    int64_t bases;      /* B - A                                                */
+} dgrp_extract_entry;
+int64_t dgrp_fasta_extract_workspace_bytes(int64_t nrec, int64_t total_bytes, int64_t nrows);
+int dgrp_fasta_extract_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                             const dgrp_segment *d_rows, const int64_t *h_row_off, const uint8_t *d_names,
+                             const int64_t *h_name_off, int64_t flank, int width, uint64_t class_mask, uint8_t *d_text,
+                             int64_t text_cap, int64_t *h_text_bytes, dgrp_extract_entry *d_entries, int64_t *h_kept,
+                             void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3: deepgrp.prediction.fetch_validation_batch (deepgrp/prediction.py:14-37)
  * Number of windows len(range(0, n - T, s)). */
 int64_t dgrp_window_count(int64_t n, int64_t T, int64_t s);
