@@ -19,7 +19,9 @@ Differences, all additive:
     mean and the smallest probability of its class and the share of its bases that carry it, summed on the GPU (deepgrp_amd/bed.py);
     with --bed_gzip the file is BGZF (`.bed.gz`), its lines written and deflated on the GPU, and with --bed_index a tabix index
     (`.bed.gz.tbi`) is built there beside it; with --bed_bigbed the file is a bigBed instead (`.bb`, deepgrp_amd/bigbed.py: binary
-    items with 32-bit coordinates, an R-tree and coverage zoom levels, written and deflated on the GPU);
+    items with 32-bit coordinates, an R-tree and coverage zoom levels, written and deflated on the GPU); with --bed_gff3 the file
+    is GFF3 instead (`.gff3`, deepgrp_amd/gff.py: one `repeat_region` feature per row with the BED's figures as attributes, written
+    on the GPU; `--bed_names A,B,...` names the labels; `.gff3.gz` and `.gff3.gz.tbi` with --bed_gzip and --bed_index);
   * `predict --seq_dir DIR [--seq_classes 1,3] [--seq_flank N] [--seq_width W]` also writes the sequences of the predicted repeats
     of every input as FASTA, DIR/<basename>.repeats.fa: one record `>NAME:A-B class<label>` per TSV row, gathered on the GPU
     (deepgrp_amd/repeatseq.py); with --seq_gzip as BGZF (`.repeats.fa.gz`), with --seq_fai a `.fai` index beside it;
@@ -219,6 +221,15 @@ def _add_bed_options(parser) -> None:
                              "built and deflated on the GPU (--gzip_level, 1 unless given); coordinates up to 2^32 - 1.  Record names "
                              "must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and no "
                              "bigBed for that input.  Not with --bed_gzip or --bed_index")
+    parser.add_argument("--bed_gff3", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the scored repeats as GFF3, DIR/<basename>.gff3, instead of BED text: "
+                             "'##gff-version 3', then per row seqid, deepgrp, repeat_region, start+1, end, mean, '.', '.', "
+                             "ID=r<ordinal>;Name=class<label>;label=;score=;min=;agree= with the BED's figures, written on the GPU.  "
+                             "With --bed_gzip DIR/<basename>.gff3.gz (BGZF), with --bed_index its tabix index (gff preset) beside it.  "
+                             "A record with an empty name: a warning and no GFF3 for that input.  Not with --bed_bigbed")
+    parser.add_argument("--bed_names", type=str, default=s,
+                        help="(addition) with --bed_gff3: the names of the labels 1..classes-1, comma-separated, written as Name= in the "
+                             "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped)")
 
 
 def _add_seq_options(parser) -> None:
@@ -373,7 +384,7 @@ class CommandLineParser:
         if not any(a in ("predict", "train", "verify", "evaluate", "optimize") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
-                           "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score",
+                           "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score", "--bed_names",
                            "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width"}
             i = 0
             while i < len(argv):
@@ -465,6 +476,9 @@ class CommandLineParser:
         _LOG.info("Model loading finished successfully!")
         if masks is not None:
             CommandLineParser._check_mask_classes(args, model.output_shape[2])
+        if bed_plan is not None and bed_plan.class_names is not None and len(bed_plan.class_names) != model.output_shape[2] - 1:
+            sys.exit(f"--bed_names gives {len(bed_plan.class_names)} names, but the model has {model.output_shape[2] - 1} repeat classes "
+                     f"(labels 1..{model.output_shape[2] - 1})")
         pipe = CommandLineParser._pipeline(args, options, model)
         outstream = None
         if rank == 0:
@@ -581,7 +595,7 @@ class CommandLineParser:
                 track_sink = score_sink = None
                 if files is not None:
                     track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
-                if beds is not None and runner.bed is not None:     # --bed_gzip, --bed_bigbed: scores and the write on the device
+                if beds is not None and runner.bed is not None:     # --bed_gzip, --bed_bigbed, --bed_gff3: scores and the write on the device
                     score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
                         merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed, chrom))
                 elif beds is not None:
@@ -589,7 +603,8 @@ class CommandLineParser:
                 rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
                 if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
                     files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
-                if n == 0 and beds is not None and runner.bed is not None and runner.bed.bigbed:    # (a chromosome of the bigBed)
+                if n == 0 and beds is not None and runner.bed is not None and (runner.bed.bigbed or runner.bed.gff3):
+                    # (a chromosome of the bigBed; a name the GFF3 counts)
                     from .bed import empty_write
                     beds.write([name], False, rows, empty_write(runner.bed, name, record_indices(rec)[0], chrom))
                 bases += n

@@ -24,7 +24,12 @@ With `--bed_bigbed` the file is `DIR/<basename>.bb` instead, bigBed as bigbed.py
 typed by an autoSql declaration, 32-bit coordinates (a tabix index ends at 2^29), an R-tree over the item blocks and coverage zoom
 levels.  Item blocks and zoom records are written and deflated on the device (ContigPipeline.bigbed_write); `BedFiles` puts the
 container around them with a bigbed.BigBedBuilder.  An input a bigBed cannot hold (an empty record name, two records of one name,
-a record that ends above 2^32 - 1) gets one warning and no `.bb`."""
+a record that ends above 2^32 - 1) gets one warning and no `.bb`.
+
+With `--bed_gff3` the file is `DIR/<basename>.gff3` instead (`.gff3.gz` with --bed_gzip, `.gff3.gz.tbi` with --bed_index), GFF3 as
+gff.py states it: the same rows and figures, written on the device whether deflated or not (ContigPipeline.gff_write).  The `ID`
+ordinals run through the file, so `BedFiles` counts the lines and hands every write its first ordinal (gff.GffWrite.render).  An
+input with an empty record name gets one warning and no `.gff3`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -49,6 +54,13 @@ class BedPlan(NamedTuple):
     gzip_level: Optional[int] = None                # --bed_gzip: the level (None: plain text from the host formatter)
     index: bool = False                             # --bed_index
     bigbed: bool = False                            # --bed_bigbed (gzip_level is then the level of its zlib streams)
+    gff3: bool = False                              # --bed_gff3 (gzip_level None: the device's text, not deflated)
+    class_names: Optional[tuple] = None             # --bed_names: the name of label 1..C-1, as given (gff.py escapes them)
+
+    @property
+    def on_device(self) -> bool:
+        """Whether the write is made on the device (ContigPipeline.bed_write) rather than from scores on the host."""
+        return self.gzip_level is not None or self.gff3
 
 
 class BedWrite(NamedTuple):
@@ -63,11 +75,11 @@ class BedWrite(NamedTuple):
     last_end: Optional[np.ndarray] = None
 
 
-def bed_path(directory: str, filename: str, gzip: bool = False, bigbed: bool = False) -> str:
+def bed_path(directory: str, filename: str, gzip: bool = False, bigbed: bool = False, gff3: bool = False) -> str:
     from .tracks import input_basename
     if bigbed:
         return os.path.join(directory, input_basename(filename) + ".bb")
-    return os.path.join(directory, input_basename(filename) + ".bed" + (".gz" if gzip else ""))
+    return os.path.join(directory, input_basename(filename) + (".gff3" if gff3 else ".bed") + (".gz" if gzip else ""))
 
 
 def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
@@ -78,12 +90,19 @@ def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
     if p.bigbed:
         from .bigbed import BigBedWrite, end_refusal
         return BigBedWrite(raw, [int(startpos)], end_refusal(raw, [int(startpos)]), chrom0=chrom)
+    if p.gff3:
+        from .gff import GffWrite
+        return GffWrite(raw)
     return BedWrite(b"", raw)
 
 
 def refuse_on_evaluate(args) -> None:
     if getattr(args, "bed_bigbed", False):
         sys.exit("--bed_bigbed belongs to predict, not evaluate")
+    if getattr(args, "bed_gff3", False):
+        sys.exit("--bed_gff3 belongs to predict, not evaluate")
+    if getattr(args, "bed_names", None) is not None:
+        sys.exit("--bed_names belongs to predict, not evaluate")
     if (getattr(args, "bed_dir", None) is not None or getattr(args, "bed_min_score", None) is not None
             or getattr(args, "bed_gzip", False) or getattr(args, "bed_index", False)):
         sys.exit("--bed_dir belongs to predict, not evaluate")
@@ -96,6 +115,18 @@ def plan(args) -> Optional[BedPlan]:
     low = getattr(args, "bed_min_score", None)
     gzip, index = bool(getattr(args, "bed_gzip", False)), bool(getattr(args, "bed_index", False))
     bigbed = bool(getattr(args, "bed_bigbed", False))
+    gff3, cnames = bool(getattr(args, "bed_gff3", False)), getattr(args, "bed_names", None)
+    if gff3 and bdir is None:
+        sys.exit("--bed_gff3 needs --bed_dir")
+    if gff3 and bigbed:
+        sys.exit("--bed_gff3 and --bed_bigbed each write their file instead of the BED text: they do not go together")
+    if cnames is not None and not gff3:
+        sys.exit("--bed_names needs --bed_gff3")
+    if cnames is not None:
+        from .gff import names_refusal
+        cnames = tuple(nm.encode("utf-8", "surrogateescape") for nm in cnames.split(","))
+        if names_refusal(cnames) is not None:
+            sys.exit(names_refusal(cnames))
     if bigbed and bdir is None:
         sys.exit("--bed_bigbed needs --bed_dir")
     if bigbed and (gzip or index):
@@ -116,7 +147,7 @@ def plan(args) -> Optional[BedPlan]:
                  "rank that holds the merged probabilities)")
     paths, seen = {}, {}
     for f in args.FASTA:
-        out = bed_path(bdir, f, gzip, bigbed)
+        out = bed_path(bdir, f, gzip, bigbed, gff3)
         base = os.path.basename(out)
         if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
             sys.exit(f"--bed_dir: the BED files of {seen[base]} and {f} have the same file name {base}; they would collide")
@@ -130,7 +161,7 @@ def plan(args) -> Optional[BedPlan]:
     if gzip or bigbed:
         from .tracks import gzip_level
         level = gzip_level(args, 1)
-    return BedPlan(bdir, int(low), paths, level, index, bigbed)
+    return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames)
 
 
 class _BigBedFile(StagedFile):
@@ -161,15 +192,66 @@ class BedFiles(StagedOutputs):
     warning and no index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed.  With
     p.bigbed the file is a `.bb` with a bigbed.BigBedBuilder on its temporary file and `write` takes a bigbed.BigBedWrite; an
     input a bigBed cannot hold (an empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and
-    no `.bb`: `commit` then removes the temporary file and any `.bb` an earlier run left."""
+    no `.bb`: `commit` then removes the temporary file and any `.bb` an earlier run left.  With p.gff3 the file is a `.gff3[.gz]`
+    that begins with gff.HEADER (a BGZF member of its own), `write` takes a gff.GffWrite and renders it with the lines written so
+    far (`lines`); the names of the index are the escaped seqids of column 1; an input with an empty record name gets one warning
+    and no `.gff3`, as a bigBed does."""
 
     def __init__(self, p: BedPlan, filename: str):
         os.makedirs(p.directory, exist_ok=True)
         self.final, self.min_score, self.bigbed = p.paths[filename], p.min_score, bool(p.bigbed)
         self.gzip = p.gzip_level is not None and not self.bigbed
         self.bb_refused = None
+        self.gff3, self.lines = bool(getattr(p, "gff3", False)), 0
+        preset = ()
+        if self.gff3:
+            from . import gff
+            preset = (gff.PRESET,)
         super().__init__(_LOG, filename, "--bed_index", self.gzip and p.index,
-                         [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index) if self.gzip else StagedFile(self.final)])
+                         [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index, *preset) if self.gzip
+                          else StagedFile(self.final)])
+        if self.gff3:
+            try:
+                self._gff_header(p.gzip_level)
+            except BaseException:
+                self.abort()
+                raise
+
+    def _gff_header(self, level) -> None:
+        """gff.HEADER in front of everything: in a BGZF file a member of its own, which no chunk of the index touches."""
+        from . import gff
+        if self.gzip:
+            sink = self.parts[0]
+            member = gff.header_member(level)
+            sink.data.fh.write(member)
+            sink.off += len(member)
+        else:
+            self.parts[0].fh.write(gff.HEADER)
+
+    def _gff(self, w) -> None:
+        """The write's part of the GFF3 file, or the input's refusal (one warning)."""
+        from . import gff
+        if not isinstance(w, gff.GffWrite):
+            raise ValueError(f"{self.filename}: a GFF3 file is written from GffWrite, not from scores on the host")
+        if self.bb_refused is not None:
+            return
+        if any(not nm for nm in w.names):
+            self.bb_refused = "a record with an empty name"
+            _LOG.warning("%s: no GFF3 file is written (--bed_gff3): %s", self.filename, self.bb_refused)
+            return
+        seqids = [gff.escape_seqid(nm) for nm in w.names]
+        if self.indexed:                                # (the names count in the order even where the write has no line)
+            self.no_index(self.name_order(seqids) or w.refused)
+        if w.render is None:
+            return
+        t = w.render(self.lines)
+        self.lines += t.lines
+        if self.indexed and t.data and t.chunks is None:
+            self.no_index("a write came without its index")
+        if self.gzip:
+            self.append(0, t.data, seqids, t.chunks, t.linear, t.wpref, t.last_end)
+        else:
+            self.append(0, t.data)
 
     def _bigbed(self, w) -> None:
         """The write's part of the bigBed, or the input's refusal (one warning)."""
@@ -194,8 +276,9 @@ class BedFiles(StagedOutputs):
         if self.bb_refused is None:
             return super().commit()
         self.abort()
-        if os.path.exists(self.final):
-            os.remove(self.final)
+        for left in [self.final] + ([self.final + ".tbi"] if self.gff3 and self.gzip and self.parts[0].index_wanted else []):
+            if os.path.exists(left):
+                os.remove(left)
 
     def write(self, names: Sequence, by_contig: bool, rows, scores) -> None:
         """The lines of one record (by_contig false: names[0]) or of a batch (rows["contig"] indexes the names); `scores` is the
@@ -203,6 +286,8 @@ class BedFiles(StagedOutputs):
         bigbed.BigBedWrite."""
         if self.bigbed:
             return self._bigbed(scores)
+        if self.gff3:
+            return self._gff(scores)
         if not isinstance(scores, BedWrite):
             if self.gzip:
                 raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")

@@ -1,4 +1,4 @@
-// What the chains over the scored rows share (bed_kernels.hip: BED text and its tabix pieces; bigbed_kernels.hip: bigBed item blocks
+// What the chains over the scored rows share (bed_kernels.hip: BED and GFF3 text and their tabix pieces; bigbed_kernels.hip: bigBed item blocks
 // and coverage zoom records): the envelope of a row's score, its four figures, the decimal writers, the refusals a check kernel
 // raises as flag words and the head of the workspace they come back in.  Integers only.  Each translation unit gets its own copy
 // (internal linkage), as with scan.h.
@@ -11,7 +11,7 @@ namespace {
 #define BED_MAX_BASES (1ll << 40)          // the envelope of the 64-bit rounding below
 #define BED_MAX_ROWS ((1ll << 31) - 256)   // one thread per row, 256 a workgroup
 
-enum { F_BASES, F_NAME, F_RANGE, F_SPAN, F_END, F_RECORDS, F_STARTS, F_OVERLAP, F_COUNT };
+enum { F_BASES, F_NAME, F_RANGE, F_SPAN, F_END, F_RECORDS, F_STARTS, F_OVERLAP, F_LABEL, F_COUNT };
 static const char *const FLAG_TEXT[F_COUNT] = {
     "a row has no scored base (bases <= 0)",
     "a row names a record outside the names (by_contig: contig not in 0..nnames-1)",
@@ -21,6 +21,7 @@ static const char *const FLAG_TEXT[F_COUNT] = {
     "the records do not ascend with the rows",
     "the starts descend inside a record (tabix needs sorted rows)",
     "a row starts below the end of a row in front of it in its record (bigBed rows ascend and do not overlap)",
+    "a row's label lies outside the class names (1..ncnames)",
 };
 
 // The four figures, R(num, den, k) = floor((2 k num + den) / (2 den)) of the header without a 128-bit division: with
@@ -91,8 +92,8 @@ __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t *a, int64_t n,
     return lo;
 }
 
-// header of the workspace: three totals, then the flag words
-struct bed_head { uint64_t bytes, lines, chunks, pad; uint32_t flags[8]; };
+// header of the workspace: three totals, then the flag words (F_COUNT of them; the head has 256 bytes of the workspace)
+struct bed_head { uint64_t bytes, lines, chunks, pad; uint32_t flags[16]; };
 
 static int bed_refusal(const char *who, const bed_head &h)
 {

@@ -44,10 +44,10 @@ class BgzfSink:
     """One BGZF file from the members of its writes.  With `index`, `builder` (a tabix.IndexBuilder, until someone sets it to None)
     takes every write at the file offset it goes to.  `finish` puts the EOF member behind the members and stages the `.tbi`;
     `commit` renames the file, then its `.tbi` -- or, the index dropped, removes a `.tbi` an earlier run left.  Without `index` a
-    `.tbi` beside the file is not this run's to touch."""
+    `.tbi` beside the file is not this run's to touch.  `preset`: the index's preset where it is not tabix.PRESET_BED."""
 
-    def __init__(self, final: str, index: bool = False):
-        self.index_wanted, self.builder = index, tabix.IndexBuilder() if index else None
+    def __init__(self, final: str, index: bool = False, preset=tabix.PRESET_BED):
+        self.index_wanted, self.builder = index, tabix.IndexBuilder(preset) if index else None
         self.off = 0                                    # bytes of members written
         self.tbi: Optional[StagedFile] = None
         self.data = StagedFile(final)

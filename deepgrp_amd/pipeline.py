@@ -804,6 +804,8 @@ class ContigPipeline:
         `bigbed_write`'s (chrom0: the ordinal of the first record in its input)."""
         if plan.bigbed:                                     # --bed_bigbed: item blocks and zoom blocks instead of text
             return self.bigbed_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan, chrom0)
+        if getattr(plan, "gff3", False):                    # --bed_gff3: GFF3 lines instead of BED lines
+            return self.gff_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan)
         from .bed import BedWrite
         from .gz import bgzf_members_device
         from .tabix import end_refusal
@@ -824,6 +826,107 @@ class ContigPipeline:
             parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends)
         del d_probs, d_rows, d_scores
         return BedWrite(bgzf_members_device(d_text, plan.gzip_level), raw, refused, *parts)
+
+    # predict --bed_gff3: the rows as GFF3 feature lines (gff.py)
+    @staticmethod
+    def _gff_tables(names, class_names):
+        """(escaped record names, their blob and offsets, class-name blob or None, its offsets' address or None, class-name count,
+        the offsets array to keep alive)."""
+        from .gff import escape_seqid, escape_value
+        raw, blob, off = name_blob([escape_seqid(nm) for nm in names])
+        if not class_names:
+            return raw, blob, off, None, None, 0, None
+        _c, cblob, coff = name_blob([escape_value(nm) for nm in class_names])
+        return raw, blob, off, cblob, coff.ctypes.data, len(class_names), coff
+
+    @staticmethod
+    def gff_text_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int = 0, class_names=None,
+                       id0: int = 0):
+        """The GFF3 feature lines (no header) of `d_rows` with `d_scores` (as bed_text_batch takes them) -> (uint8 device tensor,
+        lines): one dgrp_gff_text_batch call, the bytes gff.reference_lines gives for the same arguments.  names and class_names as
+        they come: escaped here, once.  The text is complete behind the call on the current stream."""
+        L = lib()
+        nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
+        if int(d_scores.numel()) != nrows * ROW_SCORE_DTYPE.itemsize:
+            raise ValueError(f"gff_text_batch: {nrows} rows but {int(d_scores.numel())} bytes of scores")
+        raw, blob, off, cblob, coff, nc, _keep = ContigPipeline._gff_tables(names, class_names)
+        wb = int(L.dgrp_gff_text_workspace_bytes(nrows, len(raw), len(blob), nc, len(cblob or b"")))
+        if wb <= 0:
+            raise ValueError(f"gff_text_batch: bad row count {nrows} or names")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        cap = nrows * (max(len(x) for x in raw) + 120)      # (a guess that fits most runs; a longer text takes the retry)
+        got, lines = C.c_int64(0), C.c_int64(0)
+
+        def launch(cap):
+            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            check(L.dgrp_gff_text_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff, nc, _ptr(d_rows), _ptr(d_scores),
+                                        nrows, int(min_score), int(id0), _ptr(text), cap, C.byref(got), C.byref(lines), _ptr(work), wb,
+                                        stream_ptr()), "dgrp_gff_text_batch")
+            return text, (int(got.value),)
+        return _with_room(launch, cap)[:got.value], int(lines.value)
+
+    @staticmethod
+    def gff_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, class_names=None,
+                        id0: int = 0):
+        """bed_index_batch for the text gff_text_batch gives for the same arguments (one dgrp_gff_index_batch call): what
+        gff.reference_index_parts states."""
+        from .tabix import CHUNK_DTYPE, window_prefix
+        L = lib()
+        nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
+        ends = np.ascontiguousarray(rec_end, np.int64)
+        nrec = len(ends)
+        wpref = window_prefix(ends)
+        raw, blob, off, cblob, coff, nc, _keep = ContigPipeline._gff_tables(names, class_names)
+        nwin = int(wpref[-1])
+        wb = int(L.dgrp_gff_index_workspace_bytes(nrows, len(raw), len(blob), nc, len(cblob or b""), nrec))
+        if wb <= 0:
+            raise ValueError(f"gff_index_batch: bad row count {nrows}, record count {nrec} or names")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        linear = torch.full((max(nwin, 1),), -1, dtype=torch.int64, device=dev)
+        last = torch.zeros(max(nrec, 1), dtype=torch.int64, device=dev)
+        cap = min(nrows, 2 * nwin + 4 * nrec + 16)
+        got = C.c_int64(0)
+
+        def launch(cap):
+            chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            check(L.dgrp_gff_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff, nc, _ptr(d_rows), _ptr(d_scores),
+                                         nrows, int(min_score), int(id0), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got),
+                                         _ptr(linear), nwin, _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_gff_index_batch")
+            return chunks, (int(got.value),)
+        host = _with_room(launch, cap)[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
+        return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
+
+    def gff_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan):
+        """One write of a GFF3 file (gff.GffWrite) for the arguments of bed_write: the scores are summed now and stay on the device
+        with the rows; the text, its index pieces and, with plan.gzip_level, its BGZF members are made when bed.BedFiles renders the
+        write with the lines in front of it (the ID ordinals run through the file), on the stream that is current then."""
+        from .gff import GffText, GffWrite
+        from .tabix import end_refusal
+        raw = name_blob(names)[0]
+        r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "gff_write", row0, lengths, startposes)
+        ends = sp + ln
+        refused = end_refusal(ends, raw) if plan.index else None
+        rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+        ro = np.ascontiguousarray(row_off, np.int64)
+        if len(rows) == 0:
+            return GffWrite(raw, refused)
+        if len(ro) != len(ln) + 1 or int(ro[0]) != 0 or int(ro[-1]) != len(rows):
+            raise ValueError("gff_write: the row offsets must cover all rows")
+        d_rows, d_scores = self._row_scores_device(d_probs, r0, ln, sp, rows, ro)
+        made = torch.cuda.Event()
+        made.record()
+
+        def render(id0: int) -> GffText:
+            from .gz import bgzf_members_device
+            made.wait()                                     # (the renderer's stream may be another one than the scores')
+            d_text, lines = self.gff_text_batch(raw, by_contig, d_rows, d_scores, plan.min_score, plan.class_names, id0)
+            parts = (None,) * 4
+            if plan.index and refused is None and int(d_text.numel()):
+                parts = self.gff_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends, plan.class_names, id0)
+            if plan.gzip_level is None:
+                return GffText(d_text.cpu().numpy().tobytes(), lines)
+            return GffText(bgzf_members_device(d_text, plan.gzip_level), lines, *parts)
+        return GffWrite(raw, refused, render)
 
     # predict --bed_bigbed: the rows as bigBed item blocks and coverage zoom records
     @staticmethod

@@ -92,7 +92,8 @@ class RecordRunner:
     `results`).  tracks (a tracks.TrackSpec): every record's track texts come with its rows; scores: the rows' scores
     (pipeline.ROW_SCORE_DTYPE, predict --bed_dir) do -- with bed (a bed.BedPlan with a gzip_level, --bed_gzip) the write's
     bed.BedWrite instead, made on the device where rows and scores then stay, and with a bigBed plan (--bed_bigbed) its
-    bigbed.BigBedWrite, chromIds counted by the record's ordinal in its input.  With either, every key is (header, name), name
+    bigbed.BigBedWrite, chromIds counted by the record's ordinal in its input, and with a GFF3 plan (--bed_gff3, gzip or not) its
+    gff.GffWrite, which bed.BedFiles renders in file order.  With either, every key is (header, name), name
     the first column of the record's track and BED lines (evaluation.record_name), and rows, scores and texts come from one merged
     array; with neither, keys are arbitrary and a record is one fused call (dgrp_predict_record, dgrp_predict_batch).
     probe (a callable): called on the worker's stream while the merged array of a work item is alive, probe(d_probs, row0, lengths,
@@ -103,7 +104,8 @@ class RecordRunner:
                  probe=None):
         self.pipe = pipe
         self.tracks, self.scores, self.probe = tracks, bool(scores), probe
-        self.bed = bed if bed is not None and bed.gzip_level is not None else None     # --bed_gzip: a bed.BedWrite in the scores' place
+        # --bed_gzip, --bed_gff3: a bed.BedWrite or gff.GffWrite in the scores' place
+        self.bed = bed if bed is not None and bed.on_device else None
         self.workers = workers or int(os.environ.get("DGRP_CLI_WORKERS", "16"))
         self.max_bases = max_bases
         m = pipe.model

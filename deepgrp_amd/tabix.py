@@ -16,7 +16,11 @@ run of consecutive lines with the same name and the same bin, from its first lin
 further merging and no pseudo-bin 37450.  The linear index of a sequence has n_intv = ((end of its last line - 1) >> 14) + 1 entries,
 ioff[w] = the begin of its first line whose end is greater than w << 14.  Bytes: `TBI\\1`, n_ref, format 0x10000 (generic, zero-based
 half-open: htslib's `bed` preset), col_seq 1, col_beg 2, col_end 3, meta `#`, skip 0, l_nm, the names with a NUL each; per sequence
-n_bin, the bins in ascending number (bin, n_chunk, (beg, end)... in file order), n_intv, ioff...; n_no_coor = 0 as uint64."""
+n_bin, the bins in ascending number (bin, n_chunk, (beg, end)... in file order), n_intv, ioff...; n_no_coor = 0 as uint64.
+
+A GFF3 file (`predict --bed_gff3`, gff.py) has the same index under htslib's `gff` preset (PRESET_GFF: format 0, col_seq 1, col_beg
+4, col_end 5, one-based closed columns): `payload`, `reference_index`, `read_index`, `query` and `IndexBuilder` take the preset as
+an optional last argument and do for PRESET_BED, the default, what they did without it."""
 from __future__ import annotations
 
 import struct
@@ -28,6 +32,8 @@ import numpy as np
 MIN_SHIFT = 14
 MAX_END = 1 << 29
 FORMAT_BED = 0x10000
+PRESET_BED = (FORMAT_BED, 1, 2, 3)                  # (format, col_seq, col_beg, col_end), columns counted from 1
+PRESET_GFF = (0, 1, 4, 5)                           # generic, one-based closed: htslib's `gff` preset
 _LEVELS = ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1))
 BLOCK = 0xff00                                      # text bytes per member of a write (gz.BGZF_BLOCK)
 
@@ -76,10 +82,11 @@ def reg2bins(beg: int, end: int) -> List[int]:
     return out
 
 
-def payload(names: Sequence[bytes], bins: Sequence[Dict[int, List[Tuple[int, int]]]], linear: Sequence[Sequence[int]]) -> bytes:
+def payload(names: Sequence[bytes], bins: Sequence[Dict[int, List[Tuple[int, int]]]], linear: Sequence[Sequence[int]],
+            preset: Tuple[int, int, int, int] = PRESET_BED) -> bytes:
     """The index's bytes from its parts: per sequence its name, bin -> [(beg, end), ...] in file order, and ioff."""
     blob = b"".join(nm + b"\0" for nm in names)
-    out = [b"TBI\1", struct.pack("<8i", len(names), FORMAT_BED, 1, 2, 3, ord("#"), 0, len(blob)), blob]
+    out = [b"TBI\1", struct.pack("<8i", len(names), *preset, ord("#"), 0, len(blob)), blob]
     for b, lin in zip(bins, linear):
         out.append(struct.pack("<i", len(b)))
         for k in sorted(b):
@@ -108,8 +115,15 @@ def _inflate_member(gz_bytes, off: int) -> Tuple[bytes, int]:
     return zlib.decompress(bytes(gz_bytes[off:off + size]), 31), size
 
 
-def reference_index(gz_bytes: bytes) -> bytes:
-    """The payload of the index of the BGZF bedGraph file `gz_bytes`, from the file alone: a walk over its members, zlib, the lines."""
+def _interval(f: List[bytes], preset) -> Tuple[bytes, int, int]:
+    """(sequence, beg, end), zero-based half-open, of a line's columns under a preset."""
+    beg = int(f[preset[2] - 1])
+    return f[preset[1] - 1], beg if preset[0] & FORMAT_BED else beg - 1, int(f[preset[3] - 1])
+
+
+def reference_index(gz_bytes: bytes, preset: Tuple[int, int, int, int] = PRESET_BED) -> bytes:
+    """The payload of the index of the BGZF bedGraph file `gz_bytes`, from the file alone: a walk over its members, zlib, the lines.
+    Under PRESET_GFF the lines that start with the meta character `#` are skipped, as tabix skips them."""
     starts, tstarts, parts = [], [], []
     off = total = 0
     while off < len(gz_bytes):
@@ -137,8 +151,10 @@ def reference_index(gz_bytes: bytes) -> bytes:
         lines.pop()
     for line in lines:
         v = u + len(line) + 1
-        f = line.split(b"\t")
-        name, beg, end = f[0], int(f[1]), int(f[2])
+        if preset != PRESET_BED and line.startswith(b"#"):
+            u = v
+            continue
+        name, beg, end = _interval(line.split(b"\t"), preset)
         if not name:
             raise IndexRefused("a line with an empty name")
         if not names or names[-1] != name:
@@ -164,16 +180,16 @@ def reference_index(gz_bytes: bytes) -> bytes:
     if run is not None:
         bins[run[0]].setdefault(run[1], []).append((voff(run[2]), voff(run[3])))
     linear = [lin[:((e - 1) >> MIN_SHIFT) + 1] for lin, e in zip(linear, last_end)]
-    return payload(names, bins, linear)
+    return payload(names, bins, linear, preset)
 
 
-def read_index(pl: bytes) -> dict:
+def read_index(pl: bytes, preset: Tuple[int, int, int, int] = PRESET_BED) -> dict:
     """The payload's parts: {"names": [...], "bins": [{bin: [(beg, end), ...]}, ...], "linear": [uint64 array, ...]}."""
     if pl[:4] != b"TBI\1":
         raise ValueError("not a tabix index")
     n_ref, fmt, col_seq, col_beg, col_end, meta, skip, l_nm = struct.unpack_from("<8i", pl, 4)
-    if (fmt, col_seq, col_beg, col_end) != (FORMAT_BED, 1, 2, 3):
-        raise ValueError("not an index of the bed preset")
+    if (fmt, col_seq, col_beg, col_end) != tuple(preset):
+        raise ValueError("not an index of the bed preset" if preset == PRESET_BED else f"not an index of the preset {preset}")
     p = 36
     names = pl[p:p + l_nm].split(b"\0")[:-1]
     p += l_nm
@@ -198,7 +214,7 @@ def read_index(pl: bytes) -> dict:
     return {"names": names, "bins": bins, "linear": linear}
 
 
-def query(index: dict, gz_bytes: bytes, name: bytes, beg: int, end: int) -> List[bytes]:
+def query(index: dict, gz_bytes: bytes, name: bytes, beg: int, end: int, preset: Tuple[int, int, int, int] = PRESET_BED) -> List[bytes]:
     """The lines of sequence `name` that overlap [beg, end), in file order, as tabix finds them: the bins of the region, their
     chunks that end above ioff[beg >> 14], only the members those chunks touch, and an overlap filter on the lines."""
     if name not in index["names"] or beg >= end:
@@ -216,8 +232,10 @@ def query(index: dict, gz_bytes: bytes, name: bytes, beg: int, end: int) -> List
             parts.append(text if off < ce >> 16 else text[:ce & 0xffff])
             off += size
         for line in b"".join(parts)[cb & 0xffff:].split(b"\n")[:-1]:
-            f = line.split(b"\t")
-            if f[0] == name and int(f[1]) < end and int(f[2]) > beg:
+            if preset != PRESET_BED and line.startswith(b"#"):
+                continue
+            seq, lb, le = _interval(line.split(b"\t"), preset)
+            if seq == name and lb < end and le > beg:
                 out.append(line)
     return out
 
@@ -237,7 +255,8 @@ class IndexBuilder:
     appended at a file offset; every write starts a member and its members hold BLOCK text bytes each but the last, so text offset u
     of a write lies in member u // BLOCK of it."""
 
-    def __init__(self):
+    def __init__(self, preset: Tuple[int, int, int, int] = PRESET_BED):
+        self.preset = preset
         self.names: List[bytes] = []
         self.bins: List[Dict[int, List[List[int]]]] = []
         self.linear: List[np.ndarray] = []
@@ -287,4 +306,4 @@ class IndexBuilder:
             self.n_intv[s] = len(lin) if last_end is None else ((int(last_end[r]) - 1) >> MIN_SHIFT) + 1
 
     def payload(self) -> bytes:
-        return payload(self.names, self.bins, [lin[:n] for lin, n in zip(self.linear, self.n_intv)])
+        return payload(self.names, self.bins, [lin[:n] for lin, n in zip(self.linear, self.n_intv)], self.preset)

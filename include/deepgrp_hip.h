@@ -698,6 +698,39 @@ int dgrp_bed_index_batch(const char *names, const int64_t *name_off, int64_t nna
                          dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
                          int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- GFF3 (predict --bed_gff3; deepgrp_amd/gff.py states the file format).  The rows and scores of dgrp_bed_text_batch as GFF3
+ * feature lines, one per emitted row (score >= min_score), in row order:
+ *   seqid \t deepgrp \t repeat_region \t start+1 \t end \t mean \t . \t . \t ID=r<j>;Name=<cname>;label=<L>;score=<score>;min=<min>;agree=<agree> \n
+ * score, mean, min and agree are the four figures of the BED line, the same R and the same envelope; seqid is name rows[r].contig
+ * (by_contig) or name 0; j = id0 + the 1-based ordinal of the line among the emitted lines of this call (id0: the lines the file
+ * holds in front of this text); cname is entry label - 1 of the class-name table (cnames, cname_off, ncnames: laid out like the
+ * names), or "class<label>" when ncnames == 0.  Names and class names are copied verbatim: the caller has escaped them.  The
+ * "##gff-version 3" line is not written here.  Both tables are host memory, staged on the stream, and may be dropped on return.
+ *
+ * dgrp_gff_text_batch keeps the contract of dgrp_bed_text_batch: one check kernel before any byte is written; DGRP_EINVAL with
+ * d_text untouched for that entry's refusals and for a label outside 1..ncnames when ncnames > 0; refused on the host: id0 outside
+ * 0..2^62, descending class-name offsets, a NULL table with ncnames > 0.  *h_bytes (the text's length) and *h_lines (the emitted
+ * lines) are always set on success; when the length exceeds cap nothing is written and the caller retries.  nrows == 0: no device
+ * work, both 0.  The chain: check -> emitted flag per row -> scan (the ordinals) -> line length per row -> scan (the offsets) ->
+ * ONE synchronisation (totals and flags) -> write, one thread per emitted row.  Integers only, no atomics, nothing allocated.
+ * Workspace dgrp_gff_text_workspace_bytes (0 on refused arguments): 32 bytes per row, both tables and 8 bytes per entry of each.
+ *
+ * dgrp_gff_index_batch: the tabix pieces of that text, in offsets of that text: the outputs, intervals ([start, end) of the row),
+ * bins, chunk rule, running-maximum linear rule and refusals of dgrp_bed_index_batch, plus the refusals above.  Behind the line
+ * lengths it runs the kernels of dgrp_bed_index_batch. */
+int64_t dgrp_gff_text_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t ncnames, int64_t cnames_bytes);
+int dgrp_gff_text_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const char *cnames,
+                        const int64_t *cname_off, int64_t ncnames, const dgrp_segment *d_rows, const dgrp_row_score *d_scores,
+                        int64_t nrows, int min_score, int64_t id0, char *d_text, int64_t cap, int64_t *h_bytes, int64_t *h_lines,
+                        void *d_work, int64_t work_bytes, void *stream);
+int64_t dgrp_gff_index_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t ncnames, int64_t cnames_bytes,
+                                       int64_t nrec);
+int dgrp_gff_index_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const char *cnames,
+                         const int64_t *cname_off, int64_t ncnames, const dgrp_segment *d_rows, const dgrp_row_score *d_scores,
+                         int64_t nrows, int min_score, int64_t id0, int64_t nrec, const int64_t *h_rec_end,
+                         dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
+                         int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- bigBed (predict --bed_bigbed; deepgrp_amd/bigbed.py states the file format).  Both entries take the rows and scores of
  * dgrp_bed_text_batch, no names: the record of a row is its contig with by_contig, else 0 (then nrec must be 1); h_rec_end[r] (host,
  * nrec entries, staged on the stream, may be dropped on return) is the end coordinate of record r; a row is EMITTED when its score
