@@ -25,6 +25,10 @@ Differences, all additive:
   * `predict --seq_dir DIR [--seq_classes 1,3] [--seq_flank N] [--seq_width W]` also writes the sequences of the predicted repeats
     of every input as FASTA, DIR/<basename>.repeats.fa: one record `>NAME:A-B class<label>` per TSV row, gathered on the GPU
     (deepgrp_amd/repeatseq.py); with --seq_gzip as BGZF (`.repeats.fa.gz`), with --seq_fai a `.fai` index beside it;
+  * `predict --summary_dir DIR [--summary_bin N] [--bed_names A,B,...]` also writes the repeat content of every input,
+    DIR/<basename>.summary.tsv: per record and label the rows, the bases by kind and case, minimum, maximum and N50 of the row
+    lengths, the share of the record, GC and the agreement with the input's own soft mask, counted on the GPU
+    (deepgrp_amd/summary.py); with --summary_bin also DIR/<basename>.density.tsv, the bases per label in bins of N positions;
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
@@ -229,7 +233,8 @@ def _add_bed_options(parser) -> None:
                              "A record with an empty name: a warning and no GFF3 for that input.  Not with --bed_bigbed")
     parser.add_argument("--bed_names", type=str, default=s,
                         help="(addition) with --bed_gff3: the names of the labels 1..classes-1, comma-separated, written as Name= in the "
-                             "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped)")
+                             "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped); with --summary_dir: the "
+                             "label column of its tables")
 
 
 def _add_seq_options(parser) -> None:
@@ -253,6 +258,20 @@ def _add_seq_options(parser) -> None:
     parser.add_argument("--seq_fai", action="store_true", default=s,
                         help="(addition) with --seq_dir: also write the samtools faidx index DIR/<basename>.repeats.fa.fai; not with "
                              "--seq_gzip")
+
+
+def _add_summary_options(parser) -> None:
+    """The repeat-content flags, like the repeat-sequence flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--summary_dir", type=str, default=s,
+                        help="(addition) also write the repeat content of every input as DIR/<basename of the input>.summary.tsv: per "
+                             "record and label (and for all labels > 0 together, and for the whole file) rows, bases, A, C, G, T, "
+                             "other, lower case, min, max and N50 of the row lengths, share of the record, of its ACGT bases, GC, and "
+                             "recall and precision against the input's own soft mask, counted on the GPU; --bed_names names the "
+                             "labels; one process only")
+    parser.add_argument("--summary_bin", type=int, default=s,
+                        help="(addition) with --summary_dir: also DIR/<basename>.density.tsv, per record and bin of N sequence "
+                             "positions the ACGT bases and the positions under every label > 0 (N >= 1)")
 
 
 class CommandLineParser:
@@ -282,6 +301,7 @@ class CommandLineParser:
         _add_track_options(self.parser)
         _add_bed_options(self.parser)
         _add_seq_options(self.parser)
+        _add_summary_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (GRU) on the GPU")
         train.add_argument("parameter", type=str)
@@ -342,6 +362,7 @@ class CommandLineParser:
         _add_track_options(predict)
         _add_bed_options(predict)
         _add_seq_options(predict)
+        _add_summary_options(predict)
         evaluate = subparsers.add_parser(
             name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
             description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
@@ -385,7 +406,7 @@ class CommandLineParser:
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
                            "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score", "--bed_names",
-                           "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width"}
+                           "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width", "--summary_dir", "--summary_bin"}
             i = 0
             while i < len(argv):
                 if argv[i] in takes_value:
@@ -426,6 +447,7 @@ class CommandLineParser:
         bed_plan = bed.plan(args)
         masks = CommandLineParser._mask_plan(args)
         seqs = CommandLineParser._seq_plan(args)
+        summaries = CommandLineParser._summary_plan(args)
         track_plan = tk.plan(args)
         track_spec = None
         if track_plan is not None:
@@ -479,6 +501,8 @@ class CommandLineParser:
         if bed_plan is not None and bed_plan.class_names is not None and len(bed_plan.class_names) != model.output_shape[2] - 1:
             sys.exit(f"--bed_names gives {len(bed_plan.class_names)} names, but the model has {model.output_shape[2] - 1} repeat classes "
                      f"(labels 1..{model.output_shape[2] - 1})")
+        if summaries is not None:
+            CommandLineParser._check_summary_classes(summaries, model.output_shape[2])
         pipe = CommandLineParser._pipeline(args, options, model)
         outstream = None
         if rank == 0:
@@ -495,8 +519,8 @@ class CommandLineParser:
                 for filename in args.FASTA:
                     _LOG.info("Processing %s", filename)
                     t_file = time.perf_counter()
-                    # --mask_dir, --seq_dir: the file's rows, contig = record ordinal
-                    kept = _RowsByRecord() if masks is not None or seqs is not None else None
+                    # --mask_dir, --seq_dir, --summary_dir: the file's rows, contig = record ordinal
+                    kept = _RowsByRecord() if masks is not None or seqs is not None or summaries is not None else None
                     # --track_dir, --bed_dir: the input's files are renamed into place when all of its records are done, and removed
                     # when one raises
                     outs = []
@@ -518,6 +542,9 @@ class CommandLineParser:
                     if seqs is not None:
                         outstream.flush()
                         CommandLineParser._write_seq(filename, seqs, kept.rows())
+                    if summaries is not None:
+                        outstream.flush()
+                        CommandLineParser._write_summary(filename, summaries, kept.rows(), model.output_shape[2])
                     dt = time.perf_counter() - t_file
                     _LOG.info("%s: %d bases in %.3f s (%.1f Mbp/s; ingest, upload, forward, MSS, segments and TSV text)", filename, bases, dt,
                               bases / max(dt, 1e-9) / 1e6)
@@ -875,6 +902,74 @@ class CommandLineParser:
         return dict(files=files, classes=classes, flank=flank, width=width, gzip=packed_out, fai=fai, level=level)
 
     @staticmethod
+    def _summary_plan(args):
+        """--summary_dir and its options: dict(files={input file: (summary, density table or None)}, bin, names), or None without
+        the flag.  Everything that can be refused without the model is refused here, before any prediction."""
+        sdir, nbin = getattr(args, "summary_dir", None), getattr(args, "summary_bin", None)
+        if sdir is None:
+            if nbin is not None:
+                sys.exit("--summary_bin needs --summary_dir")
+            return None
+        if nbin is not None and nbin < 1:
+            sys.exit(f"--summary_bin must be at least 1, not {nbin}")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
+            sys.exit("--summary_dir: the repeat content of an input is counted by one process, from all of its rows; it cannot be "
+                     "counted by several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
+        names = getattr(args, "bed_names", None)
+        if names is not None:
+            from .gff import names_refusal
+            names = tuple(nm.encode("utf-8", "surrogateescape") for nm in names.split(","))
+            if names_refusal(names) is not None:
+                sys.exit(names_refusal(names))
+            from .summary import names_refusal as columns_refusal
+            if columns_refusal(names) is not None:
+                sys.exit(columns_refusal(names))
+        from .tracks import input_basename
+        files, seen = {}, {}
+        for f in args.FASTA:
+            if f == "-":
+                sys.exit("--summary_dir: standard input cannot be read a second time for the counts (give a FASTA file)")
+            if f.endswith(".npz"):
+                sys.exit(f"--summary_dir: {f} is a one-hot .npz, not a FASTA file; it holds no sequence bytes to count")
+            base = input_basename(f)
+            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
+                sys.exit(f"--summary_dir: the summaries of {seen[base]} and {f} have the same file name {base}.summary.tsv; they would "
+                         "collide")
+            seen[base] = f
+            outs = (os.path.join(sdir, base + ".summary.tsv"), os.path.join(sdir, base + ".density.tsv") if nbin is not None else None)
+            for cand in filter(None, outs):
+                for g in args.FASTA:
+                    if g != "-" and os.path.exists(g) and os.path.realpath(cand) == os.path.realpath(g):
+                        sys.exit(f"--summary_dir: the output {cand} would overwrite the input {g}")
+            files[f] = outs
+        if len(files) != len(args.FASTA):
+            sys.exit("--summary_dir: an input file is given twice")
+        os.makedirs(sdir, exist_ok=True)
+        return dict(files=files, bin=nbin, names=names)
+
+    @staticmethod
+    def _check_summary_classes(summaries, classes: int) -> None:
+        from .summary import MAX_CLASSES, MIN_CLASSES
+        if not MIN_CLASSES <= classes <= MAX_CLASSES:
+            sys.exit(f"--summary_dir: the model has {classes} classes; the summary takes {MIN_CLASSES}..{MAX_CLASSES}")
+        if summaries["names"] is not None and len(summaries["names"]) != classes - 1:
+            sys.exit(f"--bed_names gives {len(summaries['names'])} names, but the model has {classes - 1} repeat classes "
+                     f"(labels 1..{classes - 1})")
+
+    @staticmethod
+    def _write_summary(filename: str, summaries, rows, classes: int) -> None:
+        """The repeat content of one input (summary.write_summary stages its files: renamed on success, removed on failure)."""
+        import time
+
+        from .summary import write_summary
+        t0 = time.perf_counter()
+        final, density = summaries["files"][filename]
+        rep = write_summary(filename, final, rows, classes, bin=summaries["bin"], bin_path=density, names=summaries["names"])
+        _LOG.info("%s: repeat content of %d records (%d counted on the device, %d on the host), %d of %d positions under %d rows, to "
+                  "%s in %.2f ms", filename, rep["records"], rep["device_records"], rep["host_records"], rep["repeat_positions"],
+                  rep["positions"], rep["rows"], final, (time.perf_counter() - t0) * 1e3)
+
+    @staticmethod
     def _check_seq_classes(seqs, classes: int) -> None:
         bad = [c for c in (seqs["classes"] or ()) if not 0 < c < classes]
         if bad:
@@ -980,6 +1075,8 @@ class CommandLineParser:
             sys.exit("--gzip_level belongs to predict, not evaluate")
         if any(getattr(args, k, None) not in (None, False) for k in ("seq_dir", "seq_classes", "seq_flank", "seq_width", "seq_gzip", "seq_fai")):
             sys.exit("--seq_dir belongs to predict, not evaluate")
+        if getattr(args, "summary_dir", None) is not None or getattr(args, "summary_bin", None) is not None:
+            sys.exit("--summary_dir belongs to predict, not evaluate")
         from .bed import refuse_on_evaluate
         refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:

@@ -46,6 +46,8 @@ _SIGNATURES = {
     "dgrp_fasta_extract_workspace_bytes": (i64, [i64, i64, i64]),
     "dgrp_fasta_extract_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, i64, cint, C.c_uint64, vp, i64, C.POINTER(i64), vp, C.POINTER(i64),
                                         vp, i64, vp]),
+    "dgrp_repeat_summary_workspace_bytes": (i64, [i64, i64, i64]),
+    "dgrp_repeat_summary_batch": (cint, [vp, i64, vp, vp, vp, vp, cint, i64, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_twobit_workspace_bytes": (i64, [i64]),
     "dgrp_twobit_encode_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp]),
     "dgrp_twobit_text_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp]),

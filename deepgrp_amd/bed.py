@@ -121,7 +121,9 @@ def plan(args) -> Optional[BedPlan]:
     if gff3 and bigbed:
         sys.exit("--bed_gff3 and --bed_bigbed each write their file instead of the BED text: they do not go together")
     if cnames is not None and not gff3:
-        sys.exit("--bed_names needs --bed_gff3")
+        if getattr(args, "summary_dir", None) is None:
+            sys.exit("--bed_names needs --bed_gff3")
+        cnames = None                                   # (they name the labels of --summary_dir only)
     if cnames is not None:
         from .gff import names_refusal
         cnames = tuple(nm.encode("utf-8", "surrogateescape") for nm in cnames.split(","))

@@ -161,6 +161,83 @@ def _extract_device(L, dev, ptr, h_off, h_len, sel, h_row_off, names: List[bytes
         del d_text, d_entries
 
 
+class WalkGroup:
+    """One ingest group of `walk_groups`.  `dev_recs`: (index in the group, ordinal) of its plain records, `dev_names` their names;
+    their bodies are bytes [h_off[j], h_off[j] + h_len[j]) of the 16-byte aligned device address `ptr` (the group's bytes stay in
+    HBM while the group lives).  `host_recs`: (ordinal, name, chunk bytes, offsets of the sequence bytes in the chunk or None for a
+    record with a non-ASCII sequence line) of the others.  `records`: the records of the file up to and including this group."""
+
+    __slots__ = ("L", "dev", "dev_recs", "dev_names", "host_recs", "ptr", "h_off", "h_len", "records", "_grp")
+
+
+def walk_groups(fasta_path, group_bytes: int, group_records: int, skipped: str):
+    """The second walk over an input that `predict` has read, with its bytes resident: plain FASTA, gzip (gz.open_inflated: the
+    inflated text) or a UCSC .2bit file (twobit.open_text: the text of the file, soft-masked bases lower case), in the ingest's
+    groups.  Yields one WalkGroup per group; a record's ordinal is its place among the records the reference loop yields, in file
+    order.  A record with a non-ASCII sequence line gets one warning that ends in `skipped`.  Close the generator (or exhaust it)
+    to release the file."""
+    import contextlib
+
+    from . import gz
+    from . import twobit as tbit
+    from ._lib import lib
+    from .fasta import RESIDENT_BYTES, _chunk_groups, _upload_file
+    from .masking import _text_encoding
+    from .pipeline import require_gpu
+
+    text = d_text = None
+    if gz.is_gzip(fasta_path):
+        text, d_text, size = gz.open_inflated(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
+    elif tbit.is_twobit(fasta_path):
+        text, d_text, size = tbit.open_text(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
+    else:
+        size = os.path.getsize(fasta_path)
+    if not size:
+        return
+    L = lib()
+    dev = require_gpu()
+    ordinal = 0
+    with contextlib.ExitStack() as stack:
+        if d_text is not None:
+            mm = text
+        else:
+            fh = stack.enter_context(open(fasta_path, "rb"))
+            mm = stack.enter_context(mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ))
+        for grp in _chunk_groups(L, dev, fasta_path, mm, 0, size, group_bytes, group_records, keep_raw=True, d_file=d_text):
+            g0 = grp.starts[grp.c0]
+            g = WalkGroup()
+            g.L, g.dev, g._grp = L, dev, grp
+            g.dev_recs, g.dev_names, g.host_recs = [], [], []
+            for i, c in enumerate(range(grp.c0, grp.c1)):
+                a, b = grp.starts[c], grp.starts[c + 1]
+                if grp.plain(i):
+                    header = mm[a:grp.head_ends[c]].decode("ascii").strip()[1:]
+                    if header:
+                        g.dev_recs.append((i, ordinal))
+                        g.dev_names.append(tbit.record_name(header))
+                        ordinal += 1
+                    continue
+                chunk = mm[a:b]
+                for header, offs in sequence_byte_offsets(chunk):
+                    if offs is None:
+                        _LOG.warning("%s: record %r has sequence lines that are not ASCII; %s", fasta_path, header, skipped)
+                    g.host_recs.append((ordinal, tbit.record_name(header, _text_encoding()), chunk, offs))
+                    ordinal += 1
+            g.ptr, g.h_off, g.h_len = 0, np.zeros(0, np.int64), np.zeros(0, np.int64)
+            if g.dev_recs:
+                # d_raw may be a view of the resident range at any offset: the kernels take the 16-byte aligned address below it
+                # (inside the same allocation) and offsets that include the difference
+                ptr = grp.d_raw.data_ptr()
+                shift = ptr & 15
+                g.ptr = ptr - shift
+                g.h_off = np.array([grp.body0s[i] - g0 + shift for i, _k in g.dev_recs], np.int64)
+                g.h_len = np.array([grp.starts[grp.c0 + i + 1] - grp.body0s[i] for i, _k in g.dev_recs], np.int64)
+            g.records = ordinal
+            del grp
+            yield g
+            del g
+
+
 def write_repeat_fasta(fasta_path, out_path, rows, classes: Optional[Iterable[int]] = None, flank: int = 0, width: int = 60,
                        compress: bool = False, level: int = 1, fai_path=None, group_bytes: int = 256 << 20,
                        group_records: int = 4096) -> int:
@@ -178,12 +255,8 @@ def write_repeat_fasta(fasta_path, out_path, rows, classes: Optional[Iterable[in
     import torch
 
     from . import gz
-    from . import twobit as tbit
-    from ._lib import lib
-    from .fasta import RESIDENT_BYTES, _chunk_groups, _upload_file
-    from .masking import _text_encoding
     from .outfiles import StagedFile
-    from .pipeline import SEGMENT_DTYPE, require_gpu
+    from .pipeline import SEGMENT_DTYPE
 
     if not 1 <= int(width) <= MAX_WIDTH:
         raise ValueError(f"line width must lie in 1..2^30, not {width}")
@@ -212,14 +285,6 @@ def write_repeat_fasta(fasta_path, out_path, rows, classes: Optional[Iterable[in
         if fai_path is not None:
             fai = StagedFile(str(fai_path))
             staged.append(fai)
-        text = d_text = None
-        if gz.is_gzip(fasta_path):
-            text, d_text, size = gz.open_inflated(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
-        elif tbit.is_twobit(fasta_path):
-            text, d_text, size = tbit.open_text(fasta_path, RESIDENT_BYTES, require_gpu, _upload_file)
-        else:
-            size = os.path.getsize(fasta_path)
-        packed = d_text is not None
 
         def emit(data, dev=None):
             """One piece of text: host bytes or a device tensor."""
@@ -234,87 +299,57 @@ def write_repeat_fasta(fasta_path, out_path, rows, classes: Optional[Iterable[in
                 out.fh.write(data)
             written += n
 
-        if size:
-            L = lib()
-            dev = require_gpu()
-            with contextlib.ExitStack() as stack:
-                if packed:
-                    mm = text
-                else:
-                    fh = stack.enter_context(open(fasta_path, "rb"))
-                    mm = stack.enter_context(mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ))
-                for grp in _chunk_groups(L, dev, fasta_path, mm, 0, size, group_bytes, group_records, keep_raw=True, d_file=d_text):
-                    g0 = grp.starts[grp.c0]
-                    dev_recs, dev_names, host_recs = [], [], []     # (i, ordinal), names; (ordinal, name, chunk bytes, offsets)
-                    for i, c in enumerate(range(grp.c0, grp.c1)):
-                        a, b = grp.starts[c], grp.starts[c + 1]
-                        if grp.plain(i):
-                            header = mm[a:grp.head_ends[c]].decode("ascii").strip()[1:]
-                            if header:
-                                dev_recs.append((i, ordinal))
-                                dev_names.append(tbit.record_name(header))
-                                ordinal += 1
-                            continue
-                        chunk = mm[a:b]
-                        for header, offs in sequence_byte_offsets(chunk):
-                            if offs is None:
-                                _LOG.warning("%s: record %r has sequence lines that are not ASCII; none of its repeats is written",
-                                             fasta_path, header)
-                            host_recs.append((ordinal, tbit.record_name(header, _text_encoding()), chunk, offs))
-                            ordinal += 1
-                    pieces = iter(())
-                    mixed = bool(host_recs)
-                    if dev_recs:
-                        # d_raw may be a view of the resident range at any offset: the kernel takes the 16-byte aligned address below
-                        # it (inside the same allocation) and offsets that include the difference
-                        ptr = grp.d_raw.data_ptr()
-                        shift = ptr & 15
-                        h_off = np.array([grp.body0s[i] - g0 + shift for i, _k in dev_recs], np.int64)
-                        h_len = np.array([grp.starts[grp.c0 + i + 1] - grp.body0s[i] for i, _k in dev_recs], np.int64)
-                        per = [rows_of(k) for _i, k in dev_recs]
-                        h_row_off = np.zeros(len(dev_recs) + 1, np.int64)
-                        np.cumsum([len(p) for p in per], out=h_row_off[1:])
-                        if h_row_off[-1]:
-                            sel = np.concatenate(per)
-                            pieces = _extract_device(L, dev, ptr - shift, h_off, h_len, sel, h_row_off, dev_names, bits, flank, width,
-                                                     mixed or fai is not None, str(fasta_path))
-                            rec_of = np.searchsorted(h_row_off, np.arange(sel.size), side="right") - 1
-                    if not mixed:
-                        for d_piece, entries, lo, hi in pieces:
-                            if fai is not None:
-                                keep = np.flatnonzero(kept_rows(sel[lo:hi], bits)) + lo
-                                for j in np.unique(rec_of[keep]).tolist():
-                                    m = rec_of[keep] == j
-                                    fai.fh.write(fai_lines(dev_names[j], sel["start"][keep[m]], entries[m], flank, width, written))
-                            emit(d_piece)
-                            del d_piece
-                    else:
-                        # (rare) records of both paths in one group: the device text comes down and is cut by record
-                        texts = {}                                  # ordinal -> [(text, entries, row starts)]
-                        for d_piece, entries, lo, hi in pieces:
-                            h_piece = d_piece.cpu().numpy().tobytes()
+        with contextlib.closing(walk_groups(fasta_path, group_bytes, group_records, "none of its repeats is written")) as groups:
+            for g in groups:
+                ordinal = g.records
+                L, dev, dev_recs, dev_names, host_recs = g.L, g.dev, g.dev_recs, g.dev_names, g.host_recs
+                pieces = iter(())
+                mixed = bool(host_recs)
+                if dev_recs:
+                    per = [rows_of(k) for _i, k in dev_recs]
+                    h_row_off = np.zeros(len(dev_recs) + 1, np.int64)
+                    np.cumsum([len(p) for p in per], out=h_row_off[1:])
+                    if h_row_off[-1]:
+                        sel = np.concatenate(per)
+                        pieces = _extract_device(L, dev, g.ptr, g.h_off, g.h_len, sel, h_row_off, dev_names, bits, flank, width,
+                                                 mixed or fai is not None, str(fasta_path))
+                        rec_of = np.searchsorted(h_row_off, np.arange(sel.size), side="right") - 1
+                if not mixed:
+                    for d_piece, entries, lo, hi in pieces:
+                        if fai is not None:
                             keep = np.flatnonzero(kept_rows(sel[lo:hi], bits)) + lo
-                            ends = np.append(entries["text_off"][1:], len(h_piece))
                             for j in np.unique(rec_of[keep]).tolist():
-                                m = np.flatnonzero(rec_of[keep] == j)
-                                t0, t1 = int(entries["text_off"][m[0]]), int(ends[m[-1]])
-                                e = entries[m].copy()
-                                e["text_off"] -= t0
-                                e["base_off"] -= t0
-                                texts.setdefault(dev_recs[j][1], []).append((h_piece[t0:t1], e, sel["start"][keep[m]], dev_names[j]))
-                            del d_piece
-                        for k, name, chunk, offs in host_recs:
-                            if offs is None:
-                                continue
-                            rk = rows_of(k)
-                            t, e = extract_host(chunk, offs, name, rk, bits, flank, width, f"{fasta_path}: record {name!r}")
-                            texts[k] = [(t, e, rk["start"][kept_rows(rk, bits)], name)]
-                        for k in sorted(texts):
-                            for t, e, starts, name in texts[k]:
-                                if fai is not None:
-                                    fai.fh.write(fai_lines(name, starts, e, flank, width, written))
-                                emit(t, dev)
-                    del grp
+                                m = rec_of[keep] == j
+                                fai.fh.write(fai_lines(dev_names[j], sel["start"][keep[m]], entries[m], flank, width, written))
+                        emit(d_piece)
+                        del d_piece
+                else:
+                    # (rare) records of both paths in one group: the device text comes down and is cut by record
+                    texts = {}                                  # ordinal -> [(text, entries, row starts)]
+                    for d_piece, entries, lo, hi in pieces:
+                        h_piece = d_piece.cpu().numpy().tobytes()
+                        keep = np.flatnonzero(kept_rows(sel[lo:hi], bits)) + lo
+                        ends = np.append(entries["text_off"][1:], len(h_piece))
+                        for j in np.unique(rec_of[keep]).tolist():
+                            m = np.flatnonzero(rec_of[keep] == j)
+                            t0, t1 = int(entries["text_off"][m[0]]), int(ends[m[-1]])
+                            e = entries[m].copy()
+                            e["text_off"] -= t0
+                            e["base_off"] -= t0
+                            texts.setdefault(dev_recs[j][1], []).append((h_piece[t0:t1], e, sel["start"][keep[m]], dev_names[j]))
+                        del d_piece
+                    for k, name, chunk, offs in host_recs:
+                        if offs is None:
+                            continue
+                        rk = rows_of(k)
+                        t, e = extract_host(chunk, offs, name, rk, bits, flank, width, f"{fasta_path}: record {name!r}")
+                        texts[k] = [(t, e, rk["start"][kept_rows(rk, bits)], name)]
+                    for k in sorted(texts):
+                        for t, e, starts, name in texts[k]:
+                            if fai is not None:
+                                fai.fh.write(fai_lines(name, starts, e, flank, width, written))
+                            emit(t, dev)
+                del g
         if contig.size and int(contig[-1]) >= ordinal:
             raise ValueError(f"{fasta_path}: rows name record {int(contig[-1])}, but only {ordinal} records were read")
         if compress:

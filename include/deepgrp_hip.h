@@ -201,6 +201,38 @@ int dgrp_fasta_extract_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *
                              int64_t text_cap, int64_t *h_text_bytes, dgrp_extract_entry *d_entries, int64_t *h_kept,
                              void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- Repeat content table (predict --summary_dir; an addition): how much of every record lies under every label, by kind of byte
+ * and case, and -- with bin > 0 -- per bin of `bin` sequence positions.  Records and rows as for dgrp_fasta_extract_batch: record r =
+ * bytes [h_off[r], h_off[r] + h_len[r]) of d_raw (16-byte aligned; the ranges ascend and do not overlap), a body with LF or CRLF
+ * line ends, sequence position p = the p-th byte that is neither CR nor LF; its rows are d_rows[h_row_off[r] .. h_row_off[r + 1])
+ * (device), ascending and disjoint.  The label of a position is the label of the row that covers it, 0 where none does; the kind
+ * of a byte is dgrp_encode's class (A,a=0 C,c=1 G,g=2 T,t=3 else 4); a byte is lower case in 'a'..'z'.
+ *   d_counts [nrec][C][5][2] int64: positions of record r per (label, kind, lower case);
+ *   d_bins   [h_bin_off[nrec]][C] int64 (bin > 0; else unused, may be NULL): row h_bin_off[r] + p / bin is the bin of position p of
+ *            record r; column 0 = its ACGT bases (kind < 4), column l >= 1 = its positions under label l.  The host does not know a
+ *            record's sequence length (h_len counts the line ends too): h_bin_off[r + 1] - h_bin_off[r] >= ceil(h_len[r] / bin), and
+ *            the bins behind the sequence stay 0;
+ *   *d_bad   int64: -1, or the smallest index i (into d_rows) of a bad row: a label outside 0..C-1, start < 0, end <= start, end
+ *            beyond the record's sequence, or the next row of the record starting below its end.  A bad row is left out of every
+ *            count; the call still returns DGRP_OK (a bad row cannot be known without a read-back; the caller reads *d_bad with
+ *            the tables).  Where the rows that are left still overlap the counts are unspecified; no access leaves the arrays.
+ * The three outputs are zeroed here (*d_bad to -1) on every call.  Everything is enqueued on `stream`: nothing synchronises,
+ * copies back or allocates; the host tables are read before the call returns.  Checked first, before any device pointer is
+ * touched: the host tables and scalars (DGRP_EINVAL; 2 <= C <= 64, bin >= 0), then the workspace
+ * (dgrp_repeat_summary_workspace_bytes of nrec, the sum of h_len and the number of rows; else DGRP_ENOMEM).  nrec == 0: nothing is
+ * queued, nothing is written.
+ * Stages: sequence bytes per 4096-byte body tile, scanned; one lane per row checks it, the good rows are compacted into the
+ * workspace; one lane per tile finds its record, first position, rows and bin; then one workgroup per tile at a time (a
+ * workgroup walks consecutive tiles), one aligned 16-byte load per lane: a lane
+ * finds the row of its first position by binary search and walks on; counts are summed in an LDS table of C * 10 counters per
+ * workgroup (several copies of each, by lane) and flushed with 64-bit integer atomics when the record changes; bin counts go to
+ * d_bins with integer atomics (through LDS where a tile lies in one bin).  Integer sums do not depend on their order: the same call
+ * gives the same bytes. */
+int64_t dgrp_repeat_summary_workspace_bytes(int64_t nrec, int64_t total_bytes, int64_t nrows);
+int dgrp_repeat_summary_batch(const uint8_t *d_raw, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                              const dgrp_segment *d_rows, const int64_t *h_row_off, int C, int64_t bin, const int64_t *h_bin_off,
+                              int64_t *d_counts, int64_t *d_bins, int64_t *d_bad, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- A3: deepgrp.prediction.fetch_validation_batch (deepgrp/prediction.py:14-37)
  * Number of windows len(range(0, n - T, s)). */
 int64_t dgrp_window_count(int64_t n, int64_t T, int64_t s);
