@@ -26,7 +26,15 @@ class TrainJob(C.Structure):
                 ("work_bytes", i64)]
 
 
-TRAIN_MAX_JOBS = 8                  # DGRP_TRAIN_MAX_JOBS
+class InflateStreamStats(C.Structure):
+    """struct dgrp_inflate_stream_stats"""
+    _fields_ = [(k, C.c_int64) for k in ("spans", "candidates", "repaired", "rounds", "longest_span", "false_starts", "chunks", "reserved")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+TRAIN_MAX_JOBS = 8                 # DGRP_TRAIN_MAX_JOBS
 
 _SIGNATURES = {
     "dgrp_abi_version": (cint, []),
@@ -135,6 +143,11 @@ _SIGNATURES = {
     "dgrp_inflate_raw_host": (cint, [vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(cint)]),
     "dgrp_inflate_workspace_bytes": (i64, [i64]),
     "dgrp_inflate_batch": (cint, [vp, i64, i64, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(cint), vp, i64, vp]),
+    "dgrp_inflate_stream_host": (cint, [vp, i64, i64, i64, cint, vp, i64, C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(cint)]),
+    "dgrp_inflate_stream_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_inflate_stream_scan": (cint, [vp, i64, i64, i64, i64, cint, C.POINTER(i64), vp, C.POINTER(cint), vp, i64, vp]),
+    "dgrp_inflate_stream_write": (cint, [vp, i64, i64, i64, vp, vp, i64, C.POINTER(C.c_uint32), C.POINTER(i64), C.POINTER(cint), vp, i64,
+                                         vp]),
     "dgrp_bgzf_bound": (i64, [i64, cint]),
     "dgrp_bgzf_workspace_bytes": (i64, [i64]),
     "dgrp_bgzf_compress": (cint, [vp, i64, vp, i64, C.POINTER(i64), cint, vp, i64, vp]),

@@ -3,7 +3,10 @@
 A gzip file is recognised by its magic bytes, not by its name.  A BGZF file (every member carries the `BC` extra subfield with its
 compressed size BSIZE, and inflates to at most 64 KiB) is split into its members by a walk over the member headers on the host;
 the compressed file is uploaded as it is and the members are inflated side by side on the device (dgrp_inflate_batch), straight
-into the buffer the FASTA ingest consumes.  Any other gzip file (one member as gzip/pigz write it, members without `BC`) is
+into the buffer the FASTA ingest consumes.  A file of one plain member (as gzip and pigz write it) of at least
+PLAIN_DEVICE_MIN_BYTES is uploaded as it is too and its one DEFLATE stream is inflated on the device as many spans
+(dgrp_inflate_stream_scan / _write); whenever that path declines -- several members, a stream of stored or fixed blocks, a corrupt
+file -- and for any other gzip file (members without `BC`) the file is
 inflated on the host with zlib and uploaded.  Corrupt input raises GzipError naming the file and the compressed byte offset of
 the first bad member.
 
@@ -27,7 +30,9 @@ _LOG = logging.getLogger(__name__)
 # DGRP_INFLATE_* (include/deepgrp_hip.h)
 REASONS = {1: "input ends inside the DEFLATE stream", 2: "invalid block type", 3: "stored block LEN/NLEN mismatch",
            4: "invalid code lengths", 5: "invalid symbol", 6: "distance too far back", 7: "more output than ISIZE",
-           8: "CRC-32 mismatch", 9: "output shorter than ISIZE", 10: "DEFLATE stream ends before the member's trailer"}
+           8: "CRC-32 mismatch", 9: "output shorter than ISIZE", 10: "DEFLATE stream ends before the member's trailer",
+           11: "a span longer than PLAIN_MAX_SPAN_BYTES (no block starts to find, as in a stream of stored or fixed blocks)",
+           12: "the chain of spans is not closed after PLAIN_MAX_ROUNDS rounds"}
 
 
 class GzipError(ValueError):
@@ -206,9 +211,88 @@ class DeviceText:
         return int(self.d[k])
 
 
+# ---- plain gzip (one member, one DEFLATE stream) on the device: dgrp_inflate_stream_scan / _write (include/deepgrp_hip.h).
+# DESIGN 5d states each value with the run it came from.
+PLAIN_CHUNK_BYTES = 16 << 10          # compressed bytes per chunk: one span start is looked for in each (below zlib's blocks of FASTA)
+PLAIN_MAX_SPAN_BYTES = 1 << 20        # one wave decodes a span serially: above this it costs what zlib costs for a 70 MB file
+PLAIN_MAX_ROUNDS = 16                 # counting rounds of the chain (one more for every start repaired behind a repaired one)
+PLAIN_DEVICE_MIN_BYTES = 16 << 20     # compressed size from which the device path is taken (float("inf"): never)
+
+
+def plain_data_off(buf) -> Optional[int]:
+    """Offset of the DEFLATE data of the first gzip member of `buf` (FEXTRA, FNAME, FCOMMENT and FHCRC skipped), or None when the
+    header is not one this parser takes or leaves no room for a trailer."""
+    n = len(buf)
+    if n < 18 or buf[0:2] != MAGIC or buf[2] != 8 or buf[3] & 0xe0:
+        return None
+    flg, pos = buf[3], 10
+    if flg & 4:
+        pos += 2 + struct.unpack_from("<H", buf, pos)[0]
+    for bit in (8, 16):                                              # FNAME, FCOMMENT: zero-terminated
+        if flg & bit:
+            if pos >= n:
+                return None
+            end = buf.find(b"\0", pos)
+            if end < 0:
+                return None
+            pos = end + 1
+    if flg & 2:
+        pos += 2
+    return pos if pos <= n - 8 else None
+
+
+def inflate_stream_device(path, size: int, data_off: int, limit: int, dev, upload):
+    """The one-member gzip file `path` inflated on the device.  -> (uint8 device tensor, None) when scan and write succeed, the
+    final block ends 8 bytes before the end of the file and CRC-32 and ISIZE match the trailer; (None, why not) otherwise.  Raises
+    only the `too_large` error."""
+    import ctypes as C
+
+    import torch
+
+    from ._lib import InflateStreamStats, check, lib
+    from .pipeline import stream_ptr
+    L = lib()
+    d_in = upload(path, size, dev)
+    wb = int(L.dgrp_inflate_stream_workspace_bytes(size, PLAIN_CHUNK_BYTES))
+    if wb <= 0:
+        return None, "a size the device entry does not take"
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    total, stats, reason = C.c_int64(0), InflateStreamStats(), C.c_int(0)
+    rc = L.dgrp_inflate_stream_scan(d_in.data_ptr(), size, data_off, PLAIN_CHUNK_BYTES, PLAIN_MAX_SPAN_BYTES, PLAIN_MAX_ROUNDS,
+                                    C.byref(total), C.byref(stats), C.byref(reason), work.data_ptr(), wb, stream_ptr())
+    if rc == -5:                                                     # DGRP_EDATA
+        return None, "scan: " + REASONS.get(reason.value, f"reason {reason.value}")
+    check(rc, "dgrp_inflate_stream_scan")
+    n = int(total.value)
+    if n > limit:
+        raise too_large(path, n, limit)
+    if n == 0:
+        return None, "no text"
+    d_out = torch.empty(n, dtype=torch.uint8, device=dev)
+    d_sym = torch.empty(n, dtype=torch.int16, device=dev)
+    crc, used = C.c_uint32(0), C.c_int64(0)
+    rc = L.dgrp_inflate_stream_write(d_in.data_ptr(), size, data_off, PLAIN_CHUNK_BYTES, d_sym.data_ptr(), d_out.data_ptr(), n,
+                                     C.byref(crc), C.byref(used), C.byref(reason), work.data_ptr(), wb, stream_ptr())
+    if rc == -5:
+        return None, "write: " + REASONS.get(reason.value, f"reason {reason.value}")
+    check(rc, "dgrp_inflate_stream_write")
+    if used.value != size - 8:
+        return None, "more than one member" if used.value < size - 8 else "truncated trailer"
+    want_crc, isize = struct.unpack("<II", d_in[size - 8:].cpu().numpy().tobytes())
+    if crc.value != want_crc or (n & 0xffffffff) != isize:
+        return None, "CRC-32 or ISIZE mismatch"
+    s = stats.as_dict()
+    _LOG.info("%s: gzip but not BGZF, inflated on the device: %d spans of %d chunks (%d starts found, %d repaired, %d false), "
+              "%d rounds, longest span %d bytes", path, s["spans"], s["chunks"], s["candidates"], s["repaired"], s["false_starts"],
+              s["rounds"], s["longest_span"])
+    return d_out, None
+
+
 def open_inflated(path, limit: int, dev_fn, upload):
-    """(host view, device bytes, size) of the gzip file `path`: the member walk, then the device (BGZF) or zlib (other gzip).
-    Everything that can be refused -- corrupt headers, an inflated size above `limit` -- is refused before `dev_fn()` is called."""
+    """(host view, device bytes, size) of the gzip file `path`: the member walk, then the device (BGZF; one-member gzip of at least
+    PLAIN_DEVICE_MIN_BYTES) or zlib (every other gzip file, and whatever the device path hands back).  Everything that can be
+    refused -- corrupt headers, an inflated size above `limit` -- is refused before `dev_fn()` is called, except on the device path
+    of a plain gzip file, which needs the device to learn the size."""
     import mmap
     with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as cm:
         members = walk_members(cm, path)
@@ -218,7 +302,22 @@ def open_inflated(path, limit: int, dev_fn, upload):
             if total > limit:
                 raise too_large(path, total, limit)
         else:
-            _LOG.info("%s: gzip but not BGZF, inflated on the host with zlib; `bgzip` would let the GPU inflate it", path)
+            why, dev = None, None
+            data_off = plain_data_off(cm)
+            if members.size < PLAIN_DEVICE_MIN_BYTES:
+                why = f"smaller than {PLAIN_DEVICE_MIN_BYTES} bytes"
+            elif data_off is None:
+                why = "a member header the device path does not take"
+            else:
+                try:
+                    dev = dev_fn()
+                except Exception:                                    # (raised again below, after what zlib refuses)
+                    why = "no device"
+            if why is None:
+                d_text, why = inflate_stream_device(path, members.size, data_off, limit, dev, upload)
+                if d_text is not None:
+                    return DeviceText(d_text), d_text, int(d_text.numel())
+            _LOG.info("%s: gzip but not BGZF, inflated on the host with zlib (%s); `bgzip` would let the GPU inflate it", path, why)
             text = inflate_host(cm, path, limit)
             total = len(text)
     if total == 0:

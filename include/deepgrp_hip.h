@@ -845,6 +845,50 @@ int dgrp_inflate_batch(const uint8_t *d_in, int64_t in_bytes, int64_t nmem, cons
                        const int64_t *h_out_off, uint8_t *d_out, int64_t out_bytes, int64_t *h_bad, int *h_reason, void *d_work,
                        int64_t work_bytes, void *stream);
 
+/* ---- plain gzip input: ONE DEFLATE stream inflated as many spans (deepgrp_amd/csrc/inflate_stream.h).  The stream is cut into
+ * chunks of chunk_bytes (64 .. 2^28) compressed bytes; in every chunk but the first the first bit offset that looks like the start
+ * of a non-final dynamic block is a span start; spans are decoded side by side without the 32 KiB of text in front of them (first
+ * counted, then into 16-bit symbols with markers for bytes of that window), a chain from bit 0 confirms the starts and replaces
+ * the wrong and the missing ones, and the markers are resolved once the windows are known.  A stream without any such start is one
+ * span.  The chain refuses (DGRP_EDATA) a span of more than max_span_bytes (1 .. 2^31 - 64) compressed bytes and a chain that is
+ * not closed after max_rounds (>= 1) counting rounds, with these reasons beside the stream errors above: */
+#define DGRP_INFLATE_ESPAN 11          /* a span is longer than max_span_bytes                      */
+#define DGRP_INFLATE_EROUNDS 12        /* the chain is not closed after max_rounds rounds           */
+typedef struct dgrp_inflate_stream_stats {
+    int64_t spans;        /* spans of the closed chain                                                                  */
+    int64_t candidates;   /* chunks in which the finder found a start                                                   */
+    int64_t repaired;     /* starts the chain replaced by the landing of the span in front                              */
+    int64_t rounds;       /* counting rounds                                                                            */
+    int64_t longest_span; /* compressed bytes of the longest span                                                       */
+    int64_t false_starts; /* of `repaired`: a start of the finder in front of the landing, that is, not a block start   */
+    int64_t chunks;
+    int64_t reserved;
+} dgrp_inflate_stream_stats;
+
+/* The whole algorithm on the HOST through the same code (finder, counting pass, chain, symbols, window walk, resolve): the raw
+ * DEFLATE stream h_in[0, in_len) into h_out[0, out_cap).  *h_out_len = bytes produced, *h_in_used = input bytes up to the end of the
+ * final block (both 0 on failure), *h_reason = DGRP_INFLATE_* (DGRP_INFLATE_EOUTPUT when the text exceeds out_cap; nothing is
+ * written then).  Returns 0, DGRP_EDATA, or DGRP_EINVAL for bad arguments.  Needs no device. */
+int dgrp_inflate_stream_host(const uint8_t *h_in, int64_t in_len, int64_t chunk_bytes, int64_t max_span_bytes, int max_rounds,
+                             uint8_t *h_out, int64_t out_cap, int64_t *h_out_len, int64_t *h_in_used,
+                             dgrp_inflate_stream_stats *h_stats, int *h_reason);
+
+/* The same on the DEVICE in two calls, because the output is allocated between them.  The stream is d_in[data_off, in_bytes)
+ * (for a gzip member: behind its header; whatever follows the final block, such as the trailer, is not read as stream).
+ * scan: finder, counting rounds and chain; *h_total = bytes of text, *h_stats as the host entry gives them (the chain is the same
+ * code), and the chain stays in the workspace.  write: the symbols into d_sym[0, out_bytes) (uint16), the text into
+ * d_out[0, out_bytes) with out_bytes = *h_total, *h_crc = CRC-32 of the text, *h_in_used = bytes of d_in up to the end of the final
+ * block (data_off included), from the chain scan left in the same workspace for the same d_in, in_bytes, data_off and chunk_bytes
+ * (anything else in the workspace is DGRP_EINVAL and launches nothing).  Workspace: dgrp_inflate_stream_workspace_bytes(in_bytes,
+ * chunk_bytes) (0 for sizes the entries refuse), 256-byte aligned.  Both are synchronous; bad arguments launch nothing. */
+int64_t dgrp_inflate_stream_workspace_bytes(int64_t in_bytes, int64_t chunk_bytes);
+int dgrp_inflate_stream_scan(const uint8_t *d_in, int64_t in_bytes, int64_t data_off, int64_t chunk_bytes, int64_t max_span_bytes,
+                             int max_rounds, int64_t *h_total, dgrp_inflate_stream_stats *h_stats, int *h_reason, void *d_work,
+                             int64_t work_bytes, void *stream);
+int dgrp_inflate_stream_write(const uint8_t *d_in, int64_t in_bytes, int64_t data_off, int64_t chunk_bytes, uint16_t *d_sym,
+                              uint8_t *d_out, int64_t out_bytes, uint32_t *h_crc, int64_t *h_in_used, int *h_reason, void *d_work,
+                              int64_t work_bytes, void *stream);
+
 /* ---- compressed output (an addition): n bytes as a BGZF file, the way bgzip lays it out -- members of 0xff00 input bytes (the last
  * one shorter; n = 0: none), each an 18-byte header with BC / BSIZE, ONE DEFLATE block, CRC-32 and ISIZE; with `eof` the empty
  * EOF member (28 bytes) behind them.  The block holds literals under a per-member dynamic Huffman code (no matches), or is a

@@ -1,7 +1,9 @@
 """Compressed input: one synthetic record of [Mbp] (default 250) in /dev/shm as .fa, as BGZF (level 6, written
 with Python's zlib the way bgzip lays it out) and as plain gzip (level 6, one member).  For each form the end-to-end rate of
 bench.py's e2e leg (read_multi_fasta_device -> RecordRunner -> TSV bytes in host memory), then the inflate kernel alone
-(dgrp_inflate_batch on the uploaded BGZF file, GB/s of output) and host zlib on the same files.  One JSON line per result.
+(dgrp_inflate_batch on the uploaded BGZF file, GB/s of output) and host zlib on the same files.  The plain-gzip file goes in twice,
+through the device path (dgrp_inflate_stream_scan / _write) and through zlib with the device path switched off by
+gz.PLAIN_DEVICE_MIN_BYTES; scan and write are timed alone as well, with the chain's statistics.  One JSON line per result.
     python tools/gz_throughput.py [Mbp]"""
 import ctypes as C
 import json
@@ -70,28 +72,72 @@ def main():
                 parts.append(rows_text_batch(path, key, rows) if kind == "batch" else rows_text(path, key, rows))
             return "".join(parts).encode()
 
-        tsv = {}
-        for form in ("fa", "bgzf", "gzip", "fa"):                        # .fa again last: the same session's drift
-            file_to_tsv(paths[form])
-            ts = []
-            for _ in range(3):
+        # three alternating rounds of the four ways in: plain gzip on the device, plain gzip through zlib (the device path switched
+        # off by its constant), BGZF, and the text itself
+        ways = {"gzip_device": ("gzip", 0), "gzip_host": ("gzip", float("inf")), "bgzf": ("bgzf", None), "fa": ("fa", None)}
+        shipped = gz.PLAIN_DEVICE_MIN_BYTES
+        tsv, ts = {}, {k: [] for k in ways}
+
+        def run(way):
+            form, min_bytes = ways[way]
+            gz.PLAIN_DEVICE_MIN_BYTES = shipped if min_bytes is None else min_bytes
+            try:
                 torch.cuda.synchronize()
                 t = time.perf_counter()
                 out = file_to_tsv(paths[form])
-                ts.append(time.perf_counter() - t)
-            tsv.setdefault(form, out.replace(paths[form].encode(), b"<file>"))
-            emit(what="e2e", form=form, mbp_per_s=round(n / float(np.mean(ts)) / 1e6, 3), ms=round(float(np.mean(ts)) * 1e3, 3),
-                 ms_each=[round(x * 1e3, 3) for x in ts], rows=out.count(b"\n"))
-        emit(what="tsv identical", bgzf=tsv["bgzf"] == tsv["fa"], gzip=tsv["gzip"] == tsv["fa"])
+                return time.perf_counter() - t, out
+            finally:
+                gz.PLAIN_DEVICE_MIN_BYTES = shipped
+        for way in ways:
+            run(way)
+        for _ in range(3):
+            for way in ways:
+                dt, out = run(way)
+                ts[way].append(dt)
+                tsv[way] = out.replace(paths[ways[way][0]].encode(), b"<file>")
+        for way in ways:
+            emit(what="e2e", form=way, mbp_per_s=round(n / float(np.mean(ts[way])) / 1e6, 3), ms=round(float(np.mean(ts[way])) * 1e3, 3),
+                 ms_each=[round(x * 1e3, 3) for x in ts[way]], rows=tsv[way].count(b"\n"))
+        emit(what="tsv identical", bgzf=tsv["bgzf"] == tsv["fa"], gzip_device=tsv["gzip_device"] == tsv["fa"],
+             gzip_host=tsv["gzip_host"] == tsv["fa"], shipped_min_bytes=str(shipped))
+
+        # ---- scan and write alone, on the uploaded plain gzip file, at the shipped chunk size and at others
+        from deepgrp_amd._lib import InflateStreamStats
+        dev = torch.device("cuda", 0)
+        L = lib()
+        size = sizes["gzip"]
+        with open(paths["gzip"], "rb") as fh:
+            data_off = gz.plain_data_off(fh.read(4096))
+        d_in = _upload_file(paths["gzip"], size, dev)
+        for chunk in sorted({gz.PLAIN_CHUNK_BYTES, 16 << 10, 32 << 10, 64 << 10, 128 << 10}):
+            wb = int(L.dgrp_inflate_stream_workspace_bytes(size, chunk))
+            work = torch.empty(wb, dtype=torch.uint8, device=dev)
+            total, st, reason, crc, used = C.c_int64(), InflateStreamStats(), C.c_int(), C.c_uint32(), C.c_int64()
+            t_scan, t_write = [], []
+            for rep in range(3):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                check(L.dgrp_inflate_stream_scan(d_in.data_ptr(), size, data_off, chunk, gz.PLAIN_MAX_SPAN_BYTES, gz.PLAIN_MAX_ROUNDS,
+                                                 C.byref(total), C.byref(st), C.byref(reason), work.data_ptr(), wb, stream_ptr()), "scan")
+                t_scan.append(time.perf_counter() - t)
+                d_out = torch.empty(total.value, dtype=torch.uint8, device=dev)
+                d_sym = torch.empty(total.value, dtype=torch.int16, device=dev)
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                check(L.dgrp_inflate_stream_write(d_in.data_ptr(), size, data_off, chunk, d_sym.data_ptr(), d_out.data_ptr(), total.value,
+                                                  C.byref(crc), C.byref(used), C.byref(reason), work.data_ptr(), wb, stream_ptr()), "write")
+                t_write.append(time.perf_counter() - t)
+            same = d_out.cpu().numpy().tobytes() == text and crc.value == zlib.crc32(text) and used.value == size - 8
+            emit(what="inflate stream", chunk_bytes=chunk, out_bytes=total.value, bytes_identical=same,
+                 scan_ms=[round(x * 1e3, 2) for x in t_scan], write_ms=[round(x * 1e3, 2) for x in t_write], stats=st.as_dict())
+            del d_out, d_sym, work
 
         # ---- the inflate kernel alone, on the uploaded BGZF file
-        dev = torch.device("cuda", 0)
         with open(paths["bgzf"], "rb") as fh:
             comp = fh.read()
         t = time.perf_counter()
         members = gz.walk_members(comp, paths["bgzf"])
         t_walk = time.perf_counter() - t
-        L = lib()
         nmem = int(members.start.size)
         out_off = np.zeros(nmem + 1, np.int64)
         np.cumsum(members.isize, out=out_off[1:])
