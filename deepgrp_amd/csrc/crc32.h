@@ -41,3 +41,21 @@ DGRP_HD static constexpr uint32_t dgrp_crc_combine(uint32_t crc_a, uint32_t crc_
 {
     return dgrp_crc_multmodp(dgrp_crc_x8n(len_b), crc_a) ^ crc_b;
 }
+
+#if defined(__HIP__) || defined(__HIPCC__)
+// One wave of 64 lanes: the CRC-32 of the bytes that the lanes' slices [a, b) make up in lane order (they are adjacent; a slice may
+// be empty).  tab = 256 words of LDS, filled here; the barrier behind the fill also makes the wave's own earlier stores to the
+// bytes visible to every lane.
+__device__ static inline uint32_t dgrp_crc_wave(const uint8_t *a, const uint8_t *b, uint32_t *tab)
+{
+    for (uint32_t i = threadIdx.x; i < 256; i += 64) tab[i] = dgrp_crc_table_entry(i);
+    __syncthreads();
+    uint32_t c = 0xffffffffu;
+    for (const uint8_t *p = a; p < b; ++p) c = tab[(c ^ *p) & 0xff] ^ (c >> 8);
+    c ^= 0xffffffffu;
+    const uint32_t px = dgrp_crc_x8n((uint64_t)(b - a));
+    uint32_t crc = __shfl(c, 0);
+    for (int i = 1; i < 64; ++i) crc = dgrp_crc_multmodp(__shfl(px, i), crc) ^ __shfl(c, i);
+    return crc;
+}
+#endif

@@ -37,12 +37,15 @@ struct dgrp_bits {
     int cnt;
 };
 
+DGRP_HD static inline uint32_t dgrp_le32(const uint8_t *p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
 DGRP_HD static inline void dgrp_bits_refill(dgrp_bits &s)
 {
     if (s.cnt <= 32 && s.pos + 4 <= s.len) {
-        const uint8_t *p = s.in + s.pos;
-        const uint64_t w = (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
-        s.buf |= w << s.cnt;
+        s.buf |= (uint64_t)dgrp_le32(s.in + s.pos) << s.cnt;
         s.cnt += 32;
         s.pos += 4;
     }
@@ -51,6 +54,25 @@ DGRP_HD static inline void dgrp_bits_refill(dgrp_bits &s)
         s.cnt += 8;
     }
 }
+
+// the reader at bit `skip` (0..7) of in[0, len)
+DGRP_HD static inline void dgrp_bits_open(dgrp_bits &s, const uint8_t *in, uint32_t len, uint32_t skip)
+{
+    s.in = in;
+    s.len = len;
+    s.pos = 0;
+    s.buf = 0;
+    s.cnt = 0;
+    if (skip) {
+        dgrp_bits_refill(s);
+        if (s.cnt >= (int)skip) {
+            s.buf >>= skip;
+            s.cnt -= (int)skip;
+        }
+    }
+}
+// the next bit not consumed, relative to the slice
+DGRP_HD static inline int64_t dgrp_bits_tell(const dgrp_bits &s) { return (int64_t)s.pos * 8 - s.cnt; }
 
 // n <= 16 bits; false when the input ends first
 DGRP_HD static inline bool dgrp_bits_get(dgrp_bits &s, int n, uint32_t &v)
@@ -66,7 +88,9 @@ DGRP_HD static inline bool dgrp_bits_get(dgrp_bits &s, int n, uint32_t &v)
 }
 
 // Canonical code of lengths length[0..n): 0 = complete, > 0 = incomplete (codes left over), < 0 = over-subscribed.
-DGRP_HD static int dgrp_huff_build(dgrp_huff *h, int16_t *offs, const int16_t *length, int n)
+// (always inline: left to itself the compiler keeps it as a call in some of the decoding kernels, and a kernel with a call in it
+// takes more registers -- the member kernel 127 VGPRs against 103 and 1.7 % more time, count and symbols ~117 against 80)
+DGRP_HD static inline __attribute__((always_inline)) int dgrp_huff_build(dgrp_huff *h, int16_t *offs, const int16_t *length, int n)
 {
     for (int len = 0; len <= DGRP_HUFF_MAXBITS; ++len) h->count[len] = 0;
     for (int sym = 0; sym < n; ++sym) h->count[length[sym]]++;
@@ -191,79 +215,153 @@ DGRP_HD static void dgrp_build_fixed(dgrp_inflate_tables *t)
     t->fixed = 1;
 }
 
-// One raw DEFLATE stream in[0, in_len) -> output [0, out_cap) through `sink`:
+// ---- the one block decoder.  Output goes through `sink`, positions relative to the first byte the decoder produces:
 //   sink.literal(pos, byte)           out[pos] = byte
-//   sink.match(pos, dist, len)        out[pos + j] = out[pos - dist + j] for j = 0 .. len-1 in order (dist <= pos checked)
+//   sink.match(pos, dist, len)        out[pos + j] = out[pos - dist + j] for j = 0 .. len-1 in order (dist <= pos + window checked)
 //   sink.stored(pos, src, len)        out[pos + j] = src[j]            (src inside the input slice, checked)
-// On return *out_len = bytes produced, *in_used = whole input bytes consumed up to the end of the last block.
+// the counting sink stores nothing
+struct dgrp_count_sink {
+    DGRP_HD void literal(uint64_t, uint32_t) {}
+    DGRP_HD void match(uint64_t, uint32_t, uint32_t) {}
+    DGRP_HD void stored(uint64_t, const uint8_t *, uint32_t) {}
+};
+
+// The body of a Huffman block, with the codes of t, up to its end-of-block symbol.  `pos` may go up to `cap`; a match may reach
+// `window` bytes in front of position 0.  Pos is 32 bits wide where bytes are written (the position sits in the per-symbol loop of
+// a latency-bound wave) and 64 bits in the candidate filter, which counts one block without a cap.
+template <class Pos, class Sink>
+DGRP_HD static inline int dgrp_huff_block(dgrp_bits &s, const dgrp_inflate_tables *t, Sink &sink, Pos &pos, Pos cap, uint32_t window)
+{
+    uint32_t v;
+    for (;;) {
+        int sym = dgrp_huff_decode(s, &t->lencode);
+        if (sym < 0) return -sym;
+        if (sym < 256) {
+            if (pos >= cap) return DGRP_INFLATE_EOUTPUT;
+            sink.literal(pos, (uint32_t)sym);
+            ++pos;
+            continue;
+        }
+        if (sym == 256) return DGRP_INFLATE_OK;
+        sym -= 257;
+        if (sym >= 29) return DGRP_INFLATE_ESYMBOL;
+        int base, extra;
+        dgrp_len_code(sym, base, extra);
+        if (!dgrp_bits_get(s, extra, v)) return DGRP_INFLATE_EINPUT;
+        const uint32_t len = (uint32_t)base + v;
+        const int dsym = dgrp_huff_decode(s, &t->distcode);
+        if (dsym < 0) return -dsym;
+        if (dsym >= 30) return DGRP_INFLATE_ESYMBOL;
+        dgrp_dist_code(dsym, base, extra);
+        if (!dgrp_bits_get(s, extra, v)) return DGRP_INFLATE_EINPUT;
+        const uint32_t dist = (uint32_t)base + v;
+        if ((uint64_t)dist > (uint64_t)pos + window) return DGRP_INFLATE_EDIST;
+        if (len > cap - pos) return DGRP_INFLATE_EOUTPUT;
+        sink.match(pos, dist, len);
+        pos += len;
+    }
+}
+
+// A stored block behind its three header bits: on to a byte boundary, LEN and NLEN, LEN bytes as they are.  An error leaves s.pos
+// at the byte dgrp_inflate_core reports as *in_used.
+template <class Sink>
+DGRP_HD static inline int dgrp_stored_block(dgrp_bits &s, Sink &sink, uint32_t &pos, uint32_t cap)
+{
+    const uint32_t at = s.pos - (uint32_t)(s.cnt >> 3);          // first byte not consumed
+    s.buf = 0;
+    s.cnt = 0;
+    s.pos = s.len;
+    if (at + 4 > s.len || at + 4 < at) return DGRP_INFLATE_EINPUT;
+    const uint32_t len = (uint32_t)s.in[at] | ((uint32_t)s.in[at + 1] << 8);
+    const uint32_t nlen = (uint32_t)s.in[at + 2] | ((uint32_t)s.in[at + 3] << 8);
+    if (len != (~nlen & 0xffffu)) {
+        s.pos = at + 4;
+        return DGRP_INFLATE_ESTORED;
+    }
+    if (len > s.len - (at + 4)) return DGRP_INFLATE_EINPUT;
+    s.pos = at + 4;
+    if (len > cap - pos) return DGRP_INFLATE_EOUTPUT;
+    sink.stored(pos, s.in + at + 4, len);
+    pos += len;
+    s.pos += len;
+    return DGRP_INFLATE_OK;
+}
+
+// Whole blocks from the reader's position (dgrp_bits_open: any bit of a byte) through `sink`, up to `out_cap` bytes.  Stops in
+// front of the first block that starts at or after slice bit `stop`, and behind the final block (*fin = 1).  *land = slice bit of
+// the last block boundary reached, *out_len = bytes produced up to there or to the error.  Every decoder is this loop: a member
+// is start bit 0, no stop and window 0 (dgrp_inflate_core); a span of a stream has all three (inflate_stream.h).
+template <class Sink>
+DGRP_HD static int dgrp_inflate_blocks(dgrp_bits &s, int64_t stop, uint32_t window, uint32_t out_cap, dgrp_inflate_tables *t, Sink &sink,
+                                       int64_t *land, uint32_t *out_len, int *fin)
+{
+    t->fixed = 0;
+    uint32_t pos = 0, last = 0, type;
+    int rc = DGRP_INFLATE_OK;
+    for (;;) {
+        *land = dgrp_bits_tell(s);
+        if (last || *land >= stop) break;
+        if (!dgrp_bits_get(s, 1, last) || !dgrp_bits_get(s, 2, type)) rc = DGRP_INFLATE_EINPUT;
+        else if (type == 0) rc = dgrp_stored_block(s, sink, pos, out_cap);
+        else if (type == 3) rc = DGRP_INFLATE_EBLOCK;
+        else {
+            if (type == 2) rc = dgrp_read_dynamic(s, t);
+            else if (!t->fixed) dgrp_build_fixed(t);
+            if (rc == DGRP_INFLATE_OK) rc = dgrp_huff_block(s, t, sink, pos, out_cap, window);
+        }
+        if (rc != DGRP_INFLATE_OK) break;
+    }
+    *out_len = pos;
+    *fin = (rc == DGRP_INFLATE_OK && last) ? 1 : 0;
+    return rc;
+}
+
+// One raw DEFLATE stream in[0, in_len) -> output [0, out_cap).  On return *out_len = bytes produced, *in_used = whole input
+// bytes consumed up to the end of the last block, or up to the error.
 template <class Sink>
 DGRP_HD static int dgrp_inflate_core(const uint8_t *in, uint32_t in_len, uint32_t out_cap, dgrp_inflate_tables *t, Sink &sink,
                                      uint32_t *out_len, uint32_t *in_used)
 {
     dgrp_bits s;
-    s.in = in;
-    s.len = in_len;
-    s.pos = 0;
-    s.buf = 0;
-    s.cnt = 0;
-    t->fixed = 0;
-    uint32_t pos = 0, last = 0, type, v;
-    int rc = DGRP_INFLATE_OK;
-    do {
-        if (!dgrp_bits_get(s, 1, last) || !dgrp_bits_get(s, 2, type)) { rc = DGRP_INFLATE_EINPUT; break; }
-        if (type == 0) {
-            // stored: skip to a byte boundary, LEN and NLEN, LEN bytes as they are
-            s.buf >>= (s.cnt & 7);
-            s.cnt &= ~7;
-            const uint32_t at = s.pos - (uint32_t)(s.cnt >> 3);      // first byte not consumed
-            s.buf = 0;
-            s.cnt = 0;
-            if (at + 4 > in_len) { s.pos = in_len; rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t len = (uint32_t)in[at] | ((uint32_t)in[at + 1] << 8);
-            const uint32_t nlen = (uint32_t)in[at + 2] | ((uint32_t)in[at + 3] << 8);
-            if (len != (~nlen & 0xffffu)) { s.pos = at + 4; rc = DGRP_INFLATE_ESTORED; break; }
-            if (len > in_len - (at + 4)) { s.pos = in_len; rc = DGRP_INFLATE_EINPUT; break; }
-            if (len > out_cap - pos) { s.pos = at + 4; rc = DGRP_INFLATE_EOUTPUT; break; }
-            sink.stored(pos, in + at + 4, len);
-            pos += len;
-            s.pos = at + 4 + len;
-            continue;
-        }
-        if (type == 3) { rc = DGRP_INFLATE_EBLOCK; break; }
-        if (type == 1) {
-            if (!t->fixed) dgrp_build_fixed(t);
-        } else if ((rc = dgrp_read_dynamic(s, t)) != DGRP_INFLATE_OK) {
-            break;
-        }
-        for (;;) {
-            int sym = dgrp_huff_decode(s, &t->lencode);
-            if (sym < 0) { rc = -sym; break; }
-            if (sym < 256) {
-                if (pos >= out_cap) { rc = DGRP_INFLATE_EOUTPUT; break; }
-                sink.literal(pos, (uint32_t)sym);
-                ++pos;
-                continue;
-            }
-            if (sym == 256) break;
-            sym -= 257;
-            if (sym >= 29) { rc = DGRP_INFLATE_ESYMBOL; break; }
-            int base, extra;
-            dgrp_len_code(sym, base, extra);
-            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t len = (uint32_t)base + v;
-            const int dsym = dgrp_huff_decode(s, &t->distcode);
-            if (dsym < 0) { rc = -dsym; break; }
-            if (dsym >= 30) { rc = DGRP_INFLATE_ESYMBOL; break; }
-            dgrp_dist_code(dsym, base, extra);
-            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t dist = (uint32_t)base + v;
-            if (dist > pos) { rc = DGRP_INFLATE_EDIST; break; }
-            if (len > out_cap - pos) { rc = DGRP_INFLATE_EOUTPUT; break; }
-            sink.match(pos, dist, len);
-            pos += len;
-        }
-    } while (rc == DGRP_INFLATE_OK && !last);
-    *out_len = pos;
+    dgrp_bits_open(s, in, in_len, 0);
+    int64_t land;
+    int fin;
+    const int rc = dgrp_inflate_blocks(s, INT64_MAX, 0, out_cap, t, sink, &land, out_len, &fin);
     *in_used = s.pos - (uint32_t)(s.cnt >> 3);
     return rc;
 }
+
+// the byte sink of the host
+struct dgrp_host_sink {
+    uint8_t *out;
+    void literal(uint32_t pos, uint32_t b) { out[pos] = (uint8_t)b; }
+    void match(uint32_t pos, uint32_t dist, uint32_t len)
+    {
+        for (uint32_t j = 0; j < len; ++j) out[pos + j] = out[pos - dist + j];
+    }
+    void stored(uint32_t pos, const uint8_t *src, uint32_t len)
+    {
+        for (uint32_t j = 0; j < len; ++j) out[pos + j] = src[j];
+    }
+};
+
+// what dgrp_last_error() says of a DGRP_INFLATE_E* reason; code 9 reads differently for a span of a stream than for a member
+static inline const char *dgrp_inflate_reason_text(int r, bool span)
+{
+    switch (r) {
+    case DGRP_INFLATE_EINPUT: return "input ends inside the stream";
+    case DGRP_INFLATE_EBLOCK: return "invalid block type";
+    case DGRP_INFLATE_ESTORED: return "stored block LEN/NLEN mismatch";
+    case DGRP_INFLATE_ECODES: return "invalid code lengths";
+    case DGRP_INFLATE_ESYMBOL: return "invalid symbol";
+    case DGRP_INFLATE_EDIST: return "distance too far back";
+    case DGRP_INFLATE_EOUTPUT: return "output beyond its size";
+    case DGRP_INFLATE_ECRC: return "CRC-32 mismatch";
+    case DGRP_INFLATE_EISIZE: return span ? "a span decoded differently than it was counted" : "output shorter than ISIZE";
+    case DGRP_INFLATE_ETRAIL: return "stream ends before the trailer";
+    case DGRP_INFLATE_ESPAN: return "a span longer than max_span_bytes";
+    case DGRP_INFLATE_EROUNDS: return "the chain is not closed after max_rounds rounds";
+    default: return "unknown";
+    }
+}
+

@@ -10,19 +10,6 @@
 #include "inflate.h"
 #include <vector>
 
-struct inflate_host_sink {
-    uint8_t *out;
-    void literal(uint32_t pos, uint32_t b) { out[pos] = (uint8_t)b; }
-    void match(uint32_t pos, uint32_t dist, uint32_t len)
-    {
-        for (uint32_t j = 0; j < len; ++j) out[pos + j] = out[pos - dist + j];
-    }
-    void stored(uint32_t pos, const uint8_t *src, uint32_t len)
-    {
-        for (uint32_t j = 0; j < len; ++j) out[pos + j] = src[j];
-    }
-};
-
 struct inflate_wave_sink {
     uint8_t *out;
     uint32_t lane;
@@ -46,11 +33,6 @@ struct inflate_wave_sink {
     }
 };
 
-__device__ __forceinline__ uint32_t inflate_le32(const uint8_t *p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
 // one workgroup (one wave) per member; tab = in_off[nmem], in_len[nmem], out_off[nmem + 1]
 __global__ void __launch_bounds__(64) inflate_member_kernel(const uint8_t *__restrict__ in, const int64_t *__restrict__ tab, int64_t nmem,
                                                             uint8_t *__restrict__ out, int32_t *__restrict__ status)
@@ -59,7 +41,6 @@ __global__ void __launch_bounds__(64) inflate_member_kernel(const uint8_t *__res
     __shared__ uint32_t crctab[256];
     const uint32_t lane = threadIdx.x;
     const int64_t m = blockIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) crctab[i] = dgrp_crc_table_entry(i);
     const uint8_t *src = in + tab[m];
     const uint32_t n_in = (uint32_t)tab[nmem + m];
     const int64_t o0 = tab[2 * nmem + m];
@@ -69,38 +50,14 @@ __global__ void __launch_bounds__(64) inflate_member_kernel(const uint8_t *__res
     uint32_t produced = 0, used = 0;
     int rc = dgrp_inflate_core(src, n_in, cap, &t, sink, &produced, &used);
     if (rc == DGRP_INFLATE_OK && used != n_in) rc = DGRP_INFLATE_ETRAIL;
-    const uint32_t crc_want = inflate_le32(src + n_in), isize = inflate_le32(src + n_in + 4);
+    const uint32_t crc_want = dgrp_le32(src + n_in), isize = dgrp_le32(src + n_in + 4);
     if (rc == DGRP_INFLATE_OK && produced != isize) rc = produced < isize ? DGRP_INFLATE_EISIZE : DGRP_INFLATE_EOUTPUT;
-    __syncthreads();                                     // the CRC table, and every lane's bytes of the output
-    if (rc == DGRP_INFLATE_OK) {
+    if (rc == DGRP_INFLATE_OK) {                         // (the same for every lane)
         const uint32_t seg = (produced + 63) / 64;
         const uint32_t a = min(lane * seg, produced), b = min(a + seg, produced);
-        uint32_t c = 0xffffffffu;
-        for (uint32_t i = a; i < b; ++i) c = crctab[(c ^ dst[i]) & 0xff] ^ (c >> 8);
-        c ^= 0xffffffffu;
-        const uint32_t px = dgrp_crc_x8n(b - a);
-        uint32_t crc = __shfl(c, 0);
-        for (int i = 1; i < 64; ++i) crc = dgrp_crc_multmodp(__shfl(px, i), crc) ^ __shfl(c, i);
-        if (crc != crc_want) rc = DGRP_INFLATE_ECRC;
+        if (dgrp_crc_wave(dst + a, dst + b, crctab) != crc_want) rc = DGRP_INFLATE_ECRC;
     }
     if (lane == 0) status[m] = rc;
-}
-
-static const char *inflate_reason_text(int r)
-{
-    switch (r) {
-    case DGRP_INFLATE_EINPUT: return "input ends inside the stream";
-    case DGRP_INFLATE_EBLOCK: return "invalid block type";
-    case DGRP_INFLATE_ESTORED: return "stored block LEN/NLEN mismatch";
-    case DGRP_INFLATE_ECODES: return "invalid code lengths";
-    case DGRP_INFLATE_ESYMBOL: return "invalid symbol";
-    case DGRP_INFLATE_EDIST: return "distance too far back";
-    case DGRP_INFLATE_EOUTPUT: return "output beyond its size";
-    case DGRP_INFLATE_ECRC: return "CRC-32 mismatch";
-    case DGRP_INFLATE_EISIZE: return "output shorter than ISIZE";
-    case DGRP_INFLATE_ETRAIL: return "stream ends before the trailer";
-    default: return "unknown";
-    }
 }
 
 DGRP_EXPORT int dgrp_inflate_raw_host(const uint8_t *h_in, int64_t in_len, uint8_t *h_out, int64_t out_cap, int64_t *h_out_len,
@@ -110,14 +67,14 @@ DGRP_EXPORT int dgrp_inflate_raw_host(const uint8_t *h_in, int64_t in_len, uint8
     DGRP_REQUIRE(in_len >= 0 && out_cap >= 0 && in_len <= INT32_MAX && out_cap <= INT32_MAX, "dgrp_inflate_raw_host: bad sizes");
     DGRP_REQUIRE((h_in || in_len == 0) && (h_out || out_cap == 0), "dgrp_inflate_raw_host: NULL pointer");
     dgrp_inflate_tables t;
-    inflate_host_sink sink{h_out};
+    dgrp_host_sink sink{h_out};
     uint32_t produced = 0, used = 0;
     const int rc = dgrp_inflate_core(h_in, (uint32_t)in_len, (uint32_t)out_cap, &t, sink, &produced, &used);
     *h_out_len = produced;
     *h_in_used = used;
     *h_reason = rc;
     if (rc != DGRP_INFLATE_OK) {
-        dgrp_set_error("dgrp_inflate_raw_host: %s (reason %d) near input byte %u", inflate_reason_text(rc), rc, used);
+        dgrp_set_error("dgrp_inflate_raw_host: %s (reason %d) near input byte %u", dgrp_inflate_reason_text(rc, false), rc, used);
         return DGRP_EDATA;
     }
     return DGRP_OK;
@@ -168,7 +125,7 @@ DGRP_EXPORT int dgrp_inflate_batch(const uint8_t *d_in, int64_t in_bytes, int64_
         if (status[(size_t)m] != DGRP_INFLATE_OK) {
             *h_bad = m;
             *h_reason = status[(size_t)m];
-            dgrp_set_error("dgrp_inflate_batch: member %lld: %s (reason %d)", (long long)m, inflate_reason_text(status[(size_t)m]),
+            dgrp_set_error("dgrp_inflate_batch: member %lld: %s (reason %d)", (long long)m, dgrp_inflate_reason_text(status[(size_t)m], false),
                            status[(size_t)m]);
             return DGRP_EDATA;
         }

@@ -16,25 +16,6 @@
 #define DGRP_STREAM_WINDOW 32768
 #define DGRP_STREAM_MARK 256                     // symbol of window byte 0
 
-// the reader at bit `skip` (0..7) of in[0, len)
-DGRP_HD static inline void dgrp_bits_open(dgrp_bits &s, const uint8_t *in, uint32_t len, uint32_t skip)
-{
-    s.in = in;
-    s.len = len;
-    s.pos = 0;
-    s.buf = 0;
-    s.cnt = 0;
-    if (skip) {
-        dgrp_bits_refill(s);
-        if (s.cnt >= (int)skip) {
-            s.buf >>= skip;
-            s.cnt -= (int)skip;
-        }
-    }
-}
-// the next bit not consumed, relative to the slice
-DGRP_HD static inline int64_t dgrp_bits_tell(const dgrp_bits &s) { return (int64_t)s.pos * 8 - s.cnt; }
-
 // The slice of the stream in[0, n) a span from bit `bit` (0 <= bit < 8 n) reads: at most `clip` bytes from the byte of its start.
 struct dgrp_stream_slice {
     const uint8_t *in;
@@ -87,116 +68,25 @@ DGRP_HD static bool dgrp_stream_candidate(const dgrp_stream_slice &sl, dgrp_infl
 {
     dgrp_bits s;
     dgrp_bits_open(s, sl.in, sl.len, sl.skip);
+    dgrp_count_sink sink;
+    uint64_t pos = 0;                            // one block of a span of up to 2^31 bytes may hold more than 2^32 bytes of text
     uint32_t v;
-    if (!dgrp_bits_get(s, 3, v) || v != 4u) return false;
-    if (dgrp_read_dynamic(s, t) != DGRP_INFLATE_OK) return false;
-    uint64_t pos = 0;
-    for (;;) {
-        int sym = dgrp_huff_decode(s, &t->lencode);
-        if (sym < 0) return false;
-        if (sym < 256) { ++pos; continue; }
-        if (sym == 256) break;
-        sym -= 257;
-        if (sym >= 29) return false;
-        int base, extra;
-        dgrp_len_code(sym, base, extra);
-        if (!dgrp_bits_get(s, extra, v)) return false;
-        const uint32_t len = (uint32_t)base + v;
-        const int dsym = dgrp_huff_decode(s, &t->distcode);
-        if (dsym < 0 || dsym >= 30) return false;
-        dgrp_dist_code(dsym, base, extra);
-        if (!dgrp_bits_get(s, extra, v)) return false;
-        if ((uint64_t)base + v > pos + DGRP_STREAM_WINDOW) return false;
-        pos += len;
-    }
-    if (!dgrp_bits_get(s, 3, v)) return false;
-    return (v >> 1) != 3u;
+    return dgrp_bits_get(s, 3, v) && v == 4u && dgrp_read_dynamic(s, t) == DGRP_INFLATE_OK &&
+           dgrp_huff_block(s, t, sink, pos, UINT64_MAX, DGRP_STREAM_WINDOW) == DGRP_INFLATE_OK && dgrp_bits_get(s, 3, v) && (v >> 1) != 3u;
 }
 
-// ---- the span decoder.  dgrp_inflate_core stays as it is (the member kernel and tests/test_inflate_host.py hold it bit for bit);
-// this is its block loop again with what that one lacks: a start inside a byte, a stop rule and a window in front of the output.
-// Whole blocks of the slice from its bit `skip`, through `sink` (as dgrp_inflate_core's, positions relative
-// to the span's first byte; a match may reach up to DGRP_STREAM_WINDOW bytes in front of it).  Stops in front of the first block
-// that starts at or after slice bit `stop`, and behind the final block (*fin = 1).  *land = slice bit of the last block boundary
-// reached, *out_len = bytes produced up to there or to the error.
+// ---- the span decoder: the block loop of inflate.h (dgrp_inflate_blocks) over a slice, with a match reaching up to
+// DGRP_STREAM_WINDOW bytes in front of the span's first byte.  `stop` and *land are stream bits.
 template <class Sink>
-DGRP_HD static int dgrp_span_decode(const uint8_t *in, uint32_t in_len, uint32_t skip, int64_t stop, uint32_t out_cap,
-                                    dgrp_inflate_tables *t, Sink &sink, int64_t *land, uint32_t *out_len, int *fin)
+DGRP_HD static int dgrp_span_decode(const dgrp_stream_slice &sl, int64_t stop, uint32_t out_cap, dgrp_inflate_tables *t, Sink &sink,
+                                    int64_t *land, uint32_t *out_len, int *fin)
 {
     dgrp_bits s;
-    dgrp_bits_open(s, in, in_len, skip);
-    t->fixed = 0;
-    uint32_t pos = 0, last = 0, type, v;
-    int rc = DGRP_INFLATE_OK;
-    *land = skip;
-    for (;;) {
-        const int64_t at_bit = dgrp_bits_tell(s);
-        *land = at_bit;
-        if (last || at_bit >= stop) break;
-        if (!dgrp_bits_get(s, 1, last) || !dgrp_bits_get(s, 2, type)) { rc = DGRP_INFLATE_EINPUT; break; }
-        if (type == 0) {
-            s.buf >>= (s.cnt & 7);
-            s.cnt &= ~7;
-            const uint32_t at = s.pos - (uint32_t)(s.cnt >> 3);
-            s.buf = 0;
-            s.cnt = 0;
-            if (at + 4 > in_len || at + 4 < at) { rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t len = (uint32_t)in[at] | ((uint32_t)in[at + 1] << 8);
-            const uint32_t nlen = (uint32_t)in[at + 2] | ((uint32_t)in[at + 3] << 8);
-            if (len != (~nlen & 0xffffu)) { rc = DGRP_INFLATE_ESTORED; break; }
-            if (len > in_len - (at + 4)) { rc = DGRP_INFLATE_EINPUT; break; }
-            if (len > out_cap - pos) { rc = DGRP_INFLATE_EOUTPUT; break; }
-            sink.stored(pos, in + at + 4, len);
-            pos += len;
-            s.pos = at + 4 + len;
-            continue;
-        }
-        if (type == 3) { rc = DGRP_INFLATE_EBLOCK; break; }
-        if (type == 1) {
-            if (!t->fixed) dgrp_build_fixed(t);
-        } else if ((rc = dgrp_read_dynamic(s, t)) != DGRP_INFLATE_OK) {
-            break;
-        }
-        for (;;) {
-            int sym = dgrp_huff_decode(s, &t->lencode);
-            if (sym < 0) { rc = -sym; break; }
-            if (sym < 256) {
-                if (pos >= out_cap) { rc = DGRP_INFLATE_EOUTPUT; break; }
-                sink.literal(pos, (uint32_t)sym);
-                ++pos;
-                continue;
-            }
-            if (sym == 256) break;
-            sym -= 257;
-            if (sym >= 29) { rc = DGRP_INFLATE_ESYMBOL; break; }
-            int base, extra;
-            dgrp_len_code(sym, base, extra);
-            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t len = (uint32_t)base + v;
-            const int dsym = dgrp_huff_decode(s, &t->distcode);
-            if (dsym < 0) { rc = -dsym; break; }
-            if (dsym >= 30) { rc = DGRP_INFLATE_ESYMBOL; break; }
-            dgrp_dist_code(dsym, base, extra);
-            if (!dgrp_bits_get(s, extra, v)) { rc = DGRP_INFLATE_EINPUT; break; }
-            const uint32_t dist = (uint32_t)base + v;
-            if ((uint64_t)dist > (uint64_t)pos + DGRP_STREAM_WINDOW) { rc = DGRP_INFLATE_EDIST; break; }
-            if (len > out_cap - pos) { rc = DGRP_INFLATE_EOUTPUT; break; }
-            sink.match(pos, dist, len);
-            pos += len;
-        }
-        if (rc != DGRP_INFLATE_OK) break;
-    }
-    *out_len = pos;
-    *fin = (rc == DGRP_INFLATE_OK && last) ? 1 : 0;
+    dgrp_bits_open(s, sl.in, sl.len, sl.skip);
+    const int rc = dgrp_inflate_blocks(s, stop - sl.bit0, DGRP_STREAM_WINDOW, out_cap, t, sink, land, out_len, fin);
+    *land += sl.bit0;
     return rc;
 }
-
-// the counting sink stores nothing
-struct dgrp_count_sink {
-    DGRP_HD void literal(uint32_t, uint32_t) {}
-    DGRP_HD void match(uint32_t, uint32_t, uint32_t) {}
-    DGRP_HD void stored(uint32_t, const uint8_t *, uint32_t) {}
-};
 
 // the symbol a match copies from j bytes into its source, which starts `dist` bytes in front of span position `pos`
 DGRP_HD static inline uint16_t dgrp_stream_match_symbol(const uint16_t *sym, uint32_t pos, uint32_t dist, uint32_t j)
@@ -223,24 +113,33 @@ DGRP_HD static dgrp_span_count dgrp_stream_count(const uint8_t *in, int64_t n, i
     dgrp_span_count r;
     const dgrp_stream_slice sl = dgrp_stream_slice_at(in, n, start, clip);
     dgrp_count_sink sink;
+    int fin = 0;
+    int rc = dgrp_span_decode(sl, stop, DGRP_SPAN_MAX_OUT, t, sink, &r.land, &r.bytes, &fin);
+    if (rc == DGRP_INFLATE_EINPUT && sl.clipped) rc = DGRP_INFLATE_ESPAN;
+    r.rc_fin = rc | (fin << 8);
+    return r;
+}
+
+struct stream_span {                             // one confirmed span (the table has one more entry: out_off = total)
+    int64_t start, stop, out_off, land;
+};
+
+// The confirmed span `sp` of in[0, n) once more, through `sink` into exactly `cap` positions: DGRP_INFLATE_EISIZE when it gives
+// other bytes or another landing than the counting pass saw.
+template <class Sink>
+DGRP_HD static int dgrp_stream_span(const uint8_t *in, int64_t n, int64_t clip, const stream_span &sp, uint32_t cap,
+                                    dgrp_inflate_tables *t, Sink &sink)
+{
     int64_t land = 0;
     uint32_t bytes = 0;
     int fin = 0;
-    int rc = dgrp_span_decode(sl.in, sl.len, sl.skip, stop - sl.bit0, DGRP_SPAN_MAX_OUT, t, sink, &land, &bytes, &fin);
-    if (rc == DGRP_INFLATE_EINPUT && sl.clipped) rc = DGRP_INFLATE_ESPAN;
-    r.land = sl.bit0 + land;
-    r.bytes = bytes;
-    r.rc_fin = rc | (fin << 8);
-    return r;
+    const int rc = dgrp_span_decode(dgrp_stream_slice_at(in, n, sp.start, clip), sp.stop, cap, t, sink, &land, &bytes, &fin);
+    return rc == DGRP_INFLATE_OK && (bytes != cap || land != sp.land) ? DGRP_INFLATE_EISIZE : rc;
 }
 
 // ================================================================================================ the host side (plain C++)
 #include <algorithm>
 #include <vector>
-
-struct stream_span {                             // one confirmed span (the table has one more entry: out_off = total)
-    int64_t start, stop, out_off, land;
-};
 
 struct stream_host_sym_sink {
     uint16_t *sym;
@@ -427,14 +326,8 @@ static int dgrp_stream_inflate_host(const uint8_t *h_in, int64_t in_len, int64_t
         std::vector<uint16_t> sym((size_t)total + 1);
         const size_t nspan = tab.size() - 1;
         for (size_t k = 0; k < nspan && rc == DGRP_OK; ++k) {
-            const dgrp_stream_slice sl = dgrp_stream_slice_at(h_in, c.n, tab[k].start, c.clip);
             stream_host_sym_sink sink{sym.data() + tab[k].out_off};
-            const uint32_t cap = (uint32_t)(tab[k + 1].out_off - tab[k].out_off);
-            int64_t land = 0;
-            uint32_t bytes = 0;
-            int fin = 0;
-            int r = dgrp_span_decode(sl.in, sl.len, sl.skip, tab[k].stop - sl.bit0, cap, &t, sink, &land, &bytes, &fin);
-            if (r == DGRP_INFLATE_OK && (bytes != cap || sl.bit0 + land != tab[k].land)) r = DGRP_INFLATE_EISIZE;
+            const int r = dgrp_stream_span(h_in, c.n, c.clip, tab[k], (uint32_t)(tab[k + 1].out_off - tab[k].out_off), &t, sink);
             if (r != DGRP_INFLATE_OK) {
                 *h_reason = r;
                 rc = DGRP_EDATA;

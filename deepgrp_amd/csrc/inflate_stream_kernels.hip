@@ -99,13 +99,8 @@ __global__ void __launch_bounds__(64) inflate_symbols_kernel(const uint8_t *__re
     if (sp.start < 0 || sp.start > 8 * n || sp.out_off < 0 || o1 < sp.out_off || o1 > total || o1 - sp.out_off > (int64_t)DGRP_SPAN_MAX_OUT) {
         rc = DGRP_INFLATE_EOUTPUT;
     } else {
-        const dgrp_stream_slice sl = dgrp_stream_slice_at(in, n, sp.start, clip);
         stream_wave_sym_sink sink{sym + sp.out_off, threadIdx.x};
-        int64_t land = 0;
-        uint32_t bytes = 0;
-        int fin = 0;
-        rc = dgrp_span_decode(sl.in, sl.len, sl.skip, sp.stop - sl.bit0, (uint32_t)(o1 - sp.out_off), &t, sink, &land, &bytes, &fin);
-        if (rc == DGRP_INFLATE_OK && (bytes != (uint32_t)(o1 - sp.out_off) || sl.bit0 + land != sp.land)) rc = DGRP_INFLATE_EISIZE;
+        rc = dgrp_stream_span(in, n, clip, sp, (uint32_t)(o1 - sp.out_off), &t, sink);
     }
     if (threadIdx.x == 0) status[k] = rc;
 }
@@ -163,40 +158,15 @@ __global__ void __launch_bounds__(256) inflate_resolve_kernel(const stream_span 
     if (bad != DGRP_INFLATE_OK) status[k] = bad;                      // (every writer holds a reason)
 }
 
-// one wave per 64 KiB piece, 1 KiB a lane, the 64 CRCs combined as inflate_member_kernel combines them
+// one wave per 64 KiB piece, 1 KiB a lane
 __global__ void __launch_bounds__(64) inflate_crc_kernel(const uint8_t *__restrict__ out, int64_t total, uint32_t *__restrict__ crcs)
 {
     __shared__ uint32_t crctab[256];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t i = lane; i < 256; i += 64) crctab[i] = dgrp_crc_table_entry(i);
-    __syncthreads();
     const int64_t p0 = (int64_t)blockIdx.x * STREAM_CRC_PIECE;
     const int64_t p1 = min(p0 + STREAM_CRC_PIECE, total);
-    const int64_t a = min(p0 + (int64_t)lane * (STREAM_CRC_PIECE / 64), p1), b = min(a + STREAM_CRC_PIECE / 64, p1);
-    uint32_t c = 0xffffffffu;
-    for (int64_t i = a; i < b; ++i) c = crctab[(c ^ out[i]) & 0xff] ^ (c >> 8);
-    c ^= 0xffffffffu;
-    const uint32_t px = dgrp_crc_x8n((uint64_t)(b - a));
-    uint32_t crc = __shfl(c, 0);
-    for (int i = 1; i < 64; ++i) crc = dgrp_crc_multmodp(__shfl(px, i), crc) ^ __shfl(c, i);
-    if (lane == 0) crcs[blockIdx.x] = crc;
-}
-
-static const char *stream_reason_text(int r)
-{
-    switch (r) {
-    case DGRP_INFLATE_EINPUT: return "input ends inside the stream";
-    case DGRP_INFLATE_EBLOCK: return "invalid block type";
-    case DGRP_INFLATE_ESTORED: return "stored block LEN/NLEN mismatch";
-    case DGRP_INFLATE_ECODES: return "invalid code lengths";
-    case DGRP_INFLATE_ESYMBOL: return "invalid symbol";
-    case DGRP_INFLATE_EDIST: return "distance too far back";
-    case DGRP_INFLATE_EOUTPUT: return "output beyond its size";
-    case DGRP_INFLATE_EISIZE: return "a span decoded differently than it was counted";
-    case DGRP_INFLATE_ESPAN: return "a span longer than max_span_bytes";
-    case DGRP_INFLATE_EROUNDS: return "the chain is not closed after max_rounds rounds";
-    default: return "unknown";
-    }
+    const int64_t a = min(p0 + (int64_t)threadIdx.x * (STREAM_CRC_PIECE / 64), p1), b = min(a + STREAM_CRC_PIECE / 64, p1);
+    const uint32_t crc = dgrp_crc_wave(out + a, out + b, crctab);
+    if (threadIdx.x == 0) crcs[blockIdx.x] = crc;
 }
 
 static bool stream_sizes_ok(int64_t n, int64_t chunk, int64_t max_span, int max_rounds)
@@ -220,7 +190,7 @@ DGRP_EXPORT int dgrp_inflate_stream_host(const uint8_t *h_in, int64_t in_len, in
     const int rc = dgrp_stream_inflate_host(h_in, in_len, chunk_bytes, max_span_bytes, max_rounds, h_out, out_cap, h_out_len, h_in_used, h_stats,
                                             h_reason);
     if (rc == DGRP_EDATA)
-        dgrp_set_error("dgrp_inflate_stream_host: %s (reason %d)", stream_reason_text(*h_reason), *h_reason);
+        dgrp_set_error("dgrp_inflate_stream_host: %s (reason %d)", dgrp_inflate_reason_text(*h_reason, true), *h_reason);
     return rc;
 }
 
@@ -308,7 +278,7 @@ DGRP_EXPORT int dgrp_inflate_stream_scan(const uint8_t *d_in, int64_t in_bytes, 
     };
     const int rc = stream_chain_run(c, max_span_bytes, max_rounds, count, h_stats, h_reason);
     if (rc == DGRP_EDATA)
-        dgrp_set_error("dgrp_inflate_stream_scan: %s (reason %d)", stream_reason_text(*h_reason), *h_reason);
+        dgrp_set_error("dgrp_inflate_stream_scan: %s (reason %d)", dgrp_inflate_reason_text(*h_reason, true), *h_reason);
     if (rc != DGRP_OK) return rc;
     std::vector<stream_span> tab;
     const int64_t total = stream_span_table(c, tab);
@@ -383,7 +353,7 @@ DGRP_EXPORT int dgrp_inflate_stream_write(const uint8_t *d_in, int64_t in_bytes,
     for (size_t k = 0; k < st.size(); ++k)
         if (st[k] != DGRP_INFLATE_OK) {
             *h_reason = st[k];
-            dgrp_set_error("dgrp_inflate_stream_write: span %lld: %s (reason %d)", (long long)k, stream_reason_text(st[k]), st[k]);
+            dgrp_set_error("dgrp_inflate_stream_write: span %lld: %s (reason %d)", (long long)k, dgrp_inflate_reason_text(st[k], true), st[k]);
             return DGRP_EDATA;
         }
     uint32_t crc = 0;

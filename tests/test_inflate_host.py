@@ -210,6 +210,58 @@ def test_corrupt_corpus(name, stream, cap, reason):
         assert rc == EDATA and got > 0
 
 
+# (return code, reason, bytes produced, input bytes used) of every fixed-reason case, recorded once on the CPU from the library as it
+# was while the member path, the span path and the candidate filter each had a block loop of their own
+PINNED = {
+    "truncated_0": (-5, 1, 0, 0), "truncated_1": (-5, 1, 0, 1), "truncated_2": (-5, 1, 0, 2), "truncated_5": (-5, 1, 0, 5),
+    "truncated_3247": (-5, 1, 9558, 3247), "truncated_6494": (-5, 1, 20000, 6494),
+    "block_type_3": (-5, 2, 0, 1), "stored_len_nlen": (-5, 3, 0, 5), "stored_truncated": (-5, 1, 0, 8), "stored_over_cap": (-5, 7, 0, 5),
+    "distance_too_far": (-5, 6, 1, 3), "distance_before_any_output": (-5, 6, 0, 2), "literal_286": (-5, 5, 1, 3),
+    "distance_code_30": (-5, 5, 1, 3), "clen_oversubscribed": (-5, 4, 0, 10), "clen_incomplete": (-5, 4, 0, 4),
+    "repeat_without_previous": (-5, 4, 0, 4), "too_many_lengths": (-5, 4, 0, 3), "no_end_of_block": (-5, 4, 0, 42),
+    "output_over_cap": (-5, 7, 19997, 6494), "empty_input": (-5, 1, 0, 0),
+}
+# one case of each reason a host entry can give, and the words dgrp_last_error() has for it
+TEXTS = {"truncated_5": "input ends inside the stream", "block_type_3": "invalid block type", "stored_len_nlen": "stored block LEN/NLEN mismatch",
+         "clen_incomplete": "invalid code lengths", "literal_286": "invalid symbol", "distance_too_far": "distance too far back",
+         "stored_over_cap": "output beyond its size"}
+
+
+def test_corrupt_corpus_results_are_pinned():
+    fixed = {c[0]: c for c in CORRUPT if c[3] is not None}
+    assert set(fixed) == set(PINNED)
+    for name, (_, stream, cap, reason) in fixed.items():
+        rc, out, used, got = inflate(stream, cap)
+        assert (rc, got, len(out), used) == PINNED[name] and got == reason, name
+
+
+def test_error_text_of_both_host_entries():
+    from deepgrp_amd._lib import InflateStreamStats
+    fixed = {c[0]: c for c in CORRUPT}
+    assert sorted(PINNED[name][1] for name in TEXTS) == [EINPUT, EBLOCK, ESTORED, ECODES, ESYMBOL, EDIST, EOUTPUT]
+    for name, text in TEXTS.items():
+        _, stream, cap, reason = fixed[name]
+        rc, _out, used, got = inflate(stream, cap)
+        assert (rc, got) == (EDATA, reason)
+        assert lib().dgrp_last_error().decode() == f"dgrp_inflate_raw_host: {text} (reason {reason}) near input byte {used}"
+        out = (C.c_uint8 * cap)()
+        ol, iu, r, st = C.c_int64(), C.c_int64(), C.c_int(), InflateStreamStats()
+        rc = lib().dgrp_inflate_stream_host(stream, len(stream), 1 << 10, 1 << 22, 64, out, cap, C.byref(ol), C.byref(iu), C.byref(st), C.byref(r))
+        assert (rc, r.value) == (EDATA, reason)
+        assert lib().dgrp_last_error().decode() == f"dgrp_inflate_stream_host: {text} (reason {reason})"
+
+
+def test_reason_nine_keeps_both_wordings():
+    """DGRP_INFLATE_EISIZE is what the trailer check of the member kernel gives, and what a span's second decode gives when it
+    disagrees with its count, which no stream makes the host do.  So no host entry can show its text: the one table both paths
+    share must still hold the member's wording and the span's."""
+    import os
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "deepgrp_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in ("inflate.h", "inflate_stream.h", "inflate_kernels.hip", "inflate_stream_kernels.hip"))
+    assert text.count('"output shorter than ISIZE"') == 1 and text.count('"a span decoded differently than it was counted"') == 1
+    assert text.count("case DGRP_INFLATE_EISIZE:") == 1
+
+
 # ---------------------------------------------------------------- argument checks (DGRP_EINVAL without a GPU)
 P = 0x10000
 I64 = lambda: C.pointer(C.c_int64())

@@ -163,6 +163,48 @@ def test_the_round_limit_refuses():
     assert stream_host(comp, 4 << 10, len(want), max_rounds=st["rounds"])[1] == want
 
 
+def test_error_text_of_the_span_and_round_limits():
+    comp, want = _unfindable()["fixed"]
+    assert stream_host(comp, 4 << 10, len(want), max_span=len(comp) - 1)[3] == ESPAN
+    assert lib().dgrp_last_error().decode() == "dgrp_inflate_stream_host: a span longer than max_span_bytes (reason 11)"
+    comp, want = gc.corpus()["half-l6"]
+    assert stream_host(comp, 4 << 10, len(want), max_rounds=3)[3] == EROUNDS
+    assert lib().dgrp_last_error().decode() == "dgrp_inflate_stream_host: the chain is not closed after max_rounds rounds (reason 12)"
+
+
+def _edge_stream(valid: bool) -> bytes:
+    """A stored block of zero bytes that ends at byte 33 * 1024 (no bit offset inside zeros reads BFINAL = 0, BTYPE = 2), then a
+    hand-built non-final dynamic block whose first symbol is a match of distance 32 768, then a final block -- or, in place of it,
+    the header of a block of type 3."""
+    b = gc.Bits()
+    b.put(0, 3)
+    b.n = 8
+    n = 33 * 1024 - 5
+    b.put(n, 16), b.put(~n & 0xffff, 16)
+    b.n += 8 * n
+    assert b.n == 8 * 33 * 1024
+    gc.hand_block(b, [(258, 32768), 65, 66], False)
+    if valid:
+        gc.hand_block(b, [67], True)
+    else:
+        b.put(1, 1), b.put(3, 2)
+    return b.bytes()
+
+
+def test_a_candidate_may_reach_the_whole_window_at_position_0():
+    """The block at the start of chunk 33 (chunks of 1 KiB) opens with a match of distance 32 768 at span position 0: the candidate
+    filter must let a match reach the whole window in front of the span, so it is found and the stream is two spans.  DEFLATE has
+    no distance above 32 768 (distance symbol 29 with all 13 extra bits set; a dynamic block has no symbol 30), so the refusal of
+    a farther one cannot be put into a stream; the block that must not be found is the same one with a block of type 3 behind it."""
+    comp = _edge_stream(True)
+    want = zlib.decompress(comp, -15)
+    rc, got, used, reason, st = stream_host(comp, 1 << 10, len(want))
+    assert (rc, reason, got, used) == (0, 0, want, len(comp))
+    assert (st["chunks"], st["candidates"], st["spans"], st["repaired"], st["longest_span"]) == (34, 1, 2, 0, 33 * 1024)
+    rc, got, used, reason, st = stream_host(_edge_stream(False), 1 << 10, 100_000)
+    assert (rc, reason, st["chunks"], st["candidates"]) == (EDATA, 2, 34, 0)
+
+
 def _zlib_says(comp: bytes):
     d = zlib.decompressobj(-15)
     try:
