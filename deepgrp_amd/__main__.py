@@ -30,6 +30,9 @@ Differences, all additive:
     lengths, the share of the record, GC and the agreement with the input's own soft mask, counted on the GPU
     (deepgrp_amd/summary.py); with --summary_bin also DIR/<basename>.density.tsv, the bases per label in bins of N positions;
   * `evaluate <model> <annotation> <FASTA>...` scores predict's rows against a repeat annotation (deepgrp_amd/evaluation.py);
+  * the annotation of `evaluate`, and the bedfile of `train` on sequence files, may be RepeatMasker's own output (`genome.fa.out`,
+    `.out.gz`, UCSC `rmsk.txt.gz`; `--annotation_format auto|table|repeatmasker`): it is parsed on the GPU into what the table of
+    `parse_rm` holds (deepgrp_amd/annotation.py); `optimize` and `train` on .npz files read the table only;
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -317,6 +320,10 @@ class CommandLineParser:
                            help="(addition) with a sequence file (FASTA, gzip, BGZF, .2bit) as trainfile: the records to train on, by "
                                 "the first word of their header, comma separated (default: every record, in file order)")
         train.add_argument("--valid_contigs", type=str, default=None, help="(addition) the same for validfile")
+        train.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+                           help="(addition) what bedfile is: `table` = the six columns parse_rm writes, `repeatmasker` = RepeatMasker's "
+                                "own listing (`.out`, `.out.gz`) or UCSC's rmsk table, parsed on the GPU (sequence files only); `auto` "
+                                "looks at the first lines")
         optimize = subparsers.add_parser(name="optimize", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                          description="(addition) hyper-parameter search (deepgrp/optimization.py): seeded random "
                                                      "search over the [space] table of a TOML file, trials trained side by side on "
@@ -327,6 +334,9 @@ class CommandLineParser:
         optimize.add_argument("trainfile", type=str)
         optimize.add_argument("validfile", type=str)
         optimize.add_argument("bedfile", type=str)
+        optimize.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+                              help="what bedfile is; only `table` (the six columns parse_rm writes) is read here: RepeatMasker "
+                                   "output is refused by name")
         optimize.add_argument("--max_evals", type=int, default=20, help="trials to add to results.json")
         optimize.add_argument("--cohort", type=int, default=DEFAULT_COHORT,
                               help="trials trained side by side, 1..64 (more than 8 run in slices of 8 per step)")
@@ -373,7 +383,11 @@ class CommandLineParser:
                         "users get is what is measured.")
         evaluate.add_argument("model", type=str, help="Keras model in HDF5 format")
         evaluate.add_argument("annotation", type=str, help="table as parse_rm writes it: contig, 0-based begin, exclusive end, "
-                                                           "repeat number, further columns ignored")
+                                                           "repeat number, further columns ignored; or RepeatMasker's own listing "
+                                                           "(`.out`, UCSC rmsk; plain, gzip or BGZF), parsed on the GPU")
+        evaluate.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+                              help="what the annotation is; `auto` looks at its first lines.  A RepeatMasker listing gives what the "
+                                   "table parse_rm writes from it gives; it is read after the device is opened, the table before")
         evaluate.add_argument("FASTA", nargs="+", type=str, help="inputs as for predict: FASTA files, '-', `<name>.gz.npz`; a "
                                                                  "record is matched to the annotation by the first word of its "
                                                                  "header (.npz: the file name up to the first '.')")
@@ -1094,8 +1108,12 @@ class CommandLineParser:
         bad = [r for r in repeats if not 0 < r < classes]
         if bad:
             sys.exit(f"--repeats: {bad[0]} is not a repeat class of this model (1..{classes - 1})")
+        from . import annotation as dgann
+        listed = dgann.resolve_format(args.annotation, args.annotation_format) == "repeatmasker"
         try:
-            annotation = read_annotation(args.annotation, repeats)
+            # a table is read here, before the device is touched; a RepeatMasker listing is parsed ON the device (the model's class
+            # check above still comes first)
+            annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else read_annotation(args.annotation, repeats)
         except AnnotationError as e:
             sys.exit(str(e))
         model = dgmodel.device_model(weights)
@@ -1184,11 +1202,15 @@ class CommandLineParser:
         sides = (("trainfile", args.trainfile, "--train_contigs", args.train_contigs),
                  ("validfile", args.validfile, "--valid_contigs", args.valid_contigs))
         npz = [dgtrain.is_npz(path) for _role, path, _flag, _contigs in sides]
+        from . import annotation as dgann
+        listed = dgann.resolve_format(args.bedfile, args.annotation_format) == "repeatmasker"
         if npz[0] != npz[1]:
             kinds = ["a .npz of preprocess_sequence" if z else "a sequence file" for z in npz]
             sys.exit(f"train: {sides[0][0]} {sides[0][1]} is {kinds[0]} and {sides[1][0]} {sides[1][1]} is {kinds[1]}: "
                      "give both sides in one form")
         if npz[0]:
+            if listed:
+                sys.exit(dgann.refuse_npz("train", args.bedfile))
             for _role, path, flag, contigs in sides:
                 if contigs is not None:
                     sys.exit(f"train: {flag} selects records of a sequence file; {path} is a .npz of preprocess_sequence, one "
@@ -1219,7 +1241,9 @@ class CommandLineParser:
                 os.mkdir(logdir)
             _LOG.info("Loading in all data necessary from %s, %s, %s", args.trainfile, args.validfile, args.bedfile)
             try:
-                train_data, val_data = (dgtrain.DeviceData.from_sequence_file(path, args.bedfile, parameter.repeats_to_search,
+                # a RepeatMasker listing is parsed once, on the device, for both sides
+                bed = dgann.read_listing(args.bedfile) if listed else args.bedfile
+                train_data, val_data = (dgtrain.DeviceData.from_sequence_file(path, bed, parameter.repeats_to_search,
                                                                              contigs, vecsize=int(parameter.vecsize))
                                         for (_role, path, _flag, _c), contigs in zip(sides, picked))
             except ValueError as exc:
@@ -1254,6 +1278,9 @@ class CommandLineParser:
             sys.exit(f"optimize: --cohort {args.cohort}: 1..64 trials can be trained side by side")
         if args.max_evals < 1:
             sys.exit(f"optimize: --max_evals {args.max_evals}: at least one trial")
+        from . import annotation as dgann
+        if dgann.resolve_format(args.bedfile, args.annotation_format) == "repeatmasker":
+            sys.exit(dgann.refuse_npz("optimize", args.bedfile))
         with open(args.space, "rb") as file:
             try:
                 space = tomli.load(file).get("space")

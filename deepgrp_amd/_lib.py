@@ -165,6 +165,8 @@ _SIGNATURES = {
     "dgrp_class_starts_workspace_bytes": (i64, [i64, i64]),
     "dgrp_class_window_starts": (cint, [vp, i64, i64, vp, vp, cint, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_train_resolve_starts": (cint, [vp, i64, vp, vp, cint, vp, vp, i64, vp, vp]),
+    "dgrp_rm_parse_workspace_bytes": (i64, [i64]),
+    "dgrp_rm_parse": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

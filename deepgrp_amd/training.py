@@ -410,7 +410,8 @@ class DeviceData:
     def from_sequence_file(cls, path, bedfile, repeats_to_search, contigs: Optional[List[str]] = None,
                            vecsize: Optional[int] = None) -> "DeviceData":
         """The records of a FASTA / gzip / BGZF / .2bit file that `contigs` names by the first word of their header (None: every
-        record), in file order, and their truth from the parse_rm table `bedfile`, painted on the device.  With `vecsize`, a record
+        record), in file order, and their truth from the parse_rm table `bedfile` (or the annotation.Listing of a RepeatMasker listing),
+        painted on the device.  With `vecsize`, a record
         that holds no window of that length is left out with a warning.  ValueError: a listed contig the file does not hold, two
         selected records with one name, a kept annotation row whose repeat number has no truth row, no record left."""
         import torch
@@ -441,7 +442,9 @@ class DeviceData:
         select_contigs(found, contigs, str(path))                        # names the absent and the duplicated
         if not parts:
             raise ValueError(f"{path}: no window of {vecsize if vecsize is not None else 1} fits into a selected record")
-        rows = read_truth_rows(bedfile, names, repeats_to_search)
+        # (a RepeatMasker listing comes parsed, as an annotation.Listing: read_truth_rows' rules on its arrays)
+        rows = (bedfile.truth_rows(names, repeats_to_search) if hasattr(bedfile, "truth_rows")
+                else read_truth_rows(bedfile, names, repeats_to_search))
         classes = len(repeats_to_search) + 1
         d_idx = torch.cat(parts)
         del parts

@@ -1026,6 +1026,33 @@ int dgrp_train_resolve_starts(const int64_t *d_picks, int64_t B, const int64_t *
                               int nsets, const int64_t *d_base, const int64_t *d_wprefix, int64_t nrec, int64_t *d_starts,
                               void *stream);
 
+/* ---- RepeatMasker listings read on the device (an addition; the reference reads them on the host: deepgrp/_scripts/parse_rm.py).
+ * d_text [n]: the text of a `.out` listing or a UCSC `rmsk` table in device memory, any alignment.  The entry finds the lines, takes
+ * each through the token statement of parse_rm's two patterns (`.out` first, then `rmsk`), numbers it and keeps it when the
+ * number is above 0:
+ *   number = position (from 1) of the family -- `rmsk`: class, or class/family where they differ -- among the nnames names
+ *   d_names[d_name_off[i] .. d_name_off[i + 1]) (device), else of the repeat name, else unit_number for a family `Simple_repeat` or
+ *   `Satellite` whose repeat name opens with `(` [ACGT]+ `)n`, the unit a multiple of five long, every 5-mer c of it with
+ *   d_pentamers[c] != 0 and one with d_pentamers[c] == 1 (device uint8 [1024], c = the five bases A C G T = 0 1 2 3 as base-4 digits,
+ *   first base highest).
+ * Kept rows, in file order, i = 0 .. kept - 1: d_begin[i] (`.out`: begin - 1), d_end[i], d_number[i], d_name_pos[i] / d_name_len[i]
+ * (the contig token as a span of d_text), d_line[i] (from 1).  d_run_first[r], r = 0 .. runs - 1: the first row of run r, a maximal
+ * stretch of rows whose contig tokens are byte-equal.  h_counts[4] (host): lines, kept rows, runs, not-plain flag.
+ * NOT PLAIN: a byte outside 0x20..0x7e other than tab and line feed, a carriage return not directly before a line feed, or a
+ * coordinate of more than 18 digits.  Then h_counts[3] = 1, no row is written and DGRP_OK is returned: the caller parses such a
+ * file on the host.  More kept rows than `cap`: DGRP_ENOMEM, h_counts[1] = the capacity needed, no row written; n / 22 + 1 rows always
+ * suffice (the shortest line that matches).  n = 0: zero counts.  Refused before any launch with DGRP_EINVAL: NULL text with n > 0,
+ * n < 0, a NULL table, a NULL output with cap > 0; with DGRP_ENOMEM: a workspace (256-byte aligned) below the companion's bytes.
+ * A workgroup takes DGRP_RM_TILE_BYTES of text, a lane 128 of them and the lines that start there; a count pass, two scans, a write
+ * pass, then the run flags, their scan and the run starts.  Integers only; the only atomic is the OR of the flag: the same call
+ * gives the same bytes.  On the caller's stream; it SYNCHRONISES that stream twice (counts, then runs) and allocates nothing. */
+#define DGRP_RM_TILE_BYTES 32768
+int64_t dgrp_rm_parse_workspace_bytes(int64_t n);
+int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                  const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number, int64_t *d_name_pos,
+                  int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap, int64_t *h_counts, void *d_work,
+                  int64_t work_bytes, void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
