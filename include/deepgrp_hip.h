@@ -839,6 +839,8 @@ int dgrp_inflate_raw_host(const uint8_t *h_in, int64_t in_len, uint8_t *h_out, i
  * prefix sum of the ISIZEs, h_out_off[nmem] <= out_bytes, each slice < 2^31).  Every member must end its final block exactly at
  * its trailer and match the trailer's CRC-32 and ISIZE (checked on the device).  On DGRP_EDATA *h_bad = the lowest failing member
  * and *h_reason its DGRP_INFLATE_* reason (bytes of failing members are undefined); on success *h_bad = -1, *h_reason = 0.
+ * A member's reason is the first that applies of: the stream's own (1 .. 7), DGRP_INFLATE_ETRAIL, DGRP_INFLATE_EISIZE or
+ * DGRP_INFLATE_EOUTPUT (fewer or more bytes than ISIZE), DGRP_INFLATE_ECRC; the members beside a failing one are complete.
  * Workspace dgrp_inflate_workspace_bytes(nmem).  Synchronous (one read-back of the per-member status). */
 int64_t dgrp_inflate_workspace_bytes(int64_t nmem);
 int dgrp_inflate_batch(const uint8_t *d_in, int64_t in_bytes, int64_t nmem, const int64_t *h_in_off, const int64_t *h_in_len,

@@ -16,6 +16,7 @@ from conftest import GOLDEN
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gzip_stream_cases as gc                          # noqa: E402
+import inflate_cases as ic                              # noqa: E402
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -42,13 +43,13 @@ def host_stats(comp, chunk, cap, max_span, max_rounds):
     return rc, r.value, st.as_dict()
 
 
-def device_inflate(comp, chunk, max_span=gc.MAX_SPAN, max_rounds=gc.MAX_ROUNDS, stream=None):
-    """scan and write on `HEAD + comp + 8 trailer bytes` -> (rc, reason, text, crc, in_used, statistics); every buffer between
-    sentinels that must survive"""
+def device_inflate(comp, chunk, max_span=gc.MAX_SPAN, max_rounds=gc.MAX_ROUNDS, stream=None, tail=b"\xee" * 8):
+    """scan and write on `HEAD + comp + tail` (8 trailer bytes) -> (rc, reason, text, crc, in_used, statistics); every buffer
+    between sentinels that must survive"""
     from deepgrp_amd._lib import InflateStreamStats, lib
     L = lib()
     dev = torch.device("cuda", torch.cuda.current_device())
-    file = HEAD + comp + b"\xee" * 8
+    file = HEAD + comp + tail
     d_in = torch.frombuffer(bytearray(file), dtype=torch.uint8).to(dev)
     wb = int(L.dgrp_inflate_stream_workspace_bytes(len(file), chunk))
     assert wb > 0 and wb % 256 == 0
@@ -101,6 +102,30 @@ def test_refusals_carry_the_reason_of_the_host_entry():
         rc, reason, _, _, _, st = device_inflate(comp, 4 << 10, **kw)
         hrc, hreason, hst = host_stats(comp, 4 << 10, 4_000_000, kw.get("max_span", gc.MAX_SPAN), kw.get("max_rounds", gc.MAX_ROUNDS))
         assert (rc, reason) == (hrc, hreason) and rc == -5 and reason in (1, 11, 12)
+
+
+CORE_CASES = [c for c in ic.CORRUPT if c[0] not in ("stored_over_cap", "output_over_cap")]
+
+
+@pytest.mark.parametrize("chunk", [64, 1024])
+@pytest.mark.parametrize("name,comp", [c[:2] for c in CORE_CASES], ids=[c[0] for c in CORE_CASES])
+def test_corrupt_corpus_of_the_decode_core_equals_the_host_entry(name, comp, chunk):
+    """The corrupt corpus of the decode core (tests/inflate_cases.py: the fixed-reason cases whose reason needs no output cap, the
+    flipped and the random streams) as a stream that ends where the file ends: scan and write give the return code and reason of
+    dgrp_inflate_stream_host, and its text and input bytes used where it decodes.  The yardstick is the stream host entry, not
+    dgrp_inflate_raw_host: both refuse the same streams, but on inflate_cases.HOST_ENTRIES_DIFFER (five random streams, at both
+    chunk sizes) with different reasons -- the span path's counting pass decodes the whole stream and meets a later error before
+    the window walk can report the bad distance the serial decoder stops at (test_inflate_cases_host.py holds that list to the
+    two host entries)."""
+    hrc, hreason, htext, hused = ic.stream_host(comp, chunk, 1 << 20, gc.MAX_SPAN, gc.MAX_ROUNDS)
+    assert (hrc, hreason) != (-5, ic.EOUTPUT)                                # the cap of the host entry plays no part
+    rc, reason, text, crc, used, _st = device_inflate(comp, chunk, tail=b"")
+    assert (rc, reason) == (hrc, hreason)
+    if hrc == 0:
+        assert ic.zlib_says(comp) == (htext, hused)
+        assert text == htext and used == len(HEAD) + hused and crc == zlib.crc32(htext)
+    else:
+        assert rc == -5 and reason > 0 and text is None
 
 
 def test_write_refuses_a_workspace_without_the_chain():

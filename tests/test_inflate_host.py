@@ -3,13 +3,18 @@ runs) against zlib, a corrupt corpus that must come back as reasons, the argumen
 and the refusals of compressed input that happen before any device work."""
 import ctypes as C
 import gzip
+import os
+import sys
 import zlib
 
 import numpy as np
 import pytest
 
-from deepgrp_amd import gz
-from deepgrp_amd._lib import lib
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from inflate_cases import CORRUPT, INPUTS, PINNED, deflate, fixed_stream   # noqa: E402  (the corpus, shared with the GPU tests)
+
+from deepgrp_amd import gz                           # noqa: E402
+from deepgrp_amd._lib import lib                     # noqa: E402
 
 EINVAL, ENOMEM, EDATA = -1, -3, -5
 EINPUT, EBLOCK, ESTORED, ECODES, ESYMBOL, EDIST, EOUTPUT = 1, 2, 3, 4, 5, 6, 7
@@ -24,81 +29,6 @@ def inflate(comp: bytes, cap: int):
     rc = lib().dgrp_inflate_raw_host(comp, len(comp), out, cap, C.byref(ol), C.byref(iu), C.byref(r))
     assert 0 <= ol.value <= cap and 0 <= iu.value <= len(comp)
     return rc, bytes(out[:ol.value]), iu.value, r.value
-
-
-def deflate(data: bytes, level: int, strategy: int) -> bytes:
-    co = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    return co.compress(data) + co.flush()
-
-
-# ---------------------------------------------------------------- a hand-written fixed-Huffman encoder (streams zlib never emits)
-class Bits:
-    def __init__(self):
-        self.acc, self.n = 0, 0
-
-    def put(self, v: int, k: int):                 # k bits of v, LSB first (header fields, extra bits)
-        self.acc |= (v & ((1 << k) - 1)) << self.n
-        self.n += k
-
-    def code(self, c: int, k: int):                 # a Huffman code: MSB first
-        self.put(int(format(c, f"0{k}b")[::-1], 2), k)
-
-    def bytes(self) -> bytes:
-        return self.acc.to_bytes((self.n + 7) // 8, "little")
-
-
-def fixed_lit(b: Bits, sym: int):
-    if sym < 144:
-        b.code(0x30 + sym, 8)
-    elif sym < 256:
-        b.code(0x190 + sym - 144, 9)
-    elif sym < 280:
-        b.code(sym - 256, 7)
-    else:
-        b.code(0xC0 + sym - 280, 8)
-
-
-def fixed_match(b: Bits, length: int, dist: int):
-    lbase = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-    lext = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-    dbase = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
-             8193, 12289, 16385, 24577]
-    dext = [0, 0, 0, 0] + [k // 2 for k in range(2, 28)]
-    i = max(k for k in range(29) if lbase[k] <= length and (k == 28) == (length == 258))
-    fixed_lit(b, 257 + i)
-    b.put(length - lbase[i], lext[i])
-    d = max(k for k in range(30) if dbase[k] <= dist)
-    b.code(d, 5)
-    b.put(dist - dbase[d], dext[d])
-
-
-def fixed_stream(items, final=True) -> bytes:
-    """items: ints (literals / raw symbols) or (length, distance) pairs; one fixed block ended by symbol 256."""
-    b = Bits()
-    b.put(1 if final else 0, 1)
-    b.put(1, 2)
-    for it in items:
-        if isinstance(it, tuple):
-            fixed_match(b, *it)
-        else:
-            fixed_lit(b, it)
-    fixed_lit(b, 256)
-    return b.bytes()
-
-
-# ---------------------------------------------------------------- inputs
-def _inputs():
-    rng = np.random.default_rng(11)
-    acgt = rng.choice(list(b"ACGT"), size=50_000).astype(np.uint8).tobytes()
-    fasta = b">chr1 test\n" + b"\n".join(acgt[i:i + 60] for i in range(0, len(acgt), 60)) + b"\n"
-    nrun = b"N" * 30_000 + acgt[:500] + b"N" * 20_000 + b"n" * 3
-    rand = rng.integers(0, 256, size=40_000, dtype=np.uint8).tobytes()
-    x = rng.integers(0, 256, size=300, dtype=np.uint8).tobytes()
-    far = x + rng.integers(0, 256, size=32_768 - 300, dtype=np.uint8).tobytes() + x + x[:100] * 3
-    return {"fasta": fasta, "nrun": nrun, "random": rand, "far": far, "empty": b"", "max": (acgt + acgt)[:65536]}
-
-
-INPUTS = _inputs()
 
 
 @pytest.mark.parametrize("strategy", sorted(STRATEGIES))
@@ -135,62 +65,6 @@ def test_output_of_exactly_64k_and_over_the_cap():
         assert (rc, reason) == (EDATA, EOUTPUT) and out == data[:len(out)]
 
 
-def _dynamic_header(clen, hlit=0, hdist=0):
-    """A dynamic block header: BFINAL=1, BTYPE=2, the code length code lengths `clen` in transmission order."""
-    b = Bits()
-    b.put(1, 1)
-    b.put(2, 2)
-    b.put(hlit, 5)
-    b.put(hdist, 5)
-    b.put(len(clen) - 4, 4)
-    for v in clen:
-        b.put(v, 3)
-    return b
-
-
-def _corrupt_corpus():
-    """(name, stream, output cap, expected reason or None = any failure)."""
-    data = INPUTS["fasta"][:20_000]
-    good = deflate(data, 6, zlib.Z_DEFAULT_STRATEGY)
-    cases = []
-    for k in (0, 1, 2, 5, len(good) // 2, len(good) - 1):
-        cases.append((f"truncated_{k}", good[:k], len(data), EINPUT))
-    cases.append(("block_type_3", bytes([0x07, 0, 0, 0]), 100, EBLOCK))
-    cases.append(("stored_len_nlen", bytes([0x01, 5, 0, 0, 0]) + b"hello", 100, ESTORED))
-    cases.append(("stored_truncated", bytes([0x01, 5, 0, 0xFA, 0xFF]) + b"hel", 100, EINPUT))
-    cases.append(("stored_over_cap", bytes([0x01, 5, 0, 0xFA, 0xFF]) + b"hello", 4, EOUTPUT))
-    cases.append(("distance_too_far", fixed_stream([65, (3, 2)]), 100, EDIST))
-    cases.append(("distance_before_any_output", fixed_stream([(3, 1)]), 100, EDIST))
-    cases.append(("literal_286", fixed_stream([65, 286]), 100, ESYMBOL))
-    b = Bits()
-    b.put(1, 1), b.put(1, 2), fixed_lit(b, 65), fixed_lit(b, 257), b.code(30, 5)
-    cases.append(("distance_code_30", b.bytes() + b"\0" * 4, 100, ESYMBOL))
-    cases.append(("clen_oversubscribed", _dynamic_header([1] * 19).bytes() + b"\0" * 8, 100, ECODES))
-    cases.append(("clen_incomplete", _dynamic_header([2, 0, 0, 0]).bytes() + b"\0" * 8, 100, ECODES))
-    b = _dynamic_header([1, 0, 1, 0])                    # codes for 16 and 18 only: the first symbol is a repeat of nothing
-    b.put(0, 1)
-    cases.append(("repeat_without_previous", b.bytes() + b"\0" * 8, 100, ECODES))
-    b = _dynamic_header([0] * 3 + [1] + [0] * 14 + [1], hlit=31)     # 0 and 1 only; hlit = 288 lengths > 286
-    cases.append(("too_many_lengths", b.bytes() + b"\0" * 8, 100, ECODES))
-    b = _dynamic_header([0] * 3 + [1] + [0] * 14 + [1])              # every literal/length code length 0: no end-of-block code
-    for _ in range(258):
-        b.put(0, 1)
-    cases.append(("no_end_of_block", b.bytes() + b"\0" * 8, 100, ECODES))
-    cases.append(("output_over_cap", good, len(data) - 1, EOUTPUT))
-    cases.append(("empty_input", b"", 100, EINPUT))
-    rng = np.random.default_rng(9)
-    for k in range(40):
-        bad = bytearray(good)
-        bad[int(rng.integers(0, len(bad)))] ^= 1 << int(rng.integers(0, 8))
-        cases.append((f"flipped_{k}", bytes(bad), 1 << 20, None))
-    for k in range(20):
-        cases.append((f"random_{k}", rng.integers(0, 256, size=int(rng.integers(1, 400)), dtype=np.uint8).tobytes(), 1 << 16, None))
-    return cases
-
-
-CORRUPT = _corrupt_corpus()
-
-
 @pytest.mark.parametrize("name,stream,cap,reason", CORRUPT, ids=[c[0] for c in CORRUPT])
 def test_corrupt_corpus(name, stream, cap, reason):
     rc, out, used, got = inflate(stream, cap)
@@ -210,17 +84,6 @@ def test_corrupt_corpus(name, stream, cap, reason):
         assert rc == EDATA and got > 0
 
 
-# (return code, reason, bytes produced, input bytes used) of every fixed-reason case, recorded once on the CPU from the library as it
-# was while the member path, the span path and the candidate filter each had a block loop of their own
-PINNED = {
-    "truncated_0": (-5, 1, 0, 0), "truncated_1": (-5, 1, 0, 1), "truncated_2": (-5, 1, 0, 2), "truncated_5": (-5, 1, 0, 5),
-    "truncated_3247": (-5, 1, 9558, 3247), "truncated_6494": (-5, 1, 20000, 6494),
-    "block_type_3": (-5, 2, 0, 1), "stored_len_nlen": (-5, 3, 0, 5), "stored_truncated": (-5, 1, 0, 8), "stored_over_cap": (-5, 7, 0, 5),
-    "distance_too_far": (-5, 6, 1, 3), "distance_before_any_output": (-5, 6, 0, 2), "literal_286": (-5, 5, 1, 3),
-    "distance_code_30": (-5, 5, 1, 3), "clen_oversubscribed": (-5, 4, 0, 10), "clen_incomplete": (-5, 4, 0, 4),
-    "repeat_without_previous": (-5, 4, 0, 4), "too_many_lengths": (-5, 4, 0, 3), "no_end_of_block": (-5, 4, 0, 42),
-    "output_over_cap": (-5, 7, 19997, 6494), "empty_input": (-5, 1, 0, 0),
-}
 # one case of each reason a host entry can give, and the words dgrp_last_error() has for it
 TEXTS = {"truncated_5": "input ends inside the stream", "block_type_3": "invalid block type", "stored_len_nlen": "stored block LEN/NLEN mismatch",
          "clen_incomplete": "invalid code lengths", "literal_286": "invalid symbol", "distance_too_far": "distance too far back",
