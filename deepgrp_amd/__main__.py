@@ -33,6 +33,8 @@ Differences, all additive:
   * the annotation of `evaluate`, and the bedfile of `train` on sequence files, may be RepeatMasker's own output (`genome.fa.out`,
     `.out.gz`, UCSC `rmsk.txt.gz`; `--annotation_format auto|table|repeatmasker`): it is parsed on the GPU into what the table of
     `parse_rm` holds (deepgrp_amd/annotation.py); `optimize` and `train` on .npz files read the table only;
+  * `evaluate --strata PREFIX` also writes recall by divergence bin and element length, PREFIX.strata.tsv and
+    PREFIX.strata.bases.tsv, from the listing's divergence column and counts made on the GPU (deepgrp_amd/strata.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -412,6 +414,18 @@ class CommandLineParser:
                                    "elements still found by the --min_overlap rule once the rows below that score are gone, recall, "
                                    "the precision of PREFIX.rows.tsv and F1); the JSON's `curves` gains `elements` (recall at 0, the "
                                    "best element-level F1 and the lowest score that reaches it)")
+        evaluate.add_argument("--strata", type=str, default=None, metavar="PREFIX",
+                              help="also write recall by divergence and element length: PREFIX.strata.tsv (per class and stratum: "
+                                   "elements, found, recall, and the bases and hits of the elements) and PREFIX.strata.bases.tsv (per "
+                                   "class, stratum and threshold: the bases whose winning element lies in the stratum); the divergence "
+                                   "comes from a RepeatMasker listing (a table has none: everything is NA); --json gains the key `strata`")
+        evaluate.add_argument("--strata_div", type=str, default=None,
+                              help="divergence edges of --strata in percent, ascending, 1..15 of them, one decimal allowed "
+                                   "(default with --strata: 5,10,15,20,25,30)")
+        evaluate.add_argument("--strata_len", type=str, default=None,
+                              help="length edges of --strata in bases, ascending, 1..15 of them (default with --strata: 100,300,1000,3000)")
+        evaluate.add_argument("--strata_bins", type=int, default=None,
+                              help="probability bins of PREFIX.strata.bases.tsv, 2..1000 (default with --strata: 100)")
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
@@ -1097,6 +1111,8 @@ class CommandLineParser:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
         from . import curves as dgcurves
         curve_plan = dgcurves.plan(args)
+        from . import strata as dgstrata
+        strata_plan = dgstrata.plan(args)
         import json
 
         from . import model as dgmodel
@@ -1124,12 +1140,16 @@ class CommandLineParser:
                                  batch_size=args.batch_size, use_mss=not args.no_use_mss, fast=bool(args.fast),
                                  min_overlap=args.min_overlap))
         curves = dgcurves.Curves(classes, curve_plan.bins, curve_plan.elements_path is not None) if curve_plan is not None else None
+        strata = dgstrata.Strata(classes, strata_plan.div_edges, strata_plan.len_edges, strata_plan.bins) if strata_plan is not None else None
         try:
-            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves)
+            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves,
+                           strata)
         except NoMatchError as e:
             sys.exit(str(e))
         if curves is not None:
             curves.write(curve_plan, _LOG)
+        if strata is not None:
+            strata.write(strata_plan, _LOG)
         text = tsv_report(rep)
         if args.output == "-":
             sys.stdout.write(text)

@@ -167,6 +167,10 @@ _SIGNATURES = {
     "dgrp_train_resolve_starts": (cint, [vp, i64, vp, vp, cint, vp, vp, i64, vp, vp]),
     "dgrp_rm_parse_workspace_bytes": (i64, [i64]),
     "dgrp_rm_parse": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_rm_parse_fields": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_paint_strata_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_prob_hist_strata_workspace_bytes": (i64, [i64]),
+    "dgrp_prob_hist_strata_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, vp, vp, vp, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import io
 import os
+import re
 import zlib
 from typing import Dict, Iterable, List, Optional, Sequence
 
@@ -121,16 +122,44 @@ def line_text(path, lineno: int) -> str:
     return ""
 
 
-class Listing:
-    """The numbered rows of a listing in file order: `begin`, `end`, `line` (int64), `number` (int32), and the runs of one contig
-    name -- run r is rows run_first[r] .. run_first[r + 1] and is named run_names[r].  `route`: "device" or "host"."""
+_DIV_OUT = re.compile(r"^\s*\d+\s+(\S+)")                          # token 1 of a line _OUT_LINE matches
+_DIV_RMSK = re.compile(r"^\d+\t\d+\t(\d+)")                         # field 2 of a line _RMSK_LINE matches
+_DIV_PERCENT = re.compile(r"([0-9]{1,6})(?:\.([0-9]*))?")
+_DIV_MILLI = re.compile(r"[0-9]{1,7}")
 
-    def __init__(self, path, begin, end, number, line, run_first, run_names: List[str], lines: int, route: str):
+
+def millidiv_of_line(line: str) -> int:
+    """The divergence of a listing's line from its consensus in tenths of a percent, -1 where it states none: the rule of
+    dgrp_rm_parse_fields on a decoded line, `.out` or `rmsk` decided exactly as parse_rm.parse_line decides.  `.out`: token 1
+    (`perc div.`) as a whole is D, `D.` or `D.d...` with D 1..6 digits -> 10 * int(D) + the first digit behind the point (0 if
+    none; further digits dropped, not rounded).  `rmsk`: field 2 (`milliDiv`) is that integer when it has at most 7 digits.
+    Anything else -- and a line that matches neither pattern -- is -1."""
+    if parse_rm._OUT_LINE.match(line):
+        m = _DIV_PERCENT.fullmatch(_DIV_OUT.match(line).group(1))
+        if m is None:
+            return -1
+        frac = m.group(2)
+        return 10 * int(m.group(1)) + (int(frac[0]) if frac else 0)
+    if parse_rm._RMSK_LINE.match(line):
+        tok = _DIV_RMSK.match(line).group(1)
+        return int(tok) if _DIV_MILLI.fullmatch(tok) else -1
+    return -1
+
+
+class Listing:
+    """The numbered rows of a listing in file order: `begin`, `end`, `line` (int64), `number`, `millidiv` (int32; the divergence in
+    tenths of a percent, -1 where not stated), and the runs of one contig name -- run r is rows run_first[r] .. run_first[r + 1]
+    and is named run_names[r].  `route`: "device" or "host"."""
+
+    def __init__(self, path, begin, end, number, line, run_first, run_names: List[str], lines: int, route: str, millidiv=None):
         self.path, self.route, self.lines = path, route, int(lines)
         self.begin, self.end, self.line = (np.ascontiguousarray(a, np.int64) for a in (begin, end, line))
         self.number = np.ascontiguousarray(number, np.int32)
         self.run_first = np.ascontiguousarray(run_first, np.int64)
         self.run_names = list(run_names)
+        self.millidiv = np.full(self.begin.size, -1, np.int32) if millidiv is None else np.ascontiguousarray(millidiv, np.int32)
+        if self.millidiv.shape != self.begin.shape:
+            raise ValueError(f"{self.millidiv.size} divergences for {self.begin.size} rows")
 
     def __len__(self) -> int:
         return int(self.begin.size)
@@ -144,12 +173,17 @@ class Listing:
     def grouped(self, keep: Optional[np.ndarray] = None):
         """({contig: SEGMENT_DTYPE rows with label = number}, {contig: their lines}) of the rows `keep` marks (None: all), file order
         within a contig, contigs sorted by name as read_annotation's dict is; contigs without a kept row are left out."""
+        return self.grouped_fields(keep)[:2]
+
+    def grouped_fields(self, keep: Optional[np.ndarray] = None):
+        """`grouped` plus {contig: the millidiv of its rows}, the same rows in the same order."""
         names, cid = self.contigs()
         idx = np.arange(len(self)) if keep is None else np.flatnonzero(keep)
         rows_of: Dict[str, np.ndarray] = {}
         lines_of: Dict[str, np.ndarray] = {}
+        div_of: Dict[str, np.ndarray] = {}
         if idx.size == 0:
-            return rows_of, lines_of
+            return rows_of, lines_of, div_of
         order = idx[np.argsort(cid[idx], kind="stable")]
         counts = np.bincount(cid[idx], minlength=len(names))
         parts = np.split(order, np.cumsum(counts)[:-1])
@@ -161,7 +195,8 @@ class Listing:
             rows["start"], rows["end"], rows["label"] = self.begin[sel], self.end[sel], self.number[sel]
             rows_of[names[k]] = rows
             lines_of[names[k]] = self.line[sel]
-        return rows_of, lines_of
+            div_of[names[k]] = self.millidiv[sel]
+        return rows_of, lines_of, div_of
 
     def _bad(self, k: int, why: str):
         from .evaluation import _bad
@@ -199,8 +234,10 @@ class Listing:
 
 
 class Rows(dict):
-    """{contig: SEGMENT_DTYPE rows}; `lines[contig]`: the line of the listing each row came from (None for a table)."""
+    """{contig: SEGMENT_DTYPE rows}; `lines[contig]`: the line of the listing each row came from (None for a table);
+    `millidiv[contig]`: the divergence of each row in tenths of a percent, -1 where not stated (None for a table: all -1)."""
     lines: Optional[Dict[str, np.ndarray]] = None
+    millidiv: Optional[Dict[str, np.ndarray]] = None
     route: str = "table"
 
 
@@ -220,15 +257,21 @@ def _listing_host(path) -> Listing:
             at[0] = k
             yield line
     names, vals = [], []
-    for r in parse_rm.read_repeatmasker(exact, one_off, numbered(io.StringIO(_read_text(path)))):
+    now = [""]
+
+    def noted(lines):
+        for line in lines:
+            now[0] = line
+            yield line
+    for r in parse_rm.read_repeatmasker(exact, one_off, noted(numbered(io.StringIO(_read_text(path))))):
         for what, v in (("begin", r.start), ("end", r.end)):
             if not -(1 << 63) <= v < (1 << 63):
                 raise AnnotationError(f"{path}:{at[0]}: {what} '{v}' is not an integer: {line_text(path, at[0]).rstrip()!r}")
         names.append(r.ctg)
-        vals.append((r.start, r.end, r.typ, at[0]))
-    a = np.asarray(vals, np.int64).reshape(-1, 4)
+        vals.append((r.start, r.end, r.typ, at[0], millidiv_of_line(now[0])))
+    a = np.asarray(vals, np.int64).reshape(-1, 5)
     run_first, run_names = _runs_of(names)
-    return Listing(path, a[:, 0], a[:, 1], a[:, 2], a[:, 3], run_first, run_names, at[0], "host")
+    return Listing(path, a[:, 0], a[:, 1], a[:, 2], a[:, 3], run_first, run_names, at[0], "host", a[:, 4])
 
 
 _DEVICE_TABLES: Dict[object, tuple] = {}
@@ -243,10 +286,11 @@ def _device_tables(dev):
     return _DEVICE_TABLES[dev]
 
 
-def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None):
+def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None, fields: bool = False):
     """dgrp_rm_parse on the uint8 device tensor `d_text` (its first `n` bytes): -> (counts = [lines, kept rows, runs, not-plain
     flag], the device arrays begin, end, number, name_pos, name_len, line, run_first of `cap` rows -- default n // 22 + 1 --, the
-    return code).  Nothing is raised for DGRP_ENOMEM (-3: more rows than `cap`; counts[1] tells the need)."""
+    return code).  Nothing is raised for DGRP_ENOMEM (-3: more rows than `cap`; counts[1] tells the need).  fields:
+    dgrp_rm_parse_fields, and `millidiv` among the arrays."""
     import ctypes as C
 
     import torch
@@ -264,24 +308,29 @@ def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None):
     wb = int(L.dgrp_rm_parse_workspace_bytes(n))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
     counts = (C.c_int64 * 4)()
-    rc = L.dgrp_rm_parse(d_text.data_ptr() if n else None, n, d_names.data_ptr(), d_off.data_ptr(), nnames, d_pent.data_ptr(), unit,
-                         out["begin"].data_ptr(), out["end"].data_ptr(), out["number"].data_ptr(), out["name_pos"].data_ptr(),
-                         out["name_len"].data_ptr(), out["line"].data_ptr(), out["run_first"].data_ptr(), cap, counts, work.data_ptr(),
-                         wb, stream_ptr())
+    head = (d_text.data_ptr() if n else None, n, d_names.data_ptr(), d_off.data_ptr(), nnames, d_pent.data_ptr(), unit,
+            out["begin"].data_ptr(), out["end"].data_ptr(), out["number"].data_ptr(), out["name_pos"].data_ptr(),
+            out["name_len"].data_ptr(), out["line"].data_ptr(), out["run_first"].data_ptr())
+    tail = (cap, counts, work.data_ptr(), wb, stream_ptr())
+    if fields:
+        out["millidiv"] = i32()
+        rc = L.dgrp_rm_parse_fields(*head, out["millidiv"].data_ptr(), *tail)
+    else:
+        rc = L.dgrp_rm_parse(*head, *tail)
     if rc not in (0, -3):
-        check(rc, "dgrp_rm_parse")
+        check(rc, "dgrp_rm_parse_fields" if fields else "dgrp_rm_parse")
     return [int(c) for c in counts], out, rc
 
 
 def listing_of_device_text(path, d_text, n: int) -> Optional[Listing]:
     """The Listing of the text in device memory, or None when the device raised the not-plain flag."""
     import torch
-    counts, out, rc = parse_device(d_text, n)
+    counts, out, rc = parse_device(d_text, n, fields=True)
     if counts[3]:
         return None
     if rc != 0:
         from ._lib import check
-        check(rc, "dgrp_rm_parse")
+        check(rc, "dgrp_rm_parse_fields")
     lines, kept, runs = counts[:3]
     host = lambda k: out[k][:kept].cpu().numpy()
     first = out["run_first"][:runs]
@@ -296,7 +345,7 @@ def listing_of_device_text(path, d_text, n: int) -> Optional[Listing]:
         cut = np.concatenate([offs.cpu().numpy(), [total]])
         names = [blob[cut[r]:cut[r + 1]].decode("ascii") for r in range(runs)]
     run_first = np.concatenate([first.cpu().numpy(), [kept]]).astype(np.int64)
-    return Listing(path, host("begin"), host("end"), host("number"), host("line"), run_first, names, lines, "device")
+    return Listing(path, host("begin"), host("end"), host("number"), host("line"), run_first, names, lines, "device", host("millidiv"))
 
 
 def read_listing(path, device: bool = True) -> Listing:
@@ -334,16 +383,16 @@ def read_rows(path, fmt: str = "auto", device: bool = True) -> Rows:
         from .evaluation import read_annotation
         return Rows(read_annotation(path, None))
     listing = read_listing(path, device)
-    rows_of, lines_of = listing.grouped(listing.table_mask())
+    rows_of, lines_of, div_of = listing.grouped_fields(listing.table_mask())
     out = Rows(rows_of)
-    out.lines, out.route = lines_of, listing.route
+    out.lines, out.millidiv, out.route = lines_of, div_of, listing.route
     return out
 
 
-def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool = True) -> Dict[str, np.ndarray]:
+def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool = True) -> Rows:
     """evaluation.read_annotation(table of the listing `path`, repeats) without the table: the same rows, and the same
     AnnotationError for a negative begin or an end below its begin -- checked on every row before `repeats` filters, the first in
-    file order named as "<listing>:<its line>: <why>: <the line>"."""
+    file order named as "<listing>:<its line>: <why>: <the line>".  `.lines` and `.millidiv` travel beside the rows."""
     listing = read_listing(path, device)
     read = listing.table_mask()
     bad = np.flatnonzero(read & ((listing.begin < 0) | (listing.end < listing.begin)))
@@ -352,7 +401,10 @@ def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool 
         raise listing._bad(k, "negative begin" if listing.begin[k] < 0 else "end below begin")
     if repeats is not None:
         read &= np.isin(listing.number, np.array(sorted(set(int(r) for r in repeats)), np.int64))
-    return listing.grouped(read)[0]
+    rows_of, lines_of, div_of = listing.grouped_fields(read)
+    out = Rows(rows_of)
+    out.lines, out.millidiv, out.route = lines_of, div_of, listing.route
+    return out
 
 
 def refuse_npz(command: str, path) -> str:

@@ -30,6 +30,8 @@ struct rm_tables {
 struct rm_row {
     int64_t begin, end, name_pos;
     int32_t number, name_len;
+    int64_t div_b, div_e;                // the divergence token: `.out` token 1 (percent), `rmsk` field 2 (tenths of a percent)
+    bool div_rmsk;
 };
 
 // a token, or two of them read as `A/B`
@@ -92,7 +94,8 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
 {
     const uint8_t simple[13] = { 'S', 'i', 'm', 'p', 'l', 'e', '_', 'r', 'e', 'p', 'e', 'a', 't' };
     const uint8_t satellite[9] = { 'S', 'a', 't', 'e', 'l', 'l', 'i', 't', 'e' };
-    int64_t cb = 0, ce = 0, rb = 0, re = 0, v5 = 0, v6 = 0;
+    int64_t cb = 0, ce = 0, rb = 0, re = 0, v5 = 0, v6 = 0, db = 0, de = 0;
+    bool rmsk = false;
     rm_str fam = { 0, 0, 0, 0, false };
     bool ok = true;
     // ---- `.out`: tokens between runs of blanks
@@ -117,6 +120,7 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
                 }
             }
             if (k == 0) ok = dig;
+            else if (k == 1) { db = b; de = p; }
             else if (k == 4) { cb = b; ce = p; }
             else if (k == 5 || k == 6) {
                 ok = dig;
@@ -150,7 +154,10 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
                 }
             }
             if (p == b) { ok = false; break; }
-            if (k <= 4) ok = dig;
+            if (k <= 4) {
+                ok = dig;
+                if (k == 2) { db = b; de = p; }
+            }
             else if (k == 6 || k == 7) {
                 ok = dig;
                 if (dig && nd > RM_MAX_DIGITS) big = true;
@@ -174,6 +181,7 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
             bool same = fam.ae - fam.ab == fam.be - fam.bb;
             for (int64_t j = 0; same && j < fam.ae - fam.ab; ++j) same = t[fam.ab + j] == t[fam.bb + j];
             fam.joined = !same;
+            rmsk = true;
         }
     }
     if (!ok) return false;
@@ -189,7 +197,36 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
     row.name_pos = cb;
     row.name_len = (int32_t)(ce - cb);
     row.number = number;
+    row.div_b = db;
+    row.div_e = de;
+    row.div_rmsk = rmsk;
     return true;
+}
+
+// The divergence of a kept row in tenths of a percent, -1 where the token does not state one (include/deepgrp_hip.h).  `rmsk`: the
+// field is digits already (the pattern asked for them) and already in tenths.  `.out`: D, `D.` or `D.d...` with 1..6 digits D and
+// digits only behind the point -> 10 D + the first of them; further digits are dropped.
+__host__ __device__ int32_t rm_millidiv(const uint8_t *__restrict__ t, const rm_row &row)
+{
+    int64_t p = row.div_b;
+    const int64_t e = row.div_e;
+    int32_t val = 0;
+    int nd = 0;
+    for (; p < e && t[p] >= '0' && t[p] <= '9'; ++p) {
+        if (nd < 7) val = val * 10 + (t[p] - '0');
+        ++nd;
+    }
+    if (row.div_rmsk) return p == e && nd >= 1 && nd <= 7 ? val : -1;
+    if (nd < 1 || nd > 6) return -1;
+    if (p == e) return 10 * val;
+    if (t[p] != '.') return -1;
+    ++p;
+    int32_t first = 0;
+    for (int64_t q = p; q < e; ++q) {
+        if (t[q] < '0' || t[q] > '9') return -1;
+        if (q == p) first = t[q] - '0';
+    }
+    return 10 * val + first;
 }
 
 // The lane's chunk: mask of its line feeds (bit k of lo / hi: byte c0 + k / c0 + 64 + k) and whether a byte of it makes the file not
@@ -235,6 +272,7 @@ struct rm_out {
     int64_t *name_pos;
     int32_t *name_len;
     int64_t *line;
+    int32_t *millidiv;                   // NULL: not asked for (dgrp_rm_parse)
     int64_t cap;
 };
 
@@ -268,6 +306,7 @@ __host__ __device__ uint32_t rm_chunk_lines(const uint8_t *__restrict__ t, int64
                     out.name_pos[i] = row.name_pos;
                     out.name_len[i] = row.name_len;
                     out.line[i] = (int64_t)(line0 + seen) + 1;
+                    if (out.millidiv) out.millidiv[i] = rm_millidiv(t, row);
                 }
             }
             ++kept;
@@ -285,7 +324,8 @@ __global__ void __launch_bounds__(256) rm_lines_kernel(const uint8_t *__restrict
                                                        uint64_t *__restrict__ keep, unsigned long long *__restrict__ g,
                                                        int64_t *__restrict__ o_begin, int64_t *__restrict__ o_end,
                                                        int32_t *__restrict__ o_number, int64_t *__restrict__ o_name_pos,
-                                                       int32_t *__restrict__ o_name_len, int64_t *__restrict__ o_line, int64_t cap)
+                                                       int32_t *__restrict__ o_name_len, int64_t *__restrict__ o_line,
+                                                       int32_t *__restrict__ o_millidiv, int64_t cap)
 {
     __shared__ uint64_t lds[4];
     const int64_t chunk = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -302,7 +342,7 @@ __global__ void __launch_bounds__(256) rm_lines_kernel(const uint8_t *__restrict
         place = keep[blockIdx.x] + (ex & 0xffffffffull);
         line0 = nl[blockIdx.x] + (ex >> 32);
     }
-    const rm_out out = { o_begin, o_end, o_number, o_name_pos, o_name_len, o_line, cap };
+    const rm_out out = { o_begin, o_end, o_number, o_name_pos, o_name_len, o_line, o_millidiv, cap };
     const uint32_t kept = c0 < n ? rm_chunk_lines<WRITE>(t, c0, n, T, lo, hi, bad, place, line0, out) : 0u;
     if (!WRITE) {
         if (c0 < n) lane_keep[chunk] = (uint8_t)kept;                        // (at most RM_CHUNK / RM_MIN_LINE + 1)
@@ -352,13 +392,14 @@ DGRP_EXPORT int64_t dgrp_rm_parse_workspace_bytes(int64_t n)
            dgrp_align_up(tiles * 256, 256) + dgrp_align_up((rows + 1) * 8, 256);
 }
 
-DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
-                              const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
-                              int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap,
-                              int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
+namespace {
+
+// both entries: d_millidiv NULL (dgrp_rm_parse) writes no divergence
+int rm_parse_run(const char *what, bool fields, const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off,
+                 int nnames, const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                 int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int32_t *d_millidiv, int64_t *d_run_first, int64_t cap,
+                 int64_t *h_counts, void *d_work, int64_t work_bytes, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    const char *what = "dgrp_rm_parse";
     DGRP_REQUIRE(h_counts, "%s: NULL counts", what);
     h_counts[0] = h_counts[1] = h_counts[2] = h_counts[3] = 0;
     DGRP_REQUIRE(n >= 0, "%s: negative size", what);
@@ -368,6 +409,7 @@ DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d
                  what, nnames, unit_number);
     DGRP_REQUIRE(cap >= 0, "%s: negative capacity", what);
     DGRP_REQUIRE(cap == 0 || (d_begin && d_end && d_number && d_name_pos && d_name_len && d_line && d_run_first), "%s: NULL output", what);
+    DGRP_REQUIRE(cap == 0 || !fields || d_millidiv, "%s: NULL output", what);
     if (n == 0) return DGRP_OK;
     const int64_t tiles = rm_tiles_of(n), bound = rm_rows_bound(n);
     DGRP_REQUIRE(tiles < (1ll << 31), "%s: too many bytes", what);
@@ -393,7 +435,7 @@ DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d
     DGRP_HIP(hipMemsetAsync(g, 0, RM_HEAD, stream));
     hipLaunchKernelGGL(rm_lines_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, d_text, n, T, d_lane, d_nl, d_keep, g,
                        (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
-                       (int64_t *)nullptr, (int64_t)0);
+                       (int64_t *)nullptr, (int32_t *)nullptr, (int64_t)0);
     DGRP_LAUNCH_CHECK();
     int rc = device_exclusive_scan(d_nl, d_nl, tiles, d_tiles, d_nl + tiles, stream);
     if (rc != DGRP_OK) return rc;
@@ -418,7 +460,7 @@ DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d
     }
     const int64_t rows = (int64_t)kept;                                      // (<= bound: every numbered line has RM_MIN_LINE bytes)
     hipLaunchKernelGGL(rm_lines_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, d_text, n, T, d_lane, d_nl, d_keep, g, d_begin,
-                       d_end, d_number, d_name_pos, d_name_len, d_line, cap);
+                       d_end, d_number, d_name_pos, d_name_len, d_line, fields ? d_millidiv : (int32_t *)nullptr, cap);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(rm_run_flag_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, d_text, d_name_pos, d_name_len, rows,
                        d_run);
@@ -434,4 +476,25 @@ DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d
     DGRP_HIP(e3);
     h_counts[2] = (int64_t)runs;
     return DGRP_OK;
+}
+
+}   // namespace
+
+DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                              const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                              int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap,
+                              int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
+{
+    return rm_parse_run("dgrp_rm_parse", false, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end, d_number,
+                        d_name_pos, d_name_len, d_line, nullptr, d_run_first, cap, h_counts, d_work, work_bytes, (hipStream_t)stream_);
+}
+
+DGRP_EXPORT int dgrp_rm_parse_fields(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                                     const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                                     int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
+                                     int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
+{
+    return rm_parse_run("dgrp_rm_parse_fields", true, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end,
+                        d_number, d_name_pos, d_name_len, d_line, d_millidiv, d_run_first, cap, h_counts, d_work, work_bytes,
+                        (hipStream_t)stream_);
 }

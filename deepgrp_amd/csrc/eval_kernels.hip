@@ -105,10 +105,7 @@ DGRP_EXPORT int dgrp_filter_segments(const int8_t *d_labels, int8_t *d_out, int6
 // the clipped lengths gives every row its place on one line of positions, and workgroup b takes positions
 // [b * EVAL_SLICE, (b + 1) * EVAL_SLICE) of that line (rows run from 10 bp to megabases).
 // ------------------------------------------------------------------------------------------------------------------------------
-#include "eval_paint.h"
-#include "bed_rows.h"
-#include "scan.h"
-#include <vector>
+#include "eval_rows.h"
 
 namespace {
 
@@ -223,21 +220,13 @@ __global__ void __launch_bounds__(256) eval_hits_kernel(const int8_t *__restrict
     }
 }
 
-struct eval_plan {
-    std::vector<int64_t> tab;          // off[nrec], len[nrec], origin[nrec], row_off[nrec + 1]
-    int64_t nrows = 0;
-    int64_t *d_off = nullptr, *d_len, *d_origin, *d_row_off, *d_dst;
-    uint64_t *d_cl = nullptr, *d_tiles = nullptr;
-    char *d_extra = nullptr;           // `extra_bytes` behind the tables, for the caller
-    unsigned long long tot[128];       // clipped length per label
-};
+}   // namespace
 
-// argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written.
+// (eval_rows.h) argument checks, tables to the device, the row check (one synchronisation): DGRP_EINVAL on a bad row before anything is written.
 // d_scores: the rows are scored rows, checked as eval_check_kernel says; extra_bytes: more workspace, 256-byte aligned, at pl.d_extra
-static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
-                        const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes,
-                        hipStream_t stream, eval_plan &pl, int max_label = 127, const dgrp_row_score *d_scores = nullptr,
-                        int64_t extra_bytes = 0)
+int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                 const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes, hipStream_t stream,
+                 eval_plan &pl, int max_label, const dgrp_row_score *d_scores, int64_t extra_bytes)
 {
     DGRP_REQUIRE(nrec >= 0 && h_row_off && (nrec == 0 || (h_off && h_len && h_origin)), "%s: bad arguments", what);
     DGRP_REQUIRE(h_row_off[0] >= 0, "%s: negative row offset", what);
@@ -302,15 +291,13 @@ static int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, co
 }
 
 // the pass's clipped lengths and first positions, scanned: d_cl[0..nrows] = exclusive scan, d_cl[nrows] = the pass's total
-static int eval_spans(const eval_plan &pl, const dgrp_segment *d_rows, int64_t nrec, int label, hipStream_t stream)
+int eval_spans(const eval_plan &pl, const dgrp_segment *d_rows, int64_t nrec, int label, hipStream_t stream)
 {
     hipLaunchKernelGGL(eval_span_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
                        pl.d_off, pl.d_len, pl.d_origin, label, pl.d_cl, pl.d_dst);
     DGRP_LAUNCH_CHECK();
     return device_exclusive_scan(pl.d_cl, pl.d_cl, pl.nrows, pl.d_tiles, pl.d_cl + pl.nrows, stream);
 }
-
-}   // namespace
 
 DGRP_EXPORT int64_t dgrp_eval_workspace_bytes(int64_t nrec, int64_t nrows)
 {

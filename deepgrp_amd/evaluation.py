@@ -15,7 +15,11 @@ With curves (`evaluate --curves`, deepgrp_amd/curves.py) the runner keeps the me
 for `Accumulator.probe`: it paints the item's truth on the worker's stream and counts every probability into per-class
 histograms split by truth (dgrp_prob_hist_batch); the rows' BED scores come with the rows (dgrp_row_scores_batch).  With element
 curves (`--curve_elements`) `Accumulator.add` also paints the predicted rows as (label, score) keys and takes every annotation row's
-detection score against them (dgrp_paint_row_keys_batch, dgrp_row_detect_batch)."""
+detection score against them (dgrp_paint_row_keys_batch, dgrp_row_detect_batch).
+
+With strata (`evaluate --strata`, deepgrp_amd/strata.py) the probe also paints the truth as (label, stratum) keys and counts the true
+class's probability by them (dgrp_paint_strata_batch, dgrp_prob_hist_strata_batch), and `Accumulator.add` groups the element counts
+it already has by label and stratum."""
 from __future__ import annotations
 
 import logging
@@ -105,11 +109,12 @@ def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
 class Accumulator:
     """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
 
-    def __init__(self, classes: int, min_overlap: float, curves=None):
+    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None):
         if not 0.0 < min_overlap <= 1.0:
             raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
         self.C, self.theta = int(classes), float(min_overlap)
         self.curves = curves                           # a curves.Curves: probability histograms and rows by score are summed into it
+        self.strata = strata                           # a strata.Strata: element counts and histograms by (label, stratum)
         self.cnf = np.zeros((self.C, self.C), np.int64)
         self.elements = np.zeros(self.C, np.int64)
         self.found = np.zeros(self.C, np.int64)
@@ -158,10 +163,70 @@ class Accumulator:
                                           stream_ptr()), "dgrp_paint_rows_batch")
         return d_labels
 
+    def _row_strata(self, annotation, name: str, rows: np.ndarray) -> np.ndarray:
+        """The stratum of every annotation row of contig `name`: its millidiv travels beside the rows (annotation.Rows.millidiv;
+        a table has none: -1 everywhere)."""
+        div_of = getattr(annotation, "millidiv", None)
+        md = None if div_of is None or name not in div_of else div_of[name]
+        return self.strata.strata_of(rows, md)
+
+    def _probe_strata(self, annotation):
+        """The strata's share of the probe: the item's truth painted as keys (dgrp_paint_strata_batch), the true class's
+        probability counted by them (dgrp_prob_hist_strata_batch) -> (hist [C, S, bins], flag) as host arrays."""
+        st, empty = self.strata, np.zeros(0, SEGMENT_DTYPE)
+
+        def run(d_probs, row0, lengths, startposes, keys):
+            import torch
+
+            from ._lib import check, lib
+            from .pipeline import require_gpu, stream_ptr
+            L = lib()
+            ln, org, off = self._tables(startposes, lengths)
+            nrec = len(ln)
+            hist = np.zeros((self.C, st.S, st.bins), np.int64)
+            if nrec == 0 or int(off[-1]) == 0 or d_probs is None:
+                return hist, 0
+            if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous() or d_probs.shape[1] != self.C:
+                raise ValueError(f"the strata take a contiguous float32 [rows, {self.C}] array")
+            dev = require_gpu()
+            tr = [np.ascontiguousarray(annotation.get(k[1], empty), SEGMENT_DTYPE) for k in keys]
+            t_off, _flat, d_trows = self._upload(tr, dev)
+            sof = [self._row_strata(annotation, k[1], t) for k, t in zip(keys, tr)]
+            d_st = torch.from_numpy(np.concatenate(sof)).to(dev) if int(t_off[-1]) else None
+            work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(nrec, int(t_off[-1]))), int(L.dgrp_prob_hist_strata_workspace_bytes(nrec)), 1),
+                               dtype=torch.uint8, device=dev)
+            d_keys = torch.empty(int(off[-1]), dtype=torch.int32, device=dev)      # (32-bit keys; the sign of the type is not read)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            check(L.dgrp_paint_strata_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_trows),
+                                            t_off.ctypes.data, ptr(d_st), work.data_ptr(), work.numel(), stream_ptr()),
+                  "dgrp_paint_strata_batch")
+            r0 = np.ascontiguousarray(row0, np.int64)
+            d_hist = torch.empty((self.C, st.S, st.bins), dtype=torch.int64, device=dev)
+            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+            check(L.dgrp_prob_hist_strata_batch(d_probs.data_ptr(), self.C, nrec, r0.ctypes.data, ln.ctypes.data, d_keys.data_ptr(),
+                                                off.ctypes.data, st.S, st.bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(),
+                                                work.numel(), stream_ptr()), "dgrp_prob_hist_strata_batch")
+            return d_hist.cpu().numpy(), int(d_bad.item())
+        return run
+
     def probe(self, annotation: Dict[str, np.ndarray]):
         """RecordRunner's probe for the curves: called on the worker's stream with the merged probabilities of a work item (record r:
         rows [row0[r], row0[r] + lengths[r]) of d_probs; keys[r][1] its annotation contig), it paints the item's truth, counts the
-        histograms (dgrp_prob_hist_batch) and returns them with the flag as host arrays; `add` sums them."""
+        histograms (dgrp_prob_hist_batch) and returns them with the flag as host arrays; `add` sums them.  With strata what it
+        returns is a dict: "curves" that pair (where there are curves), "strata" the pair of `_probe_strata`."""
+        if self.strata is not None:
+            curve_run = self._probe_curves(annotation) if self.curves is not None else None
+            strata_run = self._probe_strata(annotation)
+
+            def both(*a):
+                out = {"strata": strata_run(*a)}
+                if curve_run is not None:
+                    out["curves"] = curve_run(*a)
+                return out
+            return both
+        return self._probe_curves(annotation)
+
+    def _probe_curves(self, annotation: Dict[str, np.ndarray]):
         bins, empty = self.curves.bins, np.zeros(0, SEGMENT_DTYPE)
 
         def run(d_probs, row0, lengths, startposes, keys):
@@ -193,10 +258,12 @@ class Accumulator:
         return run
 
     def add(self, origins: Sequence[int], lengths: Sequence[int], pred_rows: Sequence[np.ndarray],
-            true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = ()) -> None:
+            true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = (),
+            true_strata: Optional[Sequence[np.ndarray]] = None) -> None:
         """One work item: records r = 0.. with startpos origins[r], kept length lengths[r], the TSV rows `predict` wrote for it
         (original coordinates) and its kept annotation rows.  With curves also the scores of the predicted rows, record after record
-        (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names for its error."""
+        (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names for its error.  With strata also the
+        stratum of every annotation row, record after record as true_rows."""
         import torch
 
         from ._lib import check, lib
@@ -207,6 +274,14 @@ class Accumulator:
             return
         ln, org, off = self._tables(origins, lengths)
         n = int(off[-1])
+        if self.strata is not None and probed is not None:
+            shist, sflag = probed["strata"]
+            if sflag:
+                raise ValueError("a probability outside [0, 1] or a key outside {} classes and {} strata reached the strata histogram "
+                                 "(record{} {})".format(self.C, self.strata.S, "s" if len(names) > 1 else "",
+                                                        ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else "")))
+            self.strata.hist += shist
+            probed = probed.get("curves")
         if self.curves is not None and probed is not None:
             hist, flag = probed
             if flag:
@@ -251,7 +326,11 @@ class Accumulator:
             raise ValueError(f"a label outside 0..{self.C - 1} reached the confusion matrix")
         self.cnf += cnf
         if t_flat.size:
-            self._count(t_flat["label"].astype(np.int64), np.concatenate(t_clen), ht, self.elements, self.found)
+            ok, hit = self._count(t_flat["label"].astype(np.int64), np.concatenate(t_clen), ht, self.elements, self.found)
+            if self.strata is not None:
+                if true_strata is None or sum(len(x) for x in true_strata) != len(t_flat):
+                    raise ValueError(f"{len(t_flat)} annotation rows but {0 if true_strata is None else sum(len(x) for x in true_strata)} strata")
+                self.strata.count(t_flat["label"], np.concatenate(true_strata), np.concatenate(t_clen), ht, ok, hit)
         if p_flat.size:
             p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(pr)])
             kept, good = self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
@@ -326,6 +405,8 @@ def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
                segments=acc.segments.tolist(), supported=acc.supported.tolist())
     if acc.curves is not None:
         out["curves"] = acc.curves.summary()
+    if acc.strata is not None:
+        out["strata"] = acc.strata.summary()
     return out
 
 
@@ -366,20 +447,26 @@ def record_name(filename: str, header: str) -> str:
 
 
 def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
-             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None) -> Dict[str, object]:
+             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None,
+             strata=None) -> Dict[str, object]:
     """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
     `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
     content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
     record read has none).  curves (a curves.Curves of the model's classes): the runner takes the merged path with scores and
     `Accumulator.probe`, the counts of the curves are summed into it and the JSON content gains the key `curves`; without it a
-    record is the fused call, as before."""
+    record is the fused call, as before.  strata (a strata.Strata of the model's classes): the same runner and probe, the counts by
+    (label, stratum) are summed into it and the JSON content gains the key `strata`; the divergence of the rows is
+    `annotation.millidiv` (annotation.Rows), -1 everywhere without it."""
     from .runner import RecordRunner
 
     classes = int(model.output_shape[2])
     if curves is not None and curves.C != classes:
         raise ValueError(f"curves of {curves.C} classes for a model of {classes}")
-    acc = Accumulator(classes, min_overlap, curves)
-    runner = RecordRunner(pipe) if curves is None else RecordRunner(pipe, scores=True, probe=acc.probe(annotation))
+    if strata is not None and strata.C != classes:
+        raise ValueError(f"strata of {strata.C} classes for a model of {classes}")
+    acc = Accumulator(classes, min_overlap, curves, strata)
+    probing = curves is not None or strata is not None
+    runner = RecordRunner(pipe, scores=True, probe=acc.probe(annotation)) if probing else RecordRunner(pipe)
     empty = np.zeros(0, SEGMENT_DTYPE)
     seen_names: List[str] = []
     state = {"matched": False, "warned": False}
@@ -410,7 +497,7 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
 
     for out in runner.outputs(keyed()):
         kind, key, rows, scores = out[:4]
-        probed = out[5] if curves is not None else None
+        probed = out[5] if probing else None
         keys = key if kind == "batch" else [key]
         rows = np.asarray(rows)
         if kind == "batch":
@@ -419,8 +506,9 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
             pred = [rows[cut[r]:cut[r + 1]] for r in range(len(keys))]
         else:
             pred = [rows]
-        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, [annotation.get(k[1], empty) for k in keys], scores, probed,
-                [k[1] for k in keys])
+        true = [annotation.get(k[1], empty) for k in keys]
+        true_strata = [acc._row_strata(annotation, k[1], t) for k, t in zip(keys, true)] if strata is not None else None
+        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, true, scores, probed, [k[1] for k in keys], true_strata)
     if acc.rows_used == 0:
         raise NoMatchError("no annotation row names a record of the inputs (records: {}; annotation: {})".format(
             ", ".join(repr(x) for x in seen_names) or "none",

@@ -649,6 +649,37 @@ int dgrp_prob_hist_batch(const float *d_probs, int C, int64_t nrec, const int64_
                          const int8_t *d_truth, const int64_t *h_off, int bins, int64_t *d_hist, int *d_bad,
                          void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- strata (an addition, evaluate --strata): which annotated element a base belongs to, and the true class's probability by that.
+ * dgrp_paint_strata_batch.  Records and rows as for dgrp_paint_rows_batch, the track being uint32 (4-byte aligned): record r is
+ * d_keys[h_off[r] .. h_off[r] + h_len[r]); h_off has nrec + 1 entries here, h_off[nrec] is the size of the track, every record
+ * lies inside it, and EVERY element of d_keys[0 .. h_off[nrec]) is written.  d_row_stratum[i] (device uint8) is the stratum of row
+ * d_rows[i], i in [h_row_off[0], h_row_off[nrec]).  A base that no row covers gets 0xFFFFFFFF; every other base the SMALLEST
+ * label << 8 | stratum among the rows that cover it -- so key >> 8 is the label dgrp_paint_rows_batch paints there, and among the
+ * rows of that label the lowest stratum wins.  A fill, then one pass of 32-bit atomic minima over the clipped spans, balanced by
+ * length: a minimum does not depend on order, the same call gives the same bytes.  The rows are checked as dgrp_paint_rows_batch
+ * checks them (one kernel, one synchronisation of the stream): DGRP_EINVAL before anything is written unless every row has
+ * 0 <= start <= end and 1 <= label <= 63.  Workspace: dgrp_eval_workspace_bytes(nrec, rows), DGRP_ENOMEM below it.
+ * dgrp_prob_hist_strata_batch.  d_probs, h_row0, h_n as dgrp_prob_hist_batch takes them; record r's keys are d_keys[h_off[r] ..
+ * h_off[r] + h_n[r]).  For every base b with a key other than 0xFFFFFFFF, with t = key >> 8, s = key & 255 and p = P[b, t]:
+ *   k = min(bins - 1, (int)(p * (float)bins))   -- the bin rule of dgrp_prob_hist_batch --
+ *   d_hist[t][s][k] += 1                         (d_hist: device int64 [C][S][bins], 8-byte aligned)
+ * t >= C, s >= S, or a p that is NaN or outside [0, 1], sets *d_bad (device int) to 1 and the base is not counted; the call still
+ * returns DGRP_OK.  d_hist and *d_bad are zeroed here on every call.  32-bit counters in LDS, sized so that none can wrap, flushed
+ * with 64-bit atomic adds: two calls give the same bytes.  Stream-ordered throughout: nothing synchronises.  Where C * S * bins
+ * counters exceed 160 KiB of LDS the (class, stratum) cells are cut into groups of 40960 / bins and every group makes a pass: it
+ * reads the 4 bytes of key of every base and the float of the bases whose cell it owns; the bytes do not depend on the cut.
+ * DGRP_EINVAL before any device work unless 1 <= C <= 64, 1 <= S <= 256, 2 <= bins <= 1000, nrec >= 0, every h_row0[r], h_n[r],
+ * h_off[r] in [0, 2^40), d_hist and d_bad non-NULL, d_hist 8-byte aligned and -- where some record has a base -- d_probs, d_keys
+ * and d_work non-NULL; DGRP_ENOMEM for work_bytes < dgrp_prob_hist_strata_workspace_bytes(nrec).  nrec == 0 or no base: d_hist
+ * and *d_bad are zeroed, nothing else runs. */
+int dgrp_paint_strata_batch(uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                            const dgrp_segment *d_rows, const int64_t *h_row_off, const uint8_t *d_row_stratum, void *d_work,
+                            int64_t work_bytes, void *stream);
+int64_t dgrp_prob_hist_strata_workspace_bytes(int64_t nrec);
+int dgrp_prob_hist_strata_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                const uint32_t *d_keys, const int64_t *h_off, int S, int bins, int64_t *d_hist, int *d_bad,
+                                void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- detection scores (an addition, evaluate --curves --curve_elements): for every annotation row the largest
  * `predict --bed_min_score` m at which the predicted rows that survive m still cover enough of it.  Records are laid out as for
  * dgrp_paint_rows_batch, the track being uint16 (2-byte aligned): record r is d_keys[h_off[r] .. h_off[r] + h_len[r]), its first
@@ -1054,6 +1085,17 @@ int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d_names, cons
                   const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number, int64_t *d_name_pos,
                   int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap, int64_t *h_counts, void *d_work,
                   int64_t work_bytes, void *stream);
+/* dgrp_rm_parse_fields: the same call -- the same counts, the same arrays, the same refusals -- plus d_millidiv[i] (device int32,
+ * `cap` elements, non-NULL where cap > 0): the divergence of kept row i from its consensus in tenths of a percent, -1 where the
+ * line does not state one.  The line is tokenised once: the pass that finds the row notes the span of the token, the write pass
+ * converts it.  `.out` (token 1, percent): the WHOLE token is D, `D.` or `D.d...` with D 1..6 decimal digits and digits only behind
+ * the point -> 10 * D + the first digit behind the point (0 if none); further digits are dropped, not rounded.  `rmsk` (field 2,
+ * `milliDiv`, digits already): that integer when it has at most 7 digits.  Anything else -- an empty integer part, a sign, an
+ * exponent, other characters, more digits -- is -1; parse_rm's pattern accepts any token there, so such a line stays a kept row. */
+int dgrp_rm_parse_fields(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                         const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                         int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
+                         int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream);
 
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
