@@ -35,6 +35,9 @@ Differences, all additive:
     `parse_rm` holds (deepgrp_amd/annotation.py); `optimize` and `train` on .npz files read the table only;
   * `evaluate --strata PREFIX` also writes recall by divergence bin and element length, PREFIX.strata.tsv and
     PREFIX.strata.bases.tsv, from the listing's divergence column and counts made on the GPU (deepgrp_amd/strata.py);
+  * `evaluate --offtarget PREFIX` also writes what the predicted repeats lie on, PREFIX.offtarget.tsv (predicted label by modelled
+    class, RepeatMasker class/family or nothing, for all bases and for the unsupported rows) and PREFIX.offtarget.rows.tsv, from
+    every row of the listing and counts made on the GPU (deepgrp_amd/offtarget.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -419,6 +422,15 @@ class CommandLineParser:
                                    "elements, found, recall, and the bases and hits of the elements) and PREFIX.strata.bases.tsv (per "
                                    "class, stratum and threshold: the bases whose winning element lies in the stratum); the divergence "
                                    "comes from a RepeatMasker listing (a table has none: everything is NA); --json gains the key `strata`")
+        evaluate.add_argument("--offtarget", type=str, default=None, metavar="PREFIX",
+                              help="also write what the predicted repeats lie on: PREFIX.offtarget.tsv (per predicted label the bases "
+                                   "under each modelled class, each other RepeatMasker class/family and nothing, for all bases and "
+                                   "for the unsupported predicted rows) and PREFIX.offtarget.rows.tsv (per class its unsupported rows "
+                                   "by what most of their bases lie on); needs a RepeatMasker listing as annotation; --json gains the "
+                                   "key `offtarget`")
+        evaluate.add_argument("--offtarget_by", choices=("family", "class"), default=None,
+                              help="names of PREFIX.offtarget.tsv: the class/family token (default with --offtarget) or its part in "
+                                   "front of the first '/'")
         evaluate.add_argument("--strata_div", type=str, default=None,
                               help="divergence edges of --strata in percent, ascending, 1..15 of them, one decimal allowed "
                                    "(default with --strata: 5,10,15,20,25,30)")
@@ -1113,6 +1125,8 @@ class CommandLineParser:
         curve_plan = dgcurves.plan(args)
         from . import strata as dgstrata
         strata_plan = dgstrata.plan(args)
+        from . import offtarget as dgofftarget
+        offtarget_plan = dgofftarget.plan(args)
         import json
 
         from . import model as dgmodel
@@ -1129,7 +1143,10 @@ class CommandLineParser:
         try:
             # a table is read here, before the device is touched; a RepeatMasker listing is parsed ON the device (the model's class
             # check above still comes first)
-            annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else read_annotation(args.annotation, repeats)
+            if offtarget_plan is not None:
+                annotation = dgann.evaluation_rows(args.annotation, repeats, offtarget=True)
+            else:
+                annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else read_annotation(args.annotation, repeats)
         except AnnotationError as e:
             sys.exit(str(e))
         model = dgmodel.device_model(weights)
@@ -1141,15 +1158,18 @@ class CommandLineParser:
                                  min_overlap=args.min_overlap))
         curves = dgcurves.Curves(classes, curve_plan.bins, curve_plan.elements_path is not None) if curve_plan is not None else None
         strata = dgstrata.Strata(classes, strata_plan.div_edges, strata_plan.len_edges, strata_plan.bins) if strata_plan is not None else None
+        offtarget = dgofftarget.Offtarget(classes, annotation.families, offtarget_plan.by) if offtarget_plan is not None else None
         try:
             rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves,
-                           strata)
+                           strata, offtarget)
         except NoMatchError as e:
             sys.exit(str(e))
         if curves is not None:
             curves.write(curve_plan, _LOG)
         if strata is not None:
             strata.write(strata_plan, _LOG)
+        if offtarget is not None:
+            offtarget.write(offtarget_plan, _LOG)
         text = tsv_report(rep)
         if args.output == "-":
             sys.stdout.write(text)

@@ -171,6 +171,13 @@ _SIGNATURES = {
     "dgrp_paint_strata_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_prob_hist_strata_workspace_bytes": (i64, [i64]),
     "dgrp_prob_hist_strata_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, vp, vp, vp, i64, vp]),
+    "dgrp_rm_parse_all_workspace_bytes": (i64, [i64]),
+    "dgrp_rm_parse_all": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_token_ids_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_token_ids": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+    "dgrp_paint_keys_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_key_crosstab_batch": (cint, [vp, vp, i64, cint, i64, vp, vp, vp]),
+    "dgrp_row_key_classes_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

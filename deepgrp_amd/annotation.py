@@ -149,9 +149,13 @@ def millidiv_of_line(line: str) -> int:
 class Listing:
     """The numbered rows of a listing in file order: `begin`, `end`, `line` (int64), `number`, `millidiv` (int32; the divergence in
     tenths of a percent, -1 where not stated), and the runs of one contig name -- run r is rows run_first[r] .. run_first[r + 1]
-    and is named run_names[r].  `route`: "device" or "host"."""
+    and is named run_names[r].  `route`: "device" or "host".  A listing of ALL rows (read_listing(all_rows=True)) holds every line
+    that matches a pattern, `number` 0 where the rule finds none, and also `family_id` (int32 per row: the rank of its family token
+    among the distinct tokens of the listing in ascending byte order) and `families` (those tokens in id order); else both are
+    None."""
 
-    def __init__(self, path, begin, end, number, line, run_first, run_names: List[str], lines: int, route: str, millidiv=None):
+    def __init__(self, path, begin, end, number, line, run_first, run_names: List[str], lines: int, route: str, millidiv=None,
+                 family_id=None, families: Optional[List[str]] = None):
         self.path, self.route, self.lines = path, route, int(lines)
         self.begin, self.end, self.line = (np.ascontiguousarray(a, np.int64) for a in (begin, end, line))
         self.number = np.ascontiguousarray(number, np.int32)
@@ -160,6 +164,10 @@ class Listing:
         self.millidiv = np.full(self.begin.size, -1, np.int32) if millidiv is None else np.ascontiguousarray(millidiv, np.int32)
         if self.millidiv.shape != self.begin.shape:
             raise ValueError(f"{self.millidiv.size} divergences for {self.begin.size} rows")
+        self.family_id = None if family_id is None else np.ascontiguousarray(family_id, np.int32)
+        self.families = None if families is None else list(families)
+        if self.family_id is not None and self.family_id.shape != self.begin.shape:
+            raise ValueError(f"{self.family_id.size} family ids for {self.begin.size} rows")
 
     def __len__(self) -> int:
         return int(self.begin.size)
@@ -177,26 +185,31 @@ class Listing:
 
     def grouped_fields(self, keep: Optional[np.ndarray] = None):
         """`grouped` plus {contig: the millidiv of its rows}, the same rows in the same order."""
-        names, cid = self.contigs()
-        idx = np.arange(len(self)) if keep is None else np.flatnonzero(keep)
         rows_of: Dict[str, np.ndarray] = {}
         lines_of: Dict[str, np.ndarray] = {}
         div_of: Dict[str, np.ndarray] = {}
+        for name, sel in self.grouped_index(keep).items():
+            rows = np.zeros(sel.size, _segment_dtype())
+            rows["start"], rows["end"], rows["label"] = self.begin[sel], self.end[sel], self.number[sel]
+            rows_of[name] = rows
+            lines_of[name] = self.line[sel]
+            div_of[name] = self.millidiv[sel]
+        return rows_of, lines_of, div_of
+
+    def grouped_index(self, keep: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+        """{contig: the indices of its rows among those `keep` marks}, in the order `grouped` states."""
+        names, cid = self.contigs()
+        idx = np.arange(len(self)) if keep is None else np.flatnonzero(keep)
+        out: Dict[str, np.ndarray] = {}
         if idx.size == 0:
-            return rows_of, lines_of, div_of
+            return out
         order = idx[np.argsort(cid[idx], kind="stable")]
         counts = np.bincount(cid[idx], minlength=len(names))
         parts = np.split(order, np.cumsum(counts)[:-1])
         for k in sorted(range(len(names)), key=lambda i: names[i]):
-            sel = parts[k]
-            if sel.size == 0:
-                continue
-            rows = np.zeros(sel.size, _segment_dtype())
-            rows["start"], rows["end"], rows["label"] = self.begin[sel], self.end[sel], self.number[sel]
-            rows_of[names[k]] = rows
-            lines_of[names[k]] = self.line[sel]
-            div_of[names[k]] = self.millidiv[sel]
-        return rows_of, lines_of, div_of
+            if parts[k].size:
+                out[names[k]] = parts[k]
+        return out
 
     def _bad(self, k: int, why: str):
         from .evaluation import _bad
@@ -235,10 +248,15 @@ class Listing:
 
 class Rows(dict):
     """{contig: SEGMENT_DTYPE rows}; `lines[contig]`: the line of the listing each row came from (None for a table);
-    `millidiv[contig]`: the divergence of each row in tenths of a percent, -1 where not stated (None for a table: all -1)."""
+    `millidiv[contig]`: the divergence of each row in tenths of a percent, -1 where not stated (None for a table: all -1).
+    From evaluation_rows(offtarget=True) also the UN-MODELLED rows of the listing: `offtarget_rows[contig]` (SEGMENT_DTYPE, label =
+    the row's number, 0 where it has none), `offtarget_keys[contig]` (uint32: 64 + family id) and `families` (the tokens in id order)."""
     lines: Optional[Dict[str, np.ndarray]] = None
     millidiv: Optional[Dict[str, np.ndarray]] = None
     route: str = "table"
+    offtarget_rows: Optional[Dict[str, np.ndarray]] = None
+    offtarget_keys: Optional[Dict[str, np.ndarray]] = None
+    families: Optional[List[str]] = None
 
 
 def _runs_of(names: List[str]):
@@ -246,8 +264,43 @@ def _runs_of(names: List[str]):
     return np.asarray(first + [len(names)], np.int64), [names[i] for i in first]
 
 
-def _listing_host(path) -> Listing:
+def family_ranks(tokens: Sequence[str]):
+    """(family_id int32 per token, the distinct tokens in id order): ranks in ascending order of the tokens' bytes (UTF-8), a proper
+    prefix first -- the order dgrp_token_ids states."""
+    raw = [t.encode("utf-8", "surrogateescape") for t in tokens]
+    distinct = sorted(set(raw))
+    rank = {t: k for k, t in enumerate(distinct)}
+    return (np.fromiter((rank[t] for t in raw), np.int32, count=len(raw)), [t.decode("utf-8", "surrogateescape") for t in distinct])
+
+
+def _listing_host_all(path) -> Listing:
+    """The host path for ALL rows: every line parse_rm.parse_line finds a contig in is a row, numbered as read_repeatmasker numbers
+    it (0 where that yields nothing), with its family token as parse_line states it."""
+    from .evaluation import AnnotationError
+    exact, one_off = parse_rm.pentamer_sets()
+    names, vals, fams = [], [], []
+    k = 0
+    for k, line in enumerate(io.StringIO(_read_text(path)), 1):
+        r = parse_rm.parse_line(line)
+        if r.ctg is None:
+            continue
+        for what, v in (("begin", r.start), ("end", r.end)):
+            if not -(1 << 63) <= v < (1 << 63):
+                raise AnnotationError(f"{path}:{k}: {what} '{v}' is not an integer: {line.rstrip()!r}")
+        numbered = list(parse_rm.read_repeatmasker(exact, one_off, [line]))
+        names.append(r.ctg)
+        fams.append(r.fam)
+        vals.append((r.start, r.end, numbered[0].typ if numbered else 0, k, millidiv_of_line(line)))
+    a = np.asarray(vals, np.int64).reshape(-1, 5)
+    run_first, run_names = _runs_of(names)
+    fid, families = family_ranks(fams)
+    return Listing(path, a[:, 0], a[:, 1], a[:, 2], a[:, 3], run_first, run_names, k, "host", a[:, 4], fid, families)
+
+
+def _listing_host(path, all_rows: bool = False) -> Listing:
     """The host path: parse_rm.read_repeatmasker on the decoded text."""
+    if all_rows:
+        return _listing_host_all(path)
     from .evaluation import AnnotationError
     exact, one_off = parse_rm.pentamer_sets()
     at = [0]
@@ -286,11 +339,12 @@ def _device_tables(dev):
     return _DEVICE_TABLES[dev]
 
 
-def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None, fields: bool = False):
+def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None, fields: bool = False, all_rows: bool = False):
     """dgrp_rm_parse on the uint8 device tensor `d_text` (its first `n` bytes): -> (counts = [lines, kept rows, runs, not-plain
     flag], the device arrays begin, end, number, name_pos, name_len, line, run_first of `cap` rows -- default n // 22 + 1 --, the
     return code).  Nothing is raised for DGRP_ENOMEM (-3: more rows than `cap`; counts[1] tells the need).  fields:
-    dgrp_rm_parse_fields, and `millidiv` among the arrays."""
+    dgrp_rm_parse_fields, and `millidiv` among the arrays.  all_rows: dgrp_rm_parse_all -- every matching line is a row -- with
+    `millidiv` and the family spans `fam_pos`, `fam_len`, `fam2_pos`, `fam2_len` among the arrays."""
     import ctypes as C
 
     import torch
@@ -305,33 +359,79 @@ def parse_device(d_text, n: Optional[int] = None, cap: Optional[int] = None, fie
     i64 = lambda: torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
     i32 = lambda: torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
     out = dict(begin=i64(), end=i64(), number=i32(), name_pos=i64(), name_len=i32(), line=i64(), run_first=i64())
-    wb = int(L.dgrp_rm_parse_workspace_bytes(n))
+    wb = int(L.dgrp_rm_parse_all_workspace_bytes(n) if all_rows else L.dgrp_rm_parse_workspace_bytes(n))
     work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
     counts = (C.c_int64 * 4)()
     head = (d_text.data_ptr() if n else None, n, d_names.data_ptr(), d_off.data_ptr(), nnames, d_pent.data_ptr(), unit,
             out["begin"].data_ptr(), out["end"].data_ptr(), out["number"].data_ptr(), out["name_pos"].data_ptr(),
             out["name_len"].data_ptr(), out["line"].data_ptr(), out["run_first"].data_ptr())
     tail = (cap, counts, work.data_ptr(), wb, stream_ptr())
-    if fields:
+    if all_rows:
+        out.update(millidiv=i32(), fam_pos=i64(), fam_len=i32(), fam2_pos=i64(), fam2_len=i32())
+        rc = L.dgrp_rm_parse_all(*head, *(out[k].data_ptr() for k in ("millidiv", "fam_pos", "fam_len", "fam2_pos", "fam2_len")), *tail)
+    elif fields:
         out["millidiv"] = i32()
         rc = L.dgrp_rm_parse_fields(*head, out["millidiv"].data_ptr(), *tail)
     else:
         rc = L.dgrp_rm_parse(*head, *tail)
     if rc not in (0, -3):
-        check(rc, "dgrp_rm_parse_fields" if fields else "dgrp_rm_parse")
+        check(rc, "dgrp_rm_parse_all" if all_rows else "dgrp_rm_parse_fields" if fields else "dgrp_rm_parse")
     return [int(c) for c in counts], out, rc
 
 
-def listing_of_device_text(path, d_text, n: int) -> Optional[Listing]:
-    """The Listing of the text in device memory, or None when the device raised the not-plain flag."""
+TOKEN_MAX = 16384                        # DGRP_TOKEN_MAX: distinct tokens the device numbers
+NAMES_BYTES = 1 << 20                    # room for the distinct tokens' bytes; the call tells the need when it is more
+
+
+def token_ids_device(d_text, n: int, rows: int, d_pos, d_len, d_pos2, d_len2, names_cap: int = NAMES_BYTES):
+    """dgrp_token_ids on `rows` tokens given as spans of the uint8 device tensor `d_text`: -> (int32 device tensor of ids, the
+    distinct tokens in id order as bytes), or None when there are more than TOKEN_MAX distinct tokens (the overflow flag)."""
+    import ctypes as C
+
     import torch
-    counts, out, rc = parse_device(d_text, n, fields=True)
+
+    from ._lib import check, lib
+    from .pipeline import stream_ptr
+    L = lib()
+    dev = d_text.device
+    d_fid = torch.empty(max(rows, 1), dtype=torch.int32, device=dev)
+    for _attempt in range(2):
+        wb = int(L.dgrp_token_ids_workspace_bytes(rows, names_cap))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        names = np.zeros(max(names_cap, 1), np.uint8)
+        off = np.zeros(TOKEN_MAX + 1, np.int64)
+        counts = (C.c_int64 * 3)()
+        rc = L.dgrp_token_ids(d_text.data_ptr(), int(n), int(rows), d_pos.data_ptr(), d_len.data_ptr(), d_pos2.data_ptr(), d_len2.data_ptr(),
+                              d_fid.data_ptr(), names.ctypes.data, names_cap, off.ctypes.data, counts, work.data_ptr(), wb, stream_ptr())
+        if rc == -3 and int(counts[2]) > names_cap:
+            names_cap = int(counts[2])
+            continue
+        check(rc, "dgrp_token_ids")
+        break
+    if counts[1]:
+        return None
+    F = int(counts[0])
+    blob = names.tobytes()
+    return d_fid[:rows], [blob[int(off[k]):int(off[k + 1])] for k in range(F)]
+
+
+def listing_of_device_text(path, d_text, n: int, all_rows: bool = False) -> Optional[Listing]:
+    """The Listing of the text in device memory, or None when the device raised the not-plain flag -- or, with all_rows, the
+    overflow flag of the family ids."""
+    import torch
+    counts, out, rc = parse_device(d_text, n, fields=True, all_rows=all_rows)
     if counts[3]:
         return None
     if rc != 0:
         from ._lib import check
-        check(rc, "dgrp_rm_parse_fields")
+        check(rc, "dgrp_rm_parse_all" if all_rows else "dgrp_rm_parse_fields")
     lines, kept, runs = counts[:3]
+    fid = families = None
+    if all_rows:
+        ids = token_ids_device(d_text, n, kept, out["fam_pos"], out["fam_len"], out["fam2_pos"], out["fam2_len"])
+        if ids is None:
+            return None
+        fid, families = ids[0].cpu().numpy(), [t.decode("ascii") for t in ids[1]]
     host = lambda k: out[k][:kept].cpu().numpy()
     first = out["run_first"][:runs]
     names: List[str] = []
@@ -345,14 +445,17 @@ def listing_of_device_text(path, d_text, n: int) -> Optional[Listing]:
         cut = np.concatenate([offs.cpu().numpy(), [total]])
         names = [blob[cut[r]:cut[r + 1]].decode("ascii") for r in range(runs)]
     run_first = np.concatenate([first.cpu().numpy(), [kept]]).astype(np.int64)
-    return Listing(path, host("begin"), host("end"), host("number"), host("line"), run_first, names, lines, "device", host("millidiv"))
+    return Listing(path, host("begin"), host("end"), host("number"), host("line"), run_first, names, lines, "device", host("millidiv"),
+                   fid, families)
 
 
-def read_listing(path, device: bool = True) -> Listing:
+def read_listing(path, device: bool = True, all_rows: bool = False) -> Listing:
     """The numbered rows of the RepeatMasker listing `path` (plain, gzip or BGZF): parsed on the device, or by the host path (module
-    docstring) with device=False, on the not-plain flag and above the resident-bytes limit."""
+    docstring) with device=False, on the not-plain flag and above the resident-bytes limit.  all_rows: EVERY row that matches a
+    pattern, with `family_id` and `families` (dgrp_rm_parse_all, dgrp_token_ids; more than TOKEN_MAX distinct family tokens take the
+    host path too)."""
     if not device:
-        return _listing_host(path)
+        return _listing_host(path, all_rows)
     from . import gz
     from .fasta import RESIDENT_BYTES, _upload_file
     from .pipeline import require_gpu
@@ -362,16 +465,16 @@ def read_listing(path, device: bool = True) -> Listing:
         except gz.GzipError:
             raise
         except ValueError:                                           # inflates to more than the limit
-            return _listing_host(path)
+            return _listing_host(path, all_rows)
     else:
         size = os.path.getsize(path)
         if size > RESIDENT_BYTES:
-            return _listing_host(path)
+            return _listing_host(path, all_rows)
         d_text = _upload_file(path, size, require_gpu()) if size else None
     if size == 0:
-        return Listing(path, [], [], [], [], [0], [], 0, "device")
-    got = listing_of_device_text(path, d_text, size)
-    return _listing_host(path) if got is None else got
+        return Listing(path, [], [], [], [], [0], [], 0, "device", None, [] if all_rows else None, [] if all_rows else None)
+    got = listing_of_device_text(path, d_text, size, all_rows)
+    return _listing_host(path, all_rows) if got is None else got
 
 
 def read_rows(path, fmt: str = "auto", device: bool = True) -> Rows:
@@ -389,12 +492,24 @@ def read_rows(path, fmt: str = "auto", device: bool = True) -> Rows:
     return out
 
 
-def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool = True) -> Rows:
+def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool = True, offtarget: bool = False) -> Rows:
     """evaluation.read_annotation(table of the listing `path`, repeats) without the table: the same rows, and the same
     AnnotationError for a negative begin or an end below its begin -- checked on every row before `repeats` filters, the first in
-    file order named as "<listing>:<its line>: <why>: <the line>".  `.lines` and `.millidiv` travel beside the rows."""
-    listing = read_listing(path, device)
+    file order named as "<listing>:<its line>: <why>: <the line>".  `.lines` and `.millidiv` travel beside the rows.
+    offtarget: the listing is parsed once for ALL its rows; the rows kept without it are the MODELLED rows and are returned as
+    before, every other row -- no number, or a number outside `repeats` -- is un-modelled and travels as `.offtarget_rows`,
+    `.offtarget_keys` (64 + family id) and `.families`; the two checks then apply to every row of the listing."""
+    listing = read_listing(path, device, all_rows=offtarget)
+    if offtarget and len(listing.families) > TOKEN_MAX:
+        from .evaluation import AnnotationError
+        raise AnnotationError(f"{path}: {len(listing.families)} distinct class/family tokens; --offtarget has room for {TOKEN_MAX}")
     read = listing.table_mask()
+    if offtarget:
+        read &= listing.number > 0
+        bad = np.flatnonzero((listing.begin < 0) | (listing.end < listing.begin))
+        if bad.size:
+            k = int(bad[0])
+            raise listing._bad(k, "negative begin" if listing.begin[k] < 0 else "end below begin")
     bad = np.flatnonzero(read & ((listing.begin < 0) | (listing.end < listing.begin)))
     if bad.size:
         k = int(bad[0])
@@ -404,6 +519,13 @@ def evaluation_rows(path, repeats: Optional[Iterable[int]] = None, device: bool 
     rows_of, lines_of, div_of = listing.grouped_fields(read)
     out = Rows(rows_of)
     out.lines, out.millidiv, out.route = lines_of, div_of, listing.route
+    if offtarget:
+        out.offtarget_rows, out.offtarget_keys, out.families = {}, {}, list(listing.families)
+        for name, sel in listing.grouped_index(~read).items():
+            rows = np.zeros(sel.size, _segment_dtype())
+            rows["start"], rows["end"], rows["label"] = listing.begin[sel], listing.end[sel], listing.number[sel]
+            out.offtarget_rows[name] = rows
+            out.offtarget_keys[name] = (64 + listing.family_id[sel].astype(np.int64)).astype(np.uint32)
     return out
 
 

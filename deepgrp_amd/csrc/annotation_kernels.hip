@@ -7,6 +7,8 @@
 // every line that STARTS in its chunk -- about one for a `.out` listing.  The lane walks its lines byte by byte in global memory: the
 // bytes were just read by the same workgroup, and a line of any length needs no staging limit.  Bytes and integers only, no atomics
 // but the OR of the flag; a count pass and a write pass around one scan give every row its place, so the same call gives the same bytes.
+// dgrp_rm_parse_all is one more mode of the same two passes: every line that matches a pattern is a row, numbered or not, and the
+// span (or the two spans) of its family token travels with it.
 #include "scan.h"
 
 namespace {
@@ -32,6 +34,8 @@ struct rm_row {
     int32_t number, name_len;
     int64_t div_b, div_e;                // the divergence token: `.out` token 1 (percent), `rmsk` field 2 (tenths of a percent)
     bool div_rmsk;
+    int64_t fam_pos, fam2_pos;           // the family token: `.out` token 10; `rmsk` field 11 and, where it differs, field 12 behind it
+    int32_t fam_len, fam2_len;           // (fam2_len = 0: the token is the first span alone)
 };
 
 // a token, or two of them read as `A/B`
@@ -89,8 +93,10 @@ __host__ __device__ bool rm_unit_rule(const uint8_t *__restrict__ t, int64_t rb,
     return in5 == 0 && all && exact;
 }
 
-// The line that starts at s: true and `row` when it is a numbered repeat.  `big`: a coordinate of more than RM_MAX_DIGITS digits.
-__host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s, int64_t n, const rm_tables &T, rm_row &row, bool &big)
+// The line that starts at s: true and `row` when it is a numbered repeat -- with `all`, when it matches a pattern at all (its number
+// is then 0 where the rule finds none).  `big`: a coordinate of more than RM_MAX_DIGITS digits.
+__host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s, int64_t n, const rm_tables &T, rm_row &row, bool &big,
+                                       bool all = false)
 {
     const uint8_t simple[13] = { 'S', 'i', 'm', 'p', 'l', 'e', '_', 'r', 'e', 'p', 'e', 'a', 't' };
     const uint8_t satellite[9] = { 'S', 'a', 't', 'e', 'l', 'l', 'i', 't', 'e' };
@@ -190,8 +196,14 @@ __host__ __device__ bool rm_parse_line(const uint8_t *__restrict__ t, int64_t s,
     if (number == 0) number = rm_number_of(t, rep, T);
     if (number == 0 && (rm_equals(t, fam, simple, 13) || rm_equals(t, fam, satellite, 9)) && rm_unit_rule(t, rb, re, T.pent))
         number = T.unit_number;
-    if (number <= 0) return false;
+    if (number <= 0 && !all) return false;
+    if (number < 0) number = 0;
     if (ce - cb > 0x7fffffffll) big = true;                                  // (a name the int32 length cannot state)
+    if (all && (fam.ae - fam.ab > 0x7fffffffll || fam.be - fam.bb > 0x7fffffffll)) big = true;
+    row.fam_pos = fam.ab;
+    row.fam_len = (int32_t)(fam.ae - fam.ab);
+    row.fam2_pos = fam.joined ? fam.bb : fam.ab;
+    row.fam2_len = fam.joined ? (int32_t)(fam.be - fam.bb) : 0;
     row.begin = v5;
     row.end = v6;
     row.name_pos = cb;
@@ -273,6 +285,10 @@ struct rm_out {
     int32_t *name_len;
     int64_t *line;
     int32_t *millidiv;                   // NULL: not asked for (dgrp_rm_parse)
+    int64_t *fam_pos;                    // NULL: not asked for; else every matching line is a row (dgrp_rm_parse_all)
+    int32_t *fam_len;
+    int64_t *fam2_pos;
+    int32_t *fam2_len;
     int64_t cap;
 };
 
@@ -280,7 +296,7 @@ struct rm_out {
 // rows place, place + 1, ... and line0 line feeds lie in front of the chunk.
 template <bool WRITE>
 __host__ __device__ uint32_t rm_chunk_lines(const uint8_t *__restrict__ t, int64_t c0, int64_t n, const rm_tables &T, uint64_t lo,
-                                            uint64_t hi, bool &bad, uint64_t place, uint64_t line0, const rm_out &out)
+                                            uint64_t hi, bool &bad, uint64_t place, uint64_t line0, const rm_out &out, bool all)
 {
     const int64_t c1 = c0 + RM_CHUNK < n ? c0 + RM_CHUNK : n;
     uint32_t kept = 0, seen = 0;
@@ -296,7 +312,7 @@ __host__ __device__ uint32_t rm_chunk_lines(const uint8_t *__restrict__ t, int64
             if (s >= c1) break;                                              // the next chunk's line (or the end of the text)
         }
         rm_row row;
-        if (rm_parse_line(t, s, n, T, row, bad)) {
+        if (rm_parse_line(t, s, n, T, row, bad, all)) {
             if (WRITE) {
                 const int64_t i = (int64_t)(place + kept);
                 if (i < out.cap) {
@@ -307,6 +323,12 @@ __host__ __device__ uint32_t rm_chunk_lines(const uint8_t *__restrict__ t, int64
                     out.name_len[i] = row.name_len;
                     out.line[i] = (int64_t)(line0 + seen) + 1;
                     if (out.millidiv) out.millidiv[i] = rm_millidiv(t, row);
+                    if (out.fam_pos) {
+                        out.fam_pos[i] = row.fam_pos;
+                        out.fam_len[i] = row.fam_len;
+                        out.fam2_pos[i] = row.fam2_pos;
+                        out.fam2_len[i] = row.fam2_len;
+                    }
                 }
             }
             ++kept;
@@ -325,7 +347,9 @@ __global__ void __launch_bounds__(256) rm_lines_kernel(const uint8_t *__restrict
                                                        int64_t *__restrict__ o_begin, int64_t *__restrict__ o_end,
                                                        int32_t *__restrict__ o_number, int64_t *__restrict__ o_name_pos,
                                                        int32_t *__restrict__ o_name_len, int64_t *__restrict__ o_line,
-                                                       int32_t *__restrict__ o_millidiv, int64_t cap)
+                                                       int32_t *__restrict__ o_millidiv, int64_t *__restrict__ o_fam_pos,
+                                                       int32_t *__restrict__ o_fam_len, int64_t *__restrict__ o_fam2_pos,
+                                                       int32_t *__restrict__ o_fam2_len, bool all, int64_t cap)
 {
     __shared__ uint64_t lds[4];
     const int64_t chunk = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -342,8 +366,8 @@ __global__ void __launch_bounds__(256) rm_lines_kernel(const uint8_t *__restrict
         place = keep[blockIdx.x] + (ex & 0xffffffffull);
         line0 = nl[blockIdx.x] + (ex >> 32);
     }
-    const rm_out out = { o_begin, o_end, o_number, o_name_pos, o_name_len, o_line, o_millidiv, cap };
-    const uint32_t kept = c0 < n ? rm_chunk_lines<WRITE>(t, c0, n, T, lo, hi, bad, place, line0, out) : 0u;
+    const rm_out out = { o_begin, o_end, o_number, o_name_pos, o_name_len, o_line, o_millidiv, o_fam_pos, o_fam_len, o_fam2_pos, o_fam2_len, cap };
+    const uint32_t kept = c0 < n ? rm_chunk_lines<WRITE>(t, c0, n, T, lo, hi, bad, place, line0, out, all) : 0u;
     if (!WRITE) {
         if (c0 < n) lane_keep[chunk] = (uint8_t)kept;                        // (at most RM_CHUNK / RM_MIN_LINE + 1)
         if (bad) atomicOr(&g[0], 1ull);
@@ -394,8 +418,15 @@ DGRP_EXPORT int64_t dgrp_rm_parse_workspace_bytes(int64_t n)
 
 namespace {
 
-// both entries: d_millidiv NULL (dgrp_rm_parse) writes no divergence
-int rm_parse_run(const char *what, bool fields, const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off,
+struct rm_fam_out {
+    int64_t *pos;
+    int32_t *len;
+    int64_t *pos2;
+    int32_t *len2;
+};
+
+// the three entries: d_millidiv NULL (dgrp_rm_parse) writes no divergence; fam non-NULL (dgrp_rm_parse_all) keeps every matching line
+int rm_parse_run(const char *what, bool fields, const rm_fam_out *fam, const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off,
                  int nnames, const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
                  int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int32_t *d_millidiv, int64_t *d_run_first, int64_t cap,
                  int64_t *h_counts, void *d_work, int64_t work_bytes, hipStream_t stream)
@@ -410,6 +441,9 @@ int rm_parse_run(const char *what, bool fields, const uint8_t *d_text, int64_t n
     DGRP_REQUIRE(cap >= 0, "%s: negative capacity", what);
     DGRP_REQUIRE(cap == 0 || (d_begin && d_end && d_number && d_name_pos && d_name_len && d_line && d_run_first), "%s: NULL output", what);
     DGRP_REQUIRE(cap == 0 || !fields || d_millidiv, "%s: NULL output", what);
+    DGRP_REQUIRE(cap == 0 || !fam || (fam->pos && fam->len && fam->pos2 && fam->len2), "%s: NULL output", what);
+    const bool all = fam != nullptr;
+    const rm_fam_out fo = all ? *fam : rm_fam_out{ nullptr, nullptr, nullptr, nullptr };
     if (n == 0) return DGRP_OK;
     const int64_t tiles = rm_tiles_of(n), bound = rm_rows_bound(n);
     DGRP_REQUIRE(tiles < (1ll << 31), "%s: too many bytes", what);
@@ -435,7 +469,8 @@ int rm_parse_run(const char *what, bool fields, const uint8_t *d_text, int64_t n
     DGRP_HIP(hipMemsetAsync(g, 0, RM_HEAD, stream));
     hipLaunchKernelGGL(rm_lines_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, d_text, n, T, d_lane, d_nl, d_keep, g,
                        (int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr,
-                       (int64_t *)nullptr, (int32_t *)nullptr, (int64_t)0);
+                       (int64_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr, (int64_t *)nullptr,
+                       (int32_t *)nullptr, all, (int64_t)0);
     DGRP_LAUNCH_CHECK();
     int rc = device_exclusive_scan(d_nl, d_nl, tiles, d_tiles, d_nl + tiles, stream);
     if (rc != DGRP_OK) return rc;
@@ -460,7 +495,8 @@ int rm_parse_run(const char *what, bool fields, const uint8_t *d_text, int64_t n
     }
     const int64_t rows = (int64_t)kept;                                      // (<= bound: every numbered line has RM_MIN_LINE bytes)
     hipLaunchKernelGGL(rm_lines_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, d_text, n, T, d_lane, d_nl, d_keep, g, d_begin,
-                       d_end, d_number, d_name_pos, d_name_len, d_line, fields ? d_millidiv : (int32_t *)nullptr, cap);
+                       d_end, d_number, d_name_pos, d_name_len, d_line, fields ? d_millidiv : (int32_t *)nullptr, fo.pos, fo.len, fo.pos2,
+                       fo.len2, all, cap);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(rm_run_flag_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, d_text, d_name_pos, d_name_len, rows,
                        d_run);
@@ -485,7 +521,7 @@ DGRP_EXPORT int dgrp_rm_parse(const uint8_t *d_text, int64_t n, const uint8_t *d
                               int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap,
                               int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
 {
-    return rm_parse_run("dgrp_rm_parse", false, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end, d_number,
+    return rm_parse_run("dgrp_rm_parse", false, nullptr, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end, d_number,
                         d_name_pos, d_name_len, d_line, nullptr, d_run_first, cap, h_counts, d_work, work_bytes, (hipStream_t)stream_);
 }
 
@@ -494,7 +530,21 @@ DGRP_EXPORT int dgrp_rm_parse_fields(const uint8_t *d_text, int64_t n, const uin
                                      int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
                                      int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
 {
-    return rm_parse_run("dgrp_rm_parse_fields", true, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end,
+    return rm_parse_run("dgrp_rm_parse_fields", true, nullptr, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end,
+                        d_number, d_name_pos, d_name_len, d_line, d_millidiv, d_run_first, cap, h_counts, d_work, work_bytes,
+                        (hipStream_t)stream_);
+}
+
+DGRP_EXPORT int64_t dgrp_rm_parse_all_workspace_bytes(int64_t n) { return dgrp_rm_parse_workspace_bytes(n); }
+
+DGRP_EXPORT int dgrp_rm_parse_all(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                                  const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                                  int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
+                                  int64_t *d_fam_pos, int32_t *d_fam_len, int64_t *d_fam2_pos, int32_t *d_fam2_len, int64_t cap,
+                                  int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream_)
+{
+    const rm_fam_out fam = { d_fam_pos, d_fam_len, d_fam2_pos, d_fam2_len };
+    return rm_parse_run("dgrp_rm_parse_all", true, &fam, d_text, n, d_names, d_name_off, nnames, d_pentamers, unit_number, d_begin, d_end,
                         d_number, d_name_pos, d_name_len, d_line, d_millidiv, d_run_first, cap, h_counts, d_work, work_bytes,
                         (hipStream_t)stream_);
 }

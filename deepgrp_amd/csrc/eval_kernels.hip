@@ -121,7 +121,8 @@ __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__r
                                                          int64_t nrec, const int64_t *__restrict__ len,
                                                          const int64_t *__restrict__ origin, int max_label,
                                                          const dgrp_row_score *__restrict__ scores,
-                                                         unsigned long long *__restrict__ g, unsigned long long *__restrict__ tot)
+                                                         unsigned long long *__restrict__ g, unsigned long long *__restrict__ tot,
+                                                         const uint32_t *__restrict__ row_key)
 {
     __shared__ unsigned long long s_tot[128];
     if (threadIdx.x < 128) s_tot[threadIdx.x] = 0ull;
@@ -129,14 +130,16 @@ __global__ void __launch_bounds__(256) eval_check_kernel(const dgrp_segment *__r
     const int64_t i = row_off[0] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < row_off[nrec]) {
         const dgrp_segment q = rows[i];
-        if (q.start < 0 || q.end < q.start || q.label < 1 || q.label > max_label) {
+        // (rows with keys of their own: the label is not read, the key must not be the fill, the lengths are summed under label 1)
+        const bool bad_mark = row_key ? row_key[i] == 0xFFFFFFFFu : (q.label < 1 || q.label > max_label);
+        if (q.start < 0 || q.end < q.start || bad_mark) {
             atomicOr(&g[0], 1ull);
             atomicMin(&g[1], (unsigned long long)i);
         } else {
             const int64_t r = dgrp_record_of(row_off, nrec, i);
             int64_t cs, cl;
             eval_clip(q, origin[r], len[r], cs, cl);
-            if (cl) atomicAdd(&s_tot[q.label], (unsigned long long)cl);
+            if (cl) atomicAdd(&s_tot[row_key ? 1 : q.label], (unsigned long long)cl);
             if (scores) {
                 if (cl && !bed_scored(scores[i])) {
                     atomicOr(&g[0], 2ull);
@@ -226,7 +229,7 @@ __global__ void __launch_bounds__(256) eval_hits_kernel(const int8_t *__restrict
 // d_scores: the rows are scored rows, checked as eval_check_kernel says; extra_bytes: more workspace, 256-byte aligned, at pl.d_extra
 int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
                  const dgrp_segment *d_rows, const int64_t *h_row_off, void *d_work, int64_t work_bytes, hipStream_t stream,
-                 eval_plan &pl, int max_label, const dgrp_row_score *d_scores, int64_t extra_bytes)
+                 eval_plan &pl, int max_label, const dgrp_row_score *d_scores, int64_t extra_bytes, const uint32_t *d_row_key)
 {
     DGRP_REQUIRE(nrec >= 0 && h_row_off && (nrec == 0 || (h_off && h_len && h_origin)), "%s: bad arguments", what);
     DGRP_REQUIRE(h_row_off[0] >= 0, "%s: negative row offset", what);
@@ -267,7 +270,7 @@ int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int
     DGRP_HIP(hipMemsetAsync(d_tot, 0, 128 * 8, stream));
     DGRP_HIP(hipMemcpyAsync(pl.d_off, pl.tab.data(), pl.tab.size() * 8, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(eval_check_kernel, dim3((unsigned)((pl.nrows + 255) / 256)), dim3(256), 0, stream, d_rows, pl.d_row_off, nrec,
-                       pl.d_len, pl.d_origin, max_label, d_scores, g, d_tot);
+                       pl.d_len, pl.d_origin, max_label, d_scores, g, d_tot, d_row_key);
     DGRP_LAUNCH_CHECK();
     unsigned long long hg[4];
     DGRP_HIP(hipMemcpyAsync(hg, g, sizeof(hg), hipMemcpyDeviceToHost, stream));
@@ -284,6 +287,8 @@ int eval_prepare(const char *what, int64_t nrec, const int64_t *h_off, const int
         DGRP_REQUIRE(kind != 3, "%s: row %lld [%lld, %lld) label %d starts below the end of the row in front of it in its record "
                      "(the rows of a record ascend and do not overlap)", what, (long long)i, (long long)q.start, (long long)q.end,
                      (int)q.label);
+        DGRP_REQUIRE(!d_row_key, "%s: row %lld [%lld, %lld): rows need 0 <= start <= end and a key below 0xFFFFFFFF", what, (long long)i,
+                     (long long)q.start, (long long)q.end);
         DGRP_REQUIRE(false, "%s: row %lld [%lld, %lld) label %d: rows need 0 <= start <= end and 1 <= label <= %d", what, (long long)i,
                      (long long)q.start, (long long)q.end, (int)q.label, max_label);
     }

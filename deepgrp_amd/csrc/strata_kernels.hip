@@ -6,6 +6,7 @@
 // does not depend on order: the track is filled with ones, then ONE pass over the line of positions of all rows (the scan of the
 // clipped lengths, 8192 positions a workgroup, lane-interleaved as eval_paint_kernel) does a 32-bit atomicMin per position.  The rows
 // are checked by the kernel under dgrp_paint_rows_batch (eval_rows.h) before a byte is written.
+// dgrp_paint_keys_batch (evaluate --offtarget) is the same body with a key of the caller's per row: the label is not read there.
 //
 // dgrp_prob_hist_strata_batch.  A cell is a (class, stratum) pair, `bins` 32-bit counters in LDS.  Where C * S * bins counters do not
 // fit the 160 KiB prob_hist_kernels.hip uses, the cells are cut into groups of G = 40960 / bins along grid.y; every group reads the
@@ -25,10 +26,18 @@ namespace {
 #define SH_MAX_TILES (1 << 19)        // tiles per workgroup: 2^19 * SH_ROWS = 2^31 bases
 #define SH_NONE 0xFFFFFFFFu
 
-// every position of the slice: keys[its base] = min(keys[its base], label << 8 | stratum of its row)
+// the key of row j: its own (dgrp_paint_keys_batch: the label is not read), or label << 8 | stratum
+__device__ __forceinline__ unsigned strata_key_of(const dgrp_segment *__restrict__ rows, const uint8_t *__restrict__ stratum,
+                                                  const unsigned *__restrict__ row_key, int64_t j)
+{
+    return row_key ? row_key[j] : ((unsigned)rows[j].label << 8 | stratum[j]);
+}
+
+// every position of the slice: keys[its base] = min(keys[its base], the key of its row)
 __global__ void __launch_bounds__(256) strata_paint_kernel(unsigned *__restrict__ keys, const uint64_t *__restrict__ ex,
                                                            const int64_t *__restrict__ dst, const dgrp_segment *__restrict__ rows,
-                                                           const uint8_t *__restrict__ stratum, int64_t n)
+                                                           const uint8_t *__restrict__ stratum, const unsigned *__restrict__ row_key,
+                                                           int64_t n)
 {
     const uint64_t total = ex[n], s0 = (uint64_t)blockIdx.x * EVAL_SLICE;
     const uint64_t s1 = s0 + EVAL_SLICE < total ? s0 + EVAL_SLICE : total;
@@ -36,11 +45,11 @@ __global__ void __launch_bounds__(256) strata_paint_kernel(unsigned *__restrict_
     if (p0 >= s1) return;
     int64_t j = eval_row_of(ex, 0, n, p0);
     uint64_t jst = ex[j], jend = ex[j + 1];
-    unsigned key = (unsigned)rows[j].label << 8 | stratum[j];
+    unsigned key = strata_key_of(rows, stratum, row_key, j);
     for (uint64_t p = p0; p < s1; p += 256) {
         if (jend <= p) {
             while (jend <= p) { ++j; jst = jend; jend = ex[j + 1]; }
-            key = (unsigned)rows[j].label << 8 | stratum[j];
+            key = strata_key_of(rows, stratum, row_key, j);
         }
         atomicMin(&keys[dst[j] + (int64_t)(p - jst)], key);
     }
@@ -130,19 +139,23 @@ __global__ void __launch_bounds__(SH_THREADS) strata_hist_kernel(sh_args a)
 
 }   // namespace
 
-DGRP_EXPORT int dgrp_paint_strata_batch(uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
-                                        const int64_t *h_origin, const dgrp_segment *d_rows, const int64_t *h_row_off,
-                                        const uint8_t *d_row_stratum, void *d_work, int64_t work_bytes, void *stream_)
+namespace {
+
+// both paints: the fill, then one pass of atomic minima.  d_row_key NULL: the strata paint (label << 8 | stratum, labels 1..63 checked);
+// else the keys are the rows' own and the label is not read.
+int strata_paint_run(const char *what, uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                     const dgrp_segment *d_rows, const int64_t *h_row_off, const uint8_t *d_row_stratum, const uint32_t *d_row_key,
+                     bool own_keys, void *d_work, int64_t work_bytes, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    const char *what = "dgrp_paint_strata_batch";
     DGRP_REQUIRE(nrec >= 0 && h_off, "%s: bad arguments", what);
     DGRP_REQUIRE(h_off[nrec] >= 0 && h_off[nrec] < (1ll << 40), "%s: a track of %lld keys", what, (long long)h_off[nrec]);
     for (int64_t r = 0; r < nrec; ++r)
         DGRP_REQUIRE(h_len && h_off[r] >= 0 && h_len[r] >= 0 && h_len[r] <= h_off[nrec] && h_off[r] <= h_off[nrec] - h_len[r],
                      "%s: record %lld does not lie in the track of %lld keys", what, (long long)r, (long long)h_off[nrec]);
     eval_plan pl;
-    const int rc = eval_prepare(what, nrec, h_off, h_len, h_origin, d_rows, h_row_off, d_work, work_bytes, stream, pl, 63);
+    DGRP_REQUIRE(!own_keys || d_row_key || !h_row_off || h_row_off[nrec] == h_row_off[0], "%s: NULL keys", what);
+    const int rc = eval_prepare(what, nrec, h_off, h_len, h_origin, d_rows, h_row_off, d_work, work_bytes, stream, pl, 63, nullptr, 0,
+                                own_keys ? d_row_key : nullptr);
     if (rc != DGRP_OK) return rc;
     const int64_t n = h_off[nrec];
     if (n == 0) return DGRP_OK;
@@ -151,14 +164,33 @@ DGRP_EXPORT int dgrp_paint_strata_batch(uint32_t *d_keys, int64_t nrec, const in
     uint64_t total = 0;
     for (int k = 1; k < 128; ++k) total += pl.tot[k];
     if (pl.nrows == 0 || nrec == 0 || total == 0) return DGRP_OK;
-    DGRP_REQUIRE(d_row_stratum, "%s: NULL strata", what);
+    DGRP_REQUIRE(own_keys || d_row_stratum, "%s: NULL strata", what);
     const int e = eval_spans(pl, d_rows, nrec, 0, stream);
     if (e != DGRP_OK) return e;
     const int64_t r0 = h_row_off[0];
     hipLaunchKernelGGL(strata_paint_kernel, dim3((unsigned)((total + EVAL_SLICE - 1) / EVAL_SLICE)), dim3(256), 0, stream, d_keys, pl.d_cl,
-                       pl.d_dst, d_rows + r0, d_row_stratum + r0, pl.nrows);
+                       pl.d_dst, d_rows + r0, own_keys ? (const uint8_t *)nullptr : d_row_stratum + r0,
+                       own_keys ? d_row_key + r0 : (const uint32_t *)nullptr, pl.nrows);
     DGRP_LAUNCH_CHECK();
     return DGRP_OK;
+}
+
+}   // namespace
+
+DGRP_EXPORT int dgrp_paint_strata_batch(uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len,
+                                        const int64_t *h_origin, const dgrp_segment *d_rows, const int64_t *h_row_off,
+                                        const uint8_t *d_row_stratum, void *d_work, int64_t work_bytes, void *stream_)
+{
+    return strata_paint_run("dgrp_paint_strata_batch", d_keys, nrec, h_off, h_len, h_origin, d_rows, h_row_off, d_row_stratum, nullptr, false,
+                            d_work, work_bytes, (hipStream_t)stream_);
+}
+
+DGRP_EXPORT int dgrp_paint_keys_batch(uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                                      const dgrp_segment *d_rows, const int64_t *h_row_off, const uint32_t *d_row_key, void *d_work,
+                                      int64_t work_bytes, void *stream_)
+{
+    return strata_paint_run("dgrp_paint_keys_batch", d_keys, nrec, h_off, h_len, h_origin, d_rows, h_row_off, nullptr, d_row_key, true,
+                            d_work, work_bytes, (hipStream_t)stream_);
 }
 
 DGRP_EXPORT int64_t dgrp_prob_hist_strata_workspace_bytes(int64_t nrec)

@@ -19,7 +19,12 @@ detection score against them (dgrp_paint_row_keys_batch, dgrp_row_detect_batch).
 
 With strata (`evaluate --strata`, deepgrp_amd/strata.py) the probe also paints the truth as (label, stratum) keys and counts the true
 class's probability by them (dgrp_paint_strata_batch, dgrp_prob_hist_strata_batch), and `Accumulator.add` groups the element counts
-it already has by label and stratum."""
+it already has by label and stratum.
+
+With off-target counts (`evaluate --offtarget`, deepgrp_amd/offtarget.py) `Accumulator.add` also paints what the listing says lies
+under every base as keys (dgrp_paint_keys_batch), cross-tabulates the predicted labels against them -- every base, and the bases
+of the unsupported predicted rows alone (dgrp_key_crosstab_batch) -- and takes four counts per predicted row
+(dgrp_row_key_classes_batch).  The runner and the probe are not touched."""
 from __future__ import annotations
 
 import logging
@@ -109,12 +114,13 @@ def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
 class Accumulator:
     """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
 
-    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None):
+    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None, offtarget=None):
         if not 0.0 < min_overlap <= 1.0:
             raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
         self.C, self.theta = int(classes), float(min_overlap)
         self.curves = curves                           # a curves.Curves: probability histograms and rows by score are summed into it
         self.strata = strata                           # a strata.Strata: element counts and histograms by (label, stratum)
+        self.offtarget = offtarget                     # an offtarget.Offtarget: predicted labels by what the listing says is there
         self.cnf = np.zeros((self.C, self.C), np.int64)
         self.elements = np.zeros(self.C, np.int64)
         self.found = np.zeros(self.C, np.int64)
@@ -259,11 +265,13 @@ class Accumulator:
 
     def add(self, origins: Sequence[int], lengths: Sequence[int], pred_rows: Sequence[np.ndarray],
             true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = (),
-            true_strata: Optional[Sequence[np.ndarray]] = None) -> None:
+            true_strata: Optional[Sequence[np.ndarray]] = None, off_rows: Optional[Sequence[np.ndarray]] = None,
+            off_keys: Optional[Sequence[np.ndarray]] = None) -> None:
         """One work item: records r = 0.. with startpos origins[r], kept length lengths[r], the TSV rows `predict` wrote for it
         (original coordinates) and its kept annotation rows.  With curves also the scores of the predicted rows, record after record
         (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names for its error.  With strata also the
-        stratum of every annotation row, record after record as true_rows."""
+        stratum of every annotation row, record after record as true_rows.  With off-target counts also the un-modelled rows of
+        every record and their keys (annotation.Rows.offtarget_rows / offtarget_keys)."""
         import torch
 
         from ._lib import check, lib
@@ -331,6 +339,7 @@ class Accumulator:
                 if true_strata is None or sum(len(x) for x in true_strata) != len(t_flat):
                     raise ValueError(f"{len(t_flat)} annotation rows but {0 if true_strata is None else sum(len(x) for x in true_strata)} strata")
                 self.strata.count(t_flat["label"], np.concatenate(true_strata), np.concatenate(t_clen), ht, ok, hit)
+        kept = good = np.zeros(0, bool)
         if p_flat.size:
             p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(pr)])
             kept, good = self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
@@ -345,6 +354,58 @@ class Accumulator:
                 self.curves.sup += sup
         if self.curves is not None and self.curves.elements and t_flat.size:
             self._detect(ln, org, off, t_off, t_flat, d_trows, np.concatenate(t_clen), p_off, d_prows, scores, names)
+        if self.offtarget is not None:
+            self._offtarget(ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good)
+
+    def _offtarget(self, ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good) -> None:
+        """The off-target share of a work item.  The key track: the item's modelled rows with their labels as keys and its
+        un-modelled rows with 64 + family id (dgrp_paint_keys_batch).  Two cross-tabulations against it (dgrp_key_crosstab_batch):
+        the predicted labels, and a second track painted from only the predicted rows `_count` found unsupported -- of which the
+        label 0, everything outside those rows, is dropped.  Four counts per predicted row (dgrp_row_key_classes_batch)."""
+        import torch
+
+        from ._lib import check, lib
+        from .pipeline import require_gpu, stream_ptr
+        ot, L, dev, s, nrec = self.offtarget, lib(), require_gpu(), stream_ptr(), len(ln)
+        n = int(off[-1])
+        if off_rows is None or off_keys is None or len(off_rows) != nrec or len(off_keys) != nrec:
+            raise ValueError("the off-target counts need the un-modelled rows and keys of every record")
+        k_rows, k_keys = [], []
+        for r in range(nrec):
+            o = np.ascontiguousarray(off_rows[r], SEGMENT_DTYPE)
+            ok = np.ascontiguousarray(off_keys[r], np.uint32)
+            if len(o) != len(ok):
+                raise ValueError(f"{len(o)} un-modelled rows but {len(ok)} keys")
+            k_rows.append(np.concatenate([tr[r], o]))
+            k_keys.append(np.concatenate([tr[r]["label"].astype(np.uint32), ok]))
+        k_off, _k_flat, d_krows = self._upload(k_rows, dev)
+        uns = kept & ~good
+        ur = [p[uns[int(p_off[r]):int(p_off[r + 1])]] for r, p in enumerate(pr)]
+        u_off, _u_flat, d_urows = self._upload(ur, dev)
+        wb = int(L.dgrp_eval_workspace_bytes(nrec, max(int(k_off[-1]), int(p_off[-1]), int(u_off[-1]))))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        d_rk = torch.from_numpy(np.concatenate(k_keys).view(np.int32)).to(dev) if int(k_off[-1]) else None   # (the sign of the type is not read)
+        d_keys = torch.empty(n, dtype=torch.int32, device=dev)                    # (32-bit keys; the sign of the type is not read)
+        check(L.dgrp_paint_keys_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_krows),
+                                      k_off.ctypes.data, ptr(d_rk), work.data_ptr(), wb, s), "dgrp_paint_keys_batch")
+        d_uns = self._paint(ln, org, off, u_off, d_urows, work, dev)
+        d_hist = torch.empty((2, self.C, ot.K), dtype=torch.int64, device=dev)
+        d_bad = torch.empty(2, dtype=torch.int32, device=dev)
+        for k, d_lab in enumerate((d_pred, d_uns)):
+            check(L.dgrp_key_crosstab_batch(d_lab.data_ptr(), d_keys.data_ptr(), n, self.C, ot.K, d_hist[k].data_ptr(), d_bad[k:].data_ptr(), s),
+                  "dgrp_key_crosstab_batch")
+        d_cls = torch.zeros((max(int(p_off[-1]), 1), 4), dtype=torch.int64, device=dev)
+        check(L.dgrp_row_key_classes_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_prows),
+                                           p_off.ctypes.data, d_cls.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_key_classes_batch")
+        hist, bad, cls = d_hist.cpu().numpy(), d_bad.cpu().numpy(), d_cls.cpu().numpy()[:int(p_off[-1])]
+        if bad.any():
+            raise ValueError(f"a predicted label outside 0..{self.C - 1} or a key outside the {ot.F} families of the listing reached the "
+                             "off-target counts")
+        hist[1, 0] = 0
+        ot.hist += hist
+        if p_flat.size:
+            ot.count_rows(p_flat["label"].astype(np.int64), kept, good, cls)
 
     def _detect(self, ln, org, off, t_off, t_flat, d_trows, t_clen, p_off, d_prows, scores, names) -> None:
         """The element curves' share of a work item: the predicted rows painted as keys (label << 10 | BED score) on a zeroed
@@ -407,6 +468,8 @@ def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
         out["curves"] = acc.curves.summary()
     if acc.strata is not None:
         out["strata"] = acc.strata.summary()
+    if acc.offtarget is not None:
+        out["offtarget"] = acc.offtarget.summary()
     return out
 
 
@@ -448,7 +511,7 @@ def record_name(filename: str, header: str) -> str:
 
 def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
              repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None,
-             strata=None) -> Dict[str, object]:
+             strata=None, offtarget=None) -> Dict[str, object]:
     """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
     `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
     content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
@@ -456,7 +519,9 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
     `Accumulator.probe`, the counts of the curves are summed into it and the JSON content gains the key `curves`; without it a
     record is the fused call, as before.  strata (a strata.Strata of the model's classes): the same runner and probe, the counts by
     (label, stratum) are summed into it and the JSON content gains the key `strata`; the divergence of the rows is
-    `annotation.millidiv` (annotation.Rows), -1 everywhere without it."""
+    `annotation.millidiv` (annotation.Rows), -1 everywhere without it.  offtarget (an offtarget.Offtarget of the model's classes
+    and the listing's families): `annotation` is what annotation.evaluation_rows(offtarget=True) returns, the counts are summed
+    into it and the JSON content gains the key `offtarget`; the runner is the one the other arguments choose."""
     from .runner import RecordRunner
 
     classes = int(model.output_shape[2])
@@ -464,7 +529,13 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
         raise ValueError(f"curves of {curves.C} classes for a model of {classes}")
     if strata is not None and strata.C != classes:
         raise ValueError(f"strata of {strata.C} classes for a model of {classes}")
-    acc = Accumulator(classes, min_overlap, curves, strata)
+    if offtarget is not None:
+        if offtarget.C != classes:
+            raise ValueError(f"off-target counts of {offtarget.C} classes for a model of {classes}")
+        if getattr(annotation, "offtarget_rows", None) is None:
+            raise ValueError("off-target counts need the un-modelled rows of a RepeatMasker listing (annotation.evaluation_rows(offtarget=True))")
+    acc = Accumulator(classes, min_overlap, curves, strata, offtarget)
+    no_keys = np.zeros(0, np.uint32)
     probing = curves is not None or strata is not None
     runner = RecordRunner(pipe, scores=True, probe=acc.probe(annotation)) if probing else RecordRunner(pipe)
     empty = np.zeros(0, SEGMENT_DTYPE)
@@ -508,7 +579,9 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
             pred = [rows]
         true = [annotation.get(k[1], empty) for k in keys]
         true_strata = [acc._row_strata(annotation, k[1], t) for k, t in zip(keys, true)] if strata is not None else None
-        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, true, scores, probed, [k[1] for k in keys], true_strata)
+        off_rows = [annotation.offtarget_rows.get(k[1], empty) for k in keys] if offtarget is not None else None
+        off_keys = [annotation.offtarget_keys.get(k[1], no_keys) for k in keys] if offtarget is not None else None
+        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, true, scores, probed, [k[1] for k in keys], true_strata, off_rows, off_keys)
     if acc.rows_used == 0:
         raise NoMatchError("no annotation row names a record of the inputs (records: {}; annotation: {})".format(
             ", ".join(repr(x) for x in seen_names) or "none",

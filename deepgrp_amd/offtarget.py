@@ -1,0 +1,211 @@
+"""`evaluate --offtarget`: what the predicted repeats lie on -- the model's false positives split by what the RepeatMasker listing
+says is there, from integer counts alone.
+
+ROWS.  Every line of the listing that matches a pattern of parse_rm is a row.  A row is MODELLED when `evaluate` keeps it today (its
+number is in --repeats): its key is its label, 1..63.  Every other row is UN-MODELLED: its key is 64 + the id of its class/family
+token, the rank of the token among the distinct tokens of the listing in ascending byte order (annotation.read_listing(all_rows=True)).
+
+KEY OF A BASE.  The smallest key among the rows that cover it, 0xFFFFFFFF where none does: a base under any modelled row has the label
+`evaluate` paints there, an un-modelled family shows only where no modelled row covers, and among several families the first in byte
+order wins (dgrp_paint_keys_batch; `reference_keys` is its numpy statement).
+
+COUNTS.  Per work item `Accumulator.add` cross-tabulates the predicted label of every base against its key, once for all bases and
+once for a track that holds only the predicted rows it found unsupported (dgrp_key_crosstab_batch; `reference_crosstab`), and takes
+per predicted row the bases of its clipped span under its own label, another label, a family, nothing (dgrp_row_key_classes_batch).
+
+Everything here is numpy over int64; the same counts give the same file bytes."""
+from __future__ import annotations
+
+import os
+import sys
+from typing import Dict, List, NamedTuple, Optional, Sequence
+
+import numpy as np
+
+NONE = 0xFFFFFFFF                                   # the key of a base that no row covers
+FIRST_FAMILY = 64                                   # keys below it are labels
+MAX_FAMILIES = 16384                                # DGRP_TOKEN_MAX
+BY = ("family", "class")
+SCOPES = ("all", "unsupported")
+COMMENT = ("# under: a base counts under the smallest key among the listing's rows that cover it -- class<L> for a row of a modelled "
+           "class, which wins over every family; else the class/family token first in byte order; `none` where no row covers it")
+HEADER = ("scope", "predicted", "under", "bases", "share")
+ROWS_HEADER = ("class", "rows", "supported", "mostly_own", "mostly_other_class", "mostly_offtarget", "mostly_unannotated")
+
+
+class OfftargetPlan(NamedTuple):
+    prefix: str
+    by: str
+    table_path: str
+    rows_path: str
+
+
+def plan(args) -> Optional[OfftargetPlan]:
+    """--offtarget and --offtarget_by, or None without --offtarget.  Every refusal is made here (sys.exit), before the model is read
+    or the GPU is touched."""
+    prefix, by = getattr(args, "offtarget", None), getattr(args, "offtarget_by", None)
+    if prefix is None:
+        if by is not None:
+            sys.exit("--offtarget_by needs --offtarget")
+        return None
+    by = BY[0] if by is None else by
+    if by not in BY:
+        sys.exit(f"--offtarget_by: one of {', '.join(BY)}, not {by!r}")
+    if prefix == "" or prefix.endswith(os.sep) or os.path.isdir(prefix):
+        sys.exit(f"--offtarget takes a file name prefix, not the directory {prefix!r}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit("--offtarget runs in one process (WORLD_SIZE > 1 is not supported: the counts are summed on the rank that holds the "
+                 "predicted rows)")
+    where = os.path.dirname(prefix) or "."
+    if not os.path.isdir(where):
+        sys.exit(f"--offtarget: the directory {where} does not exist")
+    paths = (prefix + ".offtarget.tsv", prefix + ".offtarget.rows.tsv")
+    inputs = list(getattr(args, "FASTA", [])) + [getattr(args, k, None) for k in ("annotation", "model")]
+    for f in inputs:
+        for out in paths:
+            if f not in (None, "-") and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
+                sys.exit(f"--offtarget: the file {out} would overwrite the input {f}")
+    from . import annotation
+    ann = getattr(args, "annotation", None)
+    if ann is not None and annotation.resolve_format(ann, getattr(args, "annotation_format", "auto")) == "table":
+        sys.exit(f"--offtarget: {ann} is read as a table of parse_rm, which holds the rows of the modelled classes only; what the other "
+                 "predicted bases lie on is in the RepeatMasker listing itself: give `genome.fa.out`, `genome.fa.out.gz` or a UCSC "
+                 "`rmsk.txt.gz`")
+    return OfftargetPlan(prefix, by, *paths)
+
+
+def reference_keys(origins, lengths, rows, keys) -> List[np.ndarray]:
+    """dgrp_paint_keys_batch in numpy for a list of records (record r: `lengths[r]` bases from the coordinate `origins[r]`, rows[r]
+    its rows with SEGMENT_DTYPE fields -- the label is not read --, keys[r] their keys): -> [key track uint32 per record],
+    0xFFFFFFFF where no row covers a base, else the smallest key among the rows that do."""
+    out = []
+    for r in range(len(lengths)):
+        n, o = int(lengths[r]), int(origins[r])
+        track = np.full(n, NONE, np.uint32)
+        for row, k in zip(rows[r], keys[r]):
+            a, e = min(max(int(row["start"]) - o, 0), n), min(max(int(row["end"]) - o, 0), n)
+            if e > a:
+                track[a:e] = np.minimum(track[a:e], np.uint32(int(k)))
+        out.append(track)
+    return out
+
+
+def reference_crosstab(pred, keys, C: int, K: int):
+    """dgrp_key_crosstab_batch in numpy: `pred` int8 [n], `keys` uint32 [n] -> (hist int64 [C, K], flag).  hist[p, k] counts the
+    bases with predicted label p and key k < K - 1, hist[p, K - 1] those with the key 0xFFFFFFFF; any other key, or a label outside
+    0 .. C - 1, raises the flag and the base is not counted."""
+    p = np.asarray(pred, np.int8).astype(np.int64).ravel()
+    k = np.asarray(keys, np.uint32).astype(np.int64).ravel()
+    col = np.where(k == NONE, K - 1, k)
+    ok = (p >= 0) & (p < C) & ((k == NONE) | (k < K - 1))
+    hist = np.zeros((C, K), np.int64)
+    np.add.at(hist, (p[ok], col[ok]), 1)
+    return hist, int(bool((~ok).any()))
+
+
+def reference_row_classes(keys, label: int) -> np.ndarray:
+    """dgrp_row_key_classes_batch for one row: the keys of its clipped span -> int64 [4]: key == label; another key below 64; a
+    family; 0xFFFFFFFF."""
+    k = np.asarray(keys, np.uint32).astype(np.int64)
+    return np.array([(k == label).sum(), ((k < FIRST_FAMILY) & (k != label)).sum(), ((k >= FIRST_FAMILY) & (k != NONE)).sum(),
+                     (k == NONE).sum()], np.int64)
+
+
+def fold(names: Sequence[str], by: str) -> List[str]:
+    """The name a family token is listed under: itself, or with by == "class" its part in front of the first '/'."""
+    return list(names) if by == "family" else [nm.split("/", 1)[0] for nm in names]
+
+
+def _under(hist: np.ndarray, families: Sequence[str], by: str):
+    """hist int64 [..., K] -> (names, int64 [..., len(names)]): class<L> for the keys 1..63, the (folded) family names in byte order,
+    `none`; columns of one folded name are summed."""
+    hist = np.asarray(hist, np.int64)
+    F = len(families)
+    if hist.shape[-1] != FIRST_FAMILY + F + 1:
+        raise ValueError(f"{hist.shape[-1]} key columns for {F} families")
+    folded = fold(families, by)
+    uniq = sorted(set(folded), key=lambda s: s.encode("utf-8", "surrogateescape"))
+    at = {nm: i for i, nm in enumerate(uniq)}
+    fam = np.zeros(hist.shape[:-1] + (len(uniq),), np.int64)
+    if F:
+        np.add.at(fam, (Ellipsis, np.fromiter((at[nm] for nm in folded), np.int64, count=F)), hist[..., FIRST_FAMILY:FIRST_FAMILY + F])
+    names = [f"class{k}" for k in range(FIRST_FAMILY)] + uniq + ["none"]
+    return names, np.concatenate([hist[..., :FIRST_FAMILY], fam, hist[..., -1:]], axis=-1)
+
+
+def offtarget_tsv(hist: np.ndarray, families: Sequence[str], by: str = "family") -> str:
+    """PREFIX.offtarget.tsv of hist int64 [2, C, K] (scope all / unsupported): the comment, the header, and per scope and predicted
+    label the names with bases > 0 -- bases descending, then the name in byte order -- with their share of that (scope, predicted)
+    to six decimals."""
+    names, x = _under(hist, families, by)
+    raw = [nm.encode("utf-8", "surrogateescape") for nm in names]
+    lines = [COMMENT, "\t".join(HEADER)]
+    for s, scope in enumerate(SCOPES):
+        for p in range(x.shape[1]):
+            total = int(x[s, p].sum())
+            for k in sorted(np.flatnonzero(x[s, p]).tolist(), key=lambda k: (-int(x[s, p, k]), raw[k])):
+                lines.append("\t".join([scope, str(p), names[k], str(int(x[s, p, k])), f"{int(x[s, p, k]) / total:.6f}"]))
+    return "\n".join(lines) + "\n"
+
+
+def rows_tsv(rows: np.ndarray) -> str:
+    """PREFIX.offtarget.rows.tsv of rows int64 [C, 6]: per predicted class >= 1 its rows, the supported ones, and the unsupported ones
+    by the largest of their four counts."""
+    rows = np.asarray(rows, np.int64)
+    lines = ["\t".join(ROWS_HEADER)]
+    for c in range(1, rows.shape[0]):
+        lines.append("\t".join([str(c)] + [str(int(v)) for v in rows[c]]))
+    return "\n".join(lines) + "\n"
+
+
+class Offtarget:
+    """The counts of one `evaluate --offtarget` run, summed over its work items: `hist` int64 [2, C, K] (scope all / unsupported:
+    predicted label by key column, K = 64 + F + 1) and `rows` int64 [C, 6] (ROWS_HEADER behind the class)."""
+
+    def __init__(self, classes: int, families: Sequence[str], by: str = "family"):
+        if by not in BY:
+            raise ValueError(f"by: one of {BY}, not {by!r}")
+        if len(families) > MAX_FAMILIES:
+            raise ValueError(f"{len(families)} families: at most {MAX_FAMILIES}")
+        self.C, self.by, self.families = int(classes), by, list(families)
+        self.F = len(self.families)
+        self.K = FIRST_FAMILY + self.F + 1
+        self.hist = np.zeros((2, self.C, self.K), np.int64)
+        self.rows = np.zeros((self.C, 6), np.int64)
+
+    def count_rows(self, labels: np.ndarray, kept: np.ndarray, good: np.ndarray, cls: np.ndarray) -> None:
+        """The predicted rows of a work item: `kept` has a base inside its record, `good` is supported (Accumulator._count's masks),
+        cls int64 [rows, 4] the four counts.  An unsupported row goes to the largest of its counts, ties to the first."""
+        lab = np.asarray(labels, np.int64)
+        np.add.at(self.rows[:, 0], lab[kept], 1)
+        np.add.at(self.rows[:, 1], lab[good], 1)
+        uns = kept & ~good
+        if uns.any():
+            np.add.at(self.rows, (lab[uns], 2 + np.argmax(np.asarray(cls, np.int64)[uns], axis=1)), 1)
+
+    def summary(self) -> Dict[str, object]:
+        """The `offtarget` key of the JSON report: per class its unsupported rows' bases split three ways -- under a modelled class,
+        under an un-modelled family, under nothing -- as shares (None without such bases), and its three largest families."""
+        names, x = _under(self.hist[1], self.families, self.by)
+        fam = x[:, FIRST_FAMILY:-1]
+        out = []
+        for c in range(self.C):
+            total = int(x[c].sum())
+            share = lambda v: None if total == 0 else int(v) / total
+            top = sorted(np.flatnonzero(fam[c]).tolist(), key=lambda k: (-int(fam[c, k]), names[FIRST_FAMILY + k].encode("utf-8", "surrogateescape")))[:3]
+            out.append(dict(unsupported_bases=total, modelled=share(x[c, :FIRST_FAMILY].sum()), offtarget=share(fam[c].sum()),
+                            unannotated=share(x[c, -1]), top=[[names[FIRST_FAMILY + k], int(fam[c, k])] for k in top]))
+        return dict(by=self.by, families=self.F, classes=out)
+
+    def write(self, p: OfftargetPlan, log) -> None:
+        """The two files, staged: a failure leaves neither of them, nor a temporary file."""
+        from .outfiles import StagedFile, StagedOutputs
+        texts = [offtarget_tsv(self.hist, self.families, self.by), rows_tsv(self.rows)]
+        out = StagedOutputs(log, p.prefix, "--offtarget", False, (StagedFile(f, "w") for f in (p.table_path, p.rows_path)))
+        try:
+            for part, text in zip(out.parts, texts):
+                part.fh.write(text)
+        except BaseException:
+            out.abort()
+            raise
+        out.commit()

@@ -1097,6 +1097,66 @@ int dgrp_rm_parse_fields(const uint8_t *d_text, int64_t n, const uint8_t *d_name
                          int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
                          int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream);
 
+/* dgrp_rm_parse_all: the same two passes with EVERY line that matches one of the two patterns kept as a row, whatever its number:
+ * d_number[i] is 0 where the numbering rule above finds none.  The arrays of dgrp_rm_parse_fields, and the family token of row i as
+ * spans of d_text: d_fam_pos[i] / d_fam_len[i] (`.out`: token 10; `rmsk`: field 11) and d_fam2_pos[i] / d_fam2_len[i], the second
+ * piece of the logical string `field 11` '/' `field 12` where the two fields differ -- length 0 for `.out` and where they are
+ * byte-equal (the position is then that of the first span).  The strings are compared in place and never joined.  Its rows with
+ * d_number > 0 are the rows of dgrp_rm_parse_fields in the same order with the same values.  Counts, the not-plain flag (a family
+ * token the int32 length cannot state raises it too), DGRP_ENOMEM with the need in h_counts[1], the runs, the refusals and the two
+ * synchronisations are those of dgrp_rm_parse; n / 22 + 1 rows still suffice.  Workspace: dgrp_rm_parse_all_workspace_bytes(n). */
+int64_t dgrp_rm_parse_all_workspace_bytes(int64_t n);
+int dgrp_rm_parse_all(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, int nnames,
+                      const uint8_t *d_pentamers, int unit_number, int64_t *d_begin, int64_t *d_end, int32_t *d_number,
+                      int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int32_t *d_millidiv,
+                      int64_t *d_fam_pos, int32_t *d_fam_len, int64_t *d_fam2_pos, int32_t *d_fam2_len, int64_t cap, int64_t *h_counts,
+                      void *d_work, int64_t work_bytes, void *stream);
+
+/* ---- off-target (an addition, evaluate --offtarget): what the predicted repeats lie on.
+ * dgrp_token_ids: dense ids for `rows` tokens given as spans of d_text [n] (device).  Token i is the bytes d_pos[i] .. + d_len[i],
+ * and with d_len2[i] > 0 the logical string of those bytes, '/', and the bytes d_pos2[i] .. + d_len2[i]; a one-span and a two-span
+ * spelling of one string are one token.  d_fid[i] (device int32) = the rank of token i among the DISTINCT tokens in ascending byte
+ * order (memcmp; a proper prefix first), from 0.  h_counts[3] (host): F = the number of distinct tokens, the overflow flag, the
+ * bytes of the F strings back to back.  h_names [names_cap] / h_name_off [DGRP_TOKEN_MAX + 1] (host): those strings in id order.
+ * An open-addressing table of DGRP_TOKEN_SLOTS 64-bit words in the workspace, EMPTY or the row that claimed the slot (one
+ * atomicCAS); a row that meets a taken slot compares its own bytes with the claimant's and takes the slot when they are equal, else
+ * probes on: exact, the hash is only where the search starts.  Which row claims a slot depends on timing, the token the slot stands
+ * for does not: the same call gives the same d_fid bytes.  More than DGRP_TOKEN_MAX distinct tokens: h_counts[1] = 1, no id and no
+ * name is written, DGRP_OK (the caller numbers such a file on the host).  DGRP_EINVAL: a span that leaves the text (checked on the
+ * device before a byte of it is read), NULL pointers with rows > 0; DGRP_ENOMEM: a workspace (256-byte aligned) below
+ * dgrp_token_ids_workspace_bytes(rows, names_cap), or names of more than names_cap bytes (h_counts[2] tells the need).  It
+ * SYNCHRONISES the stream three times: the count and the representative spans (one copy), the strings (one copy; the host sorts
+ * them), and behind the kernel that writes d_fid.  rows == 0: zero counts, no device work. */
+#define DGRP_TOKEN_SLOTS 65536
+#define DGRP_TOKEN_MAX 16384
+int64_t dgrp_token_ids_workspace_bytes(int64_t rows, int64_t names_cap);
+int dgrp_token_ids(const uint8_t *d_text, int64_t n, int64_t rows, const int64_t *d_pos, const int32_t *d_len, const int64_t *d_pos2,
+                   const int32_t *d_len2, int32_t *d_fid, uint8_t *h_names, int64_t names_cap, int64_t *h_name_off, int64_t *h_counts,
+                   void *d_work, int64_t work_bytes, void *stream);
+/* dgrp_paint_keys_batch: dgrp_paint_strata_batch (one body) with an arbitrary key per row: d_row_key[i] (device uint32) is the key
+ * of row d_rows[i], whose own label is NOT read.  Every element of d_keys[0 .. h_off[nrec]) is written: 0xFFFFFFFF where no row
+ * covers the base, else the smallest key among the rows that do.  DGRP_EINVAL before anything is written unless every row has
+ * 0 <= start <= end and a key below 0xFFFFFFFF (one check kernel, one synchronisation).  Workspace: dgrp_eval_workspace_bytes.
+ * dgrp_key_crosstab_batch: d_pred (int8) and d_keys (uint32, 4-byte aligned) are flat tracks of n bases, laid out as for
+ * dgrp_confusion_matrix.  For every base, d_hist[p][k'] += 1 (device int64 [C][K], 8-byte aligned) with k' = key for key < K - 1 and
+ * k' = K - 1 for 0xFFFFFFFF (K = 64 + F + 1).  Any other key, or p outside 0 .. C - 1, sets *d_bad (device int) and the base is not
+ * counted; the call still returns DGRP_OK.  d_hist and *d_bad are zeroed on every call.  32-bit counters in LDS, sized so that none
+ * can wrap, flushed with 64-bit atomic adds; where C * K counters exceed 160 KiB the cells are cut into groups of 40960 along
+ * grid.y and every group reads every base: the bytes do not depend on the cut.  Stream-ordered: nothing synchronises.  DGRP_EINVAL
+ * unless 1 <= C <= 64, 65 <= K <= 64 + DGRP_TOKEN_MAX + 1, 0 <= n < 2^40.
+ * dgrp_row_key_classes_batch: rows, records, checks (labels 1..63), workspace and balancing by clipped length as for
+ * dgrp_row_hits_batch, against a uint32 key track.  For row i with label L, d_cls[4 * i .. 4 * i + 4) (device int64) = the bases
+ * of its clipped span with key == L; key < 64 and != L; 64 <= key < 0xFFFFFFFF; key == 0xFFFFFFFF.  Integer sums: the four add up
+ * to the clipped length. */
+int dgrp_paint_keys_batch(uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                          const dgrp_segment *d_rows, const int64_t *h_row_off, const uint32_t *d_row_key, void *d_work,
+                          int64_t work_bytes, void *stream);
+int dgrp_key_crosstab_batch(const int8_t *d_pred, const uint32_t *d_keys, int64_t n, int C, int64_t K, int64_t *d_hist, int *d_bad,
+                            void *stream);
+int dgrp_row_key_classes_batch(const uint32_t *d_keys, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                               const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_cls, void *d_work, int64_t work_bytes,
+                               void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
