@@ -38,6 +38,9 @@ Differences, all additive:
   * `evaluate --offtarget PREFIX` also writes what the predicted repeats lie on, PREFIX.offtarget.tsv (predicted label by modelled
     class, RepeatMasker class/family or nothing, for all bases and for the unsupported rows) and PREFIX.offtarget.rows.tsv, from
     every row of the listing and counts made on the GPU (deepgrp_amd/offtarget.py);
+  * `evaluate --boundaries PREFIX` also writes how well the found elements are delimited, PREFIX.boundaries.tsv (the offset of
+    either edge, annotation rows against the predicted labels and predicted rows against the truth) and PREFIX.fragments.tsv (the
+    runs under a row), from counts made on the GPU (deepgrp_amd/boundaries.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -431,6 +434,17 @@ class CommandLineParser:
         evaluate.add_argument("--offtarget_by", choices=("family", "class"), default=None,
                               help="names of PREFIX.offtarget.tsv: the class/family token (default with --offtarget) or its part in "
                                    "front of the first '/'")
+        evaluate.add_argument("--boundaries", type=str, default=None, metavar="PREFIX",
+                              help="also write how well the found elements are delimited: PREFIX.boundaries.tsv (per view, class and "
+                                   "side the offset between the row's edge and the other track's run, in bases) and "
+                                   "PREFIX.fragments.tsv (per view and class the rows by the runs under them); view `element` takes "
+                                   "the annotation rows against the predicted labels, view `row` the predicted rows against the "
+                                   "truth; --json gains the key `boundaries`")
+        evaluate.add_argument("--boundary_max", type=int, default=None, metavar="W",
+                              help="largest offset of --boundaries that is told apart, 1..4096 bases (default with --boundaries: 200)")
+        evaluate.add_argument("--boundary_join", type=int, default=None, metavar="G",
+                              help="element view of --boundaries: annotation rows of one record and class at most G >= 0 bases apart "
+                                   "(abutting and overlapping rows included) count as one element (default: the rows as they are)")
         evaluate.add_argument("--strata_div", type=str, default=None,
                               help="divergence edges of --strata in percent, ascending, 1..15 of them, one decimal allowed "
                                    "(default with --strata: 5,10,15,20,25,30)")
@@ -1127,6 +1141,8 @@ class CommandLineParser:
         strata_plan = dgstrata.plan(args)
         from . import offtarget as dgofftarget
         offtarget_plan = dgofftarget.plan(args)
+        from . import boundaries as dgboundaries
+        boundary_plan = dgboundaries.plan(args)
         import json
 
         from . import model as dgmodel
@@ -1159,11 +1175,14 @@ class CommandLineParser:
         curves = dgcurves.Curves(classes, curve_plan.bins, curve_plan.elements_path is not None) if curve_plan is not None else None
         strata = dgstrata.Strata(classes, strata_plan.div_edges, strata_plan.len_edges, strata_plan.bins) if strata_plan is not None else None
         offtarget = dgofftarget.Offtarget(classes, annotation.families, offtarget_plan.by) if offtarget_plan is not None else None
+        boundaries = dgboundaries.Boundaries(classes, boundary_plan.W, boundary_plan.join) if boundary_plan is not None else None
         try:
             rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves,
-                           strata, offtarget)
+                           strata, offtarget, boundaries)
         except NoMatchError as e:
             sys.exit(str(e))
+        if boundaries is not None:
+            boundaries.write(boundary_plan, _LOG)
         if curves is not None:
             curves.write(curve_plan, _LOG)
         if strata is not None:

@@ -178,6 +178,10 @@ _SIGNATURES = {
     "dgrp_paint_keys_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_key_crosstab_batch": (cint, [vp, vp, i64, cint, i64, vp, vp, vp]),
     "dgrp_row_key_classes_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "dgrp_row_bounds_workspace_bytes": (i64, [i64, i64]),
+    "dgrp_row_bounds_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, cint, vp, vp, i64, vp]),
+    "dgrp_bound_hist_workspace_bytes": (i64, [i64]),
+    "dgrp_bound_hist_batch": (cint, [i64, vp, vp, vp, vp, vp, vp, vp, cint, cint, vp, vp, vp, vp, vp, i64, vp]),
     "dgrp_kernel_timer_enable": (cint, [cint]),
     "dgrp_kernel_timer_read": (cint, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]),
 }

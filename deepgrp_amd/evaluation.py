@@ -24,7 +24,12 @@ it already has by label and stratum.
 With off-target counts (`evaluate --offtarget`, deepgrp_amd/offtarget.py) `Accumulator.add` also paints what the listing says lies
 under every base as keys (dgrp_paint_keys_batch), cross-tabulates the predicted labels against them -- every base, and the bases
 of the unsupported predicted rows alone (dgrp_key_crosstab_batch) -- and takes four counts per predicted row
-(dgrp_row_key_classes_batch).  The runner and the probe are not touched."""
+(dgrp_row_key_classes_batch).  The runner and the probe are not touched.
+
+With boundaries (`evaluate --boundaries`, deepgrp_amd/boundaries.py) `Accumulator.add` also takes, for the annotation rows against
+the predicted labels and for the predicted rows against the truth, the runs, the first and last matching base and the two flanks of
+every row (dgrp_row_bounds_batch) and counts them into the edge-offset and fragment tables (dgrp_bound_hist_batch); only the tables
+come back.  The runner and the probe are not touched."""
 from __future__ import annotations
 
 import logging
@@ -114,13 +119,14 @@ def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
 class Accumulator:
     """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
 
-    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None, offtarget=None):
+    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None, offtarget=None, boundaries=None):
         if not 0.0 < min_overlap <= 1.0:
             raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
         self.C, self.theta = int(classes), float(min_overlap)
         self.curves = curves                           # a curves.Curves: probability histograms and rows by score are summed into it
         self.strata = strata                           # a strata.Strata: element counts and histograms by (label, stratum)
         self.offtarget = offtarget                     # an offtarget.Offtarget: predicted labels by what the listing says is there
+        self.boundaries = boundaries                   # a boundaries.Boundaries: edge offsets and runs of both views
         self.cnf = np.zeros((self.C, self.C), np.int64)
         self.elements = np.zeros(self.C, np.int64)
         self.found = np.zeros(self.C, np.int64)
@@ -356,6 +362,47 @@ class Accumulator:
             self._detect(ln, org, off, t_off, t_flat, d_trows, np.concatenate(t_clen), p_off, d_prows, scores, names)
         if self.offtarget is not None:
             self._offtarget(ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good)
+        if self.boundaries is not None:
+            self._boundaries(ln, org, off, tr, t_off, d_trows, pr, p_off, d_prows, d_true, d_pred)
+
+    def _boundaries(self, ln, org, off, tr, t_off, d_trows, pr, p_off, d_prows, d_true, d_pred) -> None:
+        """The boundaries' share of a work item, once per view: the element view takes the annotation rows (joined into units with
+        --boundary_join, uploaded anew then) against the predicted labels, the row view the predicted rows against the truth.
+        Per view dgrp_row_bounds_batch, then dgrp_bound_hist_batch with need = ceil(theta * clipped length); the three tables and
+        the flag are all that is copied back."""
+        import torch
+
+        from ._lib import check, lib
+        from .boundaries import FRAG
+        from .curves import need_of
+        from .pipeline import require_gpu, stream_ptr
+        bd, L, dev, s, nrec = self.boundaries, lib(), require_gpu(), stream_ptr(), len(ln)
+        W, C = bd.W, self.C
+        if bd.join is not None:
+            tr = [bd.units(t) for t in tr]
+            t_off, _t_flat, d_trows = self._upload(tr, dev)
+        for view, (rows, ro, d_rows, d_labels) in enumerate(((tr, t_off, d_trows, d_pred), (pr, p_off, d_prows, d_true))):
+            nrows = int(ro[-1])
+            if nrows == 0:
+                continue
+            clen = np.concatenate([clipped_lengths(q, int(org[r]), int(ln[r])) for r, q in enumerate(rows)])
+            d_need = torch.from_numpy(need_of(self.theta, clen)).to(dev)
+            wb = int(L.dgrp_row_bounds_workspace_bytes(nrec, nrows))
+            work = torch.empty(max(wb, int(L.dgrp_bound_hist_workspace_bytes(nrec)), 1), dtype=torch.uint8, device=dev)
+            d_bounds = torch.empty((nrows, 5), dtype=torch.int64, device=dev)          # (dgrp_row_bound: 40 bytes a row)
+            check(L.dgrp_row_bounds_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_rows.data_ptr(),
+                                          ro.ctypes.data, W, d_bounds.data_ptr(), work.data_ptr(), work.numel(), s), "dgrp_row_bounds_batch")
+            d_frag = torch.empty((C, FRAG), dtype=torch.int64, device=dev)
+            d_edge = torch.empty((C, 2, 2 * W + 1), dtype=torch.int64, device=dev)
+            d_tally = torch.empty((C, 2), dtype=torch.int64, device=dev)
+            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+            check(L.dgrp_bound_hist_batch(nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_rows.data_ptr(), ro.ctypes.data,
+                                          d_bounds.data_ptr(), d_need.data_ptr(), C, W, d_frag.data_ptr(), d_edge.data_ptr(),
+                                          d_tally.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), s), "dgrp_bound_hist_batch")
+            frag, edge, tally, bad = d_frag.cpu().numpy(), d_edge.cpu().numpy(), d_tally.cpu().numpy(), int(d_bad.item())
+            if bad:
+                raise ValueError(f"a row label outside 0..{C - 1} reached the boundary counts")
+            bd.count(view, frag, edge, tally)
 
     def _offtarget(self, ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good) -> None:
         """The off-target share of a work item.  The key track: the item's modelled rows with their labels as keys and its
@@ -470,6 +517,8 @@ def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
         out["strata"] = acc.strata.summary()
     if acc.offtarget is not None:
         out["offtarget"] = acc.offtarget.summary()
+    if acc.boundaries is not None:
+        out["boundaries"] = acc.boundaries.summary()
     return out
 
 
@@ -511,7 +560,7 @@ def record_name(filename: str, header: str) -> str:
 
 def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
              repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None,
-             strata=None, offtarget=None) -> Dict[str, object]:
+             strata=None, offtarget=None, boundaries=None) -> Dict[str, object]:
     """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
     `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
     content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
@@ -521,7 +570,9 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
     (label, stratum) are summed into it and the JSON content gains the key `strata`; the divergence of the rows is
     `annotation.millidiv` (annotation.Rows), -1 everywhere without it.  offtarget (an offtarget.Offtarget of the model's classes
     and the listing's families): `annotation` is what annotation.evaluation_rows(offtarget=True) returns, the counts are summed
-    into it and the JSON content gains the key `offtarget`; the runner is the one the other arguments choose."""
+    into it and the JSON content gains the key `offtarget`; the runner is the one the other arguments choose.  boundaries (a
+    boundaries.Boundaries of the model's classes): the edge offsets and runs of both views are summed into it and the JSON content
+    gains the key `boundaries`; the runner is the one the other arguments choose."""
     from .runner import RecordRunner
 
     classes = int(model.output_shape[2])
@@ -534,7 +585,9 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
             raise ValueError(f"off-target counts of {offtarget.C} classes for a model of {classes}")
         if getattr(annotation, "offtarget_rows", None) is None:
             raise ValueError("off-target counts need the un-modelled rows of a RepeatMasker listing (annotation.evaluation_rows(offtarget=True))")
-    acc = Accumulator(classes, min_overlap, curves, strata, offtarget)
+    if boundaries is not None and boundaries.C != classes:
+        raise ValueError(f"boundaries of {boundaries.C} classes for a model of {classes}")
+    acc = Accumulator(classes, min_overlap, curves, strata, offtarget, boundaries)
     no_keys = np.zeros(0, np.uint32)
     probing = curves is not None or strata is not None
     runner = RecordRunner(pipe, scores=True, probe=acc.probe(annotation)) if probing else RecordRunner(pipe)

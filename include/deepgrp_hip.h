@@ -1157,6 +1157,44 @@ int dgrp_row_key_classes_batch(const uint32_t *d_keys, int64_t nrec, const int64
                                const dgrp_segment *d_rows, const int64_t *h_row_off, int64_t *d_cls, void *d_work, int64_t work_bytes,
                                void *stream);
 
+/* ---- boundaries (an addition, evaluate --boundaries): how well a found element is delimited -- edge offsets and fragmentation.
+ * dgrp_row_bounds_batch: records, track, rows, the row check (labels 1..127, one synchronisation, DGRP_EINVAL before anything is
+ * written) and the balancing as for dgrp_row_hits_batch.  For row i with label L and clipped span [a, e) of a record of n bases from
+ * coordinate o, with in(b) = "the track byte at coordinate b equals L":
+ *   hits  = #{b in [a, e) : in(b)}                                    -- what dgrp_row_hits_batch gives
+ *   runs  = #{b in [a, e) : in(b) and (b == a or !in(b - 1))}
+ *   first / last = the smallest / largest b in [a, e) with in(b), in ORIGINAL coordinates; -1 when hits == 0
+ *   lead  = the largest k <= min(W, a - o) with in(a - j) for every j = 1..k
+ *   trail = the largest k <= min(W, o + n - e) with in(e - 1 + j) for every j = 1..k
+ * and hits = runs = lead = trail = 0, first = last = -1 for an empty clipped span.  d_bounds[i] (8-byte aligned) is written for i in
+ * [h_row_off[0], h_row_off[nrec]) and nowhere else.  0 <= W <= 4096, else DGRP_EINVAL.  One pass over the line of positions of the
+ * WIDENED spans -- a row contributes min(W, a - o) + (e - a) + min(W, o + n - e) positions, 1 byte read per position, workgroups take
+ * slices of 8192 positions -- between two one-lane-per-row kernels; no flank reads outside its record.  Integer adds, minima and
+ * maxima: the same bytes on every run.  Workspace dgrp_row_bounds_workspace_bytes(nrec, rows), DGRP_ENOMEM below it.  After the row
+ * check the entry is stream-ordered and allocates nothing.  nrec == 0 or no rows: no device work.
+ * dgrp_bound_hist_batch: the rows and record tables of that call, its d_bounds, d_need (device int64 per row, read for i in
+ * [h_row_off[0], h_row_off[nrec]) as dgrp_row_detect_batch reads it), 2 <= C <= 64 and the same W.  d_frag int64 [C][17], d_edge int64
+ * [C][2][2W + 1], d_tally int64 [C][2] (8-byte aligned) and *d_bad (device int) are zeroed, then for every row with a non-empty
+ * clipped span and label L: d_frag[L][min(runs, 16)] += 1; the row is FOUND when d_need[i] > 0 && hits >= d_need[i]; a found row adds
+ * 1 to d_tally[L][0], has the offsets
+ *   ds = first > a ? min(first - a, W) : -lead         de = last + 1 < e ? -min(e - 1 - last, W) : trail
+ * (negative ds, positive de: the track's run sticks out beyond the row; +-W: W or more), adds 1 to d_edge[L][0][ds + W] unless the
+ * record clipped its start (start < o), 1 to d_edge[L][1][de + W] unless the record clipped its end (end > o + n), and 1 to
+ * d_tally[L][1] when neither side is clipped and ds == de == 0.  A label outside 0..C-1 (or bounds taken with a larger W) sets
+ * *d_bad and the row is not counted; the call still returns DGRP_OK.  One lane per row, 32-bit counters in LDS (the edge offsets
+ * where C * 2 * (2W + 1) of them fit 64 KiB beside the others, else added to d_edge directly), flushed with 64-bit atomic adds.
+ * Stream-ordered: nothing synchronises, no row is checked.  Workspace dgrp_bound_hist_workspace_bytes(nrec) (the record tables),
+ * DGRP_ENOMEM below it.  No rows: the outputs are zeroed, nothing else runs. */
+typedef struct { int64_t hits, runs, first, last; int32_t lead, trail; } dgrp_row_bound;   /* 40 bytes */
+int64_t dgrp_row_bounds_workspace_bytes(int64_t nrec, int64_t nrows);
+int dgrp_row_bounds_batch(const int8_t *d_labels, int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin,
+                          const dgrp_segment *d_rows, const int64_t *h_row_off, int W, dgrp_row_bound *d_bounds, void *d_work,
+                          int64_t work_bytes, void *stream);
+int64_t dgrp_bound_hist_workspace_bytes(int64_t nrec);
+int dgrp_bound_hist_batch(int64_t nrec, const int64_t *h_off, const int64_t *h_len, const int64_t *h_origin, const dgrp_segment *d_rows,
+                          const int64_t *h_row_off, const dgrp_row_bound *d_bounds, const int64_t *d_need, int C, int W, int64_t *d_frag,
+                          int64_t *d_edge, int64_t *d_tally, int *d_bad, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- instrumentation (bench.py's roofline figure; no counterpart in the reference, no effect on results).
  * While enabled for the CALLING HOST THREAD, every launch of a recurrent forward kernel (GRU / LSTM, fused or split) that this
  * thread makes through any entry point above is bracketed by two HIP events on the launch's stream.  dgrp_kernel_timer_read waits
