@@ -1135,14 +1135,9 @@ class CommandLineParser:
         refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
-        from . import curves as dgcurves
-        curve_plan = dgcurves.plan(args)
-        from . import strata as dgstrata
-        strata_plan = dgstrata.plan(args)
-        from . import offtarget as dgofftarget
-        offtarget_plan = dgofftarget.plan(args)
-        from . import boundaries as dgboundaries
-        boundary_plan = dgboundaries.plan(args)
+        from . import boundaries as dgboundaries, curves as dgcurves, offtarget as dgofftarget, strata as dgstrata
+        # the reports that were asked for, in the order of their JSON keys; every plan refuses what it must before the model is read
+        plans = [(m, p) for m in (dgcurves, dgstrata, dgofftarget, dgboundaries) for p in [m.plan(args)] if p is not None]
         import json
 
         from . import model as dgmodel
@@ -1159,7 +1154,7 @@ class CommandLineParser:
         try:
             # a table is read here, before the device is touched; a RepeatMasker listing is parsed ON the device (the model's class
             # check above still comes first)
-            if offtarget_plan is not None:
+            if any(m is dgofftarget for m, _p in plans):
                 annotation = dgann.evaluation_rows(args.annotation, repeats, offtarget=True)
             else:
                 annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else read_annotation(args.annotation, repeats)
@@ -1172,23 +1167,13 @@ class CommandLineParser:
                     options=dict(step_size=args.step_size, min_mss_length=args.min_mss_length, xdrop_length=args.xdrop_length,
                                  batch_size=args.batch_size, use_mss=not args.no_use_mss, fast=bool(args.fast),
                                  min_overlap=args.min_overlap))
-        curves = dgcurves.Curves(classes, curve_plan.bins, curve_plan.elements_path is not None) if curve_plan is not None else None
-        strata = dgstrata.Strata(classes, strata_plan.div_edges, strata_plan.len_edges, strata_plan.bins) if strata_plan is not None else None
-        offtarget = dgofftarget.Offtarget(classes, annotation.families, offtarget_plan.by) if offtarget_plan is not None else None
-        boundaries = dgboundaries.Boundaries(classes, boundary_plan.W, boundary_plan.join) if boundary_plan is not None else None
+        reports = [m.from_plan(p, classes, annotation) for m, p in plans]
         try:
-            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, curves,
-                           strata, offtarget, boundaries)
+            rep = evaluate(model, annotation, ((f, _records_of(f)) for f in args.FASTA), pipe, repeats, args.min_overlap, info, reports)
         except NoMatchError as e:
             sys.exit(str(e))
-        if boundaries is not None:
-            boundaries.write(boundary_plan, _LOG)
-        if curves is not None:
-            curves.write(curve_plan, _LOG)
-        if strata is not None:
-            strata.write(strata_plan, _LOG)
-        if offtarget is not None:
-            offtarget.write(offtarget_plan, _LOG)
+        for r, (_m, p) in zip(reports, plans):
+            r.write(p, _LOG)
         text = tsv_report(rep)
         if args.output == "-":
             sys.stdout.write(text)

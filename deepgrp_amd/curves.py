@@ -14,15 +14,21 @@ with m: an element has one detection score d, the largest m at which the --min_o
 `found` at every m is a suffix sum of the histogram of d (dgrp_paint_row_keys_batch and dgrp_row_detect_batch; `reference_detect`
 is their numpy statement).
 
-Everything here is numpy over int64; the same counts give the same file bytes."""
+ON THE DEVICE (`Curves`, a report of deepgrp_amd/evaluation.py).  The runner keeps the merged probabilities of every work item long
+enough for `Curves.probe`: it paints the item's truth on the worker's stream and counts every probability into the per-class
+histograms split by truth; the rows' BED scores come with the rows (dgrp_row_scores_batch).  With element curves `Curves.add` also
+paints the predicted rows as (label, score) keys and takes every annotation row's detection score against them.
+
+Everything else here is numpy over int64; the same counts give the same file bytes."""
 from __future__ import annotations
 
 import math
-import os
 import sys
 from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
+
+from .outfiles import plan_prefix, write_texts
 
 MIN_BINS, MAX_BINS, DEFAULT_BINS = 2, 4096, 1000
 SCORES = 1001                                       # BED scores 0..1000
@@ -54,20 +60,15 @@ def plan(args) -> Optional[CurvePlan]:
     bins = DEFAULT_BINS if bins is None else bins
     if not MIN_BINS <= bins <= MAX_BINS:
         sys.exit(f"--curve_bins must lie in {MIN_BINS}..{MAX_BINS}, not {bins}")
-    if prefix == "" or prefix.endswith(os.sep):
-        sys.exit(f"--curves takes a file name prefix, not the directory {prefix!r}")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("--curves runs in one process (WORLD_SIZE > 1 is not supported: the histograms are summed on the rank that holds "
-                 "the merged probabilities)")
-    where = os.path.dirname(prefix) or "."
-    if not os.path.isdir(where):
-        sys.exit(f"--curves: the directory {where} does not exist")
-    paths = (prefix + ".bases.tsv", prefix + ".rows.tsv") + ((prefix + ".elements.tsv",) if elements else ())
-    for f in getattr(args, "FASTA", []):
-        for out in paths:
-            if f != "-" and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
-                sys.exit(f"--curves: the file {out} would overwrite the input {f}")
+    # (unlike the other reports: a prefix that exists as a directory passes, and only the FASTA inputs are guarded)
+    paths = plan_prefix("--curves", prefix, (".bases.tsv", ".rows.tsv") + ((".elements.tsv",) if elements else ()), args,
+                        "the histograms are summed on the rank that holds the merged probabilities", refuse_directory=False,
+                        other_inputs=())
     return CurvePlan(prefix, int(bins), *paths)
+
+
+def from_plan(p: CurvePlan, classes: int, annotation) -> "Curves":
+    return Curves(classes, p.bins, p.elements_path is not None)
 
 
 def bin_index(p: np.ndarray, bins: int) -> np.ndarray:
@@ -171,7 +172,7 @@ def row_curves(seg: np.ndarray, sup: np.ndarray):
 
 def need_of(theta: float, clen: np.ndarray) -> np.ndarray:
     """The bases an element of clipped length clen needs: ceil(theta * float64(clen)), 0 where clen is 0.  For integer hits,
-    hits >= need is `Accumulator._count`'s float64(hits) >= theta * float64(clen): an integer is at least x exactly when it is at
+    hits >= need is `evaluation.count`'s float64(hits) >= theta * float64(clen): an integer is at least x exactly when it is at
     least ceil(x), and both sides are exact in float64."""
     clen = np.asarray(clen, np.int64)
     return np.where(clen > 0, np.ceil(float(theta) * clen.astype(np.float64)), 0.0).astype(np.int64)
@@ -283,6 +284,7 @@ def elements_tsv(det: np.ndarray, seg: np.ndarray, sup: np.ndarray) -> str:
 class Curves:
     """The counts of one `evaluate --curves` run, summed over its work items; with `elements` (--curve_elements) also `det`, the
     elements by label and detection score + 1."""
+    key = "curves"
 
     def __init__(self, classes: int, bins: int = DEFAULT_BINS, elements: bool = False):
         if not MIN_BINS <= int(bins) <= MAX_BINS:
@@ -293,6 +295,78 @@ class Curves:
         self.sup = np.zeros((self.C, SCORES), np.int64)
         self.elements = bool(elements)
         self.det = np.zeros((self.C, SCORES + 1), np.int64)
+
+    def bind(self, annotation, classes: int) -> None:
+        if self.C != classes:
+            raise ValueError(f"curves of {self.C} classes for a model of {classes}")
+
+    def probe(self, it):
+        """The item's truth painted, every probability counted by class and truth (dgrp_prob_hist_batch) -> (hist [C, 2, bins],
+        flag) as host arrays."""
+        import torch
+
+        from ._lib import check, lib
+        from .evaluation import paint
+        from .pipeline import stream_ptr
+        L, C, bins, dev = lib(), it.C, self.bins, it.dev
+        work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(it.nrec, int(it.t_off[-1]))), int(L.dgrp_prob_hist_workspace_bytes(it.nrec, C, bins))),
+                           dtype=torch.uint8, device=dev)
+        d_true = paint(it.ln, it.org, it.off, it.t_off, it.d_trows, work, dev)
+        d_hist = torch.empty((C, 2, bins), dtype=torch.int64, device=dev)
+        d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+        check(L.dgrp_prob_hist_batch(it.d_probs.data_ptr(), C, it.nrec, it.row0.ctypes.data, it.ln.ctypes.data, d_true.data_ptr(),
+                                     it.off.ctypes.data, bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), stream_ptr()),
+              "dgrp_prob_hist_batch")
+        return d_hist.cpu().numpy(), int(d_bad.item())
+
+    def add(self, it, probed) -> None:
+        """A work item: the probe's histogram summed, the predicted rows counted by class and BED score, and with elements `_detect`."""
+        from .evaluation import naming
+        if probed is not None:
+            hist, flag = probed
+            if flag:
+                raise ValueError(f"a probability outside [0, 1] or a label outside 0..{it.C - 1} reached the probability histogram "
+                                 f"({naming(it.names)})")
+            self.hist += hist
+        if it.p_flat.size:
+            if it.scores is None or len(it.scores) != len(it.p_flat):
+                raise ValueError(f"{len(it.p_flat)} predicted rows but {0 if it.scores is None else len(it.scores)} scores")
+            sc = np.zeros(len(it.p_flat), np.int64)
+            sc[it.kept] = row_scores_of(it.scores[it.kept])
+            seg, sup = row_counts(it.p_flat["label"].astype(np.int64), sc, it.kept, it.good, it.C)
+            self.seg += seg
+            self.sup += sup
+        if self.elements and it.t_flat.size:
+            self._detect(it)
+
+    def _detect(self, it) -> None:
+        """The element curves' share of a work item: the predicted rows painted as keys (label << 10 | BED score) on a zeroed
+        uint16 track (dgrp_paint_row_keys_batch), the detection score of every annotation row against it (dgrp_row_detect_batch),
+        counted into `det` by label and score + 1 for the rows with a base inside their record."""
+        import torch
+
+        from ._lib import check, lib
+        from .evaluation import naming
+        from .pipeline import ROW_SCORE_DTYPE
+        L, dev, s, nrec = lib(), it.dev, it.stream, it.nrec
+        off, ln, org = it.off.ctypes.data, it.ln.ctypes.data, it.org.ctypes.data
+        wb = int(L.dgrp_row_detect_workspace_bytes(nrec, max(int(it.t_off[-1]), int(it.p_off[-1]))))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        d_keys = torch.zeros(it.n, dtype=torch.int16, device=dev)                  # (16-bit keys; the sign of the type is not read)
+        if it.d_prows is not None:
+            sc = np.ascontiguousarray(it.scores, ROW_SCORE_DTYPE)
+            d_sc = torch.from_numpy(sc.view(np.uint8)).to(dev)
+            rc = L.dgrp_paint_row_keys_batch(d_keys.data_ptr(), nrec, off, ln, org, it.d_prows.data_ptr(), it.p_off.ctypes.data,
+                                             d_sc.data_ptr(), work.data_ptr(), wb, s)
+            if rc != 0:
+                raise ValueError("the predicted rows of {} cannot be painted by score: {}".format(
+                    naming(it.names), L.dgrp_last_error().decode("utf-8", "replace")))
+        d_need = torch.from_numpy(need_of(it.theta, it.t_clen)).to(dev)
+        d_det = torch.empty(len(it.t_flat), dtype=torch.int32, device=dev)
+        check(L.dgrp_row_detect_batch(d_keys.data_ptr(), nrec, off, ln, org, it.d_trows.data_ptr(), it.t_off.ctypes.data,
+                                      d_need.data_ptr(), d_det.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_detect_batch")
+        det = d_det.cpu().numpy().astype(np.int64)
+        np.add.at(self.det, (it.t_flat["label"].astype(np.int64)[it.ok], det[it.ok] + 1), 1)
 
     def element_curves(self) -> Dict[str, np.ndarray]:
         return element_curves(self.det, self.seg, self.sup)
@@ -311,18 +385,10 @@ class Curves:
 
     def write(self, p: CurvePlan, log) -> None:
         """The two files, with elements the three, staged: a failure leaves none of them, nor a temporary file."""
-        from .outfiles import StagedFile, StagedOutputs
         texts, paths = [bases_tsv(self.hist), rows_tsv(self.seg, self.sup)], [p.bases_path, p.rows_path]
         if self.elements:
             if p.elements_path is None:
                 raise ValueError("element curves were counted but the plan names no PREFIX.elements.tsv")
             texts.append(self.elements_tsv())
             paths.append(p.elements_path)
-        out = StagedOutputs(log, p.prefix, "--curves", False, (StagedFile(f, "w") for f in paths))
-        try:
-            for part, text in zip(out.parts, texts):
-                part.fh.write(text)
-        except BaseException:
-            out.abort()
-            raise
-        out.commit()
+        write_texts(log, p.prefix, "--curves", paths, texts)

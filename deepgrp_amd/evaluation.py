@@ -11,25 +11,19 @@ last non-N base, and it runs filter_segments over the labels once more; here the
 Both label tracks are painted on the GPU from their rows (dgrp_paint_rows_batch) into flat buffers of the work item's records,
 scored by dgrp_confusion_matrix, and every row is counted against the other track (dgrp_row_hits_batch).
 
-With curves (`evaluate --curves`, deepgrp_amd/curves.py) the runner keeps the merged probabilities of every work item long enough
-for `Accumulator.probe`: it paints the item's truth on the worker's stream and counts every probability into per-class
-histograms split by truth (dgrp_prob_hist_batch); the rows' BED scores come with the rows (dgrp_row_scores_batch).  With element
-curves (`--curve_elements`) `Accumulator.add` also paints the predicted rows as (label, score) keys and takes every annotation row's
-detection score against them (dgrp_paint_row_keys_batch, dgrp_row_detect_batch).
-
-With strata (`evaluate --strata`, deepgrp_amd/strata.py) the probe also paints the truth as (label, stratum) keys and counts the true
-class's probability by them (dgrp_paint_strata_batch, dgrp_prob_hist_strata_batch), and `Accumulator.add` groups the element counts
-it already has by label and stratum.
-
-With off-target counts (`evaluate --offtarget`, deepgrp_amd/offtarget.py) `Accumulator.add` also paints what the listing says lies
-under every base as keys (dgrp_paint_keys_batch), cross-tabulates the predicted labels against them -- every base, and the bases
-of the unsupported predicted rows alone (dgrp_key_crosstab_batch) -- and takes four counts per predicted row
-(dgrp_row_key_classes_batch).  The runner and the probe are not touched.
-
-With boundaries (`evaluate --boundaries`, deepgrp_amd/boundaries.py) `Accumulator.add` also takes, for the annotation rows against
-the predicted labels and for the predicted rows against the truth, the runs, the first and last matching base and the two flanks of
-every row (dgrp_row_bounds_batch) and counts them into the edge-offset and fragment tables (dgrp_bound_hist_batch); only the tables
-come back.  The runner and the probe are not touched."""
+REPORTS.  Everything further that `evaluate` can count (--curves, --strata, --offtarget, --boundaries) is a report: an object of a
+module of its own that this one never imports.  `Accumulator.add` fills one `WorkItem` per work item -- the tables, both sides' rows
+on the host and on the device, their clipped lengths, hits and masks, the two label tracks -- and hands it to every report.  A
+report has
+    key                      its key in the JSON content
+    bind(annotation, classes)  the checks against the model's classes and the annotation, made before the first record runs; it
+                             keeps what it needs of the annotation and looks its per-record inputs up by the item's record names
+    probe(probe_item)        optional: its share of `Accumulator.probe`, which the runner calls on the worker's stream while the
+                             merged probabilities of a work item are alive (`ProbeItem`) -> what `add` gets as `probed`
+    add(item, probed)        its share of a work item with at least one base, on the current stream
+    summary()                the value under `key`
+    write(plan, log)         its files
+The helpers the reports share with the core stand beside the two item classes: `tables`, `upload`, `paint`, `count`, `naming`."""
 from __future__ import annotations
 
 import logging
@@ -116,17 +110,81 @@ def clipped_lengths(rows: np.ndarray, origin: int, length: int) -> np.ndarray:
     return np.maximum(e - a, 0)
 
 
-class Accumulator:
-    """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts."""
+def tables(origins: Sequence[int], lengths: Sequence[int]):
+    """Records back to back in one flat buffer: -> (lengths, origins, offsets [nrec + 1]) as the library reads them."""
+    ln = np.ascontiguousarray(lengths, np.int64)
+    org = np.ascontiguousarray(origins, np.int64)
+    off = np.zeros(len(ln) + 1, np.int64)
+    np.cumsum(ln, out=off[1:])
+    return ln, org, off
 
-    def __init__(self, classes: int, min_overlap: float, curves=None, strata=None, offtarget=None, boundaries=None):
+
+def upload(rows: Sequence[np.ndarray], dev):
+    """The rows of the records as one device array: -> (row offsets [nrec + 1], the rows on the host, on the device or None)."""
+    import torch
+    ro = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(x) for x in rows], out=ro[1:])
+    flat = np.concatenate(rows) if ro[-1] else np.zeros(0, SEGMENT_DTYPE)
+    d = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
+    return ro, flat, d
+
+
+def paint(ln: np.ndarray, org: np.ndarray, off: np.ndarray, ro: np.ndarray, d_rows, work, dev):
+    """A zeroed label track of the records with the rows painted on it, on the current stream (dgrp_paint_rows_batch)."""
+    import torch
+
+    from ._lib import check, lib
+    from .pipeline import stream_ptr
+    d_labels = torch.zeros(int(off[-1]), dtype=torch.int8, device=dev)
+    check(lib().dgrp_paint_rows_batch(d_labels.data_ptr(), len(ln), off.ctypes.data, ln.ctypes.data, org.ctypes.data,
+                                      None if d_rows is None else d_rows.data_ptr(), ro.ctypes.data, work.data_ptr(), work.numel(),
+                                      stream_ptr()), "dgrp_paint_rows_batch")
+    return d_labels
+
+
+def count(theta: float, labels: np.ndarray, clen: np.ndarray, hits: np.ndarray, total: np.ndarray, good: np.ndarray):
+    """total[label] += 1 per row with a base inside its record, good[label] += 1 per such row with hits >= theta * its clipped
+    length; -> the two masks."""
+    ok = clen > 0
+    np.add.at(total, labels[ok], 1)
+    hit = ok & (hits.astype(np.float64) >= theta * clen.astype(np.float64))
+    np.add.at(good, labels[hit], 1)
+    return ok, hit
+
+
+def naming(names: Sequence[str]) -> str:
+    """`record 'a'` or `records 'a', 'b', ...` (the first five) for an error that names a work item."""
+    return "record{} {}".format("s" if len(names) > 1 else "", ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else ""))
+
+
+class WorkItem:
+    """What `Accumulator.add` knows of one work item with at least one base, for the reports to read.
+    C, theta: the classes and --min_overlap.  names: the records' names.  ln, org, off: `tables`; n = off[-1] bases in nrec records.
+    Annotation side: tr the rows record by record, t_off, t_flat, d_trows: `upload` of them; t_clen their clipped lengths, ht their
+    hits against the predicted labels, ok, hit: the masks of `count` (a base inside the record; found).
+    Predicted side: pr, p_off, p_flat, d_prows, p_clen, hp (hits against the truth), kept, good likewise; scores: the rows' scores
+    (pipeline.ROW_SCORE_DTYPE) or None.
+    d_true, d_pred: the two int8 label tracks.  dev, stream: the device and the pointer of the stream everything was queued on."""
+    __slots__ = ("C", "theta", "names", "ln", "org", "off", "n", "nrec", "tr", "t_off", "t_flat", "d_trows", "t_clen", "ht", "ok", "hit",
+                 "pr", "p_off", "p_flat", "d_prows", "p_clen", "hp", "kept", "good", "scores", "d_true", "d_pred", "dev", "stream")
+
+
+class ProbeItem:
+    """What `Accumulator.probe` knows of one work item with at least one base.  d_probs: the merged probabilities, float32
+    [rows, C]; record r is its rows [row0[r], row0[r] + ln[r]).  ln, org, off, nrec, names as in WorkItem.  tr, t_off, d_trows: the
+    item's annotation rows record by record and `upload` of them.  dev: the device."""
+    __slots__ = ("C", "d_probs", "row0", "ln", "org", "off", "nrec", "names", "tr", "t_off", "d_trows", "dev")
+
+
+class Accumulator:
+    """Integer sums over work items: the C x C confusion matrix (cnf[truth][pred]) and the element counts; `reports` (see the
+    module's REPORTS) take their share of every item."""
+
+    def __init__(self, classes: int, min_overlap: float, reports=()):
         if not 0.0 < min_overlap <= 1.0:
             raise ValueError(f"min_overlap must lie in (0, 1], not {min_overlap}")
         self.C, self.theta = int(classes), float(min_overlap)
-        self.curves = curves                           # a curves.Curves: probability histograms and rows by score are summed into it
-        self.strata = strata                           # a strata.Strata: element counts and histograms by (label, stratum)
-        self.offtarget = offtarget                     # an offtarget.Offtarget: predicted labels by what the listing says is there
-        self.boundaries = boundaries                   # a boundaries.Boundaries: edge offsets and runs of both views
+        self.reports = list(reports)
         self.cnf = np.zeros((self.C, self.C), np.int64)
         self.elements = np.zeros(self.C, np.int64)
         self.found = np.zeros(self.C, np.int64)
@@ -134,355 +192,95 @@ class Accumulator:
         self.supported = np.zeros(self.C, np.int64)
         self.bases = self.records = self.records_annotated = self.rows_used = self.outside = 0
 
-    def _count(self, labels: np.ndarray, clen: np.ndarray, hits: np.ndarray, total: np.ndarray, good: np.ndarray):
-        """total[label] += 1 per row with a base inside its record, good[label] += 1 per such row with hits >= theta * its clipped
-        length; -> the two masks."""
-        ok = clen > 0
-        np.add.at(total, labels[ok], 1)
-        hit = ok & (hits.astype(np.float64) >= self.theta * clen.astype(np.float64))
-        np.add.at(good, labels[hit], 1)
-        return ok, hit
-
-    @staticmethod
-    def _tables(origins: Sequence[int], lengths: Sequence[int]):
-        """Records back to back in one flat buffer: -> (lengths, origins, offsets [nrec + 1]) as the library reads them."""
-        ln = np.ascontiguousarray(lengths, np.int64)
-        org = np.ascontiguousarray(origins, np.int64)
-        off = np.zeros(len(ln) + 1, np.int64)
-        np.cumsum(ln, out=off[1:])
-        return ln, org, off
-
-    @staticmethod
-    def _upload(rows: Sequence[np.ndarray], dev):
-        """The rows of the records as one device array: -> (row offsets [nrec + 1], the rows on the host, on the device or None)."""
-        import torch
-        ro = np.zeros(len(rows) + 1, np.int64)
-        np.cumsum([len(x) for x in rows], out=ro[1:])
-        flat = np.concatenate(rows) if ro[-1] else np.zeros(0, SEGMENT_DTYPE)
-        d = torch.from_numpy(flat.view(np.uint8)).to(dev) if flat.size else None
-        return ro, flat, d
-
-    @staticmethod
-    def _paint(ln: np.ndarray, org: np.ndarray, off: np.ndarray, ro: np.ndarray, d_rows, work, dev):
-        """A zeroed label track of the records with the rows painted on it, on the current stream (dgrp_paint_rows_batch)."""
-        import torch
-
-        from ._lib import check, lib
-        from .pipeline import stream_ptr
-        d_labels = torch.zeros(int(off[-1]), dtype=torch.int8, device=dev)
-        check(lib().dgrp_paint_rows_batch(d_labels.data_ptr(), len(ln), off.ctypes.data, ln.ctypes.data, org.ctypes.data,
-                                          None if d_rows is None else d_rows.data_ptr(), ro.ctypes.data, work.data_ptr(), work.numel(),
-                                          stream_ptr()), "dgrp_paint_rows_batch")
-        return d_labels
-
-    def _row_strata(self, annotation, name: str, rows: np.ndarray) -> np.ndarray:
-        """The stratum of every annotation row of contig `name`: its millidiv travels beside the rows (annotation.Rows.millidiv;
-        a table has none: -1 everywhere)."""
-        div_of = getattr(annotation, "millidiv", None)
-        md = None if div_of is None or name not in div_of else div_of[name]
-        return self.strata.strata_of(rows, md)
-
-    def _probe_strata(self, annotation):
-        """The strata's share of the probe: the item's truth painted as keys (dgrp_paint_strata_batch), the true class's
-        probability counted by them (dgrp_prob_hist_strata_batch) -> (hist [C, S, bins], flag) as host arrays."""
-        st, empty = self.strata, np.zeros(0, SEGMENT_DTYPE)
-
-        def run(d_probs, row0, lengths, startposes, keys):
-            import torch
-
-            from ._lib import check, lib
-            from .pipeline import require_gpu, stream_ptr
-            L = lib()
-            ln, org, off = self._tables(startposes, lengths)
-            nrec = len(ln)
-            hist = np.zeros((self.C, st.S, st.bins), np.int64)
-            if nrec == 0 or int(off[-1]) == 0 or d_probs is None:
-                return hist, 0
-            if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous() or d_probs.shape[1] != self.C:
-                raise ValueError(f"the strata take a contiguous float32 [rows, {self.C}] array")
-            dev = require_gpu()
-            tr = [np.ascontiguousarray(annotation.get(k[1], empty), SEGMENT_DTYPE) for k in keys]
-            t_off, _flat, d_trows = self._upload(tr, dev)
-            sof = [self._row_strata(annotation, k[1], t) for k, t in zip(keys, tr)]
-            d_st = torch.from_numpy(np.concatenate(sof)).to(dev) if int(t_off[-1]) else None
-            work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(nrec, int(t_off[-1]))), int(L.dgrp_prob_hist_strata_workspace_bytes(nrec)), 1),
-                               dtype=torch.uint8, device=dev)
-            d_keys = torch.empty(int(off[-1]), dtype=torch.int32, device=dev)      # (32-bit keys; the sign of the type is not read)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            check(L.dgrp_paint_strata_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_trows),
-                                            t_off.ctypes.data, ptr(d_st), work.data_ptr(), work.numel(), stream_ptr()),
-                  "dgrp_paint_strata_batch")
-            r0 = np.ascontiguousarray(row0, np.int64)
-            d_hist = torch.empty((self.C, st.S, st.bins), dtype=torch.int64, device=dev)
-            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
-            check(L.dgrp_prob_hist_strata_batch(d_probs.data_ptr(), self.C, nrec, r0.ctypes.data, ln.ctypes.data, d_keys.data_ptr(),
-                                                off.ctypes.data, st.S, st.bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(),
-                                                work.numel(), stream_ptr()), "dgrp_prob_hist_strata_batch")
-            return d_hist.cpu().numpy(), int(d_bad.item())
-        return run
-
     def probe(self, annotation: Dict[str, np.ndarray]):
-        """RecordRunner's probe for the curves: called on the worker's stream with the merged probabilities of a work item (record r:
-        rows [row0[r], row0[r] + lengths[r]) of d_probs; keys[r][1] its annotation contig), it paints the item's truth, counts the
-        histograms (dgrp_prob_hist_batch) and returns them with the flag as host arrays; `add` sums them.  With strata what it
-        returns is a dict: "curves" that pair (where there are curves), "strata" the pair of `_probe_strata`."""
-        if self.strata is not None:
-            curve_run = self._probe_curves(annotation) if self.curves is not None else None
-            strata_run = self._probe_strata(annotation)
-
-            def both(*a):
-                out = {"strata": strata_run(*a)}
-                if curve_run is not None:
-                    out["curves"] = curve_run(*a)
-                return out
-            return both
-        return self._probe_curves(annotation)
-
-    def _probe_curves(self, annotation: Dict[str, np.ndarray]):
-        bins, empty = self.curves.bins, np.zeros(0, SEGMENT_DTYPE)
+        """RecordRunner's probe, or None when no report has one: called on the worker's stream with the merged probabilities of a
+        work item (record r: rows [row0[r], row0[r] + lengths[r]) of d_probs; keys[r][1] its annotation contig), it uploads the
+        item's truth rows and returns {key: what the report's probe returned} as host arrays -- None for an item without a base;
+        `add` hands every report its own."""
+        asked = [r for r in self.reports if hasattr(r, "probe")][::-1]       # (the last report's device calls are queued first)
+        if not asked:
+            return None
+        empty = np.zeros(0, SEGMENT_DTYPE)
 
         def run(d_probs, row0, lengths, startposes, keys):
             import torch
 
-            from ._lib import check, lib
-            from .pipeline import require_gpu, stream_ptr
-            L = lib()
-            ln, org, off = self._tables(startposes, lengths)
-            nrec = len(ln)
-            hist = np.zeros((self.C, 2, bins), np.int64)
-            if nrec == 0 or int(off[-1]) == 0 or d_probs is None:
-                return hist, 0
+            from .pipeline import require_gpu
+            it = ProbeItem()
+            it.ln, it.org, it.off = tables(startposes, lengths)
+            it.nrec = len(it.ln)
+            if it.nrec == 0 or int(it.off[-1]) == 0 or d_probs is None:
+                return {r.key: None for r in asked}
             if d_probs.dtype != torch.float32 or d_probs.ndim != 2 or not d_probs.is_contiguous() or d_probs.shape[1] != self.C:
-                raise ValueError(f"the curves take a contiguous float32 [rows, {self.C}] array")
-            dev = require_gpu()
-            tr = [np.ascontiguousarray(annotation.get(k[1], empty), SEGMENT_DTYPE) for k in keys]
-            t_off, _flat, d_trows = self._upload(tr, dev)
-            work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(nrec, int(t_off[-1]))), int(L.dgrp_prob_hist_workspace_bytes(nrec, self.C, bins))),
-                               dtype=torch.uint8, device=dev)
-            d_true = self._paint(ln, org, off, t_off, d_trows, work, dev)
-            r0 = np.ascontiguousarray(row0, np.int64)
-            d_hist = torch.empty((self.C, 2, bins), dtype=torch.int64, device=dev)
-            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
-            check(L.dgrp_prob_hist_batch(d_probs.data_ptr(), self.C, nrec, r0.ctypes.data, ln.ctypes.data, d_true.data_ptr(), off.ctypes.data,
-                                         bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), stream_ptr()),
-                  "dgrp_prob_hist_batch")
-            return d_hist.cpu().numpy(), int(d_bad.item())
+                raise ValueError(f"the {asked[0].key} take a contiguous float32 [rows, {self.C}] array")
+            it.C, it.d_probs, it.row0, it.dev = self.C, d_probs, np.ascontiguousarray(row0, np.int64), require_gpu()
+            it.names = [k[1] for k in keys]
+            it.tr = [np.ascontiguousarray(annotation.get(nm, empty), SEGMENT_DTYPE) for nm in it.names]
+            it.t_off, _flat, it.d_trows = upload(it.tr, it.dev)
+            return {r.key: r.probe(it) for r in asked}
         return run
 
     def add(self, origins: Sequence[int], lengths: Sequence[int], pred_rows: Sequence[np.ndarray],
-            true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = (),
-            true_strata: Optional[Sequence[np.ndarray]] = None, off_rows: Optional[Sequence[np.ndarray]] = None,
-            off_keys: Optional[Sequence[np.ndarray]] = None) -> None:
+            true_rows: Sequence[np.ndarray], scores: Optional[np.ndarray] = None, probed=None, names: Sequence[str] = ()) -> None:
         """One work item: records r = 0.. with startpos origins[r], kept length lengths[r], the TSV rows `predict` wrote for it
-        (original coordinates) and its kept annotation rows.  With curves also the scores of the predicted rows, record after record
-        (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names for its error.  With strata also the
-        stratum of every annotation row, record after record as true_rows.  With off-target counts also the un-modelled rows of
-        every record and their keys (annotation.Rows.offtarget_rows / offtarget_keys)."""
+        (original coordinates) and its kept annotation rows.  For the reports also the scores of the predicted rows, record after
+        record (pipeline.ROW_SCORE_DTYPE), what `probe` returned for the item, and the records' names."""
         import torch
 
         from ._lib import check, lib
         from .pipeline import require_gpu, stream_ptr
         L = lib()
-        nrec = len(lengths)
+        it = WorkItem()
+        it.C, it.theta, it.names, it.scores = self.C, self.theta, list(names), scores
+        it.nrec = nrec = len(lengths)
         if nrec == 0:
             return
-        ln, org, off = self._tables(origins, lengths)
-        n = int(off[-1])
-        if self.strata is not None and probed is not None:
-            shist, sflag = probed["strata"]
-            if sflag:
-                raise ValueError("a probability outside [0, 1] or a key outside {} classes and {} strata reached the strata histogram "
-                                 "(record{} {})".format(self.C, self.strata.S, "s" if len(names) > 1 else "",
-                                                        ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else "")))
-            self.strata.hist += shist
-            probed = probed.get("curves")
-        if self.curves is not None and probed is not None:
-            hist, flag = probed
-            if flag:
-                raise ValueError("a probability outside [0, 1] or a label outside 0..{} reached the probability histogram (record{} {})".format(
-                    self.C - 1, "s" if len(names) > 1 else "", ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else "")))
-            self.curves.hist += hist
+        if self.reports and len(it.names) != nrec:
+            raise ValueError(f"{nrec} records but {len(it.names)} names: the reports look their inputs up by record name")
+        it.ln, it.org, it.off = ln, org, off = tables(origins, lengths)
+        it.n = n = int(off[-1])
         self.records += nrec
         self.bases += n
         self.records_annotated += sum(1 for t in true_rows if len(t))
-        tr = [np.ascontiguousarray(t, SEGMENT_DTYPE) for t in true_rows]
-        pr = [np.ascontiguousarray(p, SEGMENT_DTYPE) for p in pred_rows]
-        t_clen = [clipped_lengths(t, int(org[r]), int(ln[r])) for r, t in enumerate(tr)]
-        self.rows_used += sum(len(t) for t in tr)
-        self.outside += int(sum(int((c == 0).sum()) for c in t_clen))
+        it.tr = [np.ascontiguousarray(t, SEGMENT_DTYPE) for t in true_rows]
+        it.pr = [np.ascontiguousarray(p, SEGMENT_DTYPE) for p in pred_rows]
+        it.t_clen = np.concatenate([clipped_lengths(t, int(org[r]), int(ln[r])) for r, t in enumerate(it.tr)])
+        it.p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(it.pr)])
+        self.rows_used += len(it.t_clen)
+        self.outside += int((it.t_clen == 0).sum())
         if n == 0:
             return
-        dev = require_gpu()
-        t_off, t_flat, d_trows = self._upload(tr, dev)
-        p_off, p_flat, d_prows = self._upload(pr, dev)
-        wb = L.dgrp_eval_workspace_bytes(nrec, max(int(t_off[-1]), int(p_off[-1])))
+        it.dev = dev = require_gpu()
+        it.t_off, it.t_flat, it.d_trows = upload(it.tr, dev)
+        it.p_off, it.p_flat, it.d_prows = upload(it.pr, dev)
+        wb = L.dgrp_eval_workspace_bytes(nrec, max(int(it.t_off[-1]), int(it.p_off[-1])))
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
-        s = stream_ptr()
-        ptr = lambda t: None if t is None else t.data_ptr()
+        it.stream = s = stream_ptr()
 
         def hits(d_labels, ro, d_rows):
             d_hits = torch.zeros(max(int(ro[-1]), 1), dtype=torch.int64, device=dev)
-            check(L.dgrp_row_hits_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_rows),
-                                        ro.ctypes.data, d_hits.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_hits_batch")
+            check(L.dgrp_row_hits_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data,
+                                        None if d_rows is None else d_rows.data_ptr(), ro.ctypes.data, d_hits.data_ptr(), work.data_ptr(),
+                                        wb, s), "dgrp_row_hits_batch")
             return d_hits
 
-        d_true = self._paint(ln, org, off, t_off, d_trows, work, dev)
-        d_pred = self._paint(ln, org, off, p_off, d_prows, work, dev)
-        d_ht = hits(d_pred, t_off, d_trows)            # annotation rows against the predicted labels
-        d_hp = hits(d_true, p_off, d_prows)            # predicted rows against the truth
+        it.d_true = paint(ln, org, off, it.t_off, it.d_trows, work, dev)
+        it.d_pred = paint(ln, org, off, it.p_off, it.d_prows, work, dev)
+        d_ht = hits(it.d_pred, it.t_off, it.d_trows)   # annotation rows against the predicted labels
+        d_hp = hits(it.d_true, it.p_off, it.d_prows)   # predicted rows against the truth
         d_cnf = torch.empty((self.C, self.C), dtype=torch.int64, device=dev)
         d_bad = torch.empty(1, dtype=torch.int32, device=dev)
-        check(L.dgrp_confusion_matrix(d_true.data_ptr(), d_pred.data_ptr(), n, self.C, d_cnf.data_ptr(), d_bad.data_ptr(), s),
+        check(L.dgrp_confusion_matrix(it.d_true.data_ptr(), it.d_pred.data_ptr(), n, self.C, d_cnf.data_ptr(), d_bad.data_ptr(), s),
               "dgrp_confusion_matrix")
         cnf, bad = d_cnf.cpu().numpy(), int(d_bad.item())
-        ht, hp = d_ht.cpu().numpy()[:int(t_off[-1])], d_hp.cpu().numpy()[:int(p_off[-1])]
+        it.ht, it.hp = d_ht.cpu().numpy()[:int(it.t_off[-1])], d_hp.cpu().numpy()[:int(it.p_off[-1])]
         if bad:
             raise ValueError(f"a label outside 0..{self.C - 1} reached the confusion matrix")
         self.cnf += cnf
-        if t_flat.size:
-            ok, hit = self._count(t_flat["label"].astype(np.int64), np.concatenate(t_clen), ht, self.elements, self.found)
-            if self.strata is not None:
-                if true_strata is None or sum(len(x) for x in true_strata) != len(t_flat):
-                    raise ValueError(f"{len(t_flat)} annotation rows but {0 if true_strata is None else sum(len(x) for x in true_strata)} strata")
-                self.strata.count(t_flat["label"], np.concatenate(true_strata), np.concatenate(t_clen), ht, ok, hit)
-        kept = good = np.zeros(0, bool)
-        if p_flat.size:
-            p_clen = np.concatenate([clipped_lengths(p, int(org[r]), int(ln[r])) for r, p in enumerate(pr)])
-            kept, good = self._count(p_flat["label"].astype(np.int64), p_clen, hp, self.segments, self.supported)
-            if self.curves is not None:
-                from .curves import row_counts, row_scores_of
-                if scores is None or len(scores) != len(p_flat):
-                    raise ValueError(f"{len(p_flat)} predicted rows but {0 if scores is None else len(scores)} scores")
-                sc = np.zeros(len(p_flat), np.int64)
-                sc[kept] = row_scores_of(scores[kept])
-                seg, sup = row_counts(p_flat["label"].astype(np.int64), sc, kept, good, self.C)
-                self.curves.seg += seg
-                self.curves.sup += sup
-        if self.curves is not None and self.curves.elements and t_flat.size:
-            self._detect(ln, org, off, t_off, t_flat, d_trows, np.concatenate(t_clen), p_off, d_prows, scores, names)
-        if self.offtarget is not None:
-            self._offtarget(ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good)
-        if self.boundaries is not None:
-            self._boundaries(ln, org, off, tr, t_off, d_trows, pr, p_off, d_prows, d_true, d_pred)
-
-    def _boundaries(self, ln, org, off, tr, t_off, d_trows, pr, p_off, d_prows, d_true, d_pred) -> None:
-        """The boundaries' share of a work item, once per view: the element view takes the annotation rows (joined into units with
-        --boundary_join, uploaded anew then) against the predicted labels, the row view the predicted rows against the truth.
-        Per view dgrp_row_bounds_batch, then dgrp_bound_hist_batch with need = ceil(theta * clipped length); the three tables and
-        the flag are all that is copied back."""
-        import torch
-
-        from ._lib import check, lib
-        from .boundaries import FRAG
-        from .curves import need_of
-        from .pipeline import require_gpu, stream_ptr
-        bd, L, dev, s, nrec = self.boundaries, lib(), require_gpu(), stream_ptr(), len(ln)
-        W, C = bd.W, self.C
-        if bd.join is not None:
-            tr = [bd.units(t) for t in tr]
-            t_off, _t_flat, d_trows = self._upload(tr, dev)
-        for view, (rows, ro, d_rows, d_labels) in enumerate(((tr, t_off, d_trows, d_pred), (pr, p_off, d_prows, d_true))):
-            nrows = int(ro[-1])
-            if nrows == 0:
-                continue
-            clen = np.concatenate([clipped_lengths(q, int(org[r]), int(ln[r])) for r, q in enumerate(rows)])
-            d_need = torch.from_numpy(need_of(self.theta, clen)).to(dev)
-            wb = int(L.dgrp_row_bounds_workspace_bytes(nrec, nrows))
-            work = torch.empty(max(wb, int(L.dgrp_bound_hist_workspace_bytes(nrec)), 1), dtype=torch.uint8, device=dev)
-            d_bounds = torch.empty((nrows, 5), dtype=torch.int64, device=dev)          # (dgrp_row_bound: 40 bytes a row)
-            check(L.dgrp_row_bounds_batch(d_labels.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_rows.data_ptr(),
-                                          ro.ctypes.data, W, d_bounds.data_ptr(), work.data_ptr(), work.numel(), s), "dgrp_row_bounds_batch")
-            d_frag = torch.empty((C, FRAG), dtype=torch.int64, device=dev)
-            d_edge = torch.empty((C, 2, 2 * W + 1), dtype=torch.int64, device=dev)
-            d_tally = torch.empty((C, 2), dtype=torch.int64, device=dev)
-            d_bad = torch.empty(1, dtype=torch.int32, device=dev)
-            check(L.dgrp_bound_hist_batch(nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_rows.data_ptr(), ro.ctypes.data,
-                                          d_bounds.data_ptr(), d_need.data_ptr(), C, W, d_frag.data_ptr(), d_edge.data_ptr(),
-                                          d_tally.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), s), "dgrp_bound_hist_batch")
-            frag, edge, tally, bad = d_frag.cpu().numpy(), d_edge.cpu().numpy(), d_tally.cpu().numpy(), int(d_bad.item())
-            if bad:
-                raise ValueError(f"a row label outside 0..{C - 1} reached the boundary counts")
-            bd.count(view, frag, edge, tally)
-
-    def _offtarget(self, ln, org, off, tr, off_rows, off_keys, d_pred, pr, p_off, p_flat, d_prows, kept, good) -> None:
-        """The off-target share of a work item.  The key track: the item's modelled rows with their labels as keys and its
-        un-modelled rows with 64 + family id (dgrp_paint_keys_batch).  Two cross-tabulations against it (dgrp_key_crosstab_batch):
-        the predicted labels, and a second track painted from only the predicted rows `_count` found unsupported -- of which the
-        label 0, everything outside those rows, is dropped.  Four counts per predicted row (dgrp_row_key_classes_batch)."""
-        import torch
-
-        from ._lib import check, lib
-        from .pipeline import require_gpu, stream_ptr
-        ot, L, dev, s, nrec = self.offtarget, lib(), require_gpu(), stream_ptr(), len(ln)
-        n = int(off[-1])
-        if off_rows is None or off_keys is None or len(off_rows) != nrec or len(off_keys) != nrec:
-            raise ValueError("the off-target counts need the un-modelled rows and keys of every record")
-        k_rows, k_keys = [], []
-        for r in range(nrec):
-            o = np.ascontiguousarray(off_rows[r], SEGMENT_DTYPE)
-            ok = np.ascontiguousarray(off_keys[r], np.uint32)
-            if len(o) != len(ok):
-                raise ValueError(f"{len(o)} un-modelled rows but {len(ok)} keys")
-            k_rows.append(np.concatenate([tr[r], o]))
-            k_keys.append(np.concatenate([tr[r]["label"].astype(np.uint32), ok]))
-        k_off, _k_flat, d_krows = self._upload(k_rows, dev)
-        uns = kept & ~good
-        ur = [p[uns[int(p_off[r]):int(p_off[r + 1])]] for r, p in enumerate(pr)]
-        u_off, _u_flat, d_urows = self._upload(ur, dev)
-        wb = int(L.dgrp_eval_workspace_bytes(nrec, max(int(k_off[-1]), int(p_off[-1]), int(u_off[-1]))))
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        d_rk = torch.from_numpy(np.concatenate(k_keys).view(np.int32)).to(dev) if int(k_off[-1]) else None   # (the sign of the type is not read)
-        d_keys = torch.empty(n, dtype=torch.int32, device=dev)                    # (32-bit keys; the sign of the type is not read)
-        check(L.dgrp_paint_keys_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_krows),
-                                      k_off.ctypes.data, ptr(d_rk), work.data_ptr(), wb, s), "dgrp_paint_keys_batch")
-        d_uns = self._paint(ln, org, off, u_off, d_urows, work, dev)
-        d_hist = torch.empty((2, self.C, ot.K), dtype=torch.int64, device=dev)
-        d_bad = torch.empty(2, dtype=torch.int32, device=dev)
-        for k, d_lab in enumerate((d_pred, d_uns)):
-            check(L.dgrp_key_crosstab_batch(d_lab.data_ptr(), d_keys.data_ptr(), n, self.C, ot.K, d_hist[k].data_ptr(), d_bad[k:].data_ptr(), s),
-                  "dgrp_key_crosstab_batch")
-        d_cls = torch.zeros((max(int(p_off[-1]), 1), 4), dtype=torch.int64, device=dev)
-        check(L.dgrp_row_key_classes_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, ptr(d_prows),
-                                           p_off.ctypes.data, d_cls.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_key_classes_batch")
-        hist, bad, cls = d_hist.cpu().numpy(), d_bad.cpu().numpy(), d_cls.cpu().numpy()[:int(p_off[-1])]
-        if bad.any():
-            raise ValueError(f"a predicted label outside 0..{self.C - 1} or a key outside the {ot.F} families of the listing reached the "
-                             "off-target counts")
-        hist[1, 0] = 0
-        ot.hist += hist
-        if p_flat.size:
-            ot.count_rows(p_flat["label"].astype(np.int64), kept, good, cls)
-
-    def _detect(self, ln, org, off, t_off, t_flat, d_trows, t_clen, p_off, d_prows, scores, names) -> None:
-        """The element curves' share of a work item: the predicted rows painted as keys (label << 10 | BED score) on a zeroed
-        uint16 track (dgrp_paint_row_keys_batch), the detection score of every annotation row against it (dgrp_row_detect_batch),
-        counted into curves.det by label and score + 1 for the rows with a base inside their record."""
-        import torch
-
-        from ._lib import check, lib
-        from .curves import need_of
-        from .pipeline import ROW_SCORE_DTYPE, require_gpu, stream_ptr
-        L, dev, s, nrec = lib(), require_gpu(), stream_ptr(), len(ln)
-        wb = int(L.dgrp_row_detect_workspace_bytes(nrec, max(int(t_off[-1]), int(p_off[-1]))))
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
-        d_keys = torch.zeros(int(off[-1]), dtype=torch.int16, device=dev)          # (16-bit keys; the sign of the type is not read)
-        if d_prows is not None:
-            sc = np.ascontiguousarray(scores, ROW_SCORE_DTYPE)
-            d_sc = torch.from_numpy(sc.view(np.uint8)).to(dev)
-            rc = L.dgrp_paint_row_keys_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_prows.data_ptr(),
-                                             p_off.ctypes.data, d_sc.data_ptr(), work.data_ptr(), wb, s)
-            if rc != 0:
-                raise ValueError("the predicted rows of record{} {} cannot be painted by score: {}".format(
-                    "s" if len(names) > 1 else "", ", ".join(repr(x) for x in list(names)[:5]) + (", ..." if len(names) > 5 else ""),
-                    L.dgrp_last_error().decode("utf-8", "replace")))
-        d_need = torch.from_numpy(need_of(self.theta, t_clen)).to(dev)
-        d_det = torch.empty(len(t_flat), dtype=torch.int32, device=dev)
-        check(L.dgrp_row_detect_batch(d_keys.data_ptr(), nrec, off.ctypes.data, ln.ctypes.data, org.ctypes.data, d_trows.data_ptr(),
-                                      t_off.ctypes.data, d_need.data_ptr(), d_det.data_ptr(), work.data_ptr(), wb, s), "dgrp_row_detect_batch")
-        det = d_det.cpu().numpy().astype(np.int64)
-        ok = t_clen > 0
-        np.add.at(self.curves.det, (t_flat["label"].astype(np.int64)[ok], det[ok] + 1), 1)
+        it.ok, it.hit = count(self.theta, it.t_flat["label"].astype(np.int64), it.t_clen, it.ht, self.elements, self.found)
+        it.kept, it.good = count(self.theta, it.p_flat["label"].astype(np.int64), it.p_clen, it.hp, self.segments, self.supported)
+        for r in self.reports:
+            r.add(it, None if probed is None else probed.get(r.key))
 
 
 def metrics_of(cnf: np.ndarray, bases: int) -> Dict[str, object]:
@@ -501,7 +299,7 @@ def _num(x) -> Optional[float]:
 
 def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
     """The JSON content: `info` (paths, options) plus counts, the confusion matrix, every metric (NaN as None) and the element
-    counts; with curves also their summaries under `curves`."""
+    counts; then every report's summary under its key."""
     m = metrics_of(acc.cnf, acc.bases)
     metrics = {}
     for k, v in m.items():
@@ -511,14 +309,8 @@ def report(acc: Accumulator, info: Dict[str, object]) -> Dict[str, object]:
                rows_used=int(acc.rows_used), outside=int(acc.outside), confusion_matrix=acc.cnf.astype(int).tolist(),
                metrics=metrics, min_overlap=acc.theta, elements=acc.elements.tolist(), found=acc.found.tolist(),
                segments=acc.segments.tolist(), supported=acc.supported.tolist())
-    if acc.curves is not None:
-        out["curves"] = acc.curves.summary()
-    if acc.strata is not None:
-        out["strata"] = acc.strata.summary()
-    if acc.offtarget is not None:
-        out["offtarget"] = acc.offtarget.summary()
-    if acc.boundaries is not None:
-        out["boundaries"] = acc.boundaries.summary()
+    for r in acc.reports:
+        out[r.key] = r.summary()
     return out
 
 
@@ -559,38 +351,21 @@ def record_name(filename: str, header: str) -> str:
 
 
 def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[str, Iterable[Tuple[str, object]]]], pipe,
-             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, curves=None,
-             strata=None, offtarget=None, boundaries=None) -> Dict[str, object]:
+             repeats: Sequence[int], min_overlap: float = 0.5, info: Optional[Dict[str, object]] = None, reports=()) -> Dict[str, object]:
     """Run `pipe` (a ContigPipeline of `model`) over the records of `inputs` -- (filename, (header, record) pairs) as
     `predict` reads them -- and score the rows it produces against `annotation` (read_annotation's dict).  Returns the JSON
     content; raises NoMatchError when no annotation row belongs to any record (and logs a warning as soon as the first
-    record read has none).  curves (a curves.Curves of the model's classes): the runner takes the merged path with scores and
-    `Accumulator.probe`, the counts of the curves are summed into it and the JSON content gains the key `curves`; without it a
-    record is the fused call, as before.  strata (a strata.Strata of the model's classes): the same runner and probe, the counts by
-    (label, stratum) are summed into it and the JSON content gains the key `strata`; the divergence of the rows is
-    `annotation.millidiv` (annotation.Rows), -1 everywhere without it.  offtarget (an offtarget.Offtarget of the model's classes
-    and the listing's families): `annotation` is what annotation.evaluation_rows(offtarget=True) returns, the counts are summed
-    into it and the JSON content gains the key `offtarget`; the runner is the one the other arguments choose.  boundaries (a
-    boundaries.Boundaries of the model's classes): the edge offsets and runs of both views are summed into it and the JSON content
-    gains the key `boundaries`; the runner is the one the other arguments choose."""
+    record read has none).  reports (see the module's REPORTS): each is bound to the annotation and the model's classes, its counts
+    are summed into it and the JSON content gains its key.  Where one of them has a probe the runner takes the merged path with
+    scores and `Accumulator.probe`; else a record is the fused call."""
     from .runner import RecordRunner
 
     classes = int(model.output_shape[2])
-    if curves is not None and curves.C != classes:
-        raise ValueError(f"curves of {curves.C} classes for a model of {classes}")
-    if strata is not None and strata.C != classes:
-        raise ValueError(f"strata of {strata.C} classes for a model of {classes}")
-    if offtarget is not None:
-        if offtarget.C != classes:
-            raise ValueError(f"off-target counts of {offtarget.C} classes for a model of {classes}")
-        if getattr(annotation, "offtarget_rows", None) is None:
-            raise ValueError("off-target counts need the un-modelled rows of a RepeatMasker listing (annotation.evaluation_rows(offtarget=True))")
-    if boundaries is not None and boundaries.C != classes:
-        raise ValueError(f"boundaries of {boundaries.C} classes for a model of {classes}")
-    acc = Accumulator(classes, min_overlap, curves, strata, offtarget, boundaries)
-    no_keys = np.zeros(0, np.uint32)
-    probing = curves is not None or strata is not None
-    runner = RecordRunner(pipe, scores=True, probe=acc.probe(annotation)) if probing else RecordRunner(pipe)
+    for r in reports:
+        r.bind(annotation, classes)
+    acc = Accumulator(classes, min_overlap, reports)
+    probe = acc.probe(annotation)
+    runner = RecordRunner(pipe, scores=True, probe=probe) if probe is not None else RecordRunner(pipe)
     empty = np.zeros(0, SEGMENT_DTYPE)
     seen_names: List[str] = []
     state = {"matched": False, "warned": False}
@@ -621,7 +396,7 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
 
     for out in runner.outputs(keyed()):
         kind, key, rows, scores = out[:4]
-        probed = out[5] if probing else None
+        probed = out[5] if probe is not None else None
         keys = key if kind == "batch" else [key]
         rows = np.asarray(rows)
         if kind == "batch":
@@ -631,10 +406,7 @@ def evaluate(model, annotation: Dict[str, np.ndarray], inputs: Iterable[Tuple[st
         else:
             pred = [rows]
         true = [annotation.get(k[1], empty) for k in keys]
-        true_strata = [acc._row_strata(annotation, k[1], t) for k, t in zip(keys, true)] if strata is not None else None
-        off_rows = [annotation.offtarget_rows.get(k[1], empty) for k in keys] if offtarget is not None else None
-        off_keys = [annotation.offtarget_keys.get(k[1], no_keys) for k in keys] if offtarget is not None else None
-        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, true, scores, probed, [k[1] for k in keys], true_strata, off_rows, off_keys)
+        acc.add([k[2] for k in keys], [k[3] for k in keys], pred, true, scores, probed, [k[1] for k in keys])
     if acc.rows_used == 0:
         raise NoMatchError("no annotation row names a record of the inputs (records: {}; annotation: {})".format(
             ", ".join(repr(x) for x in seen_names) or "none",

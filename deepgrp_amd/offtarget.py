@@ -9,18 +9,20 @@ KEY OF A BASE.  The smallest key among the rows that cover it, 0xFFFFFFFF where 
 `evaluate` paints there, an un-modelled family shows only where no modelled row covers, and among several families the first in byte
 order wins (dgrp_paint_keys_batch; `reference_keys` is its numpy statement).
 
-COUNTS.  Per work item `Accumulator.add` cross-tabulates the predicted label of every base against its key, once for all bases and
-once for a track that holds only the predicted rows it found unsupported (dgrp_key_crosstab_batch; `reference_crosstab`), and takes
-per predicted row the bases of its clipped span under its own label, another label, a family, nothing (dgrp_row_key_classes_batch).
+COUNTS.  Per work item `Offtarget.add` (a report of deepgrp_amd/evaluation.py) cross-tabulates the predicted label of every base
+against its key, once for all bases and once for a track that holds only the predicted rows found unsupported
+(dgrp_key_crosstab_batch; `reference_crosstab`), and takes per predicted row the bases of its clipped span under its own label,
+another label, a family, nothing (dgrp_row_key_classes_batch).  The runner and the probe are not touched.
 
 Everything here is numpy over int64; the same counts give the same file bytes."""
 from __future__ import annotations
 
-import os
 import sys
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
+
+from .outfiles import plan_prefix, write_texts
 
 NONE = 0xFFFFFFFF                                   # the key of a base that no row covers
 FIRST_FAMILY = 64                                   # keys below it are labels
@@ -51,20 +53,8 @@ def plan(args) -> Optional[OfftargetPlan]:
     by = BY[0] if by is None else by
     if by not in BY:
         sys.exit(f"--offtarget_by: one of {', '.join(BY)}, not {by!r}")
-    if prefix == "" or prefix.endswith(os.sep) or os.path.isdir(prefix):
-        sys.exit(f"--offtarget takes a file name prefix, not the directory {prefix!r}")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("--offtarget runs in one process (WORLD_SIZE > 1 is not supported: the counts are summed on the rank that holds the "
-                 "predicted rows)")
-    where = os.path.dirname(prefix) or "."
-    if not os.path.isdir(where):
-        sys.exit(f"--offtarget: the directory {where} does not exist")
-    paths = (prefix + ".offtarget.tsv", prefix + ".offtarget.rows.tsv")
-    inputs = list(getattr(args, "FASTA", [])) + [getattr(args, k, None) for k in ("annotation", "model")]
-    for f in inputs:
-        for out in paths:
-            if f not in (None, "-") and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
-                sys.exit(f"--offtarget: the file {out} would overwrite the input {f}")
+    paths = plan_prefix("--offtarget", prefix, (".offtarget.tsv", ".offtarget.rows.tsv"), args,
+                        "the counts are summed on the rank that holds the predicted rows")
     from . import annotation
     ann = getattr(args, "annotation", None)
     if ann is not None and annotation.resolve_format(ann, getattr(args, "annotation_format", "auto")) == "table":
@@ -72,6 +62,10 @@ def plan(args) -> Optional[OfftargetPlan]:
                  "predicted bases lie on is in the RepeatMasker listing itself: give `genome.fa.out`, `genome.fa.out.gz` or a UCSC "
                  "`rmsk.txt.gz`")
     return OfftargetPlan(prefix, by, *paths)
+
+
+def from_plan(p: OfftargetPlan, classes: int, annotation) -> "Offtarget":
+    return Offtarget(classes, annotation.families, p.by)
 
 
 def reference_keys(origins, lengths, rows, keys) -> List[np.ndarray]:
@@ -161,6 +155,7 @@ def rows_tsv(rows: np.ndarray) -> str:
 class Offtarget:
     """The counts of one `evaluate --offtarget` run, summed over its work items: `hist` int64 [2, C, K] (scope all / unsupported:
     predicted label by key column, K = 64 + F + 1) and `rows` int64 [C, 6] (ROWS_HEADER behind the class)."""
+    key = "offtarget"
 
     def __init__(self, classes: int, families: Sequence[str], by: str = "family"):
         if by not in BY:
@@ -173,8 +168,65 @@ class Offtarget:
         self.hist = np.zeros((2, self.C, self.K), np.int64)
         self.rows = np.zeros((self.C, 6), np.int64)
 
+    def bind(self, annotation, classes: int) -> None:
+        if self.C != classes:
+            raise ValueError(f"off-target counts of {self.C} classes for a model of {classes}")
+        if getattr(annotation, "offtarget_rows", None) is None:
+            raise ValueError("off-target counts need the un-modelled rows of a RepeatMasker listing (annotation.evaluation_rows(offtarget=True))")
+        self.offtarget_rows, self.offtarget_keys = annotation.offtarget_rows, annotation.offtarget_keys
+
+    def add(self, it, probed) -> None:
+        """A work item.  The key track: the item's modelled rows with their labels as keys and its un-modelled rows with 64 + family
+        id (dgrp_paint_keys_batch).  Two cross-tabulations against it (dgrp_key_crosstab_batch): the predicted labels, and a second
+        track painted from only the predicted rows the item holds as unsupported -- of which the label 0, everything outside those
+        rows, is dropped.  Four counts per predicted row (dgrp_row_key_classes_batch)."""
+        import torch
+
+        from ._lib import check, lib
+        from .evaluation import paint, upload
+        from .pipeline import SEGMENT_DTYPE
+        L, dev, s, nrec, n, C = lib(), it.dev, it.stream, it.nrec, it.n, it.C
+        no_rows, no_keys = np.zeros(0, SEGMENT_DTYPE), np.zeros(0, np.uint32)
+        off, ln, org = it.off.ctypes.data, it.ln.ctypes.data, it.org.ctypes.data
+        k_rows, k_keys = [], []
+        for nm, t in zip(it.names, it.tr):
+            o = np.ascontiguousarray(self.offtarget_rows.get(nm, no_rows), SEGMENT_DTYPE)
+            ok = np.ascontiguousarray(self.offtarget_keys.get(nm, no_keys), np.uint32)
+            if len(o) != len(ok):
+                raise ValueError(f"{len(o)} un-modelled rows but {len(ok)} keys")
+            k_rows.append(np.concatenate([t, o]))
+            k_keys.append(np.concatenate([t["label"].astype(np.uint32), ok]))
+        k_off, _k_flat, d_krows = upload(k_rows, dev)
+        uns = it.kept & ~it.good
+        ur = [p[uns[int(it.p_off[r]):int(it.p_off[r + 1])]] for r, p in enumerate(it.pr)]
+        u_off, _u_flat, d_urows = upload(ur, dev)
+        wb = int(L.dgrp_eval_workspace_bytes(nrec, max(int(k_off[-1]), int(it.p_off[-1]), int(u_off[-1]))))
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        d_rk = torch.from_numpy(np.concatenate(k_keys).view(np.int32)).to(dev) if int(k_off[-1]) else None   # (the sign of the type is not read)
+        d_keys = torch.empty(n, dtype=torch.int32, device=dev)                    # (32-bit keys; the sign of the type is not read)
+        check(L.dgrp_paint_keys_batch(d_keys.data_ptr(), nrec, off, ln, org, ptr(d_krows), k_off.ctypes.data, ptr(d_rk), work.data_ptr(),
+                                      wb, s), "dgrp_paint_keys_batch")
+        d_uns = paint(it.ln, it.org, it.off, u_off, d_urows, work, dev)
+        d_hist = torch.empty((2, C, self.K), dtype=torch.int64, device=dev)
+        d_bad = torch.empty(2, dtype=torch.int32, device=dev)
+        for k, d_lab in enumerate((it.d_pred, d_uns)):
+            check(L.dgrp_key_crosstab_batch(d_lab.data_ptr(), d_keys.data_ptr(), n, C, self.K, d_hist[k].data_ptr(), d_bad[k:].data_ptr(), s),
+                  "dgrp_key_crosstab_batch")
+        d_cls = torch.zeros((max(int(it.p_off[-1]), 1), 4), dtype=torch.int64, device=dev)
+        check(L.dgrp_row_key_classes_batch(d_keys.data_ptr(), nrec, off, ln, org, ptr(it.d_prows), it.p_off.ctypes.data, d_cls.data_ptr(),
+                                           work.data_ptr(), wb, s), "dgrp_row_key_classes_batch")
+        hist, bad, cls = d_hist.cpu().numpy(), d_bad.cpu().numpy(), d_cls.cpu().numpy()[:int(it.p_off[-1])]
+        if bad.any():
+            raise ValueError(f"a predicted label outside 0..{C - 1} or a key outside the {self.F} families of the listing reached the "
+                             "off-target counts")
+        hist[1, 0] = 0
+        self.hist += hist
+        if it.p_flat.size:
+            self.count_rows(it.p_flat["label"].astype(np.int64), it.kept, it.good, cls)
+
     def count_rows(self, labels: np.ndarray, kept: np.ndarray, good: np.ndarray, cls: np.ndarray) -> None:
-        """The predicted rows of a work item: `kept` has a base inside its record, `good` is supported (Accumulator._count's masks),
+        """The predicted rows of a work item: `kept` has a base inside its record, `good` is supported (evaluation.count's masks),
         cls int64 [rows, 4] the four counts.  An unsupported row goes to the largest of its counts, ties to the first."""
         lab = np.asarray(labels, np.int64)
         np.add.at(self.rows[:, 0], lab[kept], 1)
@@ -199,13 +251,5 @@ class Offtarget:
 
     def write(self, p: OfftargetPlan, log) -> None:
         """The two files, staged: a failure leaves neither of them, nor a temporary file."""
-        from .outfiles import StagedFile, StagedOutputs
-        texts = [offtarget_tsv(self.hist, self.families, self.by), rows_tsv(self.rows)]
-        out = StagedOutputs(log, p.prefix, "--offtarget", False, (StagedFile(f, "w") for f in (p.table_path, p.rows_path)))
-        try:
-            for part, text in zip(out.parts, texts):
-                part.fh.write(text)
-        except BaseException:
-            out.abort()
-            raise
-        out.commit()
+        write_texts(log, p.prefix, "--offtarget", (p.table_path, p.rows_path),
+                    [offtarget_tsv(self.hist, self.families, self.by), rows_tsv(self.rows)])

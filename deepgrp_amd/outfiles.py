@@ -2,10 +2,12 @@
 under a temporary name next to its final one and renamed when its input is done (`StagedFile`); a BGZF file takes the members of
 every write and, where a tabix index was asked for, builds `<file>.tbi` beside it (`BgzfSink`); `StagedOutputs` is what the files
 of one input share: the rule on record names, one warning when the input cannot be indexed, and a commit that leaves no temporary
-file behind when it fails."""
+file behind when it fails.  The reports of `evaluate` share `plan_prefix`, the refusals of their `--<report> PREFIX`, and
+`write_texts`, their staged text files."""
 from __future__ import annotations
 
 import os
+import sys
 import tempfile
 from typing import Iterable, Optional, Sequence
 
@@ -150,3 +152,36 @@ class StagedOutputs:
     def abort(self) -> None:
         for p in self.parts:
             p.abort()
+
+
+def plan_prefix(flag: str, prefix: str, suffixes: Sequence[str], args, why: str, refuse_directory: bool = True,
+                other_inputs: Sequence[str] = ("annotation", "model")) -> tuple:
+    """What the `evaluate` reports refuse of `flag PREFIX` (sys.exit, before the model is read): a prefix that is a directory (one
+    that only exists as a directory passes with refuse_directory False), WORLD_SIZE > 1 -- `why` says what could not be summed --,
+    a directory that does not exist, an output PREFIX + suffix that is an input: args.FASTA and args.<other_inputs>.
+    -> the output paths."""
+    if prefix == "" or prefix.endswith(os.sep) or (refuse_directory and os.path.isdir(prefix)):
+        sys.exit(f"{flag} takes a file name prefix, not the directory {prefix!r}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        sys.exit(f"{flag} runs in one process (WORLD_SIZE > 1 is not supported: {why})")
+    where = os.path.dirname(prefix) or "."
+    if not os.path.isdir(where):
+        sys.exit(f"{flag}: the directory {where} does not exist")
+    paths = tuple(prefix + s for s in suffixes)
+    for f in list(getattr(args, "FASTA", [])) + [getattr(args, k, None) for k in other_inputs]:
+        for out in paths:
+            if f not in (None, "-") and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
+                sys.exit(f"{flag}: the file {out} would overwrite the input {f}")
+    return paths
+
+
+def write_texts(log, prefix: str, flag: str, paths: Sequence[str], texts: Sequence[str]) -> None:
+    """The text files of one report, staged: a failure leaves none of them, nor a temporary file."""
+    out = StagedOutputs(log, prefix, flag, False, (StagedFile(f, "w") for f in paths))
+    try:
+        for part, text in zip(out.parts, texts):
+            part.fh.write(text)
+    except BaseException:
+        out.abort()
+        raise
+    out.commit()

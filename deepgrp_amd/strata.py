@@ -13,16 +13,20 @@ Base counts.  The device paints the truth as keys, label << 8 | stratum, the sma
 `reference_keys` is its numpy statement) and counts the probability of the TRUE class of every annotated base into `bins` bins per
 (class, stratum) (dgrp_prob_hist_strata_batch; `reference_strata_hist`): every base once, under the element that won it.
 
-Everything here is numpy over int64; the same counts give the same file bytes."""
+ON THE DEVICE (`Strata`, a report of deepgrp_amd/evaluation.py).  `Strata.probe` does the base counts on the worker's stream while
+the runner holds the merged probabilities of a work item; `Strata.add` sums them and does the element counts.
+
+Everything else here is numpy over int64; the same counts give the same file bytes."""
 from __future__ import annotations
 
 import math
-import os
 import re
 import sys
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
+
+from .outfiles import plan_prefix, write_texts
 
 MIN_BINS, MAX_BINS, DEFAULT_BINS = 2, 1000, 100
 MAX_EDGES, MAX_STRATA = 15, 256
@@ -79,21 +83,13 @@ def plan(args) -> Optional[StrataPlan]:
     n = (len(div_edges) + 2) * (len(len_edges) + 1)
     if n > MAX_STRATA:
         sys.exit(f"--strata: {len(div_edges) + 2} divergence bins x {len(len_edges) + 1} length bins are {n} strata, more than {MAX_STRATA}")
-    if prefix == "" or prefix.endswith(os.sep) or os.path.isdir(prefix):
-        sys.exit(f"--strata takes a file name prefix, not the directory {prefix!r}")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        sys.exit("--strata runs in one process (WORLD_SIZE > 1 is not supported: the histograms are summed on the rank that holds "
-                 "the merged probabilities)")
-    where = os.path.dirname(prefix) or "."
-    if not os.path.isdir(where):
-        sys.exit(f"--strata: the directory {where} does not exist")
-    paths = (prefix + ".strata.tsv", prefix + ".strata.bases.tsv")
-    inputs = list(getattr(args, "FASTA", [])) + [getattr(args, k, None) for k in ("annotation", "model")]
-    for f in inputs:
-        for out in paths:
-            if f not in (None, "-") and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
-                sys.exit(f"--strata: the file {out} would overwrite the input {f}")
+    paths = plan_prefix("--strata", prefix, (".strata.tsv", ".strata.bases.tsv"), args,
+                        "the histograms are summed on the rank that holds the merged probabilities")
     return StrataPlan(prefix, div_edges, len_edges, int(bins), *paths)
+
+
+def from_plan(p: StrataPlan, classes: int, annotation) -> "Strata":
+    return Strata(classes, p.div_edges, p.len_edges, p.bins)
 
 
 def _percent(e: int) -> str:
@@ -229,6 +225,7 @@ def bases_tsv(hist: np.ndarray, div_edges: Sequence[int], len_edges: Sequence[in
 class Strata:
     """The counts of one `evaluate --strata` run, summed over its work items: `counts` int64 [4, C, S] (elements, found,
     element_bases, element_hits by label and stratum) and `hist` int64 [C, S, bins]."""
+    key = "strata"
 
     def __init__(self, classes: int, div_edges: Sequence[int], len_edges: Sequence[int], bins: int = DEFAULT_BINS):
         if not MIN_BINS <= int(bins) <= MAX_BINS:
@@ -241,13 +238,60 @@ class Strata:
             raise ValueError(f"{self.S} strata: at most {MAX_STRATA}")
         self.counts = np.zeros((4, self.C, self.S), np.int64)
         self.hist = np.zeros((self.C, self.S, self.bins), np.int64)
+        self.millidiv = None                            # {contig: the millidiv of its rows} once bound to a listing
+
+    def bind(self, annotation, classes: int) -> None:
+        if self.C != classes:
+            raise ValueError(f"strata of {self.C} classes for a model of {classes}")
+        self.millidiv = getattr(annotation, "millidiv", None)
 
     def strata_of(self, rows: np.ndarray, millidiv) -> np.ndarray:
         return strata_of(rows, millidiv, self.div_edges, self.len_edges)
 
+    def row_strata(self, name: str, rows: np.ndarray) -> np.ndarray:
+        """The stratum of every annotation row of contig `name`: its millidiv travels beside the rows (annotation.Rows.millidiv;
+        a table has none: -1 everywhere)."""
+        return self.strata_of(rows, None if self.millidiv is None or name not in self.millidiv else self.millidiv[name])
+
+    def probe(self, it):
+        """The item's truth painted as keys (dgrp_paint_strata_batch), the true class's probability counted by them
+        (dgrp_prob_hist_strata_batch) -> (hist [C, S, bins], flag) as host arrays."""
+        import torch
+
+        from ._lib import check, lib
+        from .pipeline import stream_ptr
+        L, C, dev, nrec = lib(), it.C, it.dev, it.nrec
+        off, ln, org = it.off.ctypes.data, it.ln.ctypes.data, it.org.ctypes.data
+        d_st = torch.from_numpy(np.concatenate([self.row_strata(nm, t) for nm, t in zip(it.names, it.tr)])).to(dev) if int(it.t_off[-1]) else None
+        work = torch.empty(max(int(L.dgrp_eval_workspace_bytes(nrec, int(it.t_off[-1]))), int(L.dgrp_prob_hist_strata_workspace_bytes(nrec)), 1),
+                           dtype=torch.uint8, device=dev)
+        d_keys = torch.empty(int(it.off[-1]), dtype=torch.int32, device=dev)      # (32-bit keys; the sign of the type is not read)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        check(L.dgrp_paint_strata_batch(d_keys.data_ptr(), nrec, off, ln, org, ptr(it.d_trows), it.t_off.ctypes.data, ptr(d_st),
+                                        work.data_ptr(), work.numel(), stream_ptr()), "dgrp_paint_strata_batch")
+        d_hist = torch.empty((C, self.S, self.bins), dtype=torch.int64, device=dev)
+        d_bad = torch.empty(1, dtype=torch.int32, device=dev)
+        check(L.dgrp_prob_hist_strata_batch(it.d_probs.data_ptr(), C, nrec, it.row0.ctypes.data, ln, d_keys.data_ptr(), off, self.S,
+                                            self.bins, d_hist.data_ptr(), d_bad.data_ptr(), work.data_ptr(), work.numel(), stream_ptr()),
+              "dgrp_prob_hist_strata_batch")
+        return d_hist.cpu().numpy(), int(d_bad.item())
+
+    def add(self, it, probed) -> None:
+        """A work item: the probe's histogram summed, the element counts the item holds grouped by label and stratum."""
+        from .evaluation import naming
+        if probed is not None:
+            hist, flag = probed
+            if flag:
+                raise ValueError(f"a probability outside [0, 1] or a key outside {it.C} classes and {self.S} strata reached the strata "
+                                 f"histogram ({naming(it.names)})")
+            self.hist += hist
+        if it.t_flat.size:
+            strata = np.concatenate([self.row_strata(nm, t) for nm, t in zip(it.names, it.tr)])
+            self.count(it.t_flat["label"], strata, it.t_clen, it.ht, it.ok, it.hit)
+
     def count(self, labels: np.ndarray, strata: np.ndarray, clen: np.ndarray, hits: np.ndarray, ok: np.ndarray, hit: np.ndarray) -> None:
         """The annotation rows of a work item: `ok` has a base inside its record, `hit` passes the --min_overlap rule
-        (Accumulator._count's masks)."""
+        (evaluation.count's masks)."""
         lab, st = np.asarray(labels, np.int64), np.asarray(strata, np.int64)
         np.add.at(self.counts[0], (lab[ok], st[ok]), 1)
         np.add.at(self.counts[1], (lab[hit], st[hit]), 1)
@@ -267,13 +311,5 @@ class Strata:
 
     def write(self, p: StrataPlan, log) -> None:
         """The two files, staged: a failure leaves neither of them, nor a temporary file."""
-        from .outfiles import StagedFile, StagedOutputs
-        texts = [strata_tsv(self.counts, self.div_edges, self.len_edges), bases_tsv(self.hist, self.div_edges, self.len_edges)]
-        out = StagedOutputs(log, p.prefix, "--strata", False, (StagedFile(f, "w") for f in (p.strata_path, p.bases_path)))
-        try:
-            for part, text in zip(out.parts, texts):
-                part.fh.write(text)
-        except BaseException:
-            out.abort()
-            raise
-        out.commit()
+        write_texts(log, p.prefix, "--strata", (p.strata_path, p.bases_path),
+                    [strata_tsv(self.counts, self.div_edges, self.len_edges), bases_tsv(self.hist, self.div_edges, self.len_edges)])

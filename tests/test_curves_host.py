@@ -224,14 +224,13 @@ def test_row_curves_on_hand_made_rows():
     """Three rows of class 1 at score 500 (a tie at m = 500), one at 501, one of class 2 at 0; one row with an empty clipped span, which
     counts nowhere; theta exactly at the boundary: hits == theta * length is supported, one hit less is not."""
     from deepgrp_amd import curves
-    from deepgrp_amd.evaluation import Accumulator
-    acc = Accumulator(3, 0.5)
+    from deepgrp_amd.evaluation import count
     labels = np.array([1, 1, 1, 1, 2, 1], np.int64)
     clen = np.array([10, 10, 8, 4, 6, 0], np.int64)
     hits = np.array([5, 4, 4, 4, 2, 0], np.int64)                # 5 >= 5 yes; 4 >= 5 no; 4 >= 4 yes; 4 >= 2 yes; 2 >= 3 no
     score = np.array([500, 500, 500, 501, 0, 999], np.int64)
     total, good = np.zeros(3, np.int64), np.zeros(3, np.int64)
-    kept, sup = acc._count(labels, clen, hits, total, good)
+    kept, sup = count(0.5, labels, clen, hits, total, good)
     assert kept.tolist() == [True, True, True, True, True, False] and sup.tolist() == [True, False, True, True, False, False]
     assert total.tolist() == [0, 4, 1] and good.tolist() == [0, 3, 0]
     seg, su = curves.row_counts(labels, score, kept, sup, 3)

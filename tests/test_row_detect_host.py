@@ -1,6 +1,6 @@
 """`evaluate --curves --curve_elements` on the CPU: the numpy statement of the detection score on hand-worked cases, the element
 curves, their file and summary on a small histogram, the flag's refusals and the plan, the staged write with and without the third
-file, and need = ceil(theta * clen) against the comparison `Accumulator._count` makes."""
+file, and need = ceil(theta * clen) against the comparison `evaluation.count` makes."""
 import logging
 import os
 import subprocess
@@ -84,7 +84,7 @@ def test_an_element_outside_its_record_is_minus_one_and_not_counted():
     true = [(0, 50, 1), (100, 100, 1), (300, 400, 1), (120, 130, 1)]
     _key, d = _detect(100, 100, [(100, 200, 1)], [640], true, 0.5)
     assert d.tolist() == [-1, -1, -1, 640]
-    # what Accumulator._detect counts: only the rows with a base inside their record
+    # what Curves._detect counts: only the rows with a base inside their record
     from deepgrp_amd.evaluation import clipped_lengths
     ok = clipped_lengths(_rows(*true), 100, 100) > 0
     c = curves.Curves(2, 4, elements=True)
@@ -109,7 +109,7 @@ def test_two_records_keep_their_own_tracks():
 @pytest.mark.parametrize("theta", [1e-9, 0.3, 1 / 3, 0.5, 1.0])
 def test_need_is_counts_comparison(theta):
     """For every clipped length 1..2000 and every integer hit count 0..clen: hits >= need is exactly the float64 comparison of
-    Accumulator._count."""
+    evaluation.count."""
     from deepgrp_amd import curves
     clen = np.arange(1, 2001, dtype=np.int64)
     need = curves.need_of(theta, clen)
