@@ -55,6 +55,27 @@ static_assert(sizeof(mss_subent) == 80, "MSS_SUBENT_BYTES");
 #define MSS_QNONE (-4096)
 #define MSS_QBAD 4096
 
+// the eight words of mss_layout::grand: scan totals and the flags the kernels raise, read by the host between the levels
+enum mss_grand {
+    MSS_G_TOTAL = 0,           // total of the scan over blk: stretch boundaries << 32 | positive-run starts
+    MSS_G_CHANGED = 1,         // a unit's exit differs from the previous pass's (or from the next unit's entry)
+    MSS_G_ERROR = 2,           // a kernel's consistency check tripped: the caller falls back
+    MSS_G_NSEG = 3,            // total kept segments (what dgrp_mss_segments_host reads)
+    MSS_G_WHY = 4,             // which check tripped in the parts scan or the stitch (bits, for the trace)
+    MSS_G_PIECES = 5,          // pieces of the converged light walk
+    MSS_G_LUNITS = 6,          // light-unit edges
+    MSS_G_SPEC = 7,            // speculative light edges inside pieces
+    MSS_G_NLONG = MSS_G_TOTAL  // mss_vote_all borrows the word once the scans are done with it: segments filed for the whole grid
+};
+
+// the skip table: per 64-block and per 64 blocks (4096 scores) -- sum, sum of |score|, quantum, bit0: contains a positive score.
+// mss_scan_kernel and mss_light_kernel build it from eight __restrict__ parameters for mss_skip_blocks: as ONE by-value kernel argument
+// the pointers lose that qualifier, and the kernels measured 1.4 % and 2.3 % slower (profiles/mss_ladder_cliff_alternating.txt, series 1)
+struct mss_stats {
+    const double *blk_sum, *blk_abs; const int32_t *blk_q; const uint8_t *flags;
+    const double *sup_sum, *sup_abs; const int32_t *sup_q; const uint8_t *sup_flags;
+};
+
 struct mss_layout {            // carve of the caller's workspace
     int64_t nblk;
     uint64_t *blk;             // [nblk+1] per-64-block (boundary flag << 32 | positive-run starts), then scanned
@@ -67,7 +88,7 @@ struct mss_layout {            // carve of the caller's workspace
     int32_t *sup_q;            // [nsup]
     uint8_t *sup_flags;        // [nsup] bit0: contains a positive score
     uint64_t *tiles;           // scan scratch
-    uint64_t *grand;           // [8]: [0] scan total, [1] changed flag, [2] error flag, [3] total kept segments
+    uint64_t *grand;           // [8]: the words of mss_grand
     int64_t *ustart;           // [nunits+1] stretch starts
     int64_t *urun;             // [nunits+1] first stack/segment slot of each stretch
     double *exitL[2];          // [nunits] final L of each stretch, ping-pong
@@ -272,9 +293,9 @@ __global__ void __launch_bounds__(256) mss_units_kernel(const uint64_t *__restri
     if (b == 0) {
         ustart[0] = 0;
         urun[0] = 0;
-        const int64_t nunits = (int64_t)(grand[0] >> 32) + 1;
+        const int64_t nunits = (int64_t)(grand[MSS_G_TOTAL] >> 32) + 1;
         ustart[nunits] = n;
-        urun[nunits] = (int64_t)(grand[0] & 0xffffffffull);
+        urun[nunits] = (int64_t)(grand[MSS_G_TOTAL] & 0xffffffffull);
     }
     if (b >= nblk) return;
     if (mss_is_boundary(flags, blk_sum, b, nblk, n, thr)) {
@@ -353,6 +374,42 @@ __device__ __forceinline__ double mss_fold(double s, double a0, int t, int nvali
     return X;
 }
 
+// (3b) In the history-free state (no open run, max = -1e30) at a 64-block edge `pos`: whole all-non-positive blocks in front of `end`
+// are skipped under the certificate, up to 64 groups of 4096 scores at a 4096-edge, else up to 64 blocks.  Returns the scores skipped
+// (0: none) with cur moved over them; the caller moves pos.  (Moving pos in here through a reference as well measured 0.3-1 % slower
+// over the structure-free styles in three formulations; this one is level with the two copies it replaces or ahead of them.)
+__device__ __forceinline__ int64_t mss_skip_blocks(const mss_stats &st, double &cur, int64_t pos, int64_t end, int lane)
+{
+    if ((pos & 4095) == 0) {
+        // 64 groups of 4096 scores at a time
+        const int64_t gj = (pos >> 12) + lane;
+        const bool stop2 = gj * 4096 + 4096 > end || (st.sup_flags[gj] & 1);
+        const unsigned long long ms2 = __ballot(stop2);
+        const int m2 = ms2 ? __builtin_ctzll(ms2) : 64;
+        if (m2 > 0) {
+            const bool in = lane < m2;
+            const double gs = wave_sum(in ? st.sup_sum[gj] : 0.0);
+            const double ga = wave_sum(in ? st.sup_abs[gj] : 0.0);
+            const int gq = wave_max(in ? st.sup_q[gj] : MSS_QNONE);
+            if (mss_certified(cur, ga, gq)) { cur += gs; return (int64_t)m2 * 4096; }
+        }
+    }
+    const int64_t b0 = pos >> 6, bend = (end + 63) >> 6;
+    const int64_t bj = b0 + lane;
+    // stop at the next 4096-aligned position so that the coarser level takes over there
+    const bool stop = bj >= bend || (st.flags[bj] & 1) || (bj * 64 + 64 > end) || (lane > 0 && (bj & 63) == 0);
+    const unsigned long long mstop = __ballot(stop);
+    const int m = mstop ? __builtin_ctzll(mstop) : 64;
+    if (m > 0) {
+        const bool in = lane < m;
+        const double gs = wave_sum(in ? st.blk_sum[bj] : 0.0);
+        const double ga = wave_sum(in ? st.blk_abs[bj] : 0.0);
+        const int gq = wave_max(in ? st.blk_q[bj] : MSS_QNONE);
+        if (mss_certified(cur, ga, gq)) { cur += gs; return (int64_t)m * 64; }
+    }
+    return 0;
+}
+
 // One wave per stretch.
 __global__ void __launch_bounds__(64) mss_scan_kernel(const double *__restrict__ S, const int64_t *__restrict__ ustart,
                                                       const int64_t *__restrict__ urun, int64_t nunits,
@@ -364,9 +421,9 @@ __global__ void __launch_bounds__(64) mss_scan_kernel(const double *__restrict__
                                                       const int32_t *__restrict__ blk_q, const uint8_t *__restrict__ flags,
                                                       const double *__restrict__ sup_sum, const double *__restrict__ sup_abs,
                                                       const int32_t *__restrict__ sup_q, const uint8_t *__restrict__ sup_flags,
-                                                      int have_stats, int independent, int cutmode,
-                                                      mss_subent *subs, mss_cand *dump_all)
+                                                      int independent, int cutmode, mss_subent *subs, mss_cand *dump_all)
 {
+    const mss_stats stats = { blk_sum, blk_abs, blk_q, flags, sup_sum, sup_abs, sup_q, sup_flags };
     __shared__ double2 sLR[MSS_LCAP];                           // (L, R)
     __shared__ int4 sIdx[MSS_LCAP];                             // (st, en, pre, left-open)
     const int lane = threadIdx.x;
@@ -457,7 +514,7 @@ __global__ void __launch_bounds__(64) mss_scan_kernel(const double *__restrict__
         }
         const int lopen = j < 0 && !head ? 1 : 0;                // the search ran off a local stack: the stitch goes on from here
         if (j < 0 && head) { flush(); peak = R; }
-        if (was_reset && lane == 0) { atomicOr((unsigned long long *)&grand[2], 1ull); atomicOr((unsigned long long *)&grand[4], 8ull); }   // (a run behind a reset opens the next piece)
+        if (was_reset && lane == 0) { atomicOr((unsigned long long *)&grand[MSS_G_ERROR], 1ull); atomicOr((unsigned long long *)&grand[MSS_G_WHY], 8ull); }   // (a run behind a reset opens the next piece)
         if (nst < MSS_LCAP) {
             if (lane == 0) {
                 sLR[nst] = make_double2(tL, R);
@@ -481,43 +538,9 @@ __global__ void __launch_bounds__(64) mss_scan_kernel(const double *__restrict__
     int64_t pos = begin;
     while (pos < end) {
         const int nvalid = (int)min((int64_t)64, end - pos);
-        // ---- (3b) skip whole all-non-positive blocks in the history-free state --------------
-        if (have_stats && !run_open && peak == MSS_NEG && (pos & 63) == 0) {
-            if ((pos & 4095) == 0) {
-                // 64 groups of 4096 scores at a time
-                const int64_t gj = (pos >> 12) + lane;
-                const bool stop2 = gj * 4096 + 4096 > end || (sup_flags[gj] & 1);
-                const unsigned long long ms2 = __ballot(stop2);
-                const int m2 = ms2 ? __builtin_ctzll(ms2) : 64;
-                if (m2 > 0) {
-                    const bool in = lane < m2;
-                    const double gs = wave_sum(in ? sup_sum[gj] : 0.0);
-                    const double ga = wave_sum(in ? sup_abs[gj] : 0.0);
-                    const int gq = wave_max(in ? sup_q[gj] : MSS_QNONE);
-                    if (mss_certified(cur, ga, gq)) {
-                        cur += gs;
-                        pos += (int64_t)m2 * 4096;
-                        continue;
-                    }
-                }
-            }
-            const int64_t b0 = pos >> 6, bend = (end + 63) >> 6;
-            const int64_t bj = b0 + lane;
-            // stop at the next 4096-aligned position so that the coarser level takes over there
-            const bool stop = bj >= bend || (flags[bj] & 1) || (bj * 64 + 64 > end) || (lane > 0 && (bj & 63) == 0);
-            const unsigned long long mstop = __ballot(stop);
-            const int m = mstop ? __builtin_ctzll(mstop) : 64;
-            if (m > 0) {
-                const bool in = lane < m;
-                const double gs = wave_sum(in ? blk_sum[bj] : 0.0);
-                const double ga = wave_sum(in ? blk_abs[bj] : 0.0);
-                const int gq = wave_max(in ? blk_q[bj] : MSS_QNONE);
-                if (mss_certified(cur, ga, gq)) {
-                    cur += gs;
-                    pos += (int64_t)m * 64;
-                    continue;
-                }
-            }
+        if (!run_open && peak == MSS_NEG && (pos & 63) == 0) {
+            const int64_t adv = mss_skip_blocks(stats, cur, pos, end, lane);
+            if (adv) { pos += adv; continue; }
         }
         const double s = lane < nvalid ? S[pos + lane] : 0.0;
         const bool ispos = lane < nvalid && s > 0;
@@ -681,13 +704,13 @@ __global__ void __launch_bounds__(64) mss_scan_kernel(const double *__restrict__
     } else if (k == nunits - 1 || independent || cutmode) {
         flush();                                              // (cutmode: the next piece opens with a flush, mss_light_kernel)
     } else if (nst != 0 || peak != MSS_NEG) {
-        if (lane == 0) atomicOr((unsigned long long *)&grand[2], 1ull);   // forced-reset argument failed: caller falls back
+        if (lane == 0) atomicOr((unsigned long long *)&grand[MSS_G_ERROR], 1ull);   // forced-reset argument failed: caller falls back
     }
     if (lane == 0) {
         segcnt[k] = (uint64_t)nseg;
         const double want = sub ? subs[k + 1].L : exit_prev[k];
         if (!independent && (pass == 0 || __double_as_longlong(want) != __double_as_longlong(cur)))
-            atomicOr((unsigned long long *)&grand[1], 1ull);
+            atomicOr((unsigned long long *)&grand[MSS_G_CHANGED], 1ull);
         exit_cur[k] = cur;
     }
 }
@@ -803,7 +826,7 @@ __global__ void __launch_bounds__(64) mss_stitch_kernel(mss_subent *subs, int64_
                 pre = (int32_t)j;
                 delta = nT - i;
             } else {
-                if (i == 0 || e.pre < 0) { bad = true; if (lane == 0) atomicOr((unsigned long long *)&grand[4], 4ull); break; }   // (a local stack starts with a left-open candidate)
+                if (i == 0 || e.pre < 0) { bad = true; if (lane == 0) atomicOr((unsigned long long *)&grand[MSS_G_WHY], 4ull); break; }   // (a local stack starts with a left-open candidate)
                 pre = (int32_t)(e.pre + delta);
             }
             volatile mss_cand *o = T + nT;
@@ -813,7 +836,7 @@ __global__ void __launch_bounds__(64) mss_stitch_kernel(mss_subent *subs, int64_
         }
     }
     if (bad) {
-        if (lane == 0) atomicOr((unsigned long long *)&grand[2], 1ull);
+        if (lane == 0) atomicOr((unsigned long long *)&grand[MSS_G_ERROR], 1ull);
         return;
     }
     // the flush at the piece's end (mss.c:35-47), behind what the head and the stitch flushed on the way
@@ -907,6 +930,7 @@ __global__ void __launch_bounds__(64) mss_light_kernel(const double *__restrict_
     const int64_t begin = ustart[k], end = ustart[k + 1];
     const int64_t slot0 = urun[k];                            // slot of the first run that starts in this unit
     const bool forced = uforced[k] != 0;
+    const mss_stats stats = { blk_sum, blk_abs, blk_q, flags, sup_sum, sup_abs, sup_q, sup_flags };
     // entry state: empty for the first unit and in the first pass (a guess), else what the unit in front ended with last pass
     double cur = 0.0, peak = MSS_NEG, Lf = INFINITY, run_L = 0.0;
     bool run_open = false;
@@ -950,33 +974,9 @@ __global__ void __launch_bounds__(64) mss_light_kernel(const double *__restrict_
     int pf_q = 0;
     while (pos < end) {
         const int nvalid = (int)min((int64_t)(64 - (pos & 63)), end - pos);
-        // ---- skip whole all-non-positive blocks in the history-free state (as mss_scan_kernel does)
         if (!run_open && peak == MSS_NEG && (pos & 63) == 0) {
-            if ((pos & 4095) == 0) {
-                const int64_t gj = (pos >> 12) + lane;
-                const bool stop2 = gj * 4096 + 4096 > end || (sup_flags[gj] & 1);
-                const unsigned long long ms2 = __ballot(stop2);
-                const int m2 = ms2 ? __builtin_ctzll(ms2) : 64;
-                if (m2 > 0) {
-                    const bool in = lane < m2;
-                    const double gs = wave_sum(in ? sup_sum[gj] : 0.0);
-                    const double ga = wave_sum(in ? sup_abs[gj] : 0.0);
-                    const int gq = wave_max(in ? sup_q[gj] : MSS_QNONE);
-                    if (mss_certified(cur, ga, gq)) { cur += gs; pos += (int64_t)m2 * 4096; continue; }
-                }
-            }
-            const int64_t b0 = pos >> 6, bend = (end + 63) >> 6;
-            const int64_t bj = b0 + lane;
-            const bool stop = bj >= bend || (flags[bj] & 1) || (bj * 64 + 64 > end) || (lane > 0 && (bj & 63) == 0);
-            const unsigned long long mstop = __ballot(stop);
-            const int m = mstop ? __builtin_ctzll(mstop) : 64;
-            if (m > 0) {
-                const bool in = lane < m;
-                const double gs = wave_sum(in ? blk_sum[bj] : 0.0);
-                const double ga = wave_sum(in ? blk_abs[bj] : 0.0);
-                const int gq = wave_max(in ? blk_q[bj] : MSS_QNONE);
-                if (mss_certified(cur, ga, gq)) { cur += gs; pos += (int64_t)m * 64; continue; }
-            }
+            const int64_t adv = mss_skip_blocks(stats, cur, pos, end, lane);
+            if (adv) { pos += adv; continue; }
         }
         const bool whole = nvalid == 64;                      // then pos is a block edge
         double s, sabs;
@@ -1116,7 +1116,7 @@ __global__ void __launch_bounds__(64) mss_light_kernel(const double *__restrict_
     if (lane == 0) {
         // a stretch boundary was placed where a reset is forced: behind it the reference's state must be empty
         if (k != nunits - 1 && uforced[k + 1] && (Lf != INFINITY || peak != MSS_NEG || run_open))
-            atomicOr((unsigned long long *)&grand[2], 1ull);
+            atomicOr((unsigned long long *)&grand[MSS_G_ERROR], 1ull);
         mss_light_state x;
         x.L = cur; x.peak = peak; x.Lf = Lf; x.run_L = run_open ? run_L : 0.0;
         x.run_st = run_open ? run_st : 0; x.run_slot = run_open ? run_slot : 0; x.last_blk = last_blk; x.open = run_open ? 1 : 0;
@@ -1126,7 +1126,7 @@ __global__ void __launch_bounds__(64) mss_light_kernel(const double *__restrict_
             const long long *o = (const long long *)&st_prev[k], *w = (const long long *)&x;
             for (int i = 0; i < 8; ++i) same = same && o[i] == w[i];
         }
-        if (!same) atomicOr((unsigned long long *)&grand[1], 1ull);
+        if (!same) atomicOr((unsigned long long *)&grand[MSS_G_CHANGED], 1ull);
         st_cur[k] = x;
         cut_cnt[k] = (uint64_t)ncut;
     }
@@ -1320,13 +1320,13 @@ __global__ void __launch_bounds__(256) mss_vote_long_kernel(const int32_t *__res
     }
 }
 
-// A9 over the kept segments (l.segs_out, count in grand[3]); l.segs is free by now: the list of the long ones and their counters
+// A9 over the kept segments (l.segs_out, count in grand[MSS_G_NSEG]); l.segs is free by now: the list of the long ones and their counters
 static int mss_vote_all(const mss_layout &l, const int8_t *d_cls, int nof_labels, int8_t *d_labels_out, int64_t n, hipStream_t stream)
 {
     const int64_t longcap = n / MSS_VOTE_LONG + 1;                 // ((1 + DGRP_MAXC) longcap ints <= the 2 (n / 2 + 2) of l.segs)
-    unsigned long long *nlong = (unsigned long long *)l.grand;     // grand[0]: the scans are done with it
+    unsigned long long *nlong = (unsigned long long *)(l.grand + MSS_G_NLONG);   // (the scans are done with the word)
     DGRP_HIP(hipMemsetAsync(nlong, 0, 8, stream));
-    hipLaunchKernelGGL(mss_vote_kernel, dim3(1024), dim3(256), 0, stream, l.segs_out, l.grand + 3, d_cls, nof_labels, d_labels_out, nlong,
+    hipLaunchKernelGGL(mss_vote_kernel, dim3(1024), dim3(256), 0, stream, l.segs_out, l.grand + MSS_G_NSEG, d_cls, nof_labels, d_labels_out, nlong,
                        l.segs, longcap);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(mss_vote_long_kernel<0>, dim3(1024), dim3(256), 0, stream, l.segs_out, d_cls, nof_labels, d_labels_out, nlong, l.segs,
@@ -1338,11 +1338,288 @@ static int mss_vote_all(const mss_layout &l, const int8_t *d_cls, int nof_labels
     return DGRP_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The host side.  What both entry points share comes first; then dgrp_mss_labels' LADDER, one function per rung.  A rung takes the
+// record (MSS_TOOK: its kept segments stand in l.segs_out, their count in grand[MSS_G_NSEG]), or leaves it to the next rung (MSS_NEXT:
+// not applicable to this record, or a kernel's own consistency check tripped), or fails hard (a DGRP_E* code, all negative).
+// ------------------------------------------------------------------------------------------
+enum { MSS_TOOK = DGRP_OK, MSS_NEXT = 1 };
+
+// the DGRP_MSS_* switches (tools/README.md), read on every call: blocks per light unit; NO_CUTS: straight to mss_scan_uncut;
+// NO_SUB: no parts, the pieces are scanned whole (mss_scan_pieces); TRACE: a line per level on stderr
+struct mss_knobs { int sub; bool no_cuts, no_sub, trace; };
+static mss_knobs mss_read_knobs()
+{
+    const char *e = getenv("DGRP_MSS_SUB");
+    return mss_knobs{ e && atoi(e) > 0 ? atoi(e) : MSS_LIGHT_SUB, getenv("DGRP_MSS_NO_CUTS") != nullptr,
+                      getenv("DGRP_MSS_NO_SUB") != nullptr, getenv("DGRP_MSS_TRACE") != nullptr };
+}
+
+// pymss.pyx:46-53 and mss.c:35 (int truncation of the threshold); thr: a chain of non-positive blocks summing below -thr forces a reset
+struct mss_par { double xdrop; int min_sc; double thr; };
+static mss_par mss_params(int min_mss_len, int xdrop_len)
+{
+    const double s0 = log(0.99 / (1.0 - 0.99));
+    const double xdrop = xdrop_len > 0 ? s0 * xdrop_len * 10.0 : -1;
+    return mss_par{ xdrop, (int)(s0 * min_mss_len), xdrop > 0.0 ? xdrop + 1.0 : -1.0 };
+}
+
+// both levels of the skip table over l.nblk blocks of n scores; l.blk takes the run starts per block
+static int mss_block_stats(const mss_layout &l, const double *d_scores, int64_t n, hipStream_t stream)
+{
+    hipLaunchKernelGGL(mss_blockstat_kernel, dim3((unsigned)((l.nblk + 3) / 4)), dim3(256), 0, stream, d_scores, n, l.blk,
+                       l.blk_sum, l.blk_abs, l.blk_q, l.flags);
+    DGRP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mss_superstat_kernel, dim3((unsigned)((l.nsup + 3) / 4)), dim3(256), 0, stream, l.blk_sum, l.blk_abs,
+                       l.blk_q, l.flags, l.nblk, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+// words of the workspace to the host, and the wait for them
+static int mss_fetch(uint64_t *h, const uint64_t *d, int nwords, hipStream_t stream)
+{
+    DGRP_HIP(hipMemcpyAsync(h, d, (size_t)nwords * 8, hipMemcpyDeviceToHost, stream));
+    DGRP_HIP(hipStreamSynchronize(stream));
+    return DGRP_OK;
+}
+
+// what one launch of mss_scan_kernel scans, a wave per unit
+enum mss_scan_mode {
+    MSS_SCAN_STRETCHES,       // l.ustart / l.urun, pass `pass` of the fixed point: entries are the exits of pass - 1 (l.exitL, ping-pong)
+    MSS_SCAN_RECORDS,         // l.ustart / l.urun: independent records, each from L = 0 to the end-of-sequence flush
+    MSS_SCAN_PIECES,          // l.ustart2 / l.urun2: every piece from its known entry (l.entry2) to a flush, its exit held against the next entry
+    MSS_SCAN_PARTS            // l.subs: the pieces cut again at speculative edges, stacks left in l.dump for mss_stitch_kernel
+};
+// (pieces and parts: `pass` is the light walk's last pass -- the exits, which nobody reads, go to the side of l.exitL that walk left free)
+static int mss_scan(const mss_layout &l, const double *d_scores, const mss_par &par, mss_scan_mode mode, int64_t nunits, int pass,
+                    hipStream_t stream)
+{
+    const bool cut = mode >= MSS_SCAN_PIECES, parts = mode == MSS_SCAN_PARTS;
+    hipLaunchKernelGGL(mss_scan_kernel, dim3((unsigned)nunits), dim3(64), 0, stream, d_scores, cut ? l.ustart2 : l.ustart,
+                       cut ? l.urun2 : l.urun, nunits, cut ? l.entry2 + 1 : l.exitL[(pass + 1) & 1], l.exitL[(cut ? pass + 1 : pass) & 1],
+                       l.stack, l.segs, l.segcnt, par.min_sc, par.xdrop, l.grand, cut ? 1 : pass, l.blk_sum, l.blk_abs,
+                       l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, mode == MSS_SCAN_RECORDS ? 1 : 0, cut ? 1 : 0, parts ? (mss_subent *)l.subs : nullptr, parts ? l.dump : nullptr);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+// the kept segments of the units that scan left -> one ordered list in l.segs_out, the total in grand[MSS_G_NSEG]
+static int mss_collect(const mss_layout &l, mss_scan_mode mode, int64_t nunits, hipStream_t stream)
+{
+    if (int rc = device_exclusive_scan(l.segcnt, l.segcnt, nunits, l.tiles, l.grand + MSS_G_NSEG, stream)) return rc;
+    hipLaunchKernelGGL(mss_compact_kernel, dim3((unsigned)((nunits + 255) / 256)), dim3(256), 0, stream, l.segs,
+                       mode >= MSS_SCAN_PIECES ? l.urun2 : l.urun, l.segcnt, l.grand + MSS_G_NSEG, nunits, l.segs_out,
+                       mode == MSS_SCAN_PARTS ? (const mss_subent *)l.subs : nullptr);
+    DGRP_LAUNCH_CHECK();
+    return DGRP_OK;
+}
+
+// one dgrp_mss_labels call: what every rung reads, and what the rungs hand down
+struct mss_job {
+    mss_layout l; const double *d_scores; int64_t n; mss_par par; mss_knobs knobs; hipStream_t stream;
+    int64_t nunits;           // stretches (mss_stretch_units)
+    int64_t nl;               // light units, and the pass in which their walk converged: its end states are l.lstate[pass & 1]
+    int pass;                 //   (mss_light_walk)
+    int64_t npieces;          // pieces (mss_piece_table)
+};
+
+// The stretch level: the unit table l.ustart / l.urun -- the record cut at its forced resets (mss_is_boundary), or (`single`, or no
+// x-drop) the record as one stretch: the plain sequential scan, still chunked and certified -- and the exits of "pass -1".
+static int mss_stretch_units(mss_job &j, bool single)
+{
+    const mss_layout &l = j.l;
+    hipStream_t stream = j.stream;
+    j.nunits = 1;
+    if (!single && j.par.xdrop > 0.0) {
+        hipLaunchKernelGGL(mss_boundary_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream,
+                           l.flags, l.blk_sum, l.nblk, j.n, j.par.thr, l.blk);
+        DGRP_LAUNCH_CHECK();
+        if (int rc = device_exclusive_scan(l.blk, l.blk, l.nblk, l.tiles, l.grand + MSS_G_TOTAL, stream)) return rc;
+        hipLaunchKernelGGL(mss_units_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.blk, l.flags,
+                           l.blk_sum, l.nblk, j.n, j.par.thr, l.ustart, l.urun, l.grand);
+        DGRP_LAUNCH_CHECK();
+        uint64_t g = 0;
+        if (int rc = mss_fetch(&g, l.grand + MSS_G_TOTAL, 1, stream)) return rc;
+        j.nunits = (int64_t)(g >> 32) + 1;
+    } else {
+        const int64_t h[2] = { 0, j.n }, r[2] = { 0, 0 };
+        DGRP_HIP(hipMemcpyAsync(l.ustart, h, 16, hipMemcpyHostToDevice, stream));
+        DGRP_HIP(hipMemcpyAsync(l.urun, r, 16, hipMemcpyHostToDevice, stream));
+        DGRP_HIP(hipStreamSynchronize(stream));
+    }
+    DGRP_REQUIRE(j.nunits < (1ll << 31), "dgrp_mss_labels: too many stretches");
+    DGRP_HIP(hipMemsetAsync(l.exitL[0], 0, j.nunits * 8, stream));
+    DGRP_HIP(hipMemsetAsync(l.exitL[1], 0, j.nunits * 8, stream));
+    return DGRP_OK;
+}
+
+// Second level: flush cuts (mss_light_kernel).  The light walk finds every stretch's entry L by the same fixed point the scan used to
+// run with the full stack machinery, and cuts the stretches where the reference's stack is flushed.  Its units: the stretches, cut
+// further every knobs.sub blocks where the input can reset by x-drop.  MSS_TOOK: converged, j.nl units, end states in l.lstate[j.pass & 1]
+// and the cuts of that last walk filed by 64-block; MSS_NEXT: inconsistent.
+static int mss_light_walk(mss_job &j)
+{
+    const mss_layout &l = j.l;
+    hipStream_t stream = j.stream;
+    j.nl = 1;
+    if (j.par.xdrop > 0.0) {
+        hipLaunchKernelGGL(mss_lightflag_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.flags, l.blk_sum,
+                           l.nblk, j.n, j.par.thr, j.knobs.sub, 1, l.lblk);
+        DGRP_LAUNCH_CHECK();
+        if (int rc = device_exclusive_scan(l.lblk, l.lblk, l.nblk, l.tiles, l.grand + MSS_G_LUNITS, stream)) return rc;
+        hipLaunchKernelGGL(mss_lightunits_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.lblk, l.grand + MSS_G_LUNITS,
+                           l.flags, l.blk_sum, l.blk, l.grand + MSS_G_TOTAL, l.nblk, j.n, j.par.thr, j.knobs.sub, 1, l.lstart, l.lrun, l.lforced);
+        DGRP_LAUNCH_CHECK();
+        uint64_t g = 0;
+        if (int rc = mss_fetch(&g, l.grand + MSS_G_LUNITS, 1, stream)) return rc;
+        j.nl = (int64_t)g + 1;
+    } else {
+        const int64_t h[2] = { 0, j.n }, r[2] = { 0, 0 };
+        const uint8_t f[2] = { 1, 1 };
+        DGRP_HIP(hipMemcpyAsync(l.lstart, h, 16, hipMemcpyHostToDevice, stream));
+        DGRP_HIP(hipMemcpyAsync(l.lrun, r, 16, hipMemcpyHostToDevice, stream));
+        DGRP_HIP(hipMemcpyAsync(l.lforced, f, 2, hipMemcpyHostToDevice, stream));
+        DGRP_HIP(hipStreamSynchronize(stream));
+    }
+    bool failed = false;
+    int pass = 0;
+    for (;; ++pass) {
+        DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_CHANGED, 0, 8, stream));
+        DGRP_HIP(hipMemsetAsync(l.cut_st, 0xff, l.nblk * 8, stream));
+        hipLaunchKernelGGL(mss_light_kernel, dim3((unsigned)j.nl), dim3(64), 0, stream, j.d_scores, l.lstart, l.lrun, l.lforced, j.nl,
+                           (const mss_light_state *)l.lstate[(pass + 1) & 1], (mss_light_state *)l.lstate[pass & 1], j.par.xdrop, l.grand,
+                           pass, l.blk_sum, l.blk_abs, l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, l.cutcnt, l.cut_st, l.cut_run, l.cut_L, l.cut_kj);
+        DGRP_LAUNCH_CHECK();
+        uint64_t g[3] = { 0, 0, 0 };
+        if (int rc = mss_fetch(g, l.grand, 3, stream)) return rc;
+        if (g[MSS_G_ERROR]) { failed = true; break; }
+        if (j.nl == 1 || (pass > 0 && g[MSS_G_CHANGED] == 0)) break;
+        if (pass > j.nl + 2) { failed = true; break; }
+    }
+    if (j.knobs.trace) fprintf(stderr, "dgrp_mss_labels: n=%lld stretches=%lld light units=%lld passes=%d%s\n", (long long)j.n,
+                               (long long)j.nunits, (long long)j.nl, pass + 1, failed ? " FAILED" : "");
+    j.pass = pass;
+    return failed ? MSS_NEXT : MSS_TOOK;
+}
+
+// The pieces of the converged walk: pieces per unit -> offsets, then every piece to its slot of l.ustart2 / l.urun2 / l.entry2, and the
+// end sentinel behind them.  MSS_NEXT: a piece count that cannot be.
+static int mss_piece_table(mss_job &j)
+{
+    const mss_layout &l = j.l;
+    hipStream_t stream = j.stream;
+    const mss_light_state *lst = (const mss_light_state *)l.lstate[j.pass & 1];
+    if (int rc = device_exclusive_scan(l.cutcnt, l.cutcnt, j.nl, l.tiles, l.grand + MSS_G_PIECES, stream)) return rc;
+    const int64_t piece_cap = 2 * l.nblk + 2, threads = j.nl > l.nblk ? j.nl : l.nblk;
+    hipLaunchKernelGGL(mss_pieces_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lrun, l.lforced,
+                       j.nl, lst, l.cutcnt, l.cut_st, l.cut_run, l.cut_L, l.cut_kj, l.nblk, piece_cap, l.ustart2, l.urun2, l.entry2);
+    DGRP_LAUNCH_CHECK();
+    uint64_t np = 0;
+    if (int rc = mss_fetch(&np, l.grand + MSS_G_PIECES, 1, stream)) return rc;
+    j.npieces = (int64_t)np;
+    if (j.npieces < 1 || j.npieces > piece_cap) return MSS_NEXT;
+    DGRP_HIP(hipMemcpyAsync(l.ustart2 + j.npieces, &j.n, 8, hipMemcpyHostToDevice, stream));   // (j outlives the copy: the caller's frame)
+    DGRP_HIP(hipMemcpyAsync(l.entry2 + j.npieces, lst + (j.nl - 1), 8, hipMemcpyDeviceToDevice, stream));   // .L is the first field
+    return MSS_TOOK;
+}
+
+// Third level: a piece that spans speculative light edges is scanned in parts, all at once, each on a local stack from the edge's
+// converged state, and stitched (mss_subent, mss_stitch_kernel).  MSS_NEXT: no such edge, light units too small for the dump slots
+// (MSS_SUB_MIN), or something the stitch does not take -- a local stack deeper than the LDS part, an impossible event.
+static int mss_scan_parts(mss_job &j)
+{
+    const mss_layout &l = j.l;
+    hipStream_t stream = j.stream;
+    if (j.nl <= 1 || !(j.par.xdrop > 0.0) || j.knobs.no_sub || j.knobs.sub < MSS_SUB_MIN) return MSS_NEXT;
+    hipLaunchKernelGGL(mss_specvalid_kernel, dim3((unsigned)((j.nl + 1 + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lforced,
+                       j.nl, l.ustart2, j.npieces, l.lblk);
+    DGRP_LAUNCH_CHECK();
+    if (int rc = device_exclusive_scan(l.lblk, l.lblk, j.nl + 1, l.tiles, l.grand + MSS_G_SPEC, stream)) return rc;
+    uint64_t nv = 0;
+    if (int rc = mss_fetch(&nv, l.grand + MSS_G_SPEC, 1, stream)) return rc;
+    if (nv == 0 || 2 * (int64_t)nv + 2 > l.dump_cap || j.npieces + (int64_t)nv > l.nblk) return MSS_NEXT;   // (segcnt / exitL hold nblk + 1 units)
+    const int64_t nsub = j.npieces + (int64_t)nv;
+    const int64_t threads = (j.npieces > j.nl ? j.npieces : j.nl) + 1;
+    hipLaunchKernelGGL(mss_subtable_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lrun,
+                       l.lforced, j.nl, (const mss_light_state *)l.lstate[j.pass & 1], l.lblk, l.grand + MSS_G_SPEC, l.ustart2,
+                       l.urun2, l.entry2, j.npieces, j.n, (mss_subent *)l.subs);
+    DGRP_LAUNCH_CHECK();
+    DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_CHANGED, 0, 16, stream));       // changed, error
+    DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_WHY, 0, 8, stream));
+    if (int rc = mss_scan(l, j.d_scores, j.par, MSS_SCAN_PARTS, nsub, j.pass, stream)) return rc;
+    hipLaunchKernelGGL(mss_stitch_kernel, dim3((unsigned)nsub), dim3(64), 0, stream, (mss_subent *)l.subs, nsub, l.stack, l.dump, l.segs,
+                       l.segcnt, j.par.min_sc, l.grand);
+    DGRP_LAUNCH_CHECK();
+    uint64_t g[5] = { 0, 0, 0, 0, 0 };
+    if (int rc = mss_fetch(g, l.grand, 5, stream)) return rc;
+    const bool bad = g[MSS_G_CHANGED] || g[MSS_G_ERROR];
+    if (j.knobs.trace)
+        fprintf(stderr, "dgrp_mss_labels: %lld pieces in %lld parts (%llu speculative edges inside pieces)%s (exit %llu, error %llu, why %llu)\n",
+                (long long)j.npieces, (long long)nsub, (unsigned long long)nv, bad ? ": not stitched" : "",
+                (unsigned long long)g[MSS_G_CHANGED], (unsigned long long)g[MSS_G_ERROR], (unsigned long long)g[MSS_G_WHY]);
+    if (bad) return MSS_NEXT;
+    return mss_collect(l, MSS_SCAN_PARTS, nsub, stream);
+}
+
+// ONE pass of the stack scan over the pieces, each whole, from its known entry L.  MSS_NEXT: inconsistent -- a piece whose exit L
+// differs from the next piece's entry, bit for bit.
+static int mss_scan_pieces(mss_job &j)
+{
+    const mss_layout &l = j.l;
+    DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_CHANGED, 0, 16, j.stream));     // changed, error
+    if (int rc = mss_scan(l, j.d_scores, j.par, MSS_SCAN_PIECES, j.npieces, j.pass, j.stream)) return rc;
+    uint64_t g[3] = { 0, 0, 0 };
+    if (int rc = mss_fetch(g, l.grand, 3, j.stream)) return rc;
+    if (g[MSS_G_CHANGED] || g[MSS_G_ERROR]) return MSS_NEXT;
+    return mss_collect(l, MSS_SCAN_PIECES, j.npieces, j.stream);
+}
+
+// The uncut scan: the stack scan over the stretches, to the fixed point of their entry L's.  MSS_NEXT: inconsistent.
+static int mss_scan_uncut(mss_job &j)
+{
+    const mss_layout &l = j.l;
+    for (int pass = 0;; ++pass) {
+        DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_CHANGED, 0, 8, j.stream));
+        if (int rc = mss_scan(l, j.d_scores, j.par, MSS_SCAN_STRETCHES, j.nunits, pass, j.stream)) return rc;
+        uint64_t g[3] = { 0, 0, 0 };
+        if (int rc = mss_fetch(g, l.grand, 3, j.stream)) return rc;
+        if (g[MSS_G_ERROR]) return MSS_NEXT;
+        if (j.nunits == 1 || (pass > 0 && g[MSS_G_CHANGED] == 0)) break;
+        if (pass > j.nunits + 2) return MSS_NEXT;
+    }
+    return mss_collect(l, MSS_SCAN_STRETCHES, j.nunits, j.stream);
+}
+
+// One trip down the ladder.  MSS_NEXT: a consistency check tripped where no lower rung is left -- the caller goes again with `single`.
+static int mss_ladder(mss_job &j, bool single)
+{
+    const mss_layout &l = j.l;
+    DGRP_HIP(hipMemsetAsync(l.grand, 0, 64, j.stream));
+    if (int rc = mss_stretch_units(j, single)) return rc;
+    if (!single && !j.knobs.no_cuts) {
+        int rc = mss_light_walk(j);
+        if (rc != MSS_TOOK) return rc;                       // (inconsistent: a forced reset did not reset -- the stretches themselves are in doubt)
+        rc = mss_piece_table(j);
+        if (rc == MSS_TOOK) {
+            rc = mss_scan_parts(j);
+            if (rc == MSS_NEXT) rc = mss_scan_pieces(j);
+        }
+        if (rc != MSS_NEXT) return rc;
+        // inconsistent: on to the uncut scan (exits start from zero again)
+        DGRP_HIP(hipMemsetAsync(l.exitL[0], 0, j.nunits * 8, j.stream));
+        DGRP_HIP(hipMemsetAsync(l.exitL[1], 0, j.nunits * 8, j.stream));
+        DGRP_HIP(hipMemsetAsync(l.grand + MSS_G_CHANGED, 0, 16, j.stream));
+    }
+    return mss_scan_uncut(j);
+}
+
 DGRP_EXPORT int dgrp_mss_labels(const double *d_scores, const int8_t *d_cls, int64_t n, int nof_labels,
                                 int min_mss_len, int xdrop_len, int8_t *d_labels_out, int64_t *d_nseg,
                                 void *d_work, int64_t work_bytes, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
+    const mss_knobs knobs = mss_read_knobs();
     DGRP_REQUIRE(n >= 0 && n < (1ll << 31), "dgrp_mss_labels: n=%lld out of range (the reference indexes with int)", (long long)n);
     DGRP_REQUIRE(nof_labels >= 2 && nof_labels <= DGRP_MAXC, "dgrp_mss_labels: nof_labels must be in 2..64");
     if (n == 0) {
@@ -1350,241 +1627,23 @@ DGRP_EXPORT int dgrp_mss_labels(const double *d_scores, const int8_t *d_cls, int
         return DGRP_OK;
     }
     DGRP_REQUIRE(d_scores && d_cls && d_labels_out && d_work, "dgrp_mss_labels: NULL pointer");
-    mss_layout l = mss_carve(d_work, n);
+    const mss_layout l = mss_carve(d_work, n);
     if (work_bytes < l.bytes) {
         dgrp_set_error("dgrp_mss_labels: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
         return DGRP_ENOMEM;
     }
-    // pymss.pyx:46-53 and mss.c:35 (int truncation of the threshold)
-    const double s0 = log(0.99 / (1.0 - 0.99));
-    const double xdrop = xdrop_len > 0 ? s0 * xdrop_len * 10.0 : -1;
-    const int min_sc = (int)(s0 * min_mss_len);
-    const double thr = xdrop > 0.0 ? xdrop + 1.0 : -1.0;
-
     DGRP_HIP(hipMemsetAsync(l.blk, 0, (l.nblk + 1) * 8, stream));
-    hipLaunchKernelGGL(mss_blockstat_kernel, dim3((unsigned)((l.nblk + 3) / 4)), dim3(256), 0, stream, d_scores, n, l.blk,
-                       l.blk_sum, l.blk_abs, l.blk_q, l.flags);
-    DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mss_superstat_kernel, dim3((unsigned)((l.nsup + 3) / 4)), dim3(256), 0, stream, l.blk_sum, l.blk_abs,
-                       l.blk_q, l.flags, l.nblk, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags);
-    DGRP_LAUNCH_CHECK();
+    if (int rc = mss_block_stats(l, d_scores, n, stream)) return rc;
 
-    bool single = false;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        int64_t nunits = 1;
-        DGRP_HIP(hipMemsetAsync(l.grand, 0, 64, stream));
-        if (!single && xdrop > 0.0) {
-            if (attempt == 0) {
-                hipLaunchKernelGGL(mss_boundary_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream,
-                                   l.flags, l.blk_sum, l.nblk, n, thr, l.blk);
-                DGRP_LAUNCH_CHECK();
-                int rc = device_exclusive_scan(l.blk, l.blk, l.nblk, l.tiles, l.grand, stream);
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(mss_units_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.blk, l.flags,
-                               l.blk_sum, l.nblk, n, thr, l.ustart, l.urun, l.grand);
-            DGRP_LAUNCH_CHECK();
-            uint64_t g = 0;
-            DGRP_HIP(hipMemcpyAsync(&g, l.grand, 8, hipMemcpyDeviceToHost, stream));
-            DGRP_HIP(hipStreamSynchronize(stream));
-            nunits = (int64_t)(g >> 32) + 1;
-        } else {
-            // one stretch: the plain sequential scan (still chunked and certified)
-            int64_t h[2] = { 0, n };
-            DGRP_HIP(hipMemcpyAsync(l.ustart, h, 16, hipMemcpyHostToDevice, stream));
-            int64_t r[2] = { 0, 0 };
-            DGRP_HIP(hipMemcpyAsync(l.urun, r, 16, hipMemcpyHostToDevice, stream));
-            DGRP_HIP(hipStreamSynchronize(stream));
-        }
-        DGRP_REQUIRE(nunits < (1ll << 31), "dgrp_mss_labels: too many stretches");
-        DGRP_HIP(hipMemsetAsync(l.exitL[0], 0, nunits * 8, stream));
-        DGRP_HIP(hipMemsetAsync(l.exitL[1], 0, nunits * 8, stream));
-        bool failed = false;
-        // ---- second level: flush cuts (mss_light_kernel).  The light walk finds every stretch's entry L by the same fixed point
-        // the scan used to run with the full stack machinery, and cuts the stretches where the reference's stack is flushed;
-        // then ONE pass of the stack scan over the pieces, each from its known entry L.  Any inconsistency (a piece whose exit L
-        // differs from the next piece's entry, bit for bit) sends the record through the uncut scan below.
-        bool done = false;
-        if (!single && !getenv("DGRP_MSS_NO_CUTS")) {
-            // light units: the stretches, cut further every `sub` blocks where the input can reset by x-drop
-            int64_t nl = 1;
-            if (xdrop > 0.0) {
-                const char *e = getenv("DGRP_MSS_SUB");
-                const int sub = e && atoi(e) > 0 ? atoi(e) : MSS_LIGHT_SUB;
-                hipLaunchKernelGGL(mss_lightflag_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.flags, l.blk_sum,
-                                   l.nblk, n, thr, sub, 1, l.lblk);
-                DGRP_LAUNCH_CHECK();
-                int rc1 = device_exclusive_scan(l.lblk, l.lblk, l.nblk, l.tiles, l.grand + 6, stream);
-                if (rc1) return rc1;
-                hipLaunchKernelGGL(mss_lightunits_kernel, dim3((unsigned)((l.nblk + 255) / 256)), dim3(256), 0, stream, l.lblk, l.grand + 6,
-                                   l.flags, l.blk_sum, l.blk, l.grand, l.nblk, n, thr, sub, 1, l.lstart, l.lrun, l.lforced);
-                DGRP_LAUNCH_CHECK();
-                uint64_t g6 = 0;
-                DGRP_HIP(hipMemcpyAsync(&g6, l.grand + 6, 8, hipMemcpyDeviceToHost, stream));
-                DGRP_HIP(hipStreamSynchronize(stream));
-                nl = (int64_t)g6 + 1;
-            } else {
-                const int64_t h[2] = { 0, n }, r[2] = { 0, 0 };
-                const uint8_t f[2] = { 1, 1 };
-                DGRP_HIP(hipMemcpyAsync(l.lstart, h, 16, hipMemcpyHostToDevice, stream));
-                DGRP_HIP(hipMemcpyAsync(l.lrun, r, 16, hipMemcpyHostToDevice, stream));
-                DGRP_HIP(hipMemcpyAsync(l.lforced, f, 2, hipMemcpyHostToDevice, stream));
-                DGRP_HIP(hipStreamSynchronize(stream));
-            }
-            int pass = 0;
-            for (;; ++pass) {
-                DGRP_HIP(hipMemsetAsync(l.grand + 1, 0, 8, stream));
-                DGRP_HIP(hipMemsetAsync(l.cut_st, 0xff, l.nblk * 8, stream));
-                hipLaunchKernelGGL(mss_light_kernel, dim3((unsigned)nl), dim3(64), 0, stream, d_scores, l.lstart, l.lrun, l.lforced, nl,
-                                   (const mss_light_state *)l.lstate[(pass + 1) & 1], (mss_light_state *)l.lstate[pass & 1], xdrop, l.grand,
-                                   pass, l.blk_sum, l.blk_abs, l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, l.cutcnt,
-                                   l.cut_st, l.cut_run, l.cut_L, l.cut_kj);
-                DGRP_LAUNCH_CHECK();
-                uint64_t g[3] = { 0, 0, 0 };
-                DGRP_HIP(hipMemcpyAsync(g, l.grand, 24, hipMemcpyDeviceToHost, stream));
-                DGRP_HIP(hipStreamSynchronize(stream));
-                if (g[2]) { failed = true; break; }
-                if (nl == 1 || (pass > 0 && g[1] == 0)) break;
-                if (pass > nl + 2) { failed = true; break; }
-            }
-            if (getenv("DGRP_MSS_TRACE")) fprintf(stderr, "dgrp_mss_labels: n=%lld stretches=%lld light units=%lld passes=%d%s\n", (long long)n,
-                                                  (long long)nunits, (long long)nl, pass + 1, failed ? " FAILED" : "");
-            if (failed) {
-                if (single) { dgrp_set_error("dgrp_mss_labels: sequential scan reported an inconsistent state"); return DGRP_EHIP; }
-                single = true;
-                continue;
-            }
-            // pieces per unit -> offsets, then every piece to its slot (the last walk's table is the converged one)
-            int rc2 = device_exclusive_scan(l.cutcnt, l.cutcnt, nl, l.tiles, l.grand + 5, stream);
-            if (rc2) return rc2;
-            const int64_t piece_cap = 2 * l.nblk + 2;
-            {
-                const int64_t threads = nl > l.nblk ? nl : l.nblk;
-                hipLaunchKernelGGL(mss_pieces_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lrun, l.lforced,
-                                   nl, (const mss_light_state *)l.lstate[pass & 1], l.cutcnt, l.cut_st, l.cut_run, l.cut_L, l.cut_kj, l.nblk,
-                                   piece_cap, l.ustart2, l.urun2, l.entry2);
-                DGRP_LAUNCH_CHECK();
-            }
-            uint64_t np = 0;
-            DGRP_HIP(hipMemcpyAsync(&np, l.grand + 5, 8, hipMemcpyDeviceToHost, stream));
-            DGRP_HIP(hipStreamSynchronize(stream));
-            const int64_t npieces = (int64_t)np;
-            if (npieces >= 1 && npieces <= piece_cap) {
-                DGRP_HIP(hipMemcpyAsync(l.ustart2 + npieces, &n, 8, hipMemcpyHostToDevice, stream));
-                DGRP_HIP(hipMemcpyAsync(l.entry2 + npieces, (const mss_light_state *)l.lstate[pass & 1] + (nl - 1), 8, hipMemcpyDeviceToDevice,
-                                        stream));   // .L is the first field
-                // ---- third level: a piece that spans speculative light edges is scanned in parts, all at once, each on a local stack
-                // from the edge's converged state, and stitched (mss_subent, mss_stitch_kernel).  Anything the stitch does not take -- a
-                // local stack deeper than the LDS part, an impossible event -- sends the pieces through the scan whole, as before.
-                bool sub_done = false;
-                mss_subent *subs = (mss_subent *)l.subs;
-                if (nl > 1 && xdrop > 0.0 && !getenv("DGRP_MSS_NO_SUB")) {
-                    const char *e = getenv("DGRP_MSS_SUB");
-                    const int sub = e && atoi(e) > 0 ? atoi(e) : MSS_LIGHT_SUB;
-                    if (sub >= MSS_SUB_MIN) {
-                        hipLaunchKernelGGL(mss_specvalid_kernel, dim3((unsigned)((nl + 1 + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lforced,
-                                           nl, l.ustart2, npieces, l.lblk);
-                        DGRP_LAUNCH_CHECK();
-                        int rcv = device_exclusive_scan(l.lblk, l.lblk, nl + 1, l.tiles, l.grand + 7, stream);
-                        if (rcv) return rcv;
-                        uint64_t nv = 0;
-                        DGRP_HIP(hipMemcpyAsync(&nv, l.grand + 7, 8, hipMemcpyDeviceToHost, stream));
-                        DGRP_HIP(hipStreamSynchronize(stream));
-                        if (nv > 0 && 2 * (int64_t)nv + 2 <= l.dump_cap && npieces + (int64_t)nv <= l.nblk) {   // (segcnt / exitL hold nblk + 1 units)
-                            const int64_t nsub = npieces + (int64_t)nv;
-                            const int64_t threads = (npieces > nl ? npieces : nl) + 1;
-                            hipLaunchKernelGGL(mss_subtable_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, l.lstart, l.lrun,
-                                               l.lforced, nl, (const mss_light_state *)l.lstate[pass & 1], l.lblk, l.grand + 7, l.ustart2,
-                                               l.urun2, l.entry2, npieces, n, subs);
-                            DGRP_LAUNCH_CHECK();
-                            DGRP_HIP(hipMemsetAsync(l.grand + 1, 0, 16, stream));
-                            DGRP_HIP(hipMemsetAsync(l.grand + 4, 0, 8, stream));
-                            hipLaunchKernelGGL(mss_scan_kernel, dim3((unsigned)nsub), dim3(64), 0, stream, d_scores, l.ustart2, l.urun2, nsub,
-                                               l.entry2 + 1, l.exitL[(pass + 1) & 1], l.stack, l.segs, l.segcnt, min_sc, xdrop, l.grand, 1,
-                                               l.blk_sum, l.blk_abs, l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, 1, 0, 1, subs,
-                                               l.dump);
-                            DGRP_LAUNCH_CHECK();
-                            hipLaunchKernelGGL(mss_stitch_kernel, dim3((unsigned)nsub), dim3(64), 0, stream, subs, nsub, l.stack, l.dump, l.segs,
-                                               l.segcnt, min_sc, l.grand);
-                            DGRP_LAUNCH_CHECK();
-                            uint64_t g[5] = { 0, 0, 0, 0, 0 };
-                            DGRP_HIP(hipMemcpyAsync(g, l.grand, 40, hipMemcpyDeviceToHost, stream));
-                            DGRP_HIP(hipStreamSynchronize(stream));
-                            if (getenv("DGRP_MSS_TRACE"))
-                                fprintf(stderr, "dgrp_mss_labels: %lld pieces in %lld parts (%llu speculative edges inside pieces)%s (exit %llu, error %llu, why %llu)\n",
-                                        (long long)npieces, (long long)nsub, (unsigned long long)nv, g[1] || g[2] ? ": not stitched" : "",
-                                        (unsigned long long)g[1], (unsigned long long)g[2], (unsigned long long)g[4]);
-                            if (!g[1] && !g[2]) {
-                                int rc3 = device_exclusive_scan(l.segcnt, l.segcnt, nsub, l.tiles, l.grand + 3, stream);
-                                if (rc3) return rc3;
-                                hipLaunchKernelGGL(mss_compact_kernel, dim3((unsigned)((nsub + 255) / 256)), dim3(256), 0, stream, l.segs,
-                                                   l.urun2, l.segcnt, l.grand + 3, nsub, l.segs_out, (const mss_subent *)subs);
-                                DGRP_LAUNCH_CHECK();
-                                done = sub_done = true;
-                            }
-                        }
-                    }
-                }
-                if (!sub_done) {
-                DGRP_HIP(hipMemsetAsync(l.grand + 1, 0, 16, stream));
-                hipLaunchKernelGGL(mss_scan_kernel, dim3((unsigned)npieces), dim3(64), 0, stream, d_scores, l.ustart2, l.urun2, npieces,
-                                   l.entry2 + 1, l.exitL[(pass + 1) & 1], l.stack, l.segs, l.segcnt, min_sc, xdrop, l.grand, 1, l.blk_sum,
-                                   l.blk_abs, l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, 1, 0, 1, (mss_subent *)nullptr,
-                                   (mss_cand *)nullptr);
-                DGRP_LAUNCH_CHECK();
-                uint64_t g[3] = { 0, 0, 0 };
-                DGRP_HIP(hipMemcpyAsync(g, l.grand, 24, hipMemcpyDeviceToHost, stream));
-                DGRP_HIP(hipStreamSynchronize(stream));
-                if (!g[1] && !g[2]) {
-                    int rc3 = device_exclusive_scan(l.segcnt, l.segcnt, npieces, l.tiles, l.grand + 3, stream);
-                    if (rc3) return rc3;
-                    hipLaunchKernelGGL(mss_compact_kernel, dim3((unsigned)((npieces + 255) / 256)), dim3(256), 0, stream, l.segs, l.urun2,
-                                       l.segcnt, l.grand + 3, npieces, l.segs_out, (const mss_subent *)nullptr);
-                    DGRP_LAUNCH_CHECK();
-                    done = true;
-                }
-                }
-            }
-            if (done) break;
-            // inconsistent: fall through to the uncut scan (exits start from zero again)
-            DGRP_HIP(hipMemsetAsync(l.exitL[0], 0, nunits * 8, stream));
-            DGRP_HIP(hipMemsetAsync(l.exitL[1], 0, nunits * 8, stream));
-            DGRP_HIP(hipMemsetAsync(l.grand + 1, 0, 16, stream));
-        }
-        for (int pass = 0;; ++pass) {
-            // pass p reads the exits of pass p-1 from exitL[(p+1)&1] and writes exitL[p&1]
-            DGRP_HIP(hipMemsetAsync(l.grand + 1, 0, 8, stream));
-            hipLaunchKernelGGL(mss_scan_kernel, dim3((unsigned)nunits), dim3(64), 0, stream, d_scores, l.ustart, l.urun,
-                               nunits, l.exitL[(pass + 1) & 1], l.exitL[pass & 1], l.stack, l.segs, l.segcnt, min_sc, xdrop,
-                               l.grand, pass, l.blk_sum, l.blk_abs, l.blk_q, l.flags, l.sup_sum, l.sup_abs, l.sup_q,
-                               l.sup_flags, 1, 0, 0, (mss_subent *)nullptr, (mss_cand *)nullptr);
-            DGRP_LAUNCH_CHECK();
-            uint64_t g[3] = { 0, 0, 0 };
-            DGRP_HIP(hipMemcpyAsync(g, l.grand, 24, hipMemcpyDeviceToHost, stream));
-            DGRP_HIP(hipStreamSynchronize(stream));
-            if (g[2]) { failed = true; break; }
-            if (nunits == 1 || (pass > 0 && g[1] == 0)) break;
-            if (pass > nunits + 2) { failed = true; break; }
-        }
-        if (failed) {
-            if (single) { dgrp_set_error("dgrp_mss_labels: sequential scan reported an inconsistent state"); return DGRP_EHIP; }
-            single = true;
-            continue;
-        }
-        // kept segments -> one ordered list
-        int rc = device_exclusive_scan(l.segcnt, l.segcnt, nunits, l.tiles, l.grand + 3, stream);
-        if (rc) return rc;
-        hipLaunchKernelGGL(mss_compact_kernel, dim3((unsigned)((nunits + 255) / 256)), dim3(256), 0, stream, l.segs, l.urun,
-                           l.segcnt, l.grand + 3, nunits, l.segs_out, (const mss_subent *)nullptr);
-        DGRP_LAUNCH_CHECK();
-        break;
-    }
+    mss_job j = { l, d_scores, n, mss_params(min_mss_len, xdrop_len), knobs, stream };
+    int rc = mss_ladder(j, false);
+    if (rc == MSS_NEXT) rc = mss_ladder(j, true);            // again as one stretch: the sequential scan
+    if (rc == MSS_NEXT) { dgrp_set_error("dgrp_mss_labels: sequential scan reported an inconsistent state"); return DGRP_EHIP; }
+    if (rc) return rc;
+
     DGRP_HIP(hipMemcpyAsync(d_labels_out, d_cls, n, hipMemcpyDeviceToDevice, stream));
-    {
-        const int rcv = mss_vote_all(l, d_cls, nof_labels, d_labels_out, n, stream);
-        if (rcv) return rcv;
-    }
-    if (d_nseg) DGRP_HIP(hipMemcpyAsync(d_nseg, l.grand + 3, 8, hipMemcpyDeviceToDevice, stream));
+    if (int rcv = mss_vote_all(l, d_cls, nof_labels, d_labels_out, n, stream)) return rcv;
+    if (d_nseg) DGRP_HIP(hipMemcpyAsync(d_nseg, l.grand + MSS_G_NSEG, 8, hipMemcpyDeviceToDevice, stream));
     return DGRP_OK;
 }
 
@@ -1603,7 +1662,7 @@ DGRP_EXPORT int dgrp_mss_segments_host(const void *d_work, int64_t work_bytes, i
     // dgrp_mss_labels writes the list behind its last synchronisation, on the caller's stream; this function has no stream argument and
     // the blocking copies below run on the null stream, which a non-blocking stream does not wait for: wait for the device
     DGRP_HIP(hipDeviceSynchronize());
-    DGRP_HIP(hipMemcpy(&cnt, l.grand + 3, 8, hipMemcpyDeviceToHost));
+    DGRP_HIP(hipMemcpy(&cnt, l.grand + MSS_G_NSEG, 8, hipMemcpyDeviceToHost));
     *n_seg = (int64_t)cnt;
     const int64_t take = (int64_t)cnt < cap ? (int64_t)cnt : cap;
     if (take > 0 && h_st_en) DGRP_HIP(hipMemcpy(h_st_en, l.segs_out, take * 8, hipMemcpyDeviceToHost));
@@ -1641,30 +1700,17 @@ DGRP_EXPORT int dgrp_mss_labels_batch(const double *d_scores, const int8_t *d_cl
     }
     l.nblk = (total_n + 63) / 64;
     l.nsup = (l.nblk + 63) / 64;
-    const double s0 = log(0.99 / (1.0 - 0.99));
-    const double xdrop = xdrop_len > 0 ? s0 * xdrop_len * 10.0 : -1;
-    const int min_sc = (int)(s0 * min_mss_len);
-    hipLaunchKernelGGL(mss_blockstat_kernel, dim3((unsigned)((l.nblk + 3) / 4)), dim3(256), 0, stream, d_scores, total_n, l.blk,
-                       l.blk_sum, l.blk_abs, l.blk_q, l.flags);
-    hipLaunchKernelGGL(mss_superstat_kernel, dim3((unsigned)((l.nsup + 3) / 4)), dim3(256), 0, stream, l.blk_sum, l.blk_abs,
-                       l.blk_q, l.flags, l.nblk, l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags);
-    DGRP_LAUNCH_CHECK();
+    const mss_par par = mss_params(min_mss_len, xdrop_len);
+    if (int rc = mss_block_stats(l, d_scores, total_n, stream)) return rc;
     std::vector<int64_t> urun((size_t)nrec + 1);
     for (int64_t r = 0; r <= nrec; ++r) urun[(size_t)r] = h_start[r] / 2 + 2 * r;      // a record of n scores has at most n/2 + 1 runs
     DGRP_HIP(hipMemcpyAsync(l.ustart, h_start, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, stream));
     DGRP_HIP(hipMemcpyAsync(l.urun, urun.data(), (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, stream));
     DGRP_HIP(hipMemsetAsync(l.grand, 0, 64, stream));
-    hipLaunchKernelGGL(mss_scan_kernel, dim3((unsigned)nrec), dim3(64), 0, stream, d_scores, l.ustart, l.urun, nrec, l.exitL[1],
-                       l.exitL[0], l.stack, l.segs, l.segcnt, min_sc, xdrop, l.grand, 0, l.blk_sum, l.blk_abs, l.blk_q, l.flags,
-                       l.sup_sum, l.sup_abs, l.sup_q, l.sup_flags, 1, 1, 0, (mss_subent *)nullptr, (mss_cand *)nullptr);
-    DGRP_LAUNCH_CHECK();
-    int rc = device_exclusive_scan(l.segcnt, l.segcnt, nrec, l.tiles, l.grand + 3, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(mss_compact_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, stream, l.segs, l.urun, l.segcnt,
-                       l.grand + 3, nrec, l.segs_out, (const mss_subent *)nullptr);
-    DGRP_LAUNCH_CHECK();
+    if (int rc = mss_scan(l, d_scores, par, MSS_SCAN_RECORDS, nrec, 0, stream)) return rc;
+    if (int rc = mss_collect(l, MSS_SCAN_RECORDS, nrec, stream)) return rc;
     DGRP_HIP(hipMemcpyAsync(d_labels_out, d_cls, total_n, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(mss_vote_kernel, dim3(1024), dim3(256), 0, stream, l.segs_out, l.grand + 3, d_cls, nof_labels, d_labels_out,
+    hipLaunchKernelGGL(mss_vote_kernel, dim3(1024), dim3(256), 0, stream, l.segs_out, l.grand + MSS_G_NSEG, d_cls, nof_labels, d_labels_out,
                        (unsigned long long *)nullptr, (int32_t *)nullptr, (int64_t)0);
     DGRP_LAUNCH_CHECK();
     // the urun vector must outlive the asynchronous copy

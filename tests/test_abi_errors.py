@@ -227,3 +227,16 @@ def test_size_queries_are_total_functions():
     for f in ("dgrp_fasta_workspace_bytes", "dgrp_mss_workspace_bytes", "dgrp_segments_workspace_bytes"):
         sizes = [getattr(L, f)(n) for n in (1, 1000, 10 ** 6, 10 ** 8, 2 ** 31 - 1)]
         assert sizes == sorted(sizes) and sizes[0] > 0, (f, sizes)
+
+
+# dgrp_mss_workspace_bytes / dgrp_mss_batch_workspace_bytes as commit 6461cd0 (the parent of the labels driver's split into rungs)
+# answered: dgrp_mss_segments_host recovers n from the byte count by bisection over the carve, so the carve is part of the ABI.
+MSS_WORKSPACE_BYTES = {0: 27136, 1: 29952, 63: 31488, 64: 31488, 65: 31488, 4095: 151040, 4096: 151040, 4097: 153088,
+                       16384 * 3 + 1: 1539840, 1 << 20: 32243456, (1 << 31) - 1: 65979181568}
+MSS_BATCH_WORKSPACE_BYTES = {(0, 0): 31488, (128, 2): 35328, (1 << 20, 400): 32291840}
+
+
+def test_mss_workspace_carve_is_pinned():
+    L = lib()
+    assert {n: L.dgrp_mss_workspace_bytes(n) for n in MSS_WORKSPACE_BYTES} == MSS_WORKSPACE_BYTES
+    assert {a: L.dgrp_mss_batch_workspace_bytes(*a) for a in MSS_BATCH_WORKSPACE_BYTES} == MSS_BATCH_WORKSPACE_BYTES

@@ -510,6 +510,56 @@ def test_mss_stitched_pieces(L, dev, orc, drift, exact, xd, monkeypatch, capfd):
         assert "parts (" in err and "not stitched" not in err, err        # the upward drift is the case this path exists for
 
 
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("xd", [50, 3])
+def test_mss_every_rung_one_input(L, dev, orc, exact, xd, monkeypatch, capfd):
+    """One input down every rung of dgrp_mss_labels' ladder: pieces in stitched parts, then pieces scanned whole
+    (DGRP_MSS_NO_SUB), then the uncut multi-pass scan (DGRP_MSS_NO_CUTS; also where every "inconsistent" verdict lands).  70 001
+    scores in light units of 256 64-blocks, the smallest that may be stitched: four full units, a short one and a tail that is no
+    multiple of 64; a forced reset and a dip off the unit edges.  The inexact style may decline the stitch: it asserts equality only."""
+    monkeypatch.setenv("DGRP_MSS_SUB", "256")
+    monkeypatch.setenv("DGRP_MSS_TRACE", "1")
+    rng = np.random.default_rng(xd + (17 if exact else 0))
+    n = 70_001
+    scores = rng.normal(0.3, 1.0, size=n)
+    if exact:
+        scores = np.round(scores * 1024) / 1024
+    else:
+        scores[::7] *= 2.0 ** -17
+        scores[:2000] += 3000.0
+    scores[rng.random(n) < 0.01] = 0.0
+    scores[30_000:30_200] = -40.0                                         # a forced reset, not on a unit edge
+    scores[50_000:50_040] = -3.0
+    cls = rng.integers(0, 5, size=n).astype(np.int64)
+    want, segs = orc.find_mss_labels(scores, cls, 5, 3, xd, return_segments=True)
+    want_segs = np.array([(a, b) for a, b, _ in segs], np.int32).reshape(-1, 2)
+    d_s, d_l = _t(scores, dev), _t(cls.astype(np.int8), dev)
+    wb = L.dgrp_mss_workspace_bytes(n)
+    traces = []
+    for knob in (None, "DGRP_MSS_NO_SUB", "DGRP_MSS_NO_CUTS"):
+        if knob:
+            monkeypatch.setenv(knob, "1")
+        lab = torch.empty(n, dtype=torch.int8, device=dev)
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        nseg = torch.zeros(1, dtype=torch.int64, device=dev)
+        _check(L.dgrp_mss_labels(d_s.data_ptr(), d_l.data_ptr(), n, 5, 3, xd, lab.data_ptr(), nseg.data_ptr(),
+                                 work.data_ptr(), wb, _sp()))
+        torch.cuda.synchronize()
+        traces.append(capfd.readouterr().err)
+        assert int(nseg.item()) == len(segs), knob
+        np.testing.assert_array_equal(lab.cpu().numpy(), want, err_msg=str(knob))
+        buf = np.zeros((max(len(segs), 1), 2), np.int32)
+        cnt = C.c_int64()
+        _check(L.dgrp_mss_segments_host(work.data_ptr(), work.numel(), buf.ctypes.data_as(C.c_void_p), len(buf), C.byref(cnt)))
+        assert cnt.value == len(segs), knob
+        np.testing.assert_array_equal(buf[:len(segs)], want_segs, err_msg=str(knob))
+    if exact:
+        parts, whole, uncut = traces
+        assert "parts (" in parts and "not stitched" not in parts, parts
+        assert "light units=" in whole and "parts (" not in whole, whole
+        assert "light units=" not in uncut and "parts (" not in uncut, uncut
+
+
 @pytest.mark.parametrize("u,T,s,B,N,lane", [(36, 60, 10, 7, 9001, 64), (60, 100, 25, 256, 20011, 160), (20, 40, 5, 5, 3003, 16)])
 def test_lanes_merge_identical(dev, orc, L, u, T, s, B, N, lane, monkeypatch):
     """dgrp_forward_merge_record on lanes (the chunks of an attention model's record alternating between three internal streams,
