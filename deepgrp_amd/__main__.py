@@ -62,10 +62,21 @@ from typing import Iterator, List, TextIO, Tuple
 
 import numpy as np
 
+from . import bed, masking, repeatseq, summary, tracks
+from .outfiles import class_list
+
 logging.basicConfig()
 _LOG = logging.getLogger(__name__)
 
 DEFAULT_COHORT = 8                   # optimize --cohort: the job count with the lowest measured time per job
+
+# The optional outputs of `predict`, each a module with add_options, refuse_on_evaluate, plan and from_plan, in the
+# order in which their plans are made (and `evaluate` sends their flags back), in which --help lists them, in which the plans meet
+# the model's class count, and in which the files of an input are committed.
+_OUTPUTS = (bed, masking, repeatseq, summary, tracks)
+_HELP_ORDER = (masking, tracks, bed, repeatseq, summary)
+_BIND_ORDER = (tracks, repeatseq, masking, bed, summary)
+_COMMIT_ORDER = (tracks, bed, masking, repeatseq, summary)
 
 
 def _read_multi_fasta(filestream: TextIO) -> Iterator[Tuple[str, str]]:
@@ -150,139 +161,45 @@ class _RowsByRecord:
         return np.concatenate(self.parts) if self.parts else np.zeros(0, SEGMENT_DTYPE)
 
 
-def _class_list(text: str) -> Tuple[int, ...]:
-    """--mask_classes: comma-separated labels."""
-    try:
-        out = tuple(int(x) for x in text.split(",") if x.strip())
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not a comma-separated list of labels: {text!r}") from None
-    if not out:
-        raise argparse.ArgumentTypeError("no label given")
-    return out
+class _Stages:
+    """predict -vv: the stage callback of RecordRunner.run_record for one record -- a device sync and a clock around every stage,
+    and the reference's debug lines (deepgrp/__main__.py:69-79), the stage's milliseconds in those of the tracks and the scores."""
 
+    def __init__(self, header: str, use_mss: bool):
+        self.header, self.use_mss, self.bases, self.ms, self.t = header, use_mss, 0, {}, 0.0
 
-def _add_mask_options(parser, suppress: bool) -> None:
-    """The masking flags: on `predict` and, for the README form with the flags in front, on the main parser as well (the values
-    are only set where given, so neither parser's default hides the other's)."""
-    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
-    parser.add_argument("--mask_dir", type=str, default=d(None),
-                        help="(addition) also write a masked copy of every input FASTA file as DIR/<basename of the input>")
-    parser.add_argument("--mask", choices=("soft", "hard"), default=d("soft"),
-                        help="(addition) soft: predicted repeats lower case, the rest upper case; hard: predicted repeats 'N'")
-    parser.add_argument("--mask_classes", type=_class_list, default=d(None),
-                        help="(addition) comma-separated labels to mask, e.g. 1,3 (default: every label > 0)")
-    parser.add_argument("--mask_gzip", action="store_true", default=d(False),
-                        help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
-                             "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
-    parser.add_argument("--mask_twobit", action="store_true", default=d(False),
-                        help="(addition) with --mask_dir: write every masked copy as a UCSC .2bit file (soft mask = mask blocks, hard "
-                             "mask = N blocks; packed on the GPU) to DIR/<basename>.2bit instead of FASTA text, and accept "
-                             "gzip-compressed inputs; one process only")
-    parser.add_argument("--gzip_level", type=int, default=d(None),
-                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig, --bed_gzip and --bed_bigbed: 0 "
-                             "literals "
-                             "only, 1 with matches (default: 0 for masked copies, 1 for tracks and the BED)")
+    def __call__(self, what: str, done: bool, bases: int = 0) -> None:
+        import time
 
+        import torch
+        if not done:
+            self.t = time.perf_counter()
+            if what == "encode":
+                _LOG.debug("One hot encoding sequence.")
+            elif what == "forward":
+                _LOG.debug("Start prediction.")
+            elif what == "labels" and self.use_mss:
+                _LOG.debug("Applying MSS.")
+            return
+        torch.cuda.synchronize()
+        self.ms[what] = (time.perf_counter() - self.t) * 1e3
+        if what == "encode":
+            self.bases = bases
+        elif what == "forward":
+            _LOG.debug("Finish prediction.")
+        elif what == "tracks":
+            _LOG.debug("%s: probability tracks %.2f ms", self.header, self.ms[what])
+        elif what == "scores":
+            _LOG.debug("%s: row scores %.2f ms", self.header, self.ms[what])
 
-def _add_track_options(parser) -> None:
-    """The probability-track flags, like the masking flags on `predict` and on the main parser, set only where given."""
-    s = argparse.SUPPRESS
-    parser.add_argument("--track_dir", type=str, default=s,
-                        help="(addition) also write the merged per-base probabilities of every selected class as bedGraph files "
-                             "DIR/<basename of the input>.class<c>.bedGraph ('stdin' for '-'); with --fast they are those of the "
-                             "fp16-operand kernels")
-    parser.add_argument("--track_gzip", action="store_true", default=s,
-                        help="(addition) with --track_dir: write every track as BGZF (bgzip's format, deflated on the GPU where the "
-                             "text is made) to DIR/<basename>.class<c>.bedGraph.gz")
-    parser.add_argument("--track_index", action="store_true", default=s,
-                        help="(addition) with --track_gzip: write the tabix index <track>.gz.tbi of every track, built on the GPU "
-                             "beside the text (records must end at or below 2^29 and names must not reappear after another name; "
-                             "otherwise a warning and no index)")
-    parser.add_argument("--track_bigwig", action="store_true", default=s,
-                        help="(addition) with --track_dir: write every track as bigWig, DIR/<basename>.class<c>.bw, instead of bedGraph: "
-                             "the same items in binary sections with zoom levels, built and deflated on the GPU (--gzip_level, 1 unless "
-                             "given).  A chromosome's size is the end of its predicted span (trailing N are not counted).  Record "
-                             "names must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and "
-                             "no bigWig for that input.  Not with --track_gzip or --track_index")
-    parser.add_argument("--track_classes", type=_class_list, default=s,
-                        help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
-    parser.add_argument("--track_digits", type=int, default=s,
-                        help="(addition) decimals of the track values, 1..4 (default: 2)")
-    parser.add_argument("--track_bin", type=int, default=s,
-                        help="(addition) bin width of the tracks in bases, >= 1; a bin's value is the maximum over its bases "
-                             "(default: 1)")
-
-
-def _add_bed_options(parser) -> None:
-    """The scored-BED flags, like the track flags on `predict` and on the main parser, set only where given."""
-    s = argparse.SUPPRESS
-    parser.add_argument("--bed_dir", type=str, default=s,
-                        help="(addition) also write the predicted repeats of every input as BED, DIR/<basename of the input>.bed ('stdin' "
-                             "for '-'): name, start, end, class<label>, score 0..1000, '.', then the mean and the smallest merged "
-                             "probability of the row's class over its bases and the share of its bases at which that class is the "
-                             "largest, four decimals each; summed on the GPU; one process only")
-    parser.add_argument("--bed_min_score", type=int, default=s,
-                        help="(addition) with --bed_dir: leave out BED lines whose score is below this, 0..1000 (the TSV is not filtered)")
-    parser.add_argument("--bed_gzip", action="store_true", default=s,
-                        help="(addition) with --bed_dir: write the BED as BGZF (bgzip's format) to DIR/<basename>.bed.gz; the lines are "
-                             "written and deflated on the GPU (--gzip_level, 1 unless given)")
-    parser.add_argument("--bed_index", action="store_true", default=s,
-                        help="(addition) with --bed_gzip: write the tabix index <basename>.bed.gz.tbi, built on the GPU beside the text "
-                             "(records must end at or below 2^29 and names must not reappear after another name; otherwise a warning "
-                             "and no index)")
-    parser.add_argument("--bed_bigbed", action="store_true", default=s,
-                        help="(addition) with --bed_dir: write the scored repeats as bigBed, DIR/<basename>.bb, instead of BED text: one "
-                             "item per BED line (bed6+3, the extra columns typed by an autoSql declaration) with coverage zoom levels, "
-                             "built and deflated on the GPU (--gzip_level, 1 unless given); coordinates up to 2^32 - 1.  Record names "
-                             "must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and no "
-                             "bigBed for that input.  Not with --bed_gzip or --bed_index")
-    parser.add_argument("--bed_gff3", action="store_true", default=s,
-                        help="(addition) with --bed_dir: write the scored repeats as GFF3, DIR/<basename>.gff3, instead of BED text: "
-                             "'##gff-version 3', then per row seqid, deepgrp, repeat_region, start+1, end, mean, '.', '.', "
-                             "ID=r<ordinal>;Name=class<label>;label=;score=;min=;agree= with the BED's figures, written on the GPU.  "
-                             "With --bed_gzip DIR/<basename>.gff3.gz (BGZF), with --bed_index its tabix index (gff preset) beside it.  "
-                             "A record with an empty name: a warning and no GFF3 for that input.  Not with --bed_bigbed")
-    parser.add_argument("--bed_names", type=str, default=s,
-                        help="(addition) with --bed_gff3: the names of the labels 1..classes-1, comma-separated, written as Name= in the "
-                             "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped); with --summary_dir: the "
-                             "label column of its tables")
-
-
-def _add_seq_options(parser) -> None:
-    """The repeat-sequence flags, like the track flags on `predict` and on the main parser, set only where given."""
-    s = argparse.SUPPRESS
-    parser.add_argument("--seq_dir", type=str, default=s,
-                        help="(addition) also write the sequences of the predicted repeats of every input as FASTA, DIR/<basename of "
-                             "the input>.repeats.fa: per TSV row one record '>NAME:A-B class<label>' (0-based, half-open, as bedtools "
-                             "getfasta names it) with the bases of the row exactly as the input has them, gathered on the GPU; one "
-                             "process only")
-    parser.add_argument("--seq_classes", type=_class_list, default=s,
-                        help="(addition) with --seq_dir: comma-separated labels to write, e.g. 1,3 (default: every label > 0)")
-    parser.add_argument("--seq_flank", type=int, default=s,
-                        help="(addition) with --seq_dir: also take up to N bases on either side of every row, clamped to the record; "
-                             "the header then ends in ' core=<start>-<end>' (default: 0)")
-    parser.add_argument("--seq_width", type=int, default=s,
-                        help="(addition) with --seq_dir: bases per line, 1..2^30 (default: 60)")
-    parser.add_argument("--seq_gzip", action="store_true", default=s,
-                        help="(addition) with --seq_dir: write the FASTA as BGZF (bgzip's format) to DIR/<basename>.repeats.fa.gz, "
-                             "deflated on the GPU (--gzip_level, 1 unless given)")
-    parser.add_argument("--seq_fai", action="store_true", default=s,
-                        help="(addition) with --seq_dir: also write the samtools faidx index DIR/<basename>.repeats.fa.fai; not with "
-                             "--seq_gzip")
-
-
-def _add_summary_options(parser) -> None:
-    """The repeat-content flags, like the repeat-sequence flags on `predict` and on the main parser, set only where given."""
-    s = argparse.SUPPRESS
-    parser.add_argument("--summary_dir", type=str, default=s,
-                        help="(addition) also write the repeat content of every input as DIR/<basename of the input>.summary.tsv: per "
-                             "record and label (and for all labels > 0 together, and for the whole file) rows, bases, A, C, G, T, "
-                             "other, lower case, min, max and N50 of the row lengths, share of the record, of its ACGT bases, GC, and "
-                             "recall and precision against the input's own soft mask, counted on the GPU; --bed_names names the "
-                             "labels; one process only")
-    parser.add_argument("--summary_bin", type=int, default=s,
-                        help="(addition) with --summary_dir: also DIR/<basename>.density.tsv, per record and bin of N sequence "
-                             "positions the ACGT bases and the positions under every label > 0 (N >= 1)")
+    def close(self, rows) -> int:
+        """The record's closing line (none for a record without a base).  -> its bases"""
+        ms, n = self.ms, self.bases
+        if n:
+            _LOG.debug("%s: %d bases; encode %.2f ms, forward + merge %.2f ms (%.1f Mbp/s), %s %.2f ms, segments + read-back %.2f ms, %d rows",
+                       self.header, n, ms["encode"], ms["forward"], n / max(ms["forward"], 1e-6) / 1e3,
+                       "scores + MSS + vote" if self.use_mss else "softmax", ms["labels"], ms["segments"], len(rows))
+        return n
 
 
 class CommandLineParser:
@@ -308,11 +225,8 @@ class CommandLineParser:
         self.parser.add_argument("--threads", "-t", type=int, default=1, help="Accepted for compatibility (ignored)")
         self.parser.add_argument("--xla", action="store_true", help="Accepted for compatibility (ignored)")
         self.parser.add_argument("-v", "--verbose", action="count", default=0, help="Increase verbosity")
-        _add_mask_options(self.parser, suppress=True)
-        _add_track_options(self.parser)
-        _add_bed_options(self.parser)
-        _add_seq_options(self.parser)
-        _add_summary_options(self.parser)
+        for output in _HELP_ORDER:
+            output.add_options(self.parser)
         train = subparsers.add_parser(name="train", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
                                       description="Train a deepgrp model (GRU) on the GPU")
         train.add_argument("parameter", type=str)
@@ -376,11 +290,8 @@ class CommandLineParser:
         predict.add_argument("--split_contigs", action="store_true",
                              help="multi-GPU only: spread the windows of EVERY record over all GPUs (for a few huge "
                                   "records) instead of sharding whole records")
-        _add_mask_options(predict, suppress=True)
-        _add_track_options(predict)
-        _add_bed_options(predict)
-        _add_seq_options(predict)
-        _add_summary_options(predict)
+        for output in _HELP_ORDER:
+            output.add_options(predict)
         evaluate = subparsers.add_parser(
             name="evaluate", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
             description="(addition) score the rows `predict` writes with the same flags against a repeat annotation: per-class "
@@ -401,7 +312,7 @@ class CommandLineParser:
                                                                  "header (.npz: the file name up to the first '.')")
         evaluate.add_argument("--no_use_mss", "-m", action="store_true", help="Disable maximum scoring segment algorithm")
         evaluate.add_argument("--fast", action="store_true", help="fp16-operand fused kernels, as for predict")
-        evaluate.add_argument("--repeats", type=_class_list, default=None,
+        evaluate.add_argument("--repeats", type=class_list, default=None,
                               help="comma-separated repeat numbers to keep from the annotation (default: 1..C-1 of the model)")
         evaluate.add_argument("--min_overlap", type=float, default=0.5,
                               help="an element is found (a predicted row supported) when at least this fraction of its bases "
@@ -495,21 +406,8 @@ class CommandLineParser:
     @staticmethod
     def predict(args: argparse.Namespace, options) -> None:
         """Predict with deepgrp (deepgrp/__main__.py:252-297)."""
-        from . import bed
-        from . import tracks as tk
-        tk.check_gzip_flags(args)                               # refusals come before anything runs
-        bed_plan = bed.plan(args)
-        masks = CommandLineParser._mask_plan(args)
-        seqs = CommandLineParser._seq_plan(args)
-        summaries = CommandLineParser._summary_plan(args)
-        track_plan = tk.plan(args)
-        track_spec = None
-        if track_plan is not None:
-            from .model import read_keras_hdf5
-            track_spec = tk.resolve(track_plan, int(read_keras_hdf5(args.model)["ff_kernel"].shape[-1]))
-        if seqs is not None and seqs["classes"] is not None:
-            from .model import read_keras_hdf5
-            CommandLineParser._check_seq_classes(seqs, int(read_keras_hdf5(args.model)["ff_kernel"].shape[-1]))
+        tracks.check_gzip_flags(args)                           # refusals come before anything runs
+        plans = {m: m.plan(args) for m in _OUTPUTS}
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             from .gz import compressed_inputs
             packed = compressed_inputs(args.FASTA)
@@ -521,12 +419,17 @@ class CommandLineParser:
             if packed and not getattr(args, "split_contigs", False):
                 sys.exit(f"{packed[0]} is a 2bit file: the ranks share a file out by byte ranges of FASTA text, and a 2bit file has "
                          "none (WORLD_SIZE > 1); convert it to FASTA, pass --split_contigs or run in one process")
+        # host work first: the model file is read once, and every plan meets its class count before the GPU is touched
+        from . import model as dgmodel
+        _LOG.debug("Loading model %s!", args.model)
+        weights = dgmodel.read_keras_hdf5(args.model)
+        classes = int(weights["ff_kernel"].shape[-1])
+        bound = {m: m.from_plan(plans[m], classes) for m in _BIND_ORDER if plans[m] is not None}
+        outputs = [bound[m] for m in _COMMIT_ORDER if m in bound]
+        masks = bound.get(masking)                              # the one output several ranks can write
         import torch
         import torch.distributed as dist
-        from . import model as dgmodel
-        from .distributed import gather_records, shard_contigs
-        from .fasta import read_multi_fasta_device
-        from .pipeline import SEGMENT_DTYPE, ContigPipeline, record_indices
+        from .pipeline import SEGMENT_DTYPE, record_indices
         from .runner import RecordRunner, rows_text
 
         world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -546,17 +449,9 @@ class CommandLineParser:
 
         if getattr(args, "precise", False) and getattr(args, "fast", False):
             sys.exit("--precise and --fast exclude each other")
-        _LOG.debug("Loading model %s!", args.model)
-        model = dgmodel.load_model(args.model, custom_objects={"ReverseComplement": dgmodel.ReverseComplement})
+        model = dgmodel.device_model(weights)
         options.vecsize = model.input_shape[1]
         _LOG.info("Model loading finished successfully!")
-        if masks is not None:
-            CommandLineParser._check_mask_classes(args, model.output_shape[2])
-        if bed_plan is not None and bed_plan.class_names is not None and len(bed_plan.class_names) != model.output_shape[2] - 1:
-            sys.exit(f"--bed_names gives {len(bed_plan.class_names)} names, but the model has {model.output_shape[2] - 1} repeat classes "
-                     f"(labels 1..{model.output_shape[2] - 1})")
-        if summaries is not None:
-            CommandLineParser._check_summary_classes(summaries, model.output_shape[2])
         pipe = CommandLineParser._pipeline(args, options, model)
         outstream = None
         if rank == 0:
@@ -565,7 +460,7 @@ class CommandLineParser:
 
         records_of = _records_of
 
-        runner = RecordRunner(pipe, tracks=track_spec, scores=bed_plan is not None, bed=bed_plan)
+        runner = RecordRunner(pipe, **{k: v for out in outputs for k, v in out.runner.items()})
 
         try:
             if world == 1:
@@ -573,32 +468,24 @@ class CommandLineParser:
                 for filename in args.FASTA:
                     _LOG.info("Processing %s", filename)
                     t_file = time.perf_counter()
-                    # --mask_dir, --seq_dir, --summary_dir: the file's rows, contig = record ordinal
-                    kept = _RowsByRecord() if masks is not None or seqs is not None or summaries is not None else None
-                    # --track_dir, --bed_dir: the input's files are renamed into place when all of its records are done, and removed
-                    # when one raises
-                    outs = []
+                    # the input's rows (contig = record ordinal) are kept once, for the outputs that are written from all of them
+                    kept = _RowsByRecord() if any(out.wants_rows for out in outputs) else None
+                    # the input's files are renamed into place when all of its records are done, in _COMMIT_ORDER; when anything
+                    # raises, what was not committed by then is removed (commit and abort are safe behind each other)
+                    handles = []
                     try:
-                        outs.append(tk.TrackFiles(track_plan, track_spec, filename) if track_spec is not None else None)
-                        outs.append(bed.BedFiles(bed_plan, filename) if bed_plan is not None else None)
-                        bases = CommandLineParser._predict_file(pipe, runner, filename, records_of(filename), outstream, kept, *outs)
-                        for out in filter(None, outs):
-                            out.commit()
+                        for out in outputs:
+                            handles.append(out.open(filename))
+                        bases = CommandLineParser._predict_file(pipe, runner, filename, records_of(filename), outstream, kept, handles)
+                        rows = kept.rows() if kept is not None else None
+                        for out, handle in zip(outputs, handles):
+                            if out.wants_rows:
+                                outstream.flush()
+                            handle.commit(rows, _LOG)
                     except BaseException:
-                        for out in filter(None, outs):
-                            out.abort()
+                        for handle in handles:
+                            handle.abort()
                         raise
-                    if masks is not None:
-                        outstream.flush()
-                        t_mask = time.perf_counter()
-                        CommandLineParser._write_mask(filename, masks[filename], kept.rows(), args)
-                        _LOG.debug("%s: masked copy %s in %.2f ms", filename, masks[filename], (time.perf_counter() - t_mask) * 1e3)
-                    if seqs is not None:
-                        outstream.flush()
-                        CommandLineParser._write_seq(filename, seqs, kept.rows())
-                    if summaries is not None:
-                        outstream.flush()
-                        CommandLineParser._write_summary(filename, summaries, kept.rows(), model.output_shape[2])
                     dt = time.perf_counter() - t_file
                     _LOG.info("%s: %d bases in %.3f s (%.1f Mbp/s; ingest, upload, forward, MSS, segments and TSV text)", filename, bases, dt,
                               bases / max(dt, 1e-9) / 1e6)
@@ -631,7 +518,7 @@ class CommandLineParser:
                                     i0, i1 = (ids[0], ids[-1] + 1) if ids else (0, 0)
                                     rows = allrows[(allrows["contig"] >= i0) & (allrows["contig"] < i1)].copy()
                                     rows["contig"] -= i0
-                                    CommandLineParser._write_mask(filename, masks[filename], rows, args)
+                                    masking.write_mask(filename, masks.plan.files[filename], rows, masks.plan, _LOG)
                             except Exception as e:          # noqa: BLE001 -- re-raised on every rank together
                                 err = e
                         raise_together(err)
@@ -656,42 +543,32 @@ class CommandLineParser:
         return pipe
 
     @staticmethod
-    def _predict_file(pipe, runner, filename, records, outstream, kept, files=None, beds=None) -> int:
-        """predict's loop over one input: the TSV rows of every record to `outstream` and to `kept` (_RowsByRecord, --mask_dir);
-        with --track_dir the track texts to `files` (tracks.TrackFiles), with --bed_dir every row's BED line to `beds`
-        (bed.BedFiles, the caller commits or aborts both), both from the merged array the rows come from (`runner` was made with
-        the same two choices).  -> bases read"""
+    def _predict_file(pipe, runner, filename, records, outstream, kept, handles=()) -> int:
+        """predict's loop over one input: the TSV rows of every record to `outstream` and to `kept` (_RowsByRecord, or None), and
+        every work item -- names, whether it is a batch, rows, scores, track texts -- to `handles`, the input's files of the outputs
+        `runner` was made for (the caller commits or aborts them).  -> bases read"""
         from .evaluation import record_name
         from .fasta import DeviceRecord
-        from .pipeline import record_indices
         from .runner import rows_text, rows_text_batch
-        from .tracks import empty_texts, record_texts
-        named = files is not None or beds is not None           # the runner's keys are then (header, name of the track and BED lines)
+        named = runner.tracks is not None or runner.scores      # the runner's keys are then (header, name of the track and BED lines)
         bases = 0
+
+        def put(headers, names, batch, rows, scores, texts):
+            outstream.write(rows_text_batch(filename, headers, rows) if batch else rows_text(filename, headers[0], rows))
+            for handle in handles:
+                handle.take(names, batch, rows, scores, texts)
+            if kept is not None:
+                kept.add(rows, len(headers))
+
         if _LOG.isEnabledFor(logging.DEBUG):
-            # -vv: record by record through the staged form of the same path, a device sync and a clock around every stage
-            # (the reference logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
+            # -vv: record by record down the runner's own record path, a device sync and a clock around every stage (the reference
+            # logs a debug line around each stage of _predict, deepgrp/__main__.py:69-79)
             for chrom, (header, rec) in enumerate(records):
                 name = record_name(filename, header) if named else None
-                track_sink = score_sink = None
-                if files is not None:
-                    track_sink = lambda merged, startpos: files.write(record_texts(pipe, merged, startpos, name, runner.tracks, chrom))
-                if beds is not None and runner.bed is not None:     # --bed_gzip, --bed_bigbed, --bed_gff3: scores and the write on the device
-                    score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.bed_write(
-                        merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, runner.bed, chrom))
-                elif beds is not None:
-                    score_sink = lambda merged, startpos, rows: beds.write([name], False, rows, pipe.row_scores(merged, startpos, rows))
-                rows, n = CommandLineParser._predict_staged(pipe, header, rec, track_sink, score_sink)
-                if n == 0 and files is not None:            # no base to predict: what empty_texts says (a chromosome of a bigWig)
-                    files.write(empty_texts(runner.tracks, name, record_indices(rec)[0]))
-                if n == 0 and beds is not None and runner.bed is not None and (runner.bed.bigbed or runner.bed.gff3):
-                    # (a chromosome of the bigBed; a name the GFF3 counts)
-                    from .bed import empty_write
-                    beds.write([name], False, rows, empty_write(runner.bed, name, record_indices(rec)[0], chrom))
-                bases += n
-                outstream.write(rows_text(filename, header, rows))
-                if kept is not None:
-                    kept.add(rows, 1)
+                stages = _Stages(header, pipe.use_mss)
+                rows, scores, texts = runner.run_record(rec, name, chrom, stage=stages)
+                bases += stages.close(rows)
+                put([header], [name], False, rows, scores, texts)
         else:
             def keyed():
                 nonlocal bases
@@ -700,63 +577,9 @@ class CommandLineParser:
                     yield ((header, record_name(filename, header)) if named else header), rec
             for kind, key, rows, scores, texts in runner.outputs(keyed()):
                 keys = key if kind == "batch" else [key]
-                headers = [header for header, _name in keys] if named else keys
-                outstream.write(rows_text_batch(filename, headers, rows) if kind == "batch" else rows_text(filename, headers[0], rows))
-                if beds is not None:
-                    beds.write([name for _header, name in keys], kind == "batch", rows, scores)
-                if files is not None:
-                    files.write(texts)
-                if kept is not None:
-                    kept.add(rows, len(keys))
+                put([header for header, _name in keys] if named else keys, [name for _header, name in keys] if named else None,
+                    kind == "batch", rows, scores, texts)
         return bases
-
-    @staticmethod
-    def _predict_staged(pipe, header, rec, track_sink=None, score_sink=None):
-        """One record through encode -> forward + merge -> scores / MSS / vote (or softmax) -> segments, each stage between device
-        syncs, with the reference's debug lines (deepgrp/__main__.py:69-79) carrying the stage's milliseconds.  -> (rows, bases)
-        track_sink(merged, startpos), if given, runs between the forward pass and the labels (--track_dir); score_sink(merged,
-        startpos, rows) behind the segments (--bed_dir)."""
-        import time
-
-        import torch
-
-        from .pipeline import SEGMENT_DTYPE, record_indices
-
-        def lap(t):
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t) * 1e3
-        t = time.perf_counter()
-        _LOG.debug("One hot encoding sequence.")
-        startpos, d_idx = record_indices(rec)
-        n = int(d_idx.numel())
-        ms_enc = lap(t)
-        if n == 0:
-            return np.zeros(0, SEGMENT_DTYPE), 0
-        t = time.perf_counter()
-        _LOG.debug("Start prediction.")
-        merged = pipe.merged(d_idx)
-        ms_fwd = lap(t)
-        _LOG.debug("Finish prediction.")
-        if track_sink is not None:
-            t = time.perf_counter()
-            track_sink(merged, startpos)
-            _LOG.debug("%s: probability tracks %.2f ms", header, lap(t))
-        t = time.perf_counter()
-        if pipe.use_mss:
-            _LOG.debug("Applying MSS.")
-        labels = pipe.labels(merged)
-        ms_post = lap(t)
-        t = time.perf_counter()
-        rows = pipe.segments(labels, startpos)
-        ms_seg = lap(t)
-        if score_sink is not None:
-            t = time.perf_counter()
-            score_sink(merged, startpos, rows)
-            _LOG.debug("%s: row scores %.2f ms", header, lap(t))
-        _LOG.debug("%s: %d bases; encode %.2f ms, forward + merge %.2f ms (%.1f Mbp/s), %s %.2f ms, segments + read-back %.2f ms, %d rows",
-                   header, n, ms_enc, ms_fwd, n / max(ms_fwd, 1e-6) / 1e3, "scores + MSS + vote" if pipe.use_mss else "softmax", ms_post,
-                   ms_seg, len(rows))
-        return rows, n
 
     @staticmethod
     def _predict_sharded(args, runner, records_of, outstream, masks=None) -> None:
@@ -851,288 +674,17 @@ class CommandLineParser:
                 mine = local[sel].copy()
                 mine["contig"] = local_ids[sel] - int(np.searchsorted(file_of, fi))
                 spans = [(a, b) for ff, a, b in ranges[rank] if ff == f]
-                CommandLineParser._write_mask_sharded(files[fi], masks[files[fi]], mine, spans, args)
+                masking.write_mask_sharded(files[fi], masks.plan.files[files[fi]], mine, spans, masks.plan)
 
     last_sharded: dict = {}
-
-    @staticmethod
-    def _mask_plan(args):
-        """--mask_dir: {input file: masked copy}, or None without the flag.  Everything that can be refused without the model is
-        refused here, before any prediction."""
-        mdir = getattr(args, "mask_dir", None)
-        packed_out = bool(getattr(args, "mask_gzip", False))
-        twobit_out = bool(getattr(args, "mask_twobit", False))
-        if mdir is None:
-            if twobit_out:
-                sys.exit("--mask_twobit needs --mask_dir")
-            if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None or packed_out:
-                sys.exit("--mask, --mask_classes and --mask_gzip need --mask_dir")
-            return None
-        if twobit_out and packed_out:
-            sys.exit("--mask_twobit and --mask_gzip exclude each other: a 2bit file is a binary format of its own and is not compressed")
-        if packed_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
-            sys.exit("--mask_gzip: a compressed masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
-                     "they share a file out by byte ranges, and a compressed file has none; run in one process")
-        if twobit_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
-            sys.exit("--mask_twobit: a 2bit masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
-                     "they share a file out by byte ranges, and a 2bit file has none of the input's; run in one process")
-        from .gz import compressed_inputs
-        from .twobit import is_twobit
-        plan, seen = {}, {}
-        for f in args.FASTA:
-            if f == "-":
-                sys.exit("--mask_dir: standard input cannot be masked (give a FASTA file)")
-            if f.endswith(".npz"):
-                sys.exit(f"--mask_dir: {f} is a one-hot .npz, not a FASTA file; it cannot be masked")
-            if not packed_out and not twobit_out and compressed_inputs([f]):
-                sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
-                         "uncompressed FASTA or pass --mask_gzip")
-            base = os.path.basename(f)
-            if twobit_out:
-                # chr.fa -> chr.fa.2bit, hg38.fa.gz -> hg38.fa.2bit, hg38.2bit -> hg38.2bit
-                if base.endswith(".gz") and compressed_inputs([f]):
-                    base = base[:-3]
-                if not base.endswith(".2bit"):
-                    base += ".2bit"
-            elif is_twobit(f):
-                base += ".fa"                                     # the masked copy of a 2bit file is its FASTA text
-            if packed_out and not base.endswith(".gz"):
-                base += ".gz"
-            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
-                sys.exit(f"--mask_dir: the masked copies of {seen[base]} and {f} have the same file name {base}; they would collide")
-            seen[base] = f
-            out = os.path.join(mdir, base)
-            if os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
-                sys.exit(f"--mask_dir: the masked copy {out} would overwrite the input {f}")
-            plan[f] = out
-        if len(plan) != len(args.FASTA):
-            sys.exit("--mask_dir: an input file is given twice")
-        os.makedirs(mdir, exist_ok=True)
-        return plan
-
-    @staticmethod
-    def _seq_plan(args):
-        """--seq_dir and its options: dict(files={input file: FASTA of its repeats}, classes, flank, width, gzip, fai, level), or None
-        without the flag.  Everything that can be refused without the model is refused here, before any prediction."""
-        sdir = getattr(args, "seq_dir", None)
-        packed_out, fai = bool(getattr(args, "seq_gzip", False)), bool(getattr(args, "seq_fai", False))
-        classes, flank, width = getattr(args, "seq_classes", None), getattr(args, "seq_flank", None), getattr(args, "seq_width", None)
-        if sdir is None:
-            if packed_out or fai or classes is not None or flank is not None or width is not None:
-                sys.exit("--seq_classes, --seq_flank, --seq_width, --seq_gzip and --seq_fai need --seq_dir")
-            return None
-        if fai and packed_out:
-            sys.exit("--seq_fai and --seq_gzip exclude each other: a .fai states offsets of the uncompressed file, a BGZF FASTA would "
-                     "also need a .gzi index, which is not written")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
-            sys.exit("--seq_dir: the repeat sequences of an input are written by one process, in TSV order; they cannot be written by "
-                     "several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
-        flank, width = (0 if flank is None else flank), (60 if width is None else width)
-        if not 1 <= width <= 1 << 30:
-            sys.exit(f"--seq_width must lie in 1..2^30, not {width}")
-        if flank < 0:
-            sys.exit(f"--seq_flank must not be negative, got {flank}")
-        from .tracks import gzip_level, input_basename
-        level = gzip_level(args, 1)
-        files, seen = {}, {}
-        for f in args.FASTA:
-            if f == "-":
-                sys.exit("--seq_dir: standard input cannot be read a second time for the sequences (give a FASTA file)")
-            if f.endswith(".npz"):
-                sys.exit(f"--seq_dir: {f} is a one-hot .npz, not a FASTA file; it holds no sequence bytes to write")
-            base = input_basename(f) + ".repeats.fa" + (".gz" if packed_out else "")
-            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
-                sys.exit(f"--seq_dir: the repeat sequences of {seen[base]} and {f} have the same file name {base}; they would collide")
-            seen[base] = f
-            out = os.path.join(sdir, base)
-            for cand in [out] + ([out + ".fai"] if fai else []):
-                for g in args.FASTA:
-                    if g != "-" and os.path.exists(g) and os.path.realpath(cand) == os.path.realpath(g):
-                        sys.exit(f"--seq_dir: the output {cand} would overwrite the input {g}")
-            files[f] = out
-        if len(files) != len(args.FASTA):
-            sys.exit("--seq_dir: an input file is given twice")
-        os.makedirs(sdir, exist_ok=True)
-        return dict(files=files, classes=classes, flank=flank, width=width, gzip=packed_out, fai=fai, level=level)
-
-    @staticmethod
-    def _summary_plan(args):
-        """--summary_dir and its options: dict(files={input file: (summary, density table or None)}, bin, names), or None without
-        the flag.  Everything that can be refused without the model is refused here, before any prediction."""
-        sdir, nbin = getattr(args, "summary_dir", None), getattr(args, "summary_bin", None)
-        if sdir is None:
-            if nbin is not None:
-                sys.exit("--summary_bin needs --summary_dir")
-            return None
-        if nbin is not None and nbin < 1:
-            sys.exit(f"--summary_bin must be at least 1, not {nbin}")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
-            sys.exit("--summary_dir: the repeat content of an input is counted by one process, from all of its rows; it cannot be "
-                     "counted by several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
-        names = getattr(args, "bed_names", None)
-        if names is not None:
-            from .gff import names_refusal
-            names = tuple(nm.encode("utf-8", "surrogateescape") for nm in names.split(","))
-            if names_refusal(names) is not None:
-                sys.exit(names_refusal(names))
-            from .summary import names_refusal as columns_refusal
-            if columns_refusal(names) is not None:
-                sys.exit(columns_refusal(names))
-        from .tracks import input_basename
-        files, seen = {}, {}
-        for f in args.FASTA:
-            if f == "-":
-                sys.exit("--summary_dir: standard input cannot be read a second time for the counts (give a FASTA file)")
-            if f.endswith(".npz"):
-                sys.exit(f"--summary_dir: {f} is a one-hot .npz, not a FASTA file; it holds no sequence bytes to count")
-            base = input_basename(f)
-            if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
-                sys.exit(f"--summary_dir: the summaries of {seen[base]} and {f} have the same file name {base}.summary.tsv; they would "
-                         "collide")
-            seen[base] = f
-            outs = (os.path.join(sdir, base + ".summary.tsv"), os.path.join(sdir, base + ".density.tsv") if nbin is not None else None)
-            for cand in filter(None, outs):
-                for g in args.FASTA:
-                    if g != "-" and os.path.exists(g) and os.path.realpath(cand) == os.path.realpath(g):
-                        sys.exit(f"--summary_dir: the output {cand} would overwrite the input {g}")
-            files[f] = outs
-        if len(files) != len(args.FASTA):
-            sys.exit("--summary_dir: an input file is given twice")
-        os.makedirs(sdir, exist_ok=True)
-        return dict(files=files, bin=nbin, names=names)
-
-    @staticmethod
-    def _check_summary_classes(summaries, classes: int) -> None:
-        from .summary import MAX_CLASSES, MIN_CLASSES
-        if not MIN_CLASSES <= classes <= MAX_CLASSES:
-            sys.exit(f"--summary_dir: the model has {classes} classes; the summary takes {MIN_CLASSES}..{MAX_CLASSES}")
-        if summaries["names"] is not None and len(summaries["names"]) != classes - 1:
-            sys.exit(f"--bed_names gives {len(summaries['names'])} names, but the model has {classes - 1} repeat classes "
-                     f"(labels 1..{classes - 1})")
-
-    @staticmethod
-    def _write_summary(filename: str, summaries, rows, classes: int) -> None:
-        """The repeat content of one input (summary.write_summary stages its files: renamed on success, removed on failure)."""
-        import time
-
-        from .summary import write_summary
-        t0 = time.perf_counter()
-        final, density = summaries["files"][filename]
-        rep = write_summary(filename, final, rows, classes, bin=summaries["bin"], bin_path=density, names=summaries["names"])
-        _LOG.info("%s: repeat content of %d records (%d counted on the device, %d on the host), %d of %d positions under %d rows, to "
-                  "%s in %.2f ms", filename, rep["records"], rep["device_records"], rep["host_records"], rep["repeat_positions"],
-                  rep["positions"], rep["rows"], final, (time.perf_counter() - t0) * 1e3)
-
-    @staticmethod
-    def _check_seq_classes(seqs, classes: int) -> None:
-        bad = [c for c in (seqs["classes"] or ()) if not 0 < c < classes]
-        if bad:
-            sys.exit(f"--seq_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
-
-    @staticmethod
-    def _write_seq(filename: str, seqs, rows) -> None:
-        """The FASTA of one input's repeats (repeatseq.write_repeat_fasta stages its files: renamed on success, removed on failure)."""
-        import time
-
-        from .repeatseq import kept_rows, write_repeat_fasta
-        from .masking import class_bits
-        t0 = time.perf_counter()
-        final = seqs["files"][filename]
-        nbytes = write_repeat_fasta(filename, final, rows, classes=seqs["classes"], flank=seqs["flank"], width=seqs["width"],
-                                    compress=seqs["gzip"], level=seqs["level"], fai_path=final + ".fai" if seqs["fai"] else None)
-        _LOG.info("%s: %d bytes of FASTA, %d of %d rows, to %s in %.2f ms", filename, nbytes,
-                  int(kept_rows(rows, class_bits(seqs["classes"])).sum()), len(rows), final, (time.perf_counter() - t0) * 1e3)
-
-    @staticmethod
-    def _check_mask_classes(args, classes: int) -> None:
-        bad = [c for c in (getattr(args, "mask_classes", None) or ()) if not 0 < c < classes]
-        if bad:
-            sys.exit(f"--mask_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
-
-    @staticmethod
-    def _write_mask(filename: str, final: str, rows, args) -> None:
-        """The masked copy of one file: written to a temporary file next to `final`, renamed on success, removed on failure.
-        --mask_twobit: an input that has no 2bit file (twobit.Refused) gets one warning and no file; the command goes on."""
-        import tempfile
-
-        from .masking import mask_fasta
-        from .twobit import Refused
-        fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
-        os.close(fd)
-        try:
-            if getattr(args, "mask_twobit", False):
-                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
-                           twobit=True)
-            else:
-                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft", classes=getattr(args, "mask_classes", None),
-                           compress=bool(getattr(args, "mask_gzip", False)), level=getattr(args, "gzip_level", None) or 0)
-            os.replace(tmp, final)
-        except Refused as e:
-            os.remove(tmp)
-            _LOG.warning("--mask_twobit: %s; no %s is written", e, final)
-        except BaseException:
-            os.remove(tmp)
-            raise
-
-    @staticmethod
-    def _write_mask_sharded(filename: str, final: str, rows, spans, args) -> None:
-        """_write_mask over the ranks: rank 0 creates the temporary file at the input's size, every rank writes its byte ranges,
-        rank 0 renames it (or removes it when any rank failed)."""
-        import tempfile
-
-        import torch.distributed as dist
-
-        from .distributed import raise_together
-        from .masking import mask_fasta
-        rank = dist.get_rank()
-        name = [None]
-        err = None
-        if rank == 0:
-            try:
-                fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
-                os.ftruncate(fd, os.path.getsize(filename))
-                os.close(fd)
-                name = [tmp]
-            except Exception as e:              # noqa: BLE001 -- re-raised on every rank together
-                err = e
-        raise_together(err)
-        dist.broadcast_object_list(name, src=0)          # (after rank 0 made the file: the barrier in front of the writes)
-        tmp = name[0]
-        try:
-            if spans:
-                mask_fasta(filename, tmp, rows, mode=getattr(args, "mask", None) or "soft",
-                           classes=getattr(args, "mask_classes", None), ranges=spans)
-        except Exception as e:                  # noqa: BLE001
-            err = e
-        try:
-            raise_together(err)                 # every rank has written (or failed): the barrier behind the writes
-        except BaseException:
-            if rank == 0:
-                os.remove(tmp)
-            raise
-        if rank == 0:
-            os.replace(tmp, final)
 
     @staticmethod
     def evaluate(args: argparse.Namespace, options) -> None:
         """Score `predict`'s rows against an annotation (deepgrp_amd/evaluation.py): TSV report, optionally JSON."""
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("evaluate runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
-        if getattr(args, "mask_twobit", False):
-            sys.exit("--mask_twobit belongs to predict, not evaluate")
-        if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
-            sys.exit("--mask_dir belongs to predict, not evaluate")
-        if (getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False)
-                or getattr(args, "track_bigwig", False)):
-            sys.exit("--track_dir belongs to predict, not evaluate")
-        if getattr(args, "gzip_level", None) is not None:
-            sys.exit("--gzip_level belongs to predict, not evaluate")
-        if any(getattr(args, k, None) not in (None, False) for k in ("seq_dir", "seq_classes", "seq_flank", "seq_width", "seq_gzip", "seq_fai")):
-            sys.exit("--seq_dir belongs to predict, not evaluate")
-        if getattr(args, "summary_dir", None) is not None or getattr(args, "summary_bin", None) is not None:
-            sys.exit("--summary_dir belongs to predict, not evaluate")
-        from .bed import refuse_on_evaluate
-        refuse_on_evaluate(args)
+        for output in _OUTPUTS:
+            output.refuse_on_evaluate(args)
         if not 0.0 < args.min_overlap <= 1.0:
             sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
         from . import boundaries as dgboundaries, curves as dgcurves, offtarget as dgofftarget, strata as dgstrata

@@ -32,6 +32,7 @@ ordinals run through the file, so `BedFiles` counts the lines and hands every wr
 input with an empty record name gets one warning and no `.gff3`."""
 from __future__ import annotations
 
+import argparse
 import ctypes as C
 import os
 import sys
@@ -96,6 +97,41 @@ def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
     return BedWrite(b"", raw)
 
 
+def add_options(parser) -> None:
+    """The scored-BED flags, like the track flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--bed_dir", type=str, default=s,
+                        help="(addition) also write the predicted repeats of every input as BED, DIR/<basename of the input>.bed ('stdin' "
+                             "for '-'): name, start, end, class<label>, score 0..1000, '.', then the mean and the smallest merged "
+                             "probability of the row's class over its bases and the share of its bases at which that class is the "
+                             "largest, four decimals each; summed on the GPU; one process only")
+    parser.add_argument("--bed_min_score", type=int, default=s,
+                        help="(addition) with --bed_dir: leave out BED lines whose score is below this, 0..1000 (the TSV is not filtered)")
+    parser.add_argument("--bed_gzip", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the BED as BGZF (bgzip's format) to DIR/<basename>.bed.gz; the lines are "
+                             "written and deflated on the GPU (--gzip_level, 1 unless given)")
+    parser.add_argument("--bed_index", action="store_true", default=s,
+                        help="(addition) with --bed_gzip: write the tabix index <basename>.bed.gz.tbi, built on the GPU beside the text "
+                             "(records must end at or below 2^29 and names must not reappear after another name; otherwise a warning "
+                             "and no index)")
+    parser.add_argument("--bed_bigbed", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the scored repeats as bigBed, DIR/<basename>.bb, instead of BED text: one "
+                             "item per BED line (bed6+3, the extra columns typed by an autoSql declaration) with coverage zoom levels, "
+                             "built and deflated on the GPU (--gzip_level, 1 unless given); coordinates up to 2^32 - 1.  Record names "
+                             "must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and no "
+                             "bigBed for that input.  Not with --bed_gzip or --bed_index")
+    parser.add_argument("--bed_gff3", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the scored repeats as GFF3, DIR/<basename>.gff3, instead of BED text: "
+                             "'##gff-version 3', then per row seqid, deepgrp, repeat_region, start+1, end, mean, '.', '.', "
+                             "ID=r<ordinal>;Name=class<label>;label=;score=;min=;agree= with the BED's figures, written on the GPU.  "
+                             "With --bed_gzip DIR/<basename>.gff3.gz (BGZF), with --bed_index its tabix index (gff preset) beside it.  "
+                             "A record with an empty name: a warning and no GFF3 for that input.  Not with --bed_bigbed")
+    parser.add_argument("--bed_names", type=str, default=s,
+                        help="(addition) with --bed_gff3: the names of the labels 1..classes-1, comma-separated, written as Name= in the "
+                             "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped); with --summary_dir: the "
+                             "label column of its tables")
+
+
 def refuse_on_evaluate(args) -> None:
     if getattr(args, "bed_bigbed", False):
         sys.exit("--bed_bigbed belongs to predict, not evaluate")
@@ -147,23 +183,34 @@ def plan(args) -> Optional[BedPlan]:
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
         sys.exit("--bed_dir runs in one process (WORLD_SIZE > 1 and --split_contigs are not supported: the scores are summed on the "
                  "rank that holds the merged probabilities)")
-    paths, seen = {}, {}
-    for f in args.FASTA:
-        out = bed_path(bdir, f, gzip, bigbed, gff3)
-        base = os.path.basename(out)
-        if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
-            sys.exit(f"--bed_dir: the BED files of {seen[base]} and {f} have the same file name {base}; they would collide")
-        seen[base] = f
-        if f != "-" and os.path.exists(f) and os.path.realpath(out) == os.path.realpath(f):
-            sys.exit(f"--bed_dir: the BED file {out} would overwrite the input {f}")
-        paths[f] = out
-    if len(paths) != len(args.FASTA):
-        sys.exit("--bed_dir: an input file is given twice")
+    from .outfiles import plan_inputs
+    paths = plan_inputs("--bed_dir", args.FASTA, lambda f: bed_path(bdir, f, gzip, bigbed, gff3), "BED files", "BED file")
     level = None
     if gzip or bigbed:
         from .tracks import gzip_level
         level = gzip_level(args, 1)
     return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames)
+
+
+def from_plan(p: BedPlan, classes: int) -> "Bed":
+    """The number of --bed_names checked against the model's class count (sys.exit)."""
+    if p.class_names is not None and len(p.class_names) != classes - 1:
+        sys.exit(f"--bed_names gives {len(p.class_names)} names, but the model has {classes - 1} repeat classes "
+                 f"(labels 1..{classes - 1})")
+    return Bed(p)
+
+
+class Bed:
+    """--bed_dir as an output of `predict`: every work item's rows come with their scores (with a plan that is on_device: with the
+    device's write of them), which go to the input's BedFiles."""
+    wants_rows = False
+
+    def __init__(self, p: BedPlan):
+        self.plan = p
+        self.runner = dict(scores=True, bed=p)          # what is asked of the RecordRunner
+
+    def open(self, filename: str) -> "BedFiles":
+        return BedFiles(self.plan, filename)
 
 
 class _BigBedFile(StagedFile):
@@ -274,7 +321,10 @@ class BedFiles(StagedOutputs):
             raise ValueError(f"{self.filename}: a bigBed write of chromId {w.chrom0} arrived as record {len(builder.names)} of the input")
         builder.add(w.names, w.sizes, w)
 
-    def commit(self) -> None:
+    def take(self, names: Sequence, batch: bool, rows, scores, texts) -> None:
+        self.write(names, batch, rows, scores)
+
+    def commit(self, rows=None, log=None) -> None:
         if self.bb_refused is None:
             return super().commit()
         self.abort()

@@ -8,13 +8,19 @@ the coordinate of the TSV rows.  Plain records (fasta.py's device path: LF / CRL
 fasta.LineLoop."""
 from __future__ import annotations
 
+import argparse
 import logging
 import mmap
 import os
 import re
-from typing import Iterable, List, Optional, Sequence, Tuple
+import sys
+import tempfile
+import time
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
+
+from .outfiles import RowsOutput, class_list
 
 _LOG = logging.getLogger(__name__)
 
@@ -332,3 +338,164 @@ def mask_fasta(fasta_path, out_path, rows, mode: str = "soft", classes: Optional
     if contig.size and int(contig[-1]) >= ordinal:
         raise ValueError(f"{fasta_path}: rows name record {int(contig[-1])}, but only {ordinal} records were read")
     return ordinal
+
+
+# ------------------------------------------------------------------------- the output of `predict`
+class MaskPlan(NamedTuple):
+    files: dict                                     # input file -> its masked copy
+    mode: str                                       # --mask: soft or hard
+    classes: Optional[Tuple[int, ...]]              # --mask_classes (None: every label > 0)
+    gzip: bool = False                              # --mask_gzip
+    twobit: bool = False                            # --mask_twobit
+    level: int = 0                                  # --gzip_level of --mask_gzip
+
+
+def add_options(parser) -> None:
+    """The masking flags: on `predict` and, for the README form with the flags in front, on the main parser as well (the values
+    are only set where given, so neither parser's default hides the other's)."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--mask_dir", type=str, default=s,
+                        help="(addition) also write a masked copy of every input FASTA file as DIR/<basename of the input>")
+    parser.add_argument("--mask", choices=("soft", "hard"), default=s,
+                        help="(addition) soft: predicted repeats lower case, the rest upper case; hard: predicted repeats 'N'")
+    parser.add_argument("--mask_classes", type=class_list, default=s,
+                        help="(addition) comma-separated labels to mask, e.g. 1,3 (default: every label > 0)")
+    parser.add_argument("--mask_gzip", action="store_true", default=s,
+                        help="(addition) with --mask_dir: write every masked copy as BGZF (bgzip's format, deflated on the GPU) to "
+                             "DIR/<basename>.gz, and accept gzip-compressed inputs; one process only")
+    parser.add_argument("--mask_twobit", action="store_true", default=s,
+                        help="(addition) with --mask_dir: write every masked copy as a UCSC .2bit file (soft mask = mask blocks, hard "
+                             "mask = N blocks; packed on the GPU) to DIR/<basename>.2bit instead of FASTA text, and accept "
+                             "gzip-compressed inputs; one process only")
+    parser.add_argument("--gzip_level", type=int, default=s,
+                        help="(addition) level of the GPU deflate of --mask_gzip, --track_gzip, --track_bigwig, --bed_gzip and --bed_bigbed: 0 "
+                             "literals "
+                             "only, 1 with matches (default: 0 for masked copies, 1 for tracks and the BED)")
+
+
+def refuse_on_evaluate(args) -> None:
+    if getattr(args, "mask_twobit", False):
+        sys.exit("--mask_twobit belongs to predict, not evaluate")
+    if getattr(args, "mask_dir", None) is not None or getattr(args, "mask_gzip", False):
+        sys.exit("--mask_dir belongs to predict, not evaluate")
+    if getattr(args, "gzip_level", None) is not None:
+        sys.exit("--gzip_level belongs to predict, not evaluate")
+
+
+def plan(args) -> Optional[MaskPlan]:
+    """--mask_dir and its options, or None without the flag.  Everything that can be refused without the model is refused here
+    (sys.exit), before any prediction."""
+    mdir = getattr(args, "mask_dir", None)
+    packed_out = bool(getattr(args, "mask_gzip", False))
+    twobit_out = bool(getattr(args, "mask_twobit", False))
+    if mdir is None:
+        if twobit_out:
+            sys.exit("--mask_twobit needs --mask_dir")
+        if getattr(args, "mask", None) is not None or getattr(args, "mask_classes", None) is not None or packed_out:
+            sys.exit("--mask, --mask_classes and --mask_gzip need --mask_dir")
+        return None
+    if twobit_out and packed_out:
+        sys.exit("--mask_twobit and --mask_gzip exclude each other: a 2bit file is a binary format of its own and is not compressed")
+    if packed_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
+        sys.exit("--mask_gzip: a compressed masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
+                 "they share a file out by byte ranges, and a compressed file has none; run in one process")
+    if twobit_out and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False)):
+        sys.exit("--mask_twobit: a 2bit masked copy cannot be written by several ranks (WORLD_SIZE > 1, --split_contigs): "
+                 "they share a file out by byte ranges, and a 2bit file has none of the input's; run in one process")
+    from .gz import compressed_inputs
+    from .outfiles import plan_inputs
+    from .twobit import is_twobit
+
+    def copy_of(f):
+        if not packed_out and not twobit_out and compressed_inputs([f]):
+            sys.exit(f"--mask_dir: {f} is gzip-compressed; the masked copy is written by byte offsets of the input, so give the "
+                     "uncompressed FASTA or pass --mask_gzip")
+        base = os.path.basename(f)
+        if twobit_out:
+            # chr.fa -> chr.fa.2bit, hg38.fa.gz -> hg38.fa.2bit, hg38.2bit -> hg38.2bit
+            if base.endswith(".gz") and compressed_inputs([f]):
+                base = base[:-3]
+            if not base.endswith(".2bit"):
+                base += ".2bit"
+        elif is_twobit(f):
+            base += ".fa"                                     # the masked copy of a 2bit file is its FASTA text
+        if packed_out and not base.endswith(".gz"):
+            base += ".gz"
+        return os.path.join(mdir, base)
+
+    files = plan_inputs("--mask_dir", args.FASTA, copy_of, "masked copies", "masked copy", stdin="masked", npz="cannot be masked",
+                        directory=mdir)
+    return MaskPlan(files, getattr(args, "mask", None) or "soft", getattr(args, "mask_classes", None), packed_out, twobit_out,
+                    getattr(args, "gzip_level", None) or 0)
+
+
+def from_plan(p: MaskPlan, classes: int) -> "Mask":
+    """The labels checked against the model's class count (sys.exit on one it lacks)."""
+    bad = [c for c in (p.classes or ()) if not 0 < c < classes]
+    if bad:
+        sys.exit(f"--mask_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
+    return Mask(p)
+
+
+class Mask(RowsOutput):
+    """--mask_dir as an output of `predict`: the masked copy of an input is written when the input is done, from all of its rows."""
+
+    def write(self, filename: str, rows, log) -> None:
+        t0 = time.perf_counter()
+        write_mask(filename, self.plan.files[filename], rows, self.plan, log)
+        log.debug("%s: masked copy %s in %.2f ms", filename, self.plan.files[filename], (time.perf_counter() - t0) * 1e3)
+
+
+def write_mask(filename: str, final: str, rows, p: MaskPlan, log=_LOG) -> None:
+    """The masked copy of one file: written to a temporary file next to `final`, renamed on success, removed on failure.
+    --mask_twobit: an input that has no 2bit file (twobit.Refused) gets one warning and no file; the command goes on."""
+    from .twobit import Refused
+    fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
+    os.close(fd)
+    try:
+        if p.twobit:
+            mask_fasta(filename, tmp, rows, mode=p.mode, classes=p.classes, twobit=True)
+        else:
+            mask_fasta(filename, tmp, rows, mode=p.mode, classes=p.classes, compress=p.gzip, level=p.level)
+        os.replace(tmp, final)
+    except Refused as e:
+        os.remove(tmp)
+        log.warning("--mask_twobit: %s; no %s is written", e, final)
+    except BaseException:
+        os.remove(tmp)
+        raise
+
+
+def write_mask_sharded(filename: str, final: str, rows, spans, p: MaskPlan) -> None:
+    """write_mask over the ranks: rank 0 creates the temporary file at the input's size, every rank writes its byte ranges,
+    rank 0 renames it (or removes it when any rank failed)."""
+    import torch.distributed as dist
+
+    from .distributed import raise_together
+    rank = dist.get_rank()
+    name = [None]
+    err = None
+    if rank == 0:
+        try:
+            fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(final) + ".", suffix=".tmp", dir=os.path.dirname(final) or ".")
+            os.ftruncate(fd, os.path.getsize(filename))
+            os.close(fd)
+            name = [tmp]
+        except Exception as e:              # noqa: BLE001 -- re-raised on every rank together
+            err = e
+    raise_together(err)
+    dist.broadcast_object_list(name, src=0)          # (after rank 0 made the file: the barrier in front of the writes)
+    tmp = name[0]
+    try:
+        if spans:
+            mask_fasta(filename, tmp, rows, mode=p.mode, classes=p.classes, ranges=spans)
+    except Exception as e:                  # noqa: BLE001
+        err = e
+    try:
+        raise_together(err)                 # every rank has written (or failed): the barrier behind the writes
+    except BaseException:
+        if rank == 0:
+            os.remove(tmp)
+        raise
+    if rank == 0:
+        os.replace(tmp, final)

@@ -2,8 +2,10 @@
 under a temporary name next to its final one and renamed when its input is done (`StagedFile`); a BGZF file takes the members of
 every write and, where a tabix index was asked for, builds `<file>.tbi` beside it (`BgzfSink`); `StagedOutputs` is what the files
 of one input share: the rule on record names, one warning when the input cannot be indexed, and a commit that leaves no temporary
-file behind when it fails.  The reports of `evaluate` share `plan_prefix`, the refusals of their `--<report> PREFIX`, and
-`write_texts`, their staged text files."""
+file behind when it fails.  The outputs that are written when their input is done (--mask_dir, --seq_dir, --summary_dir) share
+`RowsOutput` and its handle `AtCommit`; the plans of the outputs share `plan_inputs`, what they refuse of their inputs, and
+`class_list`, the type of their label flags.  The reports of `evaluate` share `plan_prefix`, the refusals of their `--<report>
+PREFIX`, and `write_texts`, their staged text files."""
 from __future__ import annotations
 
 import os
@@ -152,6 +154,81 @@ class StagedOutputs:
     def abort(self) -> None:
         for p in self.parts:
             p.abort()
+
+
+class AtCommit:
+    """The handle of a RowsOutput for one input: `take` has nothing to do with a work item, `commit(rows, log)` is the output's
+    `write(filename, rows, log)`, and `abort` has nothing to remove, because `write` stages its own files and leaves none behind
+    when it raises."""
+
+    def __init__(self, output, filename: str):
+        self.output, self.filename = output, filename
+
+    def take(self, names, batch, rows, scores, texts) -> None:
+        pass
+
+    def commit(self, rows, log) -> None:
+        self.output.write(self.filename, rows, log)
+
+    def abort(self) -> None:
+        pass
+
+
+class RowsOutput:
+    """An output of `predict` that is written when its input is done, from all of the input's rows (--mask_dir, --seq_dir,
+    --summary_dir): it wants the rows kept, asks nothing of the RecordRunner, and has `write(filename, rows, log)`."""
+    wants_rows = True
+    runner: dict = {}
+
+    def __init__(self, plan):
+        self.plan = plan
+
+    def open(self, filename: str) -> AtCommit:
+        return AtCommit(self, filename)
+
+
+def plan_inputs(flag: str, inputs: Sequence[str], outputs_of, copies: str, output: str = "output", stdin: Optional[str] = None,
+                npz: Optional[str] = None, every_input: bool = False, directory: Optional[str] = None) -> dict:
+    """What the outputs of `predict` refuse of their inputs (sys.exit, before the model is read), input by input: standard input
+    (`stdin`: what cannot be done with it; None: it is an input like any other), a one-hot .npz (`npz`: why not; None: the same),
+    two inputs whose first output has one file name -- `copies` names the outputs in the plural --, an output that is an input
+    (`output` names it; every_input: any of the inputs, else the output's own one), and an input given twice.  outputs_of(input)
+    -> the path of its output, or the paths of its outputs with None where one is not written; it may refuse the input itself.
+    Real paths are compared throughout.  `directory` is made once nothing was refused.  -> {input: what outputs_of gave}"""
+    plan, seen = {}, {}
+    for f in inputs:
+        if f == "-" and stdin is not None:
+            sys.exit(f"{flag}: standard input cannot be {stdin} (give a FASTA file)")
+        if f.endswith(".npz") and npz is not None:
+            sys.exit(f"{flag}: {f} is a one-hot .npz, not a FASTA file; it {npz}")
+        outs = outputs_of(f)
+        paths = (outs,) if isinstance(outs, str) else outs
+        base = os.path.basename(paths[0])
+        if base in seen and os.path.realpath(seen[base]) != os.path.realpath(f):
+            sys.exit(f"{flag}: the {copies} of {seen[base]} and {f} have the same file name {base}; they would collide")
+        seen[base] = f
+        for out in filter(None, paths):
+            for g in inputs if every_input else [f]:
+                if g != "-" and os.path.exists(g) and os.path.realpath(out) == os.path.realpath(g):
+                    sys.exit(f"{flag}: the {output} {out} would overwrite the input {g}")
+        plan[f] = outs
+    if len(plan) != len(inputs):
+        sys.exit(f"{flag}: an input file is given twice")
+    if directory is not None:
+        os.makedirs(directory, exist_ok=True)
+    return plan
+
+
+def class_list(text: str) -> tuple:
+    """A command-line value that is a comma-separated list of labels (argparse `type=`)."""
+    import argparse
+    try:
+        out = tuple(int(x) for x in text.split(",") if x.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma-separated list of labels: {text!r}") from None
+    if not out:
+        raise argparse.ArgumentTypeError("no label given")
+    return out
 
 
 def plan_prefix(flag: str, prefix: str, suffixes: Sequence[str], args, why: str, refuse_directory: bool = True,

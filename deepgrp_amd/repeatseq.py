@@ -13,15 +13,19 @@ A record's sequence position p is masking.py's: the p-th character of the sequen
 the others through masking.sequence_byte_offsets and `extract_host`, which gives the same bytes."""
 from __future__ import annotations
 
+import argparse
 import ctypes as C
 import logging
 import mmap
 import os
-from typing import Iterable, List, Optional, Tuple
+import sys
+import time
+from typing import Iterable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
 from .masking import class_bits, sequence_byte_offsets
+from .outfiles import RowsOutput, class_list
 
 _LOG = logging.getLogger(__name__)
 
@@ -363,3 +367,97 @@ def write_repeat_fasta(fasta_path, out_path, rows, classes: Optional[Iterable[in
             f.abort()
         raise
     return written
+
+
+# ------------------------------------------------------------------------- the output of `predict`
+class SeqPlan(NamedTuple):
+    files: dict                                     # input file -> the FASTA of its repeats
+    classes: Optional[Tuple[int, ...]]              # --seq_classes (None: every label > 0)
+    flank: int
+    width: int
+    gzip: bool                                      # --seq_gzip
+    fai: bool                                       # --seq_fai: <file>.fai beside every file
+    level: int                                      # --gzip_level of --seq_gzip
+
+
+def add_options(parser) -> None:
+    """The repeat-sequence flags, like the track flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--seq_dir", type=str, default=s,
+                        help="(addition) also write the sequences of the predicted repeats of every input as FASTA, DIR/<basename of "
+                             "the input>.repeats.fa: per TSV row one record '>NAME:A-B class<label>' (0-based, half-open, as bedtools "
+                             "getfasta names it) with the bases of the row exactly as the input has them, gathered on the GPU; one "
+                             "process only")
+    parser.add_argument("--seq_classes", type=class_list, default=s,
+                        help="(addition) with --seq_dir: comma-separated labels to write, e.g. 1,3 (default: every label > 0)")
+    parser.add_argument("--seq_flank", type=int, default=s,
+                        help="(addition) with --seq_dir: also take up to N bases on either side of every row, clamped to the record; "
+                             "the header then ends in ' core=<start>-<end>' (default: 0)")
+    parser.add_argument("--seq_width", type=int, default=s,
+                        help="(addition) with --seq_dir: bases per line, 1..2^30 (default: 60)")
+    parser.add_argument("--seq_gzip", action="store_true", default=s,
+                        help="(addition) with --seq_dir: write the FASTA as BGZF (bgzip's format) to DIR/<basename>.repeats.fa.gz, "
+                             "deflated on the GPU (--gzip_level, 1 unless given)")
+    parser.add_argument("--seq_fai", action="store_true", default=s,
+                        help="(addition) with --seq_dir: also write the samtools faidx index DIR/<basename>.repeats.fa.fai; not with "
+                             "--seq_gzip")
+
+
+def refuse_on_evaluate(args) -> None:
+    if any(getattr(args, k, None) not in (None, False) for k in ("seq_dir", "seq_classes", "seq_flank", "seq_width", "seq_gzip", "seq_fai")):
+        sys.exit("--seq_dir belongs to predict, not evaluate")
+
+
+def plan(args) -> Optional[SeqPlan]:
+    """--seq_dir and its options, or None without the flag.  Everything that can be refused without the model is refused here
+    (sys.exit), before any prediction."""
+    sdir = getattr(args, "seq_dir", None)
+    packed_out, fai = bool(getattr(args, "seq_gzip", False)), bool(getattr(args, "seq_fai", False))
+    classes, flank, width = getattr(args, "seq_classes", None), getattr(args, "seq_flank", None), getattr(args, "seq_width", None)
+    if sdir is None:
+        if packed_out or fai or classes is not None or flank is not None or width is not None:
+            sys.exit("--seq_classes, --seq_flank, --seq_width, --seq_gzip and --seq_fai need --seq_dir")
+        return None
+    if fai and packed_out:
+        sys.exit("--seq_fai and --seq_gzip exclude each other: a .fai states offsets of the uncompressed file, a BGZF FASTA would "
+                 "also need a .gzi index, which is not written")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
+        sys.exit("--seq_dir: the repeat sequences of an input are written by one process, in TSV order; they cannot be written by "
+                 "several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
+    flank, width = (0 if flank is None else flank), (60 if width is None else width)
+    if not 1 <= width <= MAX_WIDTH:
+        sys.exit(f"--seq_width must lie in 1..2^30, not {width}")
+    if flank < 0:
+        sys.exit(f"--seq_flank must not be negative, got {flank}")
+    from .outfiles import plan_inputs
+    from .tracks import gzip_level, input_basename
+    level = gzip_level(args, 1)
+
+    def outputs_of(f):
+        out = os.path.join(sdir, input_basename(f) + ".repeats.fa" + (".gz" if packed_out else ""))
+        return (out, out + ".fai" if fai else None)
+
+    files = plan_inputs("--seq_dir", args.FASTA, outputs_of, "repeat sequences", stdin="read a second time for the sequences",
+                        npz="holds no sequence bytes to write", every_input=True, directory=sdir)
+    return SeqPlan({f: outs[0] for f, outs in files.items()}, classes, flank, width, packed_out, fai, level)
+
+
+def from_plan(p: SeqPlan, classes: int) -> "RepeatSeq":
+    """The labels checked against the model's class count (sys.exit on one it lacks)."""
+    bad = [c for c in (p.classes or ()) if not 0 < c < classes]
+    if bad:
+        sys.exit(f"--seq_classes: label {bad[0]} is not a repeat class of this model (labels 1..{classes - 1})")
+    return RepeatSeq(p)
+
+
+class RepeatSeq(RowsOutput):
+    """--seq_dir as an output of `predict`: the FASTA of an input's repeats is written when the input is done, from all of its rows
+    (write_repeat_fasta stages its files: renamed on success, removed on failure)."""
+
+    def write(self, filename: str, rows, log) -> None:
+        p, t0 = self.plan, time.perf_counter()
+        final = p.files[filename]
+        nbytes = write_repeat_fasta(filename, final, rows, classes=p.classes, flank=p.flank, width=p.width, compress=p.gzip,
+                                    level=p.level, fai_path=final + ".fai" if p.fai else None)
+        log.info("%s: %d bytes of FASTA, %d of %d rows, to %s in %.2f ms", filename, nbytes,
+                 int(kept_rows(rows, class_bits(p.classes)).sum()), len(rows), final, (time.perf_counter() - t0) * 1e3)

@@ -56,6 +56,10 @@ def _worker_stream(dev: int, i: int):
         return pool[i]
 
 
+def _no_stage(*_a) -> None:
+    """run_record's stage callback where none was given: nothing is timed, nothing waits for the device."""
+
+
 def _format(prefixes: List[bytes], by_contig: bool, rows) -> str:
     """dgrp_format_rows (host code of the library): one pass over the row records, no per-row Python objects."""
     import ctypes as C
@@ -115,17 +119,23 @@ class RecordRunner:
     def _fused(self) -> bool:
         return self.tracks is None and not self.scores and self.probe is None
 
-    def run_record(self, rec, name=None, chrom: int = 0, key=None):
+    def run_record(self, rec, name=None, chrom: int = 0, key=None, stage=None):
         """One record: the fused call, or merged -> [the texts of self.tracks] -> [the probe] -> labels -> segments -> [the rows'
-        scores], because the fused call keeps its merged array inside its workspace."""
-        if self._fused():
+        scores], because the fused call keeps its merged array inside its workspace.  stage (a callable, predict -vv): the record
+        takes the second form whatever was asked for, and stage(what, done) is called in front of (done False) and behind (done
+        True) "encode", "forward", "tracks", "labels", "segments" and "scores" -- "tracks" and "scores" only where the runner makes
+        them, and behind "encode" with the record's bases as a third argument; a record without a base ends there."""
+        if stage is None and self._fused():
             if isinstance(rec, DeviceRecord):             # parsed and encoded on the GPU
                 startpos, d_idx = record_indices(rec)
                 return self.pipe.run_idx(d_idx, startpos), None, None
             return self.pipe.run(rec), None, None
         from .pipeline import ROW_SCORE_DTYPE, SEGMENT_DTYPE
         from .tracks import empty_texts, record_texts
+        stage = stage or _no_stage
+        stage("encode", False)
         startpos, d_idx = record_indices(rec)
+        stage("encode", True, int(d_idx.numel()))
         if d_idx.numel() == 0:                            # no base: no rows; with --track_bigwig still a chromosome (empty_texts)
             scores = np.zeros(0, ROW_SCORE_DTYPE) if self.scores else None
             if self.scores and self.bed is not None:
@@ -133,15 +143,30 @@ class RecordRunner:
                 scores = empty_write(self.bed, name, startpos, chrom)
             out = (np.zeros(0, SEGMENT_DTYPE), scores, empty_texts(self.tracks, name, startpos) if self.tracks is not None else None)
             return out if self.probe is None else out + (self.probe(None, [0], [0], [startpos], [key]),)
+        stage("forward", False)
         merged = self.pipe.merged(d_idx)
-        texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom) if self.tracks is not None else None
+        stage("forward", True)
+        texts = None
+        if self.tracks is not None:
+            stage("tracks", False)
+            texts = record_texts(self.pipe, merged, startpos, name, self.tracks, chrom)
+            stage("tracks", True)
         probed = self.probe(merged, [0], [len(merged)], [startpos], [key]) if self.probe is not None else None
-        rows = self.pipe.segments(self.pipe.labels(merged), startpos)
+        stage("labels", False)
+        labels = self.pipe.labels(merged)
+        stage("labels", True)
+        stage("segments", False)
+        rows = self.pipe.segments(labels, startpos)
+        del labels
+        stage("segments", True)
         scores = None
-        if self.scores and self.bed is not None:
-            scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed, chrom)
-        elif self.scores:
-            scores = self.pipe.row_scores(merged, startpos, rows)
+        if self.scores:
+            stage("scores", False)
+            if self.bed is not None:
+                scores = self.pipe.bed_write(merged, [0], [len(merged)], [startpos], rows, [0, len(rows)], [name], False, self.bed, chrom)
+            else:
+                scores = self.pipe.row_scores(merged, startpos, rows)
+            stage("scores", True)
         return (rows, scores, texts) if self.probe is None else (rows, scores, texts, probed)
 
     def run_batch(self, batch: _Batch):

@@ -38,9 +38,15 @@ Plain records (LF / CRLF line ends only) are counted on the GPU (dgrp_repeat_sum
 in one call); the others through masking.sequence_byte_offsets and `count_host` / `bins_host`, which state the same integers."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+import argparse
+import os
+import sys
+import time
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
+
+from .outfiles import RowsOutput
 
 KINDS, CASES = 5, 2
 MIN_CLASSES, MAX_CLASSES = 2, 64                      # dgrp_repeat_summary_batch's envelope
@@ -338,3 +344,87 @@ def write_summary(fasta_path, out_path, rows, classes: int, bin: Optional[int] =
     report["positions"] = int(sum(int(c.sum()) for _n, c, _r in records if c is not None))
     report["repeat_positions"] = int(sum(int(c[1:].sum()) for _n, c, _r in records if c is not None))
     return report
+
+
+# ------------------------------------------------------------------------- the output of `predict`
+class SummaryPlan(NamedTuple):
+    files: dict                                     # input file -> (its summary, its density table or None)
+    bin: Optional[int]                              # --summary_bin
+    names: Optional[tuple]                          # --bed_names: the name of label 1..C-1
+
+
+def add_options(parser) -> None:
+    """The repeat-content flags, like the repeat-sequence flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--summary_dir", type=str, default=s,
+                        help="(addition) also write the repeat content of every input as DIR/<basename of the input>.summary.tsv: per "
+                             "record and label (and for all labels > 0 together, and for the whole file) rows, bases, A, C, G, T, "
+                             "other, lower case, min, max and N50 of the row lengths, share of the record, of its ACGT bases, GC, and "
+                             "recall and precision against the input's own soft mask, counted on the GPU; --bed_names names the "
+                             "labels; one process only")
+    parser.add_argument("--summary_bin", type=int, default=s,
+                        help="(addition) with --summary_dir: also DIR/<basename>.density.tsv, per record and bin of N sequence "
+                             "positions the ACGT bases and the positions under every label > 0 (N >= 1)")
+
+
+def refuse_on_evaluate(args) -> None:
+    if getattr(args, "summary_dir", None) is not None or getattr(args, "summary_bin", None) is not None:
+        sys.exit("--summary_dir belongs to predict, not evaluate")
+
+
+def plan(args) -> Optional[SummaryPlan]:
+    """--summary_dir and its options, or None without the flag.  Everything that can be refused without the model is refused here
+    (sys.exit), before any prediction."""
+    sdir, nbin = getattr(args, "summary_dir", None), getattr(args, "summary_bin", None)
+    if sdir is None:
+        if nbin is not None:
+            sys.exit("--summary_bin needs --summary_dir")
+        return None
+    if nbin is not None and nbin < 1:
+        sys.exit(f"--summary_bin must be at least 1, not {nbin}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or getattr(args, "split_contigs", False):
+        sys.exit("--summary_dir: the repeat content of an input is counted by one process, from all of its rows; it cannot be "
+                 "counted by several ranks (WORLD_SIZE > 1, --split_contigs); run in one process")
+    names = getattr(args, "bed_names", None)
+    if names is not None:
+        from . import gff
+        names = tuple(nm.encode("utf-8", "surrogateescape") for nm in names.split(","))
+        if gff.names_refusal(names) is not None:
+            sys.exit(gff.names_refusal(names))
+        if names_refusal(names) is not None:
+            sys.exit(names_refusal(names))
+    from .outfiles import plan_inputs
+    from .tracks import input_basename
+
+    def outputs_of(f):
+        base = os.path.join(sdir, input_basename(f))
+        return (base + ".summary.tsv", base + ".density.tsv" if nbin is not None else None)
+
+    files = plan_inputs("--summary_dir", args.FASTA, outputs_of, "summaries", stdin="read a second time for the counts",
+                        npz="holds no sequence bytes to count", every_input=True, directory=sdir)
+    return SummaryPlan(files, nbin, names)
+
+
+def from_plan(p: SummaryPlan, classes: int) -> "Summary":
+    """The model's class count against the kernel's envelope and against the number of names (sys.exit)."""
+    if not MIN_CLASSES <= classes <= MAX_CLASSES:
+        sys.exit(f"--summary_dir: the model has {classes} classes; the summary takes {MIN_CLASSES}..{MAX_CLASSES}")
+    if p.names is not None and len(p.names) != classes - 1:
+        sys.exit(f"--bed_names gives {len(p.names)} names, but the model has {classes - 1} repeat classes (labels 1..{classes - 1})")
+    return Summary(p, classes)
+
+
+class Summary(RowsOutput):
+    """--summary_dir as an output of `predict`: the repeat content of an input is counted when the input is done, from all of its
+    rows (write_summary stages its files: renamed on success, removed on failure)."""
+
+    def __init__(self, p: SummaryPlan, classes: int):
+        self.plan, self.classes = p, classes
+
+    def write(self, filename: str, rows, log) -> None:
+        p, t0 = self.plan, time.perf_counter()
+        final, density = p.files[filename]
+        rep = write_summary(filename, final, rows, self.classes, bin=p.bin, bin_path=density, names=p.names)
+        log.info("%s: repeat content of %d records (%d counted on the device, %d on the host), %d of %d positions under %d rows, to "
+                 "%s in %.2f ms", filename, rep["records"], rep["device_records"], rep["host_records"], rep["repeat_positions"],
+                 rep["positions"], rep["rows"], final, (time.perf_counter() - t0) * 1e3)

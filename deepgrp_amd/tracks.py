@@ -23,6 +23,7 @@ sections with ten zoom levels at most, sections and zoom records written and def
 put around them by a bigwig.BigWigBuilder per class."""
 from __future__ import annotations
 
+import argparse
 import logging
 import os
 import sys
@@ -30,8 +31,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import name_blob
-from .outfiles import BgzfSink, StagedFile, StagedOutputs
+from .outfiles import BgzfSink, StagedFile, StagedOutputs, class_list
 
 _LOG = logging.getLogger(__name__)
 
@@ -96,6 +96,41 @@ def check_gzip_flags(args) -> None:
         gzip_level(args, 0)
 
 
+def add_options(parser) -> None:
+    """The probability-track flags, like the masking flags on `predict` and on the main parser, set only where given."""
+    s = argparse.SUPPRESS
+    parser.add_argument("--track_dir", type=str, default=s,
+                        help="(addition) also write the merged per-base probabilities of every selected class as bedGraph files "
+                             "DIR/<basename of the input>.class<c>.bedGraph ('stdin' for '-'); with --fast they are those of the "
+                             "fp16-operand kernels")
+    parser.add_argument("--track_gzip", action="store_true", default=s,
+                        help="(addition) with --track_dir: write every track as BGZF (bgzip's format, deflated on the GPU where the "
+                             "text is made) to DIR/<basename>.class<c>.bedGraph.gz")
+    parser.add_argument("--track_index", action="store_true", default=s,
+                        help="(addition) with --track_gzip: write the tabix index <track>.gz.tbi of every track, built on the GPU "
+                             "beside the text (records must end at or below 2^29 and names must not reappear after another name; "
+                             "otherwise a warning and no index)")
+    parser.add_argument("--track_bigwig", action="store_true", default=s,
+                        help="(addition) with --track_dir: write every track as bigWig, DIR/<basename>.class<c>.bw, instead of bedGraph: "
+                             "the same items in binary sections with zoom levels, built and deflated on the GPU (--gzip_level, 1 unless "
+                             "given).  A chromosome's size is the end of its predicted span (trailing N are not counted).  Record "
+                             "names must be non-empty and distinct and records must end at or below 2^32 - 1; otherwise a warning and "
+                             "no bigWig for that input.  Not with --track_gzip or --track_index")
+    parser.add_argument("--track_classes", type=class_list, default=s,
+                        help="(addition) comma-separated classes to write tracks of, 0 included (default: every repeat class 1..C-1)")
+    parser.add_argument("--track_digits", type=int, default=s,
+                        help="(addition) decimals of the track values, 1..4 (default: 2)")
+    parser.add_argument("--track_bin", type=int, default=s,
+                        help="(addition) bin width of the tracks in bases, >= 1; a bin's value is the maximum over its bases "
+                             "(default: 1)")
+
+
+def refuse_on_evaluate(args) -> None:
+    if (getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False)
+            or getattr(args, "track_bigwig", False)):
+        sys.exit("--track_dir belongs to predict, not evaluate")
+
+
 def plan(args) -> Optional[TrackPlan]:
     """--track_dir and its options, or None without the flag.  Everything that can be refused without the model is refused here
     (sys.exit), before any device work."""
@@ -134,6 +169,23 @@ def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
     if bad:
         sys.exit(f"--track_classes: label {bad[0]} is not a class of this model (labels 0..{nclasses - 1})")
     return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index, p.bigwig)
+
+
+def from_plan(p: TrackPlan, classes: int) -> "Tracks":
+    return Tracks(p, resolve(p, classes))
+
+
+class Tracks:
+    """--track_dir as an output of `predict`: every work item's rows come with the track texts of its records, which go to the
+    input's TrackFiles."""
+    wants_rows = False
+
+    def __init__(self, p: TrackPlan, spec: TrackSpec):
+        self.plan, self.spec = p, spec
+        self.runner = dict(tracks=spec)                 # what is asked of the RecordRunner
+
+    def open(self, filename: str) -> "TrackFiles":
+        return TrackFiles(self.plan, self.spec, filename)
 
 
 class WriteIndex(NamedTuple):
@@ -179,6 +231,7 @@ def _zlib_pieces(pipe, d_in, d_table, stride: int, level: int):
 
 def empty_texts(spec: TrackSpec, name, startpos: int):
     """The write of a record without a predicted base: no text; with spec.bigwig its name and size for the chromosome tree."""
+    from ._lib import name_blob
     out = TrackTexts(b"" for _ in spec.classes)
     out.bigwig = BigWigWrite(name_blob([name])[0], [int(startpos)], None, None) if spec.bigwig else None
     return out
@@ -189,6 +242,7 @@ def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpe
     from the device (dgrp_track_sections_batch, dgrp_track_zoom_batch), deflated there (dgrp_zlib_compress_batch).  chrom0 is
     the ordinal of the first record in its input: chromIds count from there."""
     from . import bigwig as bw
+    from ._lib import name_blob
     raw = name_blob(names)[0]
     sizes = [int(sp) + int(n) for sp, n in zip(startposes, lengths)]
     out = TrackTexts(b"" for _ in spec.classes)
@@ -221,6 +275,7 @@ def bigwig_write(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpe
 
 def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec) -> WriteIndex:
     """The WriteIndex of the records whose text track_text_batch_device gives for the same arguments."""
+    from ._lib import name_blob
     from .tabix import end_refusal
     raw = name_blob(names)[0]
     refused = end_refusal([int(sp) + int(n) for sp, n in zip(startposes, lengths)], raw)
@@ -303,7 +358,10 @@ class TrackFiles(StagedOutputs):
         for k, p in enumerate(self.parts):
             p.bw.add(w.names, w.sizes, None if w.classes is None else w.classes[k])
 
-    def commit(self) -> None:
+    def take(self, names, batch: bool, rows, scores, texts: Sequence[bytes]) -> None:
+        self.write(texts)
+
+    def commit(self, rows=None, log=None) -> None:
         if self.bw_refused is None:
             return super().commit()
         self.abort()

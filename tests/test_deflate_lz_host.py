@@ -178,6 +178,7 @@ def no_gpu(monkeypatch):
         raise AssertionError("the GPU was touched")
     monkeypatch.setattr(pipeline, "require_gpu", touched)
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was loaded")))
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was loaded")))
 
 
 def _refused(argv, *matches):

@@ -223,14 +223,18 @@ def test_cli_refusals(no_gpu, no_model, tmp_path, monkeypatch):
 
 
 def test_the_name_count_is_checked_behind_the_model(monkeypatch, tmp_path):
-    """classes - 1 names: refused right after the model is read, before a record is, with both numbers in the message."""
+    """classes - 1 names: refused right after the model file is read (once, on the host), before the device model is made and
+    before a record is read, with both numbers in the message."""
     from deepgrp_amd import model as dgmodel
     from deepgrp_amd.__main__ import CommandLineParser
 
-    class FakeModel:
-        input_shape, output_shape = (None, 20, 5), (None, 20, 5)
     read = []
-    monkeypatch.setattr(dgmodel, "load_model", lambda *a, **k: read.append(1) or FakeModel())
+    monkeypatch.setattr(dgmodel, "read_keras_hdf5", lambda *a, **k: read.append(1) or {"ff_kernel": np.zeros((16, 5), np.float32)})
+
+    def no_device(*_a, **_k):
+        raise AssertionError("the device model was made before the refusal")
+    monkeypatch.setattr(dgmodel, "device_model", no_device)
+    monkeypatch.setattr(dgmodel, "load_model", no_device)
 
     def no_pipeline(*_a, **_k):
         raise AssertionError("the pipeline was built before the refusal")

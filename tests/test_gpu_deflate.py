@@ -283,11 +283,12 @@ def test_cli_mask_gzip(tmp_path, mode):
     az.write_bytes(gz.bgzf_compress(data))
     import deepgrp_amd.model as dgmodel
     loaded = []
-    orig = dgmodel.load_model
-    dgmodel.load_model = lambda *x, **k: loaded.append(1) or orig(*x, **k)
+    orig = dgmodel.load_model, dgmodel.device_model
+    dgmodel.load_model = lambda *x, **k: loaded.append(1) or orig[0](*x, **k)
+    dgmodel.device_model = lambda *x, **k: loaded.append(1) or orig[1](*x, **k)
     try:
         with pytest.raises(SystemExit) as e:
             main(["predict", model, str(a), str(az), "--mask_dir", str(tmp_path / "clash"), "--mask_gzip", "--output", str(tmp_path / "c.tsv")])
     finally:
-        dgmodel.load_model = orig
+        dgmodel.load_model, dgmodel.device_model = orig
     assert "same file name" in str(e.value.code) and not loaded and not (tmp_path / "clash").exists()

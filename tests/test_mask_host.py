@@ -48,6 +48,7 @@ def test_mask_refusals_before_any_prediction(tmp_path, monkeypatch):
     mdir = str(tmp_path / "masked")
     loaded = []
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **k: loaded.append(1) or (_ for _ in ()).throw(AssertionError("ran")))
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **k: loaded.append(1) or (_ for _ in ()).throw(AssertionError("ran")))
     _refused(["predict", model, "-", "--mask_dir", mdir, "--output", out], "standard input")
     _refused(["predict", model, str(fa) + ".gz.npz", "--mask_dir", mdir, "--output", out], ".npz")
     _refused(["predict", model, str(fa), str(other / "a.fa"), "--mask_dir", mdir, "--output", out], "same file name")
@@ -69,6 +70,7 @@ def test_mask_refuses_labels_the_model_lacks(tmp_path, monkeypatch):
         input_shape, output_shape = (None, 20, 4), (None, 20, classes)
 
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **k: Stub())
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **k: Stub())
     monkeypatch.setattr(pipeline, "ContigPipeline", lambda *a, **k: (_ for _ in ()).throw(AssertionError("ran")))
     for bad in (f"1,{classes}", "0"):
         _refused(["predict", model, str(fa), "--mask_dir", str(tmp_path / "m"), "--mask_classes", bad, "--output",

@@ -125,12 +125,12 @@ def test_write_file_refuses_what_the_format_cannot_hold(tmp_path):
 
 
 def _plan(tmp_path, files, **kw):
-    from deepgrp_amd.__main__ import CommandLineParser
+    from deepgrp_amd import masking
     args = argparse.Namespace(mask_dir=str(tmp_path / "masked"), mask=None, mask_classes=None, mask_gzip=False, mask_twobit=True,
                               FASTA=[str(f) for f in files])
     for k, v in kw.items():
         setattr(args, k, v)
-    return CommandLineParser._mask_plan(args)
+    return masking.plan(args).files
 
 
 def test_the_name_plan(tmp_path, monkeypatch):
@@ -167,9 +167,9 @@ def test_the_name_plan(tmp_path, monkeypatch):
     assert "overwrite" in str(e.value) and str(tb) in str(e.value)
     assert _plan(tmp_path, [fa], mask_dir=str(tmp_path)) == {str(fa): str(tmp_path / "chr.fa.2bit")}
     # bare namespaces (no mask_twobit attribute) plan as before
-    from deepgrp_amd.__main__ import CommandLineParser
+    from deepgrp_amd import masking
     bare = argparse.Namespace(mask_dir=out, mask=None, mask_classes=None, mask_gzip=False, FASTA=[str(fa)])
-    assert CommandLineParser._mask_plan(bare) == {str(fa): join("chr.fa")}
+    assert masking.plan(bare).files == {str(fa): join("chr.fa")}
 
 
 REFUSALS = [
@@ -224,30 +224,29 @@ def test_every_refusal_comes_before_anything_is_loaded(tmp_path):
 
 @pytest.mark.parametrize("names, word", [([b"chr1 a", b"chr1 b"], "both named b'chr1'"), ([b"z" * 256], "256 bytes")])
 def test_a_refused_input_gets_one_warning_and_no_file(tmp_path, monkeypatch, caplog, names, word):
-    """_write_mask on a writer that stands in for the device work: it spools as mask_fasta does and ends in twobit.write_file.
+    """masking.write_mask on a writer that stands in for the device work: it spools as mask_fasta does and ends in twobit.write_file.
     Duplicate first words and a 256-byte name: one warning that names the input and the record, no .2bit, no staged file left, and
     the command goes on (no exception)."""
     from deepgrp_amd import masking, twobit
-    from deepgrp_amd.__main__ import CommandLineParser
     calls = []
 
     def fake(fasta_path, out_path, rows, mode="soft", classes=None, **kw):
         calls.append(kw)
-        assert os.path.exists(out_path)                                  # the staged file of _write_mask
+        assert os.path.exists(out_path)                                  # the staged file of write_mask
         cut = [twobit.record_name(n.decode()) for n in names]
         twobit.write_file(cut, [twobit.pack_record(b"ACGTnn")] * len(cut), out_path, what=str(fasta_path))
 
     monkeypatch.setattr(masking, "mask_fasta", fake)
     final = tmp_path / "masked" / "in.fa.2bit"
     final.parent.mkdir()
-    args = argparse.Namespace(mask="hard", mask_classes=None, mask_twobit=True)
+    plan = masking.MaskPlan({}, "hard", None, twobit=True)
     with caplog.at_level(logging.WARNING, logger="deepgrp_amd.__main__"):
-        CommandLineParser._write_mask("in.fa", str(final), np.zeros(0), args)
+        masking.write_mask("in.fa", str(final), np.zeros(0), plan, logging.getLogger("deepgrp_amd.__main__"))
     assert calls == [dict(twobit=True)]
     assert os.listdir(final.parent) == []
     warnings = [r.getMessage() for r in caplog.records if r.levelno == logging.WARNING]
     assert len(warnings) == 1 and "in.fa" in warnings[0] and word in warnings[0] and str(final) in warnings[0]
     # the same writer with names the format holds leaves the file
     names[:] = [b"chr1 a", b"chr2 b"]
-    CommandLineParser._write_mask("in.fa", str(final), np.zeros(0), args)
+    masking.write_mask("in.fa", str(final), np.zeros(0), plan)
     assert twobit.open_twobit(final).names == [b"chr1", b"chr2"]

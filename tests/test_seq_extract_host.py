@@ -221,6 +221,7 @@ def test_every_refusal_comes_before_the_model_is_read(tmp_path, monkeypatch, k):
         monkeypatch.setenv(key, v)
     monkeypatch.setattr(dgmodel, "read_keras_hdf5", lambda *a, **kw: pytest.fail("went past the refusal: the model was read"))
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **kw: pytest.fail("went past the refusal: the model was loaded"))
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **kw: pytest.fail("went past the refusal: the model was loaded"))
     fa = tmp_path / "in.fa"
     fa.write_bytes(b">x\nACGT\n")
     (tmp_path / "other").mkdir()
@@ -242,6 +243,7 @@ def test_a_label_outside_the_model_is_refused_once_the_class_count_is_known(tmp_
     from deepgrp_amd.__main__ import main
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **kw: pytest.fail("went past the refusal: the model was loaded"))
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **kw: pytest.fail("went past the refusal: the model was loaded"))
     fa = tmp_path / "in.fa"
     fa.write_bytes(b">x\nACGT\n")
     for labels in ("0", "5", "1,2,9"):
@@ -254,18 +256,18 @@ def test_a_label_outside_the_model_is_refused_once_the_class_count_is_known(tmp_
 def test_the_plan_names_the_files(tmp_path, monkeypatch):
     import argparse
 
-    from deepgrp_amd.__main__ import CommandLineParser
+    from deepgrp_amd import repeatseq
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     fa, gz = tmp_path / "chr.fa", tmp_path / "hg38.fa.gz"
     fa.write_bytes(b">x\nACGT\n")
     gz.write_bytes(b"\x1f\x8b")
     out = str(tmp_path / "seqs")
     args = argparse.Namespace(seq_dir=out, FASTA=[str(fa), str(gz)])
-    plan = CommandLineParser._seq_plan(args)
-    assert plan == dict(files={str(fa): os.path.join(out, "chr.fa.repeats.fa"), str(gz): os.path.join(out, "hg38.fa.gz.repeats.fa")},
+    plan = repeatseq.plan(args)
+    assert plan._asdict() == dict(files={str(fa): os.path.join(out, "chr.fa.repeats.fa"), str(gz): os.path.join(out, "hg38.fa.gz.repeats.fa")},
                         classes=None, flank=0, width=60, gzip=False, fai=False, level=1)
     args = argparse.Namespace(seq_dir=out, FASTA=[str(fa)], seq_gzip=True, seq_flank=7, seq_width=80, seq_classes=(1, 3), gzip_level=0)
-    plan = CommandLineParser._seq_plan(args)
-    assert plan == dict(files={str(fa): os.path.join(out, "chr.fa.repeats.fa.gz")}, classes=(1, 3), flank=7, width=80, gzip=True, fai=False,
+    plan = repeatseq.plan(args)
+    assert plan._asdict() == dict(files={str(fa): os.path.join(out, "chr.fa.repeats.fa.gz")}, classes=(1, 3), flank=7, width=80, gzip=True, fai=False,
                         level=0)
-    assert CommandLineParser._seq_plan(argparse.Namespace(FASTA=[str(fa)])) is None
+    assert repeatseq.plan(argparse.Namespace(FASTA=[str(fa)])) is None

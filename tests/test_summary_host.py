@@ -153,21 +153,22 @@ def test_symbols_are_declared_bound_and_exported():
 
 # ------------------------------------------------------------------------- command line
 def test_flags_parse_on_predict_and_in_the_short_form(tmp_path):
+    from deepgrp_amd import summary
     from deepgrp_amd.__main__ import CommandLineParser
     a = CommandLineParser().parse_args(["predict", "m.h5", "a.fa", "--summary_dir", "d", "--summary_bin", "1000", "--bed_names", "x,y"]).args
     assert a.summary_dir == "d" and a.summary_bin == 1000 and a.bed_names == "x,y"
     b = CommandLineParser().parse_args(["--summary_dir", "d", "--summary_bin", "5", "m.h5", "a.fa"]).args
     assert b.command == "predict" and b.summary_dir == "d" and b.summary_bin == 5 and b.FASTA == ["a.fa"]
     c = CommandLineParser().parse_args(["predict", "m.h5", "a.fa"]).args
-    assert getattr(c, "summary_dir", None) is None and CommandLineParser._summary_plan(c) is None
+    assert getattr(c, "summary_dir", None) is None and summary.plan(c) is None
     fa = tmp_path / "a.fa"
     fa.write_text(">x\nACGT\n")
     d = CommandLineParser().parse_args(["predict", "m.h5", str(fa), "--summary_dir", str(tmp_path / "o"), "--summary_bin", "9"]).args
-    plan = CommandLineParser._summary_plan(d)
-    assert plan == dict(files={str(fa): (str(tmp_path / "o" / "a.fa.summary.tsv"), str(tmp_path / "o" / "a.fa.density.tsv"))}, bin=9, names=None)
+    plan = summary.plan(d)
+    assert plan._asdict() == dict(files={str(fa): (str(tmp_path / "o" / "a.fa.summary.tsv"), str(tmp_path / "o" / "a.fa.density.tsv"))}, bin=9, names=None)
     e = CommandLineParser().parse_args(["predict", "m.h5", str(fa), "--summary_dir", str(tmp_path / "o"), "--bed_names", "L,S"]).args
-    assert CommandLineParser._summary_plan(e)["names"] == (b"L", b"S")
-    assert CommandLineParser._summary_plan(e)["files"][str(fa)][1] is None
+    assert summary.plan(e).names == (b"L", b"S")
+    assert summary.plan(e).files[str(fa)][1] is None
 
 
 CHILD = ("import sys\n"

@@ -361,6 +361,7 @@ def test_command_line_refusals_before_any_device_work(tmp_path, monkeypatch):
         raise AssertionError("the GPU was touched")
     monkeypatch.setattr(pipeline, "require_gpu", touched)
     monkeypatch.setattr(dgmodel, "load_model", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was loaded")))
+    monkeypatch.setattr(dgmodel, "device_model", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was loaded")))
     fa = tmp_path / "a.fa"
     fa.write_bytes(b">r\nACGTACGTACGT\n")
     ann = tmp_path / "a.bed"

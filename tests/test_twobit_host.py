@@ -221,11 +221,11 @@ def test_entries_check_their_tables_before_any_device_work():
 
 
 def _plan(tmp_path, files, **kw):
-    from deepgrp_amd.__main__ import CommandLineParser
+    from deepgrp_amd import masking
     args = argparse.Namespace(mask_dir=str(tmp_path / "masked"), mask=None, mask_classes=None, mask_gzip=False, FASTA=[str(f) for f in files])
     for k, v in kw.items():
         setattr(args, k, v)
-    return CommandLineParser._mask_plan(args)
+    return masking.plan(args).files
 
 
 def test_mask_plan_names_the_text_of_a_2bit_input(tmp_path, monkeypatch):

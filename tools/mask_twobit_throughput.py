@@ -1,5 +1,5 @@
 """predict --mask_twobit: the write of the masked copy of the benchmark's synthetic chromosome of [Mbp] (default 250),
-as `predict` does it -- CommandLineParser._write_mask from the FASTA file in /dev/shm (60-column lines, as bench.py writes it) to a
+as `predict` does it -- masking.write_mask from the FASTA file in /dev/shm (60-column lines, as bench.py writes it) to a
 file beside it, rows of a synthetic annotation (one row of 1 kb in every 5 kb, labels 1..3, soft mask) -- as a .2bit and as the
 plain masked text.  The plain copy is the yardstick: that path is what it was before --mask_twobit existed.  [warm-up] untimed rounds
 (default 1), then [rounds] timed rounds (default 5), the two forms alternating in every round; host clock around the call and a
@@ -7,7 +7,6 @@ device synchronise; median, fastest and slowest of each.  The 2bit file is first
 twobit.pack_record (the numpy packer).  One JSON line per result.
     python tools/mask_twobit_throughput.py [Mbp] [rounds] [warm-up] [both|twobit|plain]
 Kernel times come from a run of its own: rocprofv3 --kernel-trace --stats -- python tools/mask_twobit_throughput.py 250 1 0 twobit"""
-import argparse
 import json
 import os
 import sys
@@ -19,8 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bench import write_fasta  # noqa: E402
-from deepgrp_amd import synthetic, twobit  # noqa: E402
-from deepgrp_amd.__main__ import CommandLineParser  # noqa: E402
+from deepgrp_amd import masking, synthetic, twobit  # noqa: E402
 from deepgrp_amd.pipeline import SEGMENT_DTYPE  # noqa: E402
 
 
@@ -33,10 +31,10 @@ def spread(xs):
 
 
 def write(path, final, rows, form):
-    args = argparse.Namespace(mask="soft", mask_classes=None, mask_gzip=False, mask_twobit=form == "twobit")
+    plan = masking.MaskPlan({}, "soft", None, twobit=form == "twobit")
     torch.cuda.synchronize()
     t = time.perf_counter()
-    CommandLineParser._write_mask(path, final, rows, args)
+    masking.write_mask(path, final, rows, plan)
     torch.cuda.synchronize()
     return (time.perf_counter() - t) * 1e3
 
@@ -84,7 +82,7 @@ def main():
                 if rep >= warm:
                     ms[form].append(t)
         for form in forms:
-            emit(what="_write_mask", form=form, ms=spread(ms[form]), mbp_per_s=round(n / (float(np.median(ms[form])) * 1e-3) / 1e6, 1),
+            emit(what="write_mask", form=form, ms=spread(ms[form]), mbp_per_s=round(n / (float(np.median(ms[form])) * 1e-3) / 1e6, 1),
                  note="file bytes in the page cache -> masked copy renamed into place in /dev/shm; upload, chunk table, mask, "
                       + ("pack, read-back of the blobs, spool and assembly" if form == "twobit" else "read-back of the text, write"))
     finally:
