@@ -41,6 +41,10 @@ Differences, all additive:
   * `evaluate --boundaries PREFIX` also writes how well the found elements are delimited, PREFIX.boundaries.tsv (the offset of
     either edge, annotation rows against the predicted labels and predicted rows against the truth) and PREFIX.fragments.tsv (the
     runs under a row), from counts made on the GPU (deepgrp_amd/boundaries.py);
+  * `compare <predicted> <annotation> <FASTA>... [--classes C]` gives `evaluate`'s report, and --strata, --offtarget and
+    --boundaries, for rows that are already on disk -- a prediction TSV, a table `contig begin end number` or a RepeatMasker
+    listing -- without a model: the files are parsed on the GPU and the rows flattened to one label per base first
+    (deepgrp_amd/compare.py);
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -363,11 +367,45 @@ class CommandLineParser:
                               help="length edges of --strata in bases, ascending, 1..15 of them (default with --strata: 100,300,1000,3000)")
         evaluate.add_argument("--strata_bins", type=int, default=None,
                               help="probability bins of PREFIX.strata.bases.tsv, 2..1000 (default with --strata: 100)")
+        compare = subparsers.add_parser(
+            name="compare", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+            description="(addition) `evaluate`'s report for rows that are already on disk: the TSV `predict` (or the reference) "
+                        "wrote, another tool's calls as a table `contig begin end number`, or a RepeatMasker listing, against a "
+                        "repeat annotation.  No model is read and no forward pass runs; the inputs give the records, their names and "
+                        "the evaluated span of each.  The predicted rows of a record are flattened first: painted onto its span "
+                        "(the smallest label wins) and read back as the runs `predict` would have written.")
+        compare.add_argument("predicted", type=str, help="the rows to score: a prediction TSV, a table or a RepeatMasker listing "
+                                                         "(plain, gzip or BGZF), parsed on the GPU")
+        compare.add_argument("annotation", type=str, help="the annotation, as for evaluate")
+        compare.add_argument("FASTA", nargs="+", type=str, help="inputs as for predict and evaluate")
+        compare.add_argument("--classes", type=int, default=5, help="classes of the labels, background included, 2..64")
+        compare.add_argument("--repeats", type=class_list, default=None,
+                             help="comma-separated repeat numbers to keep from the annotation (default: 1..classes-1)")
+        compare.add_argument("--predicted_format", choices=("auto", "tsv", "table", "repeatmasker"), default="auto",
+                             help="what PREDICTED is; `auto` looks at its first lines: tsv, then repeatmasker, else table")
+        compare.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+                             help="what the annotation is; `auto` looks at its first lines")
+        compare.add_argument("--min_overlap", type=float, default=0.5, help="as for evaluate, in (0, 1]")
+        compare.add_argument("--output", type=str, default="-", help="TSV report ('-' = standard output)")
+        compare.add_argument("--json", type=str, default=None, help="also write every figure as JSON here")
+        compare.add_argument("--curves", type=str, default=None, metavar="PREFIX", help="refused: the curves need probabilities and scores")
+        compare.add_argument("--curve_bins", type=int, default=None, help="refused, as --curves")
+        compare.add_argument("--curve_elements", action="store_true", help="refused, as --curves")
+        compare.add_argument("--strata", type=str, default=None, metavar="PREFIX",
+                             help="as for evaluate, but PREFIX.strata.tsv alone: PREFIX.strata.bases.tsv needs probabilities")
+        compare.add_argument("--strata_div", type=str, default=None, help="as for evaluate")
+        compare.add_argument("--strata_len", type=str, default=None, help="as for evaluate")
+        compare.add_argument("--strata_bins", type=int, default=None, help="accepted for evaluate's sake; no file of compare reads it")
+        compare.add_argument("--offtarget", type=str, default=None, metavar="PREFIX", help="as for evaluate")
+        compare.add_argument("--offtarget_by", choices=("family", "class"), default=None, help="as for evaluate")
+        compare.add_argument("--boundaries", type=str, default=None, metavar="PREFIX", help="as for evaluate")
+        compare.add_argument("--boundary_max", type=int, default=None, metavar="W", help="as for evaluate")
+        compare.add_argument("--boundary_join", type=int, default=None, metavar="G", help="as for evaluate")
 
     def parse_args(self, argv=None) -> "CommandLineParser":
         argv = list(sys.argv[1:] if argv is None else argv)
         # README form `deepgrp <modelfile> <fastafile>`: insert the sub-command before the first positional
-        if not any(a in ("predict", "train", "verify", "evaluate", "optimize") for a in argv):
+        if not any(a in ("predict", "train", "verify", "evaluate", "optimize", "compare") for a in argv):
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
                            "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score", "--bed_names",
@@ -726,6 +764,74 @@ class CommandLineParser:
             sys.exit(str(e))
         for r, (_m, p) in zip(reports, plans):
             r.write(p, _LOG)
+        text = tsv_report(rep)
+        if args.output == "-":
+            sys.stdout.write(text)
+            sys.stdout.flush()
+        else:
+            with open(args.output, "w") as fh:
+                fh.write(text)
+        if args.json is not None:
+            with open(args.json, "w") as fh:
+                json.dump(rep, fh, indent=1, allow_nan=False)
+                fh.write("\n")
+
+    @staticmethod
+    def compare(args: argparse.Namespace, options) -> None:
+        """Score rows that are already on disk against an annotation (deepgrp_amd/compare.py): `evaluate`'s report without a model."""
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("compare runs in one process on one GPU; it cannot be sharded (WORLD_SIZE > 1)")
+        for output in _OUTPUTS:
+            output.refuse_on_evaluate(args)
+        # what needs probabilities or scores is refused by name before anything is read
+        for flag, given in (("--curves", args.curves is not None), ("--curve_elements", args.curve_elements),
+                            ("--curve_bins", args.curve_bins is not None)):
+            if given:
+                sys.exit(f"{flag} needs the probabilities and row scores of a forward pass, which compare does not run: the curves "
+                         "belong to evaluate")
+        if not 0.0 < args.min_overlap <= 1.0:
+            sys.exit(f"--min_overlap must lie in (0, 1], not {args.min_overlap}")
+        from . import compare as dgcompare
+        classes = args.classes
+        if not dgcompare.MIN_CLASSES <= classes <= dgcompare.MAX_CLASSES:
+            sys.exit(f"--classes must lie in {dgcompare.MIN_CLASSES}..{dgcompare.MAX_CLASSES}, not {classes}")
+        repeats = sorted(set(args.repeats)) if args.repeats is not None else list(range(1, classes))
+        bad = [r for r in repeats if not 0 < r < classes]
+        if bad:
+            sys.exit(f"--repeats: {bad[0]} is not a repeat class of --classes {classes} (1..{classes - 1})")
+        from . import boundaries as dgboundaries, offtarget as dgofftarget, strata as dgstrata
+        plans = [(m, p) for m in (dgstrata, dgofftarget, dgboundaries) for p in [m.plan(args)] if p is not None]
+        for _m, p in plans:
+            for out in (v for k, v in p._asdict().items() if k.endswith("_path")):
+                if os.path.exists(args.predicted) and os.path.realpath(out) == os.path.realpath(args.predicted):
+                    sys.exit(f"the file {out} would overwrite the input {args.predicted}")
+        import json
+
+        from . import annotation as dgann
+        from .evaluation import AnnotationError, NoMatchError, tsv_report
+        listed = dgann.resolve_format(args.annotation, args.annotation_format) == "repeatmasker"
+        try:
+            predicted = dgcompare.read_predicted(args.predicted, args.predicted_format, classes)
+            if any(m is dgofftarget for m, _p in plans):
+                annotation = dgann.evaluation_rows(args.annotation, repeats, offtarget=True)
+            else:
+                annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else dgcompare.read_table(args.annotation, repeats)
+        except AnnotationError as e:
+            sys.exit(str(e))
+        info = dict(predicted=args.predicted, predicted_format=predicted.format, annotation=args.annotation, inputs=list(args.FASTA),
+                    repeats=repeats, options=dict(min_overlap=args.min_overlap),
+                    predicted_rows=dict(read=predicted.rows_read, dropped=predicted.rows_dropped))
+        reports = [m.from_plan(p, classes, annotation) for m, p in plans]
+        try:
+            rep = dgcompare.compare(predicted, annotation, ((f, _records_of(f)) for f in args.FASTA), classes, repeats, args.min_overlap,
+                                    info, reports)
+        except (NoMatchError, dgcompare.NoPredictedError) as e:
+            sys.exit(str(e))
+        for r, (m, p) in zip(reports, plans):
+            if m is dgstrata:
+                dgcompare.write_strata(r, p, _LOG)
+            else:
+                r.write(p, _LOG)
         text = tsv_report(rep)
         if args.output == "-":
             sys.stdout.write(text)

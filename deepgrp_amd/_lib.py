@@ -173,6 +173,8 @@ _SIGNATURES = {
     "dgrp_prob_hist_strata_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, vp, vp, vp, i64, vp]),
     "dgrp_rm_parse_all_workspace_bytes": (i64, [i64]),
     "dgrp_rm_parse_all": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_rows_parse_workspace_bytes": (i64, [i64]),
+    "dgrp_rows_parse": (cint, [vp, i64, cint, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
     "dgrp_token_ids_workspace_bytes": (i64, [i64, i64]),
     "dgrp_token_ids": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     "dgrp_paint_keys_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),

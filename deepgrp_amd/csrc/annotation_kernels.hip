@@ -9,17 +9,12 @@
 // but the OR of the flag; a count pass and a write pass around one scan give every row its place, so the same call gives the same bytes.
 // dgrp_rm_parse_all is one more mode of the same two passes: every line that matches a pattern is a row, numbered or not, and the
 // span (or the two spans) of its family token travels with it.
-#include "scan.h"
+#include "text_lines.h"                  // tiles, chunks, the chunk scan and the run starts: shared with dgrp_rows_parse
 
 namespace {
 
-#define RM_CHUNK 128                     // bytes per lane
-#define RM_TILE (256 * RM_CHUNK)         // bytes per workgroup (DGRP_RM_TILE_BYTES)
-#define RM_HEAD 256                      // workspace head: [0] the not-plain flag
 #define RM_MIN_LINE 22                   // shortest line that can match: 11 tokens of one byte, 10 separators, the line end
 #define RM_MAX_DIGITS 18                 // a coordinate of more digits is left to the host
-
-static_assert(RM_TILE == DGRP_RM_TILE_BYTES, "the header states the tile");
 
 struct rm_tables {
     const uint8_t *names;                // the numbered names back to back
@@ -49,9 +44,6 @@ struct rm_str {
         return j < la ? t[ab + j] : (j == la ? (uint8_t)'/' : t[bb + (j - la - 1)]);
     }
 };
-
-__host__ __device__ __forceinline__ bool rm_eol(uint8_t c) { return c == '\n' || c == '\r'; }
-__host__ __device__ __forceinline__ bool rm_blank(uint8_t c) { return c == ' ' || c == '\t'; }
 
 __host__ __device__ bool rm_equals(const uint8_t *__restrict__ t, const rm_str &s, const uint8_t *__restrict__ word, int64_t wlen)
 {
@@ -241,43 +233,6 @@ __host__ __device__ int32_t rm_millidiv(const uint8_t *__restrict__ t, const rm_
     return 10 * val + first;
 }
 
-// The lane's chunk: mask of its line feeds (bit k of lo / hi: byte c0 + k / c0 + 64 + k) and whether a byte of it makes the file not
-// plain: outside 0x20..0x7e, tab and line feed, or a carriage return that no line feed follows.
-__host__ __device__ __forceinline__ void rm_scan_chunk(const uint8_t *__restrict__ t, int64_t c0, int64_t n, bool aligned, uint64_t &lo,
-                                              uint64_t &hi, bool &bad)
-{
-    lo = hi = 0;
-    bool cr = false;                                                         // the byte before was a carriage return
-    const int64_t c1 = c0 + RM_CHUNK < n ? c0 + RM_CHUNK : n;
-#pragma unroll
-    for (int g = 0; g < RM_CHUNK / 16; ++g) {
-        const int64_t p0 = c0 + 16 * g;
-        if (p0 >= c1) break;
-        uint32_t w[4] = { 0u, 0u, 0u, 0u };
-        const int valid = c1 - p0 < 16 ? (int)(c1 - p0) : 16;
-        if (valid == 16 && aligned) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(t + p0);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else {
-            for (int j = 0; j < valid; ++j) w[j >> 2] |= (uint32_t)t[p0 + j] << (8 * (j & 3));
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (j < valid) {
-                const uint32_t c = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-                const bool lf = c == '\n';
-                if (cr && !lf) bad = true;
-                cr = c == '\r';
-                if (!((c >= 0x20u && c <= 0x7eu) || c == '\t' || lf || cr)) bad = true;
-                if (lf) {
-                    if (g < 4) lo |= 1ull << (16 * g + j); else hi |= 1ull << (16 * (g - 4) + j);
-                }
-            }
-        }
-    }
-    if (cr && (c1 >= n || t[c1] != '\n')) bad = true;
-}
-
 struct rm_out {
     int64_t *begin, *end;
     int32_t *number;
@@ -380,29 +335,6 @@ __global__ void __launch_bounds__(256) rm_lines_kernel(const uint8_t *__restrict
     }
 }
 
-// flag[i] = 1 where row i opens a run: its name differs from the name of row i - 1
-__global__ void __launch_bounds__(256) rm_run_flag_kernel(const uint8_t *__restrict__ t, const int64_t *__restrict__ name_pos,
-                                                          const int32_t *__restrict__ name_len, int64_t rows,
-                                                          uint64_t *__restrict__ flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    bool opens = i == 0 || name_len[i] != name_len[i - 1];
-    if (!opens && name_pos[i] != name_pos[i - 1]) {
-        const uint8_t *a = t + name_pos[i], *b = t + name_pos[i - 1];
-        for (int32_t j = 0; j < name_len[i] && !opens; ++j) opens = a[j] != b[j];
-    }
-    flag[i] = opens ? 1ull : 0ull;
-}
-
-// run[i] = the exclusive scan of the flags, run[rows] their sum: row i opens run run[i] where the scan moves behind it
-__global__ void __launch_bounds__(256) rm_run_first_kernel(const uint64_t *__restrict__ run, int64_t rows, int64_t *__restrict__ first)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < rows && run[i + 1] != run[i]) first[run[i]] = i;
-}
-
-static inline int64_t rm_tiles_of(int64_t n) { return (n + RM_TILE - 1) / RM_TILE; }
 static inline int64_t rm_rows_bound(int64_t n) { return n / RM_MIN_LINE + 1; }
 
 }   // namespace
@@ -498,8 +430,8 @@ int rm_parse_run(const char *what, bool fields, const rm_fam_out *fam, const uin
                        d_end, d_number, d_name_pos, d_name_len, d_line, fields ? d_millidiv : (int32_t *)nullptr, fo.pos, fo.len, fo.pos2,
                        fo.len2, all, cap);
     DGRP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rm_run_flag_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, d_text, d_name_pos, d_name_len, rows,
-                       d_run);
+    hipLaunchKernelGGL(rm_run_flag_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, d_text, d_name_pos, d_name_len,
+                       (const int64_t *)nullptr, (const int32_t *)nullptr, rows, d_run);
     DGRP_LAUNCH_CHECK();
     rc = device_exclusive_scan(d_run, d_run, rows, d_tiles, d_run + rows, stream);
     if (rc != DGRP_OK) return rc;

@@ -1112,6 +1112,36 @@ int dgrp_rm_parse_all(const uint8_t *d_text, int64_t n, const uint8_t *d_names, 
                       int64_t *d_fam_pos, int32_t *d_fam_len, int64_t *d_fam2_pos, int32_t *d_fam2_len, int64_t cap, int64_t *h_counts,
                       void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- rows as text read on the device (an addition, `compare`): the table evaluation.read_annotation reads and the TSV
+ * `predict` writes.  d_text [n]: the text in device memory, any alignment.  format 0, TABLE: a line is its tokens between runs of
+ * blanks (space, tab); a line without a token, or whose first token opens with '#', is skipped; fewer than four tokens make it
+ * MALFORMED (reason 1); else it is a row: token 0 the name, tokens 1..3 begin, end, number, further tokens ignored.  format 1, TSV:
+ * a line is its fields between single tabs; an empty line is skipped; fewer than five fields make it MALFORMED (reason 2); else it
+ * is a row: the last three fields are begin, end, number, the first is the file, and what lies between (tabs included) is the
+ * header.  Its name is the first word of the header (between blanks; empty where it has none) -- but where the file field ends in
+ * `.npz`, the piece of the file field behind its last '/' up to the first '.'.  A carriage return directly before the line feed
+ * ends the line with it.
+ * Rows, in file order, i = 0 .. rows - 1: d_begin[i], d_end[i], d_number[i] (int64), d_name_pos[i] / d_name_len[i] (the name as a
+ * span of d_text), d_line[i] (from 1); TSV only, d_file_pos[i] / d_file_len[i] (the file field; both may be NULL for a table).
+ * d_run_first[r], r = 0 .. runs - 1: the first row of run r, a maximal stretch of rows whose names (TSV: and file fields) are
+ * byte-equal.  h_counts[6] (host): lines, rows, runs, the not-decided flag, the line (from 1) of the first malformed line or 0, its
+ * reason.
+ * NOT DECIDED: a byte outside 0x20..0x7e other than tab and line feed, a carriage return not directly before a line feed, or a
+ * begin, end or number that is not 1..18 plain decimal digits (a sign, '_', a blank inside a TSV field, 19 digits).  Then
+ * h_counts[3] = 1, no row is written and DGRP_OK is returned: the caller parses such a file on the host.  A MALFORMED line in a
+ * file that is decided: h_counts[4] and [5] state the first, no row is written, DGRP_OK.  More rows than `cap`: DGRP_ENOMEM,
+ * h_counts[1] = the capacity needed, no row written; n / 8 + 1 rows always suffice.  n = 0: zero counts.  Refused before any launch
+ * with DGRP_EINVAL: NULL text with n > 0, n < 0, another format, a NULL output with cap > 0, NULL counts; with DGRP_ENOMEM: a
+ * workspace (256-byte aligned) below dgrp_rows_parse_workspace_bytes(n).
+ * The work split is dgrp_rm_parse's: DGRP_RM_TILE_BYTES per workgroup, a lane per 128 bytes and the lines that start there; a count
+ * pass, two scans, a write pass, then the run flags, their scan and the run starts.  Integers only; the only atomics are the OR of
+ * the flag and the min of the first malformed line's position: the same call gives the same bytes.  On the caller's stream; it
+ * SYNCHRONISES that stream twice (counts, then runs; once where no row is written) and allocates nothing. */
+int64_t dgrp_rows_parse_workspace_bytes(int64_t n);
+int dgrp_rows_parse(const uint8_t *d_text, int64_t n, int format, int64_t *d_begin, int64_t *d_end, int64_t *d_number,
+                    int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_file_pos, int32_t *d_file_len, int64_t *d_line,
+                    int64_t *d_run_first, int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- off-target (an addition, evaluate --offtarget): what the predicted repeats lie on.
  * dgrp_token_ids: dense ids for `rows` tokens given as spans of d_text [n] (device).  Token i is the bytes d_pos[i] .. + d_len[i],
  * and with d_len2[i] > 0 the logical string of those bytes, '/', and the bytes d_pos2[i] .. + d_len2[i]; a one-span and a two-span
