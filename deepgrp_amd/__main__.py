@@ -22,6 +22,9 @@ Differences, all additive:
     items with 32-bit coordinates, an R-tree and coverage zoom levels, written and deflated on the GPU); with --bed_gff3 the file
     is GFF3 instead (`.gff3`, deepgrp_amd/gff.py: one `repeat_region` feature per row with the BED's figures as attributes, written
     on the GPU; `--bed_names A,B,...` names the labels; `.gff3.gz` and `.gff3.gz.tbi` with --bed_gzip and --bed_index);
+    with --bed_rmout the file is a RepeatMasker listing instead (`.out`, `.out.gz` with --bed_gzip; deepgrp_amd/rmout.py: the
+    format `evaluate`, `compare`, `train` and `parse_rm` read, written on the GPU; `--rmout_repeats N,N,...` or `--bed_names
+    repeat#class/family,...` name the labels, `--rmout_join G` gives the fragments of one element one ID);
   * `predict --seq_dir DIR [--seq_classes 1,3] [--seq_flank N] [--seq_width W]` also writes the sequences of the predicted repeats
     of every input as FASTA, DIR/<basename>.repeats.fa: one record `>NAME:A-B class<label>` per TSV row, gathered on the GPU
     (deepgrp_amd/repeatseq.py); with --seq_gzip as BGZF (`.repeats.fa.gz`), with --seq_fai a `.fai` index beside it;
@@ -409,6 +412,7 @@ class CommandLineParser:
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
                            "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score", "--bed_names",
+                           "--rmout_repeats", "--rmout_join",
                            "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width", "--summary_dir", "--summary_bin"}
             i = 0
             while i < len(argv):

@@ -135,6 +135,9 @@ _SIGNATURES = {
     "dgrp_gff_index_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64]),
     "dgrp_gff_index_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, i64, vp, vp, i64, C.POINTER(i64), vp, i64, vp, vp,
                                     i64, vp]),
+    "dgrp_rmout_text_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64]),
+    "dgrp_rmout_text_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, vp, i64, i64, vp, i64, C.POINTER(i64),
+                                     C.POINTER(i64), C.POINTER(i64), vp, i64, vp]),
     "dgrp_bed_blocks_workspace_bytes": (i64, [i64, i64, vp]),
     "dgrp_bed_blocks_batch": (cint, [cint, vp, vp, i64, cint, i64, vp, i64, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64),
                                      vp, i64, vp]),

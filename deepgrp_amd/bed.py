@@ -29,7 +29,13 @@ a record that ends above 2^32 - 1) gets one warning and no `.bb`.
 With `--bed_gff3` the file is `DIR/<basename>.gff3` instead (`.gff3.gz` with --bed_gzip, `.gff3.gz.tbi` with --bed_index), GFF3 as
 gff.py states it: the same rows and figures, written on the device whether deflated or not (ContigPipeline.gff_write).  The `ID`
 ordinals run through the file, so `BedFiles` counts the lines and hands every write its first ordinal (gff.GffWrite.render).  An
-input with an empty record name gets one warning and no `.gff3`."""
+input with an empty record name gets one warning and no `.gff3`.
+
+With `--bed_rmout` the file is `DIR/<basename>.out` instead (`.out.gz` with --bed_gzip), a RepeatMasker listing as rmout.py states
+it: the same rows with the BED's score, named after the numbered families of `parse_rm` (--rmout_repeats) or after --bed_names,
+written on the device whether deflated or not (ContigPipeline.rmout_write).  The IDs run through the file and fragments that
+--rmout_join joins share one, so `BedFiles` counts the IDS used and hands every write its first (rmout.RmoutWrite.render).  An input
+with a record name that cannot stand in a blank-separated column gets one warning and no `.out`."""
 from __future__ import annotations
 
 import argparse
@@ -57,11 +63,15 @@ class BedPlan(NamedTuple):
     bigbed: bool = False                            # --bed_bigbed (gzip_level is then the level of its zlib streams)
     gff3: bool = False                              # --bed_gff3 (gzip_level None: the device's text, not deflated)
     class_names: Optional[tuple] = None             # --bed_names: the name of label 1..C-1, as given (gff.py escapes them)
+    rmout: bool = False                             # --bed_rmout (gzip_level None: the device's text, not deflated)
+    rmout_repeats: Optional[tuple] = None           # --rmout_repeats: the repeat number of label 1..C-1 (None: 1..C-1)
+    rmout_join: int = -1                            # --rmout_join: the largest gap inside one ID (-1: every line its own)
+    rmout_pairs: Optional[tuple] = None             # (repeat, class/family) of label 1..C-1, once the class count is known (from_plan)
 
     @property
     def on_device(self) -> bool:
         """Whether the write is made on the device (ContigPipeline.bed_write) rather than from scores on the host."""
-        return self.gzip_level is not None or self.gff3
+        return self.gzip_level is not None or self.gff3 or self.rmout
 
 
 class BedWrite(NamedTuple):
@@ -76,11 +86,11 @@ class BedWrite(NamedTuple):
     last_end: Optional[np.ndarray] = None
 
 
-def bed_path(directory: str, filename: str, gzip: bool = False, bigbed: bool = False, gff3: bool = False) -> str:
+def bed_path(directory: str, filename: str, gzip: bool = False, bigbed: bool = False, gff3: bool = False, rmout: bool = False) -> str:
     from .tracks import input_basename
     if bigbed:
         return os.path.join(directory, input_basename(filename) + ".bb")
-    return os.path.join(directory, input_basename(filename) + (".gff3" if gff3 else ".bed") + (".gz" if gzip else ""))
+    return os.path.join(directory, input_basename(filename) + (".out" if rmout else ".gff3" if gff3 else ".bed") + (".gz" if gzip else ""))
 
 
 def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
@@ -94,6 +104,9 @@ def empty_write(p: BedPlan, name, startpos: int, chrom: int = 0):
     if p.gff3:
         from .gff import GffWrite
         return GffWrite(raw)
+    if p.rmout:
+        from .rmout import RmoutWrite
+        return RmoutWrite(raw)
     return BedWrite(b"", raw)
 
 
@@ -129,7 +142,20 @@ def add_options(parser) -> None:
     parser.add_argument("--bed_names", type=str, default=s,
                         help="(addition) with --bed_gff3: the names of the labels 1..classes-1, comma-separated, written as Name= in the "
                              "place of class<label> (each 1..255 bytes; reserved characters are %%-escaped); with --summary_dir: the "
-                             "label column of its tables")
+                             "label column of its tables; with --bed_rmout: repeat#class/family per label, the naming of "
+                             "RepeatMasker's libraries (exactly one '#', no blank)")
+    parser.add_argument("--bed_rmout", action="store_true", default=s,
+                        help="(addition) with --bed_dir: write the scored repeats as a RepeatMasker listing, DIR/<basename>.out, instead "
+                             "of BED text: the two title lines, then per row the BED's score, 0.0 0.0 0.0 (no divergence is "
+                             "predicted), the record's name, start+1, end, (left), +, repeat, class/family, 1, end-start, (0), ID, "
+                             "written on the GPU.  With --bed_gzip DIR/<basename>.out.gz (BGZF).  A record name with a blank: a "
+                             "warning and no listing for that input.  Not with --bed_bigbed, --bed_gff3 or --bed_index")
+    parser.add_argument("--rmout_repeats", type=str, default=s, metavar="N,N,...",
+                        help="(addition) with --bed_rmout: the repeat number (1..10, the numbered families of parse_rm) of the labels "
+                             "1..classes-1, distinct; 1..classes-1 unless given.  Not with --bed_names")
+    parser.add_argument("--rmout_join", type=int, default=s, metavar="G",
+                        help="(addition) with --bed_rmout: consecutive lines of one record and one label at most G bases apart share "
+                             "their ID, as RepeatMasker numbers the fragments of one element (every line its own ID unless given)")
 
 
 def refuse_on_evaluate(args) -> None:
@@ -142,6 +168,10 @@ def refuse_on_evaluate(args) -> None:
     if (getattr(args, "bed_dir", None) is not None or getattr(args, "bed_min_score", None) is not None
             or getattr(args, "bed_gzip", False) or getattr(args, "bed_index", False)):
         sys.exit("--bed_dir belongs to predict, not evaluate")
+    if getattr(args, "bed_rmout", False):
+        sys.exit("--bed_rmout belongs to predict, not evaluate or compare")
+    if getattr(args, "rmout_repeats", None) is not None or getattr(args, "rmout_join", None) is not None:
+        sys.exit("--rmout_repeats and --rmout_join belong to predict, not evaluate or compare")
 
 
 def plan(args) -> Optional[BedPlan]:
@@ -156,15 +186,17 @@ def plan(args) -> Optional[BedPlan]:
         sys.exit("--bed_gff3 needs --bed_dir")
     if gff3 and bigbed:
         sys.exit("--bed_gff3 and --bed_bigbed each write their file instead of the BED text: they do not go together")
-    if cnames is not None and not gff3:
+    rmout, repeats, join = bool(getattr(args, "bed_rmout", False)), getattr(args, "rmout_repeats", None), getattr(args, "rmout_join", None)
+    if cnames is not None and not gff3 and not rmout:
         if getattr(args, "summary_dir", None) is None:
             sys.exit("--bed_names needs --bed_gff3")
         cnames = None                                   # (they name the labels of --summary_dir only)
     if cnames is not None:
-        from .gff import names_refusal
+        from . import gff, rmout as dgrmout
         cnames = tuple(nm.encode("utf-8", "surrogateescape") for nm in cnames.split(","))
-        if names_refusal(cnames) is not None:
-            sys.exit(names_refusal(cnames))
+        refusal = dgrmout.names_refusal if rmout and not gff3 else gff.names_refusal
+        if refusal(cnames) is not None:
+            sys.exit(refusal(cnames))
     if bigbed and bdir is None:
         sys.exit("--bed_bigbed needs --bed_dir")
     if bigbed and (gzip or index):
@@ -173,6 +205,29 @@ def plan(args) -> Optional[BedPlan]:
         sys.exit("--bed_gzip needs --bed_dir")
     if index and not gzip:
         sys.exit("--bed_index needs --bed_gzip")
+    if rmout and bdir is None:
+        sys.exit("--bed_rmout needs --bed_dir")
+    if rmout and (bigbed or gff3):
+        sys.exit("--bed_rmout, --bed_gff3 and --bed_bigbed each write their file instead of the BED text: they do not go together")
+    if rmout and index:
+        sys.exit("--bed_rmout does not go with --bed_index: the listing is blank-separated, and tabix indexes tab-separated columns")
+    if repeats is not None:
+        if not rmout:
+            sys.exit("--rmout_repeats needs --bed_rmout")
+        if cnames is not None:
+            sys.exit("--rmout_repeats and --bed_names both name the labels of the listing: they do not go together")
+        from .rmout import repeats_refusal
+        try:
+            repeats = tuple(int(tok) for tok in repeats.split(","))
+        except ValueError:
+            sys.exit(f"--rmout_repeats: {repeats!r} is not a comma-separated list of numbers")
+        if repeats_refusal(repeats) is not None:
+            sys.exit(repeats_refusal(repeats))
+    if join is not None:
+        if not rmout:
+            sys.exit("--rmout_join needs --bed_rmout")
+        if join < 0:
+            sys.exit(f"--rmout_join must be 0 or more, not {join}")
     if bdir is None:
         if low is not None:
             sys.exit("--bed_min_score needs --bed_dir")
@@ -184,19 +239,35 @@ def plan(args) -> Optional[BedPlan]:
         sys.exit("--bed_dir runs in one process (WORLD_SIZE > 1 and --split_contigs are not supported: the scores are summed on the "
                  "rank that holds the merged probabilities)")
     from .outfiles import plan_inputs
-    paths = plan_inputs("--bed_dir", args.FASTA, lambda f: bed_path(bdir, f, gzip, bigbed, gff3), "BED files", "BED file")
+    paths = plan_inputs("--bed_dir", args.FASTA, lambda f: bed_path(bdir, f, gzip, bigbed, gff3, rmout), "BED files", "BED file")
     level = None
     if gzip or bigbed:
         from .tracks import gzip_level
         level = gzip_level(args, 1)
-    return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames)
+    return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames, rmout, repeats, -1 if join is None else int(join))
 
 
 def from_plan(p: BedPlan, classes: int) -> "Bed":
-    """The number of --bed_names checked against the model's class count (sys.exit)."""
+    """The number of --bed_names checked against the model's class count (sys.exit); with --bed_rmout the number of
+    --rmout_repeats as well, and the (repeat, class/family) pair of every label is settled."""
     if p.class_names is not None and len(p.class_names) != classes - 1:
         sys.exit(f"--bed_names gives {len(p.class_names)} names, but the model has {classes - 1} repeat classes "
                  f"(labels 1..{classes - 1})")
+    if p.rmout:
+        from . import rmout
+        if p.class_names is not None:
+            pairs = rmout.pairs_of_names(p.class_names)
+        elif p.rmout_repeats is not None:
+            if len(p.rmout_repeats) != classes - 1:
+                sys.exit(f"--rmout_repeats gives {len(p.rmout_repeats)} numbers, but the model has {classes - 1} repeat classes "
+                         f"(labels 1..{classes - 1})")
+            pairs = rmout.pairs_of_repeats(p.rmout_repeats)
+        elif classes - 1 > rmout.MAX_REPEATS:
+            sys.exit(f"--bed_rmout: the model has {classes - 1} repeat classes, more than the {rmout.MAX_REPEATS} numbered families "
+                     "of parse_rm: name the labels with --bed_names (repeat#class/family)")
+        else:
+            pairs = rmout.pairs_of_repeats(range(1, classes))
+        p = p._replace(rmout_pairs=pairs)
     return Bed(p)
 
 
@@ -244,7 +315,10 @@ class BedFiles(StagedOutputs):
     no `.bb`: `commit` then removes the temporary file and any `.bb` an earlier run left.  With p.gff3 the file is a `.gff3[.gz]`
     that begins with gff.HEADER (a BGZF member of its own), `write` takes a gff.GffWrite and renders it with the lines written so
     far (`lines`); the names of the index are the escaped seqids of column 1; an input with an empty record name gets one warning
-    and no `.gff3`, as a bigBed does."""
+    and no `.gff3`, as a bigBed does.  With p.rmout the file is a `.out[.gz]` that begins with rmout.HEADER (a BGZF member of its
+    own), `write` takes an rmout.RmoutWrite and renders it with the IDs used so far (`ids`: joined fragments share one, so the count
+    advances by the IDs, not by the lines); an input with a record name that cannot stand in a blank-separated column gets one
+    warning and no `.out`."""
 
     def __init__(self, p: BedPlan, filename: str):
         os.makedirs(p.directory, exist_ok=True)
@@ -252,6 +326,7 @@ class BedFiles(StagedOutputs):
         self.gzip = p.gzip_level is not None and not self.bigbed
         self.bb_refused = None
         self.gff3, self.lines = bool(getattr(p, "gff3", False)), 0
+        self.rmout, self.ids = bool(getattr(p, "rmout", False)), 0
         preset = ()
         if self.gff3:
             from . import gff
@@ -259,7 +334,7 @@ class BedFiles(StagedOutputs):
         super().__init__(_LOG, filename, "--bed_index", self.gzip and p.index,
                          [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index, *preset) if self.gzip
                           else StagedFile(self.final)])
-        if self.gff3:
+        if self.gff3 or self.rmout:
             try:
                 self._gff_header(p.gzip_level)
             except BaseException:
@@ -267,15 +342,39 @@ class BedFiles(StagedOutputs):
                 raise
 
     def _gff_header(self, level) -> None:
-        """gff.HEADER in front of everything: in a BGZF file a member of its own, which no chunk of the index touches."""
-        from . import gff
+        """gff.HEADER (rmout.HEADER) in front of everything: in a BGZF file a member of its own, which no chunk of the index touches."""
+        from . import gff, rmout
+        form = rmout if self.rmout else gff
         if self.gzip:
             sink = self.parts[0]
-            member = gff.header_member(level)
+            member = form.header_member(level)
             sink.data.fh.write(member)
             sink.off += len(member)
         else:
-            self.parts[0].fh.write(gff.HEADER)
+            self.parts[0].fh.write(form.HEADER)
+
+    def _rmout(self, w) -> None:
+        """The write's part of the listing, or the input's refusal (one warning)."""
+        from . import rmout
+        if not isinstance(w, rmout.RmoutWrite):
+            raise ValueError(f"{self.filename}: a RepeatMasker listing is written from RmoutWrite, not from scores on the host")
+        if self.bb_refused is not None:
+            return
+        for nm in w.names:
+            why = rmout.record_name_refusal(nm)
+            if why is not None:
+                self.bb_refused = why
+                _LOG.warning("%s: no RepeatMasker listing is written (--bed_rmout): %s", self.filename, why)
+                return
+        if w.render is None:
+            return
+        t = w.render(self.ids)
+        self.lines += t.lines
+        self.ids += t.ids
+        if self.gzip:
+            self.append(0, t.data, w.names)
+        else:
+            self.append(0, t.data)
 
     def _gff(self, w) -> None:
         """The write's part of the GFF3 file, or the input's refusal (one warning)."""
@@ -340,6 +439,8 @@ class BedFiles(StagedOutputs):
             return self._bigbed(scores)
         if self.gff3:
             return self._gff(scores)
+        if self.rmout:
+            return self._rmout(scores)
         if not isinstance(scores, BedWrite):
             if self.gzip:
                 raise ValueError(f"{self.filename}: a BGZF BED is written from BedWrite, not from scores on the host")

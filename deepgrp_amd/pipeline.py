@@ -806,6 +806,8 @@ class ContigPipeline:
             return self.bigbed_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan, chrom0)
         if getattr(plan, "gff3", False):                    # --bed_gff3: GFF3 lines instead of BED lines
             return self.gff_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan)
+        if getattr(plan, "rmout", False):                   # --bed_rmout: the lines of a RepeatMasker listing instead
+            return self.rmout_write(d_probs, row0, lengths, startposes, rows, row_off, names, by_contig, plan)
         from .bed import BedWrite
         from .gz import bgzf_members_device
         from .tabix import end_refusal
@@ -927,6 +929,67 @@ class ContigPipeline:
                 return GffText(d_text.cpu().numpy().tobytes(), lines)
             return GffText(bgzf_members_device(d_text, plan.gzip_level), lines, *parts)
         return GffWrite(raw, refused, render)
+
+    # predict --bed_rmout: the rows as the lines of a RepeatMasker listing (rmout.py)
+    @staticmethod
+    def rmout_text_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, pairs,
+                         join_gap: int = -1, id0: int = 0):
+        """The lines (no title lines) of `d_rows` with `d_scores` (as bed_text_batch takes them) -> (uint8 device tensor, lines, IDs
+        used): one dgrp_rmout_text_batch call, what rmout.reference_lines gives for the same arguments.  pairs[L - 1] = (repeat,
+        class/family) of label L; record r (a row's contig with by_contig, else 0) ends at rec_end[r].  The text is complete behind
+        the call on the current stream."""
+        L = lib()
+        nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
+        if int(d_scores.numel()) != nrows * ROW_SCORE_DTYPE.itemsize:
+            raise ValueError(f"rmout_text_batch: {nrows} rows but {int(d_scores.numel())} bytes of scores")
+        ends = np.ascontiguousarray(rec_end, np.int64)
+        raw, blob, off = name_blob(names)
+        craw, cblob, coff = name_blob([x for pair in pairs for x in pair])
+        wb = int(L.dgrp_rmout_text_workspace_bytes(nrows, len(raw), len(blob), len(pairs), len(cblob), len(ends)))
+        if wb <= 0:
+            raise ValueError(f"rmout_text_batch: bad row count {nrows}, record count {len(ends)} or names")
+        work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        cap = nrows * (max(max(len(x) for x in raw), 16) + 120)             # (a guess that fits most runs; a longer text takes the retry)
+        got, lines, ids = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+        def launch(cap):
+            text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            check(L.dgrp_rmout_text_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff.ctypes.data, len(pairs), _ptr(d_rows),
+                                          _ptr(d_scores), nrows, int(min_score), len(ends), ends.ctypes.data, int(join_gap), int(id0),
+                                          _ptr(text), cap, C.byref(got), C.byref(lines), C.byref(ids), _ptr(work), wb, stream_ptr()),
+                  "dgrp_rmout_text_batch")
+            return text, (int(got.value),)
+        return _with_room(launch, cap)[:got.value], int(lines.value), int(ids.value)
+
+    def rmout_write(self, d_probs: torch.Tensor, row0, lengths, startposes, rows: np.ndarray, row_off, names, by_contig: bool, plan):
+        """One write of a RepeatMasker listing (rmout.RmoutWrite) for the arguments of bed_write: the scores are summed now and stay
+        on the device with the rows; the text and, with plan.gzip_level, its BGZF members are made when bed.BedFiles renders the write
+        with the IDs used in front of it (they run through the file), on the stream that is current then."""
+        from .rmout import RmoutText, RmoutWrite
+        raw = name_blob(names)[0]
+        r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "rmout_write", row0, lengths, startposes)
+        ends = sp + ln
+        rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
+        ro = np.ascontiguousarray(row_off, np.int64)
+        if len(rows) == 0:
+            return RmoutWrite(raw)
+        if len(ro) != len(ln) + 1 or int(ro[0]) != 0 or int(ro[-1]) != len(rows):
+            raise ValueError("rmout_write: the row offsets must cover all rows")
+        if plan.rmout_pairs is None:
+            raise ValueError("rmout_write: the plan has no names for the labels (bed.from_plan settles them)")
+        d_rows, d_scores = self._row_scores_device(d_probs, r0, ln, sp, rows, ro)
+        made = torch.cuda.Event()
+        made.record()
+
+        def render(id0: int) -> RmoutText:
+            from .gz import bgzf_members_device
+            made.wait()                                     # (the renderer's stream may be another one than the scores')
+            d_text, lines, ids = self.rmout_text_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends, plan.rmout_pairs,
+                                                       plan.rmout_join, id0)
+            if plan.gzip_level is None:
+                return RmoutText(d_text.cpu().numpy().tobytes(), lines, ids)
+            return RmoutText(bgzf_members_device(d_text, plan.gzip_level), lines, ids)
+        return RmoutWrite(raw, render)
 
     # predict --bed_bigbed: the rows as bigBed item blocks and coverage zoom records
     @staticmethod

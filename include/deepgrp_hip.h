@@ -794,6 +794,38 @@ int dgrp_gff_index_batch(const char *names, const int64_t *name_off, int64_t nna
                          dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
                          int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- RepeatMasker listing (predict --bed_rmout; deepgrp_amd/rmout.py states the file format).  The rows and scores of
+ * dgrp_bed_text_batch as the lines of a RepeatMasker `.out` file, one per emitted row (score >= min_score), in row order:
+ *   "%5d %5s %4s %4s  %-16s %9d %9d %11s +  %-12s %-16s %6d %6d %6s %6d\n" %
+ *       (score, "0.0", "0.0", "0.0", name, start + 1, end, "(left)", repeat, class/family, 1, end - start, "(0)", ID)
+ * every field max(its width, its digits or bytes) wide, numbers right-aligned, names left-justified, "(left)" with its parentheses
+ * inside the 11 columns.  score is the BED line's (the same R, the same envelope); name is name rows[r].contig (by_contig) or name
+ * 0; left = h_rec_end[record] - end, h_rec_end[r] (host, nrec entries) the end coordinate of record r (a row's contig with
+ * by_contig, else 0: then nrec must be 1); repeat and class/family are entries 2 (label - 1) and 2 (label - 1) + 1 of the
+ * class-name table (cnames, cname_off: laid out like the names, TWO entries per label, ncnames labels).  ID = id0 + the number of
+ * IDs opened up to and including the line: an emitted row opens an ID unless join_gap >= 0 and the emitted row directly in front of
+ * it is of the same record and label and start - its end <= join_gap (join_gap -1: every line its own ID); filtered rows neither
+ * join nor break.  Names are copied verbatim; the title lines are not written here.  All tables are host memory, staged on the
+ * stream, and may be dropped on return.
+ *
+ * The contract of dgrp_gff_text_batch: one check kernel before any byte is written; DGRP_EINVAL with d_text untouched for the BED
+ * entry's refusals (bases <= 0, figures outside what dgrp_row_scores_batch writes, a contig outside the names or outside
+ * 0..nrec-1), a label outside 1..ncnames, a row with start < 0, start >= end or end > h_rec_end of its record, records that do not
+ * ascend with the rows.  Refused on the host: h_rec_end[r] outside 1..2^62, id0 outside 0..2^62, join_gap < -1, ncnames < 1, a
+ * NULL or descending table, nrows >= 2^31 - 256.  *h_bytes (the text's length), *h_lines (the emitted lines) and *h_ids (the IDs
+ * they use) are always set on success; when the length exceeds cap nothing is written and the caller retries.  nrows == 0: no
+ * device work, all 0.  The chain: check -> emitted flag per row -> scan (the ordinals; the emitted row in front by a binary search
+ * over them) -> head-of-ID flag -> scan (the IDs) -> line length per row -> scan (the offsets) -> ONE synchronisation (totals and
+ * flags) -> write, one thread per emitted row.  Integers only, no atomics, nothing allocated.  Workspace
+ * dgrp_rmout_text_workspace_bytes (0 on refused arguments): 48 bytes per row, the tables and 8 bytes per entry of each. */
+int64_t dgrp_rmout_text_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t ncnames, int64_t cnames_bytes,
+                                        int64_t nrec);
+int dgrp_rmout_text_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const char *cnames,
+                          const int64_t *cname_off, int64_t ncnames, const dgrp_segment *d_rows, const dgrp_row_score *d_scores,
+                          int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end, int64_t join_gap, int64_t id0,
+                          char *d_text, int64_t cap, int64_t *h_bytes, int64_t *h_lines, int64_t *h_ids, void *d_work,
+                          int64_t work_bytes, void *stream);
+
 /* ---- bigBed (predict --bed_bigbed; deepgrp_amd/bigbed.py states the file format).  Both entries take the rows and scores of
  * dgrp_bed_text_batch, no names: the record of a row is its contig with by_contig, else 0 (then nrec must be 1); h_rec_end[r] (host,
  * nrec entries, staged on the stream, may be dropped on return) is the end coordinate of record r; a row is EMITTED when its score
