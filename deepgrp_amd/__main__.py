@@ -48,6 +48,10 @@ Differences, all additive:
     --boundaries, for rows that are already on disk -- a prediction TSV, a table `contig begin end number` or a RepeatMasker
     listing -- without a model: the files are parsed on the GPU and the rows flattened to one label per base first
     (deepgrp_amd/compare.py);
+  * PREDICTED of `compare` and the annotation of `evaluate` and `compare` may be GFF3 (`--predicted_format gff3`,
+    `--annotation_format gff3`, or a first line `##gff-version 3`), `predict --bed_gff3`'s own file included: parsed on the GPU, the
+    label of a feature looked up by name (`--predicted_names`, `--annotation_names`, `--gff_key`, `--gff_by_type`;
+    deepgrp_amd/gffin.py); `train` and `optimize` refuse it by name;
   * a FASTA file may be gzip-compressed (recognised by its magic bytes); BGZF files are inflated on the GPU (deepgrp_amd/gz.py);
   * a FASTA file may also be a UCSC .2bit file (recognised by its signature): its packed bases are unpacked on the GPU and every
     command gives what it gives for the FASTA text of the file (deepgrp_amd/twobit.py); one process, or --split_contigs;
@@ -209,6 +213,40 @@ class _Stages:
         return n
 
 
+def _gff_options(parser, sides) -> None:
+    """The flags of the format `gff3` (deepgrp_amd/gffin.py): the names of the labels per side, and where the label string stands."""
+    for side in sides:
+        parser.add_argument(f"--{side}_names", type=str, default=None, metavar="NAMES",
+                            help=f"with --{side}_format gff3: what the labels 1..C-1 are called in the file, one entry per label "
+                                 "separated by commas, an entry one or more alternatives joined by '|' (`LTR|ERV1|ERVK,LINE|L1,Alu,"
+                                 "Satellite`); default: class1,class2,... as `predict --bed_gff3` writes without --bed_names")
+    parser.add_argument("--gff_key", type=str, default=None, metavar="TAG",
+                        help="gff3: the attribute of column 9 whose value is the label's name; without this flag, Name")
+    parser.add_argument("--gff_by_type", action="store_true", help="gff3: the label's name is column 3, the type; excludes --gff_key")
+
+
+def _gff_plan(args, classes: int, sides):
+    """gffin.plan with the refusal as an exit: ({names flag: names}, key)."""
+    from . import gffin
+    try:
+        return gffin.plan(args, classes, sides)
+    except ValueError as e:
+        sys.exit(str(e))
+
+
+def _gff_resolved(args, flag: str, fmt_flag: str, resolved: str) -> None:
+    from . import gffin
+    try:
+        gffin.refuse_names(flag, getattr(args, flag.lstrip("-")) is not None, fmt_flag, resolved)
+    except ValueError as e:
+        sys.exit(str(e))
+
+
+def _refuse_gff3(command: str, path) -> str:
+    return (f"{command}: {path} is GFF3, which `evaluate` and `compare` read (--annotation_format gff3); the truth of {command} is the "
+            "table of parse_rm or a RepeatMasker listing")
+
+
 class CommandLineParser:
     """Commandline parser (deepgrp/__main__.py:86-250)."""
 
@@ -249,7 +287,7 @@ class CommandLineParser:
                            help="(addition) with a sequence file (FASTA, gzip, BGZF, .2bit) as trainfile: the records to train on, by "
                                 "the first word of their header, comma separated (default: every record, in file order)")
         train.add_argument("--valid_contigs", type=str, default=None, help="(addition) the same for validfile")
-        train.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+        train.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker", "gff3"), default="auto",
                            help="(addition) what bedfile is: `table` = the six columns parse_rm writes, `repeatmasker` = RepeatMasker's "
                                 "own listing (`.out`, `.out.gz`) or UCSC's rmsk table, parsed on the GPU (sequence files only); `auto` "
                                 "looks at the first lines")
@@ -263,7 +301,7 @@ class CommandLineParser:
         optimize.add_argument("trainfile", type=str)
         optimize.add_argument("validfile", type=str)
         optimize.add_argument("bedfile", type=str)
-        optimize.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+        optimize.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker", "gff3"), default="auto",
                               help="what bedfile is; only `table` (the six columns parse_rm writes) is read here: RepeatMasker "
                                    "output is refused by name")
         optimize.add_argument("--max_evals", type=int, default=20, help="trials to add to results.json")
@@ -311,9 +349,10 @@ class CommandLineParser:
         evaluate.add_argument("annotation", type=str, help="table as parse_rm writes it: contig, 0-based begin, exclusive end, "
                                                            "repeat number, further columns ignored; or RepeatMasker's own listing "
                                                            "(`.out`, UCSC rmsk; plain, gzip or BGZF), parsed on the GPU")
-        evaluate.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+        evaluate.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker", "gff3"), default="auto",
                               help="what the annotation is; `auto` looks at its first lines.  A RepeatMasker listing gives what the "
                                    "table parse_rm writes from it gives; it is read after the device is opened, the table before")
+        _gff_options(evaluate, ("annotation",))
         evaluate.add_argument("FASTA", nargs="+", type=str, help="inputs as for predict: FASTA files, '-', `<name>.gz.npz`; a "
                                                                  "record is matched to the annotation by the first word of its "
                                                                  "header (.npz: the file name up to the first '.')")
@@ -384,10 +423,12 @@ class CommandLineParser:
         compare.add_argument("--classes", type=int, default=5, help="classes of the labels, background included, 2..64")
         compare.add_argument("--repeats", type=class_list, default=None,
                              help="comma-separated repeat numbers to keep from the annotation (default: 1..classes-1)")
-        compare.add_argument("--predicted_format", choices=("auto", "tsv", "table", "repeatmasker"), default="auto",
-                             help="what PREDICTED is; `auto` looks at its first lines: tsv, then repeatmasker, else table")
-        compare.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker"), default="auto",
+        compare.add_argument("--predicted_format", choices=("auto", "tsv", "table", "repeatmasker", "gff3"), default="auto",
+                             help="what PREDICTED is; `auto` looks at its first lines: tsv, then gff3 (a first line that begins with "
+                                  "`##gff-version 3`), then repeatmasker, else table")
+        compare.add_argument("--annotation_format", choices=("auto", "table", "repeatmasker", "gff3"), default="auto",
                              help="what the annotation is; `auto` looks at its first lines")
+        _gff_options(compare, ("predicted", "annotation"))
         compare.add_argument("--min_overlap", type=float, default=0.5, help="as for evaluate, in (0, 1]")
         compare.add_argument("--output", type=str, default="-", help="TSV report ('-' = standard output)")
         compare.add_argument("--json", type=str, default=None, help="also write every figure as JSON here")
@@ -732,6 +773,13 @@ class CommandLineParser:
         from . import boundaries as dgboundaries, curves as dgcurves, offtarget as dgofftarget, strata as dgstrata
         # the reports that were asked for, in the order of their JSON keys; every plan refuses what it must before the model is read
         plans = [(m, p) for m in (dgcurves, dgstrata, dgofftarget, dgboundaries) for p in [m.plan(args)] if p is not None]
+        gff_sides = (("--annotation_names", "--annotation_format", args.annotation_format),)
+        _gff_plan(args, None, gff_sides)                         # (the number of entries waits for the model's class count)
+        from . import annotation as dgann
+        ann_format = None
+        if args.annotation_names is not None:                    # (only this refusal needs the file's first lines this early)
+            ann_format = dgann.resolve_format(args.annotation, args.annotation_format)
+            _gff_resolved(args, "--annotation_names", "--annotation_format", ann_format)
         import json
 
         from . import model as dgmodel
@@ -743,12 +791,17 @@ class CommandLineParser:
         bad = [r for r in repeats if not 0 < r < classes]
         if bad:
             sys.exit(f"--repeats: {bad[0]} is not a repeat class of this model (1..{classes - 1})")
-        from . import annotation as dgann
-        listed = dgann.resolve_format(args.annotation, args.annotation_format) == "repeatmasker"
+        if ann_format is None:
+            ann_format = dgann.resolve_format(args.annotation, args.annotation_format)
+        listed = ann_format == "repeatmasker"
+        gff_names, gff_key = _gff_plan(args, classes, gff_sides)
         try:
-            # a table is read here, before the device is touched; a RepeatMasker listing is parsed ON the device (the model's class
-            # check above still comes first)
-            if any(m is dgofftarget for m, _p in plans):
+            # a table is read here, before the device is touched; a RepeatMasker listing and a GFF3 file are parsed ON the device
+            # (the model's class check above still comes first)
+            if ann_format == "gff3":
+                from . import gffin
+                annotation = gffin.read_annotation(args.annotation, gff_names["--annotation_names"], gff_key, repeats)
+            elif any(m is dgofftarget for m, _p in plans):
                 annotation = dgann.evaluation_rows(args.annotation, repeats, offtarget=True)
             else:
                 annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else read_annotation(args.annotation, repeats)
@@ -803,6 +856,8 @@ class CommandLineParser:
         bad = [r for r in repeats if not 0 < r < classes]
         if bad:
             sys.exit(f"--repeats: {bad[0]} is not a repeat class of --classes {classes} (1..{classes - 1})")
+        gff_names, gff_key = _gff_plan(args, classes, (("--predicted_names", "--predicted_format", args.predicted_format),
+                                                       ("--annotation_names", "--annotation_format", args.annotation_format)))
         from . import boundaries as dgboundaries, offtarget as dgofftarget, strata as dgstrata
         plans = [(m, p) for m in (dgstrata, dgofftarget, dgboundaries) for p in [m.plan(args)] if p is not None]
         for _m, p in plans:
@@ -813,10 +868,17 @@ class CommandLineParser:
 
         from . import annotation as dgann
         from .evaluation import AnnotationError, NoMatchError, tsv_report
-        listed = dgann.resolve_format(args.annotation, args.annotation_format) == "repeatmasker"
+        ann_format = dgann.resolve_format(args.annotation, args.annotation_format)
+        listed = ann_format == "repeatmasker"
+        _gff_resolved(args, "--annotation_names", "--annotation_format", ann_format)
+        _gff_resolved(args, "--predicted_names", "--predicted_format", dgcompare.resolve_predicted_format(args.predicted, args.predicted_format))
         try:
-            predicted = dgcompare.read_predicted(args.predicted, args.predicted_format, classes)
-            if any(m is dgofftarget for m, _p in plans):
+            predicted = dgcompare.read_predicted(args.predicted, args.predicted_format, classes, gff_names=gff_names["--predicted_names"],
+                                                 gff_key=gff_key)
+            if ann_format == "gff3":
+                from . import gffin
+                annotation = gffin.read_annotation(args.annotation, gff_names["--annotation_names"], gff_key, repeats)
+            elif any(m is dgofftarget for m, _p in plans):
                 annotation = dgann.evaluation_rows(args.annotation, repeats, offtarget=True)
             else:
                 annotation = dgann.evaluation_rows(args.annotation, repeats) if listed else dgcompare.read_table(args.annotation, repeats)
@@ -909,7 +971,10 @@ class CommandLineParser:
                  ("validfile", args.validfile, "--valid_contigs", args.valid_contigs))
         npz = [dgtrain.is_npz(path) for _role, path, _flag, _contigs in sides]
         from . import annotation as dgann
-        listed = dgann.resolve_format(args.bedfile, args.annotation_format) == "repeatmasker"
+        bed_format = dgann.resolve_format(args.bedfile, args.annotation_format)
+        if bed_format == "gff3":
+            sys.exit(_refuse_gff3("train", args.bedfile))
+        listed = bed_format == "repeatmasker"
         if npz[0] != npz[1]:
             kinds = ["a .npz of preprocess_sequence" if z else "a sequence file" for z in npz]
             sys.exit(f"train: {sides[0][0]} {sides[0][1]} is {kinds[0]} and {sides[1][0]} {sides[1][1]} is {kinds[1]}: "
@@ -985,7 +1050,10 @@ class CommandLineParser:
         if args.max_evals < 1:
             sys.exit(f"optimize: --max_evals {args.max_evals}: at least one trial")
         from . import annotation as dgann
-        if dgann.resolve_format(args.bedfile, args.annotation_format) == "repeatmasker":
+        bed_format = dgann.resolve_format(args.bedfile, args.annotation_format)
+        if bed_format == "gff3":
+            sys.exit(_refuse_gff3("optimize", args.bedfile))
+        if bed_format == "repeatmasker":
             sys.exit(dgann.refuse_npz("optimize", args.bedfile))
         with open(args.space, "rb") as file:
             try:

@@ -178,6 +178,8 @@ _SIGNATURES = {
     "dgrp_rm_parse_all": (cint, [vp, i64, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
     "dgrp_rows_parse_workspace_bytes": (i64, [i64]),
     "dgrp_rows_parse": (cint, [vp, i64, cint, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+    "dgrp_gff_parse_workspace_bytes": (i64, [i64]),
+    "dgrp_gff_parse": (cint, [vp, i64, vp, vp, vp, cint, vp, cint, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
     "dgrp_token_ids_workspace_bytes": (i64, [i64, i64]),
     "dgrp_token_ids": (cint, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
     "dgrp_paint_keys_batch": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]),

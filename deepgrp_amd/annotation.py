@@ -32,7 +32,7 @@ TILE_BYTES = 32768                       # DGRP_RM_TILE_BYTES: text per workgrou
 MIN_LINE_BYTES = 22                      # the shortest line that matches: n // 22 + 1 rows always suffice
 SNIFF_BYTES = 64 << 10
 SNIFF_LINES = 16
-FORMATS = ("auto", "table", "repeatmasker")
+FORMATS = ("auto", "table", "repeatmasker", "gff3")
 _BASES = {"A": 0, "C": 1, "G": 2, "T": 3}
 
 
@@ -74,9 +74,12 @@ def _head(path) -> bytes:
 
 
 def sniff(path) -> str:
-    """"repeatmasker" when one of the first 16 lines of `path` that are not blank and do not open with '#' matches a pattern of
-    parse_rm, else "table"; decided on the first 64 KiB (inflated with zlib when the magic bytes say gzip)."""
+    """"gff3" when the first line begins with `##gff-version 3` (gffin.py); else "repeatmasker" when one of the first 16 lines of
+    `path` that are not blank and do not open with '#' matches a pattern of parse_rm, else "table"; decided on the first 64 KiB
+    (inflated with zlib when the magic bytes say gzip)."""
     head = _head(path)
+    if head.startswith(b"##gff-version 3"):
+        return "gff3"
     lines = head.decode("utf-8", "replace").splitlines()
     if len(head) >= SNIFF_BYTES and lines:
         lines.pop()                                                  # (cut somewhere)
@@ -482,6 +485,8 @@ def read_rows(path, fmt: str = "auto", device: bool = True) -> Rows:
     listing exactly what evaluation.read_annotation(table, None) returns for the table parse_rm writes from it, with `.lines` =
     {contig: the listing's line of every row}; for a table read_annotation itself (`.lines` None)."""
     fmt = resolve_format(path, fmt)
+    if fmt == "gff3":
+        raise ValueError(f"{path}: GFF3 is read with names for its labels: gffin.read_annotation")
     if fmt == "table":
         from .evaluation import read_annotation
         return Rows(read_annotation(path, None))

@@ -2,13 +2,15 @@
 another tool as a table `contig begin end number`, or a RepeatMasker listing -- against an annotation.  No model is loaded and no
 forward pass runs: the inputs are read only for their records, their names and the evaluated span of each.
 
-PREDICTED, three forms (sniffed on the first 64 KiB: `tsv`, then `repeatmasker`, else `table`):
+PREDICTED, four forms (sniffed on the first 64 KiB: `tsv`, then `gff3` where the first line begins with `##gff-version 3`, then
+`repeatmasker`, else `table`):
     tsv           fields between tabs: the first is the file, the last three are start, end and label, what lies between is the
                   header and may hold tabs.  The record a row belongs to is evaluation.record_name's rule on (file, header) without
                   the `isfile` test (`tsv_name`).  An empty line is skipped; fewer than five fields are an AnnotationError.  A label
                   outside 1..C-1 is an AnnotationError naming file and line; one name under two file fields is refused.
     table         evaluation.read_annotation's grammar; a row whose number is outside 1..C-1 is dropped and counted.
     repeatmasker  annotation.read_listing; likewise.
+    gff3          gffin.py: feature lines, the label looked up by name (--predicted_names, --gff_key, --gff_by_type); likewise.
 `tsv` and `table` are parsed on the device (dgrp_rows_parse, csrc/rows_parse_kernels.hip).  What the device does not
 decide -- a byte outside 0x20..0x7e other than tab and line feed, a carriage return that no line feed follows, a number that is not
 1..18 plain digits -- goes to the host whole: `read_annotation` itself for a table, `tsv_flat_host` below for a TSV, which is also
@@ -29,7 +31,7 @@ import numpy as np
 
 from . import annotation as dgann
 
-PREDICTED_FORMATS = ("auto", "tsv", "table", "repeatmasker")
+PREDICTED_FORMATS = ("auto", "tsv", "table", "repeatmasker", "gff3")
 ANNOTATION_FORMATS = dgann.FORMATS
 MIN_CLASSES, MAX_CLASSES, DEFAULT_CLASSES = 2, 64, 5
 MIN_ROW_BYTES = 8                        # the shortest line dgrp_rows_parse keeps: n // 8 + 1 rows always suffice
@@ -316,12 +318,17 @@ def _tsv_rows(path, flat: Flat, classes: int):
     return _grouped(path, flat, np.ones(flat.begin.size, bool))
 
 
-def read_predicted(path, fmt: str = "auto", classes: int = DEFAULT_CLASSES, device: bool = True) -> Predicted:
+def read_predicted(path, fmt: str = "auto", classes: int = DEFAULT_CLASSES, device: bool = True, gff_names=None,
+                   gff_key: Optional[bytes] = b"Name") -> Predicted:
     """The predicted rows of `path` as {record name: SEGMENT_DTYPE rows}, label = class, file order within a name (module
-    docstring).  device False: the host paths."""
+    docstring).  device False: the host paths.  gff_names (gffin.parse_names; None: class1..), gff_key (None: the type column):
+    how the rows of a `gff3` file get their numbers."""
     from .evaluation import read_annotation
     classes = _check_classes(classes)
     fmt = resolve_predicted_format(path, fmt)
+    if fmt == "gff3":
+        from . import gffin
+        return gffin.read_predicted(path, gffin.default_names(classes) if gff_names is None else gff_names, gff_key, classes, device)
     if fmt == "repeatmasker":
         listing = dgann.read_listing(path, device)
         read = listing.table_mask()

@@ -57,8 +57,10 @@ def plan(args) -> Optional[OfftargetPlan]:
                         "the counts are summed on the rank that holds the predicted rows")
     from . import annotation
     ann = getattr(args, "annotation", None)
-    if ann is not None and annotation.resolve_format(ann, getattr(args, "annotation_format", "auto")) == "table":
-        sys.exit(f"--offtarget: {ann} is read as a table of parse_rm, which holds the rows of the modelled classes only; what the other "
+    fmt = annotation.resolve_format(ann, getattr(args, "annotation_format", "auto")) if ann is not None else None
+    if fmt in ("table", "gff3"):
+        how = "a table of parse_rm" if fmt == "table" else "GFF3 numbered by name, like a table of parse_rm"
+        sys.exit(f"--offtarget: {ann} is read as {how}, which holds the rows of the modelled classes only; what the other "
                  "predicted bases lie on is in the RepeatMasker listing itself: give `genome.fa.out`, `genome.fa.out.gz` or a UCSC "
                  "`rmsk.txt.gz`")
     return OfftargetPlan(prefix, by, *paths)

@@ -1174,6 +1174,49 @@ int dgrp_rows_parse(const uint8_t *d_text, int64_t n, int format, int64_t *d_beg
                     int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_file_pos, int32_t *d_file_len, int64_t *d_line,
                     int64_t *d_run_first, int64_t cap, int64_t *h_counts, void *d_work, int64_t work_bytes, void *stream);
 
+/* ---- GFF3 read on the device (an addition, `compare` and `evaluate` with the format `gff3`).  THE GRAMMAR, stated
+ * here once:
+ * TEXT, LINES, END OF FEATURES.  The text is d_text[0..n), any alignment.  Lines end at LF; a CR directly before the LF belongs to
+ * the line end.  E is the offset of the first line that is exactly `##FASTA` or that starts with '>', n where there is none: no byte
+ * at or after E is read as a line (or raises the flag below), and E is reported.  An empty line is skipped; so is a line whose first
+ * byte is '#'.
+ * FIELDS.  Any other line is a feature line: fields between single tabs.  Fewer than nine fields make it MALFORMED (reason 3); the
+ * ninth field runs to the line end, further tabs included.  Field 1 is the seqid: its span is the row's name, bytes as they stand
+ * (not decoded here).  Fields 4 and 5 are start and end, each 1..18 plain decimal digits, 1-based and closed: begin = start - 1,
+ * end = end, so start 0 gives begin -1, which the caller reports as a negative begin.
+ * THE LABEL STRING.  key_len == 0: field 3, the type.  Otherwise field 9 is cut at every ';', a piece at its first '=' into tag and
+ * value (a piece without '=' has no tag), and the first piece whose tag is byte-equal to d_key[0..key_len) gives the value; nothing
+ * is trimmed or split at commas, and a key that is a proper prefix of a tag (`Name` against `Names=`) does not match.  The string
+ * is compared DECODED: '%' followed by two hex digits of either case, both inside the string, stands for that byte; any other '%'
+ * is itself.  Decoding happens during the comparison; nothing is written back.
+ * THE NUMBER (int64).  d_names / d_name_off [nnames + 1] / d_name_number [nnames] (device): nnames alternatives
+ * d_names[d_name_off[k] .. d_name_off[k + 1]) in ASCENDING byte order (memcmp, a proper prefix first; distinct), found by binary
+ * search -- the rule is exact equality with the decoded label string.  The row's number is d_name_number[k] of that alternative; 0
+ * where none is equal, where no piece has the key, and for an empty table.  A table that is not in that order gives numbers that
+ * are not specified; the search stays inside it.
+ * Rows, counts and runs are dgrp_rows_parse's for a table (no file spans): d_begin, d_end, d_number, d_name_pos / d_name_len,
+ * d_line (from 1), d_run_first.  h_counts[7] (host): the lines in front of E, rows, runs, the not-decided flag, the line of the
+ * first malformed line or 0, its reason, E.
+ * NOT DECIDED (in front of E): a byte outside 0x20..0x7e other than tab and LF, a CR not directly before a LF, a start or end that
+ * is not 1..18 plain digits.  Then h_counts[3] = 1, no row is written, DGRP_OK: the caller parses the file on the host.  MALFORMED
+ * in a file that is decided: h_counts[4] and [5] state the first such line, no row is written, DGRP_OK.  More rows than `cap`:
+ * DGRP_ENOMEM, h_counts[1] = the capacity needed, no row written.  The shortest feature line has 11 bytes (eight tabs, one digit
+ * each for start and end, the LF), so n / 11 + 1 rows always suffice, and the at most 128 / 11 + 1 = 12 rows that start in a
+ * lane's 128 bytes fit the uint8 the count pass keeps per lane.  n = 0: zero counts.  Refused before any launch with DGRP_EINVAL:
+ * NULL text with n > 0, n < 0, nnames outside 0..4096, a NULL table pointer with nnames > 0, key_len outside 0..255, a NULL key with
+ * key_len > 0, a NULL output with cap > 0, NULL counts, a workspace that is NULL or not 256-byte aligned; with DGRP_ENOMEM: a
+ * workspace below dgrp_gff_parse_workspace_bytes(n).
+ * The work split is dgrp_rows_parse's, with one kernel in front: a 64-bit atomicMin over the line starts that end the features
+ * leaves E in the workspace; the count and write passes read it THERE (kernels of one stream are ordered, so no synchronisation is
+ * spent on it) and walk d_text[0..E), which ends in a line feed.  Integers and bytes only; the only atomics are the OR of the flag
+ * and the two minima: the same call gives the same bytes.  On the caller's stream; it SYNCHRONISES that stream twice (counts and
+ * E, then runs; once where no row is written) and allocates nothing. */
+int64_t dgrp_gff_parse_workspace_bytes(int64_t n);
+int dgrp_gff_parse(const uint8_t *d_text, int64_t n, const uint8_t *d_names, const int64_t *d_name_off, const int32_t *d_name_number,
+                   int nnames, const uint8_t *d_key, int key_len, int64_t *d_begin, int64_t *d_end, int64_t *d_number,
+                   int64_t *d_name_pos, int32_t *d_name_len, int64_t *d_line, int64_t *d_run_first, int64_t cap, int64_t *h_counts,
+                   void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- off-target (an addition, evaluate --offtarget): what the predicted repeats lie on.
  * dgrp_token_ids: dense ids for `rows` tokens given as spans of d_text [n] (device).  Token i is the bytes d_pos[i] .. + d_len[i],
  * and with d_len2[i] > 0 the logical string of those bytes, '/', and the bytes d_pos2[i] .. + d_len2[i]; a one-span and a two-span
