@@ -453,7 +453,7 @@ class CommandLineParser:
             takes_value = {"--batch_size", "-b", "--step_size", "-s", "--xdrop_length", "-x", "--min_mss_length", "-l",
                            "--threads", "-t", "--mask_dir", "--mask", "--mask_classes", "--track_dir", "--track_classes",
                            "--track_digits", "--track_bin", "--gzip_level", "--bed_dir", "--bed_min_score", "--bed_names",
-                           "--rmout_repeats", "--rmout_join",
+                           "--rmout_repeats", "--rmout_join", "--index_format",
                            "--seq_dir", "--seq_classes", "--seq_flank", "--seq_width", "--summary_dir", "--summary_bin"}
             i = 0
             while i < len(argv):

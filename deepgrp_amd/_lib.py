@@ -69,6 +69,8 @@ _SIGNATURES = {
     "dgrp_track_text_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp]),
     "dgrp_track_index_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64]),
     "dgrp_track_index_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, vp, i64, vp, vp, i64, vp, i64, vp]),
+    "dgrp_track_csi_workspace_bytes": (i64, [i64, vp, vp, i64, cint, i64, cint]),
+    "dgrp_track_csi_batch": (cint, [vp, cint, i64, vp, vp, vp, C.c_char_p, vp, vp, cint, cint, i64, cint, vp, i64, vp, vp, i64, vp, i64, vp]),
     "dgrp_track_sections_workspace_bytes": (i64, [i64, vp, vp, i64, cint]),
     "dgrp_track_sections_batch": (cint, [vp, cint, i64, vp, vp, vp, vp, cint, cint, i64, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp]),
     "dgrp_track_zoom_workspace_bytes": (i64, [i64, vp, vp, i64, cint]),
@@ -129,12 +131,17 @@ _SIGNATURES = {
     "dgrp_bed_text_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, vp, i64, C.POINTER(i64), vp, i64, vp]),
     "dgrp_bed_index_workspace_bytes": (i64, [i64, i64, i64, i64]),
     "dgrp_bed_index_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, i64, vp, vp, i64, C.POINTER(i64), vp, i64, vp, vp, i64, vp]),
+    "dgrp_bed_csi_workspace_bytes": (i64, [i64, i64, i64, i64, cint]),
+    "dgrp_bed_csi_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, cint, i64, vp, cint, vp, i64, C.POINTER(i64), vp, i64, vp, vp, i64, vp]),
     "dgrp_gff_text_workspace_bytes": (i64, [i64, i64, i64, i64, i64]),
     "dgrp_gff_text_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), vp, i64,
                                    vp]),
     "dgrp_gff_index_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64]),
     "dgrp_gff_index_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, i64, vp, vp, i64, C.POINTER(i64), vp, i64, vp, vp,
                                     i64, vp]),
+    "dgrp_gff_csi_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64, cint]),
+    "dgrp_gff_csi_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, i64, vp, cint, vp, i64, C.POINTER(i64), vp, i64, vp,
+                                  vp, i64, vp]),
     "dgrp_rmout_text_workspace_bytes": (i64, [i64, i64, i64, i64, i64, i64]),
     "dgrp_rmout_text_batch": (cint, [vp, vp, i64, cint, vp, vp, i64, vp, vp, i64, cint, i64, vp, i64, i64, vp, i64, C.POINTER(i64),
                                      C.POINTER(i64), C.POINTER(i64), vp, i64, vp]),

@@ -67,6 +67,7 @@ class BedPlan(NamedTuple):
     rmout_repeats: Optional[tuple] = None           # --rmout_repeats: the repeat number of label 1..C-1 (None: 1..C-1)
     rmout_join: int = -1                            # --rmout_join: the largest gap inside one ID (-1: every line its own)
     rmout_pairs: Optional[tuple] = None             # (repeat, class/family) of label 1..C-1, once the class count is known (from_plan)
+    index_format: str = "tbi"                       # --index_format: "csi" for <file>.gz.csi (tabix.CSI_DEPTH levels, up to 2^32)
 
     @property
     def on_device(self) -> bool:
@@ -244,7 +245,9 @@ def plan(args) -> Optional[BedPlan]:
     if gzip or bigbed:
         from .tracks import gzip_level
         level = gzip_level(args, 1)
-    return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames, rmout, repeats, -1 if join is None else int(join))
+    from .tracks import index_format
+    return BedPlan(bdir, int(low), paths, level, index, bigbed, gff3, cnames, rmout, repeats, -1 if join is None else int(join),
+                   index_format=index_format(args))
 
 
 def from_plan(p: BedPlan, classes: int) -> "Bed":
@@ -307,7 +310,8 @@ class _BigBedFile(StagedFile):
 
 class BedFiles(StagedOutputs):
     """The BED file of one input: a temporary file next to it, renamed by `commit`, removed by `abort` (outfiles.py).  With
-    p.gzip_level `write` takes a BedWrite (BGZF members, to an outfiles.BgzfSink, which with p.index builds `<file>.tbi`).  An
+    p.gzip_level `write` takes a BedWrite (BGZF members, to an outfiles.BgzfSink, which with p.index builds `<file>.tbi`; with
+    p.index_format "csi" it builds `<file>.csi` instead, and the limit below is 2^32).  An
     input that cannot be indexed (a record that ends above 2^29, an empty name, a name that comes back: name_order) gets one
     warning and no index: the `.bed.gz` is what it is without the flag, and a `.tbi` an earlier run left is removed.  With
     p.bigbed the file is a `.bb` with a bigbed.BigBedBuilder on its temporary file and `write` takes a bigbed.BigBedWrite; an
@@ -332,7 +336,7 @@ class BedFiles(StagedOutputs):
             from . import gff
             preset = (gff.PRESET,)
         super().__init__(_LOG, filename, "--bed_index", self.gzip and p.index,
-                         [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index, *preset) if self.gzip
+                         [_BigBedFile(self.final) if self.bigbed else BgzfSink(self.final, p.index, *preset, fmt=p.index_format) if self.gzip
                           else StagedFile(self.final)])
         if self.gff3 or self.rmout:
             try:
@@ -542,15 +546,16 @@ def reference_lines(names: Sequence, by_contig: bool, rows, scores, min_score: i
     return b"".join(out)
 
 
-def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_score: int, rec_end: Sequence[int]):
+def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_score: int, rec_end: Sequence[int], depth: int = 5):
     """What dgrp_bed_index_batch states about the text `reference_lines` gives for the same arguments, in Python integers:
     -> (chunks tabix.CHUNK_DTYPE, linear int64 [windows of all records], wpref int64 [records + 1], last_end int64 [records]).
     A chunk is a maximal run of consecutive emitted lines of one record with one bin; linear[wpref[r] + w] is the text offset of
     the first emitted line of record r, in file order, whose end is greater than w << 14 (the running maximum of the ends), or
-    -1; last_end[r] the end of the record's last emitted line, 0 without one."""
-    from .tabix import CHUNK_DTYPE, MIN_SHIFT, reg2bin, window_prefix
+    -1; last_end[r] the end of the record's last emitted line, 0 without one.  With another depth: what dgrp_bed_csi_batch
+    states, the bins those of tabix.csi_reg2bin at that depth."""
+    from .tabix import CHUNK_DTYPE, MIN_SHIFT, csi_reg2bin, window_prefix
     nrec = len(rec_end)
-    wpref = window_prefix(rec_end)
+    wpref = window_prefix(rec_end, depth)
     linear = np.full(int(wpref[-1]), -1, np.int64)
     filled = [0] * nrec
     last_end = np.zeros(nrec, np.int64)
@@ -561,7 +566,7 @@ def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_sc
             continue
         r = int(rows[k]["contig"]) if by_contig else 0
         start, end = int(rows[k]["start"]), int(rows[k]["end"])
-        b = reg2bin(start, end)
+        b = csi_reg2bin(start, end, depth)
         if chunks and chunks[-1][2] == r and chunks[-1][3] == b:
             chunks[-1][1] = u + len(line)
         else:

@@ -227,13 +227,13 @@ __global__ void __launch_bounds__(256) gff_write_kernel(bed_in A, gff_in G, cons
 struct bed_lines {                 // the emitted lines, compacted: m = *count of them
     const uint64_t *count;
     int64_t *beg, *end;            // text offsets: the line's first byte, the byte behind it
-    uint64_t *key;                 // record << 32 | the row's end
+    uint64_t *key;                 // record << 32 | the row's end - 1 (the end itself reaches 2^32 under a CSI index of depth 6)
     uint32_t *bin;
 };
 
 // One thread per row: an emitted row becomes line eidx[i].
 __global__ void __launch_bounds__(256) bed_compact_kernel(bed_in A, const uint64_t *__restrict__ len, const uint64_t *__restrict__ off,
-                                                          const uint64_t *__restrict__ eidx, bed_lines Ln)
+                                                          const uint64_t *__restrict__ eidx, bed_lines Ln, int depth)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= A.nrows || len[i] == 0) return;
@@ -241,8 +241,8 @@ __global__ void __launch_bounds__(256) bed_compact_kernel(bed_in A, const uint64
     const uint64_t j = eidx[i];
     Ln.beg[j] = (int64_t)off[i];
     Ln.end[j] = (int64_t)(off[i] + len[i]);
-    Ln.key[j] = (uint64_t)(uint32_t)(A.by_contig ? row.contig : 0) << 32 | (uint64_t)(row.end & 0xffffffffll);
-    Ln.bin[j] = tabix_reg2bin(row.start, row.end);
+    Ln.key[j] = (uint64_t)(uint32_t)(A.by_contig ? row.contig : 0) << 32 | (uint64_t)((row.end - 1) & 0xffffffffll);
+    Ln.bin[j] = tabix_reg2bin_depth(row.start, row.end, depth);
 }
 
 // One thread per slot: 1 where line j opens a chunk (the first line, another record, another bin), 0 elsewhere and behind the lines.
@@ -353,11 +353,11 @@ __global__ void __launch_bounds__(256) bed_linear_kernel(bed_lines Ln, const uin
     const int64_t lo = dgrp_record_of(wpref, nrec, g);
     const uint64_t r = (uint64_t)lo, w = (uint64_t)(g - wpref[lo]);
     const int64_t m = (int64_t)*Ln.count;
-    const int64_t j = lower_bound_u64(runmax, m, r << 32 | ((w << 14) + 1));
+    const int64_t j = lower_bound_u64(runmax, m, r << 32 | w << 14);             // end > w << 14: end - 1 >= w << 14, w < 2^18
     linear[g] = j < m && runmax[j] >> 32 == r ? Ln.beg[j] : -1;
     if (w == 0 && rec_last) {
         const int64_t e = lower_bound_u64(runmax, m, (r + 1) << 32);
-        rec_last[r] = e > 0 && Ln.key[e - 1] >> 32 == r ? (int64_t)(Ln.key[e - 1] & 0xffffffffull) : 0;
+        rec_last[r] = e > 0 && Ln.key[e - 1] >> 32 == r ? (int64_t)(Ln.key[e - 1] & 0xffffffffull) + 1 : 0;
     }
 }
 
@@ -537,11 +537,13 @@ static int text_entry(const char *who, const char *names, const int64_t *name_of
 }
 
 // The index entry of both formats (H == nullptr: BED): behind the front everything works from the lengths and offsets of the lines.
-static int index_entry(const char *who, const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+// depth: the levels below the root of the binning scheme (5: a .tbi; csi: the entry takes 5 or 6 and names the limit of a CSI index).
+static int index_entry(const char *who, int depth, bool csi, const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
                        const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end,
                        dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
                        int64_t *d_rec_last, void *d_work, int64_t work_bytes, hipStream_t stream, const gff_host *H)
 {
+    DGRP_REQUIRE(depth == TABIX_DEPTH || depth == CSI_DEPTH, "%s: depth must be 5 or 6, got %d", who, depth);
     DGRP_REQUIRE(h_nchunks && nrows >= 0 && chunk_cap >= 0 && linear_cap >= 0, "%s: bad arguments", who);
     const int rc = bed_check_names(who, names, name_off, nnames);
     if (rc != DGRP_OK) return rc;
@@ -553,9 +555,15 @@ static int index_entry(const char *who, const char *names, const int64_t *name_o
     DGRP_REQUIRE(by_contig || nrec == 1, "%s: without by_contig every row belongs to record 0, so nrec must be 1, not %lld", who, (long long)nrec);
     std::vector<int64_t> wpref((size_t)nrec + 1, 0);
     for (int64_t r = 0; r < nrec; ++r) {
-        DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= TABIX_MAX_END,
-                     "%s: record %lld ends at %lld, outside 1..2^29 (the largest coordinate of a tabix index)", who, (long long)r,
-                     (long long)h_rec_end[r]);
+        if (csi) {
+            DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= tabix_max_end(depth),
+                         "%s: record %lld ends at %lld, outside 1..2^%d = %lld (the largest coordinate of a CSI index of depth %d)", who,
+                         (long long)r, (long long)h_rec_end[r], TABIX_MIN_SHIFT + 3 * depth, (long long)tabix_max_end(depth), depth);
+        } else {
+            DGRP_REQUIRE(h_rec_end[r] >= 1 && h_rec_end[r] <= TABIX_MAX_END,
+                         "%s: record %lld ends at %lld, outside 1..2^29 (the largest coordinate of a tabix index)", who, (long long)r,
+                         (long long)h_rec_end[r]);
+        }
         wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_rec_end[r] - 1) >> 14) + 1;
     }
     const int64_t W = wpref[(size_t)nrec];
@@ -592,7 +600,7 @@ static int index_entry(const char *who, const char *names, const int64_t *name_o
         rc2 = device_exclusive_scan((const uint64_t *)(w + l.emit), eidx, nrows, tiles, &d_head->lines, stream);
         if (rc2 != DGRP_OK) return rc2;
     }
-    hipLaunchKernelGGL(bed_compact_kernel, grid, block, 0, stream, A, len, off, (const uint64_t *)eidx, Ln);
+    hipLaunchKernelGGL(bed_compact_kernel, grid, block, 0, stream, A, len, off, (const uint64_t *)eidx, Ln, depth);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(bed_opens_kernel, grid, block, 0, stream, Ln, nrows, opens);
     DGRP_LAUNCH_CHECK();
@@ -648,7 +656,7 @@ DGRP_EXPORT int dgrp_bed_index_batch(const char *names, const int64_t *name_off,
                                      dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear,
                                      int64_t linear_cap, int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream_)
 {
-    return index_entry("dgrp_bed_index_batch", names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec, h_rec_end,
+    return index_entry("dgrp_bed_index_batch", TABIX_DEPTH, false, names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec, h_rec_end,
                        d_chunks, chunk_cap, h_nchunks, d_linear, linear_cap, d_rec_last, d_work, work_bytes, (hipStream_t)stream_, nullptr);
 }
 
@@ -682,6 +690,42 @@ DGRP_EXPORT int dgrp_gff_index_batch(const char *names, const int64_t *name_off,
                                      int64_t linear_cap, int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream_)
 {
     const gff_host H = {cnames, cname_off, ncnames, id0};
-    return index_entry("dgrp_gff_index_batch", names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec, h_rec_end,
+    return index_entry("dgrp_gff_index_batch", TABIX_DEPTH, false, names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec, h_rec_end,
                        d_chunks, chunk_cap, h_nchunks, d_linear, linear_cap, d_rec_last, d_work, work_bytes, (hipStream_t)stream_, &H);
+}
+
+// ---- CSI (predict --index_format csi): the index entries with the depth of the binning scheme as an argument; the workspace is the
+// .tbi entries' (the depth changes bin numbers and the record-end limit, no layout)
+DGRP_EXPORT int64_t dgrp_bed_csi_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t nrec, int depth)
+{
+    return depth == TABIX_DEPTH || depth == CSI_DEPTH ? dgrp_bed_index_workspace_bytes(nrows, nnames, names_bytes, nrec) : 0;
+}
+
+DGRP_EXPORT int dgrp_bed_csi_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                                   const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end,
+                                   int depth, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear,
+                                   int64_t linear_cap, int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream_)
+{
+    return index_entry("dgrp_bed_csi_batch", depth, true, names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec,
+                       h_rec_end, d_chunks, chunk_cap, h_nchunks, d_linear, linear_cap, d_rec_last, d_work, work_bytes, (hipStream_t)stream_,
+                       nullptr);
+}
+
+DGRP_EXPORT int64_t dgrp_gff_csi_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t ncnames, int64_t cnames_bytes,
+                                                 int64_t nrec, int depth)
+{
+    return depth == TABIX_DEPTH || depth == CSI_DEPTH ? dgrp_gff_index_workspace_bytes(nrows, nnames, names_bytes, ncnames, cnames_bytes, nrec)
+                                                      : 0;
+}
+
+DGRP_EXPORT int dgrp_gff_csi_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const char *cnames,
+                                   const int64_t *cname_off, int64_t ncnames, const dgrp_segment *d_rows, const dgrp_row_score *d_scores,
+                                   int64_t nrows, int min_score, int64_t id0, int64_t nrec, const int64_t *h_rec_end, int depth,
+                                   dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear,
+                                   int64_t linear_cap, int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream_)
+{
+    const gff_host H = {cnames, cname_off, ncnames, id0};
+    return index_entry("dgrp_gff_csi_batch", depth, true, names, name_off, nnames, by_contig, d_rows, d_scores, nrows, min_score, nrec,
+                       h_rec_end, d_chunks, chunk_cap, h_nchunks, d_linear, linear_cap, d_rec_last, d_work, work_bytes, (hipStream_t)stream_,
+                       &H);
 }

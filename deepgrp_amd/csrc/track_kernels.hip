@@ -474,7 +474,7 @@ __global__ void __launch_bounds__(256) ix_tile_kernel(const uint32_t *__restrict
                                                       int64_t W, const uint64_t *__restrict__ tileoff, const uint64_t *__restrict__ bounds,
                                                       ix_state *__restrict__ tilestate, uint64_t *__restrict__ tilechunks,
                                                       const uint64_t *__restrict__ cbounds, dgrp_track_chunk *__restrict__ chunks,
-                                                      int64_t *__restrict__ linear)
+                                                      int64_t *__restrict__ linear, int depth)
 {
     __shared__ uint64_t lds[4];
     __shared__ ix_state slds[4];
@@ -516,13 +516,13 @@ __global__ void __launch_bounds__(256) ix_tile_kernel(const uint32_t *__restrict
             const int64_t p0 = pref[rr], end = t.p.hi;
             int64_t start, pstart, pend = 0, x;
             track_bin_span(g, s.F.a - p0, start, x);                       // the line's first bin
-            bn = tabix_reg2bin(start, end);
+            bn = tabix_reg2bin_depth(start, end, depth);
             const bool prev = s.L.b >= p0;                                 // the previous `last` bin lies in this record
             cs = true;
             if (prev) {
                 track_bin_span(g, s.F.b - p0, pstart, x);
                 track_bin_span(g, s.L.b - p0, x, pend);
-                cs = tabix_reg2bin(pstart, pend) != bn;
+                cs = tabix_reg2bin_depth(pstart, pend, depth) != bn;
             }
             if (MODE == 2) {
                 const int64_t len = R.name_len + track_decimal_width((uint64_t)start) + track_decimal_width((uint64_t)end) + G.digits + 6;
@@ -598,11 +598,12 @@ __global__ void __launch_bounds__(128) ix_ends_kernel(const uint64_t *__restrict
 struct ix_layout { tb_layout t; int64_t wpref, state, tilechunks, cgrand, cbounds, bytes; };
 
 static bool ix_carve(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls, int64_t names_bytes,
-                     ix_layout *l)
+                     int depth, ix_layout *l)
 {
+    if (depth != TABIX_DEPTH && depth != CSI_DEPTH) return false;
     if (!tb_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l->t) || nrec >= (1ll << 31)) return false;
     for (int64_t r = 0; r < nrec; ++r)
-        if (h_startpos[r] + h_n[r] > TABIX_MAX_END) return false;
+        if (h_startpos[r] + h_n[r] > tabix_max_end(depth)) return false;
     const int64_t ntiles = l->t.NBpad / TRACK_TILE * ncls;
     int64_t p = l->t.bytes;
     l->wpref = p;
@@ -716,56 +717,58 @@ DGRP_EXPORT int dgrp_track_text_batch(const float *d_probs, int C, int64_t nrec,
                   l, (hipStream_t)stream_);
 }
 
-DGRP_EXPORT int64_t dgrp_track_index_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
-                                                     int64_t names_bytes)
+// The index entry at `depth` levels below the root (5: the .tbi entry `who` = dgrp_track_index_batch, whose texts these are; 5 or 6:
+// dgrp_track_csi_batch).  Only the bin numbers and the record-end limit depend on the depth.
+static int ix_entry(const char *who, int depth, const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                    const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls, int ncls, int digits,
+                    int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_chunk_off, int64_t *d_linear,
+                    int64_t linear_cap, void *d_work, int64_t work_bytes, void *stream_, bool csi)
 {
-    ix_layout l;
-    return ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l) ? l.bytes : 0;
-}
-
-DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
-                                       const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls,
-                                       int ncls, int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap,
-                                       int64_t *h_chunk_off, int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes,
-                                       void *stream_)
-{
-    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC, "dgrp_track_index_batch: bad C %d", C);
-    DGRP_REQUIRE(ncls >= 1 && ncls <= C, "dgrp_track_index_batch: ncls must lie in 1..C (%d, C = %d)", ncls, C);
-    DGRP_REQUIRE(h_chunk_off && h_cls, "dgrp_track_index_batch: NULL h_chunk_off or h_cls");
+    DGRP_REQUIRE(depth == TABIX_DEPTH || depth == CSI_DEPTH, "%s: depth must be 5 or 6, got %d", who, depth);
+    DGRP_REQUIRE(C >= 1 && C <= DGRP_MAXC, "%s: bad C %d", who, C);
+    DGRP_REQUIRE(ncls >= 1 && ncls <= C, "%s: ncls must lie in 1..C (%d, C = %d)", who, ncls, C);
+    DGRP_REQUIRE(h_chunk_off && h_cls, "%s: NULL h_chunk_off or h_cls", who);
     for (int k = 0; k <= ncls; ++k) h_chunk_off[k] = 0;
-    DGRP_REQUIRE(nrec >= 0 && nrec < (1ll << 31), "dgrp_track_index_batch: bad nrec %lld", (long long)nrec);
+    DGRP_REQUIRE(nrec >= 0 && nrec < (1ll << 31), "%s: bad nrec %lld", who, (long long)nrec);
     for (int k = 0; k < ncls; ++k)
-        DGRP_REQUIRE(h_cls[k] >= 0 && h_cls[k] < C, "dgrp_track_index_batch: class %d is not in 0..%d", h_cls[k], C - 1);
-    DGRP_REQUIRE(digits >= 1 && digits <= 4, "dgrp_track_index_batch: digits must lie in 1..4, got %d", digits);
-    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: bad bin %lld", (long long)bin);
-    DGRP_REQUIRE(chunk_cap >= 0 && linear_cap >= 0, "dgrp_track_index_batch: bad chunk_cap/linear_cap (%lld, %lld)", (long long)chunk_cap,
+        DGRP_REQUIRE(h_cls[k] >= 0 && h_cls[k] < C, "%s: class %d is not in 0..%d", who, h_cls[k], C - 1);
+    DGRP_REQUIRE(digits >= 1 && digits <= 4, "%s: digits must lie in 1..4, got %d", who, digits);
+    DGRP_REQUIRE(bin >= 1 && bin <= TRACK_MAX_EXTENT, "%s: bad bin %lld", who, (long long)bin);
+    DGRP_REQUIRE(chunk_cap >= 0 && linear_cap >= 0, "%s: bad chunk_cap/linear_cap (%lld, %lld)", who, (long long)chunk_cap,
                  (long long)linear_cap);
     if (nrec == 0) return DGRP_OK;
-    DGRP_REQUIRE(h_row0 && h_n && h_startpos && h_name_off, "dgrp_track_index_batch: NULL host table");
-    DGRP_REQUIRE(h_name_off[0] >= 0, "dgrp_track_index_batch: record 0: bad name offset %lld", (long long)h_name_off[0]);
+    DGRP_REQUIRE(h_row0 && h_n && h_startpos && h_name_off, "%s: NULL host table", who);
+    DGRP_REQUIRE(h_name_off[0] >= 0, "%s: record 0: bad name offset %lld", who, (long long)h_name_off[0]);
     std::vector<int64_t> wpref((size_t)nrec + 1, 0);                       // windows in front of every record
     for (int64_t r = 0; r < nrec; ++r) {
-        DGRP_REQUIRE(h_n[r] >= 1 && h_n[r] <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: record %lld: bad n %lld", (long long)r,
+        DGRP_REQUIRE(h_n[r] >= 1 && h_n[r] <= TRACK_MAX_EXTENT, "%s: record %lld: bad n %lld", who, (long long)r,
                      (long long)h_n[r]);
-        DGRP_REQUIRE(h_startpos[r] >= 0 && h_startpos[r] <= TRACK_MAX_EXTENT, "dgrp_track_index_batch: record %lld: bad offset %lld",
+        DGRP_REQUIRE(h_startpos[r] >= 0 && h_startpos[r] <= TRACK_MAX_EXTENT, "%s: record %lld: bad offset %lld", who,
                      (long long)r, (long long)h_startpos[r]);
-        DGRP_REQUIRE(h_startpos[r] + h_n[r] <= TABIX_MAX_END,
-                     "dgrp_track_index_batch: record %lld ends at %lld, above 2^29 = 536870912, the largest coordinate of a tabix index",
-                     (long long)r, (long long)(h_startpos[r] + h_n[r]));
-        DGRP_REQUIRE(h_row0[r] >= 0, "dgrp_track_index_batch: record %lld: bad first row %lld", (long long)r, (long long)h_row0[r]);
-        DGRP_REQUIRE(h_name_off[r + 1] >= h_name_off[r], "dgrp_track_index_batch: record %lld: descending name offsets (%lld, %lld)",
+        if (csi) {
+            DGRP_REQUIRE(h_startpos[r] + h_n[r] <= tabix_max_end(depth),
+                         "%s: record %lld ends at %lld, above 2^%d = %lld, the largest coordinate of a CSI index of depth %d", who,
+                         (long long)r, (long long)(h_startpos[r] + h_n[r]), TABIX_MIN_SHIFT + 3 * depth, (long long)tabix_max_end(depth),
+                         depth);
+        } else {
+            DGRP_REQUIRE(h_startpos[r] + h_n[r] <= TABIX_MAX_END,
+                         "%s: record %lld ends at %lld, above 2^29 = 536870912, the largest coordinate of a tabix index", who,
+                         (long long)r, (long long)(h_startpos[r] + h_n[r]));
+        }
+        DGRP_REQUIRE(h_row0[r] >= 0, "%s: record %lld: bad first row %lld", who, (long long)r, (long long)h_row0[r]);
+        DGRP_REQUIRE(h_name_off[r + 1] >= h_name_off[r], "%s: record %lld: descending name offsets (%lld, %lld)", who,
                      (long long)r, (long long)h_name_off[r], (long long)h_name_off[r + 1]);
         wpref[(size_t)r + 1] = wpref[(size_t)r] + ((h_startpos[r] + h_n[r] - 1) >> TABIX_MIN_SHIFT) + 1;
     }
     const int64_t names_bytes = h_name_off[nrec], W = wpref[(size_t)nrec];
-    DGRP_REQUIRE(linear_cap >= W * ncls, "dgrp_track_index_batch: linear_cap %lld < %lld windows of %d classes", (long long)linear_cap,
+    DGRP_REQUIRE(linear_cap >= W * ncls, "%s: linear_cap %lld < %lld windows of %d classes", who, (long long)linear_cap,
                  (long long)(W * ncls), ncls);
     DGRP_REQUIRE((names || names_bytes == 0) && (d_chunks || chunk_cap == 0) && d_linear && d_probs && d_work,
-                 "dgrp_track_index_batch: NULL pointer");
+                 "%s: NULL pointer", who);
     ix_layout l;
-    DGRP_REQUIRE(ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, &l), "dgrp_track_index_batch: too many bins in one call");
+    DGRP_REQUIRE(ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, depth, &l), "%s: too many bins in one call", who);
     if (work_bytes < l.bytes) {
-        dgrp_set_error("dgrp_track_index_batch: workspace %lld < %lld bytes", (long long)work_bytes, (long long)l.bytes);
+        dgrp_set_error("%s: workspace %lld < %lld bytes", who, (long long)work_bytes, (long long)l.bytes);
         return DGRP_ENOMEM;
     }
     hipStream_t stream = (hipStream_t)stream_;
@@ -781,12 +784,12 @@ DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec
     if (rc != DGRP_OK) return rc;
     const dim3 grid((unsigned)D.ntiles), block(256);
     hipLaunchKernelGGL(ix_tile_kernel<0>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
-                       cbounds, d_chunks, d_linear);
+                       cbounds, d_chunks, d_linear, depth);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(ix_carry_kernel, dim3((unsigned)ncls), block, 0, stream, state, D.tpc);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(ix_tile_kernel<1>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
-                       cbounds, d_chunks, d_linear);
+                       cbounds, d_chunks, d_linear, depth);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), block, 0, stream, tilechunks, D.ntiles, cgrand);
     DGRP_LAUNCH_CHECK();
@@ -799,10 +802,44 @@ DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec
     if (h_chunk_off[ncls] > chunk_cap) return DGRP_OK;                      // (too small: the caller retries with room for all of them)
     DGRP_HIP(hipMemsetAsync(d_linear, 0xff, (size_t)(W * ncls) * 8, stream));          // -1: no line ends behind this window
     hipLaunchKernelGGL(ix_tile_kernel<2>, grid, block, 0, stream, D.q, D.recs, D.pref, d_wpref, D.G, W, D.tiles, D.bounds, state, tilechunks,
-                       cbounds, d_chunks, d_linear);
+                       cbounds, d_chunks, d_linear, depth);
     DGRP_LAUNCH_CHECK();
     hipLaunchKernelGGL(ix_ends_kernel, dim3(1), dim3(128), 0, stream, cbounds, D.bounds, ncls, d_chunks);
     DGRP_LAUNCH_CHECK();
     DGRP_HIP(hipStreamSynchronize(stream));
     return DGRP_OK;
+}
+
+DGRP_EXPORT int64_t dgrp_track_index_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                                     int64_t names_bytes)
+{
+    ix_layout l;
+    return ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, TABIX_DEPTH, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                       const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls,
+                                       int ncls, int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap,
+                                       int64_t *h_chunk_off, int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes,
+                                       void *stream_)
+{
+    return ix_entry("dgrp_track_index_batch", TABIX_DEPTH, d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits,
+                    bin, d_chunks, chunk_cap, h_chunk_off, d_linear, linear_cap, d_work, work_bytes, stream_, false);
+}
+
+DGRP_EXPORT int64_t dgrp_track_csi_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                                   int64_t names_bytes, int depth)
+{
+    ix_layout l;
+    return ix_carve(nrec, h_n, h_startpos, bin, ncls, names_bytes, depth, &l) ? l.bytes : 0;
+}
+
+DGRP_EXPORT int dgrp_track_csi_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                                     const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls,
+                                     int ncls, int digits, int64_t bin, int depth, dgrp_track_chunk *d_chunks, int64_t chunk_cap,
+                                     int64_t *h_chunk_off, int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes,
+                                     void *stream_)
+{
+    return ix_entry("dgrp_track_csi_batch", depth, d_probs, C, nrec, h_row0, h_n, h_startpos, names, h_name_off, h_cls, ncls, digits, bin,
+                    d_chunks, chunk_cap, h_chunk_off, d_linear, linear_cap, d_work, work_bytes, stream_, true);
 }

@@ -114,12 +114,13 @@ def reference_lines(names: Sequence, by_contig: bool, rows, scores, min_score: i
 
 
 def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_score: int, rec_end: Sequence[int],
-                          class_names: Optional[Sequence] = None, id0: int = 0):
-    """bed.reference_index_parts for the text `reference_lines` gives for the same arguments: what dgrp_gff_index_batch states.
+                          class_names: Optional[Sequence] = None, id0: int = 0, depth: int = 5):
+    """bed.reference_index_parts for the text `reference_lines` gives for the same arguments: what dgrp_gff_index_batch states
+    (with another depth: dgrp_gff_csi_batch).
     The intervals are the rows' [start, end); only the line lengths differ from the BED's."""
-    from .tabix import CHUNK_DTYPE, MIN_SHIFT, reg2bin, window_prefix
+    from .tabix import CHUNK_DTYPE, MIN_SHIFT, csi_reg2bin, window_prefix
     nrec = len(rec_end)
-    wpref = window_prefix(rec_end)
+    wpref = window_prefix(rec_end, depth)
     linear = np.full(int(wpref[-1]), -1, np.int64)
     filled = [0] * nrec
     last_end = np.zeros(nrec, np.int64)
@@ -131,7 +132,7 @@ def reference_index_parts(names: Sequence, by_contig: bool, rows, scores, min_sc
         done += 1
         r = int(rows[k]["contig"]) if by_contig else 0
         start, end = int(rows[k]["start"]), int(rows[k]["end"])
-        b = reg2bin(start, end)
+        b = csi_reg2bin(start, end, depth)
         if chunks and chunks[-1][2] == r and chunks[-1][3] == b:
             chunks[-1][1] = u + len(line)
         else:

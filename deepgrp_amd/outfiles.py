@@ -1,7 +1,7 @@
 """Staged output files, the layer under `predict --track_dir` and `--bed_dir` (tracks.TrackFiles, bed.BedFiles): a file is written
 under a temporary name next to its final one and renamed when its input is done (`StagedFile`); a BGZF file takes the members of
-every write and, where a tabix index was asked for, builds `<file>.tbi` beside it (`BgzfSink`); `StagedOutputs` is what the files
-of one input share: the rule on record names, one warning when the input cannot be indexed, and a commit that leaves no temporary
+every write and, where a tabix index was asked for, builds `<file>.tbi` or `<file>.csi` beside it (`BgzfSink`); `StagedOutputs`
+is what the files of one input share: the rule on record names, one warning when the input cannot be indexed, and a commit that leaves no temporary
 file behind when it fails.  The outputs that are written when their input is done (--mask_dir, --seq_dir, --summary_dir) share
 `RowsOutput` and its handle `AtCommit`; the plans of the outputs share `plan_inputs`, what they refuse of their inputs, and
 `class_list`, the type of their label flags.  The reports of `evaluate` share `plan_prefix`, the refusals of their `--<report>
@@ -48,12 +48,17 @@ class BgzfSink:
     """One BGZF file from the members of its writes.  With `index`, `builder` (a tabix.IndexBuilder, until someone sets it to None)
     takes every write at the file offset it goes to.  `finish` puts the EOF member behind the members and stages the `.tbi`;
     `commit` renames the file, then its `.tbi` -- or, the index dropped, removes a `.tbi` an earlier run left.  Without `index` a
-    `.tbi` beside the file is not this run's to touch.  `preset`: the index's preset where it is not tabix.PRESET_BED."""
+    `.tbi` beside the file is not this run's to touch.  `preset`: the index's preset where it is not tabix.PRESET_BED.
+    `fmt` "csi": the index is `<file>.csi` (tabix.CSI_DEPTH levels), staged, committed and aborted as the `.tbi` is.  With `index`,
+    `commit` also removes the other format's index of this file where one lies: it describes an earlier run's bytes, and a reader
+    looks for `.csi` before `.tbi`."""
 
-    def __init__(self, final: str, index: bool = False, preset=tabix.PRESET_BED):
-        self.index_wanted, self.builder = index, tabix.IndexBuilder(preset) if index else None
+    def __init__(self, final: str, index: bool = False, preset=tabix.PRESET_BED, fmt: str = "tbi"):
+        self.fmt = fmt
+        depth = tabix.CSI_DEPTH if fmt == "csi" else 5
+        self.index_wanted, self.builder = index, tabix.IndexBuilder(preset, fmt, depth) if index else None
         self.off = 0                                    # bytes of members written
-        self.tbi: Optional[StagedFile] = None
+        self.tbi: Optional[StagedFile] = None           # the staged index, of either format
         self.data = StagedFile(final)
 
     def append(self, members: bytes, names: Sequence[bytes], chunks, linear, wpref, last_end=None) -> None:
@@ -68,7 +73,7 @@ class BgzfSink:
         self.data.fh.write(BGZF_EOF)
         self.data.finish()
         if self.builder is not None:
-            self.tbi = StagedFile(self.data.final + ".tbi")
+            self.tbi = StagedFile(self.data.final + "." + self.fmt)
             self.tbi.fh.write(tabix.index_file(self.builder.payload()))
             self.tbi.finish()
 
@@ -76,8 +81,11 @@ class BgzfSink:
         self.data.commit()
         if self.tbi is not None:
             self.tbi.commit()
-        elif self.index_wanted and os.path.exists(self.data.final + ".tbi"):
-            os.remove(self.data.final + ".tbi")
+        elif self.index_wanted and os.path.exists(self.data.final + "." + self.fmt):
+            os.remove(self.data.final + "." + self.fmt)
+        other = self.data.final + (".tbi" if self.fmt == "csi" else ".csi")
+        if self.index_wanted and os.path.exists(other):
+            os.remove(other)
 
     def abort(self) -> None:
         self.data.abort()

@@ -559,20 +559,25 @@ class ContigPipeline:
         return _with_room(launch, cap)[:int(off[ncls])], off
 
     def track_index_batch_device(self, d_probs: torch.Tensor, row0, lengths, startposes, names, classes, digits: int = 2,
-                                 bin: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+                                 bin: int = 1, depth: int = 5) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """The tabix index of the text track_text_batch_device gives for the same arguments, in text offsets (one
         dgrp_track_index_batch call, read back once): -> (chunks, chunk_off [len(classes) + 1], linear [len(classes), W], wpref
         [records + 1]).  chunks (tabix.CHUNK_DTYPE) is class-major, class classes[k] at [chunk_off[k], chunk_off[k + 1]), offsets
         inside that class's slice of the text; record r of class k has its windows at linear[k, wpref[r]:wpref[r + 1]], -1 where
-        none of its lines ends behind the window.  A record that ends above 2^29 raises tabix.IndexRefused."""
+        none of its lines ends behind the window.  A record that ends above 2^29 raises tabix.IndexRefused.  depth 6: the bins of
+        a CSI index of that depth (one dgrp_track_csi_batch call), records up to 2^32."""
         from .tabix import CHUNK_DTYPE, window_prefix
         L = lib()
         r0, ln, sp, cl = ContigPipeline._track_tables(d_probs, "track_index_batch_device", row0, lengths, startposes, classes)
         c, nrec, ncls, dev = int(d_probs.shape[1]), len(ln), len(cl), d_probs.device
-        wpref = window_prefix(sp + ln)
+        depth = int(depth)
+        wpref = window_prefix(sp + ln, depth)
         blob, noff = name_blob(names)[1:]
         nwin = int(wpref[-1])
-        wb = L.dgrp_track_index_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
+        if depth == 5:
+            wb = L.dgrp_track_index_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob))
+        else:
+            wb = L.dgrp_track_csi_workspace_bytes(nrec, ln.ctypes.data, sp.ctypes.data, int(bin), ncls, len(blob), depth)
         if wb <= 0:
             raise ValueError(f"track_index_batch_device: bad record lengths, start positions, bin {bin} or class count {ncls}")
         work = torch.empty(wb, dtype=torch.uint8, device=dev)
@@ -583,9 +588,16 @@ class ContigPipeline:
 
         def launch(cap):
             chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            check(L.dgrp_track_index_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob, noff.ctypes.data,
-                                           cl.ctypes.data, ncls, int(digits), int(bin), _ptr(chunks), cap, off.ctypes.data, _ptr(linear),
-                                           ncls * nwin, _ptr(work), wb, stream_ptr()), "dgrp_track_index_batch")
+            if depth == 5:
+                check(L.dgrp_track_index_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob,
+                                               noff.ctypes.data, cl.ctypes.data, ncls, int(digits), int(bin), _ptr(chunks), cap,
+                                               off.ctypes.data, _ptr(linear), ncls * nwin, _ptr(work), wb, stream_ptr()),
+                      "dgrp_track_index_batch")
+            else:
+                check(L.dgrp_track_csi_batch(_ptr(d_probs), c, nrec, r0.ctypes.data, ln.ctypes.data, sp.ctypes.data, blob,
+                                             noff.ctypes.data, cl.ctypes.data, ncls, int(digits), int(bin), depth, _ptr(chunks), cap,
+                                             off.ctypes.data, _ptr(linear), ncls * nwin, _ptr(work), wb, stream_ptr()),
+                      "dgrp_track_csi_batch")
             return chunks, (int(off[ncls]),)
         host = _with_room(launch, cap)[:int(off[ncls]) * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, off, linear[:ncls * nwin].cpu().numpy().reshape(ncls, nwin), wpref
@@ -764,17 +776,19 @@ class ContigPipeline:
         return _with_room(launch, cap)[:got.value]
 
     @staticmethod
-    def bed_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end):
+    def bed_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, depth: int = 5):
         """The tabix pieces of the text bed_text_batch gives for the same arguments, in text offsets (one dgrp_bed_index_batch call,
         read back once): -> (chunks tabix.CHUNK_DTYPE, linear int64 [windows], wpref int64 [records + 1], last_end int64 [records]);
         record r (a row's contig with by_contig, else 0) ends at rec_end[r] and has its windows at linear[wpref[r]:wpref[r + 1]].
-        What bed.reference_index_parts states.  A record that ends above 2^29 raises tabix.IndexRefused."""
+        What bed.reference_index_parts states.  A record that ends above 2^29 raises tabix.IndexRefused.  depth 6: the bins of a
+        CSI index of that depth (one dgrp_bed_csi_batch call), records up to 2^32."""
         from .tabix import CHUNK_DTYPE, window_prefix
         L = lib()
         nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
         ends = np.ascontiguousarray(rec_end, np.int64)
         nrec = len(ends)
-        wpref = window_prefix(ends)
+        depth = int(depth)
+        wpref = window_prefix(ends, depth)
         raw, blob, off = name_blob(names)
         nwin = int(wpref[-1])
         wb = int(L.dgrp_bed_index_workspace_bytes(nrows, len(raw), len(blob), nrec))
@@ -788,9 +802,14 @@ class ContigPipeline:
 
         def launch(cap):
             chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            check(L.dgrp_bed_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows,
-                                         int(min_score), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got), _ptr(linear), nwin,
-                                         _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_bed_index_batch")
+            if depth == 5:
+                check(L.dgrp_bed_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows,
+                                             int(min_score), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got), _ptr(linear), nwin,
+                                             _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_bed_index_batch")
+            else:
+                check(L.dgrp_bed_csi_batch(blob, off.ctypes.data, len(raw), int(by_contig), _ptr(d_rows), _ptr(d_scores), nrows,
+                                           int(min_score), nrec, ends.ctypes.data, depth, _ptr(chunks), cap, C.byref(got), _ptr(linear),
+                                           nwin, _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_bed_csi_batch")
             return chunks, (int(got.value),)
         host = _with_room(launch, cap)[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
@@ -811,10 +830,12 @@ class ContigPipeline:
         from .bed import BedWrite
         from .gz import bgzf_members_device
         from .tabix import end_refusal
+        from .tracks import index_depth
         raw = name_blob(names)[0]
         r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "bed_write", row0, lengths, startposes)
         ends = sp + ln
-        refused = end_refusal(ends, raw) if plan.index else None
+        depth = index_depth(getattr(plan, "index_format", "tbi"))
+        refused = end_refusal(ends, raw, depth) if plan.index else None
         rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
         ro = np.ascontiguousarray(row_off, np.int64)
         if len(rows) == 0:
@@ -825,7 +846,7 @@ class ContigPipeline:
         d_text = self.bed_text_batch(raw, by_contig, d_rows, d_scores, plan.min_score)
         parts = (None,) * 4
         if plan.index and refused is None and int(d_text.numel()):
-            parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends)
+            parts = self.bed_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends, depth)
         del d_probs, d_rows, d_scores
         return BedWrite(bgzf_members_device(d_text, plan.gzip_level), raw, refused, *parts)
 
@@ -869,15 +890,16 @@ class ContigPipeline:
 
     @staticmethod
     def gff_index_batch(names, by_contig: bool, d_rows: torch.Tensor, d_scores: torch.Tensor, min_score: int, rec_end, class_names=None,
-                        id0: int = 0):
-        """bed_index_batch for the text gff_text_batch gives for the same arguments (one dgrp_gff_index_batch call): what
-        gff.reference_index_parts states."""
+                        id0: int = 0, depth: int = 5):
+        """bed_index_batch for the text gff_text_batch gives for the same arguments (one dgrp_gff_index_batch call, at depth 6 one
+        dgrp_gff_csi_batch call): what gff.reference_index_parts states."""
         from .tabix import CHUNK_DTYPE, window_prefix
         L = lib()
         nrows, dev = int(d_rows.numel()) // SEGMENT_DTYPE.itemsize, d_rows.device
         ends = np.ascontiguousarray(rec_end, np.int64)
         nrec = len(ends)
-        wpref = window_prefix(ends)
+        depth = int(depth)
+        wpref = window_prefix(ends, depth)
         raw, blob, off, cblob, coff, nc, _keep = ContigPipeline._gff_tables(names, class_names)
         nwin = int(wpref[-1])
         wb = int(L.dgrp_gff_index_workspace_bytes(nrows, len(raw), len(blob), nc, len(cblob or b""), nrec))
@@ -891,9 +913,15 @@ class ContigPipeline:
 
         def launch(cap):
             chunks = torch.empty(max(cap, 1) * CHUNK_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            check(L.dgrp_gff_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff, nc, _ptr(d_rows), _ptr(d_scores),
-                                         nrows, int(min_score), int(id0), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got),
-                                         _ptr(linear), nwin, _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_gff_index_batch")
+            if depth == 5:
+                check(L.dgrp_gff_index_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff, nc, _ptr(d_rows), _ptr(d_scores),
+                                             nrows, int(min_score), int(id0), nrec, ends.ctypes.data, _ptr(chunks), cap, C.byref(got),
+                                             _ptr(linear), nwin, _ptr(last), _ptr(work), wb, stream_ptr()), "dgrp_gff_index_batch")
+            else:
+                check(L.dgrp_gff_csi_batch(blob, off.ctypes.data, len(raw), int(by_contig), cblob, coff, nc, _ptr(d_rows), _ptr(d_scores),
+                                           nrows, int(min_score), int(id0), nrec, ends.ctypes.data, depth, _ptr(chunks), cap,
+                                           C.byref(got), _ptr(linear), nwin, _ptr(last), _ptr(work), wb, stream_ptr()),
+                      "dgrp_gff_csi_batch")
             return chunks, (int(got.value),)
         host = _with_room(launch, cap)[:got.value * CHUNK_DTYPE.itemsize].cpu().numpy().view(CHUNK_DTYPE)
         return host, linear[:nwin].cpu().numpy(), wpref, last[:nrec].cpu().numpy()
@@ -904,10 +932,12 @@ class ContigPipeline:
         write with the lines in front of it (the ID ordinals run through the file), on the stream that is current then."""
         from .gff import GffText, GffWrite
         from .tabix import end_refusal
+        from .tracks import index_depth
         raw = name_blob(names)[0]
         r0, ln, sp, _cl = ContigPipeline._track_tables(d_probs, "gff_write", row0, lengths, startposes)
         ends = sp + ln
-        refused = end_refusal(ends, raw) if plan.index else None
+        depth = index_depth(getattr(plan, "index_format", "tbi"))
+        refused = end_refusal(ends, raw, depth) if plan.index else None
         rows = np.ascontiguousarray(rows, dtype=SEGMENT_DTYPE)
         ro = np.ascontiguousarray(row_off, np.int64)
         if len(rows) == 0:
@@ -924,7 +954,7 @@ class ContigPipeline:
             d_text, lines = self.gff_text_batch(raw, by_contig, d_rows, d_scores, plan.min_score, plan.class_names, id0)
             parts = (None,) * 4
             if plan.index and refused is None and int(d_text.numel()):
-                parts = self.gff_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends, plan.class_names, id0)
+                parts = self.gff_index_batch(raw, by_contig, d_rows, d_scores, plan.min_score, ends, plan.class_names, id0, depth)
             if plan.gzip_level is None:
                 return GffText(d_text.cpu().numpy().tobytes(), lines)
             return GffText(bgzf_members_device(d_text, plan.gzip_level), lines, *parts)

@@ -44,6 +44,7 @@ class TrackSpec(NamedTuple):
     gzip_level: Optional[int] = None                # None: plain text; else BGZF members at this level
     index: bool = False                             # --track_index: a tabix index beside every BGZF track
     bigwig: bool = False                            # --track_bigwig: bigWig files (zlib streams at gzip_level) instead of bedGraph
+    index_format: str = "tbi"                       # --index_format: "csi" for <track>.gz.csi (tabix.CSI_DEPTH levels, up to 2^32)
 
 
 class TrackPlan(NamedTuple):
@@ -55,6 +56,7 @@ class TrackPlan(NamedTuple):
     gzip_level: Optional[int] = None                # --track_gzip: the level (None: plain bedGraph)
     index: bool = False                             # --track_index
     bigwig: bool = False                            # --track_bigwig (gzip_level is then the level of its zlib streams)
+    index_format: str = "tbi"                       # --index_format
 
 
 def input_basename(filename: str) -> str:
@@ -89,6 +91,8 @@ def check_gzip_flags(args) -> None:
             sys.exit("--track_bigwig writes bigWig files instead of bedGraph: it does not go with --track_gzip or --track_index")
     if getattr(args, "track_index", False) and not getattr(args, "track_gzip", False):
         sys.exit("--track_index needs --track_gzip (a tabix index belongs to a BGZF file)")
+    if getattr(args, "index_format", None) is not None and not (getattr(args, "track_index", False) or getattr(args, "bed_index", False)):
+        sys.exit("--index_format needs --track_index or --bed_index (it chooses the format of their index)")
     if getattr(args, "gzip_level", None) is not None:
         if not (getattr(args, "mask_gzip", False) or getattr(args, "track_gzip", False) or getattr(args, "track_bigwig", False)
                 or getattr(args, "bed_gzip", False) or getattr(args, "bed_bigbed", False) or getattr(args, "seq_gzip", False)):
@@ -110,6 +114,11 @@ def add_options(parser) -> None:
                         help="(addition) with --track_gzip: write the tabix index <track>.gz.tbi of every track, built on the GPU "
                              "beside the text (records must end at or below 2^29 and names must not reappear after another name; "
                              "otherwise a warning and no index)")
+    parser.add_argument("--index_format", choices=("tbi", "csi"), default=s,
+                        help="(addition) with --track_index or --bed_index: the format of the index.  tbi (the default): <file>.gz.tbi, "
+                             "records up to 2^29 bases.  csi: <file>.gz.csi, a CSI index of depth 6 with the same chunks and a "
+                             "per-bin offset in place of the linear index, records up to 2^32 bases (the format tabix -C writes); "
+                             "an index of the other format beside the file is removed")
     parser.add_argument("--track_bigwig", action="store_true", default=s,
                         help="(addition) with --track_dir: write every track as bigWig, DIR/<basename>.class<c>.bw, instead of bedGraph: "
                              "the same items in binary sections with zoom levels, built and deflated on the GPU (--gzip_level, 1 unless "
@@ -125,7 +134,20 @@ def add_options(parser) -> None:
                              "(default: 1)")
 
 
+def index_format(args) -> str:
+    """--index_format, "tbi" where it is not given."""
+    return getattr(args, "index_format", None) or "tbi"
+
+
+def index_depth(fmt: str) -> int:
+    """The levels below the root of the index's binning scheme: 5 of a `.tbi`, tabix.CSI_DEPTH of a `.csi`."""
+    from .tabix import CSI_DEPTH
+    return CSI_DEPTH if fmt == "csi" else 5
+
+
 def refuse_on_evaluate(args) -> None:
+    if getattr(args, "index_format", None) is not None:
+        sys.exit("--index_format belongs to predict, not evaluate")
     if (getattr(args, "track_dir", None) is not None or getattr(args, "track_gzip", False) or getattr(args, "track_index", False)
             or getattr(args, "track_bigwig", False)):
         sys.exit("--track_dir belongs to predict, not evaluate")
@@ -159,7 +181,7 @@ def plan(args) -> Optional[TrackPlan]:
     bigwig = bool(getattr(args, "track_bigwig", False))
     level = gzip_level(args, 1) if getattr(args, "track_gzip", False) or bigwig else None
     return TrackPlan(tdir, tuple(classes) if classes is not None else None, digits, width, bases, level,
-                     bool(getattr(args, "track_index", False)), bigwig)
+                     bool(getattr(args, "track_index", False)), bigwig, index_format(args))
 
 
 def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
@@ -168,7 +190,7 @@ def resolve(p: TrackPlan, nclasses: int) -> TrackSpec:
     bad = [c for c in classes if not 0 <= c < nclasses]
     if bad:
         sys.exit(f"--track_classes: label {bad[0]} is not a class of this model (labels 0..{nclasses - 1})")
-    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index, p.bigwig)
+    return TrackSpec(tuple(dict.fromkeys(classes)), p.digits, p.bin, p.gzip_level, p.index, p.bigwig, p.index_format)
 
 
 def from_plan(p: TrackPlan, classes: int) -> "Tracks":
@@ -278,10 +300,12 @@ def write_index(pipe, d_probs, row0, lengths, startposes, names, spec: TrackSpec
     from ._lib import name_blob
     from .tabix import end_refusal
     raw = name_blob(names)[0]
-    refused = end_refusal([int(sp) + int(n) for sp, n in zip(startposes, lengths)], raw)
+    depth = index_depth(spec.index_format)
+    refused = end_refusal([int(sp) + int(n) for sp, n in zip(startposes, lengths)], raw, depth)
     if refused is not None:
         return WriteIndex(raw, refused)
-    return WriteIndex(raw, None, *pipe.track_index_batch_device(d_probs, row0, lengths, startposes, raw, spec.classes, spec.digits, spec.bin))
+    return WriteIndex(raw, None, *pipe.track_index_batch_device(d_probs, row0, lengths, startposes, raw, spec.classes, spec.digits,
+                                                                spec.bin, depth))
 
 
 def record_texts(pipe, merged, startpos: int, name, spec: TrackSpec, chrom: int = 0) -> List[bytes]:
@@ -323,8 +347,8 @@ class _BigWigFile(StagedFile):
 
 class TrackFiles(StagedOutputs):
     """The track files of one input: temporary files in the directory, renamed by `commit`, removed by `abort` (outfiles.py).  With
-    spec.gzip_level `write` takes BGZF members, to an outfiles.BgzfSink per class, which with spec.index builds `<track>.gz.tbi`.
-    An input whose records cannot be indexed (WriteIndex.refused, an empty name, a name that comes back: one name_order for all
+    spec.gzip_level `write` takes BGZF members, to an outfiles.BgzfSink per class, which with spec.index builds `<track>.gz.tbi`
+    (`<track>.gz.csi` with spec.index_format "csi").  An input whose records cannot be indexed (WriteIndex.refused, an empty name, a name that comes back: one name_order for all
     classes) gets one warning and no index; its tracks are what they are without the flag.  With spec.bigwig the files are `.bw`,
     every class has a bigwig.BigWigBuilder on its temporary file, `write` takes TrackTexts with a BigWigWrite, and an input a
     bigWig cannot hold (an empty name, a name two records share, a record that ends above 2^32 - 1) gets one warning and no `.bw`
@@ -337,7 +361,7 @@ class TrackFiles(StagedOutputs):
         self.final = [track_path(p.directory, p.bases[filename], c, self.gzip, self.bigwig) for c in spec.classes]
         self.bw_refused = None
         super().__init__(_LOG, filename, "--track_index", self.gzip and spec.index,
-                         (_BigWigFile(path, spec.digits, spec.bin) if self.bigwig else BgzfSink(path, spec.index) if self.gzip
+                         (_BigWigFile(path, spec.digits, spec.bin) if self.bigwig else BgzfSink(path, spec.index, fmt=spec.index_format) if self.gzip
                           else StagedFile(path) for path in self.final))
 
     def _bigwig(self, texts: Sequence[bytes]) -> None:

@@ -473,6 +473,20 @@ int dgrp_track_index_batch(const float *d_probs, int C, int64_t nrec, const int6
                            int digits, int64_t bin, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_chunk_off,
                            int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes, void *stream);
 
+/* dgrp_track_csi_batch (predict --track_index --index_format csi): dgrp_track_index_batch with the depth of the binning scheme as an
+ * argument (deepgrp_amd/tabix.py states the CSI format).  depth is 5 or 6, anything else is DGRP_EINVAL on the host.  A line's bin
+ * is csi_reg2bin(start, end, depth): level l of 0..depth starts at bin ((1 << 3l) - 1) / 7 and has shift 14 + 3 (depth - l).  The
+ * record-end limit is 2^(14 + 3 depth), 2^32 at depth 6: a record that ends above it is refused with DGRP_EINVAL before any launch
+ * ("... the largest coordinate of a CSI index of depth D").  Everything else -- arguments, outputs, chunk rule, the 16 kb windows
+ * of d_linear and its rule, synchronisation count, workspace layout -- is dgrp_track_index_batch's, whose outputs these are bit for
+ * bit at depth 5; that entry is this code at depth 5.  A record near 2^32 has up to 2^18 windows per class in d_linear. */
+int64_t dgrp_track_csi_workspace_bytes(int64_t nrec, const int64_t *h_n, const int64_t *h_startpos, int64_t bin, int ncls,
+                                       int64_t names_bytes, int depth);
+int dgrp_track_csi_batch(const float *d_probs, int C, int64_t nrec, const int64_t *h_row0, const int64_t *h_n,
+                         const int64_t *h_startpos, const char *names, const int64_t *h_name_off, const int *h_cls, int ncls,
+                         int digits, int64_t bin, int depth, dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_chunk_off,
+                         int64_t *d_linear, int64_t linear_cap, void *d_work, int64_t work_bytes, void *stream);
+
 /* ---- bigWig tracks (predict --track_bigwig; deepgrp_amd/bigwig.py states the file format).  The ITEMS of a class are the lines of
  * the text above without the name: (start, end, q) of every maximal run of bins of equal q != 0 inside one record.  An item's value is
  * (float)((double)q / 10^digits), the float32 a reader gets from the text's decimal.
@@ -793,6 +807,26 @@ int dgrp_gff_index_batch(const char *names, const int64_t *name_off, int64_t nna
                          int64_t nrows, int min_score, int64_t id0, int64_t nrec, const int64_t *h_rec_end,
                          dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
                          int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
+
+/* dgrp_bed_csi_batch, dgrp_gff_csi_batch (predict --bed_index --index_format csi): dgrp_bed_index_batch and dgrp_gff_index_batch
+ * with the depth of the binning scheme as an argument behind h_rec_end (deepgrp_amd/tabix.py states the CSI format).  depth is 5 or
+ * 6, anything else is DGRP_EINVAL on the host.  A line's bin is csi_reg2bin(start, end, depth); h_rec_end[r] must lie in
+ * 1..2^(14 + 3 depth), 2^32 at depth 6, or the call is refused before any launch ("... the largest coordinate of a CSI index of
+ * depth D").  Arguments, outputs, chunk rule, running-maximum linear rule over 16 kb windows, refusals, the one synchronisation and
+ * the workspace (the _workspace_bytes twins give the .tbi entries' figures; 0 on another depth) are those entries'; at depth 5 the
+ * outputs are theirs bit for bit, and those entries are this code at depth 5. */
+int64_t dgrp_bed_csi_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t nrec, int depth);
+int dgrp_bed_csi_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const dgrp_segment *d_rows,
+                       const dgrp_row_score *d_scores, int64_t nrows, int min_score, int64_t nrec, const int64_t *h_rec_end, int depth,
+                       dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
+                       int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
+int64_t dgrp_gff_csi_workspace_bytes(int64_t nrows, int64_t nnames, int64_t names_bytes, int64_t ncnames, int64_t cnames_bytes,
+                                     int64_t nrec, int depth);
+int dgrp_gff_csi_batch(const char *names, const int64_t *name_off, int64_t nnames, int by_contig, const char *cnames,
+                       const int64_t *cname_off, int64_t ncnames, const dgrp_segment *d_rows, const dgrp_row_score *d_scores,
+                       int64_t nrows, int min_score, int64_t id0, int64_t nrec, const int64_t *h_rec_end, int depth,
+                       dgrp_track_chunk *d_chunks, int64_t chunk_cap, int64_t *h_nchunks, int64_t *d_linear, int64_t linear_cap,
+                       int64_t *d_rec_last, void *d_work, int64_t work_bytes, void *stream);
 
 /* ---- RepeatMasker listing (predict --bed_rmout; deepgrp_amd/rmout.py states the file format).  The rows and scores of
  * dgrp_bed_text_batch as the lines of a RepeatMasker `.out` file, one per emitted row (score >= min_score), in row order:
